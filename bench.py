@@ -22,7 +22,13 @@ The JSON line carries both halves of the metric: `value` = primary Mrays/s = ray
 frame / the traversal part of a step (max over ranks), `build_Mtri_s` = triangles / the build
 part of a step; `ms_per_step` is the whole step (build + trace), wall clock, max over ranks.
 
-`roofline` describes the dominant kernel (the packet traversal) against HBM, SURVEY 8(d)'s roofline for every stage:
+A plain run does only that: set-up, W warm-up steps, the K steps instrumented, the same K steps timed, the line.  `--full`
+adds every untimed extra, guard and baseline below (parity guards against a staged rebuild and the reference mode, the
+assembled-frame check for N > 1, trace variants, 4K, steps in flight, roofline with its counter child passes, sort
+micro-bench, CPU baseline, cfg5); `"full"` in the line says which kind of run printed it.  `--dump-outputs DIR` writes
+what the last timed step computed (the frame's hit records, a fixed sample of the rebuilt BVH) as DIR/<name>.npy.
+
+`roofline` (--full) describes the dominant kernel (the packet traversal) against HBM, SURVEY 8(d)'s roofline for every stage:
   achieved = the kernel's OWN algorithmic bytes per launch (64 B per node line + 64 B per triangle line fetched per
       64-ray packet + 16 B hit record per ray, from this run's visit counters) / its live HIP-event duration; peak 8 TB/s;
       frac = achieved / peak — a small number: the walk prunes and the scene it walks is cache-resident;
@@ -85,6 +91,12 @@ def parse():
     # --gpus N from a plain launch: the parent ends every rank and exits 124 when the whole run takes longer than this (a
     # collective library that never connects must not hold the caller until ITS timeout)
     ap.add_argument("--launch-deadline", type=float, default=900.0, metavar="SECONDS")
+    # a plain run sets up, warms up, times the K steps and prints the headline line; every other figure and check of the line
+    # (parity guards, trace variants, 4K, steps in flight, roofline, counter passes, sort micro-bench, CPU baseline, cfg5)
+    # runs only with --full, where the --no-* switches above still apply
+    ap.add_argument("--full", action="store_true", help="also run every untimed extra, guard and baseline after the timed steps")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (hit records + a fixed sample of the BVH arrays) as DIR/<name>.npy")
     return ap.parse_args()
 
 
@@ -367,6 +379,55 @@ def main():
     # N > 1: trace_ms contains the records' way to rank 0 (on rank 0: the wait for every rank's share); the traversal alone:
     # (from behind the wait for rank 0's "frame read" word to the end of this rank's own kernel: no cross-rank skew in it)
     own_trace_ms_max = reduce_max(float(np.mean([ctx.elapsed_ms(e[3], e[2]) for e in events]))) if gather is not None else trace_ms_max
+
+    if args.dump_outputs and rank == 0:
+        # before anything below touches the container or the frame: what the last timed step left there
+        dump_outputs(args.dump_outputs, drawer.container, gather.frame if gather is not None else hit_buf)
+
+    def finish(line):
+        for e in events + [(ev_start,)]:
+            for x in e:
+                ctx.destroy_event(x)
+        if gather is not None:
+            gather.close()
+        drawer.on_destroy()
+        ctx.close()
+        if dist is not None:
+            dist.barrier()
+            dist.destroy_process_group()
+        if line is not None:
+            print(json.dumps(line))
+
+    workload_text = (("cfg4: 16,000,000-triangle tiled bumpy torus (400x160 quads x 125 tiles, seed 2), sort "
+                      + (f"key-range sharded over {world} GPUs (RCCL digit-histogram all-reduce + one all-to-all), "
+                         if world > 1 else "on one GPU, ") + "1920x1080 primary rays; full LBVH rebuild + frame trace per step")
+                     if cfg4 else
+                     "cfg2: 1,000,000-triangle tiled bumpy torus (seed 2), 1920x1080 primary rays, "
+                     "camera (0,0,250) fov 60; full LBVH rebuild + frame trace per step")
+    if not args.full:
+        # the headline line alone: the same meaning of every field as with --full, nothing measured or checked beyond the steps
+        line = None
+        if rank == 0:
+            line = {
+                "metric": "LBVH build Mtri/s + primary Mrays/s at 1080p on 1M-tri synthetic mesh",
+                "value": round(W * H / (trace_ms_max * 1e-3) / 1e6, 2),
+                "unit": "Mrays/s",
+                "build_Mtri_s": round(n_tris / (build_ms_max * 1e-3) / 1e6, 2),
+                "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+                "ms_per_step": round(wall_ms, 4),
+                "ms_per_step_instrumented": round(wall_instrumented_ms, 4),
+                "build_ms": round(build_ms_max, 4), "trace_ms": round(trace_ms_max, 4),
+                "value_without_gather": round(W * H / (own_trace_ms_max * 1e-3) / 1e6, 2),
+                "trace_without_gather_ms": round(own_trace_ms_max, 4),
+                "frame_gather_transport": gather.mode if gather is not None else None,
+                "rccl_ranks": (dist.get_world_size() if dist is not None and args.backend == "nccl" else None),
+                "bench_version": 3, "full": False,
+                "higher_is_better": True, "scaling": "strong", "vs_baseline": None,
+                "dtype": "f32+u32", "data": "synthetic",
+                "config": {"workload": workload_text, "triangles": n_tris, "rays": W * H, "trace_mode": args.mode},
+            }
+        finish(line)
+        return
 
     # ---- the arrays the timed steps left behind, word for word against an independent chain (untimed) ------
     # The timed rebuild is ONE lbvh_build_scene call: two-level sort, three merged launches, the search-free tree kernel that
@@ -848,7 +909,7 @@ def main():
             # methodology marker: 2 = rounds 5+: defaults --steps 100 --warmup 10; value / build_ms / trace_ms from an
             # instrumented pass BEFORE the timed region, ms_per_step from the timed region (rounds 1-4: 20 / 3, one pass);
             # 3 = round 6: + the two parity guards above
-            "bench_version": 3,
+            "bench_version": 3, "full": True,
             "higher_is_better": True, "scaling": "strong", "vs_baseline": None,
             "scaling_note": "strong scaling of ONE 1080p frame: `value` = rays of the whole frame / the slowest rank's trace part — for N > 1 "
                             "that part ends with the whole frame in rank 0's buffer (`frame_gather`; `value_without_gather`: the traversal "
@@ -858,12 +919,7 @@ def main():
                             "(~0.4 us per step), not throughput: expect ~0.8 / 0.45 / 0.3 efficiency at 2 / 4 / 8 GPUs for `value` "
                             "(DESIGN.md sections 6 and 13.1, profiles/r4/n_shard_times_one_gpu.txt)",
             "dtype": "f32+u32", "data": "synthetic",
-            "config": {"workload": ("cfg4: 16,000,000-triangle tiled bumpy torus (400x160 quads x 125 tiles, seed 2), sort "
-                                    + (f"key-range sharded over {world} GPUs (RCCL digit-histogram all-reduce + one all-to-all), "
-                                       if world > 1 else "on one GPU, ") + "1920x1080 primary rays; full LBVH rebuild + frame trace per step")
-                       if cfg4 else
-                                   "cfg2: 1,000,000-triangle tiled bumpy torus (seed 2), 1920x1080 primary rays, "
-                                   "camera (0,0,250) fov 60; full LBVH rebuild + frame trace per step",
+            "config": {"workload": workload_text,
                        "triangles": n_tris, "rays": W * H, "trace_mode": args.mode,
                        "sharding": f"rays in interleaved groups of 8 tiles over {world} GPU(s) (one launch per GPU), BVH replicated, "
                                    "no collective in the traversal" + ("" if gather is None else
@@ -892,18 +948,34 @@ def main():
             out["value_4k"] = frame_4k["Mrays_s"]
         if in_flight is not None:
             out["steps_in_flight"] = in_flight
-    for e in events + [(ev_start,)]:
-        for x in e:
-            ctx.destroy_event(x)
-    if gather is not None:
-        gather.close()
-    drawer.on_destroy()
-    ctx.close()
-    if dist is not None:
-        dist.barrier()
-        dist.destroy_process_group()
-    if out is not None:
-        print(json.dumps(out))
+    finish(out)
+
+
+DUMP_SAMPLE = 1 << 16       # BVH entries kept by --dump-outputs (hit records: the whole frame)
+
+
+def dump_outputs(out_dir, container, frame):
+    """--dump-outputs: what a caller of the timed path receives after the last timed step, as float32 / float64 .npy files
+    (~50 MB at cfg2).  The frame's hit records whole (t, u, v float32; tri float64: every uint32 exactly, the miss word
+    included); of the rebuilt BVH a fixed sample of DUMP_SAMPLE entries (indices from a seeded generator, sorted, written
+    as bvh_sample_index): Morton keys and triangle indices after the sort, internal / leaf node words, node boxes."""
+    os.makedirs(out_dir, exist_ok=True)
+    hits = frame.get_data().copy()
+    n = container.triangles_length
+    idx = np.sort(np.random.default_rng(12345).choice(n - 1, size=min(DUMP_SAMPLE, n - 1), replace=False))
+    bvh = container.bvh_data.get_data()
+    arrays = {
+        "hit_t": hits["t"].astype(np.float32), "hit_tri": hits["tri"].astype(np.float64),
+        "hit_u": hits["u"].astype(np.float32), "hit_v": hits["v"].astype(np.float32),
+        "bvh_sample_index": idx.astype(np.float64),
+        "sorted_keys": container.keys.get_data()[idx].astype(np.float64),
+        "sorted_indices": container.triangle_index.get_data()[idx].astype(np.float64),
+        "internal_nodes": container.bvh_internal_node.get_data().view(np.uint32).reshape(-1, 6)[idx].astype(np.float64),
+        "leaf_nodes": container.bvh_leaf_node.get_data().view(np.uint32).reshape(-1, 2)[idx].astype(np.float64),
+        "bvh_min": bvh["min"][idx].astype(np.float32), "bvh_max": bvh["max"][idx].astype(np.float32),
+    }
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 def sort_microbench(ctx, log2n, copy_gbs, live):

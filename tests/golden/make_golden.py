@@ -18,6 +18,7 @@ Inputs:
                        64x64 primary rays, and the shaded RGBA16F image (Raytracing.compute:178-184).  The mesh spans
                        about +-0.7 units inside the +-125 Morton box, so nearly all Morton codes coincide: the fixture
                        that exercises DistributeKeys' duplicate handling and deep, degenerate trees.
+  reference_obj/       every OBJ mesh of Assets/_Assets, xz-compressed: the ingest tests' inputs (tests/test_scenes.py)
 Run from the repo root in the build container (needs /root/reference for the two asset fixtures):
     python tests/golden/make_golden.py
 """
@@ -60,6 +61,20 @@ def downsample4(rgb):
     return out
 
 
+def copy_obj_assets():
+    """Every OBJ mesh of the reference's asset folder, byte for byte, xz-compressed into reference_obj/<name>.obj.xz: the
+    data tests/test_scenes.py feeds the Python and the C++ ingest (the meshes are data; no other file of the folder is kept)"""
+    import lzma
+    out_dir = os.path.join(HERE, "reference_obj")
+    os.makedirs(out_dir, exist_ok=True)
+    for name in sorted(os.listdir(REF_ASSETS)):
+        if name.endswith(".obj"):
+            with open(os.path.join(REF_ASSETS, name), "rb") as src:
+                data = src.read()
+            with open(os.path.join(out_dir, name + ".xz"), "wb") as dst:
+                dst.write(lzma.compress(data, preset=9 | lzma.PRESET_EXTREME))
+
+
 def main():
     tris = scenes.random_triangles(4096, seed=1)
     cam = scenes.camera(64, 64, (0.0, 0.0, 300.0))
@@ -90,6 +105,7 @@ def main():
             res = [out["hit_t"][j, i], int(out["hit_tri"][j, i]), out["hit_u"][j, i], out["hit_v"][j, i]]
             img[j, i] = E.shade(res, vk[res[1]], tex)
     np.savez_compressed(os.path.join(HERE, "viking_room.npz"), triangles=vk, texture=tex, shaded=img.view(np.uint16), **out)
+    copy_obj_assets()
     for f in sorted(os.listdir(HERE)):
         print(f, os.path.getsize(os.path.join(HERE, f)))
 

@@ -282,7 +282,7 @@ def test_bench_two_ranks_end_every_step_with_one_whole_frame(transport):
     1080p) equals the one-GPU frame word for word and the reference mode's t bit for bit."""
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--backend", "gloo", "--device", "0", "--steps", "3",
-                        "--warmup", "1", "--gather", transport, "--no-sort-bench", "--no-cpu-baseline", "--no-dynamic", "--no-live-counters"],
+                        "--warmup", "1", "--gather", transport, "--full", "--no-sort-bench", "--no-cpu-baseline", "--no-dynamic", "--no-live-counters"],
                        capture_output=True, text=True, timeout=1500, env=env)
     assert r.returncode == 0, r.stderr[-3000:]
     line = json.loads(r.stdout.strip().splitlines()[-1])

@@ -52,25 +52,38 @@ def test_tiled_torus_is_deterministic_and_inside_the_morton_box():
         assert np.abs(a[f]).max() < 125.0
 
 
-def test_reference_assets_through_load_obj():
-    """the reference's own OBJ assets through the ingest.  /root/reference exists only in the build
-    container; the triangles it yields there are what tests/golden/{example_object3,viking_room}.npz hold (those files
-    carry the data to the GPU box, where the same triangles go through build -> trace -> shade)."""
+def _reference_objs(tmp_path):
+    """The reference's own OBJ meshes (tests/golden/reference_obj/, written by tests/golden/make_golden.py), unpacked into
+    tmp_path as the files the asset folder holds.  Returns {file name: path}."""
+    import lzma
+    import os
+    src = os.path.join(os.path.dirname(__file__), "golden", "reference_obj")
+    out = {}
+    for name in sorted(os.listdir(src)):
+        if name.endswith(".obj.xz"):
+            path = tmp_path / name[: -len(".xz")]
+            with open(os.path.join(src, name), "rb") as fh:
+                path.write_bytes(lzma.decompress(fh.read()))
+            out[path.name] = str(path)
+    assert len(out) == 7, sorted(out)
+    return out
+
+
+def test_reference_assets_through_load_obj(tmp_path):
+    """the reference's own OBJ assets through the ingest.  The triangles they yield are what
+    tests/golden/{example_object3,viking_room}.npz hold (the GPU tests take them from there through build -> trace -> shade)."""
     import os
     import numpy as np
     from unitysimpleraytracing_amd import layouts as L
-    assets = "/root/reference/Assets/_Assets"
-    if not os.path.isdir(assets):
-        import pytest
-        pytest.skip("no /root/reference on this box")
+    objs = _reference_objs(tmp_path)
     golden = os.path.join(os.path.dirname(__file__), "golden")
     for obj, fixture, faces in (("ExampleObject3.obj", "example_object3.npz", 12800), ("viking_room.obj", "viking_room.npz", 3828)):
-        t = scenes.load_obj(os.path.join(assets, obj))
+        t = scenes.load_obj(objs[obj])
         assert t.dtype == L.TRIANGLE and len(t) == faces
         g = np.load(os.path.join(golden, fixture))["triangles"]
         assert t.tobytes() == np.ascontiguousarray(g, dtype=L.TRIANGLE).tobytes()
     # the quad grid: 6 400 quads fanned into 12 800 triangles, all on z = 0 inside [-4, 4]^2, uv and normals carried
-    t = scenes.load_obj(os.path.join(assets, "ExampleObject3.obj"))
+    t = scenes.load_obj(objs["ExampleObject3.obj"])
     assert (t["a"][:, 2] == 0).all() and abs(t["a"][:, :2]).max() <= 4.0
     assert (t["a_normal"][:, 2] != 0).all() and t["a_uv"].min() >= 0.0 and t["c_uv"].max() <= 1.0
 
@@ -122,13 +135,8 @@ def test_cpp_obj_ingest_rejects_malformed_files(tmp_path):
 
 
 def test_cpp_obj_ingest_on_the_reference_assets(tmp_path):
-    import glob
-    import os
-    objs = sorted(glob.glob("/root/reference/Assets/_Assets/*.obj"))
-    if not objs:
-        import pytest
-        pytest.skip("no /root/reference on this box")
-    for obj in objs:
+    objs = _reference_objs(tmp_path)
+    for obj in objs.values():
         want = scenes.load_obj(obj)
         got = _cpp_triangles(open(obj).read(), tmp_path)
         assert len(want) > 0 and got.tobytes() == want.tobytes(), obj
