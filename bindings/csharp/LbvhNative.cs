@@ -145,6 +145,11 @@ public static class LbvhNative
         uint prefixShift, uint shift, IntPtr dHist);
     [DllImport(Lib)] public static extern int lbvh_lower_bound_device(IntPtr ctx, IntPtr dSortedKeys, uint count, IntPtr dProbes, uint nProbes,
         IntPtr dPositions);
+    // the key-range sharded sort over N contexts of this process in one call (include/lbvh.h; MultiGpuSorter.cs)
+    public const int SORT_SHARDED_MAX_CONTEXTS = 16;
+    public const uint SORT_SHARDED_REPLICATE = 1;
+    [DllImport(Lib)] public static extern int lbvh_sort_pairs_sharded(IntPtr[] ctxs, uint nCtx, IntPtr[] dKeys, IntPtr[] dValues,
+        uint[] hCounts, IntPtr[] dOutKeys, IntPtr[] dOutValues, uint[] hOutCapacity, [Out] uint[] hOutCounts, uint flags);
 
     public static void Check(IntPtr ctx, int status)
     {

@@ -263,6 +263,50 @@ lbvh_status lbvh_key_histogram_device(lbvh_context* ctx, const uint32_t* d_keys,
 lbvh_status lbvh_lower_bound_device(lbvh_context* ctx, const uint32_t* d_sorted_keys, uint32_t count,
                                     const uint32_t* d_probes, uint32_t n_probes, uint32_t* d_positions);
 
+/* ---- cfg4: the key-range sharded sort as ONE call over N contexts of this process -------------------------------------- *
+ * The same algorithm as sharded_sort.py (one process per GPU, RCCL), with the collectives replaced by peer-mapped memory and
+ * sync events, all of it HIP: every context sorts its block; four MSD rounds of 8-bit digit histograms, summed on every context
+ * from every context's table, pick the W - 1 splitters; each context's sorted block is cut at the splitters and its runs are
+ * stored straight into the destination contexts' output buffers (over xGMI on distinct GPUs); every destination sorts what it
+ * received.
+ *
+ * Input.     Block i is h_counts[i] pairs at d_keys[i] / d_values[i], memory of ctxs[i]'s device.  The global sequence is the
+ *            concatenation of the blocks in context order.
+ * Contexts.  1 <= n_ctx <= LBVH_SORT_SHARDED_MAX_CONTEXTS (16: the n_prefixes <= 16 of the histogram kernel holds the W - 1
+ *            splitter rows).  Pairwise distinct contexts; their devices may repeat (logical ranks on one GPU).  The call enables
+ *            peer access itself (lbvh_peer_enable's semantics) and returns LBVH_ERR_HIP when two devices cannot reach each other.
+ * Result, slice mode (flags == 0).  Slice q is d_out_keys[q][0 .. h_out_counts[q]) with its values.  The concatenation of the
+ *            slices in context order equals lbvh_sort_pairs over the global sequence, word for word, keys and values (stable).
+ *            Slice q holds exactly the keys in [s_q, s_{q+1}): s_q = the key at global sorted position floor(q * N / W), s_0 = 0,
+ *            s_W = infinity (the splitters of ShardedSorter.find_splitters), so equal keys never straddle slices.  Words of the
+ *            output buffers past a slice are not written.
+ * Result, LBVH_SORT_SHARDED_REPLICATE.  Every d_out_keys[i] / d_out_values[i] receives the whole sorted sequence (N pairs) —
+ *            the layout of a replicated tree build; h_out_counts still receives the slice lengths.
+ * Inputs are clobbered: they come back locally sorted.  Outputs must not overlap any input; overlap on the same context (or of a
+ *            context's two outputs) is LBVH_ERR_INVALID_ARG.  Each output array holds h_out_capacity[q] words.
+ * Capacity.  Any slice can hold all N pairs (all keys equal).  If a slice needs more than h_out_capacity[q] (under REPLICATE:
+ *            N > h_out_capacity[i] for some i), the call returns LBVH_ERR_INVALID_ARG naming the slice and the count it needs,
+ *            with h_out_counts filled and nothing written to any output; a retry with larger buffers succeeds (re-sorting
+ *            locally sorted blocks is still correct).
+ * Limits.    Total pairs <= 2^30 - 1 (the per-call count of lbvh_sort_pairs); a total of 0 is accepted (counts 0, nothing
+ *            enqueued).  Every pointer 4-byte aligned; a block of 0 pairs may have NULL pointers, an output of capacity 0 too.
+ * Ordering.  The work is enqueued on every context's stream behind what is already there.  A store into another context's
+ *            buffer happens only after everything that context had enqueued before the call.  On return, work enqueued later on
+ *            ctxs[i] sees d_out_*[i] complete (a device-side wait, no host wait).  The host blocks ONCE per call (n_ctx >= 2), to
+ *            read the W x W send-count table — the single synchronisation of sharded_sort.py.
+ * Caches.    Every buffer the call writes is a write in lbvh_note_write's sense (as lbvh_sort_pairs): derived scenes and
+ *            live-path lists built from them are dropped.
+ * The sorts inside the call always take the four-pass form and neither read nor publish lbvh_sort_pairs' two-level hint (a
+ * received slice is a narrow key range by construction): a context's later lbvh_sort_pairs behaves as before the call.
+ * Errors: lbvh_last_error of every context gives the text. */
+#define LBVH_SORT_SHARDED_MAX_CONTEXTS 16
+#define LBVH_SORT_SHARDED_REPLICATE    1u
+
+lbvh_status lbvh_sort_pairs_sharded(lbvh_context* const* ctxs, uint32_t n_ctx,
+                                    uint32_t* const* d_keys, uint32_t* const* d_values, const uint32_t* h_counts,
+                                    uint32_t* const* d_out_keys, uint32_t* const* d_out_values,
+                                    const uint32_t* h_out_capacity, uint32_t* h_out_counts, uint32_t flags);
+
 /* ---- stage a-6: DistributeKeys ---------------------------------------------------------------- */
 
 /* Replaces MeshBufferContainer.DistributeKeys (Sc/MeshBufferContainer.cs:154-169), a serial CPU

@@ -83,7 +83,9 @@ lbvh_status lbvh_trace_tile_costs(lbvh_context* ctx, const lbvh_camera* h_camera
  * launches on this context is bracketed by its own pair of HIP events (on the context's stream).
  * lbvh_profile_end waits for the stream and returns one row per kernel name: launches and the
  * summed device time.  Off by default: it adds two event records per launch, so it is never on
- * inside a throughput measurement. */
+ * inside a throughput measurement.  lbvh_sort_pairs_sharded also adds one row per stage on every context it runs on
+ * ("sharded:local_sort", "sharded:splitters", "sharded:exchange", "sharded:receive_sort", "sharded:broadcast"): the span of
+ * the stage on that context's stream, device-side waits for the other contexts included. */
 typedef struct lbvh_profile_row {
     char     name[48];
     uint32_t launches;

@@ -86,6 +86,8 @@ SIGNATURES = {
     "lbvh_trace_costs_import": (_I32, [_P, _P, _U32, _U32]),
     "lbvh_key_histogram_device": (_I32, [_P, _P, _U32, _P, _U32, _U32, _U32, _P]),
     "lbvh_lower_bound_device": (_I32, [_P, _P, _U32, _P, _U32, _P]),
+    "lbvh_sort_pairs_sharded": (_I32, [C.POINTER(_P), _U32, C.POINTER(_P), C.POINTER(_P), C.POINTER(_U32), C.POINTER(_P),
+                                       C.POINTER(_P), C.POINTER(_U32), C.POINTER(_U32), _U32]),
     "lbvh_animate": (_I32, [_P, _P, _U32, _P, _P, C.c_float, C.c_float, _P]),
     "lbvh_animate_build_scene": (_I32, [_P, _P, _P, _P, C.c_float, C.c_float, _P, _U32, _U32, _F3, _F3, _P, _P, _P, _P, _P, _P, _U32]),
     "lbvh_trace_rays": (_I32, [_P, _P, _SZ, C.c_float, C.POINTER(Scene), _P]),
@@ -114,6 +116,9 @@ SIGNATURES = {
     "lbvh_event_record": (_I32, [_P, _P]),
     "lbvh_event_elapsed_ms": (_I32, [_P, _P, _P, C.POINTER(C.c_float)]),
 }
+
+SORT_SHARDED_MAX_CONTEXTS = 16           # include/lbvh.h LBVH_SORT_SHARDED_MAX_CONTEXTS
+SORT_SHARDED_REPLICATE = 1               # LBVH_SORT_SHARDED_REPLICATE
 
 # include/lbvh_debug.h: not part of the drop-in boundary
 DEBUG_SWITCH_SORT_QUEUES, DEBUG_SWITCH_COLD_ORDER, DEBUG_SWITCH_BUILD_FORM, DEBUG_SWITCH_FRAME_WAIT_MS, DEBUG_SWITCH_SORT_FORM, DEBUG_SWITCH_FAIL_RESERVE = range(6)

@@ -230,6 +230,9 @@ lbvh_status lbvh_destroy(lbvh_context* ctx)
     if (ctx->tie_list) (void)hipFree(ctx->tie_list);
     if (ctx->wide_nodes) (void)hipFree(ctx->wide_nodes);
     if (ctx->trace_frame_costs) (void)hipFree(ctx->trace_frame_costs);
+    if (ctx->shard_scratch) (void)hipFree(ctx->shard_scratch);
+    if (ctx->shard_event) (void)hipEventDestroy(ctx->shard_event);
+    if (ctx->shard_host) (void)hipHostFree(ctx->shard_host);
     for (auto& s : ctx->prof_spans) { (void)hipEventDestroy(s.a); (void)hipEventDestroy(s.b); }
     for (auto e : ctx->prof_pool) (void)hipEventDestroy(e);
     if (ctx->own_stream && ctx->stream) (void)hipStreamDestroy(ctx->stream);

@@ -156,6 +156,13 @@ struct lbvh_context {
     lbvh_ray_stats* ray_stats = nullptr;      // lbvh_ray_stats_target: the four-wide walkers add their counters here while set
     uint32_t ray_walker = 1;                  // lbvh_debug_ray_walker: 0 binary nodes, 1 four-wide, 2 four-wide with the few-rays kernel always
 
+    // lbvh_sort_pairs_sharded (lbvh_sort_sharded.hip): one device block of four [15][256] digit tables (one per MSD round: no
+    // context overwrites a table a peer has not read yet), the splitter state and the lower-bound positions; its ordering event
+    // (a system-scope release, as lbvh_sync_event_create's); the pinned row of send offsets the host reads once per call
+    uint32_t* shard_scratch = nullptr;
+    hipEvent_t shard_event = nullptr;
+    uint32_t* shard_host = nullptr;
+
     // per-kernel event profiling (lbvh_profile_begin / lbvh_profile_end)
     struct prof_span { const char* name; hipEvent_t a, b; };
     bool prof_enabled = false;
@@ -226,8 +233,11 @@ int lbvh_launch_post_sort_merged(lbvh_context* ctx, uint32_t n, uint32_t* d_keys
 // the sort with its scratch described / already cleared by the caller
 int lbvh_sort_scratch(lbvh_context* ctx, uint32_t count, uint32_t** d_zero, uint32_t* zero_words);
 // key_bits: keys below 2^key_bits are the common case (30 for Morton codes; anything above still sorts correctly): where the
-// two-level form (lbvh_sort.hip) takes its bucket digit from
-int lbvh_launch_sort(lbvh_context* ctx, uint32_t* d_keys, uint32_t* d_values, uint32_t count, bool scratch_cleared, uint32_t key_bits = 32u);
+// two-level form (lbvh_sort.hip) takes its bucket digit from.  hints = false: always the four passes, and the two-level form's
+// hint (the largest bucket, ctx->fault_host words 16 .. 19, and the streak) is neither read nor published — the sorts inside
+// lbvh_sort_pairs_sharded, whose received slices are narrow key ranges by construction
+int lbvh_launch_sort(lbvh_context* ctx, uint32_t* d_keys, uint32_t* d_values, uint32_t count, bool scratch_cleared, uint32_t key_bits = 32u,
+                     bool hints = true);
 // the frontier counter lbvh_launch_refit(n) will use on the current lane (sizes the scratch)
 int lbvh_refit_counter(lbvh_context* ctx, uint32_t n, uint32_t** d_counter);
 // the stand-alone refit (lbvh_refit): d_sorted_indices may be nullptr (boxes already in leaf order)
@@ -249,6 +259,17 @@ int lbvh_launch_tree_boxes(lbvh_context* ctx, uint32_t n, const uint32_t* d_keys
 // LEAF | leaf_base + ORIGINAL triangle index, looked up in d_sorted_indices)
 int lbvh_launch_tree_fused(lbvh_context* ctx, uint32_t n, const uint32_t* d_keys, const uint32_t* d_sorted_indices,
                            lbvh_fast_node* d_fused, uint32_t leaf_base);
+
+// lbvh_sort_pairs_sharded's pieces (lbvh_sort.hip): the cfg4 kernels with device-side prefixes / probes, one MSD round of the
+// splitter search over the W contexts' digit tables (peer pointers), and the range copy of up to 2 x 16 word runs
+struct lbvh_copy_run { const uint32_t* src; uint32_t* dst; uint32_t count; };
+int lbvh_launch_key_histogram(lbvh_context* ctx, const uint32_t* d_keys, uint32_t count, const uint32_t* d_prefixes,
+                              uint32_t n_prefixes, uint32_t prefix_shift, uint32_t shift, uint32_t* d_hist);
+int lbvh_launch_lower_bound(lbvh_context* ctx, const uint32_t* d_sorted_keys, uint32_t count, const uint32_t* d_probes,
+                            uint32_t n_probes, uint32_t* d_positions);
+int lbvh_launch_splitter_digit(lbvh_context* ctx, const uint32_t* const* d_tables, uint32_t n_tables, uint32_t rows, uint32_t level,
+                               uint64_t total, uint32_t* d_prefixes, uint64_t* d_remaining);
+int lbvh_launch_range_copy(lbvh_context* ctx, const lbvh_copy_run* h_runs, uint32_t n_runs);
 
 // A library call is about to write [p, p + bytes): if that touches what the derived scene was built from, the
 // derived scene is stale from here on.

@@ -1055,7 +1055,8 @@ static inline bool two_level_size(uint32_t count) { return count >= (1u << 15) &
 constexpr int kBucketThreads = 1024, kBucketItems = 16;        // a bucket of up to 16 384 pairs lives in one workgroup's registers
 constexpr uint32_t kSortStreak = 3;                            // sorts in a row whose largest bucket fitted, before the two-level form is taken
 
-int lbvh_launch_sort(lbvh_context* ctx, uint32_t* d_keys, uint32_t* d_values, uint32_t count, bool scratch_cleared, uint32_t key_bits)
+int lbvh_launch_sort(lbvh_context* ctx, uint32_t* d_keys, uint32_t* d_values, uint32_t count, bool scratch_cleared, uint32_t key_bits,
+                     bool hints)
 {
     if (count < 2) return LBVH_OK;
     sort_plan pl;
@@ -1088,7 +1089,7 @@ int lbvh_launch_sort(lbvh_context* ctx, uint32_t* d_keys, uint32_t* d_values, ui
     uint32_t* gtable = gfine + kFineBins;
     uint32_t* stat_dev = ctx->fault_dev + 16;                   // words 16 .. 19 of the mapped block (word 0: the fault word)
     bool two_level = false;
-    if (two_level_size(count)) {
+    if (hints && two_level_size(count)) {
         const volatile uint32_t* st = ctx->fault_host + 16;
         uint32_t largest = 0;
         bool known = true;
@@ -1136,7 +1137,8 @@ int lbvh_launch_sort(lbvh_context* ctx, uint32_t* d_keys, uint32_t* d_values, ui
 #endif
         return LBVH_OK;       // the buckets are back in d_keys / d_values
     }
-    const bool stat = two_level_size(count);      // (then items == 8: the 512 x 8 form, whose first tile can derive the buckets)
+    // (then items == 8: the 512 x 8 form, whose first tile can derive the buckets); hints == false: the hint words are left alone
+    const bool stat = hints && two_level_size(count);
     if (stat)
         LBVH_LAUNCH(ctx, (sort_histogram_kernel<HIST_FOUR | HIST_FINE>), dim3(std::max(1u, std::min(hblocks, (count + (uint32_t)LBVH_FINE_BLOCK_KEYS - 1u) / (uint32_t)LBVH_FINE_BLOCK_KEYS))),
                     dim3(kThreads), d_keys, count, ghist, gfine, fine_shift);
@@ -1286,4 +1288,154 @@ extern "C" lbvh_status lbvh_lower_bound_device(lbvh_context* ctx, const uint32_t
                                                const uint32_t* d_probes, uint32_t n_probes, uint32_t* d_positions)
 {
     return lower_bound_impl(ctx, d_sorted_keys, count, nullptr, d_probes, n_probes, d_positions);
+}
+
+// ---- lbvh_sort_pairs_sharded: the splitter search and the exchange (orchestration: lbvh_sort_sharded.hip) ----------------
+
+struct shard_tables { const uint32_t* v[LBVH_SORT_SHARDED_MAX_CONTEXTS]; };
+
+// One MSD round of the splitter search, run redundantly (and identically) on every context: the W digit tables of the round —
+// [rows][256] u32, or one [256] row at level 0 that stands for every row — are read through peer pointers (system-scope loads:
+// another GPU's stores are not served from this GPU's caches) and summed in 64 bits.  Row p's digit is the first whose
+// cumulative count exceeds the row's remaining rank (sharded_sort.py find_splitters: cumsum + searchsorted(right=True), clamped
+// to 255); the rank drops by the keys below that digit and the prefix takes the digit.  Level 0 starts the state: prefix 0,
+// rank floor((p + 1) * total / world).  After level 3 prefixes[p] is splitter p + 1: the key at global sorted position
+// floor((p + 1) * total / world).
+__global__ __launch_bounds__(256) void splitter_digit_kernel(shard_tables tables, uint32_t n_tables, uint32_t rows, uint32_t level,
+                                                             uint64_t total, uint32_t world, uint32_t* __restrict__ prefixes,
+                                                             uint64_t* __restrict__ remaining)
+{
+    __shared__ uint64_t s_cum[256];
+    const uint32_t t = threadIdx.x;
+    for (uint32_t p = 0; p < rows; ++p) {
+        const uint32_t row = level == 0 ? 0u : p;
+        uint64_t c = 0;
+        for (uint32_t j = 0; j < n_tables; ++j)
+            c += __hip_atomic_load(tables.v[j] + row * 256u + t, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+        s_cum[t] = c;
+        __syncthreads();
+        for (uint32_t off = 1; off < 256u; off <<= 1) {          // inclusive scan of the 256 digit counts
+            const uint64_t add = t >= off ? s_cum[t - off] : 0ull;
+            __syncthreads();
+            s_cum[t] += add;
+            __syncthreads();
+        }
+        const uint64_t rem = level == 0 ? (uint64_t)(p + 1u) * total / world : remaining[p];
+        const uint32_t d = (uint32_t)__syncthreads_count(s_cum[t] <= rem);      // digits whose cumulative count is <= rem
+        if (t == 0) {
+            const uint32_t dd = d < 255u ? d : 255u;
+            remaining[p] = rem - (dd ? s_cum[dd - 1u] : 0ull);
+            prefixes[p] = (level == 0 ? 0u : prefixes[p] << 8) | dd;
+        }
+        __syncthreads();
+    }
+}
+
+// Moves runs of 32-bit words (keys or values of one (source, destination) pair) from this context's memory to any context's,
+// peer-mapped: stores to another GPU travel over xGMI.  Block b copies 4096 words of the run it falls in; word positions are
+// counted from the destination rounded down to 16 bytes, so every whole 16-byte group of the destination is one dwordx4 store
+// whatever the 4-byte offsets of source and destination (the source is read with dwordx4 too when it has the destination's
+// offset modulo 16 bytes, with four dword loads otherwise); only the first and the last group of a run go word by word.
+constexpr uint32_t kCopyThreads = 256, kCopyQuads = 4, kCopyWords = kCopyThreads * kCopyQuads * 4u;
+
+struct shard_copy_runs {
+    lbvh_copy_run r[2 * LBVH_SORT_SHARDED_MAX_CONTEXTS];
+    uint32_t first_block[2 * LBVH_SORT_SHARDED_MAX_CONTEXTS];
+    uint32_t n;
+};
+
+__global__ __launch_bounds__(kCopyThreads) void shard_range_copy_kernel(shard_copy_runs runs)
+{
+    const uint32_t b = blockIdx.x;
+    const uint32_t* src = runs.r[0].src;
+    uint32_t* dst = runs.r[0].dst;
+    uint32_t count = runs.r[0].count, first = 0;
+#pragma unroll
+    for (uint32_t k = 1; k < 2u * LBVH_SORT_SHARDED_MAX_CONTEXTS; ++k)      // (constant indices: the run list stays in the kernarg)
+        if (k < runs.n && runs.first_block[k] <= b) {
+            src = runs.r[k].src;
+            dst = runs.r[k].dst;
+            count = runs.r[k].count;
+            first = runs.first_block[k];
+        }
+    const uint32_t mis = (uint32_t)(((uintptr_t)dst >> 2) & 3u);           // words between the 16-byte boundary and dst
+    uint32_t* dst0 = dst - mis;
+    const uint32_t* src0 = src - mis;                                        // (only dereferenced inside the run)
+    const bool src_wide = ((uintptr_t)src0 & 15u) == 0;
+    const int64_t q0 = (int64_t)(b - first) * (kCopyThreads * kCopyQuads) + threadIdx.x;
+    uint4 v[kCopyQuads];
+#pragma unroll
+    for (uint32_t u = 0; u < kCopyQuads; ++u) {
+        const int64_t j = (q0 + (int64_t)u * kCopyThreads) * 4 - mis;      // run index of the group's first word
+        if (j >= 0 && j + 4 <= (int64_t)count) {
+            if (src_wide) {
+                v[u] = *reinterpret_cast<const uint4*>(src0 + (j + mis));
+            } else {
+                v[u] = make_uint4(src[j], src[j + 1], src[j + 2], src[j + 3]);
+            }
+        } else {
+            uint32_t w[4] = {0u, 0u, 0u, 0u};
+#pragma unroll
+            for (int e = 0; e < 4; ++e)
+                if (j + e >= 0 && j + e < (int64_t)count) w[e] = src[j + e];
+            v[u] = make_uint4(w[0], w[1], w[2], w[3]);
+        }
+    }
+#pragma unroll
+    for (uint32_t u = 0; u < kCopyQuads; ++u) {
+        const int64_t j = (q0 + (int64_t)u * kCopyThreads) * 4 - mis;
+        if (j >= 0 && j + 4 <= (int64_t)count) {
+            *reinterpret_cast<uint4*>(dst0 + (j + mis)) = v[u];
+        } else {
+            const uint32_t w[4] = {v[u].x, v[u].y, v[u].z, v[u].w};
+#pragma unroll
+            for (int e = 0; e < 4; ++e)
+                if (j + e >= 0 && j + e < (int64_t)count) dst[j + e] = w[e];
+        }
+    }
+}
+
+int lbvh_launch_key_histogram(lbvh_context* ctx, const uint32_t* d_keys, uint32_t count, const uint32_t* d_prefixes,
+                              uint32_t n_prefixes, uint32_t prefix_shift, uint32_t shift, uint32_t* d_hist)
+{
+    return key_histogram_impl(ctx, d_keys, count, nullptr, d_prefixes, n_prefixes, prefix_shift, shift, d_hist);
+}
+
+int lbvh_launch_lower_bound(lbvh_context* ctx, const uint32_t* d_sorted_keys, uint32_t count, const uint32_t* d_probes,
+                            uint32_t n_probes, uint32_t* d_positions)
+{
+    return lower_bound_impl(ctx, d_sorted_keys, count, nullptr, d_probes, n_probes, d_positions);
+}
+
+int lbvh_launch_splitter_digit(lbvh_context* ctx, const uint32_t* const* d_tables, uint32_t n_tables, uint32_t rows, uint32_t level,
+                               uint64_t total, uint32_t* d_prefixes, uint64_t* d_remaining)
+{
+    if (n_tables == 0 || n_tables > (uint32_t)LBVH_SORT_SHARDED_MAX_CONTEXTS || rows == 0)
+        return lbvh_set_error(ctx, LBVH_ERR_INVALID_ARG, "lbvh_launch_splitter_digit", "bad table count");
+    shard_tables tb = {};
+    for (uint32_t j = 0; j < n_tables; ++j) tb.v[j] = d_tables[j];
+    LBVH_LAUNCH(ctx, splitter_digit_kernel, dim3(1), dim3(256), tb, n_tables, rows, level, total, n_tables, d_prefixes, d_remaining);
+    LBVH_HIP_TRY(ctx, hipGetLastError());
+    return LBVH_OK;
+}
+
+int lbvh_launch_range_copy(lbvh_context* ctx, const lbvh_copy_run* h_runs, uint32_t n_runs)
+{
+    if (n_runs > 2u * LBVH_SORT_SHARDED_MAX_CONTEXTS)
+        return lbvh_set_error(ctx, LBVH_ERR_INVALID_ARG, "lbvh_launch_range_copy", "more than 2 x 16 runs");
+    shard_copy_runs runs = {};
+    uint64_t blocks = 0;
+    for (uint32_t k = 0; k < n_runs; ++k) {
+        if (h_runs[k].count == 0) continue;
+        const uint32_t mis = (uint32_t)(((uintptr_t)h_runs[k].dst >> 2) & 3u);
+        runs.r[runs.n] = h_runs[k];
+        runs.first_block[runs.n] = (uint32_t)blocks;
+        runs.n++;
+        blocks += ((uint64_t)h_runs[k].count + mis + kCopyWords - 1u) / kCopyWords;
+    }
+    if (runs.n == 0) return LBVH_OK;
+    if (blocks > 0x7FFFFFFFull) return lbvh_set_error(ctx, LBVH_ERR_INVALID_ARG, "lbvh_launch_range_copy", "too many words");
+    LBVH_LAUNCH(ctx, shard_range_copy_kernel, dim3((uint32_t)blocks), dim3(kCopyThreads), runs);
+    LBVH_HIP_TRY(ctx, hipGetLastError());
+    return LBVH_OK;
 }

@@ -518,6 +518,87 @@ class MultiGpuDrawer:
             c.close()
 
 
+class MultiGpuSorter:
+    """ComputeBufferSorter over N contexts of one process (twin of host/lbvh_host.hpp MultiGpuSorter; BASELINE configs[3]): one
+    Context per entry of `devices` (a device may repeat: logical ranks on one GPU) and one lbvh_sort_pairs_sharded call per
+    sort — the key-range sharded sort whose multi-process twin is sharded_sort.ShardedSorter.  Block i lives on context i; the
+    result is context q's slice of the globally sorted sequence, or (replicate) the whole sequence on every context."""
+
+    def __init__(self, devices):
+        self.contexts = [Context(d) for d in devices]
+        self._inputs = [None] * len(self.contexts)       # per context: (keys, values) DataBuffers, grown on demand
+        self._outputs = [None] * len(self.contexts)
+
+    def sort_device(self, keys, values, counts, out_keys, out_values, capacities, replicate=False):
+        """The C call on device pointers (one of each per context; ints or c_void_p).  Asynchronous apart from its one host
+        wait; the inputs come back locally sorted.  Returns the slice lengths."""
+        n = len(self.contexts)
+        arr = lambda t, xs: (t * n)(*[x.value if isinstance(x, C.c_void_p) else x for x in xs])    # noqa: E731
+        ctxs = (C.c_void_p * n)(*[c.handle.value for c in self.contexts])
+        out_counts = (C.c_uint32 * n)()
+        N.check(self.contexts[0].handle, N.lib.lbvh_sort_pairs_sharded(
+            ctxs, n, arr(C.c_void_p, keys), arr(C.c_void_p, values), arr(C.c_uint32, counts), arr(C.c_void_p, out_keys),
+            arr(C.c_void_p, out_values), arr(C.c_uint32, capacities), out_counts, N.SORT_SHARDED_REPLICATE if replicate else 0))
+        return list(out_counts)
+
+    def _buffers(self, slots, i, size):
+        if slots[i] is None or slots[i][0].size < size:
+            if slots[i] is not None:
+                for b in slots[i]:
+                    b.dispose()
+            slots[i] = (DataBuffer(self.contexts[i], max(size, 1), np.uint32), DataBuffer(self.contexts[i], max(size, 1), np.uint32))
+        return slots[i]
+
+    def sort(self, blocks, replicate=False):
+        """blocks: one (keys, values) pair of u32 host arrays per context.  Returns ([(keys, values)] per context, counts):
+        context q's slice of the sorted sequence (replicate: the whole sequence), as host arrays."""
+        assert len(blocks) == len(self.contexts)
+        blocks = [(np.ascontiguousarray(k, dtype=np.uint32), np.ascontiguousarray(v, dtype=np.uint32)) for k, v in blocks]
+        total = sum(len(k) for k, _ in blocks)
+        ins, outs = [], []
+        for i, (k, v) in enumerate(blocks):
+            assert len(k) == len(v)
+            bk, bv = self._buffers(self._inputs, i, len(k))
+            bk.local[: len(k)] = k
+            bv.local[: len(v)] = v
+            bk.sync()
+            bv.sync()
+            ins.append((bk, bv))
+            outs.append(self._buffers(self._outputs, i, total))       # any slice may need all N pairs
+        counts = self.sort_device([b[0].device for b in ins], [b[1].device for b in ins], [len(k) for k, _ in blocks],
+                                  [o[0].device for o in outs], [o[1].device for o in outs], [o[0].size for o in outs],
+                                  replicate=replicate)
+        res = []
+        for q, (ok, ov) in enumerate(outs):
+            m = total if replicate else counts[q]
+            res.append((ok.get_data()[:m].copy(), ov.get_data()[:m].copy()))
+        return res, counts
+
+    def sync(self):
+        for c in self.contexts:
+            c.sync()
+
+    def close(self):
+        for c in self.contexts:
+            if c.handle:
+                c.sync()
+        for slots in (self._inputs, self._outputs):
+            for pair in slots:
+                if pair is not None:
+                    for b in pair:
+                        b.dispose()
+        self._inputs = [None] * len(self.contexts)
+        self._outputs = [None] * len(self.contexts)
+        for c in self.contexts:
+            c.close()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+
 class DynamicPathTracer:
     """SURVEY 8(f) rank 3 / BASELINE configs[4] (extension, no reference counterpart): per frame the rigid bodies
     are rotated (lbvh_animate), the whole LBVH is rebuilt on the same buffers (RaytracingMeshDrawer.rebuild), primary

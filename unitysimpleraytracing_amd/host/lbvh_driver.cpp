@@ -6,6 +6,9 @@
 //     lbvh_driver multi <ranks> [n] [w] [h]      one process, <ranks> contexts (MultiGpuDrawer; rank r on device r % device
 //                                                count): frames assembled in rank 0's buffer by peer-mapped stores,
 //                                                compared word for word with one context's whole frame
+//     lbvh_driver sort <ranks> [n] [replicate]   n pairs in uneven blocks over <ranks> contexts sorted by ONE
+//                                                lbvh_sort_pairs_sharded call (MultiGpuSorter), compared word for word
+//                                                with lbvh_sort_pairs on one context; prints JSON with "equal"
 #include <chrono>
 #include <cmath>
 #include <cstdio>
@@ -113,8 +116,79 @@ static int multi_main(int argc, char** argv)
     }
 }
 
+// `sort <ranks> <n> [replicate]`: n (key, value) pairs in uneven blocks over `ranks` contexts (devices dealt round-robin; one
+// block empty when ranks > 2), sorted by MultiGpuSorter (lbvh_sort_pairs_sharded), compared word for word with lbvh_sort_pairs
+// of the whole sequence on one context.  Keys: half uniform, half from eight values (ties across blocks); values: global index.
+static int sort_main(int argc, char** argv)
+{
+    const int ranks = argc > 2 ? atoi(argv[2]) : 2;
+    const uint32_t n = argc > 3 ? (uint32_t)strtoul(argv[3], nullptr, 10) : 1000000u;
+    const bool replicate = argc > 4 && std::strcmp(argv[4], "replicate") == 0;
+    if (ranks < 1 || ranks > LBVH_SORT_SHARDED_MAX_CONTEXTS) { std::fprintf(stderr, "ranks: 1 .. 16\n"); return 1; }
+    uint64_t seed = 7;
+    std::vector<uint32_t> keys(n), values(n);
+    for (uint32_t i = 0; i < n; i++) {
+        const uint64_t r = splitmix64(seed);
+        keys[i] = (i & 1) ? (uint32_t)(r >> 32) : (uint32_t)(r % 8u) * 0x1F00A5u;
+        values[i] = i;
+    }
+    // uneven blocks: weight r + 1, block 1 empty when ranks > 2
+    std::vector<uint64_t> weight(ranks);
+    uint64_t wsum = 0;
+    for (int r = 0; r < ranks; r++) wsum += weight[r] = (ranks > 2 && r == 1) ? 0 : (uint64_t)r + 1;
+    std::vector<std::vector<uint32_t>> bk(ranks), bv(ranks);
+    uint64_t lo = 0, acc = 0;
+    for (int r = 0; r < ranks; r++) {
+        acc += weight[r];
+        const uint64_t hi = r == ranks - 1 ? n : n * acc / wsum;
+        bk[r].assign(keys.begin() + lo, keys.begin() + hi);
+        bv[r].assign(values.begin() + lo, values.begin() + hi);
+        lo = hi;
+    }
+    try {
+        const int n_dev = lbvh::Context::device_count();
+        if (n_dev <= 0) { std::fprintf(stderr, "no HIP device visible\n"); return 1; }
+        std::vector<int> devices;
+        for (int r = 0; r < ranks; r++) devices.push_back(r % n_dev);
+        lbvh::MultiGpuSorter sorter(devices);
+        sorter.SetBlocks(bk, bv);
+        auto t0 = std::chrono::steady_clock::now();
+        const std::vector<uint32_t> counts = sorter.Sort(replicate);
+        sorter.Sync();
+        const double sharded_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+        // the one-context sort of the whole sequence
+        lbvh::Context one(0);
+        lbvh::DataBuffer<uint32_t> k1(one, n ? n : 1), v1(one, n ? n : 1);
+        std::copy(keys.begin(), keys.end(), k1.LocalBuffer().begin());
+        std::copy(values.begin(), values.end(), v1.LocalBuffer().begin());
+        k1.Sync(); v1.Sync();
+        lbvh::check(one.get(), lbvh_sort_pairs(one.get(), (uint32_t*)k1.DeviceBuffer(), (uint32_t*)v1.DeviceBuffer(), n));
+        k1.GetData(); v1.GetData();
+        bool equal = true;
+        uint64_t at = 0;
+        for (int q = 0; q < ranks; q++) {
+            sorter.OutKeys(q).GetData();
+            sorter.OutValues(q).GetData();
+            const uint64_t from = replicate ? 0 : at, len = replicate ? n : counts[q];
+            equal = equal && std::memcmp(sorter.OutKeys(q).LocalBuffer().data(), k1.LocalBuffer().data() + from, len * 4) == 0 &&
+                    std::memcmp(sorter.OutValues(q).LocalBuffer().data(), v1.LocalBuffer().data() + from, len * 4) == 0;
+            at += counts[q];
+        }
+        equal = equal && at == n;
+        std::printf("{\"ranks\": %d, \"devices\": %d, \"pairs\": %u, \"replicate\": %s, \"slice_counts\": [", ranks, n_dev, n,
+                    replicate ? "true" : "false");
+        for (int q = 0; q < ranks; q++) std::printf("%s%u", q ? ", " : "", counts[q]);
+        std::printf("], \"host_ms\": %.3f, \"equal\": %s}\n", sharded_ms, equal ? "true" : "false");
+        return equal ? 0 : 2;
+    } catch (const lbvh::Error& e) {
+        std::fprintf(stderr, "%s\n", e.what());
+        return 1;
+    }
+}
+
 int main(int argc, char** argv)
 {
+    if (argc > 1 && std::strcmp(argv[1], "sort") == 0) return sort_main(argc, argv);
     if (argc > 1 && std::strcmp(argv[1], "multi") == 0) return multi_main(argc, argv);
     const bool from_obj = argc > 2 && std::strcmp(argv[1], "obj") == 0;
     uint32_t n = !from_obj && argc > 1 ? (uint32_t)atoi(argv[1]) : 4096;

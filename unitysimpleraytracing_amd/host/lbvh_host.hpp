@@ -7,6 +7,7 @@
 // reference logs and carries on; here every failing call throws lbvh::Error with the library's text.
 #pragma once
 
+#include <algorithm>
 #include <cmath>
 #include <cstdint>
 #include <cstring>
@@ -420,6 +421,85 @@ private:
     std::vector<std::unique_ptr<SyncEvent>> done_;
     std::unique_ptr<SyncEvent> consumed_;
     std::unique_ptr<DataBuffer<lbvh_hit>> frame_;
+};
+
+// ComputeBufferSorter over N contexts of one process (BASELINE configs[3]; twin of host.py MultiGpuSorter): one context per
+// entry of `devices` (a device may repeat) and ONE lbvh_sort_pairs_sharded call per Sort().  Block r = the first counts[r]
+// pairs of Keys(r) / Values(r); Sort() leaves context q's slice of the globally sorted sequence in OutKeys(q) / OutValues(q)
+// (replicate: the whole sequence on every context) and returns the slice lengths.  Buffers are grown on demand; the outputs
+// hold as many pairs as the whole sequence (any slice may need all of them).
+class MultiGpuSorter {
+public:
+    explicit MultiGpuSorter(const std::vector<int>& devices)
+    {
+        if (devices.empty() || devices.size() > LBVH_SORT_SHARDED_MAX_CONTEXTS)
+            throw Error(LBVH_ERR_INVALID_ARG, "MultiGpuSorter: 1 .. 16 contexts");
+        for (int d : devices) contexts_.emplace_back(new Context(d));
+        keys_.resize(devices.size());
+        values_.resize(devices.size());
+        out_keys_.resize(devices.size());
+        out_values_.resize(devices.size());
+    }
+    ~MultiGpuSorter()
+    {
+        try { Sync(); } catch (const Error&) {}
+    }
+    size_t Ranks() const { return contexts_.size(); }
+    Context& Ctx(size_t r) { return *contexts_[r]; }
+    DataBuffer<uint32_t>& Keys(size_t r) { return *keys_[r]; }
+    DataBuffer<uint32_t>& Values(size_t r) { return *values_[r]; }
+    DataBuffer<uint32_t>& OutKeys(size_t r) { return *out_keys_[r]; }
+    DataBuffer<uint32_t>& OutValues(size_t r) { return *out_values_[r]; }
+    // host blocks -> the contexts' input buffers (blocking uploads)
+    void SetBlocks(const std::vector<std::vector<uint32_t>>& keys, const std::vector<std::vector<uint32_t>>& values)
+    {
+        if (keys.size() != contexts_.size() || values.size() != contexts_.size())
+            throw Error(LBVH_ERR_INVALID_ARG, "MultiGpuSorter::SetBlocks: one block per context");
+        size_t total = 0;
+        for (size_t r = 0; r < keys.size(); ++r) total += keys[r].size();
+        counts_.assign(contexts_.size(), 0);
+        for (size_t r = 0; r < contexts_.size(); ++r) {
+            if (keys[r].size() != values[r].size()) throw Error(LBVH_ERR_INVALID_ARG, "MultiGpuSorter::SetBlocks: keys / values lengths");
+            grow(keys_[r], r, keys[r].size());
+            grow(values_[r], r, values[r].size());
+            grow(out_keys_[r], r, total);
+            grow(out_values_[r], r, total);
+            std::copy(keys[r].begin(), keys[r].end(), keys_[r]->LocalBuffer().begin());
+            std::copy(values[r].begin(), values[r].end(), values_[r]->LocalBuffer().begin());
+            keys_[r]->Sync();
+            values_[r]->Sync();
+            counts_[r] = (uint32_t)keys[r].size();
+        }
+    }
+    std::vector<uint32_t> Sort(bool replicate = false)
+    {
+        const size_t n = contexts_.size();
+        std::vector<lbvh_context*> ctxs(n);
+        std::vector<uint32_t*> k(n), v(n), ok(n), ov(n);
+        std::vector<uint32_t> cap(n), out(n);
+        for (size_t r = 0; r < n; ++r) {
+            if (!keys_[r]) throw Error(LBVH_ERR_INVALID_ARG, "MultiGpuSorter::Sort: SetBlocks first");
+            ctxs[r] = contexts_[r]->get();
+            k[r] = (uint32_t*)keys_[r]->DeviceBuffer();
+            v[r] = (uint32_t*)values_[r]->DeviceBuffer();
+            ok[r] = (uint32_t*)out_keys_[r]->DeviceBuffer();
+            ov[r] = (uint32_t*)out_values_[r]->DeviceBuffer();
+            cap[r] = (uint32_t)out_keys_[r]->Size();
+        }
+        check(ctxs[0], lbvh_sort_pairs_sharded(ctxs.data(), (uint32_t)n, k.data(), v.data(), counts_.data(), ok.data(), ov.data(),
+                                               cap.data(), out.data(), replicate ? LBVH_SORT_SHARDED_REPLICATE : 0u));
+        return out;
+    }
+    void Sync() { for (auto& c : contexts_) c->sync(); }
+private:
+    void grow(std::unique_ptr<DataBuffer<uint32_t>>& b, size_t r, size_t size)
+    {
+        if (!b || b->Size() < size) b.reset(new DataBuffer<uint32_t>(*contexts_[r], size ? size : 1));
+    }
+    // (destruction order: buffers before their contexts)
+    std::vector<std::unique_ptr<Context>> contexts_;
+    std::vector<std::unique_ptr<DataBuffer<uint32_t>>> keys_, values_, out_keys_, out_values_;
+    std::vector<uint32_t> counts_;
 };
 
 // BASELINE configs[4] (extension): rigid bodies rotate every frame, the LBVH is rebuilt, primary rays + `bounces`
