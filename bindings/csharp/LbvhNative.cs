@@ -25,6 +25,10 @@ public static class LbvhNative
     [StructLayout(LayoutKind.Sequential)]
     public struct Hit { public float t; public uint tri; public float u, v; }
 
+    // lbvh_ray (include/lbvh.h): a ray of the caller's own, 32 bytes; active iff tMin < tMax (RayQueries.cs)
+    [StructLayout(LayoutKind.Sequential)]
+    public struct Ray { public float originX, originY, originZ, tMin; public float dirX, dirY, dirZ, tMax; }
+
     // lbvh_camera (include/lbvh.h): the 16 matrix floats are plain fields, row-major m00..m33 as Unity's Matrix4x4 names
     // them, so the struct needs no `unsafe` / "allow unsafe code" project setting and marshals by value as it is.
     [StructLayout(LayoutKind.Sequential)]
@@ -126,6 +130,8 @@ public static class LbvhNative
         IntPtr dAabb, IntPtr dInternal, IntPtr dLeaf, IntPtr dBvh, uint flags);
     [DllImport(Lib)] public static extern int lbvh_path_begin(IntPtr ctx, ref Camera camera, IntPtr dStates);
     [DllImport(Lib)] public static extern int lbvh_trace_rays(IntPtr ctx, IntPtr dStates, UIntPtr count, float tMin, ref Scene scene, IntPtr dHits);
+    [DllImport(Lib)] public static extern int lbvh_trace_closest(IntPtr ctx, IntPtr dRays, UIntPtr count, ref Scene scene, IntPtr dHits);
+    [DllImport(Lib)] public static extern int lbvh_trace_occluded(IntPtr ctx, IntPtr dRays, UIntPtr count, ref Scene scene, IntPtr dOccluded);
     [DllImport(Lib)] public static extern int lbvh_path_scatter(IntPtr ctx, ref Scene scene, IntPtr dHits, UIntPtr count, uint bounce, uint seed,
         float albedo, IntPtr dStates);
     [DllImport(Lib)] public static extern int lbvh_path_bounce(IntPtr ctx, ref Scene scene, IntPtr dStates, IntPtr dHits, UIntPtr count,

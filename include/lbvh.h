@@ -554,6 +554,38 @@ typedef struct lbvh_path_state {
 lbvh_status lbvh_trace_rays(lbvh_context* ctx, const lbvh_path_state* d_states, size_t count, float t_min,
                             const lbvh_scene* h_scene, lbvh_hit* d_hits);
 
+/* A ray of the caller's own: 32 bytes; arrays of them 16-byte aligned. */
+typedef struct lbvh_ray {
+    float origin[3]; float t_min;
+    float dir[3];    float t_max;
+} lbvh_ray;
+
+/* Closest hit and occlusion for `count` rays of the caller's own, each with its own distance range, over the derived
+ * traversal scene — the walk of lbvh_trace_rays (and lbvh_debug_ray_walker's choice of kernel), reading lbvh_ray records
+ * directly: no live-ray pass, no list.
+ *   Active ray: t_min < t_max (false when either bound is NaN).  An inactive ray is never walked; it gets the miss record
+ *   (lbvh_trace_closest) or 0 (lbvh_trace_occluded).
+ *   Direction: need not be unit length; t is measured in units of dir.  Zero components are allowed (+-inf inverse, as in
+ *   every walker of this library).
+ *   Candidates: with T = min(t_max, LBVH_MAX_FLOAT), a triangle is a candidate iff the ray passes the slab test of the
+ *   triangle's own AABB with entry distance e, passes the Moeller-Trumbore test with the reference's rejections, t >= e (the
+ *   accept rule at the traversal flavours above) and t_min < t < T.
+ *   lbvh_trace_closest: d_hits[k] = {t, tri, u, v} of ray k's candidate with the least t; on equal t the lower triangle index.
+ *   No candidate: {LBVH_MAX_FLOAT, 0, 0, 0}, the miss record of lbvh_trace_rays — never T.
+ *   lbvh_trace_occluded: d_occluded[k] = 1 if ray k has any candidate, else 0.  The walk is the closest-hit walk (same
+ *   near-first order) cut off at its first accepted candidate: never more node fetches or triangle tests per ray.
+ * Hence: lbvh_trace_closest with t_max >= LBVH_MAX_FLOAT (or +inf) equals lbvh_trace_rays on a live path state with the same
+ * origin, dir and t_min, word for word; with a finite t_max it equals that record if its t < T and is the miss record otherwise;
+ * lbvh_trace_occluded equals (active && that t < T).
+ * Both need the derived traversal scene (lbvh_build_fast_scene; a stale one is LBVH_ERR_INVALID_ARG, as for lbvh_trace_rays),
+ * are asynchronous on the context's stream, and use the context's ray scratch: like lbvh_trace_rays they drop the path
+ * tracer's live-path list (see lbvh_path_bounce).  count == 0 is a no-op.  Rejected: NULL pointers, d_rays or d_hits not
+ * 16-byte aligned, d_occluded not 4-byte aligned, count > 2^32 - 1. */
+lbvh_status lbvh_trace_closest(lbvh_context* ctx, const lbvh_ray* d_rays, size_t count, const lbvh_scene* h_scene,
+                               lbvh_hit* d_hits);
+lbvh_status lbvh_trace_occluded(lbvh_context* ctx, const lbvh_ray* d_rays, size_t count, const lbvh_scene* h_scene,
+                                uint32_t* d_occluded);
+
 /* Camera rays into path states (origin/dir as Raytracing.compute:108-126, throughput 1, radiance 0, alive). */
 lbvh_status lbvh_path_begin(lbvh_context* ctx, const lbvh_camera* h_camera, lbvh_path_state* d_states);
 
@@ -577,7 +609,8 @@ lbvh_status lbvh_path_scatter(lbvh_context* ctx, const lbvh_scene* h_scene, cons
  * CROSS-CALL STATE: a call with bounce >= 1 — and the frame's last lbvh_path_scatter — visits only the paths the previous
  * lbvh_path_bounce on the same d_states / d_hits listed as live (a list kept by the context).  Every library call that writes
  * into those buffers drops the list (lbvh_path_begin, lbvh_trace_rays, a primary trace into any part of d_hits,
- * lbvh_buffer_upload / _fill_u32 / _free), and so does lbvh_trace_forget; then every state is scanned again.  What the library
+ * lbvh_buffer_upload / _fill_u32 / _free), and so does lbvh_trace_forget — and so do lbvh_trace_closest and
+ * lbvh_trace_occluded, whatever buffers they are given, since they use the same ray scratch; then every state is scanned again.  What the library
  * cannot see is a write of the CALLER's own (a kernel or hipMemcpy that revives or ends paths, Russian roulette): between two
  * consecutive bounces of a frame d_states and d_hits must not be written from outside the library — or lbvh_trace_forget must be
  * called after such a write. */

@@ -1,0 +1,560 @@
+"""lbvh_trace_closest / lbvh_trace_occluded: rays of the caller's own (lbvh_ray: origin, t_min, dir, t_max) through the per-ray
+walkers of lbvh_trace_rays.  The oracle's expectation comes from O.trace_rays (accept rule, lowest-index ties) through the three
+equalities the header states:
+  E1  closest with t_max >= MAX_FLOAT (or +inf) == lbvh_trace_rays on a live path state with the same origin, dir and t_min
+  E2  closest(t_max) == closest(+inf) if closest(+inf).t < min(t_max, MAX_FLOAT), else the miss record
+  E3  occluded == (active and closest(+inf).t < min(t_max, MAX_FLOAT))
+Per-ray t_min: the rays are grouped by their t_min value, one oracle call per group; on the GPU they stay interleaved in one
+buffer, so a wave sees mixed bounds."""
+import ctypes as C
+import json
+import os
+import re
+import subprocess
+
+import numpy as np
+import pytest
+
+import oracle as O
+from unitysimpleraytracing_amd import layouts as L
+from unitysimpleraytracing_amd import scenes
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+MISS = np.array([(L.MAX_FLOAT, 0, 0.0, 0.0)], dtype=L.HIT)[0]
+LIGHT = np.array([0.0, 250.0, 150.0], dtype=np.float32)       # outside the scene box of every scene here
+
+
+def H():
+    from unitysimpleraytracing_amd import host
+    return host
+
+
+def N():
+    from unitysimpleraytracing_amd import _native
+    return _native
+
+
+def words(a):
+    return np.ascontiguousarray(a).view(np.uint32)
+
+
+# ---- CPU: the surface in every host ------------------------------------------------------------------------------------
+
+def _header():
+    return open(os.path.join(ROOT, "include", "lbvh.h")).read()
+
+
+def test_header_declares_the_ray_record_and_both_queries():
+    text = re.sub(r"/\*.*?\*/", "", _header(), flags=re.S)
+    body = re.search(r"typedef struct lbvh_ray \{(.*?)\} lbvh_ray;", text, flags=re.S).group(1)
+    assert re.sub(r"\s+", " ", body).strip() == "float origin[3]; float t_min; float dir[3]; float t_max;"
+    closest = re.search(r"lbvh_status lbvh_trace_closest\s*\(([^;]*)\)\s*;", text, flags=re.S).group(1)
+    occluded = re.search(r"lbvh_status lbvh_trace_occluded\s*\(([^;]*)\)\s*;", text, flags=re.S).group(1)
+    norm = lambda a: [re.sub(r"\s+", " ", x).strip() for x in a.split(",")]
+    assert norm(closest) == ["lbvh_context* ctx", "const lbvh_ray* d_rays", "size_t count", "const lbvh_scene* h_scene",
+                             "lbvh_hit* d_hits"]
+    assert norm(occluded) == ["lbvh_context* ctx", "const lbvh_ray* d_rays", "size_t count", "const lbvh_scene* h_scene",
+                              "uint32_t* d_occluded"]
+    assert "#define LBVH_ABI_VERSION 11" in text
+
+
+def test_ray_layout():
+    assert L.RAY.itemsize == 32
+    assert [L.RAY.fields[f][1] for f in ("origin", "t_min", "dir", "t_max")] == [0, 12, 16, 28]
+
+
+def test_native_prototypes():
+    n = N()
+    want = (C.c_int32, [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(n.Scene), C.c_void_p])
+    assert n.SIGNATURES["lbvh_trace_closest"] == want
+    assert n.SIGNATURES["lbvh_trace_occluded"] == want
+    for name in ("lbvh_trace_closest", "lbvh_trace_occluded"):
+        assert getattr(n.lib, name).argtypes == want[1]
+
+
+def test_csharp_ray_struct_has_the_c_field_order():
+    text = re.sub(r"//[^\n]*", "", open(os.path.join(ROOT, "bindings", "csharp", "LbvhNative.cs")).read())
+    m = re.search(r"\[StructLayout\(LayoutKind\.Sequential\)\]\s*public struct Ray\s*\{(.*?)\}", text, flags=re.S)
+    assert m and "unsafe" not in m.group(0)
+    fields = []
+    for decl in m.group(1).split(";"):
+        decl = decl.strip()
+        if decl:
+            typ, names = re.fullmatch(r"public (\w+) (.*)", decl).groups()
+            fields += [(typ, x.strip()) for x in names.split(",")]
+    assert fields == [("float", f) for f in ("originX", "originY", "originZ", "tMin", "dirX", "dirY", "dirZ", "tMax")]
+    assert 4 * len(fields) == 32
+    rq = open(os.path.join(ROOT, "bindings", "csharp", "RayQueries.cs")).read()
+    assert "lbvh_trace_closest" in rq and "lbvh_trace_occluded" in rq
+
+
+# ---- the oracle's expectation ----------------------------------------------------------------------------------------
+
+def make_rays(origin, direction, t_min, t_max):
+    r = np.zeros(len(origin), dtype=L.RAY)
+    r["origin"], r["dir"] = origin, direction
+    r["t_min"], r["t_max"] = t_min, t_max
+    return r
+
+
+def active(rays):
+    return rays["t_min"] < rays["t_max"]
+
+
+def oracle_unbounded(b, rays):
+    """closest(+inf) of every active ray: O.trace_rays once per distinct t_min; inactive rays get the miss record"""
+    out = np.empty(len(rays), dtype=L.HIT)
+    out[:] = MISS
+    act = active(rays)
+    for tm in np.unique(rays["t_min"][act]):
+        sel = np.nonzero(act & (rays["t_min"] == tm))[0]
+        st = np.zeros(len(sel), dtype=L.PATH_STATE)
+        st["origin"], st["dir"], st["alive"] = rays["origin"][sel], rays["dir"][sel], 1
+        out[sel] = O.trace_rays(b, st, float(tm), threads=8)
+    return out
+
+
+def expect_closest(rays, unbounded):                                   # E2
+    bound = np.minimum(rays["t_max"], L.MAX_FLOAT)
+    keep = active(rays) & (unbounded["t"] < bound)
+    out = np.empty(len(rays), dtype=L.HIT)
+    out[:] = MISS
+    out[keep] = unbounded[keep]
+    return out
+
+
+def expect_occluded(rays, unbounded):                                  # E3
+    return (active(rays) & (unbounded["t"] < np.minimum(rays["t_max"], L.MAX_FLOAT))).astype(np.uint32)
+
+
+def _random_ray_states(tris, count, seed):
+    """Rays that start inside the scene's box (on and off its surfaces), random unit directions, a tenth of them along an
+    axis (zero components: infinite inverse directions in the slab test); 90 % alive."""
+    rng = np.random.default_rng(seed)
+    pts = np.concatenate([tris["a"][:, :3], tris["b"][:, :3], tris["c"][:, :3]]).astype(np.float32)
+    lo, hi = pts.min(axis=0), pts.max(axis=0)
+    st = np.zeros(count, dtype=L.PATH_STATE)
+    st["origin"] = (lo + (hi - lo) * rng.random((count, 3))).astype(np.float32)
+    on_surface = rng.random(count) < 0.5
+    st["origin"][on_surface] = tris["a"][rng.integers(0, len(tris), on_surface.sum()), :3]
+    d = rng.normal(size=(count, 3))
+    axis = rng.random(count) < 0.1
+    d[axis] = np.eye(3)[rng.integers(0, 3, axis.sum())] * rng.choice([-1.0, 1.0], axis.sum())[:, None]
+    st["dir"] = (d / np.linalg.norm(d, axis=1, keepdims=True)).astype(np.float32)
+    st["alive"] = (rng.random(count) < 0.9).astype(np.uint32)
+    return st
+
+
+def _scene(name):
+    if name == "torus":
+        return scenes.tiled_torus(nu=40, nv=24, grid=3)
+    if name == "soup":
+        return scenes.random_triangles(n=6000, seed=4, extent=60.0, edge=6.0)
+    if name == "duplicates":
+        base = scenes.random_triangles(n=2000, seed=6, extent=40.0, edge=8.0)
+        return np.concatenate([base, base[::2]])                   # every second triangle twice: exact t ties
+    return scenes.random_triangles(n={"two": 2, "three": 3, "seven": 7}[name], seed=8, extent=10.0, edge=6.0)
+
+
+class Queries:
+    """device buffers for one ray set and the three calls"""
+
+    def __init__(self, ctx, drawer, rays):
+        self.ctx, self.drawer = ctx, drawer
+        self.rays = H().DataBuffer(ctx, len(rays), L.RAY)
+        self.rays.local[:] = rays
+        self.rays.sync()
+        self.hits = H().DataBuffer(ctx, len(rays), L.HIT)
+        self.flags = H().DataBuffer(ctx, len(rays), np.uint32)
+
+    def closest(self):
+        self.hits.fill_u32(0x7FC00000)
+        self.drawer.trace_closest(self.rays, self.hits)
+        return self.hits.get_data().copy()
+
+    def occluded(self):
+        self.flags.fill_u32(0xDEADBEEF)
+        self.drawer.trace_occluded(self.rays, self.flags)
+        return self.flags.get_data().copy()
+
+    def set_rays(self, rays):
+        self.rays.local[:] = rays
+        self.rays.sync()
+
+    def dispose(self):
+        for b in (self.rays, self.hits, self.flags):
+            b.dispose()
+
+
+def trace_rays(ctx, drawer, states, t_min):
+    sb = H().DataBuffer(ctx, len(states), L.PATH_STATE)
+    sb.local[:] = states
+    sb.sync()
+    hb = H().DataBuffer(ctx, len(states), L.HIT)
+    hb.fill_u32(0x7FC00000)
+    s = drawer.container.scene()
+    N().check(ctx.handle, N().lib.lbvh_trace_rays(ctx.handle, sb.device, len(states), float(t_min), C.byref(s), hb.device))
+    out = hb.get_data().copy()
+    sb.dispose()
+    hb.dispose()
+    return out
+
+
+def mixed_rays(tris, count, seed, unbounded_of):
+    """_random_ray_states' rays with per-ray t_min in {1e-3, 0, 0.5, -3e38}, a third of the directions scaled by 0.25 .. 8 (t in
+    units of dir), then t_max from closest(+inf) (unbounded_of(rays) -> hits): random bounds around the hit, +inf, MAX_FLOAT,
+    and for hit rays the edge cases t_max = t (strict bound: a miss), nextafter(t, +inf) (a hit); inactive rays with
+    t_max <= t_min and with NaN bounds."""
+    rng = np.random.default_rng(seed)
+    st = _random_ray_states(tris, count, seed)
+    d = st["dir"].copy()
+    scale = rng.random(count) < 0.33
+    d[scale] *= rng.uniform(0.25, 8.0, scale.sum()).astype(np.float32)[:, None]
+    t_min = rng.choice(np.array([1e-3, 0.0, 0.5, -3.0e38], dtype=np.float32), count)
+    rays = make_rays(st["origin"], d, t_min, np.inf)
+    unb = unbounded_of(rays)
+    hit = unb["t"] < L.MAX_FLOAT
+    kind = rng.integers(0, 8, count)
+    t = unb["t"]
+    t_max = np.full(count, np.inf, dtype=np.float32)
+    span = np.where(hit, t, np.float32(50.0))
+    t_max = np.where(kind == 0, (span * rng.uniform(0.5, 1.5, count)).astype(np.float32), t_max)
+    t_max = np.where(kind == 1, L.MAX_FLOAT, t_max)
+    t_max = np.where((kind == 2) & hit, t, t_max)
+    t_max = np.where((kind == 3) & hit, np.nextafter(t, np.float32(np.inf)), t_max)
+    t_max = np.where(kind == 4, t_min, t_max)                                        # empty range
+    t_max = np.where(kind == 5, np.minimum(t_min, np.float32(0.0)) - np.float32(1.0), t_max)
+    rays["t_max"] = t_max
+    rays["t_min"] = np.where(kind == 6, np.float32(np.nan), rays["t_min"])
+    rays["t_max"] = np.where((kind == 7) & (rng.random(count) < 0.3), np.float32(np.nan), rays["t_max"])
+    return rays, unb
+
+
+# ---- GPU ------------------------------------------------------------------------------------------------------------
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("scene", ["bodies", "torus", "soup", "duplicates", "two", "three", "seven"])
+def test_e1_closest_with_an_open_bound_equals_trace_rays_word_for_word(ctx, scene):
+    if scene == "bodies":                                  # first-bounce path states of a small animated scene
+        tris, body, centres = scenes.tiled_torus(nu=24, nv=16, grid=2, with_bodies=True)
+        tris = O.animate(tris, body, centres, 0.05)
+        b = O.Built(tris, threads=8)
+        cam = scenes.camera(160, 96, (0.0, 0.0, 110.0))
+        st = O.path_begin(cam)
+        ph, _ = O.trace_primary(b, cam, threads=8)
+        O.path_scatter(b, ph.reshape(-1), st, 0, 5, 0.7)
+    else:
+        tris = _scene(scene)
+        st = _random_ray_states(tris, 20000, seed=len(tris))
+    d = H().RaytracingMeshDrawer(ctx, tris).awake()
+    b = O.Built(tris, capacity=d.container.capacity, threads=8)
+    ref = trace_rays(ctx, d, st, 1e-3)
+    live = st["alive"] != 0
+    oh = O.trace_rays(b, st, 1e-3, threads=8)
+    assert (words(ref) == words(oh)).all()
+    for t_max in (np.inf, L.MAX_FLOAT):
+        rays = make_rays(st["origin"], st["dir"], np.float32(1e-3), np.where(live, np.float32(t_max), np.float32(0.0)))
+        q = Queries(ctx, d, rays)
+        got = q.closest()
+        assert (words(got) == words(ref)).all(), t_max           # dead states: the miss record on both sides
+        assert (q.occluded() == (live & (ref["t"] < L.MAX_FLOAT))).all()
+        q.dispose()
+    if len(tris) > 10:
+        assert (ref["t"] < L.MAX_FLOAT).sum() > 300
+    d.on_destroy()
+
+
+@pytest.fixture(scope="module")
+def mixed(ctx):
+    """the torus (three grids) + the random soup, ray sets with mixed bounds, their oracle closest(+inf)"""
+    out = {}
+    for name in ("torus", "soup"):
+        tris = _scene(name)
+        d = H().RaytracingMeshDrawer(ctx, tris).awake()
+        b = O.Built(tris, capacity=d.container.capacity, threads=8)
+        rays, unb = mixed_rays(tris, 30000, 7 + len(tris), lambda r: oracle_unbounded(b, r))
+        unb = oracle_unbounded(b, rays)
+        out[name] = (d, b, rays, unb, tris)
+
+    def use(name):           # one context keeps one derived traversal scene: the scene a test uses is derived again first
+        out[name][0].build_fast_scene()
+        return out[name]
+    yield use
+    for d, *_ in out.values():
+        d.on_destroy()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", ["torus", "soup"])
+def test_e2_closest_with_finite_and_edge_bounds(ctx, mixed, name):
+    d, b, rays, unb, _ = mixed(name)
+    q = Queries(ctx, d, rays)
+    got = q.closest()
+    want = expect_closest(rays, unb)
+    assert (words(got) == words(want)).all(), np.nonzero((words(got) != words(want)).any(axis=-1))[0][:10]
+    act = active(rays)
+    hit = unb["t"] < L.MAX_FLOAT
+    at_t = act & hit & (rays["t_max"] == unb["t"])
+    assert at_t.sum() > 100 and (got["t"][at_t] == L.MAX_FLOAT).all()             # t_max == t: strict, a miss
+    after = act & hit & (rays["t_max"] == np.nextafter(unb["t"], np.float32(np.inf)))
+    assert after.sum() > 100 and (got["t"][after] == unb["t"][after]).all()      # one ulp further: the hit
+    assert (~act).sum() > 1000 and (words(got[~act]).reshape(-1, 4) == words(np.array([MISS])).reshape(1, 4)).all()
+    neg = act & (rays["t_min"] < -1e38) & (got["t"] <= 0)
+    assert neg.sum() > 0                                                         # primary-style bound: t <= 0 counts
+    assert (got["t"][act & (got["t"] < L.MAX_FLOAT)] > rays["t_min"][act & (got["t"] < L.MAX_FLOAT)]).all()
+    q.dispose()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", ["torus", "soup"])
+def test_e3_occlusion_on_mixed_bounds_and_shadow_rays(ctx, mixed, name):
+    d, b, rays, unb, tris = mixed(name)
+    q = Queries(ctx, d, rays)
+    occ = q.occluded()
+    assert (occ == expect_occluded(rays, unb)).all()
+    assert 0 < occ.sum() < active(rays).sum()
+    q.dispose()
+    # shadow rays: from the primary hit points toward the light, dir = light - origin (not normalised), t in (1e-4, 1)
+    cam = scenes.camera(200, 120, (0.0, 0.0, 150.0))
+    st = O.path_begin(cam)
+    ph = O.trace_rays(b, st, -3.0e38, threads=8)
+    hit = ph["t"] < L.MAX_FLOAT
+    origin = (st["origin"] + st["dir"] * ph["t"][:, None]).astype(np.float32)
+    shadow = make_rays(origin, (LIGHT - origin).astype(np.float32), np.float32(1e-4), np.where(hit, np.float32(1.0), np.float32(0.0)))
+    sunb = oracle_unbounded(b, shadow)
+    q = Queries(ctx, d, shadow)
+    occ = q.occluded()
+    assert (occ == expect_occluded(shadow, sunb)).all()
+    assert (words(q.closest()) == words(expect_closest(shadow, sunb))).all()
+    assert 0 < occ.sum() < hit.sum()
+    q.dispose()
+
+
+@pytest.mark.gpu
+def test_walkers_give_identical_records_and_flags(ctx, mixed):
+    d, b, rays, unb, _ = mixed("torus")
+    q = Queries(ctx, d, rays)
+    got = {}
+    try:
+        for walker in (0, 1, 2):
+            N().check(ctx.handle, N().lib.lbvh_debug_ray_walker(ctx.handle, walker))
+            got[walker] = (q.closest(), q.occluded())
+    finally:
+        N().check(ctx.handle, N().lib.lbvh_debug_ray_walker(ctx.handle, 1))
+    for w in (0, 2):
+        assert (words(got[w][0]) == words(got[1][0])).all(), w
+        assert (got[w][1] == got[1][1]).all(), w
+    assert (words(got[1][0]) == words(expect_closest(rays, unb))).all()
+    q.dispose()
+
+
+@pytest.mark.gpu
+def test_statistics_count_active_rays_and_occlusion_never_walks_more(ctx, mixed):
+    d, b, rays, unb, _ = mixed("torus")
+    for bounded in (False, True):
+        r = rays.copy()
+        if not bounded:
+            r["t_max"] = np.where(active(r), np.float32(np.inf), r["t_max"])
+        q = Queries(ctx, d, r)
+        stats = H().DataBuffer(ctx, 1, L.RAY_STATS)
+        per = {}
+        try:
+            for walker in (1, 2):
+                N().check(ctx.handle, N().lib.lbvh_debug_ray_walker(ctx.handle, walker))
+                for call in ("closest", "occluded"):
+                    stats.fill_u32(0)
+                    N().check(ctx.handle, N().lib.lbvh_ray_stats_target(ctx.handle, stats.device))
+                    getattr(q, call)()
+                    N().check(ctx.handle, N().lib.lbvh_ray_stats_target(ctx.handle, None))
+                    per[(walker, call)] = stats.get_data()[0].copy()
+        finally:
+            N().check(ctx.handle, N().lib.lbvh_ray_stats_target(ctx.handle, None))
+            N().check(ctx.handle, N().lib.lbvh_debug_ray_walker(ctx.handle, 1))
+        n_active = int(active(r).sum())
+        for walker in (1, 2):
+            c, o = per[(walker, "closest")], per[(walker, "occluded")]
+            assert int(c["rays"]) == n_active and int(o["rays"]) == n_active
+            assert int(o["node_fetches"]) <= int(c["node_fetches"]) and int(o["triangle_tests"]) <= int(c["triangle_tests"])
+            assert int(o["node_fetches"]) < int(c["node_fetches"])
+        stats.dispose()
+        q.dispose()
+
+
+@pytest.mark.gpu
+def test_errors_and_scratch_failure(ctx):
+    tris = scenes.tiled_torus(nu=16, nv=10, grid=2)
+    c2 = H().Context(0)                               # a context of its own: its ray scratch has never grown
+    try:
+        d = H().RaytracingMeshDrawer(c2, tris).awake()
+        b = O.Built(tris, capacity=d.container.capacity, threads=8)
+        st = _random_ray_states(tris, 5000, seed=3)
+        rays = make_rays(st["origin"], st["dir"], np.float32(1e-3), np.float32(np.inf))
+        q = Queries(c2, d, rays)
+        want = expect_closest(rays, oracle_unbounded(b, rays))
+        lib, h, s = N().lib, c2.handle, d.container.scene()
+        # a failed growth of the ray scratch: out of memory, nothing traced; the next call on the context succeeds
+        c2.debug_switch(N().DEBUG_SWITCH_FAIL_RESERVE, 1)
+        q.hits.fill_u32(0x7FC00000)
+        assert lib.lbvh_trace_closest(h, q.rays.device, len(rays), C.byref(s), q.hits.device) == -2
+        assert (words(q.hits.get_data()) == 0x7FC00000).all()
+        assert (words(q.closest()) == words(want)).all()
+        assert (q.occluded() == expect_occluded(rays, oracle_unbounded(b, rays))).all()
+        # argument checks
+        p = lambda buf, k: C.c_void_p(buf.device.value + k)
+        for fn, out, bad in ((lib.lbvh_trace_closest, q.hits, 8), (lib.lbvh_trace_occluded, q.flags, 2)):
+            assert fn(h, None, len(rays), C.byref(s), out.device) == -1
+            assert fn(h, q.rays.device, len(rays), None, out.device) == -1
+            assert fn(h, q.rays.device, len(rays), C.byref(s), None) == -1
+            assert fn(h, p(q.rays, 32), 10, C.byref(s), out.device) == 0          # rays 1 .. 10: 16-byte aligned
+            assert fn(h, p(q.rays, 4), 10, C.byref(s), out.device) == -1
+            assert fn(h, q.rays.device, 10, C.byref(s), p(out, bad)) == -1
+            assert fn(h, q.rays.device, 1 << 32, C.byref(s), out.device) == -1
+            assert fn(None, q.rays.device, 10, C.byref(s), out.device) == -1
+        # count == 0: a no-op, the outputs untouched
+        q.hits.fill_u32(0x7FC00000)
+        q.flags.fill_u32(0xDEADBEEF)
+        assert lib.lbvh_trace_closest(h, q.rays.device, 0, C.byref(s), q.hits.device) == 0
+        assert lib.lbvh_trace_occluded(h, q.rays.device, 0, C.byref(s), q.flags.device) == 0
+        assert (words(q.hits.get_data()) == 0x7FC00000).all() and (q.flags.get_data() == 0xDEADBEEF).all()
+        # a stale scene: triangles uploaded without a rebuild
+        d.container.triangle_data.sync()
+        for fn, out in ((lib.lbvh_trace_closest, q.hits), (lib.lbvh_trace_occluded, q.flags)):
+            assert fn(h, q.rays.device, len(rays), C.byref(s), out.device) == -1
+            assert b"stale" in lib.lbvh_last_error(h)
+        d.rebuild(fast=True)
+        assert (words(q.closest()) == words(want)).all()
+        q.dispose()
+        d.on_destroy()
+    finally:
+        c2.close()
+
+
+@pytest.mark.gpu
+def test_path_tracer_frame_undisturbed_by_queries_between_bounces(ctx):
+    tris, body, centres = scenes.tiled_torus(nu=24, nv=16, grid=2, with_bodies=True)
+    pt = H().DynamicPathTracer(ctx, tris, body, centres, t_min=1e-3, albedo=0.7, seed=5)
+    pt.animate(0.05)
+    cam_d = scenes.camera(160, 96, (0.0, 0.0, 110.0))
+    pt.render(cam_d, bounces=4)
+    img0 = pt.image()
+    st0 = pt.states.get_data()[: 160 * 96].copy()
+    # the same frame with both queries issued between the bounces, on buffers of their own and 4x the frame's count: the
+    # ray scratch grows in the middle of the frame
+    big = _random_ray_states(tris, 4 * 160 * 96, seed=12)
+    rays = make_rays(big["origin"], big["dir"], np.float32(1e-3), np.float32(60.0))
+    q = Queries(ctx, pt.drawer, rays)
+    cam = N().Camera.from_dict(cam_d)
+    count = 160 * 96
+    h, s = ctx.handle, pt.drawer.container.scene()
+    lib = N().lib
+
+    def queries():
+        pt.drawer.trace_closest(q.rays, q.hits)
+        pt.drawer.trace_occluded(q.rays, q.flags)
+
+    N().check(h, lib.lbvh_trace_primary(h, C.byref(cam), 0, 0, 160, 96, C.byref(s), L.TRACE_FAST, pt.hits.device, None))
+    queries()
+    N().check(h, lib.lbvh_path_first_bounce(h, C.byref(cam), C.byref(s), pt.states.device, pt.hits.device, 5, 0.7, 1e-3))
+    for bnc in range(1, 4):
+        queries()
+        N().check(h, lib.lbvh_path_bounce(h, C.byref(s), pt.states.device, pt.hits.device, count, bnc, 5, 0.7, 1e-3))
+    queries()
+    N().check(h, lib.lbvh_path_scatter(h, C.byref(s), pt.hits.device, count, 4, 5, 0.7, pt.states.device))
+    N().check(h, lib.lbvh_path_resolve(h, pt.states.device, count, pt.image_buf.device))
+    img1 = pt.image()
+    st1 = pt.states.get_data()[:count]
+    assert (words(st1) == words(st0)).all()
+    assert (img1.view(np.uint16) == img0.view(np.uint16)).all()
+    q.dispose()
+    pt.drawer.on_destroy()
+
+
+@pytest.mark.gpu
+def test_cfg2_full_frame_shadow_rays_and_cfg5_first_bounce(ctx):
+    W, Ht = 1920, 1080
+    tris = scenes.tiled_torus()
+    d = H().RaytracingMeshDrawer(ctx, tris).awake()
+    b = O.Built(tris, capacity=d.container.capacity, threads=8)
+    cam = scenes.camera(W, Ht, (0.0, 0.0, 250.0))
+    d.update(cam, mode=L.TRACE_FAST)
+    ph = d.hits().reshape(-1)
+    st = O.path_begin(cam)
+    hit = ph["t"] < L.MAX_FLOAT
+    origin = (st["origin"] + st["dir"] * ph["t"][:, None]).astype(np.float32)
+    rays = make_rays(origin, (LIGHT - origin).astype(np.float32), np.float32(1e-4), np.where(hit, np.float32(1.0), np.float32(0.0)))
+    q = Queries(ctx, d, rays)
+    occ = q.occluded()
+    want = expect_occluded(rays, oracle_unbounded(b, rays))                        # E3 on every pixel of the frame
+    assert (occ == want).all()
+    assert 0 < occ.sum() < hit.sum()
+    q.dispose()
+    d.on_destroy()
+    # cfg5's first-bounce rays: closest(+inf) == lbvh_trace_rays on the whole frame, word for word
+    tris, body, centres = scenes.tiled_torus(with_bodies=True)
+    pt = H().DynamicPathTracer(ctx, tris, body, centres, t_min=1e-3, albedo=0.7, seed=9)
+    pt.animate(0.03)
+    pt.render(cam, bounces=1)              # allocates the buffers; the states below are re-made from the primary hits
+    c_ = N().Camera.from_dict(cam)
+    h, s = ctx.handle, pt.drawer.container.scene()
+    N().check(h, N().lib.lbvh_trace_primary(h, C.byref(c_), 0, 0, W, Ht, C.byref(s), L.TRACE_FAST, pt.hits.device, None))
+    N().check(h, N().lib.lbvh_path_first_bounce(h, C.byref(c_), C.byref(s), pt.states.device, pt.hits.device, 9, 0.7, 1e-3))
+    states = pt.states.get_data()[: W * Ht].copy()
+    ref = trace_rays(ctx, pt.drawer, states, 1e-3)
+    live = states["alive"] != 0
+    assert 0.2 < live.mean() < 0.9
+    rays = make_rays(states["origin"], states["dir"], np.float32(1e-3), np.where(live, np.float32(np.inf), np.float32(0.0)))
+    q = Queries(ctx, pt.drawer, rays)
+    assert (words(q.closest()) == words(ref)).all()
+    q.dispose()
+    pt.drawer.on_destroy()
+
+
+def _splitmix_mesh(n):
+    """The mesh lbvh_driver.cpp generates (SplitMix64, seed 1)."""
+    mask = (1 << 64) - 1
+    state = 1
+    out = np.zeros((n, 3, 3), dtype=np.float32)
+
+    def nxt():
+        nonlocal state
+        state = (state + 0x9E3779B97F4A7C15) & mask
+        z = state
+        z = ((z ^ (z >> 30)) * 0xBF58476D1CE4E5B9) & mask
+        z = ((z ^ (z >> 27)) * 0x94D049BB133111EB) & mask
+        return z ^ (z >> 31)
+
+    def uni(lo, hi):
+        return np.float32(lo) + np.float32(hi - lo) * np.float32((nxt() >> 40) * (1.0 / 16777216.0))
+
+    for i in range(n):
+        for k in range(3):
+            c = uni(-100.0, 100.0)
+            out[i, 0, k] = c
+            out[i, 1, k] = np.float32(c + uni(-2.0, 2.0))
+            out[i, 2, k] = np.float32(c + uni(-2.0, 2.0))
+    return out
+
+
+@pytest.mark.gpu
+def test_cpp_host_driver_rays_matches_oracle():
+    exe = os.path.join(ROOT, "unitysimpleraytracing_amd", "host", "lbvh_driver")
+    assert os.path.exists(exe), "build it with __graft_entry__.build()"
+    res = json.loads(subprocess.run([exe, "rays", "4096", "256", "256"], check=True, capture_output=True, text=True).stdout)
+    pos = _splitmix_mesh(4096)
+    tris = np.zeros(4096, dtype=L.TRIANGLE)
+    tris["a"], tris["b"], tris["c"] = pos[:, 0], pos[:, 1], pos[:, 2]
+    b = O.Built(tris, capacity=4096, threads=8)
+    cam = scenes.camera(256, 256, (0.0, 0.0, 300.0))
+    ph, _ = O.trace_primary(b, cam, threads=8, fast_rule=True)        # the t of the driver's LBVH_TRACE_FAST frame
+    ph = ph.reshape(-1)
+    st = O.path_begin(cam)
+    hit = ph["t"] < L.MAX_FLOAT
+    origin = (st["origin"] + st["dir"] * ph["t"][:, None]).astype(np.float32)
+    rays = make_rays(origin, (LIGHT - origin).astype(np.float32), np.float32(1e-4), np.where(hit, np.float32(1.0), np.float32(0.0)))
+    unb = oracle_unbounded(b, rays)
+    closest = expect_closest(rays, unb)
+    got = closest["t"] < L.MAX_FLOAT
+    assert res["rays"] == 256 * 256 and res["hits"] == int(got.sum()) > 0
+    assert abs(res["t_sum"] - float(closest["t"][got].astype(np.float64).sum())) < 1e-3
+    assert res["occluded"] == int(expect_occluded(rays, unb).sum())
+    assert res["e3_holds"] is True

@@ -4,6 +4,7 @@
 // Strict fp32 (-ffp-contract=off), no device trig, counter-based RNG.
 #include <algorithm>
 #include <cstdlib>
+#include <type_traits>
 #include "lbvh_common.h"
 #include "lbvh_rt.h"
 
@@ -112,10 +113,54 @@ static inline uint32_t* ray_list(lbvh_context* ctx, size_t count, uint32_t turn)
 static inline uint32_t* deep_stacks(lbvh_context* ctx, size_t count) { return (uint32_t*)((char*)ctx->ray_scratch + 256 + 2 * list_bytes(count)); }
 static inline size_t ray_scratch_bytes_for(size_t count) { return 256 + 2 * list_bytes(count) + deep_bytes(count); }
 
-__global__ __launch_bounds__(64) void trace_rays_kernel(const lbvh_path_state* __restrict__ states, const uint32_t* __restrict__ n_alive,
+// The three walkers below serve two ray sources and two queries (template arguments PLAIN, ANY):
+//   PLAIN = false: path states, the live ones listed in `list` (*n_alive of them), one t_min for all (lbvh_trace_rays, the bounces)
+//   PLAIN = true:  lbvh_ray records, ray k of the call to the lane directly (n_alive = the count), per-ray [t_min, t_max);
+//                  a ray with !(t_min < t_max) gets its result when it is loaded and leaves the lane idle for the next refill
+//   ANY = false:   the closest candidate's lbvh_hit; ANY = true: a uint32_t flag, 1 as soon as any candidate is accepted (the
+//                  closest-hit walk cut off there: the same near-first order, the rest of that step's leaves skipped)
+template <bool PLAIN> using walk_src = std::conditional_t<PLAIN, lbvh_ray, lbvh_path_state>;
+template <bool PLAIN> using walk_total = std::conditional_t<PLAIN, uint32_t, const uint32_t* __restrict__>;
+template <bool ANY> using walk_out = std::conditional_t<ANY, uint32_t, lbvh_hit>;
+__device__ __forceinline__ uint32_t walk_count(uint32_t count) { return count; }
+__device__ __forceinline__ uint32_t walk_count(const uint32_t* n_alive) { return *n_alive; }
+
+// plain ray k into the lane (lo = t_min, best_t = T): false (result written, lane stays idle) for an inactive ray
+template <bool ANY>
+__device__ __forceinline__ bool load_plain_ray(const lbvh_ray* __restrict__ rays, uint32_t k, ray_t& ray, float& lo, float& best_t,
+                                               walk_out<ANY>* __restrict__ out)
+{
+    const float4* r = reinterpret_cast<const float4*>(&rays[k]);
+    const float4 o = r[0], d = r[1];
+    ray.ox = o.x; ray.oy = o.y; ray.oz = o.z;
+    ray.dx = d.x; ray.dy = d.y; ray.dz = d.z;
+    ray.ix = 1.0f / d.x; ray.iy = 1.0f / d.y; ray.iz = 1.0f / d.z;
+    lo = o.w;
+    best_t = fminf(d.w, LBVH_MAX_FLOAT);                 // T: candidates lie in (t_min, T)
+    if (o.w < d.w) return true;                          // false for NaN bounds too
+    if constexpr (ANY) out[k] = 0u;
+    else reinterpret_cast<float4*>(out)[k] = make_float4(LBVH_MAX_FLOAT, __uint_as_float(0u), 0.0f, 0.0f);
+    return false;
+}
+
+// a finished closest-hit walk's record; a plain ray that accepted nothing still holds best_t = min(t_max, MAX_FLOAT): the miss
+// record instead (a lane mask, `took`, says which: the bound itself would take one more VGPR for the whole walk)
+template <bool PLAIN>
+__device__ __forceinline__ void put_hit(lbvh_hit* __restrict__ hits, size_t i, float best_t, bool took, uint32_t best_tri, float best_u, float best_v)
+{
+    float4 out;
+    out.x = PLAIN && !took ? LBVH_MAX_FLOAT : best_t;
+    out.y = __uint_as_float(best_tri);
+    out.z = best_u;
+    out.w = best_v;
+    reinterpret_cast<float4*>(hits)[i] = out;
+}
+
+template <bool PLAIN, bool ANY>
+__global__ __launch_bounds__(64) void trace_rays_kernel(const walk_src<PLAIN>* __restrict__ states, walk_total<PLAIN> n_alive,
                                                         const uint32_t* __restrict__ list, float t_min,
                                                         const lbvh_fast_node* __restrict__ nodes,
-                                                        const lbvh_fast_tri* __restrict__ tris, lbvh_hit* __restrict__ hits,
+                                                        const lbvh_fast_tri* __restrict__ tris, walk_out<ANY>* __restrict__ hits,
                                                         uint32_t* __restrict__ deep,     // [gridDim.x][kRayStackDeep][64]
                                                         uint32_t lds_depth,              // <= kRayStackLds
                                                         uint32_t deep_cap,               // <= kRayStackDeep (lbvh_debug_ray_stack_limit lowers it)
@@ -124,7 +169,7 @@ __global__ __launch_bounds__(64) void trace_rays_kernel(const lbvh_path_state* _
     __shared__ uint32_t s_stack[kRayStackLds][LBVH_WAVE];
     uint32_t* my_deep = deep + (size_t)blockIdx.x * (kRayStackDeep * LBVH_WAVE) + threadIdx.x;
     const uint32_t lane = threadIdx.x;
-    const uint32_t total = *n_alive;
+    const uint32_t total = walk_count(n_alive);
     // at least 32 rays per wave: with fewer live rays than lanes on the chip, half-filled waves on every wave slot hide more
     // latency than full waves on half of them (4 bounces: 1.487 -> 1.443 ms; 64: 1.487, 16: 1.449, 96 / 128 / 192: 1.71 / 1.91 / 2.43)
     const uint32_t run = max((total + gridDim.x - 1) / gridDim.x, 32u);
@@ -135,6 +180,8 @@ __global__ __launch_bounds__(64) void trace_rays_kernel(const lbvh_path_state* _
     bool active = false;
     size_t i = 0;
     ray_t ray = {};
+    float lo = t_min;                                    // the ray's t_min (plain rays: best_t starts at min(t_max, MAX_FLOAT))
+    bool took = false;                                   // plain rays: a candidate was accepted (else best_t is still that bound)
     float best_t = LBVH_MAX_FLOAT, best_u = 0.0f, best_v = 0.0f;
     uint32_t best_tri = 0, sp = 0, node = 0;
     for (;;) {
@@ -144,20 +191,27 @@ __global__ __launch_bounds__(64) void trace_rays_kernel(const lbvh_path_state* _
             if (!active) {
                 const uint32_t k = next + mbcnt64(idle);
                 if (k < end) {
-                    i = list[k];
-                    const float4* st = reinterpret_cast<const float4*>(&states[i]);
-                    const float4 o = st[0], d = st[1];
-                    ray.ox = o.x; ray.oy = o.y; ray.oz = o.z;
-                    ray.dx = d.x; ray.dy = d.y; ray.dz = d.z;
-                    ray.ix = 1.0f / d.x; ray.iy = 1.0f / d.y; ray.iz = 1.0f / d.z;
-                    best_t = LBVH_MAX_FLOAT; best_tri = 0; best_u = 0.0f; best_v = 0.0f;
-                    sp = 0; node = 0;
-                    active = true;
+                    if constexpr (PLAIN) {
+                        i = k;
+                        active = load_plain_ray<ANY>(states, k, ray, lo, best_t, hits);
+                        best_tri = 0; best_u = 0.0f; best_v = 0.0f; took = false;
+                        sp = 0; node = 0;
+                    } else {
+                        i = list[k];
+                        const float4* st = reinterpret_cast<const float4*>(&states[i]);
+                        const float4 o = st[0], d = st[1];
+                        ray.ox = o.x; ray.oy = o.y; ray.oz = o.z;
+                        ray.dx = d.x; ray.dy = d.y; ray.dz = d.z;
+                        ray.ix = 1.0f / d.x; ray.iy = 1.0f / d.y; ray.iz = 1.0f / d.z;
+                        best_t = LBVH_MAX_FLOAT; best_tri = 0; best_u = 0.0f; best_v = 0.0f;
+                        sp = 0; node = 0;
+                        active = true;
+                    }
                 }
             }
             next += (uint32_t)__popcll(idle);
         }
-        if (!__any(active)) break;
+        if (!__any(active) && (!PLAIN || next >= end)) break;      // (plain rays: a whole refill can be inactive rays)
         if (active) {
             const float4* nb = reinterpret_cast<const float4*>(&nodes[node]);
             const float4 lmin = nb[0], lmax = nb[1], rmin = nb[2], rmax = nb[3];
@@ -165,22 +219,29 @@ __global__ __launch_bounds__(64) void trace_rays_kernel(const lbvh_path_state* _
             float tl, tr;
             bool hit_l = ray_box(lmin, lmax, ray, tl) && !(tl > best_t);
             bool hit_r = ray_box(rmin, rmax, ray, tr) && !(tr > best_t);
+            bool found = false;                          // ANY: a candidate was accepted
 #pragma unroll
             for (int side = 0; side < 2; side++) {
                 const bool h = side == 0 ? hit_l : hit_r;
                 const uint32_t ref = side == 0 ? lref : rref;
-                if (h && (ref & 0x80000000u)) {
+                if (h && (ref & 0x80000000u) && !found) {
                     float4 v0, v1, v2;
                     unpack_fast_triangle(reinterpret_cast<const float4*>(&nodes[ref & 0x7FFFFFFFu]), v0, v1, v2);   // a triangle line
                     float u = 0.0f, v = 0.0f;
                     const float dist = ray_fast_triangle(ray, v0, v1, v2, u, v);
                     const uint32_t tri = __float_as_uint(v0.w);
-                    if (dist > t_min && hit_counts(dist, side == 0 ? tl : tr) && (dist < best_t || (dist == best_t && tri < best_tri))) { best_t = dist; best_tri = tri; best_u = u; best_v = v; }
+                    if (dist > lo && hit_counts(dist, side == 0 ? tl : tr) && (dist < best_t || (dist == best_t && tri < best_tri))) {
+                        if constexpr (ANY) found = true;
+                        else { best_t = dist; best_tri = tri; best_u = u; best_v = v; took = true; }
+                    }
                 }
             }
             const bool go_l = hit_l && !(lref & 0x80000000u) && !(tl > best_t);
             const bool go_r = hit_r && !(rref & 0x80000000u) && !(tr > best_t);
-            if (go_l && go_r) {
+            if (ANY && found) {
+                if constexpr (ANY) hits[i] = 1u;
+                active = false;
+            } else if (go_l && go_r) {
                 const bool l_near = tl <= tr;
                 node = l_near ? lref : rref;
                 const uint32_t far = l_near ? rref : lref;
@@ -195,12 +256,8 @@ __global__ __launch_bounds__(64) void trace_rays_kernel(const lbvh_path_state* _
                 sp--;
                 node = sp < lds_depth ? s_stack[sp][lane] : my_deep[(sp - lds_depth) * LBVH_WAVE];
             } else {
-                float4 out;
-                out.x = best_t;
-                out.y = __uint_as_float(best_tri);
-                out.z = best_u;
-                out.w = best_v;
-                reinterpret_cast<float4*>(hits)[i] = out;
+                if constexpr (ANY) hits[i] = 0u;
+                else put_hit<PLAIN>(hits, i, best_t, took, best_tri, best_u, best_v);
                 active = false;
             }
         }
@@ -309,11 +366,11 @@ __device__ __forceinline__ void add_ray_stats(lbvh_ray_stats* stats, uint32_t ra
 }
 
 // Same frame as trace_rays_kernel (lane refill from the wave's run of live rays, LDS + device-memory stack).
-template <bool STATS>
-__global__ __launch_bounds__(64) void trace_rays_wide_kernel(const lbvh_path_state* __restrict__ states, const uint32_t* __restrict__ n_alive,
+template <bool PLAIN, bool ANY, bool STATS>
+__global__ __launch_bounds__(64) void trace_rays_wide_kernel(const walk_src<PLAIN>* __restrict__ states, walk_total<PLAIN> n_alive,
                                                              const uint32_t* __restrict__ list, float t_min,
                                                              const lbvh_wide_node* __restrict__ wide,
-                                                             const lbvh_fast_node* __restrict__ lines, lbvh_hit* __restrict__ hits,
+                                                             const lbvh_fast_node* __restrict__ lines, walk_out<ANY>* __restrict__ hits,
                                                              uint32_t* __restrict__ deep,     // [gridDim.x][kWideStackDeep][64]
                                                              uint32_t lds_depth,              // <= kWideStackLds
                                                              uint32_t deep_cap,               // <= kWideStackDeep
@@ -322,7 +379,7 @@ __global__ __launch_bounds__(64) void trace_rays_wide_kernel(const lbvh_path_sta
     __shared__ uint32_t s_stack[kWideStackLds][LBVH_WAVE];
     uint32_t* my_deep = deep + (size_t)blockIdx.x * (kWideStackDeep * LBVH_WAVE) + threadIdx.x;
     const uint32_t lane = threadIdx.x;
-    const uint32_t total = *n_alive;
+    const uint32_t total = walk_count(n_alive);
     const uint32_t run = max((total + gridDim.x - 1) / gridDim.x, 32u);
     uint32_t next = blockIdx.x * run;
     if (next >= total) return;
@@ -332,6 +389,8 @@ __global__ __launch_bounds__(64) void trace_rays_wide_kernel(const lbvh_path_sta
     bool active = false;
     size_t i = 0;
     ray_t ray = {};
+    float lo = t_min;
+    bool took = false;
     float best_t = LBVH_MAX_FLOAT, best_u = 0.0f, best_v = 0.0f;
     uint32_t best_tri = 0, sp = 0, node = 0;
     auto push = [&](uint32_t ref) {
@@ -347,21 +406,29 @@ __global__ __launch_bounds__(64) void trace_rays_wide_kernel(const lbvh_path_sta
             if (!active) {
                 const uint32_t k = next + mbcnt64(idle);
                 if (k < end) {
-                    i = list[k];
-                    const float4* st = reinterpret_cast<const float4*>(&states[i]);
-                    const float4 o = st[0], d = st[1];
-                    ray.ox = o.x; ray.oy = o.y; ray.oz = o.z;
-                    ray.dx = d.x; ray.dy = d.y; ray.dz = d.z;
-                    ray.ix = 1.0f / d.x; ray.iy = 1.0f / d.y; ray.iz = 1.0f / d.z;
-                    best_t = LBVH_MAX_FLOAT; best_tri = 0; best_u = 0.0f; best_v = 0.0f;
-                    sp = 0; node = 0;
-                    active = true;
-                    if (STATS) n_rays++;
+                    if constexpr (PLAIN) {
+                        i = k;
+                        active = load_plain_ray<ANY>(states, k, ray, lo, best_t, hits);
+                        best_tri = 0; best_u = 0.0f; best_v = 0.0f; took = false;
+                        sp = 0; node = 0;
+                        if (STATS && active) n_rays++;
+                    } else {
+                        i = list[k];
+                        const float4* st = reinterpret_cast<const float4*>(&states[i]);
+                        const float4 o = st[0], d = st[1];
+                        ray.ox = o.x; ray.oy = o.y; ray.oz = o.z;
+                        ray.dx = d.x; ray.dy = d.y; ray.dz = d.z;
+                        ray.ix = 1.0f / d.x; ray.iy = 1.0f / d.y; ray.iz = 1.0f / d.z;
+                        best_t = LBVH_MAX_FLOAT; best_tri = 0; best_u = 0.0f; best_v = 0.0f;
+                        sp = 0; node = 0;
+                        active = true;
+                        if (STATS) n_rays++;
+                    }
                 }
             }
             next += (uint32_t)__popcll(idle);
         }
-        if (!__any(active)) break;
+        if (!__any(active) && (!PLAIN || next >= end)) break;
         if (active) {
             if (STATS) n_steps++;
             const float4* w = reinterpret_cast<const float4*>(&wide[node]);
@@ -375,6 +442,7 @@ __global__ __launch_bounds__(64) void trace_rays_wide_kernel(const lbvh_path_sta
             // leaf slots first: a lane's leaves one after the other, every lane's k-th at the same time
             uint32_t leaves = (h0 && (ref.x >> 31) ? 1u : 0u) | (h1 && (ref.y >> 31) ? 2u : 0u) | (h2 && (ref.z >> 31) ? 4u : 0u) |
                               (h3 && (ref.w >> 31) ? 8u : 0u);
+            bool found = false;                          // ANY: a candidate was accepted
             while (leaves != 0u) {
                 const uint32_t k = (uint32_t)__builtin_ctz(leaves);
                 leaves &= leaves - 1u;
@@ -386,7 +454,15 @@ __global__ __launch_bounds__(64) void trace_rays_wide_kernel(const lbvh_path_sta
                 const uint32_t tri = __float_as_uint(v0.w);
                 const float entry = k == 0u ? t0 : (k == 1u ? t1 : (k == 2u ? t2 : t3));
                 // ties go to the lower triangle index, whatever order the leaves are met in (as in the packet walk)
-                if (dist > t_min && hit_counts(dist, entry) && (dist < best_t || (dist == best_t && tri < best_tri))) { best_t = dist; best_tri = tri; best_u = u; best_v = v; }
+                if (dist > lo && hit_counts(dist, entry) && (dist < best_t || (dist == best_t && tri < best_tri))) {
+                    if constexpr (ANY) { found = true; break; }
+                    else { best_t = dist; best_tri = tri; best_u = u; best_v = v; took = true; }
+                }
+            }
+            if (ANY && found) {
+                if constexpr (ANY) hits[i] = 1u;
+                active = false;
+                continue;
             }
             // nodes to enter, ordered by entry distance: the order key is the distance's bit pattern (non-negative floats
             // order like integers) with the slot number in its two lowest bits
@@ -412,12 +488,8 @@ __global__ __launch_bounds__(64) void trace_rays_wide_kernel(const lbvh_path_sta
                 sp--;
                 node = sp < lds_depth ? s_stack[sp][lane] : my_deep[(sp - lds_depth) * LBVH_WAVE];
             } else {
-                float4 out;
-                out.x = best_t;
-                out.y = __uint_as_float(best_tri);
-                out.z = best_u;
-                out.w = best_v;
-                reinterpret_cast<float4*>(hits)[i] = out;
+                if constexpr (ANY) hits[i] = 0u;
+                else put_hit<PLAIN>(hits, i, best_t, took, best_tri, best_u, best_v);
                 active = false;
             }
         }
@@ -429,11 +501,11 @@ __global__ __launch_bounds__(64) void trace_rays_wide_kernel(const lbvh_path_sta
 // thousand live rays, most of the chip idle for most of the launch): the next node is chosen BEFORE the step's triangles are
 // tested and requested together with the first triangle line, so the two fetches of a step are in flight at once.  84 VGPRs
 // (5 waves per SIMD instead of 8): the price where every wave slot is needed, none where they are not.
-template <bool STATS>
-__global__ __launch_bounds__(64) void trace_rays_wide_chain_kernel(const lbvh_path_state* __restrict__ states, const uint32_t* __restrict__ n_alive,
+template <bool PLAIN, bool ANY, bool STATS>
+__global__ __launch_bounds__(64) void trace_rays_wide_chain_kernel(const walk_src<PLAIN>* __restrict__ states, walk_total<PLAIN> n_alive,
                                                              const uint32_t* __restrict__ list, float t_min,
                                                              const lbvh_wide_node* __restrict__ wide,
-                                                             const lbvh_fast_node* __restrict__ lines, lbvh_hit* __restrict__ hits,
+                                                             const lbvh_fast_node* __restrict__ lines, walk_out<ANY>* __restrict__ hits,
                                                              uint32_t* __restrict__ deep,     // [gridDim.x][kWideStackDeep][64]
                                                              uint32_t lds_depth,              // <= kWideStackLds
                                                              uint32_t deep_cap,               // <= kWideStackDeep
@@ -442,7 +514,7 @@ __global__ __launch_bounds__(64) void trace_rays_wide_chain_kernel(const lbvh_pa
     __shared__ uint32_t s_stack[kWideStackLds][LBVH_WAVE];
     uint32_t* my_deep = deep + (size_t)blockIdx.x * (kWideStackDeep * LBVH_WAVE) + threadIdx.x;
     const uint32_t lane = threadIdx.x;
-    const uint32_t total = *n_alive;
+    const uint32_t total = walk_count(n_alive);
     const uint32_t run = max((total + gridDim.x - 1) / gridDim.x, 32u);
     uint32_t next = blockIdx.x * run;
     if (next >= total) return;
@@ -452,6 +524,8 @@ __global__ __launch_bounds__(64) void trace_rays_wide_chain_kernel(const lbvh_pa
     bool active = false, have = false;      // have: the registers below hold this lane's node
     uint32_t i = 0;                          // (lbvh_trace_rays: count <= 2^32 - 1)
     ray_t ray = {};
+    float lo = t_min;
+    bool took = false;
     float best_t = LBVH_MAX_FLOAT, best_u = 0.0f, best_v = 0.0f;
     uint32_t best_tri = 0, sp = 0, node = 0;
     float4 lox = {}, loy = {}, loz = {}, hix = {}, hiy = {}, hiz = {};
@@ -473,21 +547,30 @@ __global__ __launch_bounds__(64) void trace_rays_wide_chain_kernel(const lbvh_pa
             if (!active) {
                 const uint32_t k = next + mbcnt64(idle);
                 if (k < end) {
-                    i = list[k];
-                    const float4* st = reinterpret_cast<const float4*>(&states[i]);
-                    const float4 o = st[0], d = st[1];
-                    ray.ox = o.x; ray.oy = o.y; ray.oz = o.z;
-                    ray.dx = d.x; ray.dy = d.y; ray.dz = d.z;
-                    ray.ix = 1.0f / d.x; ray.iy = 1.0f / d.y; ray.iz = 1.0f / d.z;
-                    best_t = LBVH_MAX_FLOAT; best_tri = 0; best_u = 0.0f; best_v = 0.0f;
-                    sp = 0; node = 0;
-                    active = true; have = false;
-                    if (STATS) n_rays++;
+                    if constexpr (PLAIN) {
+                        i = k;
+                        active = load_plain_ray<ANY>(states, k, ray, lo, best_t, hits);
+                        best_tri = 0; best_u = 0.0f; best_v = 0.0f; took = false;
+                        sp = 0; node = 0;
+                        have = false;
+                        if (STATS && active) n_rays++;
+                    } else {
+                        i = list[k];
+                        const float4* st = reinterpret_cast<const float4*>(&states[i]);
+                        const float4 o = st[0], d = st[1];
+                        ray.ox = o.x; ray.oy = o.y; ray.oz = o.z;
+                        ray.dx = d.x; ray.dy = d.y; ray.dz = d.z;
+                        ray.ix = 1.0f / d.x; ray.iy = 1.0f / d.y; ray.iz = 1.0f / d.z;
+                        best_t = LBVH_MAX_FLOAT; best_tri = 0; best_u = 0.0f; best_v = 0.0f;
+                        sp = 0; node = 0;
+                        active = true; have = false;
+                        if (STATS) n_rays++;
+                    }
                 }
             }
             next += (uint32_t)__popcll(idle);
         }
-        if (!__any(active)) break;
+        if (!__any(active) && (!PLAIN || next >= end)) break;
         uint32_t leaves = 0u;
         uint4 leaf_ref = {};
         float4 leaf_entry = {};
@@ -544,6 +627,7 @@ __global__ __launch_bounds__(64) void trace_rays_wide_chain_kernel(const lbvh_pa
             ref = reinterpret_cast<const uint4*>(w)[6];
             have = true;
         }
+        bool found = false;                          // ANY: a candidate was accepted
         while (leaves != 0u) {
             const uint32_t slot = (uint32_t)__builtin_ctz(leaves);
             const float entry = slot == 0u ? leaf_entry.x : (slot == 1u ? leaf_entry.y : (slot == 2u ? leaf_entry.z : leaf_entry.w));
@@ -553,19 +637,21 @@ __global__ __launch_bounds__(64) void trace_rays_wide_chain_kernel(const lbvh_pa
             const float dist = ray_triangle_edges(ray, q0, q2.x, q2.y, q2.z, q1.w, q2.w, q3.w, u, v);
             const uint32_t tri = __float_as_uint(q0.w);
             // ties go to the lower triangle index, whatever order the leaves are met in (as in the packet walk)
-            if (dist > t_min && hit_counts(dist, entry) && (dist < best_t || (dist == best_t && tri < best_tri))) { best_t = dist; best_tri = tri; best_u = u; best_v = v; }
+            if (dist > lo && hit_counts(dist, entry) && (dist < best_t || (dist == best_t && tri < best_tri))) {
+                if constexpr (ANY) { found = true; break; }
+                else { best_t = dist; best_tri = tri; best_u = u; best_v = v; took = true; }
+            }
             if (leaves != 0u) {
                 const float4* line = reinterpret_cast<const float4*>(&lines[pick4(leaf_ref, (uint32_t)__builtin_ctz(leaves)) & 0x7FFFFFFFu]);
                 q0 = line[0]; q1 = line[1]; q2 = line[2]; q3 = line[3];
             }
         }
-        if (done) {
-            float4 out;
-            out.x = best_t;
-            out.y = __uint_as_float(best_tri);
-            out.z = best_u;
-            out.w = best_v;
-            reinterpret_cast<float4*>(hits)[i] = out;
+        if (ANY && found) {
+            if constexpr (ANY) hits[i] = 1u;
+            active = false;
+        } else if (done) {
+            if constexpr (ANY) hits[i] = 0u;
+            else put_hit<PLAIN>(hits, i, best_t, took, best_tri, best_u, best_v);
             active = false;
         }
     }
@@ -738,11 +824,12 @@ __global__ __launch_bounds__(256) void path_resolve_kernel(const lbvh_path_state
 
 static_assert(sizeof(lbvh_path_state) == 64, "path state must be 64 bytes");
 
-// the walk over the live rays of `list`: four-wide nodes (made on first use after a rebuild) — few_rays: with the kernel that
-// keeps two fetches of a step in flight (the later bounces of a frame) —, or the binary nodes the packet walk uses
-// (lbvh_debug_ray_walker(ctx, 0): the cross-check of the tests; 2: the few-rays kernel for every launch)
-static lbvh_status launch_ray_walk(lbvh_context* ctx, const lbvh_path_state* d_states, const uint32_t* n_alive, const uint32_t* list,
-                                   float t_min, lbvh_hit* d_hits, size_t count, bool few_rays = false)
+// the walk over the live rays of `list` (or over plain rays, PLAIN: `total` is their count): four-wide nodes (made on first use
+// after a rebuild) — few_rays: with the kernel that keeps two fetches of a step in flight (the later bounces of a frame) —, or the
+// binary nodes the packet walk uses (lbvh_debug_ray_walker(ctx, 0): the cross-check of the tests; 2: the few-rays kernel for every launch)
+template <bool PLAIN, bool ANY>
+static lbvh_status launch_ray_walk(lbvh_context* ctx, const walk_src<PLAIN>* d_states, walk_total<PLAIN> n_alive, const uint32_t* list,
+                                   float t_min, walk_out<ANY>* d_hits, size_t count, bool few_rays = false)
 {
     const uint32_t ray_waves = ray_waves_of(count);
     if (ctx->ray_walker != 0u) {
@@ -758,24 +845,45 @@ static lbvh_status launch_ray_walk(lbvh_context* ctx, const lbvh_path_state* d_s
         lbvh_ray_stats* st = ctx->ray_stats;
         const lbvh_wide_node* wn = (const lbvh_wide_node*)ctx->wide_nodes;
         if (few_rays || ctx->ray_walker == 2u) {
-            if (st) LBVH_LAUNCH(ctx, trace_rays_wide_chain_kernel<true>, dim3(ray_waves), dim3(LBVH_WAVE), d_states, n_alive, list, t_min, wn, ctx->fast_nodes,
-                                d_hits, deep_stacks(ctx, count), lds, deep_cap, ctx->fault_dev, st);
-            else LBVH_LAUNCH(ctx, trace_rays_wide_chain_kernel<false>, dim3(ray_waves), dim3(LBVH_WAVE), d_states, n_alive, list, t_min, wn, ctx->fast_nodes,
-                             d_hits, deep_stacks(ctx, count), lds, deep_cap, ctx->fault_dev, st);
+            if (st) LBVH_LAUNCH(ctx, (trace_rays_wide_chain_kernel<PLAIN, ANY, true>), dim3(ray_waves), dim3(LBVH_WAVE), d_states, n_alive, list, t_min, wn,
+                                ctx->fast_nodes, d_hits, deep_stacks(ctx, count), lds, deep_cap, ctx->fault_dev, st);
+            else LBVH_LAUNCH(ctx, (trace_rays_wide_chain_kernel<PLAIN, ANY, false>), dim3(ray_waves), dim3(LBVH_WAVE), d_states, n_alive, list, t_min, wn,
+                             ctx->fast_nodes, d_hits, deep_stacks(ctx, count), lds, deep_cap, ctx->fault_dev, st);
         } else {
-            if (st) LBVH_LAUNCH(ctx, trace_rays_wide_kernel<true>, dim3(ray_waves), dim3(LBVH_WAVE), d_states, n_alive, list, t_min, wn, ctx->fast_nodes,
-                                d_hits, deep_stacks(ctx, count), lds, deep_cap, ctx->fault_dev, st);
-            else LBVH_LAUNCH(ctx, trace_rays_wide_kernel<false>, dim3(ray_waves), dim3(LBVH_WAVE), d_states, n_alive, list, t_min, wn, ctx->fast_nodes,
-                             d_hits, deep_stacks(ctx, count), lds, deep_cap, ctx->fault_dev, st);
+            if (st) LBVH_LAUNCH(ctx, (trace_rays_wide_kernel<PLAIN, ANY, true>), dim3(ray_waves), dim3(LBVH_WAVE), d_states, n_alive, list, t_min, wn,
+                                ctx->fast_nodes, d_hits, deep_stacks(ctx, count), lds, deep_cap, ctx->fault_dev, st);
+            else LBVH_LAUNCH(ctx, (trace_rays_wide_kernel<PLAIN, ANY, false>), dim3(ray_waves), dim3(LBVH_WAVE), d_states, n_alive, list, t_min, wn,
+                             ctx->fast_nodes, d_hits, deep_stacks(ctx, count), lds, deep_cap, ctx->fault_dev, st);
         }
     } else {
-        LBVH_LAUNCH(ctx, trace_rays_kernel, dim3(ray_waves), dim3(LBVH_WAVE), d_states, n_alive, list, t_min, ctx->fast_nodes,
+        LBVH_LAUNCH(ctx, (trace_rays_kernel<PLAIN, ANY>), dim3(ray_waves), dim3(LBVH_WAVE), d_states, n_alive, list, t_min, ctx->fast_nodes,
                     ctx->fast_tris, d_hits, deep_stacks(ctx, count), ctx->ray_stack_lds, std::min<uint32_t>(ctx->ray_stack_deep, kRayStackDeep), ctx->fault_dev);
     }
     LBVH_HIP_TRY(ctx, hipGetLastError());
     return LBVH_OK;
 }
 
+// lbvh_trace_closest / lbvh_trace_occluded: plain rays by direct index, no live-ray list
+template <bool ANY>
+static lbvh_status trace_plain_rays(lbvh_context* ctx, const lbvh_ray* d_rays, size_t count, const lbvh_scene* h_scene,
+                                    walk_out<ANY>* d_out, const char* who)
+{
+    if (!ctx) return LBVH_ERR_INVALID_ARG;
+    if (count == 0) return LBVH_OK;
+    LBVH_REQUIRE(ctx, d_rays != nullptr && h_scene != nullptr && d_out != nullptr);
+    LBVH_REQUIRE(ctx, ((uintptr_t)d_rays & 15) == 0 && ((uintptr_t)d_out & (ANY ? 3 : 15)) == 0);
+    LBVH_REQUIRE(ctx, count <= 0xFFFFFFFFull);
+    {
+        const int frc = lbvh_require_fast(ctx, *h_scene, who);
+        if (frc != LBVH_OK) return frc;
+    }
+    LBVH_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    // only the deep stack slabs of the scratch are used, laid out as for lbvh_trace_rays (whose live-path list they may overwrite)
+    int rc = lbvh_reserve(ctx, &ctx->ray_scratch, &ctx->ray_scratch_bytes, ray_scratch_bytes_for(count));
+    if (rc != LBVH_OK) return rc;
+    ctx->ray_list.valid = false;
+    return launch_ray_walk<true, ANY>(ctx, d_rays, (uint32_t)count, nullptr, 0.0f, d_out, count);
+}
 
 extern "C" {
 
@@ -830,7 +938,17 @@ lbvh_status lbvh_trace_rays(lbvh_context* ctx, const lbvh_path_state* d_states, 
     uint32_t* list = ray_list(ctx, count, 0);
     LBVH_HIP_TRY(ctx, hipMemsetAsync(n_alive, 0, 4, ctx->cur_stream));
     LBVH_LAUNCH(ctx, alive_rays_kernel, dim3((unsigned)((count + 255) / 256)), dim3(256), d_states, count, n_alive, list, d_hits);
-    return launch_ray_walk(ctx, d_states, n_alive, list, t_min, d_hits, count);
+    return launch_ray_walk<false, false>(ctx, d_states, n_alive, list, t_min, d_hits, count);
+}
+
+lbvh_status lbvh_trace_closest(lbvh_context* ctx, const lbvh_ray* d_rays, size_t count, const lbvh_scene* h_scene, lbvh_hit* d_hits)
+{
+    return trace_plain_rays<false>(ctx, d_rays, count, h_scene, d_hits, "lbvh_trace_closest");
+}
+
+lbvh_status lbvh_trace_occluded(lbvh_context* ctx, const lbvh_ray* d_rays, size_t count, const lbvh_scene* h_scene, uint32_t* d_occluded)
+{
+    return trace_plain_rays<true>(ctx, d_rays, count, h_scene, d_occluded, "lbvh_trace_occluded");
 }
 
 lbvh_status lbvh_debug_ray_walker(lbvh_context* ctx, uint32_t walker)
@@ -931,7 +1049,7 @@ static lbvh_status path_bounce_impl(lbvh_context* ctx, const lbvh_scene* h_scene
     ctx->ray_list.states = d_states; ctx->ray_list.hits = d_hits; ctx->ray_list.count = count;
     ctx->ray_list.bounce = h_first_camera ? 0u : bounce;
     ctx->ray_list.turn = turn;
-    return launch_ray_walk(ctx, d_states, n_alive, list, t_min, d_hits, count, bounce >= 1u);
+    return launch_ray_walk<false, false>(ctx, d_states, n_alive, list, t_min, d_hits, count, bounce >= 1u);
 }
 
 extern "C" {

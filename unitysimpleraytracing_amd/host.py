@@ -351,6 +351,21 @@ class RaytracingMeshDrawer:
         N.check(self.ctx.handle, N.lib.lbvh_build_fast_scene(self.ctx.handle, C.byref(s), c.box_min.ctypes.data_as(f3),
                                                              c.box_max.ctypes.data_as(f3)))
 
+    def trace_closest(self, rays, hits):
+        """Closest hit of each ray of the DataBuffer `rays` (layouts.RAY: origin, t_min, dir, t_max) into the DataBuffer `hits`
+        (layouts.HIT), over the derived scene (awake(fast=True) / rebuild(fast=True)).  Asynchronous; read with hits.get_data()."""
+        self._trace_plain(N.lib.lbvh_trace_closest, rays, hits, L.HIT)
+
+    def trace_occluded(self, rays, flags):
+        """1 into the uint32 DataBuffer `flags` for each ray of `rays` that meets anything in (t_min, t_max), else 0."""
+        self._trace_plain(N.lib.lbvh_trace_occluded, rays, flags, np.dtype(np.uint32))
+
+    def _trace_plain(self, fn, rays, out, dtype):
+        if rays.dtype != L.RAY or out.dtype != dtype or out.size < rays.size:
+            raise ValueError(f"rays must be a DataBuffer of layouts.RAY and the output one of {dtype} with at least as many entries")
+        s = self.container.scene()
+        N.check(self.ctx.handle, fn(self.ctx.handle, rays.device, rays.size, C.byref(s), out.device))
+
     def update(self, camera, rect=None, mode=L.TRACE_FAST, stats=False):
         """Enqueue one frame (or the sub-rectangle (x0, y0, x1, y1) of it).  Returns the device
         hit buffer; read it back with hits()."""

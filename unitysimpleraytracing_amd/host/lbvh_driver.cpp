@@ -9,6 +9,11 @@
 //     lbvh_driver sort <ranks> [n] [replicate]   n pairs in uneven blocks over <ranks> contexts sorted by ONE
 //                                                lbvh_sort_pairs_sharded call (MultiGpuSorter), compared word for word
 //                                                with lbvh_sort_pairs on one context; prints JSON with "equal"
+//     lbvh_driver rays [n] [w] [h]               the cfg1 mesh and camera; from every primary hit a shadow ray toward the
+//                                                light (0, 250, 150): dir = light - hit point (not normalised), t in
+//                                                (1e-4, 1); pixels without a hit give inactive rays.  TraceClosest with
+//                                                t_max = 1 and = +inf, TraceOccluded; prints the hit count and t sum of the
+//                                                first, the occluded count and whether occluded == (t(+inf) < 1) on every ray
 #include <chrono>
 #include <cmath>
 #include <cstdio>
@@ -186,8 +191,71 @@ static int sort_main(int argc, char** argv)
     }
 }
 
+static int rays_main(int argc, char** argv)
+{
+    const uint32_t n = argc > 2 ? (uint32_t)atoi(argv[2]) : 4096;
+    const int w = argc > 3 ? atoi(argv[3]) : 256, h = argc > 4 ? atoi(argv[4]) : 256;
+    const size_t count = (size_t)w * h;
+    const float light[3] = {0.0f, 250.0f, 150.0f};
+    try {
+        lbvh::Context ctx(0);
+        lbvh::RaytracingMeshDrawer drawer(ctx, random_mesh(n));
+        drawer.Awake();
+        const lbvh_camera cam = camera_at(w, h, 300.0f);
+        drawer.Update(cam, LBVH_TRACE_FAST);
+        lbvh::DataBuffer<lbvh_path_state> primary(ctx, count);          // the camera rays, as the primary trace made them
+        lbvh::check(ctx.get(), lbvh_path_begin(ctx.get(), &cam, (lbvh_path_state*)primary.DeviceBuffer()));
+        primary.GetData();
+        drawer.Hits().GetData();
+        lbvh::DataBuffer<lbvh_ray> rays(ctx, count);
+        for (size_t i = 0; i < count; i++) {
+            const lbvh_path_state& p = primary.LocalBuffer()[i];
+            const float t = drawer.Hits().LocalBuffer()[i].t;
+            lbvh_ray& r = rays.LocalBuffer()[i];
+            std::memset(&r, 0, sizeof r);                                 // t_min = t_max = 0: inactive
+            if (!(t < LBVH_MAX_FLOAT)) continue;
+            for (int k = 0; k < 3; k++) {
+                r.origin[k] = p.origin[k] + p.dir[k] * t;
+                r.dir[k] = light[k] - r.origin[k];
+            }
+            r.t_min = 1e-4f;
+            r.t_max = 1.0f;
+        }
+        rays.Sync();
+        lbvh::DataBuffer<lbvh_hit> closest(ctx, count), unbounded(ctx, count);
+        lbvh::DataBuffer<uint32_t> occluded(ctx, count);
+        drawer.TraceClosest(rays, closest);
+        drawer.TraceOccluded(rays, occluded);
+        for (auto& r : rays.LocalBuffer())
+            if (r.t_max > 0.0f) r.t_max = INFINITY;
+        rays.Sync();
+        drawer.TraceClosest(rays, unbounded);
+        closest.GetData();
+        unbounded.GetData();
+        occluded.GetData();
+        size_t hits = 0, n_occluded = 0;
+        double tsum = 0;
+        bool e3 = true;
+        for (size_t i = 0; i < count; i++) {
+            const lbvh_hit& c = closest.LocalBuffer()[i];
+            if (c.t < LBVH_MAX_FLOAT) { hits++; tsum += c.t; }
+            const uint32_t o = occluded.LocalBuffer()[i];
+            n_occluded += o;
+            const bool active = rays.LocalBuffer()[i].t_max > 0.0f;
+            e3 = e3 && o == (uint32_t)(active && unbounded.LocalBuffer()[i].t < 1.0f);
+        }
+        std::printf("{\"triangles\": %u, \"rays\": %zu, \"hits\": %zu, \"t_sum\": %.6f, \"occluded\": %zu, \"e3_holds\": %s}\n", n, count,
+                    hits, tsum, n_occluded, e3 ? "true" : "false");
+    } catch (const lbvh::Error& e) {
+        std::fprintf(stderr, "%s\n", e.what());
+        return 1;
+    }
+    return 0;
+}
+
 int main(int argc, char** argv)
 {
+    if (argc > 1 && std::strcmp(argv[1], "rays") == 0) return rays_main(argc, argv);
     if (argc > 1 && std::strcmp(argv[1], "sort") == 0) return sort_main(argc, argv);
     if (argc > 1 && std::strcmp(argv[1], "multi") == 0) return multi_main(argc, argv);
     const bool from_obj = argc > 2 && std::strcmp(argv[1], "obj") == 0;

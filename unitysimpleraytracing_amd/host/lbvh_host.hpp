@@ -304,6 +304,20 @@ public:
         check(ctx_.get(), lbvh_trace_primary_shard(ctx_.get(), &cam, shard_index, shard_count, &s, mode,
                                                    (lbvh_hit*)hits_->DeviceBuffer(), nullptr));
     }
+    // rays of the caller's own (lbvh_ray: origin, t_min, dir, t_max) over the derived scene: the closest hit of each, or
+    // whether anything lies in (t_min, t_max) — 1 / 0 per ray (lbvh_trace_closest / lbvh_trace_occluded; asynchronous)
+    void TraceClosest(const DataBuffer<lbvh_ray>& rays, DataBuffer<lbvh_hit>& hits)
+    {
+        if (hits.Size() < rays.Size()) throw Error(LBVH_ERR_INVALID_ARG, "TraceClosest: fewer hit records than rays");
+        const lbvh_scene s = container_->Scene();
+        check(ctx_.get(), lbvh_trace_closest(ctx_.get(), (const lbvh_ray*)rays.DeviceBuffer(), rays.Size(), &s, (lbvh_hit*)hits.DeviceBuffer()));
+    }
+    void TraceOccluded(const DataBuffer<lbvh_ray>& rays, DataBuffer<uint32_t>& flags)
+    {
+        if (flags.Size() < rays.Size()) throw Error(LBVH_ERR_INVALID_ARG, "TraceOccluded: fewer flags than rays");
+        const lbvh_scene s = container_->Scene();
+        check(ctx_.get(), lbvh_trace_occluded(ctx_.get(), (const lbvh_ray*)rays.DeviceBuffer(), rays.Size(), &s, (uint32_t*)flags.DeviceBuffer()));
+    }
     // _objectDrawer.SetTexture("_meshTexture", ...) :61 — RGBA8, row 0 at v = 0
     void SetTexture(const std::vector<uint8_t>& rgba8, int width, int height)
     {

@@ -30,6 +30,9 @@ RAY_STATS = np.dtype([("rays", "<u8"), ("node_fetches", "<u8"), ("triangle_tests
 PATH_STATE = np.dtype([("origin", "<f4", 3), ("alive", "<u4"), ("dir", "<f4", 3), ("pad0", "<f4"),
                        ("throughput", "<f4", 3), ("pad1", "<f4"), ("radiance", "<f4", 3), ("alpha", "<f4")])
 assert PATH_STATE.itemsize == 64
+# lbvh_trace_closest / lbvh_trace_occluded: a ray of the caller's own, active iff t_min < t_max
+RAY = np.dtype([("origin", "<f4", 3), ("t_min", "<f4"), ("dir", "<f4", 3), ("t_max", "<f4")])
+assert RAY.itemsize == 32
 
 assert AABB.itemsize == 32          # Assets/_Scripts/MeshBufferContainer.cs:103
 assert TRIANGLE.itemsize == 128     # Assets/_Scripts/MeshBufferContainer.cs:98
