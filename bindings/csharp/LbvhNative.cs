@@ -29,6 +29,13 @@ public static class LbvhNative
     [StructLayout(LayoutKind.Sequential)]
     public struct Ray { public float originX, originY, originZ, tMin; public float dirX, dirY, dirZ, tMax; }
 
+    // lbvh_point_query / lbvh_closest_point (include/lbvh.h): a point with its squared search radius (active iff maxDist2 > 0) and
+    // the nearest triangle's record, 16 bytes each (PointQueries.cs)
+    [StructLayout(LayoutKind.Sequential)]
+    public struct PointQuery { public float pX, pY, pZ, maxDist2; }
+    [StructLayout(LayoutKind.Sequential)]
+    public struct ClosestPoint { public float dist2; public uint tri; public float u, v; }
+
     // lbvh_camera (include/lbvh.h): the 16 matrix floats are plain fields, row-major m00..m33 as Unity's Matrix4x4 names
     // them, so the struct needs no `unsafe` / "allow unsafe code" project setting and marshals by value as it is.
     [StructLayout(LayoutKind.Sequential)]
@@ -132,6 +139,8 @@ public static class LbvhNative
     [DllImport(Lib)] public static extern int lbvh_trace_rays(IntPtr ctx, IntPtr dStates, UIntPtr count, float tMin, ref Scene scene, IntPtr dHits);
     [DllImport(Lib)] public static extern int lbvh_trace_closest(IntPtr ctx, IntPtr dRays, UIntPtr count, ref Scene scene, IntPtr dHits);
     [DllImport(Lib)] public static extern int lbvh_trace_occluded(IntPtr ctx, IntPtr dRays, UIntPtr count, ref Scene scene, IntPtr dOccluded);
+    [DllImport(Lib)] public static extern int lbvh_closest_point_query(IntPtr ctx, IntPtr dQueries, UIntPtr count, ref Scene scene, IntPtr dOut);
+    [DllImport(Lib)] public static extern int lbvh_within_distance(IntPtr ctx, IntPtr dQueries, UIntPtr count, ref Scene scene, IntPtr dFlags);
     [DllImport(Lib)] public static extern int lbvh_path_scatter(IntPtr ctx, ref Scene scene, IntPtr dHits, UIntPtr count, uint bounce, uint seed,
         float albedo, IntPtr dStates);
     [DllImport(Lib)] public static extern int lbvh_path_bounce(IntPtr ctx, ref Scene scene, IntPtr dStates, IntPtr dHits, UIntPtr count,

@@ -586,6 +586,69 @@ lbvh_status lbvh_trace_closest(lbvh_context* ctx, const lbvh_ray* d_rays, size_t
 lbvh_status lbvh_trace_occluded(lbvh_context* ctx, const lbvh_ray* d_rays, size_t count, const lbvh_scene* h_scene,
                                 uint32_t* d_occluded);
 
+/* A point query: 16 bytes; arrays of them 16-byte aligned. */
+typedef struct lbvh_point_query {
+    float p[3];
+    float max_dist2;                /* squared search radius; +inf or >= LBVH_MAX_FLOAT = unbounded */
+} lbvh_point_query;
+
+/* The answer to one: 16 bytes, the shape of lbvh_hit. */
+typedef struct lbvh_closest_point {
+    float    dist2;                 /* squared distance; LBVH_MAX_FLOAT if none */
+    uint32_t tri;                   /* ORIGINAL triangle index; 0 if none */
+    float    u, v;                  /* barycentrics of b and c of the closest point: a + e1 * u + e2 * v; (0, 0) if none */
+} lbvh_closest_point;
+
+/* Nearest triangle and "anything within r" for `count` points, over the derived traversal scene in its four-wide form (see
+ * lbvh_trace_rays): one query per lane, the nearest child box first, boxes farther than the best distance so far skipped.
+ *   Active query: max_dist2 > 0 (false for NaN).  An inactive query is never walked; it gets the none-record
+ *   {LBVH_MAX_FLOAT, 0, 0, 0} (lbvh_closest_point_query) or 0 (lbvh_within_distance).  So does, without a walk, a point with a
+ *   NaN coordinate: all its distances are NaN and it has no candidate.  R = min(max_dist2, LBVH_MAX_FLOAT): LBVH_MAX_FLOAT is
+ *   2139095040, so "unbounded" still means dist2 < 2.14e9 — a point farther than about 46 000 units from every triangle gets
+ *   the none-record.
+ *   Distance of a point to a triangle: defined on what the triangle line of the derived scene holds, a, e1 = b - a and
+ *   e2 = c - a (the fp32 differences taken at build time), in strict fp32, every operation rounded on its own,
+ *   dot(x, y) = (x0*y0 + x1*y1) + x2*y2.  The region test of Ericson, Real-Time Collision Detection 5.1.5, on a, e1, e2:
+ *       ap = p - a
+ *       d1 = dot(e1, ap)   d2 = dot(e2, ap)
+ *       a11 = dot(e1, e1)  a12 = dot(e1, e2)  a22 = dot(e2, e2)
+ *       d3 = d1 - a11   d4 = d2 - a12   d5 = d1 - a12   d6 = d2 - a22
+ *       vc = d1*d4 - d3*d2    vb = d5*d2 - d1*d6    va = d3*d6 - d5*d4
+ *       the first case that holds, in this order, gives (u, v):
+ *         d1 <= 0 && d2 <= 0                       -> (0, 0)                     vertex a
+ *         d3 >= 0 && d4 <= d3                      -> (1, 0)                     vertex b
+ *         vc <= 0 && d1 >= 0 && d3 <= 0            -> (d1 / (d1 - d3), 0)        edge ab
+ *         d6 >= 0 && d5 <= d6                      -> (0, 1)                     vertex c
+ *         vb <= 0 && d2 >= 0 && d6 <= 0            -> (0, d2 / (d2 - d6))        edge ac
+ *         va <= 0 && d4-d3 >= 0 && d5-d6 >= 0      -> w = (d4-d3) / ((d4-d3) + (d5-d6));  (1 - w, w)   edge bc
+ *         otherwise                                -> den = 1 / ((va + vb) + vc);  (vb*den, vc*den)    face
+ *       r = ap - (e1*u + e2*v)          (per component: ap_k - (e1_k*u + e2_k*v))
+ *       dist2 = dot(r, r)
+ *   (a comparison with a NaN is false: a degenerate triangle whose test reaches the face case has a NaN dist2.)
+ *   Distance of a point to a box: per axis g = max(max(lo - p, p - hi), 0); box2 = (gx*gx + gy*gy) + gz*gz.
+ *   Candidate: triangle i is a candidate for a query iff dist2_i < R and !(dist2_i < box2(own AABB_i)), the own AABB being
+ *   scene.triangle_aabb[i], the box the derived scene keeps for the triangle's leaf.  A NaN dist2 is never a candidate.
+ *   lbvh_closest_point_query: d_out[k] = {dist2, tri, u, v} of query k's candidate with the least dist2; on equal dist2 the lower
+ *   original triangle index, whatever order the walk meets them in.  No candidate: the none-record, never R.
+ *   lbvh_within_distance: d_flags[k] = 1 if query k has any candidate, else 0.  The walk is the closest-point walk (same
+ *   nearest-first order) cut off at its first accepted candidate: never more node fetches or triangle tests per query.
+ * Why the record does not depend on the order of the walk (the argument of the accept rule for rays at the traversal flavours
+ * above, with box2 in the place of the entry distance): fp32 subtraction, max, multiplication of non-negatives and addition are
+ * monotone, and every box of the derived tree, binary or four-wide, is the exact min / max union of what is below it, so
+ * box2(ancestor) <= box2(leaf) <= dist2 for every candidate.  A subtree skipped because box2 > best (strictly) cannot hold a
+ * candidate at or below best.  A dist2 below its own box's distance is fp32 noise of the triangle arithmetic (the padded box
+ * contains the triangle); on ordinary meshes the rule rejects nothing.
+ * Both need the derived traversal scene (lbvh_build_fast_scene; a stale one is LBVH_ERR_INVALID_ARG), are asynchronous on the
+ * context's stream, and use the context's ray scratch: like lbvh_trace_rays they drop the path tracer's live-path list (see
+ * lbvh_path_bounce).  count == 0 is a no-op.  Rejected: NULL pointers, d_queries or d_out not 16-byte aligned, d_flags not
+ * 4-byte aligned, count > 2^32 - 1.
+ * Pass active queries only where time matters: a wave takes a run of consecutive queries, and runs of inactive ones leave
+ * some waves with little to do and others with all of it (as inactive rays do for lbvh_trace_closest). */
+lbvh_status lbvh_closest_point_query(lbvh_context* ctx, const lbvh_point_query* d_queries, size_t count, const lbvh_scene* h_scene,
+                                     lbvh_closest_point* d_out);
+lbvh_status lbvh_within_distance(lbvh_context* ctx, const lbvh_point_query* d_queries, size_t count, const lbvh_scene* h_scene,
+                                 uint32_t* d_flags);
+
 /* Camera rays into path states (origin/dir as Raytracing.compute:108-126, throughput 1, radiance 0, alive). */
 lbvh_status lbvh_path_begin(lbvh_context* ctx, const lbvh_camera* h_camera, lbvh_path_state* d_states);
 
@@ -609,8 +672,8 @@ lbvh_status lbvh_path_scatter(lbvh_context* ctx, const lbvh_scene* h_scene, cons
  * CROSS-CALL STATE: a call with bounce >= 1 — and the frame's last lbvh_path_scatter — visits only the paths the previous
  * lbvh_path_bounce on the same d_states / d_hits listed as live (a list kept by the context).  Every library call that writes
  * into those buffers drops the list (lbvh_path_begin, lbvh_trace_rays, a primary trace into any part of d_hits,
- * lbvh_buffer_upload / _fill_u32 / _free), and so does lbvh_trace_forget — and so do lbvh_trace_closest and
- * lbvh_trace_occluded, whatever buffers they are given, since they use the same ray scratch; then every state is scanned again.  What the library
+ * lbvh_buffer_upload / _fill_u32 / _free), and so does lbvh_trace_forget — and so do lbvh_trace_closest,
+ * lbvh_trace_occluded, lbvh_closest_point_query and lbvh_within_distance, whatever buffers they are given, since they use the same ray scratch; then every state is scanned again.  What the library
  * cannot see is a write of the CALLER's own (a kernel or hipMemcpy that revives or ends paths, Russian roulette): between two
  * consecutive bounces of a frame d_states and d_hits must not be written from outside the library — or lbvh_trace_forget must be
  * called after such a write. */

@@ -53,7 +53,8 @@ lbvh_status lbvh_debug_ray_stack_split(lbvh_context* ctx, uint32_t lds_entries);
 /* Measurement aid (cfg5's roofline): while d_stats is non-NULL, every launch of the four-wide per-ray walk (lbvh_trace_rays,
  * lbvh_path_bounce, lbvh_path_first_bounce) ADDS what it did to it: rays walked, 128-byte four-wide node lines fetched (one per
  * ray-step), triangle lines fetched and tested.  Zero it yourself; NULL switches the counting off (the default: the counting
- * kernels are separate instantiations, the product's carry none of it). */
+ * kernels are separate instantiations, the product's carry none of it).  lbvh_closest_point_query and lbvh_within_distance count
+ * too: `rays` = active queries walked, node lines per query-step, triangle lines tested. */
 typedef struct lbvh_ray_stats {
     uint64_t rays;
     uint64_t node_fetches;
@@ -71,7 +72,8 @@ lbvh_status lbvh_debug_ray_stack_limit(lbvh_context* ctx, uint32_t deep_entries)
  * largest children opened, made on first use after a rebuild; from bounce 1 on lbvh_path_bounce takes the kernel that keeps
  * a step's two fetches in flight at once: few live rays, the launch is the chain of its longest), 2: that kernel for every
  * launch, 0: the binary nodes the packet walk uses.  Hit records do not depend on it (ties go to the lower triangle index
- * on all three). */
+ * on all three).  The point queries (lbvh_closest_point_query, lbvh_within_distance) have the four-wide walk only: this hook
+ * leaves them alone.  lbvh_debug_ray_stack_split and lbvh_debug_ray_stack_limit apply to them as to the four-wide ray walk. */
 lbvh_status lbvh_debug_ray_walker(lbvh_context* ctx, uint32_t walker);
 
 /* Profiling aid: one LBVH_TRACE_FAST frame that also records, per 8x8-pixel tile (row-major,

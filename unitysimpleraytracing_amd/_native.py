@@ -93,6 +93,8 @@ SIGNATURES = {
     "lbvh_trace_rays": (_I32, [_P, _P, _SZ, C.c_float, C.POINTER(Scene), _P]),
     "lbvh_trace_closest": (_I32, [_P, _P, _SZ, C.POINTER(Scene), _P]),
     "lbvh_trace_occluded": (_I32, [_P, _P, _SZ, C.POINTER(Scene), _P]),
+    "lbvh_closest_point_query": (_I32, [_P, _P, _SZ, C.POINTER(Scene), _P]),
+    "lbvh_within_distance": (_I32, [_P, _P, _SZ, C.POINTER(Scene), _P]),
     "lbvh_path_begin": (_I32, [_P, C.POINTER(Camera), _P]),
     "lbvh_path_scatter": (_I32, [_P, C.POINTER(Scene), _P, _SZ, _U32, _U32, C.c_float, _P]),
     "lbvh_path_bounce": (_I32, [_P, C.POINTER(Scene), _P, _P, _SZ, _U32, _U32, C.c_float, C.c_float]),

@@ -658,6 +658,190 @@ __global__ __launch_bounds__(64) void trace_rays_wide_chain_kernel(const walk_sr
     if (STATS) add_ray_stats(stats, n_rays, n_steps, n_tris);
 }
 
+// ---- point queries: nearest triangle / anything within a distance (include/lbvh.h) -----------------------------------
+// squared fp32 distance of p to a box: per axis g = max(max(lo - p, p - hi), 0), (gx*gx + gy*gy) + gz*gz.  Monotone: it grows
+// from a box to any box inside it (subtraction, max, products of non-negatives and sums are monotone in fp32).
+__device__ __forceinline__ float point_box2(float lx, float ly, float lz, float hx, float hy, float hz, float px, float py, float pz)
+{
+    const float gx = fmaxf(fmaxf(lx - px, px - hx), 0.0f);
+    const float gy = fmaxf(fmaxf(ly - py, py - hy), 0.0f);
+    const float gz = fmaxf(fmaxf(lz - pz, pz - hz), 0.0f);
+    return (gx * gx + gy * gy) + gz * gz;
+}
+
+// squared fp32 distance of p to the triangle {a, e1, e2} of a derived-scene line and the barycentrics of its closest point:
+// the region test of Ericson, Real-Time Collision Detection 5.1.5, in the operation order lbvh.h writes down.  The four cases
+// that divide share one division (numerator 1 for the face case): the same operations on the same values as the definition.
+__device__ __forceinline__ float point_triangle2(float px, float py, float pz, const float4 t0, const float4 e1, const float4 e2,
+                                                 float& u_out, float& v_out)
+{
+    const float apx = px - t0.x, apy = py - t0.y, apz = pz - t0.z;
+    const float d1 = dot3(e1.x, e1.y, e1.z, apx, apy, apz), d2 = dot3(e2.x, e2.y, e2.z, apx, apy, apz);
+    const float a11 = dot3(e1.x, e1.y, e1.z, e1.x, e1.y, e1.z), a12 = dot3(e1.x, e1.y, e1.z, e2.x, e2.y, e2.z);
+    const float a22 = dot3(e2.x, e2.y, e2.z, e2.x, e2.y, e2.z);
+    const float d3 = d1 - a11, d4 = d2 - a12, d5 = d1 - a12, d6 = d2 - a22;
+    const float vc = d1 * d4 - d3 * d2, vb = d5 * d2 - d1 * d6, va = d3 * d6 - d5 * d4;
+    const float d43 = d4 - d3, d56 = d5 - d6;
+    float u, v;
+    if (d1 <= 0.0f && d2 <= 0.0f) { u = 0.0f; v = 0.0f; }                          // vertex a
+    else if (d3 >= 0.0f && d4 <= d3) { u = 1.0f; v = 0.0f; }                       // vertex b
+    else {
+        const bool ab = vc <= 0.0f && d1 >= 0.0f && d3 <= 0.0f;
+        const bool cc = !ab && d6 >= 0.0f && d5 <= d6;
+        const bool ac = !ab && !cc && vb <= 0.0f && d2 >= 0.0f && d6 <= 0.0f;
+        const bool bc = !ab && !cc && !ac && va <= 0.0f && d43 >= 0.0f && d56 >= 0.0f;
+        const float num = ab ? d1 : (ac ? d2 : (bc ? d43 : 1.0f));
+        const float den = ab ? d1 - d3 : (ac ? d2 - d6 : (bc ? d43 + d56 : (va + vb) + vc));
+        const float q = num / den;
+        if (ab) { u = q; v = 0.0f; }
+        else if (cc) { u = 0.0f; v = 1.0f; }                                       // vertex c
+        else if (ac) { u = 0.0f; v = q; }
+        else if (bc) { u = 1.0f - q; v = q; }
+        else { u = vb * q; v = vc * q; }                                           // face
+    }
+    const float rx = apx - (e1.x * u + e2.x * v), ry = apy - (e1.y * u + e2.y * v), rz = apz - (e1.z * u + e2.z * v);
+    u_out = u;
+    v_out = v;
+    return dot3(rx, ry, rz, rx, ry, rz);
+}
+
+// query k into the lane (best = R): false (none-record / 0 written, lane stays idle) for an inactive query, and for a point
+// with a NaN coordinate, whose every dist2 is NaN: no candidate by definition, but its box distances would all read 0
+template <bool ANY>
+__device__ __forceinline__ bool load_point_query(const lbvh_point_query* __restrict__ queries, uint32_t k, float& px, float& py, float& pz,
+                                                 float& best, std::conditional_t<ANY, uint32_t, lbvh_closest_point>* __restrict__ out)
+{
+    const float4 q = reinterpret_cast<const float4*>(queries)[k];
+    px = q.x; py = q.y; pz = q.z;
+    best = fminf(q.w, LBVH_MAX_FLOAT);
+    if (q.w > 0.0f && (q.x == q.x && q.y == q.y && q.z == q.z)) return true;      // false for a NaN radius too
+    if constexpr (ANY) out[k] = 0u;
+    else reinterpret_cast<float4*>(out)[k] = make_float4(LBVH_MAX_FLOAT, __uint_as_float(0u), 0.0f, 0.0f);
+    return false;
+}
+
+// One query per lane over the four-wide nodes, in the frame of trace_rays_wide_kernel<PLAIN> (persistent waves, lanes refilled from
+// the wave's run of consecutive queries, LDS + device-memory stack).  Per step one node line: four box distances, slots beyond
+// `best` dropped, leaf slots tested, the other slots entered nearest first.  A candidate is a triangle with dist2 < R that is not
+// in front of its own box (!(dist2 < box2 of its leaf slot)): box2 grows from a box to any box inside it, so a subtree skipped
+// because box2 > best holds no candidate at or below best and the record does not depend on the order of the walk.
+// ANY: a flag, the walk cut off at its first candidate (best stays R).
+template <bool ANY, bool STATS>
+__global__ __launch_bounds__(64) void point_query_wide_kernel(const lbvh_point_query* __restrict__ queries, uint32_t total,
+                                                              const lbvh_wide_node* __restrict__ wide,
+                                                              const lbvh_fast_node* __restrict__ lines,
+                                                              std::conditional_t<ANY, uint32_t, lbvh_closest_point>* __restrict__ out,
+                                                              uint32_t* __restrict__ deep,     // [gridDim.x][kWideStackDeep][64]
+                                                              uint32_t lds_depth,              // <= kWideStackLds
+                                                              uint32_t deep_cap,               // <= kWideStackDeep
+                                                              uint32_t* __restrict__ fault, lbvh_ray_stats* stats)
+{
+    __shared__ uint32_t s_stack[kWideStackLds][LBVH_WAVE];
+    uint32_t* my_deep = deep + (size_t)blockIdx.x * (kWideStackDeep * LBVH_WAVE) + threadIdx.x;
+    const uint32_t lane = threadIdx.x;
+    const uint32_t run = max((total + gridDim.x - 1) / gridDim.x, 32u);
+    uint32_t next = blockIdx.x * run;
+    if (next >= total) return;
+    const uint32_t end = min(next + run, total);
+    uint32_t n_queries = 0, n_steps = 0, n_tris = 0;
+
+    bool active = false, took = false;
+    uint32_t i = 0;
+    float px = 0.0f, py = 0.0f, pz = 0.0f;
+    float best = LBVH_MAX_FLOAT, best_u = 0.0f, best_v = 0.0f;
+    uint32_t best_tri = 0, sp = 0, node = 0;
+    auto push = [&](uint32_t ref) {
+        if (sp < lds_depth) { s_stack[sp][lane] = ref; sp++; }
+        else if (sp < lds_depth + deep_cap) { my_deep[(sp - lds_depth) * LBVH_WAVE] = ref; sp++; }
+        // a dropped entry would be a silently wrong record: report it, as the ray walkers do (lbvh_debug_ray_stack_limit provokes it)
+        else __hip_atomic_store(fault, LBVH_FAULT_RAY_STACK, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    };
+    for (;;) {
+        const uint64_t idle = __ballot(!active);
+        if (idle != 0 && next < end) {
+            if (!active) {
+                const uint32_t k = next + mbcnt64(idle);
+                if (k < end) {
+                    i = k;
+                    active = load_point_query<ANY>(queries, k, px, py, pz, best, out);
+                    best_tri = 0; best_u = 0.0f; best_v = 0.0f; took = false;
+                    sp = 0; node = 0;
+                    if (STATS && active) n_queries++;
+                }
+            }
+            next += (uint32_t)__popcll(idle);
+        }
+        if (!__any(active) && next >= end) break;
+        if (active) {
+            if (STATS) n_steps++;
+            const float4* w = reinterpret_cast<const float4*>(&wide[node]);
+            const float4 lox = w[0], loy = w[1], loz = w[2], hix = w[3], hiy = w[4], hiz = w[5];
+            const uint4 ref = reinterpret_cast<const uint4*>(w)[6];
+            const float b0 = point_box2(lox.x, loy.x, loz.x, hix.x, hiy.x, hiz.x, px, py, pz);
+            const float b1 = point_box2(lox.y, loy.y, loz.y, hix.y, hiy.y, hiz.y, px, py, pz);
+            const float b2 = point_box2(lox.z, loy.z, loz.z, hix.z, hiy.z, hiz.z, px, py, pz);
+            const float b3 = point_box2(lox.w, loy.w, loz.w, hix.w, hiy.w, hiz.w, px, py, pz);
+            const bool h0 = !(b0 > best) && ref.x != kWideEmpty, h1 = !(b1 > best) && ref.y != kWideEmpty;
+            const bool h2 = !(b2 > best) && ref.z != kWideEmpty, h3 = !(b3 > best) && ref.w != kWideEmpty;
+            // leaf slots first: a lane's leaves one after the other, every lane's k-th at the same time
+            uint32_t leaves = (h0 && (ref.x >> 31) ? 1u : 0u) | (h1 && (ref.y >> 31) ? 2u : 0u) | (h2 && (ref.z >> 31) ? 4u : 0u) |
+                              (h3 && (ref.w >> 31) ? 8u : 0u);
+            bool found = false;                          // ANY: a candidate was accepted
+            while (leaves != 0u) {
+                const uint32_t k = (uint32_t)__builtin_ctz(leaves);
+                leaves &= leaves - 1u;
+                if (STATS) n_tris++;
+                float4 v0, v1, v2;
+                unpack_fast_triangle(reinterpret_cast<const float4*>(&lines[pick4(ref, k) & 0x7FFFFFFFu]), v0, v1, v2);
+                float u = 0.0f, v = 0.0f;
+                const float dist2 = point_triangle2(px, py, pz, v0, v1, v2, u, v);
+                const uint32_t tri = __float_as_uint(v0.w);
+                const float own = k == 0u ? b0 : (k == 1u ? b1 : (k == 2u ? b2 : b3));
+                // best starts at R and best_tri at 0: dist2 == R is never taken.  Ties go to the lower triangle index.
+                if (!(dist2 < own) && (dist2 < best || (dist2 == best && tri < best_tri))) {
+                    if constexpr (ANY) { found = true; break; }
+                    else { best = dist2; best_tri = tri; best_u = u; best_v = v; took = true; }
+                }
+            }
+            if (ANY && found) {
+                if constexpr (ANY) out[i] = 1u;
+                active = false;
+                continue;
+            }
+            // nodes to enter, ordered by box distance: the order key is the distance's bit pattern (non-negative floats order
+            // like integers) with the slot number in its two lowest bits.  (`best` may have shrunk in the leaf loop since h0 .. h3
+            // were formed: the box distances are compared with it once more)
+            constexpr uint32_t none = 0xFFFFFFFFu;
+            uint32_t k0 = h0 && !(ref.x >> 31) && !(b0 > best) ? ((__float_as_uint(b0) & ~3u) | 0u) : none;
+            uint32_t k1 = h1 && !(ref.y >> 31) && !(b1 > best) ? ((__float_as_uint(b1) & ~3u) | 1u) : none;
+            uint32_t k2 = h2 && !(ref.z >> 31) && !(b2 > best) ? ((__float_as_uint(b2) & ~3u) | 2u) : none;
+            uint32_t k3 = h3 && !(ref.w >> 31) && !(b3 > best) ? ((__float_as_uint(b3) & ~3u) | 3u) : none;
+            {   // five compare-exchanges
+                uint32_t a, b;
+                a = min(k0, k1); b = max(k0, k1); k0 = a; k1 = b;
+                a = min(k2, k3); b = max(k2, k3); k2 = a; k3 = b;
+                a = min(k0, k2); b = max(k0, k2); k0 = a; k2 = b;
+                a = min(k1, k3); b = max(k1, k3); k1 = a; k3 = b;
+                a = min(k1, k2); b = max(k1, k2); k1 = a; k2 = b;
+            }
+            if (k0 != none) {
+                if (k3 != none) push(pick4(ref, k3 & 3u));       // farthest first: the nearest waiting sibling is popped first
+                if (k2 != none) push(pick4(ref, k2 & 3u));
+                if (k1 != none) push(pick4(ref, k1 & 3u));
+                node = pick4(ref, k0 & 3u);
+            } else if (sp != 0) {
+                sp--;
+                node = sp < lds_depth ? s_stack[sp][lane] : my_deep[(sp - lds_depth) * LBVH_WAVE];
+            } else {
+                if constexpr (ANY) out[i] = 0u;
+                else reinterpret_cast<float4*>(out)[i] = make_float4(took ? best : LBVH_MAX_FLOAT, __uint_as_float(best_tri), best_u, best_v);
+                active = false;
+            }
+        }
+    }
+    if (STATS) add_ray_stats(stats, n_queries, n_steps, n_tris);
+}
+
 // ---- bounce ----------------------------------------------------------------------------------------------
 __device__ __forceinline__ uint32_t pcg_hash(uint32_t v)
 {
@@ -824,6 +1008,19 @@ __global__ __launch_bounds__(256) void path_resolve_kernel(const lbvh_path_state
 
 static_assert(sizeof(lbvh_path_state) == 64, "path state must be 64 bytes");
 
+// the four-wide form of the derived tree, made on first use after a rebuild and shared by the ray and the point walkers
+static lbvh_status ensure_wide_nodes(lbvh_context* ctx)
+{
+    if (ctx->wide_valid) return LBVH_OK;
+    const uint32_t n_internal = ctx->fast_src.n - 1;
+    const int rc = lbvh_reserve(ctx, &ctx->wide_nodes, &ctx->wide_nodes_bytes, (size_t)n_internal * sizeof(lbvh_wide_node));
+    if (rc != LBVH_OK) return (lbvh_status)rc;
+    LBVH_LAUNCH(ctx, collapse_wide_kernel, dim3((n_internal + 255) / 256), dim3(256), ctx->fast_nodes, n_internal,
+                (lbvh_wide_node*)ctx->wide_nodes);
+    ctx->wide_valid = true;
+    return LBVH_OK;
+}
+
 // the walk over the live rays of `list` (or over plain rays, PLAIN: `total` is their count): four-wide nodes (made on first use
 // after a rebuild) — few_rays: with the kernel that keeps two fetches of a step in flight (the later bounces of a frame) —, or the
 // binary nodes the packet walk uses (lbvh_debug_ray_walker(ctx, 0): the cross-check of the tests; 2: the few-rays kernel for every launch)
@@ -833,14 +1030,8 @@ static lbvh_status launch_ray_walk(lbvh_context* ctx, const walk_src<PLAIN>* d_s
 {
     const uint32_t ray_waves = ray_waves_of(count);
     if (ctx->ray_walker != 0u) {
-        const uint32_t n_internal = ctx->fast_src.n - 1;
-        if (!ctx->wide_valid) {
-            const int rc = lbvh_reserve(ctx, &ctx->wide_nodes, &ctx->wide_nodes_bytes, (size_t)n_internal * sizeof(lbvh_wide_node));
-            if (rc != LBVH_OK) return (lbvh_status)rc;
-            LBVH_LAUNCH(ctx, collapse_wide_kernel, dim3((n_internal + 255) / 256), dim3(256), ctx->fast_nodes, n_internal,
-                        (lbvh_wide_node*)ctx->wide_nodes);
-            ctx->wide_valid = true;
-        }
+        const lbvh_status wrc = ensure_wide_nodes(ctx);
+        if (wrc != LBVH_OK) return wrc;
         const uint32_t lds = std::min<uint32_t>(ctx->ray_stack_lds, kWideStackLds), deep_cap = std::min<uint32_t>(ctx->ray_stack_deep, kWideStackDeep);
         lbvh_ray_stats* st = ctx->ray_stats;
         const lbvh_wide_node* wn = (const lbvh_wide_node*)ctx->wide_nodes;
@@ -885,7 +1076,50 @@ static lbvh_status trace_plain_rays(lbvh_context* ctx, const lbvh_ray* d_rays, s
     return launch_ray_walk<true, ANY>(ctx, d_rays, (uint32_t)count, nullptr, 0.0f, d_out, count);
 }
 
+// lbvh_closest_point_query / lbvh_within_distance: always the four-wide walk (lbvh_debug_ray_walker does not apply)
+template <bool ANY>
+static lbvh_status point_queries(lbvh_context* ctx, const lbvh_point_query* d_queries, size_t count, const lbvh_scene* h_scene,
+                                 std::conditional_t<ANY, uint32_t, lbvh_closest_point>* d_out, const char* who)
+{
+    if (!ctx) return LBVH_ERR_INVALID_ARG;
+    if (count == 0) return LBVH_OK;
+    LBVH_REQUIRE(ctx, d_queries != nullptr && h_scene != nullptr && d_out != nullptr);
+    LBVH_REQUIRE(ctx, ((uintptr_t)d_queries & 15) == 0 && ((uintptr_t)d_out & (ANY ? 3 : 15)) == 0);
+    LBVH_REQUIRE(ctx, count <= 0xFFFFFFFFull);
+    {
+        const int frc = lbvh_require_fast(ctx, *h_scene, who);
+        if (frc != LBVH_OK) return frc;
+    }
+    LBVH_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    // the deep stack slabs of the ray scratch, laid out as for lbvh_trace_rays (whose live-path list they may overwrite)
+    int rc = lbvh_reserve(ctx, &ctx->ray_scratch, &ctx->ray_scratch_bytes, ray_scratch_bytes_for(count));
+    if (rc != LBVH_OK) return rc;
+    ctx->ray_list.valid = false;
+    rc = ensure_wide_nodes(ctx);
+    if (rc != LBVH_OK) return rc;
+    const uint32_t lds = std::min<uint32_t>(ctx->ray_stack_lds, kWideStackLds), deep_cap = std::min<uint32_t>(ctx->ray_stack_deep, kWideStackDeep);
+    const lbvh_wide_node* wn = (const lbvh_wide_node*)ctx->wide_nodes;
+    if (ctx->ray_stats) LBVH_LAUNCH(ctx, (point_query_wide_kernel<ANY, true>), dim3(ray_waves_of(count)), dim3(LBVH_WAVE), d_queries, (uint32_t)count, wn,
+                                    ctx->fast_nodes, d_out, deep_stacks(ctx, count), lds, deep_cap, ctx->fault_dev, ctx->ray_stats);
+    else LBVH_LAUNCH(ctx, (point_query_wide_kernel<ANY, false>), dim3(ray_waves_of(count)), dim3(LBVH_WAVE), d_queries, (uint32_t)count, wn,
+                     ctx->fast_nodes, d_out, deep_stacks(ctx, count), lds, deep_cap, ctx->fault_dev, ctx->ray_stats);
+    LBVH_HIP_TRY(ctx, hipGetLastError());
+    return LBVH_OK;
+}
+
 extern "C" {
+
+lbvh_status lbvh_closest_point_query(lbvh_context* ctx, const lbvh_point_query* d_queries, size_t count, const lbvh_scene* h_scene,
+                                     lbvh_closest_point* d_out)
+{
+    return point_queries<false>(ctx, d_queries, count, h_scene, d_out, "lbvh_closest_point_query");
+}
+
+lbvh_status lbvh_within_distance(lbvh_context* ctx, const lbvh_point_query* d_queries, size_t count, const lbvh_scene* h_scene,
+                                 uint32_t* d_flags)
+{
+    return point_queries<true>(ctx, d_queries, count, h_scene, d_flags, "lbvh_within_distance");
+}
 
 lbvh_status lbvh_animate(lbvh_context* ctx, const lbvh_triangle* d_rest, uint32_t n, const uint32_t* d_body,
                          const float* d_centres, float cos_angle, float sin_angle, lbvh_triangle* d_out)

@@ -366,6 +366,21 @@ class RaytracingMeshDrawer:
         s = self.container.scene()
         N.check(self.ctx.handle, fn(self.ctx.handle, rays.device, rays.size, C.byref(s), out.device))
 
+    def closest_points(self, queries, out):
+        """Nearest triangle of each point of the DataBuffer `queries` (layouts.POINT_QUERY: p, max_dist2) into the DataBuffer `out`
+        (layouts.CLOSEST_POINT: dist2, tri, u, v), over the derived scene.  Asynchronous; read with out.get_data()."""
+        self._point_queries(N.lib.lbvh_closest_point_query, queries, out, L.CLOSEST_POINT)
+
+    def within_distance(self, queries, flags):
+        """1 into the uint32 DataBuffer `flags` for each point of `queries` with a triangle nearer than sqrt(max_dist2), else 0."""
+        self._point_queries(N.lib.lbvh_within_distance, queries, flags, np.dtype(np.uint32))
+
+    def _point_queries(self, fn, queries, out, dtype):
+        if queries.dtype != L.POINT_QUERY or out.dtype != dtype or out.size < queries.size:
+            raise ValueError(f"queries must be a DataBuffer of layouts.POINT_QUERY and the output one of {dtype} with at least as many entries")
+        s = self.container.scene()
+        N.check(self.ctx.handle, fn(self.ctx.handle, queries.device, queries.size, C.byref(s), out.device))
+
     def update(self, camera, rect=None, mode=L.TRACE_FAST, stats=False):
         """Enqueue one frame (or the sub-rectangle (x0, y0, x1, y1) of it).  Returns the device
         hit buffer; read it back with hits()."""

@@ -14,6 +14,11 @@
 //                                                (1e-4, 1); pixels without a hit give inactive rays.  TraceClosest with
 //                                                t_max = 1 and = +inf, TraceOccluded; prints the hit count and t sum of the
 //                                                first, the occluded count and whether occluded == (t(+inf) < 1) on every ray
+//     lbvh_driver points [n | file.obj] [count] [radius]   the cfg1 mesh of n triangles (or an OBJ asset); `count` points (SplitMix64,
+//                                                seed 2) uniform in the box of the vertices grown by a quarter of its extent per
+//                                                side, max_dist2 = radius * radius (default: unbounded).  ClosestPoints and
+//                                                WithinDistance; prints how many points found a triangle, the sum of all 32-bit
+//                                                words of the records (mod 2^64) and the number of set flags
 #include <chrono>
 #include <cmath>
 #include <cstdio>
@@ -253,8 +258,62 @@ static int rays_main(int argc, char** argv)
     return 0;
 }
 
+static int points_main(int argc, char** argv)
+{
+    const char* what = argc > 2 ? argv[2] : "4096";
+    const size_t len = std::strlen(what);
+    const bool from_obj = len > 4 && std::strcmp(what + len - 4, ".obj") == 0;
+    const size_t count = argc > 3 ? (size_t)strtoull(argv[3], nullptr, 10) : 65536;
+    const float radius = argc > 4 ? (float)atof(argv[4]) : INFINITY;
+    try {
+        const std::vector<lbvh_triangle> mesh = from_obj ? lbvh::MeshTriangles(lbvh::LoadObj(what)) : random_mesh((uint32_t)atoi(what));
+        float lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
+        for (const auto& t : mesh)
+            for (int k = 0; k < 3; k++) {
+                lo[k] = std::fmin(lo[k], std::fmin(t.a[k], std::fmin(t.b[k], t.c[k])));
+                hi[k] = std::fmax(hi[k], std::fmax(t.a[k], std::fmax(t.b[k], t.c[k])));
+            }
+        lbvh::Context ctx(0);
+        lbvh::RaytracingMeshDrawer drawer(ctx, mesh);
+        drawer.Awake();
+        lbvh::DataBuffer<lbvh_point_query> queries(ctx, count);
+        uint64_t seed = 2;
+        for (auto& q : queries.LocalBuffer()) {
+            for (int k = 0; k < 3; k++) {
+                const float grow = 0.25f * (hi[k] - lo[k]);
+                q.p[k] = uniform(seed, lo[k] - grow, hi[k] + grow);
+            }
+            q.max_dist2 = radius * radius;
+        }
+        queries.Sync();
+        lbvh::DataBuffer<lbvh_closest_point> closest(ctx, count);
+        lbvh::DataBuffer<uint32_t> within(ctx, count);
+        drawer.ClosestPoints(queries, closest);
+        drawer.WithinDistance(queries, within);
+        closest.GetData();
+        within.GetData();
+        size_t found = 0, n_within = 0;
+        uint64_t word_sum = 0;
+        for (size_t i = 0; i < count; i++) {
+            const lbvh_closest_point& c = closest.LocalBuffer()[i];
+            if (c.dist2 < LBVH_MAX_FLOAT) found++;
+            uint32_t w[4];
+            std::memcpy(w, &c, sizeof w);
+            word_sum += (uint64_t)w[0] + w[1] + w[2] + w[3];
+            n_within += within.LocalBuffer()[i];
+        }
+        std::printf("{\"triangles\": %zu, \"points\": %zu, \"found\": %zu, \"word_sum\": %llu, \"within\": %zu}\n", mesh.size(), count, found,
+                    (unsigned long long)word_sum, n_within);
+    } catch (const std::exception& e) {
+        std::fprintf(stderr, "%s\n", e.what());
+        return 1;
+    }
+    return 0;
+}
+
 int main(int argc, char** argv)
 {
+    if (argc > 1 && std::strcmp(argv[1], "points") == 0) return points_main(argc, argv);
     if (argc > 1 && std::strcmp(argv[1], "rays") == 0) return rays_main(argc, argv);
     if (argc > 1 && std::strcmp(argv[1], "sort") == 0) return sort_main(argc, argv);
     if (argc > 1 && std::strcmp(argv[1], "multi") == 0) return multi_main(argc, argv);

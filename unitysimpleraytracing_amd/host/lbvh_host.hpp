@@ -318,6 +318,22 @@ public:
         const lbvh_scene s = container_->Scene();
         check(ctx_.get(), lbvh_trace_occluded(ctx_.get(), (const lbvh_ray*)rays.DeviceBuffer(), rays.Size(), &s, (uint32_t*)flags.DeviceBuffer()));
     }
+    // points of the caller's own (lbvh_point_query: p, max_dist2) over the derived scene: the nearest triangle of each, or
+    // whether any lies within the radius — 1 / 0 per point (lbvh_closest_point_query / lbvh_within_distance; asynchronous)
+    void ClosestPoints(const DataBuffer<lbvh_point_query>& queries, DataBuffer<lbvh_closest_point>& out)
+    {
+        if (out.Size() < queries.Size()) throw Error(LBVH_ERR_INVALID_ARG, "ClosestPoints: fewer records than queries");
+        const lbvh_scene s = container_->Scene();
+        check(ctx_.get(), lbvh_closest_point_query(ctx_.get(), (const lbvh_point_query*)queries.DeviceBuffer(), queries.Size(), &s,
+                                                   (lbvh_closest_point*)out.DeviceBuffer()));
+    }
+    void WithinDistance(const DataBuffer<lbvh_point_query>& queries, DataBuffer<uint32_t>& flags)
+    {
+        if (flags.Size() < queries.Size()) throw Error(LBVH_ERR_INVALID_ARG, "WithinDistance: fewer flags than queries");
+        const lbvh_scene s = container_->Scene();
+        check(ctx_.get(), lbvh_within_distance(ctx_.get(), (const lbvh_point_query*)queries.DeviceBuffer(), queries.Size(), &s,
+                                               (uint32_t*)flags.DeviceBuffer()));
+    }
     // _objectDrawer.SetTexture("_meshTexture", ...) :61 — RGBA8, row 0 at v = 0
     void SetTexture(const std::vector<uint8_t>& rgba8, int width, int height)
     {
