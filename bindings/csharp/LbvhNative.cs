@@ -141,6 +141,9 @@ public static class LbvhNative
     [DllImport(Lib)] public static extern int lbvh_trace_occluded(IntPtr ctx, IntPtr dRays, UIntPtr count, ref Scene scene, IntPtr dOccluded);
     [DllImport(Lib)] public static extern int lbvh_closest_point_query(IntPtr ctx, IntPtr dQueries, UIntPtr count, ref Scene scene, IntPtr dOut);
     [DllImport(Lib)] public static extern int lbvh_within_distance(IntPtr ctx, IntPtr dQueries, UIntPtr count, ref Scene scene, IntPtr dFlags);
+    [DllImport(Lib)] public static extern int lbvh_count_hits(IntPtr ctx, IntPtr dRays, UIntPtr count, ref Scene scene, IntPtr dCounts);
+    [DllImport(Lib)] public static extern int lbvh_point_crossings(IntPtr ctx, IntPtr dPoints, UIntPtr count, float[] hDirs, uint nDirs, ref Scene scene,
+        IntPtr dParity);
     [DllImport(Lib)] public static extern int lbvh_path_scatter(IntPtr ctx, ref Scene scene, IntPtr dHits, UIntPtr count, uint bounce, uint seed,
         float albedo, IntPtr dStates);
     [DllImport(Lib)] public static extern int lbvh_path_bounce(IntPtr ctx, ref Scene scene, IntPtr dStates, IntPtr dHits, UIntPtr count,

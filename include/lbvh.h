@@ -649,6 +649,39 @@ lbvh_status lbvh_closest_point_query(lbvh_context* ctx, const lbvh_point_query* 
 lbvh_status lbvh_within_distance(lbvh_context* ctx, const lbvh_point_query* d_queries, size_t count, const lbvh_scene* h_scene,
                                  uint32_t* d_flags);
 
+/* How many surfaces a ray crosses, and crossing parities of points along fixed directions (inside / outside tests).
+ *   lbvh_count_hits: active ray, candidate set and T = min(t_max, LBVH_MAX_FLOAT) exactly those of lbvh_trace_closest (the
+ *   own-box slab test with entry e, Moeller-Trumbore with the reference's rejections, t >= e, t_min < t < T).  d_counts[k] =
+ *   the number of triangles that are candidates of ray k, every member counted once: two triangles at the same t count 2, a
+ *   ray through a shared edge counts every triangle that passes the test.  0 for an inactive ray.  Hence d_counts[k] >= 1
+ *   exactly when lbvh_trace_occluded gives 1.  The walk is lbvh_trace_rays' (lbvh_debug_ray_walker's choice of kernel)
+ *   without the shrinking bound: boxes entered beyond T are skipped, none is skipped for the candidates found so far.
+ *   lbvh_point_crossings: for point k and direction j, the ray {origin = p_k, t_min = 0, dir = dirs[j], t_max = +inf}; bit j
+ *   of d_parity[k] is that ray's lbvh_count_hits count AND 1, bits >= n_dirs are 0.  max_dist2 is not read: the buffer given
+ *   to lbvh_closest_point_query can be passed unchanged (closest point + parity = a signed distance).  No
+ *   special cases: a point with a NaN coordinate fails every box test and gets 0 from the definition itself.  Four-wide walk
+ *   only (lbvh_debug_ray_walker does not apply): one lane walks its point's directions one after the other, the rays are
+ *   made on the fly (never written to memory) and d_parity[k] is written with one plain store per point — the caller does
+ *   not pre-zero it.  h_dirs: n_dirs x 3 floats on the host, read during the call; need not be unit length.
+ * Why the count does not depend on the walk (the argument of the accept rule at the traversal flavours above, without the
+ * shrinking bound): every box of the derived tree, binary or four-wide, is the exact min / max union of what lies below it and
+ * the slab arithmetic is monotone, so every ancestor of a candidate's leaf passes its slab test with entry <= e <= t < T.  The
+ * walk may therefore skip only boxes that the ray misses, or whose entry is > T; it must never prune on the exit distance,
+ * since a candidate's computed t may lie beyond its own box's exit.  Each triangle is exactly one leaf, so each candidate is
+ * counted exactly once.
+ * Both need the derived traversal scene (lbvh_build_fast_scene; a stale one is LBVH_ERR_INVALID_ARG), are asynchronous on the
+ * context's stream, and use the context's ray scratch: they drop the path tracer's live-path list (see lbvh_path_bounce).
+ * count == 0 is a no-op.  Rejected: NULL pointers (h_dirs included), d_rays or d_points not 16-byte aligned, d_counts or
+ * d_parity not 4-byte aligned, count > 2^32 - 1, n_dirs outside 1 .. LBVH_CROSSING_MAX_DIRS, a direction with a non-finite
+ * component or with all three components zero. */
+lbvh_status lbvh_count_hits(lbvh_context* ctx, const lbvh_ray* d_rays, size_t count, const lbvh_scene* h_scene,
+                            uint32_t* d_counts);
+
+#define LBVH_CROSSING_MAX_DIRS 32
+lbvh_status lbvh_point_crossings(lbvh_context* ctx, const lbvh_point_query* d_points, size_t count,
+                                 const float* h_dirs /* n_dirs x 3 */, uint32_t n_dirs, const lbvh_scene* h_scene,
+                                 uint32_t* d_parity);
+
 /* Camera rays into path states (origin/dir as Raytracing.compute:108-126, throughput 1, radiance 0, alive). */
 lbvh_status lbvh_path_begin(lbvh_context* ctx, const lbvh_camera* h_camera, lbvh_path_state* d_states);
 
@@ -673,7 +706,7 @@ lbvh_status lbvh_path_scatter(lbvh_context* ctx, const lbvh_scene* h_scene, cons
  * lbvh_path_bounce on the same d_states / d_hits listed as live (a list kept by the context).  Every library call that writes
  * into those buffers drops the list (lbvh_path_begin, lbvh_trace_rays, a primary trace into any part of d_hits,
  * lbvh_buffer_upload / _fill_u32 / _free), and so does lbvh_trace_forget — and so do lbvh_trace_closest,
- * lbvh_trace_occluded, lbvh_closest_point_query and lbvh_within_distance, whatever buffers they are given, since they use the same ray scratch; then every state is scanned again.  What the library
+ * lbvh_trace_occluded, lbvh_closest_point_query, lbvh_within_distance, lbvh_count_hits and lbvh_point_crossings, whatever buffers they are given, since they use the same ray scratch; then every state is scanned again.  What the library
  * cannot see is a write of the CALLER's own (a kernel or hipMemcpy that revives or ends paths, Russian roulette): between two
  * consecutive bounces of a frame d_states and d_hits must not be written from outside the library — or lbvh_trace_forget must be
  * called after such a write. */

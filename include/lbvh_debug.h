@@ -54,7 +54,9 @@ lbvh_status lbvh_debug_ray_stack_split(lbvh_context* ctx, uint32_t lds_entries);
  * lbvh_path_bounce, lbvh_path_first_bounce) ADDS what it did to it: rays walked, 128-byte four-wide node lines fetched (one per
  * ray-step), triangle lines fetched and tested.  Zero it yourself; NULL switches the counting off (the default: the counting
  * kernels are separate instantiations, the product's carry none of it).  lbvh_closest_point_query and lbvh_within_distance count
- * too: `rays` = active queries walked, node lines per query-step, triangle lines tested. */
+ * too: `rays` = active queries walked, node lines per query-step, triangle lines tested.  So do lbvh_trace_closest,
+ * lbvh_trace_occluded and lbvh_count_hits on the four-wide walks (`rays` = active rays), and lbvh_point_crossings (`rays` = one
+ * per (point, direction) pair). */
 typedef struct lbvh_ray_stats {
     uint64_t rays;
     uint64_t node_fetches;
@@ -72,7 +74,8 @@ lbvh_status lbvh_debug_ray_stack_limit(lbvh_context* ctx, uint32_t deep_entries)
  * largest children opened, made on first use after a rebuild; from bounce 1 on lbvh_path_bounce takes the kernel that keeps
  * a step's two fetches in flight at once: few live rays, the launch is the chain of its longest), 2: that kernel for every
  * launch, 0: the binary nodes the packet walk uses.  Hit records do not depend on it (ties go to the lower triangle index
- * on all three).  The point queries (lbvh_closest_point_query, lbvh_within_distance) have the four-wide walk only: this hook
+ * on all three); nor do the counts of lbvh_count_hits, which this hook steers as it steers lbvh_trace_closest.  The point
+ * queries (lbvh_closest_point_query, lbvh_within_distance, lbvh_point_crossings) have the four-wide walk only: this hook
  * leaves them alone.  lbvh_debug_ray_stack_split and lbvh_debug_ray_stack_limit apply to them as to the four-wide ray walk. */
 lbvh_status lbvh_debug_ray_walker(lbvh_context* ctx, uint32_t walker);
 

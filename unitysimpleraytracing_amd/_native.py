@@ -95,6 +95,8 @@ SIGNATURES = {
     "lbvh_trace_occluded": (_I32, [_P, _P, _SZ, C.POINTER(Scene), _P]),
     "lbvh_closest_point_query": (_I32, [_P, _P, _SZ, C.POINTER(Scene), _P]),
     "lbvh_within_distance": (_I32, [_P, _P, _SZ, C.POINTER(Scene), _P]),
+    "lbvh_count_hits": (_I32, [_P, _P, _SZ, C.POINTER(Scene), _P]),
+    "lbvh_point_crossings": (_I32, [_P, _P, _SZ, C.POINTER(C.c_float), _U32, C.POINTER(Scene), _P]),
     "lbvh_path_begin": (_I32, [_P, C.POINTER(Camera), _P]),
     "lbvh_path_scatter": (_I32, [_P, C.POINTER(Scene), _P, _SZ, _U32, _U32, C.c_float, _P]),
     "lbvh_path_bounce": (_I32, [_P, C.POINTER(Scene), _P, _P, _SZ, _U32, _U32, C.c_float, C.c_float]),

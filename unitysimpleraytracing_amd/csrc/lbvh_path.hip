@@ -3,6 +3,7 @@
 // primary rays of a static mesh only.  Definitions: include/lbvh.h; bit-exact checker: oracle/.
 // Strict fp32 (-ffp-contract=off), no device trig, counter-based RNG.
 #include <algorithm>
+#include <cmath>
 #include <cstdlib>
 #include <type_traits>
 #include "lbvh_common.h"
@@ -113,22 +114,26 @@ static inline uint32_t* ray_list(lbvh_context* ctx, size_t count, uint32_t turn)
 static inline uint32_t* deep_stacks(lbvh_context* ctx, size_t count) { return (uint32_t*)((char*)ctx->ray_scratch + 256 + 2 * list_bytes(count)); }
 static inline size_t ray_scratch_bytes_for(size_t count) { return 256 + 2 * list_bytes(count) + deep_bytes(count); }
 
-// The three walkers below serve two ray sources and two queries (template arguments PLAIN, ANY):
+// The three walkers below serve two ray sources and three queries (template arguments PLAIN, Q):
 //   PLAIN = false: path states, the live ones listed in `list` (*n_alive of them), one t_min for all (lbvh_trace_rays, the bounces)
 //   PLAIN = true:  lbvh_ray records, ray k of the call to the lane directly (n_alive = the count), per-ray [t_min, t_max);
 //                  a ray with !(t_min < t_max) gets its result when it is loaded and leaves the lane idle for the next refill
-//   ANY = false:   the closest candidate's lbvh_hit; ANY = true: a uint32_t flag, 1 as soon as any candidate is accepted (the
-//                  closest-hit walk cut off there: the same near-first order, the rest of that step's leaves skipped)
+//   Q = kClosest:  the closest candidate's lbvh_hit; kAny: a uint32_t flag, 1 as soon as any candidate is accepted (the
+//                  closest-hit walk cut off there: the same near-first order, the rest of that step's leaves skipped);
+//   kCount:        a uint32_t, the number of candidates (plain rays only): best_t stays T, every accepted candidate adds one and
+//                  the walk ends with an empty stack.  Boxes are skipped as in the other two, when missed or entered beyond T,
+//                  never on their exit distance (a candidate's t may lie beyond its own box's exit)
+enum walk_query : int { kClosest = 0, kAny = 1, kCount = 2 };
 template <bool PLAIN> using walk_src = std::conditional_t<PLAIN, lbvh_ray, lbvh_path_state>;
 template <bool PLAIN> using walk_total = std::conditional_t<PLAIN, uint32_t, const uint32_t* __restrict__>;
-template <bool ANY> using walk_out = std::conditional_t<ANY, uint32_t, lbvh_hit>;
+template <int Q> using walk_out = std::conditional_t<Q != kClosest, uint32_t, lbvh_hit>;
 __device__ __forceinline__ uint32_t walk_count(uint32_t count) { return count; }
 __device__ __forceinline__ uint32_t walk_count(const uint32_t* n_alive) { return *n_alive; }
 
 // plain ray k into the lane (lo = t_min, best_t = T): false (result written, lane stays idle) for an inactive ray
-template <bool ANY>
+template <int Q>
 __device__ __forceinline__ bool load_plain_ray(const lbvh_ray* __restrict__ rays, uint32_t k, ray_t& ray, float& lo, float& best_t,
-                                               walk_out<ANY>* __restrict__ out)
+                                               walk_out<Q>* __restrict__ out)
 {
     const float4* r = reinterpret_cast<const float4*>(&rays[k]);
     const float4 o = r[0], d = r[1];
@@ -138,7 +143,7 @@ __device__ __forceinline__ bool load_plain_ray(const lbvh_ray* __restrict__ rays
     lo = o.w;
     best_t = fminf(d.w, LBVH_MAX_FLOAT);                 // T: candidates lie in (t_min, T)
     if (o.w < d.w) return true;                          // false for NaN bounds too
-    if constexpr (ANY) out[k] = 0u;
+    if constexpr (Q != kClosest) out[k] = 0u;
     else reinterpret_cast<float4*>(out)[k] = make_float4(LBVH_MAX_FLOAT, __uint_as_float(0u), 0.0f, 0.0f);
     return false;
 }
@@ -156,16 +161,17 @@ __device__ __forceinline__ void put_hit(lbvh_hit* __restrict__ hits, size_t i, f
     reinterpret_cast<float4*>(hits)[i] = out;
 }
 
-template <bool PLAIN, bool ANY>
+template <bool PLAIN, int Q>
 __global__ __launch_bounds__(64) void trace_rays_kernel(const walk_src<PLAIN>* __restrict__ states, walk_total<PLAIN> n_alive,
                                                         const uint32_t* __restrict__ list, float t_min,
                                                         const lbvh_fast_node* __restrict__ nodes,
-                                                        const lbvh_fast_tri* __restrict__ tris, walk_out<ANY>* __restrict__ hits,
+                                                        const lbvh_fast_tri* __restrict__ tris, walk_out<Q>* __restrict__ hits,
                                                         uint32_t* __restrict__ deep,     // [gridDim.x][kRayStackDeep][64]
                                                         uint32_t lds_depth,              // <= kRayStackLds
                                                         uint32_t deep_cap,               // <= kRayStackDeep (lbvh_debug_ray_stack_limit lowers it)
                                                         uint32_t* __restrict__ fault)    // mapped host word: a stack that ran out says so here
 {
+    constexpr bool ANY = Q == kAny, COUNT = Q == kCount;
     __shared__ uint32_t s_stack[kRayStackLds][LBVH_WAVE];
     uint32_t* my_deep = deep + (size_t)blockIdx.x * (kRayStackDeep * LBVH_WAVE) + threadIdx.x;
     const uint32_t lane = threadIdx.x;
@@ -184,6 +190,7 @@ __global__ __launch_bounds__(64) void trace_rays_kernel(const walk_src<PLAIN>* _
     bool took = false;                                   // plain rays: a candidate was accepted (else best_t is still that bound)
     float best_t = LBVH_MAX_FLOAT, best_u = 0.0f, best_v = 0.0f;
     uint32_t best_tri = 0, sp = 0, node = 0;
+    uint32_t n_hit = 0;                                  // COUNT: candidates accepted so far
     for (;;) {
         // refill idle lanes from the chunk
         const uint64_t idle = __ballot(!active);
@@ -193,9 +200,10 @@ __global__ __launch_bounds__(64) void trace_rays_kernel(const walk_src<PLAIN>* _
                 if (k < end) {
                     if constexpr (PLAIN) {
                         i = k;
-                        active = load_plain_ray<ANY>(states, k, ray, lo, best_t, hits);
+                        active = load_plain_ray<Q>(states, k, ray, lo, best_t, hits);
                         best_tri = 0; best_u = 0.0f; best_v = 0.0f; took = false;
                         sp = 0; node = 0;
+                        if constexpr (COUNT) n_hit = 0;
                     } else {
                         i = list[k];
                         const float4* st = reinterpret_cast<const float4*>(&states[i]);
@@ -230,7 +238,9 @@ __global__ __launch_bounds__(64) void trace_rays_kernel(const walk_src<PLAIN>* _
                     float u = 0.0f, v = 0.0f;
                     const float dist = ray_fast_triangle(ray, v0, v1, v2, u, v);
                     const uint32_t tri = __float_as_uint(v0.w);
-                    if (dist > lo && hit_counts(dist, side == 0 ? tl : tr) && (dist < best_t || (dist == best_t && tri < best_tri))) {
+                    if constexpr (COUNT) {
+                        if (dist > lo && hit_counts(dist, side == 0 ? tl : tr) && dist < best_t) n_hit++;
+                    } else if (dist > lo && hit_counts(dist, side == 0 ? tl : tr) && (dist < best_t || (dist == best_t && tri < best_tri))) {
                         if constexpr (ANY) found = true;
                         else { best_t = dist; best_tri = tri; best_u = u; best_v = v; took = true; }
                     }
@@ -256,7 +266,8 @@ __global__ __launch_bounds__(64) void trace_rays_kernel(const walk_src<PLAIN>* _
                 sp--;
                 node = sp < lds_depth ? s_stack[sp][lane] : my_deep[(sp - lds_depth) * LBVH_WAVE];
             } else {
-                if constexpr (ANY) hits[i] = 0u;
+                if constexpr (COUNT) hits[i] = n_hit;
+                else if constexpr (ANY) hits[i] = 0u;
                 else put_hit<PLAIN>(hits, i, best_t, took, best_tri, best_u, best_v);
                 active = false;
             }
@@ -366,16 +377,17 @@ __device__ __forceinline__ void add_ray_stats(lbvh_ray_stats* stats, uint32_t ra
 }
 
 // Same frame as trace_rays_kernel (lane refill from the wave's run of live rays, LDS + device-memory stack).
-template <bool PLAIN, bool ANY, bool STATS>
+template <bool PLAIN, int Q, bool STATS>
 __global__ __launch_bounds__(64) void trace_rays_wide_kernel(const walk_src<PLAIN>* __restrict__ states, walk_total<PLAIN> n_alive,
                                                              const uint32_t* __restrict__ list, float t_min,
                                                              const lbvh_wide_node* __restrict__ wide,
-                                                             const lbvh_fast_node* __restrict__ lines, walk_out<ANY>* __restrict__ hits,
+                                                             const lbvh_fast_node* __restrict__ lines, walk_out<Q>* __restrict__ hits,
                                                              uint32_t* __restrict__ deep,     // [gridDim.x][kWideStackDeep][64]
                                                              uint32_t lds_depth,              // <= kWideStackLds
                                                              uint32_t deep_cap,               // <= kWideStackDeep
                                                              uint32_t* __restrict__ fault, lbvh_ray_stats* stats)
 {
+    constexpr bool ANY = Q == kAny, COUNT = Q == kCount;
     __shared__ uint32_t s_stack[kWideStackLds][LBVH_WAVE];
     uint32_t* my_deep = deep + (size_t)blockIdx.x * (kWideStackDeep * LBVH_WAVE) + threadIdx.x;
     const uint32_t lane = threadIdx.x;
@@ -393,6 +405,7 @@ __global__ __launch_bounds__(64) void trace_rays_wide_kernel(const walk_src<PLAI
     bool took = false;
     float best_t = LBVH_MAX_FLOAT, best_u = 0.0f, best_v = 0.0f;
     uint32_t best_tri = 0, sp = 0, node = 0;
+    uint32_t n_hit = 0;                                  // COUNT: candidates accepted so far
     auto push = [&](uint32_t ref) {
         if (sp < lds_depth) { s_stack[sp][lane] = ref; sp++; }
         else if (sp < lds_depth + deep_cap) { my_deep[(sp - lds_depth) * LBVH_WAVE] = ref; sp++; }
@@ -408,9 +421,10 @@ __global__ __launch_bounds__(64) void trace_rays_wide_kernel(const walk_src<PLAI
                 if (k < end) {
                     if constexpr (PLAIN) {
                         i = k;
-                        active = load_plain_ray<ANY>(states, k, ray, lo, best_t, hits);
+                        active = load_plain_ray<Q>(states, k, ray, lo, best_t, hits);
                         best_tri = 0; best_u = 0.0f; best_v = 0.0f; took = false;
                         sp = 0; node = 0;
+                        if constexpr (COUNT) n_hit = 0;
                         if (STATS && active) n_rays++;
                     } else {
                         i = list[k];
@@ -454,7 +468,9 @@ __global__ __launch_bounds__(64) void trace_rays_wide_kernel(const walk_src<PLAI
                 const uint32_t tri = __float_as_uint(v0.w);
                 const float entry = k == 0u ? t0 : (k == 1u ? t1 : (k == 2u ? t2 : t3));
                 // ties go to the lower triangle index, whatever order the leaves are met in (as in the packet walk)
-                if (dist > lo && hit_counts(dist, entry) && (dist < best_t || (dist == best_t && tri < best_tri))) {
+                if constexpr (COUNT) {
+                    if (dist > lo && hit_counts(dist, entry) && dist < best_t) n_hit++;
+                } else if (dist > lo && hit_counts(dist, entry) && (dist < best_t || (dist == best_t && tri < best_tri))) {
                     if constexpr (ANY) { found = true; break; }
                     else { best_t = dist; best_tri = tri; best_u = u; best_v = v; took = true; }
                 }
@@ -471,7 +487,7 @@ __global__ __launch_bounds__(64) void trace_rays_wide_kernel(const walk_src<PLAI
             uint32_t k1 = h1 && !(ref.y >> 31) && !(t1 > best_t) ? ((__float_as_uint(fmaxf(t1, 0.0f)) & ~3u) | 1u) : none;
             uint32_t k2 = h2 && !(ref.z >> 31) && !(t2 > best_t) ? ((__float_as_uint(fmaxf(t2, 0.0f)) & ~3u) | 2u) : none;
             uint32_t k3 = h3 && !(ref.w >> 31) && !(t3 > best_t) ? ((__float_as_uint(fmaxf(t3, 0.0f)) & ~3u) | 3u) : none;
-            {   // five compare-exchanges
+            {   // five compare-exchanges (a count does not need the order; kept: the same three waiting siblings per level at most)
                 uint32_t a, b;
                 a = min(k0, k1); b = max(k0, k1); k0 = a; k1 = b;
                 a = min(k2, k3); b = max(k2, k3); k2 = a; k3 = b;
@@ -488,7 +504,8 @@ __global__ __launch_bounds__(64) void trace_rays_wide_kernel(const walk_src<PLAI
                 sp--;
                 node = sp < lds_depth ? s_stack[sp][lane] : my_deep[(sp - lds_depth) * LBVH_WAVE];
             } else {
-                if constexpr (ANY) hits[i] = 0u;
+                if constexpr (COUNT) hits[i] = n_hit;
+                else if constexpr (ANY) hits[i] = 0u;
                 else put_hit<PLAIN>(hits, i, best_t, took, best_tri, best_u, best_v);
                 active = false;
             }
@@ -501,16 +518,17 @@ __global__ __launch_bounds__(64) void trace_rays_wide_kernel(const walk_src<PLAI
 // thousand live rays, most of the chip idle for most of the launch): the next node is chosen BEFORE the step's triangles are
 // tested and requested together with the first triangle line, so the two fetches of a step are in flight at once.  84 VGPRs
 // (5 waves per SIMD instead of 8): the price where every wave slot is needed, none where they are not.
-template <bool PLAIN, bool ANY, bool STATS>
+template <bool PLAIN, int Q, bool STATS>
 __global__ __launch_bounds__(64) void trace_rays_wide_chain_kernel(const walk_src<PLAIN>* __restrict__ states, walk_total<PLAIN> n_alive,
                                                              const uint32_t* __restrict__ list, float t_min,
                                                              const lbvh_wide_node* __restrict__ wide,
-                                                             const lbvh_fast_node* __restrict__ lines, walk_out<ANY>* __restrict__ hits,
+                                                             const lbvh_fast_node* __restrict__ lines, walk_out<Q>* __restrict__ hits,
                                                              uint32_t* __restrict__ deep,     // [gridDim.x][kWideStackDeep][64]
                                                              uint32_t lds_depth,              // <= kWideStackLds
                                                              uint32_t deep_cap,               // <= kWideStackDeep
                                                              uint32_t* __restrict__ fault, lbvh_ray_stats* stats)
 {
+    constexpr bool ANY = Q == kAny, COUNT = Q == kCount;
     __shared__ uint32_t s_stack[kWideStackLds][LBVH_WAVE];
     uint32_t* my_deep = deep + (size_t)blockIdx.x * (kWideStackDeep * LBVH_WAVE) + threadIdx.x;
     const uint32_t lane = threadIdx.x;
@@ -528,6 +546,7 @@ __global__ __launch_bounds__(64) void trace_rays_wide_chain_kernel(const walk_sr
     bool took = false;
     float best_t = LBVH_MAX_FLOAT, best_u = 0.0f, best_v = 0.0f;
     uint32_t best_tri = 0, sp = 0, node = 0;
+    uint32_t n_hit = 0;                      // COUNT: candidates accepted so far
     float4 lox = {}, loy = {}, loz = {}, hix = {}, hiy = {}, hiz = {};
     uint4 ref = {};
     auto push = [&](uint32_t r) {
@@ -549,10 +568,11 @@ __global__ __launch_bounds__(64) void trace_rays_wide_chain_kernel(const walk_sr
                 if (k < end) {
                     if constexpr (PLAIN) {
                         i = k;
-                        active = load_plain_ray<ANY>(states, k, ray, lo, best_t, hits);
+                        active = load_plain_ray<Q>(states, k, ray, lo, best_t, hits);
                         best_tri = 0; best_u = 0.0f; best_v = 0.0f; took = false;
                         sp = 0; node = 0;
                         have = false;
+                        if constexpr (COUNT) n_hit = 0;
                         if (STATS && active) n_rays++;
                     } else {
                         i = list[k];
@@ -637,7 +657,9 @@ __global__ __launch_bounds__(64) void trace_rays_wide_chain_kernel(const walk_sr
             const float dist = ray_triangle_edges(ray, q0, q2.x, q2.y, q2.z, q1.w, q2.w, q3.w, u, v);
             const uint32_t tri = __float_as_uint(q0.w);
             // ties go to the lower triangle index, whatever order the leaves are met in (as in the packet walk)
-            if (dist > lo && hit_counts(dist, entry) && (dist < best_t || (dist == best_t && tri < best_tri))) {
+            if constexpr (COUNT) {
+                if (dist > lo && hit_counts(dist, entry) && dist < best_t) n_hit++;
+            } else if (dist > lo && hit_counts(dist, entry) && (dist < best_t || (dist == best_t && tri < best_tri))) {
                 if constexpr (ANY) { found = true; break; }
                 else { best_t = dist; best_tri = tri; best_u = u; best_v = v; took = true; }
             }
@@ -650,7 +672,8 @@ __global__ __launch_bounds__(64) void trace_rays_wide_chain_kernel(const walk_sr
             if constexpr (ANY) hits[i] = 1u;
             active = false;
         } else if (done) {
-            if constexpr (ANY) hits[i] = 0u;
+            if constexpr (COUNT) hits[i] = n_hit;
+            else if constexpr (ANY) hits[i] = 0u;
             else put_hit<PLAIN>(hits, i, best_t, took, best_tri, best_u, best_v);
             active = false;
         }
@@ -842,6 +865,121 @@ __global__ __launch_bounds__(64) void point_query_wide_kernel(const lbvh_point_q
     if (STATS) add_ray_stats(stats, n_queries, n_steps, n_tris);
 }
 
+// ---- crossing parities of points along fixed directions (lbvh_point_crossings, include/lbvh.h) -------------------------
+// The directions travel by value in the kernel's arguments; a lane reads the one it walks next from there.
+struct crossing_dirs { float d[LBVH_CROSSING_MAX_DIRS][3]; };
+
+// One POINT per lane over the four-wide nodes, in the frame of trace_rays_wide_kernel<PLAIN> (persistent waves, lanes refilled
+// from the wave's run of consecutive points, LDS + device-memory stack).  The lane walks the rays {p, t_min = 0, dirs[j],
+// T = LBVH_MAX_FLOAT} for j = 0 .. n_dirs - 1 one after the other: the count walk of the ray walkers (best_t stays T, every
+// candidate adds one, the walk ends with an empty stack), each finished count's lowest bit kept in a register and the point's
+// word stored once, after its last direction.  No ray is written to memory.  The children to enter are taken in slot order: a
+// count does not depend on the order, and at most three siblings wait per level as in the other walks.
+// amdgpu_waves_per_eu(8): without it the lane-indexed direction and the point / direction / parity registers took 66 VGPRs
+// (7 waves per SIMD) and the walk was slower than lbvh_count_hits on the same rays written out
+template <bool STATS>
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(8, 8))) void point_crossings_wide_kernel(const lbvh_point_query* __restrict__ points, uint32_t total,
+                                                                  const crossing_dirs dirs, uint32_t n_dirs,
+                                                                  const lbvh_wide_node* __restrict__ wide,
+                                                                  const lbvh_fast_node* __restrict__ lines, uint32_t* __restrict__ parity,
+                                                                  uint32_t* __restrict__ deep,     // [gridDim.x][kWideStackDeep][64]
+                                                                  uint32_t lds_depth,              // <= kWideStackLds
+                                                                  uint32_t deep_cap,               // <= kWideStackDeep
+                                                                  uint32_t* __restrict__ fault, lbvh_ray_stats* stats)
+{
+    __shared__ uint32_t s_stack[kWideStackLds][LBVH_WAVE];
+    uint32_t* my_deep = deep + (size_t)blockIdx.x * (kWideStackDeep * LBVH_WAVE) + threadIdx.x;
+    const uint32_t lane = threadIdx.x;
+    const uint32_t run = max((total + gridDim.x - 1) / gridDim.x, 32u);
+    uint32_t next = blockIdx.x * run;
+    if (next >= total) return;
+    const uint32_t end = min(next + run, total);
+    uint32_t n_rays = 0, n_steps = 0, n_tris = 0;
+
+    bool active = false;
+    uint32_t i = 0, j = 0, bits = 0, n_hit = 0;          // point, direction, parities so far, candidates of direction j so far
+    ray_t ray = {};
+    uint32_t sp = 0, node = 0;
+    auto push = [&](uint32_t ref) {
+        if (sp < lds_depth) { s_stack[sp][lane] = ref; sp++; }
+        else if (sp < lds_depth + deep_cap) { my_deep[(sp - lds_depth) * LBVH_WAVE] = ref; sp++; }
+        // a dropped entry would be a silently wrong count: report it, as the ray walkers do (lbvh_debug_ray_stack_limit provokes it)
+        else __hip_atomic_store(fault, LBVH_FAULT_RAY_STACK, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    };
+    auto aim = [&](uint32_t jj) {                        // direction jj from the lane's point: a fresh walk
+        ray.dx = dirs.d[jj][0]; ray.dy = dirs.d[jj][1]; ray.dz = dirs.d[jj][2];
+        ray.ix = 1.0f / ray.dx; ray.iy = 1.0f / ray.dy; ray.iz = 1.0f / ray.dz;
+        sp = 0; node = 0; n_hit = 0;
+        if (STATS) n_rays++;
+    };
+    for (;;) {
+        const uint64_t idle = __ballot(!active);
+        if (idle != 0 && next < end) {
+            if (!active) {
+                const uint32_t k = next + mbcnt64(idle);
+                if (k < end) {
+                    i = k;
+                    const float4 p = reinterpret_cast<const float4*>(points)[k];     // max_dist2 (.w) is not read
+                    ray.ox = p.x; ray.oy = p.y; ray.oz = p.z;
+                    j = 0; bits = 0;
+                    aim(0u);
+                    active = true;
+                }
+            }
+            next += (uint32_t)__popcll(idle);
+        }
+        if (!__any(active) && next >= end) break;
+        if (active) {
+            if (STATS) n_steps++;
+            const float4* w = reinterpret_cast<const float4*>(&wide[node]);
+            const float4 lox = w[0], loy = w[1], loz = w[2], hix = w[3], hiy = w[4], hiz = w[5];
+            const uint4 ref = reinterpret_cast<const uint4*>(w)[6];
+            float t0, t1, t2, t3;
+            // T = min(+inf, LBVH_MAX_FLOAT): a box entered beyond it holds no candidate
+            const bool h0 = wide_box(lox.x, loy.x, loz.x, hix.x, hiy.x, hiz.x, ray, t0) && !(t0 > LBVH_MAX_FLOAT) && ref.x != kWideEmpty;
+            const bool h1 = wide_box(lox.y, loy.y, loz.y, hix.y, hiy.y, hiz.y, ray, t1) && !(t1 > LBVH_MAX_FLOAT) && ref.y != kWideEmpty;
+            const bool h2 = wide_box(lox.z, loy.z, loz.z, hix.z, hiy.z, hiz.z, ray, t2) && !(t2 > LBVH_MAX_FLOAT) && ref.z != kWideEmpty;
+            const bool h3 = wide_box(lox.w, loy.w, loz.w, hix.w, hiy.w, hiz.w, ray, t3) && !(t3 > LBVH_MAX_FLOAT) && ref.w != kWideEmpty;
+            uint32_t leaves = (h0 && (ref.x >> 31) ? 1u : 0u) | (h1 && (ref.y >> 31) ? 2u : 0u) | (h2 && (ref.z >> 31) ? 4u : 0u) |
+                              (h3 && (ref.w >> 31) ? 8u : 0u);
+            while (leaves != 0u) {
+                const uint32_t k = (uint32_t)__builtin_ctz(leaves);
+                leaves &= leaves - 1u;
+                if (STATS) n_tris++;
+                float4 v0, v1, v2;
+                unpack_fast_triangle(reinterpret_cast<const float4*>(&lines[pick4(ref, k) & 0x7FFFFFFFu]), v0, v1, v2);
+                float u = 0.0f, v = 0.0f;
+                const float dist = ray_fast_triangle(ray, v0, v1, v2, u, v);
+                const float entry = k == 0u ? t0 : (k == 1u ? t1 : (k == 2u ? t2 : t3));
+                if (dist > 0.0f && hit_counts(dist, entry) && dist < LBVH_MAX_FLOAT) n_hit++;
+            }
+            // nodes to enter, in slot order: the first is walked next, the others wait
+            constexpr uint32_t none = 0xFFFFFFFFu;
+            uint32_t go = none;
+            if (h0 && !(ref.x >> 31)) go = ref.x;
+            if (h1 && !(ref.y >> 31)) { if (go != none) push(go); go = ref.y; }
+            if (h2 && !(ref.z >> 31)) { if (go != none) push(go); go = ref.z; }
+            if (h3 && !(ref.w >> 31)) { if (go != none) push(go); go = ref.w; }
+            if (go != none) {
+                node = go;
+            } else if (sp != 0) {
+                sp--;
+                node = sp < lds_depth ? s_stack[sp][lane] : my_deep[(sp - lds_depth) * LBVH_WAVE];
+            } else {
+                bits |= (n_hit & 1u) << j;
+                j++;
+                if (j < n_dirs) {
+                    aim(j);
+                } else {
+                    parity[i] = bits;
+                    active = false;
+                }
+            }
+        }
+    }
+    if (STATS) add_ray_stats(stats, n_rays, n_steps, n_tris);
+}
+
 // ---- bounce ----------------------------------------------------------------------------------------------
 __device__ __forceinline__ uint32_t pcg_hash(uint32_t v)
 {
@@ -1024,9 +1162,9 @@ static lbvh_status ensure_wide_nodes(lbvh_context* ctx)
 // the walk over the live rays of `list` (or over plain rays, PLAIN: `total` is their count): four-wide nodes (made on first use
 // after a rebuild) — few_rays: with the kernel that keeps two fetches of a step in flight (the later bounces of a frame) —, or the
 // binary nodes the packet walk uses (lbvh_debug_ray_walker(ctx, 0): the cross-check of the tests; 2: the few-rays kernel for every launch)
-template <bool PLAIN, bool ANY>
+template <bool PLAIN, int Q>
 static lbvh_status launch_ray_walk(lbvh_context* ctx, const walk_src<PLAIN>* d_states, walk_total<PLAIN> n_alive, const uint32_t* list,
-                                   float t_min, walk_out<ANY>* d_hits, size_t count, bool few_rays = false)
+                                   float t_min, walk_out<Q>* d_hits, size_t count, bool few_rays = false)
 {
     const uint32_t ray_waves = ray_waves_of(count);
     if (ctx->ray_walker != 0u) {
@@ -1036,33 +1174,33 @@ static lbvh_status launch_ray_walk(lbvh_context* ctx, const walk_src<PLAIN>* d_s
         lbvh_ray_stats* st = ctx->ray_stats;
         const lbvh_wide_node* wn = (const lbvh_wide_node*)ctx->wide_nodes;
         if (few_rays || ctx->ray_walker == 2u) {
-            if (st) LBVH_LAUNCH(ctx, (trace_rays_wide_chain_kernel<PLAIN, ANY, true>), dim3(ray_waves), dim3(LBVH_WAVE), d_states, n_alive, list, t_min, wn,
+            if (st) LBVH_LAUNCH(ctx, (trace_rays_wide_chain_kernel<PLAIN, Q, true>), dim3(ray_waves), dim3(LBVH_WAVE), d_states, n_alive, list, t_min, wn,
                                 ctx->fast_nodes, d_hits, deep_stacks(ctx, count), lds, deep_cap, ctx->fault_dev, st);
-            else LBVH_LAUNCH(ctx, (trace_rays_wide_chain_kernel<PLAIN, ANY, false>), dim3(ray_waves), dim3(LBVH_WAVE), d_states, n_alive, list, t_min, wn,
+            else LBVH_LAUNCH(ctx, (trace_rays_wide_chain_kernel<PLAIN, Q, false>), dim3(ray_waves), dim3(LBVH_WAVE), d_states, n_alive, list, t_min, wn,
                              ctx->fast_nodes, d_hits, deep_stacks(ctx, count), lds, deep_cap, ctx->fault_dev, st);
         } else {
-            if (st) LBVH_LAUNCH(ctx, (trace_rays_wide_kernel<PLAIN, ANY, true>), dim3(ray_waves), dim3(LBVH_WAVE), d_states, n_alive, list, t_min, wn,
+            if (st) LBVH_LAUNCH(ctx, (trace_rays_wide_kernel<PLAIN, Q, true>), dim3(ray_waves), dim3(LBVH_WAVE), d_states, n_alive, list, t_min, wn,
                                 ctx->fast_nodes, d_hits, deep_stacks(ctx, count), lds, deep_cap, ctx->fault_dev, st);
-            else LBVH_LAUNCH(ctx, (trace_rays_wide_kernel<PLAIN, ANY, false>), dim3(ray_waves), dim3(LBVH_WAVE), d_states, n_alive, list, t_min, wn,
+            else LBVH_LAUNCH(ctx, (trace_rays_wide_kernel<PLAIN, Q, false>), dim3(ray_waves), dim3(LBVH_WAVE), d_states, n_alive, list, t_min, wn,
                              ctx->fast_nodes, d_hits, deep_stacks(ctx, count), lds, deep_cap, ctx->fault_dev, st);
         }
     } else {
-        LBVH_LAUNCH(ctx, (trace_rays_kernel<PLAIN, ANY>), dim3(ray_waves), dim3(LBVH_WAVE), d_states, n_alive, list, t_min, ctx->fast_nodes,
+        LBVH_LAUNCH(ctx, (trace_rays_kernel<PLAIN, Q>), dim3(ray_waves), dim3(LBVH_WAVE), d_states, n_alive, list, t_min, ctx->fast_nodes,
                     ctx->fast_tris, d_hits, deep_stacks(ctx, count), ctx->ray_stack_lds, std::min<uint32_t>(ctx->ray_stack_deep, kRayStackDeep), ctx->fault_dev);
     }
     LBVH_HIP_TRY(ctx, hipGetLastError());
     return LBVH_OK;
 }
 
-// lbvh_trace_closest / lbvh_trace_occluded: plain rays by direct index, no live-ray list
-template <bool ANY>
+// lbvh_trace_closest / lbvh_trace_occluded / lbvh_count_hits: plain rays by direct index, no live-ray list
+template <int Q>
 static lbvh_status trace_plain_rays(lbvh_context* ctx, const lbvh_ray* d_rays, size_t count, const lbvh_scene* h_scene,
-                                    walk_out<ANY>* d_out, const char* who)
+                                    walk_out<Q>* d_out, const char* who)
 {
     if (!ctx) return LBVH_ERR_INVALID_ARG;
     if (count == 0) return LBVH_OK;
     LBVH_REQUIRE(ctx, d_rays != nullptr && h_scene != nullptr && d_out != nullptr);
-    LBVH_REQUIRE(ctx, ((uintptr_t)d_rays & 15) == 0 && ((uintptr_t)d_out & (ANY ? 3 : 15)) == 0);
+    LBVH_REQUIRE(ctx, ((uintptr_t)d_rays & 15) == 0 && ((uintptr_t)d_out & (Q != kClosest ? 3 : 15)) == 0);
     LBVH_REQUIRE(ctx, count <= 0xFFFFFFFFull);
     {
         const int frc = lbvh_require_fast(ctx, *h_scene, who);
@@ -1073,7 +1211,7 @@ static lbvh_status trace_plain_rays(lbvh_context* ctx, const lbvh_ray* d_rays, s
     int rc = lbvh_reserve(ctx, &ctx->ray_scratch, &ctx->ray_scratch_bytes, ray_scratch_bytes_for(count));
     if (rc != LBVH_OK) return rc;
     ctx->ray_list.valid = false;
-    return launch_ray_walk<true, ANY>(ctx, d_rays, (uint32_t)count, nullptr, 0.0f, d_out, count);
+    return launch_ray_walk<true, Q>(ctx, d_rays, (uint32_t)count, nullptr, 0.0f, d_out, count);
 }
 
 // lbvh_closest_point_query / lbvh_within_distance: always the four-wide walk (lbvh_debug_ray_walker does not apply)
@@ -1107,7 +1245,51 @@ static lbvh_status point_queries(lbvh_context* ctx, const lbvh_point_query* d_qu
     return LBVH_OK;
 }
 
+// lbvh_point_crossings: the four-wide walk only (lbvh_debug_ray_walker does not apply), the directions by value in the arguments
+static lbvh_status point_crossings(lbvh_context* ctx, const lbvh_point_query* d_points, size_t count, const float* h_dirs, uint32_t n_dirs,
+                                   const lbvh_scene* h_scene, uint32_t* d_parity)
+{
+    if (!ctx) return LBVH_ERR_INVALID_ARG;
+    if (count == 0) return LBVH_OK;
+    LBVH_REQUIRE(ctx, d_points != nullptr && h_dirs != nullptr && h_scene != nullptr && d_parity != nullptr);
+    LBVH_REQUIRE(ctx, ((uintptr_t)d_points & 15) == 0 && ((uintptr_t)d_parity & 3) == 0);
+    LBVH_REQUIRE(ctx, count <= 0xFFFFFFFFull);
+    LBVH_REQUIRE(ctx, n_dirs >= 1u && n_dirs <= (uint32_t)LBVH_CROSSING_MAX_DIRS);
+    crossing_dirs dirs = {};
+    for (uint32_t j = 0; j < n_dirs; j++) {
+        const float x = h_dirs[3 * j], y = h_dirs[3 * j + 1], z = h_dirs[3 * j + 2];
+        LBVH_REQUIRE(ctx, std::isfinite(x) && std::isfinite(y) && std::isfinite(z));
+        LBVH_REQUIRE(ctx, x != 0.0f || y != 0.0f || z != 0.0f);
+        dirs.d[j][0] = x; dirs.d[j][1] = y; dirs.d[j][2] = z;
+    }
+    {
+        const int frc = lbvh_require_fast(ctx, *h_scene, "lbvh_point_crossings");
+        if (frc != LBVH_OK) return frc;
+    }
+    LBVH_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    // the deep stack slabs of the ray scratch, laid out as for lbvh_trace_rays (whose live-path list they may overwrite)
+    int rc = lbvh_reserve(ctx, &ctx->ray_scratch, &ctx->ray_scratch_bytes, ray_scratch_bytes_for(count));
+    if (rc != LBVH_OK) return rc;
+    ctx->ray_list.valid = false;
+    rc = ensure_wide_nodes(ctx);
+    if (rc != LBVH_OK) return rc;
+    const uint32_t lds = std::min<uint32_t>(ctx->ray_stack_lds, kWideStackLds), deep_cap = std::min<uint32_t>(ctx->ray_stack_deep, kWideStackDeep);
+    const lbvh_wide_node* wn = (const lbvh_wide_node*)ctx->wide_nodes;
+    if (ctx->ray_stats) LBVH_LAUNCH(ctx, point_crossings_wide_kernel<true>, dim3(ray_waves_of(count)), dim3(LBVH_WAVE), d_points, (uint32_t)count, dirs,
+                                    n_dirs, wn, ctx->fast_nodes, d_parity, deep_stacks(ctx, count), lds, deep_cap, ctx->fault_dev, ctx->ray_stats);
+    else LBVH_LAUNCH(ctx, point_crossings_wide_kernel<false>, dim3(ray_waves_of(count)), dim3(LBVH_WAVE), d_points, (uint32_t)count, dirs,
+                     n_dirs, wn, ctx->fast_nodes, d_parity, deep_stacks(ctx, count), lds, deep_cap, ctx->fault_dev, ctx->ray_stats);
+    LBVH_HIP_TRY(ctx, hipGetLastError());
+    return LBVH_OK;
+}
+
 extern "C" {
+
+lbvh_status lbvh_point_crossings(lbvh_context* ctx, const lbvh_point_query* d_points, size_t count, const float* h_dirs, uint32_t n_dirs,
+                                 const lbvh_scene* h_scene, uint32_t* d_parity)
+{
+    return point_crossings(ctx, d_points, count, h_dirs, n_dirs, h_scene, d_parity);
+}
 
 lbvh_status lbvh_closest_point_query(lbvh_context* ctx, const lbvh_point_query* d_queries, size_t count, const lbvh_scene* h_scene,
                                      lbvh_closest_point* d_out)
@@ -1172,17 +1354,22 @@ lbvh_status lbvh_trace_rays(lbvh_context* ctx, const lbvh_path_state* d_states, 
     uint32_t* list = ray_list(ctx, count, 0);
     LBVH_HIP_TRY(ctx, hipMemsetAsync(n_alive, 0, 4, ctx->cur_stream));
     LBVH_LAUNCH(ctx, alive_rays_kernel, dim3((unsigned)((count + 255) / 256)), dim3(256), d_states, count, n_alive, list, d_hits);
-    return launch_ray_walk<false, false>(ctx, d_states, n_alive, list, t_min, d_hits, count);
+    return launch_ray_walk<false, kClosest>(ctx, d_states, n_alive, list, t_min, d_hits, count);
 }
 
 lbvh_status lbvh_trace_closest(lbvh_context* ctx, const lbvh_ray* d_rays, size_t count, const lbvh_scene* h_scene, lbvh_hit* d_hits)
 {
-    return trace_plain_rays<false>(ctx, d_rays, count, h_scene, d_hits, "lbvh_trace_closest");
+    return trace_plain_rays<kClosest>(ctx, d_rays, count, h_scene, d_hits, "lbvh_trace_closest");
 }
 
 lbvh_status lbvh_trace_occluded(lbvh_context* ctx, const lbvh_ray* d_rays, size_t count, const lbvh_scene* h_scene, uint32_t* d_occluded)
 {
-    return trace_plain_rays<true>(ctx, d_rays, count, h_scene, d_occluded, "lbvh_trace_occluded");
+    return trace_plain_rays<kAny>(ctx, d_rays, count, h_scene, d_occluded, "lbvh_trace_occluded");
+}
+
+lbvh_status lbvh_count_hits(lbvh_context* ctx, const lbvh_ray* d_rays, size_t count, const lbvh_scene* h_scene, uint32_t* d_counts)
+{
+    return trace_plain_rays<kCount>(ctx, d_rays, count, h_scene, d_counts, "lbvh_count_hits");
 }
 
 lbvh_status lbvh_debug_ray_walker(lbvh_context* ctx, uint32_t walker)
@@ -1283,7 +1470,7 @@ static lbvh_status path_bounce_impl(lbvh_context* ctx, const lbvh_scene* h_scene
     ctx->ray_list.states = d_states; ctx->ray_list.hits = d_hits; ctx->ray_list.count = count;
     ctx->ray_list.bounce = h_first_camera ? 0u : bounce;
     ctx->ray_list.turn = turn;
-    return launch_ray_walk<false, false>(ctx, d_states, n_alive, list, t_min, d_hits, count, bounce >= 1u);
+    return launch_ray_walk<false, kClosest>(ctx, d_states, n_alive, list, t_min, d_hits, count, bounce >= 1u);
 }
 
 extern "C" {

@@ -14,6 +14,19 @@ from . import _native as N
 from . import layouts as L
 from .scenes import capacity_for
 
+# RaytracingMeshDrawer.point_crossings' default directions: three fp32 unit vectors, no two in a coordinate plane together
+DEFAULT_DIRS = (np.array([[1.0, 1.0, 1.0], [-1.0, 2.0, 3.0], [4.0, -1.0, 2.0]]) /
+                np.sqrt([[3.0], [14.0], [21.0]])).astype(np.float32)
+
+
+def inside(parity, n_dirs):
+    """Inside / outside from lbvh_point_crossings words: more than half of the n_dirs directions saw an odd crossing count."""
+    p = np.asarray(parity, dtype=np.uint32)
+    ones = np.zeros(p.shape, dtype=np.int64)
+    for j in range(n_dirs):
+        ones += (p >> np.uint32(j)) & np.uint32(1)
+    return ones > n_dirs / 2
+
 
 class Context:
     """One GPU + one HIP stream.  Stands in for the implicit Unity graphics device and the
@@ -380,6 +393,22 @@ class RaytracingMeshDrawer:
             raise ValueError(f"queries must be a DataBuffer of layouts.POINT_QUERY and the output one of {dtype} with at least as many entries")
         s = self.container.scene()
         N.check(self.ctx.handle, fn(self.ctx.handle, queries.device, queries.size, C.byref(s), out.device))
+
+    def count_hits(self, rays, counts):
+        """The number of candidates of each ray of `rays` (layouts.RAY) in (t_min, t_max) into the uint32 DataBuffer `counts`: every
+        triangle crossed counts, two at the same t count 2.  Asynchronous."""
+        self._trace_plain(N.lib.lbvh_count_hits, rays, counts, np.dtype(np.uint32))
+
+    def point_crossings(self, queries, parity, dirs=None):
+        """Bit j of the uint32 DataBuffer `parity` for each point of `queries` (layouts.POINT_QUERY; max_dist2 is not read): the
+        parity of the number of triangles the ray from the point along dirs[j] crosses (dirs: up to 32 rows of x, y, z;
+        default DEFAULT_DIRS).  inside(parity, len(dirs)) turns the words into inside / outside.  Asynchronous."""
+        d = np.ascontiguousarray(DEFAULT_DIRS if dirs is None else dirs, dtype=np.float32).reshape(-1, 3)
+        if queries.dtype != L.POINT_QUERY or parity.dtype != np.uint32 or parity.size < queries.size:
+            raise ValueError("queries must be a DataBuffer of layouts.POINT_QUERY and parity one of uint32 with at least as many entries")
+        s = self.container.scene()
+        N.check(self.ctx.handle, N.lib.lbvh_point_crossings(self.ctx.handle, queries.device, queries.size,
+                                                            d.ctypes.data_as(C.POINTER(C.c_float)), len(d), C.byref(s), parity.device))
 
     def update(self, camera, rect=None, mode=L.TRACE_FAST, stats=False):
         """Enqueue one frame (or the sub-rectangle (x0, y0, x1, y1) of it).  Returns the device

@@ -19,6 +19,11 @@
 //                                                side, max_dist2 = radius * radius (default: unbounded).  ClosestPoints and
 //                                                WithinDistance; prints how many points found a triangle, the sum of all 32-bit
 //                                                words of the records (mod 2^64) and the number of set flags
+//     lbvh_driver crossings [n | file.obj] [count] the mesh and the points of `points`; PointCrossings along the three default
+//                                                directions ((1,1,1)/sqrt 3, (-1,2,3)/sqrt 14, (4,-1,2)/sqrt 21) and CountHits
+//                                                on the same rays written out ({p, 0, dir, +inf}); prints the sum of the counts,
+//                                                the sum of the parity words, how many points the majority calls inside and
+//                                                whether every parity bit equals its ray's count AND 1
 #include <chrono>
 #include <cmath>
 #include <cstdio>
@@ -311,8 +316,77 @@ static int points_main(int argc, char** argv)
     return 0;
 }
 
+static int crossings_main(int argc, char** argv)
+{
+    const char* what = argc > 2 ? argv[2] : "4096";
+    const size_t len = std::strlen(what);
+    const bool from_obj = len > 4 && std::strcmp(what + len - 4, ".obj") == 0;
+    const size_t count = argc > 3 ? (size_t)strtoull(argv[3], nullptr, 10) : 65536;
+    const std::vector<float> dirs = {(float)(1.0 / std::sqrt(3.0)),  (float)(1.0 / std::sqrt(3.0)),  (float)(1.0 / std::sqrt(3.0)),
+                                     (float)(-1.0 / std::sqrt(14.0)), (float)(2.0 / std::sqrt(14.0)), (float)(3.0 / std::sqrt(14.0)),
+                                     (float)(4.0 / std::sqrt(21.0)),  (float)(-1.0 / std::sqrt(21.0)), (float)(2.0 / std::sqrt(21.0))};
+    try {
+        const std::vector<lbvh_triangle> mesh = from_obj ? lbvh::MeshTriangles(lbvh::LoadObj(what)) : random_mesh((uint32_t)atoi(what));
+        float lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
+        for (const auto& t : mesh)
+            for (int k = 0; k < 3; k++) {
+                lo[k] = std::fmin(lo[k], std::fmin(t.a[k], std::fmin(t.b[k], t.c[k])));
+                hi[k] = std::fmax(hi[k], std::fmax(t.a[k], std::fmax(t.b[k], t.c[k])));
+            }
+        lbvh::Context ctx(0);
+        lbvh::RaytracingMeshDrawer drawer(ctx, mesh);
+        drawer.Awake();
+        lbvh::DataBuffer<lbvh_point_query> points(ctx, count);
+        lbvh::DataBuffer<lbvh_ray> rays(ctx, 3 * count);
+        uint64_t seed = 2;
+        for (size_t i = 0; i < count; i++) {
+            lbvh_point_query& q = points.LocalBuffer()[i];
+            for (int k = 0; k < 3; k++) {
+                const float grow = 0.25f * (hi[k] - lo[k]);
+                q.p[k] = uniform(seed, lo[k] - grow, hi[k] + grow);
+            }
+            q.max_dist2 = INFINITY;
+            for (int j = 0; j < 3; j++) {
+                lbvh_ray& r = rays.LocalBuffer()[3 * i + j];
+                for (int k = 0; k < 3; k++) { r.origin[k] = q.p[k]; r.dir[k] = dirs[3 * j + k]; }
+                r.t_min = 0.0f;
+                r.t_max = INFINITY;
+            }
+        }
+        points.Sync();
+        rays.Sync();
+        lbvh::DataBuffer<uint32_t> parity(ctx, count);
+        lbvh::DataBuffer<uint32_t> counts(ctx, 3 * count);
+        drawer.PointCrossings(points, dirs, parity);
+        drawer.CountHits(rays, counts);
+        parity.GetData();
+        counts.GetData();
+        uint64_t count_sum = 0, parity_sum = 0;
+        size_t n_inside = 0;
+        bool consistent = true;
+        for (size_t i = 0; i < count; i++) {
+            const uint32_t p = parity.LocalBuffer()[i];
+            parity_sum += p;
+            n_inside += __builtin_popcount(p) >= 2;
+            consistent = consistent && (p >> 3) == 0u;
+            for (int j = 0; j < 3; j++) {
+                const uint32_t c = counts.LocalBuffer()[3 * i + j];
+                count_sum += c;
+                consistent = consistent && ((p >> j) & 1u) == (c & 1u);
+            }
+        }
+        std::printf("{\"triangles\": %zu, \"points\": %zu, \"count_sum\": %llu, \"parity_sum\": %llu, \"inside\": %zu, \"consistent\": %s}\n",
+                    mesh.size(), count, (unsigned long long)count_sum, (unsigned long long)parity_sum, n_inside, consistent ? "true" : "false");
+    } catch (const std::exception& e) {
+        std::fprintf(stderr, "%s\n", e.what());
+        return 1;
+    }
+    return 0;
+}
+
 int main(int argc, char** argv)
 {
+    if (argc > 1 && std::strcmp(argv[1], "crossings") == 0) return crossings_main(argc, argv);
     if (argc > 1 && std::strcmp(argv[1], "points") == 0) return points_main(argc, argv);
     if (argc > 1 && std::strcmp(argv[1], "rays") == 0) return rays_main(argc, argv);
     if (argc > 1 && std::strcmp(argv[1], "sort") == 0) return sort_main(argc, argv);

@@ -334,6 +334,23 @@ public:
         check(ctx_.get(), lbvh_within_distance(ctx_.get(), (const lbvh_point_query*)queries.DeviceBuffer(), queries.Size(), &s,
                                                (uint32_t*)flags.DeviceBuffer()));
     }
+    // how many triangles each ray crosses in (t_min, t_max), and crossing parities of points along fixed directions — bit j of a
+    // point's word: the count of the ray from it along dirs[j] (x, y, z; 1 .. 32 of them), AND 1 (lbvh_count_hits /
+    // lbvh_point_crossings; asynchronous).  Inside / outside: more than half of the bits set.
+    void CountHits(const DataBuffer<lbvh_ray>& rays, DataBuffer<uint32_t>& counts)
+    {
+        if (counts.Size() < rays.Size()) throw Error(LBVH_ERR_INVALID_ARG, "CountHits: fewer counts than rays");
+        const lbvh_scene s = container_->Scene();
+        check(ctx_.get(), lbvh_count_hits(ctx_.get(), (const lbvh_ray*)rays.DeviceBuffer(), rays.Size(), &s, (uint32_t*)counts.DeviceBuffer()));
+    }
+    void PointCrossings(const DataBuffer<lbvh_point_query>& points, const std::vector<float>& dirs, DataBuffer<uint32_t>& parity)
+    {
+        if (parity.Size() < points.Size()) throw Error(LBVH_ERR_INVALID_ARG, "PointCrossings: fewer parity words than points");
+        if (dirs.size() % 3 != 0) throw Error(LBVH_ERR_INVALID_ARG, "PointCrossings: dirs is not a list of x, y, z");
+        const lbvh_scene s = container_->Scene();
+        check(ctx_.get(), lbvh_point_crossings(ctx_.get(), (const lbvh_point_query*)points.DeviceBuffer(), points.Size(), dirs.data(),
+                                               (uint32_t)(dirs.size() / 3), &s, (uint32_t*)parity.DeviceBuffer()));
+    }
     // _objectDrawer.SetTexture("_meshTexture", ...) :61 — RGBA8, row 0 at v = 0
     void SetTexture(const std::vector<uint8_t>& rgba8, int width, int height)
     {
