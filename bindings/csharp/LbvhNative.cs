@@ -141,6 +141,10 @@ public static class LbvhNative
     [DllImport(Lib)] public static extern int lbvh_trace_occluded(IntPtr ctx, IntPtr dRays, UIntPtr count, ref Scene scene, IntPtr dOccluded);
     [DllImport(Lib)] public static extern int lbvh_closest_point_query(IntPtr ctx, IntPtr dQueries, UIntPtr count, ref Scene scene, IntPtr dOut);
     [DllImport(Lib)] public static extern int lbvh_within_distance(IntPtr ctx, IntPtr dQueries, UIntPtr count, ref Scene scene, IntPtr dFlags);
+    [DllImport(Lib)] public static extern int lbvh_box_overlaps(IntPtr ctx, IntPtr dBoxes, UIntPtr count, ref Scene scene, IntPtr dOffsets, IntPtr dTris,
+        ulong capacity);
+    [DllImport(Lib)] public static extern int lbvh_gather_within_distance(IntPtr ctx, IntPtr dQueries, UIntPtr count, ref Scene scene, IntPtr dOffsets,
+        IntPtr dTris, ulong capacity);
     [DllImport(Lib)] public static extern int lbvh_count_hits(IntPtr ctx, IntPtr dRays, UIntPtr count, ref Scene scene, IntPtr dCounts);
     [DllImport(Lib)] public static extern int lbvh_point_crossings(IntPtr ctx, IntPtr dPoints, UIntPtr count, float[] hDirs, uint nDirs, ref Scene scene,
         IntPtr dParity);

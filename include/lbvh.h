@@ -649,6 +649,46 @@ lbvh_status lbvh_closest_point_query(lbvh_context* ctx, const lbvh_point_query* 
 lbvh_status lbvh_within_distance(lbvh_context* ctx, const lbvh_point_query* d_queries, size_t count, const lbvh_scene* h_scene,
                                  uint32_t* d_flags);
 
+/* Overlap queries: WHICH triangles are here — all triangles whose box touches a box, all triangles within a distance of a point —
+ * as a CSR list, over the derived traversal scene in its four-wide form (the scene lbvh_closest_point_query walks).
+ *   lbvh_box_overlaps: query k is an lbvh_aabb (_dummy0 / _dummy1 are not read).  Active query: min[a] <= max[a] on all three
+ *   axes (false when a bound is NaN).  Triangle i is a candidate of an active query Q iff, with A = scene.triangle_aabb[i] (the
+ *   padded own box the derived scene keeps for the triangle's leaf), Q.min[a] <= A.max[a] && A.min[a] <= Q.max[a] for a = 0, 1, 2.
+ *   Closed intervals: touching boxes overlap.  Comparisons only, nothing is rounded.  A broad phase on the triangles' BOXES by
+ *   design (no exact triangle-against-box test): the array lbvh_morton_aabb writes for ANOTHER mesh can be passed unchanged as
+ *   d_boxes, which gives the candidate pairs of a mesh-against-mesh test in one call.
+ *   lbvh_gather_within_distance: active query, R, dist2, box2 and the candidate predicate are exactly those of
+ *   lbvh_within_distance above: dist2_i < R && !(dist2_i < box2(own AABB_i)); a NaN dist2 is never a candidate, a point with a
+ *   NaN coordinate and an inactive query have none.  Segment k is non-empty exactly when lbvh_within_distance gives 1, and the
+ *   triangle lbvh_closest_point_query reports is in it.
+ *   Why the list does not depend on the walk: every box of the derived tree, binary or four-wide, is the exact min / max union of
+ *   what lies below it, so every ancestor of a candidate's leaf passes the same comparisons (box form) or has box2 <= box2(leaf)
+ *   <= dist2 < R (distance form, the argument at lbvh_closest_point_query without the shrinking bound).  The walk skips exactly
+ *   the slots that fail; each triangle is one leaf, so each candidate appears once.
+ * Output, the same for both:
+ *   d_offsets: count + 1 words of 64 bits.  d_offsets[k] = the number of candidates of queries 0 .. k-1, d_offsets[count] = the
+ *   total M.  Always written in full, whatever `capacity` is.
+ *   d_tris, `capacity` words of 32 bits: segment k = d_tris[d_offsets[k] .. d_offsets[k+1]) = the ORIGINAL triangle indices of
+ *   query k's candidates, each exactly once.  THE ORDER INSIDE A SEGMENT IS THE WALK'S AND IS NOT PART OF THE CONTRACT (the
+ *   four-wide form does not keep children in range order); sort a segment if a canonical order is needed.
+ *   Overflow: no word at index >= capacity is ever written; every segment with d_offsets[k+1] <= capacity is complete; words
+ *   below `capacity` that belong to a segment which does not fit are unspecified.  The call never waits on the host and returns
+ *   LBVH_OK in both cases: the caller reads d_offsets[count] (one 8-byte download) to learn whether everything fitted and, if
+ *   not, what to allocate.
+ *   Count-only form: capacity == 0 writes the offsets and walks once (d_tris may be NULL); otherwise the scene is walked twice
+ *   (count, device-side scan, fill).  d_tris == NULL with capacity > 0 is LBVH_ERR_INVALID_ARG.
+ * Both need the derived traversal scene (lbvh_build_fast_scene; a stale one is LBVH_ERR_INVALID_ARG), are asynchronous on the
+ * context's stream, and use the context's ray scratch: they drop the path tracer's live-path list (see lbvh_path_bounce).
+ * count == 0 is a no-op: nothing is enqueued and no buffer is touched, d_offsets[0] included.  Rejected: NULL d_boxes /
+ * d_queries / h_scene / d_offsets, queries not 16-byte aligned, d_offsets not 8-byte aligned, d_tris not 4-byte aligned,
+ * count > 2^32 - 1.
+ * One query per lane: a query with very many candidates keeps its lane busy while the rest of its wave idles — many small
+ * queries run far better than a few huge ones. */
+lbvh_status lbvh_box_overlaps(lbvh_context* ctx, const lbvh_aabb* d_boxes, size_t count, const lbvh_scene* h_scene,
+                              uint64_t* d_offsets, uint32_t* d_tris, uint64_t capacity);
+lbvh_status lbvh_gather_within_distance(lbvh_context* ctx, const lbvh_point_query* d_queries, size_t count,
+                                        const lbvh_scene* h_scene, uint64_t* d_offsets, uint32_t* d_tris, uint64_t capacity);
+
 /* How many surfaces a ray crosses, and crossing parities of points along fixed directions (inside / outside tests).
  *   lbvh_count_hits: active ray, candidate set and T = min(t_max, LBVH_MAX_FLOAT) exactly those of lbvh_trace_closest (the
  *   own-box slab test with entry e, Moeller-Trumbore with the reference's rejections, t >= e, t_min < t < T).  d_counts[k] =
@@ -706,7 +746,7 @@ lbvh_status lbvh_path_scatter(lbvh_context* ctx, const lbvh_scene* h_scene, cons
  * lbvh_path_bounce on the same d_states / d_hits listed as live (a list kept by the context).  Every library call that writes
  * into those buffers drops the list (lbvh_path_begin, lbvh_trace_rays, a primary trace into any part of d_hits,
  * lbvh_buffer_upload / _fill_u32 / _free), and so does lbvh_trace_forget — and so do lbvh_trace_closest,
- * lbvh_trace_occluded, lbvh_closest_point_query, lbvh_within_distance, lbvh_count_hits and lbvh_point_crossings, whatever buffers they are given, since they use the same ray scratch; then every state is scanned again.  What the library
+ * lbvh_trace_occluded, lbvh_closest_point_query, lbvh_within_distance, lbvh_count_hits, lbvh_point_crossings, lbvh_box_overlaps and lbvh_gather_within_distance, whatever buffers they are given, since they use the same ray scratch; then every state is scanned again.  What the library
  * cannot see is a write of the CALLER's own (a kernel or hipMemcpy that revives or ends paths, Russian roulette): between two
  * consecutive bounces of a frame d_states and d_hits must not be written from outside the library — or lbvh_trace_forget must be
  * called after such a write. */

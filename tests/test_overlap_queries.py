@@ -1,0 +1,509 @@
+"""lbvh_box_overlaps / lbvh_gather_within_distance: every triangle whose box touches a box, every triangle within a distance of a
+point, as a CSR list over the four-wide derived traversal scene.  The expectation is tests/overlap_reference.py: the header's
+definition in numpy float32, brute force over every (query, triangle) pair with the triangles' own boxes as the library produced
+them — no tree.  The order inside a segment is not part of the contract, so every GPU comparison is word for word AFTER sorting
+each segment:
+  O1  lbvh_box_overlaps == brute force               O2  lbvh_gather_within_distance == brute force
+  O3  consistent with lbvh_within_distance / lbvh_closest_point_query on the GPU itself
+  O4  count-only offsets == offsets with a capacity; node lines: count-only <= count + fill <= 2 x count-only
+  O5  overflow: offsets complete, fitting segments correct, guard words untouched, the retry equals O1
+  O6  a scene's own boxes as queries: the self broad phase          O7  one box around a million triangles (the deep stack)
+  O8  edges and errors                                              O9  constructed box-rule rejections (distance form)"""
+import ctypes as C
+import os
+import re
+
+import numpy as np
+import pytest
+
+import overlap_reference as V
+import point_reference as R
+from test_point_queries import SCENES, _scene, library_boxes, make_queries, padded_boxes, positions, golden
+from unitysimpleraytracing_amd import scenes
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+F = np.float32
+INF = F(np.inf)
+COUNT = 2048
+
+
+def H():
+    from unitysimpleraytracing_amd import host
+    return host
+
+
+def N():
+    from unitysimpleraytracing_amd import _native
+    return _native
+
+
+def L():
+    from unitysimpleraytracing_amd import layouts
+    return layouts
+
+
+# ---- the query sets of O1 / O2 ---------------------------------------------------------------------------------------------
+
+def box_queries(lo, hi, count=COUNT, seed=7):
+    """centres uniform in the scene box (the union of the padded triangle boxes) grown by 10 % per side, drawn first; then
+    half-extents uniform in [0, 0.1] x the scene's extent per axis"""
+    rng = np.random.default_rng(seed)
+    slo, shi = lo.min(axis=0).astype(np.float64), hi.max(axis=0).astype(np.float64)
+    ext = shi - slo
+    centres = rng.uniform(slo - 0.1 * ext, shi + 0.1 * ext, (count, 3))
+    half = rng.uniform(0.0, 0.1 * ext, (count, 3))
+    return V.make_boxes((centres - half).astype(F), (centres + half).astype(F))
+
+
+def distance_queries(lo, hi, count=COUNT, seed=7):
+    """the same centres; then radii uniform in [0, 0.125] x the scene's largest extent — the scale of the boxes: a ball of radius
+    r holds what a cube of half-extent h holds when r = (6 / pi)^(1/3) h = 1.24 h"""
+    rng = np.random.default_rng(seed)
+    slo, shi = lo.min(axis=0).astype(np.float64), hi.max(axis=0).astype(np.float64)
+    ext = shi - slo
+    centres = rng.uniform(slo - 0.1 * ext, shi + 0.1 * ext, (count, 3))
+    r = rng.uniform(0.0, 0.125 * ext.max(), count)
+    return make_queries(centres.astype(F), (r * r).astype(F))
+
+
+def describe(name, offsets):
+    n = np.diff(offsets).astype(np.int64)
+    return f"{name}: {100.0 * (n > 0).mean():.1f} % non-empty, longest {int(n.max())}, total {int(offsets[-1])}"
+
+
+def floor(name, offsets):
+    """a comparison of mostly empty lists shows little: asserted on the REFERENCE's result before the GPU is asked"""
+    n = np.diff(offsets).astype(np.int64)
+    print(describe(name, offsets))
+    assert (n > 0).mean() >= 0.25 and n.max() >= 32, describe(name, offsets)
+
+
+# ---- CPU: the surface in every host ----------------------------------------------------------------------------------------
+
+def test_header_declares_both_calls():
+    h = open(os.path.join(ROOT, "include", "lbvh.h")).read()
+    assert re.search(r"lbvh_status lbvh_box_overlaps\(lbvh_context\* ctx, const lbvh_aabb\* d_boxes, size_t count, const lbvh_scene\* h_scene,"
+                     r"\s+uint64_t\* d_offsets, uint32_t\* d_tris, uint64_t capacity\);", h)
+    assert re.search(r"lbvh_status lbvh_gather_within_distance\(lbvh_context\* ctx, const lbvh_point_query\* d_queries, size_t count,"
+                     r"\s+const lbvh_scene\* h_scene, uint64_t\* d_offsets, uint32_t\* d_tris, uint64_t capacity\);", h)
+    bounce = h[h.index("CROSS-CALL STATE"):h.index("lbvh_status lbvh_path_bounce(")]
+    assert "lbvh_box_overlaps" in bounce and "lbvh_gather_within_distance" in bounce
+    assert "NOT PART OF THE CONTRACT" in h and "d_offsets[0] included" in h
+
+
+def test_native_prototypes_and_the_other_hosts():
+    nat = N()
+    for fn in ("lbvh_box_overlaps", "lbvh_gather_within_distance"):
+        res, args = nat.SIGNATURES[fn]
+        assert res is C.c_int32 and len(args) == 7 and args[2] is C.c_size_t and args[6] is C.c_uint64
+        assert getattr(nat.lib, fn).argtypes is not None
+    assert nat.ABI_VERSION == 11
+    cs = open(os.path.join(ROOT, "bindings", "csharp", "LbvhNative.cs")).read()
+    for fn in ("lbvh_box_overlaps", "lbvh_gather_within_distance"):
+        assert re.search(r"public static extern int " + fn + r"\(IntPtr ctx, IntPtr \w+, UIntPtr count, ref Scene scene, IntPtr \w+,\s+IntPtr \w+,"
+                         r"\s+ulong capacity\);", cs), fn
+    oq = re.sub(r"//[^\n]*", "", open(os.path.join(ROOT, "bindings", "csharp", "OverlapQueries.cs")).read())
+    assert "lbvh_box_overlaps" in oq and "lbvh_gather_within_distance" in oq and "unsafe" not in oq
+    hpp = open(os.path.join(ROOT, "unitysimpleraytracing_amd", "host", "lbvh_host.hpp")).read()
+    assert "void BoxOverlaps(" in hpp and "void GatherWithinDistance(" in hpp
+    drawer = H().RaytracingMeshDrawer
+    assert all(hasattr(drawer, m) for m in ("box_overlaps", "gather_within_distance", "overlaps"))
+
+
+# ---- CPU: the restatement on cases with known answers ------------------------------------------------------------------------
+
+def test_a_triangles_own_box_contains_it_and_faces_touch():
+    a, b, c = positions(golden("viking_room"))
+    lo, hi = padded_boxes(a, b, c)
+    pick = np.arange(0, len(a), 97)
+    off, tris = V.box_overlaps(V.make_boxes(lo[pick], hi[pick]), lo, hi)
+    for k, i in enumerate(pick):
+        seg = tris[int(off[k]):int(off[k + 1])]
+        assert i in seg and (np.diff(seg.astype(np.int64)) > 0).all()
+    # two boxes sharing only a face overlap; one ulp apart they do not
+    lo1, hi1 = np.array([[0, 0, 0]], dtype=F), np.array([[1, 1, 1]], dtype=F)
+    q = V.make_boxes(np.array([[1, 0, 0], [np.nextafter(F(1), INF), 0, 0], [-1, -1, -1], [-2, 0, 0]], dtype=F),
+                     np.array([[2, 1, 1], [2, 1, 1], [0, 0, 0], [np.nextafter(F(0), -INF), 1, 1]], dtype=F))
+    off, tris = V.box_overlaps(q, lo1, hi1)
+    assert np.diff(off).tolist() == [1, 0, 1, 0]
+
+
+def test_inverted_and_nan_boxes_have_no_candidates():
+    lo1, hi1 = np.array([[0, 0, 0], [np.nan, 0, 0]], dtype=F), np.array([[1, 1, 1], [1, 1, 1]], dtype=F)
+    q = V.make_boxes(np.array([[0.5, 0.5, 0.5], [1, 0, 0], [np.nan, 0, 0], [0, 0, 0], [-5, -5, -5]], dtype=F),
+                     np.array([[0.5, 0.5, 0.5], [0, 1, 1], [1, 1, 1], [1, np.nan, 1], [5, 5, 5]], dtype=F))
+    assert V.box_active(q).tolist() == [True, False, False, False, True]
+    off, tris = V.box_overlaps(q, lo1, hi1)
+    assert np.diff(off).tolist() == [1, 0, 0, 0, 1] and tris.tolist() == [0, 0]          # the NaN triangle box is nobody's candidate
+
+
+@pytest.mark.parametrize("name", ["viking_room", "example_object3"])
+def test_distance_form_agrees_with_the_point_reference(name):
+    a, b, c = positions(golden(name))
+    lo, hi = padded_boxes(a, b, c)
+    q = distance_queries(lo, hi, 300, seed=3)
+    q["max_dist2"][::7] = 0.0
+    q["max_dist2"][3::11] = np.nan
+    q["p"][5::13, 1] = np.nan
+    off, tris = V.gather_within_distance(q, a, b, c, lo, hi)
+    ref = R.reference(q, a, b, c, lo, hi)
+    n = np.diff(off).astype(np.int64)
+    assert ((n > 0) == (ref.flags == 1)).all() and 0 < (n > 0).sum() < len(q)
+    e1, e2 = b - a, c - a
+    for k in np.nonzero(n > 0)[0]:
+        seg = tris[int(off[k]):int(off[k + 1])]
+        d, _, _ = R.point_triangle(q["p"][k][None], a[seg], e1[seg], e2[seg])
+        assert ref.records["tri"][k] in seg and d.min() == ref.records["dist2"][k]
+        assert ref.records["tri"][k] == seg[np.argmin(d)]                                # the lowest index among the nearest
+
+
+# ---- GPU ---------------------------------------------------------------------------------------------------------------------
+
+class Lists:
+    """device buffers of one query set; run() = one library call on caller-owned buffers"""
+
+    def __init__(self, ctx, drawer, queries, guard=0):
+        self.ctx, self.drawer, self.count = ctx, drawer, len(queries)
+        self.box = queries.dtype == L().AABB
+        self.queries = H().DataBuffer(ctx, len(queries), queries.dtype)
+        self.queries.local[:] = queries
+        self.queries.sync()
+        self.offsets = H().DataBuffer(ctx, len(queries) + 1, np.uint64)
+        self.fn = N().lib.lbvh_box_overlaps if self.box else N().lib.lbvh_gather_within_distance
+
+    def run(self, tris=None, capacity=None):
+        """offsets (host copy) after one call; tris: a uint32 DataBuffer or None, capacity defaults to its size"""
+        self.offsets.fill_u32(0xDEADBEEF)
+        s = self.drawer.container.scene()
+        cap = 0 if tris is None else (tris.size if capacity is None else capacity)
+        N().check(self.ctx.handle, self.fn(self.ctx.handle, self.queries.device, self.count, C.byref(s), self.offsets.device,
+                                           tris.device if tris is not None else None, cap))
+        return self.offsets.get_data().copy()
+
+    def dispose(self):
+        self.queries.dispose()
+        self.offsets.dispose()
+
+
+def assert_equal_lists(got, ref):
+    (go, gt), (ro, rt) = got, ref
+    assert (go == ro).all(), np.nonzero(go != ro)[0][:10]
+    assert len(gt) == len(rt) == int(ro[-1])
+    gs = V.sort_segments(go, gt)
+    bad = np.nonzero(gs != rt)[0]
+    assert len(bad) == 0, (bad[:10], gs[bad[:10]], rt[bad[:10]])
+
+
+_DRAWERS = {}
+
+
+def drawer_for(ctx, name):
+    """one drawer per scene; a context keeps one derived traversal scene, so it is derived again for the test that asks"""
+    if name not in _DRAWERS:
+        tris = _scene(name)
+        _DRAWERS[name] = (tris, H().RaytracingMeshDrawer(ctx, tris).awake())
+    _DRAWERS[name][1].build_fast_scene()
+    return _DRAWERS[name]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", SCENES)
+def test_o1_box_overlaps_equals_the_brute_force(ctx, name):
+    tris, d = drawer_for(ctx, name)
+    lo, hi = library_boxes(d)
+    boxes = box_queries(lo, hi)
+    ref = V.box_overlaps(boxes, lo, hi)
+    floor(name, ref[0])
+    q = Lists(ctx, d, boxes)
+    assert_equal_lists(d.overlaps(q.queries), ref)
+    q.dispose()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", SCENES)
+def test_o2_gather_within_distance_equals_the_brute_force(ctx, name):
+    tris, d = drawer_for(ctx, name)
+    a, b, c = positions(tris)
+    lo, hi = library_boxes(d)
+    queries = distance_queries(lo, hi)
+    ref = V.gather_within_distance(queries, a, b, c, lo, hi)
+    floor(name, ref[0])
+    q = Lists(ctx, d, queries)
+    assert_equal_lists(d.overlaps(q.queries), ref)
+    q.dispose()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", ["random", "viking_room"])
+def test_o3_consistent_with_the_flag_and_the_nearest_triangle(ctx, name):
+    tris, d = drawer_for(ctx, name)
+    lo, hi = library_boxes(d)
+    queries = distance_queries(lo, hi)
+    queries["max_dist2"][::9] = 0.0
+    q = Lists(ctx, d, queries)
+    off, lst = d.overlaps(q.queries)
+    flags = H().DataBuffer(ctx, COUNT, np.uint32)
+    out = H().DataBuffer(ctx, COUNT, L().CLOSEST_POINT)
+    d.within_distance(q.queries, flags)
+    d.closest_points(q.queries, out)
+    f, rec = flags.get_data().copy(), out.get_data().copy()
+    n = np.diff(off).astype(np.int64)
+    assert ((n > 0) == (f == 1)).all() and 0 < f.sum() < COUNT
+    for k in np.nonzero(f)[0]:
+        assert rec["tri"][k] in lst[int(off[k]):int(off[k + 1])], k
+    assert (rec["dist2"][f == 0] == R.MAX_FLOAT).all()
+    for b in (flags, out):
+        b.dispose()
+    q.dispose()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("box", [True, False])
+def test_o4_count_only_walks_once_and_gives_the_same_offsets(ctx, box):
+    tris, d = drawer_for(ctx, "random")
+    lo, hi = library_boxes(d)
+    q = Lists(ctx, d, box_queries(lo, hi) if box else distance_queries(lo, hi))
+    stats = H().DataBuffer(ctx, 1, L().RAY_STATS)
+    lines, offs = [], []
+    big = None
+    try:
+        for with_fill in (False, True):
+            stats.fill_u32(0)
+            N().check(ctx.handle, N().lib.lbvh_ray_stats_target(ctx.handle, stats.device))
+            offs.append(q.run(big if with_fill else None))
+            N().check(ctx.handle, N().lib.lbvh_ray_stats_target(ctx.handle, None))
+            lines.append(int(stats.get_data()[0]["node_fetches"]))
+            if not with_fill:
+                big = H().DataBuffer(ctx, max(int(offs[0][-1]), 1), np.uint32)
+    finally:
+        N().check(ctx.handle, N().lib.lbvh_ray_stats_target(ctx.handle, None))
+    print(f"box={box}: node lines count-only {lines[0]}, count + fill {lines[1]}, M {int(offs[0][-1])}")
+    assert (offs[0] == offs[1]).all() and int(offs[0][-1]) > 0
+    assert 0 < lines[0] <= lines[1] <= 2 * lines[0]
+    assert lines[1] == 2 * lines[0]                                    # the two walks take the same decisions
+    for b in (stats, big):
+        b.dispose()
+    q.dispose()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("box", [True, False])
+def test_o5_overflow_writes_nothing_beyond_the_capacity(ctx, box):
+    tris, d = drawer_for(ctx, "viking_room")
+    a, b, c = positions(tris)
+    lo, hi = library_boxes(d)
+    queries = box_queries(lo, hi) if box else distance_queries(lo, hi)
+    ref = V.box_overlaps(queries, lo, hi) if box else V.gather_within_distance(queries, a, b, c, lo, hi)
+    ro, rt = ref
+    total = int(ro[-1])
+    cap, guard = total // 2, 4096
+    q = Lists(ctx, d, queries)
+    buf = H().DataBuffer(ctx, total + guard, np.uint32)
+    buf.fill_u32(0xABABABAB)
+    off = q.run(buf, capacity=cap)
+    got = buf.get_data().copy()
+    assert (off == ro).all()
+    assert (got[cap:] == 0xABABABAB).all()                             # the guard words, and everything from the capacity on
+    fits = np.nonzero(ro[1:] <= cap)[0]
+    assert 0 < len(fits) < COUNT
+    last = int(ro[fits[-1] + 1])
+    assert (V.sort_segments(ro[:fits[-1] + 2], got[:last]) == rt[:last]).all()
+    # the retry with the capacity the offsets asked for
+    buf.fill_u32(0xABABABAB)
+    off = q.run(buf, capacity=total)
+    got = buf.get_data().copy()
+    assert (got[total:] == 0xABABABAB).all()
+    assert_equal_lists((off, got[:total]), ref)
+    buf.dispose()
+    q.dispose()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", ["viking_room", "example_object3"])
+def test_o6_self_broad_phase(ctx, name):
+    """the scene's own triangle boxes as queries: the device buffer lbvh_morton_aabb wrote, passed as it is"""
+    tris, d = drawer_for(ctx, name)
+    n = len(tris)
+    lo, hi = library_boxes(d)
+    ref = V.box_overlaps(V.make_boxes(lo, hi), lo, hi)
+    offsets = H().DataBuffer(ctx, n + 1, np.uint64)
+    lib, h, s = N().lib, ctx.handle, d.container.scene()
+    aabb = d.container.triangle_aabb.device
+    N().check(h, lib.lbvh_box_overlaps(h, aabb, n, C.byref(s), offsets.device, None, 0))
+    total = int(offsets.get_data()[n])
+    lst = H().DataBuffer(ctx, total, np.uint32)
+    N().check(h, lib.lbvh_box_overlaps(h, aabb, n, C.byref(s), offsets.device, lst.device, total))
+    off, got = offsets.get_data().copy(), lst.get_data().copy()
+    assert_equal_lists((off, got), ref)
+    per = np.diff(off).astype(np.int64)
+    print(f"{name}: {total} pairs, {int(per.min())} - {int(per.max())} per triangle")
+    srt = V.sort_segments(off, got).astype(np.int64)
+    seg = np.repeat(np.arange(n), per)
+    assert (np.bincount(seg[srt == seg], minlength=n) == 1).all()       # every triangle finds itself, once
+    pairs = seg * n + srt
+    assert (np.sort(pairs) == np.sort(srt * n + seg)).all()             # the pair set is symmetric
+    offsets.dispose()
+    lst.dispose()
+
+
+@pytest.mark.gpu
+def test_o7_one_box_around_a_million_triangles_and_random_boxes(ctx):
+    tris = scenes.tiled_torus()
+    n = len(tris)
+    d = H().RaytracingMeshDrawer(ctx, tris).awake()
+    lo, hi = library_boxes(d)
+    whole = V.make_boxes(lo.min(axis=0)[None] - F(1.0), hi.max(axis=0)[None] + F(1.0))
+    q = Lists(ctx, d, whole)
+    off, lst = d.overlaps(q.queries)
+    assert N().lib.lbvh_sync(ctx.handle) == 0                           # no fault word: no stack entry was dropped
+    assert off.tolist() == [0, n] and (np.sort(lst) == np.arange(n, dtype=np.uint32)).all()
+    q.dispose()
+    boxes = box_queries(lo, hi, 256, seed=9)
+    ref = V.box_overlaps(boxes, lo, hi)
+    print(describe("tiled_torus", ref[0]))
+    q = Lists(ctx, d, boxes)
+    assert_equal_lists(d.overlaps(q.queries), ref)
+    q.dispose()
+    d.on_destroy()
+
+
+@pytest.mark.gpu
+def test_o8_edges_errors_scratch_failure_and_a_stale_scene(ctx):
+    tris = scenes.tiled_torus(nu=16, nv=10, grid=2)
+    a, b, c = positions(tris)
+    c2 = H().Context(0)                                                 # a context of its own: its ray scratch has never grown
+    try:
+        d = H().RaytracingMeshDrawer(c2, tris).awake()
+        lo, hi = library_boxes(d)
+        boxes = box_queries(lo, hi, 3000, seed=4)
+        nan = F(np.nan)
+        boxes["min"][0::10] = boxes["max"][0::10] + F(1.0)              # inverted
+        boxes["min"][1::10, 1] = nan                                    # NaN bounds
+        boxes["max"][2::10, 2] = nan
+        boxes["max"][3::10] = boxes["min"][3::10]                       # zero volume: a point, still active
+        boxes["_dummy0"], boxes["_dummy1"] = nan, nan                   # not read
+        points = distance_queries(lo, hi, 3000, seed=4)
+        points["max_dist2"][0::10] = 0.0
+        points["max_dist2"][1::10] = -1.0
+        points["max_dist2"][2::10] = nan
+        points["p"][3::10, 0] = nan
+        points["max_dist2"][4::10] = INF
+        refs = (V.box_overlaps(boxes, lo, hi), V.gather_within_distance(points, a, b, c, lo, hi))
+        assert (np.diff(refs[0][0])[3::10] > 0).any() and not np.diff(refs[0][0])[0::10].any()
+        lib, h, s = N().lib, c2.handle, d.container.scene()
+        qs = (Lists(c2, d, boxes), Lists(c2, d, points))
+        n = 3000
+        # a failed growth of the ray scratch: out of memory, nothing written; the next call on the context succeeds
+        c2.debug_switch(N().DEBUG_SWITCH_FAIL_RESERVE, 1)
+        qs[0].offsets.fill_u32(0xDEADBEEF)
+        assert lib.lbvh_box_overlaps(h, qs[0].queries.device, n, C.byref(s), qs[0].offsets.device, None, 0) == -2
+        assert (qs[0].offsets.get_data().view(np.uint32) == 0xDEADBEEF).all()
+        for q, ref in zip(qs, refs):
+            assert_equal_lists(d.overlaps(q.queries), ref)
+        # argument checks
+        p = lambda buf, k: C.c_void_p(buf.device.value + k)
+        lst = H().DataBuffer(c2, 64, np.uint32)
+        for q in qs:
+            fn, dq, do = q.fn, q.queries.device, q.offsets.device
+            for args in ((None, 10, C.byref(s), do, None, 0), (dq, 10, None, do, None, 0), (dq, 10, C.byref(s), None, None, 0),
+                         (dq, 10, C.byref(s), do, None, 5), (p(q.queries, 4), 10, C.byref(s), do, None, 0),
+                         (dq, 10, C.byref(s), p(q.offsets, 4), None, 0), (dq, 10, C.byref(s), do, p(lst, 2), 8),
+                         (dq, 1 << 32, C.byref(s), do, None, 0)):
+                assert fn(h, *args) == -1, args
+                assert lib.lbvh_last_error(h)
+            assert fn(None, dq, 10, C.byref(s), do, None, 0) == -1
+            assert fn(h, p(q.queries, 32), 10, C.byref(s), p(q.offsets, 8), p(lst, 4), 8) == 0      # aligned sub-ranges are fine
+            # count == 0: a no-op, d_offsets[0] included
+            q.offsets.fill_u32(0xDEADBEEF)
+            assert fn(h, dq, 0, C.byref(s), do, None, 0) == 0
+            assert (q.offsets.get_data().view(np.uint32) == 0xDEADBEEF).all()
+        lst.dispose()
+        # a small LDS part exercises the device-memory part of the stack: same lists
+        N().check(h, lib.lbvh_debug_ray_stack_split(h, 1))
+        for q, ref in zip(qs, refs):
+            assert_equal_lists(d.overlaps(q.queries), ref)
+        N().check(h, lib.lbvh_debug_ray_stack_split(h, 16))
+        # a stale derived scene is refused
+        d.container.triangle_data.sync()
+        for q in qs:
+            assert q.fn(h, q.queries.device, n, C.byref(s), q.offsets.device, None, 0) == -1
+            assert b"stale" in lib.lbvh_last_error(h)
+        d.rebuild(fast=True)
+        for q, ref in zip(qs, refs):
+            assert_equal_lists(d.overlaps(q.queries), ref)
+            q.dispose()
+    finally:
+        c2.close()
+
+
+@pytest.mark.gpu
+def test_o8_the_live_path_list_is_dropped(ctx):
+    """a path-traced frame with both calls issued between the bounces equals the undisturbed frame"""
+    tris, body, centres = scenes.tiled_torus(nu=24, nv=16, grid=2, with_bodies=True)
+    pt = H().DynamicPathTracer(ctx, tris, body, centres, t_min=1e-3, albedo=0.7, seed=5)
+    pt.animate(0.05)
+    cam_d = scenes.camera(160, 96, (0.0, 0.0, 110.0))
+    pt.render(cam_d, bounces=4)
+    img0 = pt.image()
+    count = 160 * 96
+    st0 = pt.states.get_data()[:count].copy()
+    lo, hi = library_boxes(pt.drawer)
+    qs = (Lists(ctx, pt.drawer, box_queries(lo, hi, 4 * count, seed=12)), Lists(ctx, pt.drawer, distance_queries(lo, hi, 4 * count, seed=12)))
+    cam = N().Camera.from_dict(cam_d)
+    h, s, lib = ctx.handle, pt.drawer.container.scene(), N().lib
+
+    def both():
+        for q in qs:
+            N().check(h, q.fn(h, q.queries.device, q.count, C.byref(s), q.offsets.device, None, 0))
+
+    N().check(h, lib.lbvh_trace_primary(h, C.byref(cam), 0, 0, 160, 96, C.byref(s), L().TRACE_FAST, pt.hits.device, None))
+    both()
+    N().check(h, lib.lbvh_path_first_bounce(h, C.byref(cam), C.byref(s), pt.states.device, pt.hits.device, 5, 0.7, 1e-3))
+    for bnc in range(1, 4):
+        both()
+        N().check(h, lib.lbvh_path_bounce(h, C.byref(s), pt.states.device, pt.hits.device, count, bnc, 5, 0.7, 1e-3))
+    both()
+    N().check(h, lib.lbvh_path_scatter(h, C.byref(s), pt.hits.device, count, 4, 5, 0.7, pt.states.device))
+    N().check(h, lib.lbvh_path_resolve(h, pt.states.device, count, pt.image_buf.device))
+    assert (pt.states.get_data()[:count].view(np.uint32) == st0.view(np.uint32)).all()
+    assert (pt.image().view(np.uint16) == img0.view(np.uint16)).all()
+    assert all(int(q.offsets.get_data()[q.count]) > 0 for q in qs)
+    for q in qs:
+        q.dispose()
+    pt.drawer.on_destroy()
+
+
+@pytest.mark.gpu
+def test_o9_constructed_box_rule_rejections(ctx):
+    """A few triangles' boxes shrunk about their centres after the Morton stage and the sort, the derived scene built from them: for
+    points near those triangles' corners dist2 < box2 and the triangle is no candidate.  GPU == brute force fed the same boxes,
+    and the lists differ from the untouched scene's."""
+    tris = scenes.random_triangles(n=3000, seed=21, extent=30.0, edge=6.0)
+    a, b, c = positions(tris)
+    d = H().RaytracingMeshDrawer(ctx, tris).awake()
+    n = len(tris)
+    lo0, hi0 = library_boxes(d)
+    rng = np.random.default_rng(3)
+    picked = rng.choice(n, 60, replace=False)
+    w = rng.dirichlet((1, 1, 1), 600)
+    k = picked[rng.integers(0, len(picked), 600)]
+    pts = np.concatenate([a[picked], b[picked], c[picked], a[k] * w[:, :1] + b[k] * w[:, 1:2] + c[k] * w[:, 2:],
+                          rng.uniform(lo0.min(axis=0), hi0.max(axis=0), (800, 3))]).astype(F)
+    queries = make_queries(pts, F(16.0))[rng.permutation(len(pts))]
+    before = V.gather_within_distance(queries, a, b, c, lo0, hi0)
+    q = Lists(ctx, d, queries)
+    assert_equal_lists(d.overlaps(q.queries), before)
+    box = d.container.triangle_aabb.local                              # the mirror get_data() filled, all `capacity` entries
+    centre = (box["min"][picked] + box["max"][picked]) * F(0.5)
+    half = (box["max"][picked] - box["min"][picked]) * F(0.05)
+    box["min"][picked] = centre - half
+    box["max"][picked] = centre + half
+    d.container.triangle_aabb.sync()
+    d.build_fast_scene()
+    lo1, hi1 = box["min"][:n].copy(), box["max"][:n].copy()
+    ref = V.gather_within_distance(queries, a, b, c, lo1, hi1)
+    assert_equal_lists(d.overlaps(q.queries), ref)
+    print(f"box rule: {int(before[0][-1]) - int(ref[0][-1])} candidates rejected")
+    assert int(ref[0][-1]) < int(before[0][-1])
+    q.dispose()
+    d.on_destroy()

@@ -865,6 +865,249 @@ __global__ __launch_bounds__(64) void point_query_wide_kernel(const lbvh_point_q
     if (STATS) add_ray_stats(stats, n_queries, n_steps, n_tris);
 }
 
+// ---- overlap queries: every triangle in a box / within a distance, as a CSR list (include/lbvh.h) -----------------------
+// The first queries whose output length is not known at the call: a COUNT walk writes one 32-bit count per query into the ray
+// scratch, three small kernels scan the counts into the caller's 64-bit offsets, and a FILL walk — the same kernel, the same
+// decisions — stores candidate j of query k at offsets[k] + j while that is below the capacity.
+//   BOX:  the query is an lbvh_aabb; a slot is entered iff the two boxes overlap (closed intervals, six comparisons, nothing to
+//         round).  A leaf slot's box is the triangle's own AABB and its reference is LEAF | leaf_base + ORIGINAL index
+//         (lbvh_build.hip tree_body), so a candidate costs no triangle line at all.
+//   !BOX: the query is an lbvh_point_query; the walk of point_query_wide_kernel with the bound fixed at R: slots with box2 > R are
+//         skipped, a leaf is a candidate iff dist2 < R && !(dist2 < box2 of its slot) — lbvh_within_distance's predicate.
+// Nothing shrinks, so the slots need no order: the first passing inner slot is entered, the others wait on the stack.
+__device__ __forceinline__ bool point_query_active(const float4 q) { return q.w > 0.0f && (q.x == q.x && q.y == q.y && q.z == q.z); }
+
+// query k into the lane: BOX (ax, ay, az) = min, (bx, by, bz) = max; !BOX (ax, ay, az) = p, bx = R.  false: no candidates, no walk
+template <bool BOX>
+__device__ __forceinline__ bool load_overlap_query(const float4* __restrict__ queries, uint32_t k, float& ax, float& ay, float& az,
+                                                   float& bx, float& by, float& bz)
+{
+    if constexpr (BOX) {
+        const float4 lo = queries[2 * (size_t)k], hi = queries[2 * (size_t)k + 1];
+        ax = lo.x; ay = lo.y; az = lo.z;
+        bx = hi.x; by = hi.y; bz = hi.z;
+        return ax <= bx && ay <= by && az <= bz;             // false when a bound is NaN
+    } else {
+        const float4 q = queries[k];
+        ax = q.x; ay = q.y; az = q.z;
+        bx = fminf(q.w, LBVH_MAX_FLOAT); by = 0.0f; bz = 0.0f;
+        return point_query_active(q);
+    }
+}
+
+__device__ __forceinline__ bool boxes_overlap(float qlx, float qly, float qlz, float qhx, float qhy, float qhz,
+                                              float lx, float ly, float lz, float hx, float hy, float hz)
+{
+    return qlx <= hx && lx <= qhx && qly <= hy && ly <= qhy && qlz <= hz && lz <= qhz;
+}
+
+template <bool BOX, bool FILL, bool STATS>
+__global__ __launch_bounds__(64) void overlap_wide_kernel(const float4* __restrict__ queries, uint32_t total,
+                                                          const lbvh_wide_node* __restrict__ wide,
+                                                          const lbvh_fast_node* __restrict__ lines, uint32_t leaf_base,
+                                                          uint32_t* __restrict__ counts,            // !FILL: candidates of query k
+                                                          const uint64_t* __restrict__ offsets,     // FILL: where segment k starts
+                                                          uint32_t* __restrict__ tris, uint64_t capacity,
+                                                          uint32_t* __restrict__ deep,     // [gridDim.x][kWideStackDeep][64]
+                                                          uint32_t lds_depth,              // <= kWideStackLds
+                                                          uint32_t deep_cap,               // <= kWideStackDeep
+                                                          uint32_t* __restrict__ fault, lbvh_ray_stats* stats)
+{
+    __shared__ uint32_t s_stack[kWideStackLds][LBVH_WAVE];
+    uint32_t* my_deep = deep + (size_t)blockIdx.x * (kWideStackDeep * LBVH_WAVE) + threadIdx.x;
+    const uint32_t lane = threadIdx.x;
+    const uint32_t run = max((total + gridDim.x - 1) / gridDim.x, 32u);
+    uint32_t next = blockIdx.x * run;
+    if (next >= total) return;
+    const uint32_t end = min(next + run, total);
+    uint32_t n_queries = 0, n_steps = 0, n_tris = 0;
+
+    bool active = false;
+    uint32_t i = 0;
+    float ax = 0.0f, ay = 0.0f, az = 0.0f, bx = 0.0f, by = 0.0f, bz = 0.0f;
+    uint32_t n_found = 0, sp = 0, node = 0;
+    uint64_t pos = 0;                                    // FILL: where this lane's next candidate goes
+    auto push = [&](uint32_t ref) {
+        if (sp < lds_depth) { s_stack[sp][lane] = ref; sp++; }
+        else if (sp < lds_depth + deep_cap) { my_deep[(sp - lds_depth) * LBVH_WAVE] = ref; sp++; }
+        // a dropped entry would be a silently short list: report it, as the other walkers do (lbvh_debug_ray_stack_limit provokes it)
+        else __hip_atomic_store(fault, LBVH_FAULT_RAY_STACK, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    };
+    auto emit = [&](uint32_t tri) {
+        if constexpr (FILL) {
+            if (pos < capacity) tris[pos] = tri;         // never a word at or beyond the capacity
+            pos++;
+        } else {
+            n_found++;
+        }
+    };
+    for (;;) {
+        const uint64_t idle = __ballot(!active);
+        if (idle != 0 && next < end) {
+            if (!active) {
+                const uint32_t k = next + mbcnt64(idle);
+                if (k < end) {
+                    i = k;
+                    active = load_overlap_query<BOX>(queries, k, ax, ay, az, bx, by, bz);
+                    sp = 0; node = 0;
+                    if constexpr (FILL) { if (active) pos = offsets[k]; }
+                    else { n_found = 0; if (!active) counts[k] = 0u; }
+                    if (STATS && active) n_queries++;
+                }
+            }
+            next += (uint32_t)__popcll(idle);
+        }
+        if (!__any(active) && next >= end) break;
+        if (active) {
+            if (STATS) n_steps++;
+            const float4* w = reinterpret_cast<const float4*>(&wide[node]);
+            const float4 lox = w[0], loy = w[1], loz = w[2], hix = w[3], hiy = w[4], hiz = w[5];
+            const uint4 ref = reinterpret_cast<const uint4*>(w)[6];
+            bool h0, h1, h2, h3;
+            float b0 = 0.0f, b1 = 0.0f, b2 = 0.0f, b3 = 0.0f;
+            if constexpr (BOX) {
+                h0 = boxes_overlap(ax, ay, az, bx, by, bz, lox.x, loy.x, loz.x, hix.x, hiy.x, hiz.x) && ref.x != kWideEmpty;
+                h1 = boxes_overlap(ax, ay, az, bx, by, bz, lox.y, loy.y, loz.y, hix.y, hiy.y, hiz.y) && ref.y != kWideEmpty;
+                h2 = boxes_overlap(ax, ay, az, bx, by, bz, lox.z, loy.z, loz.z, hix.z, hiy.z, hiz.z) && ref.z != kWideEmpty;
+                h3 = boxes_overlap(ax, ay, az, bx, by, bz, lox.w, loy.w, loz.w, hix.w, hiy.w, hiz.w) && ref.w != kWideEmpty;
+            } else {
+                b0 = point_box2(lox.x, loy.x, loz.x, hix.x, hiy.x, hiz.x, ax, ay, az);
+                b1 = point_box2(lox.y, loy.y, loz.y, hix.y, hiy.y, hiz.y, ax, ay, az);
+                b2 = point_box2(lox.z, loy.z, loz.z, hix.z, hiy.z, hiz.z, ax, ay, az);
+                b3 = point_box2(lox.w, loy.w, loz.w, hix.w, hiy.w, hiz.w, ax, ay, az);
+                h0 = !(b0 > bx) && ref.x != kWideEmpty; h1 = !(b1 > bx) && ref.y != kWideEmpty;
+                h2 = !(b2 > bx) && ref.z != kWideEmpty; h3 = !(b3 > bx) && ref.w != kWideEmpty;
+            }
+            const uint32_t hit = (h0 ? 1u : 0u) | (h1 ? 2u : 0u) | (h2 ? 4u : 0u) | (h3 ? 8u : 0u);
+            const uint32_t leaf = (ref.x >> 31) | ((ref.y >> 31) << 1) | ((ref.z >> 31) << 2) | ((ref.w >> 31) << 3);
+            uint32_t leaves = hit & leaf, inner = hit & ~leaf;
+            while (leaves != 0u) {
+                const uint32_t k = (uint32_t)__builtin_ctz(leaves);
+                leaves &= leaves - 1u;
+                if (STATS) n_tris++;
+                const uint32_t line = pick4(ref, k) & 0x7FFFFFFFu;
+                if constexpr (BOX) {
+                    emit(line - leaf_base);
+                } else {
+                    float4 v0, v1, v2;
+                    unpack_fast_triangle(reinterpret_cast<const float4*>(&lines[line]), v0, v1, v2);
+                    float u = 0.0f, v = 0.0f;
+                    const float dist2 = point_triangle2(ax, ay, az, v0, v1, v2, u, v);
+                    const float own = k == 0u ? b0 : (k == 1u ? b1 : (k == 2u ? b2 : b3));
+                    if (dist2 < bx && !(dist2 < own)) emit(__float_as_uint(v0.w));
+                }
+            }
+            if (inner != 0u) {
+                node = pick4(ref, (uint32_t)__builtin_ctz(inner));
+                inner &= inner - 1u;
+                while (inner != 0u) {
+                    push(pick4(ref, (uint32_t)__builtin_ctz(inner)));
+                    inner &= inner - 1u;
+                }
+            } else if (sp != 0) {
+                sp--;
+                node = sp < lds_depth ? s_stack[sp][lane] : my_deep[(sp - lds_depth) * LBVH_WAVE];
+            } else {
+                if constexpr (!FILL) counts[i] = n_found;
+                active = false;
+            }
+        }
+    }
+    if (STATS) add_ray_stats(stats, n_queries, n_steps, n_tris);
+}
+
+// The scan of the counts into the 64-bit offsets: tiles of 1024 counts (256 threads x one 16-byte load), (1) a sum per tile,
+// (2) one workgroup scans the tile sums in place, (3) every tile scans its own counts on top of its prefix and writes
+// offsets[first .. first + 1024) — offsets[total] = the grand total included, so the tiles cover total + 1 outputs.
+constexpr uint32_t kScanTile = 1024;
+
+__device__ __forceinline__ uint64_t wave_inclusive_sum_u64(uint64_t v)
+{
+    const uint32_t lane = lane_id();
+#pragma unroll
+    for (int d = 1; d < LBVH_WAVE; d <<= 1) {
+        const uint64_t o = __shfl_up(v, d, LBVH_WAVE);
+        if (lane >= (uint32_t)d) v += o;
+    }
+    return v;
+}
+
+// the four counts of a thread of a tile; counts at or beyond `total` read as 0
+__device__ __forceinline__ uint4 load_tile_counts(const uint32_t* __restrict__ counts, uint64_t first, uint32_t total)
+{
+    uint4 c = make_uint4(0u, 0u, 0u, 0u);
+    if (first + 3 < total) c = reinterpret_cast<const uint4*>(counts)[first >> 2];
+    else {
+        if (first < total) c.x = counts[first];
+        if (first + 1 < total) c.y = counts[first + 1];
+        if (first + 2 < total) c.z = counts[first + 2];
+    }
+    return c;
+}
+
+__global__ __launch_bounds__(256) void overlap_tile_sums_kernel(const uint32_t* __restrict__ counts, uint32_t total, uint64_t* __restrict__ sums)
+{
+    __shared__ uint64_t s_wave[4];
+    const uint4 c = load_tile_counts(counts, (uint64_t)blockIdx.x * kScanTile + threadIdx.x * 4u, total);
+    const uint64_t incl = wave_inclusive_sum_u64(((uint64_t)c.x + c.y) + ((uint64_t)c.z + c.w));
+    if (lane_id() == LBVH_WAVE - 1) s_wave[threadIdx.x / LBVH_WAVE] = incl;
+    __syncthreads();
+    if (threadIdx.x == 0) sums[blockIdx.x] = (s_wave[0] + s_wave[1]) + (s_wave[2] + s_wave[3]);
+}
+
+__global__ __launch_bounds__(1024) void overlap_scan_sums_kernel(uint64_t* __restrict__ sums, uint32_t n_tiles)
+{
+    __shared__ uint64_t s_wave[16];
+    const uint32_t wave = threadIdx.x / LBVH_WAVE;
+    uint64_t carry = 0;
+    for (uint32_t base = 0; base < n_tiles; base += 1024u) {
+        const uint32_t t = base + threadIdx.x;
+        const uint64_t v = t < n_tiles ? sums[t] : 0;
+        const uint64_t incl = wave_inclusive_sum_u64(v);
+        if (lane_id() == LBVH_WAVE - 1) s_wave[wave] = incl;
+        __syncthreads();
+        uint64_t before = 0, all = 0;
+#pragma unroll
+        for (uint32_t k = 0; k < 16u; k++) {
+            const uint64_t s = s_wave[k];
+            if (k < wave) before += s;
+            all += s;
+        }
+        if (t < n_tiles) sums[t] = carry + before + (incl - v);
+        carry += all;
+        __syncthreads();
+    }
+}
+
+__global__ __launch_bounds__(256) void overlap_offsets_kernel(const uint32_t* __restrict__ counts, uint32_t total,
+                                                              const uint64_t* __restrict__ tile_prefix,   // nullptr: one tile
+                                                              uint64_t* __restrict__ offsets)             // total + 1 words
+{
+    __shared__ uint64_t s_wave[4];
+    const uint64_t first = (uint64_t)blockIdx.x * kScanTile + threadIdx.x * 4u;
+    const uint4 c = load_tile_counts(counts, first, total);
+    const uint64_t mine = ((uint64_t)c.x + c.y) + ((uint64_t)c.z + c.w);
+    const uint64_t incl = wave_inclusive_sum_u64(mine);
+    const uint32_t wave = threadIdx.x / LBVH_WAVE;
+    if (lane_id() == LBVH_WAVE - 1) s_wave[wave] = incl;
+    __syncthreads();
+    uint64_t o0 = (tile_prefix ? tile_prefix[blockIdx.x] : 0) + (incl - mine);
+#pragma unroll
+    for (uint32_t k = 0; k < 3u; k++)
+        if (k < wave) o0 += s_wave[k];
+    const uint64_t o1 = o0 + c.x, o2 = o1 + c.y, o3 = o2 + c.z;
+    if (first + 3 <= total && ((uintptr_t)offsets & 15) == 0) {
+        ulonglong2* dst = reinterpret_cast<ulonglong2*>(offsets + first);
+        dst[0] = make_ulonglong2(o0, o1);
+        dst[1] = make_ulonglong2(o2, o3);
+    } else {
+        if (first <= total) offsets[first] = o0;
+        if (first + 1 <= total) offsets[first + 1] = o1;
+        if (first + 2 <= total) offsets[first + 2] = o2;
+        if (first + 3 <= total) offsets[first + 3] = o3;
+    }
+}
+
 // ---- crossing parities of points along fixed directions (lbvh_point_crossings, include/lbvh.h) -------------------------
 // The directions travel by value in the kernel's arguments; a lane reads the one it walks next from there.
 struct crossing_dirs { float d[LBVH_CROSSING_MAX_DIRS][3]; };
@@ -1245,6 +1488,57 @@ static lbvh_status point_queries(lbvh_context* ctx, const lbvh_point_query* d_qu
     return LBVH_OK;
 }
 
+// lbvh_box_overlaps / lbvh_gather_within_distance: count walk -> scan -> fill walk, all on the context's stream, no host wait.
+// The counts (4 bytes per query) and the tile sums of the scan live where lbvh_trace_rays keeps its two live-ray lists: the ray
+// scratch is sized for 8 bytes per query there, and the list is dropped anyway.
+template <bool BOX>
+static lbvh_status overlap_queries(lbvh_context* ctx, const void* d_queries, size_t count, const lbvh_scene* h_scene, uint64_t* d_offsets,
+                                   uint32_t* d_tris, uint64_t capacity, const char* who)
+{
+    if (!ctx) return LBVH_ERR_INVALID_ARG;
+    if (count == 0) return LBVH_OK;
+    LBVH_REQUIRE(ctx, d_queries != nullptr && h_scene != nullptr && d_offsets != nullptr);
+    LBVH_REQUIRE(ctx, d_tris != nullptr || capacity == 0);
+    LBVH_REQUIRE(ctx, ((uintptr_t)d_queries & 15) == 0 && ((uintptr_t)d_offsets & 7) == 0 && ((uintptr_t)d_tris & 3) == 0);
+    LBVH_REQUIRE(ctx, count <= 0xFFFFFFFFull);
+    {
+        const int frc = lbvh_require_fast(ctx, *h_scene, who);
+        if (frc != LBVH_OK) return frc;
+    }
+    LBVH_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    int rc = lbvh_reserve(ctx, &ctx->ray_scratch, &ctx->ray_scratch_bytes, ray_scratch_bytes_for(count));
+    if (rc != LBVH_OK) return rc;
+    ctx->ray_list.valid = false;
+    rc = ensure_wide_nodes(ctx);
+    if (rc != LBVH_OK) return rc;
+    const uint32_t lds = std::min<uint32_t>(ctx->ray_stack_lds, kWideStackLds), deep_cap = std::min<uint32_t>(ctx->ray_stack_deep, kWideStackDeep);
+    const lbvh_wide_node* wn = (const lbvh_wide_node*)ctx->wide_nodes;
+    const float4* q = (const float4*)d_queries;
+    const uint32_t total = (uint32_t)count, waves = ray_waves_of(count), leaf_base = ctx->fast_capacity;
+    uint32_t* counts = ray_list(ctx, count, 0);
+    uint64_t* tile_sums = (uint64_t*)ray_list(ctx, count, 1);
+    const uint32_t n_tiles = total / kScanTile + 1u;           // the tiles cover total + 1 offsets
+    // (8 bytes per tile sum: (count / 1024 + 1) * 8 <= list_bytes(count) = 4 * count rounded up to 256, for every count >= 1)
+    if (ctx->ray_stats) LBVH_LAUNCH(ctx, (overlap_wide_kernel<BOX, false, true>), dim3(waves), dim3(LBVH_WAVE), q, total, wn, ctx->fast_nodes, leaf_base,
+                                    counts, (const uint64_t*)nullptr, (uint32_t*)nullptr, (uint64_t)0, deep_stacks(ctx, count), lds, deep_cap, ctx->fault_dev, ctx->ray_stats);
+    else LBVH_LAUNCH(ctx, (overlap_wide_kernel<BOX, false, false>), dim3(waves), dim3(LBVH_WAVE), q, total, wn, ctx->fast_nodes, leaf_base,
+                     counts, (const uint64_t*)nullptr, (uint32_t*)nullptr, (uint64_t)0, deep_stacks(ctx, count), lds, deep_cap, ctx->fault_dev, ctx->ray_stats);
+    if (n_tiles > 1u) {
+        LBVH_LAUNCH(ctx, overlap_tile_sums_kernel, dim3(n_tiles), dim3(256), (const uint32_t*)counts, total, tile_sums);
+        LBVH_LAUNCH(ctx, overlap_scan_sums_kernel, dim3(1), dim3(1024), tile_sums, n_tiles);
+    }
+    LBVH_LAUNCH(ctx, overlap_offsets_kernel, dim3(n_tiles), dim3(256), (const uint32_t*)counts, total,
+                n_tiles > 1u ? (const uint64_t*)tile_sums : (const uint64_t*)nullptr, d_offsets);
+    if (capacity != 0) {
+        if (ctx->ray_stats) LBVH_LAUNCH(ctx, (overlap_wide_kernel<BOX, true, true>), dim3(waves), dim3(LBVH_WAVE), q, total, wn, ctx->fast_nodes, leaf_base,
+                                        (uint32_t*)nullptr, (const uint64_t*)d_offsets, d_tris, capacity, deep_stacks(ctx, count), lds, deep_cap, ctx->fault_dev, ctx->ray_stats);
+        else LBVH_LAUNCH(ctx, (overlap_wide_kernel<BOX, true, false>), dim3(waves), dim3(LBVH_WAVE), q, total, wn, ctx->fast_nodes, leaf_base,
+                         (uint32_t*)nullptr, (const uint64_t*)d_offsets, d_tris, capacity, deep_stacks(ctx, count), lds, deep_cap, ctx->fault_dev, ctx->ray_stats);
+    }
+    LBVH_HIP_TRY(ctx, hipGetLastError());
+    return LBVH_OK;
+}
+
 // lbvh_point_crossings: the four-wide walk only (lbvh_debug_ray_walker does not apply), the directions by value in the arguments
 static lbvh_status point_crossings(lbvh_context* ctx, const lbvh_point_query* d_points, size_t count, const float* h_dirs, uint32_t n_dirs,
                                    const lbvh_scene* h_scene, uint32_t* d_parity)
@@ -1301,6 +1595,18 @@ lbvh_status lbvh_within_distance(lbvh_context* ctx, const lbvh_point_query* d_qu
                                  uint32_t* d_flags)
 {
     return point_queries<true>(ctx, d_queries, count, h_scene, d_flags, "lbvh_within_distance");
+}
+
+lbvh_status lbvh_box_overlaps(lbvh_context* ctx, const lbvh_aabb* d_boxes, size_t count, const lbvh_scene* h_scene,
+                              uint64_t* d_offsets, uint32_t* d_tris, uint64_t capacity)
+{
+    return overlap_queries<true>(ctx, d_boxes, count, h_scene, d_offsets, d_tris, capacity, "lbvh_box_overlaps");
+}
+
+lbvh_status lbvh_gather_within_distance(lbvh_context* ctx, const lbvh_point_query* d_queries, size_t count, const lbvh_scene* h_scene,
+                                        uint64_t* d_offsets, uint32_t* d_tris, uint64_t capacity)
+{
+    return overlap_queries<false>(ctx, d_queries, count, h_scene, d_offsets, d_tris, capacity, "lbvh_gather_within_distance");
 }
 
 lbvh_status lbvh_animate(lbvh_context* ctx, const lbvh_triangle* d_rest, uint32_t n, const uint32_t* d_body,

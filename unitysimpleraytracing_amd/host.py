@@ -394,6 +394,46 @@ class RaytracingMeshDrawer:
         s = self.container.scene()
         N.check(self.ctx.handle, fn(self.ctx.handle, queries.device, queries.size, C.byref(s), out.device))
 
+    def box_overlaps(self, boxes, offsets, tris=None):
+        """Every triangle whose own box touches each box of the DataBuffer `boxes` (layouts.AABB), as a CSR list on the caller's
+        buffers: `offsets` (uint64 DataBuffer, at least boxes.size + 1 entries) always complete; `tris` (uint32 DataBuffer, its size
+        is the capacity) receives the ORIGINAL triangle indices, segment k = tris[offsets[k] : offsets[k + 1]], in no particular
+        order.  tris=None counts only.  Nothing is written beyond tris.size; offsets[boxes.size] says what was needed.  Asynchronous."""
+        self._overlaps(N.lib.lbvh_box_overlaps, boxes, L.AABB, offsets, tris)
+
+    def gather_within_distance(self, queries, offsets, tris=None):
+        """The same for points with radii (layouts.POINT_QUERY): every triangle within_distance would accept."""
+        self._overlaps(N.lib.lbvh_gather_within_distance, queries, L.POINT_QUERY, offsets, tris)
+
+    def _overlaps(self, fn, queries, dtype, offsets, tris):
+        if queries.dtype != dtype or offsets.dtype != np.uint64 or offsets.size < queries.size + 1 or \
+                (tris is not None and tris.dtype != np.uint32):
+            raise ValueError(f"queries must be a DataBuffer of {dtype}, offsets one of uint64 with one entry more, tris one of uint32 or None")
+        s = self.container.scene()
+        N.check(self.ctx.handle, fn(self.ctx.handle, queries.device, queries.size, C.byref(s), offsets.device,
+                                    tris.device if tris is not None else None, tris.size if tris is not None else 0))
+
+    def overlaps(self, queries, min_capacity=1):
+        """Convenience: count -> one 8-byte download -> allocate -> fill.  `queries`: a DataBuffer of layouts.AABB (box form) or of
+        layouts.POINT_QUERY (distance form).  Returns (offsets, tris): host arrays, uint64[queries.size + 1] and uint32[total]."""
+        call = self.box_overlaps if queries.dtype == L.AABB else self.gather_within_distance
+        count = queries.size
+        offsets = DataBuffer(self.ctx, count + 1, np.uint64)
+        try:
+            call(queries, offsets)
+            last = np.zeros(1, dtype=np.uint64)
+            N.check(self.ctx.handle, N.lib.lbvh_buffer_download(self.ctx.handle, last.ctypes.data_as(C.c_void_p),
+                                                                C.c_void_p(offsets.device.value + 8 * count), 8))
+            total = int(last[0])
+            tris = DataBuffer(self.ctx, max(total, int(min_capacity)), np.uint32)
+            try:
+                call(queries, offsets, tris)
+                return offsets.get_data().copy(), tris.get_data()[:total].copy()
+            finally:
+                tris.dispose()
+        finally:
+            offsets.dispose()
+
     def count_hits(self, rays, counts):
         """The number of candidates of each ray of `rays` (layouts.RAY) in (t_min, t_max) into the uint32 DataBuffer `counts`: every
         triangle crossed counts, two at the same t count 2.  Asynchronous."""

@@ -316,6 +316,67 @@ static int points_main(int argc, char** argv)
     return 0;
 }
 
+// lbvh_driver overlaps [n | file.obj] [count] [size]: `count` boxes with centres in the mesh's box and half-extents up to `size` x its
+// extent, and the balls of the same centres with radius up to `size` x the largest extent; count -> one 8-byte read -> fill
+static int overlaps_main(int argc, char** argv)
+{
+    const char* what = argc > 2 ? argv[2] : "4096";
+    const size_t len = std::strlen(what);
+    const bool from_obj = len > 4 && std::strcmp(what + len - 4, ".obj") == 0;
+    const size_t count = argc > 3 ? (size_t)strtoull(argv[3], nullptr, 10) : 65536;
+    const float size = argc > 4 ? (float)atof(argv[4]) : 0.1f;
+    try {
+        const std::vector<lbvh_triangle> mesh = from_obj ? lbvh::MeshTriangles(lbvh::LoadObj(what)) : random_mesh((uint32_t)atoi(what));
+        float lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
+        for (const auto& t : mesh)
+            for (int k = 0; k < 3; k++) {
+                lo[k] = std::fmin(lo[k], std::fmin(t.a[k], std::fmin(t.b[k], t.c[k])));
+                hi[k] = std::fmax(hi[k], std::fmax(t.a[k], std::fmax(t.b[k], t.c[k])));
+            }
+        const float widest = std::fmax(hi[0] - lo[0], std::fmax(hi[1] - lo[1], hi[2] - lo[2]));
+        lbvh::Context ctx(0);
+        lbvh::RaytracingMeshDrawer drawer(ctx, mesh);
+        drawer.Awake();
+        lbvh::DataBuffer<lbvh_aabb> boxes(ctx, count);
+        lbvh::DataBuffer<lbvh_point_query> balls(ctx, count);
+        uint64_t seed = 3;
+        for (size_t i = 0; i < count; i++) {
+            lbvh_aabb& b = boxes.LocalBuffer()[i];
+            lbvh_point_query& q = balls.LocalBuffer()[i];
+            std::memset(&b, 0, sizeof b);
+            for (int k = 0; k < 3; k++) {
+                const float c = uniform(seed, lo[k], hi[k]), h = uniform(seed, 0.0f, size * (hi[k] - lo[k]));
+                b.min[k] = c - h;
+                b.max[k] = c + h;
+                q.p[k] = c;
+            }
+            const float r = uniform(seed, 0.0f, size * widest);
+            q.max_dist2 = r * r;
+        }
+        boxes.Sync();
+        balls.Sync();
+        lbvh::DataBuffer<uint64_t> offsets(ctx, count + 1);
+        unsigned long long total[2] = {0, 0}, index_sum[2] = {0, 0};
+        for (int form = 0; form < 2; form++) {
+            if (form == 0) drawer.BoxOverlaps(boxes, offsets);
+            else drawer.GatherWithinDistance(balls, offsets);
+            offsets.GetData();
+            total[form] = offsets.LocalBuffer()[count];
+            lbvh::DataBuffer<uint32_t> tris(ctx, total[form] ? (size_t)total[form] : 1);
+            if (form == 0) drawer.BoxOverlaps(boxes, offsets, &tris);
+            else drawer.GatherWithinDistance(balls, offsets, &tris);
+            tris.GetData();
+            for (size_t i = 0; i < (size_t)total[form]; i++) index_sum[form] += tris.LocalBuffer()[i];
+        }
+        std::printf("{\"triangles\": %zu, \"queries\": %zu, \"box_total\": %llu, \"box_index_sum\": %llu, \"ball_total\": %llu, \"ball_index_sum\": %llu}\n",
+                    mesh.size(), count, total[0], index_sum[0], total[1], index_sum[1]);
+    } catch (const std::exception& e) {
+        std::fprintf(stderr, "%s\n", e.what());
+        return 1;
+    }
+    return 0;
+}
+
 static int crossings_main(int argc, char** argv)
 {
     const char* what = argc > 2 ? argv[2] : "4096";
@@ -388,6 +449,7 @@ int main(int argc, char** argv)
 {
     if (argc > 1 && std::strcmp(argv[1], "crossings") == 0) return crossings_main(argc, argv);
     if (argc > 1 && std::strcmp(argv[1], "points") == 0) return points_main(argc, argv);
+    if (argc > 1 && std::strcmp(argv[1], "overlaps") == 0) return overlaps_main(argc, argv);
     if (argc > 1 && std::strcmp(argv[1], "rays") == 0) return rays_main(argc, argv);
     if (argc > 1 && std::strcmp(argv[1], "sort") == 0) return sort_main(argc, argv);
     if (argc > 1 && std::strcmp(argv[1], "multi") == 0) return multi_main(argc, argv);

@@ -334,6 +334,25 @@ public:
         check(ctx_.get(), lbvh_within_distance(ctx_.get(), (const lbvh_point_query*)queries.DeviceBuffer(), queries.Size(), &s,
                                                (uint32_t*)flags.DeviceBuffer()));
     }
+    // WHICH triangles touch each box / lie within each point's radius, as a CSR list (lbvh_box_overlaps /
+    // lbvh_gather_within_distance; asynchronous): offsets[k] .. offsets[k + 1] = query k's segment of `tris` (ORIGINAL triangle
+    // indices, in no particular order).  tris == nullptr counts only; otherwise its size is the capacity: nothing is written
+    // beyond it, and offsets[queries.Size()] says what was needed.
+    void BoxOverlaps(const DataBuffer<lbvh_aabb>& boxes, DataBuffer<uint64_t>& offsets, DataBuffer<uint32_t>* tris = nullptr)
+    {
+        if (offsets.Size() < boxes.Size() + 1) throw Error(LBVH_ERR_INVALID_ARG, "BoxOverlaps: offsets needs one entry more than boxes");
+        const lbvh_scene s = container_->Scene();
+        check(ctx_.get(), lbvh_box_overlaps(ctx_.get(), (const lbvh_aabb*)boxes.DeviceBuffer(), boxes.Size(), &s, (uint64_t*)offsets.DeviceBuffer(),
+                                            tris ? (uint32_t*)tris->DeviceBuffer() : nullptr, tris ? (uint64_t)tris->Size() : 0));
+    }
+    void GatherWithinDistance(const DataBuffer<lbvh_point_query>& queries, DataBuffer<uint64_t>& offsets, DataBuffer<uint32_t>* tris = nullptr)
+    {
+        if (offsets.Size() < queries.Size() + 1) throw Error(LBVH_ERR_INVALID_ARG, "GatherWithinDistance: offsets needs one entry more than queries");
+        const lbvh_scene s = container_->Scene();
+        check(ctx_.get(), lbvh_gather_within_distance(ctx_.get(), (const lbvh_point_query*)queries.DeviceBuffer(), queries.Size(), &s,
+                                                      (uint64_t*)offsets.DeviceBuffer(), tris ? (uint32_t*)tris->DeviceBuffer() : nullptr,
+                                                      tris ? (uint64_t)tris->Size() : 0));
+    }
     // how many triangles each ray crosses in (t_min, t_max), and crossing parities of points along fixed directions — bit j of a
     // point's word: the count of the ray from it along dirs[j] (x, y, z; 1 .. 32 of them), AND 1 (lbvh_count_hits /
     // lbvh_point_crossings; asynchronous).  Inside / outside: more than half of the bits set.
