@@ -14,6 +14,7 @@ public static class LbvhNative
 {
     const string Lib = "lbvh";   // liblbvh.so on Linux
 
+    public const int K_CLOSEST_MAX = 32;           // LBVH_K_CLOSEST_MAX
     public const int ABI_VERSION = 11;             // LBVH_ABI_VERSION of the include/lbvh.h this file was written against
     public const int TRACE_REFERENCE = 0, TRACE_FAST = 1;
     // TRACE_FAST + the reference's choice wherever two triangles are hit at exactly the same t: every record == TRACE_REFERENCE's
@@ -141,6 +142,8 @@ public static class LbvhNative
     [DllImport(Lib)] public static extern int lbvh_trace_occluded(IntPtr ctx, IntPtr dRays, UIntPtr count, ref Scene scene, IntPtr dOccluded);
     [DllImport(Lib)] public static extern int lbvh_closest_point_query(IntPtr ctx, IntPtr dQueries, UIntPtr count, ref Scene scene, IntPtr dOut);
     [DllImport(Lib)] public static extern int lbvh_within_distance(IntPtr ctx, IntPtr dQueries, UIntPtr count, ref Scene scene, IntPtr dFlags);
+    [DllImport(Lib)] public static extern int lbvh_k_closest_points(IntPtr ctx, IntPtr dQueries, UIntPtr count, uint k, ref Scene scene, IntPtr dOut,
+        IntPtr dFound);
     [DllImport(Lib)] public static extern int lbvh_box_overlaps(IntPtr ctx, IntPtr dBoxes, UIntPtr count, ref Scene scene, IntPtr dOffsets, IntPtr dTris,
         ulong capacity);
     [DllImport(Lib)] public static extern int lbvh_gather_within_distance(IntPtr ctx, IntPtr dQueries, UIntPtr count, ref Scene scene, IntPtr dOffsets,

@@ -649,6 +649,34 @@ lbvh_status lbvh_closest_point_query(lbvh_context* ctx, const lbvh_point_query* 
 lbvh_status lbvh_within_distance(lbvh_context* ctx, const lbvh_point_query* d_queries, size_t count, const lbvh_scene* h_scene,
                                  uint32_t* d_flags);
 
+/* The k nearest triangles of `count` points, 1 <= k <= LBVH_K_CLOSEST_MAX, over the same scene by the same walk.
+ *   Active query, R = min(max_dist2, LBVH_MAX_FLOAT), dist2, box2 and the candidate predicate are exactly those of
+ *   lbvh_closest_point_query above: dist2_i < R && !(dist2_i < box2(own AABB_i)); a NaN dist2 is never a candidate, a point with a
+ *   NaN coordinate and an inactive query have none and are never walked.
+ *   Order: a query's candidates are ordered by (dist2 ascending, original triangle index ascending) — a total order, a
+ *   candidate's dist2 being a non-NaN, non-negative float.
+ *   Output: d_out holds count * k records, query-major.  With m_q = min(k, the number of candidates of query q),
+ *   d_out[q * k + j] = {dist2, tri, u, v} of query q's j-th candidate in that order for j < m_q, and the none-record
+ *   {LBVH_MAX_FLOAT, 0, 0, 0} for m_q <= j < k.  Every one of the count * k records is written by the call — the caller does
+ *   not pre-fill —, also for inactive queries.  d_found[q] = m_q; d_found may be NULL.
+ *   Hence: with k = 1 the output equals lbvh_closest_point_query's word for word; record 0 of every row equals that query's
+ *   record for every k; d_found[q] >= 1 exactly when lbvh_within_distance gives 1; and row q is the first m_q elements of
+ *   segment q of lbvh_gather_within_distance sorted by (dist2, tri), with their distances.
+ * Why the rows do not depend on the order of the walk (the argument at lbvh_closest_point_query, "best so far" read as "k-th
+ * best so far"): a query's pruning bound is R while fewer than k candidates are held and the dist2 of the k-th held after
+ * that; a slot is skipped only if box2 > bound, strictly.  Every candidate below a skipped slot has dist2 >= box2(leaf) >=
+ * box2(slot) > bound, so it sorts after the k-th held whatever its index; a candidate with dist2 == bound is never skipped,
+ * and the index comparison decides it.
+ * Needs the derived traversal scene (lbvh_build_fast_scene; a stale one is LBVH_ERR_INVALID_ARG), is asynchronous on the
+ * context's stream with no host wait, and uses the context's ray scratch: it drops the path tracer's live-path list (see
+ * lbvh_path_bounce).  count == 0 is a no-op.  Rejected: NULL d_queries / h_scene / d_out, k == 0 or k > LBVH_K_CLOSEST_MAX,
+ * d_queries or d_out not 16-byte aligned, d_found not 4-byte aligned, count > 2^32 - 1.  The index q * k is formed in 64 bits.
+ * One query per lane, each with a list of k entries in the wave's LDS (768 * k bytes per wave, sized from k at the call): the
+ * cost grows with k through the wider bound (more boxes entered), the insertions, and, from k = 16 up, fewer waves per CU. */
+#define LBVH_K_CLOSEST_MAX 32
+lbvh_status lbvh_k_closest_points(lbvh_context* ctx, const lbvh_point_query* d_queries, size_t count, uint32_t k,
+                                  const lbvh_scene* h_scene, lbvh_closest_point* d_out, uint32_t* d_found);
+
 /* Overlap queries: WHICH triangles are here — all triangles whose box touches a box, all triangles within a distance of a point —
  * as a CSR list, over the derived traversal scene in its four-wide form (the scene lbvh_closest_point_query walks).
  *   lbvh_box_overlaps: query k is an lbvh_aabb (_dummy0 / _dummy1 are not read).  Active query: min[a] <= max[a] on all three
@@ -746,7 +774,7 @@ lbvh_status lbvh_path_scatter(lbvh_context* ctx, const lbvh_scene* h_scene, cons
  * lbvh_path_bounce on the same d_states / d_hits listed as live (a list kept by the context).  Every library call that writes
  * into those buffers drops the list (lbvh_path_begin, lbvh_trace_rays, a primary trace into any part of d_hits,
  * lbvh_buffer_upload / _fill_u32 / _free), and so does lbvh_trace_forget — and so do lbvh_trace_closest,
- * lbvh_trace_occluded, lbvh_closest_point_query, lbvh_within_distance, lbvh_count_hits, lbvh_point_crossings, lbvh_box_overlaps and lbvh_gather_within_distance, whatever buffers they are given, since they use the same ray scratch; then every state is scanned again.  What the library
+ * lbvh_trace_occluded, lbvh_closest_point_query, lbvh_within_distance, lbvh_count_hits, lbvh_point_crossings, lbvh_box_overlaps, lbvh_gather_within_distance and lbvh_k_closest_points, whatever buffers they are given, since they use the same ray scratch; then every state is scanned again.  What the library
  * cannot see is a write of the CALLER's own (a kernel or hipMemcpy that revives or ends paths, Russian roulette): between two
  * consecutive bounces of a frame d_states and d_hits must not be written from outside the library — or lbvh_trace_forget must be
  * called after such a write. */

@@ -173,8 +173,9 @@ struct lbvh_context {
 hipEvent_t lbvh_prof_event(lbvh_context* ctx);
 
 // Every kernel launch of the library goes through this: a plain launch on the context's current lane,
-// bracketed by two events when profiling is on.
-#define LBVH_LAUNCH(ctx, kernel, grid, block, ...)                                      \
+// bracketed by two events when profiling is on.  LBVH_LAUNCH_SHMEM: with `shmem` bytes of dynamic LDS.
+#define LBVH_LAUNCH(ctx, kernel, grid, block, ...) LBVH_LAUNCH_SHMEM(ctx, kernel, grid, block, 0, __VA_ARGS__)
+#define LBVH_LAUNCH_SHMEM(ctx, kernel, grid, block, shmem, ...)                         \
     do {                                                                                \
         hipEvent_t _a = nullptr, _b = nullptr;                                          \
         if ((ctx)->prof_enabled) {                                                      \
@@ -182,7 +183,7 @@ hipEvent_t lbvh_prof_event(lbvh_context* ctx);
             _b = lbvh_prof_event(ctx);                                                  \
             (void)hipEventRecord(_a, (ctx)->cur_stream);                                \
         }                                                                               \
-        hipLaunchKernelGGL(kernel, grid, block, 0, (ctx)->cur_stream, __VA_ARGS__);     \
+        hipLaunchKernelGGL(kernel, grid, block, shmem, (ctx)->cur_stream, __VA_ARGS__); \
         if ((ctx)->prof_enabled) {                                                      \
             (void)hipEventRecord(_b, (ctx)->cur_stream);                                \
             (ctx)->prof_spans.push_back({#kernel, _a, _b});                             \

@@ -394,6 +394,22 @@ class RaytracingMeshDrawer:
         s = self.container.scene()
         N.check(self.ctx.handle, fn(self.ctx.handle, queries.device, queries.size, C.byref(s), out.device))
 
+    def k_closest_points(self, queries, k, out, found=None):
+        """The k nearest triangles (1 <= k <= 32) of each point of `queries` (layouts.POINT_QUERY) into the DataBuffer `out`
+        (layouts.CLOSEST_POINT, at least queries.size * k entries): row q = out[q * k : (q + 1) * k], nearest first, ties by the
+        lower triangle index, padded with none-records {MAX_FLOAT, 0, 0, 0}.  `found` (uint32 DataBuffer, optional) receives the
+        number of real records per row.  Asynchronous; read with out.get_data()[: queries.size * k].reshape(-1, k)."""
+        k = int(k)
+        if queries.dtype != L.POINT_QUERY or out.dtype != L.CLOSEST_POINT or out.size < queries.size * k or \
+                (found is not None and (found.dtype != np.uint32 or found.size < queries.size)):
+            raise ValueError("queries must be a DataBuffer of layouts.POINT_QUERY, out one of layouts.CLOSEST_POINT with k entries "
+                             "per query, found one of uint32 with at least as many entries as queries, or None")
+        if not 1 <= k <= N.K_CLOSEST_MAX:
+            raise ValueError(f"k must be 1 .. {N.K_CLOSEST_MAX}")
+        s = self.container.scene()
+        N.check(self.ctx.handle, N.lib.lbvh_k_closest_points(self.ctx.handle, queries.device, queries.size, k, C.byref(s), out.device,
+                                                             found.device if found is not None else None))
+
     def box_overlaps(self, boxes, offsets, tris=None):
         """Every triangle whose own box touches each box of the DataBuffer `boxes` (layouts.AABB), as a CSR list on the caller's
         buffers: `offsets` (uint64 DataBuffer, at least boxes.size + 1 entries) always complete; `tris` (uint32 DataBuffer, its size

@@ -334,6 +334,18 @@ public:
         check(ctx_.get(), lbvh_within_distance(ctx_.get(), (const lbvh_point_query*)queries.DeviceBuffer(), queries.Size(), &s,
                                                (uint32_t*)flags.DeviceBuffer()));
     }
+    // the k nearest triangles of each point (1 <= k <= LBVH_K_CLOSEST_MAX): out[q * k + j] = the j-th nearest of query q, ties by
+    // the lower triangle index, padded with none-records; found (optional): the number of real records per row
+    // (lbvh_k_closest_points; asynchronous)
+    void KClosestPoints(const DataBuffer<lbvh_point_query>& queries, uint32_t k, DataBuffer<lbvh_closest_point>& out,
+                        DataBuffer<uint32_t>* found = nullptr)
+    {
+        if (out.Size() < queries.Size() * (size_t)k) throw Error(LBVH_ERR_INVALID_ARG, "KClosestPoints: fewer than k records per query");
+        if (found && found->Size() < queries.Size()) throw Error(LBVH_ERR_INVALID_ARG, "KClosestPoints: fewer counts than queries");
+        const lbvh_scene s = container_->Scene();
+        check(ctx_.get(), lbvh_k_closest_points(ctx_.get(), (const lbvh_point_query*)queries.DeviceBuffer(), queries.Size(), k, &s,
+                                                (lbvh_closest_point*)out.DeviceBuffer(), found ? (uint32_t*)found->DeviceBuffer() : nullptr));
+    }
     // WHICH triangles touch each box / lie within each point's radius, as a CSR list (lbvh_box_overlaps /
     // lbvh_gather_within_distance; asynchronous): offsets[k] .. offsets[k + 1] = query k's segment of `tris` (ORIGINAL triangle
     // indices, in no particular order).  tris == nullptr counts only; otherwise its size is the capacity: nothing is written
