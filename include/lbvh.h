@@ -750,6 +750,35 @@ lbvh_status lbvh_point_crossings(lbvh_context* ctx, const lbvh_point_query* d_po
                                  const float* h_dirs /* n_dirs x 3 */, uint32_t n_dirs, const lbvh_scene* h_scene,
                                  uint32_t* d_parity);
 
+/* The first k hits along `count` rays, 1 <= k <= LBVH_K_CLOSEST_MAX (the same list as lbvh_k_closest_points), over the same
+ * scene by the four-wide closest-hit walk.
+ *   Active ray, T = min(t_max, LBVH_MAX_FLOAT) and the candidate set are exactly those of lbvh_trace_closest and lbvh_count_hits:
+ *   the own-box slab test with entry e, Moeller-Trumbore with the reference's rejections, t >= e, t_min < t < T.  A NaN t is never
+ *   a candidate; an inactive ray (!(t_min < t_max), NaN bounds included) has none and is never walked.
+ *   Order: a ray's candidates are ordered by (t ascending, original triangle index ascending).  t is compared as fp32 values:
+ *   -0 and +0 are equal and the index decides between them.
+ *   Output: d_hits holds count * k records, ray-major.  With m_q = min(k, the number of candidates of ray q),
+ *   d_hits[q * k + j] = {t, tri, u, v} of ray q's j-th candidate in that order for j < m_q, and the miss record
+ *   {LBVH_MAX_FLOAT, 0, 0, 0} for m_q <= j < k.  Every one of the count * k records is written by the call — the caller does
+ *   not pre-fill —, also for inactive rays (rows of miss records).  d_found[q] = m_q; d_found may be NULL.
+ *   Hence: with k = 1 the output equals lbvh_trace_closest's word for word; record 0 of every row equals that call's record for
+ *   every k; d_found[q] == min(k, lbvh_count_hits' d_counts[q]); and d_found[q] >= 1 exactly when lbvh_trace_occluded gives 1.
+ * Why the rows do not depend on the order of the walk (the argument at lbvh_k_closest_points with entry distances in place of
+ * box2): a ray's pruning bound is T while fewer than k candidates are held and the t of the k-th held after that; a slot is
+ * skipped only if the ray misses its box or its entry is > bound, strictly.  Every candidate below a skipped slot has
+ * t >= e(leaf) >= e(slot) > bound, so it sorts after the k-th held whatever its index; a candidate with t == bound is never
+ * skipped, and the index comparison decides it.  Nothing is pruned on a box's exit distance (see the note at lbvh_count_hits).
+ * Needs the derived traversal scene (lbvh_build_fast_scene; a stale one is LBVH_ERR_INVALID_ARG), is asynchronous on the
+ * context's stream with no host wait, and uses the context's ray scratch: it drops the path tracer's live-path list (see
+ * lbvh_path_bounce); a failed growth of that scratch is LBVH_ERR_OUT_OF_MEMORY with nothing written.  count == 0 is a no-op.
+ * Rejected: NULL ctx / d_rays / h_scene / d_hits, k == 0 or k > LBVH_K_CLOSEST_MAX, d_rays or d_hits not 16-byte aligned,
+ * d_found not 4-byte aligned, count > 2^32 - 1.  The index q * k is formed in 64 bits.  Four-wide walk only
+ * (lbvh_debug_ray_walker does not apply).  One ray per lane, each with a list of k entries in the wave's LDS (768 * k bytes per
+ * wave, sized from k at the call): the cost grows with k through the wider bound (more boxes entered), the insertions, and, at
+ * large k, fewer waves per CU. */
+lbvh_status lbvh_trace_k_closest(lbvh_context* ctx, const lbvh_ray* d_rays, size_t count, uint32_t k,
+                                 const lbvh_scene* h_scene, lbvh_hit* d_hits, uint32_t* d_found);
+
 /* Camera rays into path states (origin/dir as Raytracing.compute:108-126, throughput 1, radiance 0, alive). */
 lbvh_status lbvh_path_begin(lbvh_context* ctx, const lbvh_camera* h_camera, lbvh_path_state* d_states);
 
@@ -774,7 +803,7 @@ lbvh_status lbvh_path_scatter(lbvh_context* ctx, const lbvh_scene* h_scene, cons
  * lbvh_path_bounce on the same d_states / d_hits listed as live (a list kept by the context).  Every library call that writes
  * into those buffers drops the list (lbvh_path_begin, lbvh_trace_rays, a primary trace into any part of d_hits,
  * lbvh_buffer_upload / _fill_u32 / _free), and so does lbvh_trace_forget — and so do lbvh_trace_closest,
- * lbvh_trace_occluded, lbvh_closest_point_query, lbvh_within_distance, lbvh_count_hits, lbvh_point_crossings, lbvh_box_overlaps, lbvh_gather_within_distance and lbvh_k_closest_points, whatever buffers they are given, since they use the same ray scratch; then every state is scanned again.  What the library
+ * lbvh_trace_occluded, lbvh_closest_point_query, lbvh_within_distance, lbvh_count_hits, lbvh_point_crossings, lbvh_box_overlaps, lbvh_gather_within_distance, lbvh_k_closest_points and lbvh_trace_k_closest, whatever buffers they are given, since they use the same ray scratch; then every state is scanned again.  What the library
  * cannot see is a write of the CALLER's own (a kernel or hipMemcpy that revives or ends paths, Russian roulette): between two
  * consecutive bounces of a frame d_states and d_hits must not be written from outside the library — or lbvh_trace_forget must be
  * called after such a write. */

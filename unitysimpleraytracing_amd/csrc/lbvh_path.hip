@@ -1024,6 +1024,168 @@ __global__ __launch_bounds__(64) void k_closest_wide_kernel(const lbvh_point_que
     if (STATS) add_ray_stats(stats, n_queries, n_steps, n_tris);
 }
 
+// lbvh_trace_k_closest: the walk of trace_rays_wide_kernel<true, kClosest> with "closest so far" replaced by "k-th closest so far",
+// and the per-lane list of k_closest_wide_kernel: three arrays [slot][lane] of t bits, triangle index and the index of the
+// triangle's line, `cap` slots per lane, dynamic LDS sized at the launch from k (768 * k bytes per wave).  (best_t, best_tri) is the
+// pruning bound: (T, 0) while fewer than k candidates are held — the state the closest walk starts in, so t == T is never taken —,
+// then the list's last entry; a leaf is taken by the closest walk's own comparison against it and inserted by shifting the entries
+// that sort after it.  Boxes are skipped on their ENTRY distance only, strictly beyond the bound.  With k = 1 every decision is
+// the closest walk's.  u and v are not carried: when a ray's walk ends, ray_fast_triangle is evaluated once more on the stored
+// line of each survivor — the same operations on the same values, hence the same words — and the row is written, padded with
+// miss records.
+template <bool STATS>
+__global__ __launch_bounds__(64) void k_hits_wide_kernel(const lbvh_ray* __restrict__ rays, uint32_t total, uint32_t cap,
+                                                         const lbvh_wide_node* __restrict__ wide,
+                                                         const lbvh_fast_node* __restrict__ lines,
+                                                         lbvh_hit* __restrict__ out,               // [total][cap]
+                                                         uint32_t* __restrict__ found_out,         // [total] or nullptr
+                                                         uint32_t* __restrict__ deep,     // [gridDim.x][kWideStackDeep][64]
+                                                         uint32_t lds_depth,              // <= kWideStackLds
+                                                         uint32_t deep_cap,               // <= kWideStackDeep
+                                                         uint32_t* __restrict__ fault, lbvh_ray_stats* stats)
+{
+    __shared__ uint32_t s_stack[kWideStackLds][LBVH_WAVE];
+    extern __shared__ uint32_t s_list[];                 // [3][cap][64]: t bits | triangle index | line index
+    const uint32_t lane = threadIdx.x;
+    uint32_t* const l_t = s_list + lane;
+    uint32_t* const l_tri = l_t + cap * LBVH_WAVE;
+    uint32_t* const l_line = l_tri + cap * LBVH_WAVE;
+    uint32_t* my_deep = deep + (size_t)blockIdx.x * (kWideStackDeep * LBVH_WAVE) + threadIdx.x;
+    const uint32_t run = max((total + gridDim.x - 1) / gridDim.x, 32u);
+    uint32_t next = blockIdx.x * run;
+    if (next >= total) return;
+    const uint32_t end = min(next + run, total);
+    uint32_t n_rays = 0, n_steps = 0, n_tris = 0;
+    const float4 miss_record = make_float4(LBVH_MAX_FLOAT, __uint_as_float(0u), 0.0f, 0.0f);
+
+    bool active = false;
+    uint32_t i = 0;
+    ray_t ray = {};
+    float lo = 0.0f, best_t = LBVH_MAX_FLOAT;
+    uint32_t best_tri = 0, held = 0, sp = 0, node = 0;
+    auto push = [&](uint32_t ref) {
+        if (sp < lds_depth) { s_stack[sp][lane] = ref; sp++; }
+        else if (sp < lds_depth + deep_cap) { my_deep[(sp - lds_depth) * LBVH_WAVE] = ref; sp++; }
+        // a dropped entry would be a silently wrong row: report it, as the other walkers do (lbvh_debug_ray_stack_limit provokes it)
+        else __hip_atomic_store(fault, LBVH_FAULT_RAY_STACK, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    };
+    for (;;) {
+        const uint64_t idle = __ballot(!active);
+        if (idle != 0 && next < end) {
+            if (!active) {
+                const uint32_t k = next + mbcnt64(idle);
+                if (k < end) {
+                    i = k;
+                    const float4* r = reinterpret_cast<const float4*>(&rays[k]);
+                    const float4 o = r[0], d = r[1];
+                    ray.ox = o.x; ray.oy = o.y; ray.oz = o.z;
+                    ray.dx = d.x; ray.dy = d.y; ray.dz = d.z;
+                    ray.ix = 1.0f / d.x; ray.iy = 1.0f / d.y; ray.iz = 1.0f / d.z;
+                    lo = o.w;
+                    best_t = fminf(d.w, LBVH_MAX_FLOAT);         // T: candidates lie in (t_min, T)
+                    best_tri = 0; held = 0; sp = 0; node = 0;
+                    active = o.w < d.w;                          // load_plain_ray's rule: false for NaN bounds too
+                    if (!active) {                               // no candidates, no walk: the whole row is miss records
+                        float4* row = reinterpret_cast<float4*>(out) + (size_t)k * cap;
+                        for (uint32_t j = 0; j < cap; j++) row[j] = miss_record;
+                        if (found_out) found_out[k] = 0u;
+                    }
+                    if (STATS && active) n_rays++;
+                }
+            }
+            next += (uint32_t)__popcll(idle);
+        }
+        if (!__any(active) && next >= end) break;
+        if (active) {
+            if (STATS) n_steps++;
+            const float4* w = reinterpret_cast<const float4*>(&wide[node]);
+            const float4 lox = w[0], loy = w[1], loz = w[2], hix = w[3], hiy = w[4], hiz = w[5];
+            const uint4 ref = reinterpret_cast<const uint4*>(w)[6];
+            float t0, t1, t2, t3;
+            const bool h0 = wide_box(lox.x, loy.x, loz.x, hix.x, hiy.x, hiz.x, ray, t0) && !(t0 > best_t) && ref.x != kWideEmpty;
+            const bool h1 = wide_box(lox.y, loy.y, loz.y, hix.y, hiy.y, hiz.y, ray, t1) && !(t1 > best_t) && ref.y != kWideEmpty;
+            const bool h2 = wide_box(lox.z, loy.z, loz.z, hix.z, hiy.z, hiz.z, ray, t2) && !(t2 > best_t) && ref.z != kWideEmpty;
+            const bool h3 = wide_box(lox.w, loy.w, loz.w, hix.w, hiy.w, hiz.w, ray, t3) && !(t3 > best_t) && ref.w != kWideEmpty;
+            // leaf slots first: a lane's leaves one after the other, every lane's k-th at the same time
+            uint32_t leaves = (h0 && (ref.x >> 31) ? 1u : 0u) | (h1 && (ref.y >> 31) ? 2u : 0u) | (h2 && (ref.z >> 31) ? 4u : 0u) |
+                              (h3 && (ref.w >> 31) ? 8u : 0u);
+            while (leaves != 0u) {
+                const uint32_t k = (uint32_t)__builtin_ctz(leaves);
+                leaves &= leaves - 1u;
+                if (STATS) n_tris++;
+                const uint32_t line = pick4(ref, k) & 0x7FFFFFFFu;
+                float4 v0, v1, v2;
+                unpack_fast_triangle(reinterpret_cast<const float4*>(&lines[line]), v0, v1, v2);
+                float u = 0.0f, v = 0.0f;
+                const float dist = ray_fast_triangle(ray, v0, v1, v2, u, v);
+                const uint32_t tri = __float_as_uint(v0.w);
+                const float entry = k == 0u ? t0 : (k == 1u ? t1 : (k == 2u ? t2 : t3));
+                // (best_t, best_tri) is (T, 0) until k are held: dist == T is never taken.  Then it is the k-th held: the candidate
+                // must sort before it, ties by the lower triangle index
+                if (dist > lo && hit_counts(dist, entry) && (dist < best_t || (dist == best_t && tri < best_tri))) {
+                    uint32_t j = min(held, cap - 1u);    // the slot that becomes free: the end of the list, or its dropped last entry
+                    while (j != 0u) {
+                        const float tj = __uint_as_float(l_t[(j - 1u) * LBVH_WAVE]);
+                        const uint32_t ij = l_tri[(j - 1u) * LBVH_WAVE];
+                        if (!(dist < tj || (dist == tj && tri < ij))) break;
+                        l_t[j * LBVH_WAVE] = __float_as_uint(tj);
+                        l_tri[j * LBVH_WAVE] = ij;
+                        l_line[j * LBVH_WAVE] = l_line[(j - 1u) * LBVH_WAVE];
+                        j--;
+                    }
+                    l_t[j * LBVH_WAVE] = __float_as_uint(dist);
+                    l_tri[j * LBVH_WAVE] = tri;
+                    l_line[j * LBVH_WAVE] = line;
+                    held = min(held + 1u, cap);
+                    if (held == cap) {
+                        best_t = __uint_as_float(l_t[(cap - 1u) * LBVH_WAVE]);
+                        best_tri = l_tri[(cap - 1u) * LBVH_WAVE];
+                    }
+                }
+            }
+            // nodes to enter, ordered by entry distance: the order key is the distance's bit pattern (non-negative floats
+            // order like integers) with the slot number in its two lowest bits.  (best_t may have shrunk in the leaf loop since
+            // h0 .. h3 were formed: the entry distances are compared with it once more)
+            constexpr uint32_t none = 0xFFFFFFFFu;
+            uint32_t k0 = h0 && !(ref.x >> 31) && !(t0 > best_t) ? ((__float_as_uint(fmaxf(t0, 0.0f)) & ~3u) | 0u) : none;
+            uint32_t k1 = h1 && !(ref.y >> 31) && !(t1 > best_t) ? ((__float_as_uint(fmaxf(t1, 0.0f)) & ~3u) | 1u) : none;
+            uint32_t k2 = h2 && !(ref.z >> 31) && !(t2 > best_t) ? ((__float_as_uint(fmaxf(t2, 0.0f)) & ~3u) | 2u) : none;
+            uint32_t k3 = h3 && !(ref.w >> 31) && !(t3 > best_t) ? ((__float_as_uint(fmaxf(t3, 0.0f)) & ~3u) | 3u) : none;
+            {   // five compare-exchanges
+                uint32_t a, b;
+                a = min(k0, k1); b = max(k0, k1); k0 = a; k1 = b;
+                a = min(k2, k3); b = max(k2, k3); k2 = a; k3 = b;
+                a = min(k0, k2); b = max(k0, k2); k0 = a; k2 = b;
+                a = min(k1, k3); b = max(k1, k3); k1 = a; k3 = b;
+                a = min(k1, k2); b = max(k1, k2); k1 = a; k2 = b;
+            }
+            if (k0 != none) {
+                if (k3 != none) push(pick4(ref, k3 & 3u));       // farthest first: the nearest waiting sibling is popped first
+                if (k2 != none) push(pick4(ref, k2 & 3u));
+                if (k1 != none) push(pick4(ref, k1 & 3u));
+                node = pick4(ref, k0 & 3u);
+            } else if (sp != 0) {
+                sp--;
+                node = sp < lds_depth ? s_stack[sp][lane] : my_deep[(sp - lds_depth) * LBVH_WAVE];
+            } else {
+                // the row: the survivors in order, t, u and v from their lines again, then miss records
+                float4* row = reinterpret_cast<float4*>(out) + (size_t)i * cap;
+                for (uint32_t j = 0; j < held; j++) {
+                    float4 v0, v1, v2;
+                    unpack_fast_triangle(reinterpret_cast<const float4*>(&lines[l_line[j * LBVH_WAVE]]), v0, v1, v2);
+                    float u = 0.0f, v = 0.0f;
+                    const float dist = ray_fast_triangle(ray, v0, v1, v2, u, v);
+                    row[j] = make_float4(dist, v0.w, u, v);
+                }
+                for (uint32_t j = held; j < cap; j++) row[j] = miss_record;
+                if (found_out) found_out[i] = held;
+                active = false;
+            }
+        }
+    }
+    if (STATS) add_ray_stats(stats, n_rays, n_steps, n_tris);
+}
+
 // ---- overlap queries: every triangle in a box / within a distance, as a CSR list (include/lbvh.h) -----------------------
 // The first queries whose output length is not known at the call: a COUNT walk writes one 32-bit count per query into the ray
 // scratch, three small kernels scan the counts into the caller's 64-bit offsets, and a FILL walk — the same kernel, the same
@@ -1679,6 +1841,39 @@ static lbvh_status k_closest_points(lbvh_context* ctx, const lbvh_point_query* d
     return LBVH_OK;
 }
 
+// lbvh_trace_k_closest: the four-wide walk only (lbvh_debug_ray_walker does not apply), one launch; the per-lane lists are
+// dynamic LDS sized from k
+static lbvh_status trace_k_closest(lbvh_context* ctx, const lbvh_ray* d_rays, size_t count, uint32_t k, const lbvh_scene* h_scene,
+                                   lbvh_hit* d_hits, uint32_t* d_found)
+{
+    if (!ctx) return LBVH_ERR_INVALID_ARG;
+    if (count == 0) return LBVH_OK;
+    LBVH_REQUIRE(ctx, d_rays != nullptr && h_scene != nullptr && d_hits != nullptr);
+    LBVH_REQUIRE(ctx, k >= 1u && k <= (uint32_t)LBVH_K_CLOSEST_MAX);
+    LBVH_REQUIRE(ctx, ((uintptr_t)d_rays & 15) == 0 && ((uintptr_t)d_hits & 15) == 0 && ((uintptr_t)d_found & 3) == 0);
+    LBVH_REQUIRE(ctx, count <= 0xFFFFFFFFull);
+    {
+        const int frc = lbvh_require_fast(ctx, *h_scene, "lbvh_trace_k_closest");
+        if (frc != LBVH_OK) return frc;
+    }
+    LBVH_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    // only the deep stack slabs of the scratch are used, laid out as for lbvh_trace_rays (whose live-path list they may overwrite)
+    int rc = lbvh_reserve(ctx, &ctx->ray_scratch, &ctx->ray_scratch_bytes, ray_scratch_bytes_for(count));
+    if (rc != LBVH_OK) return rc;
+    ctx->ray_list.valid = false;
+    rc = ensure_wide_nodes(ctx);
+    if (rc != LBVH_OK) return rc;
+    const uint32_t lds = std::min<uint32_t>(ctx->ray_stack_lds, kWideStackLds), deep_cap = std::min<uint32_t>(ctx->ray_stack_deep, kWideStackDeep);
+    const lbvh_wide_node* wn = (const lbvh_wide_node*)ctx->wide_nodes;
+    const size_t list_lds = (size_t)3 * k * LBVH_WAVE * sizeof(uint32_t);       // 768 bytes per slot: 24 KiB at k = 32
+    if (ctx->ray_stats) LBVH_LAUNCH_SHMEM(ctx, k_hits_wide_kernel<true>, dim3(ray_waves_of(count)), dim3(LBVH_WAVE), list_lds, d_rays, (uint32_t)count, k,
+                                          wn, ctx->fast_nodes, d_hits, d_found, deep_stacks(ctx, count), lds, deep_cap, ctx->fault_dev, ctx->ray_stats);
+    else LBVH_LAUNCH_SHMEM(ctx, k_hits_wide_kernel<false>, dim3(ray_waves_of(count)), dim3(LBVH_WAVE), list_lds, d_rays, (uint32_t)count, k,
+                           wn, ctx->fast_nodes, d_hits, d_found, deep_stacks(ctx, count), lds, deep_cap, ctx->fault_dev, ctx->ray_stats);
+    LBVH_HIP_TRY(ctx, hipGetLastError());
+    return LBVH_OK;
+}
+
 // lbvh_box_overlaps / lbvh_gather_within_distance: count walk -> scan -> fill walk, all on the context's stream, no host wait.
 // The counts (4 bytes per query) and the tile sums of the scan live where lbvh_trace_rays keeps its two live-ray lists: the ray
 // scratch is sized for 8 bytes per query there, and the list is dropped anyway.
@@ -1769,6 +1964,12 @@ static lbvh_status point_crossings(lbvh_context* ctx, const lbvh_point_query* d_
 }
 
 extern "C" {
+
+lbvh_status lbvh_trace_k_closest(lbvh_context* ctx, const lbvh_ray* d_rays, size_t count, uint32_t k, const lbvh_scene* h_scene,
+                                 lbvh_hit* d_hits, uint32_t* d_found)
+{
+    return trace_k_closest(ctx, d_rays, count, k, h_scene, d_hits, d_found);
+}
 
 lbvh_status lbvh_point_crossings(lbvh_context* ctx, const lbvh_point_query* d_points, size_t count, const float* h_dirs, uint32_t n_dirs,
                                  const lbvh_scene* h_scene, uint32_t* d_parity)

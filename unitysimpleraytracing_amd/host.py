@@ -455,6 +455,22 @@ class RaytracingMeshDrawer:
         triangle crossed counts, two at the same t count 2.  Asynchronous."""
         self._trace_plain(N.lib.lbvh_count_hits, rays, counts, np.dtype(np.uint32))
 
+    def trace_k_closest(self, rays, k, hits, found=None):
+        """The first k hits (1 <= k <= 32) along each ray of `rays` (layouts.RAY) into the DataBuffer `hits` (layouts.HIT, at least
+        rays.size * k entries): row q = hits[q * k : (q + 1) * k], nearest first, ties by the lower triangle index, padded with
+        miss records {MAX_FLOAT, 0, 0, 0}.  `found` (uint32 DataBuffer, optional) receives the number of real records per row.
+        Asynchronous; read with hits.get_data()[: rays.size * k].reshape(-1, k)."""
+        k = int(k)
+        if rays.dtype != L.RAY or hits.dtype != L.HIT or hits.size < rays.size * k or \
+                (found is not None and (found.dtype != np.uint32 or found.size < rays.size)):
+            raise ValueError("rays must be a DataBuffer of layouts.RAY, hits one of layouts.HIT with k entries per ray, found one of "
+                             "uint32 with at least as many entries as rays, or None")
+        if not 1 <= k <= N.K_CLOSEST_MAX:
+            raise ValueError(f"k must be 1 .. {N.K_CLOSEST_MAX}")
+        s = self.container.scene()
+        N.check(self.ctx.handle, N.lib.lbvh_trace_k_closest(self.ctx.handle, rays.device, rays.size, k, C.byref(s), hits.device,
+                                                            found.device if found is not None else None))
+
     def point_crossings(self, queries, parity, dirs=None):
         """Bit j of the uint32 DataBuffer `parity` for each point of `queries` (layouts.POINT_QUERY; max_dist2 is not read): the
         parity of the number of triangles the ray from the point along dirs[j] crosses (dirs: up to 32 rows of x, y, z;

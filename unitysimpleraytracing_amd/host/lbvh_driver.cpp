@@ -22,6 +22,11 @@
 //     lbvh_driver knn <k> [n | file.obj] [count] [radius]   the mesh and the points of `points`; KClosestPoints with k records per
 //                                                point; prints the sum of the found counts, how many rows are full, the sum of all
 //                                                32-bit words of the count * k records (mod 2^64) and the first rows
+//     lbvh_driver khits <k> <n> <count> [t_max]  n random triangles and `count` rays from points around the mesh's box towards
+//                                                points inside it (t = 1 at the target, t_max default unbounded); TraceKClosest
+//                                                with k records per ray; prints the sum of the found counts, how many rows are
+//                                                full, the sum of all 32-bit words of the count * k records (mod 2^64) and the
+//                                                first rows
 //     lbvh_driver crossings [n | file.obj] [count] the mesh and the points of `points`; PointCrossings along the three default
 //                                                directions ((1,1,1)/sqrt 3, (-1,2,3)/sqrt 14, (4,-1,2)/sqrt 21) and CountHits
 //                                                on the same rays written out ({p, 0, dir, +inf}); prints the sum of the counts,
@@ -382,6 +387,69 @@ static int knn_main(int argc, char** argv)
     return 0;
 }
 
+static int khits_main(int argc, char** argv)
+{
+    const uint32_t k = argc > 2 ? (uint32_t)atoi(argv[2]) : 8;
+    const uint32_t n = argc > 3 ? (uint32_t)atoi(argv[3]) : 4096;
+    const size_t count = argc > 4 ? (size_t)strtoull(argv[4], nullptr, 10) : 65536;
+    const float t_max = argc > 5 ? (float)atof(argv[5]) : INFINITY;
+    try {
+        const std::vector<lbvh_triangle> mesh = random_mesh(n);
+        float lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
+        for (const auto& t : mesh)
+            for (int a = 0; a < 3; a++) {
+                lo[a] = std::fmin(lo[a], std::fmin(t.a[a], std::fmin(t.b[a], t.c[a])));
+                hi[a] = std::fmax(hi[a], std::fmax(t.a[a], std::fmax(t.b[a], t.c[a])));
+            }
+        lbvh::Context ctx(0);
+        lbvh::RaytracingMeshDrawer drawer(ctx, mesh);
+        drawer.Awake();
+        lbvh::DataBuffer<lbvh_ray> rays(ctx, count);
+        uint64_t seed = 3;
+        for (auto& r : rays.LocalBuffer()) {
+            for (int a = 0; a < 3; a++) {
+                const float grow = 0.25f * (hi[a] - lo[a]);
+                r.origin[a] = uniform(seed, lo[a] - grow, hi[a] + grow);
+                r.dir[a] = uniform(seed, lo[a], hi[a]) - r.origin[a];
+            }
+            r.t_min = 0.0f;
+            r.t_max = t_max;
+        }
+        rays.Sync();
+        lbvh::DataBuffer<lbvh_hit> rows(ctx, count * (size_t)k);
+        lbvh::DataBuffer<uint32_t> found(ctx, count);
+        drawer.TraceKClosest(rays, k, rows, &found);
+        rows.GetData();
+        found.GetData();
+        size_t found_sum = 0, full = 0;
+        uint64_t word_sum = 0;
+        for (size_t i = 0; i < count; i++) {
+            found_sum += found.LocalBuffer()[i];
+            full += found.LocalBuffer()[i] == k;
+        }
+        for (const lbvh_hit& c : rows.LocalBuffer()) {
+            uint32_t w[4];
+            std::memcpy(w, &c, sizeof w);
+            word_sum += (uint64_t)w[0] + w[1] + w[2] + w[3];
+        }
+        std::printf("{\"triangles\": %zu, \"rays\": %zu, \"k\": %u, \"found_sum\": %zu, \"full_rows\": %zu, \"word_sum\": %llu, \"rows\": [",
+                    mesh.size(), count, k, found_sum, full, (unsigned long long)word_sum);
+        for (size_t i = 0; i < std::min<size_t>(count, 3); i++) {
+            std::printf("%s[", i ? ", " : "");
+            for (uint32_t j = 0; j < found.LocalBuffer()[i]; j++) {
+                const lbvh_hit& c = rows.LocalBuffer()[i * k + j];
+                std::printf("%s[%.9g, %u]", j ? ", " : "", c.t, c.tri);
+            }
+            std::printf("]");
+        }
+        std::printf("]}\n");
+    } catch (const std::exception& e) {
+        std::fprintf(stderr, "%s\n", e.what());
+        return 1;
+    }
+    return 0;
+}
+
 // lbvh_driver overlaps [n | file.obj] [count] [size]: `count` boxes with centres in the mesh's box and half-extents up to `size` x its
 // extent, and the balls of the same centres with radius up to `size` x the largest extent; count -> one 8-byte read -> fill
 static int overlaps_main(int argc, char** argv)
@@ -516,6 +584,7 @@ int main(int argc, char** argv)
     if (argc > 1 && std::strcmp(argv[1], "crossings") == 0) return crossings_main(argc, argv);
     if (argc > 1 && std::strcmp(argv[1], "points") == 0) return points_main(argc, argv);
     if (argc > 1 && std::strcmp(argv[1], "knn") == 0) return knn_main(argc, argv);
+    if (argc > 1 && std::strcmp(argv[1], "khits") == 0) return khits_main(argc, argv);
     if (argc > 1 && std::strcmp(argv[1], "overlaps") == 0) return overlaps_main(argc, argv);
     if (argc > 1 && std::strcmp(argv[1], "rays") == 0) return rays_main(argc, argv);
     if (argc > 1 && std::strcmp(argv[1], "sort") == 0) return sort_main(argc, argv);

@@ -374,6 +374,17 @@ public:
         const lbvh_scene s = container_->Scene();
         check(ctx_.get(), lbvh_count_hits(ctx_.get(), (const lbvh_ray*)rays.DeviceBuffer(), rays.Size(), &s, (uint32_t*)counts.DeviceBuffer()));
     }
+    // the first k hits along each ray (1 <= k <= LBVH_K_CLOSEST_MAX): hits[q * k + j] = the j-th nearest hit of ray q, ties by the
+    // lower triangle index, padded with miss records; found (optional): the number of real records per row
+    // (lbvh_trace_k_closest; asynchronous)
+    void TraceKClosest(const DataBuffer<lbvh_ray>& rays, uint32_t k, DataBuffer<lbvh_hit>& hits, DataBuffer<uint32_t>* found = nullptr)
+    {
+        if (hits.Size() < rays.Size() * (size_t)k) throw Error(LBVH_ERR_INVALID_ARG, "TraceKClosest: fewer than k hit records per ray");
+        if (found && found->Size() < rays.Size()) throw Error(LBVH_ERR_INVALID_ARG, "TraceKClosest: fewer counts than rays");
+        const lbvh_scene s = container_->Scene();
+        check(ctx_.get(), lbvh_trace_k_closest(ctx_.get(), (const lbvh_ray*)rays.DeviceBuffer(), rays.Size(), k, &s,
+                                               (lbvh_hit*)hits.DeviceBuffer(), found ? (uint32_t*)found->DeviceBuffer() : nullptr));
+    }
     void PointCrossings(const DataBuffer<lbvh_point_query>& points, const std::vector<float>& dirs, DataBuffer<uint32_t>& parity)
     {
         if (parity.Size() < points.Size()) throw Error(LBVH_ERR_INVALID_ARG, "PointCrossings: fewer parity words than points");
