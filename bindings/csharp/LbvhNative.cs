@@ -30,6 +30,10 @@ public static class LbvhNative
     [StructLayout(LayoutKind.Sequential)]
     public struct Ray { public float originX, originY, originZ, tMin; public float dirX, dirY, dirZ, tMax; }
 
+    // lbvh_sphere_ray (include/lbvh.h): a moving sphere, 32 bytes: Ray with the radius where tMin is (SphereCasts.cs)
+    [StructLayout(LayoutKind.Sequential)]
+    public struct SphereRay { public float originX, originY, originZ, radius; public float dirX, dirY, dirZ, tMax; }
+
     // lbvh_point_query / lbvh_closest_point (include/lbvh.h): a point with its squared search radius (active iff maxDist2 > 0) and
     // the nearest triangle's record, 16 bytes each (PointQueries.cs)
     [StructLayout(LayoutKind.Sequential)]
@@ -142,6 +146,8 @@ public static class LbvhNative
     [DllImport(Lib)] public static extern int lbvh_trace_occluded(IntPtr ctx, IntPtr dRays, UIntPtr count, ref Scene scene, IntPtr dOccluded);
     [DllImport(Lib)] public static extern int lbvh_closest_point_query(IntPtr ctx, IntPtr dQueries, UIntPtr count, ref Scene scene, IntPtr dOut);
     [DllImport(Lib)] public static extern int lbvh_within_distance(IntPtr ctx, IntPtr dQueries, UIntPtr count, ref Scene scene, IntPtr dFlags);
+    [DllImport(Lib)] public static extern int lbvh_sphere_cast(IntPtr ctx, IntPtr dCasts, UIntPtr count, ref Scene scene, IntPtr dHits);
+    [DllImport(Lib)] public static extern int lbvh_sphere_cast_any(IntPtr ctx, IntPtr dCasts, UIntPtr count, ref Scene scene, IntPtr dFlags);
     [DllImport(Lib)] public static extern int lbvh_k_closest_points(IntPtr ctx, IntPtr dQueries, UIntPtr count, uint k, ref Scene scene, IntPtr dOut,
         IntPtr dFound);
     [DllImport(Lib)] public static extern int lbvh_trace_k_closest(IntPtr ctx, IntPtr dRays, UIntPtr count, uint k, ref Scene scene, IntPtr dHits,

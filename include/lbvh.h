@@ -779,6 +779,68 @@ lbvh_status lbvh_point_crossings(lbvh_context* ctx, const lbvh_point_query* d_po
 lbvh_status lbvh_trace_k_closest(lbvh_context* ctx, const lbvh_ray* d_rays, size_t count, uint32_t k,
                                  const lbvh_scene* h_scene, lbvh_hit* d_hits, uint32_t* d_found);
 
+/* A moving sphere: 32 bytes, arrays 16-byte aligned: lbvh_ray with the radius where t_min is. */
+typedef struct lbvh_sphere_ray {
+    float origin[3]; float radius;
+    float dir[3];    float t_max;
+} lbvh_sphere_ray;
+
+/* First contact of `count` moving spheres with the mesh (a sweep, "sphere cast"), over the derived traversal scene in its four-wide
+ * form by the per-lane walk of lbvh_trace_closest.  The sphere's centre moves as c(t) = origin + dir * t for 0 <= t < T,
+ * T = min(t_max, LBVH_MAX_FLOAT); dir need not be unit length and t is in units of dir.
+ *   Active cast: radius > 0 and radius < +inf, t_max > 0, no NaN in origin, every dir component finite, dot(dir, dir) > 0 (the
+ *   fp32 value; all false for NaN).  An inactive cast is never walked; it gets the miss record {LBVH_MAX_FLOAT, 0, 0, 0}
+ *   (lbvh_sphere_cast) or 0 (lbvh_sphere_cast_any).
+ *   Time of contact with one triangle: defined on a, e1, e2 of the triangle's line of the derived scene, in strict fp32, every
+ *   operation rounded on its own, dot as at lbvh_closest_point_query, cross(x, y) per component x1*y2 - x2*y1 (two products, one
+ *   difference), sqrtf and / correctly rounded.  With o = origin, d = dir, r = radius, R2 = r*r, dd = dot(d, d), and a11, a12, a22
+ *   of lbvh_closest_point_query:
+ *     start overlap   d0 = dist2 of lbvh_closest_point_query for the point o.  If d0 <= R2 the time is 0 (+0) and no other
+ *                     feature is looked at.
+ *     Otherwise the time is the least t among the features below that are valid and have t >= 0, taken in this order, a later
+ *     one replacing an earlier one only when strictly less (which fixes the sign of a zero); no such feature: no time.
+ *     face            n = cross(e1, e2)   h = r * sqrtf(dot(n, n))   m = o - a   s = dot(m, n)   dn = dot(d, n)
+ *                     sg = (s >= 0 ? 1 : -1)   s' = s*sg   dn' = dn*sg   t = (h - s') / dn'
+ *                     q = c(t) - a  (per component (o_k + d_k*t) - a_k)   d1 = dot(e1, q)   d2 = dot(e2, q)
+ *                     det = a11*a22 - a12*a12   u = (a22*d1 - a12*d2) / det   v = (a11*d2 - a12*d1) / det
+ *                     valid iff s' > h && dn' < 0 && u >= 0 && v >= 0 && u + v <= 1
+ *     three edges     (P, E) = (a, e1), (a, e2), (a + e1, e2 - e1), P and E per component in fp32:   m = o - P
+ *                     ee = dot(E, E)   me = dot(m, E)   de = dot(d, E)
+ *                     A = ee*dd - de*de   B = ee*dot(m, d) - de*me   Cq = ee*(dot(m, m) - R2) - me*me   disc = B*B - A*Cq
+ *                     t = (-B - sqrtf(disc)) / A   s = me + t*de
+ *                     valid iff A > 0 && disc >= 0 && 0 <= s && s <= ee
+ *     three vertices  P = a, a + e1, a + e2:   m = o - P   B = dot(m, d)   Cq = dot(m, m) - R2   disc = B*B - dd*Cq
+ *                     t = (-B - sqrtf(disc)) / dd          valid iff disc >= 0
+ *   (a comparison with a NaN is false: a NaN t never counts.)  The face is the slab of thickness r on the side the sphere starts
+ *   on, the edges are infinite cylinders cut to the segment, the vertices are spheres; a start inside a cylinder or a sphere that
+ *   is not a start overlap has a negative root there and the contact comes from another feature.
+ *   Candidate: triangle i is a candidate iff it has a time t_i, t_i < T, the ray (origin, dir) passes the slab test of the
+ *   triangle's own box grown by r — scene.triangle_aabb[i] with min - r and max + r, one fp32 operation per bound, the slab test of
+ *   every walker of this library — with entry distance e_i, and !(t_i < e_i).  A ray that misses the grown box has no candidate there.
+ *   lbvh_sphere_cast: d_hits[k] = {t, tri, u, v} of cast k's candidate with the least t (compared as fp32 values: -0 and +0 are
+ *   equal); on equal t the lower original triangle index, whatever order the walk meets them in.  (u, v) are those
+ *   lbvh_closest_point_query's definition gives for the point c(t) (per component o_k + d_k*t) and this triangle: the barycentrics
+ *   of the contact point a + e1*u + e2*v; the contact normal is (c(t) - contact point) / r.  No candidate: the miss record, never T.
+ *   lbvh_sphere_cast_any: d_flags[k] = 1 if cast k has any candidate, else 0.  The walk is the same (same near-first order) cut off
+ *   at its first accepted candidate: never more node fetches or triangle tests per cast.
+ * Why the record does not depend on the order of the walk (the argument of lbvh_trace_closest with grown boxes): lo - r and hi + r
+ * are monotone in lo and hi, and every box of the derived tree is the exact min / max union of what is below it, so the grown box
+ * of an ancestor contains the grown box of everything below it exactly in fp32; slab entries grow from a box to any box inside
+ * it, so e(ancestor) <= e(leaf) <= t for every candidate.  A slot is skipped only if the ray misses its grown box or its entry is
+ * > best, strictly: a subtree skipped that way holds no candidate at or below best.  Nothing is pruned on a box's exit distance.
+ * A time in front of its own grown box is fp32 noise (the sphere touching the triangle at c(t) puts c(t) inside the grown box); on
+ * ordinary meshes the rule rejects next to nothing.
+ * Both need the derived traversal scene (lbvh_build_fast_scene; a stale one is LBVH_ERR_INVALID_ARG), are asynchronous on the
+ * context's stream with no host wait, and use the context's ray scratch: they drop the path tracer's live-path list (see
+ * lbvh_path_bounce).  count == 0 is a no-op.  Rejected: NULL pointers, d_casts or d_hits not 16-byte aligned, d_flags not 4-byte
+ * aligned, count > 2^32 - 1.  Four-wide walk only (lbvh_debug_ray_walker does not apply); lbvh_debug_ray_stack_split,
+ * lbvh_debug_ray_stack_limit and lbvh_ray_stats_target apply as to the point queries.  The cost grows with the radius: every box
+ * is r larger on each side. */
+lbvh_status lbvh_sphere_cast(lbvh_context* ctx, const lbvh_sphere_ray* d_casts, size_t count, const lbvh_scene* h_scene,
+                             lbvh_hit* d_hits);
+lbvh_status lbvh_sphere_cast_any(lbvh_context* ctx, const lbvh_sphere_ray* d_casts, size_t count, const lbvh_scene* h_scene,
+                                 uint32_t* d_flags);
+
 /* Camera rays into path states (origin/dir as Raytracing.compute:108-126, throughput 1, radiance 0, alive). */
 lbvh_status lbvh_path_begin(lbvh_context* ctx, const lbvh_camera* h_camera, lbvh_path_state* d_states);
 
@@ -803,7 +865,7 @@ lbvh_status lbvh_path_scatter(lbvh_context* ctx, const lbvh_scene* h_scene, cons
  * lbvh_path_bounce on the same d_states / d_hits listed as live (a list kept by the context).  Every library call that writes
  * into those buffers drops the list (lbvh_path_begin, lbvh_trace_rays, a primary trace into any part of d_hits,
  * lbvh_buffer_upload / _fill_u32 / _free), and so does lbvh_trace_forget — and so do lbvh_trace_closest,
- * lbvh_trace_occluded, lbvh_closest_point_query, lbvh_within_distance, lbvh_count_hits, lbvh_point_crossings, lbvh_box_overlaps, lbvh_gather_within_distance, lbvh_k_closest_points and lbvh_trace_k_closest, whatever buffers they are given, since they use the same ray scratch; then every state is scanned again.  What the library
+ * lbvh_trace_occluded, lbvh_closest_point_query, lbvh_within_distance, lbvh_count_hits, lbvh_point_crossings, lbvh_box_overlaps, lbvh_gather_within_distance, lbvh_k_closest_points, lbvh_trace_k_closest, lbvh_sphere_cast and lbvh_sphere_cast_any, whatever buffers they are given, since they use the same ray scratch; then every state is scanned again.  What the library
  * cannot see is a write of the CALLER's own (a kernel or hipMemcpy that revives or ends paths, Russian roulette): between two
  * consecutive bounces of a frame d_states and d_hits must not be written from outside the library — or lbvh_trace_forget must be
  * called after such a write. */

@@ -58,7 +58,8 @@ lbvh_status lbvh_debug_ray_stack_split(lbvh_context* ctx, uint32_t lds_entries);
  * lbvh_trace_occluded and lbvh_count_hits on the four-wide walks (`rays` = active rays), and lbvh_point_crossings (`rays` = one
  * per (point, direction) pair), and lbvh_k_closest_points (`rays` = active queries; the triangle lines read again for the
  * survivors' u, v at the end of a query are not counted: with k = 1 the three counters equal lbvh_closest_point_query's),
- * and lbvh_trace_k_closest in the same way (`rays` = active rays; with k = 1 the counters equal the four-wide lbvh_trace_closest's). */
+ * and lbvh_trace_k_closest in the same way (`rays` = active rays; with k = 1 the counters equal the four-wide lbvh_trace_closest's),
+ * and lbvh_sphere_cast / lbvh_sphere_cast_any (`rays` = active casts). */
 typedef struct lbvh_ray_stats {
     uint64_t rays;
     uint64_t node_fetches;
@@ -77,7 +78,7 @@ lbvh_status lbvh_debug_ray_stack_limit(lbvh_context* ctx, uint32_t deep_entries)
  * a step's two fetches in flight at once: few live rays, the launch is the chain of its longest), 2: that kernel for every
  * launch, 0: the binary nodes the packet walk uses.  Hit records do not depend on it (ties go to the lower triangle index
  * on all three); nor do the counts of lbvh_count_hits, which this hook steers as it steers lbvh_trace_closest.  The point
- * queries (lbvh_closest_point_query, lbvh_within_distance, lbvh_point_crossings, lbvh_k_closest_points) and lbvh_trace_k_closest have the four-wide walk only: this hook
+ * queries (lbvh_closest_point_query, lbvh_within_distance, lbvh_point_crossings, lbvh_k_closest_points), lbvh_trace_k_closest and the sphere casts have the four-wide walk only: this hook
  * leaves them alone.  lbvh_debug_ray_stack_split and lbvh_debug_ray_stack_limit apply to them as to the four-wide ray walk. */
 lbvh_status lbvh_debug_ray_walker(lbvh_context* ctx, uint32_t walker);
 

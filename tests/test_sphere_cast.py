@@ -1,0 +1,714 @@
+"""lbvh_sphere_cast / lbvh_sphere_cast_any: first contact of a moving sphere with the mesh, over the four-wide derived traversal
+scene.  The expectation is tests/sweep_reference.py: the header's time of contact in numpy float32, brute force over every (cast,
+triangle) pair with the boxes the library produced.  Every GPU comparison is word for word on uint32 views, no tolerance."""
+import ctypes as C
+import json
+import os
+import re
+import subprocess
+
+import numpy as np
+import pytest
+
+import point_reference as P
+import sweep_reference as S
+from unitysimpleraytracing_amd import scenes
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+F = np.float32
+INF = F(np.inf)
+RADII = (0.005, 0.02, 0.1)                  # of the scene's extent
+
+
+def H():
+    from unitysimpleraytracing_amd import host
+    return host
+
+
+def N():
+    from unitysimpleraytracing_amd import _native
+    return _native
+
+
+def L():
+    from unitysimpleraytracing_amd import layouts
+    return layouts
+
+
+def words(a):
+    return np.ascontiguousarray(a).view(np.uint32)
+
+
+def golden(name):
+    return np.load(os.path.join(ROOT, "tests", "golden", name + ".npz"))["triangles"]
+
+
+def positions(tris):
+    return tuple(np.ascontiguousarray(tris[k][:, :3], dtype=F) for k in "abc")
+
+
+def padded_boxes(a, b, c):
+    """scene.triangle_aabb as the Morton stage makes it (CPU tests only; the GPU tests take the boxes the library produced)"""
+    return np.minimum(np.minimum(a, b), c) - F(0.001), np.maximum(np.maximum(a, b), c) + F(0.001)
+
+
+def pack(a, b, c):
+    t = np.zeros(len(a), dtype=L().TRIANGLE)
+    t["a"][:, :3], t["b"][:, :3], t["c"][:, :3] = a, b, c
+    return t
+
+
+def make_casts(origin, direction, radius, t_max=INF):
+    s = np.zeros(len(origin), dtype=S.SPHERE_RAY)
+    s["origin"], s["dir"], s["radius"], s["t_max"] = origin, direction, radius, t_max
+    return s
+
+
+MISS_WORDS = words(np.array([S.MISS]))
+
+
+def extent_of(a, b, c):
+    pts = np.concatenate([a, b, c])
+    return float((pts.max(axis=0) - pts.min(axis=0)).max())
+
+
+# ---- CPU: the surface in every host ------------------------------------------------------------------------------------
+
+def test_header_declares_the_struct_and_both_prototypes_and_keeps_the_abi_version():
+    h = open(os.path.join(ROOT, "include", "lbvh.h")).read()
+    m = re.search(r"typedef struct lbvh_sphere_ray \{(.*?)\} lbvh_sphere_ray;", h, re.S)
+    assert m and re.findall(r"float\s+(\w+)", m.group(1)) == ["origin", "radius", "dir", "t_max"]
+    for fn, out in (("lbvh_sphere_cast", r"lbvh_hit\* d_hits"), ("lbvh_sphere_cast_any", r"uint32_t\* d_flags")):
+        assert re.search(r"lbvh_status " + fn + r"\(lbvh_context\* ctx, const lbvh_sphere_ray\* d_casts, size_t count, "
+                         r"const lbvh_scene\* h_scene,\s+" + out + r"\);", h), fn
+    assert re.search(r"#define LBVH_ABI_VERSION 11\b", h)                  # purely additive
+    bounce = h[h.index("CROSS-CALL STATE"):h.index("lbvh_status lbvh_path_bounce(")]
+    assert "lbvh_sphere_cast" in bounce and "lbvh_sphere_cast_any" in bounce
+
+
+def test_layout_signatures_csharp_and_cpp_host():
+    lay, nat = L(), N()
+    assert lay.SPHERE_RAY.itemsize == 32
+    assert [lay.SPHERE_RAY.fields[k][1] for k in ("origin", "radius", "dir", "t_max")] == [0, 12, 16, 28]
+    assert lay.SPHERE_RAY is S.SPHERE_RAY
+    for fn in ("lbvh_sphere_cast", "lbvh_sphere_cast_any"):
+        res, args = nat.SIGNATURES[fn]
+        assert res is C.c_int32 and len(args) == 5 and args[2] is C.c_size_t
+        assert getattr(nat.lib, fn).argtypes is not None
+    cs = open(os.path.join(ROOT, "bindings", "csharp", "LbvhNative.cs")).read()
+    m = re.search(r"public struct SphereRay \{(.*?)\}", cs, re.S)
+    assert m and re.findall(r"\b(\w+)\s*[,;]", m.group(1)) == ["originX", "originY", "originZ", "radius", "dirX", "dirY", "dirZ", "tMax"]
+    for fn in ("lbvh_sphere_cast", "lbvh_sphere_cast_any"):
+        assert re.search(r"public static extern int " + fn + r"\(IntPtr ctx, IntPtr \w+, UIntPtr count, ref Scene scene, IntPtr \w+\);", cs)
+    sc = open(os.path.join(ROOT, "bindings", "csharp", "SphereCasts.cs")).read()
+    assert "lbvh_sphere_cast(" in sc and "lbvh_sphere_cast_any(" in sc and "unsafe" not in sc
+    hpp = open(os.path.join(ROOT, "unitysimpleraytracing_amd", "host", "lbvh_host.hpp")).read()
+    assert "void SphereCast(" in hpp and "void SphereCastAny(" in hpp
+    assert hasattr(H().RaytracingMeshDrawer, "sphere_cast") and hasattr(H().RaytracingMeshDrawer, "sphere_cast_any")
+
+
+# ---- CPU: known answers of the restatement ------------------------------------------------------------------------------
+
+BIG = (np.array([[0, 0, 0], [500, 500, 500]], dtype=F), np.array([[8, 0, 0], [501, 500, 500]], dtype=F),
+       np.array([[0, 8, 0], [500, 501, 500]], dtype=F))        # one big triangle in z = 0 and a far dummy (scenes need n >= 2)
+
+
+def _one(origin, direction, radius, t_max=INF, tri=BIG):
+    a, b, c = tri
+    lo, hi = padded_boxes(a, b, c)
+    casts = make_casts(np.asarray(origin, dtype=F).reshape(-1, 3), np.asarray(direction, dtype=F).reshape(-1, 3), radius, t_max)
+    return S.reference(casts, a, b, c, lo, hi)
+
+
+def test_known_answers():
+    # dropped on the face interior from height 5 with r = 1: exactly h - r; twice the speed: half the time
+    r = _one([[2, 2, 5], [2, 2, 5]], [[0, 0, -1], [0, 0, -2]], F(1.0))
+    assert r.records["t"].tolist() == [4.0, 2.0] and r.records["tri"].tolist() == [0, 0] and r.flags.tolist() == [1, 1]
+    assert r.records["u"].tolist() == [0.25, 0.25] and r.records["v"].tolist() == [0.25, 0.25]
+    # onto the middle of edge ab from outside, in the plane: the centre stops r before the edge
+    r = _one([[4, -5, 0]], [[0, 1, 0]], F(1.0))
+    assert r.records["t"][0] == F(4.0) and (r.records["u"][0], r.records["v"][0]) == (F(0.5), F(0.0))
+    # onto vertex a along the diagonal of the plane: |origin - a| - r
+    r = _one([[-3, -4, 0]], [[0.6, 0.8, 0]], F(1.0))
+    assert abs(float(r.records["t"][0]) - 4.0) < 1e-5 and (r.records["u"][0], r.records["v"][0]) == (F(0.0), F(0.0))
+    # a start in overlap: t = 0 whatever the direction, the barycentrics of the nearest point
+    r = _one([[2, 2, 0.5], [2, 2, 0.5]], [[0, 0, 1], [1, 0, 0]], F(1.0))
+    assert r.records["t"].tolist() == [0.0, 0.0] and r.records["u"].tolist() == [0.25, 0.25]
+    # moving away: a miss
+    r = _one([[2, 2, 5]], [[0, 0, 1]], F(1.0))
+    assert r.flags[0] == 0 and (words(r.records) == MISS_WORDS).all()
+    # passing parallel to the face: clearance just above r misses, just below r hits (the rim of edge ac is met first)
+    r = _one([[-5, 2, 1.001], [-5, 2, 0.999]], [[1, 0, 0], [1, 0, 0]], F(1.0))
+    assert r.flags.tolist() == [0, 1] and 3.9 < r.records["t"][1] < 5.0
+    # t_max just short of contact: a miss; just past it: the hit (the bound is strict)
+    r = _one([[2, 2, 5]] * 3, [[0, 0, -1]] * 3, F(1.0), np.array([np.nextafter(F(4), F(0)), 4.0, np.nextafter(F(4), INF)], dtype=F))
+    assert r.flags.tolist() == [0, 0, 1]
+
+
+def test_every_inactive_form_is_a_miss_record():
+    o, d = [2, 2, 5], [0, 0, -1]
+    forms = [(o, d, 0.0, INF), (o, d, -1.0, INF), (o, d, np.nan, INF), (o, d, np.inf, INF), (o, d, 1.0, 0.0), (o, d, 1.0, -1.0),
+             (o, d, 1.0, np.nan), ([np.nan, 2, 5], d, 1.0, INF), (o, [0, np.inf, -1], 1.0, INF), (o, [0, np.nan, -1], 1.0, INF),
+             (o, [0, 0, 0], 1.0, INF), (o, [0, 0, -1e-30], 1.0, INF)]
+    casts = make_casts(np.array([f[0] for f in forms], dtype=F), np.array([f[1] for f in forms], dtype=F),
+                       np.array([f[2] for f in forms], dtype=F), np.array([f[3] for f in forms], dtype=F))
+    assert not S.active(casts).any()
+    a, b, c = BIG
+    r = S.reference(casts, a, b, c, *padded_boxes(a, b, c))
+    assert (r.flags == 0).all() and (words(r.records).reshape(-1, 4) == MISS_WORDS).all()
+    assert S.active(make_casts(np.array([o], dtype=F), np.array([d], dtype=F), F(1.0), INF)).all()
+
+
+# ---- cast sets ----------------------------------------------------------------------------------------------------------
+
+def aimed_casts(a, b, c, count, rng, radii=RADII, plain=False):
+    """Spheres that start outside the mesh's box and aim at points of its surface; the three radii in turn.  plain: unit
+    directions and t_max = +inf only (the float64 comparison).  Otherwise a mix: 15 % axis-aligned directions, 40 % non-unit
+    (scaled by 0.25 .. 4), half with a finite t_max around the contact, 10 % starting in overlap with a surface, and inactive
+    forms — scattered ones and one run of 70 in a row."""
+    ext = extent_of(a, b, c)
+    pts = np.concatenate([a, b, c])
+    k = rng.integers(0, len(a), count)
+    w = rng.dirichlet((1, 1, 1), count)
+    target = a[k] * w[:, :1] + b[k] * w[:, 1:2] + c[k] * w[:, 2:]
+    d = rng.normal(size=(count, 3))
+    if not plain:
+        axis = rng.random(count) < 0.15
+        d[axis] = np.eye(3)[rng.integers(0, 3, axis.sum())] * rng.choice([-1.0, 1.0], axis.sum())[:, None]
+    d /= np.linalg.norm(d, axis=1, keepdims=True)
+    reach = 1.25 * np.linalg.norm(pts.max(axis=0) - pts.min(axis=0)) + 0.2 * ext
+    origin = target - d * reach
+    radius = (np.array(radii)[np.arange(count) % len(radii)] * ext).astype(F)
+    t_max = np.full(count, INF, dtype=F)
+    if not plain:
+        scale = np.where(rng.random(count) < 0.4, rng.uniform(0.25, 4.0, count), 1.0)
+        d = d * scale[:, None]
+        finite = rng.random(count) < 0.5
+        t_max[finite] = (reach / scale * rng.uniform(0.6, 1.3, count))[finite]
+        inside = rng.random(count) < 0.1
+        origin[inside] = target[inside] + rng.normal(size=(inside.sum(), 3)) * (0.4 * radius[inside])[:, None]
+    casts = make_casts(origin.astype(F), d.astype(F), radius, t_max)
+    if not plain:
+        dead = rng.random(count) < 0.05
+        dead[count // 2: count // 2 + 70] = True
+        kind = rng.integers(0, 5, count)
+        casts["radius"][dead & (kind == 0)] = 0.0
+        casts["radius"][dead & (kind == 1)] = np.nan
+        casts["t_max"][dead & (kind == 2)] = -1.0
+        casts["dir"][dead & (kind == 3)] = 0.0
+        casts["origin"][dead & (kind == 4), 1] = np.nan
+    return casts
+
+
+def scene_positions(name):
+    if name == "cfg1_4096":
+        pos = np.load(os.path.join(ROOT, "tests", "golden", name + ".npz"))["positions"]
+        return tuple(np.ascontiguousarray(pos[:, k], dtype=F) for k in range(3))
+    return positions(golden(name))
+
+
+COUNTS = {"viking_room": 1500, "example_object3": 1000, "cfg1_4096": 1500}
+
+
+def parity_casts(name, a, b, c):
+    return aimed_casts(a, b, c, COUNTS[name], np.random.default_rng(5 + len(a)))
+
+
+# ---- CPU: the restatement against its float64 evaluation, and its self-consistency -----------------------------------------
+
+K_BOUND = 4 * 20384.0
+
+
+@pytest.mark.parametrize("name", ["viking_room", "example_object3"])
+def test_reference_agrees_with_its_float64_evaluation(name):
+    """Closest time: |t32 - t64| <= K * 2^-24 * extent / |dir| wherever both evaluations agree on hit or miss, t64 the same
+    definition in float64 on the same fp32 inputs, and at most 0.5 % of the casts flip between hit and miss.
+    Why K is large: the cylinder quadratic forms disc = B*B - A*Cq from terms of size ee^2 * dd * reach^2 that cancel down to
+    ee^2 * dd * r^2-sized values when the sphere grazes an edge, so t inherits an error of about 2^-24 * reach^2 / r relative to
+    the extent: the smallest radius (0.5 % of the extent) from a start 2.5 extents away is the worst.
+    Measured while the definition was written (150 casts per radius and scene), worst |t32 - t64| in units of 2^-24 * extent /
+    |dir| at the radii 0.5 % / 2 % / 10 % of the extent: viking_room 3497 / 1071 / 139, example_object3 20384 / 1813 / 277
+    (medians 1.5 .. 17; no cast flips between hit and miss on either scene).  K = 4 * 20384 = 81536.  The same figures as
+    distances |dist(c(t), reported triangle) - r|: viking_room 2707 / 786 / 83, example_object3 1343 / 389 / 99 units of
+    2^-24 * extent."""
+    a, b, c = positions(golden(name))
+    ext = extent_of(a, b, c)
+    worst_all, flips, total = 0.0, 0, 0
+    for j, radius in enumerate(RADII):
+        casts = aimed_casts(a, b, c, 150, np.random.default_rng(100 + j), radii=(radius,), plain=True)
+        t32, _ = S.nearest_time(casts, a, b, c, np.float32)
+        t64, tri64 = S.nearest_time(casts, a, b, c, np.float64)
+        both = np.isfinite(t32) & np.isfinite(t64)
+        flip = np.isfinite(t32) != np.isfinite(t64)
+        unit = 2.0 ** -24 * ext / np.linalg.norm(casts["dir"].astype(np.float64), axis=1)
+        err = np.abs(t32.astype(np.float64) - t64)[both] / unit[both]
+        print(f"{name}, r = {radius} * extent: {int(both.sum())} hits, worst |t32 - t64| = {err.max():.1f} * 2^-24 * extent / |dir|, "
+              f"median {np.median(err):.2f}, {int(flip.sum())} flips")
+        assert both.sum() > 100
+        assert err.max() <= K_BOUND
+        worst_all, flips, total = max(worst_all, float(err.max())), flips + int(flip.sum()), total + len(casts)
+        # self-consistency in float64: at c(t) the reported triangle is r away and nothing is nearer than r, within the same bound
+        # as a distance (|dir| * the bound on t)
+        hit = both & (t32 > 0)
+        ct = casts["origin"][hit].astype(np.float64) + casts["dir"][hit].astype(np.float64) * t32[hit].astype(np.float64)[:, None]
+        a64, e1, e2 = a.astype(np.float64), (b - a).astype(np.float64), (c - a).astype(np.float64)
+        d2, _, _ = P.point_triangle(ct[:, None, :], a64[None], e1[None], e2[None])
+        dist = np.sqrt(d2)
+        _, tri32 = S.nearest_time(casts[hit], a, b, c, np.float32)
+        tol = K_BOUND * 2.0 ** -24 * ext
+        rr = casts["radius"][hit].astype(np.float64)
+        own = dist[np.arange(len(ct)), tri32]
+        print(f"    worst |dist(c(t), reported) - r| = {np.abs(own - rr).max() / (2.0 ** -24 * ext):.1f}, worst r - nearest = "
+              f"{(rr - np.nanmin(dist, axis=1)).max() / (2.0 ** -24 * ext):.1f}  (units of 2^-24 * extent)")
+        assert (np.abs(own - rr) <= tol).all()
+        assert (np.nanmin(dist, axis=1) >= rr - tol).all()
+    print(f"{name}: worst over the radii {worst_all:.1f}, {flips} of {total} casts flip = {100.0 * flips / total:.2f} %")
+    assert flips <= 0.005 * total
+
+
+@pytest.mark.parametrize("name", ["viking_room", "example_object3", "cfg1_4096"])
+def test_the_accept_rule_rejects_next_to_nothing_on_the_parity_inputs(name):
+    """Of all (cast, triangle) pairs with a time in [0, T), the share that misses its grown box or has t < entry is at most 1 %:
+    the rule does not carry the parity tests.  Every pair of every parity cast is evaluated, with the Morton stage's boxes.
+    Measured: viking_room 0 of 196 251, example_object3 2 of 296 111, cfg1_4096 8 of 47 341 (0.017 %)."""
+    a, b, c = scene_positions(name)
+    lo, hi = padded_boxes(a, b, c)
+    casts = parity_casts(name, a, b, c)
+    r = S.reference(casts, a, b, c, lo, hi, casts_per_chunk=32, count_rule=True)
+    print(f"{name}: {r.valid} pairs with a time, {r.rejected} rejected = {100.0 * r.rejected / max(r.valid, 1):.3f} %")
+    assert r.valid > 1000 and r.rejected <= 0.01 * r.valid
+    plain = S.reference(casts, a, b, c, lo, hi)
+    assert (words(plain.records) == words(r.records)).all() and (plain.flags == r.flags).all()
+
+
+def test_shrunk_boxes_make_the_rule_reject():
+    a, b, c = positions(golden("viking_room"))
+    lo, hi = padded_boxes(a, b, c)
+    casts = parity_casts("viking_room", a, b, c)
+    before = S.reference(casts, a, b, c, lo, hi, casts_per_chunk=32, count_rule=True)
+    picked = np.unique(before.records["tri"][before.flags == 1])[:40]
+    centre, half = (lo[picked] + hi[picked]) * F(0.5), (hi[picked] - lo[picked]) * F(0.05)
+    lo2, hi2 = lo.copy(), hi.copy()
+    lo2[picked], hi2[picked] = centre - half, centre + half
+    after = S.reference(casts, a, b, c, lo2, hi2, casts_per_chunk=32, count_rule=True)
+    print(f"shrunk boxes: rejected {before.rejected} -> {after.rejected}")
+    assert after.valid == before.valid and after.rejected > before.rejected
+    assert (words(after.records) != words(before.records)).any()
+
+
+# ---- GPU -------------------------------------------------------------------------------------------------------------------
+
+class Casts:
+    """device buffers for one cast set and the two calls"""
+
+    def __init__(self, ctx, drawer, casts):
+        self.ctx, self.drawer, self.n = ctx, drawer, len(casts)
+        self.casts = H().DataBuffer(ctx, self.n, L().SPHERE_RAY)
+        self.casts.local[:] = casts
+        self.casts.sync()
+        self.hits = H().DataBuffer(ctx, self.n + 1, L().HIT)
+        self.flags = H().DataBuffer(ctx, self.n + 1, np.uint32)
+
+    def cast(self):
+        self.hits.fill_u32(0x7FC00000)
+        self.drawer.sphere_cast(self.casts, self.hits)
+        got = self.hits.get_data().copy()
+        assert (words(got[self.n:]) == 0x7FC00000).all()
+        return got[: self.n]
+
+    def any(self):
+        self.flags.fill_u32(0xDEADBEEF)
+        self.drawer.sphere_cast_any(self.casts, self.flags)
+        got = self.flags.get_data().copy()
+        assert got[self.n] == 0xDEADBEEF
+        return got[: self.n]
+
+    def dispose(self):
+        for b in (self.casts, self.hits, self.flags):
+            b.dispose()
+
+
+def assert_records(got, ref, what=""):
+    bad = np.nonzero((words(got).reshape(-1, 4) != words(ref.records).reshape(-1, 4)).any(axis=1))[0]
+    assert len(bad) == 0, (what, len(bad), bad[:10], got[bad[:3]], ref.records[bad[:3]])
+
+
+def library_boxes(drawer):
+    n = drawer.container.triangles_length
+    box = drawer.container.triangle_aabb.get_data()[:n]
+    return box["min"].copy(), box["max"].copy()
+
+
+_CASES = {}
+
+
+def parity_case(ctx, name):
+    """(positions, casts, reference, drawer): the reference is computed once per scene with the library's boxes; one context keeps
+    one derived traversal scene, so the scene is derived again for the test that asks"""
+    if name not in _CASES:
+        a, b, c = scene_positions(name)
+        d = H().RaytracingMeshDrawer(ctx, pack(a, b, c)).awake()
+        lo, hi = library_boxes(d)
+        casts = parity_casts(name, a, b, c)
+        _CASES[name] = ((a, b, c), casts, S.reference(casts, a, b, c, lo, hi), d)
+    _CASES[name][3].build_fast_scene()
+    return _CASES[name]
+
+
+SCENES = ["viking_room", "example_object3", "cfg1_4096"]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", SCENES)
+def test_s1_s2_records_and_flags_equal_the_brute_force_word_for_word(ctx, name):
+    _, casts, ref, d = parity_case(ctx, name)
+    q = Casts(ctx, d, casts)
+    got, flags = q.cast(), q.any()
+    q.dispose()
+    act = S.active(casts)
+    hit = ref.flags == 1
+    print(f"{name}: {len(casts)} casts, {int(act.sum())} active, {int(hit.sum())} touch, {int((ref.records['t'][hit] == 0).sum())} at "
+          f"t = 0, {int((ref.ties > 1).sum())} ties")
+    assert hit.sum() > 300 and (hit & (ref.records["t"] == 0)).sum() > 30 and (act & ~hit).sum() > 30 and (~act).sum() > 70
+    assert_records(got, ref, name)
+    assert (flags == ref.flags).all(), np.nonzero(flags != ref.flags)[0][:10]
+    assert (words(got[~act]).reshape(-1, 4) == MISS_WORDS).all() and (flags[~act] == 0).all()
+
+
+def pair_casts(count, seed=3):
+    a, b, c = BIG
+    rng = np.random.default_rng(seed)
+    casts = aimed_casts(a[:1], b[:1], c[:1], count, rng)
+    casts["radius"] = rng.choice(np.array([0.05, 0.5, 2.0], dtype=F), count)
+    return casts
+
+
+@pytest.mark.gpu
+def test_two_triangles_and_small_counts(ctx):
+    a, b, c = BIG
+    d = H().RaytracingMeshDrawer(ctx, pack(a, b, c)).awake()
+    lo, hi = library_boxes(d)
+    for count in (1, 31, 64, 65, 257):
+        casts = pair_casts(count, seed=count)
+        casts["radius"][0], casts["t_max"][0] = F(0.5), INF                      # the first cast is a live one
+        casts["origin"][0], casts["dir"][0] = (2, 2, 5), (0, 0, -1)
+        ref = S.reference(casts, a, b, c, lo, hi)
+        q = Casts(ctx, d, casts)
+        got, flags = q.cast(), q.any()
+        q.dispose()
+        assert_records(got, ref, count)
+        assert (flags == ref.flags).all() and got["t"][0] == F(4.5) and got["tri"][0] == 0
+    # runs of 64 or more inactive casts between active ones
+    casts = pair_casts(400, seed=9)
+    casts["radius"][50:130] = 0.0
+    casts["t_max"][200:270] = np.nan
+    ref = S.reference(casts, a, b, c, lo, hi)
+    act = S.active(casts)
+    assert not act[50:130].any() and not act[200:270].any() and ref.flags[:50].sum() > 5 and ref.flags[270:].sum() > 5
+    q = Casts(ctx, d, casts)
+    got, flags = q.cast(), q.any()
+    q.dispose()
+    assert_records(got, ref, "inactive runs")
+    assert (flags == ref.flags).all() and (words(got[~act]).reshape(-1, 4) == MISS_WORDS).all()
+    d.on_destroy()
+
+
+@pytest.mark.gpu
+def test_device_stack_radius_beyond_the_scene_and_the_rebuilt_wide_nodes(ctx):
+    (a, b, c), casts, ref, d = parity_case(ctx, "viking_room")
+    h, lib = ctx.handle, N().lib
+    q = Casts(ctx, d, casts)
+    try:
+        N().check(h, lib.lbvh_debug_ray_stack_split(h, 1))                       # all but one entry in device memory
+        assert_records(q.cast(), ref, "stack split 1")
+        assert (q.any() == ref.flags).all()
+    finally:
+        N().check(h, lib.lbvh_debug_ray_stack_split(h, 16))
+    d.build_fast_scene()                                                         # the four-wide nodes are made again on first use
+    assert_records(q.cast(), ref, "after a second build_fast_scene")
+    q.dispose()
+    # a radius larger than the whole scene: t = 0 on the lowest-index overlapping triangle
+    ext = extent_of(a, b, c)
+    centre = np.concatenate([a, b, c]).mean(axis=0)
+    big = make_casts(np.tile(centre, (70, 1)).astype(F), np.random.default_rng(1).normal(size=(70, 3)).astype(F), F(3.0 * ext))
+    lo, hi = library_boxes(d)
+    rb = S.reference(big, a, b, c, lo, hi)
+    q = Casts(ctx, d, big)
+    got, flags = q.cast(), q.any()
+    q.dispose()
+    assert_records(got, rb, "huge radius")
+    assert (got["t"] == 0).all() and (got["tri"] == 0).all() and (flags == 1).all()
+
+
+@pytest.mark.gpu
+def test_a_contact_on_a_shared_edge_goes_to_the_lower_index(ctx):
+    """two coplanar triangles sharing the edge (4, 0, 0) - (0, 4, 0), a sphere dropped on the middle of that edge: both have
+    t = 4 exactly, index 0 wins in either order"""
+    t0 = ([0, 0, 0], [4, 0, 0], [0, 4, 0])
+    t1 = ([4, 0, 0], [4, 4, 0], [0, 4, 0])
+    casts = make_casts(np.array([[2, 2, 5]] * 3, dtype=F), np.array([[0, 0, -1]] * 3, dtype=F), F(1.0),
+                       np.array([np.inf, 4.0, 4.5], dtype=F))
+    for order in ((t0, t1), (t1, t0)):
+        a, b, c = (np.array([t[k] for t in order], dtype=F) for k in range(3))
+        d = H().RaytracingMeshDrawer(ctx, pack(a, b, c)).awake()
+        ref = S.reference(casts, a, b, c, *library_boxes(d))
+        assert ref.ties.tolist() == [2, 0, 2] and ref.records["tri"].tolist() == [0, 0, 0] and ref.records["t"].tolist()[::2] == [4.0, 4.0]
+        q = Casts(ctx, d, casts)
+        got, flags = q.cast(), q.any()
+        q.dispose()
+        assert_records(got, ref, "shared edge")
+        assert flags.tolist() == [1, 0, 1]
+        d.on_destroy()
+
+
+@pytest.mark.gpu
+def test_order_independence_under_a_shuffle_of_the_triangles(ctx):
+    (a, b, c), casts, ref, d = parity_case(ctx, "cfg1_4096")
+    perm = np.random.default_rng(8).permutation(len(a))                          # new index j holds old triangle perm[j]
+    d2 = H().RaytracingMeshDrawer(ctx, pack(a[perm], b[perm], c[perm])).awake()
+    q = Casts(ctx, d2, casts)
+    got, flags = q.cast(), q.any()
+    q.dispose()
+    d2.on_destroy()
+    assert (words(got["t"]) == words(ref.records["t"])).all() and (flags == ref.flags).all()
+    unique = (ref.flags == 1) & (ref.ties == 1)
+    assert unique.sum() > 300 and (perm[got["tri"][unique]] == ref.records["tri"][unique]).all()
+    for k in ("u", "v"):                                                         # the same triangle, the same contact point
+        assert (words(got[k][unique]) == words(ref.records[k][unique])).all()
+
+
+@pytest.mark.gpu
+def test_a_hit_at_time_zero_exists_exactly_for_an_accepted_start_overlap(ctx):
+    (a, b, c), casts, ref, d = parity_case(ctx, "viking_room")
+    q = Casts(ctx, d, casts)
+    got = q.cast()
+    q.dispose()
+    lo, hi = library_boxes(d)
+    act = np.nonzero(S.active(casts))[0]
+    sub = casts[act]
+    d0, _, _ = P.point_triangle(sub["origin"][:, None, :], a[None], (b - a)[None], (c - a)[None])
+    passes, entry = S.grown_entry(sub, lo, hi)
+    with np.errstate(invalid="ignore"):
+        overlap = ((d0 <= (sub["radius"] * sub["radius"])[:, None]) & passes & ~(F(0) < entry)).any(axis=1)
+    zero = (got["t"][act] == 0) & (words(got["t"][act]) != words(np.array([S.MISS["t"]])))
+    assert overlap.sum() > 30 and (zero == overlap).all()
+
+
+@pytest.mark.gpu
+def test_statistics_count_the_active_casts(ctx):
+    _, casts, ref, d = parity_case(ctx, "viking_room")
+    q = Casts(ctx, d, casts)
+    stats = H().DataBuffer(ctx, 1, L().RAY_STATS)
+    per = {}
+    try:
+        for name, call in (("cast", q.cast), ("any", q.any)):
+            stats.fill_u32(0)
+            N().check(ctx.handle, N().lib.lbvh_ray_stats_target(ctx.handle, stats.device))
+            got = call()
+            N().check(ctx.handle, N().lib.lbvh_ray_stats_target(ctx.handle, None))
+            s = stats.get_data()[0]
+            per[name] = (int(s["rays"]), int(s["node_fetches"]), int(s["triangle_tests"]))
+            assert (words(got) == words(ref.records if name == "cast" else ref.flags)).all()          # the counting kernels: same answers
+    finally:
+        N().check(ctx.handle, N().lib.lbvh_ray_stats_target(ctx.handle, None))
+    print("casts, node lines, triangle tests:", per)
+    n_active = int(S.active(casts).sum())
+    assert per["cast"][0] == n_active and per["any"][0] == n_active
+    assert per["any"][1] <= per["cast"][1] and per["any"][2] <= per["cast"][2] and per["cast"][1] >= n_active
+    stats.dispose()
+    q.dispose()
+
+
+@pytest.mark.gpu
+def test_errors_the_stale_scene_and_the_stack_limit(ctx):
+    tris = scenes.tiled_torus(nu=16, nv=10, grid=2)
+    a, b, c = positions(tris)
+    c2 = H().Context(0)                               # a context of its own: its ray scratch has never grown
+    try:
+        d = H().RaytracingMeshDrawer(c2, tris).awake()
+        casts = aimed_casts(a, b, c, 600, np.random.default_rng(2))
+        ref = S.reference(casts, a, b, c, *library_boxes(d))
+        assert 100 < ref.flags.sum() < 600
+        q = Casts(c2, d, casts)
+        lib, h, s = N().lib, c2.handle, d.container.scene()
+        n = len(casts)
+        p = lambda buf, k: C.c_void_p(buf.device.value + k)
+
+        def untouched():
+            return (words(q.hits.get_data()) == 0x7FC00000).all() and (q.flags.get_data() == 0xDEADBEEF).all()
+
+        # a failed growth of the ray scratch: out of memory, nothing written; the next call on the context succeeds
+        c2.debug_switch(N().DEBUG_SWITCH_FAIL_RESERVE, 1)
+        q.hits.fill_u32(0x7FC00000)
+        q.flags.fill_u32(0xDEADBEEF)
+        assert lib.lbvh_sphere_cast(h, q.casts.device, n, C.byref(s), q.hits.device) == -2
+        assert untouched()
+        assert_records(q.cast(), ref, "after the failed reservation")
+        q.hits.fill_u32(0x7FC00000)
+        q.flags.fill_u32(0xDEADBEEF)
+        for fn, out, off in ((lib.lbvh_sphere_cast, q.hits, 8), (lib.lbvh_sphere_cast_any, q.flags, 2)):
+            assert fn(h, None, n, C.byref(s), out.device) == -1
+            assert fn(h, q.casts.device, n, None, out.device) == -1
+            assert fn(h, q.casts.device, n, C.byref(s), None) == -1
+            assert fn(h, p(q.casts, 4), 10, C.byref(s), out.device) == -1
+            assert fn(h, q.casts.device, 10, C.byref(s), p(out, off)) == -1
+            assert fn(h, q.casts.device, 1 << 32, C.byref(s), out.device) == -1
+            assert fn(None, q.casts.device, 10, C.byref(s), out.device) == -1
+            assert fn(h, q.casts.device, 0, C.byref(s), out.device) == 0              # count == 0: a no-op
+        assert untouched()
+        # aligned sub-ranges are accepted: casts 1 .. 10 into records from record 1
+        assert lib.lbvh_sphere_cast(h, p(q.casts, 32), 10, C.byref(s), p(q.hits, 16)) == 0
+        assert (words(q.hits.get_data()[1:11]) == words(ref.records[1:11])).all()
+        # a stale scene: triangles uploaded without a rebuild
+        d.container.triangle_data.sync()
+        q.hits.fill_u32(0x7FC00000)
+        q.flags.fill_u32(0xDEADBEEF)
+        assert lib.lbvh_sphere_cast(h, q.casts.device, n, C.byref(s), q.hits.device) == -1
+        assert b"stale" in lib.lbvh_last_error(h)
+        assert lib.lbvh_sphere_cast_any(h, q.casts.device, n, C.byref(s), q.flags.device) == -1
+        assert untouched()
+        d.rebuild(fast=True)
+        # the stack limit: a reported error (LBVH_ERR_HIP at the next sync), never a silently wrong record
+        N().check(h, lib.lbvh_debug_ray_stack_split(h, 1))
+        N().check(h, lib.lbvh_debug_ray_stack_limit(h, 1))
+        q.drawer.sphere_cast(q.casts, q.hits)
+        assert lib.lbvh_sync(h) == -3
+        assert b"stack" in lib.lbvh_last_error(h)
+        N().check(h, lib.lbvh_debug_ray_stack_limit(h, 0))
+        N().check(h, lib.lbvh_debug_ray_stack_split(h, 16))
+        assert_records(q.cast(), ref, "after the stack limit")
+        q.dispose()
+    finally:
+        c2.close()
+
+
+@pytest.mark.gpu
+def test_path_tracer_frame_undisturbed_by_a_cast_between_bounces(ctx):
+    """the casts drop the live-path list: the next lbvh_path_bounce scans again and the frame is the one without them"""
+    tris, body, centres = scenes.tiled_torus(nu=24, nv=16, grid=2, with_bodies=True)
+    pt = H().DynamicPathTracer(ctx, tris, body, centres, t_min=1e-3, albedo=0.7, seed=5)
+    pt.animate(0.05)
+    cam_d = scenes.camera(160, 96, (0.0, 0.0, 110.0))
+    pt.render(cam_d, bounces=4)
+    img0 = pt.image()
+    st0 = pt.states.get_data()[: 160 * 96].copy()
+    a, b, c = positions(tris)
+    big = aimed_casts(a, b, c, 4 * 160 * 96, np.random.default_rng(12), radii=(0.005,))      # 4x the frame: the scratch grows in mid-frame
+    q = Casts(ctx, pt.drawer, big)
+    cam = N().Camera.from_dict(cam_d)
+    count = 160 * 96
+    h, s = ctx.handle, pt.drawer.container.scene()
+    lib = N().lib
+
+    def cast():
+        pt.drawer.sphere_cast(q.casts, q.hits)
+        pt.drawer.sphere_cast_any(q.casts, q.flags)
+
+    N().check(h, lib.lbvh_trace_primary(h, C.byref(cam), 0, 0, 160, 96, C.byref(s), L().TRACE_FAST, pt.hits.device, None))
+    cast()
+    N().check(h, lib.lbvh_path_first_bounce(h, C.byref(cam), C.byref(s), pt.states.device, pt.hits.device, 5, 0.7, 1e-3))
+    for bnc in range(1, 4):
+        cast()
+        N().check(h, lib.lbvh_path_bounce(h, C.byref(s), pt.states.device, pt.hits.device, count, bnc, 5, 0.7, 1e-3))
+    cast()
+    N().check(h, lib.lbvh_path_scatter(h, C.byref(s), pt.hits.device, count, 4, 5, 0.7, pt.states.device))
+    N().check(h, lib.lbvh_path_resolve(h, pt.states.device, count, pt.image_buf.device))
+    img1 = pt.image()
+    st1 = pt.states.get_data()[:count]
+    assert (words(st1) == words(st0)).all()
+    assert (img1.view(np.uint16) == img0.view(np.uint16)).all()
+    f = q.flags.get_data()[: q.n]
+    assert 0 < f.sum() < q.n and ((q.hits.get_data()[: q.n]["t"] < S.MAX_FLOAT) == (f == 1)).all()
+    q.dispose()
+    pt.drawer.on_destroy()
+
+
+def _splitmix():
+    mask = (1 << 64) - 1
+    state = 0
+
+    def seed(s):
+        nonlocal state
+        state = s
+
+    def nxt():
+        nonlocal state
+        state = (state + 0x9E3779B97F4A7C15) & mask
+        z = state
+        z = ((z ^ (z >> 30)) * 0xBF58476D1CE4E5B9) & mask
+        z = ((z ^ (z >> 27)) * 0x94D049BB133111EB) & mask
+        return z ^ (z >> 31)
+
+    def uni(lo, hi):
+        return F(lo) + F(F(hi) - F(lo)) * F((nxt() >> 40) * (1.0 / 16777216.0))
+    return seed, uni
+
+
+def _driver_mesh(n):
+    """the mesh lbvh_driver.cpp generates for a number (SplitMix64, seed 1)"""
+    seed, uni = _splitmix()
+    seed(1)
+    pos = np.zeros((n, 3, 3), dtype=F)
+    for i in range(n):
+        for j in range(3):
+            ctr = uni(-100.0, 100.0)
+            pos[i, 0, j] = ctr
+            pos[i, 1, j] = F(ctr + uni(-2.0, 2.0))
+            pos[i, 2, j] = F(ctr + uni(-2.0, 2.0))
+    tris = np.zeros(n, dtype=L().TRIANGLE)
+    tris["a"], tris["b"], tris["c"] = pos[:, 0], pos[:, 1], pos[:, 2]
+    return tris
+
+
+def _driver_casts(tris, count, radius):
+    """the casts `lbvh_driver sweep` makes from the mesh's box (SplitMix64, seed 3: origin and target drawn axis by axis; t_max 2);
+    radius None: the driver's default, 1 % of the largest extent in fp32"""
+    pos = np.stack([tris[k][:, :3] for k in "abc"]).astype(F)
+    lo, hi = pos.min(axis=(0, 1)), pos.max(axis=(0, 1))
+    if radius is None:
+        radius = F(0.01) * F(max(F(hi[j] - lo[j]) for j in range(3)))
+    seed, uni = _splitmix()
+    seed(3)
+    origin = np.zeros((count, 3), dtype=F)
+    direction = np.zeros((count, 3), dtype=F)
+    for i in range(count):
+        for j in range(3):
+            grow = F(0.25) * F(hi[j] - lo[j])
+            origin[i, j] = uni(F(lo[j] - grow), F(hi[j] + grow))
+            direction[i, j] = F(uni(lo[j], hi[j]) - origin[i, j])
+    return make_casts(origin, direction, F(radius), F(2.0))
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("mesh, radius", [("viking_room", None), ("viking_room", 0.05), ("random", 1.5)])
+def test_cpp_host_driver_sweep_matches_the_python_host(ctx, tmp_path, mesh, radius):
+    """`lbvh_driver sweep` on the golden viking_room mesh (its OBJ through the C++ ingest; default and given radius) and on the
+    driver's own random mesh, against the Python host on the same triangles and the same casts"""
+    exe = os.path.join(ROOT, "unitysimpleraytracing_amd", "host", "lbvh_driver")
+    assert os.path.exists(exe), "build it with __graft_entry__.build()"
+    count = 8000
+    if mesh == "viking_room":
+        import lzma
+        what = str(tmp_path / "viking_room.obj")
+        with open(os.path.join(ROOT, "tests", "golden", "reference_obj", "viking_room.obj.xz"), "rb") as fh:
+            open(what, "wb").write(lzma.decompress(fh.read()))
+        tris = scenes.load_obj(what)
+        assert tris.tobytes() == np.ascontiguousarray(golden("viking_room"), dtype=L().TRIANGLE).tobytes()      # the golden scene
+    else:
+        what = "4096"
+        tris = _driver_mesh(4096)
+    args = [exe, "sweep", what, str(count)] + ([str(radius)] if radius is not None else [])
+    res = json.loads(subprocess.run(args, check=True, capture_output=True, text=True).stdout)
+    casts = _driver_casts(tris, count, radius)
+    d = H().RaytracingMeshDrawer(ctx, tris).awake()
+    q = Casts(ctx, d, casts)
+    got, flags = q.cast(), q.any()
+    q.dispose()
+    d.on_destroy()
+    assert res["triangles"] == len(tris) and res["casts"] == count and F(res["radius"]) == casts["radius"][0]
+    assert res["touching"] == int((got["t"] < S.MAX_FLOAT).sum()) == res["flagged"] == int(flags.sum())
+    assert res["at_start"] == int((got["t"] == 0).sum())
+    assert res["word_sum"] == int(words(got).astype(np.uint64).sum())
+    assert [r[1] for r in res["records"]] == got["tri"][:3].tolist()
+    assert [words(np.array(r[0], dtype=F))[0] for r in res["records"]] == words(got["t"][:3]).tolist()
+    assert 0 < res["touching"] < count

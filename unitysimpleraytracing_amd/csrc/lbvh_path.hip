@@ -865,6 +865,213 @@ __global__ __launch_bounds__(64) void point_query_wide_kernel(const lbvh_point_q
     if (STATS) add_ray_stats(stats, n_queries, n_steps, n_tris);
 }
 
+// ---- sphere casts: first contact of a moving sphere (include/lbvh.h, lbvh_sphere_cast) ---------------------------------
+// The time at which the sphere of radius r whose centre moves along the ray touches the triangle {a, e1, e2} of a derived-scene
+// line, +inf if it never does: the features of lbvh.h in its order (start overlap, face, three edges, three vertices), a later
+// one taken only when strictly less, every operation the header's.  m = origin - P, dot(m, d) and dot(m, m) are formed once per
+// vertex and serve its edge and its vertex sphere; a11 / a12 / a22 are point_triangle2's (the same expressions: the compiler
+// forms them once); each quadratic divides once.
+__device__ __forceinline__ float sphere_triangle_time(const ray_t& c, float r, const float4 a, const float4 e1, const float4 e2)
+{
+    const float inf = __builtin_inff();
+    const float R2 = r * r, dd = dot3(c.dx, c.dy, c.dz, c.dx, c.dy, c.dz);
+    float u0, v0;
+    if (point_triangle2(c.ox, c.oy, c.oz, a, e1, e2, u0, v0) <= R2) return 0.0f;
+    float t = inf;
+    auto take = [&](bool valid, float cand) { if (valid && cand >= 0.0f && cand < t) t = cand; };
+    const float a11 = dot3(e1.x, e1.y, e1.z, e1.x, e1.y, e1.z), a12 = dot3(e1.x, e1.y, e1.z, e2.x, e2.y, e2.z);
+    const float a22 = dot3(e2.x, e2.y, e2.z, e2.x, e2.y, e2.z);
+    const float max_ = c.ox - a.x, may = c.oy - a.y, maz = c.oz - a.z;
+    {   // face
+        const float nx = e1.y * e2.z - e1.z * e2.y, ny = e1.z * e2.x - e1.x * e2.z, nz = e1.x * e2.y - e1.y * e2.x;
+        const float h = r * sqrtf(dot3(nx, ny, nz, nx, ny, nz));
+        float s = dot3(max_, may, maz, nx, ny, nz), dn = dot3(c.dx, c.dy, c.dz, nx, ny, nz);
+        const float sg = s >= 0.0f ? 1.0f : -1.0f;
+        s = s * sg;
+        dn = dn * sg;
+        const float tf = (h - s) / dn;
+        const float qx = (c.ox + c.dx * tf) - a.x, qy = (c.oy + c.dy * tf) - a.y, qz = (c.oz + c.dz * tf) - a.z;
+        const float d1 = dot3(e1.x, e1.y, e1.z, qx, qy, qz), d2 = dot3(e2.x, e2.y, e2.z, qx, qy, qz);
+        const float det = a11 * a22 - a12 * a12;
+        const float u = (a22 * d1 - a12 * d2) / det, v = (a11 * d2 - a12 * d1) / det;
+        take(s > h && dn < 0.0f && u >= 0.0f && v >= 0.0f && u + v <= 1.0f, tf);
+    }
+    const float bx = a.x + e1.x, by = a.y + e1.y, bz = a.z + e1.z;
+    const float cx = a.x + e2.x, cy = a.y + e2.y, cz = a.z + e2.z;
+    const float e3x = e2.x - e1.x, e3y = e2.y - e1.y, e3z = e2.z - e1.z;
+    const float mbx = c.ox - bx, mby = c.oy - by, mbz = c.oz - bz;
+    const float mcx = c.ox - cx, mcy = c.oy - cy, mcz = c.oz - cz;
+    const float mda = dot3(max_, may, maz, c.dx, c.dy, c.dz), mma = dot3(max_, may, maz, max_, may, maz);
+    const float mdb = dot3(mbx, mby, mbz, c.dx, c.dy, c.dz), mmb = dot3(mbx, mby, mbz, mbx, mby, mbz);
+    const float mdc = dot3(mcx, mcy, mcz, c.dx, c.dy, c.dz), mmc = dot3(mcx, mcy, mcz, mcx, mcy, mcz);
+    auto edge = [&](float mx, float my, float mz, float md, float mm, float ex, float ey, float ez, float ee) {
+        const float me = dot3(mx, my, mz, ex, ey, ez), de = dot3(c.dx, c.dy, c.dz, ex, ey, ez);
+        const float A = ee * dd - de * de;
+        const float B = ee * md - de * me;
+        const float Cq = ee * (mm - R2) - me * me;
+        const float disc = B * B - A * Cq;
+        const float te = (-B - sqrtf(disc)) / A;
+        const float se = me + te * de;
+        take(A > 0.0f && disc >= 0.0f && 0.0f <= se && se <= ee, te);
+    };
+    edge(max_, may, maz, mda, mma, e1.x, e1.y, e1.z, a11);
+    edge(max_, may, maz, mda, mma, e2.x, e2.y, e2.z, a22);
+    edge(mbx, mby, mbz, mdb, mmb, e3x, e3y, e3z, dot3(e3x, e3y, e3z, e3x, e3y, e3z));
+    auto vertex = [&](float B, float mm) {
+        const float Cq = mm - R2;
+        const float disc = B * B - dd * Cq;
+        take(disc >= 0.0f, (-B - sqrtf(disc)) / dd);
+    };
+    vertex(mda, mma);
+    vertex(mdb, mmb);
+    vertex(mdc, mmc);
+    return t;
+}
+
+// cast k into the lane (best_t = T): false (miss record / 0 written, lane stays idle) for an inactive cast
+template <bool ANY>
+__device__ __forceinline__ bool load_sphere_cast(const lbvh_sphere_ray* __restrict__ casts, uint32_t k, ray_t& ray, float& r, float& best_t,
+                                                 std::conditional_t<ANY, uint32_t, lbvh_hit>* __restrict__ out)
+{
+    const float inf = __builtin_inff();
+    const float4* q = reinterpret_cast<const float4*>(&casts[k]);
+    const float4 o = q[0], d = q[1];
+    ray.ox = o.x; ray.oy = o.y; ray.oz = o.z;
+    ray.dx = d.x; ray.dy = d.y; ray.dz = d.z;
+    ray.ix = 1.0f / d.x; ray.iy = 1.0f / d.y; ray.iz = 1.0f / d.z;
+    r = o.w;
+    best_t = fminf(d.w, LBVH_MAX_FLOAT);                 // T: candidates have t < T
+    if (o.w > 0.0f && o.w < inf && d.w > 0.0f && (o.x == o.x && o.y == o.y && o.z == o.z) &&
+        fabsf(d.x) < inf && fabsf(d.y) < inf && fabsf(d.z) < inf && dot3(d.x, d.y, d.z, d.x, d.y, d.z) > 0.0f) return true;
+    if constexpr (ANY) out[k] = 0u;
+    else reinterpret_cast<float4*>(out)[k] = make_float4(LBVH_MAX_FLOAT, __uint_as_float(0u), 0.0f, 0.0f);
+    return false;
+}
+
+// One cast per lane over the four-wide nodes, in the frame of trace_rays_wide_kernel<PLAIN> (persistent waves, lanes refilled from
+// the wave's run of consecutive casts, LDS + device-memory stack, leaf slots first, inner slots entered nearest entry first).  The
+// four slot boxes are grown by the lane's radius (lo - r, hi + r: monotone, so a grown box contains the grown boxes of everything
+// below it) before the slab test; a slot is skipped when the ray misses its grown box or enters it beyond best_t, strictly, never
+// on its exit distance.  A candidate is a triangle with a time t < T that is not in front of its own grown box (hit_counts), so
+// the record does not depend on the order of the walk.  u and v are point_triangle2's at c(t), formed when a candidate is taken.
+// ANY: a flag, the walk cut off at its first candidate (best_t stays T).
+template <bool ANY, bool STATS>
+__global__ __launch_bounds__(64) void sphere_cast_wide_kernel(const lbvh_sphere_ray* __restrict__ casts, uint32_t total,
+                                                              const lbvh_wide_node* __restrict__ wide,
+                                                              const lbvh_fast_node* __restrict__ lines,
+                                                              std::conditional_t<ANY, uint32_t, lbvh_hit>* __restrict__ out,
+                                                              uint32_t* __restrict__ deep,     // [gridDim.x][kWideStackDeep][64]
+                                                              uint32_t lds_depth,              // <= kWideStackLds
+                                                              uint32_t deep_cap,               // <= kWideStackDeep
+                                                              uint32_t* __restrict__ fault, lbvh_ray_stats* stats)
+{
+    __shared__ uint32_t s_stack[kWideStackLds][LBVH_WAVE];
+    uint32_t* my_deep = deep + (size_t)blockIdx.x * (kWideStackDeep * LBVH_WAVE) + threadIdx.x;
+    const uint32_t lane = threadIdx.x;
+    const uint32_t run = max((total + gridDim.x - 1) / gridDim.x, 32u);
+    uint32_t next = blockIdx.x * run;
+    if (next >= total) return;
+    const uint32_t end = min(next + run, total);
+    uint32_t n_casts = 0, n_steps = 0, n_tris = 0;
+
+    bool active = false, took = false;
+    uint32_t i = 0;
+    ray_t ray = {};
+    float r = 0.0f;
+    float best_t = LBVH_MAX_FLOAT, best_u = 0.0f, best_v = 0.0f;
+    uint32_t best_tri = 0, sp = 0, node = 0;
+    auto push = [&](uint32_t ref) {
+        if (sp < lds_depth) { s_stack[sp][lane] = ref; sp++; }
+        else if (sp < lds_depth + deep_cap) { my_deep[(sp - lds_depth) * LBVH_WAVE] = ref; sp++; }
+        // a dropped entry would be a silently wrong record: report it, as the ray walkers do (lbvh_debug_ray_stack_limit provokes it)
+        else __hip_atomic_store(fault, LBVH_FAULT_RAY_STACK, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    };
+    for (;;) {
+        const uint64_t idle = __ballot(!active);
+        if (idle != 0 && next < end) {
+            if (!active) {
+                const uint32_t k = next + mbcnt64(idle);
+                if (k < end) {
+                    i = k;
+                    active = load_sphere_cast<ANY>(casts, k, ray, r, best_t, out);
+                    best_tri = 0; best_u = 0.0f; best_v = 0.0f; took = false;
+                    sp = 0; node = 0;
+                    if (STATS && active) n_casts++;
+                }
+            }
+            next += (uint32_t)__popcll(idle);
+        }
+        if (!__any(active) && next >= end) break;
+        if (active) {
+            if (STATS) n_steps++;
+            const float4* w = reinterpret_cast<const float4*>(&wide[node]);
+            const float4 lox = w[0], loy = w[1], loz = w[2], hix = w[3], hiy = w[4], hiz = w[5];
+            const uint4 ref = reinterpret_cast<const uint4*>(w)[6];
+            float t0, t1, t2, t3;
+            const bool h0 = wide_box(lox.x - r, loy.x - r, loz.x - r, hix.x + r, hiy.x + r, hiz.x + r, ray, t0) && !(t0 > best_t) && ref.x != kWideEmpty;
+            const bool h1 = wide_box(lox.y - r, loy.y - r, loz.y - r, hix.y + r, hiy.y + r, hiz.y + r, ray, t1) && !(t1 > best_t) && ref.y != kWideEmpty;
+            const bool h2 = wide_box(lox.z - r, loy.z - r, loz.z - r, hix.z + r, hiy.z + r, hiz.z + r, ray, t2) && !(t2 > best_t) && ref.z != kWideEmpty;
+            const bool h3 = wide_box(lox.w - r, loy.w - r, loz.w - r, hix.w + r, hiy.w + r, hiz.w + r, ray, t3) && !(t3 > best_t) && ref.w != kWideEmpty;
+            // leaf slots first: a lane's leaves one after the other, every lane's k-th at the same time
+            uint32_t leaves = (h0 && (ref.x >> 31) ? 1u : 0u) | (h1 && (ref.y >> 31) ? 2u : 0u) | (h2 && (ref.z >> 31) ? 4u : 0u) |
+                              (h3 && (ref.w >> 31) ? 8u : 0u);
+            bool found = false;                          // ANY: a candidate was accepted
+            while (leaves != 0u) {
+                const uint32_t k = (uint32_t)__builtin_ctz(leaves);
+                leaves &= leaves - 1u;
+                if (STATS) n_tris++;
+                float4 v0, v1, v2;
+                unpack_fast_triangle(reinterpret_cast<const float4*>(&lines[pick4(ref, k) & 0x7FFFFFFFu]), v0, v1, v2);
+                const float t = sphere_triangle_time(ray, r, v0, v1, v2);
+                const uint32_t tri = __float_as_uint(v0.w);
+                const float entry = k == 0u ? t0 : (k == 1u ? t1 : (k == 2u ? t2 : t3));
+                // best_t starts at T and best_tri at 0: t == T is never taken.  Ties go to the lower triangle index.
+                if (hit_counts(t, entry) && (t < best_t || (t == best_t && tri < best_tri))) {
+                    if constexpr (ANY) { found = true; break; }
+                    else {
+                        best_t = t; best_tri = tri; took = true;
+                        point_triangle2(ray.ox + ray.dx * t, ray.oy + ray.dy * t, ray.oz + ray.dz * t, v0, v1, v2, best_u, best_v);
+                    }
+                }
+            }
+            if (ANY && found) {
+                if constexpr (ANY) out[i] = 1u;
+                active = false;
+                continue;
+            }
+            // nodes to enter, ordered by entry distance: the order key is the distance's bit pattern (non-negative floats
+            // order like integers) with the slot number in its two lowest bits
+            constexpr uint32_t none = 0xFFFFFFFFu;
+            uint32_t k0 = h0 && !(ref.x >> 31) && !(t0 > best_t) ? ((__float_as_uint(fmaxf(t0, 0.0f)) & ~3u) | 0u) : none;
+            uint32_t k1 = h1 && !(ref.y >> 31) && !(t1 > best_t) ? ((__float_as_uint(fmaxf(t1, 0.0f)) & ~3u) | 1u) : none;
+            uint32_t k2 = h2 && !(ref.z >> 31) && !(t2 > best_t) ? ((__float_as_uint(fmaxf(t2, 0.0f)) & ~3u) | 2u) : none;
+            uint32_t k3 = h3 && !(ref.w >> 31) && !(t3 > best_t) ? ((__float_as_uint(fmaxf(t3, 0.0f)) & ~3u) | 3u) : none;
+            {   // five compare-exchanges
+                uint32_t a, b;
+                a = min(k0, k1); b = max(k0, k1); k0 = a; k1 = b;
+                a = min(k2, k3); b = max(k2, k3); k2 = a; k3 = b;
+                a = min(k0, k2); b = max(k0, k2); k0 = a; k2 = b;
+                a = min(k1, k3); b = max(k1, k3); k1 = a; k3 = b;
+                a = min(k1, k2); b = max(k1, k2); k1 = a; k2 = b;
+            }
+            if (k0 != none) {
+                if (k3 != none) push(pick4(ref, k3 & 3u));       // farthest first: the nearest waiting sibling is popped first
+                if (k2 != none) push(pick4(ref, k2 & 3u));
+                if (k1 != none) push(pick4(ref, k1 & 3u));
+                node = pick4(ref, k0 & 3u);
+            } else if (sp != 0) {
+                sp--;
+                node = sp < lds_depth ? s_stack[sp][lane] : my_deep[(sp - lds_depth) * LBVH_WAVE];
+            } else {
+                if constexpr (ANY) out[i] = 0u;
+                else put_hit<true>(out, i, best_t, took, best_tri, best_u, best_v);
+                active = false;
+            }
+        }
+    }
+    if (STATS) add_ray_stats(stats, n_casts, n_steps, n_tris);
+}
+
 // lbvh_k_closest_points: the walk of point_query_wide_kernel<false> with "best so far" replaced by "k-th best so far".  Each lane
 // keeps the k best candidates met so far, sorted by (dist2, tri), in LDS: three arrays [slot][lane] of dist2, triangle index and
 // the index of the triangle's line in the derived scene — 12 bytes per slot, `cap` slots per lane, sized at the launch from k
@@ -1809,6 +2016,37 @@ static lbvh_status point_queries(lbvh_context* ctx, const lbvh_point_query* d_qu
     return LBVH_OK;
 }
 
+// lbvh_sphere_cast / lbvh_sphere_cast_any: always the four-wide walk (lbvh_debug_ray_walker does not apply), one launch
+template <bool ANY>
+static lbvh_status sphere_casts(lbvh_context* ctx, const lbvh_sphere_ray* d_casts, size_t count, const lbvh_scene* h_scene,
+                                std::conditional_t<ANY, uint32_t, lbvh_hit>* d_out, const char* who)
+{
+    if (!ctx) return LBVH_ERR_INVALID_ARG;
+    if (count == 0) return LBVH_OK;
+    LBVH_REQUIRE(ctx, d_casts != nullptr && h_scene != nullptr && d_out != nullptr);
+    LBVH_REQUIRE(ctx, ((uintptr_t)d_casts & 15) == 0 && ((uintptr_t)d_out & (ANY ? 3 : 15)) == 0);
+    LBVH_REQUIRE(ctx, count <= 0xFFFFFFFFull);
+    {
+        const int frc = lbvh_require_fast(ctx, *h_scene, who);
+        if (frc != LBVH_OK) return frc;
+    }
+    LBVH_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    // the deep stack slabs of the ray scratch, laid out as for lbvh_trace_rays (whose live-path list they may overwrite)
+    int rc = lbvh_reserve(ctx, &ctx->ray_scratch, &ctx->ray_scratch_bytes, ray_scratch_bytes_for(count));
+    if (rc != LBVH_OK) return rc;
+    ctx->ray_list.valid = false;
+    rc = ensure_wide_nodes(ctx);
+    if (rc != LBVH_OK) return rc;
+    const uint32_t lds = std::min<uint32_t>(ctx->ray_stack_lds, kWideStackLds), deep_cap = std::min<uint32_t>(ctx->ray_stack_deep, kWideStackDeep);
+    const lbvh_wide_node* wn = (const lbvh_wide_node*)ctx->wide_nodes;
+    if (ctx->ray_stats) LBVH_LAUNCH(ctx, (sphere_cast_wide_kernel<ANY, true>), dim3(ray_waves_of(count)), dim3(LBVH_WAVE), d_casts, (uint32_t)count, wn,
+                                    ctx->fast_nodes, d_out, deep_stacks(ctx, count), lds, deep_cap, ctx->fault_dev, ctx->ray_stats);
+    else LBVH_LAUNCH(ctx, (sphere_cast_wide_kernel<ANY, false>), dim3(ray_waves_of(count)), dim3(LBVH_WAVE), d_casts, (uint32_t)count, wn,
+                     ctx->fast_nodes, d_out, deep_stacks(ctx, count), lds, deep_cap, ctx->fault_dev, ctx->ray_stats);
+    LBVH_HIP_TRY(ctx, hipGetLastError());
+    return LBVH_OK;
+}
+
 // lbvh_k_closest_points: the four-wide walk only, one launch; the per-lane lists are dynamic LDS sized from k
 static lbvh_status k_closest_points(lbvh_context* ctx, const lbvh_point_query* d_queries, size_t count, uint32_t k, const lbvh_scene* h_scene,
                                     lbvh_closest_point* d_out, uint32_t* d_found)
@@ -1969,6 +2207,16 @@ lbvh_status lbvh_trace_k_closest(lbvh_context* ctx, const lbvh_ray* d_rays, size
                                  lbvh_hit* d_hits, uint32_t* d_found)
 {
     return trace_k_closest(ctx, d_rays, count, k, h_scene, d_hits, d_found);
+}
+
+lbvh_status lbvh_sphere_cast(lbvh_context* ctx, const lbvh_sphere_ray* d_casts, size_t count, const lbvh_scene* h_scene, lbvh_hit* d_hits)
+{
+    return sphere_casts<false>(ctx, d_casts, count, h_scene, d_hits, "lbvh_sphere_cast");
+}
+
+lbvh_status lbvh_sphere_cast_any(lbvh_context* ctx, const lbvh_sphere_ray* d_casts, size_t count, const lbvh_scene* h_scene, uint32_t* d_flags)
+{
+    return sphere_casts<true>(ctx, d_casts, count, h_scene, d_flags, "lbvh_sphere_cast_any");
 }
 
 lbvh_status lbvh_point_crossings(lbvh_context* ctx, const lbvh_point_query* d_points, size_t count, const float* h_dirs, uint32_t n_dirs,

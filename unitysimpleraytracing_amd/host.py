@@ -379,6 +379,23 @@ class RaytracingMeshDrawer:
         s = self.container.scene()
         N.check(self.ctx.handle, fn(self.ctx.handle, rays.device, rays.size, C.byref(s), out.device))
 
+    def sphere_cast(self, casts, hits):
+        """First contact of each moving sphere of the DataBuffer `casts` (layouts.SPHERE_RAY: origin, radius, dir, t_max) with the
+        mesh into the DataBuffer `hits` (layouts.HIT: t, tri, and the barycentrics u, v of the contact point), over the derived
+        scene.  The centre is at origin + dir * t; no contact in [0, t_max): the miss record.  Asynchronous; read with
+        hits.get_data()."""
+        self._sphere_casts(N.lib.lbvh_sphere_cast, casts, hits, L.HIT)
+
+    def sphere_cast_any(self, casts, flags):
+        """1 into the uint32 DataBuffer `flags` for each sphere of `casts` that touches anything on its way, else 0."""
+        self._sphere_casts(N.lib.lbvh_sphere_cast_any, casts, flags, np.dtype(np.uint32))
+
+    def _sphere_casts(self, fn, casts, out, dtype):
+        if casts.dtype != L.SPHERE_RAY or out.dtype != dtype or out.size < casts.size:
+            raise ValueError(f"casts must be a DataBuffer of layouts.SPHERE_RAY and the output one of {dtype} with at least as many entries")
+        s = self.container.scene()
+        N.check(self.ctx.handle, fn(self.ctx.handle, casts.device, casts.size, C.byref(s), out.device))
+
     def closest_points(self, queries, out):
         """Nearest triangle of each point of the DataBuffer `queries` (layouts.POINT_QUERY: p, max_dist2) into the DataBuffer `out`
         (layouts.CLOSEST_POINT: dist2, tri, u, v), over the derived scene.  Asynchronous; read with out.get_data()."""

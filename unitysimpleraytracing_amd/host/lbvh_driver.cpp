@@ -27,6 +27,11 @@
 //                                                with k records per ray; prints the sum of the found counts, how many rows are
 //                                                full, the sum of all 32-bit words of the count * k records (mod 2^64) and the
 //                                                first rows
+//     lbvh_driver sweep [n | file.obj] [count] [radius]  the mesh of `points` and `count` spheres of the given radius (default 1 %
+//                                                of the largest extent) from points around the mesh's box towards points inside
+//                                                it (t = 1 at the target, t_max 2); SphereCast and SphereCastAny; prints how
+//                                                many casts touch, the sum of all 32-bit words of the records (mod 2^64) and the
+//                                                first records
 //     lbvh_driver crossings [n | file.obj] [count] the mesh and the points of `points`; PointCrossings along the three default
 //                                                directions ((1,1,1)/sqrt 3, (-1,2,3)/sqrt 14, (4,-1,2)/sqrt 21) and CountHits
 //                                                on the same rays written out ({p, 0, dir, +inf}); prints the sum of the counts,
@@ -450,6 +455,68 @@ static int khits_main(int argc, char** argv)
     return 0;
 }
 
+static int sweep_main(int argc, char** argv)
+{
+    const size_t count = argc > 3 ? (size_t)strtoull(argv[3], nullptr, 10) : 65536;
+    try {
+        const char* what = argc > 2 ? argv[2] : "4096";
+        const bool from_obj = std::strlen(what) > 4 && std::strcmp(what + std::strlen(what) - 4, ".obj") == 0;
+        const std::vector<lbvh_triangle> mesh = from_obj ? lbvh::MeshTriangles(lbvh::LoadObj(what)) : random_mesh((uint32_t)atoi(what));
+        float lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
+        for (const auto& t : mesh)
+            for (int a = 0; a < 3; a++) {
+                lo[a] = std::fmin(lo[a], std::fmin(t.a[a], std::fmin(t.b[a], t.c[a])));
+                hi[a] = std::fmax(hi[a], std::fmax(t.a[a], std::fmax(t.b[a], t.c[a])));
+            }
+        const float extent = std::fmax(hi[0] - lo[0], std::fmax(hi[1] - lo[1], hi[2] - lo[2]));
+        const float radius = argc > 4 ? (float)atof(argv[4]) : 0.01f * extent;
+        lbvh::Context ctx(0);
+        lbvh::RaytracingMeshDrawer drawer(ctx, mesh);
+        drawer.Awake();
+        lbvh::DataBuffer<lbvh_sphere_ray> casts(ctx, count);
+        uint64_t seed = 3;
+        for (auto& c : casts.LocalBuffer()) {
+            for (int a = 0; a < 3; a++) {
+                const float grow = 0.25f * (hi[a] - lo[a]);
+                c.origin[a] = uniform(seed, lo[a] - grow, hi[a] + grow);
+                c.dir[a] = uniform(seed, lo[a], hi[a]) - c.origin[a];
+            }
+            c.radius = radius;
+            c.t_max = 2.0f;
+        }
+        casts.Sync();
+        lbvh::DataBuffer<lbvh_hit> hits(ctx, count);
+        lbvh::DataBuffer<uint32_t> flags(ctx, count);
+        drawer.SphereCast(casts, hits);
+        drawer.SphereCastAny(casts, flags);
+        hits.GetData();
+        flags.GetData();
+        size_t touching = 0, flagged = 0, at_start = 0;
+        uint64_t word_sum = 0;
+        for (size_t i = 0; i < count; i++) {
+            const lbvh_hit& h = hits.LocalBuffer()[i];
+            uint32_t w[4];
+            std::memcpy(w, &h, sizeof w);
+            word_sum += (uint64_t)w[0] + w[1] + w[2] + w[3];
+            touching += h.t < LBVH_MAX_FLOAT;
+            at_start += h.t == 0.0f;
+            flagged += flags.LocalBuffer()[i];
+        }
+        std::printf("{\"triangles\": %zu, \"casts\": %zu, \"radius\": %.9g, \"touching\": %zu, \"flagged\": %zu, \"at_start\": %zu, "
+                    "\"word_sum\": %llu, \"records\": [",
+                    mesh.size(), count, radius, touching, flagged, at_start, (unsigned long long)word_sum);
+        for (size_t i = 0; i < std::min<size_t>(count, 3); i++) {
+            const lbvh_hit& h = hits.LocalBuffer()[i];
+            std::printf("%s[%.9g, %u, %.9g, %.9g]", i ? ", " : "", h.t, h.tri, h.u, h.v);
+        }
+        std::printf("]}\n");
+    } catch (const std::exception& e) {
+        std::fprintf(stderr, "%s\n", e.what());
+        return 1;
+    }
+    return 0;
+}
+
 // lbvh_driver overlaps [n | file.obj] [count] [size]: `count` boxes with centres in the mesh's box and half-extents up to `size` x its
 // extent, and the balls of the same centres with radius up to `size` x the largest extent; count -> one 8-byte read -> fill
 static int overlaps_main(int argc, char** argv)
@@ -585,6 +652,7 @@ int main(int argc, char** argv)
     if (argc > 1 && std::strcmp(argv[1], "points") == 0) return points_main(argc, argv);
     if (argc > 1 && std::strcmp(argv[1], "knn") == 0) return knn_main(argc, argv);
     if (argc > 1 && std::strcmp(argv[1], "khits") == 0) return khits_main(argc, argv);
+    if (argc > 1 && std::strcmp(argv[1], "sweep") == 0) return sweep_main(argc, argv);
     if (argc > 1 && std::strcmp(argv[1], "overlaps") == 0) return overlaps_main(argc, argv);
     if (argc > 1 && std::strcmp(argv[1], "rays") == 0) return rays_main(argc, argv);
     if (argc > 1 && std::strcmp(argv[1], "sort") == 0) return sort_main(argc, argv);

@@ -33,6 +33,9 @@ assert PATH_STATE.itemsize == 64
 # lbvh_trace_closest / lbvh_trace_occluded: a ray of the caller's own, active iff t_min < t_max
 RAY = np.dtype([("origin", "<f4", 3), ("t_min", "<f4"), ("dir", "<f4", 3), ("t_max", "<f4")])
 assert RAY.itemsize == 32
+# lbvh_sphere_cast / lbvh_sphere_cast_any: lbvh_ray with the sphere's radius where t_min is
+SPHERE_RAY = np.dtype([("origin", "<f4", 3), ("radius", "<f4"), ("dir", "<f4", 3), ("t_max", "<f4")])
+assert SPHERE_RAY.itemsize == 32
 # lbvh_closest_point_query / lbvh_within_distance: a point with its squared search radius (active iff max_dist2 > 0), and the answer
 POINT_QUERY = np.dtype([("p", "<f4", 3), ("max_dist2", "<f4")])
 CLOSEST_POINT = np.dtype([("dist2", "<f4"), ("tri", "<u4"), ("u", "<f4"), ("v", "<f4")])
