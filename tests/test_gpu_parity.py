@@ -377,7 +377,7 @@ def _wide_node_keys(shape, n):
 @pytest.mark.parametrize("n", [257, 65536, 200001])
 def test_build_tree_wide_nodes_bit_exact(ctx, shape, n):
     """Nodes whose searches leave the workgroup's LDS key window are searched by the whole wave with a 64-ary search
-    (wide_node_search, lbvh_build.hip): same ranges and splits as BVH.compute:35-92 on key sets built to put range
+    (wide_node_range / wide_node_split, lbvh_build.hip): same ranges and splits as BVH.compute:35-92 on key sets built to put range
     ends and splits on, just before and just after the window borders, in both search directions."""
     keys = _wide_node_keys(shape, n)
     cap = n + 3

@@ -3,7 +3,15 @@
 
     python tools/isa_resources.py <tree> [file.hip]     # <tree>: a checkout's root (default file: lbvh_path.hip)
 
-One line per kernel, demangled name first, so that two trees' listings can be compared line by line (profiles/ray_queries/)."""
+One line per kernel, demangled name first, so that two trees' listings can be compared line by line (profiles/ray_queries/).
+
+    python tools/isa_resources.py --compare <tree a> <tree b> <file.hip>
+
+The gate for a change that must leave the device code alone: both trees' file is compiled for the device only, with the
+flags of each tree's csrc/Makefile, and every kernel's instruction stream is compared as text — comments and directive lines dropped,
+local labels (.LBB...) folded to one token, so that moved or renumbered source does not show.  One line per kernel, `same` or
+`DIFFERENT`, `missing` for a kernel only <tree a> has and `extra` for one only <tree b> has; the exit status is 1 unless every line
+says `same`."""
 import os
 import re
 import subprocess
@@ -45,7 +53,48 @@ def resources(tree, src="lbvh_path.hip"):
     return {pretty[n]: r for n, r in kernels.items()}
 
 
+def makefile_flags(csrc):
+    m = re.search(r"^CXXFLAGS\s*\?=\s*(.+)$", open(os.path.join(csrc, "Makefile")).read(), re.M)
+    return m.group(1).split()
+
+
+def instruction_streams(tree, src):
+    """{mangled kernel name: its instructions, normalised, one per line}"""
+    csrc = os.path.join(os.path.abspath(tree), "unitysimpleraytracing_amd", "csrc")
+    with tempfile.TemporaryDirectory() as tmp:
+        out = os.path.join(tmp, "device.s")
+        subprocess.run(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950"] + makefile_flags(csrc) +
+                       ["--offload-device-only", "-S", os.path.join(csrc, src), "-o", out], cwd=tmp, capture_output=True, text=True, check=True)
+        asm = open(out).read()
+    streams = {}
+    for name in re.findall(r"^\s*\.amdhsa_kernel\s+(\S+)", asm, re.M):
+        body = asm[asm.index(f"\n{name}:") + 1:]
+        body = body[: body.index(".Lfunc_end")]
+        lines = []
+        for ln in body.splitlines()[1:]:
+            ln = re.sub(r"\.LBB\w+", ".LBB", ln.split(";")[0]).strip()
+            if ln and (ln == ".LBB:" or not ln.startswith(".")):
+                lines.append(" ".join(ln.split()))
+        streams[name] = "\n".join(lines)
+    return streams
+
+
+def compare(tree_a, tree_b, src):
+    a, b = instruction_streams(tree_a, src), instruction_streams(tree_b, src)
+    pretty = demangle(sorted(set(a) | set(b)))
+    bad = 0
+    for name in sorted(pretty, key=pretty.get):
+        verdict = "missing" if name not in b else "extra" if name not in a else "same" if a[name] == b[name] else "DIFFERENT"
+        bad += verdict != "same"
+        insts = sum(1 for ln in (a.get(name) or b[name]).splitlines() if ln != ".LBB:")
+        print(f"{src}: {verdict:9s} {pretty[name]}  insts={insts}")
+    print(f"{src}: {len(pretty)} kernels, {len(pretty) - bad} same, {bad} not")
+    return bad
+
+
 def main():
+    if len(sys.argv) > 1 and sys.argv[1] == "--compare":
+        sys.exit(1 if compare(*sys.argv[2:5]) else 0)
     tree = sys.argv[1] if len(sys.argv) > 1 else "."
     src = sys.argv[2] if len(sys.argv) > 2 else "lbvh_path.hip"
     for name, r in sorted(resources(tree, src).items()):

@@ -354,7 +354,7 @@ struct key_window {
     __device__ __forceinline__ bool inside(int y) const { return (uint32_t)(y - w0) < (uint32_t)(w1 - w0); }
     __device__ __forceinline__ uint32_t at(int y) const { return lds[y - w0]; }            // y inside the window
     // delta(x, y) of BVH.compute:23-33 for a y inside the window (x is always in range); `left` is set when y is a
-    // valid key OUTSIDE the window: the node is a WIDE one and goes to wide_node_search below
+    // valid key OUTSIDE the window: the node is a WIDE one and goes to wide_node_range / wide_node_split below
     __device__ __forceinline__ int delta(uint32_t x_code, int y, bool& left) const
     {
         if (y < 0 || y > num - 1) return -1;
@@ -432,12 +432,15 @@ __device__ __forceinline__ int wide_node_split(const uint32_t* __restrict__ code
 // leaves lane v holding 32 positions of B[v] — ~20 instructions per 64 positions.  A node is then two lookups (word pair, shift,
 // count trailing / leading zeros) instead of two dependent probe loops of 9 (mean) .. 26 (a wave's widest node) LDS round trips at
 // 45 % lane utilisation (25 us each at 1 M nodes, HISTORY.md §4).  A lookup that finds nothing inside the window hands the node to
-// wide_node_search above, as a probe leaving the window did before.  tests/test_tree_bitmaps.py restates all of this on the CPU
+// wide_node_range / wide_node_split above, as a probe leaving the window did before.  tests/test_tree_bitmaps.py restates all of this on the CPU
 // against the oracle's literal searches.
 constexpr int kTreeWords = kTreeWindow / 32;          // 32-position words per B[v]
 constexpr int kBitStride = 33;                        // words of one position block for v = 0 .. 31 (+1: conflict-free columns)
 constexpr int kBitWords = (kTreeWords + 2) * kBitStride;      // one all-zero block in front and one behind: lookups read word pairs
 constexpr int kBitSums = 34;                          // per v: one bit per non-empty word; [32]: "equal neighbours seen" (see below)
+// LBVH_TREE_HALO: a node looks at its neighbours on both sides, and the summary of B[v] has one bit per word of the window
+static_assert(kTreeHalo >= 1 && kTreeWords == (kTreeThreads + 2 * kTreeHalo) / 32 && kTreeWords <= 32,
+              "the window of kTreeThreads + 2 * kTreeHalo keys needs a halo, and one 32-bit summary word per B[v]: at most 1024 keys");
 
 template <int J>
 __device__ __forceinline__ uint32_t swizzle_xor(uint32_t x)        // lane l <- lane l ^ J inside each half of the wave
@@ -728,23 +731,8 @@ __device__ __forceinline__ void range_boxes(const hier_t& h, const uint32_t a[NQ
 #ifndef LBVH_RQ_LV2
 #define LBVH_RQ_LV2 3
 #endif
-__device__ __noinline__ void codes_sink(lbvh_internal_node* a, lbvh_fast_node* b)
-{
-    if (a) reinterpret_cast<uint32_t*>(a)[5] = 1u;
-    if (b) reinterpret_cast<uint32_t*>(b)[0] = 1u;
-}
-#ifdef LBVH_TREE_CLOCK
-__device__ unsigned long long g_tree_clock[2][16];       // [tree mode - 1][phase]: wave-cycles summed over all waves
-#define TREE_TICK(ph) do { const long long now_ = clock64(); if (lane_id() == 0 && MODE != TREE_TOPOLOGY) atomicAdd(&g_tree_clock[MODE - 1][ph], (unsigned long long)(now_ - tick_)); tick_ = now_; } while (0)
-#else
-#define TREE_TICK(ph) do { } while (0)
-#endif
 enum { TREE_TOPOLOGY = 0, TREE_REFERENCE = 1, TREE_FUSED = 2 };
-// measurement builds only (tools/build_variant.sh tree_eN -DLBVH_TREE_EXP=N): 1 = no node / leaf stores, 2 = no range queries,
-// 4 = no box / traversal-node output; LBVH_TREE_LOOPS: the probe loops instead of the bitmap lookups
-#ifndef LBVH_TREE_EXP
-#define LBVH_TREE_EXP 0
-#endif
+// measurement builds only (-DLBVH_TREE_LOOPS): the probe loops instead of the bitmap lookups
 #ifdef LBVH_TREE_LOOPS
 constexpr bool kTreeLookups = false;
 #else
@@ -763,9 +751,6 @@ __device__ __forceinline__ void tree_body(uint32_t block, uint32_t* s_keys, uint
                                           lbvh_fast_node* __restrict__ fused, uint32_t leaf_base,
                                           const uint32_t* __restrict__ sorted_indices)
 {
-#ifdef LBVH_TREE_CLOCK
-    long long tick_ = clock64();
-#endif
     const uint32_t thread_id = block * kTreeThreads + threadIdx.x;
     if (thread_id == 0 && zero_word) *zero_word = 0u;      // lbvh_build_tree + lbvh_refit: the refit's frontier counter
     key_window win;
@@ -781,7 +766,6 @@ __device__ __forceinline__ void tree_body(uint32_t block, uint32_t* s_keys, uint
         for (int k = win.w0 + (int)threadIdx.x; k < win.w1; k += kTreeThreads) s_keys[k - win.w0] = codes[k];
     }
     __syncthreads();
-    TREE_TICK(0);
     // (no early return: the boxes leave through a workgroup-wide LDS transpose below)
     const bool in_range = thread_id < n - 1;                                               // :101
     const int idx = in_range ? (int)thread_id : win.w0;    // threads past the last node: a key INSIDE the window (results unused)
@@ -797,9 +781,7 @@ __device__ __forceinline__ void tree_body(uint32_t block, uint32_t* s_keys, uint
     int first, last, split;
     // (equal neighbours somewhere in the window — possible only for a caller's raw keys, lbvh_build_tree — or d == 0: the loops)
     const bool lookups = LOOKUPS && s_sums[32] == 0u;
-    if (LBVH_TREE_EXP & 32) {
-        first = idx; last = idx + (int)(self & 3u); split = idx;
-    } else if (lookups) {
+    if (lookups) {
         // "search-free form" above: the other end of the range and the split by nearest-set-bit lookups
         const delta_bitmaps bm = {(lds_u32*)s_bits, (lds_u32*)s_sums};
         const int p0 = idx - win.w0;
@@ -864,9 +846,8 @@ __device__ __forceinline__ void tree_body(uint32_t block, uint32_t* s_keys, uint
             }
         }
     }
-    TREE_TICK(1);
     // the wave's wide nodes, one after the other, every lane probing
-    for (uint64_t todo = (LBVH_TREE_EXP & 8) ? 0ull : __ballot(in_range && wide); todo != 0; todo &= todo - 1) {
+    for (uint64_t todo = __ballot(in_range && wide); todo != 0; todo &= todo - 1) {
         const int src = __builtin_ctzll(todo);
         const int widx = __builtin_amdgcn_readlane(idx, src);
         const uint32_t wself = (uint32_t)__builtin_amdgcn_readlane((int)self, src);
@@ -885,13 +866,11 @@ __device__ __forceinline__ void tree_body(uint32_t block, uint32_t* s_keys, uint
             sp = wide_node_split(codes, f, la, fc, lc);
         if ((int)lane_id() == src) { first = f; last = la; split = sp; }
     }
-    TREE_TICK(2);
     const bool valid = in_range && !(split < 0 || (uint32_t)split + 1u >= n);   // invalid: only reachable with non-unique keys
 
     const bool left_leaf = split == first;                                                 // :114
     const bool right_leaf = split + 1 == last;                                             // :132
-    if ((LBVH_TREE_EXP & 1) && valid && (first ^ last ^ split) == 0x7FFFFFF1) codes_sink(internal, fused);
-    if (MODE != TREE_FUSED && valid && !(LBVH_TREE_EXP & 1)) {
+    if (MODE != TREE_FUSED && valid) {
         uint32_t* node = reinterpret_cast<uint32_t*>(&internal[thread_id]);
         // Inside lbvh_build_scene (TREE_REFERENCE) the reference's arrays are written as streaming data, here and below:
         // the frame that follows a rebuild walks the DERIVED scene, and 64 MB of node words and boxes written last would
@@ -916,15 +895,13 @@ __device__ __forceinline__ void tree_body(uint32_t block, uint32_t* s_keys, uint
         if (right_leaf) st2(&leaf[split + 1], thread_id, (uint32_t)split + 1u);
         else st1(&internal[split + 1].parent, thread_id);                                  // :144
     }
-    TREE_TICK(3);
     // The boxes: computed per node, written per LINE — every thread parks its record in LDS and its WAVE writes the wave's 64
     // records as consecutive float4 (a wave's store covers 1 KB of whole records, not 64 quarter lines).
     constexpr int kQuads = MODE == TREE_FUSED ? 4 : 2;             // float4 per record: 64-byte traversal node / 32-byte AABB
     if (MODE == TREE_REFERENCE) {
         const uint32_t a[1] = {(uint32_t)first}, b[1] = {valid ? (uint32_t)last : (uint32_t)first};
         float mn[1][3], mx[1][3];
-        if (LBVH_TREE_EXP & 2) { for (int k = 0; k < 3; k++) { mn[0][k] = (float)first; mx[0][k] = (float)last; } }
-        else range_boxes<1, LBVH_RQ_LV1>(hier, a, b, mn, mx);
+        range_boxes<1, LBVH_RQ_LV1>(hier, a, b, mn, mx);
         s_out[threadIdx.x * 2 + 0] = make_float4(mn[0][0], mn[0][1], mn[0][2], 0.0f);      // :215
         s_out[threadIdx.x * 2 + 1] = make_float4(mx[0][0], mx[0][1], mx[0][2], 0.0f);
     }
@@ -932,15 +909,12 @@ __device__ __forceinline__ void tree_body(uint32_t block, uint32_t* s_keys, uint
         const uint32_t a[2] = {(uint32_t)first, (uint32_t)split + 1u};
         const uint32_t b[2] = {(uint32_t)split, valid ? (uint32_t)last : (uint32_t)split};
         float cmn[2][3], cmx[2][3];
-        if (LBVH_TREE_EXP & 2) { for (int k = 0; k < 3; k++) { cmn[0][k] = cmn[1][k] = (float)first; cmx[0][k] = cmx[1][k] = (float)last; } }
-        else {
-            // the two child ranges one after the other, LBVH_RQ_LV2 levels per round each (round 6: 3) — not both at once with one
-            // level per round (rounds 2 - 5): a round is a full memory latency, the waves wait 64 % of their cycles
-            // (profiles/r6/tree_pair_counters.txt), and two queries of three levels keep as many corners in registers as the
-            // reference's one (four levels per round: 62 -> 70 registers, one wave per SIMD less, 72 -> 82 us)
-            range_boxes<1, LBVH_RQ_LV2>(hier, &a[0], &b[0], &cmn[0], &cmx[0]);
-            range_boxes<1, LBVH_RQ_LV2>(hier, &a[1], &b[1], &cmn[1], &cmx[1]);
-        }
+        // the two child ranges one after the other, LBVH_RQ_LV2 levels per round each (round 6: 3) — not both at once with one
+        // level per round (rounds 2 - 5): a round is a full memory latency, the waves wait 64 % of their cycles
+        // (profiles/r6/tree_pair_counters.txt), and two queries of three levels keep as many corners in registers as the
+        // reference's one (four levels per round: 62 -> 70 registers, one wave per SIMD less, 72 -> 82 us)
+        range_boxes<1, LBVH_RQ_LV2>(hier, &a[0], &b[0], &cmn[0], &cmx[0]);
+        range_boxes<1, LBVH_RQ_LV2>(hier, &a[1], &b[1], &cmn[1], &cmx[1]);
         // child reference: a line index — node index, or LEAF | leaf_base + the triangle's ORIGINAL index (the triangle
         // lines stay in the caller's order: lbvh_common.h)
         uint32_t lref = (uint32_t)split, rref = (uint32_t)split + 1u;
@@ -952,14 +926,12 @@ __device__ __forceinline__ void tree_body(uint32_t block, uint32_t* s_keys, uint
         s_out[threadIdx.x * 4 + 2] = make_float4(cmn[1][0], cmn[1][1], cmn[1][2], __uint_as_float((uint32_t)split));
         s_out[threadIdx.x * 4 + 3] = make_float4(cmx[1][0], cmx[1][1], cmx[1][2], __uint_as_float((uint32_t)split + 1u));
     }
-    TREE_TICK(4);
     if (MODE != TREE_TOPOLOGY) {
         // a wave's 64 records are one contiguous piece of the output and of the staging area: the wave writes them out itself, without
         // waiting for the workgroup's other waves (LDS executes a wave's instructions in order; round 6: the workgroup-wide barrier
         // that stood here made every wave wait for the one searching a wide node in memory — 73.3 -> 72.2 us)
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
         __builtin_amdgcn_wave_barrier();
-        TREE_TICK(5);
         const uint32_t b0 = block * kTreeThreads;
         float4* out = MODE == TREE_FUSED ? reinterpret_cast<float4*>(fused + b0) : reinterpret_cast<float4*>(bvh + b0);
         const uint32_t live = n - 1 > b0 ? min(n - 1 - b0, (uint32_t)kTreeThreads) * kQuads : 0u;   // float4s of existing nodes
@@ -967,14 +939,12 @@ __device__ __forceinline__ void tree_body(uint32_t block, uint32_t* s_keys, uint
 #pragma unroll
         for (int k = 0; k < kQuads; k++) {
             const uint32_t q = wbase + (uint32_t)k * 64u + lane_id();
-            if ((LBVH_TREE_EXP & 4) && s_out[q].x != 12345.678f) continue;
             if (q < live) {
                 if (MODE == TREE_REFERENCE) lbvh_nt_store(&out[q], s_out[q]);
                 else out[q] = s_out[q];
             }
         }
     }
-    TREE_TICK(6);
 }
 
 template <int MODE>
@@ -1830,15 +1800,6 @@ int lbvh_launch_refit(lbvh_context* ctx, uint32_t n, const lbvh_internal_node* d
     }
     return LBVH_OK;
 }
-
-#ifdef LBVH_TREE_CLOCK
-extern "C" int lbvh_debug_tree_clock(unsigned long long* out32, int reset)
-{
-    if (out32 && hipMemcpyFromSymbol(out32, HIP_SYMBOL(g_tree_clock), sizeof(unsigned long long) * 32) != hipSuccess) return -1;
-    if (reset) { unsigned long long z[32] = {}; if (hipMemcpyToSymbol(HIP_SYMBOL(g_tree_clock), z, sizeof(z)) != hipSuccess) return -1; }
-    return 0;
-}
-#endif
 
 extern "C" {
 

@@ -190,6 +190,20 @@ hipEvent_t lbvh_prof_event(lbvh_context* ctx);
         }                                                                               \
     } while (0)
 
+// A kernel with a counting and a plain instantiation (lbvh_ray_stats_target), named once: `kernel` spells the template argument
+// that differs as STATS, and the launch goes to the STATS = true instantiation when `stats` holds, to the other one otherwise.
+#define LBVH_LAUNCH_STATS(ctx, stats, kernel, grid, block, ...) LBVH_LAUNCH_STATS_SHMEM(ctx, stats, kernel, grid, block, 0, __VA_ARGS__)
+#define LBVH_LAUNCH_STATS_SHMEM(ctx, stats, kernel, grid, block, shmem, ...)            \
+    do {                                                                                \
+        if (stats) {                                                                    \
+            constexpr bool STATS = true;                                                \
+            LBVH_LAUNCH_SHMEM(ctx, kernel, grid, block, shmem, __VA_ARGS__);            \
+        } else {                                                                        \
+            constexpr bool STATS = false;                                               \
+            LBVH_LAUNCH_SHMEM(ctx, kernel, grid, block, shmem, __VA_ARGS__);            \
+        }                                                                               \
+    } while (0)
+
 int lbvh_set_error(lbvh_context* ctx, int code, const char* what, const char* detail);
 
 #define LBVH_HIP_TRY(ctx, expr)                                                      \

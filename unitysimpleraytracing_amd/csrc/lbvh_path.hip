@@ -1917,17 +1917,56 @@ __global__ __launch_bounds__(256) void path_resolve_kernel(const lbvh_path_state
 
 static_assert(sizeof(lbvh_path_state) == 64, "path state must be 64 bytes");
 
-// the four-wide form of the derived tree, made on first use after a rebuild and shared by the ray and the point walkers
-static lbvh_status ensure_wide_nodes(lbvh_context* ctx)
+// what the launch of a per-lane walk takes from the context: filled by begin_walk, the last three by use_wide_nodes
+struct walk_launch {
+    uint32_t waves = 0;                     // the grid: one wave per workgroup, one deep stack slab per wave
+    uint32_t* deep = nullptr;               // the deep stack slabs
+    uint32_t lds = 0, deep_cap = 0;         // a lane's stack entries in LDS / in its wave's slab, as the four-wide walkers take them
+    const lbvh_wide_node* wn = nullptr;
+};
+
+// the four-wide form of the derived tree, made on first use after a rebuild and shared by the ray and the point walkers, and the
+// stack split clamped to what those walkers have room for
+static lbvh_status use_wide_nodes(lbvh_context* ctx, walk_launch* w)
 {
-    if (ctx->wide_valid) return LBVH_OK;
-    const uint32_t n_internal = ctx->fast_src.n - 1;
-    const int rc = lbvh_reserve(ctx, &ctx->wide_nodes, &ctx->wide_nodes_bytes, (size_t)n_internal * sizeof(lbvh_wide_node));
-    if (rc != LBVH_OK) return (lbvh_status)rc;
-    LBVH_LAUNCH(ctx, collapse_wide_kernel, dim3((n_internal + 255) / 256), dim3(256), ctx->fast_nodes, n_internal,
-                (lbvh_wide_node*)ctx->wide_nodes);
-    ctx->wide_valid = true;
+    if (!ctx->wide_valid) {
+        const uint32_t n_internal = ctx->fast_src.n - 1;
+        const int rc = lbvh_reserve(ctx, &ctx->wide_nodes, &ctx->wide_nodes_bytes, (size_t)n_internal * sizeof(lbvh_wide_node));
+        if (rc != LBVH_OK) return (lbvh_status)rc;
+        LBVH_LAUNCH(ctx, collapse_wide_kernel, dim3((n_internal + 255) / 256), dim3(256), ctx->fast_nodes, n_internal,
+                    (lbvh_wide_node*)ctx->wide_nodes);
+        ctx->wide_valid = true;
+    }
+    w->lds = std::min<uint32_t>(ctx->ray_stack_lds, kWideStackLds);
+    w->deep_cap = std::min<uint32_t>(ctx->ray_stack_deep, kWideStackDeep);
+    w->wn = (const lbvh_wide_node*)ctx->wide_nodes;
     return LBVH_OK;
+}
+
+// The prologue of every entry point that walks the derived scene one ray or query per lane, after the entry point's own argument
+// checks: h_scene must be what the derived scene was built from (`who`: the entry point's name in the message), the ray scratch
+// holds `count` lanes' worth, and `w` is what the launches take.
+// The scratch is laid out as for lbvh_trace_rays whatever the caller, [two live-ray counters (256 B) | live-ray list 0 | live-ray
+// list 1 | deep stack slabs of the launch's waves] (ray_scratch_bytes_for): the queries over plain rays, points and spheres use
+// the slabs only (the overlap queries also the lists' space), so the live-path list a bounce may have left there is dropped —
+// except for keep_list (lbvh_path_bounce, which goes on from that list) while the scratch stays where it was.
+// wide: the four-wide walk is the only one the caller has.  launch_ray_walk's callers pass false: it asks for the wide nodes itself,
+// after their own launches, where its walker switch takes that walk.
+static lbvh_status begin_walk(lbvh_context* ctx, const lbvh_scene* h_scene, size_t count, const char* who, bool wide, walk_launch* w,
+                              bool keep_list = false)
+{
+    {
+        const int frc = lbvh_require_fast(ctx, *h_scene, who);
+        if (frc != LBVH_OK) return frc;
+    }
+    LBVH_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    void* before = ctx->ray_scratch;
+    const int rc = lbvh_reserve(ctx, &ctx->ray_scratch, &ctx->ray_scratch_bytes, ray_scratch_bytes_for(count));
+    if (rc != LBVH_OK) return rc;
+    if (!keep_list || ctx->ray_scratch != before) ctx->ray_list.valid = false;
+    w->waves = ray_waves_of(count);
+    w->deep = deep_stacks(ctx, count);
+    return wide ? use_wide_nodes(ctx, w) : LBVH_OK;
 }
 
 // the walk over the live rays of `list` (or over plain rays, PLAIN: `total` is their count): four-wide nodes (made on first use
@@ -1935,29 +1974,21 @@ static lbvh_status ensure_wide_nodes(lbvh_context* ctx)
 // binary nodes the packet walk uses (lbvh_debug_ray_walker(ctx, 0): the cross-check of the tests; 2: the few-rays kernel for every launch)
 template <bool PLAIN, int Q>
 static lbvh_status launch_ray_walk(lbvh_context* ctx, const walk_src<PLAIN>* d_states, walk_total<PLAIN> n_alive, const uint32_t* list,
-                                   float t_min, walk_out<Q>* d_hits, size_t count, bool few_rays = false)
+                                   float t_min, walk_out<Q>* d_hits, walk_launch w, bool few_rays = false)
 {
-    const uint32_t ray_waves = ray_waves_of(count);
     if (ctx->ray_walker != 0u) {
-        const lbvh_status wrc = ensure_wide_nodes(ctx);
+        const lbvh_status wrc = use_wide_nodes(ctx, &w);
         if (wrc != LBVH_OK) return wrc;
-        const uint32_t lds = std::min<uint32_t>(ctx->ray_stack_lds, kWideStackLds), deep_cap = std::min<uint32_t>(ctx->ray_stack_deep, kWideStackDeep);
         lbvh_ray_stats* st = ctx->ray_stats;
-        const lbvh_wide_node* wn = (const lbvh_wide_node*)ctx->wide_nodes;
-        if (few_rays || ctx->ray_walker == 2u) {
-            if (st) LBVH_LAUNCH(ctx, (trace_rays_wide_chain_kernel<PLAIN, Q, true>), dim3(ray_waves), dim3(LBVH_WAVE), d_states, n_alive, list, t_min, wn,
-                                ctx->fast_nodes, d_hits, deep_stacks(ctx, count), lds, deep_cap, ctx->fault_dev, st);
-            else LBVH_LAUNCH(ctx, (trace_rays_wide_chain_kernel<PLAIN, Q, false>), dim3(ray_waves), dim3(LBVH_WAVE), d_states, n_alive, list, t_min, wn,
-                             ctx->fast_nodes, d_hits, deep_stacks(ctx, count), lds, deep_cap, ctx->fault_dev, st);
-        } else {
-            if (st) LBVH_LAUNCH(ctx, (trace_rays_wide_kernel<PLAIN, Q, true>), dim3(ray_waves), dim3(LBVH_WAVE), d_states, n_alive, list, t_min, wn,
-                                ctx->fast_nodes, d_hits, deep_stacks(ctx, count), lds, deep_cap, ctx->fault_dev, st);
-            else LBVH_LAUNCH(ctx, (trace_rays_wide_kernel<PLAIN, Q, false>), dim3(ray_waves), dim3(LBVH_WAVE), d_states, n_alive, list, t_min, wn,
-                             ctx->fast_nodes, d_hits, deep_stacks(ctx, count), lds, deep_cap, ctx->fault_dev, st);
-        }
+        if (few_rays || ctx->ray_walker == 2u)
+            LBVH_LAUNCH_STATS(ctx, st, (trace_rays_wide_chain_kernel<PLAIN, Q, STATS>), dim3(w.waves), dim3(LBVH_WAVE), d_states, n_alive, list, t_min,
+                              w.wn, ctx->fast_nodes, d_hits, w.deep, w.lds, w.deep_cap, ctx->fault_dev, st);
+        else
+            LBVH_LAUNCH_STATS(ctx, st, (trace_rays_wide_kernel<PLAIN, Q, STATS>), dim3(w.waves), dim3(LBVH_WAVE), d_states, n_alive, list, t_min,
+                              w.wn, ctx->fast_nodes, d_hits, w.deep, w.lds, w.deep_cap, ctx->fault_dev, st);
     } else {
-        LBVH_LAUNCH(ctx, (trace_rays_kernel<PLAIN, Q>), dim3(ray_waves), dim3(LBVH_WAVE), d_states, n_alive, list, t_min, ctx->fast_nodes,
-                    ctx->fast_tris, d_hits, deep_stacks(ctx, count), ctx->ray_stack_lds, std::min<uint32_t>(ctx->ray_stack_deep, kRayStackDeep), ctx->fault_dev);
+        LBVH_LAUNCH(ctx, (trace_rays_kernel<PLAIN, Q>), dim3(w.waves), dim3(LBVH_WAVE), d_states, n_alive, list, t_min, ctx->fast_nodes,
+                    ctx->fast_tris, d_hits, w.deep, ctx->ray_stack_lds, std::min<uint32_t>(ctx->ray_stack_deep, kRayStackDeep), ctx->fault_dev);
     }
     LBVH_HIP_TRY(ctx, hipGetLastError());
     return LBVH_OK;
@@ -1973,16 +2004,10 @@ static lbvh_status trace_plain_rays(lbvh_context* ctx, const lbvh_ray* d_rays, s
     LBVH_REQUIRE(ctx, d_rays != nullptr && h_scene != nullptr && d_out != nullptr);
     LBVH_REQUIRE(ctx, ((uintptr_t)d_rays & 15) == 0 && ((uintptr_t)d_out & (Q != kClosest ? 3 : 15)) == 0);
     LBVH_REQUIRE(ctx, count <= 0xFFFFFFFFull);
-    {
-        const int frc = lbvh_require_fast(ctx, *h_scene, who);
-        if (frc != LBVH_OK) return frc;
-    }
-    LBVH_HIP_TRY(ctx, hipSetDevice(ctx->device));
-    // only the deep stack slabs of the scratch are used, laid out as for lbvh_trace_rays (whose live-path list they may overwrite)
-    int rc = lbvh_reserve(ctx, &ctx->ray_scratch, &ctx->ray_scratch_bytes, ray_scratch_bytes_for(count));
+    walk_launch w;
+    const lbvh_status rc = begin_walk(ctx, h_scene, count, who, false, &w);
     if (rc != LBVH_OK) return rc;
-    ctx->ray_list.valid = false;
-    return launch_ray_walk<true, Q>(ctx, d_rays, (uint32_t)count, nullptr, 0.0f, d_out, count);
+    return launch_ray_walk<true, Q>(ctx, d_rays, (uint32_t)count, nullptr, 0.0f, d_out, w);
 }
 
 // lbvh_closest_point_query / lbvh_within_distance: always the four-wide walk (lbvh_debug_ray_walker does not apply)
@@ -1995,23 +2020,11 @@ static lbvh_status point_queries(lbvh_context* ctx, const lbvh_point_query* d_qu
     LBVH_REQUIRE(ctx, d_queries != nullptr && h_scene != nullptr && d_out != nullptr);
     LBVH_REQUIRE(ctx, ((uintptr_t)d_queries & 15) == 0 && ((uintptr_t)d_out & (ANY ? 3 : 15)) == 0);
     LBVH_REQUIRE(ctx, count <= 0xFFFFFFFFull);
-    {
-        const int frc = lbvh_require_fast(ctx, *h_scene, who);
-        if (frc != LBVH_OK) return frc;
-    }
-    LBVH_HIP_TRY(ctx, hipSetDevice(ctx->device));
-    // the deep stack slabs of the ray scratch, laid out as for lbvh_trace_rays (whose live-path list they may overwrite)
-    int rc = lbvh_reserve(ctx, &ctx->ray_scratch, &ctx->ray_scratch_bytes, ray_scratch_bytes_for(count));
+    walk_launch w;
+    const lbvh_status rc = begin_walk(ctx, h_scene, count, who, true, &w);
     if (rc != LBVH_OK) return rc;
-    ctx->ray_list.valid = false;
-    rc = ensure_wide_nodes(ctx);
-    if (rc != LBVH_OK) return rc;
-    const uint32_t lds = std::min<uint32_t>(ctx->ray_stack_lds, kWideStackLds), deep_cap = std::min<uint32_t>(ctx->ray_stack_deep, kWideStackDeep);
-    const lbvh_wide_node* wn = (const lbvh_wide_node*)ctx->wide_nodes;
-    if (ctx->ray_stats) LBVH_LAUNCH(ctx, (point_query_wide_kernel<ANY, true>), dim3(ray_waves_of(count)), dim3(LBVH_WAVE), d_queries, (uint32_t)count, wn,
-                                    ctx->fast_nodes, d_out, deep_stacks(ctx, count), lds, deep_cap, ctx->fault_dev, ctx->ray_stats);
-    else LBVH_LAUNCH(ctx, (point_query_wide_kernel<ANY, false>), dim3(ray_waves_of(count)), dim3(LBVH_WAVE), d_queries, (uint32_t)count, wn,
-                     ctx->fast_nodes, d_out, deep_stacks(ctx, count), lds, deep_cap, ctx->fault_dev, ctx->ray_stats);
+    LBVH_LAUNCH_STATS(ctx, ctx->ray_stats, (point_query_wide_kernel<ANY, STATS>), dim3(w.waves), dim3(LBVH_WAVE), d_queries, (uint32_t)count, w.wn,
+                      ctx->fast_nodes, d_out, w.deep, w.lds, w.deep_cap, ctx->fault_dev, ctx->ray_stats);
     LBVH_HIP_TRY(ctx, hipGetLastError());
     return LBVH_OK;
 }
@@ -2026,88 +2039,11 @@ static lbvh_status sphere_casts(lbvh_context* ctx, const lbvh_sphere_ray* d_cast
     LBVH_REQUIRE(ctx, d_casts != nullptr && h_scene != nullptr && d_out != nullptr);
     LBVH_REQUIRE(ctx, ((uintptr_t)d_casts & 15) == 0 && ((uintptr_t)d_out & (ANY ? 3 : 15)) == 0);
     LBVH_REQUIRE(ctx, count <= 0xFFFFFFFFull);
-    {
-        const int frc = lbvh_require_fast(ctx, *h_scene, who);
-        if (frc != LBVH_OK) return frc;
-    }
-    LBVH_HIP_TRY(ctx, hipSetDevice(ctx->device));
-    // the deep stack slabs of the ray scratch, laid out as for lbvh_trace_rays (whose live-path list they may overwrite)
-    int rc = lbvh_reserve(ctx, &ctx->ray_scratch, &ctx->ray_scratch_bytes, ray_scratch_bytes_for(count));
+    walk_launch w;
+    const lbvh_status rc = begin_walk(ctx, h_scene, count, who, true, &w);
     if (rc != LBVH_OK) return rc;
-    ctx->ray_list.valid = false;
-    rc = ensure_wide_nodes(ctx);
-    if (rc != LBVH_OK) return rc;
-    const uint32_t lds = std::min<uint32_t>(ctx->ray_stack_lds, kWideStackLds), deep_cap = std::min<uint32_t>(ctx->ray_stack_deep, kWideStackDeep);
-    const lbvh_wide_node* wn = (const lbvh_wide_node*)ctx->wide_nodes;
-    if (ctx->ray_stats) LBVH_LAUNCH(ctx, (sphere_cast_wide_kernel<ANY, true>), dim3(ray_waves_of(count)), dim3(LBVH_WAVE), d_casts, (uint32_t)count, wn,
-                                    ctx->fast_nodes, d_out, deep_stacks(ctx, count), lds, deep_cap, ctx->fault_dev, ctx->ray_stats);
-    else LBVH_LAUNCH(ctx, (sphere_cast_wide_kernel<ANY, false>), dim3(ray_waves_of(count)), dim3(LBVH_WAVE), d_casts, (uint32_t)count, wn,
-                     ctx->fast_nodes, d_out, deep_stacks(ctx, count), lds, deep_cap, ctx->fault_dev, ctx->ray_stats);
-    LBVH_HIP_TRY(ctx, hipGetLastError());
-    return LBVH_OK;
-}
-
-// lbvh_k_closest_points: the four-wide walk only, one launch; the per-lane lists are dynamic LDS sized from k
-static lbvh_status k_closest_points(lbvh_context* ctx, const lbvh_point_query* d_queries, size_t count, uint32_t k, const lbvh_scene* h_scene,
-                                    lbvh_closest_point* d_out, uint32_t* d_found)
-{
-    if (!ctx) return LBVH_ERR_INVALID_ARG;
-    if (count == 0) return LBVH_OK;
-    LBVH_REQUIRE(ctx, d_queries != nullptr && h_scene != nullptr && d_out != nullptr);
-    LBVH_REQUIRE(ctx, k >= 1u && k <= (uint32_t)LBVH_K_CLOSEST_MAX);
-    LBVH_REQUIRE(ctx, ((uintptr_t)d_queries & 15) == 0 && ((uintptr_t)d_out & 15) == 0 && ((uintptr_t)d_found & 3) == 0);
-    LBVH_REQUIRE(ctx, count <= 0xFFFFFFFFull);
-    {
-        const int frc = lbvh_require_fast(ctx, *h_scene, "lbvh_k_closest_points");
-        if (frc != LBVH_OK) return frc;
-    }
-    LBVH_HIP_TRY(ctx, hipSetDevice(ctx->device));
-    // the deep stack slabs of the ray scratch, laid out as for lbvh_trace_rays (whose live-path list they may overwrite)
-    int rc = lbvh_reserve(ctx, &ctx->ray_scratch, &ctx->ray_scratch_bytes, ray_scratch_bytes_for(count));
-    if (rc != LBVH_OK) return rc;
-    ctx->ray_list.valid = false;
-    rc = ensure_wide_nodes(ctx);
-    if (rc != LBVH_OK) return rc;
-    const uint32_t lds = std::min<uint32_t>(ctx->ray_stack_lds, kWideStackLds), deep_cap = std::min<uint32_t>(ctx->ray_stack_deep, kWideStackDeep);
-    const lbvh_wide_node* wn = (const lbvh_wide_node*)ctx->wide_nodes;
-    const size_t list_lds = (size_t)3 * k * LBVH_WAVE * sizeof(uint32_t);       // 768 bytes per slot: 24 KiB at k = 32
-    if (ctx->ray_stats) LBVH_LAUNCH_SHMEM(ctx, k_closest_wide_kernel<true>, dim3(ray_waves_of(count)), dim3(LBVH_WAVE), list_lds, d_queries, (uint32_t)count, k,
-                                          wn, ctx->fast_nodes, d_out, d_found, deep_stacks(ctx, count), lds, deep_cap, ctx->fault_dev, ctx->ray_stats);
-    else LBVH_LAUNCH_SHMEM(ctx, k_closest_wide_kernel<false>, dim3(ray_waves_of(count)), dim3(LBVH_WAVE), list_lds, d_queries, (uint32_t)count, k,
-                           wn, ctx->fast_nodes, d_out, d_found, deep_stacks(ctx, count), lds, deep_cap, ctx->fault_dev, ctx->ray_stats);
-    LBVH_HIP_TRY(ctx, hipGetLastError());
-    return LBVH_OK;
-}
-
-// lbvh_trace_k_closest: the four-wide walk only (lbvh_debug_ray_walker does not apply), one launch; the per-lane lists are
-// dynamic LDS sized from k
-static lbvh_status trace_k_closest(lbvh_context* ctx, const lbvh_ray* d_rays, size_t count, uint32_t k, const lbvh_scene* h_scene,
-                                   lbvh_hit* d_hits, uint32_t* d_found)
-{
-    if (!ctx) return LBVH_ERR_INVALID_ARG;
-    if (count == 0) return LBVH_OK;
-    LBVH_REQUIRE(ctx, d_rays != nullptr && h_scene != nullptr && d_hits != nullptr);
-    LBVH_REQUIRE(ctx, k >= 1u && k <= (uint32_t)LBVH_K_CLOSEST_MAX);
-    LBVH_REQUIRE(ctx, ((uintptr_t)d_rays & 15) == 0 && ((uintptr_t)d_hits & 15) == 0 && ((uintptr_t)d_found & 3) == 0);
-    LBVH_REQUIRE(ctx, count <= 0xFFFFFFFFull);
-    {
-        const int frc = lbvh_require_fast(ctx, *h_scene, "lbvh_trace_k_closest");
-        if (frc != LBVH_OK) return frc;
-    }
-    LBVH_HIP_TRY(ctx, hipSetDevice(ctx->device));
-    // only the deep stack slabs of the scratch are used, laid out as for lbvh_trace_rays (whose live-path list they may overwrite)
-    int rc = lbvh_reserve(ctx, &ctx->ray_scratch, &ctx->ray_scratch_bytes, ray_scratch_bytes_for(count));
-    if (rc != LBVH_OK) return rc;
-    ctx->ray_list.valid = false;
-    rc = ensure_wide_nodes(ctx);
-    if (rc != LBVH_OK) return rc;
-    const uint32_t lds = std::min<uint32_t>(ctx->ray_stack_lds, kWideStackLds), deep_cap = std::min<uint32_t>(ctx->ray_stack_deep, kWideStackDeep);
-    const lbvh_wide_node* wn = (const lbvh_wide_node*)ctx->wide_nodes;
-    const size_t list_lds = (size_t)3 * k * LBVH_WAVE * sizeof(uint32_t);       // 768 bytes per slot: 24 KiB at k = 32
-    if (ctx->ray_stats) LBVH_LAUNCH_SHMEM(ctx, k_hits_wide_kernel<true>, dim3(ray_waves_of(count)), dim3(LBVH_WAVE), list_lds, d_rays, (uint32_t)count, k,
-                                          wn, ctx->fast_nodes, d_hits, d_found, deep_stacks(ctx, count), lds, deep_cap, ctx->fault_dev, ctx->ray_stats);
-    else LBVH_LAUNCH_SHMEM(ctx, k_hits_wide_kernel<false>, dim3(ray_waves_of(count)), dim3(LBVH_WAVE), list_lds, d_rays, (uint32_t)count, k,
-                           wn, ctx->fast_nodes, d_hits, d_found, deep_stacks(ctx, count), lds, deep_cap, ctx->fault_dev, ctx->ray_stats);
+    LBVH_LAUNCH_STATS(ctx, ctx->ray_stats, (sphere_cast_wide_kernel<ANY, STATS>), dim3(w.waves), dim3(LBVH_WAVE), d_casts, (uint32_t)count, w.wn,
+                      ctx->fast_nodes, d_out, w.deep, w.lds, w.deep_cap, ctx->fault_dev, ctx->ray_stats);
     LBVH_HIP_TRY(ctx, hipGetLastError());
     return LBVH_OK;
 }
@@ -2125,47 +2061,65 @@ static lbvh_status overlap_queries(lbvh_context* ctx, const void* d_queries, siz
     LBVH_REQUIRE(ctx, d_tris != nullptr || capacity == 0);
     LBVH_REQUIRE(ctx, ((uintptr_t)d_queries & 15) == 0 && ((uintptr_t)d_offsets & 7) == 0 && ((uintptr_t)d_tris & 3) == 0);
     LBVH_REQUIRE(ctx, count <= 0xFFFFFFFFull);
-    {
-        const int frc = lbvh_require_fast(ctx, *h_scene, who);
-        if (frc != LBVH_OK) return frc;
-    }
-    LBVH_HIP_TRY(ctx, hipSetDevice(ctx->device));
-    int rc = lbvh_reserve(ctx, &ctx->ray_scratch, &ctx->ray_scratch_bytes, ray_scratch_bytes_for(count));
+    walk_launch w;
+    const lbvh_status rc = begin_walk(ctx, h_scene, count, who, true, &w);
     if (rc != LBVH_OK) return rc;
-    ctx->ray_list.valid = false;
-    rc = ensure_wide_nodes(ctx);
-    if (rc != LBVH_OK) return rc;
-    const uint32_t lds = std::min<uint32_t>(ctx->ray_stack_lds, kWideStackLds), deep_cap = std::min<uint32_t>(ctx->ray_stack_deep, kWideStackDeep);
-    const lbvh_wide_node* wn = (const lbvh_wide_node*)ctx->wide_nodes;
     const float4* q = (const float4*)d_queries;
-    const uint32_t total = (uint32_t)count, waves = ray_waves_of(count), leaf_base = ctx->fast_capacity;
+    const uint32_t total = (uint32_t)count, leaf_base = ctx->fast_capacity;
     uint32_t* counts = ray_list(ctx, count, 0);
     uint64_t* tile_sums = (uint64_t*)ray_list(ctx, count, 1);
     const uint32_t n_tiles = total / kScanTile + 1u;           // the tiles cover total + 1 offsets
     // (8 bytes per tile sum: (count / 1024 + 1) * 8 <= list_bytes(count) = 4 * count rounded up to 256, for every count >= 1)
-    if (ctx->ray_stats) LBVH_LAUNCH(ctx, (overlap_wide_kernel<BOX, false, true>), dim3(waves), dim3(LBVH_WAVE), q, total, wn, ctx->fast_nodes, leaf_base,
-                                    counts, (const uint64_t*)nullptr, (uint32_t*)nullptr, (uint64_t)0, deep_stacks(ctx, count), lds, deep_cap, ctx->fault_dev, ctx->ray_stats);
-    else LBVH_LAUNCH(ctx, (overlap_wide_kernel<BOX, false, false>), dim3(waves), dim3(LBVH_WAVE), q, total, wn, ctx->fast_nodes, leaf_base,
-                     counts, (const uint64_t*)nullptr, (uint32_t*)nullptr, (uint64_t)0, deep_stacks(ctx, count), lds, deep_cap, ctx->fault_dev, ctx->ray_stats);
+    LBVH_LAUNCH_STATS(ctx, ctx->ray_stats, (overlap_wide_kernel<BOX, false, STATS>), dim3(w.waves), dim3(LBVH_WAVE), q, total, w.wn, ctx->fast_nodes, leaf_base,
+                      counts, (const uint64_t*)nullptr, (uint32_t*)nullptr, (uint64_t)0, w.deep, w.lds, w.deep_cap, ctx->fault_dev, ctx->ray_stats);
     if (n_tiles > 1u) {
         LBVH_LAUNCH(ctx, overlap_tile_sums_kernel, dim3(n_tiles), dim3(256), (const uint32_t*)counts, total, tile_sums);
         LBVH_LAUNCH(ctx, overlap_scan_sums_kernel, dim3(1), dim3(1024), tile_sums, n_tiles);
     }
     LBVH_LAUNCH(ctx, overlap_offsets_kernel, dim3(n_tiles), dim3(256), (const uint32_t*)counts, total,
                 n_tiles > 1u ? (const uint64_t*)tile_sums : (const uint64_t*)nullptr, d_offsets);
-    if (capacity != 0) {
-        if (ctx->ray_stats) LBVH_LAUNCH(ctx, (overlap_wide_kernel<BOX, true, true>), dim3(waves), dim3(LBVH_WAVE), q, total, wn, ctx->fast_nodes, leaf_base,
-                                        (uint32_t*)nullptr, (const uint64_t*)d_offsets, d_tris, capacity, deep_stacks(ctx, count), lds, deep_cap, ctx->fault_dev, ctx->ray_stats);
-        else LBVH_LAUNCH(ctx, (overlap_wide_kernel<BOX, true, false>), dim3(waves), dim3(LBVH_WAVE), q, total, wn, ctx->fast_nodes, leaf_base,
-                         (uint32_t*)nullptr, (const uint64_t*)d_offsets, d_tris, capacity, deep_stacks(ctx, count), lds, deep_cap, ctx->fault_dev, ctx->ray_stats);
-    }
+    if (capacity != 0)
+        LBVH_LAUNCH_STATS(ctx, ctx->ray_stats, (overlap_wide_kernel<BOX, true, STATS>), dim3(w.waves), dim3(LBVH_WAVE), q, total, w.wn, ctx->fast_nodes, leaf_base,
+                          (uint32_t*)nullptr, (const uint64_t*)d_offsets, d_tris, capacity, w.deep, w.lds, w.deep_cap, ctx->fault_dev, ctx->ray_stats);
     LBVH_HIP_TRY(ctx, hipGetLastError());
     return LBVH_OK;
 }
 
-// lbvh_point_crossings: the four-wide walk only (lbvh_debug_ray_walker does not apply), the directions by value in the arguments
-static lbvh_status point_crossings(lbvh_context* ctx, const lbvh_point_query* d_points, size_t count, const float* h_dirs, uint32_t n_dirs,
-                                   const lbvh_scene* h_scene, uint32_t* d_parity)
+extern "C" {
+
+// the four-wide walk only (lbvh_debug_ray_walker does not apply), one launch; the per-lane lists are dynamic LDS sized from k
+lbvh_status lbvh_trace_k_closest(lbvh_context* ctx, const lbvh_ray* d_rays, size_t count, uint32_t k, const lbvh_scene* h_scene,
+                                 lbvh_hit* d_hits, uint32_t* d_found)
+{
+    if (!ctx) return LBVH_ERR_INVALID_ARG;
+    if (count == 0) return LBVH_OK;
+    LBVH_REQUIRE(ctx, d_rays != nullptr && h_scene != nullptr && d_hits != nullptr);
+    LBVH_REQUIRE(ctx, k >= 1u && k <= (uint32_t)LBVH_K_CLOSEST_MAX);
+    LBVH_REQUIRE(ctx, ((uintptr_t)d_rays & 15) == 0 && ((uintptr_t)d_hits & 15) == 0 && ((uintptr_t)d_found & 3) == 0);
+    LBVH_REQUIRE(ctx, count <= 0xFFFFFFFFull);
+    walk_launch w;
+    const lbvh_status rc = begin_walk(ctx, h_scene, count, "lbvh_trace_k_closest", true, &w);
+    if (rc != LBVH_OK) return rc;
+    const size_t list_lds = (size_t)3 * k * LBVH_WAVE * sizeof(uint32_t);       // 768 bytes per slot: 24 KiB at k = 32
+    LBVH_LAUNCH_STATS_SHMEM(ctx, ctx->ray_stats, k_hits_wide_kernel<STATS>, dim3(w.waves), dim3(LBVH_WAVE), list_lds, d_rays, (uint32_t)count, k,
+                            w.wn, ctx->fast_nodes, d_hits, d_found, w.deep, w.lds, w.deep_cap, ctx->fault_dev, ctx->ray_stats);
+    LBVH_HIP_TRY(ctx, hipGetLastError());
+    return LBVH_OK;
+}
+
+lbvh_status lbvh_sphere_cast(lbvh_context* ctx, const lbvh_sphere_ray* d_casts, size_t count, const lbvh_scene* h_scene, lbvh_hit* d_hits)
+{
+    return sphere_casts<false>(ctx, d_casts, count, h_scene, d_hits, "lbvh_sphere_cast");
+}
+
+lbvh_status lbvh_sphere_cast_any(lbvh_context* ctx, const lbvh_sphere_ray* d_casts, size_t count, const lbvh_scene* h_scene, uint32_t* d_flags)
+{
+    return sphere_casts<true>(ctx, d_casts, count, h_scene, d_flags, "lbvh_sphere_cast_any");
+}
+
+// the four-wide walk only (lbvh_debug_ray_walker does not apply), the directions by value in the arguments
+lbvh_status lbvh_point_crossings(lbvh_context* ctx, const lbvh_point_query* d_points, size_t count, const float* h_dirs, uint32_t n_dirs,
+                                 const lbvh_scene* h_scene, uint32_t* d_parity)
 {
     if (!ctx) return LBVH_ERR_INVALID_ARG;
     if (count == 0) return LBVH_OK;
@@ -2180,49 +2134,13 @@ static lbvh_status point_crossings(lbvh_context* ctx, const lbvh_point_query* d_
         LBVH_REQUIRE(ctx, x != 0.0f || y != 0.0f || z != 0.0f);
         dirs.d[j][0] = x; dirs.d[j][1] = y; dirs.d[j][2] = z;
     }
-    {
-        const int frc = lbvh_require_fast(ctx, *h_scene, "lbvh_point_crossings");
-        if (frc != LBVH_OK) return frc;
-    }
-    LBVH_HIP_TRY(ctx, hipSetDevice(ctx->device));
-    // the deep stack slabs of the ray scratch, laid out as for lbvh_trace_rays (whose live-path list they may overwrite)
-    int rc = lbvh_reserve(ctx, &ctx->ray_scratch, &ctx->ray_scratch_bytes, ray_scratch_bytes_for(count));
+    walk_launch w;
+    const lbvh_status rc = begin_walk(ctx, h_scene, count, "lbvh_point_crossings", true, &w);
     if (rc != LBVH_OK) return rc;
-    ctx->ray_list.valid = false;
-    rc = ensure_wide_nodes(ctx);
-    if (rc != LBVH_OK) return rc;
-    const uint32_t lds = std::min<uint32_t>(ctx->ray_stack_lds, kWideStackLds), deep_cap = std::min<uint32_t>(ctx->ray_stack_deep, kWideStackDeep);
-    const lbvh_wide_node* wn = (const lbvh_wide_node*)ctx->wide_nodes;
-    if (ctx->ray_stats) LBVH_LAUNCH(ctx, point_crossings_wide_kernel<true>, dim3(ray_waves_of(count)), dim3(LBVH_WAVE), d_points, (uint32_t)count, dirs,
-                                    n_dirs, wn, ctx->fast_nodes, d_parity, deep_stacks(ctx, count), lds, deep_cap, ctx->fault_dev, ctx->ray_stats);
-    else LBVH_LAUNCH(ctx, point_crossings_wide_kernel<false>, dim3(ray_waves_of(count)), dim3(LBVH_WAVE), d_points, (uint32_t)count, dirs,
-                     n_dirs, wn, ctx->fast_nodes, d_parity, deep_stacks(ctx, count), lds, deep_cap, ctx->fault_dev, ctx->ray_stats);
+    LBVH_LAUNCH_STATS(ctx, ctx->ray_stats, point_crossings_wide_kernel<STATS>, dim3(w.waves), dim3(LBVH_WAVE), d_points, (uint32_t)count, dirs,
+                      n_dirs, w.wn, ctx->fast_nodes, d_parity, w.deep, w.lds, w.deep_cap, ctx->fault_dev, ctx->ray_stats);
     LBVH_HIP_TRY(ctx, hipGetLastError());
     return LBVH_OK;
-}
-
-extern "C" {
-
-lbvh_status lbvh_trace_k_closest(lbvh_context* ctx, const lbvh_ray* d_rays, size_t count, uint32_t k, const lbvh_scene* h_scene,
-                                 lbvh_hit* d_hits, uint32_t* d_found)
-{
-    return trace_k_closest(ctx, d_rays, count, k, h_scene, d_hits, d_found);
-}
-
-lbvh_status lbvh_sphere_cast(lbvh_context* ctx, const lbvh_sphere_ray* d_casts, size_t count, const lbvh_scene* h_scene, lbvh_hit* d_hits)
-{
-    return sphere_casts<false>(ctx, d_casts, count, h_scene, d_hits, "lbvh_sphere_cast");
-}
-
-lbvh_status lbvh_sphere_cast_any(lbvh_context* ctx, const lbvh_sphere_ray* d_casts, size_t count, const lbvh_scene* h_scene, uint32_t* d_flags)
-{
-    return sphere_casts<true>(ctx, d_casts, count, h_scene, d_flags, "lbvh_sphere_cast_any");
-}
-
-lbvh_status lbvh_point_crossings(lbvh_context* ctx, const lbvh_point_query* d_points, size_t count, const float* h_dirs, uint32_t n_dirs,
-                                 const lbvh_scene* h_scene, uint32_t* d_parity)
-{
-    return point_crossings(ctx, d_points, count, h_dirs, n_dirs, h_scene, d_parity);
 }
 
 lbvh_status lbvh_closest_point_query(lbvh_context* ctx, const lbvh_point_query* d_queries, size_t count, const lbvh_scene* h_scene,
@@ -2237,10 +2155,24 @@ lbvh_status lbvh_within_distance(lbvh_context* ctx, const lbvh_point_query* d_qu
     return point_queries<true>(ctx, d_queries, count, h_scene, d_flags, "lbvh_within_distance");
 }
 
+// the four-wide walk only, one launch; the per-lane lists are dynamic LDS sized from k
 lbvh_status lbvh_k_closest_points(lbvh_context* ctx, const lbvh_point_query* d_queries, size_t count, uint32_t k,
                                   const lbvh_scene* h_scene, lbvh_closest_point* d_out, uint32_t* d_found)
 {
-    return k_closest_points(ctx, d_queries, count, k, h_scene, d_out, d_found);
+    if (!ctx) return LBVH_ERR_INVALID_ARG;
+    if (count == 0) return LBVH_OK;
+    LBVH_REQUIRE(ctx, d_queries != nullptr && h_scene != nullptr && d_out != nullptr);
+    LBVH_REQUIRE(ctx, k >= 1u && k <= (uint32_t)LBVH_K_CLOSEST_MAX);
+    LBVH_REQUIRE(ctx, ((uintptr_t)d_queries & 15) == 0 && ((uintptr_t)d_out & 15) == 0 && ((uintptr_t)d_found & 3) == 0);
+    LBVH_REQUIRE(ctx, count <= 0xFFFFFFFFull);
+    walk_launch w;
+    const lbvh_status rc = begin_walk(ctx, h_scene, count, "lbvh_k_closest_points", true, &w);
+    if (rc != LBVH_OK) return rc;
+    const size_t list_lds = (size_t)3 * k * LBVH_WAVE * sizeof(uint32_t);       // 768 bytes per slot: 24 KiB at k = 32
+    LBVH_LAUNCH_STATS_SHMEM(ctx, ctx->ray_stats, k_closest_wide_kernel<STATS>, dim3(w.waves), dim3(LBVH_WAVE), list_lds, d_queries, (uint32_t)count, k,
+                            w.wn, ctx->fast_nodes, d_out, d_found, w.deep, w.lds, w.deep_cap, ctx->fault_dev, ctx->ray_stats);
+    LBVH_HIP_TRY(ctx, hipGetLastError());
+    return LBVH_OK;
 }
 
 lbvh_status lbvh_box_overlaps(lbvh_context* ctx, const lbvh_aabb* d_boxes, size_t count, const lbvh_scene* h_scene,
@@ -2293,20 +2225,14 @@ lbvh_status lbvh_trace_rays(lbvh_context* ctx, const lbvh_path_state* d_states, 
     LBVH_REQUIRE(ctx, d_states != nullptr && h_scene != nullptr && d_hits != nullptr);
     LBVH_REQUIRE(ctx, ((uintptr_t)d_states & 15) == 0 && ((uintptr_t)d_hits & 15) == 0);
     LBVH_REQUIRE(ctx, count <= 0xFFFFFFFFull);
-    {
-        const int frc = lbvh_require_fast(ctx, *h_scene, "lbvh_trace_rays");
-        if (frc != LBVH_OK) return frc;
-    }
-    LBVH_HIP_TRY(ctx, hipSetDevice(ctx->device));
-    // scratch: [live-ray count (256 B) | indices of the live rays]
-    int rc = lbvh_reserve(ctx, &ctx->ray_scratch, &ctx->ray_scratch_bytes, ray_scratch_bytes_for(count));
+    walk_launch w;
+    const lbvh_status rc = begin_walk(ctx, h_scene, count, "lbvh_trace_rays", false, &w);     // (the list is dropped: this call takes list 0 for its own rays)
     if (rc != LBVH_OK) return rc;
-    ctx->ray_list.valid = false;                      // this call takes list 0 for its own rays
     uint32_t* n_alive = ray_counter(ctx, 0);
     uint32_t* list = ray_list(ctx, count, 0);
     LBVH_HIP_TRY(ctx, hipMemsetAsync(n_alive, 0, 4, ctx->cur_stream));
     LBVH_LAUNCH(ctx, alive_rays_kernel, dim3((unsigned)((count + 255) / 256)), dim3(256), d_states, count, n_alive, list, d_hits);
-    return launch_ray_walk<false, kClosest>(ctx, d_states, n_alive, list, t_min, d_hits, count);
+    return launch_ray_walk<false, kClosest>(ctx, d_states, n_alive, list, t_min, d_hits, w);
 }
 
 lbvh_status lbvh_trace_closest(lbvh_context* ctx, const lbvh_ray* d_rays, size_t count, const lbvh_scene* h_scene, lbvh_hit* d_hits)
@@ -2388,15 +2314,9 @@ static lbvh_status path_bounce_impl(lbvh_context* ctx, const lbvh_scene* h_scene
     if (count == 0) return LBVH_OK;
     LBVH_REQUIRE(ctx, h_scene != nullptr && h_scene->triangles != nullptr && d_hits != nullptr && d_states != nullptr);
     LBVH_REQUIRE(ctx, ((uintptr_t)d_states & 15) == 0 && ((uintptr_t)d_hits & 15) == 0 && count <= 0xFFFFFFFFull);
-    {
-        const int frc = lbvh_require_fast(ctx, *h_scene, "lbvh_path_bounce");
-        if (frc != LBVH_OK) return frc;
-    }
-    LBVH_HIP_TRY(ctx, hipSetDevice(ctx->device));
-    void* before = ctx->ray_scratch;
-    int rc = lbvh_reserve(ctx, &ctx->ray_scratch, &ctx->ray_scratch_bytes, ray_scratch_bytes_for(count));
+    walk_launch w;
+    const lbvh_status rc = begin_walk(ctx, h_scene, count, "lbvh_path_bounce", false, &w, /* keep_list */ true);
     if (rc != LBVH_OK) return rc;
-    if (ctx->ray_scratch != before) ctx->ray_list.valid = false;
     // the paths to look at: the list the bounce before left behind, if this call continues that very frame (same buffers, next
     // bounce, nothing written into them since: lbvh_note_write); otherwise every pixel.  The new list goes into the other buffer.
     // (from the second bounce on: at bounce 1 two fifths of a frame's paths are still alive and the two forms cost the same, 53 - 56 us
@@ -2422,7 +2342,7 @@ static lbvh_status path_bounce_impl(lbvh_context* ctx, const lbvh_scene* h_scene
     ctx->ray_list.states = d_states; ctx->ray_list.hits = d_hits; ctx->ray_list.count = count;
     ctx->ray_list.bounce = h_first_camera ? 0u : bounce;
     ctx->ray_list.turn = turn;
-    return launch_ray_walk<false, kClosest>(ctx, d_states, n_alive, list, t_min, d_hits, count, bounce >= 1u);
+    return launch_ray_walk<false, kClosest>(ctx, d_states, n_alive, list, t_min, d_hits, w, bounce >= 1u);
 }
 
 extern "C" {
