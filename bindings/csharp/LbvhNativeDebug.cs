@@ -15,6 +15,7 @@ public static class LbvhNativeDebug
     // host-side model of the sort's tile hand-out order (no GPU involved)
     [DllImport(Lib)] public static extern uint lbvh_debug_sort_ticket_tile(uint k, uint x, uint group, uint queues);
     [DllImport(Lib)] public static extern int lbvh_debug_ray_stack_split(IntPtr ctx, uint ldsEntries);
+    [DllImport(Lib)] public static extern int lbvh_debug_ray_waves(IntPtr ctx, uint maxWaves);
     [DllImport(Lib)] public static extern int lbvh_debug_ray_walker(IntPtr ctx, uint walker);
     [DllImport(Lib)] public static extern int lbvh_debug_ray_stack_limit(IntPtr ctx, uint deepEntries);
     // measurement: the four-wide per-ray walkers add {rays, node lines fetched, triangles tested} (3 x ulong) while set

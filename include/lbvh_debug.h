@@ -50,6 +50,15 @@ uint32_t lbvh_debug_sort_ticket_tile(uint32_t k, uint32_t x, uint32_t group, uin
  * of the stack is exercised by ordinary scenes. */
 lbvh_status lbvh_debug_ray_stack_split(lbvh_context* ctx, uint32_t lds_entries);
 
+/* Test hook: the largest grid of a per-lane walk (every entry point that walks one ray, point, sphere or box per lane:
+ * lbvh_trace_rays, the bounces, lbvh_trace_closest / _occluded, lbvh_count_hits, the point queries, lbvh_k_closest_points,
+ * lbvh_trace_k_closest, the sphere casts, lbvh_point_crossings and both walks of the overlap queries).  Such a launch is
+ * min(8192, ceil(count / 64)) one-wave workgroups; each wave owns a run of ceil(count / waves) consecutive queries and refills a
+ * lane from the run when the lane's query is finished.  0 (default): 8192.  n >= 1: at most n waves, so the runs of a small call
+ * get long and every lane is refilled many times (tests/test_walk_refill.py: 1 500 queries on one wave, about 23 refills per
+ * lane); above 8192: LBVH_ERR_INVALID_ARG.  Results do not depend on it.  Per context, as the stack split. */
+lbvh_status lbvh_debug_ray_waves(lbvh_context* ctx, uint32_t max_waves);
+
 /* Measurement aid (cfg5's roofline): while d_stats is non-NULL, every launch of the four-wide per-ray walk (lbvh_trace_rays,
  * lbvh_path_bounce, lbvh_path_first_bounce) ADDS what it did to it: rays walked, 128-byte four-wide node lines fetched (one per
  * ray-step), triangle lines fetched and tested.  Zero it yourself; NULL switches the counting off (the default: the counting

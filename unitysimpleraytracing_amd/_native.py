@@ -139,6 +139,7 @@ DEBUG_SIGNATURES = {
     "lbvh_debug_switch": (_I32, [_P, _U32, _U32]),
     "lbvh_debug_sort_ticket_tile": (_U32, [_U32, _U32, _U32, _U32]),
     "lbvh_debug_ray_stack_split": (_I32, [_P, _U32]),
+    "lbvh_debug_ray_waves": (_I32, [_P, _U32]),
     "lbvh_debug_ray_walker": (_I32, [_P, _U32]),
     "lbvh_debug_ray_stack_limit": (_I32, [_P, _U32]),
     "lbvh_ray_stats_target": (_I32, [_P, _P]),

@@ -1964,7 +1964,9 @@ static lbvh_status begin_walk(lbvh_context* ctx, const lbvh_scene* h_scene, size
     const int rc = lbvh_reserve(ctx, &ctx->ray_scratch, &ctx->ray_scratch_bytes, ray_scratch_bytes_for(count));
     if (rc != LBVH_OK) return rc;
     if (!keep_list || ctx->ray_scratch != before) ctx->ray_list.valid = false;
+    // (lbvh_debug_ray_waves can only lower the grid: the slabs stay sized by ray_waves_of(count), one per launched wave and more)
     w->waves = ray_waves_of(count);
+    if (ctx->ray_max_waves != 0u) w->waves = std::min(w->waves, ctx->ray_max_waves);
     w->deep = deep_stacks(ctx, count);
     return wide ? use_wide_nodes(ctx, w) : LBVH_OK;
 }
@@ -2263,6 +2265,14 @@ lbvh_status lbvh_debug_ray_stack_split(lbvh_context* ctx, uint32_t lds_entries)
     if (!ctx) return LBVH_ERR_INVALID_ARG;
     LBVH_REQUIRE(ctx, lds_entries >= 1 && lds_entries <= (uint32_t)kRayStackLds);
     ctx->ray_stack_lds = lds_entries;
+    return LBVH_OK;
+}
+
+lbvh_status lbvh_debug_ray_waves(lbvh_context* ctx, uint32_t max_waves)
+{
+    if (!ctx) return LBVH_ERR_INVALID_ARG;
+    LBVH_REQUIRE(ctx, max_waves <= kRayWaves);
+    ctx->ray_max_waves = max_waves;
     return LBVH_OK;
 }
 
