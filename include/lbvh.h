@@ -498,7 +498,13 @@ lbvh_status lbvh_frame_unpack(lbvh_context* ctx, const lbvh_hit* d_packed, uint6
  * Texture: d_texture_rgba8 = tex_h rows of tex_w RGBA8 texels, row 0 at v = 0 (Unity's convention), no
  * sRGB decode (the project is in Gamma colour space, ProjectSettings.asset:50), sampled like
  * SampleLevel(linearClampSampler, uv, 0): bilinear on texel centres in fp32, clamp addressing, mip 0.
- * d_rgba16f receives count x 4 IEEE half floats. */
+ * Clamp addressing holds for every finite uv: one so large that uv * size overflows fp32 gives the edge texel (the texel
+ * coordinate is clamped to +-2^24 before its floor is taken, which changes no finite result).  A NaN uv stays a NaN colour.
+ * A miss record carries triangle 0 and is shaded with it.  The record lbvh_path_bounce leaves for an ended path,
+ * {LBVH_MAX_FLOAT, 0xFFFFFFFF, 0, 0}, is safe to shade: it reads triangle 0 and gives what {LBVH_MAX_FLOAT, 0, 0, 0} gives.
+ * d_rgba16f receives count x 4 IEEE half floats: the fp32 value rounded to nearest even, 65520 and up to infinity.  Of a NaN
+ * only the class is specified (lbvh_shade, lbvh_compose, lbvh_path_resolve): the GPU's conversion keeps the sign and the top
+ * payload bits, the CPU oracle returns 0x7E00 / 0xFE00. */
 lbvh_status lbvh_shade(lbvh_context* ctx, const lbvh_hit* d_hits, size_t count, const lbvh_triangle* d_triangles,
                        const uint8_t* d_texture_rgba8, int32_t tex_w, int32_t tex_h, uint16_t* d_rgba16f);
 

@@ -106,12 +106,30 @@ _lib.orc_path_resolve.restype = None
 
 
 def animate(rest, body, centres, angle):
+    return animate_cs(rest, body, centres, np.float32(np.cos(angle)), np.float32(np.sin(angle)))
+
+
+def animate_cs(rest, body, centres, cos_angle, sin_angle):
+    """orc_animate with the (cos, sin) pair as lbvh_animate takes it: any two floats, unit or not"""
     rest = np.ascontiguousarray(rest, dtype=L.TRIANGLE)
     out = np.zeros_like(rest)
     _lib.orc_animate(_ptr(rest), len(rest), _ptr(np.ascontiguousarray(body, dtype=np.uint32)),
                      _ptr(np.ascontiguousarray(centres, dtype=np.float32)),
-                     float(np.float32(np.cos(angle))), float(np.float32(np.sin(angle))), _ptr(out))
+                     float(np.float32(cos_angle)), float(np.float32(sin_angle)), _ptr(out))
     return out
+
+
+class TrianglesOnly:
+    """what path_scatter needs of a Built: a scene whose only array is the triangles"""
+
+    def __init__(self, triangles):
+        self.triangles = np.ascontiguousarray(triangles, dtype=L.TRIANGLE)
+
+    def scene(self):
+        s = _Scene()
+        s.n = len(self.triangles)
+        s.triangles = self.triangles.ctypes.data
+        return s
 
 
 def path_begin(camera):

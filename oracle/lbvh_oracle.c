@@ -823,7 +823,10 @@ static void texel_rgba(const uint8_t* tex, int w, int x, int y, float c[4])
 /* SampleLevel(linearClampSampler, uv, 0)  :183 — bilinear on texel centres, clamp addressing, fp32 */
 static void sample_bilinear_clamp(const uint8_t* tex, int w, int h, float u, float v, float out[4])
 {
-    const float x = u * (float)w - 0.5f, y = v * (float)h - 0.5f;
+    float x = u * (float)w - 0.5f, y = v * (float)h - 0.5f;
+    /* u * w may overflow: clamp to +-2^24, where x is an integer already (weight 0, edge texel); compares keep a NaN a NaN */
+    x = x > 16777216.0f ? 16777216.0f : x; x = x < -16777216.0f ? -16777216.0f : x;
+    y = y > 16777216.0f ? 16777216.0f : y; y = y < -16777216.0f ? -16777216.0f : y;
     const float xf = floorf(x), yf = floorf(y);
     const float fx = x - xf, fy = y - yf;
     const float xc0 = fminf(fmaxf(xf, 0.0f), (float)(w - 1)), xc1 = fminf(fmaxf(xf + 1.0f, 0.0f), (float)(w - 1));
@@ -842,7 +845,7 @@ void orc_shade(const lbvh_hit* hits, size_t count, const lbvh_triangle* tris, co
 {
     for (size_t i = 0; i < count; i++) {
         const lbvh_hit* r = &hits[i];
-        const lbvh_triangle* t = &tris[r->tri];                                              /* :178 */
+        const lbvh_triangle* t = &tris[r->t == LBVH_MAX_FLOAT && r->tri == 0xFFFFFFFFu ? 0u : r->tri];   /* :178; an ended path's record: triangle 0 */
         const float w = (1.0f - r->u) - r->v;
         const float tu = (w * t->a_uv[0] + r->u * t->b_uv[0]) + r->v * t->c_uv[0];          /* :179 */
         const float tv = (w * t->a_uv[1] + r->u * t->b_uv[1]) + r->v * t->c_uv[1];

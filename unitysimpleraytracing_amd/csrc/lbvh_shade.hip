@@ -15,7 +15,11 @@ __device__ __forceinline__ float4 texel(const uint8_t* __restrict__ tex, int w, 
 // SampleLevel(linearClampSampler, uv, 0): bilinear on texel centres, clamp addressing
 __device__ __forceinline__ float4 sample_bilinear_clamp(const uint8_t* __restrict__ tex, int w, int h, float u, float v)
 {
-    const float x = u * (float)w - 0.5f, y = v * (float)h - 0.5f;
+    float x = u * (float)w - 0.5f, y = v * (float)h - 0.5f;
+    // u * w may overflow: inf - floorf(inf) would be a NaN weight.  From 2^24 on x is an integer (weight 0, edge texel), so the
+    // clamp changes no finite result; written with compares so that a NaN uv stays a NaN colour
+    x = x > 16777216.0f ? 16777216.0f : x; x = x < -16777216.0f ? -16777216.0f : x;
+    y = y > 16777216.0f ? 16777216.0f : y; y = y < -16777216.0f ? -16777216.0f : y;
     const float xf = floorf(x), yf = floorf(y);
     const float fx = x - xf, fy = y - yf;
     // clamp in float first: u, v may be far outside [0, 1]
@@ -42,7 +46,9 @@ __global__ __launch_bounds__(256) void shade_kernel(const lbvh_hit* __restrict__
     if (i >= count) return;
     const float4 hr = reinterpret_cast<const float4*>(hits)[i];
     const float dist = hr.x, u = hr.z, v = hr.w;
-    const uint32_t tri = __float_as_uint(hr.y);
+    // the record lbvh_path_bounce leaves for an ended path, {MAX_FLOAT, 0xFFFFFFFF, 0, 0}, is a miss like {MAX_FLOAT, 0, 0, 0}: triangle 0
+    const uint32_t word = __float_as_uint(hr.y);
+    const uint32_t tri = (dist == LBVH_MAX_FLOAT && word == 0xFFFFFFFFu) ? 0u : word;
     const float4* tp = reinterpret_cast<const float4*>(&tris[tri]);     // Raytracing.compute:178
     const float4 uv0 = tp[3], uv1 = tp[4];       // a_uv, b_uv | c_uv, pad
     const float4 an = tp[5], bn = tp[6], cn = tp[7];
@@ -56,8 +62,12 @@ __global__ __launch_bounds__(256) void shade_kernel(const lbvh_hit* __restrict__
     const float lambert = fmaxf(0.4f, (light_dir * nx + light_dir * ny) + light_dir * nz);
     const float4 c = sample_bilinear_clamp(tex, tex_w, tex_h, tu, tv);  // :183
     const float alpha = dist != LBVH_MAX_FLOAT ? 1.0f : 0.0f;           // :184
-    const __half h0 = __float2half_rn(c.x * lambert), h1 = __float2half_rn(c.y * lambert),
-                 h2 = __float2half_rn(c.z * lambert), h3 = __float2half_rn(alpha);
+    // colour * lambert rounds to fp32 FIRST and to half second, as the oracle does.  Left to itself the compiler folds a product
+    // and its conversion into one v_fma_mixlo_f16 — one rounding, not two — whatever -ffp-contract says: another half wherever
+    // the fp32 product lands on a tie between two halves.  The empty asm keeps the product a value of its own.
+    float r0 = c.x * lambert, r1 = c.y * lambert, r2 = c.z * lambert;
+    asm volatile("" : "+v"(r0), "+v"(r1), "+v"(r2));
+    const __half h0 = __float2half_rn(r0), h1 = __float2half_rn(r1), h2 = __float2half_rn(r2), h3 = __float2half_rn(alpha);
     ushort4 o;
     o.x = __half_as_ushort(h0); o.y = __half_as_ushort(h1); o.z = __half_as_ushort(h2); o.w = __half_as_ushort(h3);
     reinterpret_cast<ushort4*>(out)[i] = o;
