@@ -156,6 +156,8 @@ public static class LbvhNative
         ulong capacity);
     [DllImport(Lib)] public static extern int lbvh_gather_within_distance(IntPtr ctx, IntPtr dQueries, UIntPtr count, ref Scene scene, IntPtr dOffsets,
         IntPtr dTris, ulong capacity);
+    [DllImport(Lib)] public static extern int lbvh_gather_hits(IntPtr ctx, IntPtr dRays, UIntPtr count, ref Scene scene, IntPtr dOffsets, IntPtr dHits,
+        ulong capacity);
     [DllImport(Lib)] public static extern int lbvh_count_hits(IntPtr ctx, IntPtr dRays, UIntPtr count, ref Scene scene, IntPtr dCounts);
     [DllImport(Lib)] public static extern int lbvh_point_crossings(IntPtr ctx, IntPtr dPoints, UIntPtr count, float[] hDirs, uint nDirs, ref Scene scene,
         IntPtr dParity);

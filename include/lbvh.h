@@ -785,6 +785,49 @@ lbvh_status lbvh_point_crossings(lbvh_context* ctx, const lbvh_point_query* d_po
 lbvh_status lbvh_trace_k_closest(lbvh_context* ctx, const lbvh_ray* d_rays, size_t count, uint32_t k,
                                  const lbvh_scene* h_scene, lbvh_hit* d_hits, uint32_t* d_found);
 
+/* EVERY hit along `count` rays as a CSR list — the "all" form of the ray queries (nearest: lbvh_trace_closest, any:
+ * lbvh_trace_occluded, how many: lbvh_count_hits, first k <= 32: lbvh_trace_k_closest) —, over the same scene by the four-wide walk
+ * of lbvh_count_hits, in the count -> device-side scan -> fill shape of the overlap queries.
+ *   Active ray, T = min(t_max, LBVH_MAX_FLOAT) and the candidate set are exactly those of lbvh_trace_closest and lbvh_count_hits:
+ *   the own-box slab test with entry e, Moeller-Trumbore with the reference's rejections, t >= e, t_min < t < T.  A NaN t is never
+ *   a candidate; an inactive ray (!(t_min < t_max), NaN bounds included) has none and is never walked.
+ * Output:
+ *   d_offsets: count + 1 words of 64 bits.  d_offsets[q] = the number of candidates of rays 0 .. q-1, d_offsets[count] = the
+ *   total M.  Always written in full, whatever `capacity` is.
+ *   d_hits, `capacity` records of 16 bytes: segment q = d_hits[d_offsets[q] .. d_offsets[q+1]) = {t, tri, u, v} of every candidate
+ *   of ray q, each exactly once; the four words are the ones lbvh_trace_closest would write if that candidate were the nearest.
+ *   THE ORDER INSIDE A SEGMENT IS THE WALK'S AND IS NOT PART OF THE CONTRACT (the convention of the overlap queries: the four-wide
+ *   form does not keep children in range order, and the walk enters boxes in slot order, not by distance).  Every record carries
+ *   its t: sort a segment by (t, tri) if an order is needed — two candidates of a ray never share a triangle index, so that
+ *   order is canonical.  A device-side sort of segments of unbounded length is not part of this call; the first 32 in order
+ *   are lbvh_trace_k_closest.
+ *   Overflow: no record at index >= capacity is ever written; every segment with d_offsets[q+1] <= capacity is complete; records
+ *   below `capacity` that belong to a segment which does not fit are unspecified.  The call never waits on the host and returns
+ *   LBVH_OK in both cases: the caller reads d_offsets[count] (one 8-byte download) to learn whether everything fitted and, if
+ *   not, what to allocate.
+ *   Count-only form: capacity == 0 writes the offsets and walks once (d_hits may be NULL); otherwise the scene is walked twice
+ *   (count, device-side scan, fill).  d_hits == NULL with capacity > 0 is LBVH_ERR_INVALID_ARG.
+ * Hence, for every ray q with m = d_offsets[q+1] - d_offsets[q]: m == lbvh_count_hits' d_counts[q]; m >= 1 exactly when
+ * lbvh_trace_occluded gives 1; the least element of segment q by (t, tri) is lbvh_trace_closest's record (the miss record when
+ * m == 0); and its first min(k, m) elements by (t, tri) are the first min(k, m) records of row q of lbvh_trace_k_closest, word
+ * for word (t compared as fp32 values, as there).
+ * Why the list does not depend on the walk: the argument at lbvh_count_hits.  Every ancestor of a candidate's leaf passes its
+ * slab test with entry <= e <= t < T, and the walk skips only boxes that the ray misses or whose entry is > T; the bound is T
+ * from the first step to the last — nothing shrinks —, and nothing is pruned on a box's exit distance.  Each triangle is
+ * exactly one leaf, so each candidate is met exactly once.  The count walk and the fill walk are the same kernel making the same
+ * decisions, so a segment never outgrows its slot.
+ * Needs the derived traversal scene (lbvh_build_fast_scene; a stale one is LBVH_ERR_INVALID_ARG), is asynchronous on the
+ * context's stream, and uses the context's ray scratch: it drops the path tracer's live-path list (see lbvh_path_bounce); a
+ * failed growth of that scratch is LBVH_ERR_OUT_OF_MEMORY with nothing written.  count == 0 is a no-op: nothing is enqueued and
+ * no buffer is touched, d_offsets[0] included.  Rejected: NULL ctx / d_rays / h_scene / d_offsets, d_rays or d_hits not 16-byte
+ * aligned, d_offsets not 8-byte aligned, count > 2^32 - 1.  Four-wide walk only (lbvh_debug_ray_walker does not apply);
+ * lbvh_debug_ray_waves, lbvh_debug_ray_stack_split, lbvh_debug_ray_stack_limit and lbvh_ray_stats_target apply as to the overlap
+ * queries (the stats of both walks are added: the full form reports twice the count-only form's).
+ * One ray per lane: a ray with very many hits keeps its lane busy while the rest of its wave idles — many ordinary rays run far
+ * better than a few that cross thousands of layers. */
+lbvh_status lbvh_gather_hits(lbvh_context* ctx, const lbvh_ray* d_rays, size_t count, const lbvh_scene* h_scene,
+                             uint64_t* d_offsets, lbvh_hit* d_hits, uint64_t capacity);
+
 /* A moving sphere: 32 bytes, arrays 16-byte aligned: lbvh_ray with the radius where t_min is. */
 typedef struct lbvh_sphere_ray {
     float origin[3]; float radius;
@@ -871,7 +914,7 @@ lbvh_status lbvh_path_scatter(lbvh_context* ctx, const lbvh_scene* h_scene, cons
  * lbvh_path_bounce on the same d_states / d_hits listed as live (a list kept by the context).  Every library call that writes
  * into those buffers drops the list (lbvh_path_begin, lbvh_trace_rays, a primary trace into any part of d_hits,
  * lbvh_buffer_upload / _fill_u32 / _free), and so does lbvh_trace_forget — and so do lbvh_trace_closest,
- * lbvh_trace_occluded, lbvh_closest_point_query, lbvh_within_distance, lbvh_count_hits, lbvh_point_crossings, lbvh_box_overlaps, lbvh_gather_within_distance, lbvh_k_closest_points, lbvh_trace_k_closest, lbvh_sphere_cast and lbvh_sphere_cast_any, whatever buffers they are given, since they use the same ray scratch; then every state is scanned again.  What the library
+ * lbvh_trace_occluded, lbvh_closest_point_query, lbvh_within_distance, lbvh_count_hits, lbvh_point_crossings, lbvh_box_overlaps, lbvh_gather_within_distance, lbvh_k_closest_points, lbvh_trace_k_closest, lbvh_gather_hits, lbvh_sphere_cast and lbvh_sphere_cast_any, whatever buffers they are given, since they use the same ray scratch; then every state is scanned again.  What the library
  * cannot see is a write of the CALLER's own (a kernel or hipMemcpy that revives or ends paths, Russian roulette): between two
  * consecutive bounces of a frame d_states and d_hits must not be written from outside the library — or lbvh_trace_forget must be
  * called after such a write. */

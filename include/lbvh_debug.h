@@ -52,7 +52,7 @@ lbvh_status lbvh_debug_ray_stack_split(lbvh_context* ctx, uint32_t lds_entries);
 
 /* Test hook: the largest grid of a per-lane walk (every entry point that walks one ray, point, sphere or box per lane:
  * lbvh_trace_rays, the bounces, lbvh_trace_closest / _occluded, lbvh_count_hits, the point queries, lbvh_k_closest_points,
- * lbvh_trace_k_closest, the sphere casts, lbvh_point_crossings and both walks of the overlap queries).  Such a launch is
+ * lbvh_trace_k_closest, the sphere casts, lbvh_point_crossings and both walks of the overlap queries and of lbvh_gather_hits).  Such a launch is
  * min(8192, ceil(count / 64)) one-wave workgroups; each wave owns a run of ceil(count / waves) consecutive queries and refills a
  * lane from the run when the lane's query is finished.  0 (default): 8192.  n >= 1: at most n waves, so the runs of a small call
  * get long and every lane is refilled many times (tests/test_walk_refill.py: 1 500 queries on one wave, about 23 refills per
@@ -68,7 +68,8 @@ lbvh_status lbvh_debug_ray_waves(lbvh_context* ctx, uint32_t max_waves);
  * per (point, direction) pair), and lbvh_k_closest_points (`rays` = active queries; the triangle lines read again for the
  * survivors' u, v at the end of a query are not counted: with k = 1 the three counters equal lbvh_closest_point_query's),
  * and lbvh_trace_k_closest in the same way (`rays` = active rays; with k = 1 the counters equal the four-wide lbvh_trace_closest's),
- * and lbvh_sphere_cast / lbvh_sphere_cast_any (`rays` = active casts). */
+ * and lbvh_sphere_cast / lbvh_sphere_cast_any (`rays` = active casts), and both walks of lbvh_gather_hits (`rays` = active rays: the
+ * full form adds twice what the count-only form adds). */
 typedef struct lbvh_ray_stats {
     uint64_t rays;
     uint64_t node_fetches;
@@ -87,7 +88,7 @@ lbvh_status lbvh_debug_ray_stack_limit(lbvh_context* ctx, uint32_t deep_entries)
  * a step's two fetches in flight at once: few live rays, the launch is the chain of its longest), 2: that kernel for every
  * launch, 0: the binary nodes the packet walk uses.  Hit records do not depend on it (ties go to the lower triangle index
  * on all three); nor do the counts of lbvh_count_hits, which this hook steers as it steers lbvh_trace_closest.  The point
- * queries (lbvh_closest_point_query, lbvh_within_distance, lbvh_point_crossings, lbvh_k_closest_points), lbvh_trace_k_closest and the sphere casts have the four-wide walk only: this hook
+ * queries (lbvh_closest_point_query, lbvh_within_distance, lbvh_point_crossings, lbvh_k_closest_points), lbvh_trace_k_closest, lbvh_gather_hits and the sphere casts have the four-wide walk only: this hook
  * leaves them alone.  lbvh_debug_ray_stack_split and lbvh_debug_ray_stack_limit apply to them as to the four-wide ray walk. */
 lbvh_status lbvh_debug_ray_walker(lbvh_context* ctx, uint32_t walker);
 

@@ -1636,6 +1636,120 @@ __global__ __launch_bounds__(256) void overlap_offsets_kernel(const uint32_t* __
     }
 }
 
+// ---- every hit along a ray as a CSR list (lbvh_gather_hits, include/lbvh.h) --------------------------------------------
+// The frame of overlap_wide_kernel (count walk, the scan above, fill walk: the same kernel, the same decisions, so a segment can
+// never outgrow its slot) around the ray arithmetic of trace_rays_wide_kernel<true, kCount>: load_plain_ray's activity test and T,
+// the slab tests against the FIXED bound T, ray_fast_triangle, hit_counts(dist, entry) and lo < dist < T.  Nothing shrinks and no
+// order is promised, so the ordering network of the ray walkers is not needed: the first passing inner slot is entered, the
+// others wait on the stack.  A candidate's record is the float4 put_hit would write were it the nearest: {dist, tri, u, v}.
+// A kernel of its own and not a fourth walk_query: a new parameter would move the arguments of every other instantiation.
+template <bool FILL, bool STATS>
+__global__ __launch_bounds__(64) void gather_hits_wide_kernel(const lbvh_ray* __restrict__ rays, uint32_t total,
+                                                              const lbvh_wide_node* __restrict__ wide,
+                                                              const lbvh_fast_node* __restrict__ lines,
+                                                              uint32_t* __restrict__ counts,            // !FILL: candidates of ray k
+                                                              const uint64_t* __restrict__ offsets,     // FILL: where segment k starts
+                                                              lbvh_hit* __restrict__ hits, uint64_t capacity,
+                                                              uint32_t* __restrict__ deep,     // [gridDim.x][kWideStackDeep][64]
+                                                              uint32_t lds_depth,              // <= kWideStackLds
+                                                              uint32_t deep_cap,               // <= kWideStackDeep
+                                                              uint32_t* __restrict__ fault, lbvh_ray_stats* stats)
+{
+    __shared__ uint32_t s_stack[kWideStackLds][LBVH_WAVE];
+    uint32_t* my_deep = deep + (size_t)blockIdx.x * (kWideStackDeep * LBVH_WAVE) + threadIdx.x;
+    const uint32_t lane = threadIdx.x;
+    const uint32_t run = max((total + gridDim.x - 1) / gridDim.x, 32u);
+    uint32_t next = blockIdx.x * run;
+    if (next >= total) return;
+    const uint32_t end = min(next + run, total);
+    uint32_t n_rays = 0, n_steps = 0, n_tris = 0;
+
+    bool active = false;
+    uint32_t i = 0;
+    ray_t ray = {};
+    float lo = 0.0f, T = LBVH_MAX_FLOAT;
+    uint32_t n_found = 0, sp = 0, node = 0;
+    uint64_t pos = 0;                                    // FILL: where this lane's next record goes
+    auto push = [&](uint32_t ref) {
+        if (sp < lds_depth) { s_stack[sp][lane] = ref; sp++; }
+        else if (sp < lds_depth + deep_cap) { my_deep[(sp - lds_depth) * LBVH_WAVE] = ref; sp++; }
+        // a dropped entry would be a silently short segment: report it, as the other walkers do (lbvh_debug_ray_stack_limit provokes it)
+        else __hip_atomic_store(fault, LBVH_FAULT_RAY_STACK, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    };
+    for (;;) {
+        const uint64_t idle = __ballot(!active);
+        if (idle != 0 && next < end) {
+            if (!active) {
+                const uint32_t k = next + mbcnt64(idle);
+                if (k < end) {
+                    i = k;
+                    const float4* r = reinterpret_cast<const float4*>(&rays[k]);
+                    const float4 o = r[0], d = r[1];
+                    ray.ox = o.x; ray.oy = o.y; ray.oz = o.z;
+                    ray.dx = d.x; ray.dy = d.y; ray.dz = d.z;
+                    ray.ix = 1.0f / d.x; ray.iy = 1.0f / d.y; ray.iz = 1.0f / d.z;
+                    lo = o.w;
+                    T = fminf(d.w, LBVH_MAX_FLOAT);              // candidates lie in (t_min, T)
+                    active = o.w < d.w;                          // load_plain_ray's rule: false for NaN bounds too
+                    sp = 0; node = 0;
+                    if constexpr (FILL) { if (active) pos = offsets[k]; }      // (reloaded at every refill: a lane serves many rays)
+                    else { n_found = 0; if (!active) counts[k] = 0u; }
+                    if (STATS && active) n_rays++;
+                }
+            }
+            next += (uint32_t)__popcll(idle);
+        }
+        if (!__any(active) && next >= end) break;
+        if (active) {
+            if (STATS) n_steps++;
+            const float4* w = reinterpret_cast<const float4*>(&wide[node]);
+            const float4 lox = w[0], loy = w[1], loz = w[2], hix = w[3], hiy = w[4], hiz = w[5];
+            const uint4 ref = reinterpret_cast<const uint4*>(w)[6];
+            float t0, t1, t2, t3;
+            const bool h0 = wide_box(lox.x, loy.x, loz.x, hix.x, hiy.x, hiz.x, ray, t0) && !(t0 > T) && ref.x != kWideEmpty;
+            const bool h1 = wide_box(lox.y, loy.y, loz.y, hix.y, hiy.y, hiz.y, ray, t1) && !(t1 > T) && ref.y != kWideEmpty;
+            const bool h2 = wide_box(lox.z, loy.z, loz.z, hix.z, hiy.z, hiz.z, ray, t2) && !(t2 > T) && ref.z != kWideEmpty;
+            const bool h3 = wide_box(lox.w, loy.w, loz.w, hix.w, hiy.w, hiz.w, ray, t3) && !(t3 > T) && ref.w != kWideEmpty;
+            const uint32_t hit = (h0 ? 1u : 0u) | (h1 ? 2u : 0u) | (h2 ? 4u : 0u) | (h3 ? 8u : 0u);
+            const uint32_t leaf = (ref.x >> 31) | ((ref.y >> 31) << 1) | ((ref.z >> 31) << 2) | ((ref.w >> 31) << 3);
+            uint32_t leaves = hit & leaf, inner = hit & ~leaf;
+            while (leaves != 0u) {
+                const uint32_t k = (uint32_t)__builtin_ctz(leaves);
+                leaves &= leaves - 1u;
+                if (STATS) n_tris++;
+                float4 v0, v1, v2;
+                unpack_fast_triangle(reinterpret_cast<const float4*>(&lines[pick4(ref, k) & 0x7FFFFFFFu]), v0, v1, v2);
+                float u = 0.0f, v = 0.0f;
+                const float dist = ray_fast_triangle(ray, v0, v1, v2, u, v);
+                const float entry = k == 0u ? t0 : (k == 1u ? t1 : (k == 2u ? t2 : t3));
+                if (dist > lo && hit_counts(dist, entry) && dist < T) {
+                    if constexpr (FILL) {
+                        if (pos < capacity) reinterpret_cast<float4*>(hits)[pos] = make_float4(dist, v0.w, u, v);   // never at or beyond the capacity
+                        pos++;
+                    } else {
+                        n_found++;
+                    }
+                }
+            }
+            if (inner != 0u) {
+                node = pick4(ref, (uint32_t)__builtin_ctz(inner));
+                inner &= inner - 1u;
+                while (inner != 0u) {
+                    push(pick4(ref, (uint32_t)__builtin_ctz(inner)));
+                    inner &= inner - 1u;
+                }
+            } else if (sp != 0) {
+                sp--;
+                node = sp < lds_depth ? s_stack[sp][lane] : my_deep[(sp - lds_depth) * LBVH_WAVE];
+            } else {
+                if constexpr (!FILL) counts[i] = n_found;
+                active = false;
+            }
+        }
+    }
+    if (STATS) add_ray_stats(stats, n_rays, n_steps, n_tris);
+}
+
 // ---- crossing parities of points along fixed directions (lbvh_point_crossings, include/lbvh.h) -------------------------
 // The directions travel by value in the kernel's arguments; a lane reads the one it walks next from there.
 struct crossing_dirs { float d[LBVH_CROSSING_MAX_DIRS][3]; };
@@ -2187,6 +2301,39 @@ lbvh_status lbvh_gather_within_distance(lbvh_context* ctx, const lbvh_point_quer
                                         uint64_t* d_offsets, uint32_t* d_tris, uint64_t capacity)
 {
     return overlap_queries<false>(ctx, d_queries, count, h_scene, d_offsets, d_tris, capacity, "lbvh_gather_within_distance");
+}
+
+// overlap_queries<>'s shape with the ray walk: count walk -> the same three scan kernels -> fill walk, the counts and the tile sums
+// in the same two slices of the ray scratch, all on the context's stream, no host wait.  Four-wide walk only.
+lbvh_status lbvh_gather_hits(lbvh_context* ctx, const lbvh_ray* d_rays, size_t count, const lbvh_scene* h_scene, uint64_t* d_offsets,
+                             lbvh_hit* d_hits, uint64_t capacity)
+{
+    if (!ctx) return LBVH_ERR_INVALID_ARG;
+    if (count == 0) return LBVH_OK;
+    LBVH_REQUIRE(ctx, d_rays != nullptr && h_scene != nullptr && d_offsets != nullptr);
+    LBVH_REQUIRE(ctx, d_hits != nullptr || capacity == 0);
+    LBVH_REQUIRE(ctx, ((uintptr_t)d_rays & 15) == 0 && ((uintptr_t)d_offsets & 7) == 0 && ((uintptr_t)d_hits & 15) == 0);
+    LBVH_REQUIRE(ctx, count <= 0xFFFFFFFFull);
+    walk_launch w;
+    const lbvh_status rc = begin_walk(ctx, h_scene, count, "lbvh_gather_hits", true, &w);
+    if (rc != LBVH_OK) return rc;
+    const uint32_t total = (uint32_t)count;
+    uint32_t* counts = ray_list(ctx, count, 0);
+    uint64_t* tile_sums = (uint64_t*)ray_list(ctx, count, 1);
+    const uint32_t n_tiles = total / kScanTile + 1u;           // the tiles cover total + 1 offsets (sizes: see overlap_queries)
+    LBVH_LAUNCH_STATS(ctx, ctx->ray_stats, (gather_hits_wide_kernel<false, STATS>), dim3(w.waves), dim3(LBVH_WAVE), d_rays, total, w.wn, ctx->fast_nodes,
+                      counts, (const uint64_t*)nullptr, (lbvh_hit*)nullptr, (uint64_t)0, w.deep, w.lds, w.deep_cap, ctx->fault_dev, ctx->ray_stats);
+    if (n_tiles > 1u) {
+        LBVH_LAUNCH(ctx, overlap_tile_sums_kernel, dim3(n_tiles), dim3(256), (const uint32_t*)counts, total, tile_sums);
+        LBVH_LAUNCH(ctx, overlap_scan_sums_kernel, dim3(1), dim3(1024), tile_sums, n_tiles);
+    }
+    LBVH_LAUNCH(ctx, overlap_offsets_kernel, dim3(n_tiles), dim3(256), (const uint32_t*)counts, total,
+                n_tiles > 1u ? (const uint64_t*)tile_sums : (const uint64_t*)nullptr, d_offsets);
+    if (capacity != 0)
+        LBVH_LAUNCH_STATS(ctx, ctx->ray_stats, (gather_hits_wide_kernel<true, STATS>), dim3(w.waves), dim3(LBVH_WAVE), d_rays, total, w.wn, ctx->fast_nodes,
+                          (uint32_t*)nullptr, (const uint64_t*)d_offsets, d_hits, capacity, w.deep, w.lds, w.deep_cap, ctx->fault_dev, ctx->ray_stats);
+    LBVH_HIP_TRY(ctx, hipGetLastError());
+    return LBVH_OK;
 }
 
 lbvh_status lbvh_animate(lbvh_context* ctx, const lbvh_triangle* d_rest, uint32_t n, const uint32_t* d_body,

@@ -488,6 +488,43 @@ class RaytracingMeshDrawer:
         N.check(self.ctx.handle, N.lib.lbvh_trace_k_closest(self.ctx.handle, rays.device, rays.size, k, C.byref(s), hits.device,
                                                             found.device if found is not None else None))
 
+    def gather_hits(self, rays, offsets, hits=None):
+        """Every hit along each ray of `rays` (layouts.RAY) as a CSR list on the caller's buffers: `offsets` (uint64 DataBuffer, at
+        least rays.size + 1 entries) always complete; `hits` (layouts.HIT DataBuffer, its size is the capacity) receives the
+        records, segment q = hits[offsets[q] : offsets[q + 1]], IN NO PARTICULAR ORDER (each record carries its t).  hits=None
+        counts only.  Nothing is written beyond hits.size; offsets[rays.size] says what was needed.  Asynchronous."""
+        if rays.dtype != L.RAY or offsets.dtype != np.uint64 or offsets.size < rays.size + 1 or \
+                (hits is not None and hits.dtype != L.HIT):
+            raise ValueError("rays must be a DataBuffer of layouts.RAY, offsets one of uint64 with one entry more, hits one of layouts.HIT or None")
+        s = self.container.scene()
+        N.check(self.ctx.handle, N.lib.lbvh_gather_hits(self.ctx.handle, rays.device, rays.size, C.byref(s), offsets.device,
+                                                        hits.device if hits is not None else None, hits.size if hits is not None else 0))
+
+    def all_hits(self, rays, sort=False, min_capacity=1):
+        """Convenience: count -> one 8-byte download -> allocate -> fill.  Returns (offsets, hits): host arrays, uint64[rays.size + 1]
+        and layouts.HIT[total].  The library leaves a segment in the order of its walk; sort=True orders every segment by
+        (t, tri) HERE, ON THE HOST (np.lexsort over the downloaded records — not a device sort)."""
+        count = rays.size
+        offsets = DataBuffer(self.ctx, count + 1, np.uint64)
+        try:
+            self.gather_hits(rays, offsets)
+            last = np.zeros(1, dtype=np.uint64)
+            N.check(self.ctx.handle, N.lib.lbvh_buffer_download(self.ctx.handle, last.ctypes.data_as(C.c_void_p),
+                                                                C.c_void_p(offsets.device.value + 8 * count), 8))
+            total = int(last[0])
+            hits = DataBuffer(self.ctx, max(total, int(min_capacity)), L.HIT)
+            try:
+                self.gather_hits(rays, offsets, hits)
+                off, rec = offsets.get_data().copy(), hits.get_data()[:total].copy()
+            finally:
+                hits.dispose()
+        finally:
+            offsets.dispose()
+        if sort:
+            segment = np.repeat(np.arange(count), np.diff(off).astype(np.int64))
+            rec = rec[np.lexsort((rec["tri"], rec["t"], segment))]
+        return off, rec
+
     def point_crossings(self, queries, parity, dirs=None):
         """Bit j of the uint32 DataBuffer `parity` for each point of `queries` (layouts.POINT_QUERY; max_dist2 is not read): the
         parity of the number of triangles the ray from the point along dirs[j] crosses (dirs: up to 32 rows of x, y, z;

@@ -27,6 +27,11 @@
 //                                                with k records per ray; prints the sum of the found counts, how many rows are
 //                                                full, the sum of all 32-bit words of the count * k records (mod 2^64) and the
 //                                                first rows
+//     lbvh_driver gather <n_rays> [t_max]        the 4 096 triangles and the rays of `khits`; GatherHits twice (count only, one
+//                                                8-byte read, fill); every segment sorted by (t, tri) on the host; prints the total,
+//                                                how many segments are non-empty, the sum of all 32-bit words of the records (mod
+//                                                2^64), the sum of (position + 1) * triangle index over the sorted list (mod 2^64) and
+//                                                the first segments
 //     lbvh_driver sweep [n | file.obj] [count] [radius]  the mesh of `points` and `count` spheres of the given radius (default 1 %
 //                                                of the largest extent) from points around the mesh's box towards points inside
 //                                                it (t = 1 at the target, t_max 2); SphereCast and SphereCastAny; prints how
@@ -455,6 +460,71 @@ static int khits_main(int argc, char** argv)
     return 0;
 }
 
+static int gather_main(int argc, char** argv)
+{
+    const size_t count = argc > 2 ? (size_t)strtoull(argv[2], nullptr, 10) : 65536;
+    const float t_max = argc > 3 ? (float)atof(argv[3]) : INFINITY;
+    try {
+        const std::vector<lbvh_triangle> mesh = random_mesh(4096);
+        float lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
+        for (const auto& t : mesh)
+            for (int a = 0; a < 3; a++) {
+                lo[a] = std::fmin(lo[a], std::fmin(t.a[a], std::fmin(t.b[a], t.c[a])));
+                hi[a] = std::fmax(hi[a], std::fmax(t.a[a], std::fmax(t.b[a], t.c[a])));
+            }
+        lbvh::Context ctx(0);
+        lbvh::RaytracingMeshDrawer drawer(ctx, mesh);
+        drawer.Awake();
+        lbvh::DataBuffer<lbvh_ray> rays(ctx, count);
+        uint64_t seed = 3;
+        for (auto& r : rays.LocalBuffer()) {
+            for (int a = 0; a < 3; a++) {
+                const float grow = 0.25f * (hi[a] - lo[a]);
+                r.origin[a] = uniform(seed, lo[a] - grow, hi[a] + grow);
+                r.dir[a] = uniform(seed, lo[a], hi[a]) - r.origin[a];
+            }
+            r.t_min = 0.0f;
+            r.t_max = t_max;
+        }
+        rays.Sync();
+        lbvh::DataBuffer<uint64_t> offsets(ctx, count + 1);
+        drawer.GatherHits(rays, offsets);                       // count only
+        offsets.GetData();
+        const uint64_t total = offsets.LocalBuffer()[count];
+        lbvh::DataBuffer<lbvh_hit> hits(ctx, std::max<size_t>((size_t)total, 1));
+        drawer.GatherHits(rays, offsets, &hits);
+        offsets.GetData();
+        hits.GetData();
+        const std::vector<uint64_t>& off = offsets.LocalBuffer();
+        std::vector<lbvh_hit>& rec = hits.LocalBuffer();
+        size_t nonempty = 0;
+        for (size_t q = 0; q < count; q++) {                    // the library promises no order inside a segment: (t, tri) here
+            std::sort(rec.begin() + off[q], rec.begin() + off[q + 1],
+                      [](const lbvh_hit& x, const lbvh_hit& y) { return x.t < y.t || (x.t == y.t && x.tri < y.tri); });
+            nonempty += off[q + 1] > off[q];
+        }
+        uint64_t word_sum = 0, weighted_sum = 0;
+        for (uint64_t i = 0; i < total; i++) {
+            uint32_t w[4];
+            std::memcpy(w, &rec[i], sizeof w);
+            word_sum += (uint64_t)w[0] + w[1] + w[2] + w[3];
+            weighted_sum += (i + 1) * (uint64_t)rec[i].tri;
+        }
+        std::printf("{\"triangles\": %zu, \"rays\": %zu, \"total\": %llu, \"nonempty\": %zu, \"word_sum\": %llu, \"weighted_sum\": %llu, \"rows\": [",
+                    mesh.size(), count, (unsigned long long)off[count], nonempty, (unsigned long long)word_sum, (unsigned long long)weighted_sum);
+        for (size_t q = 0; q < std::min<size_t>(count, 3); q++) {
+            std::printf("%s[", q ? ", " : "");
+            for (uint64_t j = off[q]; j < off[q + 1]; j++) std::printf("%s[%.9g, %u]", j != off[q] ? ", " : "", rec[j].t, rec[j].tri);
+            std::printf("]");
+        }
+        std::printf("]}\n");
+    } catch (const std::exception& e) {
+        std::fprintf(stderr, "%s\n", e.what());
+        return 1;
+    }
+    return 0;
+}
+
 static int sweep_main(int argc, char** argv)
 {
     const size_t count = argc > 3 ? (size_t)strtoull(argv[3], nullptr, 10) : 65536;
@@ -652,6 +722,7 @@ int main(int argc, char** argv)
     if (argc > 1 && std::strcmp(argv[1], "points") == 0) return points_main(argc, argv);
     if (argc > 1 && std::strcmp(argv[1], "knn") == 0) return knn_main(argc, argv);
     if (argc > 1 && std::strcmp(argv[1], "khits") == 0) return khits_main(argc, argv);
+    if (argc > 1 && std::strcmp(argv[1], "gather") == 0) return gather_main(argc, argv);
     if (argc > 1 && std::strcmp(argv[1], "sweep") == 0) return sweep_main(argc, argv);
     if (argc > 1 && std::strcmp(argv[1], "overlaps") == 0) return overlaps_main(argc, argv);
     if (argc > 1 && std::strcmp(argv[1], "rays") == 0) return rays_main(argc, argv);

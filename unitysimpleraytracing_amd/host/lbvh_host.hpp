@@ -400,6 +400,16 @@ public:
         check(ctx_.get(), lbvh_trace_k_closest(ctx_.get(), (const lbvh_ray*)rays.DeviceBuffer(), rays.Size(), k, &s,
                                                (lbvh_hit*)hits.DeviceBuffer(), found ? (uint32_t*)found->DeviceBuffer() : nullptr));
     }
+    // EVERY hit along each ray, as a CSR list (lbvh_gather_hits; asynchronous): offsets[q] .. offsets[q + 1] = ray q's segment of
+    // `hits` ({t, tri, u, v} records, IN NO PARTICULAR ORDER: sort a segment by (t, tri) if an order is needed).  hits == nullptr
+    // counts only; otherwise its size is the capacity: nothing is written beyond it, and offsets[rays.Size()] says what was needed.
+    void GatherHits(const DataBuffer<lbvh_ray>& rays, DataBuffer<uint64_t>& offsets, DataBuffer<lbvh_hit>* hits = nullptr)
+    {
+        if (offsets.Size() < rays.Size() + 1) throw Error(LBVH_ERR_INVALID_ARG, "GatherHits: offsets needs one entry more than rays");
+        const lbvh_scene s = container_->Scene();
+        check(ctx_.get(), lbvh_gather_hits(ctx_.get(), (const lbvh_ray*)rays.DeviceBuffer(), rays.Size(), &s, (uint64_t*)offsets.DeviceBuffer(),
+                                           hits ? (lbvh_hit*)hits->DeviceBuffer() : nullptr, hits ? (uint64_t)hits->Size() : 0));
+    }
     void PointCrossings(const DataBuffer<lbvh_point_query>& points, const std::vector<float>& dirs, DataBuffer<uint32_t>& parity)
     {
         if (parity.Size() < points.Size()) throw Error(LBVH_ERR_INVALID_ARG, "PointCrossings: fewer parity words than points");
