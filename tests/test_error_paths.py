@@ -13,24 +13,11 @@ import pytest
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import oracle as O                                                   # noqa: E402
+from query_support import H, N, words                                # noqa: E402
 from unitysimpleraytracing_amd import layouts as L, scenes           # noqa: E402
 
 pytestmark = pytest.mark.gpu
 ERR_OUT_OF_MEMORY = -2
-
-
-def N():
-    from unitysimpleraytracing_amd import _native
-    return _native
-
-
-def H():
-    from unitysimpleraytracing_amd import host
-    return host
-
-
-def words(a):
-    return np.ascontiguousarray(a).view(np.uint32)
 
 
 def sort_once(c, keys, vals):

@@ -19,14 +19,11 @@ import pytest
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import oracle as O                                                   # noqa: E402
+from query_support import words                                      # noqa: E402
 from unitysimpleraytracing_amd import layouts as L, scenes           # noqa: E402
 
 FIXTURE = json.load(open(os.path.join(ROOT, "tests", "golden", "fuzz_cases_seed101.json")))
 CASES = FIXTURE["cases"]
-
-
-def words(a):
-    return np.ascontiguousarray(a).view(np.uint32)
 
 
 def make_scene(kind, n, p):

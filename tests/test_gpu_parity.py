@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 
 import oracle as O
+from query_support import H, N, _random_ray_states, _splitmix_mesh, words
 from unitysimpleraytracing_amd import layouts as L
 from unitysimpleraytracing_amd import scenes
 
@@ -18,26 +19,12 @@ F = 0xFFFFFFFF
 GOLDEN = os.path.join(os.path.dirname(__file__), "golden")
 
 
-def H():
-    from unitysimpleraytracing_amd import host
-    return host
-
-
-def N():
-    from unitysimpleraytracing_amd import _native
-    return _native
-
-
 def up(ctx, arr, dtype=None):
     a = np.ascontiguousarray(arr, dtype=dtype)
     b = H().DataBuffer(ctx, max(len(a), 1), a.dtype)
     b.local[: len(a)] = a
     b.sync()
     return b
-
-
-def words(a):
-    return np.ascontiguousarray(a).view(np.uint32)
 
 
 # ---- a-2..a-5 sort ---------------------------------------------------------------------------------
@@ -1406,32 +1393,6 @@ def test_derived_scene_is_keyed_to_its_scene(ctx):
 
 # ---- the compiled-language host layer (C++ classes over the C ABI) ---------------------------------------------
 
-def _splitmix_mesh(n):
-    """The mesh lbvh_driver.cpp generates (SplitMix64, seed 1)."""
-    mask = (1 << 64) - 1
-    state = 1
-    out = np.zeros((n, 3, 3), dtype=np.float32)          # [tri, vertex(a,b,c), axis]
-
-    def nxt():
-        nonlocal state
-        state = (state + 0x9E3779B97F4A7C15) & mask
-        z = state
-        z = ((z ^ (z >> 30)) * 0xBF58476D1CE4E5B9) & mask
-        z = ((z ^ (z >> 27)) * 0x94D049BB133111EB) & mask
-        return z ^ (z >> 31)
-
-    def uni(lo, hi):
-        return np.float32(lo) + np.float32(hi - lo) * np.float32((nxt() >> 40) * (1.0 / 16777216.0))
-
-    for i in range(n):
-        for k in range(3):
-            c = uni(-100.0, 100.0)
-            out[i, 0, k] = c
-            out[i, 1, k] = np.float32(c + uni(-2.0, 2.0))
-            out[i, 2, k] = np.float32(c + uni(-2.0, 2.0))
-    return out
-
-
 def test_cpp_host_driver_matches_oracle():
     """BASELINE config 1 through host/lbvh_host.hpp (Awake + Update in the reference's call order)."""
     import json
@@ -1753,24 +1714,6 @@ def test_secondary_rays_deep_stack_in_device_memory(ctx, lds_entries):
     oh = O.trace_rays(b, st, 1e-3, threads=8)
     assert (frames[1]["t"] == oh["t"]).all()
     pt.drawer.on_destroy()
-
-
-def _random_ray_states(tris, count, seed):
-    """Rays that start inside the scene's box (on and off its surfaces), random directions — a few of them along the
-    axes (zero direction components: infinite inverse directions in the slab test)."""
-    rng = np.random.default_rng(seed)
-    pts = np.concatenate([tris["a"][:, :3], tris["b"][:, :3], tris["c"][:, :3]]).astype(np.float32)
-    lo, hi = pts.min(axis=0), pts.max(axis=0)
-    st = np.zeros(count, dtype=L.PATH_STATE)
-    st["origin"] = (lo + (hi - lo) * rng.random((count, 3))).astype(np.float32)
-    on_surface = rng.random(count) < 0.5                       # half of the rays leave a triangle's first vertex
-    st["origin"][on_surface] = tris["a"][rng.integers(0, len(tris), on_surface.sum()), :3]
-    d = rng.normal(size=(count, 3))
-    axis = rng.random(count) < 0.1
-    d[axis] = np.eye(3)[rng.integers(0, 3, axis.sum())] * rng.choice([-1.0, 1.0], axis.sum())[:, None]
-    st["dir"] = (d / np.linalg.norm(d, axis=1, keepdims=True)).astype(np.float32)
-    st["alive"] = (rng.random(count) < 0.9).astype(np.uint32)
-    return st
 
 
 @pytest.mark.parametrize("scene", ["torus", "soup", "duplicates", "two", "three", "seven"])

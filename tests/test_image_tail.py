@@ -12,6 +12,7 @@ import pytest
 
 import image_reference as R
 import oracle as O
+from query_support import H, N, words
 from unitysimpleraytracing_amd import layouts as L
 from unitysimpleraytracing_amd import scenes
 
@@ -19,20 +20,6 @@ gpu = pytest.mark.gpu
 GUARD = 0xA5C35A3C
 SLACK = 64
 COUNTS = (1, 255, 256, 257, 256 + 37)
-
-
-def H():
-    from unitysimpleraytracing_amd import host
-    return host
-
-
-def N():
-    from unitysimpleraytracing_amd import _native
-    return _native
-
-
-def words(a):
-    return np.ascontiguousarray(a).view(np.uint32)
 
 
 def up(ctx, arr):

@@ -14,6 +14,8 @@ import pytest
 
 import k_closest_reference as K
 import point_reference as R
+from query_support import (assert_rows, driver_mesh, driver_points, golden, H, L, library_boxes, make_queries, _mixed_points,
+                           mixed_queries, N, pack, padded_boxes, positions, row_words, words)
 from unitysimpleraytracing_amd import scenes
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -21,56 +23,6 @@ F = np.float32
 INF = F(np.inf)
 KMAX = 32
 KS = [1, 2, 5, 8, 32]
-
-
-def H():
-    from unitysimpleraytracing_amd import host
-    return host
-
-
-def N():
-    from unitysimpleraytracing_amd import _native
-    return _native
-
-
-def L():
-    from unitysimpleraytracing_amd import layouts
-    return layouts
-
-
-def words(a):
-    return np.ascontiguousarray(a).view(np.uint32)
-
-
-def row_words(a):
-    """(rows, k) records -> (rows, 4 * k) words"""
-    a = np.ascontiguousarray(a)
-    return a.view(np.uint32).reshape(a.shape[0], -1)
-
-
-def golden(name):
-    return np.load(os.path.join(ROOT, "tests", "golden", name + ".npz"))["triangles"]
-
-
-def positions(tris):
-    return (np.ascontiguousarray(tris[k][:, :3], dtype=F) for k in "abc")
-
-
-def padded_boxes(a, b, c):
-    """scene.triangle_aabb as the Morton stage makes it (CPU tests only; the GPU tests take the boxes the library produced)"""
-    return np.minimum(np.minimum(a, b), c) - F(0.001), np.maximum(np.maximum(a, b), c) + F(0.001)
-
-
-def make_queries(p, r2):
-    q = np.zeros(len(p), dtype=R.POINT_QUERY)
-    q["p"], q["max_dist2"] = p, r2
-    return q
-
-
-def pack(a, b, c):
-    t = np.zeros(len(a), dtype=L().TRIANGLE)
-    t["a"][:, :3], t["b"][:, :3], t["c"][:, :3] = a, b, c
-    return t
 
 
 NONE_WORDS = words(np.array([R.NONE]))
@@ -132,20 +84,6 @@ def test_reference_known_answers_duplicated_triangle():
     assert r.found.tolist() == [0, 2]
 
 
-def _mixed_points(a, b, c, count, rng):
-    """a third each: uniform in the vertices' box grown by 25 % per side, on triangle surfaces, exactly at vertices"""
-    lo, hi = np.minimum(np.minimum(a, b), c).min(axis=0), np.maximum(np.maximum(a, b), c).max(axis=0)
-    ext = hi - lo
-    third = count // 3
-    k = rng.integers(0, len(a), third)
-    w = rng.dirichlet((1, 1, 1), third)
-    kv = rng.integers(0, len(a), count - 2 * third)
-    corner = rng.integers(0, 3, count - 2 * third)
-    return np.concatenate([rng.uniform(lo - 0.25 * ext, hi + 0.25 * ext, (third, 3)),
-                           a[k] * w[:, :1] + b[k] * w[:, 1:2] + c[k] * w[:, 2:],
-                           np.stack([a, b, c])[corner, kv]]).astype(F)
-
-
 def test_reference_k1_is_the_closest_point_reference():
     a, b, c = positions(golden("viking_room"))
     lo, hi = padded_boxes(a, b, c)
@@ -198,48 +136,12 @@ class KPoints:
             b.dispose()
 
 
-def assert_rows(got, found, ref, what=""):
-    bad = np.nonzero((row_words(got) != row_words(ref.records)).any(axis=1))[0]
-    assert len(bad) == 0, (what, bad[:10], got[bad[:2]], ref.records[bad[:2]])
-    assert (found == ref.found).all(), (what, np.nonzero(found != ref.found)[0][:10])
-
-
-def library_boxes(drawer):
-    n = drawer.container.triangles_length
-    box = drawer.container.triangle_aabb.get_data()[:n]
-    return box["min"].copy(), box["max"].copy()
-
-
 def _scene(name):
     if name == "random":
         return scenes.random_triangles(4096)
     if name == "grid":
         return scenes.grid_scene()
     return golden(name)
-
-
-def mixed_queries(a, b, c, lo, hi, count, seed):
-    """One interleaved buffer: _mixed_points shuffled, a tenth of them overwritten by copies of other points; then the radii, from
-    the reference's unbounded answer d of each point: +inf, MAX_FLOAT, a finite radius around the scene's typical nearest
-    distance, exactly d, the next float above and below d, 0, -1, NaN."""
-    rng = np.random.default_rng(seed)
-    pts = _mixed_points(a, b, c, count, rng)[rng.permutation(count)]
-    dup = rng.random(count) < 0.1
-    pts[dup] = pts[rng.integers(0, count, dup.sum())]
-    unb = R.reference(make_queries(pts, INF), a, b, c, lo, hi)
-    d = unb.records["dist2"]
-    typical = F(np.median(d[d > 0]))
-    kind = rng.integers(0, 9, count)
-    r2 = np.full(count, INF, dtype=F)
-    r2 = np.where(kind == 1, R.MAX_FLOAT, r2)
-    r2 = np.where(kind == 2, (typical * rng.uniform(0.25, 4.0, count)).astype(F), r2)
-    r2 = np.where(kind == 3, d, r2)
-    r2 = np.where(kind == 4, np.nextafter(d, INF), r2)
-    r2 = np.where(kind == 5, np.nextafter(d, -INF), r2)
-    r2 = np.where(kind == 6, F(0.0), r2)
-    r2 = np.where(kind == 7, F(-1.0), r2)
-    r2 = np.where(kind == 8, F(np.nan), r2).astype(F)
-    return make_queries(pts, r2), unb
 
 
 _CASES = {}
@@ -598,27 +500,6 @@ def test_9_path_tracer_frame_undisturbed_by_a_k_nearest_call_between_bounces(ctx
     pt.drawer.on_destroy()
 
 
-def _splitmix():
-    mask = (1 << 64) - 1
-    state = 0
-
-    def seed(s):
-        nonlocal state
-        state = s
-
-    def nxt():
-        nonlocal state
-        state = (state + 0x9E3779B97F4A7C15) & mask
-        z = state
-        z = ((z ^ (z >> 30)) * 0xBF58476D1CE4E5B9) & mask
-        z = ((z ^ (z >> 27)) * 0x94D049BB133111EB) & mask
-        return z ^ (z >> 31)
-
-    def uni(lo, hi):
-        return F(lo) + F(F(hi) - F(lo)) * F((nxt() >> 40) * (1.0 / 16777216.0))
-    return seed, uni
-
-
 @pytest.mark.gpu
 @pytest.mark.parametrize("radius", [None, 12.0])
 def test_10_cpp_host_driver_knn_matches_the_python_host(ctx, radius):
@@ -627,24 +508,8 @@ def test_10_cpp_host_driver_knn_matches_the_python_host(ctx, radius):
     n, count, k = 4096, 20000, 8
     args = [exe, "knn", str(k), str(n), str(count)] + ([str(radius)] if radius is not None else [])
     res = json.loads(subprocess.run(args, check=True, capture_output=True, text=True).stdout)
-    seed, uni = _splitmix()
-    seed(1)                                                            # the mesh lbvh_driver.cpp generates (SplitMix64, seed 1)
-    pos = np.zeros((n, 3, 3), dtype=F)
-    for i in range(n):
-        for j in range(3):
-            ctr = uni(-100.0, 100.0)
-            pos[i, 0, j] = ctr
-            pos[i, 1, j] = F(ctr + uni(-2.0, 2.0))
-            pos[i, 2, j] = F(ctr + uni(-2.0, 2.0))
-    tris = np.zeros(n, dtype=L().TRIANGLE)
-    tris["a"], tris["b"], tris["c"] = pos[:, 0], pos[:, 1], pos[:, 2]
-    lo, hi = pos.min(axis=(0, 1)), pos.max(axis=(0, 1))
-    seed(2)
-    pts = np.zeros((count, 3), dtype=F)
-    for i in range(count):
-        for j in range(3):
-            grow = F(0.25) * F(hi[j] - lo[j])
-            pts[i, j] = uni(F(lo[j] - grow), F(hi[j] + grow))
+    tris, pos, lo, hi = driver_mesh(n)                                 # the mesh lbvh_driver.cpp generates (SplitMix64, seed 1)
+    pts = driver_points(lo, hi, count)                                 # and its points (seed 2)
     queries = make_queries(pts, INF if radius is None else F(radius) * F(radius))
     d = H().RaytracingMeshDrawer(ctx, tris).awake()
     rows = H().DataBuffer(ctx, count * k, L().CLOSEST_POINT)

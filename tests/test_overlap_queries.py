@@ -18,28 +18,14 @@ import pytest
 
 import overlap_reference as V
 import point_reference as R
-from test_point_queries import SCENES, _scene, library_boxes, make_queries, padded_boxes, positions, golden
+from test_point_queries import SCENES, _scene
+from query_support import golden, H, L, library_boxes, make_queries, N, padded_boxes, positions
 from unitysimpleraytracing_amd import scenes
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 F = np.float32
 INF = F(np.inf)
 COUNT = 2048
-
-
-def H():
-    from unitysimpleraytracing_amd import host
-    return host
-
-
-def N():
-    from unitysimpleraytracing_amd import _native
-    return _native
-
-
-def L():
-    from unitysimpleraytracing_amd import layouts
-    return layouts
 
 
 # ---- the query sets of O1 / O2 ---------------------------------------------------------------------------------------------

@@ -16,50 +16,13 @@ import numpy as np
 import pytest
 
 import point_reference as R
+from query_support import (driver_mesh, driver_points, golden, H, L, library_boxes, make_queries, _mixed_points, mixed_queries,
+                           N, padded_boxes, positions, words)
 from unitysimpleraytracing_amd import scenes
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 F = np.float32
 INF = F(np.inf)
-
-
-def H():
-    from unitysimpleraytracing_amd import host
-    return host
-
-
-def N():
-    from unitysimpleraytracing_amd import _native
-    return _native
-
-
-def L():
-    from unitysimpleraytracing_amd import layouts
-    return layouts
-
-
-def words(a):
-    return np.ascontiguousarray(a).view(np.uint32)
-
-
-def golden(name):
-    return np.load(os.path.join(ROOT, "tests", "golden", name + ".npz"))["triangles"]
-
-
-def positions(tris):
-    return (np.ascontiguousarray(tris[k][:, :3], dtype=F) for k in "abc")
-
-
-def padded_boxes(a, b, c):
-    """scene.triangle_aabb as the Morton stage makes it: min / max of the vertices, 0.001 per side (CPU tests only; the GPU tests
-    take the boxes the library produced)"""
-    return np.minimum(np.minimum(a, b), c) - F(0.001), np.maximum(np.maximum(a, b), c) + F(0.001)
-
-
-def make_queries(p, r2):
-    q = np.zeros(len(p), dtype=R.POINT_QUERY)
-    q["p"], q["max_dist2"] = p, r2
-    return q
 
 
 # ---- CPU: the surface in every host ------------------------------------------------------------------------------------
@@ -112,20 +75,6 @@ def test_csharp_structs_have_the_c_field_order():
 
 
 # ---- CPU: the restatement against float64 and against cases with known answers ---------------------------------------------
-
-def _mixed_points(a, b, c, count, rng):
-    """a third each: uniform in the vertices' box grown by 25 % per side, on triangle surfaces, exactly at vertices"""
-    lo, hi = np.minimum(np.minimum(a, b), c).min(axis=0), np.maximum(np.maximum(a, b), c).max(axis=0)
-    ext = hi - lo
-    third = count // 3
-    k = rng.integers(0, len(a), third)
-    w = rng.dirichlet((1, 1, 1), third)
-    kv = rng.integers(0, len(a), count - 2 * third)
-    corner = rng.integers(0, 3, count - 2 * third)
-    return np.concatenate([rng.uniform(lo - 0.25 * ext, hi + 0.25 * ext, (third, 3)),
-                           a[k] * w[:, :1] + b[k] * w[:, 1:2] + c[k] * w[:, 2:],
-                           np.stack([a, b, c])[corner, kv]]).astype(F)
-
 
 @pytest.mark.parametrize("name", ["viking_room", "example_object3"])
 def test_reference_agrees_with_its_float64_evaluation(name):
@@ -241,42 +190,12 @@ class Points:
             b.dispose()
 
 
-def library_boxes(drawer):
-    n = drawer.container.triangles_length
-    box = drawer.container.triangle_aabb.get_data()[:n]
-    return box["min"].copy(), box["max"].copy()
-
-
 def _scene(name):
     if name == "random":
         return scenes.random_triangles(4096)
     if name == "grid":
         return scenes.grid_scene()
     return golden(name)
-
-
-def mixed_queries(a, b, c, lo, hi, count, seed):
-    """One interleaved buffer: _mixed_points shuffled, a tenth of them overwritten by copies of other points; then the radii, from
-    the reference's unbounded answer d of each point: +inf, MAX_FLOAT, a finite radius around the scene's typical nearest
-    distance, exactly d, the next float above and below d, 0, -1, NaN."""
-    rng = np.random.default_rng(seed)
-    pts = _mixed_points(a, b, c, count, rng)[rng.permutation(count)]
-    dup = rng.random(count) < 0.1
-    pts[dup] = pts[rng.integers(0, count, dup.sum())]
-    unb = R.reference(make_queries(pts, INF), a, b, c, lo, hi)
-    d = unb.records["dist2"]
-    typical = F(np.median(d[d > 0]))
-    kind = rng.integers(0, 9, count)
-    r2 = np.full(count, INF, dtype=F)
-    r2 = np.where(kind == 1, R.MAX_FLOAT, r2)
-    r2 = np.where(kind == 2, (typical * rng.uniform(0.25, 4.0, count)).astype(F), r2)
-    r2 = np.where(kind == 3, d, r2)
-    r2 = np.where(kind == 4, np.nextafter(d, INF), r2)
-    r2 = np.where(kind == 5, np.nextafter(d, -INF), r2)
-    r2 = np.where(kind == 6, F(0.0), r2)
-    r2 = np.where(kind == 7, F(-1.0), r2)
-    r2 = np.where(kind == 8, F(np.nan), r2).astype(F)
-    return make_queries(pts, r2), unb
 
 
 _CASES = {}
@@ -592,27 +511,6 @@ def test_scale_one_million_triangles_one_million_queries(ctx):
     assert (words(got[sub]) == words(ref.records)).all() and (flags[sub] == ref.flags).all()
 
 
-def _splitmix():
-    mask = (1 << 64) - 1
-    state = 0
-
-    def seed(s):
-        nonlocal state
-        state = s
-
-    def nxt():
-        nonlocal state
-        state = (state + 0x9E3779B97F4A7C15) & mask
-        z = state
-        z = ((z ^ (z >> 30)) * 0xBF58476D1CE4E5B9) & mask
-        z = ((z ^ (z >> 27)) * 0x94D049BB133111EB) & mask
-        return z ^ (z >> 31)
-
-    def uni(lo, hi):
-        return F(lo) + F(F(hi) - F(lo)) * F((nxt() >> 40) * (1.0 / 16777216.0))
-    return seed, uni
-
-
 @pytest.mark.gpu
 @pytest.mark.parametrize("radius", [None, 3.0])
 def test_cpp_host_driver_points_matches_the_python_host(ctx, radius):
@@ -621,24 +519,8 @@ def test_cpp_host_driver_points_matches_the_python_host(ctx, radius):
     n, count = 4096, 20000
     args = [exe, "points", str(n), str(count)] + ([str(radius)] if radius is not None else [])
     res = json.loads(subprocess.run(args, check=True, capture_output=True, text=True).stdout)
-    seed, uni = _splitmix()
-    seed(1)                                                            # the mesh lbvh_driver.cpp generates (SplitMix64, seed 1)
-    pos = np.zeros((n, 3, 3), dtype=F)
-    for i in range(n):
-        for k in range(3):
-            ctr = uni(-100.0, 100.0)
-            pos[i, 0, k] = ctr
-            pos[i, 1, k] = F(ctr + uni(-2.0, 2.0))
-            pos[i, 2, k] = F(ctr + uni(-2.0, 2.0))
-    tris = np.zeros(n, dtype=L().TRIANGLE)
-    tris["a"], tris["b"], tris["c"] = pos[:, 0], pos[:, 1], pos[:, 2]
-    lo, hi = pos.min(axis=(0, 1)), pos.max(axis=(0, 1))
-    seed(2)
-    pts = np.zeros((count, 3), dtype=F)
-    for i in range(count):
-        for k in range(3):
-            grow = F(0.25) * F(hi[k] - lo[k])
-            pts[i, k] = uni(F(lo[k] - grow), F(hi[k] + grow))
+    tris, _, lo, hi = driver_mesh(n)                                   # the mesh lbvh_driver.cpp generates (SplitMix64, seed 1)
+    pts = driver_points(lo, hi, count)                                 # and its points (seed 2)
     queries = make_queries(pts, INF if radius is None else F(radius) * F(radius))
     d = H().RaytracingMeshDrawer(ctx, tris).awake()
     q = Points(ctx, d, queries)

@@ -10,6 +10,7 @@ import ctypes as C
 import numpy as np
 import pytest
 
+from query_support import H, L, N, words
 from unitysimpleraytracing_amd import scenes
 
 pytestmark = pytest.mark.gpu
@@ -18,25 +19,6 @@ COUNT = 130
 K = 3
 POISON = 0x7FC0DEAD
 F = np.float32
-
-
-def H():
-    from unitysimpleraytracing_amd import host
-    return host
-
-
-def N():
-    from unitysimpleraytracing_amd import _native
-    return _native
-
-
-def L():
-    from unitysimpleraytracing_amd import layouts
-    return layouts
-
-
-def words(a):
-    return np.ascontiguousarray(a).view(np.uint32)
 
 
 def _rays(tris, rng):

@@ -16,26 +16,13 @@ import numpy as np
 import pytest
 
 import oracle as O
+from query_support import H, make_rays, N, _random_ray_states, _splitmix_mesh, words
 from unitysimpleraytracing_amd import layouts as L
 from unitysimpleraytracing_amd import scenes
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 MISS = np.array([(L.MAX_FLOAT, 0, 0.0, 0.0)], dtype=L.HIT)[0]
 LIGHT = np.array([0.0, 250.0, 150.0], dtype=np.float32)       # outside the scene box of every scene here
-
-
-def H():
-    from unitysimpleraytracing_amd import host
-    return host
-
-
-def N():
-    from unitysimpleraytracing_amd import _native
-    return _native
-
-
-def words(a):
-    return np.ascontiguousarray(a).view(np.uint32)
 
 
 # ---- CPU: the surface in every host ------------------------------------------------------------------------------------
@@ -90,13 +77,6 @@ def test_csharp_ray_struct_has_the_c_field_order():
 
 # ---- the oracle's expectation ----------------------------------------------------------------------------------------
 
-def make_rays(origin, direction, t_min, t_max):
-    r = np.zeros(len(origin), dtype=L.RAY)
-    r["origin"], r["dir"] = origin, direction
-    r["t_min"], r["t_max"] = t_min, t_max
-    return r
-
-
 def active(rays):
     return rays["t_min"] < rays["t_max"]
 
@@ -125,24 +105,6 @@ def expect_closest(rays, unbounded):                                   # E2
 
 def expect_occluded(rays, unbounded):                                  # E3
     return (active(rays) & (unbounded["t"] < np.minimum(rays["t_max"], L.MAX_FLOAT))).astype(np.uint32)
-
-
-def _random_ray_states(tris, count, seed):
-    """Rays that start inside the scene's box (on and off its surfaces), random unit directions, a tenth of them along an
-    axis (zero components: infinite inverse directions in the slab test); 90 % alive."""
-    rng = np.random.default_rng(seed)
-    pts = np.concatenate([tris["a"][:, :3], tris["b"][:, :3], tris["c"][:, :3]]).astype(np.float32)
-    lo, hi = pts.min(axis=0), pts.max(axis=0)
-    st = np.zeros(count, dtype=L.PATH_STATE)
-    st["origin"] = (lo + (hi - lo) * rng.random((count, 3))).astype(np.float32)
-    on_surface = rng.random(count) < 0.5
-    st["origin"][on_surface] = tris["a"][rng.integers(0, len(tris), on_surface.sum()), :3]
-    d = rng.normal(size=(count, 3))
-    axis = rng.random(count) < 0.1
-    d[axis] = np.eye(3)[rng.integers(0, 3, axis.sum())] * rng.choice([-1.0, 1.0], axis.sum())[:, None]
-    st["dir"] = (d / np.linalg.norm(d, axis=1, keepdims=True)).astype(np.float32)
-    st["alive"] = (rng.random(count) < 0.9).astype(np.uint32)
-    return st
 
 
 def _scene(name):
@@ -507,32 +469,6 @@ def test_cfg2_full_frame_shadow_rays_and_cfg5_first_bounce(ctx):
     assert (words(q.closest()) == words(ref)).all()
     q.dispose()
     pt.drawer.on_destroy()
-
-
-def _splitmix_mesh(n):
-    """The mesh lbvh_driver.cpp generates (SplitMix64, seed 1)."""
-    mask = (1 << 64) - 1
-    state = 1
-    out = np.zeros((n, 3, 3), dtype=np.float32)
-
-    def nxt():
-        nonlocal state
-        state = (state + 0x9E3779B97F4A7C15) & mask
-        z = state
-        z = ((z ^ (z >> 30)) * 0xBF58476D1CE4E5B9) & mask
-        z = ((z ^ (z >> 27)) * 0x94D049BB133111EB) & mask
-        return z ^ (z >> 31)
-
-    def uni(lo, hi):
-        return np.float32(lo) + np.float32(hi - lo) * np.float32((nxt() >> 40) * (1.0 / 16777216.0))
-
-    for i in range(n):
-        for k in range(3):
-            c = uni(-100.0, 100.0)
-            out[i, 0, k] = c
-            out[i, 1, k] = np.float32(c + uni(-2.0, 2.0))
-            out[i, 2, k] = np.float32(c + uni(-2.0, 2.0))
-    return out
 
 
 @pytest.mark.gpu

@@ -12,50 +12,13 @@ import pytest
 
 import point_reference as P
 import sweep_reference as S
+from query_support import driver_mesh, driver_rays, golden, H, L, library_boxes, N, pack, padded_boxes, positions, words
 from unitysimpleraytracing_amd import scenes
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 F = np.float32
 INF = F(np.inf)
 RADII = (0.005, 0.02, 0.1)                  # of the scene's extent
-
-
-def H():
-    from unitysimpleraytracing_amd import host
-    return host
-
-
-def N():
-    from unitysimpleraytracing_amd import _native
-    return _native
-
-
-def L():
-    from unitysimpleraytracing_amd import layouts
-    return layouts
-
-
-def words(a):
-    return np.ascontiguousarray(a).view(np.uint32)
-
-
-def golden(name):
-    return np.load(os.path.join(ROOT, "tests", "golden", name + ".npz"))["triangles"]
-
-
-def positions(tris):
-    return tuple(np.ascontiguousarray(tris[k][:, :3], dtype=F) for k in "abc")
-
-
-def padded_boxes(a, b, c):
-    """scene.triangle_aabb as the Morton stage makes it (CPU tests only; the GPU tests take the boxes the library produced)"""
-    return np.minimum(np.minimum(a, b), c) - F(0.001), np.maximum(np.maximum(a, b), c) + F(0.001)
-
-
-def pack(a, b, c):
-    t = np.zeros(len(a), dtype=L().TRIANGLE)
-    t["a"][:, :3], t["b"][:, :3], t["c"][:, :3] = a, b, c
-    return t
 
 
 def make_casts(origin, direction, radius, t_max=INF):
@@ -331,12 +294,6 @@ class Casts:
 def assert_records(got, ref, what=""):
     bad = np.nonzero((words(got).reshape(-1, 4) != words(ref.records).reshape(-1, 4)).any(axis=1))[0]
     assert len(bad) == 0, (what, len(bad), bad[:10], got[bad[:3]], ref.records[bad[:3]])
-
-
-def library_boxes(drawer):
-    n = drawer.container.triangles_length
-    box = drawer.container.triangle_aabb.get_data()[:n]
-    return box["min"].copy(), box["max"].copy()
 
 
 _CASES = {}
@@ -623,43 +580,6 @@ def test_path_tracer_frame_undisturbed_by_a_cast_between_bounces(ctx):
     pt.drawer.on_destroy()
 
 
-def _splitmix():
-    mask = (1 << 64) - 1
-    state = 0
-
-    def seed(s):
-        nonlocal state
-        state = s
-
-    def nxt():
-        nonlocal state
-        state = (state + 0x9E3779B97F4A7C15) & mask
-        z = state
-        z = ((z ^ (z >> 30)) * 0xBF58476D1CE4E5B9) & mask
-        z = ((z ^ (z >> 27)) * 0x94D049BB133111EB) & mask
-        return z ^ (z >> 31)
-
-    def uni(lo, hi):
-        return F(lo) + F(F(hi) - F(lo)) * F((nxt() >> 40) * (1.0 / 16777216.0))
-    return seed, uni
-
-
-def _driver_mesh(n):
-    """the mesh lbvh_driver.cpp generates for a number (SplitMix64, seed 1)"""
-    seed, uni = _splitmix()
-    seed(1)
-    pos = np.zeros((n, 3, 3), dtype=F)
-    for i in range(n):
-        for j in range(3):
-            ctr = uni(-100.0, 100.0)
-            pos[i, 0, j] = ctr
-            pos[i, 1, j] = F(ctr + uni(-2.0, 2.0))
-            pos[i, 2, j] = F(ctr + uni(-2.0, 2.0))
-    tris = np.zeros(n, dtype=L().TRIANGLE)
-    tris["a"], tris["b"], tris["c"] = pos[:, 0], pos[:, 1], pos[:, 2]
-    return tris
-
-
 def _driver_casts(tris, count, radius):
     """the casts `lbvh_driver sweep` makes from the mesh's box (SplitMix64, seed 3: origin and target drawn axis by axis; t_max 2);
     radius None: the driver's default, 1 % of the largest extent in fp32"""
@@ -667,15 +587,7 @@ def _driver_casts(tris, count, radius):
     lo, hi = pos.min(axis=(0, 1)), pos.max(axis=(0, 1))
     if radius is None:
         radius = F(0.01) * F(max(F(hi[j] - lo[j]) for j in range(3)))
-    seed, uni = _splitmix()
-    seed(3)
-    origin = np.zeros((count, 3), dtype=F)
-    direction = np.zeros((count, 3), dtype=F)
-    for i in range(count):
-        for j in range(3):
-            grow = F(0.25) * F(hi[j] - lo[j])
-            origin[i, j] = uni(F(lo[j] - grow), F(hi[j] + grow))
-            direction[i, j] = F(uni(lo[j], hi[j]) - origin[i, j])
+    origin, direction = driver_rays(lo, hi, count)
     return make_casts(origin, direction, F(radius), F(2.0))
 
 
@@ -696,7 +608,7 @@ def test_cpp_host_driver_sweep_matches_the_python_host(ctx, tmp_path, mesh, radi
         assert tris.tobytes() == np.ascontiguousarray(golden("viking_room"), dtype=L().TRIANGLE).tobytes()      # the golden scene
     else:
         what = "4096"
-        tris = _driver_mesh(4096)
+        tris = driver_mesh(4096)[0]
     args = [exe, "sweep", what, str(count)] + ([str(radius)] if radius is not None else [])
     res = json.loads(subprocess.run(args, check=True, capture_output=True, text=True).stdout)
     casts = _driver_casts(tris, count, radius)

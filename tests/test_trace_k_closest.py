@@ -13,6 +13,8 @@ import pytest
 
 import k_hits_reference as K
 import ray_reference as R
+from query_support import (aimed_rays, assert_rows, driver_mesh, driver_rays, H, L, library_boxes, make_rays, mixed_rays_of, N,
+                           pack, padded_boxes, positions, row_words, scene_rays, stacked_sheets, words)
 from unitysimpleraytracing_amd import scenes
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -20,53 +22,6 @@ F = np.float32
 INF = F(np.inf)
 KMAX = 32
 KS = [1, 2, 5, 8, 32]
-
-
-def H():
-    from unitysimpleraytracing_amd import host
-    return host
-
-
-def N():
-    from unitysimpleraytracing_amd import _native
-    return _native
-
-
-def L():
-    from unitysimpleraytracing_amd import layouts
-    return layouts
-
-
-def words(a):
-    return np.ascontiguousarray(a).view(np.uint32)
-
-
-def row_words(a):
-    """(rows, k) records -> (rows, 4 * k) words"""
-    a = np.ascontiguousarray(a)
-    return a.view(np.uint32).reshape(a.shape[0], -1)
-
-
-def positions(tris):
-    return (np.ascontiguousarray(tris[k][:, :3], dtype=F) for k in "abc")
-
-
-def padded_boxes(a, b, c):
-    """scene.triangle_aabb as the Morton stage makes it (CPU tests only; the GPU tests take the boxes the library produced)"""
-    return np.minimum(np.minimum(a, b), c) - F(0.001), np.maximum(np.maximum(a, b), c) + F(0.001)
-
-
-def make_rays(origin, direction, t_min, t_max):
-    r = np.zeros(len(origin), dtype=R.RAY)
-    r["origin"], r["dir"] = origin, direction
-    r["t_min"], r["t_max"] = t_min, t_max
-    return r
-
-
-def pack(a, b, c):
-    t = np.zeros(len(a), dtype=L().TRIANGLE)
-    t["a"][:, :3], t["b"][:, :3], t["c"][:, :3] = a, b, c
-    return t
 
 
 MISS_WORDS = words(np.array([R.MISS]))
@@ -150,23 +105,6 @@ def test_reference_orders_by_t_then_index():
     assert r.records["t"][0, :4].tolist() == [0.5, 2.5, 2.5, 4.5]
 
 
-def scene_rays(a, b, c, count, rng):
-    """rays that start in the scene's box (half of them on a surface), random directions, a tenth along an axis (zero
-    components: infinite inverse directions in the slab test), a third scaled by 0.25 .. 8"""
-    pts = np.concatenate([a, b, c])
-    lo, hi = pts.min(axis=0), pts.max(axis=0)
-    origin = (lo + (hi - lo) * rng.random((count, 3))).astype(F)
-    on = rng.random(count) < 0.5
-    origin[on] = a[rng.integers(0, len(a), on.sum())]
-    d = rng.normal(size=(count, 3))
-    axis = rng.random(count) < 0.1
-    d[axis] = np.eye(3)[rng.integers(0, 3, axis.sum())] * rng.choice([-1.0, 1.0], axis.sum())[:, None]
-    d = (d / np.linalg.norm(d, axis=1, keepdims=True)).astype(F)
-    scale = rng.random(count) < 0.33
-    d[scale] *= rng.uniform(0.25, 8.0, scale.sum()).astype(F)[:, None]
-    return origin, d
-
-
 def test_reference_k1_is_the_closest_hit_reference():
     tris = scenes.tiled_torus(nu=16, nv=10, grid=2)
     a, b, c = positions(tris)
@@ -184,87 +122,12 @@ def test_reference_k1_is_the_closest_hit_reference():
 
 # ---- scenes and ray sets ---------------------------------------------------------------------------------------------------
 
-def stacked_sheets():
-    """an 8 x 8 grid of quads (128 triangles) over a 16 x 16 square, repeated at 40 z-levels one unit apart, vertex heights
-    jittered by +-0.2, the triangle order permuted: 5 120 triangles, rays along z cross up to 40 of them"""
-    rng = np.random.default_rng(40)
-    gx, gy = np.meshgrid(np.arange(9) * 2.0, np.arange(9) * 2.0, indexing="ij")
-    a, b, c = [], [], []
-    for level in range(40):
-        z = level + rng.uniform(-0.2, 0.2, (9, 9))
-        v = np.stack([gx, gy, z], axis=-1)
-        p00, p10, p01, p11 = v[:-1, :-1], v[1:, :-1], v[:-1, 1:], v[1:, 1:]
-        a += [p00.reshape(-1, 3), p11.reshape(-1, 3)]
-        b += [p10.reshape(-1, 3), p01.reshape(-1, 3)]
-        c += [p11.reshape(-1, 3), p00.reshape(-1, 3)]
-    a, b, c = (np.concatenate(x).astype(F) for x in (a, b, c))
-    order = rng.permutation(len(a))
-    return a[order], b[order], c[order]
-
-
-def aimed_rays(a, b, c, count, rng, along_z=0.6):
-    """rays from outside the scene's box at random surface points: `along_z` of the directions biased toward the z axis, the
-    lengths scaled by 0.25 .. 4 (t in units of dir).  -> (origin, dir, the t at which each ray reaches its point)"""
-    k = rng.integers(0, len(a), count)
-    w = rng.dirichlet((1, 1, 1), count)
-    target = a[k] * w[:, :1] + b[k] * w[:, 1:2] + c[k] * w[:, 2:]
-    d = rng.normal(size=(count, 3))
-    z = rng.random(count) < along_z
-    d[z] *= np.array([0.15, 0.15, 1.0])
-    d /= np.linalg.norm(d, axis=1, keepdims=True)
-    pts = np.concatenate([a, b, c])
-    reach = 1.25 * np.linalg.norm(pts.max(axis=0) - pts.min(axis=0))       # farther than the box's diagonal: outside it
-    origin = target - d * reach
-    scale = rng.uniform(0.25, 4.0, count)
-    return origin.astype(F), (d * scale[:, None]).astype(F), (reach / scale).astype(F)
-
-
-def mix_ranges(origin, d, rng, open_reference):
-    """One interleaved buffer, as mixed_rays of tests/test_ray_queries.py: per-ray t_min in {1e-3, 0, 0.5, -3e38}; then, from the
-    open range's candidates of each ray (open_reference(rays) -> a k = KMAX Result) and one of them picked at random, t_j: open,
-    MAX_FLOAT, a finite t_max around the row's span, t_max = t_j / the float above / below, t_min = t_j / the float below /
-    above, t_min >= t_max, NaN bounds."""
-    count = len(origin)
-    t_min = rng.choice(np.array([1e-3, 0.0, 0.5, -3.0e38], dtype=F), count)
-    rays = make_rays(origin, d, t_min, INF)
-    unb = open_reference(rays)
-    hit = unb.found > 0
-    j = (rng.random(count) * np.maximum(unb.found, 1)).astype(np.int64)
-    rows = np.arange(count)
-    tj = unb.records["t"][rows, j]
-    last = unb.records["t"][rows, np.maximum(unb.found.astype(np.int64), 1) - 1]
-    kind = rng.integers(0, 12, count)
-    span = np.where(hit, last, F(50.0))
-    t_max = np.full(count, INF, dtype=F)
-    t_max = np.where(kind == 2, R.MAX_FLOAT, t_max)
-    t_max = np.where(kind == 3, (span * rng.uniform(0.3, 1.5, count)).astype(F), t_max)
-    t_max = np.where((kind == 4) & hit, tj, t_max)
-    t_max = np.where((kind == 5) & hit, np.nextafter(tj, INF), t_max)
-    t_max = np.where((kind == 6) & hit, np.nextafter(tj, -INF), t_max)
-    t_min = np.where((kind == 7) & hit, tj, t_min)
-    t_min = np.where((kind == 8) & hit, np.nextafter(tj, -INF), t_min)
-    t_min = np.where((kind == 9) & hit, np.nextafter(tj, INF), t_min)
-    empty = rng.random(count) < 0.5
-    t_max = np.where((kind == 10) & empty, t_min, t_max)
-    t_max = np.where((kind == 10) & ~empty, np.minimum(t_min, F(0.0)) - F(1.0), t_max)
-    t_min = np.where((kind == 11) & empty, F(np.nan), t_min)
-    t_max = np.where((kind == 11) & ~empty, F(np.nan), t_max)
-    rays["t_min"], rays["t_max"] = t_min.astype(F), t_max.astype(F)
-    return rays
-
-
 def scene_positions(name):
     if name == "sheets":
         return stacked_sheets()
     if name == "torus":
         return tuple(positions(scenes.tiled_torus(nu=24, nv=16, grid=2)))
     return tuple(positions(scenes.random_triangles(4096)))
-
-
-def mixed_rays_of(name, a, b, c, lo, hi):
-    rng = np.random.default_rng(7 + len(a))
-    origin, d = aimed_rays(a, b, c, 1500, rng)[:2] if name == "sheets" else scene_rays(a, b, c, 1500, rng)
-    return mix_ranges(origin, d, rng, lambda rays: K.reference(rays, a, b, c, lo, hi, KMAX))
 
 
 def exercised(rays, ref32):
@@ -333,18 +196,6 @@ class KRays:
     def dispose(self):
         for b in (self.rays, self.rows, self.found, self.hits, self.flags):
             b.dispose()
-
-
-def assert_rows(got, found, ref, what=""):
-    bad = np.nonzero((row_words(got) != row_words(ref.records)).any(axis=1))[0]
-    assert len(bad) == 0, (what, bad[:10], got[bad[:2]], ref.records[bad[:2]])
-    assert (found == ref.found).all(), (what, np.nonzero(found != ref.found)[0][:10])
-
-
-def library_boxes(drawer):
-    n = drawer.container.triangles_length
-    box = drawer.container.triangle_aabb.get_data()[:n]
-    return box["min"].copy(), box["max"].copy()
 
 
 _CASES = {}
@@ -669,27 +520,6 @@ def test_8_path_tracer_frame_undisturbed_by_a_call_between_bounces(ctx):
     pt.drawer.on_destroy()
 
 
-def _splitmix():
-    mask = (1 << 64) - 1
-    state = 0
-
-    def seed(s):
-        nonlocal state
-        state = s
-
-    def nxt():
-        nonlocal state
-        state = (state + 0x9E3779B97F4A7C15) & mask
-        z = state
-        z = ((z ^ (z >> 30)) * 0xBF58476D1CE4E5B9) & mask
-        z = ((z ^ (z >> 27)) * 0x94D049BB133111EB) & mask
-        return z ^ (z >> 31)
-
-    def uni(lo, hi):
-        return F(lo) + F(F(hi) - F(lo)) * F((nxt() >> 40) * (1.0 / 16777216.0))
-    return seed, uni
-
-
 @pytest.mark.gpu
 @pytest.mark.parametrize("t_max", [None, 1.0])
 def test_9_cpp_host_driver_khits_matches_the_python_host(ctx, t_max):
@@ -698,26 +528,8 @@ def test_9_cpp_host_driver_khits_matches_the_python_host(ctx, t_max):
     n, count, k = 4096, 20000, 2
     args = [exe, "khits", str(k), str(n), str(count)] + ([str(t_max)] if t_max is not None else [])
     res = json.loads(subprocess.run(args, check=True, capture_output=True, text=True).stdout)
-    seed, uni = _splitmix()
-    seed(1)                                                            # the mesh lbvh_driver.cpp generates (SplitMix64, seed 1)
-    pos = np.zeros((n, 3, 3), dtype=F)
-    for i in range(n):
-        for j in range(3):
-            ctr = uni(-100.0, 100.0)
-            pos[i, 0, j] = ctr
-            pos[i, 1, j] = F(ctr + uni(-2.0, 2.0))
-            pos[i, 2, j] = F(ctr + uni(-2.0, 2.0))
-    tris = np.zeros(n, dtype=L().TRIANGLE)
-    tris["a"], tris["b"], tris["c"] = pos[:, 0], pos[:, 1], pos[:, 2]
-    lo, hi = pos.min(axis=(0, 1)), pos.max(axis=(0, 1))
-    seed(3)                                                            # and its rays (seed 3): origin and target drawn axis by axis
-    origin = np.zeros((count, 3), dtype=F)
-    direction = np.zeros((count, 3), dtype=F)
-    for i in range(count):
-        for j in range(3):
-            grow = F(0.25) * F(hi[j] - lo[j])
-            origin[i, j] = uni(F(lo[j] - grow), F(hi[j] + grow))
-            direction[i, j] = F(uni(lo[j], hi[j]) - origin[i, j])
+    tris, pos, lo, hi = driver_mesh(n)                                 # the mesh lbvh_driver.cpp generates (SplitMix64, seed 1)
+    origin, direction = driver_rays(lo, hi, count)                     # and its rays (seed 3): origin and target drawn axis by axis
     rays = make_rays(origin, direction, F(0.0), INF if t_max is None else F(t_max))
     d = H().RaytracingMeshDrawer(ctx, tris).awake()
     rows = H().DataBuffer(ctx, count * k, L().HIT)

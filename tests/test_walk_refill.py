@@ -25,12 +25,10 @@ import point_reference as PR
 import ray_reference as RR
 import sweep_reference as SW
 import test_crossings as TC
-import test_k_closest_points as TKC
 import test_overlap_queries as TO
-import test_point_queries as TP
-import test_ray_queries as TR
 import test_sphere_cast as TS
-import test_trace_k_closest as TKH
+from query_support import (H, library_boxes, mixed_queries, mixed_rays_of, N, pack, padded_boxes, positions,
+                           _random_ray_states, stacked_sheets, words)
 from unitysimpleraytracing_amd import layouts as L
 from unitysimpleraytracing_amd import scenes
 
@@ -50,20 +48,6 @@ BLOCK = (700, 835)                      # (a): 135 consecutive inactive queries
 PLANT = (100, 164)                      # (d): 64 queries, long and short walks in turn
 LONG_COUNT = 2 * 8192 * 64 + 8192 + 77  # part 3: 1 056 845 queries, runs of 130 on 8192 waves
 PART = 524288                           # ... and the largest call without a refill
-
-
-def H():
-    from unitysimpleraytracing_amd import host
-    return host
-
-
-def N():
-    from unitysimpleraytracing_amd import _native
-    return _native
-
-
-def words(a):
-    return np.ascontiguousarray(a).view(np.uint32)
 
 
 def run_of(count, waves):
@@ -258,13 +242,13 @@ def query_set(name, a, b, c, lo, hi):
         q = TC.mixed_rays(a, b, c, 1500, 21, lambda r: RR.reference(r, a, b, c, lo, hi).records)[0]
         kind = "rays"
     elif name in ("khits_torus", "khits_sheets"):
-        q = TKH.mixed_rays_of("sheets" if name == "khits_sheets" else "torus", a, b, c, lo, hi)
+        q = mixed_rays_of("sheets" if name == "khits_sheets" else "torus", a, b, c, lo, hi)
         kind = "rays"
     elif name == "points":
-        q = TP.mixed_queries(a, b, c, lo, hi, 1501, 22)[0]
+        q = mixed_queries(a, b, c, lo, hi, 1501, 22)[0]
         kind = "points"
     elif name == "kclosest":
-        q = TKC.mixed_queries(a, b, c, lo, hi, 1500, 23)[0]
+        q = mixed_queries(a, b, c, lo, hi, 1500, 23)[0]
         kind = "points"
     elif name == "casts":
         q = TS.aimed_casts(a, b, c, 1501, np.random.default_rng(24))
@@ -280,7 +264,7 @@ def query_set(name, a, b, c, lo, hi):
         kind = "distance"
     else:
         assert name == "states"
-        q = TR._random_ray_states(TS.pack(a, b, c), 1501, 29)
+        q = _random_ray_states(pack(a, b, c), 1501, 29)
         q["alive"] = (np.random.default_rng(30).random(1501) < 0.5).astype(np.uint32)      # about half the states are dead
         kind = "states"
     q = arrange(kind, q, box)
@@ -293,8 +277,8 @@ SET_NAMES = ["rays", "khits_torus", "khits_sheets", "points", "kclosest", "casts
 
 @pytest.mark.parametrize("name", SET_NAMES)
 def test_every_arranged_set_holds_the_inactive_block_the_ends_and_the_mixed_neighbours(name):
-    a, b, c = TKH.stacked_sheets() if name == "khits_sheets" else TC.positions(torus())
-    lo, hi = TC.padded_boxes(a, b, c)
+    a, b, c = stacked_sheets() if name == "khits_sheets" else positions(torus())
+    lo, hi = padded_boxes(a, b, c)
     kind, q, act = query_set(name, a, b, c, lo, hi)
     assert not act[BLOCK[0]:BLOCK[1]].any() and act[PLANT[0]:PLANT[1]].all()
     if name == "states":
@@ -302,8 +286,8 @@ def test_every_arranged_set_holds_the_inactive_block_the_ends_and_the_mixed_neig
 
 
 def test_check_arranged_refuses_a_set_without_the_block_or_with_short_runs():
-    a, b, c = TC.positions(torus())
-    lo, hi = TC.padded_boxes(a, b, c)
+    a, b, c = positions(torus())
+    lo, hi = padded_boxes(a, b, c)
     box = scene_box(a, b, c)
     kind, q, _ = query_set("points", a, b, c, lo, hi)
     plain = q.copy()
@@ -377,7 +361,7 @@ def check_scan_layout(pick, offsets, counts):
 def test_scan_palette_and_layout():
     pos = np.load(os.path.join(ROOT, "tests", "golden", "cfg1_4096.npz"))["positions"]
     a, b, c = (np.ascontiguousarray(pos[:, k], dtype=F) for k in range(3))
-    lo, hi = TC.padded_boxes(a, b, c)
+    lo, hi = padded_boxes(a, b, c)
     palette = scan_palette(lo, hi)
     off, tris = V.box_overlaps(palette, lo, hi)
     counts = np.diff(off).astype(np.int64)
@@ -483,11 +467,11 @@ _SCENES = {}
 def scene_case(ctx, name):
     """(a, b, c, the library's boxes, drawer, the oracle's build) of "torus" or "sheets"; the derived scene is this one's again"""
     if name not in _SCENES:
-        tris = torus() if name == "torus" else TS.pack(*TKH.stacked_sheets())
+        tris = torus() if name == "torus" else pack(*stacked_sheets())
         d = H().RaytracingMeshDrawer(ctx, tris).awake()
-        a, b, c = TC.positions(tris)
-        lo, hi = TC.library_boxes(d)
-        plo, phi = TC.padded_boxes(a, b, c)
+        a, b, c = positions(tris)
+        lo, hi = library_boxes(d)
+        plo, phi = padded_boxes(a, b, c)
         assert (words(lo) == words(plo)).all() and (words(hi) == words(phi)).all()      # the CPU tests' sets are these sets
         _SCENES[name] = (a, b, c, lo, hi, d, tris)
     _SCENES[name][5].build_fast_scene()
@@ -842,9 +826,9 @@ def test_scan_over_more_than_1024_tiles_and_a_total_beyond_two_to_the_32(ctx):
     are the brute force's, everything from the capacity on is untouched — a position cut to 32 bits would land there or, for
     the queries after the total has passed 2^32, on the first segments with the triangles of another box."""
     pos = np.load(os.path.join(ROOT, "tests", "golden", "cfg1_4096.npz"))["positions"]
-    tris = TS.pack(*(np.ascontiguousarray(pos[:, k], dtype=F) for k in range(3)))
+    tris = pack(*(np.ascontiguousarray(pos[:, k], dtype=F) for k in range(3)))
     d = H().RaytracingMeshDrawer(ctx, tris).awake()
-    lo, hi = TC.library_boxes(d)
+    lo, hi = library_boxes(d)
     palette = scan_palette(lo, hi)
     po, pt = V.box_overlaps(palette, lo, hi)
     counts = np.diff(po).astype(np.int64)

@@ -11,7 +11,6 @@
 Before anything is printed the outputs are checked: count >= 1 <=> occluded; with t_max = the closest t the count is 0 and
 with t_max one ulp above it >= 1 (a); every parity bit == its ray's count AND 1 (b).  Times: device events around `--launches`
 back-to-back calls, `--reps` times after `--warmup` calls; per call = median over the reps (min / max beside it)."""
-import argparse
 import ctypes as C
 import json
 import os
@@ -19,20 +18,18 @@ import sys
 
 import numpy as np
 
+import query_bench as Q
+from query_bench import LIGHT
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
-LIGHT = np.array([0.0, 250.0, 150.0], dtype=np.float32)
 F = np.float32
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--launches", type=int, default=100)
-    ap.add_argument("--reps", type=int, default=5)
-    ap.add_argument("--warmup", type=int, default=10)
+    ap = Q.arguments(launches=100, reps=5, warmup=10)
     ap.add_argument("--points", type=int, default=1 << 20)
-    ap.add_argument("--out", default=None, help="also write the JSON here")
     ap.add_argument("--crossings-out", default=None, help="write part (b) alone here")
     a = ap.parse_args()
 
@@ -50,28 +47,11 @@ def main():
     s = d.container.scene()
     cam = N.Camera.from_dict(scenes.camera(W, Ht, (0.0, 0.0, 250.0)))
 
-    states = DataBuffer(ctx, n, L.PATH_STATE)
-    prim = DataBuffer(ctx, n, L.HIT)
-    N.check(h, N.lib.lbvh_trace_primary(h, C.byref(cam), 0, 0, W, Ht, C.byref(s), L.TRACE_FAST, prim.device, None))
-    N.check(h, N.lib.lbvh_path_begin(h, C.byref(cam), states.device))
-    camera_rays = states.get_data().copy()
-    ph = prim.get_data().copy()
-    N.check(h, N.lib.lbvh_path_first_bounce(h, C.byref(cam), C.byref(s), states.device, prim.device, 9, 0.7, 1e-3))
-    first = states.get_data().copy()
-    live = first["alive"] != 0
-
-    def ray_buffer(origin, direction, t_min, t_max):
-        b = DataBuffer(ctx, len(origin), L.RAY)
-        b.local["origin"], b.local["dir"], b.local["t_min"], b.local["t_max"] = origin, direction, t_min, t_max
-        b.sync()
-        return b
-
-    sec = ray_buffer(first["origin"][live], first["dir"][live], F(1e-3), F(np.inf))
-    hit = ph["t"] < L.MAX_FLOAT
-    origin = (camera_rays["origin"] + camera_rays["dir"] * ph["t"][:, None]).astype(F)
-    shadow = ray_buffer(origin, (LIGHT - origin).astype(F), F(1e-4), np.where(hit, F(1.0), F(0.0)))
+    first, live, hit, origin, set_buffers = Q.ray_sets(ctx, s, cam, W, Ht)
+    sec = Q.ray_buffer(ctx, first["origin"][live], first["dir"][live], F(1e-3), F(np.inf))     # the live rays only
+    shadow = Q.ray_buffer(ctx, origin, (LIGHT - origin).astype(F), F(1e-4), np.where(hit, F(1.0), F(0.0)))
     out_hits = DataBuffer(ctx, n, L.HIT)
-    out_u32 = DataBuffer(ctx, 3 * a.points, np.uint32)
+    out_u32 = DataBuffer(ctx, max(3 * a.points, n), np.uint32)      # part (a) writes one word per pixel into it, whatever --points is
 
     def call(fn, rays):
         return lambda: fn(h, rays.device, rays.size, C.byref(s), out_hits.device if fn is N.lib.lbvh_trace_closest else out_u32.device)
@@ -133,38 +113,18 @@ def main():
     # ---- work per ray
     stats = DataBuffer(ctx, 1, L.RAY_STATS)
 
-    def counters(fn):
-        stats.fill_u32(0)
-        N.check(h, N.lib.lbvh_ray_stats_target(h, stats.device))
-        N.check(h, fn())
-        N.check(h, N.lib.lbvh_ray_stats_target(h, None))
-        st = stats.get_data()[0]
-        r = max(int(st["rays"]), 1)
-        return {"rays": int(st["rays"]), "node_fetches_per_ray": round(int(st["node_fetches"]) / r, 3),
-                "triangle_tests_per_ray": round(int(st["triangle_tests"]) / r, 3)}
-
-    e0, e1 = ctx.event(), ctx.event()
-
-    def rep(fn):
-        ctx.record(e0)
-        for _ in range(a.launches):
-            N.check(h, fn())
-        ctx.record(e1)
-        return ctx.elapsed_ms(e0, e1) / a.launches
-
-    def summary(per):
-        per = sorted(per)
-        return {"ms": round(per[len(per) // 2], 4), "ms_min": round(per[0], 4), "ms_max": round(per[-1], 4)}
+    def work(fn):
+        c = Q.counters(ctx, stats, fn)
+        fetches, tests = Q.per_active(c)
+        return {"rays": c.rays, "node_fetches_per_ray": fetches, "triangle_tests_per_ray": tests}
 
     res = {"workload": "lbvh_count_hits / lbvh_point_crossings on the cfg2 mesh (1 M triangles)", "launches": a.launches, "reps": a.reps,
            "checks": "count >= 1 <=> occluded; count(t_max = t*) == 0, count(nextafter(t*)) >= 1; parity bit == count AND 1: hold",
            "a": {}, "b": {}}
     for name, fn in calls.items():
-        for _ in range(a.warmup):
-            N.check(h, fn())
-        r = summary([rep(fn) for _ in range(a.reps)])
         tag = name.rsplit("_", 1)[0]
-        res["a"][name] = {**r, "active_rays": active[tag], **counters(fn)}
+        res["a"][name] = {**Q.timed(ctx, fn, None, a.launches, a.reps, a.warmup), "active_rays": active[tag], **work(fn)}
+    events = (ctx.event(), ctx.event())
     for set_name, pts in point_sets.items():
         load(pts)
         parity.fill_u32(0xDEADBEEF)
@@ -180,22 +140,18 @@ def main():
         per = {k: [] for k in cross_calls}
         for _ in range(a.reps):                                   # alternating
             for k2, fn in cross_calls.items():
-                per[k2].append(rep(fn))
-        row = {k2: {**summary(v), **counters(cross_calls[k2])} for k2, v in per.items()}
+                per[k2].append(Q.rep(ctx, events, fn, a.launches))
+        row = {k2: {**Q.summary(v), **work(cross_calls[k2])} for k2, v in per.items()}
         spread = max(row[k2]["ms_max"] - row[k2]["ms_min"] for k2 in row)
         bar = row["materialised_count"]["ms"] + 3 * spread
         row.update(points=a.points, directions=3, inside_majority=int((np.unpackbits(par.view(np.uint8)).reshape(-1, 32).sum(axis=1) >= 2).sum()),
                    bar_ms=round(bar, 4), bar_holds=bool(row["crossings"]["ms"] <= bar))
         res["b"][set_name] = row
-    line = json.dumps(res)
-    print(line)
-    if a.out:
-        with open(a.out, "w") as f:
-            f.write(line + "\n")
+    Q.emit(res, a.out)
     if a.crossings_out:
         with open(a.crossings_out, "w") as f:
             f.write(json.dumps({"workload": res["workload"], "launches": a.launches, "reps": a.reps, **res["b"]}) + "\n")
-    for b in (states, prim, sec, shadow, out_hits, out_u32, pbuf, rbuf, parity, stats):
+    for b in set_buffers + [sec, shadow, out_hits, out_u32, pbuf, rbuf, parity, stats]:
         b.dispose()
     d.on_destroy()
     ctx.close()

@@ -20,7 +20,6 @@ sorted head of every segment == its row of lbvh_trace_k_closest at k = 32 (recor
 against tests/gather_hits_reference.py (brute force over all triangles, word for word after the canonical sort).  Times: device
 events around `--launches` back-to-back calls, `--reps` times after `--warmup` calls (the clocks settle there); per call = median
 over the repetitions of all rounds (min / max beside it: the spread)."""
-import argparse
 import ctypes as C
 import json
 import os
@@ -29,24 +28,21 @@ import sys
 
 import numpy as np
 
+import query_bench as Q
+from query_bench import LIGHT
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
-LIGHT = np.array([0.0, 250.0, 150.0], dtype=np.float32)
 N_RAYS = 1 << 20
 
 
 def summary(per, active):
-    per = sorted(per)
-    ms = per[len(per) // 2]
-    return {"ms": round(ms, 4), "ms_min": round(per[0], 4), "ms_max": round(per[-1], 4), "reps": len(per),
-            "Mrays_s_active": round(active / (ms * 1e-3) / 1e6, 1)}
+    t = Q.summary(per, active)
+    return {"ms": t["ms"], "ms_min": t["ms_min"], "ms_max": t["ms_max"], "reps": len(per), "Mrays_s_active": t["Mrays_s_active"]}
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--launches", type=int, default=10)
-    ap.add_argument("--reps", type=int, default=5)
-    ap.add_argument("--warmup", type=int, default=5)
+    ap = Q.arguments(launches=10, reps=5, warmup=5, out=os.path.join(ROOT, "profiles", "gather_hits", "gather_hits.json"))
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--width", type=int, default=1920)
     ap.add_argument("--height", type=int, default=1080)
@@ -55,7 +51,6 @@ def main():
     ap.add_argument("--parent-tree", default=None, help="a built checkout of the parent commit: its lbvh_count_hits is the yardstick")
     ap.add_argument("--count-hits-only", action="store_true", help="child mode: time lbvh_count_hits on both sets, print JSON")
     ap.add_argument("--tree", default=ROOT, help="where the package and its library are imported from")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "gather_hits", "gather_hits.json"))
     a = ap.parse_args()
     sys.path.insert(0, os.path.abspath(a.tree))
     sys.path.insert(0, os.path.join(ROOT, "tests"))
@@ -76,43 +71,18 @@ def main():
     cam = N.Camera.from_dict(scenes.camera(W, Ht, (0.0, 0.0, 250.0)))
 
     # primary hits + first-bounce states, as tools/k_hits_bench.py makes them
-    states = DataBuffer(ctx, n_px, L.PATH_STATE)
-    prim = DataBuffer(ctx, n_px, L.HIT)
-    hits = DataBuffer(ctx, n_px, L.HIT)
-    N.check(h, N.lib.lbvh_trace_primary(h, C.byref(cam), 0, 0, W, Ht, C.byref(s), L.TRACE_FAST, prim.device, None))
-    N.check(h, N.lib.lbvh_path_begin(h, C.byref(cam), states.device))
-    camera_rays = states.get_data().copy()
-    ph = prim.get_data().copy()
-    N.check(h, N.lib.lbvh_buffer_upload(h, hits.device, ph.ctypes.data_as(C.c_void_p), ph.nbytes))
-    N.check(h, N.lib.lbvh_path_first_bounce(h, C.byref(cam), C.byref(s), states.device, hits.device, 9, 0.7, 1e-3))
-    first = states.get_data().copy()
-    live = first["alive"] != 0
+    first, live, hit, origin, set_buffers = Q.ray_sets(ctx, s, cam, W, Ht)
 
-    def ray_buffer(origin, direction, t_min, t_max):
-        b = DataBuffer(ctx, n, L.RAY)
-        b.local["origin"], b.local["dir"], b.local["t_min"], b.local["t_max"] = origin[:n], direction[:n], t_min, t_max[:n]
-        b.sync()
-        return b
+    def ray_buffer(origin, direction, t_min, t_max):         # the first n rays of a set
+        return Q.ray_buffer(ctx, origin[:n], direction[:n], t_min, t_max[:n])
 
-    hit = ph["t"] < L.MAX_FLOAT
-    origin = (camera_rays["origin"] + camera_rays["dir"] * ph["t"][:, None]).astype(np.float32)
     sets = {"a": ray_buffer(first["origin"], first["dir"], np.float32(1e-3), np.where(live, np.float32(np.inf), np.float32(0.0))),
             "b": ray_buffer(origin, (LIGHT - origin).astype(np.float32), np.float32(1e-4), np.where(hit, np.float32(1.0), np.float32(0.0)))}
     active = {k: int((b.local["t_min"] < b.local["t_max"]).sum()) for k, b in sets.items()}
     cnt = DataBuffer(ctx, n, np.uint32)
-    e0, e1 = ctx.event(), ctx.event()
 
     def reps_of(fn):
-        for _ in range(a.warmup):
-            N.check(h, fn())
-        per = []
-        for _ in range(a.reps):
-            ctx.record(e0)
-            for _ in range(a.launches):
-                N.check(h, fn())
-            ctx.record(e1)
-            per.append(ctx.elapsed_ms(e0, e1) / a.launches)
-        return per
+        return Q.reps_of(ctx, fn, a.launches, a.reps, a.warmup)
 
     count_fn = lambda rays: (lambda: N.lib.lbvh_count_hits(h, rays.device, n, C.byref(s), cnt.device))
 
@@ -134,15 +104,10 @@ def main():
     found = DataBuffer(ctx, n, np.uint32)
     stats = DataBuffer(ctx, 1, L.RAY_STATS)
 
-    def counters(fn):
-        stats.fill_u32(0)
-        N.check(h, N.lib.lbvh_ray_stats_target(h, stats.device))
-        N.check(h, fn())
-        N.check(h, N.lib.lbvh_ray_stats_target(h, None))
-        c = stats.get_data()[0]
-        r = max(int(c["rays"]), 1)
-        return {"rays_walked": int(c["rays"]), "node_lines_per_ray": round(int(c["node_fetches"]) / r, 3),
-                "triangle_tests_per_ray": round(int(c["triangle_tests"]) / r, 3)}
+    def work(fn):
+        c = Q.counters(ctx, stats, fn)
+        lines, tests = Q.per_active(c)
+        return {"rays_walked": c.rays, "node_lines_per_ray": lines, "triangle_tests_per_ray": tests}
 
     words = lambda x: np.ascontiguousarray(x).view(np.uint32)
     res = {"workload": "cfg2 mesh (%d triangles), the first %d rays of the %dx%d sets: (a) first-bounce rays, open range; (b) shadow rays, "
@@ -205,7 +170,7 @@ def main():
     for name in sets:
         out = res["sets"][name]
         for k, fn in calls[name].items():
-            out[k] = {**summary(per[name][k], active[name]), **counters(fn)}
+            out[k] = {**summary(per[name][k], active[name]), **work(fn)}
         co, fu, ch = out["gather_count_only"], out["gather_full"], out["count_hits"]
         out["full_over_count_only"] = {"ms": round(fu["ms"] - co["ms"], 4), "ratio": round(fu["ms"] / co["ms"], 3)}
         out["count_only_vs_count_hits_this_library"] = round(co["ms"] / ch["ms"], 3)
@@ -218,13 +183,8 @@ def main():
             out["count_only_slower_than_parent_count_by_more_than_the_spread"] = bool(co["ms"] > p["ms"] + spread)
         else:
             out["parent_count_hits"] = "not measured (no --parent-tree)"
-    line = json.dumps(res)
-    print(line)
-    if a.out:
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-        with open(a.out, "w") as f:
-            f.write(line + "\n")
-    for b in [states, prim, hits, rows, found, cnt, stats, offsets] + list(sets.values()) + list(fills.values()):
+    Q.emit(res, a.out)
+    for b in set_buffers + [rows, found, cnt, stats, offsets] + list(sets.values()) + list(fills.values()):
         b.dispose()
     d.on_destroy()
     ctx.close()

@@ -14,13 +14,13 @@ Before anything is printed the outputs are checked: `--check` queries against te
 force over all triangles, word for word, zero box-rule rejections), k = 1 against lbvh_closest_point_query on every query, and
 record 0 of every row of every k against it.  Times: device events around `--launches` back-to-back calls, `--reps` times after
 `--warmup` calls (the clocks settle there); per call = median over the reps (min / max beside it: the spread)."""
-import argparse
 import ctypes as C
-import json
 import os
 import sys
 
 import numpy as np
+
+import query_bench as Q
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -31,15 +31,11 @@ STACK_LDS = 16 * 64 * 4          # the walk's 16-entry stack
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--launches", type=int, default=20)
-    ap.add_argument("--reps", type=int, default=5)
-    ap.add_argument("--warmup", type=int, default=5)
+    ap = Q.arguments(launches=20, reps=5, warmup=5)
     ap.add_argument("--log2-queries", type=int, default=20)
     ap.add_argument("--offset", type=float, default=0.05)
     ap.add_argument("--ks", default="1,4,8,16,32")
     ap.add_argument("--check", type=int, default=16, help="queries compared with the brute force")
-    ap.add_argument("--out", default=None, help="also write the JSON here")
     a = ap.parse_args()
     ks = [int(x) for x in a.ks.split(",")]
 
@@ -90,30 +86,12 @@ def main():
 
     stats = DataBuffer(ctx, 1, L.RAY_STATS)
 
-    def counters(fn):
-        stats.fill_u32(0)
-        N.check(h, N.lib.lbvh_ray_stats_target(h, stats.device))
-        N.check(h, fn())
-        N.check(h, N.lib.lbvh_ray_stats_target(h, None))
-        c = stats.get_data()[0]
-        r = max(int(c["rays"]), 1)
-        return {"node_lines_per_query": round(int(c["node_fetches"]) / r, 3), "triangle_tests_per_query": round(int(c["triangle_tests"]) / r, 3)}
+    def work(fn):
+        lines, tests = Q.per_active(Q.counters(ctx, stats, fn))
+        return {"node_lines_per_query": lines, "triangle_tests_per_query": tests}
 
-    e0, e1 = ctx.event(), ctx.event()
-
-    def timed(fn):
-        for _ in range(a.warmup):
-            N.check(h, fn())
-        per = []
-        for _ in range(a.reps):
-            ctx.record(e0)
-            for _ in range(a.launches):
-                N.check(h, fn())
-            ctx.record(e1)
-            per.append(ctx.elapsed_ms(e0, e1) / a.launches)
-        per.sort()
-        ms = per[len(per) // 2]
-        return {"ms": round(ms, 4), "ms_min": round(per[0], 4), "ms_max": round(per[-1], 4), "Mqueries_s": round(n / (ms * 1e-3) / 1e6, 2)}
+    def times(fn):
+        return Q.timed(ctx, fn, n, a.launches, a.reps, a.warmup, rate="Mqueries_s", digits=2)
 
     # ---- the gather route: the radius whose median segment length is 8
     offsets = DataBuffer(ctx, n + 1, np.uint64)
@@ -135,7 +113,7 @@ def main():
     med, total = median_len(r_hi)
     seg = DataBuffer(ctx, max(total, 1), np.uint32)
     gather = lambda: N.lib.lbvh_gather_within_distance(h, q.device, n, C.byref(s), offsets.device, seg.device, seg.size)
-    res_gather = {**timed(gather), **counters(gather), "max_dist2": round(r_hi, 5), "median_segment": med, "total_triangles": total,
+    res_gather = {**times(gather), **work(gather), "max_dist2": round(r_hi, 5), "median_segment": med, "total_triangles": total,
                   "note": "count walk + scan + fill walk; the host-side sort and cut at 8 is not counted"}
     q.local["max_dist2"] = np.float32(np.inf)
     q.sync()
@@ -144,10 +122,10 @@ def main():
            "launches": a.launches, "reps": a.reps,
            "checks": "rows and found word for word against the brute force on %d queries for every k, record 0 of every row == "
                      "lbvh_closest_point_query on every query for every k, zero box-rule rejections: hold" % a.check,
-           "closest_point_query": {**timed(closest), **counters(closest)}, "k": {}, "gather_within_distance_median_8": res_gather}
+           "closest_point_query": {**times(closest), **work(closest)}, "k": {}, "gather_within_distance_median_8": res_gather}
     for k in ks:
         lds = STACK_LDS + 3 * k * 64 * 4
-        res["k"][str(k)] = {**timed(knn(k)), **counters(knn(k)), "lds_bytes_per_wave": lds, "waves_per_cu_by_lds": min(LDS_PER_CU // lds, 32)}
+        res["k"][str(k)] = {**times(knn(k)), **work(knn(k)), "lds_bytes_per_wave": lds, "waves_per_cu_by_lds": min(LDS_PER_CU // lds, 32)}
     cp = res["closest_point_query"]
     if "1" in res["k"]:
         k1 = res["k"]["1"]
@@ -156,11 +134,7 @@ def main():
                                             "ratio": round(k1["ms"] / cp["ms"], 3)}
     if "8" in res["k"]:
         res["k8_vs_gather"] = {"ratio": round(res["k"]["8"]["ms"] / res_gather["ms"], 3)}
-    line = json.dumps(res)
-    print(line)
-    if a.out:
-        with open(a.out, "w") as f:
-            f.write(line + "\n")
+    Q.emit(res, a.out)
     for b in (q, rows, found, rec, stats, offsets, seg):
         b.dispose()
     d.on_destroy()

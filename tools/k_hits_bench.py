@@ -16,33 +16,29 @@ lbvh_trace_closest's record word for word (k = 1: the whole output), found == mi
 each set against tests/k_hits_reference.py (brute force over all triangles, word for word).  Times: device events around
 `--launches` back-to-back calls, `--reps` times after `--warmup` calls (the clocks settle there); per call = median over the
 reps (min / max beside it: the spread)."""
-import argparse
 import ctypes as C
-import json
 import os
 import sys
 
 import numpy as np
 
+import query_bench as Q
+from query_bench import LIGHT
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
-LIGHT = np.array([0.0, 250.0, 150.0], dtype=np.float32)
 LDS_PER_CU = 160 * 1024          # gfx950
 STACK_LDS = 16 * 64 * 4          # the walk's 16-entry stack
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--launches", type=int, default=20)
-    ap.add_argument("--reps", type=int, default=5)
-    ap.add_argument("--warmup", type=int, default=5)
+    ap = Q.arguments(launches=20, reps=5, warmup=5)
     ap.add_argument("--width", type=int, default=1920)
     ap.add_argument("--height", type=int, default=1080)
     ap.add_argument("--ks", default="1,2,4,8,16,32")
     ap.add_argument("--check", type=int, default=16, help="rays of each set compared with the brute force")
-    ap.add_argument("--out", default=None, help="also write the JSON here")
     a = ap.parse_args()
     ks = [int(x) for x in a.ks.split(",")]
 
@@ -65,58 +61,22 @@ def main():
     cam = N.Camera.from_dict(scenes.camera(W, Ht, (0.0, 0.0, 250.0)))
 
     # primary hits + first-bounce states, as tools/ray_queries_bench.py makes them
-    states = DataBuffer(ctx, n, L.PATH_STATE)
-    prim = DataBuffer(ctx, n, L.HIT)
-    hits = DataBuffer(ctx, n, L.HIT)
-    N.check(h, N.lib.lbvh_trace_primary(h, C.byref(cam), 0, 0, W, Ht, C.byref(s), L.TRACE_FAST, prim.device, None))
-    N.check(h, N.lib.lbvh_path_begin(h, C.byref(cam), states.device))
-    camera_rays = states.get_data().copy()
-    ph = prim.get_data().copy()
-    N.check(h, N.lib.lbvh_buffer_upload(h, hits.device, ph.ctypes.data_as(C.c_void_p), ph.nbytes))
-    N.check(h, N.lib.lbvh_path_first_bounce(h, C.byref(cam), C.byref(s), states.device, hits.device, 9, 0.7, 1e-3))
-    first = states.get_data().copy()
-    live = first["alive"] != 0
-
-    def ray_buffer(origin, direction, t_min, t_max):
-        b = DataBuffer(ctx, n, L.RAY)
-        b.local["origin"], b.local["dir"], b.local["t_min"], b.local["t_max"] = origin, direction, t_min, t_max
-        b.sync()
-        return b
-
-    hit = ph["t"] < L.MAX_FLOAT
-    origin = (camera_rays["origin"] + camera_rays["dir"] * ph["t"][:, None]).astype(np.float32)
-    sets = {"a": (ray_buffer(first["origin"], first["dir"], np.float32(1e-3), np.where(live, np.float32(np.inf), np.float32(0.0))), int(live.sum())),
-            "b": (ray_buffer(origin, (LIGHT - origin).astype(np.float32), np.float32(1e-4), np.where(hit, np.float32(1.0), np.float32(0.0))),
+    first, live, hit, origin, set_buffers = Q.ray_sets(ctx, s, cam, W, Ht)
+    sets = {"a": (Q.ray_buffer(ctx, first["origin"], first["dir"], np.float32(1e-3), np.where(live, np.float32(np.inf), np.float32(0.0))), int(live.sum())),
+            "b": (Q.ray_buffer(ctx, origin, (LIGHT - origin).astype(np.float32), np.float32(1e-4), np.where(hit, np.float32(1.0), np.float32(0.0))),
                   int(hit.sum()))}
     rows = DataBuffer(ctx, n * max(ks), L.HIT)
     found = DataBuffer(ctx, n, np.uint32)
     rec = DataBuffer(ctx, n, L.HIT)
     cnt = DataBuffer(ctx, n, np.uint32)
     stats = DataBuffer(ctx, 1, L.RAY_STATS)
-    e0, e1 = ctx.event(), ctx.event()
 
-    def counters(fn):
-        stats.fill_u32(0)
-        N.check(h, N.lib.lbvh_ray_stats_target(h, stats.device))
-        N.check(h, fn())
-        N.check(h, N.lib.lbvh_ray_stats_target(h, None))
-        c = stats.get_data()[0]
-        r = max(int(c["rays"]), 1)
-        return {"node_lines_per_ray": round(int(c["node_fetches"]) / r, 3), "triangle_tests_per_ray": round(int(c["triangle_tests"]) / r, 3)}
+    def work(fn):
+        lines, tests = Q.per_active(Q.counters(ctx, stats, fn))
+        return {"node_lines_per_ray": lines, "triangle_tests_per_ray": tests}
 
-    def timed(fn, active):
-        for _ in range(a.warmup):
-            N.check(h, fn())
-        per = []
-        for _ in range(a.reps):
-            ctx.record(e0)
-            for _ in range(a.launches):
-                N.check(h, fn())
-            ctx.record(e1)
-            per.append(ctx.elapsed_ms(e0, e1) / a.launches)
-        per.sort()
-        ms = per[len(per) // 2]
-        return {"ms": round(ms, 4), "ms_min": round(per[0], 4), "ms_max": round(per[-1], 4), "Mrays_s_active": round(active / (ms * 1e-3) / 1e6, 1)}
+    def times(fn, active):
+        return Q.timed(ctx, fn, active, a.launches, a.reps, a.warmup)
 
     res = {"workload": "cfg2 mesh (%d triangles), %dx%d: (a) first-bounce rays, open range; (b) shadow rays, t in (1e-4, 1)" % (len(tris), W, Ht),
            "launches": a.launches, "reps": a.reps,
@@ -148,11 +108,11 @@ def main():
             per_k[k] = {"found_sum": int(f.sum()), "full_rows": int((f == k).sum())}
         out = {"rays_in_buffer": n, "active_rays": active, "candidates_per_active_ray": round(float(counts.sum()) / max(active, 1), 3),
                "most_candidates": int(counts.max()),
-               "trace_closest": {**timed(closest, active), **counters(closest)}, "count_hits": {**timed(count, active), **counters(count)},
+               "trace_closest": {**times(closest, active), **work(closest)}, "count_hits": {**times(count, active), **work(count)},
                "k": {}}
         for k in ks:
             lds = STACK_LDS + 3 * k * 64 * 4
-            out["k"][str(k)] = {**timed(khits(k), active), **counters(khits(k)), **per_k[k], "lds_bytes_per_wave": lds,
+            out["k"][str(k)] = {**times(khits(k), active), **work(khits(k)), **per_k[k], "lds_bytes_per_wave": lds,
                                 "waves_per_cu_by_lds": min(LDS_PER_CU // lds, 32)}
         tc_, ch = out["trace_closest"], out["count_hits"]
         if "1" in out["k"]:
@@ -164,12 +124,8 @@ def main():
             out["k32_vs_count_hits"] = {"ratio": round(k32["ms"] / ch["ms"], 3),
                                         "ratio_range": [round(k32["ms_min"] / ch["ms_max"], 3), round(k32["ms_max"] / ch["ms_min"], 3)]}
         res["sets"][name] = out
-    line = json.dumps(res)
-    print(line)
-    if a.out:
-        with open(a.out, "w") as f:
-            f.write(line + "\n")
-    for b in (states, prim, hits, rows, found, rec, cnt, stats, sets["a"][0], sets["b"][0]):
+    Q.emit(res, a.out)
+    for b in set_buffers + [rows, found, rec, cnt, stats, sets["a"][0], sets["b"][0]]:
         b.dispose()
     d.on_destroy()
     ctx.close()

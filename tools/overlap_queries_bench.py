@@ -13,13 +13,13 @@ triangles, every segment sorted, word for word), and the offsets of the count-on
 device events around `--launches` back-to-back calls, `--reps` times after `--warmup`; per call = median (min / max beside it).
 Node lines and triangle tests: lbvh_ray_stats_target on one more call.  The scan's share: the library's per-kernel event
 profile (lbvh_profile_begin / _end) of one count + fill call."""
-import argparse
 import ctypes as C
-import json
 import os
 import sys
 
 import numpy as np
+
+import query_bench as Q
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -27,16 +27,12 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--launches", type=int, default=100)
+    ap = Q.arguments(launches=100, reps=5, warmup=5)
     ap.add_argument("--huge-launches", type=int, default=2)
-    ap.add_argument("--reps", type=int, default=5)
-    ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--log2-queries", type=int, default=21)
     ap.add_argument("--half", type=float, default=1.5)
     ap.add_argument("--radius", type=float, default=3.0)
     ap.add_argument("--check", type=int, default=24, help="queries per set compared with the brute force")
-    ap.add_argument("--out", default=None, help="also write the JSON here")
     a = ap.parse_args()
 
     import overlap_reference as V
@@ -86,33 +82,14 @@ def main():
     }
     offsets = DataBuffer(ctx, max(n, nt) + 1, np.uint64)
     stats = DataBuffer(ctx, 1, L.RAY_STATS)
-    e0, e1 = ctx.event(), ctx.event()
 
     def total_of(count):
         last = np.zeros(1, dtype=np.uint64)
         N.check(h, N.lib.lbvh_buffer_download(h, last.ctypes.data_as(C.c_void_p), C.c_void_p(offsets.device.value + 8 * count), 8))
         return int(last[0])
 
-    def timed(call, launches):
-        for _ in range(min(a.warmup, launches)):
-            N.check(h, call())
-        per = []
-        for _ in range(a.reps):
-            ctx.record(e0)
-            for _ in range(launches):
-                N.check(h, call())
-            ctx.record(e1)
-            per.append(ctx.elapsed_ms(e0, e1) / launches)
-        per.sort()
-        return {"ms": round(per[len(per) // 2], 4), "ms_min": round(per[0], 4), "ms_max": round(per[-1], 4)}
-
-    def counters(call):
-        stats.fill_u32(0)
-        N.check(h, N.lib.lbvh_ray_stats_target(h, stats.device))
-        N.check(h, call())
-        N.check(h, N.lib.lbvh_ray_stats_target(h, None))
-        c = stats.get_data()[0]
-        return int(c["rays"]), int(c["node_fetches"]), int(c["triangle_tests"])
+    def times(call, launches):                              # no more warm-up calls than launches: the huge boxes
+        return Q.timed(ctx, call, None, launches, a.reps, min(a.warmup, launches))
 
     res = {"workload": "overlap queries on the cfg2 mesh (%d triangles), 2^%d queries (self: one per triangle; huge_boxes: 64)" % (nt, a.log2_queries),
            "launches": a.launches, "huge_launches": a.huge_launches, "reps": a.reps, "half": a.half, "radius": a.radius, "sets": {}}
@@ -137,9 +114,9 @@ def main():
             seg = np.sort(got[int(off[k]):int(off[k + 1])])
             assert (seg == rt[int(ro[j]):int(ro[j + 1])]).all() and len(seg) == int(ro[j + 1] - ro[j]), (name, int(k))
         row = {"queries": count, "M": m, "candidates_per_query": round(m / count, 3), "longest_segment": int(np.diff(off).max()),
-               "count_only": timed(count_only, launches), "count_and_fill": timed(fill, launches)}
-        active, lines, tests = counters(count_only)
-        active2, lines2, _ = counters(fill)
+               "count_only": times(count_only, launches), "count_and_fill": times(fill, launches)}
+        active, lines, tests = Q.counters(ctx, stats, count_only)
+        active2, lines2, _ = Q.counters(ctx, stats, fill)
         row.update({"active": active, "node_lines_per_query": round(lines / max(active, 1), 3), "triangle_tests_per_query": round(tests / max(active, 1), 3),
                     "node_lines_count_only": lines, "node_lines_count_and_fill": lines2,
                     "Mcandidates_written_per_s": round(m / (row["count_and_fill"]["ms"] * 1e-3) / 1e6, 1)})
@@ -155,18 +132,14 @@ def main():
     flags, rec = DataBuffer(ctx, n, np.uint32), DataBuffer(ctx, n, L.CLOSEST_POINT)
     within = lambda: N.lib.lbvh_within_distance(h, points.device, n, C.byref(s), flags.device)
     closest = lambda: N.lib.lbvh_closest_point_query(h, points.device, n, C.byref(s), rec.device)
-    _, w_lines, _ = counters(within)
-    res["radius_yardsticks"] = {"within_distance": {**timed(within, a.launches), "node_lines": w_lines},
-                                "closest_point_query": {**timed(closest, a.launches), "node_lines": counters(closest)[1]}}
+    _, w_lines, _ = Q.counters(ctx, stats, within)
+    res["radius_yardsticks"] = {"within_distance": {**times(within, a.launches), "node_lines": w_lines},
+                                "closest_point_query": {**times(closest, a.launches), "node_lines": Q.counters(ctx, stats, closest)[1]}}
     res["conditions"] = {
         "count_only_never_slower_than_count_and_fill": all(r["count_only"]["ms"] <= r["count_and_fill"]["ms"] for r in res["sets"].values()),
         "distance_count_walk_fetches_no_fewer_lines_than_within_distance": res["sets"]["radius"]["node_lines_count_only"] >= w_lines,
         "fill_walk_repeats_the_count_walk": all(r["node_lines_count_and_fill"] == 2 * r["node_lines_count_only"] for r in res["sets"].values())}
-    line = json.dumps(res)
-    print(line)
-    if a.out:
-        with open(a.out, "w") as f:
-            f.write(line + "\n")
+    Q.emit(res, a.out)
     for b in (small, points, huge, offsets, stats, flags, rec):
         b.dispose()
     d.on_destroy()

@@ -13,14 +13,14 @@ over all triangles, word for word: P1 records, P2 flags, zero box-rule rejection
 within-distance == (closest found a triangle).  Times: device events around `--launches` back-to-back calls, `--reps` times
 after `--warmup` calls; per call = median over the reps (min / max beside it: the spread).  Node lines and triangle tests per
 active query: lbvh_ray_stats_target on one more call of each.  The CPU restatement's rate comes from the check itself."""
-import argparse
 import ctypes as C
-import json
 import os
 import sys
 import time
 
 import numpy as np
+
+import query_bench as Q
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -28,14 +28,10 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--launches", type=int, default=100)
-    ap.add_argument("--reps", type=int, default=5)
-    ap.add_argument("--warmup", type=int, default=10)
+    ap = Q.arguments(launches=100, reps=5, warmup=10)
     ap.add_argument("--log2-queries", type=int, default=21)
     ap.add_argument("--radius", type=float, default=3.0)
     ap.add_argument("--check", type=int, default=24, help="queries per set compared with the brute force")
-    ap.add_argument("--out", default=None, help="also write the JSON here")
     a = ap.parse_args()
 
     import point_reference as R
@@ -119,31 +115,11 @@ def main():
 
     stats = DataBuffer(ctx, 1, L.RAY_STATS)
 
-    def counters(name):
-        stats.fill_u32(0)
-        N.check(h, N.lib.lbvh_ray_stats_target(h, stats.device))
-        N.check(h, calls[name][0]())
-        N.check(h, N.lib.lbvh_ray_stats_target(h, None))
-        c = stats.get_data()[0]
-        r = max(int(c["rays"]), 1)
-        return {"active": int(c["rays"]), "node_lines": int(c["node_fetches"]), "triangle_tests": int(c["triangle_tests"]),
-                "node_lines_per_query": round(int(c["node_fetches"]) / r, 3), "triangle_tests_per_query": round(int(c["triangle_tests"]) / r, 3)}
-
-    e0, e1 = ctx.event(), ctx.event()
-
-    def timed(name):
-        fn = calls[name][0]
-        for _ in range(a.warmup):
-            N.check(h, fn())
-        per = []
-        for _ in range(a.reps):
-            ctx.record(e0)
-            for _ in range(a.launches):
-                N.check(h, fn())
-            ctx.record(e1)
-            per.append(ctx.elapsed_ms(e0, e1) / a.launches)
-        per.sort()
-        return per
+    def work(name):
+        c = Q.counters(ctx, stats, calls[name][0])
+        lines, tests = Q.per_active(c)
+        return {"active": c.rays, "node_lines": c.node_fetches, "triangle_tests": c.triangle_tests,
+                "node_lines_per_query": lines, "triangle_tests_per_query": tests}
 
     res = {"workload": "point queries on the cfg2 mesh (1 M triangles), 2^%d queries; (d) %dx%d camera rays" % (a.log2_queries, W, Ht),
            "launches": a.launches, "reps": a.reps, "radius": a.radius,
@@ -152,10 +128,7 @@ def main():
                                "queries_s": round(cpu_pairs / len(tris) / cpu_s, 2)},
            "sets": {}}
     for name in calls:
-        per = timed(name)
-        ms = per[len(per) // 2]
-        row = {"ms": round(ms, 4), "ms_min": round(per[0], 4), "ms_max": round(per[-1], 4), "Mqueries_s": round(n / (ms * 1e-3) / 1e6, 1),
-               **counters(name)}
+        row = {**Q.timed(ctx, calls[name][0], n, a.launches, a.reps, a.warmup, rate="Mqueries_s"), **work(name)}
         key = name.replace("within", "closest")
         if key in found:
             row["found"] = int(found[key].sum())
@@ -168,11 +141,7 @@ def main():
                                                 for x in ("a_closest_surface", "c_closest_uniform_radius")),
         "c_within_ms_minus_closest_ms": round(w_["ms"] - c["ms"], 4),
         "c_spread_ms": round(max(c["ms_max"] - c["ms_min"], w_["ms_max"] - w_["ms_min"]), 4)}
-    line = json.dumps(res)
-    print(line)
-    if a.out:
-        with open(a.out, "w") as f:
-            f.write(line + "\n")
+    Q.emit(res, a.out)
     for b in (qa, qb, qc, rays, out_rec, out_flags, out_hits, stats):
         b.dispose()
     d.on_destroy()

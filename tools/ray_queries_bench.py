@@ -13,28 +13,23 @@ arrays word for word; E2 (b)'s closest records == the unbounded closest records 
 occlusion flag == (active and unbounded t < min(t_max, MAX_FLOAT)).  Times: device events around `--launches` back-to-back
 calls, `--reps` times after `--warmup` calls; per call = median over the reps (min / max beside it).  Node fetches and
 triangle tests per active ray: lbvh_ray_stats_target on one more call of each (the four-wide walker, the default)."""
-import argparse
 import ctypes as C
-import json
 import os
 import sys
 
 import numpy as np
 
+import query_bench as Q
+from query_bench import LIGHT
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
-LIGHT = np.array([0.0, 250.0, 150.0], dtype=np.float32)
-
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--launches", type=int, default=100)
-    ap.add_argument("--reps", type=int, default=5)
-    ap.add_argument("--warmup", type=int, default=10)
+    ap = Q.arguments(launches=100, reps=5, warmup=10)
     ap.add_argument("--width", type=int, default=1920)
     ap.add_argument("--height", type=int, default=1080)
-    ap.add_argument("--out", default=None, help="also write the JSON here")
     a = ap.parse_args()
 
     from unitysimpleraytracing_amd import _native as N
@@ -48,38 +43,20 @@ def main():
     h = ctx.handle
     d = RaytracingMeshDrawer(ctx, scenes.tiled_torus()).awake()
     s = d.container.scene()
-    cam_d = scenes.camera(W, Ht, (0.0, 0.0, 250.0))
-    cam = N.Camera.from_dict(cam_d)
+    cam = N.Camera.from_dict(scenes.camera(W, Ht, (0.0, 0.0, 250.0)))
 
     # primary hits + first-bounce states
-    states = DataBuffer(ctx, n, L.PATH_STATE)
-    prim = DataBuffer(ctx, n, L.HIT)
-    hits = DataBuffer(ctx, n, L.HIT)
-    N.check(h, N.lib.lbvh_trace_primary(h, C.byref(cam), 0, 0, W, Ht, C.byref(s), L.TRACE_FAST, prim.device, None))
-    N.check(h, N.lib.lbvh_path_begin(h, C.byref(cam), states.device))
-    camera_rays = states.get_data().copy()
-    ph = prim.get_data().copy()
-    N.check(h, N.lib.lbvh_buffer_upload(h, hits.device, ph.ctypes.data_as(C.c_void_p), ph.nbytes))
-    N.check(h, N.lib.lbvh_path_first_bounce(h, C.byref(cam), C.byref(s), states.device, hits.device, 9, 0.7, 1e-3))
-    first = states.get_data().copy()
-    live = first["alive"] != 0
+    first, live, hit, origin, set_buffers = Q.ray_sets(ctx, s, cam, W, Ht)
+    states = set_buffers[0]                                  # the first-bounce states on the device
 
-    def ray_buffer(origin, direction, t_min, t_max):
-        b = DataBuffer(ctx, n, L.RAY)
-        b.local["origin"], b.local["dir"], b.local["t_min"], b.local["t_max"] = origin, direction, t_min, t_max
-        b.sync()
-        return b
-
-    sec = ray_buffer(first["origin"], first["dir"], np.float32(1e-3), np.where(live, np.float32(np.inf), np.float32(0.0)))
+    sec = Q.ray_buffer(ctx, first["origin"], first["dir"], np.float32(1e-3), np.where(live, np.float32(np.inf), np.float32(0.0)))
     # (a) once more with the live rays only, compacted on the host: what the inactive rays left in place cost
     sec_live = DataBuffer(ctx, int(live.sum()), L.RAY)
     sec_live.local[:] = sec.local[live]
     sec_live.sync()
-    hit = ph["t"] < L.MAX_FLOAT
-    origin = (camera_rays["origin"] + camera_rays["dir"] * ph["t"][:, None]).astype(np.float32)
     shadow_bound = np.where(hit, np.float32(1.0), np.float32(0.0))
-    shadow = ray_buffer(origin, (LIGHT - origin).astype(np.float32), np.float32(1e-4), shadow_bound)
-    shadow_inf = ray_buffer(origin, (LIGHT - origin).astype(np.float32), np.float32(1e-4), np.where(hit, np.float32(np.inf), np.float32(0.0)))
+    shadow = Q.ray_buffer(ctx, origin, (LIGHT - origin).astype(np.float32), np.float32(1e-4), shadow_bound)
+    shadow_inf = Q.ray_buffer(ctx, origin, (LIGHT - origin).astype(np.float32), np.float32(1e-4), np.where(hit, np.float32(np.inf), np.float32(0.0)))
     out_hits = DataBuffer(ctx, n, L.HIT)
     out_flags = DataBuffer(ctx, n, np.uint32)
 
@@ -120,51 +97,25 @@ def main():
     # ---- work per ray
     stats = DataBuffer(ctx, 1, L.RAY_STATS)
 
-    def counters(name, out):
-        stats.fill_u32(0)
-        N.check(h, N.lib.lbvh_ray_stats_target(h, stats.device))
-        N.check(h, calls[name]())
-        N.check(h, N.lib.lbvh_ray_stats_target(h, None))
-        st = stats.get_data()[0]
-        r = max(int(st["rays"]), 1)
-        return {"rays": int(st["rays"]), "node_fetches_per_ray": round(int(st["node_fetches"]) / r, 3),
-                "triangle_tests_per_ray": round(int(st["triangle_tests"]) / r, 3)}
+    def work(name):
+        c = Q.counters(ctx, stats, calls[name])
+        fetches, tests = Q.per_active(c)
+        return {"rays": c.rays, "node_fetches_per_ray": fetches, "triangle_tests_per_ray": tests}
 
     # ---- times
-    e0, e1 = ctx.event(), ctx.event()
-
-    def timed(name):
-        for _ in range(a.warmup):
-            N.check(h, calls[name]())
-        per = []
-        for _ in range(a.reps):
-            ctx.record(e0)
-            for _ in range(a.launches):
-                N.check(h, calls[name]())
-            ctx.record(e1)
-            per.append(ctx.elapsed_ms(e0, e1) / a.launches)
-        per.sort()
-        return per
-
     res = {"workload": "ray queries on the cfg2 mesh (1 M triangles), %dx%d" % (W, Ht), "launches": a.launches, "reps": a.reps,
            "equalities": "E1 (a) word for word, E2 (b), E3 (b) and (c): hold", "sets": {}}
     active = {"a": int(live.sum()), "b": int(hit.sum()), "c": int(live.sum())}
     for name in calls:
-        per = timed(name)
-        ms = per[len(per) // 2]
         k = name[0]
-        res["sets"][name] = {"ms": round(ms, 4), "ms_min": round(per[0], 4), "ms_max": round(per[-1], 4),
+        t = Q.timed(ctx, calls[name], active[k], a.launches, a.reps, a.warmup)
+        res["sets"][name] = {"ms": t["ms"], "ms_min": t["ms_min"], "ms_max": t["ms_max"],
                              "rays_in_buffer": int(live.sum()) if "live_only" in name else n, "active_rays": active[k],
-                             "Mrays_s_active": round(active[k] / (ms * 1e-3) / 1e6, 1),
-                             **counters(name, out_flags if "occluded" in name else out_hits)}
+                             "Mrays_s_active": t["Mrays_s_active"], **work(name)}
     res["sets"]["b_trace_occluded"]["occluded_rays"] = int(b_occ.sum())
     res["sets"]["c_trace_occluded"]["occluded_rays"] = int(c_occ.sum())
-    line = json.dumps(res)
-    print(line)
-    if a.out:
-        with open(a.out, "w") as f:
-            f.write(line + "\n")
-    for b in (states, prim, hits, sec, sec_live, shadow, shadow_inf, out_hits, out_flags, stats):
+    Q.emit(res, a.out)
+    for b in set_buffers + [sec, sec_live, shadow, shadow_inf, out_hits, out_flags, stats]:
         b.dispose()
     d.on_destroy()
     ctx.close()

@@ -10,13 +10,13 @@ Before anything is printed the outputs are checked: the flags equal (t < LBVH_MA
 `--check` casts of each radius against tests/sweep_reference.py (brute force over all triangles, word for word).  Times: device
 events around `--launches` back-to-back calls, `--reps` times after `--warmup` calls (the clocks settle there); per call = median
 over the reps (min / max beside it: the spread)."""
-import argparse
 import ctypes as C
-import json
 import os
 import sys
 
 import numpy as np
+
+import query_bench as Q
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -26,13 +26,9 @@ RADII = (0.005, 0.02, 0.1)
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--launches", type=int, default=10)
-    ap.add_argument("--reps", type=int, default=5)
-    ap.add_argument("--warmup", type=int, default=3)
+    ap = Q.arguments(launches=10, reps=5, warmup=3)
     ap.add_argument("--casts", type=int, default=1 << 20)
     ap.add_argument("--check", type=int, default=16, help="casts of each radius compared with the brute force")
-    ap.add_argument("--out", default=None, help="also write the JSON here")
     a = ap.parse_args()
 
     import sweep_reference as S
@@ -68,30 +64,13 @@ def main():
     rec = DataBuffer(ctx, n, L.HIT)
     flg = DataBuffer(ctx, n, np.uint32)
     stats = DataBuffer(ctx, 1, L.RAY_STATS)
-    e0, e1 = ctx.event(), ctx.event()
 
-    def counters(fn):
-        stats.fill_u32(0)
-        N.check(h, N.lib.lbvh_ray_stats_target(h, stats.device))
-        N.check(h, fn())
-        N.check(h, N.lib.lbvh_ray_stats_target(h, None))
-        c = stats.get_data()[0]
-        r = max(int(c["rays"]), 1)
-        return {"steps_per_cast": round(int(c["node_fetches"]) / r, 3), "triangle_tests_per_cast": round(int(c["triangle_tests"]) / r, 3)}
+    def work(fn):
+        steps, tests = Q.per_active(Q.counters(ctx, stats, fn))
+        return {"steps_per_cast": steps, "triangle_tests_per_cast": tests}
 
-    def timed(fn):
-        for _ in range(a.warmup):
-            N.check(h, fn())
-        per = []
-        for _ in range(a.reps):
-            ctx.record(e0)
-            for _ in range(a.launches):
-                N.check(h, fn())
-            ctx.record(e1)
-            per.append(ctx.elapsed_ms(e0, e1) / a.launches)
-        per.sort()
-        ms = per[len(per) // 2]
-        return {"ms": round(ms, 4), "ms_min": round(per[0], 4), "ms_max": round(per[-1], 4), "Mcasts_s": round(n / (ms * 1e-3) / 1e6, 1)}
+    def times(fn):
+        return Q.timed(ctx, fn, n, a.launches, a.reps, a.warmup, rate="Mcasts_s")
 
     closest = lambda: N.lib.lbvh_trace_closest(h, rays.device, n, C.byref(s), rec.device)
     cast = lambda: N.lib.lbvh_sphere_cast(h, casts.device, n, C.byref(s), rec.device)
@@ -101,7 +80,7 @@ def main():
            "launches": a.launches, "reps": a.reps,
            "checks": "flags == (t < LBVH_MAX_FLOAT) on every cast; records and flags word for word against the brute force on %d casts "
                      "of each radius: hold" % a.check,
-           "trace_closest": {**timed(closest), **counters(closest)}, "radius": {}}
+           "trace_closest": {**times(closest), **work(closest)}, "radius": {}}
     for radius in RADII:
         casts.local["origin"], casts.local["dir"] = origin, direction
         casts.local["radius"], casts.local["t_max"] = np.float32(radius * extent), np.float32(np.inf)
@@ -116,14 +95,9 @@ def main():
         assert (np.ascontiguousarray(got[sub]).view(np.uint32) == ref.records.view(np.uint32)).all(), "records, radius %g" % radius
         assert (flags[sub] == ref.flags).all(), "flags, radius %g" % radius
         res["radius"][str(radius)] = {"radius": round(radius * extent, 4), "touching": int(flags.sum()), "start_in_overlap": int((got["t"] == 0).sum()),
-                                      "sphere_cast": {**timed(cast), **counters(cast)},
-                                      "sphere_cast_any": {**timed(cast_any), **counters(cast_any)}}
-    line = json.dumps(res)
-    print(line)
-    if a.out:
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-        with open(a.out, "w") as f:
-            f.write(line + "\n")
+                                      "sphere_cast": {**times(cast), **work(cast)},
+                                      "sphere_cast_any": {**times(cast_any), **work(cast_any)}}
+    Q.emit(res, a.out)
     for b in (casts, rays, rec, flg, stats):
         b.dispose()
     d.on_destroy()

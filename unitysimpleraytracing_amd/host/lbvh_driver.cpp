@@ -90,6 +90,60 @@ static lbvh_camera camera_at(int w, int h, float z, float yaw_deg = 0.0f)
     return cam;
 }
 
+// the mesh argument of the query sub-commands: a triangle count (the cfg1 mesh) or an OBJ asset (MeshBufferContainer.cs:117-146)
+static std::vector<lbvh_triangle> load_mesh(const char* what)
+{
+    const size_t len = std::strlen(what);
+    const bool from_obj = len > 4 && std::strcmp(what + len - 4, ".obj") == 0;
+    return from_obj ? lbvh::MeshTriangles(lbvh::LoadObj(what)) : random_mesh((uint32_t)atoi(what));
+}
+
+// the box of the vertices
+static void mesh_box(const std::vector<lbvh_triangle>& mesh, float lo[3], float hi[3])
+{
+    for (int k = 0; k < 3; k++) { lo[k] = INFINITY; hi[k] = -INFINITY; }
+    for (const auto& t : mesh)
+        for (int k = 0; k < 3; k++) {
+            lo[k] = std::fmin(lo[k], std::fmin(t.a[k], std::fmin(t.b[k], t.c[k])));
+            hi[k] = std::fmax(hi[k], std::fmax(t.a[k], std::fmax(t.b[k], t.c[k])));
+        }
+}
+
+// points uniform in the box grown by a quarter of its extent per side, every one with the same max_dist2; draws axis by axis
+static void points_around(const float lo[3], const float hi[3], uint64_t seed, float max_dist2, std::vector<lbvh_point_query>& points)
+{
+    for (auto& q : points) {
+        for (int k = 0; k < 3; k++) {
+            const float grow = 0.25f * (hi[k] - lo[k]);
+            q.p[k] = uniform(seed, lo[k] - grow, hi[k] + grow);
+        }
+        q.max_dist2 = max_dist2;
+    }
+}
+
+// origin and dir of lbvh_ray or lbvh_sphere_ray records: from points around the box (as points_around) towards points inside it,
+// t = 1 at the target; per axis the origin is drawn before the target.  The fourth float of each half is the caller's
+template <class Ray>
+static void rays_into(const float lo[3], const float hi[3], uint64_t seed, std::vector<Ray>& rays)
+{
+    for (auto& r : rays)
+        for (int k = 0; k < 3; k++) {
+            const float grow = 0.25f * (hi[k] - lo[k]);
+            r.origin[k] = uniform(seed, lo[k] - grow, hi[k] + grow);
+            r.dir[k] = uniform(seed, lo[k], hi[k]) - r.origin[k];
+        }
+}
+
+// the sum of the four 32-bit words of a 16-byte record (lbvh_hit, lbvh_closest_point)
+template <class Record>
+static uint64_t word_sum(const Record& record)
+{
+    static_assert(sizeof(Record) == 16, "four words");
+    uint32_t w[4];
+    std::memcpy(w, &record, sizeof w);
+    return (uint64_t)w[0] + w[1] + w[2] + w[3];
+}
+
 // BASELINE configs[2] through the one-process host: every frame of every camera / mode assembled from <ranks> shares must
 // equal the frame one context traces alone, the assembled buffer poisoned before each frame
 static int multi_main(int argc, char** argv)
@@ -101,52 +155,47 @@ static int multi_main(int argc, char** argv)
     // frame (system-scope loads and compare-and-swaps on peer memory): ADVICE r4
     const bool doubled = argc > 6 && std::strcmp(argv[6], "doubled") == 0;
     const std::vector<lbvh_triangle> mesh = random_mesh(n, doubled);
-    try {
-        const int n_dev = lbvh::Context::device_count();
-        if (n_dev <= 0) { std::fprintf(stderr, "no HIP device visible\n"); return 1; }
-        std::vector<int> devices;
-        for (int r = 0; r < ranks; r++) devices.push_back(r % n_dev);
-        lbvh::MultiGpuDrawer multi(devices, mesh);
-        multi.Awake();
-        lbvh::Context one(0);
-        lbvh::RaytracingMeshDrawer single(one, mesh);
-        single.Awake();
-        int frames = 0, equal = 0;
-        size_t hits = 0;
-        for (int mode : {LBVH_TRACE_FAST, LBVH_TRACE_REFERENCE, LBVH_TRACE_FAST_EXACT})
-            for (int f = 0; f < 4; f++) {
-                // two frames from one camera (the second is dispatched by the first one's costs), then a turned one, then a
-                // rebuilt scene
-                const lbvh_camera cam = camera_at(w, h, 300.0f, f < 2 ? 0.0f : 2.0f * f);
-                if (f == 3) { multi.Rebuild(); single.Rebuild(); }
-                if (frames) multi.Hits().Fill(0x7FC00000u, false);            // poison: a missing tile cannot pass on old values
-                multi.Update(cam, mode);
-                single.Update(cam, mode);
-                multi.Hits().GetData();                                      // on the owner's stream: behind the device-side gather
+    const int n_dev = lbvh::Context::device_count();
+    if (n_dev <= 0) { std::fprintf(stderr, "no HIP device visible\n"); return 1; }
+    std::vector<int> devices;
+    for (int r = 0; r < ranks; r++) devices.push_back(r % n_dev);
+    lbvh::MultiGpuDrawer multi(devices, mesh);
+    multi.Awake();
+    lbvh::Context one(0);
+    lbvh::RaytracingMeshDrawer single(one, mesh);
+    single.Awake();
+    int frames = 0, equal = 0;
+    size_t hits = 0;
+    for (int mode : {LBVH_TRACE_FAST, LBVH_TRACE_REFERENCE, LBVH_TRACE_FAST_EXACT})
+        for (int f = 0; f < 4; f++) {
+            // two frames from one camera (the second is dispatched by the first one's costs), then a turned one, then a
+            // rebuilt scene
+            const lbvh_camera cam = camera_at(w, h, 300.0f, f < 2 ? 0.0f : 2.0f * f);
+            if (f == 3) { multi.Rebuild(); single.Rebuild(); }
+            if (frames) multi.Hits().Fill(0x7FC00000u, false);            // poison: a missing tile cannot pass on old values
+            multi.Update(cam, mode);
+            single.Update(cam, mode);
+            multi.Hits().GetData();                                      // on the owner's stream: behind the device-side gather
+            single.Hits().GetData();
+            const bool same = std::memcmp(multi.Hits().LocalBuffer().data(), single.Hits().LocalBuffer().data(),
+                                          (size_t)w * h * sizeof(lbvh_hit)) == 0;
+            frames++;
+            equal += same ? 1 : 0;
+            if (mode == LBVH_TRACE_FAST_EXACT) {      // ... and the exact mode's frame is the reference mode's, word for word
+                // (include/lbvh.h: except at a pixel whose reference winner lies in front of its own triangle's box — this
+                // scene and these cameras have none; the general case is checked against the oracle by the Python suite)
+                single.Update(cam, LBVH_TRACE_REFERENCE);
                 single.Hits().GetData();
-                const bool same = std::memcmp(multi.Hits().LocalBuffer().data(), single.Hits().LocalBuffer().data(),
-                                              (size_t)w * h * sizeof(lbvh_hit)) == 0;
-                frames++;
-                equal += same ? 1 : 0;
-                if (mode == LBVH_TRACE_FAST_EXACT) {      // ... and the exact mode's frame is the reference mode's, word for word
-                    // (include/lbvh.h: except at a pixel whose reference winner lies in front of its own triangle's box — this
-                    // scene and these cameras have none; the general case is checked against the oracle by the Python suite)
-                    single.Update(cam, LBVH_TRACE_REFERENCE);
-                    single.Hits().GetData();
-                    if (std::memcmp(multi.Hits().LocalBuffer().data(), single.Hits().LocalBuffer().data(), (size_t)w * h * sizeof(lbvh_hit)) != 0)
-                        equal--;
-                }
-                if (mode == LBVH_TRACE_REFERENCE && f == 0)
-                    for (size_t i = 0; i < (size_t)w * h; i++) hits += multi.Hits().LocalBuffer()[i].t < LBVH_MAX_FLOAT ? 1 : 0;
+                if (std::memcmp(multi.Hits().LocalBuffer().data(), single.Hits().LocalBuffer().data(), (size_t)w * h * sizeof(lbvh_hit)) != 0)
+                    equal--;
             }
-        multi.Sync();
-        std::printf("{\"ranks\": %d, \"devices\": %d, \"triangles\": %u, \"rays\": %d, \"frames\": %d, \"frames_equal\": %d, \"hits\": %zu}\n",
-                    ranks, n_dev, n, w * h, frames, equal, hits);
-        return equal == frames ? 0 : 2;
-    } catch (const lbvh::Error& e) {
-        std::fprintf(stderr, "%s\n", e.what());
-        return 1;
-    }
+            if (mode == LBVH_TRACE_REFERENCE && f == 0)
+                for (size_t i = 0; i < (size_t)w * h; i++) hits += multi.Hits().LocalBuffer()[i].t < LBVH_MAX_FLOAT ? 1 : 0;
+        }
+    multi.Sync();
+    std::printf("{\"ranks\": %d, \"devices\": %d, \"triangles\": %u, \"rays\": %d, \"frames\": %d, \"frames_equal\": %d, \"hits\": %zu}\n",
+                ranks, n_dev, n, w * h, frames, equal, hits);
+    return equal == frames ? 0 : 2;
 }
 
 // `sort <ranks> <n> [replicate]`: n (key, value) pairs in uneven blocks over `ranks` contexts (devices dealt round-robin; one
@@ -178,45 +227,40 @@ static int sort_main(int argc, char** argv)
         bv[r].assign(values.begin() + lo, values.begin() + hi);
         lo = hi;
     }
-    try {
-        const int n_dev = lbvh::Context::device_count();
-        if (n_dev <= 0) { std::fprintf(stderr, "no HIP device visible\n"); return 1; }
-        std::vector<int> devices;
-        for (int r = 0; r < ranks; r++) devices.push_back(r % n_dev);
-        lbvh::MultiGpuSorter sorter(devices);
-        sorter.SetBlocks(bk, bv);
-        auto t0 = std::chrono::steady_clock::now();
-        const std::vector<uint32_t> counts = sorter.Sort(replicate);
-        sorter.Sync();
-        const double sharded_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-        // the one-context sort of the whole sequence
-        lbvh::Context one(0);
-        lbvh::DataBuffer<uint32_t> k1(one, n ? n : 1), v1(one, n ? n : 1);
-        std::copy(keys.begin(), keys.end(), k1.LocalBuffer().begin());
-        std::copy(values.begin(), values.end(), v1.LocalBuffer().begin());
-        k1.Sync(); v1.Sync();
-        lbvh::check(one.get(), lbvh_sort_pairs(one.get(), (uint32_t*)k1.DeviceBuffer(), (uint32_t*)v1.DeviceBuffer(), n));
-        k1.GetData(); v1.GetData();
-        bool equal = true;
-        uint64_t at = 0;
-        for (int q = 0; q < ranks; q++) {
-            sorter.OutKeys(q).GetData();
-            sorter.OutValues(q).GetData();
-            const uint64_t from = replicate ? 0 : at, len = replicate ? n : counts[q];
-            equal = equal && std::memcmp(sorter.OutKeys(q).LocalBuffer().data(), k1.LocalBuffer().data() + from, len * 4) == 0 &&
-                    std::memcmp(sorter.OutValues(q).LocalBuffer().data(), v1.LocalBuffer().data() + from, len * 4) == 0;
-            at += counts[q];
-        }
-        equal = equal && at == n;
-        std::printf("{\"ranks\": %d, \"devices\": %d, \"pairs\": %u, \"replicate\": %s, \"slice_counts\": [", ranks, n_dev, n,
-                    replicate ? "true" : "false");
-        for (int q = 0; q < ranks; q++) std::printf("%s%u", q ? ", " : "", counts[q]);
-        std::printf("], \"host_ms\": %.3f, \"equal\": %s}\n", sharded_ms, equal ? "true" : "false");
-        return equal ? 0 : 2;
-    } catch (const lbvh::Error& e) {
-        std::fprintf(stderr, "%s\n", e.what());
-        return 1;
+    const int n_dev = lbvh::Context::device_count();
+    if (n_dev <= 0) { std::fprintf(stderr, "no HIP device visible\n"); return 1; }
+    std::vector<int> devices;
+    for (int r = 0; r < ranks; r++) devices.push_back(r % n_dev);
+    lbvh::MultiGpuSorter sorter(devices);
+    sorter.SetBlocks(bk, bv);
+    auto t0 = std::chrono::steady_clock::now();
+    const std::vector<uint32_t> counts = sorter.Sort(replicate);
+    sorter.Sync();
+    const double sharded_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    // the one-context sort of the whole sequence
+    lbvh::Context one(0);
+    lbvh::DataBuffer<uint32_t> k1(one, n ? n : 1), v1(one, n ? n : 1);
+    std::copy(keys.begin(), keys.end(), k1.LocalBuffer().begin());
+    std::copy(values.begin(), values.end(), v1.LocalBuffer().begin());
+    k1.Sync(); v1.Sync();
+    lbvh::check(one.get(), lbvh_sort_pairs(one.get(), (uint32_t*)k1.DeviceBuffer(), (uint32_t*)v1.DeviceBuffer(), n));
+    k1.GetData(); v1.GetData();
+    bool equal = true;
+    uint64_t at = 0;
+    for (int q = 0; q < ranks; q++) {
+        sorter.OutKeys(q).GetData();
+        sorter.OutValues(q).GetData();
+        const uint64_t from = replicate ? 0 : at, len = replicate ? n : counts[q];
+        equal = equal && std::memcmp(sorter.OutKeys(q).LocalBuffer().data(), k1.LocalBuffer().data() + from, len * 4) == 0 &&
+                std::memcmp(sorter.OutValues(q).LocalBuffer().data(), v1.LocalBuffer().data() + from, len * 4) == 0;
+        at += counts[q];
     }
+    equal = equal && at == n;
+    std::printf("{\"ranks\": %d, \"devices\": %d, \"pairs\": %u, \"replicate\": %s, \"slice_counts\": [", ranks, n_dev, n,
+                replicate ? "true" : "false");
+    for (int q = 0; q < ranks; q++) std::printf("%s%u", q ? ", " : "", counts[q]);
+    std::printf("], \"host_ms\": %.3f, \"equal\": %s}\n", sharded_ms, equal ? "true" : "false");
+    return equal ? 0 : 2;
 }
 
 static int rays_main(int argc, char** argv)
@@ -225,175 +269,135 @@ static int rays_main(int argc, char** argv)
     const int w = argc > 3 ? atoi(argv[3]) : 256, h = argc > 4 ? atoi(argv[4]) : 256;
     const size_t count = (size_t)w * h;
     const float light[3] = {0.0f, 250.0f, 150.0f};
-    try {
-        lbvh::Context ctx(0);
-        lbvh::RaytracingMeshDrawer drawer(ctx, random_mesh(n));
-        drawer.Awake();
-        const lbvh_camera cam = camera_at(w, h, 300.0f);
-        drawer.Update(cam, LBVH_TRACE_FAST);
-        lbvh::DataBuffer<lbvh_path_state> primary(ctx, count);          // the camera rays, as the primary trace made them
-        lbvh::check(ctx.get(), lbvh_path_begin(ctx.get(), &cam, (lbvh_path_state*)primary.DeviceBuffer()));
-        primary.GetData();
-        drawer.Hits().GetData();
-        lbvh::DataBuffer<lbvh_ray> rays(ctx, count);
-        for (size_t i = 0; i < count; i++) {
-            const lbvh_path_state& p = primary.LocalBuffer()[i];
-            const float t = drawer.Hits().LocalBuffer()[i].t;
-            lbvh_ray& r = rays.LocalBuffer()[i];
-            std::memset(&r, 0, sizeof r);                                 // t_min = t_max = 0: inactive
-            if (!(t < LBVH_MAX_FLOAT)) continue;
-            for (int k = 0; k < 3; k++) {
-                r.origin[k] = p.origin[k] + p.dir[k] * t;
-                r.dir[k] = light[k] - r.origin[k];
-            }
-            r.t_min = 1e-4f;
-            r.t_max = 1.0f;
+    lbvh::Context ctx(0);
+    lbvh::RaytracingMeshDrawer drawer(ctx, random_mesh(n));
+    drawer.Awake();
+    const lbvh_camera cam = camera_at(w, h, 300.0f);
+    drawer.Update(cam, LBVH_TRACE_FAST);
+    lbvh::DataBuffer<lbvh_path_state> primary(ctx, count);          // the camera rays, as the primary trace made them
+    lbvh::check(ctx.get(), lbvh_path_begin(ctx.get(), &cam, (lbvh_path_state*)primary.DeviceBuffer()));
+    primary.GetData();
+    drawer.Hits().GetData();
+    lbvh::DataBuffer<lbvh_ray> rays(ctx, count);
+    for (size_t i = 0; i < count; i++) {
+        const lbvh_path_state& p = primary.LocalBuffer()[i];
+        const float t = drawer.Hits().LocalBuffer()[i].t;
+        lbvh_ray& r = rays.LocalBuffer()[i];
+        std::memset(&r, 0, sizeof r);                                 // t_min = t_max = 0: inactive
+        if (!(t < LBVH_MAX_FLOAT)) continue;
+        for (int k = 0; k < 3; k++) {
+            r.origin[k] = p.origin[k] + p.dir[k] * t;
+            r.dir[k] = light[k] - r.origin[k];
         }
-        rays.Sync();
-        lbvh::DataBuffer<lbvh_hit> closest(ctx, count), unbounded(ctx, count);
-        lbvh::DataBuffer<uint32_t> occluded(ctx, count);
-        drawer.TraceClosest(rays, closest);
-        drawer.TraceOccluded(rays, occluded);
-        for (auto& r : rays.LocalBuffer())
-            if (r.t_max > 0.0f) r.t_max = INFINITY;
-        rays.Sync();
-        drawer.TraceClosest(rays, unbounded);
-        closest.GetData();
-        unbounded.GetData();
-        occluded.GetData();
-        size_t hits = 0, n_occluded = 0;
-        double tsum = 0;
-        bool e3 = true;
-        for (size_t i = 0; i < count; i++) {
-            const lbvh_hit& c = closest.LocalBuffer()[i];
-            if (c.t < LBVH_MAX_FLOAT) { hits++; tsum += c.t; }
-            const uint32_t o = occluded.LocalBuffer()[i];
-            n_occluded += o;
-            const bool active = rays.LocalBuffer()[i].t_max > 0.0f;
-            e3 = e3 && o == (uint32_t)(active && unbounded.LocalBuffer()[i].t < 1.0f);
-        }
-        std::printf("{\"triangles\": %u, \"rays\": %zu, \"hits\": %zu, \"t_sum\": %.6f, \"occluded\": %zu, \"e3_holds\": %s}\n", n, count,
-                    hits, tsum, n_occluded, e3 ? "true" : "false");
-    } catch (const lbvh::Error& e) {
-        std::fprintf(stderr, "%s\n", e.what());
-        return 1;
+        r.t_min = 1e-4f;
+        r.t_max = 1.0f;
     }
+    rays.Sync();
+    lbvh::DataBuffer<lbvh_hit> closest(ctx, count), unbounded(ctx, count);
+    lbvh::DataBuffer<uint32_t> occluded(ctx, count);
+    drawer.TraceClosest(rays, closest);
+    drawer.TraceOccluded(rays, occluded);
+    for (auto& r : rays.LocalBuffer())
+        if (r.t_max > 0.0f) r.t_max = INFINITY;
+    rays.Sync();
+    drawer.TraceClosest(rays, unbounded);
+    closest.GetData();
+    unbounded.GetData();
+    occluded.GetData();
+    size_t hits = 0, n_occluded = 0;
+    double tsum = 0;
+    bool e3 = true;
+    for (size_t i = 0; i < count; i++) {
+        const lbvh_hit& c = closest.LocalBuffer()[i];
+        if (c.t < LBVH_MAX_FLOAT) { hits++; tsum += c.t; }
+        const uint32_t o = occluded.LocalBuffer()[i];
+        n_occluded += o;
+        const bool active = rays.LocalBuffer()[i].t_max > 0.0f;
+        e3 = e3 && o == (uint32_t)(active && unbounded.LocalBuffer()[i].t < 1.0f);
+    }
+    std::printf("{\"triangles\": %u, \"rays\": %zu, \"hits\": %zu, \"t_sum\": %.6f, \"occluded\": %zu, \"e3_holds\": %s}\n", n, count,
+                hits, tsum, n_occluded, e3 ? "true" : "false");
     return 0;
 }
 
 static int points_main(int argc, char** argv)
 {
-    const char* what = argc > 2 ? argv[2] : "4096";
-    const size_t len = std::strlen(what);
-    const bool from_obj = len > 4 && std::strcmp(what + len - 4, ".obj") == 0;
     const size_t count = argc > 3 ? (size_t)strtoull(argv[3], nullptr, 10) : 65536;
     const float radius = argc > 4 ? (float)atof(argv[4]) : INFINITY;
-    try {
-        const std::vector<lbvh_triangle> mesh = from_obj ? lbvh::MeshTriangles(lbvh::LoadObj(what)) : random_mesh((uint32_t)atoi(what));
-        float lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
-        for (const auto& t : mesh)
-            for (int k = 0; k < 3; k++) {
-                lo[k] = std::fmin(lo[k], std::fmin(t.a[k], std::fmin(t.b[k], t.c[k])));
-                hi[k] = std::fmax(hi[k], std::fmax(t.a[k], std::fmax(t.b[k], t.c[k])));
-            }
-        lbvh::Context ctx(0);
-        lbvh::RaytracingMeshDrawer drawer(ctx, mesh);
-        drawer.Awake();
-        lbvh::DataBuffer<lbvh_point_query> queries(ctx, count);
-        uint64_t seed = 2;
-        for (auto& q : queries.LocalBuffer()) {
-            for (int k = 0; k < 3; k++) {
-                const float grow = 0.25f * (hi[k] - lo[k]);
-                q.p[k] = uniform(seed, lo[k] - grow, hi[k] + grow);
-            }
-            q.max_dist2 = radius * radius;
-        }
-        queries.Sync();
-        lbvh::DataBuffer<lbvh_closest_point> closest(ctx, count);
-        lbvh::DataBuffer<uint32_t> within(ctx, count);
-        drawer.ClosestPoints(queries, closest);
-        drawer.WithinDistance(queries, within);
-        closest.GetData();
-        within.GetData();
-        size_t found = 0, n_within = 0;
-        uint64_t word_sum = 0;
-        for (size_t i = 0; i < count; i++) {
-            const lbvh_closest_point& c = closest.LocalBuffer()[i];
-            if (c.dist2 < LBVH_MAX_FLOAT) found++;
-            uint32_t w[4];
-            std::memcpy(w, &c, sizeof w);
-            word_sum += (uint64_t)w[0] + w[1] + w[2] + w[3];
-            n_within += within.LocalBuffer()[i];
-        }
-        std::printf("{\"triangles\": %zu, \"points\": %zu, \"found\": %zu, \"word_sum\": %llu, \"within\": %zu}\n", mesh.size(), count, found,
-                    (unsigned long long)word_sum, n_within);
-    } catch (const std::exception& e) {
-        std::fprintf(stderr, "%s\n", e.what());
-        return 1;
+    const std::vector<lbvh_triangle> mesh = load_mesh(argc > 2 ? argv[2] : "4096");
+    float lo[3], hi[3];
+    mesh_box(mesh, lo, hi);
+    lbvh::Context ctx(0);
+    lbvh::RaytracingMeshDrawer drawer(ctx, mesh);
+    drawer.Awake();
+    lbvh::DataBuffer<lbvh_point_query> queries(ctx, count);
+    points_around(lo, hi, 2, radius * radius, queries.LocalBuffer());
+    queries.Sync();
+    lbvh::DataBuffer<lbvh_closest_point> closest(ctx, count);
+    lbvh::DataBuffer<uint32_t> within(ctx, count);
+    drawer.ClosestPoints(queries, closest);
+    drawer.WithinDistance(queries, within);
+    closest.GetData();
+    within.GetData();
+    size_t found = 0, n_within = 0;
+    uint64_t words = 0;
+    for (size_t i = 0; i < count; i++) {
+        const lbvh_closest_point& c = closest.LocalBuffer()[i];
+        if (c.dist2 < LBVH_MAX_FLOAT) found++;
+        words += word_sum(c);
+        n_within += within.LocalBuffer()[i];
     }
+    std::printf("{\"triangles\": %zu, \"points\": %zu, \"found\": %zu, \"word_sum\": %llu, \"within\": %zu}\n", mesh.size(), count, found,
+                (unsigned long long)words, n_within);
     return 0;
+}
+
+static float first_of(const lbvh_closest_point& c) { return c.dist2; }
+static float first_of(const lbvh_hit& h) { return h.t; }
+
+// what knn and khits print of their count * k records: the sum of the found counts, how many rows are full, the word sum and the
+// first rows as [dist2 or t, tri] pairs.  Record: lbvh_closest_point or lbvh_hit (the same 16-byte shape)
+template <class Record>
+static void print_rows(const char* queries, size_t triangles, size_t count, uint32_t k, const std::vector<Record>& rows,
+                       const std::vector<uint32_t>& found)
+{
+    size_t found_sum = 0, full = 0;
+    uint64_t words = 0;
+    for (size_t i = 0; i < count; i++) {
+        found_sum += found[i];
+        full += found[i] == k;
+    }
+    for (const Record& c : rows) words += word_sum(c);
+    std::printf("{\"triangles\": %zu, \"%s\": %zu, \"k\": %u, \"found_sum\": %zu, \"full_rows\": %zu, \"word_sum\": %llu, \"rows\": [",
+                triangles, queries, count, k, found_sum, full, (unsigned long long)words);
+    for (size_t i = 0; i < std::min<size_t>(count, 3); i++) {
+        std::printf("%s[", i ? ", " : "");
+        for (uint32_t j = 0; j < found[i]; j++) std::printf("%s[%.9g, %u]", j ? ", " : "", first_of(rows[i * k + j]), rows[i * k + j].tri);
+        std::printf("]");
+    }
+    std::printf("]}\n");
 }
 
 static int knn_main(int argc, char** argv)
 {
     const uint32_t k = argc > 2 ? (uint32_t)atoi(argv[2]) : 8;
-    const char* what = argc > 3 ? argv[3] : "4096";
-    const size_t len = std::strlen(what);
-    const bool from_obj = len > 4 && std::strcmp(what + len - 4, ".obj") == 0;
     const size_t count = argc > 4 ? (size_t)strtoull(argv[4], nullptr, 10) : 65536;
     const float radius = argc > 5 ? (float)atof(argv[5]) : INFINITY;
-    try {
-        const std::vector<lbvh_triangle> mesh = from_obj ? lbvh::MeshTriangles(lbvh::LoadObj(what)) : random_mesh((uint32_t)atoi(what));
-        float lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
-        for (const auto& t : mesh)
-            for (int a = 0; a < 3; a++) {
-                lo[a] = std::fmin(lo[a], std::fmin(t.a[a], std::fmin(t.b[a], t.c[a])));
-                hi[a] = std::fmax(hi[a], std::fmax(t.a[a], std::fmax(t.b[a], t.c[a])));
-            }
-        lbvh::Context ctx(0);
-        lbvh::RaytracingMeshDrawer drawer(ctx, mesh);
-        drawer.Awake();
-        lbvh::DataBuffer<lbvh_point_query> queries(ctx, count);
-        uint64_t seed = 2;
-        for (auto& q : queries.LocalBuffer()) {
-            for (int a = 0; a < 3; a++) {
-                const float grow = 0.25f * (hi[a] - lo[a]);
-                q.p[a] = uniform(seed, lo[a] - grow, hi[a] + grow);
-            }
-            q.max_dist2 = radius * radius;
-        }
-        queries.Sync();
-        lbvh::DataBuffer<lbvh_closest_point> rows(ctx, count * (size_t)k);
-        lbvh::DataBuffer<uint32_t> found(ctx, count);
-        drawer.KClosestPoints(queries, k, rows, &found);
-        rows.GetData();
-        found.GetData();
-        size_t found_sum = 0, full = 0;
-        uint64_t word_sum = 0;
-        for (size_t i = 0; i < count; i++) {
-            found_sum += found.LocalBuffer()[i];
-            full += found.LocalBuffer()[i] == k;
-        }
-        for (const lbvh_closest_point& c : rows.LocalBuffer()) {
-            uint32_t w[4];
-            std::memcpy(w, &c, sizeof w);
-            word_sum += (uint64_t)w[0] + w[1] + w[2] + w[3];
-        }
-        std::printf("{\"triangles\": %zu, \"points\": %zu, \"k\": %u, \"found_sum\": %zu, \"full_rows\": %zu, \"word_sum\": %llu, \"rows\": [",
-                    mesh.size(), count, k, found_sum, full, (unsigned long long)word_sum);
-        for (size_t i = 0; i < std::min<size_t>(count, 3); i++) {
-            std::printf("%s[", i ? ", " : "");
-            for (uint32_t j = 0; j < found.LocalBuffer()[i]; j++) {
-                const lbvh_closest_point& c = rows.LocalBuffer()[i * k + j];
-                std::printf("%s[%.9g, %u]", j ? ", " : "", c.dist2, c.tri);
-            }
-            std::printf("]");
-        }
-        std::printf("]}\n");
-    } catch (const std::exception& e) {
-        std::fprintf(stderr, "%s\n", e.what());
-        return 1;
-    }
+    const std::vector<lbvh_triangle> mesh = load_mesh(argc > 3 ? argv[3] : "4096");
+    float lo[3], hi[3];
+    mesh_box(mesh, lo, hi);
+    lbvh::Context ctx(0);
+    lbvh::RaytracingMeshDrawer drawer(ctx, mesh);
+    drawer.Awake();
+    lbvh::DataBuffer<lbvh_point_query> queries(ctx, count);
+    points_around(lo, hi, 2, radius * radius, queries.LocalBuffer());
+    queries.Sync();
+    lbvh::DataBuffer<lbvh_closest_point> rows(ctx, count * (size_t)k);
+    lbvh::DataBuffer<uint32_t> found(ctx, count);
+    drawer.KClosestPoints(queries, k, rows, &found);
+    rows.GetData();
+    found.GetData();
+    print_rows("points", mesh.size(), count, k, rows.LocalBuffer(), found.LocalBuffer());
     return 0;
 }
 
@@ -403,60 +407,22 @@ static int khits_main(int argc, char** argv)
     const uint32_t n = argc > 3 ? (uint32_t)atoi(argv[3]) : 4096;
     const size_t count = argc > 4 ? (size_t)strtoull(argv[4], nullptr, 10) : 65536;
     const float t_max = argc > 5 ? (float)atof(argv[5]) : INFINITY;
-    try {
-        const std::vector<lbvh_triangle> mesh = random_mesh(n);
-        float lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
-        for (const auto& t : mesh)
-            for (int a = 0; a < 3; a++) {
-                lo[a] = std::fmin(lo[a], std::fmin(t.a[a], std::fmin(t.b[a], t.c[a])));
-                hi[a] = std::fmax(hi[a], std::fmax(t.a[a], std::fmax(t.b[a], t.c[a])));
-            }
-        lbvh::Context ctx(0);
-        lbvh::RaytracingMeshDrawer drawer(ctx, mesh);
-        drawer.Awake();
-        lbvh::DataBuffer<lbvh_ray> rays(ctx, count);
-        uint64_t seed = 3;
-        for (auto& r : rays.LocalBuffer()) {
-            for (int a = 0; a < 3; a++) {
-                const float grow = 0.25f * (hi[a] - lo[a]);
-                r.origin[a] = uniform(seed, lo[a] - grow, hi[a] + grow);
-                r.dir[a] = uniform(seed, lo[a], hi[a]) - r.origin[a];
-            }
-            r.t_min = 0.0f;
-            r.t_max = t_max;
-        }
-        rays.Sync();
-        lbvh::DataBuffer<lbvh_hit> rows(ctx, count * (size_t)k);
-        lbvh::DataBuffer<uint32_t> found(ctx, count);
-        drawer.TraceKClosest(rays, k, rows, &found);
-        rows.GetData();
-        found.GetData();
-        size_t found_sum = 0, full = 0;
-        uint64_t word_sum = 0;
-        for (size_t i = 0; i < count; i++) {
-            found_sum += found.LocalBuffer()[i];
-            full += found.LocalBuffer()[i] == k;
-        }
-        for (const lbvh_hit& c : rows.LocalBuffer()) {
-            uint32_t w[4];
-            std::memcpy(w, &c, sizeof w);
-            word_sum += (uint64_t)w[0] + w[1] + w[2] + w[3];
-        }
-        std::printf("{\"triangles\": %zu, \"rays\": %zu, \"k\": %u, \"found_sum\": %zu, \"full_rows\": %zu, \"word_sum\": %llu, \"rows\": [",
-                    mesh.size(), count, k, found_sum, full, (unsigned long long)word_sum);
-        for (size_t i = 0; i < std::min<size_t>(count, 3); i++) {
-            std::printf("%s[", i ? ", " : "");
-            for (uint32_t j = 0; j < found.LocalBuffer()[i]; j++) {
-                const lbvh_hit& c = rows.LocalBuffer()[i * k + j];
-                std::printf("%s[%.9g, %u]", j ? ", " : "", c.t, c.tri);
-            }
-            std::printf("]");
-        }
-        std::printf("]}\n");
-    } catch (const std::exception& e) {
-        std::fprintf(stderr, "%s\n", e.what());
-        return 1;
-    }
+    const std::vector<lbvh_triangle> mesh = random_mesh(n);
+    float lo[3], hi[3];
+    mesh_box(mesh, lo, hi);
+    lbvh::Context ctx(0);
+    lbvh::RaytracingMeshDrawer drawer(ctx, mesh);
+    drawer.Awake();
+    lbvh::DataBuffer<lbvh_ray> rays(ctx, count);
+    rays_into(lo, hi, 3, rays.LocalBuffer());
+    for (auto& r : rays.LocalBuffer()) { r.t_min = 0.0f; r.t_max = t_max; }
+    rays.Sync();
+    lbvh::DataBuffer<lbvh_hit> rows(ctx, count * (size_t)k);
+    lbvh::DataBuffer<uint32_t> found(ctx, count);
+    drawer.TraceKClosest(rays, k, rows, &found);
+    rows.GetData();
+    found.GetData();
+    print_rows("rays", mesh.size(), count, k, rows.LocalBuffer(), found.LocalBuffer());
     return 0;
 }
 
@@ -464,126 +430,86 @@ static int gather_main(int argc, char** argv)
 {
     const size_t count = argc > 2 ? (size_t)strtoull(argv[2], nullptr, 10) : 65536;
     const float t_max = argc > 3 ? (float)atof(argv[3]) : INFINITY;
-    try {
-        const std::vector<lbvh_triangle> mesh = random_mesh(4096);
-        float lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
-        for (const auto& t : mesh)
-            for (int a = 0; a < 3; a++) {
-                lo[a] = std::fmin(lo[a], std::fmin(t.a[a], std::fmin(t.b[a], t.c[a])));
-                hi[a] = std::fmax(hi[a], std::fmax(t.a[a], std::fmax(t.b[a], t.c[a])));
-            }
-        lbvh::Context ctx(0);
-        lbvh::RaytracingMeshDrawer drawer(ctx, mesh);
-        drawer.Awake();
-        lbvh::DataBuffer<lbvh_ray> rays(ctx, count);
-        uint64_t seed = 3;
-        for (auto& r : rays.LocalBuffer()) {
-            for (int a = 0; a < 3; a++) {
-                const float grow = 0.25f * (hi[a] - lo[a]);
-                r.origin[a] = uniform(seed, lo[a] - grow, hi[a] + grow);
-                r.dir[a] = uniform(seed, lo[a], hi[a]) - r.origin[a];
-            }
-            r.t_min = 0.0f;
-            r.t_max = t_max;
-        }
-        rays.Sync();
-        lbvh::DataBuffer<uint64_t> offsets(ctx, count + 1);
-        drawer.GatherHits(rays, offsets);                       // count only
-        offsets.GetData();
-        const uint64_t total = offsets.LocalBuffer()[count];
-        lbvh::DataBuffer<lbvh_hit> hits(ctx, std::max<size_t>((size_t)total, 1));
-        drawer.GatherHits(rays, offsets, &hits);
-        offsets.GetData();
-        hits.GetData();
-        const std::vector<uint64_t>& off = offsets.LocalBuffer();
-        std::vector<lbvh_hit>& rec = hits.LocalBuffer();
-        size_t nonempty = 0;
-        for (size_t q = 0; q < count; q++) {                    // the library promises no order inside a segment: (t, tri) here
-            std::sort(rec.begin() + off[q], rec.begin() + off[q + 1],
-                      [](const lbvh_hit& x, const lbvh_hit& y) { return x.t < y.t || (x.t == y.t && x.tri < y.tri); });
-            nonempty += off[q + 1] > off[q];
-        }
-        uint64_t word_sum = 0, weighted_sum = 0;
-        for (uint64_t i = 0; i < total; i++) {
-            uint32_t w[4];
-            std::memcpy(w, &rec[i], sizeof w);
-            word_sum += (uint64_t)w[0] + w[1] + w[2] + w[3];
-            weighted_sum += (i + 1) * (uint64_t)rec[i].tri;
-        }
-        std::printf("{\"triangles\": %zu, \"rays\": %zu, \"total\": %llu, \"nonempty\": %zu, \"word_sum\": %llu, \"weighted_sum\": %llu, \"rows\": [",
-                    mesh.size(), count, (unsigned long long)off[count], nonempty, (unsigned long long)word_sum, (unsigned long long)weighted_sum);
-        for (size_t q = 0; q < std::min<size_t>(count, 3); q++) {
-            std::printf("%s[", q ? ", " : "");
-            for (uint64_t j = off[q]; j < off[q + 1]; j++) std::printf("%s[%.9g, %u]", j != off[q] ? ", " : "", rec[j].t, rec[j].tri);
-            std::printf("]");
-        }
-        std::printf("]}\n");
-    } catch (const std::exception& e) {
-        std::fprintf(stderr, "%s\n", e.what());
-        return 1;
+    const std::vector<lbvh_triangle> mesh = random_mesh(4096);
+    float lo[3], hi[3];
+    mesh_box(mesh, lo, hi);
+    lbvh::Context ctx(0);
+    lbvh::RaytracingMeshDrawer drawer(ctx, mesh);
+    drawer.Awake();
+    lbvh::DataBuffer<lbvh_ray> rays(ctx, count);
+    rays_into(lo, hi, 3, rays.LocalBuffer());
+    for (auto& r : rays.LocalBuffer()) { r.t_min = 0.0f; r.t_max = t_max; }
+    rays.Sync();
+    lbvh::DataBuffer<uint64_t> offsets(ctx, count + 1);
+    drawer.GatherHits(rays, offsets);                       // count only
+    offsets.GetData();
+    const uint64_t total = offsets.LocalBuffer()[count];
+    lbvh::DataBuffer<lbvh_hit> hits(ctx, std::max<size_t>((size_t)total, 1));
+    drawer.GatherHits(rays, offsets, &hits);
+    offsets.GetData();
+    hits.GetData();
+    const std::vector<uint64_t>& off = offsets.LocalBuffer();
+    std::vector<lbvh_hit>& rec = hits.LocalBuffer();
+    size_t nonempty = 0;
+    for (size_t q = 0; q < count; q++) {                    // the library promises no order inside a segment: (t, tri) here
+        std::sort(rec.begin() + off[q], rec.begin() + off[q + 1],
+                  [](const lbvh_hit& x, const lbvh_hit& y) { return x.t < y.t || (x.t == y.t && x.tri < y.tri); });
+        nonempty += off[q + 1] > off[q];
     }
+    uint64_t words = 0, weighted_sum = 0;
+    for (uint64_t i = 0; i < total; i++) {
+        words += word_sum(rec[i]);
+        weighted_sum += (i + 1) * (uint64_t)rec[i].tri;
+    }
+    std::printf("{\"triangles\": %zu, \"rays\": %zu, \"total\": %llu, \"nonempty\": %zu, \"word_sum\": %llu, \"weighted_sum\": %llu, \"rows\": [",
+                mesh.size(), count, (unsigned long long)off[count], nonempty, (unsigned long long)words, (unsigned long long)weighted_sum);
+    for (size_t q = 0; q < std::min<size_t>(count, 3); q++) {
+        std::printf("%s[", q ? ", " : "");
+        for (uint64_t j = off[q]; j < off[q + 1]; j++) std::printf("%s[%.9g, %u]", j != off[q] ? ", " : "", rec[j].t, rec[j].tri);
+        std::printf("]");
+    }
+    std::printf("]}\n");
     return 0;
 }
 
 static int sweep_main(int argc, char** argv)
 {
     const size_t count = argc > 3 ? (size_t)strtoull(argv[3], nullptr, 10) : 65536;
-    try {
-        const char* what = argc > 2 ? argv[2] : "4096";
-        const bool from_obj = std::strlen(what) > 4 && std::strcmp(what + std::strlen(what) - 4, ".obj") == 0;
-        const std::vector<lbvh_triangle> mesh = from_obj ? lbvh::MeshTriangles(lbvh::LoadObj(what)) : random_mesh((uint32_t)atoi(what));
-        float lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
-        for (const auto& t : mesh)
-            for (int a = 0; a < 3; a++) {
-                lo[a] = std::fmin(lo[a], std::fmin(t.a[a], std::fmin(t.b[a], t.c[a])));
-                hi[a] = std::fmax(hi[a], std::fmax(t.a[a], std::fmax(t.b[a], t.c[a])));
-            }
-        const float extent = std::fmax(hi[0] - lo[0], std::fmax(hi[1] - lo[1], hi[2] - lo[2]));
-        const float radius = argc > 4 ? (float)atof(argv[4]) : 0.01f * extent;
-        lbvh::Context ctx(0);
-        lbvh::RaytracingMeshDrawer drawer(ctx, mesh);
-        drawer.Awake();
-        lbvh::DataBuffer<lbvh_sphere_ray> casts(ctx, count);
-        uint64_t seed = 3;
-        for (auto& c : casts.LocalBuffer()) {
-            for (int a = 0; a < 3; a++) {
-                const float grow = 0.25f * (hi[a] - lo[a]);
-                c.origin[a] = uniform(seed, lo[a] - grow, hi[a] + grow);
-                c.dir[a] = uniform(seed, lo[a], hi[a]) - c.origin[a];
-            }
-            c.radius = radius;
-            c.t_max = 2.0f;
-        }
-        casts.Sync();
-        lbvh::DataBuffer<lbvh_hit> hits(ctx, count);
-        lbvh::DataBuffer<uint32_t> flags(ctx, count);
-        drawer.SphereCast(casts, hits);
-        drawer.SphereCastAny(casts, flags);
-        hits.GetData();
-        flags.GetData();
-        size_t touching = 0, flagged = 0, at_start = 0;
-        uint64_t word_sum = 0;
-        for (size_t i = 0; i < count; i++) {
-            const lbvh_hit& h = hits.LocalBuffer()[i];
-            uint32_t w[4];
-            std::memcpy(w, &h, sizeof w);
-            word_sum += (uint64_t)w[0] + w[1] + w[2] + w[3];
-            touching += h.t < LBVH_MAX_FLOAT;
-            at_start += h.t == 0.0f;
-            flagged += flags.LocalBuffer()[i];
-        }
-        std::printf("{\"triangles\": %zu, \"casts\": %zu, \"radius\": %.9g, \"touching\": %zu, \"flagged\": %zu, \"at_start\": %zu, "
-                    "\"word_sum\": %llu, \"records\": [",
-                    mesh.size(), count, radius, touching, flagged, at_start, (unsigned long long)word_sum);
-        for (size_t i = 0; i < std::min<size_t>(count, 3); i++) {
-            const lbvh_hit& h = hits.LocalBuffer()[i];
-            std::printf("%s[%.9g, %u, %.9g, %.9g]", i ? ", " : "", h.t, h.tri, h.u, h.v);
-        }
-        std::printf("]}\n");
-    } catch (const std::exception& e) {
-        std::fprintf(stderr, "%s\n", e.what());
-        return 1;
+    const std::vector<lbvh_triangle> mesh = load_mesh(argc > 2 ? argv[2] : "4096");
+    float lo[3], hi[3];
+    mesh_box(mesh, lo, hi);
+    const float extent = std::fmax(hi[0] - lo[0], std::fmax(hi[1] - lo[1], hi[2] - lo[2]));
+    const float radius = argc > 4 ? (float)atof(argv[4]) : 0.01f * extent;
+    lbvh::Context ctx(0);
+    lbvh::RaytracingMeshDrawer drawer(ctx, mesh);
+    drawer.Awake();
+    lbvh::DataBuffer<lbvh_sphere_ray> casts(ctx, count);
+    rays_into(lo, hi, 3, casts.LocalBuffer());
+    for (auto& c : casts.LocalBuffer()) { c.radius = radius; c.t_max = 2.0f; }
+    casts.Sync();
+    lbvh::DataBuffer<lbvh_hit> hits(ctx, count);
+    lbvh::DataBuffer<uint32_t> flags(ctx, count);
+    drawer.SphereCast(casts, hits);
+    drawer.SphereCastAny(casts, flags);
+    hits.GetData();
+    flags.GetData();
+    size_t touching = 0, flagged = 0, at_start = 0;
+    uint64_t words = 0;
+    for (size_t i = 0; i < count; i++) {
+        const lbvh_hit& h = hits.LocalBuffer()[i];
+        words += word_sum(h);
+        touching += h.t < LBVH_MAX_FLOAT;
+        at_start += h.t == 0.0f;
+        flagged += flags.LocalBuffer()[i];
     }
+    std::printf("{\"triangles\": %zu, \"casts\": %zu, \"radius\": %.9g, \"touching\": %zu, \"flagged\": %zu, \"at_start\": %zu, "
+                "\"word_sum\": %llu, \"records\": [",
+                mesh.size(), count, radius, touching, flagged, at_start, (unsigned long long)words);
+    for (size_t i = 0; i < std::min<size_t>(count, 3); i++) {
+        const lbvh_hit& h = hits.LocalBuffer()[i];
+        std::printf("%s[%.9g, %u, %.9g, %.9g]", i ? ", " : "", h.t, h.tri, h.u, h.v);
+    }
+    std::printf("]}\n");
     return 0;
 }
 
@@ -591,251 +517,191 @@ static int sweep_main(int argc, char** argv)
 // extent, and the balls of the same centres with radius up to `size` x the largest extent; count -> one 8-byte read -> fill
 static int overlaps_main(int argc, char** argv)
 {
-    const char* what = argc > 2 ? argv[2] : "4096";
-    const size_t len = std::strlen(what);
-    const bool from_obj = len > 4 && std::strcmp(what + len - 4, ".obj") == 0;
     const size_t count = argc > 3 ? (size_t)strtoull(argv[3], nullptr, 10) : 65536;
     const float size = argc > 4 ? (float)atof(argv[4]) : 0.1f;
-    try {
-        const std::vector<lbvh_triangle> mesh = from_obj ? lbvh::MeshTriangles(lbvh::LoadObj(what)) : random_mesh((uint32_t)atoi(what));
-        float lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
-        for (const auto& t : mesh)
-            for (int k = 0; k < 3; k++) {
-                lo[k] = std::fmin(lo[k], std::fmin(t.a[k], std::fmin(t.b[k], t.c[k])));
-                hi[k] = std::fmax(hi[k], std::fmax(t.a[k], std::fmax(t.b[k], t.c[k])));
-            }
-        const float widest = std::fmax(hi[0] - lo[0], std::fmax(hi[1] - lo[1], hi[2] - lo[2]));
-        lbvh::Context ctx(0);
-        lbvh::RaytracingMeshDrawer drawer(ctx, mesh);
-        drawer.Awake();
-        lbvh::DataBuffer<lbvh_aabb> boxes(ctx, count);
-        lbvh::DataBuffer<lbvh_point_query> balls(ctx, count);
-        uint64_t seed = 3;
-        for (size_t i = 0; i < count; i++) {
-            lbvh_aabb& b = boxes.LocalBuffer()[i];
-            lbvh_point_query& q = balls.LocalBuffer()[i];
-            std::memset(&b, 0, sizeof b);
-            for (int k = 0; k < 3; k++) {
-                const float c = uniform(seed, lo[k], hi[k]), h = uniform(seed, 0.0f, size * (hi[k] - lo[k]));
-                b.min[k] = c - h;
-                b.max[k] = c + h;
-                q.p[k] = c;
-            }
-            const float r = uniform(seed, 0.0f, size * widest);
-            q.max_dist2 = r * r;
+    const std::vector<lbvh_triangle> mesh = load_mesh(argc > 2 ? argv[2] : "4096");
+    float lo[3], hi[3];
+    mesh_box(mesh, lo, hi);
+    const float widest = std::fmax(hi[0] - lo[0], std::fmax(hi[1] - lo[1], hi[2] - lo[2]));
+    lbvh::Context ctx(0);
+    lbvh::RaytracingMeshDrawer drawer(ctx, mesh);
+    drawer.Awake();
+    lbvh::DataBuffer<lbvh_aabb> boxes(ctx, count);
+    lbvh::DataBuffer<lbvh_point_query> balls(ctx, count);
+    uint64_t seed = 3;
+    for (size_t i = 0; i < count; i++) {
+        lbvh_aabb& b = boxes.LocalBuffer()[i];
+        lbvh_point_query& q = balls.LocalBuffer()[i];
+        std::memset(&b, 0, sizeof b);
+        for (int k = 0; k < 3; k++) {
+            const float c = uniform(seed, lo[k], hi[k]), h = uniform(seed, 0.0f, size * (hi[k] - lo[k]));
+            b.min[k] = c - h;
+            b.max[k] = c + h;
+            q.p[k] = c;
         }
-        boxes.Sync();
-        balls.Sync();
-        lbvh::DataBuffer<uint64_t> offsets(ctx, count + 1);
-        unsigned long long total[2] = {0, 0}, index_sum[2] = {0, 0};
-        for (int form = 0; form < 2; form++) {
-            if (form == 0) drawer.BoxOverlaps(boxes, offsets);
-            else drawer.GatherWithinDistance(balls, offsets);
-            offsets.GetData();
-            total[form] = offsets.LocalBuffer()[count];
-            lbvh::DataBuffer<uint32_t> tris(ctx, total[form] ? (size_t)total[form] : 1);
-            if (form == 0) drawer.BoxOverlaps(boxes, offsets, &tris);
-            else drawer.GatherWithinDistance(balls, offsets, &tris);
-            tris.GetData();
-            for (size_t i = 0; i < (size_t)total[form]; i++) index_sum[form] += tris.LocalBuffer()[i];
-        }
-        std::printf("{\"triangles\": %zu, \"queries\": %zu, \"box_total\": %llu, \"box_index_sum\": %llu, \"ball_total\": %llu, \"ball_index_sum\": %llu}\n",
-                    mesh.size(), count, total[0], index_sum[0], total[1], index_sum[1]);
-    } catch (const std::exception& e) {
-        std::fprintf(stderr, "%s\n", e.what());
-        return 1;
+        const float r = uniform(seed, 0.0f, size * widest);
+        q.max_dist2 = r * r;
     }
+    boxes.Sync();
+    balls.Sync();
+    lbvh::DataBuffer<uint64_t> offsets(ctx, count + 1);
+    unsigned long long total[2] = {0, 0}, index_sum[2] = {0, 0};
+    for (int form = 0; form < 2; form++) {
+        if (form == 0) drawer.BoxOverlaps(boxes, offsets);
+        else drawer.GatherWithinDistance(balls, offsets);
+        offsets.GetData();
+        total[form] = offsets.LocalBuffer()[count];
+        lbvh::DataBuffer<uint32_t> tris(ctx, total[form] ? (size_t)total[form] : 1);
+        if (form == 0) drawer.BoxOverlaps(boxes, offsets, &tris);
+        else drawer.GatherWithinDistance(balls, offsets, &tris);
+        tris.GetData();
+        for (size_t i = 0; i < (size_t)total[form]; i++) index_sum[form] += tris.LocalBuffer()[i];
+    }
+    std::printf("{\"triangles\": %zu, \"queries\": %zu, \"box_total\": %llu, \"box_index_sum\": %llu, \"ball_total\": %llu, \"ball_index_sum\": %llu}\n",
+                mesh.size(), count, total[0], index_sum[0], total[1], index_sum[1]);
     return 0;
 }
 
 static int crossings_main(int argc, char** argv)
 {
-    const char* what = argc > 2 ? argv[2] : "4096";
-    const size_t len = std::strlen(what);
-    const bool from_obj = len > 4 && std::strcmp(what + len - 4, ".obj") == 0;
     const size_t count = argc > 3 ? (size_t)strtoull(argv[3], nullptr, 10) : 65536;
     const std::vector<float> dirs = {(float)(1.0 / std::sqrt(3.0)),  (float)(1.0 / std::sqrt(3.0)),  (float)(1.0 / std::sqrt(3.0)),
                                      (float)(-1.0 / std::sqrt(14.0)), (float)(2.0 / std::sqrt(14.0)), (float)(3.0 / std::sqrt(14.0)),
                                      (float)(4.0 / std::sqrt(21.0)),  (float)(-1.0 / std::sqrt(21.0)), (float)(2.0 / std::sqrt(21.0))};
+    const std::vector<lbvh_triangle> mesh = load_mesh(argc > 2 ? argv[2] : "4096");
+    float lo[3], hi[3];
+    mesh_box(mesh, lo, hi);
+    lbvh::Context ctx(0);
+    lbvh::RaytracingMeshDrawer drawer(ctx, mesh);
+    drawer.Awake();
+    lbvh::DataBuffer<lbvh_point_query> points(ctx, count);
+    lbvh::DataBuffer<lbvh_ray> rays(ctx, 3 * count);
+    points_around(lo, hi, 2, INFINITY, points.LocalBuffer());
+    for (size_t i = 0; i < count; i++) {
+        const lbvh_point_query& q = points.LocalBuffer()[i];
+        for (int j = 0; j < 3; j++) {
+            lbvh_ray& r = rays.LocalBuffer()[3 * i + j];
+            for (int k = 0; k < 3; k++) { r.origin[k] = q.p[k]; r.dir[k] = dirs[3 * j + k]; }
+            r.t_min = 0.0f;
+            r.t_max = INFINITY;
+        }
+    }
+    points.Sync();
+    rays.Sync();
+    lbvh::DataBuffer<uint32_t> parity(ctx, count);
+    lbvh::DataBuffer<uint32_t> counts(ctx, 3 * count);
+    drawer.PointCrossings(points, dirs, parity);
+    drawer.CountHits(rays, counts);
+    parity.GetData();
+    counts.GetData();
+    uint64_t count_sum = 0, parity_sum = 0;
+    size_t n_inside = 0;
+    bool consistent = true;
+    for (size_t i = 0; i < count; i++) {
+        const uint32_t p = parity.LocalBuffer()[i];
+        parity_sum += p;
+        n_inside += __builtin_popcount(p) >= 2;
+        consistent = consistent && (p >> 3) == 0u;
+        for (int j = 0; j < 3; j++) {
+            const uint32_t c = counts.LocalBuffer()[3 * i + j];
+            count_sum += c;
+            consistent = consistent && ((p >> j) & 1u) == (c & 1u);
+        }
+    }
+    std::printf("{\"triangles\": %zu, \"points\": %zu, \"count_sum\": %llu, \"parity_sum\": %llu, \"inside\": %zu, \"consistent\": %s}\n",
+                mesh.size(), count, (unsigned long long)count_sum, (unsigned long long)parity_sum, n_inside, consistent ? "true" : "false");
+    return 0;
+}
+
+// the default command: `[n] [w] [h] [dynamic]` or `obj <file.obj> [w] [h] [z]`
+static int frame_main(int argc, char** argv)
+{
+    const bool from_obj = argc > 2 && std::strcmp(argv[1], "obj") == 0;
+    const int w = from_obj ? (argc > 3 ? atoi(argv[3]) : 256) : (argc > 2 ? atoi(argv[2]) : 256);
+    const int h = from_obj ? (argc > 4 ? atoi(argv[4]) : 256) : (argc > 3 ? atoi(argv[3]) : 256);
+    const float cam_z = from_obj && argc > 5 ? (float)atof(argv[5]) : 300.0f;
+    const std::vector<lbvh_triangle> mesh = from_obj ? lbvh::MeshTriangles(lbvh::LoadObj(argv[2]))       // MeshBufferContainer.cs:117-146
+                                                     : random_mesh(argc > 1 ? (uint32_t)atoi(argv[1]) : 4096);
+    const uint32_t n = (uint32_t)mesh.size();
+    const bool dynamic = !from_obj && argc > 4 && std::strcmp(argv[4], "dynamic") == 0;
+    lbvh::Context ctx(0);
+    if (dynamic) {
+        // BASELINE configs[4] in miniature: 8 rigid bodies (triangle i belongs to body i % 8), one animated frame,
+        // primary rays + 2 bounces; prints a checksum of the RGBA16F image
+        std::vector<uint32_t> body(n);
+        for (uint32_t i = 0; i < n; i++) body[i] = i % 8;
+        std::vector<float> centres(8 * 4, 0.0f);
+        for (int bdy = 0; bdy < 8; bdy++) {
+            centres[bdy * 4 + 0] = (bdy & 1) ? 40.0f : -40.0f;
+            centres[bdy * 4 + 1] = (bdy & 2) ? 40.0f : -40.0f;
+            centres[bdy * 4 + 2] = (bdy & 4) ? 40.0f : -40.0f;
+        }
+        lbvh::DynamicPathTracer pt(ctx, mesh, body, centres, 1e-3f, 0.7f, 3);
+        pt.Animate(0.1f);
+        pt.Render(camera_at(w, h, 300.0f), 2);
+        pt.Image().GetData();
+        uint64_t image_sum = 0;
+        for (size_t i = 0; i < (size_t)w * h; i++) {
+            const uint64_t px = pt.Image().LocalBuffer()[i];
+            image_sum += (px & 0xFFFF) + ((px >> 16) & 0xFFFF) * 3 + ((px >> 32) & 0xFFFF) * 5 + ((px >> 48) & 0xFFFF) * 7;
+        }
+        std::printf("{\"triangles\": %u, \"rays\": %d, \"image_sum\": %llu}\n", n, w * h, (unsigned long long)image_sum);
+        return 0;
+    }
+    lbvh::RaytracingMeshDrawer drawer(ctx, mesh);
+    auto t0 = std::chrono::steady_clock::now();
+    drawer.Awake();
+    ctx.sync();
+    auto t1 = std::chrono::steady_clock::now();
+    const lbvh_camera cam = camera_at(w, h, cam_z);
+    lbvh::Event e0(ctx), e1(ctx);
+    e0.record();
+    drawer.Update(cam, LBVH_TRACE_FAST);
+    e1.record();
+    ctx.sync();
+    auto t2 = std::chrono::steady_clock::now();
+    const float update_device_ms = lbvh::Event::elapsed_ms(e0, e1);
+    // the same frame as three shards traced one after the other into the one buffer: must reproduce it exactly
+    drawer.Hits().GetData();
+    const std::vector<lbvh_hit> whole = drawer.Hits().LocalBuffer();
+    drawer.Hits().Fill(0xFFFFFFFFu);
+    for (uint32_t r = 0; r < 3; r++) drawer.UpdateShard(cam, r, 3, LBVH_TRACE_FAST);
+    drawer.Hits().GetData();
+    const bool shards_equal = std::memcmp(whole.data(), drawer.Hits().LocalBuffer().data(), whole.size() * sizeof(lbvh_hit)) == 0;
+    ctx.trace_forget();
+    drawer.Update(cam, LBVH_TRACE_FAST);
+    drawer.Container().GetAllGpuData();          // throws on a corrupted node (MeshBufferContainer.cs:181-195)
+    drawer.Hits().GetData();
+    uint64_t key_sum = 0, node_sum = 0;
+    for (uint32_t i = 0; i < n; i++) key_sum += drawer.Container().Keys().LocalBuffer()[i];
+    for (uint32_t i = 0; i + 1 < n; i++) {
+        const auto& nd = drawer.Container().BvhInternalNode().LocalBuffer()[i];
+        node_sum += (uint64_t)nd.leftNode * 3 + (uint64_t)nd.rightNode * 5 + (uint64_t)nd.parent * 7 + nd.leftNodeType + nd.rightNodeType;
+    }
+    size_t hits = 0;
+    double tsum = 0;
+    for (size_t i = 0; i < (size_t)w * h; i++)
+        if (drawer.Hits().LocalBuffer()[i].t < LBVH_MAX_FLOAT) { hits++; tsum += drawer.Hits().LocalBuffer()[i].t; }
+    std::printf("{\"triangles\": %u, \"rays\": %d, \"awake_ms\": %.3f, \"update_ms\": %.3f, \"update_device_ms\": %.4f, "
+                "\"key_sum\": %llu, \"node_sum\": %llu, \"hits\": %zu, \"t_sum\": %.6f, \"shards_equal\": %s}\n",
+                n, w * h, std::chrono::duration<double, std::milli>(t1 - t0).count(),
+                std::chrono::duration<double, std::milli>(t2 - t1).count(), update_device_ms, (unsigned long long)key_sum,
+                (unsigned long long)node_sum, hits, tsum, shards_equal ? "true" : "false");
+    return 0;
+}
+
+// lbvh::Error is a std::runtime_error, and the OBJ reader throws std::runtime_error: every failure is one line on stderr and status 1
+int main(int argc, char** argv)
+{
+    static const struct { const char* name; int (*run)(int, char**); } commands[] = {
+        {"crossings", crossings_main}, {"points", points_main}, {"knn", knn_main},   {"khits", khits_main}, {"gather", gather_main},
+        {"sweep", sweep_main},         {"overlaps", overlaps_main}, {"rays", rays_main}, {"sort", sort_main},   {"multi", multi_main}};
     try {
-        const std::vector<lbvh_triangle> mesh = from_obj ? lbvh::MeshTriangles(lbvh::LoadObj(what)) : random_mesh((uint32_t)atoi(what));
-        float lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
-        for (const auto& t : mesh)
-            for (int k = 0; k < 3; k++) {
-                lo[k] = std::fmin(lo[k], std::fmin(t.a[k], std::fmin(t.b[k], t.c[k])));
-                hi[k] = std::fmax(hi[k], std::fmax(t.a[k], std::fmax(t.b[k], t.c[k])));
-            }
-        lbvh::Context ctx(0);
-        lbvh::RaytracingMeshDrawer drawer(ctx, mesh);
-        drawer.Awake();
-        lbvh::DataBuffer<lbvh_point_query> points(ctx, count);
-        lbvh::DataBuffer<lbvh_ray> rays(ctx, 3 * count);
-        uint64_t seed = 2;
-        for (size_t i = 0; i < count; i++) {
-            lbvh_point_query& q = points.LocalBuffer()[i];
-            for (int k = 0; k < 3; k++) {
-                const float grow = 0.25f * (hi[k] - lo[k]);
-                q.p[k] = uniform(seed, lo[k] - grow, hi[k] + grow);
-            }
-            q.max_dist2 = INFINITY;
-            for (int j = 0; j < 3; j++) {
-                lbvh_ray& r = rays.LocalBuffer()[3 * i + j];
-                for (int k = 0; k < 3; k++) { r.origin[k] = q.p[k]; r.dir[k] = dirs[3 * j + k]; }
-                r.t_min = 0.0f;
-                r.t_max = INFINITY;
-            }
-        }
-        points.Sync();
-        rays.Sync();
-        lbvh::DataBuffer<uint32_t> parity(ctx, count);
-        lbvh::DataBuffer<uint32_t> counts(ctx, 3 * count);
-        drawer.PointCrossings(points, dirs, parity);
-        drawer.CountHits(rays, counts);
-        parity.GetData();
-        counts.GetData();
-        uint64_t count_sum = 0, parity_sum = 0;
-        size_t n_inside = 0;
-        bool consistent = true;
-        for (size_t i = 0; i < count; i++) {
-            const uint32_t p = parity.LocalBuffer()[i];
-            parity_sum += p;
-            n_inside += __builtin_popcount(p) >= 2;
-            consistent = consistent && (p >> 3) == 0u;
-            for (int j = 0; j < 3; j++) {
-                const uint32_t c = counts.LocalBuffer()[3 * i + j];
-                count_sum += c;
-                consistent = consistent && ((p >> j) & 1u) == (c & 1u);
-            }
-        }
-        std::printf("{\"triangles\": %zu, \"points\": %zu, \"count_sum\": %llu, \"parity_sum\": %llu, \"inside\": %zu, \"consistent\": %s}\n",
-                    mesh.size(), count, (unsigned long long)count_sum, (unsigned long long)parity_sum, n_inside, consistent ? "true" : "false");
+        for (const auto& c : commands)
+            if (argc > 1 && std::strcmp(argv[1], c.name) == 0) return c.run(argc, argv);
+        return frame_main(argc, argv);
     } catch (const std::exception& e) {
         std::fprintf(stderr, "%s\n", e.what());
         return 1;
     }
-    return 0;
-}
-
-int main(int argc, char** argv)
-{
-    if (argc > 1 && std::strcmp(argv[1], "crossings") == 0) return crossings_main(argc, argv);
-    if (argc > 1 && std::strcmp(argv[1], "points") == 0) return points_main(argc, argv);
-    if (argc > 1 && std::strcmp(argv[1], "knn") == 0) return knn_main(argc, argv);
-    if (argc > 1 && std::strcmp(argv[1], "khits") == 0) return khits_main(argc, argv);
-    if (argc > 1 && std::strcmp(argv[1], "gather") == 0) return gather_main(argc, argv);
-    if (argc > 1 && std::strcmp(argv[1], "sweep") == 0) return sweep_main(argc, argv);
-    if (argc > 1 && std::strcmp(argv[1], "overlaps") == 0) return overlaps_main(argc, argv);
-    if (argc > 1 && std::strcmp(argv[1], "rays") == 0) return rays_main(argc, argv);
-    if (argc > 1 && std::strcmp(argv[1], "sort") == 0) return sort_main(argc, argv);
-    if (argc > 1 && std::strcmp(argv[1], "multi") == 0) return multi_main(argc, argv);
-    const bool from_obj = argc > 2 && std::strcmp(argv[1], "obj") == 0;
-    uint32_t n = !from_obj && argc > 1 ? (uint32_t)atoi(argv[1]) : 4096;
-    const int w = from_obj ? (argc > 3 ? atoi(argv[3]) : 256) : (argc > 2 ? atoi(argv[2]) : 256);
-    const int h = from_obj ? (argc > 4 ? atoi(argv[4]) : 256) : (argc > 3 ? atoi(argv[3]) : 256);
-    const float cam_z = from_obj && argc > 5 ? (float)atof(argv[5]) : 300.0f;
-    std::vector<lbvh_triangle> mesh;
-    if (from_obj) {
-        try {
-            mesh = lbvh::MeshTriangles(lbvh::LoadObj(argv[2]));       // MeshBufferContainer.cs:117-146 for an OBJ asset
-        } catch (const std::exception& e) {
-            std::fprintf(stderr, "%s\n", e.what());
-            return 1;
-        }
-        n = (uint32_t)mesh.size();
-    } else {
-        mesh.resize(n);
-    }
-    uint64_t seed = 1;
-    for (auto& t : mesh) {
-        if (from_obj) break;
-        std::memset(&t, 0, sizeof t);
-        for (int k = 0; k < 3; k++) {
-            const float c = uniform(seed, -100.0f, 100.0f);
-            t.a[k] = c;
-            t.b[k] = c + uniform(seed, -2.0f, 2.0f);
-            t.c[k] = c + uniform(seed, -2.0f, 2.0f);
-        }
-        t.b_uv[0] = 1.0f; t.c_uv[1] = 1.0f;
-    }
-    const bool dynamic = !from_obj && argc > 4 && std::strcmp(argv[4], "dynamic") == 0;
-    try {
-        lbvh::Context ctx(0);
-        if (dynamic) {
-            // BASELINE configs[4] in miniature: 8 rigid bodies (triangle i belongs to body i % 8), one animated frame,
-            // primary rays + 2 bounces; prints a checksum of the RGBA16F image
-            std::vector<uint32_t> body(n);
-            for (uint32_t i = 0; i < n; i++) body[i] = i % 8;
-            std::vector<float> centres(8 * 4, 0.0f);
-            for (int bdy = 0; bdy < 8; bdy++) {
-                centres[bdy * 4 + 0] = (bdy & 1) ? 40.0f : -40.0f;
-                centres[bdy * 4 + 1] = (bdy & 2) ? 40.0f : -40.0f;
-                centres[bdy * 4 + 2] = (bdy & 4) ? 40.0f : -40.0f;
-            }
-            lbvh::DynamicPathTracer pt(ctx, mesh, body, centres, 1e-3f, 0.7f, 3);
-            pt.Animate(0.1f);
-            lbvh_camera cam;
-            cam.screen_width = w; cam.screen_height = h;
-            cam.camera_fov = (float)std::tan(60.0 * 3.14159265358979323846 / 180.0 / 2.0);
-            cam.near_plane = 0.3f;
-            const float m[16] = {-1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 300, 0, 0, 0, 1};
-            std::memcpy(cam.camera_to_world, m, sizeof m);
-            pt.Render(cam, 2);
-            pt.Image().GetData();
-            uint64_t image_sum = 0;
-            for (size_t i = 0; i < (size_t)w * h; i++) {
-                const uint64_t px = pt.Image().LocalBuffer()[i];
-                image_sum += (px & 0xFFFF) + ((px >> 16) & 0xFFFF) * 3 + ((px >> 32) & 0xFFFF) * 5 + ((px >> 48) & 0xFFFF) * 7;
-            }
-            std::printf("{\"triangles\": %u, \"rays\": %d, \"image_sum\": %llu}\n", n, w * h, (unsigned long long)image_sum);
-            return 0;
-        }
-        lbvh::RaytracingMeshDrawer drawer(ctx, mesh);
-        auto t0 = std::chrono::steady_clock::now();
-        drawer.Awake();
-        ctx.sync();
-        auto t1 = std::chrono::steady_clock::now();
-        lbvh_camera cam;
-        cam.screen_width = w; cam.screen_height = h;
-        cam.camera_fov = (float)std::tan(60.0 * 3.14159265358979323846 / 180.0 / 2.0);   // Mathf.Tan(fov * Deg2Rad / 2)
-        cam.near_plane = 0.3f;
-        const float m[16] = {-1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, cam_z, 0, 0, 0, 1};
-        std::memcpy(cam.camera_to_world, m, sizeof m);
-        lbvh::Event e0(ctx), e1(ctx);
-        e0.record();
-        drawer.Update(cam, LBVH_TRACE_FAST);
-        e1.record();
-        ctx.sync();
-        auto t2 = std::chrono::steady_clock::now();
-        const float update_device_ms = lbvh::Event::elapsed_ms(e0, e1);
-        // the same frame as three shards traced one after the other into the one buffer: must reproduce it exactly
-        drawer.Hits().GetData();
-        const std::vector<lbvh_hit> whole = drawer.Hits().LocalBuffer();
-        drawer.Hits().Fill(0xFFFFFFFFu);
-        for (uint32_t r = 0; r < 3; r++) drawer.UpdateShard(cam, r, 3, LBVH_TRACE_FAST);
-        drawer.Hits().GetData();
-        const bool shards_equal = std::memcmp(whole.data(), drawer.Hits().LocalBuffer().data(), whole.size() * sizeof(lbvh_hit)) == 0;
-        ctx.trace_forget();
-        drawer.Update(cam, LBVH_TRACE_FAST);
-        drawer.Container().GetAllGpuData();          // throws on a corrupted node (MeshBufferContainer.cs:181-195)
-        drawer.Hits().GetData();
-        uint64_t key_sum = 0, node_sum = 0;
-        for (uint32_t i = 0; i < n; i++) key_sum += drawer.Container().Keys().LocalBuffer()[i];
-        for (uint32_t i = 0; i + 1 < n; i++) {
-            const auto& nd = drawer.Container().BvhInternalNode().LocalBuffer()[i];
-            node_sum += (uint64_t)nd.leftNode * 3 + (uint64_t)nd.rightNode * 5 + (uint64_t)nd.parent * 7 + nd.leftNodeType + nd.rightNodeType;
-        }
-        size_t hits = 0;
-        double tsum = 0;
-        for (size_t i = 0; i < (size_t)w * h; i++)
-            if (drawer.Hits().LocalBuffer()[i].t < LBVH_MAX_FLOAT) { hits++; tsum += drawer.Hits().LocalBuffer()[i].t; }
-        std::printf("{\"triangles\": %u, \"rays\": %d, \"awake_ms\": %.3f, \"update_ms\": %.3f, \"update_device_ms\": %.4f, "
-                    "\"key_sum\": %llu, \"node_sum\": %llu, \"hits\": %zu, \"t_sum\": %.6f, \"shards_equal\": %s}\n",
-                    n, w * h, std::chrono::duration<double, std::milli>(t1 - t0).count(),
-                    std::chrono::duration<double, std::milli>(t2 - t1).count(), update_device_ms, (unsigned long long)key_sum,
-                    (unsigned long long)node_sum, hits, tsum, shards_equal ? "true" : "false");
-    } catch (const lbvh::Error& e) {
-        std::fprintf(stderr, "%s\n", e.what());
-        return 1;
-    }
-    return 0;
 }
