@@ -158,6 +158,8 @@ public static class LbvhNative
         IntPtr dTris, ulong capacity);
     [DllImport(Lib)] public static extern int lbvh_gather_hits(IntPtr ctx, IntPtr dRays, UIntPtr count, ref Scene scene, IntPtr dOffsets, IntPtr dHits,
         ulong capacity);
+    [DllImport(Lib)] public static extern int lbvh_sort_hit_segments(IntPtr ctx, IntPtr dOffsets, UIntPtr count, IntPtr dHits, ulong capacity);
+    [DllImport(Lib)] public static extern int lbvh_sort_index_segments(IntPtr ctx, IntPtr dOffsets, UIntPtr count, IntPtr dTris, ulong capacity);
     [DllImport(Lib)] public static extern int lbvh_count_hits(IntPtr ctx, IntPtr dRays, UIntPtr count, ref Scene scene, IntPtr dCounts);
     [DllImport(Lib)] public static extern int lbvh_point_crossings(IntPtr ctx, IntPtr dPoints, UIntPtr count, float[] hDirs, uint nDirs, ref Scene scene,
         IntPtr dParity);

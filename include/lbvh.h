@@ -799,8 +799,8 @@ lbvh_status lbvh_trace_k_closest(lbvh_context* ctx, const lbvh_ray* d_rays, size
  *   THE ORDER INSIDE A SEGMENT IS THE WALK'S AND IS NOT PART OF THE CONTRACT (the convention of the overlap queries: the four-wide
  *   form does not keep children in range order, and the walk enters boxes in slot order, not by distance).  Every record carries
  *   its t: sort a segment by (t, tri) if an order is needed — two candidates of a ray never share a triangle index, so that
- *   order is canonical.  A device-side sort of segments of unbounded length is not part of this call; the first 32 in order
- *   are lbvh_trace_k_closest.
+ *   order is canonical.  lbvh_sort_hit_segments (below) puts every segment into that order on the device, in place; the first 32
+ *   in order are lbvh_trace_k_closest.
  *   Overflow: no record at index >= capacity is ever written; every segment with d_offsets[q+1] <= capacity is complete; records
  *   below `capacity` that belong to a segment which does not fit are unspecified.  The call never waits on the host and returns
  *   LBVH_OK in both cases: the caller reads d_offsets[count] (one 8-byte download) to learn whether everything fitted and, if
@@ -827,6 +827,44 @@ lbvh_status lbvh_trace_k_closest(lbvh_context* ctx, const lbvh_ray* d_rays, size
  * better than a few that cross thousands of layers. */
 lbvh_status lbvh_gather_hits(lbvh_context* ctx, const lbvh_ray* d_rays, size_t count, const lbvh_scene* h_scene,
                              uint64_t* d_offsets, lbvh_hit* d_hits, uint64_t capacity);
+
+/* Every segment of a CSR list put into ascending key order, in place, on the device: the pass after lbvh_gather_hits
+ * (lbvh_sort_hit_segments) and after lbvh_box_overlaps / lbvh_gather_within_distance (lbvh_sort_index_segments), for a consumer
+ * that needs the segments ordered.  A stand-alone pass over any CSR list: it needs no scene.
+ *   d_offsets: count + 1 words of 64 bits, exactly as the three queries write them; read only.  `capacity`: the number of records
+ *   (d_hits) or words (d_tris) of the data buffer — the capacity that was given to the query.
+ *   What is sorted: every segment q with d_offsets[q] <= d_offsets[q+1] <= capacity is rearranged in place into ascending key
+ *   order; after the call it is a permutation of what it was.
+ *   What is left alone: a segment that does not fit the capacity is left untouched (its records are unspecified anyway), and so is
+ *   one whose pair of offsets decreases; no record at index >= capacity is ever read or written; d_offsets is never written.
+ *   (Offsets that the queries cannot produce — fitting segments that overlap each other — leave the records of the overlap
+ *   unspecified, still inside the capacity.)
+ *   Key of a hit record: the 64-bit pair (K(t), tri), K(t) the more significant half.  K maps the fp32 value to an unsigned word
+ *   that orders as the values do; with w = the 32 bits of t, operation by operation:
+ *     if ((w & 0x7FFFFFFF) > 0x7F800000) K = 0xFFFFFFFF          every NaN: one class, after +inf (K(+inf) = 0xFF800000)
+ *     else { if (w == 0x80000000) w = 0;                           -0 and +0 map to the same word
+ *            K = (w & 0x80000000) ? ~w : (w | 0x80000000); }       negative values reversed below the positive ones
+ *   This is the order of lbvh_trace_k_closest (t compared as fp32 values, the index decides), made total: lbvh_gather_hits never
+ *   writes a NaN, but the call is defined on any input.  u and v travel with their record and are not compared.
+ *   Key of an index segment: the 32-bit word, ascending.
+ *   Records of equal key come out in an unspecified relative order: THE SORT IS NOT STABLE.
+ * Hence: after lbvh_gather_hits followed by lbvh_sort_hit_segments with the same d_offsets and capacity, every fitting segment q
+ * is in (t, tri) order — two candidates of a ray never share a triangle index, so the order is canonical and the segment equals
+ * the brute force's (tests/gather_hits_reference.py) word for word; with m its length, its first min(k, m) records are the first
+ * min(k, m) records of row q of lbvh_trace_k_closest, and its first record is lbvh_trace_closest's.  After lbvh_box_overlaps or
+ * lbvh_gather_within_distance followed by lbvh_sort_index_segments, every fitting segment is strictly ascending (each candidate
+ * appears once).
+ * Asynchronous on the context's stream with no host wait: segment lengths are only ever read on the device.  Takes NO context
+ * scratch: it does not touch the ray scratch and does NOT drop the path tracer's live-path list (see lbvh_path_bounce) — unless
+ * the data buffer is that frame's d_hits, which it then writes like any other call.  No derived scene is needed: a context that
+ * never built one may call it.  count == 0 is a no-op; capacity == 0 is a no-op that still returns LBVH_OK.  Rejected with
+ * LBVH_ERR_INVALID_ARG: NULL ctx / d_offsets / d_hits / d_tris, d_offsets not 8-byte aligned, d_hits not 16-byte aligned, d_tris
+ * not 4-byte aligned, count > 2^32 - 1.  A segment may have any length up to the capacity; positions are formed in 64 bits.
+ * Segments of up to 256 records are sorted 64 queries at a time by one wave, in LDS; a longer one is sorted by ONE workgroup (up
+ * to 4 096 records in LDS, beyond that in O(n log^2 n) exchanges partly on device memory): many ordinary segments run far better
+ * than one of a million records. */
+lbvh_status lbvh_sort_hit_segments(lbvh_context* ctx, const uint64_t* d_offsets, size_t count, lbvh_hit* d_hits, uint64_t capacity);
+lbvh_status lbvh_sort_index_segments(lbvh_context* ctx, const uint64_t* d_offsets, size_t count, uint32_t* d_tris, uint64_t capacity);
 
 /* A moving sphere: 32 bytes, arrays 16-byte aligned: lbvh_ray with the radius where t_min is. */
 typedef struct lbvh_sphere_ray {
@@ -914,7 +952,9 @@ lbvh_status lbvh_path_scatter(lbvh_context* ctx, const lbvh_scene* h_scene, cons
  * lbvh_path_bounce on the same d_states / d_hits listed as live (a list kept by the context).  Every library call that writes
  * into those buffers drops the list (lbvh_path_begin, lbvh_trace_rays, a primary trace into any part of d_hits,
  * lbvh_buffer_upload / _fill_u32 / _free), and so does lbvh_trace_forget — and so do lbvh_trace_closest,
- * lbvh_trace_occluded, lbvh_closest_point_query, lbvh_within_distance, lbvh_count_hits, lbvh_point_crossings, lbvh_box_overlaps, lbvh_gather_within_distance, lbvh_k_closest_points, lbvh_trace_k_closest, lbvh_gather_hits, lbvh_sphere_cast and lbvh_sphere_cast_any, whatever buffers they are given, since they use the same ray scratch; then every state is scanned again.  What the library
+ * lbvh_trace_occluded, lbvh_closest_point_query, lbvh_within_distance, lbvh_count_hits, lbvh_point_crossings, lbvh_box_overlaps, lbvh_gather_within_distance, lbvh_k_closest_points, lbvh_trace_k_closest, lbvh_gather_hits, lbvh_sphere_cast and lbvh_sphere_cast_any, whatever buffers they are given, since they use the same ray scratch; then every state is scanned again.  The one exception among the query calls:
+ * lbvh_sort_hit_segments and lbvh_sort_index_segments take no context scratch and keep the live-path list (they drop it only when the
+ * buffer they sort is d_hits itself).  What the library
  * cannot see is a write of the CALLER's own (a kernel or hipMemcpy that revives or ends paths, Russian roulette): between two
  * consecutive bounces of a frame d_states and d_hits must not be written from outside the library — or lbvh_trace_forget must be
  * called after such a write. */

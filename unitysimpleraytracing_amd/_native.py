@@ -100,6 +100,8 @@ SIGNATURES = {
     "lbvh_k_closest_points": (_I32, [_P, _P, _SZ, _U32, C.POINTER(Scene), _P, _P]),
     "lbvh_trace_k_closest": (_I32, [_P, _P, _SZ, _U32, C.POINTER(Scene), _P, _P]),
     "lbvh_gather_hits": (_I32, [_P, _P, _SZ, C.POINTER(Scene), _P, _P, C.c_uint64]),
+    "lbvh_sort_hit_segments": (_I32, [_P, _P, _SZ, _P, C.c_uint64]),
+    "lbvh_sort_index_segments": (_I32, [_P, _P, _SZ, _P, C.c_uint64]),
     "lbvh_sphere_cast": (_I32, [_P, _P, _SZ, C.POINTER(Scene), _P]),
     "lbvh_sphere_cast_any": (_I32, [_P, _P, _SZ, C.POINTER(Scene), _P]),
     "lbvh_count_hits": (_I32, [_P, _P, _SZ, C.POINTER(Scene), _P]),

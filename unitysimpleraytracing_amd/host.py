@@ -201,6 +201,26 @@ class DataBuffer:
             self.device = None
 
 
+def sort_hit_segments(ctx, offsets, hits, count=None):
+    """Every segment of a gathered list into (t, tri) order, in place, on the device (lbvh_sort_hit_segments): `offsets` the uint64
+    DataBuffer a gather wrote (count + 1 entries; count defaults to offsets.size - 1), `hits` the layouts.HIT DataBuffer given to
+    that gather — its size is the capacity; a segment that did not fit is left as it is.  Needs no scene.  Asynchronous."""
+    _sort_segments(N.lib.lbvh_sort_hit_segments, ctx, offsets, hits, L.HIT, count)
+
+
+def sort_index_segments(ctx, offsets, tris, count=None):
+    """The same for the uint32 DataBuffer `tris` of box_overlaps / gather_within_distance (lbvh_sort_index_segments): every
+    segment ascending."""
+    _sort_segments(N.lib.lbvh_sort_index_segments, ctx, offsets, tris, np.dtype(np.uint32), count)
+
+
+def _sort_segments(fn, ctx, offsets, data, dtype, count):
+    count = offsets.size - 1 if count is None else int(count)
+    if offsets.dtype != np.uint64 or data.dtype != dtype or count < 0 or offsets.size < count + 1:
+        raise ValueError(f"offsets must be a DataBuffer of uint64 with count + 1 entries and the data one of {dtype}")
+    N.check(ctx.handle, fn(ctx.handle, offsets.device, count, data.device, data.size))
+
+
 class MeshBufferContainer:
     """Assets/_Scripts/MeshBufferContainer.cs.  The constructor takes the triangle soup (the
     reference's Mesh -> Triangle[] conversion, :117-146, stays on the caller's side) and runs the
@@ -446,9 +466,10 @@ class RaytracingMeshDrawer:
         N.check(self.ctx.handle, fn(self.ctx.handle, queries.device, queries.size, C.byref(s), offsets.device,
                                     tris.device if tris is not None else None, tris.size if tris is not None else 0))
 
-    def overlaps(self, queries, min_capacity=1):
+    def overlaps(self, queries, min_capacity=1, device_sort=False):
         """Convenience: count -> one 8-byte download -> allocate -> fill.  `queries`: a DataBuffer of layouts.AABB (box form) or of
-        layouts.POINT_QUERY (distance form).  Returns (offsets, tris): host arrays, uint64[queries.size + 1] and uint32[total]."""
+        layouts.POINT_QUERY (distance form).  Returns (offsets, tris): host arrays, uint64[queries.size + 1] and uint32[total].
+        device_sort=True issues sort_index_segments before the download: every segment ascending."""
         call = self.box_overlaps if queries.dtype == L.AABB else self.gather_within_distance
         count = queries.size
         offsets = DataBuffer(self.ctx, count + 1, np.uint64)
@@ -461,6 +482,8 @@ class RaytracingMeshDrawer:
             tris = DataBuffer(self.ctx, max(total, int(min_capacity)), np.uint32)
             try:
                 call(queries, offsets, tris)
+                if device_sort:
+                    sort_index_segments(self.ctx, offsets, tris, count)
                 return offsets.get_data().copy(), tris.get_data()[:total].copy()
             finally:
                 tris.dispose()
@@ -500,10 +523,11 @@ class RaytracingMeshDrawer:
         N.check(self.ctx.handle, N.lib.lbvh_gather_hits(self.ctx.handle, rays.device, rays.size, C.byref(s), offsets.device,
                                                         hits.device if hits is not None else None, hits.size if hits is not None else 0))
 
-    def all_hits(self, rays, sort=False, min_capacity=1):
+    def all_hits(self, rays, sort=False, min_capacity=1, device_sort=False):
         """Convenience: count -> one 8-byte download -> allocate -> fill.  Returns (offsets, hits): host arrays, uint64[rays.size + 1]
         and layouts.HIT[total].  The library leaves a segment in the order of its walk; sort=True orders every segment by
-        (t, tri) HERE, ON THE HOST (np.lexsort over the downloaded records — not a device sort)."""
+        (t, tri) HERE, ON THE HOST (np.lexsort over the downloaded records — not a device sort).  device_sort=True issues
+        sort_hit_segments before the download instead: the same order, made on the device."""
         count = rays.size
         offsets = DataBuffer(self.ctx, count + 1, np.uint64)
         try:
@@ -515,6 +539,8 @@ class RaytracingMeshDrawer:
             hits = DataBuffer(self.ctx, max(total, int(min_capacity)), L.HIT)
             try:
                 self.gather_hits(rays, offsets, hits)
+                if device_sort:
+                    sort_hit_segments(self.ctx, offsets, hits, count)
                 off, rec = offsets.get_data().copy(), hits.get_data()[:total].copy()
             finally:
                 hits.dispose()

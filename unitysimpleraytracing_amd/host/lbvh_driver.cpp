@@ -32,6 +32,9 @@
 //                                                how many segments are non-empty, the sum of all 32-bit words of the records (mod
 //                                                2^64), the sum of (position + 1) * triangle index over the sorted list (mod 2^64) and
 //                                                the first segments
+//     lbvh_driver sortedhits <n_rays> [t_max]    `gather` with the segments ordered on the device instead: GatherHits, then
+//                                                SortHitSegments, then the download; no host sort; prints the same fields, the
+//                                                position-weighted sum now over the device-sorted order
 //     lbvh_driver sweep [n | file.obj] [count] [radius]  the mesh of `points` and `count` spheres of the given radius (default 1 %
 //                                                of the largest extent) from points around the mesh's box towards points inside
 //                                                it (t = 1 at the target, t_max 2); SphereCast and SphereCastAny; prints how
@@ -426,7 +429,8 @@ static int khits_main(int argc, char** argv)
     return 0;
 }
 
-static int gather_main(int argc, char** argv)
+// `gather` and `sortedhits`: the same list, ordered by (t, tri) on the host / by lbvh_sort_hit_segments on the device
+static int gather_run(int argc, char** argv, bool device_sort)
 {
     const size_t count = argc > 2 ? (size_t)strtoull(argv[2], nullptr, 10) : 65536;
     const float t_max = argc > 3 ? (float)atof(argv[3]) : INFINITY;
@@ -446,14 +450,16 @@ static int gather_main(int argc, char** argv)
     const uint64_t total = offsets.LocalBuffer()[count];
     lbvh::DataBuffer<lbvh_hit> hits(ctx, std::max<size_t>((size_t)total, 1));
     drawer.GatherHits(rays, offsets, &hits);
+    if (device_sort) drawer.SortHitSegments(offsets, hits, count);
     offsets.GetData();
     hits.GetData();
     const std::vector<uint64_t>& off = offsets.LocalBuffer();
     std::vector<lbvh_hit>& rec = hits.LocalBuffer();
     size_t nonempty = 0;
-    for (size_t q = 0; q < count; q++) {                    // the library promises no order inside a segment: (t, tri) here
-        std::sort(rec.begin() + off[q], rec.begin() + off[q + 1],
-                  [](const lbvh_hit& x, const lbvh_hit& y) { return x.t < y.t || (x.t == y.t && x.tri < y.tri); });
+    for (size_t q = 0; q < count; q++) {                    // the gather promises no order inside a segment: (t, tri) here
+        if (!device_sort)
+            std::sort(rec.begin() + off[q], rec.begin() + off[q + 1],
+                      [](const lbvh_hit& x, const lbvh_hit& y) { return x.t < y.t || (x.t == y.t && x.tri < y.tri); });
         nonempty += off[q + 1] > off[q];
     }
     uint64_t words = 0, weighted_sum = 0;
@@ -471,6 +477,9 @@ static int gather_main(int argc, char** argv)
     std::printf("]}\n");
     return 0;
 }
+
+static int gather_main(int argc, char** argv) { return gather_run(argc, argv, false); }
+static int sortedhits_main(int argc, char** argv) { return gather_run(argc, argv, true); }
 
 static int sweep_main(int argc, char** argv)
 {
@@ -694,7 +703,7 @@ static int frame_main(int argc, char** argv)
 int main(int argc, char** argv)
 {
     static const struct { const char* name; int (*run)(int, char**); } commands[] = {
-        {"crossings", crossings_main}, {"points", points_main}, {"knn", knn_main},   {"khits", khits_main}, {"gather", gather_main},
+        {"crossings", crossings_main}, {"points", points_main}, {"knn", knn_main},   {"khits", khits_main}, {"gather", gather_main}, {"sortedhits", sortedhits_main},
         {"sweep", sweep_main},         {"overlaps", overlaps_main}, {"rays", rays_main}, {"sort", sort_main},   {"multi", multi_main}};
     try {
         for (const auto& c : commands)

@@ -410,6 +410,21 @@ public:
         check(ctx_.get(), lbvh_gather_hits(ctx_.get(), (const lbvh_ray*)rays.DeviceBuffer(), rays.Size(), &s, (uint64_t*)offsets.DeviceBuffer(),
                                            hits ? (lbvh_hit*)hits->DeviceBuffer() : nullptr, hits ? (uint64_t)hits->Size() : 0));
     }
+    // Every segment of a gathered list into (t, tri) order / ascending index order, in place, on the device (lbvh_sort_hit_segments,
+    // lbvh_sort_index_segments; asynchronous, no scratch, the path tracer's live-path list is kept).  The data buffer's size is the
+    // capacity: pass the buffer that was given to GatherHits / the overlap query.  A segment that did not fit is left as it is.
+    void SortHitSegments(const DataBuffer<uint64_t>& offsets, DataBuffer<lbvh_hit>& hits, size_t count)
+    {
+        if (offsets.Size() < count + 1) throw Error(LBVH_ERR_INVALID_ARG, "SortHitSegments: offsets needs count + 1 entries");
+        check(ctx_.get(), lbvh_sort_hit_segments(ctx_.get(), (const uint64_t*)offsets.DeviceBuffer(), count, (lbvh_hit*)hits.DeviceBuffer(),
+                                                 (uint64_t)hits.Size()));
+    }
+    void SortIndexSegments(const DataBuffer<uint64_t>& offsets, DataBuffer<uint32_t>& tris, size_t count)
+    {
+        if (offsets.Size() < count + 1) throw Error(LBVH_ERR_INVALID_ARG, "SortIndexSegments: offsets needs count + 1 entries");
+        check(ctx_.get(), lbvh_sort_index_segments(ctx_.get(), (const uint64_t*)offsets.DeviceBuffer(), count, (uint32_t*)tris.DeviceBuffer(),
+                                                   (uint64_t)tris.Size()));
+    }
     void PointCrossings(const DataBuffer<lbvh_point_query>& points, const std::vector<float>& dirs, DataBuffer<uint32_t>& parity)
     {
         if (parity.Size() < points.Size()) throw Error(LBVH_ERR_INVALID_ARG, "PointCrossings: fewer parity words than points");
