@@ -928,6 +928,78 @@ lbvh_status lbvh_sphere_cast(lbvh_context* ctx, const lbvh_sphere_ray* d_casts, 
 lbvh_status lbvh_sphere_cast_any(lbvh_context* ctx, const lbvh_sphere_ray* d_casts, size_t count, const lbvh_scene* h_scene,
                                  uint32_t* d_flags);
 
+/* A query triangle: 48 bytes; arrays of them 16-byte aligned. */
+typedef struct lbvh_tri_query {
+    float a[3]; uint32_t skip;     /* ORIGINAL index of a scene triangle that is never a candidate; LBVH_NULL = none */
+    float b[3]; uint32_t _pad0;    /* not read */
+    float c[3]; uint32_t _pad1;    /* not read */
+} lbvh_tri_query;
+
+/* Triangle queries: WHICH scene triangles does a triangle intersect — the narrow phase behind lbvh_box_overlaps —, as a CSR list
+ * (lbvh_triangle_intersections) or as one flag per query (lbvh_triangle_intersects_any), over the derived traversal scene in its
+ * four-wide form by the walk of lbvh_box_overlaps.
+ *   Active query: all nine coordinates of a, b and c are finite.  An inactive query is never walked; it gets an empty segment, or
+ *   the flag 0.
+ *   Query box: Q.min[k] = fminf(fminf(a[k], b[k]), c[k]), Q.max[k] = fmaxf(fmaxf(a[k], b[k]), c[k]): exact, not padded.
+ *   Edge test: pierce(P, D; V, E1, E2) is the Moeller-Trumbore test of every ray walker of this library (lbvh_trace_closest), for the
+ *   ray origin P, direction D (not normalised) against the triangle with first vertex V and edge vectors E1, E2, in strict fp32,
+ *   every operation rounded on its own, dot(x, y) = (x0*y0 + x1*y1) + x2*y2, cross(x, y) per component x1*y2 - x2*y1:
+ *       p = cross(D, E2)      det = dot(E1, p)      if (det < 1e-8 && det > -1e-8) miss
+ *       inv = 1 / det         s = P - V             u = dot(s, p) * inv           if (u < 0 || u > 1) miss
+ *       q = cross(s, E1)      v = dot(D, q) * inv                                 if (v < 0 || u + v > 1) miss
+ *       t = dot(E2, q) * inv
+ *   A miss has t = LBVH_MAX_FLOAT.  The test PASSES iff 0 <= t && t <= 1 (false for a miss and for a NaN t).
+ *   Candidate: scene triangle i — first vertex v0 and edge vectors e1 = v1 - v0, e2 = v2 - v0 as its line of the derived scene
+ *   holds them (the fp32 differences taken at build time) — is a candidate of an active query iff
+ *     (1) its ORIGINAL index is not `skip`, and
+ *     (2) its own box A = scene.triangle_aabb[i] overlaps Q in closed intervals, Q.min[k] <= A.max[k] && A.min[k] <= Q.max[k] for
+ *         k = 0, 1, 2 (the six comparisons of lbvh_box_overlaps), and
+ *     (3) at least one of these six edge tests passes, every P and D formed per component in fp32:
+ *         the query's edges against the scene triangle:     pierce(a, b - a; v0, e1, e2)   pierce(b, c - b; v0, e1, e2)
+ *                                                           pierce(c, a - c; v0, e1, e2)
+ *         the scene triangle's edges against the query:     pierce(v0, e1; a, b - a, c - a)   pierce(v0, e2; a, b - a, c - a)
+ *                                                           pierce(v0 + e1, e2 - e1; a, b - a, c - a)
+ *         (the edge list of lbvh_sphere_cast).
+ *   What follows from this definition:
+ *     Coplanar overlapping triangles are generally NOT reported: an edge parallel to the other triangle's plane has det ~ 0 and is
+ *     rejected by the det test.  Exact coplanar overlap is out of scope.
+ *     Triangles that only touch (a shared vertex or edge) are reported exactly when the arithmetic above says so — u, v or t at a
+ *     bound after rounding —, not by a rule of their own.  `skip` removes the query's own triangle when a mesh is tested against
+ *     itself (skip = the triangle's original index); removing neighbours that share a vertex is the caller's job on the returned pairs.
+ *     A pierce computed for a pair whose boxes do not overlap is fp32 noise and is not a candidate (rule (2)): the analogue of the
+ *     accept rule of the ray walkers.
+ *   Why the list does not depend on the walk (the argument at lbvh_box_overlaps): every box of the derived tree, binary or
+ *   four-wide, is the exact min / max union of what lies below it, so every ancestor of a candidate's leaf passes the same six
+ *   comparisons; the walk skips exactly the slots that fail.  (1) and (3) are functions of (query, triangle) only.  Each triangle is
+ *   one leaf, so each candidate appears once.
+ * Output of lbvh_triangle_intersections — the CSR contract of lbvh_box_overlaps, word for word:
+ *   d_offsets: count + 1 words of 64 bits.  d_offsets[k] = the number of candidates of queries 0 .. k-1, d_offsets[count] = the
+ *   total M.  Always written in full, whatever `capacity` is.
+ *   d_tris, `capacity` words of 32 bits: segment k = d_tris[d_offsets[k] .. d_offsets[k+1]) = the ORIGINAL triangle indices of
+ *   query k's candidates, each exactly once.  THE ORDER INSIDE A SEGMENT IS THE WALK'S AND IS NOT PART OF THE CONTRACT;
+ *   lbvh_sort_index_segments applies unchanged and leaves every fitting segment strictly ascending.
+ *   Overflow: no word at index >= capacity is ever written; every segment with d_offsets[k+1] <= capacity is complete; words
+ *   below `capacity` that belong to a segment which does not fit are unspecified.  The call never waits on the host and returns
+ *   LBVH_OK in both cases: the caller reads d_offsets[count] (one 8-byte download) to learn what was needed.
+ *   Count-only form: capacity == 0 writes the offsets and walks once (d_tris may be NULL); otherwise the scene is walked twice
+ *   (count, device-side scan, fill: the same kernel making the same decisions, so a segment never outgrows its slot).
+ *   d_tris == NULL with capacity > 0 is LBVH_ERR_INVALID_ARG.
+ * Output of lbvh_triangle_intersects_any: d_flags[k] = 1 exactly when segment k would be non-empty, else 0; every one of the `count`
+ * words is written.  The walk is the same, cut off at a query's first candidate.
+ * Both need the derived traversal scene (lbvh_build_fast_scene; a stale one is LBVH_ERR_INVALID_ARG), are asynchronous on the
+ * context's stream with no host wait, and use the context's ray scratch: they drop the path tracer's live-path list (see
+ * lbvh_path_bounce).  count == 0 is a no-op: nothing is enqueued and no buffer is touched, d_offsets[0] included.  Rejected: NULL
+ * ctx / d_queries / h_scene / d_offsets / d_flags, d_queries not 16-byte aligned, d_offsets not 8-byte aligned, d_tris or d_flags
+ * not 4-byte aligned, count > 2^32 - 1.  Four-wide walk only (lbvh_debug_ray_walker does not apply); lbvh_debug_ray_waves,
+ * lbvh_debug_ray_stack_split, lbvh_debug_ray_stack_limit and lbvh_ray_stats_target apply as to the overlap queries (triangle_tests
+ * counts the triangles that reached the edge tests; the full form reports twice the count-only form's).
+ * One query per lane; the cost is that of lbvh_box_overlaps on the queries' boxes plus one 64-byte triangle line and up to six
+ * edge tests per box-overlapping triangle: a query much larger than the scene's triangles keeps its lane busy for long. */
+lbvh_status lbvh_triangle_intersections(lbvh_context* ctx, const lbvh_tri_query* d_queries, size_t count, const lbvh_scene* h_scene,
+                                        uint64_t* d_offsets, uint32_t* d_tris, uint64_t capacity);
+lbvh_status lbvh_triangle_intersects_any(lbvh_context* ctx, const lbvh_tri_query* d_queries, size_t count, const lbvh_scene* h_scene,
+                                         uint32_t* d_flags);
+
 /* Camera rays into path states (origin/dir as Raytracing.compute:108-126, throughput 1, radiance 0, alive). */
 lbvh_status lbvh_path_begin(lbvh_context* ctx, const lbvh_camera* h_camera, lbvh_path_state* d_states);
 
@@ -952,7 +1024,7 @@ lbvh_status lbvh_path_scatter(lbvh_context* ctx, const lbvh_scene* h_scene, cons
  * lbvh_path_bounce on the same d_states / d_hits listed as live (a list kept by the context).  Every library call that writes
  * into those buffers drops the list (lbvh_path_begin, lbvh_trace_rays, a primary trace into any part of d_hits,
  * lbvh_buffer_upload / _fill_u32 / _free), and so does lbvh_trace_forget — and so do lbvh_trace_closest,
- * lbvh_trace_occluded, lbvh_closest_point_query, lbvh_within_distance, lbvh_count_hits, lbvh_point_crossings, lbvh_box_overlaps, lbvh_gather_within_distance, lbvh_k_closest_points, lbvh_trace_k_closest, lbvh_gather_hits, lbvh_sphere_cast and lbvh_sphere_cast_any, whatever buffers they are given, since they use the same ray scratch; then every state is scanned again.  The one exception among the query calls:
+ * lbvh_trace_occluded, lbvh_closest_point_query, lbvh_within_distance, lbvh_count_hits, lbvh_point_crossings, lbvh_box_overlaps, lbvh_gather_within_distance, lbvh_k_closest_points, lbvh_trace_k_closest, lbvh_gather_hits, lbvh_sphere_cast, lbvh_sphere_cast_any, lbvh_triangle_intersections and lbvh_triangle_intersects_any, whatever buffers they are given, since they use the same ray scratch; then every state is scanned again.  The one exception among the query calls:
  * lbvh_sort_hit_segments and lbvh_sort_index_segments take no context scratch and keep the live-path list (they drop it only when the
  * buffer they sort is d_hits itself).  What the library
  * cannot see is a write of the CALLER's own (a kernel or hipMemcpy that revives or ends paths, Russian roulette): between two

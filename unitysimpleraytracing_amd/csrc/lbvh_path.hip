@@ -1750,6 +1750,166 @@ __global__ __launch_bounds__(64) void gather_hits_wide_kernel(const lbvh_ray* __
     if (STATS) add_ray_stats(stats, n_rays, n_steps, n_tris);
 }
 
+// ---- triangle queries: which scene triangles a triangle intersects (lbvh_triangle_intersections, include/lbvh.h) ----------
+// The narrow phase behind lbvh_box_overlaps, in the frame of overlap_wide_kernel<BOX = true>: the query's box is the exact min / max
+// of its three vertices, a slot is entered iff the two boxes overlap (the same six comparisons), and at a leaf slot — whose box is
+// the triangle's own — the triangle line is read and the pair is a candidate iff one of six ray_triangle_edges calls gives
+// 0 <= t <= 1: the three query edges against the scene triangle, then the three scene edges (the edge list of lbvh_sphere_cast)
+// against the query triangle, first pass wins.  kTriCount and kTriFill are the two walks of the CSR protocol; kTriAny stops a lane
+// at its first candidate.
+// Registers: a lane keeps the nine coordinates, the box and `skip` (16 VGPRs) and forms the edge vectors at the leaf — nine
+// subtractions per tested triangle against nine more registers held through the whole walk (DESIGN §28 has the counts).  Leaf tests
+// are not deferred: a leaf slot is tested where it is met, as in every other walker here.
+enum tri_query_mode : int { kTriCount = 0, kTriFill = 1, kTriAny = 2 };
+
+// ray (P, D) against the triangle (v0, e1, e2): ray_triangle_edges as the ray walkers call it, then 0 <= t <= 1 (false for a NaN t
+// and for the miss value LBVH_MAX_FLOAT)
+__device__ __forceinline__ bool edge_pierces(float px, float py, float pz, float dx, float dy, float dz, const float4 v0, float e1x, float e1y,
+                                             float e1z, float e2x, float e2y, float e2z)
+{
+    ray_t r;
+    r.ox = px; r.oy = py; r.oz = pz;
+    r.dx = dx; r.dy = dy; r.dz = dz;
+    r.ix = 0.0f; r.iy = 0.0f; r.iz = 0.0f;               // (not read by the triangle test)
+    float u = 0.0f, v = 0.0f;
+    const float t = ray_triangle_edges(r, v0, e1x, e1y, e1z, e2x, e2y, e2z, u, v);
+    return 0.0f <= t && t <= 1.0f;
+}
+
+// the six edge tests of include/lbvh.h in its order; (ax ..) (bx ..) (cx ..) the query's vertices, (t0, t1, t2) the scene triangle's line
+__device__ __forceinline__ bool triangles_pierce(float ax, float ay, float az, float bx, float by, float bz, float cx, float cy, float cz,
+                                                 const float4 t0, const float4 t1, const float4 t2)
+{
+    // One copy of the test in a loop that is not unrolled, its operands selected by j: six inlined copies took 102 - 108 VGPRs
+    // (4 waves per SIMD).  j = 0, 1, 2: the ray (a, b - a), (b, c - b), (c, a - c) against (v0, e1, e2); j = 3, 4, 5: the ray
+    // (v0, e1), (v0, e2), (v0 + e1, e2 - e1) against (a, b - a, c - a).  Every difference is the one fp32 operation of the header.
+    const float abx = bx - ax, aby = by - ay, abz = bz - az;
+    const float acx = cx - ax, acy = cy - ay, acz = cz - az;
+#pragma nounroll
+    for (uint32_t j = 0; j < 6u; j++) {
+        const bool query_edge = j < 3u;
+        float px, py, pz, dx, dy, dz;
+        if (j == 0u) { px = ax; py = ay; pz = az; dx = abx; dy = aby; dz = abz; }
+        else if (j == 1u) { px = bx; py = by; pz = bz; dx = cx - bx; dy = cy - by; dz = cz - bz; }
+        else if (j == 2u) { px = cx; py = cy; pz = cz; dx = ax - cx; dy = ay - cy; dz = az - cz; }
+        else if (j == 3u) { px = t0.x; py = t0.y; pz = t0.z; dx = t1.x; dy = t1.y; dz = t1.z; }
+        else if (j == 4u) { px = t0.x; py = t0.y; pz = t0.z; dx = t2.x; dy = t2.y; dz = t2.z; }
+        else { px = t0.x + t1.x; py = t0.y + t1.y; pz = t0.z + t1.z; dx = t2.x - t1.x; dy = t2.y - t1.y; dz = t2.z - t1.z; }
+        const float4 v = query_edge ? t0 : make_float4(ax, ay, az, 0.0f);
+        if (edge_pierces(px, py, pz, dx, dy, dz, v, query_edge ? t1.x : abx, query_edge ? t1.y : aby, query_edge ? t1.z : abz,
+                         query_edge ? t2.x : acx, query_edge ? t2.y : acy, query_edge ? t2.z : acz))
+            return true;
+    }
+    return false;
+}
+
+template <int MODE, bool STATS>
+__global__ __launch_bounds__(64) void triangle_query_wide_kernel(const float4* __restrict__ queries, uint32_t total,     // three float4 per query
+                                                                 const lbvh_wide_node* __restrict__ wide,
+                                                                 const lbvh_fast_node* __restrict__ lines,
+                                                                 uint32_t* __restrict__ counts,            // kTriCount: candidates of query k; kTriAny: the flags
+                                                                 const uint64_t* __restrict__ offsets,     // kTriFill: where segment k starts
+                                                                 uint32_t* __restrict__ tris, uint64_t capacity,
+                                                                 uint32_t* __restrict__ deep,     // [gridDim.x][kWideStackDeep][64]
+                                                                 uint32_t lds_depth,              // <= kWideStackLds
+                                                                 uint32_t deep_cap,               // <= kWideStackDeep
+                                                                 uint32_t* __restrict__ fault, lbvh_ray_stats* stats)
+{
+    __shared__ uint32_t s_stack[kWideStackLds][LBVH_WAVE];
+    uint32_t* my_deep = deep + (size_t)blockIdx.x * (kWideStackDeep * LBVH_WAVE) + threadIdx.x;
+    const uint32_t lane = threadIdx.x;
+    const uint32_t run = max((total + gridDim.x - 1) / gridDim.x, 32u);
+    uint32_t next = blockIdx.x * run;
+    if (next >= total) return;
+    const uint32_t end = min(next + run, total);
+    uint32_t n_queries = 0, n_steps = 0, n_tris = 0;
+
+    bool active = false;
+    uint32_t i = 0, skip = kWideEmpty;
+    float ax = 0.0f, ay = 0.0f, az = 0.0f, bx = 0.0f, by = 0.0f, bz = 0.0f, cx = 0.0f, cy = 0.0f, cz = 0.0f;
+    float lx = 0.0f, ly = 0.0f, lz = 0.0f, hx = 0.0f, hy = 0.0f, hz = 0.0f;      // the query's box
+    uint32_t n_found = 0, sp = 0, node = 0;
+    uint64_t pos = 0;                                    // kTriFill: where this lane's next candidate goes
+    auto push = [&](uint32_t ref) {
+        if (sp < lds_depth) { s_stack[sp][lane] = ref; sp++; }
+        else if (sp < lds_depth + deep_cap) { my_deep[(sp - lds_depth) * LBVH_WAVE] = ref; sp++; }
+        // a dropped entry would be a silently short list: report it, as the other walkers do (lbvh_debug_ray_stack_limit provokes it)
+        else __hip_atomic_store(fault, LBVH_FAULT_RAY_STACK, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    };
+    for (;;) {
+        const uint64_t idle = __ballot(!active);
+        if (idle != 0 && next < end) {
+            if (!active) {
+                const uint32_t k = next + mbcnt64(idle);
+                if (k < end) {
+                    i = k;
+                    const float inf = __builtin_inff();
+                    const float4 qa = queries[3 * (size_t)k], qb = queries[3 * (size_t)k + 1], qc = queries[3 * (size_t)k + 2];
+                    ax = qa.x; ay = qa.y; az = qa.z; skip = __float_as_uint(qa.w);
+                    bx = qb.x; by = qb.y; bz = qb.z;
+                    cx = qc.x; cy = qc.y; cz = qc.z;
+                    lx = fminf(fminf(ax, bx), cx); ly = fminf(fminf(ay, by), cy); lz = fminf(fminf(az, bz), cz);
+                    hx = fmaxf(fmaxf(ax, bx), cx); hy = fmaxf(fmaxf(ay, by), cy); hz = fmaxf(fmaxf(az, bz), cz);
+                    active = fabsf(ax) < inf && fabsf(ay) < inf && fabsf(az) < inf && fabsf(bx) < inf && fabsf(by) < inf && fabsf(bz) < inf &&
+                             fabsf(cx) < inf && fabsf(cy) < inf && fabsf(cz) < inf;         // all nine finite (false for NaN)
+                    sp = 0; node = 0;
+                    if constexpr (MODE == kTriFill) { if (active) pos = offsets[k]; }
+                    else { n_found = 0; if (!active) counts[k] = 0u; }
+                    if (STATS && active) n_queries++;
+                }
+            }
+            next += (uint32_t)__popcll(idle);
+        }
+        if (!__any(active) && next >= end) break;
+        if (active) {
+            if (STATS) n_steps++;
+            const float4* w = reinterpret_cast<const float4*>(&wide[node]);
+            const float4 lox = w[0], loy = w[1], loz = w[2], hix = w[3], hiy = w[4], hiz = w[5];
+            const uint4 ref = reinterpret_cast<const uint4*>(w)[6];
+            const bool h0 = boxes_overlap(lx, ly, lz, hx, hy, hz, lox.x, loy.x, loz.x, hix.x, hiy.x, hiz.x) && ref.x != kWideEmpty;
+            const bool h1 = boxes_overlap(lx, ly, lz, hx, hy, hz, lox.y, loy.y, loz.y, hix.y, hiy.y, hiz.y) && ref.y != kWideEmpty;
+            const bool h2 = boxes_overlap(lx, ly, lz, hx, hy, hz, lox.z, loy.z, loz.z, hix.z, hiy.z, hiz.z) && ref.z != kWideEmpty;
+            const bool h3 = boxes_overlap(lx, ly, lz, hx, hy, hz, lox.w, loy.w, loz.w, hix.w, hiy.w, hiz.w) && ref.w != kWideEmpty;
+            const uint32_t hit = (h0 ? 1u : 0u) | (h1 ? 2u : 0u) | (h2 ? 4u : 0u) | (h3 ? 8u : 0u);
+            const uint32_t leaf = (ref.x >> 31) | ((ref.y >> 31) << 1) | ((ref.z >> 31) << 2) | ((ref.w >> 31) << 3);
+            uint32_t leaves = hit & leaf, inner = hit & ~leaf;
+            while (leaves != 0u) {
+                const uint32_t k = (uint32_t)__builtin_ctz(leaves);
+                leaves &= leaves - 1u;
+                const uint32_t line = pick4(ref, k) & 0x7FFFFFFFu;
+                float4 t0, t1, t2;
+                unpack_fast_triangle(reinterpret_cast<const float4*>(&lines[line]), t0, t1, t2);
+                const uint32_t tri = __float_as_uint(t0.w);
+                if (tri == skip) continue;
+                if (STATS) n_tris++;
+                if (!triangles_pierce(ax, ay, az, bx, by, bz, cx, cy, cz, t0, t1, t2)) continue;
+                if constexpr (MODE == kTriFill) {
+                    if (pos < capacity) tris[pos] = tri;         // never a word at or beyond the capacity
+                    pos++;
+                } else {
+                    n_found++;
+                    if constexpr (MODE == kTriAny) { leaves = 0u; inner = 0u; sp = 0; }       // the first candidate ends the walk
+                }
+            }
+            if (inner != 0u) {
+                node = pick4(ref, (uint32_t)__builtin_ctz(inner));
+                inner &= inner - 1u;
+                while (inner != 0u) {
+                    push(pick4(ref, (uint32_t)__builtin_ctz(inner)));
+                    inner &= inner - 1u;
+                }
+            } else if (sp != 0) {
+                sp--;
+                node = sp < lds_depth ? s_stack[sp][lane] : my_deep[(sp - lds_depth) * LBVH_WAVE];
+            } else {
+                if constexpr (MODE != kTriFill) counts[i] = n_found;
+                active = false;
+            }
+        }
+    }
+    if (STATS) add_ray_stats(stats, n_queries, n_steps, n_tris);
+}
+
 // ---- crossing parities of points along fixed directions (lbvh_point_crossings, include/lbvh.h) -------------------------
 // The directions travel by value in the kernel's arguments; a lane reads the one it walks next from there.
 struct crossing_dirs { float d[LBVH_CROSSING_MAX_DIRS][3]; };
@@ -2201,7 +2361,60 @@ static lbvh_status overlap_queries(lbvh_context* ctx, const void* d_queries, siz
     return LBVH_OK;
 }
 
+// lbvh_triangle_intersections: overlap_queries<>'s shape with the triangle walk (count walk -> the same three scan kernels -> fill
+// walk, counts and tile sums in the same two slices of the ray scratch); lbvh_triangle_intersects_any: one launch, the flags are the
+// walk's own output.  Four-wide walk only.
+template <bool ANY>
+static lbvh_status triangle_queries(lbvh_context* ctx, const lbvh_tri_query* d_queries, size_t count, const lbvh_scene* h_scene, uint64_t* d_offsets,
+                                    uint32_t* d_tris, uint64_t capacity, uint32_t* d_flags, const char* who)
+{
+    if (!ctx) return LBVH_ERR_INVALID_ARG;
+    if (count == 0) return LBVH_OK;
+    LBVH_REQUIRE(ctx, d_queries != nullptr && h_scene != nullptr && (ANY ? d_flags != nullptr : d_offsets != nullptr));
+    LBVH_REQUIRE(ctx, d_tris != nullptr || capacity == 0);
+    LBVH_REQUIRE(ctx, ((uintptr_t)d_queries & 15) == 0 && ((uintptr_t)d_offsets & 7) == 0 && ((uintptr_t)d_tris & 3) == 0 && ((uintptr_t)d_flags & 3) == 0);
+    LBVH_REQUIRE(ctx, count <= 0xFFFFFFFFull);
+    walk_launch w;
+    const lbvh_status rc = begin_walk(ctx, h_scene, count, who, true, &w);
+    if (rc != LBVH_OK) return rc;
+    const float4* q = (const float4*)d_queries;
+    const uint32_t total = (uint32_t)count;
+    if constexpr (ANY) {
+        LBVH_LAUNCH_STATS(ctx, ctx->ray_stats, (triangle_query_wide_kernel<kTriAny, STATS>), dim3(w.waves), dim3(LBVH_WAVE), q, total, w.wn, ctx->fast_nodes,
+                          d_flags, (const uint64_t*)nullptr, (uint32_t*)nullptr, (uint64_t)0, w.deep, w.lds, w.deep_cap, ctx->fault_dev, ctx->ray_stats);
+    } else {
+        uint32_t* counts = ray_list(ctx, count, 0);
+        uint64_t* tile_sums = (uint64_t*)ray_list(ctx, count, 1);
+        const uint32_t n_tiles = total / kScanTile + 1u;           // the tiles cover total + 1 offsets (sizes: see overlap_queries)
+        LBVH_LAUNCH_STATS(ctx, ctx->ray_stats, (triangle_query_wide_kernel<kTriCount, STATS>), dim3(w.waves), dim3(LBVH_WAVE), q, total, w.wn, ctx->fast_nodes,
+                          counts, (const uint64_t*)nullptr, (uint32_t*)nullptr, (uint64_t)0, w.deep, w.lds, w.deep_cap, ctx->fault_dev, ctx->ray_stats);
+        if (n_tiles > 1u) {
+            LBVH_LAUNCH(ctx, overlap_tile_sums_kernel, dim3(n_tiles), dim3(256), (const uint32_t*)counts, total, tile_sums);
+            LBVH_LAUNCH(ctx, overlap_scan_sums_kernel, dim3(1), dim3(1024), tile_sums, n_tiles);
+        }
+        LBVH_LAUNCH(ctx, overlap_offsets_kernel, dim3(n_tiles), dim3(256), (const uint32_t*)counts, total,
+                    n_tiles > 1u ? (const uint64_t*)tile_sums : (const uint64_t*)nullptr, d_offsets);
+        if (capacity != 0)
+            LBVH_LAUNCH_STATS(ctx, ctx->ray_stats, (triangle_query_wide_kernel<kTriFill, STATS>), dim3(w.waves), dim3(LBVH_WAVE), q, total, w.wn, ctx->fast_nodes,
+                              (uint32_t*)nullptr, (const uint64_t*)d_offsets, d_tris, capacity, w.deep, w.lds, w.deep_cap, ctx->fault_dev, ctx->ray_stats);
+    }
+    LBVH_HIP_TRY(ctx, hipGetLastError());
+    return LBVH_OK;
+}
+
 extern "C" {
+
+lbvh_status lbvh_triangle_intersections(lbvh_context* ctx, const lbvh_tri_query* d_queries, size_t count, const lbvh_scene* h_scene,
+                                        uint64_t* d_offsets, uint32_t* d_tris, uint64_t capacity)
+{
+    return triangle_queries<false>(ctx, d_queries, count, h_scene, d_offsets, d_tris, capacity, nullptr, "lbvh_triangle_intersections");
+}
+
+lbvh_status lbvh_triangle_intersects_any(lbvh_context* ctx, const lbvh_tri_query* d_queries, size_t count, const lbvh_scene* h_scene,
+                                         uint32_t* d_flags)
+{
+    return triangle_queries<true>(ctx, d_queries, count, h_scene, nullptr, nullptr, 0, d_flags, "lbvh_triangle_intersects_any");
+}
 
 // the four-wide walk only (lbvh_debug_ray_walker does not apply), one launch; the per-lane lists are dynamic LDS sized from k
 lbvh_status lbvh_trace_k_closest(lbvh_context* ctx, const lbvh_ray* d_rays, size_t count, uint32_t k, const lbvh_scene* h_scene,

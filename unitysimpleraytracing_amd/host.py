@@ -470,7 +470,9 @@ class RaytracingMeshDrawer:
         """Convenience: count -> one 8-byte download -> allocate -> fill.  `queries`: a DataBuffer of layouts.AABB (box form) or of
         layouts.POINT_QUERY (distance form).  Returns (offsets, tris): host arrays, uint64[queries.size + 1] and uint32[total].
         device_sort=True issues sort_index_segments before the download: every segment ascending."""
-        call = self.box_overlaps if queries.dtype == L.AABB else self.gather_within_distance
+        return self._csr_lists(self.box_overlaps if queries.dtype == L.AABB else self.gather_within_distance, queries, min_capacity, device_sort)
+
+    def _csr_lists(self, call, queries, min_capacity, device_sort):
         count = queries.size
         offsets = DataBuffer(self.ctx, count + 1, np.uint64)
         try:
@@ -489,6 +491,27 @@ class RaytracingMeshDrawer:
                 tris.dispose()
         finally:
             offsets.dispose()
+
+    def triangle_intersections(self, queries, offsets, tris=None):
+        """Every scene triangle each triangle of the DataBuffer `queries` (layouts.TRI_QUERY: a, skip, b, c) intersects — the narrow
+        phase behind box_overlaps —, as a CSR list on the caller's buffers exactly as box_overlaps writes it: `offsets` (uint64
+        DataBuffer, at least queries.size + 1 entries) always complete, `tris` (uint32 DataBuffer, its size is the capacity) the
+        ORIGINAL triangle indices in no particular order; tris=None counts only.  skip = the original index of a scene triangle
+        that is never reported (a mesh against itself), layouts.NULL for none.  Asynchronous."""
+        self._overlaps(N.lib.lbvh_triangle_intersections, queries, L.TRI_QUERY, offsets, tris)
+
+    def triangle_intersects_any(self, queries, flags):
+        """1 into the uint32 DataBuffer `flags` for each triangle of `queries` that intersects any scene triangle, else 0."""
+        if queries.dtype != L.TRI_QUERY or flags.dtype != np.uint32 or flags.size < queries.size:
+            raise ValueError("queries must be a DataBuffer of layouts.TRI_QUERY and flags one of uint32 with at least as many entries")
+        s = self.container.scene()
+        N.check(self.ctx.handle, N.lib.lbvh_triangle_intersects_any(self.ctx.handle, queries.device, queries.size, C.byref(s), flags.device))
+
+    def intersections(self, queries, min_capacity=1, device_sort=False):
+        """Convenience, as overlaps(): count -> one 8-byte download -> allocate -> fill, for a DataBuffer of layouts.TRI_QUERY.
+        Returns (offsets, tris): host arrays, uint64[queries.size + 1] and uint32[total].  device_sort=True issues
+        sort_index_segments before the download: every segment ascending."""
+        return self._csr_lists(self.triangle_intersections, queries, min_capacity, device_sort)
 
     def count_hits(self, rays, counts):
         """The number of candidates of each ray of `rays` (layouts.RAY) in (t_min, t_max) into the uint32 DataBuffer `counts`: every

@@ -45,6 +45,12 @@
 //                                                on the same rays written out ({p, 0, dir, +inf}); prints the sum of the counts,
 //                                                the sum of the parity words, how many points the majority calls inside and
 //                                                whether every parity bit equals its ray's count AND 1
+//     lbvh_driver tris <n_queries> [seed]        the 4 096 triangles of cfg1 and n_queries query triangles (SplitMix64, seed default 5):
+//                                                per axis a centre uniform in the mesh's box, then b's and c's offsets uniform in
+//                                                [-3, 3].  TriangleIntersections (count only, one 8-byte read, fill),
+//                                                SortIndexSegments, TriangleIntersectsAny; prints the total, how many segments are
+//                                                non-empty, how many flags are set, the sum of (position + 1) * triangle index over
+//                                                the device-sorted list (mod 2^64) and the first segments
 #include <chrono>
 #include <cmath>
 #include <cstdio>
@@ -571,6 +577,62 @@ static int overlaps_main(int argc, char** argv)
     return 0;
 }
 
+static int tris_main(int argc, char** argv)
+{
+    const size_t count = argc > 2 ? (size_t)strtoull(argv[2], nullptr, 10) : 65536;
+    uint64_t seed = argc > 3 ? strtoull(argv[3], nullptr, 10) : 5;
+    const std::vector<lbvh_triangle> mesh = random_mesh(4096);
+    float lo[3], hi[3];
+    mesh_box(mesh, lo, hi);
+    lbvh::Context ctx(0);
+    lbvh::RaytracingMeshDrawer drawer(ctx, mesh);
+    drawer.Awake();
+    lbvh::DataBuffer<lbvh_tri_query> queries(ctx, count);
+    for (size_t i = 0; i < count; i++) {
+        lbvh_tri_query& q = queries.LocalBuffer()[i];
+        std::memset(&q, 0, sizeof q);
+        q.skip = LBVH_NULL;
+        for (int k = 0; k < 3; k++) {
+            const float centre = uniform(seed, lo[k], hi[k]);
+            q.a[k] = centre;
+            q.b[k] = centre + uniform(seed, -3.0f, 3.0f);
+            q.c[k] = centre + uniform(seed, -3.0f, 3.0f);
+        }
+    }
+    queries.Sync();
+    lbvh::DataBuffer<uint64_t> offsets(ctx, count + 1);
+    drawer.TriangleIntersections(queries, offsets);
+    offsets.GetData();
+    const unsigned long long total = offsets.LocalBuffer()[count];
+    lbvh::DataBuffer<uint32_t> tris(ctx, total ? (size_t)total : 1);
+    drawer.TriangleIntersections(queries, offsets, &tris);
+    drawer.SortIndexSegments(offsets, tris, count);
+    lbvh::DataBuffer<uint32_t> flags(ctx, count);
+    drawer.TriangleIntersectsAny(queries, flags);
+    offsets.GetData();
+    tris.GetData();
+    flags.GetData();
+    size_t non_empty = 0, flagged = 0;
+    unsigned long long weighted = 0;
+    for (size_t i = 0; i < count; i++) {
+        non_empty += offsets.LocalBuffer()[i + 1] > offsets.LocalBuffer()[i];
+        flagged += flags.LocalBuffer()[i];
+    }
+    for (size_t i = 0; i < (size_t)total; i++) weighted += (unsigned long long)(i + 1) * tris.LocalBuffer()[i];
+    std::printf("{\"triangles\": %zu, \"queries\": %zu, \"total\": %llu, \"non_empty\": %zu, \"flagged\": %zu, \"weighted_index_sum\": %llu, \"segments\": [",
+                mesh.size(), count, total, non_empty, flagged, weighted);
+    size_t shown = 0;
+    for (size_t i = 0; i < count && shown < 3; i++) {
+        const uint64_t first = offsets.LocalBuffer()[i], last = offsets.LocalBuffer()[i + 1];
+        if (first == last) continue;
+        std::printf("%s[%zu", shown++ ? ", " : "", i);
+        for (uint64_t j = first; j < last; j++) std::printf(", %u", tris.LocalBuffer()[j]);
+        std::printf("]");
+    }
+    std::printf("]}\n");
+    return 0;
+}
+
 static int crossings_main(int argc, char** argv)
 {
     const size_t count = argc > 3 ? (size_t)strtoull(argv[3], nullptr, 10) : 65536;
@@ -704,7 +766,7 @@ int main(int argc, char** argv)
 {
     static const struct { const char* name; int (*run)(int, char**); } commands[] = {
         {"crossings", crossings_main}, {"points", points_main}, {"knn", knn_main},   {"khits", khits_main}, {"gather", gather_main}, {"sortedhits", sortedhits_main},
-        {"sweep", sweep_main},         {"overlaps", overlaps_main}, {"rays", rays_main}, {"sort", sort_main},   {"multi", multi_main}};
+        {"sweep", sweep_main},         {"overlaps", overlaps_main}, {"tris", tris_main}, {"rays", rays_main}, {"sort", sort_main},   {"multi", multi_main}};
     try {
         for (const auto& c : commands)
             if (argc > 1 && std::strcmp(argv[1], c.name) == 0) return c.run(argc, argv);

@@ -380,6 +380,24 @@ public:
                                                       (uint64_t*)offsets.DeviceBuffer(), tris ? (uint32_t*)tris->DeviceBuffer() : nullptr,
                                                       tris ? (uint64_t)tris->Size() : 0));
     }
+    // WHICH scene triangles each query triangle intersects — the narrow phase behind BoxOverlaps —, as the same CSR list, or one
+    // flag per query (lbvh_triangle_intersections / lbvh_triangle_intersects_any; asynchronous).  skip = the ORIGINAL index of a
+    // scene triangle that is never reported (a mesh against itself), LBVH_NULL for none.
+    void TriangleIntersections(const DataBuffer<lbvh_tri_query>& queries, DataBuffer<uint64_t>& offsets, DataBuffer<uint32_t>* tris = nullptr)
+    {
+        if (offsets.Size() < queries.Size() + 1) throw Error(LBVH_ERR_INVALID_ARG, "TriangleIntersections: offsets needs one entry more than queries");
+        const lbvh_scene s = container_->Scene();
+        check(ctx_.get(), lbvh_triangle_intersections(ctx_.get(), (const lbvh_tri_query*)queries.DeviceBuffer(), queries.Size(), &s,
+                                                      (uint64_t*)offsets.DeviceBuffer(), tris ? (uint32_t*)tris->DeviceBuffer() : nullptr,
+                                                      tris ? (uint64_t)tris->Size() : 0));
+    }
+    void TriangleIntersectsAny(const DataBuffer<lbvh_tri_query>& queries, DataBuffer<uint32_t>& flags)
+    {
+        if (flags.Size() < queries.Size()) throw Error(LBVH_ERR_INVALID_ARG, "TriangleIntersectsAny: fewer flags than queries");
+        const lbvh_scene s = container_->Scene();
+        check(ctx_.get(), lbvh_triangle_intersects_any(ctx_.get(), (const lbvh_tri_query*)queries.DeviceBuffer(), queries.Size(), &s,
+                                                       (uint32_t*)flags.DeviceBuffer()));
+    }
     // how many triangles each ray crosses in (t_min, t_max), and crossing parities of points along fixed directions — bit j of a
     // point's word: the count of the ray from it along dirs[j] (x, y, z; 1 .. 32 of them), AND 1 (lbvh_count_hits /
     // lbvh_point_crossings; asynchronous).  Inside / outside: more than half of the bits set.

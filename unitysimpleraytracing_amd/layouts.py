@@ -40,6 +40,10 @@ assert SPHERE_RAY.itemsize == 32
 POINT_QUERY = np.dtype([("p", "<f4", 3), ("max_dist2", "<f4")])
 CLOSEST_POINT = np.dtype([("dist2", "<f4"), ("tri", "<u4"), ("u", "<f4"), ("v", "<f4")])
 assert POINT_QUERY.itemsize == 16 and CLOSEST_POINT.itemsize == 16
+# lbvh_triangle_intersections / lbvh_triangle_intersects_any: a query triangle; skip = the ORIGINAL index of a scene triangle that is
+# never a candidate (NULL below, LBVH_NULL: none)
+TRI_QUERY = np.dtype([("a", "<f4", 3), ("skip", "<u4"), ("b", "<f4", 3), ("_pad0", "<u4"), ("c", "<f4", 3), ("_pad1", "<u4")])
+assert TRI_QUERY.itemsize == 48
 
 assert AABB.itemsize == 32          # Assets/_Scripts/MeshBufferContainer.cs:103
 assert TRIANGLE.itemsize == 128     # Assets/_Scripts/MeshBufferContainer.cs:98
