@@ -1000,6 +1000,66 @@ lbvh_status lbvh_triangle_intersections(lbvh_context* ctx, const lbvh_tri_query*
 lbvh_status lbvh_triangle_intersects_any(lbvh_context* ctx, const lbvh_tri_query* d_queries, size_t count, const lbvh_scene* h_scene,
                                          uint32_t* d_flags);
 
+/* A convex region bounded by six planes: 96 bytes; arrays of them 16-byte aligned.  A plane {nx, ny, nz, d} keeps the half space
+ * n . x + d >= 0; the region is the intersection of its six half spaces.  Normals need not be unit length.  A region with fewer
+ * faces repeats a plane or pads with {0, 0, 0, 1}. */
+#define LBVH_REGION_PLANES    6
+#define LBVH_REGION_TOUCHING  0u   /* triangles whose box is not wholly outside any plane  */
+#define LBVH_REGION_CONTAINED 1u   /* triangles whose box is wholly inside every plane     */
+typedef struct lbvh_region { float plane[LBVH_REGION_PLANES][4]; } lbvh_region;   /* 96 bytes, arrays 16-byte aligned */
+
+/* Region queries: WHICH triangles lie in a convex region bounded by planes — a camera or light frustum, an oriented box, an
+ * editor's window / crossing selection —, as a CSR list (lbvh_region_overlaps) or as one flag per region
+ * (lbvh_region_overlaps_any), over the derived traversal scene in its four-wide form by the walk of lbvh_box_overlaps.
+ *   Arithmetic: strict fp32, every operation rounded on its own, no contraction, gradual underflow (what numpy does).  For a box
+ *   [lo, hi] and a plane {nx, ny, nz, d} — the comparison n_a >= 0 is true for -0 and false for NaN —
+ *       P = ((nx * (nx >= 0 ? hi.x : lo.x) + ny * (ny >= 0 ? hi.y : lo.y)) + nz * (nz >= 0 ? hi.z : lo.z)) + d
+ *       N = ((nx * (nx >= 0 ? lo.x : hi.x) + ny * (ny >= 0 ? lo.y : hi.y)) + nz * (nz >= 0 ? lo.z : hi.z)) + d
+ *   P is the plane's value at the box corner farthest along the normal, N at the nearest.
+ *   Candidate: with A = scene.triangle_aabb[i], the padded own box the leaf slot holds, and P_j, N_j for plane j = 0 .. 5,
+ *     mode LBVH_REGION_TOUCHING:  triangle i is a candidate iff P_j(A) >= 0 for all six planes;
+ *     mode LBVH_REGION_CONTAINED: triangle i is a candidate iff N_j(A) >= 0 for all six planes.
+ *   What follows from this definition:
+ *     A NaN anywhere makes its comparison false, so there are no special cases and no "inactive query" rule: a region with a NaN
+ *     plane simply has no candidates.  (An infinite word gives what the arithmetic gives: +-inf or, from inf - inf or 0 * inf, NaN.)
+ *     TOUCHING is a broad phase on the triangles' BOXES by design: the standard conservative frustum test, which may accept a box
+ *     near a corner of the region that no single plane rejects.  It is the box analogue of lbvh_box_overlaps.
+ *     CONTAINED is exact in the useful direction: a triangle lies inside its own box, so a CONTAINED triangle is wholly inside
+ *     the region.  A caller can skip clipping for it, and an editor gets window selection.
+ *   Why the list does not depend on the walk: fp32 multiplication by a fixed factor and fp32 addition are monotone, and every box
+ *   of the derived tree, binary or four-wide, is the exact min / max union of what lies below it.  So for a leaf box A below a slot
+ *   box B, P_j(B) >= P_j(A): per axis the factor's sign picks hi, which only grows towards the root, or lo, which only shrinks.
+ *   With lo <= hi, N_j(A) <= P_j(A).  Hence every ancestor slot of a candidate of EITHER mode passes the TOUCHING test.  The walk
+ *   enters a slot iff all six P_j >= 0 and applies the mode's test at leaf slots only.  Each triangle is one leaf, so each
+ *   candidate appears exactly once.
+ * Output of lbvh_region_overlaps — the CSR contract of lbvh_box_overlaps, word for word:
+ *   d_offsets: count + 1 words of 64 bits.  d_offsets[k] = the number of candidates of regions 0 .. k-1, d_offsets[count] = the
+ *   total M.  Always written in full, whatever `capacity` is.
+ *   d_tris, `capacity` words of 32 bits: segment k = d_tris[d_offsets[k] .. d_offsets[k+1]) = the ORIGINAL triangle indices of
+ *   region k's candidates, each exactly once.  THE ORDER INSIDE A SEGMENT IS THE WALK'S AND IS NOT PART OF THE CONTRACT;
+ *   lbvh_sort_index_segments applies unchanged and leaves every fitting segment strictly ascending.
+ *   Overflow: no word at index >= capacity is ever written; every segment with d_offsets[k+1] <= capacity is complete; words
+ *   below `capacity` that belong to a segment which does not fit are unspecified.  The call never waits on the host and returns
+ *   LBVH_OK in both cases: the caller reads d_offsets[count] (one 8-byte download) to learn what was needed.
+ *   Count-only form: capacity == 0 writes the offsets and walks once (d_tris may be NULL); otherwise the scene is walked twice
+ *   (count, device-side scan, fill: the same kernel making the same decisions, so a segment never outgrows its slot).
+ * Output of lbvh_region_overlaps_any: d_flags[k] = 1 exactly when segment k would be non-empty, else 0; every one of the `count`
+ * words is written.  The walk is the same, cut off at a region's first candidate.
+ * Both need the derived traversal scene (lbvh_build_fast_scene; a stale one is LBVH_ERR_INVALID_ARG), are asynchronous on the
+ * context's stream with no host wait, and use the context's ray scratch: they drop the path tracer's live-path list (see
+ * lbvh_path_bounce).  count == 0 is a no-op: nothing is enqueued and no buffer is touched, d_offsets[0] included.  Rejected
+ * (LBVH_ERR_INVALID_ARG): NULL ctx / d_regions / h_scene / d_offsets / d_flags, mode > 1, d_regions not 16-byte aligned, d_offsets
+ * not 8-byte aligned, d_tris or d_flags not 4-byte aligned, d_tris == NULL with capacity > 0, count > 2^32 - 1.  Four-wide walk
+ * only (lbvh_debug_ray_walker does not apply); lbvh_debug_ray_waves, lbvh_debug_ray_stack_split, lbvh_debug_ray_stack_limit and
+ * lbvh_ray_stats_target apply as to the overlap queries (rays counts every region, triangle_tests the leaf slots that passed the
+ * TOUCHING test; the full form reports twice the count-only form's).
+ * One region per lane: a single camera frustum over the whole mesh keeps one lane busy while 63 idle.  The call is for MANY
+ * regions (clusters, lights, oriented boxes, portals), not for one huge one. */
+lbvh_status lbvh_region_overlaps(lbvh_context* ctx, const lbvh_region* d_regions, size_t count, uint32_t mode, const lbvh_scene* h_scene,
+                                 uint64_t* d_offsets, uint32_t* d_tris, uint64_t capacity);
+lbvh_status lbvh_region_overlaps_any(lbvh_context* ctx, const lbvh_region* d_regions, size_t count, uint32_t mode, const lbvh_scene* h_scene,
+                                     uint32_t* d_flags);
+
 /* Camera rays into path states (origin/dir as Raytracing.compute:108-126, throughput 1, radiance 0, alive). */
 lbvh_status lbvh_path_begin(lbvh_context* ctx, const lbvh_camera* h_camera, lbvh_path_state* d_states);
 
@@ -1024,7 +1084,7 @@ lbvh_status lbvh_path_scatter(lbvh_context* ctx, const lbvh_scene* h_scene, cons
  * lbvh_path_bounce on the same d_states / d_hits listed as live (a list kept by the context).  Every library call that writes
  * into those buffers drops the list (lbvh_path_begin, lbvh_trace_rays, a primary trace into any part of d_hits,
  * lbvh_buffer_upload / _fill_u32 / _free), and so does lbvh_trace_forget — and so do lbvh_trace_closest,
- * lbvh_trace_occluded, lbvh_closest_point_query, lbvh_within_distance, lbvh_count_hits, lbvh_point_crossings, lbvh_box_overlaps, lbvh_gather_within_distance, lbvh_k_closest_points, lbvh_trace_k_closest, lbvh_gather_hits, lbvh_sphere_cast, lbvh_sphere_cast_any, lbvh_triangle_intersections and lbvh_triangle_intersects_any, whatever buffers they are given, since they use the same ray scratch; then every state is scanned again.  The one exception among the query calls:
+ * lbvh_trace_occluded, lbvh_closest_point_query, lbvh_within_distance, lbvh_count_hits, lbvh_point_crossings, lbvh_box_overlaps, lbvh_gather_within_distance, lbvh_k_closest_points, lbvh_trace_k_closest, lbvh_gather_hits, lbvh_sphere_cast, lbvh_sphere_cast_any, lbvh_triangle_intersections, lbvh_triangle_intersects_any, lbvh_region_overlaps and lbvh_region_overlaps_any, whatever buffers they are given, since they use the same ray scratch; then every state is scanned again.  The one exception among the query calls:
  * lbvh_sort_hit_segments and lbvh_sort_index_segments take no context scratch and keep the live-path list (they drop it only when the
  * buffer they sort is d_hits itself).  What the library
  * cannot see is a write of the CALLER's own (a kernel or hipMemcpy that revives or ends paths, Russian roulette): between two

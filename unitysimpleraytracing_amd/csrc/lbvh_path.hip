@@ -1910,6 +1910,147 @@ __global__ __launch_bounds__(64) void triangle_query_wide_kernel(const float4* _
     if (STATS) add_ray_stats(stats, n_queries, n_steps, n_tris);
 }
 
+// ---- region queries: which triangles lie in a convex region of six planes (lbvh_region_overlaps, include/lbvh.h) ---------
+// The frame of overlap_wide_kernel<BOX = true> with another slot test: a slot is entered iff for each of the six planes
+// {nx, ny, nz, d} the box corner farthest along the normal is on the kept side, P = ((nx * X + ny * Y) + nz * Z) + d >= 0 with
+// X = nx >= 0 ? hi.x : lo.x and so on (the conservative frustum test).  A leaf slot's box is the triangle's own, so a leaf slot
+// that passes IS a TOUCHING candidate and, as for the box form, costs no triangle line: line - leaf_base is the original index.
+// CONTAINED asks the same of the nearest corner (N, the other choice on every axis) at leaf slots only; N <= P, so the walk's
+// pruning is the same for both modes (the argument is in the header).  Nothing shrinks: the first passing inner slot is entered,
+// the others wait on the stack.  There is no inactive region: a NaN fails every comparison, so such a region leaves at the root.
+// Registers: the 24 plane words stay in the lane; which corner feeds P is decided once per query (18 flags, far_x / far_y / far_z),
+// not in every slot.  The sums cannot contract: the file is compiled with -ffp-contract=off.
+// `contained` is a kernel argument, not a template parameter: one branch per leaf slot against twice the instantiations.
+enum region_mode : int { kRegionCount = 0, kRegionFill = 1, kRegionAny = 2 };
+
+__device__ __forceinline__ float pickf4(const float4 v, uint32_t k) { return k == 0u ? v.x : (k == 1u ? v.y : (k == 2u ? v.z : v.w)); }
+
+__device__ __forceinline__ float plane_value(float nx, float ny, float nz, float d, float x, float y, float z)
+{
+    return ((nx * x + ny * y) + nz * z) + d;
+}
+
+template <int MODE, bool STATS>
+__global__ __launch_bounds__(64) void region_wide_kernel(const float4* __restrict__ regions, uint32_t total,      // six float4 per region
+                                                         uint32_t contained,                       // LBVH_REGION_CONTAINED != 0
+                                                         const lbvh_wide_node* __restrict__ wide, uint32_t leaf_base,
+                                                         uint32_t* __restrict__ counts,            // kRegionCount: candidates of region k; kRegionAny: the flags
+                                                         const uint64_t* __restrict__ offsets,     // kRegionFill: where segment k starts
+                                                         uint32_t* __restrict__ tris, uint64_t capacity,
+                                                         uint32_t* __restrict__ deep,     // [gridDim.x][kWideStackDeep][64]
+                                                         uint32_t lds_depth,              // <= kWideStackLds
+                                                         uint32_t deep_cap,               // <= kWideStackDeep
+                                                         uint32_t* __restrict__ fault, lbvh_ray_stats* stats)
+{
+    __shared__ uint32_t s_stack[kWideStackLds][LBVH_WAVE];
+    uint32_t* my_deep = deep + (size_t)blockIdx.x * (kWideStackDeep * LBVH_WAVE) + threadIdx.x;
+    const uint32_t lane = threadIdx.x;
+    const uint32_t run = max((total + gridDim.x - 1) / gridDim.x, 32u);
+    uint32_t next = blockIdx.x * run;
+    if (next >= total) return;
+    const uint32_t end = min(next + run, total);
+    uint32_t n_queries = 0, n_steps = 0, n_tris = 0;
+
+    bool active = false;
+    uint32_t i = 0;
+    float4 pl[LBVH_REGION_PLANES];                                   // the planes, in registers (every index below is a constant)
+    bool far_x[LBVH_REGION_PLANES], far_y[LBVH_REGION_PLANES], far_z[LBVH_REGION_PLANES];      // n >= 0: hi feeds P (and lo feeds N)
+#pragma unroll
+    for (int j = 0; j < LBVH_REGION_PLANES; j++) {
+        pl[j] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+        far_x[j] = far_y[j] = far_z[j] = false;
+    }
+    uint32_t n_found = 0, sp = 0, node = 0;
+    uint64_t pos = 0;                                    // kRegionFill: where this lane's next candidate goes
+    auto push = [&](uint32_t ref) {
+        if (sp < lds_depth) { s_stack[sp][lane] = ref; sp++; }
+        else if (sp < lds_depth + deep_cap) { my_deep[(sp - lds_depth) * LBVH_WAVE] = ref; sp++; }
+        // a dropped entry would be a silently short list: report it, as the other walkers do (lbvh_debug_ray_stack_limit provokes it)
+        else __hip_atomic_store(fault, LBVH_FAULT_RAY_STACK, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    };
+    auto emit = [&](uint32_t tri) {
+        if constexpr (MODE == kRegionFill) {
+            if (pos < capacity) tris[pos] = tri;         // never a word at or beyond the capacity
+            pos++;
+        } else {
+            n_found++;
+        }
+    };
+    for (;;) {
+        const uint64_t idle = __ballot(!active);
+        if (idle != 0 && next < end) {
+            if (!active) {
+                const uint32_t k = next + mbcnt64(idle);
+                if (k < end) {
+                    i = k;
+#pragma unroll
+                    for (int j = 0; j < LBVH_REGION_PLANES; j++) {
+                        pl[j] = regions[LBVH_REGION_PLANES * (size_t)k + j];
+                        far_x[j] = pl[j].x >= 0.0f; far_y[j] = pl[j].y >= 0.0f; far_z[j] = pl[j].z >= 0.0f;      // true for -0, false for NaN
+                    }
+                    active = true;
+                    sp = 0; node = 0;
+                    if constexpr (MODE == kRegionFill) pos = offsets[k];
+                    else n_found = 0;
+                    if (STATS) n_queries++;
+                }
+            }
+            next += (uint32_t)__popcll(idle);
+        }
+        if (!__any(active) && next >= end) break;
+        if (active) {
+            if (STATS) n_steps++;
+            const float4* w = reinterpret_cast<const float4*>(&wide[node]);
+            const float4 lox = w[0], loy = w[1], loz = w[2], hix = w[3], hiy = w[4], hiz = w[5];
+            const uint4 ref = reinterpret_cast<const uint4*>(w)[6];
+            bool h0 = ref.x != kWideEmpty, h1 = ref.y != kWideEmpty, h2 = ref.z != kWideEmpty, h3 = ref.w != kWideEmpty;
+#pragma unroll
+            for (int j = 0; j < LBVH_REGION_PLANES; j++) {
+                const float4 x = far_x[j] ? hix : lox, y = far_y[j] ? hiy : loy, z = far_z[j] ? hiz : loz;
+                h0 &= plane_value(pl[j].x, pl[j].y, pl[j].z, pl[j].w, x.x, y.x, z.x) >= 0.0f;
+                h1 &= plane_value(pl[j].x, pl[j].y, pl[j].z, pl[j].w, x.y, y.y, z.y) >= 0.0f;
+                h2 &= plane_value(pl[j].x, pl[j].y, pl[j].z, pl[j].w, x.z, y.z, z.z) >= 0.0f;
+                h3 &= plane_value(pl[j].x, pl[j].y, pl[j].z, pl[j].w, x.w, y.w, z.w) >= 0.0f;
+            }
+            const uint32_t hit = (h0 ? 1u : 0u) | (h1 ? 2u : 0u) | (h2 ? 4u : 0u) | (h3 ? 8u : 0u);
+            const uint32_t leaf = (ref.x >> 31) | ((ref.y >> 31) << 1) | ((ref.z >> 31) << 2) | ((ref.w >> 31) << 3);
+            uint32_t leaves = hit & leaf, inner = hit & ~leaf;
+            while (leaves != 0u) {
+                const uint32_t k = (uint32_t)__builtin_ctz(leaves);
+                leaves &= leaves - 1u;
+                if (STATS) n_tris++;
+                if (contained != 0u) {
+                    const float lx = pickf4(lox, k), ly = pickf4(loy, k), lz = pickf4(loz, k);
+                    const float hx = pickf4(hix, k), hy = pickf4(hiy, k), hz = pickf4(hiz, k);
+                    bool inside = true;
+#pragma unroll
+                    for (int j = 0; j < LBVH_REGION_PLANES; j++)
+                        inside &= plane_value(pl[j].x, pl[j].y, pl[j].z, pl[j].w, far_x[j] ? lx : hx, far_y[j] ? ly : hy,
+                                                       far_z[j] ? lz : hz) >= 0.0f;
+                    if (!inside) continue;
+                }
+                emit((pick4(ref, k) & 0x7FFFFFFFu) - leaf_base);
+                if constexpr (MODE == kRegionAny) { leaves = 0u; inner = 0u; sp = 0; }         // the first candidate ends the walk
+            }
+            if (inner != 0u) {
+                node = pick4(ref, (uint32_t)__builtin_ctz(inner));
+                inner &= inner - 1u;
+                while (inner != 0u) {
+                    push(pick4(ref, (uint32_t)__builtin_ctz(inner)));
+                    inner &= inner - 1u;
+                }
+            } else if (sp != 0) {
+                sp--;
+                node = sp < lds_depth ? s_stack[sp][lane] : my_deep[(sp - lds_depth) * LBVH_WAVE];
+            } else {
+                if constexpr (MODE != kRegionFill) counts[i] = n_found;
+                active = false;
+            }
+        }
+    }
+    if (STATS) add_ray_stats(stats, n_queries, n_steps, n_tris);
+}
+
 // ---- crossing parities of points along fixed directions (lbvh_point_crossings, include/lbvh.h) -------------------------
 // The directions travel by value in the kernel's arguments; a lane reads the one it walks next from there.
 struct crossing_dirs { float d[LBVH_CROSSING_MAX_DIRS][3]; };
@@ -2402,7 +2543,67 @@ static lbvh_status triangle_queries(lbvh_context* ctx, const lbvh_tri_query* d_q
     return LBVH_OK;
 }
 
+// lbvh_region_overlaps: triangle_queries<>'s shape with the region walk (count walk -> the same three scan kernels -> fill walk, counts
+// and tile sums in the same two slices of the ray scratch); lbvh_region_overlaps_any: one launch, the flags are the walk's own
+// output.  Four-wide walk only.
+// (a rejection names the entry point, as the stale-scene message of begin_walk does)
+#define REGION_REQUIRE(cond)                                                                                        \
+    do {                                                                                                            \
+        if (!(cond)) return (lbvh_status)lbvh_set_error(ctx, LBVH_ERR_INVALID_ARG, who, "invalid argument: " #cond); \
+    } while (0)
+template <bool ANY>
+static lbvh_status region_queries(lbvh_context* ctx, const lbvh_region* d_regions, size_t count, uint32_t mode, const lbvh_scene* h_scene,
+                                  uint64_t* d_offsets, uint32_t* d_tris, uint64_t capacity, uint32_t* d_flags, const char* who)
+{
+    if (!ctx) return LBVH_ERR_INVALID_ARG;
+    if (count == 0) return LBVH_OK;
+    REGION_REQUIRE(d_regions != nullptr && h_scene != nullptr && (ANY ? d_flags != nullptr : d_offsets != nullptr));
+    REGION_REQUIRE(mode <= LBVH_REGION_CONTAINED);
+    REGION_REQUIRE(d_tris != nullptr || capacity == 0);
+    REGION_REQUIRE(((uintptr_t)d_regions & 15) == 0 && ((uintptr_t)d_offsets & 7) == 0 && ((uintptr_t)d_tris & 3) == 0 && ((uintptr_t)d_flags & 3) == 0);
+    REGION_REQUIRE(count <= 0xFFFFFFFFull);
+    walk_launch w;
+    const lbvh_status rc = begin_walk(ctx, h_scene, count, who, true, &w);
+    if (rc != LBVH_OK) return rc;
+    const float4* q = (const float4*)d_regions;
+    const uint32_t total = (uint32_t)count, leaf_base = ctx->fast_capacity;
+    if constexpr (ANY) {
+        LBVH_LAUNCH_STATS(ctx, ctx->ray_stats, (region_wide_kernel<kRegionAny, STATS>), dim3(w.waves), dim3(LBVH_WAVE), q, total, mode, w.wn, leaf_base,
+                          d_flags, (const uint64_t*)nullptr, (uint32_t*)nullptr, (uint64_t)0, w.deep, w.lds, w.deep_cap, ctx->fault_dev, ctx->ray_stats);
+    } else {
+        uint32_t* counts = ray_list(ctx, count, 0);
+        uint64_t* tile_sums = (uint64_t*)ray_list(ctx, count, 1);
+        const uint32_t n_tiles = total / kScanTile + 1u;           // the tiles cover total + 1 offsets (sizes: see overlap_queries)
+        LBVH_LAUNCH_STATS(ctx, ctx->ray_stats, (region_wide_kernel<kRegionCount, STATS>), dim3(w.waves), dim3(LBVH_WAVE), q, total, mode, w.wn, leaf_base,
+                          counts, (const uint64_t*)nullptr, (uint32_t*)nullptr, (uint64_t)0, w.deep, w.lds, w.deep_cap, ctx->fault_dev, ctx->ray_stats);
+        if (n_tiles > 1u) {
+            LBVH_LAUNCH(ctx, overlap_tile_sums_kernel, dim3(n_tiles), dim3(256), (const uint32_t*)counts, total, tile_sums);
+            LBVH_LAUNCH(ctx, overlap_scan_sums_kernel, dim3(1), dim3(1024), tile_sums, n_tiles);
+        }
+        LBVH_LAUNCH(ctx, overlap_offsets_kernel, dim3(n_tiles), dim3(256), (const uint32_t*)counts, total,
+                    n_tiles > 1u ? (const uint64_t*)tile_sums : (const uint64_t*)nullptr, d_offsets);
+        if (capacity != 0)
+            LBVH_LAUNCH_STATS(ctx, ctx->ray_stats, (region_wide_kernel<kRegionFill, STATS>), dim3(w.waves), dim3(LBVH_WAVE), q, total, mode, w.wn, leaf_base,
+                              (uint32_t*)nullptr, (const uint64_t*)d_offsets, d_tris, capacity, w.deep, w.lds, w.deep_cap, ctx->fault_dev, ctx->ray_stats);
+    }
+    LBVH_HIP_TRY(ctx, hipGetLastError());
+    return LBVH_OK;
+}
+#undef REGION_REQUIRE
+
 extern "C" {
+
+lbvh_status lbvh_region_overlaps(lbvh_context* ctx, const lbvh_region* d_regions, size_t count, uint32_t mode, const lbvh_scene* h_scene,
+                                 uint64_t* d_offsets, uint32_t* d_tris, uint64_t capacity)
+{
+    return region_queries<false>(ctx, d_regions, count, mode, h_scene, d_offsets, d_tris, capacity, nullptr, "lbvh_region_overlaps");
+}
+
+lbvh_status lbvh_region_overlaps_any(lbvh_context* ctx, const lbvh_region* d_regions, size_t count, uint32_t mode, const lbvh_scene* h_scene,
+                                     uint32_t* d_flags)
+{
+    return region_queries<true>(ctx, d_regions, count, mode, h_scene, nullptr, nullptr, 0, d_flags, "lbvh_region_overlaps_any");
+}
 
 lbvh_status lbvh_triangle_intersections(lbvh_context* ctx, const lbvh_tri_query* d_queries, size_t count, const lbvh_scene* h_scene,
                                         uint64_t* d_offsets, uint32_t* d_tris, uint64_t capacity)

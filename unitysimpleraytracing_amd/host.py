@@ -28,6 +28,68 @@ def inside(parity, n_dirs):
     return ones > n_dirs / 2
 
 
+# ---- plane builders for lbvh_region_overlaps: conveniences, computed in float64 and rounded once to fp32.  The contract is on
+# the planes (include/lbvh.h), not on these builders: a plane {nx, ny, nz, d} keeps n . x + d >= 0, normals point inward. ------------
+
+def _regions(planes):
+    out = np.zeros(planes.shape[:-2], dtype=L.REGION)
+    out["plane"] = planes.astype(np.float32)
+    return out if out.ndim else out.reshape(1)
+
+
+def aabb_planes(lo, hi):
+    """The box [lo, hi] (arrays of shape (..., 3)) as layouts.REGION records: unit axis normals, d = -lo for +axis, d = +hi for -axis
+    (exact in fp32 for fp32 bounds: in TOUCHING mode the region is lbvh_box_overlaps' box)."""
+    lo, hi = np.broadcast_arrays(np.asarray(lo, dtype=np.float64), np.asarray(hi, dtype=np.float64))
+    planes = np.zeros(lo.shape[:-1] + (6, 4))
+    for k in range(3):
+        planes[..., 2 * k, k], planes[..., 2 * k, 3] = 1.0, -lo[..., k]
+        planes[..., 2 * k + 1, k], planes[..., 2 * k + 1, 3] = -1.0, hi[..., k]
+    return _regions(planes)
+
+
+def obb_planes(centre, axes3x3, half_extents):
+    """The oriented box { centre + sum_k s_k * axes3x3[k] : |s_k| <= half_extents[k] } (rows of axes3x3: the box's axes; they are
+    normalised here and assumed orthogonal) as layouts.REGION records: planes {+-axis_k, half_extents[k] -+ axis_k . centre}.
+    Shapes (..., 3), (..., 3, 3), (..., 3)."""
+    c, ax, he = np.asarray(centre, dtype=np.float64), np.asarray(axes3x3, dtype=np.float64), np.asarray(half_extents, dtype=np.float64)
+    ax = ax / np.linalg.norm(ax, axis=-1, keepdims=True)
+    along = (ax * c[..., None, :]).sum(axis=-1)                       # axis_k . centre
+    planes = np.zeros(np.broadcast_shapes(c.shape[:-1], ax.shape[:-2], he.shape[:-1]) + (6, 4))
+    for k in range(3):
+        planes[..., 2 * k, :3], planes[..., 2 * k, 3] = ax[..., k, :], he[..., k] - along[..., k]
+        planes[..., 2 * k + 1, :3], planes[..., 2 * k + 1, 3] = -ax[..., k, :], he[..., k] + along[..., k]
+    return _regions(planes)
+
+
+def frustum_planes(camera, far, rect=None):
+    """The view frustum of `camera` (the dict of scenes.camera or an N.Camera) as one layouts.REGION record, in the convention of
+    lbvh_trace_primary's ray generation: the eye at camera_to_world * (0, 0, 0, 1), looking along the camera's -z; the image plane at
+    depth near_plane is 2 * near_plane * camera_fov high (camera_fov is the tangent of half the vertical angle) and screen_width /
+    screen_height times as wide.  Planes: left, right, bottom, top (through the eye), near (depth >= near_plane), far (depth <= far);
+    depth is measured along the view axis.  rect = (x0, y0, x1, y1) in pixels narrows the four side planes to that part of the
+    image (a tile or cluster frustum)."""
+    if isinstance(camera, N.Camera):
+        camera = {k: getattr(camera, k) for k in ("screen_width", "screen_height", "camera_fov", "near_plane")} | \
+            {"camera_to_world": np.array(camera.camera_to_world[:], dtype=np.float32)}
+    sw, sh = float(camera["screen_width"]), float(camera["screen_height"])
+    t = float(np.float32(camera["camera_fov"]))
+    near = float(np.float32(camera["near_plane"]))
+    m = np.asarray(camera["camera_to_world"], dtype=np.float32).astype(np.float64).reshape(4, 4)
+    x0, y0, x1, y1 = rect if rect is not None else (0.0, 0.0, sw, sh)
+    ta = t * sw / sh
+    # the slopes x / depth and y / depth of the rect's edges: pixel x maps to (-1 + 2 x / sw) * ta, pixel y to (-1 + 2 y / sh) * t
+    xl, xr = (-1.0 + 2.0 * x0 / sw) * ta, (-1.0 + 2.0 * x1 / sw) * ta
+    yb, yt = (-1.0 + 2.0 * y0 / sh) * t, (-1.0 + 2.0 * y1 / sh) * t
+    cam = np.array([[1.0, 0.0, xl, 0.0],         # x_c - xl * depth >= 0, depth = -z_c
+                    [-1.0, 0.0, -xr, 0.0],       # xr * depth - x_c >= 0
+                    [0.0, 1.0, yb, 0.0],
+                    [0.0, -1.0, -yt, 0.0],
+                    [0.0, 0.0, -1.0, -near],     # depth - near >= 0
+                    [0.0, 0.0, 1.0, float(far)]])  # far - depth >= 0
+    return _regions(cam @ np.linalg.inv(m))      # a plane is a row vector: (n, d) . x_c = (n, d) . M^-1 . x_w
+
+
 class Context:
     """One GPU + one HIP stream.  Stands in for the implicit Unity graphics device and the
     IShaderContainer kernel registry (Assets/_Scripts/ShaderContainer.cs:6-40)."""
@@ -512,6 +574,31 @@ class RaytracingMeshDrawer:
         Returns (offsets, tris): host arrays, uint64[queries.size + 1] and uint32[total].  device_sort=True issues
         sort_index_segments before the download: every segment ascending."""
         return self._csr_lists(self.triangle_intersections, queries, min_capacity, device_sort)
+
+    def region_overlaps(self, regions, mode, offsets, tris=None):
+        """Every triangle in each convex region of the DataBuffer `regions` (layouts.REGION: six planes {nx, ny, nz, d}, each keeping
+        n . x + d >= 0; see frustum_planes, obb_planes, aabb_planes), as a CSR list on the caller's buffers exactly as box_overlaps
+        writes it.  mode = layouts.REGION_TOUCHING: the triangles whose own box is not wholly outside any plane (the conservative
+        frustum test); layouts.REGION_CONTAINED: those whose own box is wholly inside every plane.  tris=None counts only.
+        Asynchronous."""
+        if mode not in (L.REGION_TOUCHING, L.REGION_CONTAINED):
+            raise ValueError("mode must be layouts.REGION_TOUCHING or layouts.REGION_CONTAINED")
+        self._overlaps(lambda h, q, n, s, o, t, cap: N.lib.lbvh_region_overlaps(h, q, n, mode, s, o, t, cap), regions, L.REGION, offsets, tris)
+
+    def region_overlaps_any(self, regions, mode, flags):
+        """1 into the uint32 DataBuffer `flags` for each region of `regions` that has a candidate in `mode`, else 0."""
+        if regions.dtype != L.REGION or flags.dtype != np.uint32 or flags.size < regions.size:
+            raise ValueError("regions must be a DataBuffer of layouts.REGION and flags one of uint32 with at least as many entries")
+        if mode not in (L.REGION_TOUCHING, L.REGION_CONTAINED):
+            raise ValueError("mode must be layouts.REGION_TOUCHING or layouts.REGION_CONTAINED")
+        s = self.container.scene()
+        N.check(self.ctx.handle, N.lib.lbvh_region_overlaps_any(self.ctx.handle, regions.device, regions.size, mode, C.byref(s), flags.device))
+
+    def in_regions(self, regions, mode=L.REGION_TOUCHING, min_capacity=1, device_sort=False):
+        """Convenience, as overlaps(): count -> one 8-byte download -> allocate -> fill, for a DataBuffer of layouts.REGION.
+        Returns (offsets, tris): host arrays, uint64[regions.size + 1] and uint32[total].  device_sort=True issues
+        sort_index_segments before the download: every segment ascending."""
+        return self._csr_lists(lambda q, o, t=None: self.region_overlaps(q, mode, o, t), regions, min_capacity, device_sort)
 
     def count_hits(self, rays, counts):
         """The number of candidates of each ray of `rays` (layouts.RAY) in (t_min, t_max) into the uint32 DataBuffer `counts`: every

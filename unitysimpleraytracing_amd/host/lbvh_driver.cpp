@@ -51,6 +51,14 @@
 //                                                SortIndexSegments, TriangleIntersectsAny; prints the total, how many segments are
 //                                                non-empty, how many flags are set, the sum of (position + 1) * triangle index over
 //                                                the device-sorted list (mod 2^64) and the first segments
+//     lbvh_driver regions <n_regions> [seed]     the 4 096 triangles of cfg1 and n_regions sheared boxes (SplitMix64, seed default 6):
+//                                                the centre uniform in the mesh's box, then per axis k a normal — the axis' unit
+//                                                vector with its two other components uniform in [-0.5, 0.5] — and a half width
+//                                                uniform in [1, 12]: the planes {n, h - n . c} and {-n, h + n . c}.  RegionOverlaps
+//                                                (count only, one 8-byte read, fill) in both modes, SortIndexSegments,
+//                                                RegionOverlapsAny; prints per mode the total, how many segments are non-empty, how
+//                                                many flags are set and the sum of (position + 1) * triangle index over the
+//                                                device-sorted list (mod 2^64), and the first TOUCHING segments
 #include <chrono>
 #include <cmath>
 #include <cstdio>
@@ -633,6 +641,75 @@ static int tris_main(int argc, char** argv)
     return 0;
 }
 
+static int regions_main(int argc, char** argv)
+{
+    const size_t count = argc > 2 ? (size_t)strtoull(argv[2], nullptr, 10) : 65536;
+    uint64_t seed = argc > 3 ? strtoull(argv[3], nullptr, 10) : 6;
+    const std::vector<lbvh_triangle> mesh = random_mesh(4096);
+    float lo[3], hi[3];
+    mesh_box(mesh, lo, hi);
+    lbvh::Context ctx(0);
+    lbvh::RaytracingMeshDrawer drawer(ctx, mesh);
+    drawer.Awake();
+    lbvh::DataBuffer<lbvh_region> regions(ctx, count);
+    for (size_t i = 0; i < count; i++) {
+        lbvh_region& r = regions.LocalBuffer()[i];
+        float c[3];
+        for (int k = 0; k < 3; k++) c[k] = uniform(seed, lo[k], hi[k]);
+        for (int k = 0; k < 3; k++) {
+            float n[3] = {0.0f, 0.0f, 0.0f};
+            n[k] = 1.0f;
+            for (int j = 0; j < 3; j++)
+                if (j != k) n[j] = uniform(seed, -0.5f, 0.5f);
+            const float h = uniform(seed, 1.0f, 12.0f);
+            const float p0 = n[0] * c[0], p1 = n[1] * c[1], p2 = n[2] * c[2];         // every operation rounded on its own, as the mirror has it
+            const float s01 = p0 + p1;
+            const float s = s01 + p2;
+            for (int j = 0; j < 3; j++) { r.plane[2 * k][j] = n[j]; r.plane[2 * k + 1][j] = -n[j]; }
+            r.plane[2 * k][3] = h - s;
+            r.plane[2 * k + 1][3] = h + s;
+        }
+    }
+    regions.Sync();
+    lbvh::DataBuffer<uint64_t> offsets(ctx, count + 1);
+    lbvh::DataBuffer<uint32_t> flags(ctx, count);
+    std::printf("{\"triangles\": %zu, \"regions\": %zu", mesh.size(), count);
+    for (uint32_t mode : {LBVH_REGION_CONTAINED, LBVH_REGION_TOUCHING}) {
+        drawer.RegionOverlaps(regions, mode, offsets);
+        offsets.GetData();
+        const unsigned long long total = offsets.LocalBuffer()[count];
+        lbvh::DataBuffer<uint32_t> tris(ctx, total ? (size_t)total : 1);
+        drawer.RegionOverlaps(regions, mode, offsets, &tris);
+        drawer.SortIndexSegments(offsets, tris, count);
+        drawer.RegionOverlapsAny(regions, mode, flags);
+        offsets.GetData();
+        tris.GetData();
+        flags.GetData();
+        size_t non_empty = 0, flagged = 0;
+        unsigned long long weighted = 0;
+        for (size_t i = 0; i < count; i++) {
+            non_empty += offsets.LocalBuffer()[i + 1] > offsets.LocalBuffer()[i];
+            flagged += flags.LocalBuffer()[i];
+        }
+        for (size_t i = 0; i < (size_t)total; i++) weighted += (unsigned long long)(i + 1) * tris.LocalBuffer()[i];
+        std::printf(", \"%s\": {\"total\": %llu, \"non_empty\": %zu, \"flagged\": %zu, \"weighted_index_sum\": %llu}",
+                    mode == LBVH_REGION_TOUCHING ? "touching" : "contained", total, non_empty, flagged, weighted);
+        if (mode != LBVH_REGION_TOUCHING) continue;
+        std::printf(", \"segments\": [");
+        size_t shown = 0;
+        for (size_t i = 0; i < count && shown < 3; i++) {
+            const uint64_t first = offsets.LocalBuffer()[i], last = offsets.LocalBuffer()[i + 1];
+            if (first == last) continue;
+            std::printf("%s[%zu", shown++ ? ", " : "", i);
+            for (uint64_t j = first; j < last; j++) std::printf(", %u", tris.LocalBuffer()[j]);
+            std::printf("]");
+        }
+        std::printf("]");
+    }
+    std::printf("}\n");
+    return 0;
+}
+
 static int crossings_main(int argc, char** argv)
 {
     const size_t count = argc > 3 ? (size_t)strtoull(argv[3], nullptr, 10) : 65536;
@@ -766,7 +843,7 @@ int main(int argc, char** argv)
 {
     static const struct { const char* name; int (*run)(int, char**); } commands[] = {
         {"crossings", crossings_main}, {"points", points_main}, {"knn", knn_main},   {"khits", khits_main}, {"gather", gather_main}, {"sortedhits", sortedhits_main},
-        {"sweep", sweep_main},         {"overlaps", overlaps_main}, {"tris", tris_main}, {"rays", rays_main}, {"sort", sort_main},   {"multi", multi_main}};
+        {"sweep", sweep_main},         {"overlaps", overlaps_main}, {"tris", tris_main}, {"regions", regions_main}, {"rays", rays_main}, {"sort", sort_main},   {"multi", multi_main}};
     try {
         for (const auto& c : commands)
             if (argc > 1 && std::strcmp(argv[1], c.name) == 0) return c.run(argc, argv);

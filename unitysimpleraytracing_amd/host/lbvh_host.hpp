@@ -143,6 +143,60 @@ private:
 
 inline uint32_t CapacityFor(uint32_t n, uint32_t tile = 1024) { return (n + tile - 1) / tile * tile; }
 
+// ---- plane builders for lbvh_region_overlaps: conveniences, computed in double and rounded once to float.  The contract is on the
+// planes (include/lbvh.h), not on these builders: a plane {nx, ny, nz, d} keeps n . x + d >= 0, normals point inward. ----------------
+inline void SetPlane(lbvh_region& r, int j, double nx, double ny, double nz, double d)
+{
+    r.plane[j][0] = (float)nx; r.plane[j][1] = (float)ny; r.plane[j][2] = (float)nz; r.plane[j][3] = (float)d;
+}
+
+// the box [lo, hi]: unit axis normals, d = -lo / +hi (exact for float bounds: in TOUCHING mode the region is lbvh_box_overlaps' box)
+inline lbvh_region AabbPlanes(const float lo[3], const float hi[3])
+{
+    lbvh_region r;
+    for (int k = 0; k < 3; k++) {
+        SetPlane(r, 2 * k, k == 0, k == 1, k == 2, -(double)lo[k]);
+        SetPlane(r, 2 * k + 1, -(double)(k == 0), -(double)(k == 1), -(double)(k == 2), (double)hi[k]);
+    }
+    return r;
+}
+
+// the oriented box { centre + sum_k s_k * axes[k] : |s_k| <= half_extents[k] }; the rows of `axes` are normalised here and
+// assumed orthogonal
+inline lbvh_region ObbPlanes(const float centre[3], const float axes[3][3], const float half_extents[3])
+{
+    lbvh_region r;
+    for (int k = 0; k < 3; k++) {
+        const double len = std::sqrt((double)axes[k][0] * axes[k][0] + (double)axes[k][1] * axes[k][1] + (double)axes[k][2] * axes[k][2]);
+        const double n[3] = {axes[k][0] / len, axes[k][1] / len, axes[k][2] / len};
+        const double along = n[0] * centre[0] + n[1] * centre[1] + n[2] * centre[2];
+        SetPlane(r, 2 * k, n[0], n[1], n[2], half_extents[k] - along);
+        SetPlane(r, 2 * k + 1, -n[0], -n[1], -n[2], half_extents[k] + along);
+    }
+    return r;
+}
+
+// The view frustum of `cam` in the convention of lbvh_trace_primary's ray generation: the eye at camera_to_world * (0, 0, 0, 1),
+// looking along the camera's -z, the image plane at depth near_plane 2 * near_plane * camera_fov high (camera_fov: the tangent of
+// half the vertical angle) and screen_width / screen_height times as wide.  Planes: left, right, bottom, top (through the eye), near
+// (depth >= near_plane), far (depth <= far); depth is measured along the view axis.  camera_to_world is taken as a rigid motion
+// times a uniform scale (what a camera has): its inverse's rotation part is its transpose over the squared scale.
+inline lbvh_region FrustumPlanes(const lbvh_camera& cam, float far_depth)
+{
+    const double t = cam.camera_fov, ta = t * (double)cam.screen_width / (double)cam.screen_height;
+    const double c[6][4] = {{1, 0, -ta, 0}, {-1, 0, -ta, 0}, {0, 1, -t, 0}, {0, -1, -t, 0}, {0, 0, -1, -(double)cam.near_plane}, {0, 0, 1, far_depth}};
+    const float* m = cam.camera_to_world;                     // row-major 4 x 4
+    const double s2 = (double)m[0] * m[0] + (double)m[4] * m[4] + (double)m[8] * m[8];
+    lbvh_region r;
+    for (int j = 0; j < 6; j++) {
+        // x_c = R^T (x_w - T) / s2, so n_w = R n_c / s2 and d_w = d_c - n_w . T
+        double n[3];
+        for (int k = 0; k < 3; k++) n[k] = (m[4 * k] * c[j][0] + m[4 * k + 1] * c[j][1] + m[4 * k + 2] * c[j][2]) / s2;
+        SetPlane(r, j, n[0], n[1], n[2], c[j][3] - (n[0] * m[3] + n[1] * m[7] + n[2] * m[11]));
+    }
+    return r;
+}
+
 // Assets/_Scripts/MeshBufferContainer.cs
 class MeshBufferContainer {
 public:
@@ -397,6 +451,25 @@ public:
         const lbvh_scene s = container_->Scene();
         check(ctx_.get(), lbvh_triangle_intersects_any(ctx_.get(), (const lbvh_tri_query*)queries.DeviceBuffer(), queries.Size(), &s,
                                                        (uint32_t*)flags.DeviceBuffer()));
+    }
+    // WHICH triangles lie in each convex region of six planes (a frustum, an oriented box, a selection window), as the same CSR
+    // list, or one flag per region (lbvh_region_overlaps / lbvh_region_overlaps_any; asynchronous).  mode: LBVH_REGION_TOUCHING —
+    // the triangle's own box is not wholly outside any plane — or LBVH_REGION_CONTAINED — it is wholly inside every plane.
+    // FrustumPlanes / ObbPlanes / AabbPlanes below make the planes.
+    void RegionOverlaps(const DataBuffer<lbvh_region>& regions, uint32_t mode, DataBuffer<uint64_t>& offsets, DataBuffer<uint32_t>* tris = nullptr)
+    {
+        if (offsets.Size() < regions.Size() + 1) throw Error(LBVH_ERR_INVALID_ARG, "RegionOverlaps: offsets needs one entry more than regions");
+        const lbvh_scene s = container_->Scene();
+        check(ctx_.get(), lbvh_region_overlaps(ctx_.get(), (const lbvh_region*)regions.DeviceBuffer(), regions.Size(), mode, &s,
+                                               (uint64_t*)offsets.DeviceBuffer(), tris ? (uint32_t*)tris->DeviceBuffer() : nullptr,
+                                               tris ? (uint64_t)tris->Size() : 0));
+    }
+    void RegionOverlapsAny(const DataBuffer<lbvh_region>& regions, uint32_t mode, DataBuffer<uint32_t>& flags)
+    {
+        if (flags.Size() < regions.Size()) throw Error(LBVH_ERR_INVALID_ARG, "RegionOverlapsAny: fewer flags than regions");
+        const lbvh_scene s = container_->Scene();
+        check(ctx_.get(), lbvh_region_overlaps_any(ctx_.get(), (const lbvh_region*)regions.DeviceBuffer(), regions.Size(), mode, &s,
+                                                   (uint32_t*)flags.DeviceBuffer()));
     }
     // how many triangles each ray crosses in (t_min, t_max), and crossing parities of points along fixed directions — bit j of a
     // point's word: the count of the ray from it along dirs[j] (x, y, z; 1 .. 32 of them), AND 1 (lbvh_count_hits /

@@ -44,6 +44,10 @@ assert POINT_QUERY.itemsize == 16 and CLOSEST_POINT.itemsize == 16
 # never a candidate (NULL below, LBVH_NULL: none)
 TRI_QUERY = np.dtype([("a", "<f4", 3), ("skip", "<u4"), ("b", "<f4", 3), ("_pad0", "<u4"), ("c", "<f4", 3), ("_pad1", "<u4")])
 assert TRI_QUERY.itemsize == 48
+# lbvh_region_overlaps / lbvh_region_overlaps_any: six planes {nx, ny, nz, d}, each keeping n . x + d >= 0; the two modes
+REGION = np.dtype([("plane", "<f4", (6, 4))])
+assert REGION.itemsize == 96
+REGION_TOUCHING, REGION_CONTAINED = 0, 1
 
 assert AABB.itemsize == 32          # Assets/_Scripts/MeshBufferContainer.cs:103
 assert TRIANGLE.itemsize == 128     # Assets/_Scripts/MeshBufferContainer.cs:98
