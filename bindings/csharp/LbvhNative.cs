@@ -154,6 +154,9 @@ public static class LbvhNative
     [DllImport(Lib)] public static extern int lbvh_region_overlaps(IntPtr ctx, IntPtr dRegions, UIntPtr count, uint mode, ref Scene scene, IntPtr dOffsets,
         IntPtr dTris, ulong capacity);
     [DllImport(Lib)] public static extern int lbvh_region_overlaps_any(IntPtr ctx, IntPtr dRegions, UIntPtr count, uint mode, ref Scene scene, IntPtr dFlags);
+    // few large regions (at most 65 536), each spread over the device: the same lists as lbvh_region_overlaps
+    [DllImport(Lib)] public static extern int lbvh_region_overlaps_large(IntPtr ctx, IntPtr dRegions, UIntPtr count, uint mode, ref Scene scene, IntPtr dOffsets,
+        IntPtr dTris, ulong capacity);
     [DllImport(Lib)] public static extern int lbvh_k_closest_points(IntPtr ctx, IntPtr dQueries, UIntPtr count, uint k, ref Scene scene, IntPtr dOut,
         IntPtr dFound);
     [DllImport(Lib)] public static extern int lbvh_trace_k_closest(IntPtr ctx, IntPtr dRays, UIntPtr count, uint k, ref Scene scene, IntPtr dHits,

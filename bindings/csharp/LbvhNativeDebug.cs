@@ -18,6 +18,9 @@ public static class LbvhNativeDebug
     [DllImport(Lib)] public static extern int lbvh_debug_ray_waves(IntPtr ctx, uint maxWaves);
     [DllImport(Lib)] public static extern int lbvh_debug_ray_walker(IntPtr ctx, uint walker);
     [DllImport(Lib)] public static extern int lbvh_debug_ray_stack_limit(IntPtr ctx, uint deepEntries);
+    // lbvh_region_overlaps_large: tasks per region (4 .. 65536, 0: the host's choice), and the rule itself (no GPU involved)
+    [DllImport(Lib)] public static extern int lbvh_debug_region_task_cap(IntPtr ctx, uint cap);
+    [DllImport(Lib)] public static extern uint lbvh_debug_region_task_cap_of(uint cap, UIntPtr count);
     // measurement: the four-wide per-ray walkers add {rays, node lines fetched, triangles tested} (3 x ulong) while set
     [DllImport(Lib)] public static extern int lbvh_ray_stats_target(IntPtr ctx, IntPtr dStats);
     // measurement helper: shader clock held under a vector-ALU-bound load, MHz

@@ -6,7 +6,9 @@
 // form is the CSR list of OverlapQueries: offsets (ulong, count + 1 of them) and the ORIGINAL triangle indices (uint), in no particular
 // order inside a region's segment; SegmentSort orders them on the device.  Twin of host.py / lbvh_host.hpp
 // RaytracingMeshDrawer.region_overlaps / RegionOverlaps.  No reference counterpart.  The scene is the container's; it must have been
-// built with the derived traversal scene (the drawer's Awake does that).  One region per lane: the call is for many regions.
+// built with the derived traversal scene (the drawer's Awake does that).  One region per lane: RegionOverlaps is for many regions;
+// RegionOverlapsLarge (lbvh_region_overlaps_large) spreads each of a few large regions — one camera frustum, a cascade, a marquee
+// selection — over the device and gives the same lists.
 // SOURCE ONLY (no C# toolchain in the build image).
 using System;
 
@@ -15,6 +17,7 @@ public sealed class RegionQueries
     public const int RegionStride = 96;
     public const uint Touching = 0u;
     public const uint Contained = 1u;
+    public const int LargeMaxCount = 65536;
 
     readonly MeshBufferContainer _container;
 
@@ -32,6 +35,21 @@ public sealed class RegionQueries
             throw new ArgumentException("RegionQueries: the buffers live on different contexts");
         LbvhNative.Scene scene = _container.NativeScene();
         LbvhNative.Check(regions.Context, LbvhNative.lbvh_region_overlaps(regions.Context, regions.Pointer, (UIntPtr)(ulong)count, mode, ref scene,
+            offsets.Pointer, tris == null ? IntPtr.Zero : tris.Pointer, tris == null ? 0UL : (ulong)tris.count));
+    }
+
+    /// RegionOverlaps for few large regions (count <= LargeMaxCount): the same offsets and, per segment, the same set of indices, in
+    /// another order.
+    public void RegionOverlapsLarge(NativeBuffer regions, uint mode, NativeBuffer offsets, NativeBuffer tris, int count)
+    {
+        Check(regions, mode, count);
+        if (count > LargeMaxCount) throw new ArgumentException("RegionQueries: RegionOverlapsLarge takes at most 65536 regions");
+        if (offsets.stride != 8 || count + 1 > offsets.count || (tris != null && tris.stride != 4))
+            throw new ArgumentException("RegionQueries: offsets are ulong with count + 1 entries, tris are uint");
+        if (offsets.Context != regions.Context || (tris != null && tris.Context != regions.Context))
+            throw new ArgumentException("RegionQueries: the buffers live on different contexts");
+        LbvhNative.Scene scene = _container.NativeScene();
+        LbvhNative.Check(regions.Context, LbvhNative.lbvh_region_overlaps_large(regions.Context, regions.Pointer, (UIntPtr)(ulong)count, mode, ref scene,
             offsets.Pointer, tris == null ? IntPtr.Zero : tris.Pointer, tris == null ? 0UL : (ulong)tris.count));
     }
 

@@ -1054,11 +1054,51 @@ typedef struct lbvh_region { float plane[LBVH_REGION_PLANES][4]; } lbvh_region; 
  * lbvh_ray_stats_target apply as to the overlap queries (rays counts every region, triangle_tests the leaf slots that passed the
  * TOUCHING test; the full form reports twice the count-only form's).
  * One region per lane: a single camera frustum over the whole mesh keeps one lane busy while 63 idle.  The call is for MANY
- * regions (clusters, lights, oriented boxes, portals), not for one huge one. */
+ * regions (clusters, lights, oriented boxes, portals), not for one huge one: that is lbvh_region_overlaps_large below. */
 lbvh_status lbvh_region_overlaps(lbvh_context* ctx, const lbvh_region* d_regions, size_t count, uint32_t mode, const lbvh_scene* h_scene,
                                  uint64_t* d_offsets, uint32_t* d_tris, uint64_t capacity);
 lbvh_status lbvh_region_overlaps_any(lbvh_context* ctx, const lbvh_region* d_regions, size_t count, uint32_t mode, const lbvh_scene* h_scene,
                                      uint32_t* d_flags);
+
+/* lbvh_region_overlaps for FEW, LARGE regions — one camera or light frustum, a cascade, a marquee selection: every region is
+ * spread over the device instead of over one lane.  The same lbvh_region, the same two modes, the same candidate predicate
+ * operation by operation, the same CSR contract word for word: d_offsets (count + 1 words of 64 bits) is always written in full
+ * and EQUALS lbvh_region_overlaps' d_offsets on the same inputs; segment k holds the same SET of ORIGINAL triangle indices, each
+ * exactly once — after lbvh_sort_index_segments d_tris equals that call's sorted d_tris word for word; no word at index >=
+ * capacity is ever written and every segment with d_offsets[k+1] <= capacity is complete; capacity == 0 is the count-only form
+ * (d_tris may be NULL).  THE ORDER INSIDE A SEGMENT IS NOT PART OF THE CONTRACT (it differs from lbvh_region_overlaps'), but two
+ * calls with the same inputs on the same scene write the same bytes: no atomic is on the output path.
+ *   How: a region is cut into up to task_cap TASKS.  One workgroup per region opens the four-wide tree breadth first from the
+ *   root with the slot test of lbvh_region_overlaps (an inner slot that passes all six P_j >= 0 replaces its parent; a leaf slot
+ *   stays only if it is a candidate of the mode) until one more round could exceed task_cap entries or only leaves are left.
+ *   By the monotonicity argument above, a region's candidates are the union of the candidates below the subtrees of ANY such
+ *   frontier, and no two of them share a triangle.  Every task is then walked by one lane exactly as lbvh_region_overlaps
+ *   walks a region, a leaf task is a candidate already; the per-task counts are scanned on the device into 64-bit task offsets,
+ *   d_offsets picks every region's first, and the fill walk writes each task's candidates at the task's own offset.  No kernel
+ *   waits for another workgroup.  task_cap is chosen by the host: the largest power of two not above min(65536, 2^22 / count),
+ *   so count * task_cap <= 2^22 task slots; count <= LBVH_REGION_LARGE_MAX_COUNT keeps it at 64 or more.
+ *   When to use which (MI355X, 1 M triangles, TOUCHING, tools/region_large_bench.py -> profiles/region_large/, table in DESIGN.md
+ *   §30): use this call when there are at most 65 536 regions and a region holds hundreds of triangles or more.  One frustum
+ *   over 50 % of the mesh: 0.38 ms count only and 0.68 ms full against lbvh_region_overlaps' 316 ms and 717 ms; one region of
+ *   829 triangles: 0.044 ms against 0.49 ms; 4 096 regions of 47 000 triangles: 4.2 ms against 55 ms.  The gap closes as the
+ *   regions get many and small: 65 536 regions of about 600 triangles take 2.18 ms against 2.68 ms count only (1.2x) and 4.00 ms
+ *   against 6.13 ms full (1.5x), the smallest gain measured; it lost in no cell measured.  Below that size — regions of a few
+ *   triangles, where the 64 task slots per region are mostly empty — and above 65 536 regions lbvh_region_overlaps is the call
+ *   (2^20 regions of about 100 triangles: 1.99 ms there).
+ * Everything else is lbvh_region_overlaps': the derived traversal scene is needed (a stale one is LBVH_ERR_INVALID_ARG),
+ * asynchronous on the context's stream with no host wait, the path tracer's live-path list is dropped, count == 0 is a no-op that
+ * touches no buffer.  It keeps count * task_cap * 16 bytes (up to 64 MB) of context scratch of its own beside the ray scratch;
+ * a failed allocation is LBVH_ERR_OUT_OF_MEMORY and leaves the context usable.  Rejected (LBVH_ERR_INVALID_ARG, the message
+ * names this entry point): NULL ctx / d_regions / h_scene / d_offsets, mode > 1, d_regions not 16-byte aligned, d_offsets not
+ * 8-byte aligned, d_tris not 4-byte aligned, d_tris == NULL with capacity > 0, count > LBVH_REGION_LARGE_MAX_COUNT.
+ * lbvh_debug_ray_waves, lbvh_debug_ray_stack_split and lbvh_debug_ray_stack_limit apply to the task walks;
+ * lbvh_ray_stats_target: rays counts the tasks that are not empty, node_fetches the node lines of the task walks PLUS the nodes
+ * the expansion opened, triangle_tests the leaf slots that passed the TOUCHING test in a task walk plus the leaf tasks; the
+ * full form adds the walks' share twice.  There is no _any twin: lbvh_region_overlaps_any stops at a region's first candidate,
+ * so a large region is its fast case already. */
+#define LBVH_REGION_LARGE_MAX_COUNT 65536
+lbvh_status lbvh_region_overlaps_large(lbvh_context* ctx, const lbvh_region* d_regions, size_t count, uint32_t mode, const lbvh_scene* h_scene,
+                                       uint64_t* d_offsets, uint32_t* d_tris, uint64_t capacity);
 
 /* Camera rays into path states (origin/dir as Raytracing.compute:108-126, throughput 1, radiance 0, alive). */
 lbvh_status lbvh_path_begin(lbvh_context* ctx, const lbvh_camera* h_camera, lbvh_path_state* d_states);
@@ -1084,7 +1124,7 @@ lbvh_status lbvh_path_scatter(lbvh_context* ctx, const lbvh_scene* h_scene, cons
  * lbvh_path_bounce on the same d_states / d_hits listed as live (a list kept by the context).  Every library call that writes
  * into those buffers drops the list (lbvh_path_begin, lbvh_trace_rays, a primary trace into any part of d_hits,
  * lbvh_buffer_upload / _fill_u32 / _free), and so does lbvh_trace_forget — and so do lbvh_trace_closest,
- * lbvh_trace_occluded, lbvh_closest_point_query, lbvh_within_distance, lbvh_count_hits, lbvh_point_crossings, lbvh_box_overlaps, lbvh_gather_within_distance, lbvh_k_closest_points, lbvh_trace_k_closest, lbvh_gather_hits, lbvh_sphere_cast, lbvh_sphere_cast_any, lbvh_triangle_intersections, lbvh_triangle_intersects_any, lbvh_region_overlaps and lbvh_region_overlaps_any, whatever buffers they are given, since they use the same ray scratch; then every state is scanned again.  The one exception among the query calls:
+ * lbvh_trace_occluded, lbvh_closest_point_query, lbvh_within_distance, lbvh_count_hits, lbvh_point_crossings, lbvh_box_overlaps, lbvh_gather_within_distance, lbvh_k_closest_points, lbvh_trace_k_closest, lbvh_gather_hits, lbvh_sphere_cast, lbvh_sphere_cast_any, lbvh_triangle_intersections, lbvh_triangle_intersects_any, lbvh_region_overlaps, lbvh_region_overlaps_any and lbvh_region_overlaps_large, whatever buffers they are given, since they use the same ray scratch; then every state is scanned again.  The one exception among the query calls:
  * lbvh_sort_hit_segments and lbvh_sort_index_segments take no context scratch and keep the live-path list (they drop it only when the
  * buffer they sort is d_hits itself).  What the library
  * cannot see is a write of the CALLER's own (a kernel or hipMemcpy that revives or ends paths, Russian roulette): between two

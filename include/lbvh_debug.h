@@ -92,6 +92,16 @@ lbvh_status lbvh_debug_ray_stack_limit(lbvh_context* ctx, uint32_t deep_entries)
  * leaves them alone.  lbvh_debug_ray_stack_split and lbvh_debug_ray_stack_limit apply to them as to the four-wide ray walk. */
 lbvh_status lbvh_debug_ray_walker(lbvh_context* ctx, uint32_t walker);
 
+/* Test hook: the tasks per region of lbvh_region_overlaps_large.  cap = 4 .. 65536, not necessarily a power of two, replaces the
+ * host's choice (the largest power of two not above min(65536, 2^22 / count)); 0 restores it; anything else is
+ * LBVH_ERR_INVALID_ARG.  The slot budget still holds: a call with `count` regions uses min(cap, 2^22 / count) tasks per region,
+ * so the scratch stays at 64 MB whatever a test asks for.  Results do not depend on it beyond the order inside a segment; tests
+ * lower it so that a small mesh runs several expansion rounds that stop on the cap, and raise it so that every task is a leaf.
+ * lbvh_debug_region_task_cap_of is the rule itself, a pure function without a GPU: the tasks per region a call with `count`
+ * regions (1 .. LBVH_REGION_LARGE_MAX_COUNT; 0 for any other count) uses while the hook holds `cap` (0: the host's choice). */
+lbvh_status lbvh_debug_region_task_cap(lbvh_context* ctx, uint32_t cap);
+uint32_t lbvh_debug_region_task_cap_of(uint32_t cap, size_t count);
+
 /* Profiling aid: one LBVH_TRACE_FAST frame that also records, per 8x8-pixel tile (row-major,
  * ceil(W/8) x ceil(H/8) entries), the number of node fetches its packet needed. */
 lbvh_status lbvh_trace_tile_costs(lbvh_context* ctx, const lbvh_camera* h_camera, const lbvh_scene* h_scene,

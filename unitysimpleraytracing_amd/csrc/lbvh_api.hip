@@ -229,6 +229,7 @@ lbvh_status lbvh_destroy(lbvh_context* ctx)
     if (ctx->ray_scratch) (void)hipFree(ctx->ray_scratch);
     if (ctx->tie_list) (void)hipFree(ctx->tie_list);
     if (ctx->wide_nodes) (void)hipFree(ctx->wide_nodes);
+    if (ctx->region_tasks) (void)hipFree(ctx->region_tasks);
     if (ctx->trace_frame_costs) (void)hipFree(ctx->trace_frame_costs);
     if (ctx->shard_scratch) (void)hipFree(ctx->shard_scratch);
     if (ctx->shard_event) (void)hipEventDestroy(ctx->shard_event);

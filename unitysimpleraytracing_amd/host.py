@@ -585,6 +585,16 @@ class RaytracingMeshDrawer:
             raise ValueError("mode must be layouts.REGION_TOUCHING or layouts.REGION_CONTAINED")
         self._overlaps(lambda h, q, n, s, o, t, cap: N.lib.lbvh_region_overlaps(h, q, n, mode, s, o, t, cap), regions, L.REGION, offsets, tris)
 
+    def region_overlaps_large(self, regions, mode, offsets, tris=None):
+        """region_overlaps for few large regions (one camera frustum, a cascade, a marquee selection; at most
+        _native.REGION_LARGE_MAX_COUNT of them): each region is spread over the device instead of over one lane
+        (lbvh_region_overlaps_large).  The same offsets and, per segment, the same set of indices, in another order.  Asynchronous."""
+        if mode not in (L.REGION_TOUCHING, L.REGION_CONTAINED):
+            raise ValueError("mode must be layouts.REGION_TOUCHING or layouts.REGION_CONTAINED")
+        if regions.size > N.REGION_LARGE_MAX_COUNT:
+            raise ValueError(f"region_overlaps_large takes at most {N.REGION_LARGE_MAX_COUNT} regions")
+        self._overlaps(lambda h, q, n, s, o, t, cap: N.lib.lbvh_region_overlaps_large(h, q, n, mode, s, o, t, cap), regions, L.REGION, offsets, tris)
+
     def region_overlaps_any(self, regions, mode, flags):
         """1 into the uint32 DataBuffer `flags` for each region of `regions` that has a candidate in `mode`, else 0."""
         if regions.dtype != L.REGION or flags.dtype != np.uint32 or flags.size < regions.size:
@@ -594,11 +604,12 @@ class RaytracingMeshDrawer:
         s = self.container.scene()
         N.check(self.ctx.handle, N.lib.lbvh_region_overlaps_any(self.ctx.handle, regions.device, regions.size, mode, C.byref(s), flags.device))
 
-    def in_regions(self, regions, mode=L.REGION_TOUCHING, min_capacity=1, device_sort=False):
+    def in_regions(self, regions, mode=L.REGION_TOUCHING, min_capacity=1, device_sort=False, large=False):
         """Convenience, as overlaps(): count -> one 8-byte download -> allocate -> fill, for a DataBuffer of layouts.REGION.
         Returns (offsets, tris): host arrays, uint64[regions.size + 1] and uint32[total].  device_sort=True issues
-        sort_index_segments before the download: every segment ascending."""
-        return self._csr_lists(lambda q, o, t=None: self.region_overlaps(q, mode, o, t), regions, min_capacity, device_sort)
+        sort_index_segments before the download: every segment ascending.  large=True: through region_overlaps_large."""
+        call = self.region_overlaps_large if large else self.region_overlaps
+        return self._csr_lists(lambda q, o, t=None: call(q, mode, o, t), regions, min_capacity, device_sort)
 
     def count_hits(self, rays, counts):
         """The number of candidates of each ray of `rays` (layouts.RAY) in (t_min, t_max) into the uint32 DataBuffer `counts`: every

@@ -51,14 +51,16 @@
 //                                                SortIndexSegments, TriangleIntersectsAny; prints the total, how many segments are
 //                                                non-empty, how many flags are set, the sum of (position + 1) * triangle index over
 //                                                the device-sorted list (mod 2^64) and the first segments
-//     lbvh_driver regions <n_regions> [seed]     the 4 096 triangles of cfg1 and n_regions sheared boxes (SplitMix64, seed default 6):
+//     lbvh_driver regions <n_regions> [seed] [large]  the 4 096 triangles of cfg1 and n_regions sheared boxes (SplitMix64, seed default 6):
 //                                                the centre uniform in the mesh's box, then per axis k a normal — the axis' unit
 //                                                vector with its two other components uniform in [-0.5, 0.5] — and a half width
 //                                                uniform in [1, 12]: the planes {n, h - n . c} and {-n, h + n . c}.  RegionOverlaps
 //                                                (count only, one 8-byte read, fill) in both modes, SortIndexSegments,
 //                                                RegionOverlapsAny; prints per mode the total, how many segments are non-empty, how
 //                                                many flags are set and the sum of (position + 1) * triangle index over the
-//                                                device-sorted list (mod 2^64), and the first TOUCHING segments
+//                                                device-sorted list (mod 2^64), and the first TOUCHING segments.  With `large` after
+//                                                the seed the lists come from RegionOverlapsLarge (n_regions <= 65 536): the same
+//                                                numbers, and "large": true in the output
 #include <chrono>
 #include <cmath>
 #include <cstdio>
@@ -645,6 +647,7 @@ static int regions_main(int argc, char** argv)
 {
     const size_t count = argc > 2 ? (size_t)strtoull(argv[2], nullptr, 10) : 65536;
     uint64_t seed = argc > 3 ? strtoull(argv[3], nullptr, 10) : 6;
+    const bool large = argc > 4 && std::string(argv[4]) == "large";
     const std::vector<lbvh_triangle> mesh = random_mesh(4096);
     float lo[3], hi[3];
     mesh_box(mesh, lo, hi);
@@ -673,13 +676,17 @@ static int regions_main(int argc, char** argv)
     regions.Sync();
     lbvh::DataBuffer<uint64_t> offsets(ctx, count + 1);
     lbvh::DataBuffer<uint32_t> flags(ctx, count);
-    std::printf("{\"triangles\": %zu, \"regions\": %zu", mesh.size(), count);
+    std::printf("{\"triangles\": %zu, \"regions\": %zu%s", mesh.size(), count, large ? ", \"large\": true" : "");
+    auto lists = [&](uint32_t mode, lbvh::DataBuffer<uint32_t>* tris) {
+        if (large) drawer.RegionOverlapsLarge(regions, mode, offsets, tris);
+        else drawer.RegionOverlaps(regions, mode, offsets, tris);
+    };
     for (uint32_t mode : {LBVH_REGION_CONTAINED, LBVH_REGION_TOUCHING}) {
-        drawer.RegionOverlaps(regions, mode, offsets);
+        lists(mode, nullptr);
         offsets.GetData();
         const unsigned long long total = offsets.LocalBuffer()[count];
         lbvh::DataBuffer<uint32_t> tris(ctx, total ? (size_t)total : 1);
-        drawer.RegionOverlaps(regions, mode, offsets, &tris);
+        lists(mode, &tris);
         drawer.SortIndexSegments(offsets, tris, count);
         drawer.RegionOverlapsAny(regions, mode, flags);
         offsets.GetData();

@@ -464,6 +464,17 @@ public:
                                                (uint64_t*)offsets.DeviceBuffer(), tris ? (uint32_t*)tris->DeviceBuffer() : nullptr,
                                                tris ? (uint64_t)tris->Size() : 0));
     }
+    // RegionOverlaps for few large regions (one frustum, a cascade, a marquee selection; at most LBVH_REGION_LARGE_MAX_COUNT): every
+    // region is spread over the device.  The same offsets and, per segment, the same set of indices, in another order
+    // (lbvh_region_overlaps_large; asynchronous).
+    void RegionOverlapsLarge(const DataBuffer<lbvh_region>& regions, uint32_t mode, DataBuffer<uint64_t>& offsets, DataBuffer<uint32_t>* tris = nullptr)
+    {
+        if (offsets.Size() < regions.Size() + 1) throw Error(LBVH_ERR_INVALID_ARG, "RegionOverlapsLarge: offsets needs one entry more than regions");
+        const lbvh_scene s = container_->Scene();
+        check(ctx_.get(), lbvh_region_overlaps_large(ctx_.get(), (const lbvh_region*)regions.DeviceBuffer(), regions.Size(), mode, &s,
+                                                     (uint64_t*)offsets.DeviceBuffer(), tris ? (uint32_t*)tris->DeviceBuffer() : nullptr,
+                                                     tris ? (uint64_t)tris->Size() : 0));
+    }
     void RegionOverlapsAny(const DataBuffer<lbvh_region>& regions, uint32_t mode, DataBuffer<uint32_t>& flags)
     {
         if (flags.Size() < regions.Size()) throw Error(LBVH_ERR_INVALID_ARG, "RegionOverlapsAny: fewer flags than regions");
