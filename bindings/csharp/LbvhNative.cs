@@ -34,6 +34,11 @@ public static class LbvhNative
     [StructLayout(LayoutKind.Sequential)]
     public struct SphereRay { public float originX, originY, originZ, radius; public float dirX, dirY, dirZ, tMax; }
 
+    // lbvh_capsule_ray (include/lbvh.h): a moving capsule, 48 bytes: SphereRay and the axis, whose other end is origin + axis
+    // (CapsuleCasts.cs); pad is not read
+    [StructLayout(LayoutKind.Sequential)]
+    public struct CapsuleRay { public float originX, originY, originZ, radius; public float dirX, dirY, dirZ, tMax; public float axisX, axisY, axisZ; public uint pad; }
+
     // lbvh_point_query / lbvh_closest_point (include/lbvh.h): a point with its squared search radius (active iff maxDist2 > 0) and
     // the nearest triangle's record, 16 bytes each (PointQueries.cs)
     [StructLayout(LayoutKind.Sequential)]
@@ -148,6 +153,8 @@ public static class LbvhNative
     [DllImport(Lib)] public static extern int lbvh_within_distance(IntPtr ctx, IntPtr dQueries, UIntPtr count, ref Scene scene, IntPtr dFlags);
     [DllImport(Lib)] public static extern int lbvh_sphere_cast(IntPtr ctx, IntPtr dCasts, UIntPtr count, ref Scene scene, IntPtr dHits);
     [DllImport(Lib)] public static extern int lbvh_sphere_cast_any(IntPtr ctx, IntPtr dCasts, UIntPtr count, ref Scene scene, IntPtr dFlags);
+    [DllImport(Lib)] public static extern int lbvh_capsule_cast(IntPtr ctx, IntPtr dCasts, UIntPtr count, ref Scene scene, IntPtr dHits);
+    [DllImport(Lib)] public static extern int lbvh_capsule_cast_any(IntPtr ctx, IntPtr dCasts, UIntPtr count, ref Scene scene, IntPtr dFlags);
     [DllImport(Lib)] public static extern int lbvh_triangle_intersections(IntPtr ctx, IntPtr dQueries, UIntPtr count, ref Scene scene, IntPtr dOffsets,
         IntPtr dTris, ulong capacity);
     [DllImport(Lib)] public static extern int lbvh_triangle_intersects_any(IntPtr ctx, IntPtr dQueries, UIntPtr count, ref Scene scene, IntPtr dFlags);

@@ -928,6 +928,68 @@ lbvh_status lbvh_sphere_cast(lbvh_context* ctx, const lbvh_sphere_ray* d_casts, 
 lbvh_status lbvh_sphere_cast_any(lbvh_context* ctx, const lbvh_sphere_ray* d_casts, size_t count, const lbvh_scene* h_scene,
                                  uint32_t* d_flags);
 
+/* A moving capsule: 48 bytes, arrays 16-byte aligned: lbvh_sphere_ray and the axis. */
+typedef struct lbvh_capsule_ray {
+    float origin[3]; float radius;     /* p: one end of the axis */
+    float dir[3];    float t_max;
+    float axis[3];   uint32_t _pad;    /* h: the other end is origin + axis; _pad is not read */
+} lbvh_capsule_ray;
+
+/* First contact of `count` moving capsules with the mesh (a "capsule cast": the shape a character controller sweeps), over the
+ * derived traversal scene in its four-wide form by the walk of lbvh_sphere_cast.  A capsule is every point within `radius` of its
+ * axis, the segment [c, c + h] with h = axis.  The axis moves without turning: c(t) = origin + dir * t for 0 <= t < T,
+ * T = min(t_max, LBVH_MAX_FLOAT); dir need not be unit length and t is in units of dir.
+ *   Active cast: the conditions of lbvh_sphere_cast on radius, t_max, origin and dir, and every component of axis finite.  axis = 0
+ *   is allowed (a sphere, by this definition's arithmetic).  An inactive cast is never walked; it gets the miss record
+ *   {LBVH_MAX_FLOAT, 0, 0, 0} (lbvh_capsule_cast) or 0 (lbvh_capsule_cast_any).
+ *   The definition goes through lbvh_sphere_cast: the capsule touches a triangle exactly when the sphere (c, radius) touches the
+ *   prism "triangle + segment [0, -h]", and the surface of that prism is eight triangles.
+ *   Derived triangles of a scene triangle with the line a, e1, e2: A = a, B = a + e1, C = a + e2, A' = A - h, B' = B - h,
+ *   C' = C - h, each per component in fp32.  Derived triangle j has a_j = P, e1_j = Q - P, e2_j = R - P, per component in fp32, for
+ *     j = 0   (P, Q, R) = (A, B, C): the line's own a, e1, e2 as stored, not formed again
+ *     j = 1   (A', B', C')
+ *     j = 2   (A, B, A')      j = 3   (B', A', B)        the side over AB
+ *     j = 4   (B, C, B')      j = 5   (C', B', C)        the side over BC
+ *     j = 6   (C, A, C')      j = 7   (A', C', A)        the side over CA
+ *   (each side is a parallelogram cut along one diagonal: the two triangles share it and cover the side).
+ *   Time with one scene triangle: t_j = the time lbvh_sphere_cast defines for the sphere (origin, radius, dir) against derived
+ *   triangle j (+0 on a start overlap there; none if that definition gives none).  The triangle's time is the least t_j, taken in
+ *   the order j = 0 .. 7, a later one replacing an earlier one only when strictly less, compared as fp32 values.  If no t_j equals
+ *   0 and pierce(origin, axis; a, e1, e2) of lbvh_triangle_intersections passes with its t = t_p (0 <= t_p <= 1), the time is +0:
+ *   the axis goes through the face at the start with both ends and all edges farther than the radius (the sphere's centre is inside
+ *   the prism).  A NaN never counts.
+ *   Candidate: triangle i is a candidate iff it has a time t_i, t_i < T, the ray (origin, dir) passes the slab test of the
+ *   triangle's own box grown by the axis and the radius — scene.triangle_aabb[i] with, per axis k,
+ *   min' = (min_k - max(h_k, 0)) - r and max' = (max_k - min(h_k, 0)) + r, two fp32 operations per bound, the slab test of every
+ *   walker of this library — with entry distance e_i, and !(t_i < e_i).  (c is in the grown box exactly when some point of the
+ *   axis is within r of the own box, per axis.)
+ *   lbvh_capsule_cast: d_hits[k] = {t, tri, u, v} of cast k's candidate with the least t (compared as fp32 values); on equal t the
+ *   lower original triangle index, whatever order the walk meets them in.  With j the derived triangle that gave the time, (u', v')
+ *   lbvh_closest_point_query's barycentrics of the point c(t) (per component o_k + d_k*t) on derived triangle j, the axis parameter
+ *   of the touching point is s = 0 for j = 0, 1 for j = 1, v' for j = 2, 4, 6, 1 - v' for j = 3, 5, 7, and t_p in the pierce case;
+ *   (u, v) are lbvh_closest_point_query's for the point x = c(t) + h*s (per component (o_k + d_k*t) + h_k*s) and the scene triangle.
+ *   The contact point on the mesh is q = a + e1*u + e2*v; x is the point of the axis nearest to it, s = clamp(dot(q - c(t), h) /
+ *   dot(h, h), 0, 1) recovers it, and the contact normal is (x - q) / r (for t = 0: any separating direction; x - q may be 0).
+ *   No candidate: the miss record, never T.
+ *   lbvh_capsule_cast_any: d_flags[k] = 1 if cast k has any candidate, else 0.  The walk is the same (same near-first order) cut
+ *   off at its first accepted candidate: never more node fetches or triangle tests per cast.
+ * Why the record does not depend on the order of the walk (the argument of lbvh_sphere_cast): (lo - max(h, 0)) - r and
+ * (hi - min(h, 0)) + r are each two operations monotone in lo and hi, and every box of the derived tree is the exact min / max union
+ * of what is below it, so the grown box of an ancestor contains the grown box of everything below it exactly in fp32; slab entries
+ * grow from a box to any box inside it, so e(ancestor) <= e(leaf) <= t for every candidate.  A slot is skipped only if the ray
+ * misses its grown box or its entry is > best, strictly: a subtree skipped that way holds no candidate at or below best.  Nothing
+ * is pruned on a box's exit distance.
+ * Both need the derived traversal scene (lbvh_build_fast_scene; a stale one is LBVH_ERR_INVALID_ARG), are asynchronous on the
+ * context's stream with no host wait, and use the context's ray scratch: they drop the path tracer's live-path list (see
+ * lbvh_path_bounce).  count == 0 is a no-op.  Rejected: NULL pointers, d_casts or d_hits not 16-byte aligned, d_flags not 4-byte
+ * aligned, count > 2^32 - 1.  Four-wide walk only (lbvh_debug_ray_walker does not apply); lbvh_debug_ray_stack_split,
+ * lbvh_debug_ray_stack_limit, lbvh_ray_stats_target and lbvh_debug_ray_waves apply as to the sphere cast.  The cost grows with the
+ * radius and the axis (every box is larger by both) and each tested triangle costs up to eight sphere tests. */
+lbvh_status lbvh_capsule_cast(lbvh_context* ctx, const lbvh_capsule_ray* d_casts, size_t count, const lbvh_scene* h_scene,
+                              lbvh_hit* d_hits);
+lbvh_status lbvh_capsule_cast_any(lbvh_context* ctx, const lbvh_capsule_ray* d_casts, size_t count, const lbvh_scene* h_scene,
+                                  uint32_t* d_flags);
+
 /* A query triangle: 48 bytes; arrays of them 16-byte aligned. */
 typedef struct lbvh_tri_query {
     float a[3]; uint32_t skip;     /* ORIGINAL index of a scene triangle that is never a candidate; LBVH_NULL = none */
@@ -1124,7 +1186,7 @@ lbvh_status lbvh_path_scatter(lbvh_context* ctx, const lbvh_scene* h_scene, cons
  * lbvh_path_bounce on the same d_states / d_hits listed as live (a list kept by the context).  Every library call that writes
  * into those buffers drops the list (lbvh_path_begin, lbvh_trace_rays, a primary trace into any part of d_hits,
  * lbvh_buffer_upload / _fill_u32 / _free), and so does lbvh_trace_forget — and so do lbvh_trace_closest,
- * lbvh_trace_occluded, lbvh_closest_point_query, lbvh_within_distance, lbvh_count_hits, lbvh_point_crossings, lbvh_box_overlaps, lbvh_gather_within_distance, lbvh_k_closest_points, lbvh_trace_k_closest, lbvh_gather_hits, lbvh_sphere_cast, lbvh_sphere_cast_any, lbvh_triangle_intersections, lbvh_triangle_intersects_any, lbvh_region_overlaps, lbvh_region_overlaps_any and lbvh_region_overlaps_large, whatever buffers they are given, since they use the same ray scratch; then every state is scanned again.  The one exception among the query calls:
+ * lbvh_trace_occluded, lbvh_closest_point_query, lbvh_within_distance, lbvh_count_hits, lbvh_point_crossings, lbvh_box_overlaps, lbvh_gather_within_distance, lbvh_k_closest_points, lbvh_trace_k_closest, lbvh_gather_hits, lbvh_sphere_cast, lbvh_sphere_cast_any, lbvh_capsule_cast, lbvh_capsule_cast_any, lbvh_triangle_intersections, lbvh_triangle_intersects_any, lbvh_region_overlaps, lbvh_region_overlaps_any and lbvh_region_overlaps_large, whatever buffers they are given, since they use the same ray scratch; then every state is scanned again.  The one exception among the query calls:
  * lbvh_sort_hit_segments and lbvh_sort_index_segments take no context scratch and keep the live-path list (they drop it only when the
  * buffer they sort is d_hits itself).  What the library
  * cannot see is a write of the CALLER's own (a kernel or hipMemcpy that revives or ends paths, Russian roulette): between two

@@ -1072,6 +1072,236 @@ __global__ __launch_bounds__(64) void sphere_cast_wide_kernel(const lbvh_sphere_
     if (STATS) add_ray_stats(stats, n_casts, n_steps, n_tris);
 }
 
+// ---- capsule casts: first contact of a moving capsule (include/lbvh.h, lbvh_capsule_cast) -------------------------------
+// A capsule (axis [p, p + h], radius r) touches a triangle exactly when the sphere (p, r) touches the prism "triangle + segment
+// [0, -h]", whose surface is eight triangles: the header's derived triangles.  Vertex id 0 .. 5 = A, B, C, A', B', C' of the
+// header: A = a, B = a + e1, C = a + e2 and X' = X - h, every one per component in fp32.
+__device__ __forceinline__ void capsule_vertex(uint32_t id, const float4 a, const float4 e1, const float4 e2, float hx, float hy, float hz,
+                                               float& x, float& y, float& z)
+{
+    const uint32_t base = id >= 3u ? id - 3u : id;
+    const float ex = base == 1u ? e1.x : e2.x, ey = base == 1u ? e1.y : e2.y, ez = base == 1u ? e1.z : e2.z;
+    x = base == 0u ? a.x : a.x + ex;
+    y = base == 0u ? a.y : a.y + ey;
+    z = base == 0u ? a.z : a.z + ez;
+    if (id >= 3u) { x = x - hx; y = y - hy; z = z - hz; }
+}
+
+// derived triangle j of the header as {P, Q - P, R - P}; j = 0 is the line as stored.  One nibble per j and corner:
+// (P, Q, R) = (A, B, C) (A', B', C') (A, B, A') (B', A', B) (B, C, B') (C', B', C) (C, A, C') (A', C', A)
+__device__ __forceinline__ void capsule_triangle(uint32_t j, const float4 a, const float4 e1, const float4 e2, float hx, float hy, float hz,
+                                                 float4& p, float4& q1, float4& q2)
+{
+    const uint32_t sh = 4u * j;
+    float px, py, pz, qx, qy, qz, rx, ry, rz;
+    capsule_vertex((0x32514030u >> sh) & 7u, a, e1, e2, hx, hy, hz, px, py, pz);
+    capsule_vertex((0x50423141u >> sh) & 7u, a, e1, e2, hx, hy, hz, qx, qy, qz);
+    capsule_vertex((0x05241352u >> sh) & 7u, a, e1, e2, hx, hy, hz, rx, ry, rz);
+    const bool own = j == 0u;
+    p = make_float4(px, py, pz, 0.0f);
+    q1 = make_float4(own ? e1.x : qx - px, own ? e1.y : qy - py, own ? e1.z : qz - pz, 0.0f);
+    q2 = make_float4(own ? e2.x : rx - px, own ? e2.y : ry - py, own ? e2.z : rz - pz, 0.0f);
+}
+
+// The header's time of a capsule with one scene triangle, +inf if it has none: the least sphere_triangle_time over the derived
+// triangles j = 0 .. 7 in that order, a later one taken only when strictly less (so the loop may stop at the first zero), then the
+// pierce of the axis through the face.  `which` = the winning j, 8 for the pierce, whose parameter is `t_p`.  One copy of the
+// sphere test in a loop that is not unrolled, the corners selected by j: eight inlined copies do not fit the register file.
+__device__ __forceinline__ float capsule_triangle_time(const ray_t& c, float r, float hx, float hy, float hz, const float4 a, const float4 e1,
+                                                       const float4 e2, uint32_t& which, float& t_p)
+{
+    float t = __builtin_inff();
+    which = 0u;
+#pragma nounroll
+    for (uint32_t j = 0; j < 8u; j++) {
+        float4 p, q1, q2;
+        capsule_triangle(j, a, e1, e2, hx, hy, hz, p, q1, q2);
+        const float tj = sphere_triangle_time(c, r, p, q1, q2);
+        if (tj < t) { t = tj; which = j; }
+        if (t == 0.0f) return t;
+    }
+    ray_t ax;
+    ax.ox = c.ox; ax.oy = c.oy; ax.oz = c.oz;
+    ax.dx = hx; ax.dy = hy; ax.dz = hz;
+    ax.ix = 0.0f; ax.iy = 0.0f; ax.iz = 0.0f;            // (not read by the triangle test)
+    float u = 0.0f, v = 0.0f;
+    const float tp = ray_triangle_edges(ax, a, e1.x, e1.y, e1.z, e2.x, e2.y, e2.z, u, v);
+    if (0.0f <= tp && tp <= 1.0f) { t = 0.0f; which = 8u; t_p = tp; }
+    return t;
+}
+
+// (u, v) of a taken candidate: s, the axis parameter of the touching point, from point_triangle2 at c(t) on the winning derived
+// triangle (0 on the triangle itself, 1 on its shifted copy, v' or 1 - v' on a side, t_p for the pierce), then point_triangle2 of
+// c(t) + h*s on the scene triangle
+__device__ __forceinline__ void capsule_contact(const ray_t& c, float t, float hx, float hy, float hz, const float4 a, const float4 e1,
+                                                const float4 e2, uint32_t which, float t_p, float& u_out, float& v_out)
+{
+    const float cx = c.ox + c.dx * t, cy = c.oy + c.dy * t, cz = c.oz + c.dz * t;
+    float s = which == 8u ? t_p : (which == 1u ? 1.0f : 0.0f);
+    if (which >= 2u && which < 8u) {
+        float4 p, q1, q2;
+        capsule_triangle(which, a, e1, e2, hx, hy, hz, p, q1, q2);
+        float u1, v1;
+        point_triangle2(cx, cy, cz, p, q1, q2, u1, v1);
+        s = (which & 1u) ? 1.0f - v1 : v1;
+    }
+    point_triangle2(cx + hx * s, cy + hy * s, cz + hz * s, a, e1, e2, u_out, v_out);
+}
+
+// cast k into the lane (best_t = T): false (miss record / 0 written, lane stays idle) for an inactive cast
+template <bool ANY>
+__device__ __forceinline__ bool load_capsule_cast(const lbvh_capsule_ray* __restrict__ casts, uint32_t k, ray_t& ray, float& r, float& hx,
+                                                  float& hy, float& hz, float& best_t,
+                                                  std::conditional_t<ANY, uint32_t, lbvh_hit>* __restrict__ out)
+{
+    const float inf = __builtin_inff();
+    const float4* q = reinterpret_cast<const float4*>(&casts[k]);
+    const float4 o = q[0], d = q[1], h = q[2];
+    ray.ox = o.x; ray.oy = o.y; ray.oz = o.z;
+    ray.dx = d.x; ray.dy = d.y; ray.dz = d.z;
+    ray.ix = 1.0f / d.x; ray.iy = 1.0f / d.y; ray.iz = 1.0f / d.z;
+    r = o.w;
+    hx = h.x; hy = h.y; hz = h.z;
+    best_t = fminf(d.w, LBVH_MAX_FLOAT);                 // T: candidates have t < T
+    if (o.w > 0.0f && o.w < inf && d.w > 0.0f && (o.x == o.x && o.y == o.y && o.z == o.z) &&
+        fabsf(d.x) < inf && fabsf(d.y) < inf && fabsf(d.z) < inf && dot3(d.x, d.y, d.z, d.x, d.y, d.z) > 0.0f &&
+        fabsf(h.x) < inf && fabsf(h.y) < inf && fabsf(h.z) < inf) return true;
+    if constexpr (ANY) out[k] = 0u;
+    else reinterpret_cast<float4*>(out)[k] = make_float4(LBVH_MAX_FLOAT, __uint_as_float(0u), 0.0f, 0.0f);
+    return false;
+}
+
+// One cast per lane in the frame of sphere_cast_wide_kernel.  The four slot boxes are grown by the sweep of the axis and the radius,
+// (lo - max(h, 0)) - r and (hi - min(h, 0)) + r — two operations per bound, both monotone in lo / hi, so a grown box contains the
+// grown boxes of everything below it and the record does not depend on the order of the walk, as there.  At a leaf the triangle
+// line is read once and the eight derived triangles are formed from it in registers; s, (u', v') and (u, v) only for a candidate
+// that is taken.
+template <bool ANY, bool STATS>
+__global__ __launch_bounds__(64) void capsule_cast_wide_kernel(const lbvh_capsule_ray* __restrict__ casts, uint32_t total,
+                                                               const lbvh_wide_node* __restrict__ wide,
+                                                               const lbvh_fast_node* __restrict__ lines,
+                                                               std::conditional_t<ANY, uint32_t, lbvh_hit>* __restrict__ out,
+                                                               uint32_t* __restrict__ deep,     // [gridDim.x][kWideStackDeep][64]
+                                                               uint32_t lds_depth,              // <= kWideStackLds
+                                                               uint32_t deep_cap,               // <= kWideStackDeep
+                                                               uint32_t* __restrict__ fault, lbvh_ray_stats* stats)
+{
+    __shared__ uint32_t s_stack[kWideStackLds][LBVH_WAVE];
+    uint32_t* my_deep = deep + (size_t)blockIdx.x * (kWideStackDeep * LBVH_WAVE) + threadIdx.x;
+    const uint32_t lane = threadIdx.x;
+    const uint32_t run = max((total + gridDim.x - 1) / gridDim.x, 32u);
+    uint32_t next = blockIdx.x * run;
+    if (next >= total) return;
+    const uint32_t end = min(next + run, total);
+    uint32_t n_casts = 0, n_steps = 0, n_tris = 0;
+
+    bool active = false, took = false;
+    uint32_t i = 0;
+    ray_t ray = {};
+    float r = 0.0f, hx = 0.0f, hy = 0.0f, hz = 0.0f;
+    float best_t = LBVH_MAX_FLOAT, best_u = 0.0f, best_v = 0.0f;
+    uint32_t best_tri = 0, sp = 0, node = 0;
+    auto push = [&](uint32_t ref) {
+        if (sp < lds_depth) { s_stack[sp][lane] = ref; sp++; }
+        else if (sp < lds_depth + deep_cap) { my_deep[(sp - lds_depth) * LBVH_WAVE] = ref; sp++; }
+        // a dropped entry would be a silently wrong record: report it, as the ray walkers do (lbvh_debug_ray_stack_limit provokes it)
+        else __hip_atomic_store(fault, LBVH_FAULT_RAY_STACK, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    };
+    for (;;) {
+        const uint64_t idle = __ballot(!active);
+        if (idle != 0 && next < end) {
+            if (!active) {
+                const uint32_t k = next + mbcnt64(idle);
+                if (k < end) {
+                    i = k;
+                    active = load_capsule_cast<ANY>(casts, k, ray, r, hx, hy, hz, best_t, out);
+                    best_tri = 0; best_u = 0.0f; best_v = 0.0f; took = false;
+                    sp = 0; node = 0;
+                    if (STATS && active) n_casts++;
+                }
+            }
+            next += (uint32_t)__popcll(idle);
+        }
+        if (!__any(active) && next >= end) break;
+        if (active) {
+            if (STATS) n_steps++;
+            const float4* w = reinterpret_cast<const float4*>(&wide[node]);
+            const float4 lox = w[0], loy = w[1], loz = w[2], hix = w[3], hiy = w[4], hiz = w[5];
+            const uint4 ref = reinterpret_cast<const uint4*>(w)[6];
+            // max(h, 0) and min(h, 0) are formed here from h, which the leaf test needs anyway: held through the walk they are six
+            // more registers and the record form drops from four waves per SIMD to three
+            const float px = fmaxf(hx, 0.0f), py = fmaxf(hy, 0.0f), pz = fmaxf(hz, 0.0f);
+            const float nx = fminf(hx, 0.0f), ny = fminf(hy, 0.0f), nz = fminf(hz, 0.0f);
+            float t0, t1, t2, t3;
+            const bool h0 = wide_box((lox.x - px) - r, (loy.x - py) - r, (loz.x - pz) - r, (hix.x - nx) + r, (hiy.x - ny) + r, (hiz.x - nz) + r, ray, t0) &&
+                            !(t0 > best_t) && ref.x != kWideEmpty;
+            const bool h1 = wide_box((lox.y - px) - r, (loy.y - py) - r, (loz.y - pz) - r, (hix.y - nx) + r, (hiy.y - ny) + r, (hiz.y - nz) + r, ray, t1) &&
+                            !(t1 > best_t) && ref.y != kWideEmpty;
+            const bool h2 = wide_box((lox.z - px) - r, (loy.z - py) - r, (loz.z - pz) - r, (hix.z - nx) + r, (hiy.z - ny) + r, (hiz.z - nz) + r, ray, t2) &&
+                            !(t2 > best_t) && ref.z != kWideEmpty;
+            const bool h3 = wide_box((lox.w - px) - r, (loy.w - py) - r, (loz.w - pz) - r, (hix.w - nx) + r, (hiy.w - ny) + r, (hiz.w - nz) + r, ray, t3) &&
+                            !(t3 > best_t) && ref.w != kWideEmpty;
+            // leaf slots first: a lane's leaves one after the other, every lane's k-th at the same time
+            uint32_t leaves = (h0 && (ref.x >> 31) ? 1u : 0u) | (h1 && (ref.y >> 31) ? 2u : 0u) | (h2 && (ref.z >> 31) ? 4u : 0u) |
+                              (h3 && (ref.w >> 31) ? 8u : 0u);
+            bool found = false;                          // ANY: a candidate was accepted
+            while (leaves != 0u) {
+                const uint32_t k = (uint32_t)__builtin_ctz(leaves);
+                leaves &= leaves - 1u;
+                if (STATS) n_tris++;
+                float4 v0, v1, v2;
+                unpack_fast_triangle(reinterpret_cast<const float4*>(&lines[pick4(ref, k) & 0x7FFFFFFFu]), v0, v1, v2);
+                uint32_t which;
+                float t_p = 0.0f;
+                const float t = capsule_triangle_time(ray, r, hx, hy, hz, v0, v1, v2, which, t_p);
+                const uint32_t tri = __float_as_uint(v0.w);
+                const float entry = k == 0u ? t0 : (k == 1u ? t1 : (k == 2u ? t2 : t3));
+                // best_t starts at T and best_tri at 0: t == T is never taken.  Ties go to the lower triangle index.
+                if (hit_counts(t, entry) && (t < best_t || (t == best_t && tri < best_tri))) {
+                    if constexpr (ANY) { found = true; break; }
+                    else {
+                        best_t = t; best_tri = tri; took = true;
+                        capsule_contact(ray, t, hx, hy, hz, v0, v1, v2, which, t_p, best_u, best_v);
+                    }
+                }
+            }
+            if (ANY && found) {
+                if constexpr (ANY) out[i] = 1u;
+                active = false;
+                continue;
+            }
+            // nodes to enter, ordered by entry distance (the order key of sphere_cast_wide_kernel)
+            constexpr uint32_t none = 0xFFFFFFFFu;
+            uint32_t k0 = h0 && !(ref.x >> 31) && !(t0 > best_t) ? ((__float_as_uint(fmaxf(t0, 0.0f)) & ~3u) | 0u) : none;
+            uint32_t k1 = h1 && !(ref.y >> 31) && !(t1 > best_t) ? ((__float_as_uint(fmaxf(t1, 0.0f)) & ~3u) | 1u) : none;
+            uint32_t k2 = h2 && !(ref.z >> 31) && !(t2 > best_t) ? ((__float_as_uint(fmaxf(t2, 0.0f)) & ~3u) | 2u) : none;
+            uint32_t k3 = h3 && !(ref.w >> 31) && !(t3 > best_t) ? ((__float_as_uint(fmaxf(t3, 0.0f)) & ~3u) | 3u) : none;
+            {   // five compare-exchanges
+                uint32_t a, b;
+                a = min(k0, k1); b = max(k0, k1); k0 = a; k1 = b;
+                a = min(k2, k3); b = max(k2, k3); k2 = a; k3 = b;
+                a = min(k0, k2); b = max(k0, k2); k0 = a; k2 = b;
+                a = min(k1, k3); b = max(k1, k3); k1 = a; k3 = b;
+                a = min(k1, k2); b = max(k1, k2); k1 = a; k2 = b;
+            }
+            if (k0 != none) {
+                if (k3 != none) push(pick4(ref, k3 & 3u));       // farthest first: the nearest waiting sibling is popped first
+                if (k2 != none) push(pick4(ref, k2 & 3u));
+                if (k1 != none) push(pick4(ref, k1 & 3u));
+                node = pick4(ref, k0 & 3u);
+            } else if (sp != 0) {
+                sp--;
+                node = sp < lds_depth ? s_stack[sp][lane] : my_deep[(sp - lds_depth) * LBVH_WAVE];
+            } else {
+                if constexpr (ANY) out[i] = 0u;
+                else put_hit<true>(out, i, best_t, took, best_tri, best_u, best_v);
+                active = false;
+            }
+        }
+    }
+    if (STATS) add_ray_stats(stats, n_casts, n_steps, n_tris);
+}
+
 // lbvh_k_closest_points: the walk of point_query_wide_kernel<false> with "best so far" replaced by "k-th best so far".  Each lane
 // keeps the k best candidates met so far, sorted by (dist2, tri), in LDS: three arrays [slot][lane] of dist2, triangle index and
 // the index of the triangle's line in the derived scene — 12 bytes per slot, `cap` slots per lane, sized at the launch from k
@@ -2723,6 +2953,25 @@ static lbvh_status sphere_casts(lbvh_context* ctx, const lbvh_sphere_ray* d_cast
     return LBVH_OK;
 }
 
+// lbvh_capsule_cast / lbvh_capsule_cast_any: as sphere_casts, one launch
+template <bool ANY>
+static lbvh_status capsule_casts(lbvh_context* ctx, const lbvh_capsule_ray* d_casts, size_t count, const lbvh_scene* h_scene,
+                                 std::conditional_t<ANY, uint32_t, lbvh_hit>* d_out, const char* who)
+{
+    if (!ctx) return LBVH_ERR_INVALID_ARG;
+    if (count == 0) return LBVH_OK;
+    LBVH_REQUIRE(ctx, d_casts != nullptr && h_scene != nullptr && d_out != nullptr);
+    LBVH_REQUIRE(ctx, ((uintptr_t)d_casts & 15) == 0 && ((uintptr_t)d_out & (ANY ? 3 : 15)) == 0);
+    LBVH_REQUIRE(ctx, count <= 0xFFFFFFFFull);
+    walk_launch w;
+    const lbvh_status rc = begin_walk(ctx, h_scene, count, who, true, &w);
+    if (rc != LBVH_OK) return rc;
+    LBVH_LAUNCH_STATS(ctx, ctx->ray_stats, (capsule_cast_wide_kernel<ANY, STATS>), dim3(w.waves), dim3(LBVH_WAVE), d_casts, (uint32_t)count, w.wn,
+                      ctx->fast_nodes, d_out, w.deep, w.lds, w.deep_cap, ctx->fault_dev, ctx->ray_stats);
+    LBVH_HIP_TRY(ctx, hipGetLastError());
+    return LBVH_OK;
+}
+
 // lbvh_box_overlaps / lbvh_gather_within_distance: count walk -> scan -> fill walk, all on the context's stream, no host wait.
 // The counts (4 bytes per query) and the tile sums of the scan live where lbvh_trace_rays keeps its two live-ray lists: the ray
 // scratch is sized for 8 bytes per query there, and the list is dropped anyway.
@@ -2982,6 +3231,16 @@ lbvh_status lbvh_sphere_cast(lbvh_context* ctx, const lbvh_sphere_ray* d_casts, 
 lbvh_status lbvh_sphere_cast_any(lbvh_context* ctx, const lbvh_sphere_ray* d_casts, size_t count, const lbvh_scene* h_scene, uint32_t* d_flags)
 {
     return sphere_casts<true>(ctx, d_casts, count, h_scene, d_flags, "lbvh_sphere_cast_any");
+}
+
+lbvh_status lbvh_capsule_cast(lbvh_context* ctx, const lbvh_capsule_ray* d_casts, size_t count, const lbvh_scene* h_scene, lbvh_hit* d_hits)
+{
+    return capsule_casts<false>(ctx, d_casts, count, h_scene, d_hits, "lbvh_capsule_cast");
+}
+
+lbvh_status lbvh_capsule_cast_any(lbvh_context* ctx, const lbvh_capsule_ray* d_casts, size_t count, const lbvh_scene* h_scene, uint32_t* d_flags)
+{
+    return capsule_casts<true>(ctx, d_casts, count, h_scene, d_flags, "lbvh_capsule_cast_any");
 }
 
 // the four-wide walk only (lbvh_debug_ray_walker does not apply), the directions by value in the arguments

@@ -478,6 +478,24 @@ class RaytracingMeshDrawer:
         s = self.container.scene()
         N.check(self.ctx.handle, fn(self.ctx.handle, casts.device, casts.size, C.byref(s), out.device))
 
+    def capsule_cast(self, casts, hits):
+        """First contact of each moving capsule of the DataBuffer `casts` (layouts.CAPSULE_RAY: origin, radius, dir, t_max, axis —
+        the axis is the segment from origin to origin + axis, every point within `radius` of it the capsule) with the mesh into the
+        DataBuffer `hits` (layouts.HIT: t, tri, and the barycentrics u, v of the contact point on the triangle), over the derived
+        scene.  The axis starts at origin + dir * t; no contact in [0, t_max): the miss record.  Asynchronous; read with
+        hits.get_data()."""
+        self._capsule_casts(N.lib.lbvh_capsule_cast, casts, hits, L.HIT)
+
+    def capsule_cast_any(self, casts, flags):
+        """1 into the uint32 DataBuffer `flags` for each capsule of `casts` that touches anything on its way, else 0."""
+        self._capsule_casts(N.lib.lbvh_capsule_cast_any, casts, flags, np.dtype(np.uint32))
+
+    def _capsule_casts(self, fn, casts, out, dtype):
+        if casts.dtype != L.CAPSULE_RAY or out.dtype != dtype or out.size < casts.size:
+            raise ValueError(f"casts must be a DataBuffer of layouts.CAPSULE_RAY and the output one of {dtype} with at least as many entries")
+        s = self.container.scene()
+        N.check(self.ctx.handle, fn(self.ctx.handle, casts.device, casts.size, C.byref(s), out.device))
+
     def closest_points(self, queries, out):
         """Nearest triangle of each point of the DataBuffer `queries` (layouts.POINT_QUERY: p, max_dist2) into the DataBuffer `out`
         (layouts.CLOSEST_POINT: dist2, tri, u, v), over the derived scene.  Asynchronous; read with out.get_data()."""

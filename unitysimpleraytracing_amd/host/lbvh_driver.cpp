@@ -40,6 +40,10 @@
 //                                                it (t = 1 at the target, t_max 2); SphereCast and SphereCastAny; prints how
 //                                                many casts touch, the sum of all 32-bit words of the records (mod 2^64) and the
 //                                                first records
+//     lbvh_driver capsule <n_casts> [seed] [radius] [height]  the 4 096 triangles of cfg1 and n_casts capsules (SplitMix64, seed
+//                                                default 3; radius default 1.5, height default 4): per axis the origin and the
+//                                                target as `sweep` draws them, then the axis component uniform in [-height,
+//                                                height]; t_max 2.  CapsuleCast and CapsuleCastAny; prints the fields of `sweep`
 //     lbvh_driver crossings [n | file.obj] [count] the mesh and the points of `points`; PointCrossings along the three default
 //                                                directions ((1,1,1)/sqrt 3, (-1,2,3)/sqrt 14, (4,-1,2)/sqrt 21) and CountHits
 //                                                on the same rays written out ({p, 0, dir, +inf}); prints the sum of the counts,
@@ -717,6 +721,57 @@ static int regions_main(int argc, char** argv)
     return 0;
 }
 
+static int capsule_main(int argc, char** argv)
+{
+    const size_t count = argc > 2 ? (size_t)strtoull(argv[2], nullptr, 10) : 65536;
+    uint64_t seed = argc > 3 ? strtoull(argv[3], nullptr, 10) : 3;
+    const float radius = argc > 4 ? (float)atof(argv[4]) : 1.5f;
+    const float height = argc > 5 ? (float)atof(argv[5]) : 4.0f;
+    const std::vector<lbvh_triangle> mesh = random_mesh(4096);
+    float lo[3], hi[3];
+    mesh_box(mesh, lo, hi);
+    lbvh::Context ctx(0);
+    lbvh::RaytracingMeshDrawer drawer(ctx, mesh);
+    drawer.Awake();
+    lbvh::DataBuffer<lbvh_capsule_ray> casts(ctx, count);
+    for (auto& c : casts.LocalBuffer()) {
+        std::memset(&c, 0, sizeof c);
+        for (int k = 0; k < 3; k++) {
+            const float grow = 0.25f * (hi[k] - lo[k]);
+            c.origin[k] = uniform(seed, lo[k] - grow, hi[k] + grow);
+            c.dir[k] = uniform(seed, lo[k], hi[k]) - c.origin[k];
+            c.axis[k] = uniform(seed, -height, height);
+        }
+        c.radius = radius;
+        c.t_max = 2.0f;
+    }
+    casts.Sync();
+    lbvh::DataBuffer<lbvh_hit> hits(ctx, count);
+    lbvh::DataBuffer<uint32_t> flags(ctx, count);
+    drawer.CapsuleCast(casts, hits);
+    drawer.CapsuleCastAny(casts, flags);
+    hits.GetData();
+    flags.GetData();
+    size_t touching = 0, flagged = 0, at_start = 0;
+    uint64_t words = 0;
+    for (size_t i = 0; i < count; i++) {
+        const lbvh_hit& h = hits.LocalBuffer()[i];
+        words += word_sum(h);
+        touching += h.t < LBVH_MAX_FLOAT;
+        at_start += h.t == 0.0f;
+        flagged += flags.LocalBuffer()[i];
+    }
+    std::printf("{\"triangles\": %zu, \"casts\": %zu, \"radius\": %.9g, \"height\": %.9g, \"touching\": %zu, \"flagged\": %zu, "
+                "\"at_start\": %zu, \"word_sum\": %llu, \"records\": [",
+                mesh.size(), count, radius, height, touching, flagged, at_start, (unsigned long long)words);
+    for (size_t i = 0; i < std::min<size_t>(count, 3); i++) {
+        const lbvh_hit& h = hits.LocalBuffer()[i];
+        std::printf("%s[%.9g, %u, %.9g, %.9g]", i ? ", " : "", h.t, h.tri, h.u, h.v);
+    }
+    std::printf("]}\n");
+    return 0;
+}
+
 static int crossings_main(int argc, char** argv)
 {
     const size_t count = argc > 3 ? (size_t)strtoull(argv[3], nullptr, 10) : 65536;
@@ -850,7 +905,7 @@ int main(int argc, char** argv)
 {
     static const struct { const char* name; int (*run)(int, char**); } commands[] = {
         {"crossings", crossings_main}, {"points", points_main}, {"knn", knn_main},   {"khits", khits_main}, {"gather", gather_main}, {"sortedhits", sortedhits_main},
-        {"sweep", sweep_main},         {"overlaps", overlaps_main}, {"tris", tris_main}, {"regions", regions_main}, {"rays", rays_main}, {"sort", sort_main},   {"multi", multi_main}};
+        {"sweep", sweep_main},         {"capsule", capsule_main},         {"overlaps", overlaps_main}, {"tris", tris_main}, {"regions", regions_main}, {"rays", rays_main}, {"sort", sort_main},   {"multi", multi_main}};
     try {
         for (const auto& c : commands)
             if (argc > 1 && std::strcmp(argv[1], c.name) == 0) return c.run(argc, argv);

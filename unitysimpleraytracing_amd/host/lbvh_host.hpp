@@ -403,6 +403,22 @@ public:
         const lbvh_scene s = container_->Scene();
         check(ctx_.get(), lbvh_sphere_cast_any(ctx_.get(), (const lbvh_sphere_ray*)casts.DeviceBuffer(), casts.Size(), &s, (uint32_t*)flags.DeviceBuffer()));
     }
+    // moving capsules of the caller's own (lbvh_capsule_ray: origin, radius, dir, t_max, axis; the axis is the segment from origin
+    // to origin + axis) over the derived scene: the first contact of each — {t, tri, u, v}, the axis starting at origin + dir * t,
+    // (u, v) the barycentrics of the contact point on the triangle — or whether it touches anything on its way, 1 / 0 per cast
+    // (lbvh_capsule_cast / lbvh_capsule_cast_any; asynchronous)
+    void CapsuleCast(const DataBuffer<lbvh_capsule_ray>& casts, DataBuffer<lbvh_hit>& hits)
+    {
+        if (hits.Size() < casts.Size()) throw Error(LBVH_ERR_INVALID_ARG, "CapsuleCast: fewer hit records than casts");
+        const lbvh_scene s = container_->Scene();
+        check(ctx_.get(), lbvh_capsule_cast(ctx_.get(), (const lbvh_capsule_ray*)casts.DeviceBuffer(), casts.Size(), &s, (lbvh_hit*)hits.DeviceBuffer()));
+    }
+    void CapsuleCastAny(const DataBuffer<lbvh_capsule_ray>& casts, DataBuffer<uint32_t>& flags)
+    {
+        if (flags.Size() < casts.Size()) throw Error(LBVH_ERR_INVALID_ARG, "CapsuleCastAny: fewer flags than casts");
+        const lbvh_scene s = container_->Scene();
+        check(ctx_.get(), lbvh_capsule_cast_any(ctx_.get(), (const lbvh_capsule_ray*)casts.DeviceBuffer(), casts.Size(), &s, (uint32_t*)flags.DeviceBuffer()));
+    }
     // the k nearest triangles of each point (1 <= k <= LBVH_K_CLOSEST_MAX): out[q * k + j] = the j-th nearest of query q, ties by
     // the lower triangle index, padded with none-records; found (optional): the number of real records per row
     // (lbvh_k_closest_points; asynchronous)

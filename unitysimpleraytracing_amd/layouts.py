@@ -36,6 +36,9 @@ assert RAY.itemsize == 32
 # lbvh_sphere_cast / lbvh_sphere_cast_any: lbvh_ray with the sphere's radius where t_min is
 SPHERE_RAY = np.dtype([("origin", "<f4", 3), ("radius", "<f4"), ("dir", "<f4", 3), ("t_max", "<f4")])
 assert SPHERE_RAY.itemsize == 32
+# lbvh_capsule_cast / lbvh_capsule_cast_any: the sphere's record and the axis (the other end is origin + axis)
+CAPSULE_RAY = np.dtype([("origin", "<f4", 3), ("radius", "<f4"), ("dir", "<f4", 3), ("t_max", "<f4"), ("axis", "<f4", 3), ("_pad", "<u4")])
+assert CAPSULE_RAY.itemsize == 48
 # lbvh_closest_point_query / lbvh_within_distance: a point with its squared search radius (active iff max_dist2 > 0), and the answer
 POINT_QUERY = np.dtype([("p", "<f4", 3), ("max_dist2", "<f4")])
 CLOSEST_POINT = np.dtype([("dist2", "<f4"), ("tri", "<u4"), ("u", "<f4"), ("v", "<f4")])
