@@ -1,5 +1,7 @@
 """What the entry points that walk the derived scene one ray or query per lane have in common (lbvh_path.hip: begin_walk, the
-prologue they share, and LBVH_LAUNCH_STATS, the one place that picks the counting or the plain instantiation of a walker): one
+prologue they share; LBVH_LAUNCH_STATS, the one place that picks the counting or the plain instantiation of a walker;
+launch_per_query, the one launch of the point queries and the sphere and capsule casts; csr_query and csr_offsets, the count walk
+-> scan -> fill walk of every CSR answer — while each family keeps its own argument checks, whose text a row quotes): one
 table, one test, a row per entry point.  The answers themselves are the per-query test files' business; here every comparison
 is between two calls of the library, word for word on uint32 views.
 
@@ -33,9 +35,11 @@ def _rays(tris, rng):
 
 
 def _table(tris):
-    """name -> (query dtype, queries, extra arguments between count and the scene, arguments between the scene's place and the
-    outputs, outputs as (dtype, entries, required alignment in bytes)).  The call is fn(ctx, queries, count, *extra, scene, *outputs)
-    except for lbvh_point_crossings, whose directions come before the scene."""
+    """name -> (queries, extra arguments between count and the scene, outputs as (dtype, entries, required alignment in bytes),
+    lbvh_last_error after a misaligned pointer).  The call is fn(ctx, queries, count, *extra, scene, *outputs), a CSR row's capacity
+    last; the extra arguments are lbvh_point_crossings' directions, k, and the region rows' mode.  The message is the text of the
+    alignment check of the entry point's family in lbvh_path.hip, as LBVH_REQUIRE reports it ("invalid argument: " and the
+    condition) or, for the region rows, under the entry point's own name."""
     lay = L()
     rng = np.random.default_rng(23)
     origin, d, target = _rays(tris, rng)
@@ -43,36 +47,69 @@ def _table(tris):
     rays["origin"], rays["dir"], rays["t_min"], rays["t_max"] = origin, d, 0.0, np.inf
     casts = np.zeros(COUNT, dtype=lay.SPHERE_RAY)
     casts["origin"], casts["dir"], casts["radius"], casts["t_max"] = origin, d, 0.4, np.inf
+    capsules = np.zeros(COUNT, dtype=lay.CAPSULE_RAY)
+    capsules["origin"], capsules["dir"], capsules["radius"], capsules["t_max"] = origin, d, 0.4, np.inf
+    capsules["axis"] = rng.normal(size=(COUNT, 3)).astype(F)
     points = np.zeros(COUNT, dtype=lay.POINT_QUERY)
     points["p"] = target + rng.normal(size=(COUNT, 3)).astype(F)
     points["max_dist2"] = 9.0
     boxes = np.zeros(COUNT, dtype=lay.AABB)
     boxes["min"], boxes["max"] = points["p"] - F(2.0), points["p"] + F(2.0)
+    regions = H().aabb_planes(boxes["min"], boxes["max"])
+    tri_queries = np.zeros(COUNT, dtype=lay.TRI_QUERY)
+    tri_queries["a"], tri_queries["skip"] = points["p"], lay.NULL
+    tri_queries["b"] = points["p"] + rng.normal(size=(COUNT, 3)).astype(F) * F(3.0)
+    tri_queries["c"] = points["p"] + rng.normal(size=(COUNT, 3)).astype(F) * F(3.0)
     dirs = np.array([[1, 0, 0], [0.3, 1, 0.2], [0.1, -0.2, 1]], dtype=F)
     u32, u64 = np.dtype(np.uint32), np.dtype(np.uint64)
     hit, cp = (lay.HIT, COUNT, 16), (lay.CLOSEST_POINT, COUNT, 16)
     flag = (u32, COUNT, 4)
     csr = [(u64, COUNT + 1, 8), (u32, COUNT * len(tris), 4)]
+    csr_hits = [(u64, COUNT + 1, 8), (lay.HIT, COUNT * len(tris), 16)]
+    touching = (lay.REGION_TOUCHING,)
+    bad = "invalid argument: "
+    out_any = " && ((uintptr_t)d_out & (ANY ? 3 : 15)) == 0"
+    found = " && ((uintptr_t)d_found & 3) == 0"
+    lists = "((uintptr_t)d_queries & 15) == 0 && ((uintptr_t)d_offsets & 7) == 0 && ((uintptr_t)d_tris & 3) == 0"
+    region_lists = "((uintptr_t)d_regions & 15) == 0 && ((uintptr_t)d_offsets & 7) == 0 && ((uintptr_t)d_tris & 3) == 0"
+    flags = " && ((uintptr_t)d_flags & 3) == 0"
+    plain_rays = bad + "((uintptr_t)d_rays & 15) == 0 && ((uintptr_t)d_out & (Q != kClosest ? 3 : 15)) == 0"
     return {
-        "lbvh_trace_closest": (rays, (), [hit]),
-        "lbvh_trace_occluded": (rays, (), [flag]),
-        "lbvh_count_hits": (rays, (), [flag]),
-        "lbvh_closest_point_query": (points, (), [cp]),
-        "lbvh_within_distance": (points, (), [flag]),
-        "lbvh_sphere_cast": (casts, (), [hit]),
-        "lbvh_sphere_cast_any": (casts, (), [flag]),
-        "lbvh_k_closest_points": (points, (K,), [(lay.CLOSEST_POINT, COUNT * K, 16), flag]),
-        "lbvh_trace_k_closest": (rays, (K,), [(lay.HIT, COUNT * K, 16), flag]),
-        "lbvh_box_overlaps": (boxes, (), csr),
-        "lbvh_gather_within_distance": (points, (), csr),
-        "lbvh_point_crossings": (points, (dirs.ctypes.data_as(C.POINTER(C.c_float)), len(dirs)), [flag]),
+        "lbvh_trace_closest": (rays, (), [hit], plain_rays),
+        "lbvh_trace_occluded": (rays, (), [flag], plain_rays),
+        "lbvh_count_hits": (rays, (), [flag], plain_rays),
+        "lbvh_closest_point_query": (points, (), [cp], bad + "((uintptr_t)d_queries & 15) == 0" + out_any),
+        "lbvh_within_distance": (points, (), [flag], bad + "((uintptr_t)d_queries & 15) == 0" + out_any),
+        "lbvh_sphere_cast": (casts, (), [hit], bad + "((uintptr_t)d_casts & 15) == 0" + out_any),
+        "lbvh_sphere_cast_any": (casts, (), [flag], bad + "((uintptr_t)d_casts & 15) == 0" + out_any),
+        "lbvh_k_closest_points": (points, (K,), [(lay.CLOSEST_POINT, COUNT * K, 16), flag],
+                                  bad + "((uintptr_t)d_queries & 15) == 0 && ((uintptr_t)d_out & 15) == 0" + found),
+        "lbvh_trace_k_closest": (rays, (K,), [(lay.HIT, COUNT * K, 16), flag],
+                                 bad + "((uintptr_t)d_rays & 15) == 0 && ((uintptr_t)d_hits & 15) == 0" + found),
+        "lbvh_box_overlaps": (boxes, (), csr, bad + lists),
+        "lbvh_gather_within_distance": (points, (), csr, bad + lists),
+        "lbvh_point_crossings": (points, (dirs.ctypes.data_as(C.POINTER(C.c_float)), len(dirs)), [flag],
+                                 bad + "((uintptr_t)d_points & 15) == 0 && ((uintptr_t)d_parity & 3) == 0"),
+        "lbvh_gather_hits": (rays, (), csr_hits,
+                             bad + "((uintptr_t)d_rays & 15) == 0 && ((uintptr_t)d_offsets & 7) == 0 && ((uintptr_t)d_hits & 15) == 0"),
+        "lbvh_triangle_intersections": (tri_queries, (), csr, bad + lists + flags),
+        "lbvh_triangle_intersects_any": (tri_queries, (), [flag], bad + lists + flags),
+        "lbvh_region_overlaps": (regions, touching, csr, "lbvh_region_overlaps: " + bad + region_lists + flags),
+        "lbvh_region_overlaps_any": (regions, touching, [flag], "lbvh_region_overlaps_any: " + bad + region_lists + flags),
+        # 130 regions: at or below LBVH_REGION_LARGE_MAX_COUNT (65 536), so the table's count stands.  The host gives each 16 384
+        # task slots (the largest power of two not above 2^22 / 130): 2 129 920 slots, 33 280 waves of them on the 8 192 launched
+        "lbvh_region_overlaps_large": (regions, touching, csr, "lbvh_region_overlaps_large: " + bad + region_lists),
+        "lbvh_capsule_cast": (capsules, (), [hit], bad + "((uintptr_t)d_casts & 15) == 0" + out_any),
+        "lbvh_capsule_cast_any": (capsules, (), [flag], bad + "((uintptr_t)d_casts & 15) == 0" + out_any),
     }, rays, dirs
 
 
 PLAIN_RAYS = ("lbvh_trace_closest", "lbvh_trace_occluded", "lbvh_count_hits")
 ENTRY_POINTS = PLAIN_RAYS + ("lbvh_closest_point_query", "lbvh_within_distance", "lbvh_sphere_cast", "lbvh_sphere_cast_any",
                              "lbvh_k_closest_points", "lbvh_trace_k_closest", "lbvh_box_overlaps", "lbvh_gather_within_distance",
-                             "lbvh_point_crossings")
+                             "lbvh_point_crossings", "lbvh_gather_hits", "lbvh_triangle_intersections", "lbvh_triangle_intersects_any",
+                             "lbvh_region_overlaps", "lbvh_region_overlaps_any", "lbvh_capsule_cast", "lbvh_capsule_cast_any",
+                             "lbvh_region_overlaps_large")                   # (last: its task slots grow the ray scratch)
 
 
 class Bench:
@@ -116,7 +153,8 @@ def bench():
 def test_entry_point_keeps_the_shared_contract(bench, name):
     nat, h, lib = N(), bench.ctx.handle, N().lib
     fn = getattr(lib, name)
-    queries, extra, outs = bench.table[name]
+    queries, extra, outs, misaligned = bench.table[name]
+    csr = outs[0][0] == np.uint64
     qb = H().DataBuffer(bench.ctx, COUNT + 1, queries.dtype)
     qb.local[:COUNT] = queries
     qb.sync()
@@ -126,7 +164,7 @@ def test_entry_point_keeps_the_shared_contract(bench, name):
 
     def call(count=COUNT, q=None, out0=None):
         ptrs = [out0 if out0 is not None else bufs[0].device] + [b.device for b in bufs[1:]]
-        if name in ("lbvh_box_overlaps", "lbvh_gather_within_distance"):
+        if csr:
             ptrs.append(bufs[1].size - 1)                                  # the capacity
         return fn(h, q if q is not None else qb.device, count, *extra, C.byref(s), *ptrs)
 
@@ -141,21 +179,24 @@ def test_entry_point_keeps_the_shared_contract(bench, name):
         poison()
         nat.check(h, call())
         got = [words(b.get_data()).copy() for b in bufs]
-        if len(outs) == 2 and outs[0][0] == np.uint64:                     # CSR: the triangle list as far as the last offset says
+        if csr:                                                            # the list as far as the last offset says
             total = int(bufs[0].local[COUNT])
             assert 0 < total <= bufs[1].size - 1
-            got[1] = got[1][:total]
+            got[1] = got[1][:total * (outs[1][0].itemsize // 4)]
         return got
 
     def same(a, b):
         return len(a) == len(b) and all(x.shape == y.shape and (x == y).all() for x, y in zip(a, b))
 
     try:
-        # count == 0 is a no-op; a misaligned query or output pointer is refused; nothing is written by either
+        # count == 0 is a no-op; a misaligned query or output pointer is refused with the family's own message; nothing is
+        # written by either
         poison()
         assert call(count=0) == 0
         assert call(q=at(qb, 4)) == -1
+        assert lib.lbvh_last_error(h) == misaligned.encode()
         assert call(out0=at(bufs[0], 4 if outs[0][2] > 4 else 2)) == -1
+        assert lib.lbvh_last_error(h) == misaligned.encode()
         assert untouched()
         # triangles uploaded without a rebuild: the derived scene is stale, and the message names this entry point
         bench.drawer.container.triangle_data.sync()

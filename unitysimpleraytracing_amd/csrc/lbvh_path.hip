@@ -2915,7 +2915,26 @@ static lbvh_status trace_plain_rays(lbvh_context* ctx, const lbvh_ray* d_rays, s
     return launch_ray_walk<true, Q>(ctx, d_rays, (uint32_t)count, nullptr, 0.0f, d_out, w);
 }
 
-// lbvh_closest_point_query / lbvh_within_distance: always the four-wide walk (lbvh_debug_ray_walker does not apply)
+// One record or flag per query, after the entry family's own argument checks: begin_walk, the one launch of the four-wide walk
+// (lbvh_debug_ray_walker does not apply), hipGetLastError.  The three walkers take the same arguments; the record type picks one.
+template <bool ANY, class QUERY, class OUT>
+static lbvh_status launch_per_query(lbvh_context* ctx, const QUERY* d_queries, size_t count, const lbvh_scene* h_scene, OUT* d_out, const char* who)
+{
+    walk_launch w;
+    const lbvh_status rc = begin_walk(ctx, h_scene, count, who, true, &w);
+    if (rc != LBVH_OK) return rc;
+#define PER_QUERY_WALK(kernel)                                                                                                     \
+    LBVH_LAUNCH_STATS(ctx, ctx->ray_stats, (kernel<ANY, STATS>), dim3(w.waves), dim3(LBVH_WAVE), d_queries, (uint32_t)count, w.wn, \
+                      ctx->fast_nodes, d_out, w.deep, w.lds, w.deep_cap, ctx->fault_dev, ctx->ray_stats)
+    if constexpr (std::is_same_v<QUERY, lbvh_point_query>) PER_QUERY_WALK(point_query_wide_kernel);
+    else if constexpr (std::is_same_v<QUERY, lbvh_sphere_ray>) PER_QUERY_WALK(sphere_cast_wide_kernel);
+    else PER_QUERY_WALK(capsule_cast_wide_kernel);
+#undef PER_QUERY_WALK
+    LBVH_HIP_TRY(ctx, hipGetLastError());
+    return LBVH_OK;
+}
+
+// lbvh_closest_point_query / lbvh_within_distance
 template <bool ANY>
 static lbvh_status point_queries(lbvh_context* ctx, const lbvh_point_query* d_queries, size_t count, const lbvh_scene* h_scene,
                                  std::conditional_t<ANY, uint32_t, lbvh_closest_point>* d_out, const char* who)
@@ -2925,56 +2944,54 @@ static lbvh_status point_queries(lbvh_context* ctx, const lbvh_point_query* d_qu
     LBVH_REQUIRE(ctx, d_queries != nullptr && h_scene != nullptr && d_out != nullptr);
     LBVH_REQUIRE(ctx, ((uintptr_t)d_queries & 15) == 0 && ((uintptr_t)d_out & (ANY ? 3 : 15)) == 0);
     LBVH_REQUIRE(ctx, count <= 0xFFFFFFFFull);
-    walk_launch w;
-    const lbvh_status rc = begin_walk(ctx, h_scene, count, who, true, &w);
-    if (rc != LBVH_OK) return rc;
-    LBVH_LAUNCH_STATS(ctx, ctx->ray_stats, (point_query_wide_kernel<ANY, STATS>), dim3(w.waves), dim3(LBVH_WAVE), d_queries, (uint32_t)count, w.wn,
-                      ctx->fast_nodes, d_out, w.deep, w.lds, w.deep_cap, ctx->fault_dev, ctx->ray_stats);
-    LBVH_HIP_TRY(ctx, hipGetLastError());
-    return LBVH_OK;
+    return launch_per_query<ANY>(ctx, d_queries, count, h_scene, d_out, who);
 }
 
-// lbvh_sphere_cast / lbvh_sphere_cast_any: always the four-wide walk (lbvh_debug_ray_walker does not apply), one launch
-template <bool ANY>
-static lbvh_status sphere_casts(lbvh_context* ctx, const lbvh_sphere_ray* d_casts, size_t count, const lbvh_scene* h_scene,
-                                std::conditional_t<ANY, uint32_t, lbvh_hit>* d_out, const char* who)
+// lbvh_sphere_cast / lbvh_sphere_cast_any (CAST = lbvh_sphere_ray), lbvh_capsule_cast / lbvh_capsule_cast_any (lbvh_capsule_ray)
+template <bool ANY, class CAST>
+static lbvh_status shape_casts(lbvh_context* ctx, const CAST* d_casts, size_t count, const lbvh_scene* h_scene,
+                               std::conditional_t<ANY, uint32_t, lbvh_hit>* d_out, const char* who)
 {
     if (!ctx) return LBVH_ERR_INVALID_ARG;
     if (count == 0) return LBVH_OK;
     LBVH_REQUIRE(ctx, d_casts != nullptr && h_scene != nullptr && d_out != nullptr);
     LBVH_REQUIRE(ctx, ((uintptr_t)d_casts & 15) == 0 && ((uintptr_t)d_out & (ANY ? 3 : 15)) == 0);
     LBVH_REQUIRE(ctx, count <= 0xFFFFFFFFull);
-    walk_launch w;
-    const lbvh_status rc = begin_walk(ctx, h_scene, count, who, true, &w);
-    if (rc != LBVH_OK) return rc;
-    LBVH_LAUNCH_STATS(ctx, ctx->ray_stats, (sphere_cast_wide_kernel<ANY, STATS>), dim3(w.waves), dim3(LBVH_WAVE), d_casts, (uint32_t)count, w.wn,
-                      ctx->fast_nodes, d_out, w.deep, w.lds, w.deep_cap, ctx->fault_dev, ctx->ray_stats);
-    LBVH_HIP_TRY(ctx, hipGetLastError());
-    return LBVH_OK;
+    return launch_per_query<ANY>(ctx, d_casts, count, h_scene, d_out, who);
 }
 
-// lbvh_capsule_cast / lbvh_capsule_cast_any: as sphere_casts, one launch
-template <bool ANY>
-static lbvh_status capsule_casts(lbvh_context* ctx, const lbvh_capsule_ray* d_casts, size_t count, const lbvh_scene* h_scene,
-                                 std::conditional_t<ANY, uint32_t, lbvh_hit>* d_out, const char* who)
+// The scan behind every CSR answer: the `slots` 32-bit counts a count walk left in slice 0 of the ray scratch (csr_counts) ->
+// their slots + 1 exclusive 64-bit offsets in d_offsets_out, the grand total last.  The counts (4 bytes per slot) and the tile
+// sums of the scan live where lbvh_trace_rays keeps its two live-ray lists: the ray scratch is sized for 8 bytes per slot there
+// (begin_walk with the same `slots`), and the list is dropped anyway.  The tiles cover slots + 1 offsets, 8 bytes per tile sum:
+// (slots / 1024 + 1) * 8 <= list_bytes(slots) = 4 * slots rounded up to 256, for every slots >= 1.  One tile needs no sums.
+static inline uint32_t* csr_counts(lbvh_context* ctx, size_t slots) { return ray_list(ctx, slots, 0); }
+static void csr_offsets(lbvh_context* ctx, size_t slots, uint64_t* d_offsets_out)
 {
-    if (!ctx) return LBVH_ERR_INVALID_ARG;
-    if (count == 0) return LBVH_OK;
-    LBVH_REQUIRE(ctx, d_casts != nullptr && h_scene != nullptr && d_out != nullptr);
-    LBVH_REQUIRE(ctx, ((uintptr_t)d_casts & 15) == 0 && ((uintptr_t)d_out & (ANY ? 3 : 15)) == 0);
-    LBVH_REQUIRE(ctx, count <= 0xFFFFFFFFull);
-    walk_launch w;
-    const lbvh_status rc = begin_walk(ctx, h_scene, count, who, true, &w);
-    if (rc != LBVH_OK) return rc;
-    LBVH_LAUNCH_STATS(ctx, ctx->ray_stats, (capsule_cast_wide_kernel<ANY, STATS>), dim3(w.waves), dim3(LBVH_WAVE), d_casts, (uint32_t)count, w.wn,
-                      ctx->fast_nodes, d_out, w.deep, w.lds, w.deep_cap, ctx->fault_dev, ctx->ray_stats);
+    const uint32_t total = (uint32_t)slots, n_tiles = total / kScanTile + 1u;
+    const uint32_t* counts = csr_counts(ctx, slots);
+    uint64_t* tile_sums = n_tiles > 1u ? (uint64_t*)ray_list(ctx, slots, 1) : nullptr;
+    if (tile_sums) {
+        LBVH_LAUNCH(ctx, overlap_tile_sums_kernel, dim3(n_tiles), dim3(256), counts, total, tile_sums);
+        LBVH_LAUNCH(ctx, overlap_scan_sums_kernel, dim3(1), dim3(1024), tile_sums, n_tiles);
+    }
+    LBVH_LAUNCH(ctx, overlap_offsets_kernel, dim3(n_tiles), dim3(256), counts, total, (const uint64_t*)tile_sums, d_offsets_out);
+}
+
+// A CSR answer on the caller's buffers, after begin_walk: count_walk(counts) launches the family's walk in its counting form,
+// the scan turns the counts into d_offsets, fill_walk() launches the filling form unless the call only counts.  All on the
+// context's stream, no host wait.
+template <class COUNT_WALK, class FILL_WALK>
+static lbvh_status csr_query(lbvh_context* ctx, size_t count, uint64_t* d_offsets, uint64_t capacity, COUNT_WALK count_walk, FILL_WALK fill_walk)
+{
+    count_walk(csr_counts(ctx, count));
+    csr_offsets(ctx, count, d_offsets);
+    if (capacity != 0) fill_walk();
     LBVH_HIP_TRY(ctx, hipGetLastError());
     return LBVH_OK;
 }
 
-// lbvh_box_overlaps / lbvh_gather_within_distance: count walk -> scan -> fill walk, all on the context's stream, no host wait.
-// The counts (4 bytes per query) and the tile sums of the scan live where lbvh_trace_rays keeps its two live-ray lists: the ray
-// scratch is sized for 8 bytes per query there, and the list is dropped anyway.
+// lbvh_box_overlaps / lbvh_gather_within_distance.  Four-wide walk only.
 template <bool BOX>
 static lbvh_status overlap_queries(lbvh_context* ctx, const void* d_queries, size_t count, const lbvh_scene* h_scene, uint64_t* d_offsets,
                                    uint32_t* d_tris, uint64_t capacity, const char* who)
@@ -2990,28 +3007,20 @@ static lbvh_status overlap_queries(lbvh_context* ctx, const void* d_queries, siz
     if (rc != LBVH_OK) return rc;
     const float4* q = (const float4*)d_queries;
     const uint32_t total = (uint32_t)count, leaf_base = ctx->fast_capacity;
-    uint32_t* counts = ray_list(ctx, count, 0);
-    uint64_t* tile_sums = (uint64_t*)ray_list(ctx, count, 1);
-    const uint32_t n_tiles = total / kScanTile + 1u;           // the tiles cover total + 1 offsets
-    // (8 bytes per tile sum: (count / 1024 + 1) * 8 <= list_bytes(count) = 4 * count rounded up to 256, for every count >= 1)
-    LBVH_LAUNCH_STATS(ctx, ctx->ray_stats, (overlap_wide_kernel<BOX, false, STATS>), dim3(w.waves), dim3(LBVH_WAVE), q, total, w.wn, ctx->fast_nodes, leaf_base,
-                      counts, (const uint64_t*)nullptr, (uint32_t*)nullptr, (uint64_t)0, w.deep, w.lds, w.deep_cap, ctx->fault_dev, ctx->ray_stats);
-    if (n_tiles > 1u) {
-        LBVH_LAUNCH(ctx, overlap_tile_sums_kernel, dim3(n_tiles), dim3(256), (const uint32_t*)counts, total, tile_sums);
-        LBVH_LAUNCH(ctx, overlap_scan_sums_kernel, dim3(1), dim3(1024), tile_sums, n_tiles);
-    }
-    LBVH_LAUNCH(ctx, overlap_offsets_kernel, dim3(n_tiles), dim3(256), (const uint32_t*)counts, total,
-                n_tiles > 1u ? (const uint64_t*)tile_sums : (const uint64_t*)nullptr, d_offsets);
-    if (capacity != 0)
-        LBVH_LAUNCH_STATS(ctx, ctx->ray_stats, (overlap_wide_kernel<BOX, true, STATS>), dim3(w.waves), dim3(LBVH_WAVE), q, total, w.wn, ctx->fast_nodes, leaf_base,
-                          (uint32_t*)nullptr, (const uint64_t*)d_offsets, d_tris, capacity, w.deep, w.lds, w.deep_cap, ctx->fault_dev, ctx->ray_stats);
-    LBVH_HIP_TRY(ctx, hipGetLastError());
-    return LBVH_OK;
+    return csr_query(
+        ctx, count, d_offsets, capacity,
+        [&](uint32_t* counts) {
+            LBVH_LAUNCH_STATS(ctx, ctx->ray_stats, (overlap_wide_kernel<BOX, false, STATS>), dim3(w.waves), dim3(LBVH_WAVE), q, total, w.wn, ctx->fast_nodes, leaf_base,
+                              counts, (const uint64_t*)nullptr, (uint32_t*)nullptr, (uint64_t)0, w.deep, w.lds, w.deep_cap, ctx->fault_dev, ctx->ray_stats);
+        },
+        [&] {
+            LBVH_LAUNCH_STATS(ctx, ctx->ray_stats, (overlap_wide_kernel<BOX, true, STATS>), dim3(w.waves), dim3(LBVH_WAVE), q, total, w.wn, ctx->fast_nodes, leaf_base,
+                              (uint32_t*)nullptr, (const uint64_t*)d_offsets, d_tris, capacity, w.deep, w.lds, w.deep_cap, ctx->fault_dev, ctx->ray_stats);
+        });
 }
 
-// lbvh_triangle_intersections: overlap_queries<>'s shape with the triangle walk (count walk -> the same three scan kernels -> fill
-// walk, counts and tile sums in the same two slices of the ray scratch); lbvh_triangle_intersects_any: one launch, the flags are the
-// walk's own output.  Four-wide walk only.
+// lbvh_triangle_intersections: a CSR answer; lbvh_triangle_intersects_any: one launch, the flags are the walk's own output.
+// Four-wide walk only.
 template <bool ANY>
 static lbvh_status triangle_queries(lbvh_context* ctx, const lbvh_tri_query* d_queries, size_t count, const lbvh_scene* h_scene, uint64_t* d_offsets,
                                     uint32_t* d_tris, uint64_t capacity, uint32_t* d_flags, const char* who)
@@ -3030,29 +3039,23 @@ static lbvh_status triangle_queries(lbvh_context* ctx, const lbvh_tri_query* d_q
     if constexpr (ANY) {
         LBVH_LAUNCH_STATS(ctx, ctx->ray_stats, (triangle_query_wide_kernel<kTriAny, STATS>), dim3(w.waves), dim3(LBVH_WAVE), q, total, w.wn, ctx->fast_nodes,
                           d_flags, (const uint64_t*)nullptr, (uint32_t*)nullptr, (uint64_t)0, w.deep, w.lds, w.deep_cap, ctx->fault_dev, ctx->ray_stats);
+        LBVH_HIP_TRY(ctx, hipGetLastError());
+        return LBVH_OK;
     } else {
-        uint32_t* counts = ray_list(ctx, count, 0);
-        uint64_t* tile_sums = (uint64_t*)ray_list(ctx, count, 1);
-        const uint32_t n_tiles = total / kScanTile + 1u;           // the tiles cover total + 1 offsets (sizes: see overlap_queries)
-        LBVH_LAUNCH_STATS(ctx, ctx->ray_stats, (triangle_query_wide_kernel<kTriCount, STATS>), dim3(w.waves), dim3(LBVH_WAVE), q, total, w.wn, ctx->fast_nodes,
-                          counts, (const uint64_t*)nullptr, (uint32_t*)nullptr, (uint64_t)0, w.deep, w.lds, w.deep_cap, ctx->fault_dev, ctx->ray_stats);
-        if (n_tiles > 1u) {
-            LBVH_LAUNCH(ctx, overlap_tile_sums_kernel, dim3(n_tiles), dim3(256), (const uint32_t*)counts, total, tile_sums);
-            LBVH_LAUNCH(ctx, overlap_scan_sums_kernel, dim3(1), dim3(1024), tile_sums, n_tiles);
-        }
-        LBVH_LAUNCH(ctx, overlap_offsets_kernel, dim3(n_tiles), dim3(256), (const uint32_t*)counts, total,
-                    n_tiles > 1u ? (const uint64_t*)tile_sums : (const uint64_t*)nullptr, d_offsets);
-        if (capacity != 0)
-            LBVH_LAUNCH_STATS(ctx, ctx->ray_stats, (triangle_query_wide_kernel<kTriFill, STATS>), dim3(w.waves), dim3(LBVH_WAVE), q, total, w.wn, ctx->fast_nodes,
-                              (uint32_t*)nullptr, (const uint64_t*)d_offsets, d_tris, capacity, w.deep, w.lds, w.deep_cap, ctx->fault_dev, ctx->ray_stats);
+        return csr_query(
+            ctx, count, d_offsets, capacity,
+            [&](uint32_t* counts) {
+                LBVH_LAUNCH_STATS(ctx, ctx->ray_stats, (triangle_query_wide_kernel<kTriCount, STATS>), dim3(w.waves), dim3(LBVH_WAVE), q, total, w.wn, ctx->fast_nodes,
+                                  counts, (const uint64_t*)nullptr, (uint32_t*)nullptr, (uint64_t)0, w.deep, w.lds, w.deep_cap, ctx->fault_dev, ctx->ray_stats);
+            },
+            [&] {
+                LBVH_LAUNCH_STATS(ctx, ctx->ray_stats, (triangle_query_wide_kernel<kTriFill, STATS>), dim3(w.waves), dim3(LBVH_WAVE), q, total, w.wn, ctx->fast_nodes,
+                                  (uint32_t*)nullptr, (const uint64_t*)d_offsets, d_tris, capacity, w.deep, w.lds, w.deep_cap, ctx->fault_dev, ctx->ray_stats);
+            });
     }
-    LBVH_HIP_TRY(ctx, hipGetLastError());
-    return LBVH_OK;
 }
 
-// lbvh_region_overlaps: triangle_queries<>'s shape with the region walk (count walk -> the same three scan kernels -> fill walk, counts
-// and tile sums in the same two slices of the ray scratch); lbvh_region_overlaps_any: one launch, the flags are the walk's own
-// output.  Four-wide walk only.
+// lbvh_region_overlaps: a CSR answer; lbvh_region_overlaps_any: one launch, the flags are the walk's own output.  Four-wide walk only.
 // (a rejection names the entry point, as the stale-scene message of begin_walk does)
 #define REGION_REQUIRE(cond)                                                                                        \
     do {                                                                                                            \
@@ -3077,24 +3080,20 @@ static lbvh_status region_queries(lbvh_context* ctx, const lbvh_region* d_region
     if constexpr (ANY) {
         LBVH_LAUNCH_STATS(ctx, ctx->ray_stats, (region_wide_kernel<kRegionAny, STATS>), dim3(w.waves), dim3(LBVH_WAVE), q, total, mode, w.wn, leaf_base,
                           d_flags, (const uint64_t*)nullptr, (uint32_t*)nullptr, (uint64_t)0, w.deep, w.lds, w.deep_cap, ctx->fault_dev, ctx->ray_stats);
+        LBVH_HIP_TRY(ctx, hipGetLastError());
+        return LBVH_OK;
     } else {
-        uint32_t* counts = ray_list(ctx, count, 0);
-        uint64_t* tile_sums = (uint64_t*)ray_list(ctx, count, 1);
-        const uint32_t n_tiles = total / kScanTile + 1u;           // the tiles cover total + 1 offsets (sizes: see overlap_queries)
-        LBVH_LAUNCH_STATS(ctx, ctx->ray_stats, (region_wide_kernel<kRegionCount, STATS>), dim3(w.waves), dim3(LBVH_WAVE), q, total, mode, w.wn, leaf_base,
-                          counts, (const uint64_t*)nullptr, (uint32_t*)nullptr, (uint64_t)0, w.deep, w.lds, w.deep_cap, ctx->fault_dev, ctx->ray_stats);
-        if (n_tiles > 1u) {
-            LBVH_LAUNCH(ctx, overlap_tile_sums_kernel, dim3(n_tiles), dim3(256), (const uint32_t*)counts, total, tile_sums);
-            LBVH_LAUNCH(ctx, overlap_scan_sums_kernel, dim3(1), dim3(1024), tile_sums, n_tiles);
-        }
-        LBVH_LAUNCH(ctx, overlap_offsets_kernel, dim3(n_tiles), dim3(256), (const uint32_t*)counts, total,
-                    n_tiles > 1u ? (const uint64_t*)tile_sums : (const uint64_t*)nullptr, d_offsets);
-        if (capacity != 0)
-            LBVH_LAUNCH_STATS(ctx, ctx->ray_stats, (region_wide_kernel<kRegionFill, STATS>), dim3(w.waves), dim3(LBVH_WAVE), q, total, mode, w.wn, leaf_base,
-                              (uint32_t*)nullptr, (const uint64_t*)d_offsets, d_tris, capacity, w.deep, w.lds, w.deep_cap, ctx->fault_dev, ctx->ray_stats);
+        return csr_query(
+            ctx, count, d_offsets, capacity,
+            [&](uint32_t* counts) {
+                LBVH_LAUNCH_STATS(ctx, ctx->ray_stats, (region_wide_kernel<kRegionCount, STATS>), dim3(w.waves), dim3(LBVH_WAVE), q, total, mode, w.wn, leaf_base,
+                                  counts, (const uint64_t*)nullptr, (uint32_t*)nullptr, (uint64_t)0, w.deep, w.lds, w.deep_cap, ctx->fault_dev, ctx->ray_stats);
+            },
+            [&] {
+                LBVH_LAUNCH_STATS(ctx, ctx->ray_stats, (region_wide_kernel<kRegionFill, STATS>), dim3(w.waves), dim3(LBVH_WAVE), q, total, mode, w.wn, leaf_base,
+                                  (uint32_t*)nullptr, (const uint64_t*)d_offsets, d_tris, capacity, w.deep, w.lds, w.deep_cap, ctx->fault_dev, ctx->ray_stats);
+            });
     }
-    LBVH_HIP_TRY(ctx, hipGetLastError());
-    return LBVH_OK;
 }
 
 // tasks per region of lbvh_region_overlaps_large: the largest power of two not above min(kRegionTaskCapMax, kRegionTaskSlots / count),
@@ -3110,9 +3109,8 @@ static uint32_t region_task_cap_of(uint32_t forced, size_t count)
 }
 
 // lbvh_region_overlaps_large: region_queries<false>'s shape over count * task_cap task slots — expansion -> task count walk -> the
-// same three scan kernels over the per-task counts into the task offsets -> d_offsets picked from them -> task fill walk.  The
-// counts and tile sums live in the two slices of the ray scratch, sized for the slots; the task array, its twin and the slots + 1
-// task offsets in a context buffer of their own.
+// scan over the per-task counts into the task offsets -> d_offsets picked from them -> task fill walk.  The ray scratch is sized
+// for the slots; the task array, its twin and the slots + 1 task offsets live in a context buffer of their own.
 static lbvh_status region_queries_large(lbvh_context* ctx, const lbvh_region* d_regions, size_t count, uint32_t mode, const lbvh_scene* h_scene,
                                         uint64_t* d_offsets, uint32_t* d_tris, uint64_t capacity, const char* who)
 {
@@ -3136,20 +3134,12 @@ static lbvh_status region_queries_large(lbvh_context* ctx, const lbvh_region* d_
     uint64_t* task_offsets = (uint64_t*)((char*)ctx->region_tasks + 2 * slice);
     const float4* q = (const float4*)d_regions;
     const uint32_t total = (uint32_t)slots, leaf_base = ctx->fast_capacity;
-    uint32_t* counts = ray_list(ctx, slots, 0);
-    uint64_t* tile_sums = (uint64_t*)ray_list(ctx, slots, 1);
-    const uint32_t n_tiles = total / kScanTile + 1u;           // the tiles cover total + 1 offsets (sizes: see overlap_queries)
     LBVH_LAUNCH_STATS(ctx, ctx->ray_stats, (region_expand_kernel<STATS>), dim3((uint32_t)count), dim3(256), q, mode, w.wn, task_cap, tasks, twin,
                       ctx->ray_stats);
     LBVH_LAUNCH_STATS(ctx, ctx->ray_stats, (region_task_wide_kernel<kRegionCount, STATS>), dim3(w.waves), dim3(LBVH_WAVE), q, total, task_cap,
-                      (const uint32_t*)tasks, mode, w.wn, leaf_base, counts, (const uint64_t*)nullptr, (uint32_t*)nullptr, (uint64_t)0, w.deep, w.lds,
-                      w.deep_cap, ctx->fault_dev, ctx->ray_stats);
-    if (n_tiles > 1u) {
-        LBVH_LAUNCH(ctx, overlap_tile_sums_kernel, dim3(n_tiles), dim3(256), (const uint32_t*)counts, total, tile_sums);
-        LBVH_LAUNCH(ctx, overlap_scan_sums_kernel, dim3(1), dim3(1024), tile_sums, n_tiles);
-    }
-    LBVH_LAUNCH(ctx, overlap_offsets_kernel, dim3(n_tiles), dim3(256), (const uint32_t*)counts, total,
-                n_tiles > 1u ? (const uint64_t*)tile_sums : (const uint64_t*)nullptr, task_offsets);
+                      (const uint32_t*)tasks, mode, w.wn, leaf_base, csr_counts(ctx, slots), (const uint64_t*)nullptr, (uint32_t*)nullptr, (uint64_t)0,
+                      w.deep, w.lds, w.deep_cap, ctx->fault_dev, ctx->ray_stats);
+    csr_offsets(ctx, slots, task_offsets);
     LBVH_LAUNCH(ctx, region_offsets_kernel, dim3((uint32_t)(count / 256 + 1)), dim3(256), (const uint64_t*)task_offsets, task_cap, (uint32_t)count,
                 d_offsets);
     if (capacity != 0)
@@ -3225,22 +3215,22 @@ lbvh_status lbvh_trace_k_closest(lbvh_context* ctx, const lbvh_ray* d_rays, size
 
 lbvh_status lbvh_sphere_cast(lbvh_context* ctx, const lbvh_sphere_ray* d_casts, size_t count, const lbvh_scene* h_scene, lbvh_hit* d_hits)
 {
-    return sphere_casts<false>(ctx, d_casts, count, h_scene, d_hits, "lbvh_sphere_cast");
+    return shape_casts<false>(ctx, d_casts, count, h_scene, d_hits, "lbvh_sphere_cast");
 }
 
 lbvh_status lbvh_sphere_cast_any(lbvh_context* ctx, const lbvh_sphere_ray* d_casts, size_t count, const lbvh_scene* h_scene, uint32_t* d_flags)
 {
-    return sphere_casts<true>(ctx, d_casts, count, h_scene, d_flags, "lbvh_sphere_cast_any");
+    return shape_casts<true>(ctx, d_casts, count, h_scene, d_flags, "lbvh_sphere_cast_any");
 }
 
 lbvh_status lbvh_capsule_cast(lbvh_context* ctx, const lbvh_capsule_ray* d_casts, size_t count, const lbvh_scene* h_scene, lbvh_hit* d_hits)
 {
-    return capsule_casts<false>(ctx, d_casts, count, h_scene, d_hits, "lbvh_capsule_cast");
+    return shape_casts<false>(ctx, d_casts, count, h_scene, d_hits, "lbvh_capsule_cast");
 }
 
 lbvh_status lbvh_capsule_cast_any(lbvh_context* ctx, const lbvh_capsule_ray* d_casts, size_t count, const lbvh_scene* h_scene, uint32_t* d_flags)
 {
-    return capsule_casts<true>(ctx, d_casts, count, h_scene, d_flags, "lbvh_capsule_cast_any");
+    return shape_casts<true>(ctx, d_casts, count, h_scene, d_flags, "lbvh_capsule_cast_any");
 }
 
 // the four-wide walk only (lbvh_debug_ray_walker does not apply), the directions by value in the arguments
@@ -3313,8 +3303,7 @@ lbvh_status lbvh_gather_within_distance(lbvh_context* ctx, const lbvh_point_quer
     return overlap_queries<false>(ctx, d_queries, count, h_scene, d_offsets, d_tris, capacity, "lbvh_gather_within_distance");
 }
 
-// overlap_queries<>'s shape with the ray walk: count walk -> the same three scan kernels -> fill walk, the counts and the tile sums
-// in the same two slices of the ray scratch, all on the context's stream, no host wait.  Four-wide walk only.
+// a CSR answer of hit records.  Four-wide walk only.
 lbvh_status lbvh_gather_hits(lbvh_context* ctx, const lbvh_ray* d_rays, size_t count, const lbvh_scene* h_scene, uint64_t* d_offsets,
                              lbvh_hit* d_hits, uint64_t capacity)
 {
@@ -3328,22 +3317,16 @@ lbvh_status lbvh_gather_hits(lbvh_context* ctx, const lbvh_ray* d_rays, size_t c
     const lbvh_status rc = begin_walk(ctx, h_scene, count, "lbvh_gather_hits", true, &w);
     if (rc != LBVH_OK) return rc;
     const uint32_t total = (uint32_t)count;
-    uint32_t* counts = ray_list(ctx, count, 0);
-    uint64_t* tile_sums = (uint64_t*)ray_list(ctx, count, 1);
-    const uint32_t n_tiles = total / kScanTile + 1u;           // the tiles cover total + 1 offsets (sizes: see overlap_queries)
-    LBVH_LAUNCH_STATS(ctx, ctx->ray_stats, (gather_hits_wide_kernel<false, STATS>), dim3(w.waves), dim3(LBVH_WAVE), d_rays, total, w.wn, ctx->fast_nodes,
-                      counts, (const uint64_t*)nullptr, (lbvh_hit*)nullptr, (uint64_t)0, w.deep, w.lds, w.deep_cap, ctx->fault_dev, ctx->ray_stats);
-    if (n_tiles > 1u) {
-        LBVH_LAUNCH(ctx, overlap_tile_sums_kernel, dim3(n_tiles), dim3(256), (const uint32_t*)counts, total, tile_sums);
-        LBVH_LAUNCH(ctx, overlap_scan_sums_kernel, dim3(1), dim3(1024), tile_sums, n_tiles);
-    }
-    LBVH_LAUNCH(ctx, overlap_offsets_kernel, dim3(n_tiles), dim3(256), (const uint32_t*)counts, total,
-                n_tiles > 1u ? (const uint64_t*)tile_sums : (const uint64_t*)nullptr, d_offsets);
-    if (capacity != 0)
-        LBVH_LAUNCH_STATS(ctx, ctx->ray_stats, (gather_hits_wide_kernel<true, STATS>), dim3(w.waves), dim3(LBVH_WAVE), d_rays, total, w.wn, ctx->fast_nodes,
-                          (uint32_t*)nullptr, (const uint64_t*)d_offsets, d_hits, capacity, w.deep, w.lds, w.deep_cap, ctx->fault_dev, ctx->ray_stats);
-    LBVH_HIP_TRY(ctx, hipGetLastError());
-    return LBVH_OK;
+    return csr_query(
+        ctx, count, d_offsets, capacity,
+        [&](uint32_t* counts) {
+            LBVH_LAUNCH_STATS(ctx, ctx->ray_stats, (gather_hits_wide_kernel<false, STATS>), dim3(w.waves), dim3(LBVH_WAVE), d_rays, total, w.wn, ctx->fast_nodes,
+                              counts, (const uint64_t*)nullptr, (lbvh_hit*)nullptr, (uint64_t)0, w.deep, w.lds, w.deep_cap, ctx->fault_dev, ctx->ray_stats);
+        },
+        [&] {
+            LBVH_LAUNCH_STATS(ctx, ctx->ray_stats, (gather_hits_wide_kernel<true, STATS>), dim3(w.waves), dim3(LBVH_WAVE), d_rays, total, w.wn, ctx->fast_nodes,
+                              (uint32_t*)nullptr, (const uint64_t*)d_offsets, d_hits, capacity, w.deep, w.lds, w.deep_cap, ctx->fault_dev, ctx->ray_stats);
+        });
 }
 
 lbvh_status lbvh_animate(lbvh_context* ctx, const lbvh_triangle* d_rest, uint32_t n, const uint32_t* d_body,

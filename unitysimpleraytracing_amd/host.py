@@ -449,34 +449,30 @@ class RaytracingMeshDrawer:
     def trace_closest(self, rays, hits):
         """Closest hit of each ray of the DataBuffer `rays` (layouts.RAY: origin, t_min, dir, t_max) into the DataBuffer `hits`
         (layouts.HIT), over the derived scene (awake(fast=True) / rebuild(fast=True)).  Asynchronous; read with hits.get_data()."""
-        self._trace_plain(N.lib.lbvh_trace_closest, rays, hits, L.HIT)
+        self._per_query(N.lib.lbvh_trace_closest, rays, "RAY", hits, L.HIT, "rays")
 
     def trace_occluded(self, rays, flags):
         """1 into the uint32 DataBuffer `flags` for each ray of `rays` that meets anything in (t_min, t_max), else 0."""
-        self._trace_plain(N.lib.lbvh_trace_occluded, rays, flags, np.dtype(np.uint32))
+        self._per_query(N.lib.lbvh_trace_occluded, rays, "RAY", flags, np.uint32, "rays")
 
-    def _trace_plain(self, fn, rays, out, dtype):
-        if rays.dtype != L.RAY or out.dtype != dtype or out.size < rays.size:
-            raise ValueError(f"rays must be a DataBuffer of layouts.RAY and the output one of {dtype} with at least as many entries")
+    def _per_query(self, fn, queries, layout, out, dtype, noun, out_noun="the output"):
+        """One record or flag per query: fn(ctx, queries, count, scene, out) on a DataBuffer of layouts.<layout> (`noun` in the
+        message) and one of `dtype` that holds as many entries."""
+        if queries.dtype != getattr(L, layout) or out.dtype != dtype or out.size < queries.size:
+            raise ValueError(f"{noun} must be a DataBuffer of layouts.{layout} and {out_noun} one of {np.dtype(dtype)} with at least as many entries")
         s = self.container.scene()
-        N.check(self.ctx.handle, fn(self.ctx.handle, rays.device, rays.size, C.byref(s), out.device))
+        N.check(self.ctx.handle, fn(self.ctx.handle, queries.device, queries.size, C.byref(s), out.device))
 
     def sphere_cast(self, casts, hits):
         """First contact of each moving sphere of the DataBuffer `casts` (layouts.SPHERE_RAY: origin, radius, dir, t_max) with the
         mesh into the DataBuffer `hits` (layouts.HIT: t, tri, and the barycentrics u, v of the contact point), over the derived
         scene.  The centre is at origin + dir * t; no contact in [0, t_max): the miss record.  Asynchronous; read with
         hits.get_data()."""
-        self._sphere_casts(N.lib.lbvh_sphere_cast, casts, hits, L.HIT)
+        self._per_query(N.lib.lbvh_sphere_cast, casts, "SPHERE_RAY", hits, L.HIT, "casts")
 
     def sphere_cast_any(self, casts, flags):
         """1 into the uint32 DataBuffer `flags` for each sphere of `casts` that touches anything on its way, else 0."""
-        self._sphere_casts(N.lib.lbvh_sphere_cast_any, casts, flags, np.dtype(np.uint32))
-
-    def _sphere_casts(self, fn, casts, out, dtype):
-        if casts.dtype != L.SPHERE_RAY or out.dtype != dtype or out.size < casts.size:
-            raise ValueError(f"casts must be a DataBuffer of layouts.SPHERE_RAY and the output one of {dtype} with at least as many entries")
-        s = self.container.scene()
-        N.check(self.ctx.handle, fn(self.ctx.handle, casts.device, casts.size, C.byref(s), out.device))
+        self._per_query(N.lib.lbvh_sphere_cast_any, casts, "SPHERE_RAY", flags, np.uint32, "casts")
 
     def capsule_cast(self, casts, hits):
         """First contact of each moving capsule of the DataBuffer `casts` (layouts.CAPSULE_RAY: origin, radius, dir, t_max, axis —
@@ -484,32 +480,20 @@ class RaytracingMeshDrawer:
         DataBuffer `hits` (layouts.HIT: t, tri, and the barycentrics u, v of the contact point on the triangle), over the derived
         scene.  The axis starts at origin + dir * t; no contact in [0, t_max): the miss record.  Asynchronous; read with
         hits.get_data()."""
-        self._capsule_casts(N.lib.lbvh_capsule_cast, casts, hits, L.HIT)
+        self._per_query(N.lib.lbvh_capsule_cast, casts, "CAPSULE_RAY", hits, L.HIT, "casts")
 
     def capsule_cast_any(self, casts, flags):
         """1 into the uint32 DataBuffer `flags` for each capsule of `casts` that touches anything on its way, else 0."""
-        self._capsule_casts(N.lib.lbvh_capsule_cast_any, casts, flags, np.dtype(np.uint32))
-
-    def _capsule_casts(self, fn, casts, out, dtype):
-        if casts.dtype != L.CAPSULE_RAY or out.dtype != dtype or out.size < casts.size:
-            raise ValueError(f"casts must be a DataBuffer of layouts.CAPSULE_RAY and the output one of {dtype} with at least as many entries")
-        s = self.container.scene()
-        N.check(self.ctx.handle, fn(self.ctx.handle, casts.device, casts.size, C.byref(s), out.device))
+        self._per_query(N.lib.lbvh_capsule_cast_any, casts, "CAPSULE_RAY", flags, np.uint32, "casts")
 
     def closest_points(self, queries, out):
         """Nearest triangle of each point of the DataBuffer `queries` (layouts.POINT_QUERY: p, max_dist2) into the DataBuffer `out`
         (layouts.CLOSEST_POINT: dist2, tri, u, v), over the derived scene.  Asynchronous; read with out.get_data()."""
-        self._point_queries(N.lib.lbvh_closest_point_query, queries, out, L.CLOSEST_POINT)
+        self._per_query(N.lib.lbvh_closest_point_query, queries, "POINT_QUERY", out, L.CLOSEST_POINT, "queries")
 
     def within_distance(self, queries, flags):
         """1 into the uint32 DataBuffer `flags` for each point of `queries` with a triangle nearer than sqrt(max_dist2), else 0."""
-        self._point_queries(N.lib.lbvh_within_distance, queries, flags, np.dtype(np.uint32))
-
-    def _point_queries(self, fn, queries, out, dtype):
-        if queries.dtype != L.POINT_QUERY or out.dtype != dtype or out.size < queries.size:
-            raise ValueError(f"queries must be a DataBuffer of layouts.POINT_QUERY and the output one of {dtype} with at least as many entries")
-        s = self.container.scene()
-        N.check(self.ctx.handle, fn(self.ctx.handle, queries.device, queries.size, C.byref(s), out.device))
+        self._per_query(N.lib.lbvh_within_distance, queries, "POINT_QUERY", flags, np.uint32, "queries")
 
     def k_closest_points(self, queries, k, out, found=None):
         """The k nearest triangles (1 <= k <= 32) of each point of `queries` (layouts.POINT_QUERY) into the DataBuffer `out`
@@ -552,7 +536,8 @@ class RaytracingMeshDrawer:
         device_sort=True issues sort_index_segments before the download: every segment ascending."""
         return self._csr_lists(self.box_overlaps if queries.dtype == L.AABB else self.gather_within_distance, queries, min_capacity, device_sort)
 
-    def _csr_lists(self, call, queries, min_capacity, device_sort):
+    def _csr_lists(self, call, queries, min_capacity, device_sort, dtype=np.uint32, segment_sort=sort_index_segments):
+        """count -> one 8-byte download -> allocate -> fill -> (device_sort: segment_sort on the device) -> (offsets, records of `dtype`)"""
         count = queries.size
         offsets = DataBuffer(self.ctx, count + 1, np.uint64)
         try:
@@ -561,14 +546,14 @@ class RaytracingMeshDrawer:
             N.check(self.ctx.handle, N.lib.lbvh_buffer_download(self.ctx.handle, last.ctypes.data_as(C.c_void_p),
                                                                 C.c_void_p(offsets.device.value + 8 * count), 8))
             total = int(last[0])
-            tris = DataBuffer(self.ctx, max(total, int(min_capacity)), np.uint32)
+            records = DataBuffer(self.ctx, max(total, int(min_capacity)), dtype)
             try:
-                call(queries, offsets, tris)
+                call(queries, offsets, records)
                 if device_sort:
-                    sort_index_segments(self.ctx, offsets, tris, count)
-                return offsets.get_data().copy(), tris.get_data()[:total].copy()
+                    segment_sort(self.ctx, offsets, records, count)
+                return offsets.get_data().copy(), records.get_data()[:total].copy()
             finally:
-                tris.dispose()
+                records.dispose()
         finally:
             offsets.dispose()
 
@@ -582,10 +567,7 @@ class RaytracingMeshDrawer:
 
     def triangle_intersects_any(self, queries, flags):
         """1 into the uint32 DataBuffer `flags` for each triangle of `queries` that intersects any scene triangle, else 0."""
-        if queries.dtype != L.TRI_QUERY or flags.dtype != np.uint32 or flags.size < queries.size:
-            raise ValueError("queries must be a DataBuffer of layouts.TRI_QUERY and flags one of uint32 with at least as many entries")
-        s = self.container.scene()
-        N.check(self.ctx.handle, N.lib.lbvh_triangle_intersects_any(self.ctx.handle, queries.device, queries.size, C.byref(s), flags.device))
+        self._per_query(N.lib.lbvh_triangle_intersects_any, queries, "TRI_QUERY", flags, np.uint32, "queries", "flags")
 
     def intersections(self, queries, min_capacity=1, device_sort=False):
         """Convenience, as overlaps(): count -> one 8-byte download -> allocate -> fill, for a DataBuffer of layouts.TRI_QUERY.
@@ -615,12 +597,9 @@ class RaytracingMeshDrawer:
 
     def region_overlaps_any(self, regions, mode, flags):
         """1 into the uint32 DataBuffer `flags` for each region of `regions` that has a candidate in `mode`, else 0."""
-        if regions.dtype != L.REGION or flags.dtype != np.uint32 or flags.size < regions.size:
-            raise ValueError("regions must be a DataBuffer of layouts.REGION and flags one of uint32 with at least as many entries")
         if mode not in (L.REGION_TOUCHING, L.REGION_CONTAINED):
             raise ValueError("mode must be layouts.REGION_TOUCHING or layouts.REGION_CONTAINED")
-        s = self.container.scene()
-        N.check(self.ctx.handle, N.lib.lbvh_region_overlaps_any(self.ctx.handle, regions.device, regions.size, mode, C.byref(s), flags.device))
+        self._per_query(lambda h, q, n, s, f: N.lib.lbvh_region_overlaps_any(h, q, n, mode, s, f), regions, "REGION", flags, np.uint32, "regions", "flags")
 
     def in_regions(self, regions, mode=L.REGION_TOUCHING, min_capacity=1, device_sort=False, large=False):
         """Convenience, as overlaps(): count -> one 8-byte download -> allocate -> fill, for a DataBuffer of layouts.REGION.
@@ -632,7 +611,7 @@ class RaytracingMeshDrawer:
     def count_hits(self, rays, counts):
         """The number of candidates of each ray of `rays` (layouts.RAY) in (t_min, t_max) into the uint32 DataBuffer `counts`: every
         triangle crossed counts, two at the same t count 2.  Asynchronous."""
-        self._trace_plain(N.lib.lbvh_count_hits, rays, counts, np.dtype(np.uint32))
+        self._per_query(N.lib.lbvh_count_hits, rays, "RAY", counts, np.uint32, "rays")
 
     def trace_k_closest(self, rays, k, hits, found=None):
         """The first k hits (1 <= k <= 32) along each ray of `rays` (layouts.RAY) into the DataBuffer `hits` (layouts.HIT, at least
@@ -667,26 +646,9 @@ class RaytracingMeshDrawer:
         and layouts.HIT[total].  The library leaves a segment in the order of its walk; sort=True orders every segment by
         (t, tri) HERE, ON THE HOST (np.lexsort over the downloaded records — not a device sort).  device_sort=True issues
         sort_hit_segments before the download instead: the same order, made on the device."""
-        count = rays.size
-        offsets = DataBuffer(self.ctx, count + 1, np.uint64)
-        try:
-            self.gather_hits(rays, offsets)
-            last = np.zeros(1, dtype=np.uint64)
-            N.check(self.ctx.handle, N.lib.lbvh_buffer_download(self.ctx.handle, last.ctypes.data_as(C.c_void_p),
-                                                                C.c_void_p(offsets.device.value + 8 * count), 8))
-            total = int(last[0])
-            hits = DataBuffer(self.ctx, max(total, int(min_capacity)), L.HIT)
-            try:
-                self.gather_hits(rays, offsets, hits)
-                if device_sort:
-                    sort_hit_segments(self.ctx, offsets, hits, count)
-                off, rec = offsets.get_data().copy(), hits.get_data()[:total].copy()
-            finally:
-                hits.dispose()
-        finally:
-            offsets.dispose()
+        off, rec = self._csr_lists(self.gather_hits, rays, min_capacity, device_sort, L.HIT, sort_hit_segments)
         if sort:
-            segment = np.repeat(np.arange(count), np.diff(off).astype(np.int64))
+            segment = np.repeat(np.arange(rays.size), np.diff(off).astype(np.int64))
             rec = rec[np.lexsort((rec["tri"], rec["t"], segment))]
         return off, rec
 
