@@ -39,6 +39,14 @@ public static class LbvhNative
     [StructLayout(LayoutKind.Sequential)]
     public struct CapsuleRay { public float originX, originY, originZ, radius; public float dirX, dirY, dirZ, tMax; public float axisX, axisY, axisZ; public uint pad; }
 
+    // lbvh_box_ray / lbvh_box_hit (include/lbvh.h): a moving box, 80 bytes: the centre, tMax, dir and three half-axis vectors (the box is
+    // centre + s0*ax + s1*ay + s2*az, |s_i| <= 1; the pads are not read), and its record, 16 bytes: axis = the separating axis that
+    // gave the time, 13 = overlapping at the start (BoxCasts.cs)
+    [StructLayout(LayoutKind.Sequential)]
+    public struct BoxRay { public float centreX, centreY, centreZ, tMax; public float dirX, dirY, dirZ; public uint pad0; public float axX, axY, axZ; public uint pad1; public float ayX, ayY, ayZ; public uint pad2; public float azX, azY, azZ; public uint pad3; }
+    [StructLayout(LayoutKind.Sequential)]
+    public struct BoxHit { public float t; public uint tri; public uint axis; public uint zero; }
+
     // lbvh_point_query / lbvh_closest_point (include/lbvh.h): a point with its squared search radius (active iff maxDist2 > 0) and
     // the nearest triangle's record, 16 bytes each (PointQueries.cs)
     [StructLayout(LayoutKind.Sequential)]
@@ -155,6 +163,8 @@ public static class LbvhNative
     [DllImport(Lib)] public static extern int lbvh_sphere_cast_any(IntPtr ctx, IntPtr dCasts, UIntPtr count, ref Scene scene, IntPtr dFlags);
     [DllImport(Lib)] public static extern int lbvh_capsule_cast(IntPtr ctx, IntPtr dCasts, UIntPtr count, ref Scene scene, IntPtr dHits);
     [DllImport(Lib)] public static extern int lbvh_capsule_cast_any(IntPtr ctx, IntPtr dCasts, UIntPtr count, ref Scene scene, IntPtr dFlags);
+    [DllImport(Lib)] public static extern int lbvh_box_cast(IntPtr ctx, IntPtr dCasts, UIntPtr count, ref Scene scene, IntPtr dHits);
+    [DllImport(Lib)] public static extern int lbvh_box_cast_any(IntPtr ctx, IntPtr dCasts, UIntPtr count, ref Scene scene, IntPtr dFlags);
     [DllImport(Lib)] public static extern int lbvh_triangle_intersections(IntPtr ctx, IntPtr dQueries, UIntPtr count, ref Scene scene, IntPtr dOffsets,
         IntPtr dTris, ulong capacity);
     [DllImport(Lib)] public static extern int lbvh_triangle_intersects_any(IntPtr ctx, IntPtr dQueries, UIntPtr count, ref Scene scene, IntPtr dFlags);

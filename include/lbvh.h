@@ -990,6 +990,86 @@ lbvh_status lbvh_capsule_cast(lbvh_context* ctx, const lbvh_capsule_ray* d_casts
 lbvh_status lbvh_capsule_cast_any(lbvh_context* ctx, const lbvh_capsule_ray* d_casts, size_t count, const lbvh_scene* h_scene,
                                   uint32_t* d_flags);
 
+/* A moving box: 80 bytes, arrays 16-byte aligned. */
+typedef struct lbvh_box_ray {
+    float centre[3]; float t_max;
+    float dir[3];    uint32_t _pad0;
+    float ax[3];     uint32_t _pad1;   /* three half-axis vectors: the box is                */
+    float ay[3];     uint32_t _pad2;   /* { centre + s0*ax + s1*ay + s2*az : |s_i| <= 1 }   */
+    float az[3];     uint32_t _pad3;   /* pads are not read                                  */
+} lbvh_box_ray;
+
+/* lbvh_box_cast's record, 16 bytes: the time, the ORIGINAL triangle index and the separating axis that gave the time. */
+typedef struct lbvh_box_hit { float t; uint32_t tri; uint32_t axis; uint32_t _zero; } lbvh_box_hit;
+
+#define LBVH_BOX_AXIS_START 13u   /* lbvh_box_hit.axis of a box that overlaps the triangle at the start (t = +0) */
+
+/* First contact of `count` moving boxes with the mesh (a "box cast": crates, hulls, doors, placement previews), over the derived
+ * traversal scene in its four-wide form by the walk of lbvh_sphere_cast.  The half-axis VECTORS make the box: three orthogonal
+ * ones an oriented box, three axis-aligned ones an AABB, any three independent ones a sheared box (a parallelepiped) — nothing
+ * below assumes orthogonality and nothing is normalised.  The box moves without turning: c(t) = centre + dir * t for 0 <= t < T,
+ * T = min(t_max, LBVH_MAX_FLOAT); dir need not be unit length and t is in units of dir.
+ *   Active cast: the conditions of lbvh_sphere_cast on t_max, centre (for its origin) and dir; every component of ax, ay, az
+ *   finite; and the fp32 value det = dot(ax, cross(ay, az)) finite and != 0 (the box is solid; flat boxes are out of scope).  An
+ *   inactive cast is never walked; it gets the miss record {LBVH_MAX_FLOAT, 0, 0, 0} (lbvh_box_cast) or 0 (lbvh_box_cast_any).
+ *   Time of contact with one triangle: a swept separating-axis test on a, e1, e2 of the triangle's line of the derived scene, in
+ *   strict fp32, every operation rounded on its own, dot and cross as at lbvh_sphere_cast, / correctly rounded, min and max as
+ *   fminf and fmaxf (of a NaN and a number: the number), |x| exact.  With b_0, b_1, b_2 = ax, ay, az and E_0, E_1, E_2 = e1, e2,
+ *   e2 - e1 (per component), the thirteen axes L_j in this order:
+ *     j = 0            cross(e1, e2)                                      the triangle's face
+ *     j = 1, 2, 3      cross(ay, az), cross(az, ax), cross(ax, ay)        the box's faces
+ *     j = 4 + 3*i + k  cross(b_i, E_k), i = 0 .. 2, k = 0 .. 2            a box edge against a triangle edge
+ *   Per axis, with L = L_j:
+ *     m = a - centre (per component)   p0 = dot(m, L)   p1 = p0 + dot(e1, L)   p2 = p0 + dot(e2, L)
+ *     lo = min(p0, min(p1, p2))   hi = max(p0, max(p1, p2))           the triangle's interval, from the box's centre
+ *     rb = (|dot(ax, L)| + |dot(ay, L)|) + |dot(az, L)|                the box's half width
+ *     v = dot(dir, L)
+ *     if v > 0:      tin = (lo - rb) / v   tout = (hi + rb) / v
+ *     else if v < 0: tin = (hi + rb) / v   tout = (lo - rb) / v
+ *     else (v is 0 or a NaN): the axis gives no constraint if lo <= rb && -rb <= hi, and the triangle has NO TIME if not.
+ *   Start with enter = +0, exit = +inf, axis = 13 (LBVH_BOX_AXIS_START).  In the order j = 0 .. 12: tin replaces enter, and j
+ *   replaces axis, only when tin > enter; tout replaces exit only when tout < exit.  The triangle has the time enter iff
+ *   enter <= exit after all thirteen.  Two consequences:
+ *     a zero axis (parallel edges) has rb = lo = hi = v = 0 and constrains nothing;
+ *     a near-zero axis is taken as the direction it is: the projections are accurate relative to the computed L, and two convex
+ *     sets that overlap do so along every direction, so it cannot separate them beyond ordinary roundoff.
+ *   NaN (only from infinities: an infinite centre, or products that overflow): a comparison with a NaN is false, so a NaN tin or
+ *   tout replaces nothing, a NaN v takes the third branch, and there a NaN lo, hi or rb means no time.  enter and exit are
+ *   never NaN, a time is never NaN, and enter is never -0: t = +0 exactly for a start in overlap.
+ *   The thirteen axes suffice for a parallelepiped: it and the triangle are convex polytopes, and two convex polytopes are
+ *   disjoint iff a face normal of one or the cross product of an edge of each separates them; a parallelepiped has three face
+ *   normals and three edge directions whether or not they are orthogonal.  Moving the box by dir*t shifts its interval on every
+ *   axis by v*t, which gives the interval of t in which that axis does not separate; the box touches the triangle from the
+ *   largest entry on, while that is before the smallest exit.
+ *   Candidate: with g_k = (|ax_k| + |ay_k|) + |az_k| per world axis k (the half extent of the box's own AABB), triangle i is a
+ *   candidate iff it has a time t_i, t_i < T, the ray (centre, dir) passes the slab test of the triangle's own box grown by g —
+ *   scene.triangle_aabb[i] with min_k - g_k and max_k + g_k, one fp32 operation per bound, the slab test of every walker of this
+ *   library — with entry distance e_i, and !(t_i < e_i).
+ *   lbvh_box_cast: d_hits[k] = {t, tri, axis, 0} of cast k's candidate with the least t (compared as fp32 values); on equal t the
+ *   lower original triangle index, whatever order the walk meets them in.  axis = the j that gave the time (13: overlapping at
+ *   the start).  The contact normal, pointing from the triangle to the box, is -sign(v_j) * L_j / |L_j| for axis = j < 13 (for
+ *   13: none).  A contact POINT is not part of the record and is out of scope: a box touches a triangle in a point, a segment or
+ *   a polygon.  No candidate: the miss record, never T.
+ *   lbvh_box_cast_any: d_flags[k] = 1 if cast k has any candidate, else 0.  The walk is the same (same near-first order) cut
+ *   off at its first accepted candidate: never more node fetches or triangle tests per cast.
+ * Why the record does not depend on the order of the walk (the argument of lbvh_sphere_cast): lo - g and hi + g are each one
+ * operation monotone in lo and hi, and every box of the derived tree is the exact min / max union of what is below it, so the
+ * grown box of an ancestor contains the grown box of everything below it exactly in fp32; slab entries grow from a box to any box
+ * inside it, so e(ancestor) <= e(leaf) <= t for every candidate.  A slot is skipped only if the ray misses its grown box or its
+ * entry is > best, strictly: a subtree skipped that way holds no candidate at or below best.  Nothing is pruned on a box's exit
+ * distance.  A time in front of its own grown box is fp32 noise (a box touching the triangle has its centre within g of the
+ * triangle's box on every world axis); on ordinary meshes the rule rejects next to nothing.
+ * Both need the derived traversal scene (lbvh_build_fast_scene; a stale one is LBVH_ERR_INVALID_ARG), are asynchronous on the
+ * context's stream with no host wait, and use the context's ray scratch: they drop the path tracer's live-path list (see
+ * lbvh_path_bounce).  count == 0 is a no-op.  Rejected: NULL pointers, d_casts or d_hits not 16-byte aligned, d_flags not 4-byte
+ * aligned, count > 2^32 - 1.  Four-wide walk only (lbvh_debug_ray_walker does not apply); lbvh_debug_ray_stack_split,
+ * lbvh_debug_ray_stack_limit, lbvh_ray_stats_target and lbvh_debug_ray_waves apply as to the sphere cast.  The cost grows with the
+ * box (every tree box is larger by g) and each tested triangle costs up to thirteen axes. */
+lbvh_status lbvh_box_cast(lbvh_context* ctx, const lbvh_box_ray* d_casts, size_t count, const lbvh_scene* h_scene,
+                          lbvh_box_hit* d_hits);
+lbvh_status lbvh_box_cast_any(lbvh_context* ctx, const lbvh_box_ray* d_casts, size_t count, const lbvh_scene* h_scene,
+                              uint32_t* d_flags);
+
 /* A query triangle: 48 bytes; arrays of them 16-byte aligned. */
 typedef struct lbvh_tri_query {
     float a[3]; uint32_t skip;     /* ORIGINAL index of a scene triangle that is never a candidate; LBVH_NULL = none */
@@ -1186,7 +1266,7 @@ lbvh_status lbvh_path_scatter(lbvh_context* ctx, const lbvh_scene* h_scene, cons
  * lbvh_path_bounce on the same d_states / d_hits listed as live (a list kept by the context).  Every library call that writes
  * into those buffers drops the list (lbvh_path_begin, lbvh_trace_rays, a primary trace into any part of d_hits,
  * lbvh_buffer_upload / _fill_u32 / _free), and so does lbvh_trace_forget — and so do lbvh_trace_closest,
- * lbvh_trace_occluded, lbvh_closest_point_query, lbvh_within_distance, lbvh_count_hits, lbvh_point_crossings, lbvh_box_overlaps, lbvh_gather_within_distance, lbvh_k_closest_points, lbvh_trace_k_closest, lbvh_gather_hits, lbvh_sphere_cast, lbvh_sphere_cast_any, lbvh_capsule_cast, lbvh_capsule_cast_any, lbvh_triangle_intersections, lbvh_triangle_intersects_any, lbvh_region_overlaps, lbvh_region_overlaps_any and lbvh_region_overlaps_large, whatever buffers they are given, since they use the same ray scratch; then every state is scanned again.  The one exception among the query calls:
+ * lbvh_trace_occluded, lbvh_closest_point_query, lbvh_within_distance, lbvh_count_hits, lbvh_point_crossings, lbvh_box_overlaps, lbvh_gather_within_distance, lbvh_k_closest_points, lbvh_trace_k_closest, lbvh_gather_hits, lbvh_sphere_cast, lbvh_sphere_cast_any, lbvh_capsule_cast, lbvh_capsule_cast_any, lbvh_box_cast, lbvh_box_cast_any, lbvh_triangle_intersections, lbvh_triangle_intersects_any, lbvh_region_overlaps, lbvh_region_overlaps_any and lbvh_region_overlaps_large, whatever buffers they are given, since they use the same ray scratch; then every state is scanned again.  The one exception among the query calls:
  * lbvh_sort_hit_segments and lbvh_sort_index_segments take no context scratch and keep the live-path list (they drop it only when the
  * buffer they sort is d_hits itself).  What the library
  * cannot see is a write of the CALLER's own (a kernel or hipMemcpy that revives or ends paths, Russian roulette): between two

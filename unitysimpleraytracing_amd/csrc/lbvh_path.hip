@@ -1302,6 +1302,203 @@ __global__ __launch_bounds__(64) void capsule_cast_wide_kernel(const lbvh_capsul
     if (STATS) add_ray_stats(stats, n_casts, n_steps, n_tris);
 }
 
+// ---- box casts: first contact of a moving oriented box (include/lbvh.h, lbvh_box_cast) ----------------------------------
+// the three half-axis vectors of a cast: the box is { centre + s0*x + s1*y + s2*z : |s_i| <= 1 }
+struct box_axes { float xx, xy, xz, yx, yy, yz, zx, zy, zz; };
+
+// The header's time of a box with one scene triangle, +inf if it has none: the swept separating-axis test over the thirteen axes
+// L_j = cross(P_j, Q_j) in the header's order, `axis` = the j that set the time (LBVH_BOX_AXIS_START: overlapping at the start).
+// One copy of the axis body in a loop that is not unrolled, P_j and Q_j picked by j from a nibble table (j is the same in every
+// lane: the picks are selects on a scalar condition).  P: 0 1 2 = the box's x y z, 3 = e1; Q: the same and 4 = e2, 5 = e2 - e1.
+// The loop leaves as soon as enter > exit or enter > bound.  Neither changes a record: enter only grows and exit only shrinks
+// from axis to axis (a value replaces them only through a strict comparison, so neither is ever a NaN), hence enter > exit after
+// some axis is enter > exit after all thirteen, no time; and a time is the final enter >= this enter > bound, where bound is the
+// lane's best_t (T until a candidate is taken), which the candidate test t < best_t || (t == best_t && ...) refuses.
+__device__ __forceinline__ float box_triangle_time(const ray_t& c, const box_axes& b, const float4 a, const float4 e1, const float4 e2,
+                                                   float bound, uint32_t& axis)
+{
+    const float inf = __builtin_inff();
+    const float mx = a.x - c.ox, my = a.y - c.oy, mz = a.z - c.oz;
+    const float e3x = e2.x - e1.x, e3y = e2.y - e1.y, e3z = e2.z - e1.z;
+    float enter = 0.0f, exit = inf;
+    axis = LBVH_BOX_AXIS_START;
+#pragma nounroll
+    for (uint32_t j = 0; j < 13u; j++) {
+        const uint32_t pi = (uint32_t)(0x2221110000213ull >> (4u * j)) & 7u;
+        const uint32_t qi = (uint32_t)(0x5435435431024ull >> (4u * j)) & 7u;
+        const float px = pi == 0u ? b.xx : (pi == 1u ? b.yx : (pi == 2u ? b.zx : e1.x));
+        const float py = pi == 0u ? b.xy : (pi == 1u ? b.yy : (pi == 2u ? b.zy : e1.y));
+        const float pz = pi == 0u ? b.xz : (pi == 1u ? b.yz : (pi == 2u ? b.zz : e1.z));
+        const float qx = qi == 0u ? b.xx : (qi == 1u ? b.yx : (qi == 2u ? b.zx : (qi == 3u ? e1.x : (qi == 4u ? e2.x : e3x))));
+        const float qy = qi == 0u ? b.xy : (qi == 1u ? b.yy : (qi == 2u ? b.zy : (qi == 3u ? e1.y : (qi == 4u ? e2.y : e3y))));
+        const float qz = qi == 0u ? b.xz : (qi == 1u ? b.yz : (qi == 2u ? b.zz : (qi == 3u ? e1.z : (qi == 4u ? e2.z : e3z))));
+        const float lx = py * qz - pz * qy, ly = pz * qx - px * qz, lz = px * qy - py * qx;
+        const float p0 = dot3(mx, my, mz, lx, ly, lz);
+        const float p1 = p0 + dot3(e1.x, e1.y, e1.z, lx, ly, lz), p2 = p0 + dot3(e2.x, e2.y, e2.z, lx, ly, lz);
+        const float lo = fminf(p0, fminf(p1, p2)), hi = fmaxf(p0, fmaxf(p1, p2));
+        const float rb = (fabsf(dot3(b.xx, b.xy, b.xz, lx, ly, lz)) + fabsf(dot3(b.yx, b.yy, b.yz, lx, ly, lz))) +
+                         fabsf(dot3(b.zx, b.zy, b.zz, lx, ly, lz));
+        const float v = dot3(c.dx, c.dy, c.dz, lx, ly, lz);
+        const float under = lo - rb, over = hi + rb;
+        if (v > 0.0f || v < 0.0f) {
+            const float tin = (v > 0.0f ? under : over) / v, tout = (v > 0.0f ? over : under) / v;
+            if (tin > enter) { enter = tin; axis = j; }
+            if (tout < exit) exit = tout;
+        } else if (!(lo <= rb && -rb <= hi)) return inf;     // v = 0 (or a NaN): apart on this axis for ever
+        if (enter > exit || enter > bound) return inf;
+    }
+    return enter;
+}
+
+// cast k into the lane (best_t = T): false (miss record / 0 written, lane stays idle) for an inactive cast
+template <bool ANY>
+__device__ __forceinline__ bool load_box_cast(const lbvh_box_ray* __restrict__ casts, uint32_t k, ray_t& ray, box_axes& b, float& best_t,
+                                              std::conditional_t<ANY, uint32_t, lbvh_box_hit>* __restrict__ out)
+{
+    const float inf = __builtin_inff();
+    const float4* q = reinterpret_cast<const float4*>(&casts[k]);
+    const float4 o = q[0], d = q[1], x = q[2], y = q[3], z = q[4];
+    ray.ox = o.x; ray.oy = o.y; ray.oz = o.z;
+    ray.dx = d.x; ray.dy = d.y; ray.dz = d.z;
+    ray.ix = 1.0f / d.x; ray.iy = 1.0f / d.y; ray.iz = 1.0f / d.z;
+    b.xx = x.x; b.xy = x.y; b.xz = x.z;
+    b.yx = y.x; b.yy = y.y; b.yz = y.z;
+    b.zx = z.x; b.zy = z.y; b.zz = z.z;
+    best_t = fminf(o.w, LBVH_MAX_FLOAT);                 // T: candidates have t < T
+    const float det = dot3(x.x, x.y, x.z, y.y * z.z - y.z * z.y, y.z * z.x - y.x * z.z, y.x * z.y - y.y * z.x);
+    if (o.w > 0.0f && (o.x == o.x && o.y == o.y && o.z == o.z) &&
+        fabsf(d.x) < inf && fabsf(d.y) < inf && fabsf(d.z) < inf && dot3(d.x, d.y, d.z, d.x, d.y, d.z) > 0.0f &&
+        fabsf(x.x) < inf && fabsf(x.y) < inf && fabsf(x.z) < inf && fabsf(y.x) < inf && fabsf(y.y) < inf && fabsf(y.z) < inf &&
+        fabsf(z.x) < inf && fabsf(z.y) < inf && fabsf(z.z) < inf && fabsf(det) < inf && det != 0.0f) return true;
+    if constexpr (ANY) out[k] = 0u;
+    else reinterpret_cast<float4*>(out)[k] = make_float4(LBVH_MAX_FLOAT, __uint_as_float(0u), __uint_as_float(0u), __uint_as_float(0u));
+    return false;
+}
+
+// One cast per lane in the frame of capsule_cast_wide_kernel.  The four slot boxes are grown by g, the half extent of the cast's
+// box along each world axis ((|x_k| + |y_k|) + |z_k|): lo - g and hi + g, one operation per bound and monotone in lo / hi, so a
+// grown box contains the grown boxes of everything below it and the record does not depend on the order of the walk, as there.
+// A slot is skipped when the ray of the centre misses its grown box or enters it beyond best_t, strictly, never on an exit
+// distance.  The record is {t, tri, axis, 0}; ANY: a flag, the walk cut off at its first candidate (best_t stays T).
+template <bool ANY, bool STATS>
+__global__ __launch_bounds__(64) void box_cast_wide_kernel(const lbvh_box_ray* __restrict__ casts, uint32_t total,
+                                                           const lbvh_wide_node* __restrict__ wide,
+                                                           const lbvh_fast_node* __restrict__ lines,
+                                                           std::conditional_t<ANY, uint32_t, lbvh_box_hit>* __restrict__ out,
+                                                           uint32_t* __restrict__ deep,     // [gridDim.x][kWideStackDeep][64]
+                                                           uint32_t lds_depth,              // <= kWideStackLds
+                                                           uint32_t deep_cap,               // <= kWideStackDeep
+                                                           uint32_t* __restrict__ fault, lbvh_ray_stats* stats)
+{
+    __shared__ uint32_t s_stack[kWideStackLds][LBVH_WAVE];
+    uint32_t* my_deep = deep + (size_t)blockIdx.x * (kWideStackDeep * LBVH_WAVE) + threadIdx.x;
+    const uint32_t lane = threadIdx.x;
+    const uint32_t run = max((total + gridDim.x - 1) / gridDim.x, 32u);
+    uint32_t next = blockIdx.x * run;
+    if (next >= total) return;
+    const uint32_t end = min(next + run, total);
+    uint32_t n_casts = 0, n_steps = 0, n_tris = 0;
+
+    bool active = false, took = false;
+    uint32_t i = 0;
+    ray_t ray = {};
+    box_axes b = {};
+    float gx = 0.0f, gy = 0.0f, gz = 0.0f;
+    float best_t = LBVH_MAX_FLOAT;
+    uint32_t best_tri = 0, best_axis = 0, sp = 0, node = 0;
+    auto push = [&](uint32_t ref) {
+        if (sp < lds_depth) { s_stack[sp][lane] = ref; sp++; }
+        else if (sp < lds_depth + deep_cap) { my_deep[(sp - lds_depth) * LBVH_WAVE] = ref; sp++; }
+        // a dropped entry would be a silently wrong record: report it, as the ray walkers do (lbvh_debug_ray_stack_limit provokes it)
+        else __hip_atomic_store(fault, LBVH_FAULT_RAY_STACK, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    };
+    for (;;) {
+        const uint64_t idle = __ballot(!active);
+        if (idle != 0 && next < end) {
+            if (!active) {
+                const uint32_t k = next + mbcnt64(idle);
+                if (k < end) {
+                    i = k;
+                    active = load_box_cast<ANY>(casts, k, ray, b, best_t, out);
+                    gx = (fabsf(b.xx) + fabsf(b.yx)) + fabsf(b.zx);
+                    gy = (fabsf(b.xy) + fabsf(b.yy)) + fabsf(b.zy);
+                    gz = (fabsf(b.xz) + fabsf(b.yz)) + fabsf(b.zz);
+                    best_tri = 0; best_axis = 0; took = false;
+                    sp = 0; node = 0;
+                    if (STATS && active) n_casts++;
+                }
+            }
+            next += (uint32_t)__popcll(idle);
+        }
+        if (!__any(active) && next >= end) break;
+        if (active) {
+            if (STATS) n_steps++;
+            const float4* w = reinterpret_cast<const float4*>(&wide[node]);
+            const float4 lox = w[0], loy = w[1], loz = w[2], hix = w[3], hiy = w[4], hiz = w[5];
+            const uint4 ref = reinterpret_cast<const uint4*>(w)[6];
+            float t0, t1, t2, t3;
+            const bool h0 = wide_box(lox.x - gx, loy.x - gy, loz.x - gz, hix.x + gx, hiy.x + gy, hiz.x + gz, ray, t0) && !(t0 > best_t) && ref.x != kWideEmpty;
+            const bool h1 = wide_box(lox.y - gx, loy.y - gy, loz.y - gz, hix.y + gx, hiy.y + gy, hiz.y + gz, ray, t1) && !(t1 > best_t) && ref.y != kWideEmpty;
+            const bool h2 = wide_box(lox.z - gx, loy.z - gy, loz.z - gz, hix.z + gx, hiy.z + gy, hiz.z + gz, ray, t2) && !(t2 > best_t) && ref.z != kWideEmpty;
+            const bool h3 = wide_box(lox.w - gx, loy.w - gy, loz.w - gz, hix.w + gx, hiy.w + gy, hiz.w + gz, ray, t3) && !(t3 > best_t) && ref.w != kWideEmpty;
+            // leaf slots first: a lane's leaves one after the other, every lane's k-th at the same time
+            uint32_t leaves = (h0 && (ref.x >> 31) ? 1u : 0u) | (h1 && (ref.y >> 31) ? 2u : 0u) | (h2 && (ref.z >> 31) ? 4u : 0u) |
+                              (h3 && (ref.w >> 31) ? 8u : 0u);
+            bool found = false;                          // ANY: a candidate was accepted
+            while (leaves != 0u) {
+                const uint32_t k = (uint32_t)__builtin_ctz(leaves);
+                leaves &= leaves - 1u;
+                if (STATS) n_tris++;
+                float4 v0, v1, v2;
+                unpack_fast_triangle(reinterpret_cast<const float4*>(&lines[pick4(ref, k) & 0x7FFFFFFFu]), v0, v1, v2);
+                uint32_t axis;
+                const float t = box_triangle_time(ray, b, v0, v1, v2, best_t, axis);
+                const uint32_t tri = __float_as_uint(v0.w);
+                const float entry = k == 0u ? t0 : (k == 1u ? t1 : (k == 2u ? t2 : t3));
+                // best_t starts at T and best_tri at 0: t == T is never taken.  Ties go to the lower triangle index.
+                if (hit_counts(t, entry) && (t < best_t || (t == best_t && tri < best_tri))) {
+                    if constexpr (ANY) { found = true; break; }
+                    else { best_t = t; best_tri = tri; best_axis = axis; took = true; }
+                }
+            }
+            if (ANY && found) {
+                if constexpr (ANY) out[i] = 1u;
+                active = false;
+                continue;
+            }
+            // nodes to enter, ordered by entry distance (the order key of sphere_cast_wide_kernel)
+            constexpr uint32_t none = 0xFFFFFFFFu;
+            uint32_t k0 = h0 && !(ref.x >> 31) && !(t0 > best_t) ? ((__float_as_uint(fmaxf(t0, 0.0f)) & ~3u) | 0u) : none;
+            uint32_t k1 = h1 && !(ref.y >> 31) && !(t1 > best_t) ? ((__float_as_uint(fmaxf(t1, 0.0f)) & ~3u) | 1u) : none;
+            uint32_t k2 = h2 && !(ref.z >> 31) && !(t2 > best_t) ? ((__float_as_uint(fmaxf(t2, 0.0f)) & ~3u) | 2u) : none;
+            uint32_t k3 = h3 && !(ref.w >> 31) && !(t3 > best_t) ? ((__float_as_uint(fmaxf(t3, 0.0f)) & ~3u) | 3u) : none;
+            {   // five compare-exchanges
+                uint32_t a, c;
+                a = min(k0, k1); c = max(k0, k1); k0 = a; k1 = c;
+                a = min(k2, k3); c = max(k2, k3); k2 = a; k3 = c;
+                a = min(k0, k2); c = max(k0, k2); k0 = a; k2 = c;
+                a = min(k1, k3); c = max(k1, k3); k1 = a; k3 = c;
+                a = min(k1, k2); c = max(k1, k2); k1 = a; k2 = c;
+            }
+            if (k0 != none) {
+                if (k3 != none) push(pick4(ref, k3 & 3u));       // farthest first: the nearest waiting sibling is popped first
+                if (k2 != none) push(pick4(ref, k2 & 3u));
+                if (k1 != none) push(pick4(ref, k1 & 3u));
+                node = pick4(ref, k0 & 3u);
+            } else if (sp != 0) {
+                sp--;
+                node = sp < lds_depth ? s_stack[sp][lane] : my_deep[(sp - lds_depth) * LBVH_WAVE];
+            } else {
+                if constexpr (ANY) out[i] = 0u;
+                else reinterpret_cast<float4*>(out)[i] = make_float4(took ? best_t : LBVH_MAX_FLOAT, __uint_as_float(best_tri),
+                                                                     __uint_as_float(best_axis), __uint_as_float(0u));
+                active = false;
+            }
+        }
+    }
+    if (STATS) add_ray_stats(stats, n_casts, n_steps, n_tris);
+}
+
 // lbvh_k_closest_points: the walk of point_query_wide_kernel<false> with "best so far" replaced by "k-th best so far".  Each lane
 // keeps the k best candidates met so far, sorted by (dist2, tri), in LDS: three arrays [slot][lane] of dist2, triangle index and
 // the index of the triangle's line in the derived scene — 12 bytes per slot, `cap` slots per lane, sized at the launch from k
@@ -2916,7 +3113,7 @@ static lbvh_status trace_plain_rays(lbvh_context* ctx, const lbvh_ray* d_rays, s
 }
 
 // One record or flag per query, after the entry family's own argument checks: begin_walk, the one launch of the four-wide walk
-// (lbvh_debug_ray_walker does not apply), hipGetLastError.  The three walkers take the same arguments; the record type picks one.
+// (lbvh_debug_ray_walker does not apply), hipGetLastError.  The four walkers take the same arguments; the record type picks one.
 template <bool ANY, class QUERY, class OUT>
 static lbvh_status launch_per_query(lbvh_context* ctx, const QUERY* d_queries, size_t count, const lbvh_scene* h_scene, OUT* d_out, const char* who)
 {
@@ -2928,7 +3125,8 @@ static lbvh_status launch_per_query(lbvh_context* ctx, const QUERY* d_queries, s
                       ctx->fast_nodes, d_out, w.deep, w.lds, w.deep_cap, ctx->fault_dev, ctx->ray_stats)
     if constexpr (std::is_same_v<QUERY, lbvh_point_query>) PER_QUERY_WALK(point_query_wide_kernel);
     else if constexpr (std::is_same_v<QUERY, lbvh_sphere_ray>) PER_QUERY_WALK(sphere_cast_wide_kernel);
-    else PER_QUERY_WALK(capsule_cast_wide_kernel);
+    else if constexpr (std::is_same_v<QUERY, lbvh_capsule_ray>) PER_QUERY_WALK(capsule_cast_wide_kernel);
+    else PER_QUERY_WALK(box_cast_wide_kernel);
 #undef PER_QUERY_WALK
     LBVH_HIP_TRY(ctx, hipGetLastError());
     return LBVH_OK;
@@ -2947,16 +3145,31 @@ static lbvh_status point_queries(lbvh_context* ctx, const lbvh_point_query* d_qu
     return launch_per_query<ANY>(ctx, d_queries, count, h_scene, d_out, who);
 }
 
-// lbvh_sphere_cast / lbvh_sphere_cast_any (CAST = lbvh_sphere_ray), lbvh_capsule_cast / lbvh_capsule_cast_any (lbvh_capsule_ray)
-template <bool ANY, class CAST>
+// LBVH_REQUIRE with the entry point's name (`who`, a variable of the caller) in front of the message, as the stale-scene message
+// of begin_walk has it: the box casts and the region family
+#define NAMED_REQUIRE(cond)                                                                                         \
+    do {                                                                                                            \
+        if (!(cond)) return (lbvh_status)lbvh_set_error(ctx, LBVH_ERR_INVALID_ARG, who, "invalid argument: " #cond); \
+    } while (0)
+
+// lbvh_sphere_cast / lbvh_sphere_cast_any (CAST = lbvh_sphere_ray), lbvh_capsule_cast / lbvh_capsule_cast_any (lbvh_capsule_ray),
+// lbvh_box_cast / lbvh_box_cast_any (lbvh_box_ray, HIT = lbvh_box_hit).  The box casts' rejections name the entry point; the
+// sphere and capsule casts keep the text they have had.
+template <bool ANY, class CAST, class HIT = lbvh_hit>
 static lbvh_status shape_casts(lbvh_context* ctx, const CAST* d_casts, size_t count, const lbvh_scene* h_scene,
-                               std::conditional_t<ANY, uint32_t, lbvh_hit>* d_out, const char* who)
+                               std::conditional_t<ANY, uint32_t, HIT>* d_out, const char* who)
 {
+#define CAST_REQUIRE(cond)                                                                          \
+    do {                                                                                            \
+        if constexpr (std::is_same_v<CAST, lbvh_box_ray>) NAMED_REQUIRE(cond);                      \
+        else LBVH_REQUIRE(ctx, cond);                                                               \
+    } while (0)
     if (!ctx) return LBVH_ERR_INVALID_ARG;
     if (count == 0) return LBVH_OK;
-    LBVH_REQUIRE(ctx, d_casts != nullptr && h_scene != nullptr && d_out != nullptr);
-    LBVH_REQUIRE(ctx, ((uintptr_t)d_casts & 15) == 0 && ((uintptr_t)d_out & (ANY ? 3 : 15)) == 0);
-    LBVH_REQUIRE(ctx, count <= 0xFFFFFFFFull);
+    CAST_REQUIRE(d_casts != nullptr && h_scene != nullptr && d_out != nullptr);
+    CAST_REQUIRE(((uintptr_t)d_casts & 15) == 0 && ((uintptr_t)d_out & (ANY ? 3 : 15)) == 0);
+    CAST_REQUIRE(count <= 0xFFFFFFFFull);
+#undef CAST_REQUIRE
     return launch_per_query<ANY>(ctx, d_casts, count, h_scene, d_out, who);
 }
 
@@ -3057,21 +3270,17 @@ static lbvh_status triangle_queries(lbvh_context* ctx, const lbvh_tri_query* d_q
 
 // lbvh_region_overlaps: a CSR answer; lbvh_region_overlaps_any: one launch, the flags are the walk's own output.  Four-wide walk only.
 // (a rejection names the entry point, as the stale-scene message of begin_walk does)
-#define REGION_REQUIRE(cond)                                                                                        \
-    do {                                                                                                            \
-        if (!(cond)) return (lbvh_status)lbvh_set_error(ctx, LBVH_ERR_INVALID_ARG, who, "invalid argument: " #cond); \
-    } while (0)
 template <bool ANY>
 static lbvh_status region_queries(lbvh_context* ctx, const lbvh_region* d_regions, size_t count, uint32_t mode, const lbvh_scene* h_scene,
                                   uint64_t* d_offsets, uint32_t* d_tris, uint64_t capacity, uint32_t* d_flags, const char* who)
 {
     if (!ctx) return LBVH_ERR_INVALID_ARG;
     if (count == 0) return LBVH_OK;
-    REGION_REQUIRE(d_regions != nullptr && h_scene != nullptr && (ANY ? d_flags != nullptr : d_offsets != nullptr));
-    REGION_REQUIRE(mode <= LBVH_REGION_CONTAINED);
-    REGION_REQUIRE(d_tris != nullptr || capacity == 0);
-    REGION_REQUIRE(((uintptr_t)d_regions & 15) == 0 && ((uintptr_t)d_offsets & 7) == 0 && ((uintptr_t)d_tris & 3) == 0 && ((uintptr_t)d_flags & 3) == 0);
-    REGION_REQUIRE(count <= 0xFFFFFFFFull);
+    NAMED_REQUIRE(d_regions != nullptr && h_scene != nullptr && (ANY ? d_flags != nullptr : d_offsets != nullptr));
+    NAMED_REQUIRE(mode <= LBVH_REGION_CONTAINED);
+    NAMED_REQUIRE(d_tris != nullptr || capacity == 0);
+    NAMED_REQUIRE(((uintptr_t)d_regions & 15) == 0 && ((uintptr_t)d_offsets & 7) == 0 && ((uintptr_t)d_tris & 3) == 0 && ((uintptr_t)d_flags & 3) == 0);
+    NAMED_REQUIRE(count <= 0xFFFFFFFFull);
     walk_launch w;
     const lbvh_status rc = begin_walk(ctx, h_scene, count, who, true, &w);
     if (rc != LBVH_OK) return rc;
@@ -3116,11 +3325,11 @@ static lbvh_status region_queries_large(lbvh_context* ctx, const lbvh_region* d_
 {
     if (!ctx) return LBVH_ERR_INVALID_ARG;
     if (count == 0) return LBVH_OK;
-    REGION_REQUIRE(d_regions != nullptr && h_scene != nullptr && d_offsets != nullptr);
-    REGION_REQUIRE(mode <= LBVH_REGION_CONTAINED);
-    REGION_REQUIRE(d_tris != nullptr || capacity == 0);
-    REGION_REQUIRE(((uintptr_t)d_regions & 15) == 0 && ((uintptr_t)d_offsets & 7) == 0 && ((uintptr_t)d_tris & 3) == 0);
-    REGION_REQUIRE(count <= LBVH_REGION_LARGE_MAX_COUNT);
+    NAMED_REQUIRE(d_regions != nullptr && h_scene != nullptr && d_offsets != nullptr);
+    NAMED_REQUIRE(mode <= LBVH_REGION_CONTAINED);
+    NAMED_REQUIRE(d_tris != nullptr || capacity == 0);
+    NAMED_REQUIRE(((uintptr_t)d_regions & 15) == 0 && ((uintptr_t)d_offsets & 7) == 0 && ((uintptr_t)d_tris & 3) == 0);
+    NAMED_REQUIRE(count <= LBVH_REGION_LARGE_MAX_COUNT);
     const uint32_t task_cap = region_task_cap_of(ctx->region_task_cap, count);
     const size_t slots = count * (size_t)task_cap;                    // <= kRegionTaskSlots
     walk_launch w;
@@ -3149,7 +3358,7 @@ static lbvh_status region_queries_large(lbvh_context* ctx, const lbvh_region* d_
     LBVH_HIP_TRY(ctx, hipGetLastError());
     return LBVH_OK;
 }
-#undef REGION_REQUIRE
+#undef NAMED_REQUIRE
 
 extern "C" {
 
@@ -3231,6 +3440,16 @@ lbvh_status lbvh_capsule_cast(lbvh_context* ctx, const lbvh_capsule_ray* d_casts
 lbvh_status lbvh_capsule_cast_any(lbvh_context* ctx, const lbvh_capsule_ray* d_casts, size_t count, const lbvh_scene* h_scene, uint32_t* d_flags)
 {
     return shape_casts<true>(ctx, d_casts, count, h_scene, d_flags, "lbvh_capsule_cast_any");
+}
+
+lbvh_status lbvh_box_cast(lbvh_context* ctx, const lbvh_box_ray* d_casts, size_t count, const lbvh_scene* h_scene, lbvh_box_hit* d_hits)
+{
+    return shape_casts<false, lbvh_box_ray, lbvh_box_hit>(ctx, d_casts, count, h_scene, d_hits, "lbvh_box_cast");
+}
+
+lbvh_status lbvh_box_cast_any(lbvh_context* ctx, const lbvh_box_ray* d_casts, size_t count, const lbvh_scene* h_scene, uint32_t* d_flags)
+{
+    return shape_casts<true, lbvh_box_ray, lbvh_box_hit>(ctx, d_casts, count, h_scene, d_flags, "lbvh_box_cast_any");
 }
 
 // the four-wide walk only (lbvh_debug_ray_walker does not apply), the directions by value in the arguments

@@ -62,6 +62,41 @@ def obb_planes(centre, axes3x3, half_extents):
     return _regions(planes)
 
 
+def obb_half_axes(half_extents, rotation3x3=None):
+    """The three half-axis vectors (ax, ay, az) of layouts.BOX_RAY for a box of the given half extents turned by rotation3x3, whose
+    COLUMNS are the box's axes in world space (a rotation matrix as it multiplies a column vector; None: an AABB): ax =
+    rotation[:, 0] * half_extents[0] and so on, rounded to fp32 once.  Shapes (..., 3) and (..., 3, 3) -> three arrays (..., 3).
+    Nothing is normalised or made orthogonal: a sheared matrix gives a sheared box, which lbvh_box_cast takes as it is."""
+    he = np.asarray(half_extents, dtype=np.float64)
+    rot = np.eye(3) if rotation3x3 is None else np.asarray(rotation3x3, dtype=np.float64)
+    axes = np.swapaxes(rot, -1, -2) * he[..., :, None]                # row k = column k of the rotation, scaled
+    return tuple(np.ascontiguousarray(axes[..., k, :], dtype=np.float32) for k in range(3))
+
+
+def box_cast_axis(cast, triangle_line, axis):
+    """L_j of include/lbvh.h (lbvh_box_cast) for j = axis < 13, in float64 from the fp32 values: `cast` one layouts.BOX_RAY record,
+    `triangle_line` = (a, e1, e2) of the reported triangle (e1 = b - a, e2 = c - a)."""
+    _, e1, e2 = (np.asarray(x, dtype=np.float64) for x in triangle_line)
+    b = [np.asarray(cast[k], dtype=np.float64) for k in ("ax", "ay", "az")]
+    if axis == 0:
+        return np.cross(e1, e2)
+    if axis < 4:
+        return np.cross(b[axis % 3], b[(axis + 1) % 3])
+    return np.cross(b[(axis - 4) // 3], (e1, e2, e2 - e1)[(axis - 4) % 3])
+
+
+def box_cast_normal(cast, triangle_line, axis):
+    """The contact normal of a lbvh_box_cast record, pointing from the triangle to the box: -sign(v) * L / |L| with L the record's
+    separating axis and v = dot(dir, L).  None for axis = layouts.BOX_AXIS_START (overlapping at the start: no normal).  The miss
+    record has axis = 0 like a contact with the face: test t < layouts.MAX_FLOAT before asking for a normal.  A contact point is not
+    defined by the record (a box touches a triangle in a point, a segment or a polygon)."""
+    if axis >= L.BOX_AXIS_START:
+        return None
+    line = box_cast_axis(cast, triangle_line, axis)
+    v = float(np.dot(np.asarray(cast["dir"], dtype=np.float64), line))
+    return -np.sign(v) * line / np.linalg.norm(line)
+
+
 def frustum_planes(camera, far, rect=None):
     """The view frustum of `camera` (the dict of scenes.camera or an N.Camera) as one layouts.REGION record, in the convention of
     lbvh_trace_primary's ray generation: the eye at camera_to_world * (0, 0, 0, 1), looking along the camera's -z; the image plane at
@@ -485,6 +520,17 @@ class RaytracingMeshDrawer:
     def capsule_cast_any(self, casts, flags):
         """1 into the uint32 DataBuffer `flags` for each capsule of `casts` that touches anything on its way, else 0."""
         self._per_query(N.lib.lbvh_capsule_cast_any, casts, "CAPSULE_RAY", flags, np.uint32, "casts")
+
+    def box_cast(self, casts, hits):
+        """First contact of each moving box of the DataBuffer `casts` (layouts.BOX_RAY: centre, t_max, dir and the half-axis vectors
+        ax, ay, az, as obb_half_axes makes them) with the mesh into the DataBuffer `hits` (layouts.BOX_HIT: t, tri, and the
+        separating axis that gave the time — box_cast_normal turns it into the contact normal), over the derived scene.  The centre
+        is at centre + dir * t; no contact in [0, t_max): the miss record.  Asynchronous; read with hits.get_data()."""
+        self._per_query(N.lib.lbvh_box_cast, casts, "BOX_RAY", hits, L.BOX_HIT, "casts")
+
+    def box_cast_any(self, casts, flags):
+        """1 into the uint32 DataBuffer `flags` for each box of `casts` that touches anything on its way, else 0."""
+        self._per_query(N.lib.lbvh_box_cast_any, casts, "BOX_RAY", flags, np.uint32, "casts")
 
     def closest_points(self, queries, out):
         """Nearest triangle of each point of the DataBuffer `queries` (layouts.POINT_QUERY: p, max_dist2) into the DataBuffer `out`

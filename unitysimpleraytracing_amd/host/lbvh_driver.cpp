@@ -44,6 +44,13 @@
 //                                                default 3; radius default 1.5, height default 4): per axis the origin and the
 //                                                target as `sweep` draws them, then the axis component uniform in [-height,
 //                                                height]; t_max 2.  CapsuleCast and CapsuleCastAny; prints the fields of `sweep`
+//     lbvh_driver boxcast [seed] [half_extent] [t_max] [n_casts]  the 4 096 triangles of cfg1 and n_casts (default 6 000) boxes
+//                                                (SplitMix64, seed default 3; half_extent default 1.5, t_max default 2): per
+//                                                axis k the centre and the target as `sweep` draws them, then component k of
+//                                                ax, ay, az: half_extent on the diagonal, 0 off it, plus uniform in
+//                                                [-half_extent / 2, half_extent / 2] (sheared, always solid).  BoxCast and
+//                                                BoxCastAny; prints how many casts touch, how many overlap at the start, the
+//                                                number of records per axis, the word sum and the first records
 //     lbvh_driver crossings [n | file.obj] [count] the mesh and the points of `points`; PointCrossings along the three default
 //                                                directions ((1,1,1)/sqrt 3, (-1,2,3)/sqrt 14, (4,-1,2)/sqrt 21) and CountHits
 //                                                on the same rays written out ({p, 0, dir, +inf}); prints the sum of the counts,
@@ -772,6 +779,61 @@ static int capsule_main(int argc, char** argv)
     return 0;
 }
 
+static int boxcast_main(int argc, char** argv)
+{
+    uint64_t seed = argc > 2 ? strtoull(argv[2], nullptr, 10) : 3;
+    const float half = argc > 3 ? (float)atof(argv[3]) : 1.5f;
+    const float t_max = argc > 4 ? (float)atof(argv[4]) : 2.0f;
+    const size_t count = argc > 5 ? (size_t)strtoull(argv[5], nullptr, 10) : 6000;
+    const std::vector<lbvh_triangle> mesh = random_mesh(4096);
+    float lo[3], hi[3];
+    mesh_box(mesh, lo, hi);
+    lbvh::Context ctx(0);
+    lbvh::RaytracingMeshDrawer drawer(ctx, mesh);
+    drawer.Awake();
+    lbvh::DataBuffer<lbvh_box_ray> casts(ctx, count);
+    for (auto& c : casts.LocalBuffer()) {
+        std::memset(&c, 0, sizeof c);
+        for (int k = 0; k < 3; k++) {
+            const float grow = 0.25f * (hi[k] - lo[k]);
+            c.centre[k] = uniform(seed, lo[k] - grow, hi[k] + grow);
+            c.dir[k] = uniform(seed, lo[k], hi[k]) - c.centre[k];
+            c.ax[k] = (k == 0 ? half : 0.0f) + uniform(seed, -0.5f * half, 0.5f * half);
+            c.ay[k] = (k == 1 ? half : 0.0f) + uniform(seed, -0.5f * half, 0.5f * half);
+            c.az[k] = (k == 2 ? half : 0.0f) + uniform(seed, -0.5f * half, 0.5f * half);
+        }
+        c.t_max = t_max;
+    }
+    casts.Sync();
+    lbvh::DataBuffer<lbvh_box_hit> hits(ctx, count);
+    lbvh::DataBuffer<uint32_t> flags(ctx, count);
+    drawer.BoxCast(casts, hits);
+    drawer.BoxCastAny(casts, flags);
+    hits.GetData();
+    flags.GetData();
+    size_t touching = 0, flagged = 0, at_start = 0, by_axis[14] = {};
+    uint64_t words = 0;
+    for (size_t i = 0; i < count; i++) {
+        const lbvh_box_hit& h = hits.LocalBuffer()[i];
+        words += word_sum(h);
+        touching += h.t < LBVH_MAX_FLOAT;
+        at_start += h.t == 0.0f;
+        if (h.t < LBVH_MAX_FLOAT && h.axis < 14) by_axis[h.axis]++;
+        flagged += flags.LocalBuffer()[i];
+    }
+    std::printf("{\"triangles\": %zu, \"casts\": %zu, \"half_extent\": %.9g, \"t_max\": %.9g, \"touching\": %zu, \"flagged\": %zu, "
+                "\"at_start\": %zu, \"word_sum\": %llu, \"by_axis\": [",
+                mesh.size(), count, half, t_max, touching, flagged, at_start, (unsigned long long)words);
+    for (int j = 0; j < 14; j++) std::printf("%s%zu", j ? ", " : "", by_axis[j]);
+    std::printf("], \"records\": [");
+    for (size_t i = 0; i < std::min<size_t>(count, 3); i++) {
+        const lbvh_box_hit& h = hits.LocalBuffer()[i];
+        std::printf("%s[%.9g, %u, %u]", i ? ", " : "", h.t, h.tri, h.axis);
+    }
+    std::printf("]}\n");
+    return 0;
+}
+
 static int crossings_main(int argc, char** argv)
 {
     const size_t count = argc > 3 ? (size_t)strtoull(argv[3], nullptr, 10) : 65536;
@@ -905,7 +967,7 @@ int main(int argc, char** argv)
 {
     static const struct { const char* name; int (*run)(int, char**); } commands[] = {
         {"crossings", crossings_main}, {"points", points_main}, {"knn", knn_main},   {"khits", khits_main}, {"gather", gather_main}, {"sortedhits", sortedhits_main},
-        {"sweep", sweep_main},         {"capsule", capsule_main},         {"overlaps", overlaps_main}, {"tris", tris_main}, {"regions", regions_main}, {"rays", rays_main}, {"sort", sort_main},   {"multi", multi_main}};
+        {"sweep", sweep_main},         {"capsule", capsule_main}, {"boxcast", boxcast_main},         {"overlaps", overlaps_main}, {"tris", tris_main}, {"regions", regions_main}, {"rays", rays_main}, {"sort", sort_main},   {"multi", multi_main}};
     try {
         for (const auto& c : commands)
             if (argc > 1 && std::strcmp(argv[1], c.name) == 0) return c.run(argc, argv);

@@ -419,6 +419,22 @@ public:
         const lbvh_scene s = container_->Scene();
         check(ctx_.get(), lbvh_capsule_cast_any(ctx_.get(), (const lbvh_capsule_ray*)casts.DeviceBuffer(), casts.Size(), &s, (uint32_t*)flags.DeviceBuffer()));
     }
+    // moving boxes of the caller's own (lbvh_box_ray: centre, t_max, dir and the three half-axis vectors ax, ay, az; the box is
+    // centre + s0*ax + s1*ay + s2*az, |s_i| <= 1) over the derived scene: the first contact of each — {t, tri, axis, 0}, the centre
+    // at centre + dir * t, axis the separating axis that gave the time (LBVH_BOX_AXIS_START: overlapping at the start) — or
+    // whether it touches anything on its way, 1 / 0 per cast (lbvh_box_cast / lbvh_box_cast_any; asynchronous)
+    void BoxCast(const DataBuffer<lbvh_box_ray>& casts, DataBuffer<lbvh_box_hit>& hits)
+    {
+        if (hits.Size() < casts.Size()) throw Error(LBVH_ERR_INVALID_ARG, "BoxCast: fewer hit records than casts");
+        const lbvh_scene s = container_->Scene();
+        check(ctx_.get(), lbvh_box_cast(ctx_.get(), (const lbvh_box_ray*)casts.DeviceBuffer(), casts.Size(), &s, (lbvh_box_hit*)hits.DeviceBuffer()));
+    }
+    void BoxCastAny(const DataBuffer<lbvh_box_ray>& casts, DataBuffer<uint32_t>& flags)
+    {
+        if (flags.Size() < casts.Size()) throw Error(LBVH_ERR_INVALID_ARG, "BoxCastAny: fewer flags than casts");
+        const lbvh_scene s = container_->Scene();
+        check(ctx_.get(), lbvh_box_cast_any(ctx_.get(), (const lbvh_box_ray*)casts.DeviceBuffer(), casts.Size(), &s, (uint32_t*)flags.DeviceBuffer()));
+    }
     // the k nearest triangles of each point (1 <= k <= LBVH_K_CLOSEST_MAX): out[q * k + j] = the j-th nearest of query q, ties by
     // the lower triangle index, padded with none-records; found (optional): the number of real records per row
     // (lbvh_k_closest_points; asynchronous)

@@ -39,6 +39,13 @@ assert SPHERE_RAY.itemsize == 32
 # lbvh_capsule_cast / lbvh_capsule_cast_any: the sphere's record and the axis (the other end is origin + axis)
 CAPSULE_RAY = np.dtype([("origin", "<f4", 3), ("radius", "<f4"), ("dir", "<f4", 3), ("t_max", "<f4"), ("axis", "<f4", 3), ("_pad", "<u4")])
 assert CAPSULE_RAY.itemsize == 48
+# lbvh_box_cast / lbvh_box_cast_any: a moving box { centre + s0*ax + s1*ay + s2*az : |s_i| <= 1 } (three half-axis vectors; the pads
+# are not read) and its record; axis = the separating axis that gave the time, BOX_AXIS_START = overlapping at the start
+BOX_RAY = np.dtype([("centre", "<f4", 3), ("t_max", "<f4"), ("dir", "<f4", 3), ("_pad0", "<u4"), ("ax", "<f4", 3), ("_pad1", "<u4"),
+                    ("ay", "<f4", 3), ("_pad2", "<u4"), ("az", "<f4", 3), ("_pad3", "<u4")])
+BOX_HIT = np.dtype([("t", "<f4"), ("tri", "<u4"), ("axis", "<u4"), ("_zero", "<u4")])
+assert BOX_RAY.itemsize == 80 and BOX_HIT.itemsize == 16
+BOX_AXIS_START = 13
 # lbvh_closest_point_query / lbvh_within_distance: a point with its squared search radius (active iff max_dist2 > 0), and the answer
 POINT_QUERY = np.dtype([("p", "<f4", 3), ("max_dist2", "<f4")])
 CLOSEST_POINT = np.dtype([("dist2", "<f4"), ("tri", "<u4"), ("u", "<f4"), ("v", "<f4")])
