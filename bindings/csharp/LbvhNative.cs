@@ -47,6 +47,13 @@ public static class LbvhNative
     [StructLayout(LayoutKind.Sequential)]
     public struct BoxHit { public float t; public uint tri; public uint axis; public uint zero; }
 
+    // lbvh_capsule / lbvh_obb (include/lbvh.h): a capsule (32 bytes) and an oriented box (64 bytes) where they stand, CapsuleRay and
+    // BoxRay without the motion; the pads are not read (ShapeOverlaps.cs)
+    [StructLayout(LayoutKind.Sequential)]
+    public struct Capsule { public float originX, originY, originZ, radius; public float axisX, axisY, axisZ; public uint pad; }
+    [StructLayout(LayoutKind.Sequential)]
+    public struct Obb { public float centreX, centreY, centreZ; public uint pad0; public float axX, axY, axZ; public uint pad1; public float ayX, ayY, ayZ; public uint pad2; public float azX, azY, azZ; public uint pad3; }
+
     // lbvh_point_query / lbvh_closest_point (include/lbvh.h): a point with its squared search radius (active iff maxDist2 > 0) and
     // the nearest triangle's record, 16 bytes each (PointQueries.cs)
     [StructLayout(LayoutKind.Sequential)]
@@ -168,6 +175,12 @@ public static class LbvhNative
     [DllImport(Lib)] public static extern int lbvh_triangle_intersections(IntPtr ctx, IntPtr dQueries, UIntPtr count, ref Scene scene, IntPtr dOffsets,
         IntPtr dTris, ulong capacity);
     [DllImport(Lib)] public static extern int lbvh_triangle_intersects_any(IntPtr ctx, IntPtr dQueries, UIntPtr count, ref Scene scene, IntPtr dFlags);
+    [DllImport(Lib)] public static extern int lbvh_capsule_overlaps(IntPtr ctx, IntPtr dShapes, UIntPtr count, ref Scene scene, IntPtr dOffsets,
+        IntPtr dTris, ulong capacity);
+    [DllImport(Lib)] public static extern int lbvh_capsule_overlaps_any(IntPtr ctx, IntPtr dShapes, UIntPtr count, ref Scene scene, IntPtr dFlags);
+    [DllImport(Lib)] public static extern int lbvh_obb_overlaps(IntPtr ctx, IntPtr dShapes, UIntPtr count, ref Scene scene, IntPtr dOffsets,
+        IntPtr dTris, ulong capacity);
+    [DllImport(Lib)] public static extern int lbvh_obb_overlaps_any(IntPtr ctx, IntPtr dShapes, UIntPtr count, ref Scene scene, IntPtr dFlags);
     [DllImport(Lib)] public static extern int lbvh_region_overlaps(IntPtr ctx, IntPtr dRegions, UIntPtr count, uint mode, ref Scene scene, IntPtr dOffsets,
         IntPtr dTris, ulong capacity);
     [DllImport(Lib)] public static extern int lbvh_region_overlaps_any(IntPtr ctx, IntPtr dRegions, UIntPtr count, uint mode, ref Scene scene, IntPtr dFlags);

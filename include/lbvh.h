@@ -1142,6 +1142,91 @@ lbvh_status lbvh_triangle_intersections(lbvh_context* ctx, const lbvh_tri_query*
 lbvh_status lbvh_triangle_intersects_any(lbvh_context* ctx, const lbvh_tri_query* d_queries, size_t count, const lbvh_scene* h_scene,
                                          uint32_t* d_flags);
 
+/* A capsule where it stands: 32 bytes, arrays 16-byte aligned: every point within `radius` of the segment [origin, origin + axis]
+ * (lbvh_capsule_ray without the motion).  _pad is not read. */
+typedef struct lbvh_capsule { float origin[3]; float radius; float axis[3]; uint32_t _pad; } lbvh_capsule;
+/* An oriented box where it stands: 64 bytes, arrays 16-byte aligned: { centre + s0*ax + s1*ay + s2*az : |s_i| <= 1 }, the three
+ * half-axis VECTORS of lbvh_box_ray — a parallelepiped, nothing normalised, nothing assumed orthogonal.  The pads are not read. */
+typedef struct lbvh_obb { float centre[3]; uint32_t _pad0; float ax[3]; uint32_t _pad1;
+                          float ay[3]; uint32_t _pad2; float az[3]; uint32_t _pad3; } lbvh_obb;
+
+/* Shape overlaps: WHICH triangles does a capsule or an oriented box touch where it stands (what a character controller asks
+ * right after a sweep: move, list what the shape now touches, push out; Physics.OverlapCapsule / OverlapBox, and CheckCapsule /
+ * CheckBox without an invented direction), as a CSR list (lbvh_capsule_overlaps, lbvh_obb_overlaps) or as one flag per shape
+ * (lbvh_capsule_overlaps_any, lbvh_obb_overlaps_any), over the derived traversal scene in its four-wide form by the walk of
+ * lbvh_triangle_intersections.  The definition is the start overlap of lbvh_capsule_cast / lbvh_box_cast with the motion taken
+ * out, in strict fp32, every operation rounded on its own, with the operations, the order and the names of those definitions.
+ * Triangle i, with the line a, e1, e2 of the derived scene and its own box A = scene.triangle_aabb[i], is a candidate of an
+ * ACTIVE shape iff rule 1 and rule 2 below both hold.  An inactive shape is never walked; it gets an empty segment, or the flag 0.
+ *   Capsule (o = origin, h = axis, r = radius):
+ *     Active: radius > 0 and radius < +inf, no NaN in origin, every component of axis finite (lbvh_capsule_cast's conditions on
+ *     radius, origin and axis; all false for NaN).  axis = 0 is allowed.
+ *     Rule 1, own box: for each world axis k
+ *         (A.min[k] - max(h_k, 0)) - r <= o_k && o_k <= (A.max[k] - min(h_k, 0)) + r
+ *     lbvh_capsule_cast's grown bounds, two fp32 operations each, max and min as fmaxf and fminf, in closed comparisons.
+ *     Rule 2, touch: for some derived triangle j = 0 .. 7 of lbvh_capsule_cast (a_j, e1_j, e2_j formed as there, j = 0 the line as
+ *     stored), dist2 of lbvh_closest_point_query for the point o against it is <= R2, R2 = r*r (one operation); OR
+ *     pierce(o, h; a, e1, e2) of lbvh_triangle_intersections passes, 0 <= t <= 1 (the axis goes through the face with both ends
+ *     and all edges farther than the radius).
+ *   Box (c = centre, b_0, b_1, b_2 = ax, ay, az):
+ *     Active: no NaN in centre, every component of ax, ay, az finite, and the fp32 value det = dot(ax, cross(ay, az)) finite and
+ *     != 0 (lbvh_box_cast's conditions on centre, ax, ay, az and det; flat boxes are out of scope).
+ *     Rule 1, own box: with g_k = (|ax_k| + |ay_k|) + |az_k| as in lbvh_box_cast, for each world axis k
+ *         A.min[k] - g_k <= c_k && c_k <= A.max[k] + g_k                 one fp32 operation per bound, closed comparisons.
+ *     Rule 2, touch: for EVERY one of the thirteen axes L_j of lbvh_box_cast, in its order, with m = a - c, p0, p1, p2, lo, hi and
+ *     rb exactly as there:   lo <= rb && -rb <= hi.   That definition's v = 0 branch on all thirteen axes: no axis separates.
+ *   A NaN never counts: a comparison with a NaN is false, so a NaN dist2 or t passes nothing and a NaN lo, hi or rb means not a
+ *   candidate.  A zero axis L_j (parallel edges) has lo = hi = rb = 0 and passes.
+ *   Why the list does not depend on the walk (the argument at lbvh_triangle_intersections with grown boxes): the grown bounds are
+ *   monotone in lo and hi — (lo - max(h, 0)) - r, (hi - min(h, 0)) + r, lo - g, hi + g, every operation monotone —, and every box
+ *   of the derived tree, binary or four-wide, is the exact min / max union of what lies below it; so every ancestor of a
+ *   candidate's leaf passes rule 1 on its own box, and the walk skips exactly the slots that fail it.  Rule 2 is a function of
+ *   (shape, triangle) only.  Each triangle is one leaf, so each candidate appears once.
+ *   The relation to the casts goes ONE WAY exactly: if triangle i is a candidate here, lbvh_capsule_cast (lbvh_box_cast) of the
+ *   same origin (centre), radius and axes gives t = +0 for every active dir whose three components are non-zero and normal and every
+ *   t_max > 0 — rule 2 is that definition's start overlap, and rule 1 puts the origin in the closed grown box, where the slab test
+ *   of such a dir passes with an entry <= 0 — for the box with axis = LBVH_BOX_AXIS_START.  The cast's triangle index is therefore
+ *   <= the least index of the segment.  The converse is NOT promised: a cast may also report t = 0 from a feature root or a
+ *   quotient that rounds to zero (the sphere starts one rounding outside and touches within less than the smallest time), and such
+ *   a triangle is no candidate here.
+ *   A capsule with axis = 0 is allowed: a sphere by this arithmetic (every derived triangle lies in the scene triangle, and the
+ *   pierce has det = 0).  Its list is a SUBSET of lbvh_gather_within_distance's for the point origin with r2 = r*r, up to pairs
+ *   at the bound itself: dist2 == R2 exactly (closed here, open there), and a derived triangle j >= 1, whose corners are formed
+ *   again from a + e, passing one rounding beside j = 0.
+ * Output of lbvh_capsule_overlaps / lbvh_obb_overlaps — the CSR contract of lbvh_triangle_intersections, word for word:
+ *   d_offsets: count + 1 words of 64 bits.  d_offsets[k] = the number of candidates of shapes 0 .. k-1, d_offsets[count] = the
+ *   total M.  Always written in full, whatever `capacity` is.
+ *   d_tris, `capacity` words of 32 bits: segment k = d_tris[d_offsets[k] .. d_offsets[k+1]) = the ORIGINAL triangle indices of
+ *   shape k's candidates, each exactly once.  THE ORDER INSIDE A SEGMENT IS THE WALK'S AND IS NOT PART OF THE CONTRACT;
+ *   lbvh_sort_index_segments applies unchanged and leaves every fitting segment strictly ascending.
+ *   Overflow: no word at index >= capacity is ever written; every segment with d_offsets[k+1] <= capacity is complete; words
+ *   below `capacity` that belong to a segment which does not fit are unspecified.  The call never waits on the host and returns
+ *   LBVH_OK in both cases: the caller reads d_offsets[count] (one 8-byte download) to learn what was needed.
+ *   Count-only form: capacity == 0 writes the offsets and walks once (d_tris may be NULL); otherwise the scene is walked twice
+ *   (count, device-side scan, fill: the same kernel making the same decisions, so a segment never outgrows its slot).
+ *   d_tris == NULL with capacity > 0 is LBVH_ERR_INVALID_ARG.
+ * Output of lbvh_capsule_overlaps_any / lbvh_obb_overlaps_any: d_flags[k] = 1 exactly when segment k would be non-empty, else 0;
+ * every one of the `count` words is written.  The walk is the same, cut off at a shape's first candidate.
+ * All four need the derived traversal scene (lbvh_build_fast_scene; a stale one is LBVH_ERR_INVALID_ARG), are asynchronous on the
+ * context's stream with no host wait, and use the context's ray scratch: they drop the path tracer's live-path list (see
+ * lbvh_path_bounce).  count == 0 is a no-op: nothing is enqueued and no buffer is touched, d_offsets[0] included.  Rejected: NULL
+ * ctx / d_shapes / h_scene / d_offsets / d_flags, d_shapes not 16-byte aligned, d_offsets not 8-byte aligned, d_tris or d_flags
+ * not 4-byte aligned, count > 2^32 - 1.  Four-wide walk only (lbvh_debug_ray_walker does not apply); lbvh_debug_ray_waves,
+ * lbvh_debug_ray_stack_split, lbvh_debug_ray_stack_limit and lbvh_ray_stats_target apply as to the triangle queries (`rays` =
+ * active shapes; triangle_tests counts the triangle lines read, whatever number of derived triangles or axes is tested; the full
+ * form reports twice the count-only form's).
+ * One shape per lane; the cost is that of a box overlap walk on boxes larger by the shape, plus one 64-byte triangle line and up
+ * to eight point tests and a pierce (capsule) or thirteen axes (box) per triangle that passes rule 1.  Out of scope: penetration
+ * depth or direction, a contact manifold, flat boxes, a form that spreads one huge shape over the device. */
+lbvh_status lbvh_capsule_overlaps(lbvh_context* ctx, const lbvh_capsule* d_shapes, size_t count, const lbvh_scene* h_scene,
+                                  uint64_t* d_offsets, uint32_t* d_tris, uint64_t capacity);
+lbvh_status lbvh_capsule_overlaps_any(lbvh_context* ctx, const lbvh_capsule* d_shapes, size_t count, const lbvh_scene* h_scene,
+                                      uint32_t* d_flags);
+lbvh_status lbvh_obb_overlaps(lbvh_context* ctx, const lbvh_obb* d_shapes, size_t count, const lbvh_scene* h_scene,
+                              uint64_t* d_offsets, uint32_t* d_tris, uint64_t capacity);
+lbvh_status lbvh_obb_overlaps_any(lbvh_context* ctx, const lbvh_obb* d_shapes, size_t count, const lbvh_scene* h_scene,
+                                  uint32_t* d_flags);
+
 /* A convex region bounded by six planes: 96 bytes; arrays of them 16-byte aligned.  A plane {nx, ny, nz, d} keeps the half space
  * n . x + d >= 0; the region is the intersection of its six half spaces.  Normals need not be unit length.  A region with fewer
  * faces repeats a plane or pads with {0, 0, 0, 1}. */
@@ -1266,7 +1351,7 @@ lbvh_status lbvh_path_scatter(lbvh_context* ctx, const lbvh_scene* h_scene, cons
  * lbvh_path_bounce on the same d_states / d_hits listed as live (a list kept by the context).  Every library call that writes
  * into those buffers drops the list (lbvh_path_begin, lbvh_trace_rays, a primary trace into any part of d_hits,
  * lbvh_buffer_upload / _fill_u32 / _free), and so does lbvh_trace_forget — and so do lbvh_trace_closest,
- * lbvh_trace_occluded, lbvh_closest_point_query, lbvh_within_distance, lbvh_count_hits, lbvh_point_crossings, lbvh_box_overlaps, lbvh_gather_within_distance, lbvh_k_closest_points, lbvh_trace_k_closest, lbvh_gather_hits, lbvh_sphere_cast, lbvh_sphere_cast_any, lbvh_capsule_cast, lbvh_capsule_cast_any, lbvh_box_cast, lbvh_box_cast_any, lbvh_triangle_intersections, lbvh_triangle_intersects_any, lbvh_region_overlaps, lbvh_region_overlaps_any and lbvh_region_overlaps_large, whatever buffers they are given, since they use the same ray scratch; then every state is scanned again.  The one exception among the query calls:
+ * lbvh_trace_occluded, lbvh_closest_point_query, lbvh_within_distance, lbvh_count_hits, lbvh_point_crossings, lbvh_box_overlaps, lbvh_gather_within_distance, lbvh_k_closest_points, lbvh_trace_k_closest, lbvh_gather_hits, lbvh_sphere_cast, lbvh_sphere_cast_any, lbvh_capsule_cast, lbvh_capsule_cast_any, lbvh_box_cast, lbvh_box_cast_any, lbvh_triangle_intersections, lbvh_triangle_intersects_any, lbvh_capsule_overlaps, lbvh_capsule_overlaps_any, lbvh_obb_overlaps, lbvh_obb_overlaps_any, lbvh_region_overlaps, lbvh_region_overlaps_any and lbvh_region_overlaps_large, whatever buffers they are given, since they use the same ray scratch; then every state is scanned again.  The one exception among the query calls:
  * lbvh_sort_hit_segments and lbvh_sort_index_segments take no context scratch and keep the live-path list (they drop it only when the
  * buffer they sort is d_hits itself).  What the library
  * cannot see is a write of the CALLER's own (a kernel or hipMemcpy that revives or ends paths, Russian roulette): between two

@@ -69,7 +69,9 @@ lbvh_status lbvh_debug_ray_waves(lbvh_context* ctx, uint32_t max_waves);
  * survivors' u, v at the end of a query are not counted: with k = 1 the three counters equal lbvh_closest_point_query's),
  * and lbvh_trace_k_closest in the same way (`rays` = active rays; with k = 1 the counters equal the four-wide lbvh_trace_closest's),
  * and lbvh_sphere_cast / lbvh_sphere_cast_any, lbvh_capsule_cast / lbvh_capsule_cast_any and lbvh_box_cast / lbvh_box_cast_any
- * (`rays` = active casts; a triangle line counts once, whatever number of its derived triangles or axes is tested), and both walks of lbvh_gather_hits (`rays` = active rays: the
+ * (`rays` = active casts; a triangle line counts once, whatever number of its derived triangles or axes is tested), and
+ * lbvh_capsule_overlaps / lbvh_obb_overlaps and their _any forms in the same way (`rays` = active shapes; the full form adds twice
+ * what the count-only form adds), and both walks of lbvh_gather_hits (`rays` = active rays: the
  * full form adds twice what the count-only form adds). */
 typedef struct lbvh_ray_stats {
     uint64_t rays;

@@ -110,6 +110,10 @@ SIGNATURES = {
     "lbvh_box_cast_any": (_I32, [_P, _P, _SZ, C.POINTER(Scene), _P]),
     "lbvh_triangle_intersections": (_I32, [_P, _P, _SZ, C.POINTER(Scene), _P, _P, C.c_uint64]),
     "lbvh_triangle_intersects_any": (_I32, [_P, _P, _SZ, C.POINTER(Scene), _P]),
+    "lbvh_capsule_overlaps": (_I32, [_P, _P, _SZ, C.POINTER(Scene), _P, _P, C.c_uint64]),
+    "lbvh_capsule_overlaps_any": (_I32, [_P, _P, _SZ, C.POINTER(Scene), _P]),
+    "lbvh_obb_overlaps": (_I32, [_P, _P, _SZ, C.POINTER(Scene), _P, _P, C.c_uint64]),
+    "lbvh_obb_overlaps_any": (_I32, [_P, _P, _SZ, C.POINTER(Scene), _P]),
     "lbvh_region_overlaps": (_I32, [_P, _P, _SZ, _U32, C.POINTER(Scene), _P, _P, C.c_uint64]),
     "lbvh_region_overlaps_any": (_I32, [_P, _P, _SZ, _U32, C.POINTER(Scene), _P]),
     "lbvh_region_overlaps_large": (_I32, [_P, _P, _SZ, _U32, C.POINTER(Scene), _P, _P, C.c_uint64]),

@@ -1314,6 +1314,27 @@ struct box_axes { float xx, xy, xz, yx, yy, yz, zx, zy, zz; };
 // from axis to axis (a value replaces them only through a strict comparison, so neither is ever a NaN), hence enter > exit after
 // some axis is enter > exit after all thirteen, no time; and a time is the final enter >= this enter > bound, where bound is the
 // lane's best_t (T until a candidate is taken), which the candidate test t < best_t || (t == best_t && ...) refuses.
+// Axis j of the header, L = cross(P_j, Q_j), and on it the triangle's interval [lo, hi] from the box's centre (m = a - centre,
+// e3 = e2 - e1) and the box's half width rb: the part of the axis body that lbvh_box_cast and lbvh_obb_overlaps share.
+__device__ __forceinline__ void box_axis_spans(uint32_t j, float mx, float my, float mz, const box_axes& b, const float4 e1, const float4 e2,
+                                               float e3x, float e3y, float e3z, float& lx, float& ly, float& lz, float& lo, float& hi, float& rb)
+{
+    const uint32_t pi = (uint32_t)(0x2221110000213ull >> (4u * j)) & 7u;
+    const uint32_t qi = (uint32_t)(0x5435435431024ull >> (4u * j)) & 7u;
+    const float px = pi == 0u ? b.xx : (pi == 1u ? b.yx : (pi == 2u ? b.zx : e1.x));
+    const float py = pi == 0u ? b.xy : (pi == 1u ? b.yy : (pi == 2u ? b.zy : e1.y));
+    const float pz = pi == 0u ? b.xz : (pi == 1u ? b.yz : (pi == 2u ? b.zz : e1.z));
+    const float qx = qi == 0u ? b.xx : (qi == 1u ? b.yx : (qi == 2u ? b.zx : (qi == 3u ? e1.x : (qi == 4u ? e2.x : e3x))));
+    const float qy = qi == 0u ? b.xy : (qi == 1u ? b.yy : (qi == 2u ? b.zy : (qi == 3u ? e1.y : (qi == 4u ? e2.y : e3y))));
+    const float qz = qi == 0u ? b.xz : (qi == 1u ? b.yz : (qi == 2u ? b.zz : (qi == 3u ? e1.z : (qi == 4u ? e2.z : e3z))));
+    lx = py * qz - pz * qy; ly = pz * qx - px * qz; lz = px * qy - py * qx;
+    const float p0 = dot3(mx, my, mz, lx, ly, lz);
+    const float p1 = p0 + dot3(e1.x, e1.y, e1.z, lx, ly, lz), p2 = p0 + dot3(e2.x, e2.y, e2.z, lx, ly, lz);
+    lo = fminf(p0, fminf(p1, p2)); hi = fmaxf(p0, fmaxf(p1, p2));
+    rb = (fabsf(dot3(b.xx, b.xy, b.xz, lx, ly, lz)) + fabsf(dot3(b.yx, b.yy, b.yz, lx, ly, lz))) +
+         fabsf(dot3(b.zx, b.zy, b.zz, lx, ly, lz));
+}
+
 __device__ __forceinline__ float box_triangle_time(const ray_t& c, const box_axes& b, const float4 a, const float4 e1, const float4 e2,
                                                    float bound, uint32_t& axis)
 {
@@ -1324,20 +1345,8 @@ __device__ __forceinline__ float box_triangle_time(const ray_t& c, const box_axe
     axis = LBVH_BOX_AXIS_START;
 #pragma nounroll
     for (uint32_t j = 0; j < 13u; j++) {
-        const uint32_t pi = (uint32_t)(0x2221110000213ull >> (4u * j)) & 7u;
-        const uint32_t qi = (uint32_t)(0x5435435431024ull >> (4u * j)) & 7u;
-        const float px = pi == 0u ? b.xx : (pi == 1u ? b.yx : (pi == 2u ? b.zx : e1.x));
-        const float py = pi == 0u ? b.xy : (pi == 1u ? b.yy : (pi == 2u ? b.zy : e1.y));
-        const float pz = pi == 0u ? b.xz : (pi == 1u ? b.yz : (pi == 2u ? b.zz : e1.z));
-        const float qx = qi == 0u ? b.xx : (qi == 1u ? b.yx : (qi == 2u ? b.zx : (qi == 3u ? e1.x : (qi == 4u ? e2.x : e3x))));
-        const float qy = qi == 0u ? b.xy : (qi == 1u ? b.yy : (qi == 2u ? b.zy : (qi == 3u ? e1.y : (qi == 4u ? e2.y : e3y))));
-        const float qz = qi == 0u ? b.xz : (qi == 1u ? b.yz : (qi == 2u ? b.zz : (qi == 3u ? e1.z : (qi == 4u ? e2.z : e3z))));
-        const float lx = py * qz - pz * qy, ly = pz * qx - px * qz, lz = px * qy - py * qx;
-        const float p0 = dot3(mx, my, mz, lx, ly, lz);
-        const float p1 = p0 + dot3(e1.x, e1.y, e1.z, lx, ly, lz), p2 = p0 + dot3(e2.x, e2.y, e2.z, lx, ly, lz);
-        const float lo = fminf(p0, fminf(p1, p2)), hi = fmaxf(p0, fmaxf(p1, p2));
-        const float rb = (fabsf(dot3(b.xx, b.xy, b.xz, lx, ly, lz)) + fabsf(dot3(b.yx, b.yy, b.yz, lx, ly, lz))) +
-                         fabsf(dot3(b.zx, b.zy, b.zz, lx, ly, lz));
+        float lx, ly, lz, lo, hi, rb;
+        box_axis_spans(j, mx, my, mz, b, e1, e2, e3x, e3y, e3z, lx, ly, lz, lo, hi, rb);
         const float v = dot3(c.dx, c.dy, c.dz, lx, ly, lz);
         const float under = lo - rb, over = hi + rb;
         if (v > 0.0f || v < 0.0f) {
@@ -2337,6 +2346,192 @@ __global__ __launch_bounds__(64) void triangle_query_wide_kernel(const float4* _
     if (STATS) add_ray_stats(stats, n_queries, n_steps, n_tris);
 }
 
+// ---- shape overlaps: which triangles a capsule or an oriented box touches where it stands (lbvh_capsule_overlaps, -------
+// lbvh_obb_overlaps, include/lbvh.h).  The frame of triangle_query_wide_kernel with the casts' grown bounds for the slot test: a
+// slot is entered iff the shape's origin (centre) lies in the slot's box grown as capsule_cast_wide_kernel / box_cast_wide_kernel
+// grow it, formed per slot (two operations per bound for the capsule, one for the box, each monotone in lo / hi, so every ancestor
+// of a candidate's leaf passes), in closed comparisons.  At a leaf slot that passes — its box is the triangle's own — the triangle
+// line is read once and the casts' start-overlap arithmetic decides: shape_touches below.  kTriCount and kTriFill are the two
+// walks of the CSR protocol; kTriAny stops a lane at its first candidate.
+enum overlap_shape : int { kShapeCapsule = 0, kShapeObb = 1 };
+
+// a capsule (origin o, axis h, R2 = r*r) against the triangle line (a, e1, e2): some derived triangle j = 0 .. 7 of lbvh_capsule_cast
+// has point_triangle2(o) <= R2 — the start overlap of sphere_triangle_time, the first one ends the loop —, or the axis pierces the
+// face.  One copy of the point test in a loop that is not unrolled, as in capsule_triangle_time; the loop leaves through its
+// condition: with a `return` in its body the compiler unrolled it all the same (240 VGPRs, 2 waves per SIMD, against 85 / 5).
+__device__ __forceinline__ bool capsule_touches(const ray_t& o, float R2, float hx, float hy, float hz, const float4 a, const float4 e1,
+                                                const float4 e2)
+{
+    bool within = false;
+#pragma nounroll
+    for (uint32_t j = 0; j < 8u && !within; j++) {
+        float4 p, q1, q2;
+        capsule_triangle(j, a, e1, e2, hx, hy, hz, p, q1, q2);
+        float u, v;
+        within = point_triangle2(o.ox, o.oy, o.oz, p, q1, q2, u, v) <= R2;
+    }
+    if (within) return true;
+    ray_t ax;
+    ax.ox = o.ox; ax.oy = o.oy; ax.oz = o.oz;
+    ax.dx = hx; ax.dy = hy; ax.dz = hz;
+    ax.ix = 0.0f; ax.iy = 0.0f; ax.iz = 0.0f;            // (not read by the triangle test)
+    float u = 0.0f, v = 0.0f;
+    const float tp = ray_triangle_edges(ax, a, e1.x, e1.y, e1.z, e2.x, e2.y, e2.z, u, v);
+    return 0.0f <= tp && tp <= 1.0f;
+}
+
+// a box (centre c, half-axis vectors b) against the triangle line: no one of the thirteen axes of lbvh_box_cast separates them,
+// lo <= rb && -rb <= hi on every axis (box_triangle_time's v = 0 branch); the first separating axis ends the loop.  A NaN in lo,
+// hi or rb fails the comparison: no candidate.
+__device__ __forceinline__ bool box_touches(const ray_t& c, const box_axes& b, const float4 a, const float4 e1, const float4 e2)
+{
+    const float mx = a.x - c.ox, my = a.y - c.oy, mz = a.z - c.oz;
+    const float e3x = e2.x - e1.x, e3y = e2.y - e1.y, e3z = e2.z - e1.z;
+#pragma nounroll
+    for (uint32_t j = 0; j < 13u; j++) {
+        float lx, ly, lz, lo, hi, rb;
+        box_axis_spans(j, mx, my, mz, b, e1, e2, e3x, e3y, e3z, lx, ly, lz, lo, hi, rb);
+        if (!(lo <= rb && -rb <= hi)) return false;
+    }
+    return true;
+}
+
+// the origin (centre) o against one slot box [lo, hi] grown below by `under` and above by `over`, then by r on both sides
+// (capsule: under = max(h, 0), over = min(h, 0), the cast's (lo - max(h, 0)) - r and (hi - min(h, 0)) + r; box: lo - g and hi + g)
+template <int SHAPE>
+__device__ __forceinline__ bool shape_in_grown(float lo, float hi, float o, float under, float over, float r)
+{
+    if constexpr (SHAPE == kShapeCapsule) return (lo - under) - r <= o && o <= (hi - over) + r;
+    else return lo - under <= o && o <= hi + under;
+}
+
+template <int SHAPE, int MODE, bool STATS>
+__global__ __launch_bounds__(64) void shape_overlap_wide_kernel(const float4* __restrict__ shapes, uint32_t total,   // two (capsule) or four (box) float4 per shape
+                                                                const lbvh_wide_node* __restrict__ wide,
+                                                                const lbvh_fast_node* __restrict__ lines,
+                                                                uint32_t* __restrict__ counts,            // kTriCount: candidates of shape k; kTriAny: the flags
+                                                                const uint64_t* __restrict__ offsets,     // kTriFill: where segment k starts
+                                                                uint32_t* __restrict__ tris, uint64_t capacity,
+                                                                uint32_t* __restrict__ deep,     // [gridDim.x][kWideStackDeep][64]
+                                                                uint32_t lds_depth,              // <= kWideStackLds
+                                                                uint32_t deep_cap,               // <= kWideStackDeep
+                                                                uint32_t* __restrict__ fault, lbvh_ray_stats* stats)
+{
+    __shared__ uint32_t s_stack[kWideStackLds][LBVH_WAVE];
+    uint32_t* my_deep = deep + (size_t)blockIdx.x * (kWideStackDeep * LBVH_WAVE) + threadIdx.x;
+    const uint32_t lane = threadIdx.x;
+    const uint32_t run = max((total + gridDim.x - 1) / gridDim.x, 32u);
+    uint32_t next = blockIdx.x * run;
+    if (next >= total) return;
+    const uint32_t end = min(next + run, total);
+    uint32_t n_shapes = 0, n_steps = 0, n_tris = 0;
+
+    bool active = false;
+    uint32_t i = 0;
+    ray_t o = {};                                        // the origin / centre (the direction is not read)
+    box_axes b = {};                                     // box: the half-axis vectors
+    float r = 0.0f, hx = 0.0f, hy = 0.0f, hz = 0.0f;     // capsule: the radius and the axis; box: h = g, the half extent per world axis
+    uint32_t n_found = 0, sp = 0, node = 0;
+    uint64_t pos = 0;                                    // kTriFill: where this lane's next candidate goes
+    auto push = [&](uint32_t ref) {
+        if (sp < lds_depth) { s_stack[sp][lane] = ref; sp++; }
+        else if (sp < lds_depth + deep_cap) { my_deep[(sp - lds_depth) * LBVH_WAVE] = ref; sp++; }
+        // a dropped entry would be a silently short list: report it, as the other walkers do (lbvh_debug_ray_stack_limit provokes it)
+        else __hip_atomic_store(fault, LBVH_FAULT_RAY_STACK, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    };
+    for (;;) {
+        const uint64_t idle = __ballot(!active);
+        if (idle != 0 && next < end) {
+            if (!active) {
+                const uint32_t k = next + mbcnt64(idle);
+                if (k < end) {
+                    i = k;
+                    const float inf = __builtin_inff();
+                    if constexpr (SHAPE == kShapeCapsule) {
+                        const float4 q0 = shapes[2 * (size_t)k], q1 = shapes[2 * (size_t)k + 1];
+                        o.ox = q0.x; o.oy = q0.y; o.oz = q0.z; r = q0.w;
+                        hx = q1.x; hy = q1.y; hz = q1.z;
+                        active = r > 0.0f && r < inf && (q0.x == q0.x && q0.y == q0.y && q0.z == q0.z) &&
+                                 fabsf(hx) < inf && fabsf(hy) < inf && fabsf(hz) < inf;
+                    } else {
+                        const float4 q0 = shapes[4 * (size_t)k], x = shapes[4 * (size_t)k + 1], y = shapes[4 * (size_t)k + 2], z = shapes[4 * (size_t)k + 3];
+                        o.ox = q0.x; o.oy = q0.y; o.oz = q0.z;
+                        b.xx = x.x; b.xy = x.y; b.xz = x.z;
+                        b.yx = y.x; b.yy = y.y; b.yz = y.z;
+                        b.zx = z.x; b.zy = z.y; b.zz = z.z;
+                        hx = (fabsf(b.xx) + fabsf(b.yx)) + fabsf(b.zx);
+                        hy = (fabsf(b.xy) + fabsf(b.yy)) + fabsf(b.zy);
+                        hz = (fabsf(b.xz) + fabsf(b.yz)) + fabsf(b.zz);
+                        const float det = dot3(x.x, x.y, x.z, y.y * z.z - y.z * z.y, y.z * z.x - y.x * z.z, y.x * z.y - y.y * z.x);
+                        active = (q0.x == q0.x && q0.y == q0.y && q0.z == q0.z) &&
+                                 fabsf(x.x) < inf && fabsf(x.y) < inf && fabsf(x.z) < inf && fabsf(y.x) < inf && fabsf(y.y) < inf && fabsf(y.z) < inf &&
+                                 fabsf(z.x) < inf && fabsf(z.y) < inf && fabsf(z.z) < inf && fabsf(det) < inf && det != 0.0f;
+                    }
+                    sp = 0; node = 0;
+                    if constexpr (MODE == kTriFill) { if (active) pos = offsets[k]; }
+                    else { n_found = 0; if (!active) counts[k] = 0u; }
+                    if (STATS && active) n_shapes++;
+                }
+            }
+            next += (uint32_t)__popcll(idle);
+        }
+        if (!__any(active) && next >= end) break;
+        if (active) {
+            if (STATS) n_steps++;
+            const float4* w = reinterpret_cast<const float4*>(&wide[node]);
+            const float4 lox = w[0], loy = w[1], loz = w[2], hix = w[3], hiy = w[4], hiz = w[5];
+            const uint4 ref = reinterpret_cast<const uint4*>(w)[6];
+            // capsule: max(h, 0) and min(h, 0) are formed here from h, as in capsule_cast_wide_kernel; box: g both ways
+            const bool cap = SHAPE == kShapeCapsule;
+            const float ux = cap ? fmaxf(hx, 0.0f) : hx, uy = cap ? fmaxf(hy, 0.0f) : hy, uz = cap ? fmaxf(hz, 0.0f) : hz;
+            const float vx = cap ? fminf(hx, 0.0f) : hx, vy = cap ? fminf(hy, 0.0f) : hy, vz = cap ? fminf(hz, 0.0f) : hz;
+#define SHAPE_SLOT(c)                                                                                                          \
+    (shape_in_grown<SHAPE>(lox.c, hix.c, o.ox, ux, vx, r) && shape_in_grown<SHAPE>(loy.c, hiy.c, o.oy, uy, vy, r) &&          \
+     shape_in_grown<SHAPE>(loz.c, hiz.c, o.oz, uz, vz, r) && ref.c != kWideEmpty)
+            const bool h0 = SHAPE_SLOT(x), h1 = SHAPE_SLOT(y), h2 = SHAPE_SLOT(z), h3 = SHAPE_SLOT(w);
+#undef SHAPE_SLOT
+            const uint32_t hit = (h0 ? 1u : 0u) | (h1 ? 2u : 0u) | (h2 ? 4u : 0u) | (h3 ? 8u : 0u);
+            const uint32_t leaf = (ref.x >> 31) | ((ref.y >> 31) << 1) | ((ref.z >> 31) << 2) | ((ref.w >> 31) << 3);
+            uint32_t leaves = hit & leaf, inner = hit & ~leaf;
+            while (leaves != 0u) {
+                const uint32_t k = (uint32_t)__builtin_ctz(leaves);
+                leaves &= leaves - 1u;
+                const uint32_t line = pick4(ref, k) & 0x7FFFFFFFu;
+                float4 t0, t1, t2;
+                unpack_fast_triangle(reinterpret_cast<const float4*>(&lines[line]), t0, t1, t2);
+                const uint32_t tri = __float_as_uint(t0.w);
+                if (STATS) n_tris++;
+                bool touches;
+                if constexpr (SHAPE == kShapeCapsule) touches = capsule_touches(o, r * r, hx, hy, hz, t0, t1, t2);
+                else touches = box_touches(o, b, t0, t1, t2);
+                if (!touches) continue;
+                if constexpr (MODE == kTriFill) {
+                    if (pos < capacity) tris[pos] = tri;         // never a word at or beyond the capacity
+                    pos++;
+                } else {
+                    n_found++;
+                    if constexpr (MODE == kTriAny) { leaves = 0u; inner = 0u; sp = 0; }       // the first candidate ends the walk
+                }
+            }
+            if (inner != 0u) {
+                node = pick4(ref, (uint32_t)__builtin_ctz(inner));
+                inner &= inner - 1u;
+                while (inner != 0u) {
+                    push(pick4(ref, (uint32_t)__builtin_ctz(inner)));
+                    inner &= inner - 1u;
+                }
+            } else if (sp != 0) {
+                sp--;
+                node = sp < lds_depth ? s_stack[sp][lane] : my_deep[(sp - lds_depth) * LBVH_WAVE];
+            } else {
+                if constexpr (MODE != kTriFill) counts[i] = n_found;
+                active = false;
+            }
+        }
+    }
+    if (STATS) add_ray_stats(stats, n_shapes, n_steps, n_tris);
+}
+
 // ---- region queries: which triangles lie in a convex region of six planes (lbvh_region_overlaps, include/lbvh.h) ---------
 // The frame of overlap_wide_kernel<BOX = true> with another slot test: a slot is entered iff for each of the six planes
 // {nx, ny, nz, d} the box corner farthest along the normal is on the kept side, P = ((nx * X + ny * Y) + nz * Z) + d >= 0 with
@@ -3268,6 +3463,44 @@ static lbvh_status triangle_queries(lbvh_context* ctx, const lbvh_tri_query* d_q
     }
 }
 
+// lbvh_capsule_overlaps / lbvh_obb_overlaps: a CSR answer; lbvh_capsule_overlaps_any / lbvh_obb_overlaps_any: one launch, the
+// flags are the walk's own output — triangle_queries with the shape's walk.  Four-wide walk only.  (a rejection names the entry point)
+template <int SHAPE, bool ANY>
+static lbvh_status shape_overlaps(lbvh_context* ctx, const void* d_shapes, size_t count, const lbvh_scene* h_scene, uint64_t* d_offsets,
+                                  uint32_t* d_tris, uint64_t capacity, uint32_t* d_flags, const char* who)
+{
+    if (!ctx) return LBVH_ERR_INVALID_ARG;
+    if (count == 0) return LBVH_OK;
+    NAMED_REQUIRE(d_shapes != nullptr && h_scene != nullptr && (ANY ? d_flags != nullptr : d_offsets != nullptr));
+    NAMED_REQUIRE(d_tris != nullptr || capacity == 0);
+    NAMED_REQUIRE(((uintptr_t)d_shapes & 15) == 0 && ((uintptr_t)d_offsets & 7) == 0 && ((uintptr_t)d_tris & 3) == 0 && ((uintptr_t)d_flags & 3) == 0);
+    NAMED_REQUIRE(count <= 0xFFFFFFFFull);
+    walk_launch w;
+    const lbvh_status rc = begin_walk(ctx, h_scene, count, who, true, &w);
+    if (rc != LBVH_OK) return rc;
+    const float4* q = (const float4*)d_shapes;
+    const uint32_t total = (uint32_t)count;
+    if constexpr (ANY) {
+        LBVH_LAUNCH_STATS(ctx, ctx->ray_stats, (shape_overlap_wide_kernel<SHAPE, kTriAny, STATS>), dim3(w.waves), dim3(LBVH_WAVE), q, total, w.wn, ctx->fast_nodes,
+                          d_flags, (const uint64_t*)nullptr, (uint32_t*)nullptr, (uint64_t)0, w.deep, w.lds, w.deep_cap, ctx->fault_dev, ctx->ray_stats);
+        LBVH_HIP_TRY(ctx, hipGetLastError());
+        return LBVH_OK;
+    } else {
+        return csr_query(
+            ctx, count, d_offsets, capacity,
+            [&](uint32_t* counts) {
+                LBVH_LAUNCH_STATS(ctx, ctx->ray_stats, (shape_overlap_wide_kernel<SHAPE, kTriCount, STATS>), dim3(w.waves), dim3(LBVH_WAVE), q, total, w.wn,
+                                  ctx->fast_nodes, counts, (const uint64_t*)nullptr, (uint32_t*)nullptr, (uint64_t)0, w.deep, w.lds, w.deep_cap, ctx->fault_dev,
+                                  ctx->ray_stats);
+            },
+            [&] {
+                LBVH_LAUNCH_STATS(ctx, ctx->ray_stats, (shape_overlap_wide_kernel<SHAPE, kTriFill, STATS>), dim3(w.waves), dim3(LBVH_WAVE), q, total, w.wn,
+                                  ctx->fast_nodes, (uint32_t*)nullptr, (const uint64_t*)d_offsets, d_tris, capacity, w.deep, w.lds, w.deep_cap, ctx->fault_dev,
+                                  ctx->ray_stats);
+            });
+    }
+}
+
 // lbvh_region_overlaps: a CSR answer; lbvh_region_overlaps_any: one launch, the flags are the walk's own output.  Four-wide walk only.
 // (a rejection names the entry point, as the stale-scene message of begin_walk does)
 template <bool ANY>
@@ -3400,6 +3633,30 @@ lbvh_status lbvh_triangle_intersects_any(lbvh_context* ctx, const lbvh_tri_query
                                          uint32_t* d_flags)
 {
     return triangle_queries<true>(ctx, d_queries, count, h_scene, nullptr, nullptr, 0, d_flags, "lbvh_triangle_intersects_any");
+}
+
+lbvh_status lbvh_capsule_overlaps(lbvh_context* ctx, const lbvh_capsule* d_shapes, size_t count, const lbvh_scene* h_scene,
+                                  uint64_t* d_offsets, uint32_t* d_tris, uint64_t capacity)
+{
+    return shape_overlaps<kShapeCapsule, false>(ctx, d_shapes, count, h_scene, d_offsets, d_tris, capacity, nullptr, "lbvh_capsule_overlaps");
+}
+
+lbvh_status lbvh_capsule_overlaps_any(lbvh_context* ctx, const lbvh_capsule* d_shapes, size_t count, const lbvh_scene* h_scene,
+                                      uint32_t* d_flags)
+{
+    return shape_overlaps<kShapeCapsule, true>(ctx, d_shapes, count, h_scene, nullptr, nullptr, 0, d_flags, "lbvh_capsule_overlaps_any");
+}
+
+lbvh_status lbvh_obb_overlaps(lbvh_context* ctx, const lbvh_obb* d_shapes, size_t count, const lbvh_scene* h_scene,
+                              uint64_t* d_offsets, uint32_t* d_tris, uint64_t capacity)
+{
+    return shape_overlaps<kShapeObb, false>(ctx, d_shapes, count, h_scene, d_offsets, d_tris, capacity, nullptr, "lbvh_obb_overlaps");
+}
+
+lbvh_status lbvh_obb_overlaps_any(lbvh_context* ctx, const lbvh_obb* d_shapes, size_t count, const lbvh_scene* h_scene,
+                                  uint32_t* d_flags)
+{
+    return shape_overlaps<kShapeObb, true>(ctx, d_shapes, count, h_scene, nullptr, nullptr, 0, d_flags, "lbvh_obb_overlaps_any");
 }
 
 // the four-wide walk only (lbvh_debug_ray_walker does not apply), one launch; the per-lane lists are dynamic LDS sized from k

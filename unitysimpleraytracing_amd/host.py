@@ -73,6 +73,26 @@ def obb_half_axes(half_extents, rotation3x3=None):
     return tuple(np.ascontiguousarray(axes[..., k, :], dtype=np.float32) for k in range(3))
 
 
+def capsule_shapes(origin, axis, radius):
+    """layouts.CAPSULE records for lbvh_capsule_overlaps: the capsules with the segments origin .. origin + axis (shapes (..., 3),
+    broadcast against each other) and the given radii, rounded to fp32 once."""
+    o, h = np.broadcast_arrays(np.asarray(origin, dtype=np.float32), np.asarray(axis, dtype=np.float32))
+    out = np.zeros(o.shape[:-1], dtype=L.CAPSULE)
+    out["origin"], out["axis"], out["radius"] = o, h, np.asarray(radius, dtype=np.float32)
+    return out if out.ndim else out.reshape(1)
+
+
+def obb_shapes(centre, half_extents, rotation3x3=None):
+    """layouts.OBB records for lbvh_obb_overlaps: boxes of the given half extents turned by rotation3x3 (COLUMNS = the box's axes in
+    world space; None: AABBs) about `centre`, the half-axis vectors as obb_half_axes makes them.  Shapes (..., 3), (..., 3) and
+    (..., 3, 3)."""
+    ax, ay, az = obb_half_axes(half_extents, rotation3x3)
+    c = np.asarray(centre, dtype=np.float32)
+    out = np.zeros(np.broadcast_shapes(c.shape[:-1], ax.shape[:-1]), dtype=L.OBB)
+    out["centre"], out["ax"], out["ay"], out["az"] = c, ax, ay, az
+    return out if out.ndim else out.reshape(1)
+
+
 def box_cast_axis(cast, triangle_line, axis):
     """L_j of include/lbvh.h (lbvh_box_cast) for j = axis < 13, in float64 from the fp32 values: `cast` one layouts.BOX_RAY record,
     `triangle_line` = (a, e1, e2) of the reported triangle (e1 = b - a, e2 = c - a)."""
@@ -620,6 +640,35 @@ class RaytracingMeshDrawer:
         Returns (offsets, tris): host arrays, uint64[queries.size + 1] and uint32[total].  device_sort=True issues
         sort_index_segments before the download: every segment ascending."""
         return self._csr_lists(self.triangle_intersections, queries, min_capacity, device_sort)
+
+    def capsule_overlaps(self, shapes, offsets, tris=None):
+        """Every triangle each capsule of the DataBuffer `shapes` (layouts.CAPSULE: origin, radius, axis; see capsule_shapes)
+        touches where it stands — the start overlap of capsule_cast without a direction —, as a CSR list on the caller's buffers
+        exactly as box_overlaps writes it: `offsets` (uint64 DataBuffer, at least shapes.size + 1 entries) always complete, `tris`
+        (uint32 DataBuffer, its size is the capacity) the ORIGINAL triangle indices in no particular order; tris=None counts only.
+        Asynchronous."""
+        self._overlaps(N.lib.lbvh_capsule_overlaps, shapes, L.CAPSULE, offsets, tris)
+
+    def capsule_overlaps_any(self, shapes, flags):
+        """1 into the uint32 DataBuffer `flags` for each capsule of `shapes` that touches any triangle, else 0."""
+        self._per_query(N.lib.lbvh_capsule_overlaps_any, shapes, "CAPSULE", flags, np.uint32, "shapes", "flags")
+
+    def obb_overlaps(self, shapes, offsets, tris=None):
+        """The same for the oriented boxes of the DataBuffer `shapes` (layouts.OBB: centre and the half-axis vectors ax, ay, az; see
+        obb_shapes): every triangle each box touches, the start overlap of box_cast without a direction.  Asynchronous."""
+        self._overlaps(N.lib.lbvh_obb_overlaps, shapes, L.OBB, offsets, tris)
+
+    def obb_overlaps_any(self, shapes, flags):
+        """1 into the uint32 DataBuffer `flags` for each box of `shapes` that touches any triangle, else 0."""
+        self._per_query(N.lib.lbvh_obb_overlaps_any, shapes, "OBB", flags, np.uint32, "shapes", "flags")
+
+    def touching(self, shapes, min_capacity=1, device_sort=False):
+        """Convenience, as intersections(): count -> one 8-byte download -> allocate -> fill, for a DataBuffer of layouts.CAPSULE or
+        of layouts.OBB.  Returns (offsets, tris): host arrays, uint64[shapes.size + 1] and uint32[total].  device_sort=True issues
+        sort_index_segments before the download: every segment ascending."""
+        if shapes.dtype not in (L.CAPSULE, L.OBB):
+            raise ValueError("shapes must be a DataBuffer of layouts.CAPSULE or layouts.OBB")
+        return self._csr_lists(self.capsule_overlaps if shapes.dtype == L.CAPSULE else self.obb_overlaps, shapes, min_capacity, device_sort)
 
     def region_overlaps(self, regions, mode, offsets, tris=None):
         """Every triangle in each convex region of the DataBuffer `regions` (layouts.REGION: six planes {nx, ny, nz, d}, each keeping

@@ -62,6 +62,13 @@
 //                                                SortIndexSegments, TriangleIntersectsAny; prints the total, how many segments are
 //                                                non-empty, how many flags are set, the sum of (position + 1) * triangle index over
 //                                                the device-sorted list (mod 2^64) and the first segments
+//     lbvh_driver shapes <n_shapes> [seed]       the 4 096 triangles of cfg1 and n_shapes capsules and as many boxes (SplitMix64, seed
+//                                                default 7): per shape and axis k the capsule's origin uniform in the mesh's box and
+//                                                its axis component uniform in [-6, 6] (radius 3), then the box's centre uniform in
+//                                                the mesh's box and component k of ax, ay, az: 3 on the diagonal, 0 off it, plus
+//                                                uniform in [-1.5, 1.5].  CapsuleOverlaps / ObbOverlaps (count only, one 8-byte read,
+//                                                fill), SortIndexSegments, CapsuleOverlapsAny / ObbOverlapsAny; prints per family what
+//                                                `tris` prints
 //     lbvh_driver regions <n_regions> [seed] [large]  the 4 096 triangles of cfg1 and n_regions sheared boxes (SplitMix64, seed default 6):
 //                                                the centre uniform in the mesh's box, then per axis k a normal — the axis' unit
 //                                                vector with its two other components uniform in [-0.5, 0.5] — and a half width
@@ -654,6 +661,85 @@ static int tris_main(int argc, char** argv)
     return 0;
 }
 
+// one shape family of `shapes`: the CSR list (count only, one 8-byte read, fill), the device sort and the flags, printed as fields
+// of the line `shapes_main` opens
+template <class SHAPE, class LIST, class ANY>
+static void shape_lists(lbvh::Context& ctx, lbvh::RaytracingMeshDrawer& drawer, const lbvh::DataBuffer<SHAPE>& shapes, const char* name, LIST list, ANY any)
+{
+    const size_t count = shapes.Size();
+    lbvh::DataBuffer<uint64_t> offsets(ctx, count + 1);
+    list(shapes, offsets, nullptr);
+    offsets.GetData();
+    const unsigned long long total = offsets.LocalBuffer()[count];
+    lbvh::DataBuffer<uint32_t> tris(ctx, total ? (size_t)total : 1);
+    list(shapes, offsets, &tris);
+    drawer.SortIndexSegments(offsets, tris, count);
+    lbvh::DataBuffer<uint32_t> flags(ctx, count);
+    any(shapes, flags);
+    offsets.GetData();
+    tris.GetData();
+    flags.GetData();
+    size_t non_empty = 0, flagged = 0;
+    unsigned long long weighted = 0;
+    for (size_t i = 0; i < count; i++) {
+        non_empty += offsets.LocalBuffer()[i + 1] > offsets.LocalBuffer()[i];
+        flagged += flags.LocalBuffer()[i];
+    }
+    for (size_t i = 0; i < (size_t)total; i++) weighted += (unsigned long long)(i + 1) * tris.LocalBuffer()[i];
+    std::printf(", \"%s\": {\"total\": %llu, \"non_empty\": %zu, \"flagged\": %zu, \"weighted_index_sum\": %llu, \"segments\": [", name, total,
+                non_empty, flagged, weighted);
+    size_t shown = 0;
+    for (size_t i = 0; i < count && shown < 3; i++) {
+        const uint64_t first = offsets.LocalBuffer()[i], last = offsets.LocalBuffer()[i + 1];
+        if (first == last) continue;
+        std::printf("%s[%zu", shown++ ? ", " : "", i);
+        for (uint64_t j = first; j < last; j++) std::printf(", %u", tris.LocalBuffer()[j]);
+        std::printf("]");
+    }
+    std::printf("]}");
+}
+
+static int shapes_main(int argc, char** argv)
+{
+    const size_t count = argc > 2 ? (size_t)strtoull(argv[2], nullptr, 10) : 65536;
+    uint64_t seed = argc > 3 ? strtoull(argv[3], nullptr, 10) : 7;
+    const std::vector<lbvh_triangle> mesh = random_mesh(4096);
+    float lo[3], hi[3];
+    mesh_box(mesh, lo, hi);
+    lbvh::Context ctx(0);
+    lbvh::RaytracingMeshDrawer drawer(ctx, mesh);
+    drawer.Awake();
+    lbvh::DataBuffer<lbvh_capsule> capsules(ctx, count);
+    lbvh::DataBuffer<lbvh_obb> boxes(ctx, count);
+    const float half = 3.0f;
+    for (size_t i = 0; i < count; i++) {
+        lbvh_capsule& c = capsules.LocalBuffer()[i];
+        lbvh_obb& b = boxes.LocalBuffer()[i];
+        std::memset(&c, 0, sizeof c);
+        std::memset(&b, 0, sizeof b);
+        c.radius = 3.0f;
+        for (int k = 0; k < 3; k++) {
+            c.origin[k] = uniform(seed, lo[k], hi[k]);
+            c.axis[k] = uniform(seed, -6.0f, 6.0f);
+            b.centre[k] = uniform(seed, lo[k], hi[k]);
+            b.ax[k] = (k == 0 ? half : 0.0f) + uniform(seed, -0.5f * half, 0.5f * half);
+            b.ay[k] = (k == 1 ? half : 0.0f) + uniform(seed, -0.5f * half, 0.5f * half);
+            b.az[k] = (k == 2 ? half : 0.0f) + uniform(seed, -0.5f * half, 0.5f * half);
+        }
+    }
+    capsules.Sync();
+    boxes.Sync();
+    std::printf("{\"triangles\": %zu, \"shapes\": %zu", mesh.size(), count);
+    shape_lists(ctx, drawer, capsules, "capsule",
+                [&](const lbvh::DataBuffer<lbvh_capsule>& s, lbvh::DataBuffer<uint64_t>& o, lbvh::DataBuffer<uint32_t>* t) { drawer.CapsuleOverlaps(s, o, t); },
+                [&](const lbvh::DataBuffer<lbvh_capsule>& s, lbvh::DataBuffer<uint32_t>& f) { drawer.CapsuleOverlapsAny(s, f); });
+    shape_lists(ctx, drawer, boxes, "obb",
+                [&](const lbvh::DataBuffer<lbvh_obb>& s, lbvh::DataBuffer<uint64_t>& o, lbvh::DataBuffer<uint32_t>* t) { drawer.ObbOverlaps(s, o, t); },
+                [&](const lbvh::DataBuffer<lbvh_obb>& s, lbvh::DataBuffer<uint32_t>& f) { drawer.ObbOverlapsAny(s, f); });
+    std::printf("}\n");
+    return 0;
+}
+
 static int regions_main(int argc, char** argv)
 {
     const size_t count = argc > 2 ? (size_t)strtoull(argv[2], nullptr, 10) : 65536;
@@ -967,7 +1053,7 @@ int main(int argc, char** argv)
 {
     static const struct { const char* name; int (*run)(int, char**); } commands[] = {
         {"crossings", crossings_main}, {"points", points_main}, {"knn", knn_main},   {"khits", khits_main}, {"gather", gather_main}, {"sortedhits", sortedhits_main},
-        {"sweep", sweep_main},         {"capsule", capsule_main}, {"boxcast", boxcast_main},         {"overlaps", overlaps_main}, {"tris", tris_main}, {"regions", regions_main}, {"rays", rays_main}, {"sort", sort_main},   {"multi", multi_main}};
+        {"sweep", sweep_main},         {"capsule", capsule_main}, {"boxcast", boxcast_main},         {"overlaps", overlaps_main}, {"tris", tris_main}, {"shapes", shapes_main}, {"regions", regions_main}, {"rays", rays_main}, {"sort", sort_main},   {"multi", multi_main}};
     try {
         for (const auto& c : commands)
             if (argc > 1 && std::strcmp(argv[1], c.name) == 0) return c.run(argc, argv);

@@ -484,6 +484,39 @@ public:
         check(ctx_.get(), lbvh_triangle_intersects_any(ctx_.get(), (const lbvh_tri_query*)queries.DeviceBuffer(), queries.Size(), &s,
                                                        (uint32_t*)flags.DeviceBuffer()));
     }
+    // WHICH triangles each capsule (lbvh_capsule: origin, radius, axis) or oriented box (lbvh_obb: centre and the three half-axis
+    // vectors) touches where it stands — the start overlap of CapsuleCast / BoxCast without a direction —, as the same CSR list, or
+    // one flag per shape (lbvh_capsule_overlaps / _any, lbvh_obb_overlaps / _any; asynchronous)
+    void CapsuleOverlaps(const DataBuffer<lbvh_capsule>& shapes, DataBuffer<uint64_t>& offsets, DataBuffer<uint32_t>* tris = nullptr)
+    {
+        if (offsets.Size() < shapes.Size() + 1) throw Error(LBVH_ERR_INVALID_ARG, "CapsuleOverlaps: offsets needs one entry more than shapes");
+        const lbvh_scene s = container_->Scene();
+        check(ctx_.get(), lbvh_capsule_overlaps(ctx_.get(), (const lbvh_capsule*)shapes.DeviceBuffer(), shapes.Size(), &s,
+                                                (uint64_t*)offsets.DeviceBuffer(), tris ? (uint32_t*)tris->DeviceBuffer() : nullptr,
+                                                tris ? (uint64_t)tris->Size() : 0));
+    }
+    void CapsuleOverlapsAny(const DataBuffer<lbvh_capsule>& shapes, DataBuffer<uint32_t>& flags)
+    {
+        if (flags.Size() < shapes.Size()) throw Error(LBVH_ERR_INVALID_ARG, "CapsuleOverlapsAny: fewer flags than shapes");
+        const lbvh_scene s = container_->Scene();
+        check(ctx_.get(), lbvh_capsule_overlaps_any(ctx_.get(), (const lbvh_capsule*)shapes.DeviceBuffer(), shapes.Size(), &s,
+                                                    (uint32_t*)flags.DeviceBuffer()));
+    }
+    void ObbOverlaps(const DataBuffer<lbvh_obb>& shapes, DataBuffer<uint64_t>& offsets, DataBuffer<uint32_t>* tris = nullptr)
+    {
+        if (offsets.Size() < shapes.Size() + 1) throw Error(LBVH_ERR_INVALID_ARG, "ObbOverlaps: offsets needs one entry more than shapes");
+        const lbvh_scene s = container_->Scene();
+        check(ctx_.get(), lbvh_obb_overlaps(ctx_.get(), (const lbvh_obb*)shapes.DeviceBuffer(), shapes.Size(), &s,
+                                            (uint64_t*)offsets.DeviceBuffer(), tris ? (uint32_t*)tris->DeviceBuffer() : nullptr,
+                                            tris ? (uint64_t)tris->Size() : 0));
+    }
+    void ObbOverlapsAny(const DataBuffer<lbvh_obb>& shapes, DataBuffer<uint32_t>& flags)
+    {
+        if (flags.Size() < shapes.Size()) throw Error(LBVH_ERR_INVALID_ARG, "ObbOverlapsAny: fewer flags than shapes");
+        const lbvh_scene s = container_->Scene();
+        check(ctx_.get(), lbvh_obb_overlaps_any(ctx_.get(), (const lbvh_obb*)shapes.DeviceBuffer(), shapes.Size(), &s,
+                                                (uint32_t*)flags.DeviceBuffer()));
+    }
     // WHICH triangles lie in each convex region of six planes (a frustum, an oriented box, a selection window), as the same CSR
     // list, or one flag per region (lbvh_region_overlaps / lbvh_region_overlaps_any; asynchronous).  mode: LBVH_REGION_TOUCHING —
     // the triangle's own box is not wholly outside any plane — or LBVH_REGION_CONTAINED — it is wholly inside every plane.

@@ -54,6 +54,13 @@ assert POINT_QUERY.itemsize == 16 and CLOSEST_POINT.itemsize == 16
 # never a candidate (NULL below, LBVH_NULL: none)
 TRI_QUERY = np.dtype([("a", "<f4", 3), ("skip", "<u4"), ("b", "<f4", 3), ("_pad0", "<u4"), ("c", "<f4", 3), ("_pad1", "<u4")])
 assert TRI_QUERY.itemsize == 48
+# lbvh_capsule_overlaps / lbvh_obb_overlaps and their _any forms: a capsule (the segment origin .. origin + axis and the radius) and
+# an oriented box { centre + s0*ax + s1*ay + s2*az : |s_i| <= 1 } where they stand — CAPSULE_RAY and BOX_RAY without the motion;
+# the pads are not read
+CAPSULE = np.dtype([("origin", "<f4", 3), ("radius", "<f4"), ("axis", "<f4", 3), ("_pad", "<u4")])
+OBB = np.dtype([("centre", "<f4", 3), ("_pad0", "<u4"), ("ax", "<f4", 3), ("_pad1", "<u4"), ("ay", "<f4", 3), ("_pad2", "<u4"),
+                ("az", "<f4", 3), ("_pad3", "<u4")])
+assert CAPSULE.itemsize == 32 and OBB.itemsize == 64
 # lbvh_region_overlaps / lbvh_region_overlaps_any: six planes {nx, ny, nz, d}, each keeping n . x + d >= 0; the two modes
 REGION = np.dtype([("plane", "<f4", (6, 4))])
 assert REGION.itemsize == 96
