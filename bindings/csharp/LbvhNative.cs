@@ -53,6 +53,11 @@ public static class LbvhNative
     public struct Capsule { public float originX, originY, originZ, radius; public float axisX, axisY, axisZ; public uint pad; }
     [StructLayout(LayoutKind.Sequential)]
     public struct Obb { public float centreX, centreY, centreZ; public uint pad0; public float axX, axY, axZ; public uint pad1; public float ayX, ayY, ayZ; public uint pad2; public float azX, azY, azZ; public uint pad3; }
+    // lbvh_contact (include/lbvh.h): one contact of a capsule with a triangle, 32 bytes: depth = radius - distance of the axis from the
+    // triangle, the contact point a + e1*u + e2*v on the triangle, the unit push-out normal, the contact point origin + axis*s on the
+    // axis; tri = 0xFFFFFFFF in the none-record of lbvh_capsule_deepest (ShapeContacts.cs)
+    [StructLayout(LayoutKind.Sequential)]
+    public struct Contact { public float depth; public uint tri; public float u, v; public float normalX, normalY, normalZ; public float s; }
 
     // lbvh_point_query / lbvh_closest_point (include/lbvh.h): a point with its squared search radius (active iff maxDist2 > 0) and
     // the nearest triangle's record, 16 bytes each (PointQueries.cs)
@@ -178,6 +183,9 @@ public static class LbvhNative
     [DllImport(Lib)] public static extern int lbvh_capsule_overlaps(IntPtr ctx, IntPtr dShapes, UIntPtr count, ref Scene scene, IntPtr dOffsets,
         IntPtr dTris, ulong capacity);
     [DllImport(Lib)] public static extern int lbvh_capsule_overlaps_any(IntPtr ctx, IntPtr dShapes, UIntPtr count, ref Scene scene, IntPtr dFlags);
+    [DllImport(Lib)] public static extern int lbvh_capsule_contacts(IntPtr ctx, IntPtr dShapes, UIntPtr count, ref Scene scene, IntPtr dOffsets,
+        IntPtr dContacts, ulong capacity);
+    [DllImport(Lib)] public static extern int lbvh_capsule_deepest(IntPtr ctx, IntPtr dShapes, UIntPtr count, ref Scene scene, IntPtr dOut);
     [DllImport(Lib)] public static extern int lbvh_obb_overlaps(IntPtr ctx, IntPtr dShapes, UIntPtr count, ref Scene scene, IntPtr dOffsets,
         IntPtr dTris, ulong capacity);
     [DllImport(Lib)] public static extern int lbvh_obb_overlaps_any(IntPtr ctx, IntPtr dShapes, UIntPtr count, ref Scene scene, IntPtr dFlags);

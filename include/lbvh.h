@@ -1216,8 +1216,9 @@ typedef struct lbvh_obb { float centre[3]; uint32_t _pad0; float ax[3]; uint32_t
  * active shapes; triangle_tests counts the triangle lines read, whatever number of derived triangles or axes is tested; the full
  * form reports twice the count-only form's).
  * One shape per lane; the cost is that of a box overlap walk on boxes larger by the shape, plus one 64-byte triangle line and up
- * to eight point tests and a pierce (capsule) or thirteen axes (box) per triangle that passes rule 1.  Out of scope: penetration
- * depth or direction, a contact manifold, flat boxes, a form that spreads one huge shape over the device. */
+ * to eight point tests and a pierce (capsule) or thirteen axes (box) per triangle that passes rule 1.  The capsule's penetration
+ * depth and push-out direction per touched triangle are lbvh_capsule_contacts / lbvh_capsule_deepest below.  Out of scope: the
+ * box's penetration depth or direction, a contact manifold, flat boxes, a form that spreads one huge shape over the device. */
 lbvh_status lbvh_capsule_overlaps(lbvh_context* ctx, const lbvh_capsule* d_shapes, size_t count, const lbvh_scene* h_scene,
                                   uint64_t* d_offsets, uint32_t* d_tris, uint64_t capacity);
 lbvh_status lbvh_capsule_overlaps_any(lbvh_context* ctx, const lbvh_capsule* d_shapes, size_t count, const lbvh_scene* h_scene,
@@ -1226,6 +1227,75 @@ lbvh_status lbvh_obb_overlaps(lbvh_context* ctx, const lbvh_obb* d_shapes, size_
                               uint64_t* d_offsets, uint32_t* d_tris, uint64_t capacity);
 lbvh_status lbvh_obb_overlaps_any(lbvh_context* ctx, const lbvh_obb* d_shapes, size_t count, const lbvh_scene* h_scene,
                                   uint32_t* d_flags);
+
+/* One contact of a capsule with a triangle: 32 bytes, arrays 16-byte aligned. */
+typedef struct lbvh_contact {
+    float    depth;                /* radius - distance of the axis from the triangle; >= radius when the axis reaches the face */
+    uint32_t tri;                  /* ORIGINAL triangle index; LBVH_NULL in the none-record */
+    float    u, v;                 /* contact point on the triangle: a + e1*u + e2*v */
+    float    normal[3];            /* unit push-out direction, from the triangle towards the axis */
+    float    s;                    /* contact point on the axis: origin + axis*s, 0 <= s <= 1 */
+} lbvh_contact;
+
+/* Capsule contacts: HOW DEEP is a capsule in each triangle it touches, and WHICH WAY OUT (what a character controller asks after
+ * lbvh_capsule_overlaps: Physics.ComputePenetration; the per-triangle contacts of a mesh collider), as a CSR list of records
+ * (lbvh_capsule_contacts) or as the deepest record per shape (lbvh_capsule_deepest), over the derived traversal scene in its
+ * four-wide form by the walk of lbvh_capsule_overlaps.  The active rule, rule 1, rule 2 and therefore the candidate set are
+ * lbvh_capsule_overlaps' exactly, from the same operations on the same values: "touches" there and a record here never disagree.
+ *   The contact of a candidate (o = origin, h = axis, r = radius; the triangle line a, e1, e2), in strict fp32, every operation
+ *   rounded on its own, dot, cross, pierce, dist2 and the derived triangles as defined above:
+ *     1. Pierce first.  pierce(o, h; a, e1, e2) of lbvh_triangle_intersections is evaluated for every candidate.  If it passes,
+ *        0 <= t_p <= 1, the axis goes through the face: a FACE CONTACT (step 4) with s = t_p.  The centre lies inside the prism
+ *        "triangle + segment [0, -h]" exactly in this case, and only then are the distances to the prism's surface not the
+ *        distance of the axis from the triangle; so the pierce comes before the distances here, not after all eight fail.
+ *     2. Otherwise the nearest derived triangle: d_j = dist2 of lbvh_closest_point_query for o against derived triangle j = 0 .. 7
+ *        of lbvh_capsule_cast, with its barycentrics (u', v').  Start with least = +inf and j* = 0; in the order j = 0 .. 7, d_j
+ *        replaces least, and j replaces j*, only when d_j < least (strictly; false for a NaN).  s from j* exactly as
+ *        lbvh_capsule_cast derives it: 0 for j* = 0, 1 for j* = 1, v' for j* = 2, 4, 6 and 1 - v' for j* = 3, 5, 7.
+ *     3. On the scene triangle: x = o + h*s per component; (u, v), ap = x - a, the residual rv = ap - (e1*u + e2*v) per component
+ *        and dist2 = dot(rv, rv) are lbvh_closest_point_query's for x against a, e1, e2 — the residual is the vector from the
+ *        contact point to the axis.  If dist2 == 0 or dist2 is NaN: a face contact with this s, u, v (step 4).  Otherwise
+ *            dist = sqrt(dist2)      normal = rv / dist per component      depth = r - dist.
+ *        depth may be a rounding below zero for a candidate at the bound; it is NOT clamped, so that the list stays
+ *        lbvh_capsule_overlaps'.
+ *     4. Face contact.  N = cross(e1, e2), len = sqrt(dot(N, N)).  If len is 0 or NaN (a degenerate triangle): normal = (0, 0, 0),
+ *        depth = r.  Otherwise
+ *            g0 = dot(N, o - a)      g1 = dot(N, (o + h) - a)      sign = +1 if g0 + g1 >= 0, else -1
+ *            normal = (sign * N) / len per component      depth = r + fmaxf(fmaxf(-sign * g0, -sign * g1), 0) / len
+ *        sign is the side the middle of the axis is on, and depth the push along normal that brings the whole axis to the distance
+ *        r from the triangle's plane.  In the pierce case (u, v) are lbvh_closest_point_query's for x = o + h*t_p, as in the cast.
+ * Output of lbvh_capsule_contacts — lbvh_capsule_overlaps' CSR contract with a record in place of an index:
+ *   d_offsets: count + 1 words of 64 bits, the SAME words lbvh_capsule_overlaps writes for these shapes.  Always written in full.
+ *   d_contacts, `capacity` records of 32 bytes: segment k = d_contacts[d_offsets[k] .. d_offsets[k+1]) = one record per candidate
+ *   of shape k, each triangle exactly once.  THE ORDER INSIDE A SEGMENT IS THE WALK'S AND IS NOT PART OF THE CONTRACT.
+ *   Overflow: no record at index >= capacity is ever written; every segment with d_offsets[k+1] <= capacity is complete; records
+ *   below `capacity` that belong to a segment which does not fit are unspecified.  The call never waits on the host and returns
+ *   LBVH_OK in both cases: the caller reads d_offsets[count] to learn what was needed.
+ *   Count-only form: capacity == 0 writes the offsets and walks once (d_contacts may be NULL) — it IS lbvh_capsule_overlaps'
+ *   count-only form; otherwise the scene is walked twice (that count walk, the device-side scan, a fill walk that makes the
+ *   same decisions from the same values and forms the records).  d_contacts == NULL with capacity > 0 is LBVH_ERR_INVALID_ARG.
+ * Output of lbvh_capsule_deepest: d_out[k] = the contact of shape k with the greatest depth (compared as fp32 values); on equal
+ *   depth the lower original triangle index, whatever order the walk meets them in.  A shape with no candidate, or an inactive
+ *   shape: the none-record {0, LBVH_NULL, 0, 0, {0, 0, 0}, 0}.  Every one of the `count` records is written.  One walk, no scan.
+ *   Nothing can be pruned beyond rule 1: depth has no bound from a box that is monotone in the box — the depth of a face contact
+ *   grows with how far the axis reaches THROUGH the triangle, which a box around the triangle says nothing about, and a shallow
+ *   contact found first excludes no subtree —, so the walk is lbvh_capsule_overlaps' and visits every candidate.
+ * Both need the derived traversal scene (lbvh_build_fast_scene; a stale one is LBVH_ERR_INVALID_ARG), are asynchronous on the
+ * context's stream with no host wait, and use the context's ray scratch: they drop the path tracer's live-path list (see
+ * lbvh_path_bounce).  count == 0 is a no-op: nothing is enqueued and no buffer is touched, d_offsets[0] included.  Rejected: NULL
+ * ctx / d_shapes / h_scene / d_offsets / d_out, d_shapes, d_contacts or d_out not 16-byte aligned, d_offsets not 8-byte aligned,
+ * count > 2^32 - 1.  Four-wide walk only; lbvh_debug_ray_waves, lbvh_debug_ray_stack_split, lbvh_debug_ray_stack_limit and
+ * lbvh_ray_stats_target apply as to lbvh_capsule_overlaps (the full form reports the count walk's plus the fill walk's triangle
+ * lines: twice the count-only form's).
+ * Cost: a walk of these two visits what lbvh_capsule_overlaps' visits, but no derived triangle ends the loop over the eight, the
+ * pierce is evaluated for every triangle that passes rule 1, a candidate takes a ninth point test, and a record is 32 bytes.
+ * Out of scope: box and sheared-box contacts (the least-overlap axis of the thirteen); a manifold of more than one point per
+ * triangle; a device-side sort of contact segments (lbvh_sort_hit_segments is for 16-byte records); a form that spreads one huge
+ * capsule over the device. */
+lbvh_status lbvh_capsule_contacts(lbvh_context* ctx, const lbvh_capsule* d_shapes, size_t count, const lbvh_scene* h_scene,
+                                  uint64_t* d_offsets, lbvh_contact* d_contacts, uint64_t capacity);
+lbvh_status lbvh_capsule_deepest(lbvh_context* ctx, const lbvh_capsule* d_shapes, size_t count, const lbvh_scene* h_scene,
+                                 lbvh_contact* d_out);
 
 /* A convex region bounded by six planes: 96 bytes; arrays of them 16-byte aligned.  A plane {nx, ny, nz, d} keeps the half space
  * n . x + d >= 0; the region is the intersection of its six half spaces.  Normals need not be unit length.  A region with fewer
@@ -1351,7 +1421,7 @@ lbvh_status lbvh_path_scatter(lbvh_context* ctx, const lbvh_scene* h_scene, cons
  * lbvh_path_bounce on the same d_states / d_hits listed as live (a list kept by the context).  Every library call that writes
  * into those buffers drops the list (lbvh_path_begin, lbvh_trace_rays, a primary trace into any part of d_hits,
  * lbvh_buffer_upload / _fill_u32 / _free), and so does lbvh_trace_forget — and so do lbvh_trace_closest,
- * lbvh_trace_occluded, lbvh_closest_point_query, lbvh_within_distance, lbvh_count_hits, lbvh_point_crossings, lbvh_box_overlaps, lbvh_gather_within_distance, lbvh_k_closest_points, lbvh_trace_k_closest, lbvh_gather_hits, lbvh_sphere_cast, lbvh_sphere_cast_any, lbvh_capsule_cast, lbvh_capsule_cast_any, lbvh_box_cast, lbvh_box_cast_any, lbvh_triangle_intersections, lbvh_triangle_intersects_any, lbvh_capsule_overlaps, lbvh_capsule_overlaps_any, lbvh_obb_overlaps, lbvh_obb_overlaps_any, lbvh_region_overlaps, lbvh_region_overlaps_any and lbvh_region_overlaps_large, whatever buffers they are given, since they use the same ray scratch; then every state is scanned again.  The one exception among the query calls:
+ * lbvh_trace_occluded, lbvh_closest_point_query, lbvh_within_distance, lbvh_count_hits, lbvh_point_crossings, lbvh_box_overlaps, lbvh_gather_within_distance, lbvh_k_closest_points, lbvh_trace_k_closest, lbvh_gather_hits, lbvh_sphere_cast, lbvh_sphere_cast_any, lbvh_capsule_cast, lbvh_capsule_cast_any, lbvh_box_cast, lbvh_box_cast_any, lbvh_triangle_intersections, lbvh_triangle_intersects_any, lbvh_capsule_overlaps, lbvh_capsule_overlaps_any, lbvh_obb_overlaps, lbvh_obb_overlaps_any, lbvh_capsule_contacts, lbvh_capsule_deepest, lbvh_region_overlaps, lbvh_region_overlaps_any and lbvh_region_overlaps_large, whatever buffers they are given, since they use the same ray scratch; then every state is scanned again.  The one exception among the query calls:
  * lbvh_sort_hit_segments and lbvh_sort_index_segments take no context scratch and keep the live-path list (they drop it only when the
  * buffer they sort is d_hits itself).  What the library
  * cannot see is a write of the CALLER's own (a kernel or hipMemcpy that revives or ends paths, Russian roulette): between two

@@ -2532,6 +2532,188 @@ __global__ __launch_bounds__(64) void shape_overlap_wide_kernel(const float4* __
     if (STATS) add_ray_stats(stats, n_shapes, n_steps, n_tris);
 }
 
+// ---- capsule contacts: how deep a capsule is in each triangle it touches, and which way out (lbvh_capsule_contacts, --------
+// lbvh_capsule_deepest, include/lbvh.h).  The frame and the slot test of shape_overlap_wide_kernel<kShapeCapsule>; the count walk
+// of lbvh_capsule_contacts IS that kernel's kTriCount form.  kContactFill writes a 32-byte record where the overlap's fill walk
+// writes an index; kContactDeepest keeps the deepest record of the lane's shape in registers and writes it when the walk ends.
+enum contact_mode : int { kContactFill = 0, kContactDeepest = 1 };
+
+// The header's contact of a capsule (origin o, axis h, radius r) with the triangle line (a, e1, e2); false: not a candidate.
+// The decision is capsule_touches' on the same values — `within` is some d_j <= R2 over the same eight dist2, the pierce is the
+// same call —, but no derived triangle ends the loop: the least d_j picks s.  One copy of the point test in one rolled loop that
+// leaves through its condition (as capsule_touches): j = 0 .. 7 the derived triangles at o, j = 8 the scene triangle at
+// x = o + h*s, entered by candidates only.  rec0 = {depth, tri (set by the caller), u, v}, rec1 = {normal, s}.
+__device__ __forceinline__ bool capsule_contact_of(const ray_t& o, float r, float hx, float hy, float hz, const float4 a, const float4 e1,
+                                                   const float4 e2, float4& rec0, float4& rec1)
+{
+    ray_t ax;
+    ax.ox = o.ox; ax.oy = o.oy; ax.oz = o.oz;
+    ax.dx = hx; ax.dy = hy; ax.dz = hz;
+    ax.ix = 0.0f; ax.iy = 0.0f; ax.iz = 0.0f;            // (not read by the triangle test)
+    float pu = 0.0f, pv = 0.0f;
+    const float tp = ray_triangle_edges(ax, a, e1.x, e1.y, e1.z, e2.x, e2.y, e2.z, pu, pv);
+    const bool pierced = 0.0f <= tp && tp <= 1.0f;
+    const float R2 = r * r;
+    bool within = false;
+    float least = __builtin_inff(), least_v = 0.0f;
+    uint32_t which = 0u;
+    float s = 0.0f, dist2 = 0.0f, u = 0.0f, v = 0.0f;
+#pragma nounroll
+    for (uint32_t j = 0; j < 9u && (j < 8u || within || pierced); j++) {
+        const bool last = j == 8u;
+        // s as lbvh_capsule_cast derives it from the winning j: 0, 1, v' or 1 - v'; t_p for the pierce (read at j = 8 only)
+        s = pierced ? tp : (which == 0u ? 0.0f : (which == 1u ? 1.0f : ((which & 1u) ? 1.0f - least_v : least_v)));
+        float4 p, q1, q2;
+        capsule_triangle(last ? 0u : j, a, e1, e2, hx, hy, hz, p, q1, q2);
+        const float px = last ? o.ox + hx * s : o.ox, py = last ? o.oy + hy * s : o.oy, pz = last ? o.oz + hz * s : o.oz;
+        float uj, vj;
+        const float d = point_triangle2(px, py, pz, p, q1, q2, uj, vj);
+        if (last) { dist2 = d; u = uj; v = vj; }
+        else {
+            within = within || d <= R2;
+            if (d < least) { least = d; which = j; least_v = vj; }     // strictly less; false for a NaN
+        }
+    }
+    if (!(within || pierced)) return false;
+    float depth, nx, ny, nz;
+    if (!pierced && dist2 > 0.0f) {                      // the residual of point_triangle2 at x, divided by its length
+        const float apx = (o.ox + hx * s) - a.x, apy = (o.oy + hy * s) - a.y, apz = (o.oz + hz * s) - a.z;
+        const float rx = apx - (e1.x * u + e2.x * v), ry = apy - (e1.y * u + e2.y * v), rz = apz - (e1.z * u + e2.z * v);
+        const float dist = sqrtf(dist2);
+        nx = rx / dist; ny = ry / dist; nz = rz / dist;
+        depth = r - dist;
+    } else {                                             // face contact: the axis pierces the face, or x lies on the triangle
+        const float Nx = e1.y * e2.z - e1.z * e2.y, Ny = e1.z * e2.x - e1.x * e2.z, Nz = e1.x * e2.y - e1.y * e2.x;
+        const float len = sqrtf(dot3(Nx, Ny, Nz, Nx, Ny, Nz));
+        if (len == 0.0f || len != len) { nx = 0.0f; ny = 0.0f; nz = 0.0f; depth = r; }
+        else {
+            const float g0 = dot3(Nx, Ny, Nz, o.ox - a.x, o.oy - a.y, o.oz - a.z);
+            const float g1 = dot3(Nx, Ny, Nz, (o.ox + hx) - a.x, (o.oy + hy) - a.y, (o.oz + hz) - a.z);
+            const float sign = g0 + g1 >= 0.0f ? 1.0f : -1.0f;
+            nx = (sign * Nx) / len; ny = (sign * Ny) / len; nz = (sign * Nz) / len;
+            depth = r + fmaxf(fmaxf(-sign * g0, -sign * g1), 0.0f) / len;
+        }
+    }
+    rec0.x = depth; rec0.z = u; rec0.w = v;
+    rec1 = make_float4(nx, ny, nz, s);
+    return true;
+}
+
+template <int MODE, bool STATS>
+__global__ __launch_bounds__(64) void capsule_contact_wide_kernel(const lbvh_capsule* __restrict__ capsules, uint32_t total,
+                                                                  const lbvh_wide_node* __restrict__ wide,
+                                                                  const lbvh_fast_node* __restrict__ lines,
+                                                                  const uint64_t* __restrict__ offsets,     // kContactFill: where segment k starts
+                                                                  lbvh_contact* __restrict__ out,           // kContactFill: the records; kContactDeepest: one per shape
+                                                                  uint64_t capacity,                        // kContactFill: records in `out`
+                                                                  uint32_t* __restrict__ deep,     // [gridDim.x][kWideStackDeep][64]
+                                                                  uint32_t lds_depth,              // <= kWideStackLds
+                                                                  uint32_t deep_cap,               // <= kWideStackDeep
+                                                                  uint32_t* __restrict__ fault, lbvh_ray_stats* stats)
+{
+    __shared__ uint32_t s_stack[kWideStackLds][LBVH_WAVE];
+    uint32_t* my_deep = deep + (size_t)blockIdx.x * (kWideStackDeep * LBVH_WAVE) + threadIdx.x;
+    const float4* shapes = reinterpret_cast<const float4*>(capsules);
+    float4* records = reinterpret_cast<float4*>(out);
+    const uint32_t lane = threadIdx.x;
+    const uint32_t run = max((total + gridDim.x - 1) / gridDim.x, 32u);
+    uint32_t next = blockIdx.x * run;
+    if (next >= total) return;
+    const uint32_t end = min(next + run, total);
+    uint32_t n_shapes = 0, n_steps = 0, n_tris = 0;
+
+    bool active = false;
+    uint32_t i = 0;
+    ray_t o = {};                                        // the origin (the direction is not read)
+    float r = 0.0f, hx = 0.0f, hy = 0.0f, hz = 0.0f;
+    uint32_t sp = 0, node = 0;
+    uint64_t pos = 0;                                    // kContactFill: where this lane's next record goes
+    float4 best0 = {}, best1 = {};                       // kContactDeepest: the deepest record so far
+    const float4 none0 = make_float4(0.0f, __uint_as_float(LBVH_NULL), 0.0f, 0.0f), none1 = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    auto push = [&](uint32_t ref) {
+        if (sp < lds_depth) { s_stack[sp][lane] = ref; sp++; }
+        else if (sp < lds_depth + deep_cap) { my_deep[(sp - lds_depth) * LBVH_WAVE] = ref; sp++; }
+        // a dropped entry would be a silently short list: report it, as the other walkers do (lbvh_debug_ray_stack_limit provokes it)
+        else __hip_atomic_store(fault, LBVH_FAULT_RAY_STACK, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    };
+    for (;;) {
+        const uint64_t idle = __ballot(!active);
+        if (idle != 0 && next < end) {
+            if (!active) {
+                const uint32_t k = next + mbcnt64(idle);
+                if (k < end) {
+                    i = k;
+                    const float inf = __builtin_inff();
+                    const float4 q0 = shapes[2 * (size_t)k], q1 = shapes[2 * (size_t)k + 1];
+                    o.ox = q0.x; o.oy = q0.y; o.oz = q0.z; r = q0.w;
+                    hx = q1.x; hy = q1.y; hz = q1.z;
+                    active = r > 0.0f && r < inf && (q0.x == q0.x && q0.y == q0.y && q0.z == q0.z) &&
+                             fabsf(hx) < inf && fabsf(hy) < inf && fabsf(hz) < inf;
+                    sp = 0; node = 0;
+                    if constexpr (MODE == kContactFill) { if (active) pos = offsets[k]; }
+                    else {
+                        best0 = none0; best1 = none1;
+                        if (!active) { records[2 * (size_t)k] = none0; records[2 * (size_t)k + 1] = none1; }
+                    }
+                    if (STATS && active) n_shapes++;
+                }
+            }
+            next += (uint32_t)__popcll(idle);
+        }
+        if (!__any(active) && next >= end) break;
+        if (active) {
+            if (STATS) n_steps++;
+            const float4* w = reinterpret_cast<const float4*>(&wide[node]);
+            const float4 lox = w[0], loy = w[1], loz = w[2], hix = w[3], hiy = w[4], hiz = w[5];
+            const uint4 ref = reinterpret_cast<const uint4*>(w)[6];
+            const float ux = fmaxf(hx, 0.0f), uy = fmaxf(hy, 0.0f), uz = fmaxf(hz, 0.0f);
+            const float vx = fminf(hx, 0.0f), vy = fminf(hy, 0.0f), vz = fminf(hz, 0.0f);
+#define SHAPE_SLOT(c)                                                                                                                  \
+    (shape_in_grown<kShapeCapsule>(lox.c, hix.c, o.ox, ux, vx, r) && shape_in_grown<kShapeCapsule>(loy.c, hiy.c, o.oy, uy, vy, r) &&  \
+     shape_in_grown<kShapeCapsule>(loz.c, hiz.c, o.oz, uz, vz, r) && ref.c != kWideEmpty)
+            const bool h0 = SHAPE_SLOT(x), h1 = SHAPE_SLOT(y), h2 = SHAPE_SLOT(z), h3 = SHAPE_SLOT(w);
+#undef SHAPE_SLOT
+            const uint32_t hit = (h0 ? 1u : 0u) | (h1 ? 2u : 0u) | (h2 ? 4u : 0u) | (h3 ? 8u : 0u);
+            const uint32_t leaf = (ref.x >> 31) | ((ref.y >> 31) << 1) | ((ref.z >> 31) << 2) | ((ref.w >> 31) << 3);
+            uint32_t leaves = hit & leaf, inner = hit & ~leaf;
+            while (leaves != 0u) {
+                const uint32_t k = (uint32_t)__builtin_ctz(leaves);
+                leaves &= leaves - 1u;
+                const uint32_t line = pick4(ref, k) & 0x7FFFFFFFu;
+                float4 t0, t1, t2;
+                unpack_fast_triangle(reinterpret_cast<const float4*>(&lines[line]), t0, t1, t2);
+                if (STATS) n_tris++;
+                float4 rec0, rec1;
+                rec0.y = t0.w;                                   // the ORIGINAL triangle index
+                if (!capsule_contact_of(o, r, hx, hy, hz, t0, t1, t2, rec0, rec1)) continue;
+                if constexpr (MODE == kContactFill) {
+                    if (pos < capacity) { records[2 * pos] = rec0; records[2 * pos + 1] = rec1; }     // never a record at or beyond the capacity
+                    pos++;
+                } else {
+                    // the greatest depth; on equal depth the lower original index (the none-record's index is above every one)
+                    const uint32_t tri = __float_as_uint(rec0.y), best_tri = __float_as_uint(best0.y);
+                    if (best_tri == LBVH_NULL || rec0.x > best0.x || (!(rec0.x < best0.x) && tri < best_tri)) { best0 = rec0; best1 = rec1; }
+                }
+            }
+            if (inner != 0u) {
+                node = pick4(ref, (uint32_t)__builtin_ctz(inner));
+                inner &= inner - 1u;
+                while (inner != 0u) {
+                    push(pick4(ref, (uint32_t)__builtin_ctz(inner)));
+                    inner &= inner - 1u;
+                }
+            } else if (sp != 0) {
+                sp--;
+                node = sp < lds_depth ? s_stack[sp][lane] : my_deep[(sp - lds_depth) * LBVH_WAVE];
+            } else {
+                if constexpr (MODE == kContactDeepest) { records[2 * (size_t)i] = best0; records[2 * (size_t)i + 1] = best1; }
+                active = false;
+            }
+        }
+    }
+    if (STATS) add_ray_stats(stats, n_shapes, n_steps, n_tris);
+}
+
 // ---- region queries: which triangles lie in a convex region of six planes (lbvh_region_overlaps, include/lbvh.h) ---------
 // The frame of overlap_wide_kernel<BOX = true> with another slot test: a slot is entered iff for each of the six planes
 // {nx, ny, nz, d} the box corner farthest along the normal is on the kept side, P = ((nx * X + ny * Y) + nz * Z) + d >= 0 with
@@ -3321,6 +3503,10 @@ static lbvh_status launch_per_query(lbvh_context* ctx, const QUERY* d_queries, s
     if constexpr (std::is_same_v<QUERY, lbvh_point_query>) PER_QUERY_WALK(point_query_wide_kernel);
     else if constexpr (std::is_same_v<QUERY, lbvh_sphere_ray>) PER_QUERY_WALK(sphere_cast_wide_kernel);
     else if constexpr (std::is_same_v<QUERY, lbvh_capsule_ray>) PER_QUERY_WALK(capsule_cast_wide_kernel);
+    else if constexpr (std::is_same_v<QUERY, lbvh_capsule>)          // lbvh_capsule_deepest: the contact walk's one-record form
+        LBVH_LAUNCH_STATS(ctx, ctx->ray_stats, (capsule_contact_wide_kernel<kContactDeepest, STATS>), dim3(w.waves), dim3(LBVH_WAVE), d_queries,
+                          (uint32_t)count, w.wn, ctx->fast_nodes, (const uint64_t*)nullptr, d_out, (uint64_t)0, w.deep, w.lds, w.deep_cap,
+                          ctx->fault_dev, ctx->ray_stats);
     else PER_QUERY_WALK(box_cast_wide_kernel);
 #undef PER_QUERY_WALK
     LBVH_HIP_TRY(ctx, hipGetLastError());
@@ -3501,6 +3687,46 @@ static lbvh_status shape_overlaps(lbvh_context* ctx, const void* d_shapes, size_
     }
 }
 
+// lbvh_capsule_contacts: shape_overlaps<kShapeCapsule, false> with a record in place of an index — the count walk is that
+// function's, the fill walk forms the contacts.  lbvh_capsule_deepest: one record per shape through launch_per_query.
+static lbvh_status capsule_contacts(lbvh_context* ctx, const lbvh_capsule* d_shapes, size_t count, const lbvh_scene* h_scene, uint64_t* d_offsets,
+                                    lbvh_contact* d_contacts, uint64_t capacity, const char* who)
+{
+    if (!ctx) return LBVH_ERR_INVALID_ARG;
+    if (count == 0) return LBVH_OK;
+    NAMED_REQUIRE(d_shapes != nullptr && h_scene != nullptr && d_offsets != nullptr);
+    NAMED_REQUIRE(d_contacts != nullptr || capacity == 0);
+    NAMED_REQUIRE(((uintptr_t)d_shapes & 15) == 0 && ((uintptr_t)d_offsets & 7) == 0 && ((uintptr_t)d_contacts & 15) == 0);
+    NAMED_REQUIRE(count <= 0xFFFFFFFFull);
+    walk_launch w;
+    const lbvh_status rc = begin_walk(ctx, h_scene, count, who, true, &w);
+    if (rc != LBVH_OK) return rc;
+    const uint32_t total = (uint32_t)count;
+    return csr_query(
+        ctx, count, d_offsets, capacity,
+        [&](uint32_t* counts) {
+            LBVH_LAUNCH_STATS(ctx, ctx->ray_stats, (shape_overlap_wide_kernel<kShapeCapsule, kTriCount, STATS>), dim3(w.waves), dim3(LBVH_WAVE),
+                              (const float4*)d_shapes, total, w.wn, ctx->fast_nodes, counts, (const uint64_t*)nullptr, (uint32_t*)nullptr, (uint64_t)0,
+                              w.deep, w.lds, w.deep_cap, ctx->fault_dev, ctx->ray_stats);
+        },
+        [&] {
+            LBVH_LAUNCH_STATS(ctx, ctx->ray_stats, (capsule_contact_wide_kernel<kContactFill, STATS>), dim3(w.waves), dim3(LBVH_WAVE), d_shapes, total,
+                              w.wn, ctx->fast_nodes, (const uint64_t*)d_offsets, d_contacts, capacity, w.deep, w.lds, w.deep_cap, ctx->fault_dev,
+                              ctx->ray_stats);
+        });
+}
+
+static lbvh_status capsule_deepest(lbvh_context* ctx, const lbvh_capsule* d_shapes, size_t count, const lbvh_scene* h_scene, lbvh_contact* d_out,
+                                   const char* who)
+{
+    if (!ctx) return LBVH_ERR_INVALID_ARG;
+    if (count == 0) return LBVH_OK;
+    NAMED_REQUIRE(d_shapes != nullptr && h_scene != nullptr && d_out != nullptr);
+    NAMED_REQUIRE(((uintptr_t)d_shapes & 15) == 0 && ((uintptr_t)d_out & 15) == 0);
+    NAMED_REQUIRE(count <= 0xFFFFFFFFull);
+    return launch_per_query<false>(ctx, d_shapes, count, h_scene, d_out, who);
+}
+
 // lbvh_region_overlaps: a CSR answer; lbvh_region_overlaps_any: one launch, the flags are the walk's own output.  Four-wide walk only.
 // (a rejection names the entry point, as the stale-scene message of begin_walk does)
 template <bool ANY>
@@ -3645,6 +3871,18 @@ lbvh_status lbvh_capsule_overlaps_any(lbvh_context* ctx, const lbvh_capsule* d_s
                                       uint32_t* d_flags)
 {
     return shape_overlaps<kShapeCapsule, true>(ctx, d_shapes, count, h_scene, nullptr, nullptr, 0, d_flags, "lbvh_capsule_overlaps_any");
+}
+
+lbvh_status lbvh_capsule_contacts(lbvh_context* ctx, const lbvh_capsule* d_shapes, size_t count, const lbvh_scene* h_scene,
+                                  uint64_t* d_offsets, lbvh_contact* d_contacts, uint64_t capacity)
+{
+    return capsule_contacts(ctx, d_shapes, count, h_scene, d_offsets, d_contacts, capacity, "lbvh_capsule_contacts");
+}
+
+lbvh_status lbvh_capsule_deepest(lbvh_context* ctx, const lbvh_capsule* d_shapes, size_t count, const lbvh_scene* h_scene,
+                                 lbvh_contact* d_out)
+{
+    return capsule_deepest(ctx, d_shapes, count, h_scene, d_out, "lbvh_capsule_deepest");
 }
 
 lbvh_status lbvh_obb_overlaps(lbvh_context* ctx, const lbvh_obb* d_shapes, size_t count, const lbvh_scene* h_scene,

@@ -93,6 +93,46 @@ def obb_shapes(centre, half_extents, rotation3x3=None):
     return out if out.ndim else out.reshape(1)
 
 
+class _DeviceWords:
+    """`count` 32-bit floats at a device pointer, for torch.as_tensor (zero copy)"""
+
+    def __init__(self, ptr, count):
+        self.__cuda_array_interface__ = {"shape": (int(count),), "typestr": "<f4", "data": (int(ptr), False), "version": 2, "strides": None}
+
+
+def push_out(drawer, shapes, skin, iterations=4):
+    """What capsule_deepest is for, as a convenience: up to `iterations` times, ask for the deepest contact of every capsule of the
+    DataBuffer `shapes` (layouts.CAPSULE) and move every capsule with depth > 0 by normal * (depth + skin), in place on the device
+    (torch); stop when no depth is > 0.  Returns (shapes, depths): the same DataBuffer and the float32 host array of the depths
+    that capsule_deepest reports for the final positions (0 for a capsule that touches nothing).  One contact is resolved per
+    iteration and capsule: a corner of k planes needs about k iterations.  Waits on the host in every iteration; not part of
+    the word-for-word contract of include/lbvh.h."""
+    import torch
+    if shapes.dtype != L.CAPSULE:
+        raise ValueError("shapes must be a DataBuffer of layouts.CAPSULE")
+    if not torch.cuda.is_available():
+        # (a torch that brings a HIP runtime of its own sees the GPU only if it was imported before this package loaded the library)
+        raise RuntimeError("push_out needs torch on the GPU: import torch before unitysimpleraytracing_amd")
+    ctx, n = drawer.ctx, shapes.size
+    dev = torch.device("cuda", ctx.device_id)
+    out = DataBuffer(ctx, n, L.CONTACT)
+    try:
+        caps = torch.as_tensor(_DeviceWords(shapes.device.value, n * 8), device=dev).view(n, 8)
+        recs = torch.as_tensor(_DeviceWords(out.device.value, n * 8), device=dev).view(n, 8)
+        for it in range(int(iterations) + 1):
+            drawer.capsule_deepest(shapes, out)
+            ctx.sync()                                              # the library's stream is not torch's
+            deep = recs[:, 0] > 0
+            if it == int(iterations) or not bool(deep.any()):
+                break
+            caps[:, 0:3] += torch.where(deep[:, None], recs[:, 4:7] * (recs[:, 0:1] + float(skin)), torch.zeros_like(recs[:, 4:7]))
+            torch.cuda.synchronize(dev)
+        shapes._synced = False
+        return shapes, out.get_data()["depth"].copy()
+    finally:
+        out.dispose()
+
+
 def box_cast_axis(cast, triangle_line, axis):
     """L_j of include/lbvh.h (lbvh_box_cast) for j = axis < 13, in float64 from the fp32 values: `cast` one layouts.BOX_RAY record,
     `triangle_line` = (a, e1, e2) of the reported triangle (e1 = b - a, e2 = c - a)."""
@@ -669,6 +709,36 @@ class RaytracingMeshDrawer:
         if shapes.dtype not in (L.CAPSULE, L.OBB):
             raise ValueError("shapes must be a DataBuffer of layouts.CAPSULE or layouts.OBB")
         return self._csr_lists(self.capsule_overlaps if shapes.dtype == L.CAPSULE else self.obb_overlaps, shapes, min_capacity, device_sort)
+
+    def capsule_contacts(self, shapes, offsets, contacts=None):
+        """How deep each capsule of the DataBuffer `shapes` (layouts.CAPSULE) is in every triangle it touches, and which way out:
+        capsule_overlaps with a layouts.CONTACT record (depth, tri, the contact point's u, v on the triangle, the unit push-out
+        normal, the contact point's parameter s on the axis) in place of an index.  `offsets` (uint64 DataBuffer, at least
+        shapes.size + 1 entries) receives the words capsule_overlaps writes; `contacts` (layouts.CONTACT DataBuffer, its size is the
+        capacity) the records, segment k = contacts[offsets[k] : offsets[k + 1]], in no particular order; contacts=None counts
+        only.  Asynchronous."""
+        if shapes.dtype != L.CAPSULE or offsets.dtype != np.uint64 or offsets.size < shapes.size + 1 or \
+                (contacts is not None and contacts.dtype != L.CONTACT):
+            raise ValueError("shapes must be a DataBuffer of layouts.CAPSULE, offsets one of uint64 with one entry more, contacts one of "
+                             "layouts.CONTACT or None")
+        s = self.container.scene()
+        N.check(self.ctx.handle, N.lib.lbvh_capsule_contacts(self.ctx.handle, shapes.device, shapes.size, C.byref(s), offsets.device,
+                                                             contacts.device if contacts is not None else None,
+                                                             contacts.size if contacts is not None else 0))
+
+    def capsule_deepest(self, shapes, out):
+        """The deepest contact of each capsule of `shapes` (layouts.CAPSULE) into the DataBuffer `out` (layouts.CONTACT): the record
+        with the greatest depth, ties to the lower triangle index; tri = layouts.NULL and zeros for a capsule that touches nothing.
+        Asynchronous; read with out.get_data()."""
+        self._per_query(N.lib.lbvh_capsule_deepest, shapes, "CAPSULE", out, L.CONTACT, "shapes")
+
+    def contacts(self, shapes, min_capacity=1):
+        """Convenience, as touching(): count -> one 8-byte download -> allocate -> fill, for a DataBuffer of layouts.CAPSULE.
+        Returns (offsets, contacts): host arrays, uint64[shapes.size + 1] and layouts.CONTACT[total], every segment in the walk's
+        order."""
+        if shapes.dtype != L.CAPSULE:
+            raise ValueError("shapes must be a DataBuffer of layouts.CAPSULE")
+        return self._csr_lists(self.capsule_contacts, shapes, min_capacity, False, dtype=L.CONTACT)
 
     def region_overlaps(self, regions, mode, offsets, tris=None):
         """Every triangle in each convex region of the DataBuffer `regions` (layouts.REGION: six planes {nx, ny, nz, d}, each keeping

@@ -69,6 +69,12 @@
 //                                                uniform in [-1.5, 1.5].  CapsuleOverlaps / ObbOverlaps (count only, one 8-byte read,
 //                                                fill), SortIndexSegments, CapsuleOverlapsAny / ObbOverlapsAny; prints per family what
 //                                                `tris` prints
+//     lbvh_driver contacts <n_shapes> [seed]     the same mesh and n_shapes capsules (SplitMix64, seed default 11): per capsule and
+//                                                axis k the origin uniform in the mesh's box and the axis component uniform in [-6, 6]
+//                                                (radius 3).  CapsuleContacts (count only, one 8-byte read, fill) and CapsuleDeepest;
+//                                                prints the total, how many segments are non-empty, how many capsules touch, the
+//                                                order-free sum of the records' words, the same of the deepest records weighted by
+//                                                shape, and the first deepest records as words
 //     lbvh_driver regions <n_regions> [seed] [large]  the 4 096 triangles of cfg1 and n_regions sheared boxes (SplitMix64, seed default 6):
 //                                                the centre uniform in the mesh's box, then per axis k a normal — the axis' unit
 //                                                vector with its two other components uniform in [-0.5, 0.5] — and a half width
@@ -740,6 +746,71 @@ static int shapes_main(int argc, char** argv)
     return 0;
 }
 
+// `contacts`: CapsuleContacts (count only, one 8-byte read, fill) and CapsuleDeepest on the capsules of `shapes`' generator alone.
+// The order inside a segment is the walk's, so the list is summed: word_sum = the sum over all records of sum_k (k + 1) * word k
+// of the record (64-bit, wrapping); deepest_sum weights shape i's record by i + 1 as well.
+static int contacts_main(int argc, char** argv)
+{
+    const size_t count = argc > 2 ? (size_t)strtoull(argv[2], nullptr, 10) : 65536;
+    uint64_t seed = argc > 3 ? strtoull(argv[3], nullptr, 10) : 11;
+    const std::vector<lbvh_triangle> mesh = random_mesh(4096);
+    float lo[3], hi[3];
+    mesh_box(mesh, lo, hi);
+    lbvh::Context ctx(0);
+    lbvh::RaytracingMeshDrawer drawer(ctx, mesh);
+    drawer.Awake();
+    lbvh::DataBuffer<lbvh_capsule> capsules(ctx, count);
+    for (size_t i = 0; i < count; i++) {
+        lbvh_capsule& c = capsules.LocalBuffer()[i];
+        std::memset(&c, 0, sizeof c);
+        c.radius = 3.0f;
+        for (int k = 0; k < 3; k++) {
+            c.origin[k] = uniform(seed, lo[k], hi[k]);
+            c.axis[k] = uniform(seed, -6.0f, 6.0f);
+        }
+    }
+    capsules.Sync();
+    lbvh::DataBuffer<uint64_t> offsets(ctx, count + 1);
+    drawer.CapsuleContacts(capsules, offsets, nullptr);
+    offsets.GetData();
+    const unsigned long long total = offsets.LocalBuffer()[count];
+    lbvh::DataBuffer<lbvh_contact> contacts(ctx, total ? (size_t)total : 1);
+    drawer.CapsuleContacts(capsules, offsets, &contacts);
+    lbvh::DataBuffer<lbvh_contact> deepest(ctx, count);
+    drawer.CapsuleDeepest(capsules, deepest);
+    offsets.GetData();
+    contacts.GetData();
+    deepest.GetData();
+    auto weigh = [](const lbvh_contact& c) {
+        uint32_t w[8];
+        std::memcpy(w, &c, sizeof w);
+        unsigned long long sum = 0;
+        for (int k = 0; k < 8; k++) sum += (unsigned long long)(k + 1) * w[k];
+        return sum;
+    };
+    size_t non_empty = 0, touching = 0;
+    unsigned long long word_sum = 0, deepest_sum = 0;
+    for (size_t i = 0; i < count; i++) {
+        non_empty += offsets.LocalBuffer()[i + 1] > offsets.LocalBuffer()[i];
+        touching += deepest.LocalBuffer()[i].tri != LBVH_NULL;
+        deepest_sum += (unsigned long long)(i + 1) * weigh(deepest.LocalBuffer()[i]);
+    }
+    for (size_t i = 0; i < (size_t)total; i++) word_sum += weigh(contacts.LocalBuffer()[i]);
+    std::printf("{\"triangles\": %zu, \"shapes\": %zu, \"total\": %llu, \"non_empty\": %zu, \"touching\": %zu, \"word_sum\": %llu, \"deepest_sum\": %llu, "
+                "\"deepest\": [", mesh.size(), count, total, non_empty, touching, word_sum, deepest_sum);
+    size_t shown = 0;
+    for (size_t i = 0; i < count && shown < 3; i++) {
+        if (deepest.LocalBuffer()[i].tri == LBVH_NULL) continue;
+        uint32_t w[8];
+        std::memcpy(w, &deepest.LocalBuffer()[i], sizeof w);
+        std::printf("%s[%zu", shown++ ? ", " : "", i);
+        for (int k = 0; k < 8; k++) std::printf(", %u", w[k]);
+        std::printf("]");
+    }
+    std::printf("]}\n");
+    return 0;
+}
+
 static int regions_main(int argc, char** argv)
 {
     const size_t count = argc > 2 ? (size_t)strtoull(argv[2], nullptr, 10) : 65536;
@@ -1053,7 +1124,7 @@ int main(int argc, char** argv)
 {
     static const struct { const char* name; int (*run)(int, char**); } commands[] = {
         {"crossings", crossings_main}, {"points", points_main}, {"knn", knn_main},   {"khits", khits_main}, {"gather", gather_main}, {"sortedhits", sortedhits_main},
-        {"sweep", sweep_main},         {"capsule", capsule_main}, {"boxcast", boxcast_main},         {"overlaps", overlaps_main}, {"tris", tris_main}, {"shapes", shapes_main}, {"regions", regions_main}, {"rays", rays_main}, {"sort", sort_main},   {"multi", multi_main}};
+        {"sweep", sweep_main},         {"capsule", capsule_main}, {"boxcast", boxcast_main},         {"overlaps", overlaps_main}, {"tris", tris_main}, {"shapes", shapes_main}, {"contacts", contacts_main}, {"regions", regions_main}, {"rays", rays_main}, {"sort", sort_main},   {"multi", multi_main}};
     try {
         for (const auto& c : commands)
             if (argc > 1 && std::strcmp(argv[1], c.name) == 0) return c.run(argc, argv);

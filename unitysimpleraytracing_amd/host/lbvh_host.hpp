@@ -502,6 +502,24 @@ public:
         check(ctx_.get(), lbvh_capsule_overlaps_any(ctx_.get(), (const lbvh_capsule*)shapes.DeviceBuffer(), shapes.Size(), &s,
                                                     (uint32_t*)flags.DeviceBuffer()));
     }
+    // HOW DEEP each capsule is in every triangle it touches and which way out: CapsuleOverlaps with a lbvh_contact record (depth,
+    // tri, u, v, the unit push-out normal, s) in place of an index, the same offsets; or the deepest record per capsule, tri =
+    // LBVH_NULL for one that touches nothing (lbvh_capsule_contacts / lbvh_capsule_deepest; asynchronous)
+    void CapsuleContacts(const DataBuffer<lbvh_capsule>& shapes, DataBuffer<uint64_t>& offsets, DataBuffer<lbvh_contact>* contacts = nullptr)
+    {
+        if (offsets.Size() < shapes.Size() + 1) throw Error(LBVH_ERR_INVALID_ARG, "CapsuleContacts: offsets needs one entry more than shapes");
+        const lbvh_scene s = container_->Scene();
+        check(ctx_.get(), lbvh_capsule_contacts(ctx_.get(), (const lbvh_capsule*)shapes.DeviceBuffer(), shapes.Size(), &s,
+                                                (uint64_t*)offsets.DeviceBuffer(), contacts ? (lbvh_contact*)contacts->DeviceBuffer() : nullptr,
+                                                contacts ? (uint64_t)contacts->Size() : 0));
+    }
+    void CapsuleDeepest(const DataBuffer<lbvh_capsule>& shapes, DataBuffer<lbvh_contact>& out)
+    {
+        if (out.Size() < shapes.Size()) throw Error(LBVH_ERR_INVALID_ARG, "CapsuleDeepest: fewer records than shapes");
+        const lbvh_scene s = container_->Scene();
+        check(ctx_.get(), lbvh_capsule_deepest(ctx_.get(), (const lbvh_capsule*)shapes.DeviceBuffer(), shapes.Size(), &s,
+                                               (lbvh_contact*)out.DeviceBuffer()));
+    }
     void ObbOverlaps(const DataBuffer<lbvh_obb>& shapes, DataBuffer<uint64_t>& offsets, DataBuffer<uint32_t>* tris = nullptr)
     {
         if (offsets.Size() < shapes.Size() + 1) throw Error(LBVH_ERR_INVALID_ARG, "ObbOverlaps: offsets needs one entry more than shapes");

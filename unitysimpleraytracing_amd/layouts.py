@@ -61,6 +61,11 @@ CAPSULE = np.dtype([("origin", "<f4", 3), ("radius", "<f4"), ("axis", "<f4", 3),
 OBB = np.dtype([("centre", "<f4", 3), ("_pad0", "<u4"), ("ax", "<f4", 3), ("_pad1", "<u4"), ("ay", "<f4", 3), ("_pad2", "<u4"),
                 ("az", "<f4", 3), ("_pad3", "<u4")])
 assert CAPSULE.itemsize == 32 and OBB.itemsize == 64
+# lbvh_capsule_contacts / lbvh_capsule_deepest: one contact of a capsule with a triangle — depth = radius - distance of the axis from
+# the triangle, (u, v) the contact point on the triangle, normal the unit push-out direction, s the contact point on the axis; the
+# none-record of lbvh_capsule_deepest has tri = NULL below and zeros elsewhere
+CONTACT = np.dtype([("depth", "<f4"), ("tri", "<u4"), ("u", "<f4"), ("v", "<f4"), ("normal", "<f4", 3), ("s", "<f4")])
+assert CONTACT.itemsize == 32
 # lbvh_region_overlaps / lbvh_region_overlaps_any: six planes {nx, ny, nz, d}, each keeping n . x + d >= 0; the two modes
 REGION = np.dtype([("plane", "<f4", (6, 4))])
 assert REGION.itemsize == 96
