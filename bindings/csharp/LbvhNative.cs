@@ -58,6 +58,11 @@ public static class LbvhNative
     // axis; tri = 0xFFFFFFFF in the none-record of lbvh_capsule_deepest (ShapeContacts.cs)
     [StructLayout(LayoutKind.Sequential)]
     public struct Contact { public float depth; public uint tri; public float u, v; public float normalX, normalY, normalZ; public float s; }
+    // lbvh_box_contact (include/lbvh.h): one contact of an oriented box with a triangle, 32 bytes: depth = the least push along the
+    // unit normal that separates them, axis = which of the box cast's thirteen axes gave it (13: none counted), back = the push
+    // along -normal on the same axis; tri = 0xFFFFFFFF in the none-record of lbvh_obb_deepest (ShapeContacts.cs)
+    [StructLayout(LayoutKind.Sequential)]
+    public struct BoxContact { public float depth; public uint tri; public uint axis; public float back; public float normalX, normalY, normalZ; public uint zero; }
 
     // lbvh_point_query / lbvh_closest_point (include/lbvh.h): a point with its squared search radius (active iff maxDist2 > 0) and
     // the nearest triangle's record, 16 bytes each (PointQueries.cs)
@@ -186,6 +191,9 @@ public static class LbvhNative
     [DllImport(Lib)] public static extern int lbvh_capsule_contacts(IntPtr ctx, IntPtr dShapes, UIntPtr count, ref Scene scene, IntPtr dOffsets,
         IntPtr dContacts, ulong capacity);
     [DllImport(Lib)] public static extern int lbvh_capsule_deepest(IntPtr ctx, IntPtr dShapes, UIntPtr count, ref Scene scene, IntPtr dOut);
+    [DllImport(Lib)] public static extern int lbvh_obb_contacts(IntPtr ctx, IntPtr dShapes, UIntPtr count, ref Scene scene, IntPtr dOffsets,
+        IntPtr dContacts, ulong capacity);
+    [DllImport(Lib)] public static extern int lbvh_obb_deepest(IntPtr ctx, IntPtr dShapes, UIntPtr count, ref Scene scene, IntPtr dOut);
     [DllImport(Lib)] public static extern int lbvh_obb_overlaps(IntPtr ctx, IntPtr dShapes, UIntPtr count, ref Scene scene, IntPtr dOffsets,
         IntPtr dTris, ulong capacity);
     [DllImport(Lib)] public static extern int lbvh_obb_overlaps_any(IntPtr ctx, IntPtr dShapes, UIntPtr count, ref Scene scene, IntPtr dFlags);

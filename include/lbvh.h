@@ -1218,7 +1218,9 @@ typedef struct lbvh_obb { float centre[3]; uint32_t _pad0; float ax[3]; uint32_t
  * One shape per lane; the cost is that of a box overlap walk on boxes larger by the shape, plus one 64-byte triangle line and up
  * to eight point tests and a pierce (capsule) or thirteen axes (box) per triangle that passes rule 1.  The capsule's penetration
  * depth and push-out direction per touched triangle are lbvh_capsule_contacts / lbvh_capsule_deepest below.  Out of scope: the
- * box's penetration depth or direction, a contact manifold, flat boxes, a form that spreads one huge shape over the device. */
+ * box's penetration depth or direction, a contact manifold, flat boxes, a form that spreads one huge shape over the device.
+ * (Out of scope of THESE four calls: the box's depth and push-out direction per touched triangle are lbvh_obb_contacts /
+ * lbvh_obb_deepest below.) */
 lbvh_status lbvh_capsule_overlaps(lbvh_context* ctx, const lbvh_capsule* d_shapes, size_t count, const lbvh_scene* h_scene,
                                   uint64_t* d_offsets, uint32_t* d_tris, uint64_t capacity);
 lbvh_status lbvh_capsule_overlaps_any(lbvh_context* ctx, const lbvh_capsule* d_shapes, size_t count, const lbvh_scene* h_scene,
@@ -1291,11 +1293,86 @@ typedef struct lbvh_contact {
  * pierce is evaluated for every triangle that passes rule 1, a candidate takes a ninth point test, and a record is 32 bytes.
  * Out of scope: box and sheared-box contacts (the least-overlap axis of the thirteen); a manifold of more than one point per
  * triangle; a device-side sort of contact segments (lbvh_sort_hit_segments is for 16-byte records); a form that spreads one huge
- * capsule over the device. */
+ * capsule over the device.  (The box and the sheared box have calls of their own: lbvh_obb_contacts / lbvh_obb_deepest below.) */
 lbvh_status lbvh_capsule_contacts(lbvh_context* ctx, const lbvh_capsule* d_shapes, size_t count, const lbvh_scene* h_scene,
                                   uint64_t* d_offsets, lbvh_contact* d_contacts, uint64_t capacity);
 lbvh_status lbvh_capsule_deepest(lbvh_context* ctx, const lbvh_capsule* d_shapes, size_t count, const lbvh_scene* h_scene,
                                  lbvh_contact* d_out);
+
+/* One contact of an oriented box with a triangle: 32 bytes, arrays 16-byte aligned; written as two 16-byte stores. */
+typedef struct lbvh_box_contact {
+    float    depth;                /* least push, along normal, that separates the box from the triangle; >= 0 */
+    uint32_t tri;                  /* ORIGINAL triangle index; LBVH_NULL in the none-record */
+    uint32_t axis;                 /* the j of lbvh_box_cast's thirteen axes that gave depth; LBVH_BOX_AXIS_START if none counted */
+    float    back;                 /* the push that separates along -normal on the same axis; >= depth */
+    float    normal[3];            /* unit push-out direction for the BOX, from the triangle towards the box */
+    uint32_t _zero;
+} lbvh_box_contact;
+
+/* Box contacts: HOW DEEP is an oriented box in each triangle it touches, and WHICH WAY OUT (what a crate, a hull or a placement
+ * preview asks after lbvh_obb_overlaps: Physics.ComputePenetration for a BoxCollider), as a CSR list of records
+ * (lbvh_obb_contacts) or as the deepest record per shape (lbvh_obb_deepest), over the derived traversal scene in its four-wide
+ * form by the walk of lbvh_obb_overlaps.  The active rule, rule 1, rule 2 and therefore the candidate set are lbvh_obb_overlaps'
+ * exactly, from the same operations on the same values: "touches" there and a record here never disagree.
+ *   The contact of a candidate (c = centre, b_0, b_1, b_2 = ax, ay, az; the triangle line a, e1, e2), in strict fp32, every
+ *   operation rounded on its own, dot, cross, min, max and / as at lbvh_box_cast, sqrt correctly rounded: the least-overlap axis
+ *   of the thirteen.  For every axis j = 0 .. 12 of lbvh_box_cast, in its order, with L = L_j, m = a - c, lo, hi and rb exactly
+ *   as there (the values rule 2 compares):
+ *       len2 = dot(L, L)      pos = hi + rb      neg = rb - lo
+ *   From the box's centre the triangle covers [lo, hi] on L and the box [-rb, rb]: moved by pos along +L the box's interval
+ *   begins where the triangle's ends, moved by neg along -L it ends where the triangle's begins.  Both are >= 0 for a candidate
+ *   (rule 2: -rb <= hi and lo <= rb, and a sum of two fp32 values whose exact sum is >= 0 rounds to a value >= 0).
+ *   Axis j COUNTS only if len2 is a normal finite number, 2^-126 <= len2 < +inf.  A zero axis (parallel edges, a degenerate
+ *   triangle) has no direction, and a denormal len2 no longer carries L's precision: both are skipped, and so is an overflow.
+ *   A near-zero but normal axis is taken as the direction it is, as lbvh_box_cast takes it: the projections are accurate
+ *   relative to the computed L, the push along ANY direction separates, and the least push over all directions is attained on
+ *   one of the thirteen exact axes; a noisy extra direction therefore cannot undercut the answer beyond ordinary roundoff.
+ *   For an axis that counts:
+ *       len = sqrt(len2)      pen = fminf(pos, neg)      far = fmaxf(pos, neg)      d_j = pen / len
+ *       sign = +1 if pos <= neg, else -1
+ *   Start with least = +inf and axis = LBVH_BOX_AXIS_START.  In the order of j, d_j replaces least, and j replaces axis, only
+ *   when d_j < least (strictly; false for a NaN).  For the winner j:
+ *       depth = d_j      back = far / len      normal = (sign * L) / len per component
+ *   depth and back come from the same axis: the box is free after depth along normal or after back along -normal, and
+ *   back >= depth.  depth >= 0, and it is NOT the distance to travel along any other direction.  If no axis counts (every L_j
+ *   zero, denormal or overflowing): the record {0, tri, LBVH_BOX_AXIS_START, 0, {0, 0, 0}, 0}.  The record is a function of
+ *   (shape, triangle) only.
+ *   For axis = 0 normal is the triangle's face normal, for 1 .. 3 a face normal of the box, for 4 + 3*i + k the common
+ *   perpendicular of the box's edge b_i and the triangle's edge E_k.  This is the direction lbvh_box_cast reports for a box that
+ *   arrives along -normal, with the sign chosen by the shorter way out instead of by a motion.
+ * Output of lbvh_obb_contacts — lbvh_obb_overlaps' CSR contract with a record in place of an index:
+ *   d_offsets: count + 1 words of 64 bits, the SAME words lbvh_obb_overlaps writes for these shapes.  Always written in full.
+ *   d_contacts, `capacity` records of 32 bytes: segment k = d_contacts[d_offsets[k] .. d_offsets[k+1]) = one record per candidate
+ *   of shape k, each triangle exactly once.  THE ORDER INSIDE A SEGMENT IS THE WALK'S AND IS NOT PART OF THE CONTRACT.
+ *   Overflow: no record at index >= capacity is ever written; every segment with d_offsets[k+1] <= capacity is complete; records
+ *   below `capacity` that belong to a segment which does not fit are unspecified.  The call never waits on the host and returns
+ *   LBVH_OK in both cases: the caller reads d_offsets[count] to learn what was needed.
+ *   Count-only form: capacity == 0 writes the offsets and walks once (d_contacts may be NULL) — it IS lbvh_obb_overlaps'
+ *   count-only form; otherwise the scene is walked twice (that count walk, the device-side scan, a fill walk that makes the
+ *   same decisions from the same values and forms the records).  d_contacts == NULL with capacity > 0 is LBVH_ERR_INVALID_ARG.
+ * Output of lbvh_obb_deepest: d_out[k] = the contact of shape k with the greatest depth (compared as fp32 values); on equal
+ *   depth the lower original triangle index, whatever order the walk meets them in.  A shape with no candidate, or an inactive
+ *   shape: the none-record {0, LBVH_NULL, 0, 0, {0, 0, 0}, 0}.  Every one of the `count` records is written.  One walk, no scan.
+ *   Nothing can be pruned beyond rule 1: the depth of a contact grows with how far the box reaches THROUGH the triangle, which a
+ *   box around the triangle says nothing about, and a shallow contact found first excludes no subtree, so the walk is
+ *   lbvh_obb_overlaps' and visits every candidate.
+ * Both need the derived traversal scene (lbvh_build_fast_scene; a stale one is LBVH_ERR_INVALID_ARG), are asynchronous on the
+ * context's stream with no host wait, and use the context's ray scratch: they drop the path tracer's live-path list (see
+ * lbvh_path_bounce).  count == 0 is a no-op: nothing is enqueued and no buffer is touched, d_offsets[0] included.  Rejected: NULL
+ * ctx / d_shapes / h_scene / d_offsets / d_out, d_shapes, d_contacts or d_out not 16-byte aligned, d_offsets not 8-byte aligned,
+ * count > 2^32 - 1.  Four-wide walk only; lbvh_debug_ray_waves, lbvh_debug_ray_stack_split, lbvh_debug_ray_stack_limit and
+ * lbvh_ray_stats_target apply as to lbvh_obb_overlaps (the full form reports the count walk's plus the fill walk's triangle
+ * lines: twice the count-only form's).
+ * Cost: a walk of these two visits what lbvh_obb_overlaps' visits; a triangle that passes rule 1 takes, per axis that counts
+ * and until the first separating axis, one square root and one division more, a candidate four divisions more, and a record is
+ * 32 bytes.
+ * Out of scope: a contact point or a manifold for the box (a box touches a triangle in a point, a segment or a polygon); flat
+ * boxes (det == 0 is inactive, as everywhere); a device-side sort of 32-byte segments (lbvh_sort_hit_segments is for 16-byte
+ * records); a form that spreads one huge box over the device. */
+lbvh_status lbvh_obb_contacts(lbvh_context* ctx, const lbvh_obb* d_shapes, size_t count, const lbvh_scene* h_scene,
+                              uint64_t* d_offsets, lbvh_box_contact* d_contacts, uint64_t capacity);
+lbvh_status lbvh_obb_deepest(lbvh_context* ctx, const lbvh_obb* d_shapes, size_t count, const lbvh_scene* h_scene,
+                             lbvh_box_contact* d_out);
 
 /* A convex region bounded by six planes: 96 bytes; arrays of them 16-byte aligned.  A plane {nx, ny, nz, d} keeps the half space
  * n . x + d >= 0; the region is the intersection of its six half spaces.  Normals need not be unit length.  A region with fewer
@@ -1421,7 +1498,7 @@ lbvh_status lbvh_path_scatter(lbvh_context* ctx, const lbvh_scene* h_scene, cons
  * lbvh_path_bounce on the same d_states / d_hits listed as live (a list kept by the context).  Every library call that writes
  * into those buffers drops the list (lbvh_path_begin, lbvh_trace_rays, a primary trace into any part of d_hits,
  * lbvh_buffer_upload / _fill_u32 / _free), and so does lbvh_trace_forget — and so do lbvh_trace_closest,
- * lbvh_trace_occluded, lbvh_closest_point_query, lbvh_within_distance, lbvh_count_hits, lbvh_point_crossings, lbvh_box_overlaps, lbvh_gather_within_distance, lbvh_k_closest_points, lbvh_trace_k_closest, lbvh_gather_hits, lbvh_sphere_cast, lbvh_sphere_cast_any, lbvh_capsule_cast, lbvh_capsule_cast_any, lbvh_box_cast, lbvh_box_cast_any, lbvh_triangle_intersections, lbvh_triangle_intersects_any, lbvh_capsule_overlaps, lbvh_capsule_overlaps_any, lbvh_obb_overlaps, lbvh_obb_overlaps_any, lbvh_capsule_contacts, lbvh_capsule_deepest, lbvh_region_overlaps, lbvh_region_overlaps_any and lbvh_region_overlaps_large, whatever buffers they are given, since they use the same ray scratch; then every state is scanned again.  The one exception among the query calls:
+ * lbvh_trace_occluded, lbvh_closest_point_query, lbvh_within_distance, lbvh_count_hits, lbvh_point_crossings, lbvh_box_overlaps, lbvh_gather_within_distance, lbvh_k_closest_points, lbvh_trace_k_closest, lbvh_gather_hits, lbvh_sphere_cast, lbvh_sphere_cast_any, lbvh_capsule_cast, lbvh_capsule_cast_any, lbvh_box_cast, lbvh_box_cast_any, lbvh_triangle_intersections, lbvh_triangle_intersects_any, lbvh_capsule_overlaps, lbvh_capsule_overlaps_any, lbvh_obb_overlaps, lbvh_obb_overlaps_any, lbvh_capsule_contacts, lbvh_capsule_deepest, lbvh_obb_contacts, lbvh_obb_deepest, lbvh_region_overlaps, lbvh_region_overlaps_any and lbvh_region_overlaps_large, whatever buffers they are given, since they use the same ray scratch; then every state is scanned again.  The one exception among the query calls:
  * lbvh_sort_hit_segments and lbvh_sort_index_segments take no context scratch and keep the live-path list (they drop it only when the
  * buffer they sort is d_hits itself).  What the library
  * cannot see is a write of the CALLER's own (a kernel or hipMemcpy that revives or ends paths, Russian roulette): between two

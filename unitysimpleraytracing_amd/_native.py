@@ -116,6 +116,8 @@ SIGNATURES = {
     "lbvh_capsule_deepest": (_I32, [_P, _P, _SZ, C.POINTER(Scene), _P]),
     "lbvh_obb_overlaps": (_I32, [_P, _P, _SZ, C.POINTER(Scene), _P, _P, C.c_uint64]),
     "lbvh_obb_overlaps_any": (_I32, [_P, _P, _SZ, C.POINTER(Scene), _P]),
+    "lbvh_obb_contacts": (_I32, [_P, _P, _SZ, C.POINTER(Scene), _P, _P, C.c_uint64]),
+    "lbvh_obb_deepest": (_I32, [_P, _P, _SZ, C.POINTER(Scene), _P]),
     "lbvh_region_overlaps": (_I32, [_P, _P, _SZ, _U32, C.POINTER(Scene), _P, _P, C.c_uint64]),
     "lbvh_region_overlaps_any": (_I32, [_P, _P, _SZ, _U32, C.POINTER(Scene), _P]),
     "lbvh_region_overlaps_large": (_I32, [_P, _P, _SZ, _U32, C.POINTER(Scene), _P, _P, C.c_uint64]),

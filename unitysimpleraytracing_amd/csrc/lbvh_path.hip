@@ -2714,6 +2714,172 @@ __global__ __launch_bounds__(64) void capsule_contact_wide_kernel(const lbvh_cap
     if (STATS) add_ray_stats(stats, n_shapes, n_steps, n_tris);
 }
 
+// ---- box contacts: how deep an oriented box is in each triangle it touches, and which way out (lbvh_obb_contacts, ------------
+// lbvh_obb_deepest, include/lbvh.h).  The frame and the slot test of shape_overlap_wide_kernel<kShapeObb>; the count walk of
+// lbvh_obb_contacts IS that kernel's kTriCount form.  The two forms are capsule_contact_wide_kernel's.
+
+// The header's contact of a box (centre c, half-axis vectors b) with the triangle line (a, e1, e2); false: not a candidate.  The
+// decision is box_touches' on the same values — lo <= rb && -rb <= hi on every axis from the same box_axis_spans, the first
+// separating axis ends the loop (through its condition, as capsule_contact_of) —, and the same pass keeps the least d_j = pen / len
+// over the axes that count.  Per counting axis one square root and one division; the winner's sign * L, len and far are kept
+// and its four other quotients are formed once, after the loop.  rec0 = {depth, tri (set by the caller), axis, back},
+// rec1 = {normal, 0}.
+__device__ __forceinline__ bool box_contact_of(const ray_t& c, const box_axes& b, const float4 a, const float4 e1, const float4 e2,
+                                               float4& rec0, float4& rec1)
+{
+    const float inf = __builtin_inff();
+    const float mx = a.x - c.ox, my = a.y - c.oy, mz = a.z - c.oz;
+    const float e3x = e2.x - e1.x, e3y = e2.y - e1.y, e3z = e2.z - e1.z;
+    float least = inf, win_len = 1.0f, win_far = 0.0f, wx = 0.0f, wy = 0.0f, wz = 0.0f;
+    uint32_t axis = LBVH_BOX_AXIS_START;
+    bool apart = false;
+#pragma nounroll
+    for (uint32_t j = 0; j < 13u && !apart; j++) {
+        float lx, ly, lz, lo, hi, rb;
+        box_axis_spans(j, mx, my, mz, b, e1, e2, e3x, e3y, e3z, lx, ly, lz, lo, hi, rb);
+        apart = !(lo <= rb && -rb <= hi);
+        const float len2 = dot3(lx, ly, lz, lx, ly, lz);
+        if (len2 >= 1.17549435e-38f && len2 < inf) {         // a normal finite number: a zero or denormal axis does not count
+            const float pos = hi + rb, neg = rb - lo;        // the push along +L and along -L
+            const float len = sqrtf(len2);
+            const float d = fminf(pos, neg) / len;
+            if (d < least) {                                 // strictly less; false for a NaN
+                least = d; axis = j; win_len = len; win_far = fmaxf(pos, neg);
+                const bool up = pos <= neg;
+                wx = up ? lx : -lx; wy = up ? ly : -ly; wz = up ? lz : -lz;
+            }
+        }
+    }
+    if (apart) return false;
+    const bool none = axis == LBVH_BOX_AXIS_START;
+    rec0.x = none ? 0.0f : least;
+    rec0.z = __uint_as_float(axis);
+    rec0.w = none ? 0.0f : win_far / win_len;
+    rec1 = make_float4(wx / win_len, wy / win_len, wz / win_len, 0.0f);     // (none: 0 / 1)
+    return true;
+}
+
+template <int MODE, bool STATS>
+__global__ __launch_bounds__(64) void box_contact_wide_kernel(const lbvh_obb* __restrict__ boxes, uint32_t total,
+                                                              const lbvh_wide_node* __restrict__ wide,
+                                                              const lbvh_fast_node* __restrict__ lines,
+                                                              const uint64_t* __restrict__ offsets,     // kContactFill: where segment k starts
+                                                              lbvh_box_contact* __restrict__ out,       // kContactFill: the records; kContactDeepest: one per shape
+                                                              uint64_t capacity,                        // kContactFill: records in `out`
+                                                              uint32_t* __restrict__ deep,     // [gridDim.x][kWideStackDeep][64]
+                                                              uint32_t lds_depth,              // <= kWideStackLds
+                                                              uint32_t deep_cap,               // <= kWideStackDeep
+                                                              uint32_t* __restrict__ fault, lbvh_ray_stats* stats)
+{
+    __shared__ uint32_t s_stack[kWideStackLds][LBVH_WAVE];
+    uint32_t* my_deep = deep + (size_t)blockIdx.x * (kWideStackDeep * LBVH_WAVE) + threadIdx.x;
+    const float4* shapes = reinterpret_cast<const float4*>(boxes);
+    float4* records = reinterpret_cast<float4*>(out);
+    const uint32_t lane = threadIdx.x;
+    const uint32_t run = max((total + gridDim.x - 1) / gridDim.x, 32u);
+    uint32_t next = blockIdx.x * run;
+    if (next >= total) return;
+    const uint32_t end = min(next + run, total);
+    uint32_t n_shapes = 0, n_steps = 0, n_tris = 0;
+
+    bool active = false;
+    uint32_t i = 0;
+    ray_t o = {};                                        // the centre (the direction is not read)
+    box_axes b = {};                                     // the half-axis vectors
+    float hx = 0.0f, hy = 0.0f, hz = 0.0f;               // g, the half extent per world axis
+    uint32_t sp = 0, node = 0;
+    uint64_t pos = 0;                                    // kContactFill: where this lane's next record goes
+    float4 best0 = {}, best1 = {};                       // kContactDeepest: the deepest record so far
+    const float4 none0 = make_float4(0.0f, __uint_as_float(LBVH_NULL), 0.0f, 0.0f), none1 = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    auto push = [&](uint32_t ref) {
+        if (sp < lds_depth) { s_stack[sp][lane] = ref; sp++; }
+        else if (sp < lds_depth + deep_cap) { my_deep[(sp - lds_depth) * LBVH_WAVE] = ref; sp++; }
+        // a dropped entry would be a silently short list: report it, as the other walkers do (lbvh_debug_ray_stack_limit provokes it)
+        else __hip_atomic_store(fault, LBVH_FAULT_RAY_STACK, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    };
+    for (;;) {
+        const uint64_t idle = __ballot(!active);
+        if (idle != 0 && next < end) {
+            if (!active) {
+                const uint32_t k = next + mbcnt64(idle);
+                if (k < end) {
+                    i = k;
+                    const float inf = __builtin_inff();
+                    const float4 q0 = shapes[4 * (size_t)k], x = shapes[4 * (size_t)k + 1], y = shapes[4 * (size_t)k + 2], z = shapes[4 * (size_t)k + 3];
+                    o.ox = q0.x; o.oy = q0.y; o.oz = q0.z;
+                    b.xx = x.x; b.xy = x.y; b.xz = x.z;
+                    b.yx = y.x; b.yy = y.y; b.yz = y.z;
+                    b.zx = z.x; b.zy = z.y; b.zz = z.z;
+                    hx = (fabsf(b.xx) + fabsf(b.yx)) + fabsf(b.zx);
+                    hy = (fabsf(b.xy) + fabsf(b.yy)) + fabsf(b.zy);
+                    hz = (fabsf(b.xz) + fabsf(b.yz)) + fabsf(b.zz);
+                    const float det = dot3(x.x, x.y, x.z, y.y * z.z - y.z * z.y, y.z * z.x - y.x * z.z, y.x * z.y - y.y * z.x);
+                    active = (q0.x == q0.x && q0.y == q0.y && q0.z == q0.z) &&
+                             fabsf(x.x) < inf && fabsf(x.y) < inf && fabsf(x.z) < inf && fabsf(y.x) < inf && fabsf(y.y) < inf && fabsf(y.z) < inf &&
+                             fabsf(z.x) < inf && fabsf(z.y) < inf && fabsf(z.z) < inf && fabsf(det) < inf && det != 0.0f;
+                    sp = 0; node = 0;
+                    if constexpr (MODE == kContactFill) { if (active) pos = offsets[k]; }
+                    else {
+                        best0 = none0; best1 = none1;
+                        if (!active) { records[2 * (size_t)k] = none0; records[2 * (size_t)k + 1] = none1; }
+                    }
+                    if (STATS && active) n_shapes++;
+                }
+            }
+            next += (uint32_t)__popcll(idle);
+        }
+        if (!__any(active) && next >= end) break;
+        if (active) {
+            if (STATS) n_steps++;
+            const float4* w = reinterpret_cast<const float4*>(&wide[node]);
+            const float4 lox = w[0], loy = w[1], loz = w[2], hix = w[3], hiy = w[4], hiz = w[5];
+            const uint4 ref = reinterpret_cast<const uint4*>(w)[6];
+#define SHAPE_SLOT(c)                                                                                                                  \
+    (shape_in_grown<kShapeObb>(lox.c, hix.c, o.ox, hx, hx, 0.0f) && shape_in_grown<kShapeObb>(loy.c, hiy.c, o.oy, hy, hy, 0.0f) &&    \
+     shape_in_grown<kShapeObb>(loz.c, hiz.c, o.oz, hz, hz, 0.0f) && ref.c != kWideEmpty)
+            const bool h0 = SHAPE_SLOT(x), h1 = SHAPE_SLOT(y), h2 = SHAPE_SLOT(z), h3 = SHAPE_SLOT(w);
+#undef SHAPE_SLOT
+            const uint32_t hit = (h0 ? 1u : 0u) | (h1 ? 2u : 0u) | (h2 ? 4u : 0u) | (h3 ? 8u : 0u);
+            const uint32_t leaf = (ref.x >> 31) | ((ref.y >> 31) << 1) | ((ref.z >> 31) << 2) | ((ref.w >> 31) << 3);
+            uint32_t leaves = hit & leaf, inner = hit & ~leaf;
+            while (leaves != 0u) {
+                const uint32_t k = (uint32_t)__builtin_ctz(leaves);
+                leaves &= leaves - 1u;
+                const uint32_t line = pick4(ref, k) & 0x7FFFFFFFu;
+                float4 t0, t1, t2;
+                unpack_fast_triangle(reinterpret_cast<const float4*>(&lines[line]), t0, t1, t2);
+                if (STATS) n_tris++;
+                float4 rec0, rec1;
+                rec0.y = t0.w;                                   // the ORIGINAL triangle index
+                if (!box_contact_of(o, b, t0, t1, t2, rec0, rec1)) continue;
+                if constexpr (MODE == kContactFill) {
+                    if (pos < capacity) { records[2 * pos] = rec0; records[2 * pos + 1] = rec1; }     // never a record at or beyond the capacity
+                    pos++;
+                } else {
+                    // the greatest depth; on equal depth the lower original index (the none-record's index is above every one)
+                    const uint32_t tri = __float_as_uint(rec0.y), best_tri = __float_as_uint(best0.y);
+                    if (best_tri == LBVH_NULL || rec0.x > best0.x || (!(rec0.x < best0.x) && tri < best_tri)) { best0 = rec0; best1 = rec1; }
+                }
+            }
+            if (inner != 0u) {
+                node = pick4(ref, (uint32_t)__builtin_ctz(inner));
+                inner &= inner - 1u;
+                while (inner != 0u) {
+                    push(pick4(ref, (uint32_t)__builtin_ctz(inner)));
+                    inner &= inner - 1u;
+                }
+            } else if (sp != 0) {
+                sp--;
+                node = sp < lds_depth ? s_stack[sp][lane] : my_deep[(sp - lds_depth) * LBVH_WAVE];
+            } else {
+                if constexpr (MODE == kContactDeepest) { records[2 * (size_t)i] = best0; records[2 * (size_t)i + 1] = best1; }
+                active = false;
+            }
+        }
+    }
+    if (STATS) add_ray_stats(stats, n_shapes, n_steps, n_tris);
+}
+
 // ---- region queries: which triangles lie in a convex region of six planes (lbvh_region_overlaps, include/lbvh.h) ---------
 // The frame of overlap_wide_kernel<BOX = true> with another slot test: a slot is entered iff for each of the six planes
 // {nx, ny, nz, d} the box corner farthest along the normal is on the kept side, P = ((nx * X + ny * Y) + nz * Z) + d >= 0 with
@@ -3507,6 +3673,10 @@ static lbvh_status launch_per_query(lbvh_context* ctx, const QUERY* d_queries, s
         LBVH_LAUNCH_STATS(ctx, ctx->ray_stats, (capsule_contact_wide_kernel<kContactDeepest, STATS>), dim3(w.waves), dim3(LBVH_WAVE), d_queries,
                           (uint32_t)count, w.wn, ctx->fast_nodes, (const uint64_t*)nullptr, d_out, (uint64_t)0, w.deep, w.lds, w.deep_cap,
                           ctx->fault_dev, ctx->ray_stats);
+    else if constexpr (std::is_same_v<QUERY, lbvh_obb>)              // lbvh_obb_deepest: the same of the box contact walk
+        LBVH_LAUNCH_STATS(ctx, ctx->ray_stats, (box_contact_wide_kernel<kContactDeepest, STATS>), dim3(w.waves), dim3(LBVH_WAVE), d_queries,
+                          (uint32_t)count, w.wn, ctx->fast_nodes, (const uint64_t*)nullptr, d_out, (uint64_t)0, w.deep, w.lds, w.deep_cap,
+                          ctx->fault_dev, ctx->ray_stats);
     else PER_QUERY_WALK(box_cast_wide_kernel);
 #undef PER_QUERY_WALK
     LBVH_HIP_TRY(ctx, hipGetLastError());
@@ -3727,6 +3897,46 @@ static lbvh_status capsule_deepest(lbvh_context* ctx, const lbvh_capsule* d_shap
     return launch_per_query<false>(ctx, d_shapes, count, h_scene, d_out, who);
 }
 
+// lbvh_obb_contacts / lbvh_obb_deepest: capsule_contacts / capsule_deepest for the box — the count walk is
+// shape_overlaps<kShapeObb, false>'s, the fill walk forms the contacts; one record per shape through launch_per_query.
+static lbvh_status obb_contacts(lbvh_context* ctx, const lbvh_obb* d_shapes, size_t count, const lbvh_scene* h_scene, uint64_t* d_offsets,
+                                lbvh_box_contact* d_contacts, uint64_t capacity, const char* who)
+{
+    if (!ctx) return LBVH_ERR_INVALID_ARG;
+    if (count == 0) return LBVH_OK;
+    NAMED_REQUIRE(d_shapes != nullptr && h_scene != nullptr && d_offsets != nullptr);
+    NAMED_REQUIRE(d_contacts != nullptr || capacity == 0);
+    NAMED_REQUIRE(((uintptr_t)d_shapes & 15) == 0 && ((uintptr_t)d_offsets & 7) == 0 && ((uintptr_t)d_contacts & 15) == 0);
+    NAMED_REQUIRE(count <= 0xFFFFFFFFull);
+    walk_launch w;
+    const lbvh_status rc = begin_walk(ctx, h_scene, count, who, true, &w);
+    if (rc != LBVH_OK) return rc;
+    const uint32_t total = (uint32_t)count;
+    return csr_query(
+        ctx, count, d_offsets, capacity,
+        [&](uint32_t* counts) {
+            LBVH_LAUNCH_STATS(ctx, ctx->ray_stats, (shape_overlap_wide_kernel<kShapeObb, kTriCount, STATS>), dim3(w.waves), dim3(LBVH_WAVE),
+                              (const float4*)d_shapes, total, w.wn, ctx->fast_nodes, counts, (const uint64_t*)nullptr, (uint32_t*)nullptr, (uint64_t)0,
+                              w.deep, w.lds, w.deep_cap, ctx->fault_dev, ctx->ray_stats);
+        },
+        [&] {
+            LBVH_LAUNCH_STATS(ctx, ctx->ray_stats, (box_contact_wide_kernel<kContactFill, STATS>), dim3(w.waves), dim3(LBVH_WAVE), d_shapes, total,
+                              w.wn, ctx->fast_nodes, (const uint64_t*)d_offsets, d_contacts, capacity, w.deep, w.lds, w.deep_cap, ctx->fault_dev,
+                              ctx->ray_stats);
+        });
+}
+
+static lbvh_status obb_deepest(lbvh_context* ctx, const lbvh_obb* d_shapes, size_t count, const lbvh_scene* h_scene, lbvh_box_contact* d_out,
+                               const char* who)
+{
+    if (!ctx) return LBVH_ERR_INVALID_ARG;
+    if (count == 0) return LBVH_OK;
+    NAMED_REQUIRE(d_shapes != nullptr && h_scene != nullptr && d_out != nullptr);
+    NAMED_REQUIRE(((uintptr_t)d_shapes & 15) == 0 && ((uintptr_t)d_out & 15) == 0);
+    NAMED_REQUIRE(count <= 0xFFFFFFFFull);
+    return launch_per_query<false>(ctx, d_shapes, count, h_scene, d_out, who);
+}
+
 // lbvh_region_overlaps: a CSR answer; lbvh_region_overlaps_any: one launch, the flags are the walk's own output.  Four-wide walk only.
 // (a rejection names the entry point, as the stale-scene message of begin_walk does)
 template <bool ANY>
@@ -3883,6 +4093,18 @@ lbvh_status lbvh_capsule_deepest(lbvh_context* ctx, const lbvh_capsule* d_shapes
                                  lbvh_contact* d_out)
 {
     return capsule_deepest(ctx, d_shapes, count, h_scene, d_out, "lbvh_capsule_deepest");
+}
+
+lbvh_status lbvh_obb_contacts(lbvh_context* ctx, const lbvh_obb* d_shapes, size_t count, const lbvh_scene* h_scene,
+                              uint64_t* d_offsets, lbvh_box_contact* d_contacts, uint64_t capacity)
+{
+    return obb_contacts(ctx, d_shapes, count, h_scene, d_offsets, d_contacts, capacity, "lbvh_obb_contacts");
+}
+
+lbvh_status lbvh_obb_deepest(lbvh_context* ctx, const lbvh_obb* d_shapes, size_t count, const lbvh_scene* h_scene,
+                             lbvh_box_contact* d_out)
+{
+    return obb_deepest(ctx, d_shapes, count, h_scene, d_out, "lbvh_obb_deepest");
 }
 
 lbvh_status lbvh_obb_overlaps(lbvh_context* ctx, const lbvh_obb* d_shapes, size_t count, const lbvh_scene* h_scene,

@@ -106,21 +106,25 @@ def push_out(drawer, shapes, skin, iterations=4):
     (torch); stop when no depth is > 0.  Returns (shapes, depths): the same DataBuffer and the float32 host array of the depths
     that capsule_deepest reports for the final positions (0 for a capsule that touches nothing).  One contact is resolved per
     iteration and capsule: a corner of k planes needs about k iterations.  Waits on the host in every iteration; not part of
-    the word-for-word contract of include/lbvh.h."""
+    the word-for-word contract of include/lbvh.h.
+    A DataBuffer of layouts.OBB is taken the same way through obb_deepest: the centre (words 0 .. 2 of each 16-word record) moves,
+    the half-axis vectors stay.  A box that merely touches has depth 0 and is left where it is."""
     import torch
-    if shapes.dtype != L.CAPSULE:
-        raise ValueError("shapes must be a DataBuffer of layouts.CAPSULE")
+    if shapes.dtype not in (L.CAPSULE, L.OBB):
+        raise ValueError("shapes must be a DataBuffer of layouts.CAPSULE or layouts.OBB")
+    box = shapes.dtype == L.OBB
+    stride = 16 if box else 8
     if not torch.cuda.is_available():
         # (a torch that brings a HIP runtime of its own sees the GPU only if it was imported before this package loaded the library)
         raise RuntimeError("push_out needs torch on the GPU: import torch before unitysimpleraytracing_amd")
     ctx, n = drawer.ctx, shapes.size
     dev = torch.device("cuda", ctx.device_id)
-    out = DataBuffer(ctx, n, L.CONTACT)
+    out = DataBuffer(ctx, n, L.BOX_CONTACT if box else L.CONTACT)
     try:
-        caps = torch.as_tensor(_DeviceWords(shapes.device.value, n * 8), device=dev).view(n, 8)
+        caps = torch.as_tensor(_DeviceWords(shapes.device.value, n * stride), device=dev).view(n, stride)
         recs = torch.as_tensor(_DeviceWords(out.device.value, n * 8), device=dev).view(n, 8)
         for it in range(int(iterations) + 1):
-            drawer.capsule_deepest(shapes, out)
+            (drawer.obb_deepest if box else drawer.capsule_deepest)(shapes, out)
             ctx.sync()                                              # the library's stream is not torch's
             deep = recs[:, 0] > 0
             if it == int(iterations) or not bool(deep.any()):
@@ -732,12 +736,35 @@ class RaytracingMeshDrawer:
         Asynchronous; read with out.get_data()."""
         self._per_query(N.lib.lbvh_capsule_deepest, shapes, "CAPSULE", out, L.CONTACT, "shapes")
 
+    def obb_contacts(self, shapes, offsets, contacts=None):
+        """The same for the oriented boxes of the DataBuffer `shapes` (layouts.OBB): obb_overlaps with a layouts.BOX_CONTACT record
+        (depth = the least push along normal that frees the box from the triangle, tri, axis = which of box_cast's thirteen axes
+        gave it, back = the push along -normal, the unit push-out normal) in place of an index.  `offsets` receives the words
+        obb_overlaps writes; `contacts` (layouts.BOX_CONTACT DataBuffer, its size is the capacity) the records, in no particular
+        order inside a segment; contacts=None counts only.  Asynchronous."""
+        if shapes.dtype != L.OBB or offsets.dtype != np.uint64 or offsets.size < shapes.size + 1 or \
+                (contacts is not None and contacts.dtype != L.BOX_CONTACT):
+            raise ValueError("shapes must be a DataBuffer of layouts.OBB, offsets one of uint64 with one entry more, contacts one of "
+                             "layouts.BOX_CONTACT or None")
+        s = self.container.scene()
+        N.check(self.ctx.handle, N.lib.lbvh_obb_contacts(self.ctx.handle, shapes.device, shapes.size, C.byref(s), offsets.device,
+                                                         contacts.device if contacts is not None else None,
+                                                         contacts.size if contacts is not None else 0))
+
+    def obb_deepest(self, shapes, out):
+        """The deepest contact of each box of `shapes` (layouts.OBB) into the DataBuffer `out` (layouts.BOX_CONTACT): the record with
+        the greatest depth, ties to the lower triangle index; tri = layouts.NULL and zeros for a box that touches nothing.
+        Asynchronous; read with out.get_data()."""
+        self._per_query(N.lib.lbvh_obb_deepest, shapes, "OBB", out, L.BOX_CONTACT, "shapes")
+
     def contacts(self, shapes, min_capacity=1):
-        """Convenience, as touching(): count -> one 8-byte download -> allocate -> fill, for a DataBuffer of layouts.CAPSULE.
-        Returns (offsets, contacts): host arrays, uint64[shapes.size + 1] and layouts.CONTACT[total], every segment in the walk's
-        order."""
-        if shapes.dtype != L.CAPSULE:
-            raise ValueError("shapes must be a DataBuffer of layouts.CAPSULE")
+        """Convenience, as touching(): count -> one 8-byte download -> allocate -> fill, for a DataBuffer of layouts.CAPSULE or of
+        layouts.OBB.  Returns (offsets, contacts): host arrays, uint64[shapes.size + 1] and layouts.CONTACT[total] (capsules) or
+        layouts.BOX_CONTACT[total] (boxes), every segment in the walk's order."""
+        if shapes.dtype not in (L.CAPSULE, L.OBB):
+            raise ValueError("shapes must be a DataBuffer of layouts.CAPSULE or layouts.OBB")
+        if shapes.dtype == L.OBB:
+            return self._csr_lists(self.obb_contacts, shapes, min_capacity, False, dtype=L.BOX_CONTACT)
         return self._csr_lists(self.capsule_contacts, shapes, min_capacity, False, dtype=L.CONTACT)
 
     def region_overlaps(self, regions, mode, offsets, tris=None):

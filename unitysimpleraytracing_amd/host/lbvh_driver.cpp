@@ -75,6 +75,10 @@
 //                                                prints the total, how many segments are non-empty, how many capsules touch, the
 //                                                order-free sum of the records' words, the same of the deepest records weighted by
 //                                                shape, and the first deepest records as words
+//     lbvh_driver boxcontacts <n_shapes> [seed]  the same mesh and n_shapes sheared boxes (SplitMix64, seed default 13): per box and axis
+//                                                k the centre uniform in the mesh's box, then component k of ax, ay, az as `shapes`
+//                                                draws them.  ObbContacts (count only, one 8-byte read, fill) and ObbDeepest; prints
+//                                                what `contacts` prints
 //     lbvh_driver regions <n_regions> [seed] [large]  the 4 096 triangles of cfg1 and n_regions sheared boxes (SplitMix64, seed default 6):
 //                                                the centre uniform in the mesh's box, then per axis k a normal — the axis' unit
 //                                                vector with its two other components uniform in [-0.5, 0.5] — and a half width
@@ -746,9 +750,54 @@ static int shapes_main(int argc, char** argv)
     return 0;
 }
 
-// `contacts`: CapsuleContacts (count only, one 8-byte read, fill) and CapsuleDeepest on the capsules of `shapes`' generator alone.
-// The order inside a segment is the walk's, so the list is summed: word_sum = the sum over all records of sum_k (k + 1) * word k
-// of the record (64-bit, wrapping); deepest_sum weights shape i's record by i + 1 as well.
+// `contacts` / `boxcontacts`: the list form (count only, one 8-byte read, fill) and the deepest form on one set of shapes; REC is the
+// 32-byte record.  The order inside a segment is the walk's, so the list is summed: word_sum = the sum over all records of
+// sum_k (k + 1) * word k of the record (64-bit, wrapping); deepest_sum weights shape i's record by i + 1 as well.
+template <class REC, class SHAPE, class LIST, class DEEPEST>
+static void contact_report(lbvh::Context& ctx, const lbvh::DataBuffer<SHAPE>& shapes, size_t triangles, LIST list, DEEPEST deepest_of)
+{
+    static_assert(sizeof(REC) == 32, "a contact record is eight words");
+    const size_t count = shapes.Size();
+    lbvh::DataBuffer<uint64_t> offsets(ctx, count + 1);
+    list(shapes, offsets, nullptr);
+    offsets.GetData();
+    const unsigned long long total = offsets.LocalBuffer()[count];
+    lbvh::DataBuffer<REC> contacts(ctx, total ? (size_t)total : 1);
+    list(shapes, offsets, &contacts);
+    lbvh::DataBuffer<REC> deepest(ctx, count);
+    deepest_of(shapes, deepest);
+    offsets.GetData();
+    contacts.GetData();
+    deepest.GetData();
+    auto weigh = [](const REC& c) {
+        uint32_t w[8];
+        std::memcpy(w, &c, sizeof w);
+        unsigned long long sum = 0;
+        for (int k = 0; k < 8; k++) sum += (unsigned long long)(k + 1) * w[k];
+        return sum;
+    };
+    size_t non_empty = 0, touching = 0;
+    unsigned long long word_sum = 0, deepest_sum = 0;
+    for (size_t i = 0; i < count; i++) {
+        non_empty += offsets.LocalBuffer()[i + 1] > offsets.LocalBuffer()[i];
+        touching += deepest.LocalBuffer()[i].tri != LBVH_NULL;
+        deepest_sum += (unsigned long long)(i + 1) * weigh(deepest.LocalBuffer()[i]);
+    }
+    for (size_t i = 0; i < (size_t)total; i++) word_sum += weigh(contacts.LocalBuffer()[i]);
+    std::printf("{\"triangles\": %zu, \"shapes\": %zu, \"total\": %llu, \"non_empty\": %zu, \"touching\": %zu, \"word_sum\": %llu, \"deepest_sum\": %llu, "
+                "\"deepest\": [", triangles, count, total, non_empty, touching, word_sum, deepest_sum);
+    size_t shown = 0;
+    for (size_t i = 0; i < count && shown < 3; i++) {
+        if (deepest.LocalBuffer()[i].tri == LBVH_NULL) continue;
+        uint32_t w[8];
+        std::memcpy(w, &deepest.LocalBuffer()[i], sizeof w);
+        std::printf("%s[%zu", shown++ ? ", " : "", i);
+        for (int k = 0; k < 8; k++) std::printf(", %u", w[k]);
+        std::printf("]");
+    }
+    std::printf("]}\n");
+}
+
 static int contacts_main(int argc, char** argv)
 {
     const size_t count = argc > 2 ? (size_t)strtoull(argv[2], nullptr, 10) : 65536;
@@ -770,44 +819,40 @@ static int contacts_main(int argc, char** argv)
         }
     }
     capsules.Sync();
-    lbvh::DataBuffer<uint64_t> offsets(ctx, count + 1);
-    drawer.CapsuleContacts(capsules, offsets, nullptr);
-    offsets.GetData();
-    const unsigned long long total = offsets.LocalBuffer()[count];
-    lbvh::DataBuffer<lbvh_contact> contacts(ctx, total ? (size_t)total : 1);
-    drawer.CapsuleContacts(capsules, offsets, &contacts);
-    lbvh::DataBuffer<lbvh_contact> deepest(ctx, count);
-    drawer.CapsuleDeepest(capsules, deepest);
-    offsets.GetData();
-    contacts.GetData();
-    deepest.GetData();
-    auto weigh = [](const lbvh_contact& c) {
-        uint32_t w[8];
-        std::memcpy(w, &c, sizeof w);
-        unsigned long long sum = 0;
-        for (int k = 0; k < 8; k++) sum += (unsigned long long)(k + 1) * w[k];
-        return sum;
-    };
-    size_t non_empty = 0, touching = 0;
-    unsigned long long word_sum = 0, deepest_sum = 0;
+    contact_report<lbvh_contact>(
+        ctx, capsules, mesh.size(),
+        [&](const lbvh::DataBuffer<lbvh_capsule>& s, lbvh::DataBuffer<uint64_t>& o, lbvh::DataBuffer<lbvh_contact>* c) { drawer.CapsuleContacts(s, o, c); },
+        [&](const lbvh::DataBuffer<lbvh_capsule>& s, lbvh::DataBuffer<lbvh_contact>& d) { drawer.CapsuleDeepest(s, d); });
+    return 0;
+}
+
+static int boxcontacts_main(int argc, char** argv)
+{
+    const size_t count = argc > 2 ? (size_t)strtoull(argv[2], nullptr, 10) : 65536;
+    uint64_t seed = argc > 3 ? strtoull(argv[3], nullptr, 10) : 13;
+    const std::vector<lbvh_triangle> mesh = random_mesh(4096);
+    float lo[3], hi[3];
+    mesh_box(mesh, lo, hi);
+    lbvh::Context ctx(0);
+    lbvh::RaytracingMeshDrawer drawer(ctx, mesh);
+    drawer.Awake();
+    lbvh::DataBuffer<lbvh_obb> boxes(ctx, count);
+    const float half = 3.0f;
     for (size_t i = 0; i < count; i++) {
-        non_empty += offsets.LocalBuffer()[i + 1] > offsets.LocalBuffer()[i];
-        touching += deepest.LocalBuffer()[i].tri != LBVH_NULL;
-        deepest_sum += (unsigned long long)(i + 1) * weigh(deepest.LocalBuffer()[i]);
+        lbvh_obb& b = boxes.LocalBuffer()[i];
+        std::memset(&b, 0, sizeof b);
+        for (int k = 0; k < 3; k++) {
+            b.centre[k] = uniform(seed, lo[k], hi[k]);
+            b.ax[k] = (k == 0 ? half : 0.0f) + uniform(seed, -0.5f * half, 0.5f * half);
+            b.ay[k] = (k == 1 ? half : 0.0f) + uniform(seed, -0.5f * half, 0.5f * half);
+            b.az[k] = (k == 2 ? half : 0.0f) + uniform(seed, -0.5f * half, 0.5f * half);
+        }
     }
-    for (size_t i = 0; i < (size_t)total; i++) word_sum += weigh(contacts.LocalBuffer()[i]);
-    std::printf("{\"triangles\": %zu, \"shapes\": %zu, \"total\": %llu, \"non_empty\": %zu, \"touching\": %zu, \"word_sum\": %llu, \"deepest_sum\": %llu, "
-                "\"deepest\": [", mesh.size(), count, total, non_empty, touching, word_sum, deepest_sum);
-    size_t shown = 0;
-    for (size_t i = 0; i < count && shown < 3; i++) {
-        if (deepest.LocalBuffer()[i].tri == LBVH_NULL) continue;
-        uint32_t w[8];
-        std::memcpy(w, &deepest.LocalBuffer()[i], sizeof w);
-        std::printf("%s[%zu", shown++ ? ", " : "", i);
-        for (int k = 0; k < 8; k++) std::printf(", %u", w[k]);
-        std::printf("]");
-    }
-    std::printf("]}\n");
+    boxes.Sync();
+    contact_report<lbvh_box_contact>(
+        ctx, boxes, mesh.size(),
+        [&](const lbvh::DataBuffer<lbvh_obb>& s, lbvh::DataBuffer<uint64_t>& o, lbvh::DataBuffer<lbvh_box_contact>* c) { drawer.ObbContacts(s, o, c); },
+        [&](const lbvh::DataBuffer<lbvh_obb>& s, lbvh::DataBuffer<lbvh_box_contact>& d) { drawer.ObbDeepest(s, d); });
     return 0;
 }
 
@@ -1124,7 +1169,7 @@ int main(int argc, char** argv)
 {
     static const struct { const char* name; int (*run)(int, char**); } commands[] = {
         {"crossings", crossings_main}, {"points", points_main}, {"knn", knn_main},   {"khits", khits_main}, {"gather", gather_main}, {"sortedhits", sortedhits_main},
-        {"sweep", sweep_main},         {"capsule", capsule_main}, {"boxcast", boxcast_main},         {"overlaps", overlaps_main}, {"tris", tris_main}, {"shapes", shapes_main}, {"contacts", contacts_main}, {"regions", regions_main}, {"rays", rays_main}, {"sort", sort_main},   {"multi", multi_main}};
+        {"sweep", sweep_main},         {"capsule", capsule_main}, {"boxcast", boxcast_main},         {"overlaps", overlaps_main}, {"tris", tris_main}, {"shapes", shapes_main}, {"contacts", contacts_main}, {"boxcontacts", boxcontacts_main}, {"regions", regions_main}, {"rays", rays_main}, {"sort", sort_main},   {"multi", multi_main}};
     try {
         for (const auto& c : commands)
             if (argc > 1 && std::strcmp(argv[1], c.name) == 0) return c.run(argc, argv);

@@ -520,6 +520,23 @@ public:
         check(ctx_.get(), lbvh_capsule_deepest(ctx_.get(), (const lbvh_capsule*)shapes.DeviceBuffer(), shapes.Size(), &s,
                                                (lbvh_contact*)out.DeviceBuffer()));
     }
+    // The same for oriented boxes: ObbOverlaps with a lbvh_box_contact record (depth, tri, the axis of the thirteen that gave it,
+    // back, the unit push-out normal) in place of an index; or the deepest record per box (lbvh_obb_contacts / lbvh_obb_deepest)
+    void ObbContacts(const DataBuffer<lbvh_obb>& shapes, DataBuffer<uint64_t>& offsets, DataBuffer<lbvh_box_contact>* contacts = nullptr)
+    {
+        if (offsets.Size() < shapes.Size() + 1) throw Error(LBVH_ERR_INVALID_ARG, "ObbContacts: offsets needs one entry more than shapes");
+        const lbvh_scene s = container_->Scene();
+        check(ctx_.get(), lbvh_obb_contacts(ctx_.get(), (const lbvh_obb*)shapes.DeviceBuffer(), shapes.Size(), &s,
+                                            (uint64_t*)offsets.DeviceBuffer(), contacts ? (lbvh_box_contact*)contacts->DeviceBuffer() : nullptr,
+                                            contacts ? (uint64_t)contacts->Size() : 0));
+    }
+    void ObbDeepest(const DataBuffer<lbvh_obb>& shapes, DataBuffer<lbvh_box_contact>& out)
+    {
+        if (out.Size() < shapes.Size()) throw Error(LBVH_ERR_INVALID_ARG, "ObbDeepest: fewer records than shapes");
+        const lbvh_scene s = container_->Scene();
+        check(ctx_.get(), lbvh_obb_deepest(ctx_.get(), (const lbvh_obb*)shapes.DeviceBuffer(), shapes.Size(), &s,
+                                           (lbvh_box_contact*)out.DeviceBuffer()));
+    }
     void ObbOverlaps(const DataBuffer<lbvh_obb>& shapes, DataBuffer<uint64_t>& offsets, DataBuffer<uint32_t>* tris = nullptr)
     {
         if (offsets.Size() < shapes.Size() + 1) throw Error(LBVH_ERR_INVALID_ARG, "ObbOverlaps: offsets needs one entry more than shapes");

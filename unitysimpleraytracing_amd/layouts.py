@@ -66,6 +66,11 @@ assert CAPSULE.itemsize == 32 and OBB.itemsize == 64
 # none-record of lbvh_capsule_deepest has tri = NULL below and zeros elsewhere
 CONTACT = np.dtype([("depth", "<f4"), ("tri", "<u4"), ("u", "<f4"), ("v", "<f4"), ("normal", "<f4", 3), ("s", "<f4")])
 assert CONTACT.itemsize == 32
+# lbvh_obb_contacts / lbvh_obb_deepest: one contact of an oriented box with a triangle — depth = the least push along normal that
+# separates them, axis the j of the box cast's thirteen axes that gave it (BOX_AXIS_START: none counted), back the push along
+# -normal on the same axis; the none-record of lbvh_obb_deepest has tri = NULL below and zeros elsewhere
+BOX_CONTACT = np.dtype([("depth", "<f4"), ("tri", "<u4"), ("axis", "<u4"), ("back", "<f4"), ("normal", "<f4", 3), ("_zero", "<u4")])
+assert BOX_CONTACT.itemsize == 32
 # lbvh_region_overlaps / lbvh_region_overlaps_any: six planes {nx, ny, nz, d}, each keeping n . x + d >= 0; the two modes
 REGION = np.dtype([("plane", "<f4", (6, 4))])
 assert REGION.itemsize == 96
