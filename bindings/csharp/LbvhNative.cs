@@ -182,6 +182,12 @@ public static class LbvhNative
     [DllImport(Lib)] public static extern int lbvh_capsule_cast_any(IntPtr ctx, IntPtr dCasts, UIntPtr count, ref Scene scene, IntPtr dFlags);
     [DllImport(Lib)] public static extern int lbvh_box_cast(IntPtr ctx, IntPtr dCasts, UIntPtr count, ref Scene scene, IntPtr dHits);
     [DllImport(Lib)] public static extern int lbvh_box_cast_any(IntPtr ctx, IntPtr dCasts, UIntPtr count, ref Scene scene, IntPtr dFlags);
+    [DllImport(Lib)] public static extern int lbvh_sphere_cast_all(IntPtr ctx, IntPtr dCasts, UIntPtr count, ref Scene scene, IntPtr dOffsets, IntPtr dHits,
+        ulong capacity);
+    [DllImport(Lib)] public static extern int lbvh_capsule_cast_all(IntPtr ctx, IntPtr dCasts, UIntPtr count, ref Scene scene, IntPtr dOffsets, IntPtr dHits,
+        ulong capacity);
+    [DllImport(Lib)] public static extern int lbvh_box_cast_all(IntPtr ctx, IntPtr dCasts, UIntPtr count, ref Scene scene, IntPtr dOffsets, IntPtr dHits,
+        ulong capacity);
     [DllImport(Lib)] public static extern int lbvh_triangle_intersections(IntPtr ctx, IntPtr dQueries, UIntPtr count, ref Scene scene, IntPtr dOffsets,
         IntPtr dTris, ulong capacity);
     [DllImport(Lib)] public static extern int lbvh_triangle_intersects_any(IntPtr ctx, IntPtr dQueries, UIntPtr count, ref Scene scene, IntPtr dFlags);

@@ -1070,6 +1070,62 @@ lbvh_status lbvh_box_cast(lbvh_context* ctx, const lbvh_box_ray* d_casts, size_t
 lbvh_status lbvh_box_cast_any(lbvh_context* ctx, const lbvh_box_ray* d_casts, size_t count, const lbvh_scene* h_scene,
                               uint32_t* d_flags);
 
+/* EVERY contact along `count` sweeps as a CSR list — the "all" form of the three casts (first contact: lbvh_sphere_cast /
+ * lbvh_capsule_cast / lbvh_box_cast, any: their _any forms), what lbvh_gather_hits is to lbvh_trace_closest —, over the same scene
+ * by the four-wide walk of the casts, in the count -> device-side scan -> fill shape of lbvh_gather_hits.  Nothing below is new
+ * arithmetic: every term is the one defined at the shape's cast.
+ *   Active cast, T = min(t_max, LBVH_MAX_FLOAT), the time of contact with one triangle, the triangle's own grown box, its entry
+ *   distance e_i and the candidate rule are exactly those of lbvh_sphere_cast / lbvh_capsule_cast / lbvh_box_cast: triangle i is a
+ *   candidate iff it has a time t_i, t_i < T, the ray of the cast passes the slab test of the triangle's own grown box, and
+ *   !(t_i < e_i).  A NaN never counts; an inactive cast has an empty segment and is never walked.
+ * Output: lbvh_gather_hits' contract, verbatim.
+ *   d_offsets: count + 1 words of 64 bits.  d_offsets[q] = the number of candidates of casts 0 .. q-1, d_offsets[count] = the
+ *   total M.  Always written in full, whatever `capacity` is.
+ *   d_hits, `capacity` records of 16 bytes: segment q = d_hits[d_offsets[q] .. d_offsets[q+1]) = one record per candidate of cast
+ *   q, each exactly once; the four words are the ones the first-contact call would write if that candidate were the nearest:
+ *     lbvh_sphere_cast_all    {t, tri, u, v}, (u, v) lbvh_closest_point_query's for the point c(t) and this triangle;
+ *     lbvh_capsule_cast_all   {t, tri, u, v}, (u, v) through the axis parameter s of the derived triangle that gave the time, or of
+ *                             the pierce, as lbvh_capsule_cast defines them;
+ *     lbvh_box_cast_all       {t, tri, axis, 0} (lbvh_box_hit).
+ *   THE ORDER INSIDE A SEGMENT IS THE WALK'S AND IS NOT PART OF THE CONTRACT.  Every record carries its t: sort a segment by
+ *   (t, tri) if an order is needed — two candidates of a cast never share a triangle index, so that order is canonical.
+ *   lbvh_sort_hit_segments applies unchanged and puts every segment into that order on the device, in place: lbvh_box_hit has t and
+ *   tri in words 0 and 1 like lbvh_hit, and words 2 and 3 (axis, 0) travel with their record as u and v do — pass the box records
+ *   to it as lbvh_hit*.
+ *   Overflow: no record at index >= capacity is ever written; every segment with d_offsets[q+1] <= capacity is complete; records
+ *   below `capacity` that belong to a segment which does not fit are unspecified.  The call never waits on the host and returns
+ *   LBVH_OK in both cases: the caller reads d_offsets[count] (one 8-byte download) to learn whether everything fitted.
+ *   Count-only form: capacity == 0 writes the offsets and walks once (d_hits may be NULL); otherwise the scene is walked twice
+ *   (count, device-side scan, fill).  d_hits == NULL with capacity > 0 is LBVH_ERR_INVALID_ARG.
+ * Hence, for every cast q with m = d_offsets[q+1] - d_offsets[q]: m >= 1 exactly when the shape's _cast_any gives 1; the least
+ * element of segment q by (t, tri), t compared as fp32 values, is the first-contact call's record word for word (the miss record
+ * when m == 0); and every triangle that lbvh_capsule_overlaps / lbvh_obb_overlaps lists for the shape where it stands at t = 0
+ * (capsule {origin, radius, axis}, box {centre, ax, ay, az}) is in the segment with t = +0 (tests/test_cast_all.py asserts the
+ * inclusion on its sets; DESIGN.md records whether equality held there).
+ * Why the list does not depend on the walk: the grown-box containment argument of each cast with the fixed bound T in place of
+ * best.  The grown box of an ancestor contains the grown box of everything below it exactly in fp32, slab entries grow from a box
+ * to any box inside it, so every ancestor of a candidate's leaf passes its slab test with entry <= e <= t < T; the walk skips
+ * only boxes that the ray misses or whose entry is > T.  The bound is T from the first step to the last — nothing shrinks, the
+ * box cast's early out over its axes included, which is fed T —, and nothing is pruned on a box's exit distance.  Each triangle
+ * is exactly one leaf, so each candidate is met exactly once.  The count walk and the fill walk are the same kernel making the
+ * same decisions on t and the entry alone, so a segment never outgrows its slot.
+ * Needs the derived traversal scene (lbvh_build_fast_scene; a stale one is LBVH_ERR_INVALID_ARG), is asynchronous on the
+ * context's stream with no host wait, and uses the context's ray scratch: it drops the path tracer's live-path list (see
+ * lbvh_path_bounce); a failed growth of that scratch is LBVH_ERR_OUT_OF_MEMORY with nothing written.  count == 0 is a no-op:
+ * nothing is enqueued and no buffer is touched, d_offsets[0] included.  Rejected, the message naming the entry point: NULL ctx /
+ * d_casts / h_scene / d_offsets, d_casts or d_hits not 16-byte aligned, d_offsets not 8-byte aligned, count > 2^32 - 1.  Four-wide
+ * walk only (lbvh_debug_ray_walker does not apply); lbvh_debug_ray_waves, lbvh_debug_ray_stack_split, lbvh_debug_ray_stack_limit
+ * and lbvh_ray_stats_target apply as to lbvh_gather_hits (the stats of both walks are added: the full form reports twice the
+ * count-only form's).
+ * One cast per lane.  The cost grows with the swept volume: every grown box the motion crosses before T is opened, where the
+ * first-contact call stops opening boxes behind its best — give a move its real length as t_max, not +inf. */
+lbvh_status lbvh_sphere_cast_all(lbvh_context* ctx, const lbvh_sphere_ray* d_casts, size_t count, const lbvh_scene* h_scene,
+                                 uint64_t* d_offsets, lbvh_hit* d_hits, uint64_t capacity);
+lbvh_status lbvh_capsule_cast_all(lbvh_context* ctx, const lbvh_capsule_ray* d_casts, size_t count, const lbvh_scene* h_scene,
+                                  uint64_t* d_offsets, lbvh_hit* d_hits, uint64_t capacity);
+lbvh_status lbvh_box_cast_all(lbvh_context* ctx, const lbvh_box_ray* d_casts, size_t count, const lbvh_scene* h_scene,
+                              uint64_t* d_offsets, lbvh_box_hit* d_hits, uint64_t capacity);
+
 /* A query triangle: 48 bytes; arrays of them 16-byte aligned. */
 typedef struct lbvh_tri_query {
     float a[3]; uint32_t skip;     /* ORIGINAL index of a scene triangle that is never a candidate; LBVH_NULL = none */
@@ -1498,7 +1554,7 @@ lbvh_status lbvh_path_scatter(lbvh_context* ctx, const lbvh_scene* h_scene, cons
  * lbvh_path_bounce on the same d_states / d_hits listed as live (a list kept by the context).  Every library call that writes
  * into those buffers drops the list (lbvh_path_begin, lbvh_trace_rays, a primary trace into any part of d_hits,
  * lbvh_buffer_upload / _fill_u32 / _free), and so does lbvh_trace_forget — and so do lbvh_trace_closest,
- * lbvh_trace_occluded, lbvh_closest_point_query, lbvh_within_distance, lbvh_count_hits, lbvh_point_crossings, lbvh_box_overlaps, lbvh_gather_within_distance, lbvh_k_closest_points, lbvh_trace_k_closest, lbvh_gather_hits, lbvh_sphere_cast, lbvh_sphere_cast_any, lbvh_capsule_cast, lbvh_capsule_cast_any, lbvh_box_cast, lbvh_box_cast_any, lbvh_triangle_intersections, lbvh_triangle_intersects_any, lbvh_capsule_overlaps, lbvh_capsule_overlaps_any, lbvh_obb_overlaps, lbvh_obb_overlaps_any, lbvh_capsule_contacts, lbvh_capsule_deepest, lbvh_obb_contacts, lbvh_obb_deepest, lbvh_region_overlaps, lbvh_region_overlaps_any and lbvh_region_overlaps_large, whatever buffers they are given, since they use the same ray scratch; then every state is scanned again.  The one exception among the query calls:
+ * lbvh_trace_occluded, lbvh_closest_point_query, lbvh_within_distance, lbvh_count_hits, lbvh_point_crossings, lbvh_box_overlaps, lbvh_gather_within_distance, lbvh_k_closest_points, lbvh_trace_k_closest, lbvh_gather_hits, lbvh_sphere_cast, lbvh_sphere_cast_any, lbvh_capsule_cast, lbvh_capsule_cast_any, lbvh_box_cast, lbvh_box_cast_any, lbvh_triangle_intersections, lbvh_triangle_intersects_any, lbvh_capsule_overlaps, lbvh_capsule_overlaps_any, lbvh_obb_overlaps, lbvh_obb_overlaps_any, lbvh_capsule_contacts, lbvh_capsule_deepest, lbvh_obb_contacts, lbvh_obb_deepest, lbvh_sphere_cast_all, lbvh_capsule_cast_all, lbvh_box_cast_all, lbvh_region_overlaps, lbvh_region_overlaps_any and lbvh_region_overlaps_large, whatever buffers they are given, since they use the same ray scratch; then every state is scanned again.  The one exception among the query calls:
  * lbvh_sort_hit_segments and lbvh_sort_index_segments take no context scratch and keep the live-path list (they drop it only when the
  * buffer they sort is d_hits itself).  What the library
  * cannot see is a write of the CALLER's own (a kernel or hipMemcpy that revives or ends paths, Russian roulette): between two

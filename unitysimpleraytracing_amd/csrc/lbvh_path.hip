@@ -928,8 +928,9 @@ __device__ __forceinline__ float sphere_triangle_time(const ray_t& c, float r, c
     return t;
 }
 
-// cast k into the lane (best_t = T): false (miss record / 0 written, lane stays idle) for an inactive cast
-template <bool ANY>
+// cast k into the lane (best_t = T): false (miss record / 0 written, lane stays idle) for an inactive cast.  !RECORD (the cast-all
+// walk, whose inactive casts have an empty segment): nothing is written and `out` is not read
+template <bool ANY, bool RECORD = true>
 __device__ __forceinline__ bool load_sphere_cast(const lbvh_sphere_ray* __restrict__ casts, uint32_t k, ray_t& ray, float& r, float& best_t,
                                                  std::conditional_t<ANY, uint32_t, lbvh_hit>* __restrict__ out)
 {
@@ -943,7 +944,8 @@ __device__ __forceinline__ bool load_sphere_cast(const lbvh_sphere_ray* __restri
     best_t = fminf(d.w, LBVH_MAX_FLOAT);                 // T: candidates have t < T
     if (o.w > 0.0f && o.w < inf && d.w > 0.0f && (o.x == o.x && o.y == o.y && o.z == o.z) &&
         fabsf(d.x) < inf && fabsf(d.y) < inf && fabsf(d.z) < inf && dot3(d.x, d.y, d.z, d.x, d.y, d.z) > 0.0f) return true;
-    if constexpr (ANY) out[k] = 0u;
+    if constexpr (!RECORD) return false;
+    else if constexpr (ANY) out[k] = 0u;
     else reinterpret_cast<float4*>(out)[k] = make_float4(LBVH_MAX_FLOAT, __uint_as_float(0u), 0.0f, 0.0f);
     return false;
 }
@@ -1148,8 +1150,8 @@ __device__ __forceinline__ void capsule_contact(const ray_t& c, float t, float h
     point_triangle2(cx + hx * s, cy + hy * s, cz + hz * s, a, e1, e2, u_out, v_out);
 }
 
-// cast k into the lane (best_t = T): false (miss record / 0 written, lane stays idle) for an inactive cast
-template <bool ANY>
+// cast k into the lane (best_t = T): false (miss record / 0 written, lane stays idle; !RECORD: nothing written) for an inactive cast
+template <bool ANY, bool RECORD = true>
 __device__ __forceinline__ bool load_capsule_cast(const lbvh_capsule_ray* __restrict__ casts, uint32_t k, ray_t& ray, float& r, float& hx,
                                                   float& hy, float& hz, float& best_t,
                                                   std::conditional_t<ANY, uint32_t, lbvh_hit>* __restrict__ out)
@@ -1166,7 +1168,8 @@ __device__ __forceinline__ bool load_capsule_cast(const lbvh_capsule_ray* __rest
     if (o.w > 0.0f && o.w < inf && d.w > 0.0f && (o.x == o.x && o.y == o.y && o.z == o.z) &&
         fabsf(d.x) < inf && fabsf(d.y) < inf && fabsf(d.z) < inf && dot3(d.x, d.y, d.z, d.x, d.y, d.z) > 0.0f &&
         fabsf(h.x) < inf && fabsf(h.y) < inf && fabsf(h.z) < inf) return true;
-    if constexpr (ANY) out[k] = 0u;
+    if constexpr (!RECORD) return false;
+    else if constexpr (ANY) out[k] = 0u;
     else reinterpret_cast<float4*>(out)[k] = make_float4(LBVH_MAX_FLOAT, __uint_as_float(0u), 0.0f, 0.0f);
     return false;
 }
@@ -1359,8 +1362,8 @@ __device__ __forceinline__ float box_triangle_time(const ray_t& c, const box_axe
     return enter;
 }
 
-// cast k into the lane (best_t = T): false (miss record / 0 written, lane stays idle) for an inactive cast
-template <bool ANY>
+// cast k into the lane (best_t = T): false (miss record / 0 written, lane stays idle; !RECORD: nothing written) for an inactive cast
+template <bool ANY, bool RECORD = true>
 __device__ __forceinline__ bool load_box_cast(const lbvh_box_ray* __restrict__ casts, uint32_t k, ray_t& ray, box_axes& b, float& best_t,
                                               std::conditional_t<ANY, uint32_t, lbvh_box_hit>* __restrict__ out)
 {
@@ -1379,7 +1382,8 @@ __device__ __forceinline__ bool load_box_cast(const lbvh_box_ray* __restrict__ c
         fabsf(d.x) < inf && fabsf(d.y) < inf && fabsf(d.z) < inf && dot3(d.x, d.y, d.z, d.x, d.y, d.z) > 0.0f &&
         fabsf(x.x) < inf && fabsf(x.y) < inf && fabsf(x.z) < inf && fabsf(y.x) < inf && fabsf(y.y) < inf && fabsf(y.z) < inf &&
         fabsf(z.x) < inf && fabsf(z.y) < inf && fabsf(z.z) < inf && fabsf(det) < inf && det != 0.0f) return true;
-    if constexpr (ANY) out[k] = 0u;
+    if constexpr (!RECORD) return false;
+    else if constexpr (ANY) out[k] = 0u;
     else reinterpret_cast<float4*>(out)[k] = make_float4(LBVH_MAX_FLOAT, __uint_as_float(0u), __uint_as_float(0u), __uint_as_float(0u));
     return false;
 }
@@ -2184,6 +2188,148 @@ __global__ __launch_bounds__(64) void gather_hits_wide_kernel(const lbvh_ray* __
         }
     }
     if (STATS) add_ray_stats(stats, n_rays, n_steps, n_tris);
+}
+
+// ---- every contact of a sweep as a CSR list (lbvh_sphere_cast_all / lbvh_capsule_cast_all / lbvh_box_cast_all, include/lbvh.h) --
+// The frame of gather_hits_wide_kernel (count walk, scan, fill walk: the same kernel, the same decisions; persistent waves, lane
+// refill, LDS + device-memory stack, leaf slots first, the first passing inner slot entered and the others pushed) around the
+// arithmetic of the three cast kernels: load_*_cast's activity test and T, the shape's own grown-box slab test (the cast kernel's
+// expressions, the same operations per bound) against the FIXED bound T, and the shape's time of contact — sphere_triangle_time,
+// capsule_triangle_time, box_triangle_time with T where the cast passes its shrinking best_t.  A candidate is what the cast kernel
+// accepts while its best is still (T, 0): hit_counts(t, entry) && t < T.  The count walk decides on t and the entry alone; the fill
+// walk makes the same decision and forms the rest of the record — u / v by point_triangle2 at c(t) (sphere) or capsule_contact
+// (capsule), the axis word (box) — only for an accepted candidate: the float4 the cast would write were that candidate the nearest.
+enum cast_shape : int { kCastSphere = 0, kCastCapsule = 1, kCastBox = 2 };
+template <int SHAPE>
+using cast_ray = std::conditional_t<SHAPE == kCastSphere, lbvh_sphere_ray, std::conditional_t<SHAPE == kCastCapsule, lbvh_capsule_ray, lbvh_box_ray>>;
+
+template <int SHAPE, bool FILL, bool STATS>
+__global__ __launch_bounds__(64) void cast_gather_wide_kernel(const cast_ray<SHAPE>* __restrict__ casts, uint32_t total,
+                                                              const lbvh_wide_node* __restrict__ wide,
+                                                              const lbvh_fast_node* __restrict__ lines,
+                                                              uint32_t* __restrict__ counts,            // !FILL: candidates of cast k
+                                                              const uint64_t* __restrict__ offsets,     // FILL: where segment k starts
+                                                              float4* __restrict__ hits, uint64_t capacity,     // lbvh_hit / lbvh_box_hit records
+                                                              uint32_t* __restrict__ deep,     // [gridDim.x][kWideStackDeep][64]
+                                                              uint32_t lds_depth,              // <= kWideStackLds
+                                                              uint32_t deep_cap,               // <= kWideStackDeep
+                                                              uint32_t* __restrict__ fault, lbvh_ray_stats* stats)
+{
+    __shared__ uint32_t s_stack[kWideStackLds][LBVH_WAVE];
+    uint32_t* my_deep = deep + (size_t)blockIdx.x * (kWideStackDeep * LBVH_WAVE) + threadIdx.x;
+    const uint32_t lane = threadIdx.x;
+    const uint32_t run = max((total + gridDim.x - 1) / gridDim.x, 32u);
+    uint32_t next = blockIdx.x * run;
+    if (next >= total) return;
+    const uint32_t end = min(next + run, total);
+    uint32_t n_casts = 0, n_steps = 0, n_tris = 0;
+
+    bool active = false;
+    uint32_t i = 0;
+    ray_t ray = {};
+    float r = 0.0f, hx = 0.0f, hy = 0.0f, hz = 0.0f;     // sphere: r; capsule: r and the axis
+    box_axes b = {};                                     // box: the half-axis vectors and g, the half extent per world axis
+    float gx = 0.0f, gy = 0.0f, gz = 0.0f;
+    float T = LBVH_MAX_FLOAT;
+    uint32_t n_found = 0, sp = 0, node = 0;
+    uint64_t pos = 0;                                    // FILL: where this lane's next record goes
+    auto push = [&](uint32_t ref) {
+        if (sp < lds_depth) { s_stack[sp][lane] = ref; sp++; }
+        else if (sp < lds_depth + deep_cap) { my_deep[(sp - lds_depth) * LBVH_WAVE] = ref; sp++; }
+        // a dropped entry would be a silently short segment: report it, as the other walkers do (lbvh_debug_ray_stack_limit provokes it)
+        else __hip_atomic_store(fault, LBVH_FAULT_RAY_STACK, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    };
+    for (;;) {
+        const uint64_t idle = __ballot(!active);
+        if (idle != 0 && next < end) {
+            if (!active) {
+                const uint32_t k = next + mbcnt64(idle);
+                if (k < end) {
+                    i = k;
+                    if constexpr (SHAPE == kCastSphere) active = load_sphere_cast<false, false>(casts, k, ray, r, T, nullptr);
+                    else if constexpr (SHAPE == kCastCapsule) active = load_capsule_cast<false, false>(casts, k, ray, r, hx, hy, hz, T, nullptr);
+                    else {
+                        active = load_box_cast<false, false>(casts, k, ray, b, T, nullptr);
+                        gx = (fabsf(b.xx) + fabsf(b.yx)) + fabsf(b.zx);
+                        gy = (fabsf(b.xy) + fabsf(b.yy)) + fabsf(b.zy);
+                        gz = (fabsf(b.xz) + fabsf(b.yz)) + fabsf(b.zz);
+                    }
+                    sp = 0; node = 0;
+                    if constexpr (FILL) { if (active) pos = offsets[k]; }      // (reloaded at every refill: a lane serves many casts)
+                    else { n_found = 0; if (!active) counts[k] = 0u; }
+                    if (STATS && active) n_casts++;
+                }
+            }
+            next += (uint32_t)__popcll(idle);
+        }
+        if (!__any(active) && next >= end) break;
+        if (active) {
+            if (STATS) n_steps++;
+            const float4* w = reinterpret_cast<const float4*>(&wide[node]);
+            const float4 lox = w[0], loy = w[1], loz = w[2], hix = w[3], hiy = w[4], hiz = w[5];
+            const uint4 ref = reinterpret_cast<const uint4*>(w)[6];
+            // the slab test of one slot's grown box: the expressions of the shape's cast kernel
+            auto grown = [&](float lx, float ly, float lz, float ux, float uy, float uz, float& t) {
+                if constexpr (SHAPE == kCastSphere) return wide_box(lx - r, ly - r, lz - r, ux + r, uy + r, uz + r, ray, t);
+                else if constexpr (SHAPE == kCastCapsule) {
+                    // max(h, 0) and min(h, 0) formed here, not held through the walk (capsule_cast_wide_kernel)
+                    const float px = fmaxf(hx, 0.0f), py = fmaxf(hy, 0.0f), pz = fmaxf(hz, 0.0f);
+                    const float nx = fminf(hx, 0.0f), ny = fminf(hy, 0.0f), nz = fminf(hz, 0.0f);
+                    return wide_box((lx - px) - r, (ly - py) - r, (lz - pz) - r, (ux - nx) + r, (uy - ny) + r, (uz - nz) + r, ray, t);
+                } else return wide_box(lx - gx, ly - gy, lz - gz, ux + gx, uy + gy, uz + gz, ray, t);
+            };
+            float t0, t1, t2, t3;
+            const bool h0 = grown(lox.x, loy.x, loz.x, hix.x, hiy.x, hiz.x, t0) && !(t0 > T) && ref.x != kWideEmpty;
+            const bool h1 = grown(lox.y, loy.y, loz.y, hix.y, hiy.y, hiz.y, t1) && !(t1 > T) && ref.y != kWideEmpty;
+            const bool h2 = grown(lox.z, loy.z, loz.z, hix.z, hiy.z, hiz.z, t2) && !(t2 > T) && ref.z != kWideEmpty;
+            const bool h3 = grown(lox.w, loy.w, loz.w, hix.w, hiy.w, hiz.w, t3) && !(t3 > T) && ref.w != kWideEmpty;
+            const uint32_t hit = (h0 ? 1u : 0u) | (h1 ? 2u : 0u) | (h2 ? 4u : 0u) | (h3 ? 8u : 0u);
+            const uint32_t leaf = (ref.x >> 31) | ((ref.y >> 31) << 1) | ((ref.z >> 31) << 2) | ((ref.w >> 31) << 3);
+            uint32_t leaves = hit & leaf, inner = hit & ~leaf;
+            while (leaves != 0u) {
+                const uint32_t k = (uint32_t)__builtin_ctz(leaves);
+                leaves &= leaves - 1u;
+                if (STATS) n_tris++;
+                float4 v0, v1, v2;
+                unpack_fast_triangle(reinterpret_cast<const float4*>(&lines[pick4(ref, k) & 0x7FFFFFFFu]), v0, v1, v2);
+                uint32_t which = 0u;                     // capsule: the winning derived triangle; box: the axis
+                float t_p = 0.0f, t;
+                if constexpr (SHAPE == kCastSphere) t = sphere_triangle_time(ray, r, v0, v1, v2);
+                else if constexpr (SHAPE == kCastCapsule) t = capsule_triangle_time(ray, r, hx, hy, hz, v0, v1, v2, which, t_p);
+                else t = box_triangle_time(ray, b, v0, v1, v2, T, which);      // its early out takes the fixed bound
+                const float entry = k == 0u ? t0 : (k == 1u ? t1 : (k == 2u ? t2 : t3));
+                if (hit_counts(t, entry) && t < T) {
+                    if constexpr (FILL) {
+                        if (pos < capacity) {                                   // never at or beyond the capacity
+                            float4 rec = make_float4(t, v0.w, __uint_as_float(which), __uint_as_float(0u));
+                            if constexpr (SHAPE == kCastSphere)
+                                point_triangle2(ray.ox + ray.dx * t, ray.oy + ray.dy * t, ray.oz + ray.dz * t, v0, v1, v2, rec.z, rec.w);
+                            else if constexpr (SHAPE == kCastCapsule) capsule_contact(ray, t, hx, hy, hz, v0, v1, v2, which, t_p, rec.z, rec.w);
+                            hits[pos] = rec;
+                        }
+                        pos++;
+                    } else {
+                        n_found++;
+                    }
+                }
+            }
+            if (inner != 0u) {
+                node = pick4(ref, (uint32_t)__builtin_ctz(inner));
+                inner &= inner - 1u;
+                while (inner != 0u) {
+                    push(pick4(ref, (uint32_t)__builtin_ctz(inner)));
+                    inner &= inner - 1u;
+                }
+            } else if (sp != 0) {
+                sp--;
+                node = sp < lds_depth ? s_stack[sp][lane] : my_deep[(sp - lds_depth) * LBVH_WAVE];
+            } else {
+                if constexpr (!FILL) counts[i] = n_found;
+                active = false;
+            }
+        }
+    }
+    if (STATS) add_ray_stats(stats, n_casts, n_steps, n_tris);
 }
 
 // ---- triangle queries: which scene triangles a triangle intersects (lbvh_triangle_intersections, include/lbvh.h) ----------
@@ -3857,6 +4003,37 @@ static lbvh_status shape_overlaps(lbvh_context* ctx, const void* d_shapes, size_
     }
 }
 
+// lbvh_sphere_cast_all / lbvh_capsule_cast_all / lbvh_box_cast_all: a CSR answer of hit records (lbvh_box_hit for the box) —
+// lbvh_gather_hits with the shape's walk.  Four-wide walk only.  (a rejection names the entry point)
+template <int SHAPE, class HIT>
+static lbvh_status cast_gathers(lbvh_context* ctx, const cast_ray<SHAPE>* d_casts, size_t count, const lbvh_scene* h_scene, uint64_t* d_offsets,
+                                HIT* d_hits, uint64_t capacity, const char* who)
+{
+    static_assert(sizeof(HIT) == sizeof(float4), "a cast-all record is one float4");
+    if (!ctx) return LBVH_ERR_INVALID_ARG;
+    if (count == 0) return LBVH_OK;
+    NAMED_REQUIRE(d_casts != nullptr && h_scene != nullptr && d_offsets != nullptr);
+    NAMED_REQUIRE(d_hits != nullptr || capacity == 0);
+    NAMED_REQUIRE(((uintptr_t)d_casts & 15) == 0 && ((uintptr_t)d_offsets & 7) == 0 && ((uintptr_t)d_hits & 15) == 0);
+    NAMED_REQUIRE(count <= 0xFFFFFFFFull);
+    walk_launch w;
+    const lbvh_status rc = begin_walk(ctx, h_scene, count, who, true, &w);
+    if (rc != LBVH_OK) return rc;
+    const uint32_t total = (uint32_t)count;
+    return csr_query(
+        ctx, count, d_offsets, capacity,
+        [&](uint32_t* counts) {
+            LBVH_LAUNCH_STATS(ctx, ctx->ray_stats, (cast_gather_wide_kernel<SHAPE, false, STATS>), dim3(w.waves), dim3(LBVH_WAVE), d_casts, total, w.wn,
+                              ctx->fast_nodes, counts, (const uint64_t*)nullptr, (float4*)nullptr, (uint64_t)0, w.deep, w.lds, w.deep_cap, ctx->fault_dev,
+                              ctx->ray_stats);
+        },
+        [&] {
+            LBVH_LAUNCH_STATS(ctx, ctx->ray_stats, (cast_gather_wide_kernel<SHAPE, true, STATS>), dim3(w.waves), dim3(LBVH_WAVE), d_casts, total, w.wn,
+                              ctx->fast_nodes, (uint32_t*)nullptr, (const uint64_t*)d_offsets, (float4*)d_hits, capacity, w.deep, w.lds, w.deep_cap,
+                              ctx->fault_dev, ctx->ray_stats);
+        });
+}
+
 // lbvh_capsule_contacts: shape_overlaps<kShapeCapsule, false> with a record in place of an index — the count walk is that
 // function's, the fill walk forms the contacts.  lbvh_capsule_deepest: one record per shape through launch_per_query.
 static lbvh_status capsule_contacts(lbvh_context* ctx, const lbvh_capsule* d_shapes, size_t count, const lbvh_scene* h_scene, uint64_t* d_offsets,
@@ -4263,6 +4440,24 @@ lbvh_status lbvh_gather_hits(lbvh_context* ctx, const lbvh_ray* d_rays, size_t c
             LBVH_LAUNCH_STATS(ctx, ctx->ray_stats, (gather_hits_wide_kernel<true, STATS>), dim3(w.waves), dim3(LBVH_WAVE), d_rays, total, w.wn, ctx->fast_nodes,
                               (uint32_t*)nullptr, (const uint64_t*)d_offsets, d_hits, capacity, w.deep, w.lds, w.deep_cap, ctx->fault_dev, ctx->ray_stats);
         });
+}
+
+lbvh_status lbvh_sphere_cast_all(lbvh_context* ctx, const lbvh_sphere_ray* d_casts, size_t count, const lbvh_scene* h_scene,
+                                 uint64_t* d_offsets, lbvh_hit* d_hits, uint64_t capacity)
+{
+    return cast_gathers<kCastSphere>(ctx, d_casts, count, h_scene, d_offsets, d_hits, capacity, "lbvh_sphere_cast_all");
+}
+
+lbvh_status lbvh_capsule_cast_all(lbvh_context* ctx, const lbvh_capsule_ray* d_casts, size_t count, const lbvh_scene* h_scene,
+                                  uint64_t* d_offsets, lbvh_hit* d_hits, uint64_t capacity)
+{
+    return cast_gathers<kCastCapsule>(ctx, d_casts, count, h_scene, d_offsets, d_hits, capacity, "lbvh_capsule_cast_all");
+}
+
+lbvh_status lbvh_box_cast_all(lbvh_context* ctx, const lbvh_box_ray* d_casts, size_t count, const lbvh_scene* h_scene,
+                              uint64_t* d_offsets, lbvh_box_hit* d_hits, uint64_t capacity)
+{
+    return cast_gathers<kCastBox>(ctx, d_casts, count, h_scene, d_offsets, d_hits, capacity, "lbvh_box_cast_all");
 }
 
 lbvh_status lbvh_animate(lbvh_context* ctx, const lbvh_triangle* d_rest, uint32_t n, const uint32_t* d_body,

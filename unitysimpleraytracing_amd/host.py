@@ -365,8 +365,9 @@ class DataBuffer:
 def sort_hit_segments(ctx, offsets, hits, count=None):
     """Every segment of a gathered list into (t, tri) order, in place, on the device (lbvh_sort_hit_segments): `offsets` the uint64
     DataBuffer a gather wrote (count + 1 entries; count defaults to offsets.size - 1), `hits` the layouts.HIT DataBuffer given to
-    that gather — its size is the capacity; a segment that did not fit is left as it is.  Needs no scene.  Asynchronous."""
-    _sort_segments(N.lib.lbvh_sort_hit_segments, ctx, offsets, hits, L.HIT, count)
+    that gather — its size is the capacity; a segment that did not fit is left as it is.  Needs no scene.  Asynchronous.
+    The layouts.BOX_HIT records of box_cast_all are taken too: t and tri are in the same words, axis travels with its record."""
+    _sort_segments(N.lib.lbvh_sort_hit_segments, ctx, offsets, hits, L.BOX_HIT if hits.dtype == L.BOX_HIT else L.HIT, count)
 
 
 def sort_index_segments(ctx, offsets, tris, count=None):
@@ -841,6 +842,47 @@ class RaytracingMeshDrawer:
         off, rec = self._csr_lists(self.gather_hits, rays, min_capacity, device_sort, L.HIT, sort_hit_segments)
         if sort:
             segment = np.repeat(np.arange(rays.size), np.diff(off).astype(np.int64))
+            rec = rec[np.lexsort((rec["tri"], rec["t"], segment))]
+        return off, rec
+
+    def sphere_cast_all(self, casts, offsets, hits=None):
+        """EVERY triangle each moving sphere of `casts` (layouts.SPHERE_RAY) touches before t_max, as a CSR list on the caller's
+        buffers exactly as gather_hits writes it: `offsets` (uint64 DataBuffer, at least casts.size + 1 entries) always complete;
+        `hits` (layouts.HIT DataBuffer, its size is the capacity) receives the records sphere_cast would write were that triangle
+        the first, segment q = hits[offsets[q] : offsets[q + 1]], IN NO PARTICULAR ORDER (each record carries its t).  hits=None
+        counts only.  Nothing is written beyond hits.size; offsets[casts.size] says what was needed.  Asynchronous."""
+        self._cast_all(N.lib.lbvh_sphere_cast_all, casts, "SPHERE_RAY", offsets, hits, "HIT")
+
+    def capsule_cast_all(self, casts, offsets, hits=None):
+        """The same for the moving capsules of `casts` (layouts.CAPSULE_RAY): capsule_cast's record of every triangle touched."""
+        self._cast_all(N.lib.lbvh_capsule_cast_all, casts, "CAPSULE_RAY", offsets, hits, "HIT")
+
+    def box_cast_all(self, casts, offsets, hits=None):
+        """The same for the moving boxes of `casts` (layouts.BOX_RAY), `hits` a layouts.BOX_HIT DataBuffer: box_cast's record
+        (t, tri, axis) of every triangle touched.  sort_hit_segments takes these records as they are."""
+        self._cast_all(N.lib.lbvh_box_cast_all, casts, "BOX_RAY", offsets, hits, "BOX_HIT")
+
+    def _cast_all(self, fn, casts, layout, offsets, hits, record):
+        if casts.dtype != getattr(L, layout) or offsets.dtype != np.uint64 or offsets.size < casts.size + 1 or \
+                (hits is not None and hits.dtype != getattr(L, record)):
+            raise ValueError(f"casts must be a DataBuffer of layouts.{layout}, offsets one of uint64 with one entry more, hits one of "
+                             f"layouts.{record} or None")
+        s = self.container.scene()
+        N.check(self.ctx.handle, fn(self.ctx.handle, casts.device, casts.size, C.byref(s), offsets.device,
+                                    hits.device if hits is not None else None, hits.size if hits is not None else 0))
+
+    def cast_all(self, casts, sort=False, device_sort=False, min_capacity=1):
+        """Convenience, as all_hits(): count -> one 8-byte download -> allocate -> fill, for a DataBuffer of layouts.SPHERE_RAY,
+        layouts.CAPSULE_RAY or layouts.BOX_RAY.  Returns (offsets, records): host arrays, uint64[casts.size + 1] and layouts.HIT[total]
+        (layouts.BOX_HIT[total] for boxes).  sort=True orders every segment by (t, tri) on the host; device_sort=True issues
+        sort_hit_segments before the download instead."""
+        calls = {L.SPHERE_RAY: (self.sphere_cast_all, L.HIT), L.CAPSULE_RAY: (self.capsule_cast_all, L.HIT), L.BOX_RAY: (self.box_cast_all, L.BOX_HIT)}
+        if casts.dtype not in calls:
+            raise ValueError("casts must be a DataBuffer of layouts.SPHERE_RAY, layouts.CAPSULE_RAY or layouts.BOX_RAY")
+        call, record = calls[casts.dtype]
+        off, rec = self._csr_lists(call, casts, min_capacity, device_sort, record, sort_hit_segments)
+        if sort:
+            segment = np.repeat(np.arange(casts.size), np.diff(off).astype(np.int64))
             rec = rec[np.lexsort((rec["tri"], rec["t"], segment))]
         return off, rec
 

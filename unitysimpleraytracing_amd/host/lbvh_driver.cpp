@@ -51,6 +51,15 @@
 //                                                [-half_extent / 2, half_extent / 2] (sheared, always solid).  BoxCast and
 //                                                BoxCastAny; prints how many casts touch, how many overlap at the start, the
 //                                                number of records per axis, the word sum and the first records
+//     lbvh_driver castall <sphere|capsule|box> <n_casts> [seed] [t_max]  the 4 096 triangles of cfg1 and n_casts sweeps (seed default 3,
+//                                                t_max default 2): spheres of radius 1.5 drawn as `sweep` draws them, the capsules of
+//                                                `capsule` (radius 1.5, height 4) or the boxes of `boxcast` (half_extent 1.5).  The
+//                                                shape's CastAll (count only, one 8-byte read, fill), SortHitSegments, then the
+//                                                first-contact and the any-contact call on the same casts; prints the total, how many
+//                                                segments are non-empty, how many flags are set, for how many casts the first record of
+//                                                the sorted segment is the first-contact record word for word (the miss record for an
+//                                                empty one), the longest segment, how many records have t = 0, the word sum, the sum
+//                                                of (position + 1) * triangle index over the device-sorted list and the first segments
 //     lbvh_driver crossings [n | file.obj] [count] the mesh and the points of `points`; PointCrossings along the three default
 //                                                directions ((1,1,1)/sqrt 3, (-1,2,3)/sqrt 14, (4,-1,2)/sqrt 21) and CountHits
 //                                                on the same rays written out ({p, 0, dir, +inf}); prints the sum of the counts,
@@ -930,6 +939,40 @@ static int regions_main(int argc, char** argv)
     return 0;
 }
 
+// the casts of `capsule` and of `castall capsule`: per axis the origin and the target as rays_into draws them, then the axis component
+static void capsule_casts(const float lo[3], const float hi[3], uint64_t seed, float radius, float height, float t_max,
+                          std::vector<lbvh_capsule_ray>& casts)
+{
+    for (auto& c : casts) {
+        std::memset(&c, 0, sizeof c);
+        for (int k = 0; k < 3; k++) {
+            const float grow = 0.25f * (hi[k] - lo[k]);
+            c.origin[k] = uniform(seed, lo[k] - grow, hi[k] + grow);
+            c.dir[k] = uniform(seed, lo[k], hi[k]) - c.origin[k];
+            c.axis[k] = uniform(seed, -height, height);
+        }
+        c.radius = radius;
+        c.t_max = t_max;
+    }
+}
+
+// the casts of `boxcast` and of `castall box`: per axis k the centre and the target, then component k of ax, ay, az
+static void box_casts(const float lo[3], const float hi[3], uint64_t seed, float half, float t_max, std::vector<lbvh_box_ray>& casts)
+{
+    for (auto& c : casts) {
+        std::memset(&c, 0, sizeof c);
+        for (int k = 0; k < 3; k++) {
+            const float grow = 0.25f * (hi[k] - lo[k]);
+            c.centre[k] = uniform(seed, lo[k] - grow, hi[k] + grow);
+            c.dir[k] = uniform(seed, lo[k], hi[k]) - c.centre[k];
+            c.ax[k] = (k == 0 ? half : 0.0f) + uniform(seed, -0.5f * half, 0.5f * half);
+            c.ay[k] = (k == 1 ? half : 0.0f) + uniform(seed, -0.5f * half, 0.5f * half);
+            c.az[k] = (k == 2 ? half : 0.0f) + uniform(seed, -0.5f * half, 0.5f * half);
+        }
+        c.t_max = t_max;
+    }
+}
+
 static int capsule_main(int argc, char** argv)
 {
     const size_t count = argc > 2 ? (size_t)strtoull(argv[2], nullptr, 10) : 65536;
@@ -943,17 +986,7 @@ static int capsule_main(int argc, char** argv)
     lbvh::RaytracingMeshDrawer drawer(ctx, mesh);
     drawer.Awake();
     lbvh::DataBuffer<lbvh_capsule_ray> casts(ctx, count);
-    for (auto& c : casts.LocalBuffer()) {
-        std::memset(&c, 0, sizeof c);
-        for (int k = 0; k < 3; k++) {
-            const float grow = 0.25f * (hi[k] - lo[k]);
-            c.origin[k] = uniform(seed, lo[k] - grow, hi[k] + grow);
-            c.dir[k] = uniform(seed, lo[k], hi[k]) - c.origin[k];
-            c.axis[k] = uniform(seed, -height, height);
-        }
-        c.radius = radius;
-        c.t_max = 2.0f;
-    }
+    capsule_casts(lo, hi, seed, radius, height, 2.0f, casts.LocalBuffer());
     casts.Sync();
     lbvh::DataBuffer<lbvh_hit> hits(ctx, count);
     lbvh::DataBuffer<uint32_t> flags(ctx, count);
@@ -994,18 +1027,7 @@ static int boxcast_main(int argc, char** argv)
     lbvh::RaytracingMeshDrawer drawer(ctx, mesh);
     drawer.Awake();
     lbvh::DataBuffer<lbvh_box_ray> casts(ctx, count);
-    for (auto& c : casts.LocalBuffer()) {
-        std::memset(&c, 0, sizeof c);
-        for (int k = 0; k < 3; k++) {
-            const float grow = 0.25f * (hi[k] - lo[k]);
-            c.centre[k] = uniform(seed, lo[k] - grow, hi[k] + grow);
-            c.dir[k] = uniform(seed, lo[k], hi[k]) - c.centre[k];
-            c.ax[k] = (k == 0 ? half : 0.0f) + uniform(seed, -0.5f * half, 0.5f * half);
-            c.ay[k] = (k == 1 ? half : 0.0f) + uniform(seed, -0.5f * half, 0.5f * half);
-            c.az[k] = (k == 2 ? half : 0.0f) + uniform(seed, -0.5f * half, 0.5f * half);
-        }
-        c.t_max = t_max;
-    }
+    box_casts(lo, hi, seed, half, t_max, casts.LocalBuffer());
     casts.Sync();
     lbvh::DataBuffer<lbvh_box_hit> hits(ctx, count);
     lbvh::DataBuffer<uint32_t> flags(ctx, count);
@@ -1034,6 +1056,99 @@ static int boxcast_main(int argc, char** argv)
     }
     std::printf("]}\n");
     return 0;
+}
+
+// `castall`: CAST_ALL (count only, one 8-byte read, fill), SortHitSegments on the device, then what the first-contact call and the
+// any-contact call give on the same casts
+template <class CAST, class HIT, class ALL, class FIRST, class ANY>
+static int castall_report(lbvh::Context& ctx, lbvh::RaytracingMeshDrawer& drawer, const char* shape, size_t triangles, const lbvh::DataBuffer<CAST>& casts, float t_max, ALL all, FIRST first,
+                          ANY any)
+{
+    const size_t count = casts.Size();
+    lbvh::DataBuffer<uint64_t> offsets(ctx, count + 1);
+    all(offsets, (lbvh::DataBuffer<HIT>*)nullptr);          // count only
+    offsets.GetData();
+    const uint64_t total = offsets.LocalBuffer()[count];
+    lbvh::DataBuffer<HIT> hits(ctx, std::max<size_t>((size_t)total, 1));
+    all(offsets, &hits);
+    drawer.SortHitSegments(offsets, hits, count);
+    lbvh::DataBuffer<HIT> nearest(ctx, count);
+    lbvh::DataBuffer<uint32_t> flags(ctx, count);
+    first(nearest);
+    any(flags);
+    offsets.GetData();
+    hits.GetData();
+    nearest.GetData();
+    flags.GetData();
+    const std::vector<uint64_t>& off = offsets.LocalBuffer();
+    const std::vector<HIT>& rec = hits.LocalBuffer();
+    size_t nonempty = 0, at_start = 0, flagged = 0, first_equal = 0;
+    uint64_t longest = 0, words = 0, weighted_sum = 0;
+    for (size_t q = 0; q < count; q++) {
+        const uint64_t m = off[q + 1] - off[q];
+        nonempty += m != 0;
+        longest = std::max(longest, m);
+        flagged += flags.LocalBuffer()[q];
+        const HIT& n = nearest.LocalBuffer()[q];            // the least of a device-sorted segment is the first-contact record
+        first_equal += m != 0 ? std::memcmp(&rec[off[q]], &n, sizeof n) == 0 : n.t == LBVH_MAX_FLOAT;
+    }
+    for (uint64_t i = 0; i < total; i++) {
+        words += word_sum(rec[i]);
+        weighted_sum += (i + 1) * (uint64_t)rec[i].tri;
+        at_start += rec[i].t == 0.0f;
+    }
+    std::printf("{\"shape\": \"%s\", \"triangles\": %zu, \"casts\": %zu, \"t_max\": %.9g, \"total\": %llu, \"nonempty\": %zu, \"flagged\": %zu, "
+                "\"first_equal\": %zu, \"longest\": %llu, \"at_start\": %zu, \"word_sum\": %llu, \"weighted_sum\": %llu, \"rows\": [",
+                shape, triangles, count, t_max, (unsigned long long)total, nonempty, flagged, first_equal, (unsigned long long)longest, at_start,
+                (unsigned long long)words, (unsigned long long)weighted_sum);
+    for (size_t q = 0; q < std::min<size_t>(count, 3); q++) {
+        std::printf("%s[", q ? ", " : "");
+        for (uint64_t j = off[q]; j < off[q + 1]; j++) std::printf("%s[%.9g, %u]", j != off[q] ? ", " : "", rec[j].t, rec[j].tri);
+        std::printf("]");
+    }
+    std::printf("]}\n");
+    return 0;
+}
+
+static int castall_main(int argc, char** argv)
+{
+    const char* shape = argc > 2 ? argv[2] : "sphere";
+    const size_t count = argc > 3 ? (size_t)strtoull(argv[3], nullptr, 10) : 4096;
+    const uint64_t seed = argc > 4 ? strtoull(argv[4], nullptr, 10) : 3;
+    const float t_max = argc > 5 ? (float)atof(argv[5]) : 2.0f;
+    const std::vector<lbvh_triangle> mesh = random_mesh(4096);
+    float lo[3], hi[3];
+    mesh_box(mesh, lo, hi);
+    lbvh::Context ctx(0);
+    lbvh::RaytracingMeshDrawer drawer(ctx, mesh);
+    drawer.Awake();
+    if (std::strcmp(shape, "sphere") == 0) {
+        lbvh::DataBuffer<lbvh_sphere_ray> casts(ctx, count);
+        rays_into(lo, hi, seed, casts.LocalBuffer());
+        for (auto& c : casts.LocalBuffer()) { c.radius = 1.5f; c.t_max = t_max; }
+        casts.Sync();
+        return castall_report<lbvh_sphere_ray, lbvh_hit>(
+            ctx, drawer, shape, mesh.size(), casts, t_max, [&](lbvh::DataBuffer<uint64_t>& o, lbvh::DataBuffer<lbvh_hit>* h) { drawer.SphereCastAll(casts, o, h); },
+            [&](lbvh::DataBuffer<lbvh_hit>& h) { drawer.SphereCast(casts, h); }, [&](lbvh::DataBuffer<uint32_t>& f) { drawer.SphereCastAny(casts, f); });
+    }
+    if (std::strcmp(shape, "capsule") == 0) {
+        lbvh::DataBuffer<lbvh_capsule_ray> casts(ctx, count);
+        capsule_casts(lo, hi, seed, 1.5f, 4.0f, t_max, casts.LocalBuffer());
+        casts.Sync();
+        return castall_report<lbvh_capsule_ray, lbvh_hit>(
+            ctx, drawer, shape, mesh.size(), casts, t_max, [&](lbvh::DataBuffer<uint64_t>& o, lbvh::DataBuffer<lbvh_hit>* h) { drawer.CapsuleCastAll(casts, o, h); },
+            [&](lbvh::DataBuffer<lbvh_hit>& h) { drawer.CapsuleCast(casts, h); }, [&](lbvh::DataBuffer<uint32_t>& f) { drawer.CapsuleCastAny(casts, f); });
+    }
+    if (std::strcmp(shape, "box") == 0) {
+        lbvh::DataBuffer<lbvh_box_ray> casts(ctx, count);
+        box_casts(lo, hi, seed, 1.5f, t_max, casts.LocalBuffer());
+        casts.Sync();
+        return castall_report<lbvh_box_ray, lbvh_box_hit>(
+            ctx, drawer, shape, mesh.size(), casts, t_max, [&](lbvh::DataBuffer<uint64_t>& o, lbvh::DataBuffer<lbvh_box_hit>* h) { drawer.BoxCastAll(casts, o, h); },
+            [&](lbvh::DataBuffer<lbvh_box_hit>& h) { drawer.BoxCast(casts, h); }, [&](lbvh::DataBuffer<uint32_t>& f) { drawer.BoxCastAny(casts, f); });
+    }
+    std::fprintf(stderr, "castall: the shape is sphere, capsule or box\n");
+    return 2;
 }
 
 static int crossings_main(int argc, char** argv)
@@ -1169,7 +1284,7 @@ int main(int argc, char** argv)
 {
     static const struct { const char* name; int (*run)(int, char**); } commands[] = {
         {"crossings", crossings_main}, {"points", points_main}, {"knn", knn_main},   {"khits", khits_main}, {"gather", gather_main}, {"sortedhits", sortedhits_main},
-        {"sweep", sweep_main},         {"capsule", capsule_main}, {"boxcast", boxcast_main},         {"overlaps", overlaps_main}, {"tris", tris_main}, {"shapes", shapes_main}, {"contacts", contacts_main}, {"boxcontacts", boxcontacts_main}, {"regions", regions_main}, {"rays", rays_main}, {"sort", sort_main},   {"multi", multi_main}};
+        {"sweep", sweep_main},         {"capsule", capsule_main}, {"boxcast", boxcast_main}, {"castall", castall_main},         {"overlaps", overlaps_main}, {"tris", tris_main}, {"shapes", shapes_main}, {"contacts", contacts_main}, {"boxcontacts", boxcontacts_main}, {"regions", regions_main}, {"rays", rays_main}, {"sort", sort_main},   {"multi", multi_main}};
     try {
         for (const auto& c : commands)
             if (argc > 1 && std::strcmp(argv[1], c.name) == 0) return c.run(argc, argv);

@@ -612,10 +612,42 @@ public:
         check(ctx_.get(), lbvh_gather_hits(ctx_.get(), (const lbvh_ray*)rays.DeviceBuffer(), rays.Size(), &s, (uint64_t*)offsets.DeviceBuffer(),
                                            hits ? (lbvh_hit*)hits->DeviceBuffer() : nullptr, hits ? (uint64_t)hits->Size() : 0));
     }
+    // EVERY triangle each sweep touches before its t_max, as a CSR list exactly as GatherHits writes it (lbvh_sphere_cast_all /
+    // lbvh_capsule_cast_all / lbvh_box_cast_all; asynchronous): offsets[q] .. offsets[q + 1] = cast q's segment of `hits`, the
+    // records the first-contact call would write were that triangle the first ({t, tri, u, v}; boxes: {t, tri, axis, 0}), IN NO
+    // PARTICULAR ORDER — SortHitSegments orders them by (t, tri).  hits == nullptr counts only; otherwise its size is the capacity.
+    void SphereCastAll(const DataBuffer<lbvh_sphere_ray>& casts, DataBuffer<uint64_t>& offsets, DataBuffer<lbvh_hit>* hits = nullptr)
+    {
+        if (offsets.Size() < casts.Size() + 1) throw Error(LBVH_ERR_INVALID_ARG, "SphereCastAll: offsets needs one entry more than casts");
+        const lbvh_scene s = container_->Scene();
+        check(ctx_.get(), lbvh_sphere_cast_all(ctx_.get(), (const lbvh_sphere_ray*)casts.DeviceBuffer(), casts.Size(), &s, (uint64_t*)offsets.DeviceBuffer(),
+                                               hits ? (lbvh_hit*)hits->DeviceBuffer() : nullptr, hits ? (uint64_t)hits->Size() : 0));
+    }
+    void CapsuleCastAll(const DataBuffer<lbvh_capsule_ray>& casts, DataBuffer<uint64_t>& offsets, DataBuffer<lbvh_hit>* hits = nullptr)
+    {
+        if (offsets.Size() < casts.Size() + 1) throw Error(LBVH_ERR_INVALID_ARG, "CapsuleCastAll: offsets needs one entry more than casts");
+        const lbvh_scene s = container_->Scene();
+        check(ctx_.get(), lbvh_capsule_cast_all(ctx_.get(), (const lbvh_capsule_ray*)casts.DeviceBuffer(), casts.Size(), &s, (uint64_t*)offsets.DeviceBuffer(),
+                                                hits ? (lbvh_hit*)hits->DeviceBuffer() : nullptr, hits ? (uint64_t)hits->Size() : 0));
+    }
+    void BoxCastAll(const DataBuffer<lbvh_box_ray>& casts, DataBuffer<uint64_t>& offsets, DataBuffer<lbvh_box_hit>* hits = nullptr)
+    {
+        if (offsets.Size() < casts.Size() + 1) throw Error(LBVH_ERR_INVALID_ARG, "BoxCastAll: offsets needs one entry more than casts");
+        const lbvh_scene s = container_->Scene();
+        check(ctx_.get(), lbvh_box_cast_all(ctx_.get(), (const lbvh_box_ray*)casts.DeviceBuffer(), casts.Size(), &s, (uint64_t*)offsets.DeviceBuffer(),
+                                            hits ? (lbvh_box_hit*)hits->DeviceBuffer() : nullptr, hits ? (uint64_t)hits->Size() : 0));
+    }
     // Every segment of a gathered list into (t, tri) order / ascending index order, in place, on the device (lbvh_sort_hit_segments,
     // lbvh_sort_index_segments; asynchronous, no scratch, the path tracer's live-path list is kept).  The data buffer's size is the
     // capacity: pass the buffer that was given to GatherHits / the overlap query.  A segment that did not fit is left as it is.
     void SortHitSegments(const DataBuffer<uint64_t>& offsets, DataBuffer<lbvh_hit>& hits, size_t count)
+    {
+        if (offsets.Size() < count + 1) throw Error(LBVH_ERR_INVALID_ARG, "SortHitSegments: offsets needs count + 1 entries");
+        check(ctx_.get(), lbvh_sort_hit_segments(ctx_.get(), (const uint64_t*)offsets.DeviceBuffer(), count, (lbvh_hit*)hits.DeviceBuffer(),
+                                                 (uint64_t)hits.Size()));
+    }
+    // the same for the lbvh_box_hit records of BoxCastAll: t and tri are the same two words, axis travels with its record
+    void SortHitSegments(const DataBuffer<uint64_t>& offsets, DataBuffer<lbvh_box_hit>& hits, size_t count)
     {
         if (offsets.Size() < count + 1) throw Error(LBVH_ERR_INVALID_ARG, "SortHitSegments: offsets needs count + 1 entries");
         check(ctx_.get(), lbvh_sort_hit_segments(ctx_.get(), (const uint64_t*)offsets.DeviceBuffer(), count, (lbvh_hit*)hits.DeviceBuffer(),
