@@ -63,6 +63,11 @@ public static class LbvhNative
     // along -normal on the same axis; tri = 0xFFFFFFFF in the none-record of lbvh_obb_deepest (ShapeContacts.cs)
     [StructLayout(LayoutKind.Sequential)]
     public struct BoxContact { public float depth; public uint tri; public uint axis; public float back; public float normalX, normalY, normalZ; public uint zero; }
+    // lbvh_tri_segment (include/lbvh.h): where a query triangle cuts scene triangle tri, 32 bytes: the two ends p0 and p1, and edges:
+    // bits 0 .. 5 which of the six edge tests passed, bits 8 .. 10 the test that gave p0, bits 12 .. 14 the one that gave p1
+    // (TriangleSegments.cs)
+    [StructLayout(LayoutKind.Sequential)]
+    public struct TriSegment { public float p0X, p0Y, p0Z; public uint tri; public float p1X, p1Y, p1Z; public uint edges; }
 
     // lbvh_point_query / lbvh_closest_point (include/lbvh.h): a point with its squared search radius (active iff maxDist2 > 0) and
     // the nearest triangle's record, 16 bytes each (PointQueries.cs)
@@ -191,6 +196,8 @@ public static class LbvhNative
     [DllImport(Lib)] public static extern int lbvh_triangle_intersections(IntPtr ctx, IntPtr dQueries, UIntPtr count, ref Scene scene, IntPtr dOffsets,
         IntPtr dTris, ulong capacity);
     [DllImport(Lib)] public static extern int lbvh_triangle_intersects_any(IntPtr ctx, IntPtr dQueries, UIntPtr count, ref Scene scene, IntPtr dFlags);
+    [DllImport(Lib)] public static extern int lbvh_triangle_intersection_segments(IntPtr ctx, IntPtr dQueries, UIntPtr count, ref Scene scene, IntPtr dOffsets,
+        IntPtr dSegments, ulong capacity);
     [DllImport(Lib)] public static extern int lbvh_capsule_overlaps(IntPtr ctx, IntPtr dShapes, UIntPtr count, ref Scene scene, IntPtr dOffsets,
         IntPtr dTris, ulong capacity);
     [DllImport(Lib)] public static extern int lbvh_capsule_overlaps_any(IntPtr ctx, IntPtr dShapes, UIntPtr count, ref Scene scene, IntPtr dFlags);

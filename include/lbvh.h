@@ -1198,6 +1198,65 @@ lbvh_status lbvh_triangle_intersections(lbvh_context* ctx, const lbvh_tri_query*
 lbvh_status lbvh_triangle_intersects_any(lbvh_context* ctx, const lbvh_tri_query* d_queries, size_t count, const lbvh_scene* h_scene,
                                          uint32_t* d_flags);
 
+/* Where a query triangle cuts one scene triangle: 32 bytes, arrays 16-byte aligned; written as two 16-byte stores. */
+typedef struct lbvh_tri_segment {
+    float p0[3]; uint32_t tri;     /* one end of the segment; ORIGINAL index of the scene triangle */
+    float p1[3]; uint32_t edges;   /* the other end; which edge tests passed, and which gave p0 / p1 (below) */
+} lbvh_tri_segment;
+
+/* Triangle intersection segments: WHERE does a triangle cut each scene triangle it intersects (the contact polyline between two
+ * meshes, the cut curve of a CSG or slicing step, a cross-section, self-intersection repair), as a CSR list of records over the
+ * derived traversal scene in its four-wide form by the walk of lbvh_triangle_intersections.  The active rule, the query box, `skip`,
+ * rules (1) to (3) and therefore the candidate set are lbvh_triangle_intersections' exactly, from the same operations on the same
+ * values: "is a candidate" there and "has a record" here never disagree, and a caller need not redo the edge arithmetic on the host
+ * (whose roundings would differ from the library's exactly at the bounds).
+ *   The record of a candidate pair, in strict fp32, every operation rounded on its own, dot and pierce as defined above:
+ *     All six edge tests of rule (3) are evaluated, in the order they are listed there, j = 0 .. 5 (j = 0, 1, 2 the query's edges
+ *     from a, b, c; j = 3, 4, 5 the scene triangle's edges (v0, e1), (v0, e2), (v0 + e1, e2 - e1)).  No test ends the sequence.
+ *     For every j that PASSES (0 <= t_j <= 1):   X_j = P_j + D_j * t_j   per component, one multiplication and one addition, with
+ *     the P_j, D_j and t_j the test itself used.
+ *     A running pair (p0, p1) is kept over the passing j in ascending order:
+ *       the first passing j:    p0 = p1 = X_j;
+ *       the second passing j:   p1 = X_j;
+ *       every later passing j:  d01 = dot(p0 - p1, p0 - p1), d0 = dot(p0 - X_j, p0 - X_j), d1 = dot(p1 - X_j, p1 - X_j), the
+ *                               differences per component in fp32;
+ *                               if (d0 > d01 && d0 >= d1) p1 = X_j;   else if (d1 > d01) p0 = X_j;   else nothing changes.
+ *     The passing points lie on the line in which the two triangles' planes meet, so in exact arithmetic this update keeps the two
+ *     extreme points: the segment the triangles share.  In generic position exactly two tests pass and (p0, p1) are those two
+ *     points in the order of j.  A pair with one passing test (a touch at a bound) has p0 == p1, bit for bit.
+ *     edges: bit j (0 .. 5) is set iff test j passed; bits 8 .. 10 hold the j that gave p0, bits 12 .. 14 the j that gave p1; every
+ *     other bit is zero.  A caller stitching a cut polyline can match the ends of neighbouring records by (triangle, edge) — an end
+ *     from j = 0, 1, 2 lies on that edge of the QUERY triangle, one from j = 3, 4, 5 on that edge of scene triangle `tri` — and
+ *     need not compare floats.
+ *   The record is a function of (query, triangle) only, so the list does not depend on the walk by the argument at
+ *   lbvh_triangle_intersections, unchanged.  Coplanar overlap is not reported there and has no segment here.
+ * Output — lbvh_triangle_intersections' CSR contract with a record in place of an index:
+ *   d_offsets: count + 1 words of 64 bits, the SAME words lbvh_triangle_intersections writes for these queries.  Always written in
+ *   full, whatever `capacity` is.
+ *   d_segments, `capacity` records of 32 bytes: segment k = d_segments[d_offsets[k] .. d_offsets[k+1]) = one record per candidate of
+ *   query k, each triangle exactly once.  THE ORDER INSIDE A SEGMENT IS THE WALK'S AND IS NOT PART OF THE CONTRACT (sort by `tri` on
+ *   the host if an order is needed: lbvh_sort_index_segments and lbvh_sort_hit_segments are for 4- and 16-byte records).
+ *   Overflow: no record at index >= capacity is ever written; every segment with d_offsets[k+1] <= capacity is complete; records
+ *   below `capacity` that belong to a segment which does not fit are unspecified.  The call never waits on the host and returns
+ *   LBVH_OK in both cases: the caller reads d_offsets[count] (one 8-byte download) to learn what was needed.
+ *   Count-only form: capacity == 0 writes the offsets and walks once (d_segments may be NULL) — it IS
+ *   lbvh_triangle_intersections' count-only form; otherwise the scene is walked twice (that count walk, the device-side scan, a fill
+ *   walk that takes the candidate decision from the same six t and forms the records, so a segment never outgrows its slot).
+ *   d_segments == NULL with capacity > 0 is LBVH_ERR_INVALID_ARG.
+ * Needs the derived traversal scene (lbvh_build_fast_scene; a stale one is LBVH_ERR_INVALID_ARG), is asynchronous on the context's
+ * stream with no host wait, and uses the context's ray scratch: it drops the path tracer's live-path list (see lbvh_path_bounce).
+ * count == 0 is a no-op: nothing is enqueued and no buffer is touched, d_offsets[0] included.  Rejected: NULL ctx / d_queries /
+ * h_scene / d_offsets, d_queries or d_segments not 16-byte aligned, d_offsets not 8-byte aligned, count > 2^32 - 1.  Four-wide walk
+ * only; lbvh_debug_ray_waves, lbvh_debug_ray_stack_split, lbvh_debug_ray_stack_limit and lbvh_ray_stats_target apply as to
+ * lbvh_triangle_intersections (triangle_tests of the full form is twice the count-only form's).
+ * Cost: the fill walk visits what lbvh_triangle_intersections' visits, but evaluates all six tests for every box-overlapping
+ * triangle where that call stops at the first that passes, and a record is 32 bytes.
+ * Out of scope: a device-side sort of 32-byte record segments; exact coplanar overlap; merging records into polylines; a contact
+ * normal or depth for triangle pairs; an _any form (it is lbvh_triangle_intersects_any) or a form for one huge query. */
+lbvh_status lbvh_triangle_intersection_segments(lbvh_context* ctx, const lbvh_tri_query* d_queries, size_t count,
+                                                const lbvh_scene* h_scene, uint64_t* d_offsets,
+                                                lbvh_tri_segment* d_segments, uint64_t capacity);
+
 /* A capsule where it stands: 32 bytes, arrays 16-byte aligned: every point within `radius` of the segment [origin, origin + axis]
  * (lbvh_capsule_ray without the motion).  _pad is not read. */
 typedef struct lbvh_capsule { float origin[3]; float radius; float axis[3]; uint32_t _pad; } lbvh_capsule;
@@ -1554,7 +1613,7 @@ lbvh_status lbvh_path_scatter(lbvh_context* ctx, const lbvh_scene* h_scene, cons
  * lbvh_path_bounce on the same d_states / d_hits listed as live (a list kept by the context).  Every library call that writes
  * into those buffers drops the list (lbvh_path_begin, lbvh_trace_rays, a primary trace into any part of d_hits,
  * lbvh_buffer_upload / _fill_u32 / _free), and so does lbvh_trace_forget — and so do lbvh_trace_closest,
- * lbvh_trace_occluded, lbvh_closest_point_query, lbvh_within_distance, lbvh_count_hits, lbvh_point_crossings, lbvh_box_overlaps, lbvh_gather_within_distance, lbvh_k_closest_points, lbvh_trace_k_closest, lbvh_gather_hits, lbvh_sphere_cast, lbvh_sphere_cast_any, lbvh_capsule_cast, lbvh_capsule_cast_any, lbvh_box_cast, lbvh_box_cast_any, lbvh_triangle_intersections, lbvh_triangle_intersects_any, lbvh_capsule_overlaps, lbvh_capsule_overlaps_any, lbvh_obb_overlaps, lbvh_obb_overlaps_any, lbvh_capsule_contacts, lbvh_capsule_deepest, lbvh_obb_contacts, lbvh_obb_deepest, lbvh_sphere_cast_all, lbvh_capsule_cast_all, lbvh_box_cast_all, lbvh_region_overlaps, lbvh_region_overlaps_any and lbvh_region_overlaps_large, whatever buffers they are given, since they use the same ray scratch; then every state is scanned again.  The one exception among the query calls:
+ * lbvh_trace_occluded, lbvh_closest_point_query, lbvh_within_distance, lbvh_count_hits, lbvh_point_crossings, lbvh_box_overlaps, lbvh_gather_within_distance, lbvh_k_closest_points, lbvh_trace_k_closest, lbvh_gather_hits, lbvh_sphere_cast, lbvh_sphere_cast_any, lbvh_capsule_cast, lbvh_capsule_cast_any, lbvh_box_cast, lbvh_box_cast_any, lbvh_triangle_intersections, lbvh_triangle_intersects_any, lbvh_triangle_intersection_segments, lbvh_capsule_overlaps, lbvh_capsule_overlaps_any, lbvh_obb_overlaps, lbvh_obb_overlaps_any, lbvh_capsule_contacts, lbvh_capsule_deepest, lbvh_obb_contacts, lbvh_obb_deepest, lbvh_sphere_cast_all, lbvh_capsule_cast_all, lbvh_box_cast_all, lbvh_region_overlaps, lbvh_region_overlaps_any and lbvh_region_overlaps_large, whatever buffers they are given, since they use the same ray scratch; then every state is scanned again.  The one exception among the query calls:
  * lbvh_sort_hit_segments and lbvh_sort_index_segments take no context scratch and keep the live-path list (they drop it only when the
  * buffer they sort is d_hits itself).  What the library
  * cannot see is a write of the CALLER's own (a kernel or hipMemcpy that revives or ends paths, Russian roulette): between two

@@ -2492,6 +2492,161 @@ __global__ __launch_bounds__(64) void triangle_query_wide_kernel(const float4* _
     if (STATS) add_ray_stats(stats, n_queries, n_steps, n_tris);
 }
 
+// ---- triangle intersection segments: WHERE a triangle cuts each scene triangle it intersects ------------------------------
+// (lbvh_triangle_intersection_segments, include/lbvh.h).  The frame, the slot test and `skip` of triangle_query_wide_kernel; the
+// count walk of the call IS that kernel's kTriCount form.  This is the fill walk: it writes a 32-byte lbvh_tri_segment where
+// kTriFill writes an index.
+
+// The header's record of a query (a, b, c) with the triangle line (t0, t1, t2); false: not a candidate.  The six tests are
+// triangles_pierce's — the same operand selection, the same ray_triangle_edges call, so the same six t —, but no test ends the
+// loop: a pair is a candidate iff some t passes, which is the decision of the count walk, and every passing t gives a point
+// X_j = P_j + D_j * t_j (one multiplication and one addition per component).  The loop carries the pass mask, the running pair
+// (six floats) and the two test numbers that gave it; nothing is indexed, so nothing goes to scratch.  Every lane takes six
+// turns: a wave whose lanes disagree on which tests pass still merges at the loop's end.
+// rec0 = {p0, tri (set by the caller)}, rec1 = {p1, edges}.
+__device__ __forceinline__ bool triangle_segment_of(float ax, float ay, float az, float bx, float by, float bz, float cx, float cy, float cz,
+                                                    const float4 t0, const float4 t1, const float4 t2, float4& rec0, float4& rec1)
+{
+    const float abx = bx - ax, aby = by - ay, abz = bz - az;
+    const float acx = cx - ax, acy = cy - ay, acz = cz - az;
+    uint32_t mask = 0u, j0 = 0u, j1 = 0u;
+    float p0x = 0.0f, p0y = 0.0f, p0z = 0.0f, p1x = 0.0f, p1y = 0.0f, p1z = 0.0f;
+#pragma nounroll
+    for (uint32_t j = 0; j < 6u; j++) {
+        const bool query_edge = j < 3u;
+        ray_t r;
+        if (j == 0u) { r.ox = ax; r.oy = ay; r.oz = az; r.dx = abx; r.dy = aby; r.dz = abz; }
+        else if (j == 1u) { r.ox = bx; r.oy = by; r.oz = bz; r.dx = cx - bx; r.dy = cy - by; r.dz = cz - bz; }
+        else if (j == 2u) { r.ox = cx; r.oy = cy; r.oz = cz; r.dx = ax - cx; r.dy = ay - cy; r.dz = az - cz; }
+        else if (j == 3u) { r.ox = t0.x; r.oy = t0.y; r.oz = t0.z; r.dx = t1.x; r.dy = t1.y; r.dz = t1.z; }
+        else if (j == 4u) { r.ox = t0.x; r.oy = t0.y; r.oz = t0.z; r.dx = t2.x; r.dy = t2.y; r.dz = t2.z; }
+        else { r.ox = t0.x + t1.x; r.oy = t0.y + t1.y; r.oz = t0.z + t1.z; r.dx = t2.x - t1.x; r.dy = t2.y - t1.y; r.dz = t2.z - t1.z; }
+        r.ix = 0.0f; r.iy = 0.0f; r.iz = 0.0f;           // (not read by the triangle test)
+        const float4 v = query_edge ? t0 : make_float4(ax, ay, az, 0.0f);
+        float bu = 0.0f, bv = 0.0f;
+        const float t = ray_triangle_edges(r, v, query_edge ? t1.x : abx, query_edge ? t1.y : aby, query_edge ? t1.z : abz,
+                                           query_edge ? t2.x : acx, query_edge ? t2.y : acy, query_edge ? t2.z : acz, bu, bv);
+        if (0.0f <= t && t <= 1.0f) {                    // edge_pierces' decision (false for a NaN t and for the miss value)
+            const float x = r.ox + r.dx * t, y = r.oy + r.dy * t, z = r.oz + r.dz * t;
+            if (mask == 0u) { p0x = x; p0y = y; p0z = z; p1x = x; p1y = y; p1z = z; j0 = j; j1 = j; }
+            else if ((mask & (mask - 1u)) == 0u) { p1x = x; p1y = y; p1z = z; j1 = j; }
+            else {                                       // a third point or later: keep the two that lie farthest apart
+                const float ex = p0x - p1x, ey = p0y - p1y, ez = p0z - p1z;
+                const float fx = p0x - x, fy = p0y - y, fz = p0z - z;
+                const float gx = p1x - x, gy = p1y - y, gz = p1z - z;
+                const float d01 = dot3(ex, ey, ez, ex, ey, ez), d0 = dot3(fx, fy, fz, fx, fy, fz), d1 = dot3(gx, gy, gz, gx, gy, gz);
+                if (d0 > d01 && d0 >= d1) { p1x = x; p1y = y; p1z = z; j1 = j; }
+                else if (d1 > d01) { p0x = x; p0y = y; p0z = z; j0 = j; }
+            }
+            mask |= 1u << j;
+        }
+    }
+    if (mask == 0u) return false;
+    rec0.x = p0x; rec0.y = p0y; rec0.z = p0z;
+    rec1 = make_float4(p1x, p1y, p1z, __uint_as_float(mask | (j0 << 8) | (j1 << 12)));
+    return true;
+}
+
+template <bool STATS>
+__global__ __launch_bounds__(64) void triangle_segment_wide_kernel(const float4* __restrict__ queries, uint32_t total,     // three float4 per query
+                                                                   const lbvh_wide_node* __restrict__ wide,
+                                                                   const lbvh_fast_node* __restrict__ lines,
+                                                                   const uint64_t* __restrict__ offsets,     // where segment k starts
+                                                                   lbvh_tri_segment* __restrict__ out, uint64_t capacity,
+                                                                   uint32_t* __restrict__ deep,     // [gridDim.x][kWideStackDeep][64]
+                                                                   uint32_t lds_depth,              // <= kWideStackLds
+                                                                   uint32_t deep_cap,               // <= kWideStackDeep
+                                                                   uint32_t* __restrict__ fault, lbvh_ray_stats* stats)
+{
+    __shared__ uint32_t s_stack[kWideStackLds][LBVH_WAVE];
+    uint32_t* my_deep = deep + (size_t)blockIdx.x * (kWideStackDeep * LBVH_WAVE) + threadIdx.x;
+    float4* records = reinterpret_cast<float4*>(out);
+    const uint32_t lane = threadIdx.x;
+    const uint32_t run = max((total + gridDim.x - 1) / gridDim.x, 32u);
+    uint32_t next = blockIdx.x * run;
+    if (next >= total) return;
+    const uint32_t end = min(next + run, total);
+    uint32_t n_queries = 0, n_steps = 0, n_tris = 0;
+
+    bool active = false;
+    uint32_t skip = kWideEmpty;
+    float ax = 0.0f, ay = 0.0f, az = 0.0f, bx = 0.0f, by = 0.0f, bz = 0.0f, cx = 0.0f, cy = 0.0f, cz = 0.0f;
+    float lx = 0.0f, ly = 0.0f, lz = 0.0f, hx = 0.0f, hy = 0.0f, hz = 0.0f;      // the query's box
+    uint32_t sp = 0, node = 0;
+    uint64_t pos = 0;                                    // where this lane's next record goes
+    auto push = [&](uint32_t ref) {
+        if (sp < lds_depth) { s_stack[sp][lane] = ref; sp++; }
+        else if (sp < lds_depth + deep_cap) { my_deep[(sp - lds_depth) * LBVH_WAVE] = ref; sp++; }
+        // a dropped entry would be a silently short list: report it, as the other walkers do (lbvh_debug_ray_stack_limit provokes it)
+        else __hip_atomic_store(fault, LBVH_FAULT_RAY_STACK, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    };
+    for (;;) {
+        const uint64_t idle = __ballot(!active);
+        if (idle != 0 && next < end) {
+            if (!active) {
+                const uint32_t k = next + mbcnt64(idle);
+                if (k < end) {
+                    const float inf = __builtin_inff();
+                    const float4 qa = queries[3 * (size_t)k], qb = queries[3 * (size_t)k + 1], qc = queries[3 * (size_t)k + 2];
+                    ax = qa.x; ay = qa.y; az = qa.z; skip = __float_as_uint(qa.w);
+                    bx = qb.x; by = qb.y; bz = qb.z;
+                    cx = qc.x; cy = qc.y; cz = qc.z;
+                    lx = fminf(fminf(ax, bx), cx); ly = fminf(fminf(ay, by), cy); lz = fminf(fminf(az, bz), cz);
+                    hx = fmaxf(fmaxf(ax, bx), cx); hy = fmaxf(fmaxf(ay, by), cy); hz = fmaxf(fmaxf(az, bz), cz);
+                    active = fabsf(ax) < inf && fabsf(ay) < inf && fabsf(az) < inf && fabsf(bx) < inf && fabsf(by) < inf && fabsf(bz) < inf &&
+                             fabsf(cx) < inf && fabsf(cy) < inf && fabsf(cz) < inf;         // all nine finite (false for NaN)
+                    sp = 0; node = 0;
+                    if (active) pos = offsets[k];
+                    if (STATS && active) n_queries++;
+                }
+            }
+            next += (uint32_t)__popcll(idle);
+        }
+        if (!__any(active) && next >= end) break;
+        if (active) {
+            if (STATS) n_steps++;
+            const float4* w = reinterpret_cast<const float4*>(&wide[node]);
+            const float4 lox = w[0], loy = w[1], loz = w[2], hix = w[3], hiy = w[4], hiz = w[5];
+            const uint4 ref = reinterpret_cast<const uint4*>(w)[6];
+            const bool h0 = boxes_overlap(lx, ly, lz, hx, hy, hz, lox.x, loy.x, loz.x, hix.x, hiy.x, hiz.x) && ref.x != kWideEmpty;
+            const bool h1 = boxes_overlap(lx, ly, lz, hx, hy, hz, lox.y, loy.y, loz.y, hix.y, hiy.y, hiz.y) && ref.y != kWideEmpty;
+            const bool h2 = boxes_overlap(lx, ly, lz, hx, hy, hz, lox.z, loy.z, loz.z, hix.z, hiy.z, hiz.z) && ref.z != kWideEmpty;
+            const bool h3 = boxes_overlap(lx, ly, lz, hx, hy, hz, lox.w, loy.w, loz.w, hix.w, hiy.w, hiz.w) && ref.w != kWideEmpty;
+            const uint32_t hit = (h0 ? 1u : 0u) | (h1 ? 2u : 0u) | (h2 ? 4u : 0u) | (h3 ? 8u : 0u);
+            const uint32_t leaf = (ref.x >> 31) | ((ref.y >> 31) << 1) | ((ref.z >> 31) << 2) | ((ref.w >> 31) << 3);
+            uint32_t leaves = hit & leaf, inner = hit & ~leaf;
+            while (leaves != 0u) {
+                const uint32_t k = (uint32_t)__builtin_ctz(leaves);
+                leaves &= leaves - 1u;
+                const uint32_t line = pick4(ref, k) & 0x7FFFFFFFu;
+                float4 t0, t1, t2;
+                unpack_fast_triangle(reinterpret_cast<const float4*>(&lines[line]), t0, t1, t2);
+                if (__float_as_uint(t0.w) == skip) continue;
+                if (STATS) n_tris++;
+                float4 rec0, rec1;
+                rec0.w = t0.w;                                   // the ORIGINAL triangle index
+                if (!triangle_segment_of(ax, ay, az, bx, by, bz, cx, cy, cz, t0, t1, t2, rec0, rec1)) continue;
+                if (pos < capacity) { records[2 * pos] = rec0; records[2 * pos + 1] = rec1; }     // never a record at or beyond the capacity
+                pos++;
+            }
+            if (inner != 0u) {
+                node = pick4(ref, (uint32_t)__builtin_ctz(inner));
+                inner &= inner - 1u;
+                while (inner != 0u) {
+                    push(pick4(ref, (uint32_t)__builtin_ctz(inner)));
+                    inner &= inner - 1u;
+                }
+            } else if (sp != 0) {
+                sp--;
+                node = sp < lds_depth ? s_stack[sp][lane] : my_deep[(sp - lds_depth) * LBVH_WAVE];
+            } else {
+                active = false;
+            }
+        }
+    }
+    if (STATS) add_ray_stats(stats, n_queries, n_steps, n_tris);
+}
+
 // ---- shape overlaps: which triangles a capsule or an oriented box touches where it stands (lbvh_capsule_overlaps, -------
 // lbvh_obb_overlaps, include/lbvh.h).  The frame of triangle_query_wide_kernel with the casts' grown bounds for the slot test: a
 // slot is entered iff the shape's origin (centre) lies in the slot's box grown as capsule_cast_wide_kernel / box_cast_wide_kernel
@@ -3965,6 +4120,34 @@ static lbvh_status triangle_queries(lbvh_context* ctx, const lbvh_tri_query* d_q
     }
 }
 
+// lbvh_triangle_intersection_segments: triangle_queries<false> with a record in place of an index — the count walk is that
+// function's, the fill walk forms the segments.  Four-wide walk only.  (a rejection names the entry point)
+static lbvh_status triangle_segments(lbvh_context* ctx, const lbvh_tri_query* d_queries, size_t count, const lbvh_scene* h_scene, uint64_t* d_offsets,
+                                     lbvh_tri_segment* d_segments, uint64_t capacity, const char* who)
+{
+    if (!ctx) return LBVH_ERR_INVALID_ARG;
+    if (count == 0) return LBVH_OK;
+    NAMED_REQUIRE(d_queries != nullptr && h_scene != nullptr && d_offsets != nullptr);
+    NAMED_REQUIRE(d_segments != nullptr || capacity == 0);
+    NAMED_REQUIRE(((uintptr_t)d_queries & 15) == 0 && ((uintptr_t)d_offsets & 7) == 0 && ((uintptr_t)d_segments & 15) == 0);
+    NAMED_REQUIRE(count <= 0xFFFFFFFFull);
+    walk_launch w;
+    const lbvh_status rc = begin_walk(ctx, h_scene, count, who, true, &w);
+    if (rc != LBVH_OK) return rc;
+    const float4* q = (const float4*)d_queries;
+    const uint32_t total = (uint32_t)count;
+    return csr_query(
+        ctx, count, d_offsets, capacity,
+        [&](uint32_t* counts) {
+            LBVH_LAUNCH_STATS(ctx, ctx->ray_stats, (triangle_query_wide_kernel<kTriCount, STATS>), dim3(w.waves), dim3(LBVH_WAVE), q, total, w.wn, ctx->fast_nodes,
+                              counts, (const uint64_t*)nullptr, (uint32_t*)nullptr, (uint64_t)0, w.deep, w.lds, w.deep_cap, ctx->fault_dev, ctx->ray_stats);
+        },
+        [&] {
+            LBVH_LAUNCH_STATS(ctx, ctx->ray_stats, (triangle_segment_wide_kernel<STATS>), dim3(w.waves), dim3(LBVH_WAVE), q, total, w.wn, ctx->fast_nodes,
+                              (const uint64_t*)d_offsets, d_segments, capacity, w.deep, w.lds, w.deep_cap, ctx->fault_dev, ctx->ray_stats);
+        });
+}
+
 // lbvh_capsule_overlaps / lbvh_obb_overlaps: a CSR answer; lbvh_capsule_overlaps_any / lbvh_obb_overlaps_any: one launch, the
 // flags are the walk's own output — triangle_queries with the shape's walk.  Four-wide walk only.  (a rejection names the entry point)
 template <int SHAPE, bool ANY>
@@ -4246,6 +4429,12 @@ lbvh_status lbvh_triangle_intersects_any(lbvh_context* ctx, const lbvh_tri_query
                                          uint32_t* d_flags)
 {
     return triangle_queries<true>(ctx, d_queries, count, h_scene, nullptr, nullptr, 0, d_flags, "lbvh_triangle_intersects_any");
+}
+
+lbvh_status lbvh_triangle_intersection_segments(lbvh_context* ctx, const lbvh_tri_query* d_queries, size_t count, const lbvh_scene* h_scene,
+                                                uint64_t* d_offsets, lbvh_tri_segment* d_segments, uint64_t capacity)
+{
+    return triangle_segments(ctx, d_queries, count, h_scene, d_offsets, d_segments, capacity, "lbvh_triangle_intersection_segments");
 }
 
 lbvh_status lbvh_capsule_overlaps(lbvh_context* ctx, const lbvh_capsule* d_shapes, size_t count, const lbvh_scene* h_scene,

@@ -93,6 +93,31 @@ def obb_shapes(centre, half_extents, rotation3x3=None):
     return out if out.ndim else out.reshape(1)
 
 
+def tri_queries_from_mesh(triangles, skip_self=False):
+    """layouts.TRI_QUERY records for triangle_intersections / triangle_intersection_segments from another mesh — or the same one:
+    `triangles` is an array of layouts.TRIANGLE, or a tuple (a, b, c) of (n, 3) vertex arrays.  skip_self=True sets skip = each
+    query's own index (a mesh against itself: a triangle never reports itself; neighbours that share a vertex are the caller's to
+    remove from the returned pairs), else layouts.NULL."""
+    if isinstance(triangles, np.ndarray) and triangles.dtype == L.TRIANGLE:
+        a, b, c = (triangles[k][:, :3] for k in "abc")
+    else:
+        a, b, c = (np.asarray(x, dtype=np.float32).reshape(-1, 3) for x in triangles)
+    out = np.zeros(len(a), dtype=L.TRI_QUERY)
+    out["a"], out["b"], out["c"] = a, b, c
+    out["skip"] = np.arange(len(a), dtype=np.uint32) if skip_self else L.NULL
+    return out
+
+
+def segment_edges(records):
+    """The `edges` word of layouts.TRI_SEGMENT records, unpacked: -> (passed, from_p0, from_p1): passed is a bool array (..., 6),
+    passed[..., j] = edge test j passed (j = 0, 1, 2: the query's edges from a, b, c; j = 3, 4, 5: the scene triangle's edges
+    v0-v1, v0-v2, v1-v2); from_p0 / from_p1 the test that gave p0 / p1 — an end from j < 3 lies on that edge of the query triangle, one
+    from j >= 3 on that edge of scene triangle `tri`, so a cut polyline is stitched by (triangle, edge), not by comparing floats."""
+    e = np.asarray(records["edges"] if getattr(records, "dtype", None) == L.TRI_SEGMENT else records, dtype=np.uint32)
+    passed = ((e[..., None] >> np.arange(6, dtype=np.uint32)) & 1).astype(bool)
+    return passed, ((e >> 8) & 7).astype(np.uint32), ((e >> 12) & 7).astype(np.uint32)
+
+
 class _DeviceWords:
     """`count` 32-bit floats at a device pointer, for torch.as_tensor (zero copy)"""
 
@@ -685,6 +710,33 @@ class RaytracingMeshDrawer:
         Returns (offsets, tris): host arrays, uint64[queries.size + 1] and uint32[total].  device_sort=True issues
         sort_index_segments before the download: every segment ascending."""
         return self._csr_lists(self.triangle_intersections, queries, min_capacity, device_sort)
+
+    def triangle_intersection_segments(self, queries, offsets, segments=None):
+        """WHERE each triangle of the DataBuffer `queries` (layouts.TRI_QUERY) cuts every scene triangle it intersects:
+        triangle_intersections with a layouts.TRI_SEGMENT record (the two ends p0, p1 of the shared segment, tri, and `edges`: which
+        of the six edge tests passed and which gave each end; see segment_edges) in place of an index.  `offsets` (uint64
+        DataBuffer, at least queries.size + 1 entries) receives the words triangle_intersections writes; `segments`
+        (layouts.TRI_SEGMENT DataBuffer, its size is the capacity) the records, segment k = segments[offsets[k] : offsets[k + 1]],
+        in no particular order; segments=None counts only.  Asynchronous."""
+        if queries.dtype != L.TRI_QUERY or offsets.dtype != np.uint64 or offsets.size < queries.size + 1 or \
+                (segments is not None and segments.dtype != L.TRI_SEGMENT):
+            raise ValueError("queries must be a DataBuffer of layouts.TRI_QUERY, offsets one of uint64 with one entry more, segments one of "
+                             "layouts.TRI_SEGMENT or None")
+        s = self.container.scene()
+        N.check(self.ctx.handle, N.lib.lbvh_triangle_intersection_segments(self.ctx.handle, queries.device, queries.size, C.byref(s), offsets.device,
+                                                                           segments.device if segments is not None else None,
+                                                                           segments.size if segments is not None else 0))
+
+    def intersection_segments(self, queries, sort=False, min_capacity=1):
+        """Convenience, as intersections(): count -> one 8-byte download -> allocate -> fill, for a DataBuffer of layouts.TRI_QUERY.
+        Returns (offsets, records): host arrays, uint64[queries.size + 1] and layouts.TRI_SEGMENT[total], every segment in the
+        walk's order.  sort=True orders every segment by `tri` HERE, ON THE HOST (each triangle appears once per segment, so the
+        order is total)."""
+        off, rec = self._csr_lists(self.triangle_intersection_segments, queries, min_capacity, False, dtype=L.TRI_SEGMENT)
+        if sort:
+            segment = np.repeat(np.arange(queries.size), np.diff(off).astype(np.int64))
+            rec = rec[np.lexsort((rec["tri"], segment))]
+        return off, rec
 
     def capsule_overlaps(self, shapes, offsets, tris=None):
         """Every triangle each capsule of the DataBuffer `shapes` (layouts.CAPSULE: origin, radius, axis; see capsule_shapes)

@@ -71,6 +71,11 @@
 //                                                SortIndexSegments, TriangleIntersectsAny; prints the total, how many segments are
 //                                                non-empty, how many flags are set, the sum of (position + 1) * triangle index over
 //                                                the device-sorted list (mod 2^64) and the first segments
+//     lbvh_driver trisegs <n_queries> [seed]     the mesh and the queries of `tris`; TriangleIntersectionSegments (count only, one
+//                                                8-byte read, fill), every segment sorted by tri on the host; prints the total, how
+//                                                many segments are non-empty, how many records have two different ends, the sum of
+//                                                (k + 1) * offsets[k] and the sum of (position + 1) * (the record's eight words) over
+//                                                the sorted list (both mod 2^64)
 //     lbvh_driver shapes <n_shapes> [seed]       the 4 096 triangles of cfg1 and n_shapes capsules and as many boxes (SplitMix64, seed
 //                                                default 7): per shape and axis k the capsule's origin uniform in the mesh's box and
 //                                                its axis component uniform in [-6, 6] (radius 3), then the box's centre uniform in
@@ -98,6 +103,7 @@
 //                                                device-sorted list (mod 2^64), and the first TOUCHING segments.  With `large` after
 //                                                the seed the lists come from RegionOverlapsLarge (n_regions <= 65 536): the same
 //                                                numbers, and "large": true in the output
+#include <algorithm>
 #include <chrono>
 #include <cmath>
 #include <cstdio>
@@ -624,18 +630,10 @@ static int overlaps_main(int argc, char** argv)
     return 0;
 }
 
-static int tris_main(int argc, char** argv)
+// the query triangles of `tris` and `trisegs`: per axis a centre uniform in the box, then b's and c's offsets uniform in [-3, 3]
+static void triangles_in(lbvh::DataBuffer<lbvh_tri_query>& queries, uint64_t& seed, const float lo[3], const float hi[3])
 {
-    const size_t count = argc > 2 ? (size_t)strtoull(argv[2], nullptr, 10) : 65536;
-    uint64_t seed = argc > 3 ? strtoull(argv[3], nullptr, 10) : 5;
-    const std::vector<lbvh_triangle> mesh = random_mesh(4096);
-    float lo[3], hi[3];
-    mesh_box(mesh, lo, hi);
-    lbvh::Context ctx(0);
-    lbvh::RaytracingMeshDrawer drawer(ctx, mesh);
-    drawer.Awake();
-    lbvh::DataBuffer<lbvh_tri_query> queries(ctx, count);
-    for (size_t i = 0; i < count; i++) {
+    for (size_t i = 0; i < queries.Size(); i++) {
         lbvh_tri_query& q = queries.LocalBuffer()[i];
         std::memset(&q, 0, sizeof q);
         q.skip = LBVH_NULL;
@@ -647,6 +645,20 @@ static int tris_main(int argc, char** argv)
         }
     }
     queries.Sync();
+}
+
+static int tris_main(int argc, char** argv)
+{
+    const size_t count = argc > 2 ? (size_t)strtoull(argv[2], nullptr, 10) : 65536;
+    uint64_t seed = argc > 3 ? strtoull(argv[3], nullptr, 10) : 5;
+    const std::vector<lbvh_triangle> mesh = random_mesh(4096);
+    float lo[3], hi[3];
+    mesh_box(mesh, lo, hi);
+    lbvh::Context ctx(0);
+    lbvh::RaytracingMeshDrawer drawer(ctx, mesh);
+    drawer.Awake();
+    lbvh::DataBuffer<lbvh_tri_query> queries(ctx, count);
+    triangles_in(queries, seed, lo, hi);
     lbvh::DataBuffer<uint64_t> offsets(ctx, count + 1);
     drawer.TriangleIntersections(queries, offsets);
     offsets.GetData();
@@ -677,6 +689,52 @@ static int tris_main(int argc, char** argv)
         std::printf("]");
     }
     std::printf("]}\n");
+    return 0;
+}
+
+// `tris` with a record in place of an index: TriangleIntersectionSegments (count only, one 8-byte read, fill), every segment sorted
+// by tri on the host.  offset_sum = the sum of (k + 1) * offsets[k], record_sum = the sum of (position + 1) * (the sum of the
+// record's eight words) over the sorted list, both mod 2^64.
+static int trisegs_main(int argc, char** argv)
+{
+    const size_t count = argc > 2 ? (size_t)strtoull(argv[2], nullptr, 10) : 65536;
+    uint64_t seed = argc > 3 ? strtoull(argv[3], nullptr, 10) : 5;
+    const std::vector<lbvh_triangle> mesh = random_mesh(4096);
+    float lo[3], hi[3];
+    mesh_box(mesh, lo, hi);
+    lbvh::Context ctx(0);
+    lbvh::RaytracingMeshDrawer drawer(ctx, mesh);
+    drawer.Awake();
+    lbvh::DataBuffer<lbvh_tri_query> queries(ctx, count);
+    triangles_in(queries, seed, lo, hi);
+    lbvh::DataBuffer<uint64_t> offsets(ctx, count + 1);
+    drawer.TriangleIntersectionSegments(queries, offsets);
+    offsets.GetData();
+    const unsigned long long total = offsets.LocalBuffer()[count];
+    lbvh::DataBuffer<lbvh_tri_segment> segments(ctx, total ? (size_t)total : 1);
+    drawer.TriangleIntersectionSegments(queries, offsets, &segments);
+    offsets.GetData();
+    segments.GetData();
+    std::vector<lbvh_tri_segment>& rec = segments.LocalBuffer();
+    size_t non_empty = 0, two_ends = 0;
+    unsigned long long offset_sum = 0, record_sum = 0;
+    for (size_t k = 0; k <= count; k++) offset_sum += (unsigned long long)(k + 1) * offsets.LocalBuffer()[k];
+    for (size_t k = 0; k < count; k++) {
+        const uint64_t first = offsets.LocalBuffer()[k], last = offsets.LocalBuffer()[k + 1];
+        non_empty += last > first;
+        std::sort(rec.begin() + (ptrdiff_t)first, rec.begin() + (ptrdiff_t)last,
+                  [](const lbvh_tri_segment& x, const lbvh_tri_segment& y) { return x.tri < y.tri; });
+    }
+    for (size_t i = 0; i < (size_t)total; i++) {
+        uint32_t w[8];
+        std::memcpy(w, &rec[i], sizeof w);
+        unsigned long long words = 0;
+        for (uint32_t x : w) words += x;
+        record_sum += (unsigned long long)(i + 1) * words;
+        two_ends += ((rec[i].edges >> 8) & 7u) != ((rec[i].edges >> 12) & 7u);
+    }
+    std::printf("{\"triangles\": %zu, \"queries\": %zu, \"total\": %llu, \"non_empty\": %zu, \"two_ends\": %zu, \"offset_sum\": %llu, "
+                "\"record_sum\": %llu}\n", mesh.size(), count, total, non_empty, two_ends, offset_sum, record_sum);
     return 0;
 }
 
@@ -1284,7 +1342,7 @@ int main(int argc, char** argv)
 {
     static const struct { const char* name; int (*run)(int, char**); } commands[] = {
         {"crossings", crossings_main}, {"points", points_main}, {"knn", knn_main},   {"khits", khits_main}, {"gather", gather_main}, {"sortedhits", sortedhits_main},
-        {"sweep", sweep_main},         {"capsule", capsule_main}, {"boxcast", boxcast_main}, {"castall", castall_main},         {"overlaps", overlaps_main}, {"tris", tris_main}, {"shapes", shapes_main}, {"contacts", contacts_main}, {"boxcontacts", boxcontacts_main}, {"regions", regions_main}, {"rays", rays_main}, {"sort", sort_main},   {"multi", multi_main}};
+        {"sweep", sweep_main},         {"capsule", capsule_main}, {"boxcast", boxcast_main}, {"castall", castall_main},         {"overlaps", overlaps_main}, {"tris", tris_main}, {"trisegs", trisegs_main}, {"shapes", shapes_main}, {"contacts", contacts_main}, {"boxcontacts", boxcontacts_main}, {"regions", regions_main}, {"rays", rays_main}, {"sort", sort_main},   {"multi", multi_main}};
     try {
         for (const auto& c : commands)
             if (argc > 1 && std::strcmp(argv[1], c.name) == 0) return c.run(argc, argv);

@@ -484,6 +484,20 @@ public:
         check(ctx_.get(), lbvh_triangle_intersects_any(ctx_.get(), (const lbvh_tri_query*)queries.DeviceBuffer(), queries.Size(), &s,
                                                        (uint32_t*)flags.DeviceBuffer()));
     }
+    // WHERE each query triangle cuts every scene triangle it intersects: TriangleIntersections with a lbvh_tri_segment record (the
+    // two ends p0, p1, tri, and edges: which of the six edge tests passed and which gave each end) in place of an index, the same
+    // offsets (lbvh_triangle_intersection_segments; asynchronous)
+    void TriangleIntersectionSegments(const DataBuffer<lbvh_tri_query>& queries, DataBuffer<uint64_t>& offsets,
+                                      DataBuffer<lbvh_tri_segment>* segments = nullptr)
+    {
+        if (offsets.Size() < queries.Size() + 1)
+            throw Error(LBVH_ERR_INVALID_ARG, "TriangleIntersectionSegments: offsets needs one entry more than queries");
+        const lbvh_scene s = container_->Scene();
+        check(ctx_.get(), lbvh_triangle_intersection_segments(ctx_.get(), (const lbvh_tri_query*)queries.DeviceBuffer(), queries.Size(), &s,
+                                                              (uint64_t*)offsets.DeviceBuffer(),
+                                                              segments ? (lbvh_tri_segment*)segments->DeviceBuffer() : nullptr,
+                                                              segments ? (uint64_t)segments->Size() : 0));
+    }
     // WHICH triangles each capsule (lbvh_capsule: origin, radius, axis) or oriented box (lbvh_obb: centre and the three half-axis
     // vectors) touches where it stands — the start overlap of CapsuleCast / BoxCast without a direction —, as the same CSR list, or
     // one flag per shape (lbvh_capsule_overlaps / _any, lbvh_obb_overlaps / _any; asynchronous)

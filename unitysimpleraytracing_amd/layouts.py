@@ -54,6 +54,10 @@ assert POINT_QUERY.itemsize == 16 and CLOSEST_POINT.itemsize == 16
 # never a candidate (NULL below, LBVH_NULL: none)
 TRI_QUERY = np.dtype([("a", "<f4", 3), ("skip", "<u4"), ("b", "<f4", 3), ("_pad0", "<u4"), ("c", "<f4", 3), ("_pad1", "<u4")])
 assert TRI_QUERY.itemsize == 48
+# lbvh_triangle_intersection_segments: where a query triangle cuts scene triangle `tri` — the two ends p0, p1 and `edges`: bits 0 .. 5
+# which of the six edge tests passed, bits 8 .. 10 the test that gave p0, bits 12 .. 14 the one that gave p1 (host.segment_edges)
+TRI_SEGMENT = np.dtype([("p0", "<f4", 3), ("tri", "<u4"), ("p1", "<f4", 3), ("edges", "<u4")])
+assert TRI_SEGMENT.itemsize == 32
 # lbvh_capsule_overlaps / lbvh_obb_overlaps and their _any forms: a capsule (the segment origin .. origin + axis and the radius) and
 # an oriented box { centre + s0*ax + s1*ay + s2*az : |s_i| <= 1 } where they stand — CAPSULE_RAY and BOX_RAY without the motion;
 # the pads are not read
