@@ -58,6 +58,13 @@ public static class LbvhNative
     // axis; tri = 0xFFFFFFFF in the none-record of lbvh_capsule_deepest (ShapeContacts.cs)
     [StructLayout(LayoutKind.Sequential)]
     public struct Contact { public float depth; public uint tri; public float u, v; public float normalX, normalY, normalZ; public float s; }
+    // lbvh_segment_query / lbvh_segment_closest (include/lbvh.h): the segment origin .. origin + axis with its squared search radius
+    // (active iff maxDist2 > 0), and the answer, 32 bytes: dist2 of the segment from triangle tri (2139095040 = none), the nearest
+    // point a + e1*u + e2*v on the triangle, delta from it to the nearest point origin + axis*s of the segment (SegmentQueries.cs)
+    [StructLayout(LayoutKind.Sequential)]
+    public struct SegmentQuery { public float originX, originY, originZ, maxDist2; public float axisX, axisY, axisZ; public uint pad; }
+    [StructLayout(LayoutKind.Sequential)]
+    public struct SegmentClosest { public float dist2; public uint tri; public float u, v; public float deltaX, deltaY, deltaZ; public float s; }
     // lbvh_box_contact (include/lbvh.h): one contact of an oriented box with a triangle, 32 bytes: depth = the least push along the
     // unit normal that separates them, axis = which of the box cast's thirteen axes gave it (13: none counted), back = the push
     // along -normal on the same axis; tri = 0xFFFFFFFF in the none-record of lbvh_obb_deepest (ShapeContacts.cs)
@@ -204,6 +211,8 @@ public static class LbvhNative
     [DllImport(Lib)] public static extern int lbvh_capsule_contacts(IntPtr ctx, IntPtr dShapes, UIntPtr count, ref Scene scene, IntPtr dOffsets,
         IntPtr dContacts, ulong capacity);
     [DllImport(Lib)] public static extern int lbvh_capsule_deepest(IntPtr ctx, IntPtr dShapes, UIntPtr count, ref Scene scene, IntPtr dOut);
+    [DllImport(Lib)] public static extern int lbvh_segment_closest_point(IntPtr ctx, IntPtr dQueries, UIntPtr count, ref Scene scene, IntPtr dOut);
+    [DllImport(Lib)] public static extern int lbvh_segment_within_distance(IntPtr ctx, IntPtr dQueries, UIntPtr count, ref Scene scene, IntPtr dFlags);
     [DllImport(Lib)] public static extern int lbvh_obb_contacts(IntPtr ctx, IntPtr dShapes, UIntPtr count, ref Scene scene, IntPtr dOffsets,
         IntPtr dContacts, ulong capacity);
     [DllImport(Lib)] public static extern int lbvh_obb_deepest(IntPtr ctx, IntPtr dShapes, UIntPtr count, ref Scene scene, IntPtr dOut);

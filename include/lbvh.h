@@ -1414,6 +1414,91 @@ lbvh_status lbvh_capsule_contacts(lbvh_context* ctx, const lbvh_capsule* d_shape
 lbvh_status lbvh_capsule_deepest(lbvh_context* ctx, const lbvh_capsule* d_shapes, size_t count, const lbvh_scene* h_scene,
                                  lbvh_contact* d_out);
 
+/* A segment query: 32 bytes, arrays 16-byte aligned: lbvh_capsule with a search bound in place of the radius. */
+typedef struct lbvh_segment_query {
+    float origin[3]; float max_dist2;  /* squared search radius; +inf or >= LBVH_MAX_FLOAT = unbounded */
+    float axis[3];   uint32_t _pad;    /* the segment is [origin, origin + axis]; _pad is not read */
+} lbvh_segment_query;
+
+/* The answer to one: 32 bytes, arrays 16-byte aligned; written as two 16-byte stores. */
+typedef struct lbvh_segment_closest {
+    float    dist2;                /* squared distance of the segment from the triangle; LBVH_MAX_FLOAT if none */
+    uint32_t tri;                  /* ORIGINAL triangle index; 0 if none */
+    float    u, v;                 /* nearest point on the triangle: a + e1*u + e2*v */
+    float    delta[3];             /* from that point to the nearest point of the segment; (0, 0, 0) if pierced / none */
+    float    s;                    /* nearest point on the segment: origin + axis*s */
+} lbvh_segment_closest;
+
+/* Segment closest-point queries: HOW FAR is a segment from the mesh, WHERE and IN WHICH DIRECTION (a capsule's clearance when it
+ * touches nothing: Physics.ClosestPoint and the separated case of Physics.ComputePenetration, agent clearance, speculative
+ * contacts inside a margin, the nearest surface to a bone, a cable or an edge), as the nearest record per segment
+ * (lbvh_segment_closest_point) or as one flag per segment (lbvh_segment_within_distance), over the derived traversal scene in its
+ * four-wide form by the walk of lbvh_closest_point_query: one segment per lane, the nearest child box first, boxes farther than
+ * the best distance so far skipped.  lbvh_closest_point_query at sample points along the axis misses the nearest feature between
+ * samples; lbvh_capsule_deepest with the radius blown up to the search distance prunes nothing beyond its rule 1.  Distance,
+ * unlike depth, has a box bound that is monotone in the box.
+ *   Active query (o = origin, h = axis): max_dist2 > 0 (false for NaN), no NaN in origin, every component of axis finite.
+ *   axis = 0 is allowed (a point, by this definition's arithmetic).  An inactive query is never walked; it gets the none-record
+ *   {LBVH_MAX_FLOAT, 0, 0, 0, {0, 0, 0}, 0} (lbvh_segment_closest_point) or 0 (lbvh_segment_within_distance).
+ *   R = min(max_dist2, LBVH_MAX_FLOAT), as at the point queries.
+ *   Distance of the segment to one triangle (the line a, e1, e2 of the derived scene), in strict fp32, every operation rounded on
+ *   its own: steps 1 - 3 of lbvh_capsule_contacts, with dot, pierce, dist2 and the derived triangles as defined above.
+ *     1. Pierce first.  pierce(o, h; a, e1, e2) of lbvh_triangle_intersections is evaluated first.  If it passes, 0 <= t_p <= 1:
+ *        dist2 = +0, s = t_p, delta = (0, 0, 0), and (u, v) are lbvh_closest_point_query's for x = o + h*t_p (per component
+ *        o_k + h_k*t_p) against a, e1, e2.
+ *     2. Otherwise the nearest derived triangle: d_j = dist2 of lbvh_closest_point_query for o against derived triangle j = 0 .. 7
+ *        of lbvh_capsule_cast, with its barycentrics (u', v').  Start with least = +inf and j* = 0; in the order j = 0 .. 7, d_j
+ *        replaces least, and j replaces j*, only when d_j < least (strictly; false for a NaN).  s from j* exactly as
+ *        lbvh_capsule_cast derives it: 0 for j* = 0, 1 for j* = 1, v' for j* = 2, 4, 6 and 1 - v' for j* = 3, 5, 7.
+ *     3. On the scene triangle: x = o + h*s per component; (u, v), ap = x - a, the residual rv = ap - (e1*u + e2*v) per component
+ *        and dist2 = dot(rv, rv) are lbvh_closest_point_query's for x against a, e1, e2.  delta = rv: the vector from the nearest
+ *        point of the triangle to the nearest point of the segment.
+ *   No square root and no division beyond the point test's own.  A NaN dist2 never counts (every comparison with it is false).
+ *   Distance to a box: the box grown by the axis only, one fp32 operation per bound, max and min as fmaxf and fminf,
+ *       lo'_k = lo_k - max(h_k, 0)      hi'_k = hi_k - min(h_k, 0)
+ *   and box2g = box2 of lbvh_closest_point_query for the point o against (lo', hi'): per axis g = max(max(lo' - o, o - hi'), 0),
+ *   (gx*gx + gy*gy) + gz*gz.  (Some point of the segment is in the box, per axis, exactly when o is in the grown box.)
+ *   Candidate: triangle i is a candidate for a query iff dist2_i < R and !(dist2_i < box2g(own AABB_i)), the own AABB being
+ *   scene.triangle_aabb[i].
+ *   lbvh_segment_closest_point: d_out[k] = {dist2, tri, u, v, delta, s} of query k's candidate with the least dist2 (compared as
+ *   fp32 values); on equal dist2 the lower original triangle index, whatever order the walk meets them in.  No candidate: the
+ *   none-record, never R.  Every one of the `count` records is written, as two 16-byte stores.
+ *   lbvh_segment_within_distance: d_flags[k] = 1 if query k has any candidate, else 0.  The walk is the closest walk (same
+ *   nearest-first order) cut off at its first accepted candidate: never more node fetches or triangle tests per query.
+ * Why the record does not depend on the order of the walk (the argument at lbvh_closest_point_query with grown boxes): the grown
+ * bounds lo - max(h, 0) and hi - min(h, 0) are monotone in lo and hi, fp32 subtraction, max, multiplication of non-negatives and
+ * addition are monotone, and every box of the derived tree, binary or four-wide, is the exact min / max union of what is below it;
+ * so box2g(ancestor) <= box2g(leaf) <= dist2 for every candidate.  A slot is skipped only if box2g > best, strictly: a subtree
+ * skipped that way holds no candidate at or below best.  The grown box contains box + segment [0, -h], so box2g is a true lower
+ * bound of the distance in exact arithmetic; a dist2 below its own box's box2g is fp32 noise of the triangle arithmetic, which
+ * the accept rule removes, as at the point query (on ordinary meshes it rejects nothing).
+ * Relations (tests/test_segment_closest.py holds each):
+ *   (a) the flag is 1 exactly when the record's dist2 != LBVH_MAX_FLOAT.
+ *   (b) with axis = (+0, +0, +0), the same point and the same max_dist2, the first four words {dist2, tri, u, v} equal
+ *       lbvh_closest_point_query's record word for word: x = o + 0*s is o exactly, the box is not grown, and the pierce has
+ *       det = 0.  (A derived triangle j >= 1, formed again from a + e, may win by a rounding and give another s; x is o all the
+ *       same.  Not covered: an origin component that is -0, where o + 0*s is +0.)
+ *   (c) per pair: if the capsule {o, r, h} lists the winning triangle in lbvh_capsule_contacts, that contact's s, u, v equal this
+ *       record's; when that contact is not a face contact, its depth == r - sqrtf(dist2) and its normal == delta / sqrtf(dist2)
+ *       per component, word for word.
+ *   (d) the converse of "touching" is NOT promised: rule 2 of lbvh_capsule_overlaps compares d_j <= r*r on the derived triangles;
+ *       dist2 here is the ninth test, on the scene triangle at x, and may lie one rounding on the other side of r*r.
+ * Both need the derived traversal scene (lbvh_build_fast_scene; a stale one is LBVH_ERR_INVALID_ARG), are asynchronous on the
+ * context's stream with no host wait, and use the context's ray scratch: they drop the path tracer's live-path list (see
+ * lbvh_path_bounce).  count == 0 is a no-op.  Rejected: NULL pointers, d_queries or d_out not 16-byte aligned, d_flags not 4-byte
+ * aligned, count > 2^32 - 1.  Four-wide walk only (lbvh_debug_ray_walker does not apply); lbvh_debug_ray_waves,
+ * lbvh_debug_ray_stack_split, lbvh_debug_ray_stack_limit and lbvh_ray_stats_target apply as to the capsule contacts (`rays` =
+ * active queries; triangle_tests counts the triangle lines read, whatever number of derived triangles is tested).
+ * Cost: a point query's walk on boxes larger by the axis, and per triangle line the pierce and up to nine point tests.  Pass
+ * active queries only where time matters, as at the point queries.
+ * Out of scope: the k nearest triangles of a segment; a gather of every triangle within the distance (lbvh_capsule_overlaps with
+ * the radius as the distance lists them); oriented boxes (the library has no closed per-pair distance for them yet); a unit
+ * normal in the record (delta / sqrtf(dist2) where dist2 > 0; the caller's square root). */
+lbvh_status lbvh_segment_closest_point(lbvh_context* ctx, const lbvh_segment_query* d_queries, size_t count, const lbvh_scene* h_scene,
+                                       lbvh_segment_closest* d_out);
+lbvh_status lbvh_segment_within_distance(lbvh_context* ctx, const lbvh_segment_query* d_queries, size_t count, const lbvh_scene* h_scene,
+                                         uint32_t* d_flags);
+
 /* One contact of an oriented box with a triangle: 32 bytes, arrays 16-byte aligned; written as two 16-byte stores. */
 typedef struct lbvh_box_contact {
     float    depth;                /* least push, along normal, that separates the box from the triangle; >= 0 */
@@ -1613,7 +1698,7 @@ lbvh_status lbvh_path_scatter(lbvh_context* ctx, const lbvh_scene* h_scene, cons
  * lbvh_path_bounce on the same d_states / d_hits listed as live (a list kept by the context).  Every library call that writes
  * into those buffers drops the list (lbvh_path_begin, lbvh_trace_rays, a primary trace into any part of d_hits,
  * lbvh_buffer_upload / _fill_u32 / _free), and so does lbvh_trace_forget — and so do lbvh_trace_closest,
- * lbvh_trace_occluded, lbvh_closest_point_query, lbvh_within_distance, lbvh_count_hits, lbvh_point_crossings, lbvh_box_overlaps, lbvh_gather_within_distance, lbvh_k_closest_points, lbvh_trace_k_closest, lbvh_gather_hits, lbvh_sphere_cast, lbvh_sphere_cast_any, lbvh_capsule_cast, lbvh_capsule_cast_any, lbvh_box_cast, lbvh_box_cast_any, lbvh_triangle_intersections, lbvh_triangle_intersects_any, lbvh_triangle_intersection_segments, lbvh_capsule_overlaps, lbvh_capsule_overlaps_any, lbvh_obb_overlaps, lbvh_obb_overlaps_any, lbvh_capsule_contacts, lbvh_capsule_deepest, lbvh_obb_contacts, lbvh_obb_deepest, lbvh_sphere_cast_all, lbvh_capsule_cast_all, lbvh_box_cast_all, lbvh_region_overlaps, lbvh_region_overlaps_any and lbvh_region_overlaps_large, whatever buffers they are given, since they use the same ray scratch; then every state is scanned again.  The one exception among the query calls:
+ * lbvh_trace_occluded, lbvh_closest_point_query, lbvh_within_distance, lbvh_count_hits, lbvh_point_crossings, lbvh_box_overlaps, lbvh_gather_within_distance, lbvh_k_closest_points, lbvh_trace_k_closest, lbvh_gather_hits, lbvh_sphere_cast, lbvh_sphere_cast_any, lbvh_capsule_cast, lbvh_capsule_cast_any, lbvh_box_cast, lbvh_box_cast_any, lbvh_triangle_intersections, lbvh_triangle_intersects_any, lbvh_triangle_intersection_segments, lbvh_capsule_overlaps, lbvh_capsule_overlaps_any, lbvh_obb_overlaps, lbvh_obb_overlaps_any, lbvh_capsule_contacts, lbvh_capsule_deepest, lbvh_obb_contacts, lbvh_obb_deepest, lbvh_segment_closest_point, lbvh_segment_within_distance, lbvh_sphere_cast_all, lbvh_capsule_cast_all, lbvh_box_cast_all, lbvh_region_overlaps, lbvh_region_overlaps_any and lbvh_region_overlaps_large, whatever buffers they are given, since they use the same ray scratch; then every state is scanned again.  The one exception among the query calls:
  * lbvh_sort_hit_segments and lbvh_sort_index_segments take no context scratch and keep the live-path list (they drop it only when the
  * buffer they sort is d_hits itself).  What the library
  * cannot see is a write of the CALLER's own (a kernel or hipMemcpy that revives or ends paths, Russian roulette): between two

@@ -3015,6 +3015,197 @@ __global__ __launch_bounds__(64) void capsule_contact_wide_kernel(const lbvh_cap
     if (STATS) add_ray_stats(stats, n_shapes, n_steps, n_tris);
 }
 
+// ---- segment queries: the nearest triangle of a segment / anything within a distance (lbvh_segment_closest_point, -----------
+// lbvh_segment_within_distance, include/lbvh.h).  The frame and the nearest-first order of point_query_wide_kernel, with the box
+// distance taken on bounds grown by the segment's axis; the narrow phase is steps 1 - 3 of capsule_contact_of.
+
+// The header's distance of the segment [o, o + h] (`seg`: the origin, h in the direction; the inverse is not read) from the
+// triangle line (a, e1, e2), with s, (u, v) and whether the pierce gave it (dist2 = +0 then, and the caller's delta is 0).  The
+// rolled loop of capsule_contact_of without `within`, R2 and step 4: j = 0 .. 7 the derived triangles at o, j = 8 the scene
+// triangle at x = o + h*s.  A pierced pair enters at j = 8 — the eight distances decide nothing for it —, and the ninth test is
+// left out when no d_j was below +inf: which = 0 and s = 0 then, x is o, and its dist2 is d_0, which was not: NaN is returned.
+__device__ __forceinline__ float segment_triangle2(const ray_t& seg, const float4 a, const float4 e1, const float4 e2, float& u_out,
+                                                   float& v_out, float& s_out, bool& pierced_out)
+{
+    float pu = 0.0f, pv = 0.0f;
+    const float tp = ray_triangle_edges(seg, a, e1.x, e1.y, e1.z, e2.x, e2.y, e2.z, pu, pv);
+    const bool pierced = 0.0f <= tp && tp <= 1.0f;
+    float least = __builtin_inff(), least_v = 0.0f;
+    uint32_t which = 0u;
+    float s = 0.0f, dist2 = __builtin_nanf(""), u = 0.0f, v = 0.0f;
+#pragma nounroll
+    for (uint32_t j = pierced ? 8u : 0u; j < 9u && (j < 8u || pierced || least < __builtin_inff()); j++) {
+        const bool last = j == 8u;
+        // s as lbvh_capsule_cast derives it from the winning j: 0, 1, v' or 1 - v'; t_p for the pierce (read at j = 8 only)
+        s = pierced ? tp : (which == 0u ? 0.0f : (which == 1u ? 1.0f : ((which & 1u) ? 1.0f - least_v : least_v)));
+        float4 p, q1, q2;
+        capsule_triangle(last ? 0u : j, a, e1, e2, seg.dx, seg.dy, seg.dz, p, q1, q2);
+        const float px = last ? seg.ox + seg.dx * s : seg.ox, py = last ? seg.oy + seg.dy * s : seg.oy, pz = last ? seg.oz + seg.dz * s : seg.oz;
+        float uj, vj;
+        const float d = point_triangle2(px, py, pz, p, q1, q2, uj, vj);
+        if (last) { dist2 = d; u = uj; v = vj; }
+        else if (d < least) { least = d; which = j; least_v = vj; }        // strictly less; false for a NaN
+    }
+    u_out = u; v_out = v; s_out = s;
+    pierced_out = pierced;
+    return pierced ? 0.0f : dist2;
+}
+
+// query k into the lane (best = R; the axis into seg's direction): false (none-record / 0 written, lane stays idle) for an inactive query
+template <bool ANY>
+__device__ __forceinline__ bool load_segment_query(const lbvh_segment_query* __restrict__ queries, uint32_t k, ray_t& seg, float& best,
+                                                   std::conditional_t<ANY, uint32_t, lbvh_segment_closest>* __restrict__ out)
+{
+    const float inf = __builtin_inff();
+    const float4 q0 = reinterpret_cast<const float4*>(queries)[2 * (size_t)k], q1 = reinterpret_cast<const float4*>(queries)[2 * (size_t)k + 1];
+    seg.ox = q0.x; seg.oy = q0.y; seg.oz = q0.z;
+    seg.dx = q1.x; seg.dy = q1.y; seg.dz = q1.z;
+    best = fminf(q0.w, LBVH_MAX_FLOAT);
+    if (q0.w > 0.0f && (q0.x == q0.x && q0.y == q0.y && q0.z == q0.z) && fabsf(q1.x) < inf && fabsf(q1.y) < inf && fabsf(q1.z) < inf)
+        return true;                                                              // false for a NaN radius too
+    if constexpr (ANY) out[k] = 0u;
+    else {
+        reinterpret_cast<float4*>(out)[2 * (size_t)k] = make_float4(LBVH_MAX_FLOAT, __uint_as_float(0u), 0.0f, 0.0f);
+        reinterpret_cast<float4*>(out)[2 * (size_t)k + 1] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    }
+    return false;
+}
+
+// One segment per lane over the four-wide nodes: point_query_wide_kernel with every box grown by the lane's axis before its
+// distance from the origin is taken — lo - max(h, 0), hi - min(h, 0), one operation per bound, the max and min once per query —
+// and segment_triangle2 at a leaf slot.  The grown bounds are monotone in lo and hi, so box2g grows from a box to any box inside
+// it as box2 does, a subtree skipped because box2g > best holds no candidate at or below best, and the record does not depend on
+// the order of the walk.  The closest form keeps {best, tri, u, v, delta, s} in registers and writes two 16-byte stores when the
+// lane's walk ends.  ANY: a flag, the walk cut off at its first candidate (best stays R).
+template <bool ANY, bool STATS>
+__global__ __launch_bounds__(64) void segment_query_wide_kernel(const lbvh_segment_query* __restrict__ queries, uint32_t total,
+                                                                const lbvh_wide_node* __restrict__ wide,
+                                                                const lbvh_fast_node* __restrict__ lines,
+                                                                std::conditional_t<ANY, uint32_t, lbvh_segment_closest>* __restrict__ out,
+                                                                uint32_t* __restrict__ deep,     // [gridDim.x][kWideStackDeep][64]
+                                                                uint32_t lds_depth,              // <= kWideStackLds
+                                                                uint32_t deep_cap,               // <= kWideStackDeep
+                                                                uint32_t* __restrict__ fault, lbvh_ray_stats* stats)
+{
+    __shared__ uint32_t s_stack[kWideStackLds][LBVH_WAVE];
+    uint32_t* my_deep = deep + (size_t)blockIdx.x * (kWideStackDeep * LBVH_WAVE) + threadIdx.x;
+    const uint32_t lane = threadIdx.x;
+    const uint32_t run = max((total + gridDim.x - 1) / gridDim.x, 32u);
+    uint32_t next = blockIdx.x * run;
+    if (next >= total) return;
+    const uint32_t end = min(next + run, total);
+    uint32_t n_queries = 0, n_steps = 0, n_tris = 0;
+
+    bool active = false, took = false;
+    uint32_t i = 0;
+    ray_t seg = {};                                      // the origin and, as the direction, the axis (the inverse is not read)
+    float ux = 0.0f, uy = 0.0f, uz = 0.0f, vx = 0.0f, vy = 0.0f, vz = 0.0f;      // max(h, 0) and min(h, 0) per axis
+    float best = LBVH_MAX_FLOAT, best_u = 0.0f, best_v = 0.0f, best_s = 0.0f, best_dx = 0.0f, best_dy = 0.0f, best_dz = 0.0f;
+    uint32_t best_tri = 0, sp = 0, node = 0;
+    auto push = [&](uint32_t ref) {
+        if (sp < lds_depth) { s_stack[sp][lane] = ref; sp++; }
+        else if (sp < lds_depth + deep_cap) { my_deep[(sp - lds_depth) * LBVH_WAVE] = ref; sp++; }
+        // a dropped entry would be a silently wrong record: report it, as the ray walkers do (lbvh_debug_ray_stack_limit provokes it)
+        else __hip_atomic_store(fault, LBVH_FAULT_RAY_STACK, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    };
+    for (;;) {
+        const uint64_t idle = __ballot(!active);
+        if (idle != 0 && next < end) {
+            if (!active) {
+                const uint32_t k = next + mbcnt64(idle);
+                if (k < end) {
+                    i = k;
+                    active = load_segment_query<ANY>(queries, k, seg, best, out);
+                    ux = fmaxf(seg.dx, 0.0f); uy = fmaxf(seg.dy, 0.0f); uz = fmaxf(seg.dz, 0.0f);
+                    vx = fminf(seg.dx, 0.0f); vy = fminf(seg.dy, 0.0f); vz = fminf(seg.dz, 0.0f);
+                    best_tri = 0; best_u = 0.0f; best_v = 0.0f; best_s = 0.0f; best_dx = 0.0f; best_dy = 0.0f; best_dz = 0.0f; took = false;
+                    sp = 0; node = 0;
+                    if (STATS && active) n_queries++;
+                }
+            }
+            next += (uint32_t)__popcll(idle);
+        }
+        if (!__any(active) && next >= end) break;
+        if (active) {
+            if (STATS) n_steps++;
+            const float4* w = reinterpret_cast<const float4*>(&wide[node]);
+            const float4 lox = w[0], loy = w[1], loz = w[2], hix = w[3], hiy = w[4], hiz = w[5];
+            const uint4 ref = reinterpret_cast<const uint4*>(w)[6];
+#define GROWN_BOX2(c) point_box2(lox.c - ux, loy.c - uy, loz.c - uz, hix.c - vx, hiy.c - vy, hiz.c - vz, seg.ox, seg.oy, seg.oz)
+            const float b0 = GROWN_BOX2(x), b1 = GROWN_BOX2(y), b2 = GROWN_BOX2(z), b3 = GROWN_BOX2(w);
+#undef GROWN_BOX2
+            const bool h0 = !(b0 > best) && ref.x != kWideEmpty, h1 = !(b1 > best) && ref.y != kWideEmpty;
+            const bool h2 = !(b2 > best) && ref.z != kWideEmpty, h3 = !(b3 > best) && ref.w != kWideEmpty;
+            // leaf slots first: a lane's leaves one after the other, every lane's k-th at the same time
+            uint32_t leaves = (h0 && (ref.x >> 31) ? 1u : 0u) | (h1 && (ref.y >> 31) ? 2u : 0u) | (h2 && (ref.z >> 31) ? 4u : 0u) |
+                              (h3 && (ref.w >> 31) ? 8u : 0u);
+            bool found = false;                          // ANY: a candidate was accepted
+            while (leaves != 0u) {
+                const uint32_t k = (uint32_t)__builtin_ctz(leaves);
+                leaves &= leaves - 1u;
+                if (STATS) n_tris++;
+                float4 v0, v1, v2;
+                unpack_fast_triangle(reinterpret_cast<const float4*>(&lines[pick4(ref, k) & 0x7FFFFFFFu]), v0, v1, v2);
+                float u = 0.0f, v = 0.0f, s = 0.0f;
+                bool pierced = false;
+                const float dist2 = segment_triangle2(seg, v0, v1, v2, u, v, s, pierced);
+                const uint32_t tri = __float_as_uint(v0.w);
+                const float own = k == 0u ? b0 : (k == 1u ? b1 : (k == 2u ? b2 : b3));
+                // best starts at R and best_tri at 0: dist2 == R is never taken.  Ties go to the lower triangle index.
+                if (!(dist2 < own) && (dist2 < best || (dist2 == best && tri < best_tri))) {
+                    if constexpr (ANY) { found = true; break; }
+                    else {
+                        best = dist2; best_tri = tri; best_u = u; best_v = v; best_s = s; took = true;
+                        // delta: the residual of point_triangle2 at x, from the nearest point of the triangle to x; 0 where pierced
+                        const float apx = (seg.ox + seg.dx * s) - v0.x, apy = (seg.oy + seg.dy * s) - v0.y, apz = (seg.oz + seg.dz * s) - v0.z;
+                        best_dx = pierced ? 0.0f : apx - (v1.x * u + v2.x * v);
+                        best_dy = pierced ? 0.0f : apy - (v1.y * u + v2.y * v);
+                        best_dz = pierced ? 0.0f : apz - (v1.z * u + v2.z * v);
+                    }
+                }
+            }
+            if (ANY && found) {
+                if constexpr (ANY) out[i] = 1u;
+                active = false;
+                continue;
+            }
+            // nodes to enter, ordered by box distance as in point_query_wide_kernel: the distance's bit pattern with the slot number
+            // in its two lowest bits; compared with `best` once more, which may have shrunk in the leaf loop
+            constexpr uint32_t none = 0xFFFFFFFFu;
+            uint32_t k0 = h0 && !(ref.x >> 31) && !(b0 > best) ? ((__float_as_uint(b0) & ~3u) | 0u) : none;
+            uint32_t k1 = h1 && !(ref.y >> 31) && !(b1 > best) ? ((__float_as_uint(b1) & ~3u) | 1u) : none;
+            uint32_t k2 = h2 && !(ref.z >> 31) && !(b2 > best) ? ((__float_as_uint(b2) & ~3u) | 2u) : none;
+            uint32_t k3 = h3 && !(ref.w >> 31) && !(b3 > best) ? ((__float_as_uint(b3) & ~3u) | 3u) : none;
+            {   // five compare-exchanges
+                uint32_t a, b;
+                a = min(k0, k1); b = max(k0, k1); k0 = a; k1 = b;
+                a = min(k2, k3); b = max(k2, k3); k2 = a; k3 = b;
+                a = min(k0, k2); b = max(k0, k2); k0 = a; k2 = b;
+                a = min(k1, k3); b = max(k1, k3); k1 = a; k3 = b;
+                a = min(k1, k2); b = max(k1, k2); k1 = a; k2 = b;
+            }
+            if (k0 != none) {
+                if (k3 != none) push(pick4(ref, k3 & 3u));       // farthest first: the nearest waiting sibling is popped first
+                if (k2 != none) push(pick4(ref, k2 & 3u));
+                if (k1 != none) push(pick4(ref, k1 & 3u));
+                node = pick4(ref, k0 & 3u);
+            } else if (sp != 0) {
+                sp--;
+                node = sp < lds_depth ? s_stack[sp][lane] : my_deep[(sp - lds_depth) * LBVH_WAVE];
+            } else {
+                if constexpr (ANY) out[i] = 0u;
+                else {
+                    float4* rec = reinterpret_cast<float4*>(out) + 2 * (size_t)i;
+                    rec[0] = make_float4(took ? best : LBVH_MAX_FLOAT, __uint_as_float(best_tri), best_u, best_v);
+                    rec[1] = make_float4(best_dx, best_dy, best_dz, best_s);
+                }
+                active = false;
+            }
+        }
+    }
+    if (STATS) add_ray_stats(stats, n_queries, n_steps, n_tris);
+}
+
 // ---- box contacts: how deep an oriented box is in each triangle it touches, and which way out (lbvh_obb_contacts, ------------
 // lbvh_obb_deepest, include/lbvh.h).  The frame and the slot test of shape_overlap_wide_kernel<kShapeObb>; the count walk of
 // lbvh_obb_contacts IS that kernel's kTriCount form.  The two forms are capsule_contact_wide_kernel's.
@@ -3968,6 +4159,7 @@ static lbvh_status launch_per_query(lbvh_context* ctx, const QUERY* d_queries, s
     LBVH_LAUNCH_STATS(ctx, ctx->ray_stats, (kernel<ANY, STATS>), dim3(w.waves), dim3(LBVH_WAVE), d_queries, (uint32_t)count, w.wn, \
                       ctx->fast_nodes, d_out, w.deep, w.lds, w.deep_cap, ctx->fault_dev, ctx->ray_stats)
     if constexpr (std::is_same_v<QUERY, lbvh_point_query>) PER_QUERY_WALK(point_query_wide_kernel);
+    else if constexpr (std::is_same_v<QUERY, lbvh_segment_query>) PER_QUERY_WALK(segment_query_wide_kernel);
     else if constexpr (std::is_same_v<QUERY, lbvh_sphere_ray>) PER_QUERY_WALK(sphere_cast_wide_kernel);
     else if constexpr (std::is_same_v<QUERY, lbvh_capsule_ray>) PER_QUERY_WALK(capsule_cast_wide_kernel);
     else if constexpr (std::is_same_v<QUERY, lbvh_capsule>)          // lbvh_capsule_deepest: the contact walk's one-record form
@@ -3988,6 +4180,19 @@ static lbvh_status launch_per_query(lbvh_context* ctx, const QUERY* d_queries, s
 template <bool ANY>
 static lbvh_status point_queries(lbvh_context* ctx, const lbvh_point_query* d_queries, size_t count, const lbvh_scene* h_scene,
                                  std::conditional_t<ANY, uint32_t, lbvh_closest_point>* d_out, const char* who)
+{
+    if (!ctx) return LBVH_ERR_INVALID_ARG;
+    if (count == 0) return LBVH_OK;
+    LBVH_REQUIRE(ctx, d_queries != nullptr && h_scene != nullptr && d_out != nullptr);
+    LBVH_REQUIRE(ctx, ((uintptr_t)d_queries & 15) == 0 && ((uintptr_t)d_out & (ANY ? 3 : 15)) == 0);
+    LBVH_REQUIRE(ctx, count <= 0xFFFFFFFFull);
+    return launch_per_query<ANY>(ctx, d_queries, count, h_scene, d_out, who);
+}
+
+// lbvh_segment_closest_point / lbvh_segment_within_distance: the point queries' checks on 32-byte queries and records
+template <bool ANY>
+static lbvh_status segment_queries(lbvh_context* ctx, const lbvh_segment_query* d_queries, size_t count, const lbvh_scene* h_scene,
+                                   std::conditional_t<ANY, uint32_t, lbvh_segment_closest>* d_out, const char* who)
 {
     if (!ctx) return LBVH_ERR_INVALID_ARG;
     if (count == 0) return LBVH_OK;
@@ -4571,6 +4776,18 @@ lbvh_status lbvh_within_distance(lbvh_context* ctx, const lbvh_point_query* d_qu
                                  uint32_t* d_flags)
 {
     return point_queries<true>(ctx, d_queries, count, h_scene, d_flags, "lbvh_within_distance");
+}
+
+lbvh_status lbvh_segment_closest_point(lbvh_context* ctx, const lbvh_segment_query* d_queries, size_t count, const lbvh_scene* h_scene,
+                                       lbvh_segment_closest* d_out)
+{
+    return segment_queries<false>(ctx, d_queries, count, h_scene, d_out, "lbvh_segment_closest_point");
+}
+
+lbvh_status lbvh_segment_within_distance(lbvh_context* ctx, const lbvh_segment_query* d_queries, size_t count, const lbvh_scene* h_scene,
+                                         uint32_t* d_flags)
+{
+    return segment_queries<true>(ctx, d_queries, count, h_scene, d_flags, "lbvh_segment_within_distance");
 }
 
 // the four-wide walk only, one launch; the per-lane lists are dynamic LDS sized from k

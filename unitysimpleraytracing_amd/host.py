@@ -82,6 +82,15 @@ def capsule_shapes(origin, axis, radius):
     return out if out.ndim else out.reshape(1)
 
 
+def segment_queries(origins, axes, max_dist2=np.inf):
+    """layouts.SEGMENT_QUERY records for segment_closest_points / segment_within_distance: the segments origins .. origins + axes
+    (shapes (..., 3), broadcast against each other) with the given SQUARED search radii (+inf: unbounded), rounded to fp32 once."""
+    o, h = np.broadcast_arrays(np.asarray(origins, dtype=np.float32), np.asarray(axes, dtype=np.float32))
+    out = np.zeros(o.shape[:-1], dtype=L.SEGMENT_QUERY)
+    out["origin"], out["axis"], out["max_dist2"] = o, h, np.asarray(max_dist2, dtype=np.float32)
+    return out if out.ndim else out.reshape(1)
+
+
 def obb_shapes(centre, half_extents, rotation3x3=None):
     """layouts.OBB records for lbvh_obb_overlaps: boxes of the given half extents turned by rotation3x3 (COLUMNS = the box's axes in
     world space; None: AABBs) about `centre`, the half-axis vectors as obb_half_axes makes them.  Shapes (..., 3), (..., 3) and
@@ -788,6 +797,43 @@ class RaytracingMeshDrawer:
         with the greatest depth, ties to the lower triangle index; tri = layouts.NULL and zeros for a capsule that touches nothing.
         Asynchronous; read with out.get_data()."""
         self._per_query(N.lib.lbvh_capsule_deepest, shapes, "CAPSULE", out, L.CONTACT, "shapes")
+
+    def segment_closest_points(self, queries, out):
+        """Nearest triangle of each segment of the DataBuffer `queries` (layouts.SEGMENT_QUERY: origin, max_dist2, axis — the segment
+        from origin to origin + axis; see segment_queries) into the DataBuffer `out` (layouts.SEGMENT_CLOSEST: dist2, tri, the nearest
+        point (u, v) on the triangle, delta from it to the nearest point origin + axis*s of the segment), over the derived scene.  No
+        triangle nearer than sqrt(max_dist2): dist2 = layouts.MAX_FLOAT and zeros.  Asynchronous; read with out.get_data()."""
+        self._per_query(N.lib.lbvh_segment_closest_point, queries, "SEGMENT_QUERY", out, L.SEGMENT_CLOSEST, "queries")
+
+    def segment_within_distance(self, queries, flags):
+        """1 into the uint32 DataBuffer `flags` for each segment of `queries` with a triangle nearer than sqrt(max_dist2), else 0."""
+        self._per_query(N.lib.lbvh_segment_within_distance, queries, "SEGMENT_QUERY", flags, np.uint32, "queries")
+
+    def clearance(self, capsules):
+        """Convenience: how far each capsule of `capsules` (a host array or a DataBuffer of layouts.CAPSULE) is from the mesh, by an
+        unbounded segment_closest_points on its axis.  Returns (clearance, records): sqrt(dist2) - radius as a float32 host array
+        (negative: the capsule is that deep in the nearest triangle; +inf where no triangle was found) and the layouts.SEGMENT_CLOSEST
+        records.  Allocates, waits on the host; not part of the word-for-word contract of include/lbvh.h."""
+        shapes = capsules.get_data() if isinstance(capsules, DataBuffer) else np.asarray(capsules)
+        if shapes.dtype != L.CAPSULE:
+            raise ValueError("capsules must be an array or a DataBuffer of layouts.CAPSULE")
+        shapes = shapes.reshape(-1)
+        n = len(shapes)
+        queries = DataBuffer(self.ctx, max(n, 1), L.SEGMENT_QUERY)
+        out = DataBuffer(self.ctx, max(n, 1), L.SEGMENT_CLOSEST)
+        try:
+            queries.local[:n] = segment_queries(shapes["origin"], shapes["axis"], np.inf)
+            queries.local[n:]["max_dist2"] = 0                        # (the one spare query of an empty set is inactive)
+            queries.sync()
+            self.segment_closest_points(queries, out)
+            records = out.get_data()[:n].copy()
+        finally:
+            queries.dispose()
+            out.dispose()
+        found = records["dist2"] != L.MAX_FLOAT
+        with np.errstate(invalid="ignore"):
+            gap = np.where(found, np.sqrt(records["dist2"]) - shapes["radius"], np.float32(np.inf)).astype(np.float32)
+        return gap, records
 
     def obb_contacts(self, shapes, offsets, contacts=None):
         """The same for the oriented boxes of the DataBuffer `shapes` (layouts.OBB): obb_overlaps with a layouts.BOX_CONTACT record

@@ -89,6 +89,11 @@
 //                                                prints the total, how many segments are non-empty, how many capsules touch, the
 //                                                order-free sum of the records' words, the same of the deepest records weighted by
 //                                                shape, and the first deepest records as words
+//     lbvh_driver segclosest <n_segments> [seed] the same mesh and n_segments segments (SplitMix64, seed default 15): per segment and
+//                                                axis k the origin uniform in the mesh's box and the axis component uniform in [-6, 6];
+//                                                max_dist2 = 9 for the even ones, +inf for the odd ones.  SegmentClosestPoints and
+//                                                SegmentWithinDistance; prints how many have a record, how many flags are set, the sum
+//                                                of the records' words weighted by word and segment, and the first records as words
 //     lbvh_driver boxcontacts <n_shapes> [seed]  the same mesh and n_shapes sheared boxes (SplitMix64, seed default 13): per box and axis
 //                                                k the centre uniform in the mesh's box, then component k of ax, ay, az as `shapes`
 //                                                draws them.  ObbContacts (count only, one 8-byte read, fill) and ObbDeepest; prints
@@ -893,6 +898,59 @@ static int contacts_main(int argc, char** argv)
     return 0;
 }
 
+static int segclosest_main(int argc, char** argv)
+{
+    const size_t count = argc > 2 ? (size_t)strtoull(argv[2], nullptr, 10) : 65536;
+    uint64_t seed = argc > 3 ? strtoull(argv[3], nullptr, 10) : 15;
+    const std::vector<lbvh_triangle> mesh = random_mesh(4096);
+    float lo[3], hi[3];
+    mesh_box(mesh, lo, hi);
+    lbvh::Context ctx(0);
+    lbvh::RaytracingMeshDrawer drawer(ctx, mesh);
+    drawer.Awake();
+    lbvh::DataBuffer<lbvh_segment_query> queries(ctx, count);
+    for (size_t i = 0; i < count; i++) {
+        lbvh_segment_query& q = queries.LocalBuffer()[i];
+        std::memset(&q, 0, sizeof q);
+        q.max_dist2 = (i & 1) ? INFINITY : 9.0f;
+        for (int k = 0; k < 3; k++) {
+            q.origin[k] = uniform(seed, lo[k], hi[k]);
+            q.axis[k] = uniform(seed, -6.0f, 6.0f);
+        }
+    }
+    queries.Sync();
+    lbvh::DataBuffer<lbvh_segment_closest> closest(ctx, count);
+    lbvh::DataBuffer<uint32_t> within(ctx, count);
+    drawer.SegmentClosestPoints(queries, closest);
+    drawer.SegmentWithinDistance(queries, within);
+    closest.GetData();
+    within.GetData();
+    size_t found = 0, n_within = 0;
+    unsigned long long words = 0;
+    for (size_t i = 0; i < count; i++) {
+        uint32_t w[8];
+        std::memcpy(w, &closest.LocalBuffer()[i], sizeof w);
+        unsigned long long sum = 0;
+        for (int k = 0; k < 8; k++) sum += (unsigned long long)(k + 1) * w[k];
+        words += (unsigned long long)(i + 1) * sum;
+        found += closest.LocalBuffer()[i].dist2 != LBVH_MAX_FLOAT;
+        n_within += within.LocalBuffer()[i];
+    }
+    std::printf("{\"triangles\": %zu, \"segments\": %zu, \"found\": %zu, \"within\": %zu, \"word_sum\": %llu, \"closest\": [", mesh.size(), count,
+                found, n_within, words);
+    size_t shown = 0;
+    for (size_t i = 0; i < count && shown < 3; i++) {
+        if (closest.LocalBuffer()[i].dist2 == LBVH_MAX_FLOAT) continue;
+        uint32_t w[8];
+        std::memcpy(w, &closest.LocalBuffer()[i], sizeof w);
+        std::printf("%s[%zu", shown++ ? ", " : "", i);
+        for (int k = 0; k < 8; k++) std::printf(", %u", w[k]);
+        std::printf("]");
+    }
+    std::printf("]}\n");
+    return 0;
+}
+
 static int boxcontacts_main(int argc, char** argv)
 {
     const size_t count = argc > 2 ? (size_t)strtoull(argv[2], nullptr, 10) : 65536;
@@ -1342,7 +1400,7 @@ int main(int argc, char** argv)
 {
     static const struct { const char* name; int (*run)(int, char**); } commands[] = {
         {"crossings", crossings_main}, {"points", points_main}, {"knn", knn_main},   {"khits", khits_main}, {"gather", gather_main}, {"sortedhits", sortedhits_main},
-        {"sweep", sweep_main},         {"capsule", capsule_main}, {"boxcast", boxcast_main}, {"castall", castall_main},         {"overlaps", overlaps_main}, {"tris", tris_main}, {"trisegs", trisegs_main}, {"shapes", shapes_main}, {"contacts", contacts_main}, {"boxcontacts", boxcontacts_main}, {"regions", regions_main}, {"rays", rays_main}, {"sort", sort_main},   {"multi", multi_main}};
+        {"sweep", sweep_main},         {"capsule", capsule_main}, {"boxcast", boxcast_main}, {"castall", castall_main},         {"overlaps", overlaps_main}, {"tris", tris_main}, {"trisegs", trisegs_main}, {"shapes", shapes_main}, {"contacts", contacts_main}, {"boxcontacts", boxcontacts_main}, {"segclosest", segclosest_main}, {"regions", regions_main}, {"rays", rays_main}, {"sort", sort_main},   {"multi", multi_main}};
     try {
         for (const auto& c : commands)
             if (argc > 1 && std::strcmp(argv[1], c.name) == 0) return c.run(argc, argv);

@@ -534,6 +534,23 @@ public:
         check(ctx_.get(), lbvh_capsule_deepest(ctx_.get(), (const lbvh_capsule*)shapes.DeviceBuffer(), shapes.Size(), &s,
                                                (lbvh_contact*)out.DeviceBuffer()));
     }
+    // segments of the caller's own (lbvh_segment_query: origin, max_dist2, axis) over the derived scene: the nearest triangle of each
+    // — {dist2, tri, u, v, delta, s}: a capsule's clearance is sqrt(dist2) - radius — or whether any lies within the radius, 1 / 0 per
+    // segment (lbvh_segment_closest_point / lbvh_segment_within_distance; asynchronous)
+    void SegmentClosestPoints(const DataBuffer<lbvh_segment_query>& queries, DataBuffer<lbvh_segment_closest>& out)
+    {
+        if (out.Size() < queries.Size()) throw Error(LBVH_ERR_INVALID_ARG, "SegmentClosestPoints: fewer records than queries");
+        const lbvh_scene s = container_->Scene();
+        check(ctx_.get(), lbvh_segment_closest_point(ctx_.get(), (const lbvh_segment_query*)queries.DeviceBuffer(), queries.Size(), &s,
+                                                     (lbvh_segment_closest*)out.DeviceBuffer()));
+    }
+    void SegmentWithinDistance(const DataBuffer<lbvh_segment_query>& queries, DataBuffer<uint32_t>& flags)
+    {
+        if (flags.Size() < queries.Size()) throw Error(LBVH_ERR_INVALID_ARG, "SegmentWithinDistance: fewer flags than queries");
+        const lbvh_scene s = container_->Scene();
+        check(ctx_.get(), lbvh_segment_within_distance(ctx_.get(), (const lbvh_segment_query*)queries.DeviceBuffer(), queries.Size(), &s,
+                                                       (uint32_t*)flags.DeviceBuffer()));
+    }
     // The same for oriented boxes: ObbOverlaps with a lbvh_box_contact record (depth, tri, the axis of the thirteen that gave it,
     // back, the unit push-out normal) in place of an index; or the deepest record per box (lbvh_obb_contacts / lbvh_obb_deepest)
     void ObbContacts(const DataBuffer<lbvh_obb>& shapes, DataBuffer<uint64_t>& offsets, DataBuffer<lbvh_box_contact>* contacts = nullptr)

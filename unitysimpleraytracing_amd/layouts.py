@@ -70,6 +70,13 @@ assert CAPSULE.itemsize == 32 and OBB.itemsize == 64
 # none-record of lbvh_capsule_deepest has tri = NULL below and zeros elsewhere
 CONTACT = np.dtype([("depth", "<f4"), ("tri", "<u4"), ("u", "<f4"), ("v", "<f4"), ("normal", "<f4", 3), ("s", "<f4")])
 assert CONTACT.itemsize == 32
+# lbvh_segment_closest_point / lbvh_segment_within_distance: the segment origin .. origin + axis with its squared search radius (CAPSULE
+# with the bound in place of the radius; active iff max_dist2 > 0), and the answer: dist2 of the segment from triangle `tri`, (u, v) the
+# nearest point on the triangle, delta from it to the nearest point of the segment, origin + axis*s; the none-record is
+# {MAX_FLOAT, 0, 0, 0, (0, 0, 0), 0}
+SEGMENT_QUERY = np.dtype([("origin", "<f4", 3), ("max_dist2", "<f4"), ("axis", "<f4", 3), ("_pad", "<u4")])
+SEGMENT_CLOSEST = np.dtype([("dist2", "<f4"), ("tri", "<u4"), ("u", "<f4"), ("v", "<f4"), ("delta", "<f4", 3), ("s", "<f4")])
+assert SEGMENT_QUERY.itemsize == 32 and SEGMENT_CLOSEST.itemsize == 32
 # lbvh_obb_contacts / lbvh_obb_deepest: one contact of an oriented box with a triangle — depth = the least push along normal that
 # separates them, axis the j of the box cast's thirteen axes that gave it (BOX_AXIS_START: none counted), back the push along
 # -normal on the same axis; the none-record of lbvh_obb_deepest has tri = NULL below and zeros elsewhere
