@@ -65,6 +65,14 @@ public static class LbvhNative
     public struct SegmentQuery { public float originX, originY, originZ, maxDist2; public float axisX, axisY, axisZ; public uint pad; }
     [StructLayout(LayoutKind.Sequential)]
     public struct SegmentClosest { public float dist2; public uint tri; public float u, v; public float deltaX, deltaY, deltaZ; public float s; }
+    // lbvh_tri_distance_query / lbvh_tri_closest (include/lbvh.h): a query triangle with `skip` and its squared search radius (active iff
+    // maxDist2 > 0 and all nine coordinates are finite), 48 bytes, and the answer, 32 bytes: dist2 from triangle tri (2139095040 = none),
+    // the edge test that gave it (0 .. 2 the query's edges, 3 .. 5 the scene triangle's; | 8: it pierces), s on that edge, delta from the
+    // scene triangle's nearest point to the query's (TriangleDistance.cs)
+    [StructLayout(LayoutKind.Sequential)]
+    public struct TriDistanceQuery { public float ax, ay, az; public uint skip; public float bx, by, bz; public float maxDist2; public float cx, cy, cz; public uint pad; }
+    [StructLayout(LayoutKind.Sequential)]
+    public struct TriClosest { public float dist2; public uint tri; public uint edge; public float s; public float deltaX, deltaY, deltaZ; public uint zero; }
     // lbvh_box_contact (include/lbvh.h): one contact of an oriented box with a triangle, 32 bytes: depth = the least push along the
     // unit normal that separates them, axis = which of the box cast's thirteen axes gave it (13: none counted), back = the push
     // along -normal on the same axis; tri = 0xFFFFFFFF in the none-record of lbvh_obb_deepest (ShapeContacts.cs)
@@ -213,6 +221,8 @@ public static class LbvhNative
     [DllImport(Lib)] public static extern int lbvh_capsule_deepest(IntPtr ctx, IntPtr dShapes, UIntPtr count, ref Scene scene, IntPtr dOut);
     [DllImport(Lib)] public static extern int lbvh_segment_closest_point(IntPtr ctx, IntPtr dQueries, UIntPtr count, ref Scene scene, IntPtr dOut);
     [DllImport(Lib)] public static extern int lbvh_segment_within_distance(IntPtr ctx, IntPtr dQueries, UIntPtr count, ref Scene scene, IntPtr dFlags);
+    [DllImport(Lib)] public static extern int lbvh_triangle_closest_point(IntPtr ctx, IntPtr dQueries, UIntPtr count, ref Scene scene, IntPtr dOut);
+    [DllImport(Lib)] public static extern int lbvh_triangle_within_distance(IntPtr ctx, IntPtr dQueries, UIntPtr count, ref Scene scene, IntPtr dFlags);
     [DllImport(Lib)] public static extern int lbvh_obb_contacts(IntPtr ctx, IntPtr dShapes, UIntPtr count, ref Scene scene, IntPtr dOffsets,
         IntPtr dContacts, ulong capacity);
     [DllImport(Lib)] public static extern int lbvh_obb_deepest(IntPtr ctx, IntPtr dShapes, UIntPtr count, ref Scene scene, IntPtr dOut);

@@ -1499,6 +1499,96 @@ lbvh_status lbvh_segment_closest_point(lbvh_context* ctx, const lbvh_segment_que
 lbvh_status lbvh_segment_within_distance(lbvh_context* ctx, const lbvh_segment_query* d_queries, size_t count, const lbvh_scene* h_scene,
                                          uint32_t* d_flags);
 
+/* A triangle distance query: 48 bytes, arrays 16-byte aligned: lbvh_tri_query with a search bound (lbvh_tri_query._pad0 stays
+ * "not read": that is why this is a struct of its own). */
+typedef struct lbvh_tri_distance_query {
+    float a[3]; uint32_t skip;       /* ORIGINAL index never a candidate; LBVH_NULL = none (as lbvh_tri_query) */
+    float b[3]; float max_dist2;     /* squared search radius; +inf or >= LBVH_MAX_FLOAT = unbounded */
+    float c[3]; uint32_t _pad;       /* not read */
+} lbvh_tri_distance_query;
+
+/* The answer to one: 32 bytes, arrays 16-byte aligned; written as two 16-byte stores. */
+typedef struct lbvh_tri_closest {
+    float    dist2;                /* squared distance of the two triangles; LBVH_MAX_FLOAT if none */
+    uint32_t tri;                  /* ORIGINAL triangle index; 0 if none */
+    uint32_t edge;                 /* m = 0..5: which edge test gave the record; | 8 when that edge pierces */
+    float    s;                    /* nearest point on that edge: P_m + D_m * s */
+    float    delta[3];             /* from the scene triangle's nearest point to the query's nearest point; 0 if pierced / none */
+    uint32_t _zero;                /* written as 0 */
+} lbvh_tri_closest;
+
+/* Triangle closest-point queries: HOW FAR is a triangle from the mesh, WHERE and IN WHICH DIRECTION (the minimum distance between
+ * two meshes: clearance and tolerance checks, assembly planning; proximity pairs for cloth and self-collision, a mesh against
+ * itself with `skip`; speculative contacts for mesh colliders inside a margin), as the nearest record per query triangle
+ * (lbvh_triangle_closest_point) or as one flag per query (lbvh_triangle_within_distance), over the derived traversal scene in its
+ * four-wide form by the walk of lbvh_segment_closest_point: one query per lane, the nearest child box first, boxes farther than
+ * the best distance so far skipped.  Three lbvh_segment_closest_point calls on the query's edges miss every case where a scene
+ * vertex or edge is nearest to the interior of the query's face (the usual case when the query is larger than the scene's
+ * triangles); rows of lbvh_closest_point_query samples miss features between samples; lbvh_box_overlaps with a padded box and a
+ * host narrow phase prunes nothing by distance.
+ *   Active query: all nine coordinates of a, b, c finite and max_dist2 > 0 (false for NaN).  a == b == c is allowed (by this
+ *   definition's arithmetic; see (d)).  An inactive query is never walked; it gets the none-record
+ *   {LBVH_MAX_FLOAT, 0, 0, 0, {0, 0, 0}, 0} (lbvh_triangle_closest_point) or 0 (lbvh_triangle_within_distance).
+ *   R = min(max_dist2, LBVH_MAX_FLOAT), as at the point queries.
+ *   Query box: Q.min_k = min(min(a_k, b_k), c_k), Q.max_k = max(max(a_k, b_k), c_k), exactly as lbvh_triangle_intersections forms
+ *   them: exact, not padded.
+ *   Distance of the query to one triangle (the line v0, e1, e2 of the derived scene), in strict fp32, every operation rounded on
+ *   its own: the distance between two triangles is zero if an edge of one pierces the other, else the least distance between an
+ *   edge of one and the other triangle.  Six edge tests, in the order and with the P, D of lbvh_triangle_intersections, every
+ *   difference and sum one fp32 operation per component:
+ *     m = 0, 1, 2: the query's edges (P, D) = (a, b - a), (b, c - b), (c, a - c) against the scene line (v0, e1, e2);
+ *     m = 3, 4, 5: the scene's edges (P, D) = (v0, e1), (v0, e2), (v0 + e1, e2 - e1) against the query's line (a, b - a, c - a).
+ *   Each test is the full per-pair distance of lbvh_segment_closest_point for the segment (o, h) = (P, D) against that line, its
+ *   steps 1 - 3 (pierce first — the very pierce of lbvh_triangle_intersections' test m —, else the nearest derived triangle picks
+ *   s, then the point test at x = P + D*s): it gives dist2_m, s_m, the residual rv_m (step 3's rv) and whether it pierced.
+ *   Pair result: start with least = +inf; in the order m = 0 .. 5, test m replaces the running result only when dist2_m < least,
+ *   strictly (false for a NaN).  The record takes dist2 = dist2_m, s = s_m, edge = m | (pierced ? 8 : 0), and delta = rv_m for
+ *   m < 3, -rv_m per component for m >= 3 (an fp32 sign flip: it may produce -0), (+0, +0, +0) where pierced: delta always points
+ *   from the scene triangle's nearest point to the query's nearest point.  With no dist2_m below +inf the pair's dist2 is +inf:
+ *   never a candidate.
+ *   Early exit: an implementation may stop at the first m with dist2_m == +0: nothing after it is strictly less.
+ *   Distance to a box B (box against box): per axis g_k = fmaxf(fmaxf(B.lo_k - Q.max_k, Q.min_k - B.hi_k), 0) and
+ *   box2q(B) = (gx*gx + gy*gy) + gz*gz.
+ *   Candidate: triangle i is a candidate for a query iff its ORIGINAL index != skip, dist2_i < R and
+ *   !(dist2_i < box2q(own AABB_i)), the own AABB being scene.triangle_aabb[i].
+ *   lbvh_triangle_closest_point: d_out[k] = {dist2, tri, edge, s, delta, 0} of query k's candidate with the least dist2 (compared as
+ *   fp32 values); on equal dist2 the lower original triangle index, whatever order the walk meets them in.  No candidate: the
+ *   none-record, never R.  Every one of the `count` records is written, as two 16-byte stores.
+ *   lbvh_triangle_within_distance: d_flags[k] = 1 if query k has any candidate, else 0.  The walk is the closest walk (same
+ *   nearest-first order) cut off at its first accepted candidate: never more node fetches or triangle tests per query.
+ * Why the record does not depend on the order of the walk (the argument at lbvh_segment_closest_point with box2q for box2g): box2q
+ * is monotone in B.lo and B.hi — fp32 subtraction, max, multiplication of non-negatives and addition are monotone — and every box
+ * of the derived tree, binary or four-wide, is the exact min / max union of what is below it; so
+ * box2q(ancestor) <= box2q(leaf) <= dist2 for every candidate.  A slot is skipped only if box2q > best, strictly: a subtree
+ * skipped that way holds no candidate at or below best.  Both triangles lie in their boxes, so box2q is a true lower bound of the
+ * distance in exact arithmetic; a dist2 below its own box's box2q is fp32 noise of the triangle arithmetic, which the accept rule
+ * removes (on ordinary meshes it rejects nothing).
+ * Relations (tests/test_triangle_closest.py holds each):
+ *   (a) the flag is 1 exactly when the record's dist2 != LBVH_MAX_FLOAT.
+ *   (b) if lbvh_triangle_intersections lists any triangle for {a, b, c, skip}, the record has dist2 == +0, edge & 8 set and
+ *       tri <= the least listed index: the pierce tests are the same six calls, and overlapping boxes have box2q = 0.
+ *   (c) with skip = LBVH_NULL, for m = 0, 1, 2 the record's dist2 is <= the dist2 of lbvh_segment_closest_point on edge m
+ *       ({P_m, max_dist2, D_m}) wherever the accept rule rejected nothing for that query; where the record has edge == m < 3 and the
+ *       same tri as that segment record, dist2, s and delta are equal word for word.
+ *   (d) NOT promised: that a degenerate query (a == b == c) equals lbvh_closest_point_query at a.  Tests m >= 3 run the point
+ *       test against a degenerate triangle (a, 0, 0) and may give another rounding of the same distance.
+ * Both need the derived traversal scene (lbvh_build_fast_scene; a stale one is LBVH_ERR_INVALID_ARG), are asynchronous on the
+ * context's stream with no host wait, and use the context's ray scratch: they drop the path tracer's live-path list (see
+ * lbvh_path_bounce).  count == 0 is a no-op.  Rejected: NULL pointers, d_queries or d_out not 16-byte aligned, d_flags not 4-byte
+ * aligned, count > 2^32 - 1.  Four-wide walk only (lbvh_debug_ray_walker does not apply); lbvh_debug_ray_waves,
+ * lbvh_debug_ray_stack_split, lbvh_debug_ray_stack_limit and lbvh_ray_stats_target apply as to the segment queries (`rays` =
+ * active queries; triangle_tests counts the triangle lines read and tested, whatever number of edge tests each takes; a line whose
+ * index is `skip` is not counted, as at lbvh_triangle_intersections).
+ * Cost: up to six segment tests (54 point tests) per triangle line read: several times lbvh_segment_closest_point's narrow phase on
+ * boxes grown by the whole query.  Pass active queries only where time matters, and a search radius where one is known.
+ * Out of scope: the k nearest triangles of a triangle; a gather of every triangle within the distance; a two-tree (mesh-BVH against
+ * mesh-BVH) descent; exact coplanar-overlap handling beyond what the arithmetic gives; oriented-box distance; a unit
+ * normal in the record (delta / sqrtf(dist2) where dist2 > 0; the caller's square root). */
+lbvh_status lbvh_triangle_closest_point(lbvh_context* ctx, const lbvh_tri_distance_query* d_queries, size_t count, const lbvh_scene* h_scene,
+                                        lbvh_tri_closest* d_out);
+lbvh_status lbvh_triangle_within_distance(lbvh_context* ctx, const lbvh_tri_distance_query* d_queries, size_t count, const lbvh_scene* h_scene,
+                                          uint32_t* d_flags);
+
 /* One contact of an oriented box with a triangle: 32 bytes, arrays 16-byte aligned; written as two 16-byte stores. */
 typedef struct lbvh_box_contact {
     float    depth;                /* least push, along normal, that separates the box from the triangle; >= 0 */
@@ -1698,7 +1788,7 @@ lbvh_status lbvh_path_scatter(lbvh_context* ctx, const lbvh_scene* h_scene, cons
  * lbvh_path_bounce on the same d_states / d_hits listed as live (a list kept by the context).  Every library call that writes
  * into those buffers drops the list (lbvh_path_begin, lbvh_trace_rays, a primary trace into any part of d_hits,
  * lbvh_buffer_upload / _fill_u32 / _free), and so does lbvh_trace_forget — and so do lbvh_trace_closest,
- * lbvh_trace_occluded, lbvh_closest_point_query, lbvh_within_distance, lbvh_count_hits, lbvh_point_crossings, lbvh_box_overlaps, lbvh_gather_within_distance, lbvh_k_closest_points, lbvh_trace_k_closest, lbvh_gather_hits, lbvh_sphere_cast, lbvh_sphere_cast_any, lbvh_capsule_cast, lbvh_capsule_cast_any, lbvh_box_cast, lbvh_box_cast_any, lbvh_triangle_intersections, lbvh_triangle_intersects_any, lbvh_triangle_intersection_segments, lbvh_capsule_overlaps, lbvh_capsule_overlaps_any, lbvh_obb_overlaps, lbvh_obb_overlaps_any, lbvh_capsule_contacts, lbvh_capsule_deepest, lbvh_obb_contacts, lbvh_obb_deepest, lbvh_segment_closest_point, lbvh_segment_within_distance, lbvh_sphere_cast_all, lbvh_capsule_cast_all, lbvh_box_cast_all, lbvh_region_overlaps, lbvh_region_overlaps_any and lbvh_region_overlaps_large, whatever buffers they are given, since they use the same ray scratch; then every state is scanned again.  The one exception among the query calls:
+ * lbvh_trace_occluded, lbvh_closest_point_query, lbvh_within_distance, lbvh_count_hits, lbvh_point_crossings, lbvh_box_overlaps, lbvh_gather_within_distance, lbvh_k_closest_points, lbvh_trace_k_closest, lbvh_gather_hits, lbvh_sphere_cast, lbvh_sphere_cast_any, lbvh_capsule_cast, lbvh_capsule_cast_any, lbvh_box_cast, lbvh_box_cast_any, lbvh_triangle_intersections, lbvh_triangle_intersects_any, lbvh_triangle_intersection_segments, lbvh_capsule_overlaps, lbvh_capsule_overlaps_any, lbvh_obb_overlaps, lbvh_obb_overlaps_any, lbvh_capsule_contacts, lbvh_capsule_deepest, lbvh_obb_contacts, lbvh_obb_deepest, lbvh_segment_closest_point, lbvh_segment_within_distance, lbvh_triangle_closest_point, lbvh_triangle_within_distance, lbvh_sphere_cast_all, lbvh_capsule_cast_all, lbvh_box_cast_all, lbvh_region_overlaps, lbvh_region_overlaps_any and lbvh_region_overlaps_large, whatever buffers they are given, since they use the same ray scratch; then every state is scanned again.  The one exception among the query calls:
  * lbvh_sort_hit_segments and lbvh_sort_index_segments take no context scratch and keep the live-path list (they drop it only when the
  * buffer they sort is d_hits itself).  What the library
  * cannot see is a write of the CALLER's own (a kernel or hipMemcpy that revives or ends paths, Russian roulette): between two

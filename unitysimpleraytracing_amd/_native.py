@@ -120,6 +120,8 @@ SIGNATURES = {
     "lbvh_capsule_deepest": (_I32, [_P, _P, _SZ, C.POINTER(Scene), _P]),
     "lbvh_segment_closest_point": (_I32, [_P, _P, _SZ, C.POINTER(Scene), _P]),
     "lbvh_segment_within_distance": (_I32, [_P, _P, _SZ, C.POINTER(Scene), _P]),
+    "lbvh_triangle_closest_point": (_I32, [_P, _P, _SZ, C.POINTER(Scene), _P]),
+    "lbvh_triangle_within_distance": (_I32, [_P, _P, _SZ, C.POINTER(Scene), _P]),
     "lbvh_obb_overlaps": (_I32, [_P, _P, _SZ, C.POINTER(Scene), _P, _P, C.c_uint64]),
     "lbvh_obb_overlaps_any": (_I32, [_P, _P, _SZ, C.POINTER(Scene), _P]),
     "lbvh_obb_contacts": (_I32, [_P, _P, _SZ, C.POINTER(Scene), _P, _P, C.c_uint64]),

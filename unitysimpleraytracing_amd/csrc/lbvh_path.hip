@@ -3206,6 +3206,240 @@ __global__ __launch_bounds__(64) void segment_query_wide_kernel(const lbvh_segme
     if (STATS) add_ray_stats(stats, n_queries, n_steps, n_tris);
 }
 
+// ---- triangle distance queries: the nearest triangle of a triangle / anything within a distance (lbvh_triangle_closest_point, --
+// lbvh_triangle_within_distance, include/lbvh.h).  The frame and the nearest-first order of segment_query_wide_kernel with the
+// box-against-box distance for the slot test; the narrow phase is six calls of segment_triangle2 with the operands of
+// triangles_pierce.
+
+// Edge test m of the header for the query (a, b, c) and the scene line (t0, t1, t2): the segment (P, D) into `seg` and the other
+// triangle's line into (v, f1, f2) — triangles_pierce's operands, every difference and sum the one fp32 operation of the header.
+__device__ __forceinline__ void triangle_edge_test(uint32_t m, float ax, float ay, float az, float bx, float by, float bz, float cx, float cy,
+                                                   float cz, const float4 t0, const float4 t1, const float4 t2, ray_t& seg, float4& v,
+                                                   float4& f1, float4& f2)
+{
+    float px, py, pz, dx, dy, dz;
+    if (m == 0u) { px = ax; py = ay; pz = az; dx = bx - ax; dy = by - ay; dz = bz - az; }
+    else if (m == 1u) { px = bx; py = by; pz = bz; dx = cx - bx; dy = cy - by; dz = cz - bz; }
+    else if (m == 2u) { px = cx; py = cy; pz = cz; dx = ax - cx; dy = ay - cy; dz = az - cz; }
+    else if (m == 3u) { px = t0.x; py = t0.y; pz = t0.z; dx = t1.x; dy = t1.y; dz = t1.z; }
+    else if (m == 4u) { px = t0.x; py = t0.y; pz = t0.z; dx = t2.x; dy = t2.y; dz = t2.z; }
+    else { px = t0.x + t1.x; py = t0.y + t1.y; pz = t0.z + t1.z; dx = t2.x - t1.x; dy = t2.y - t1.y; dz = t2.z - t1.z; }
+    seg.ox = px; seg.oy = py; seg.oz = pz;
+    seg.dx = dx; seg.dy = dy; seg.dz = dz;
+    seg.ix = 0.0f; seg.iy = 0.0f; seg.iz = 0.0f;         // (not read)
+    const bool query_edge = m < 3u;
+    v = query_edge ? t0 : make_float4(ax, ay, az, 0.0f);
+    f1 = query_edge ? t1 : make_float4(bx - ax, by - ay, bz - az, 0.0f);
+    f2 = query_edge ? t2 : make_float4(cx - ax, cy - ay, cz - az, 0.0f);
+}
+
+// The header's distance of the query triangle from the scene line: the least dist2_m in the order m = 0 .. 5, strictly less, with
+// edge = m | (pierced ? 8 : 0), s and the (u, v) of that test's step 3 (what delta is formed from when the pair is taken).  ONE
+// copy of segment_triangle2 in a loop that is not unrolled (six inlined copies of its nine-test loop would be six times the code
+// and the registers of the widest); the loop ends at the first dist2_m == +0: nothing after it is strictly less.  +inf when no
+// test gave a number.
+__device__ __forceinline__ float triangle_triangle2(float ax, float ay, float az, float bx, float by, float bz, float cx, float cy, float cz,
+                                                    const float4 t0, const float4 t1, const float4 t2, uint32_t& edge_out, float& s_out,
+                                                    float& u_out, float& v_out)
+{
+    float least = __builtin_inff(), s = 0.0f, u = 0.0f, v = 0.0f;
+    uint32_t edge = 0u;
+#pragma nounroll
+    for (uint32_t m = 0; m < 6u && !(least == 0.0f); m++) {
+        ray_t seg;
+        float4 p, f1, f2;
+        triangle_edge_test(m, ax, ay, az, bx, by, bz, cx, cy, cz, t0, t1, t2, seg, p, f1, f2);
+        float um = 0.0f, vm = 0.0f, sm = 0.0f;
+        bool pierced = false;
+        const float d = segment_triangle2(seg, p, f1, f2, um, vm, sm, pierced);
+        if (d < least) { least = d; edge = m | (pierced ? 8u : 0u); s = sm; u = um; v = vm; }     // strictly less; false for a NaN
+    }
+    edge_out = edge; s_out = s; u_out = u; v_out = v;
+    return least;
+}
+
+// query k into the lane (best = R): false (none-record / 0 written, lane stays idle) for an inactive query
+template <bool ANY>
+__device__ __forceinline__ bool load_tri_distance_query(const lbvh_tri_distance_query* __restrict__ queries, uint32_t k, float4& qa, float4& qb,
+                                                        float4& qc, float& best,
+                                                        std::conditional_t<ANY, uint32_t, lbvh_tri_closest>* __restrict__ out)
+{
+    const float inf = __builtin_inff();
+    qa = reinterpret_cast<const float4*>(queries)[3 * (size_t)k];
+    qb = reinterpret_cast<const float4*>(queries)[3 * (size_t)k + 1];
+    qc = reinterpret_cast<const float4*>(queries)[3 * (size_t)k + 2];
+    best = fminf(qb.w, LBVH_MAX_FLOAT);
+    if (qb.w > 0.0f && fabsf(qa.x) < inf && fabsf(qa.y) < inf && fabsf(qa.z) < inf && fabsf(qb.x) < inf && fabsf(qb.y) < inf &&
+        fabsf(qb.z) < inf && fabsf(qc.x) < inf && fabsf(qc.y) < inf && fabsf(qc.z) < inf)
+        return true;                                                              // false for a NaN radius or coordinate
+    if constexpr (ANY) out[k] = 0u;
+    else {
+        reinterpret_cast<float4*>(out)[2 * (size_t)k] = make_float4(LBVH_MAX_FLOAT, __uint_as_float(0u), __uint_as_float(0u), 0.0f);
+        reinterpret_cast<float4*>(out)[2 * (size_t)k + 1] = make_float4(0.0f, 0.0f, 0.0f, __uint_as_float(0u));
+    }
+    return false;
+}
+
+// box2q of the header: the squared distance of the box (lx .. hz) from the query's box (qlx .. qhz), point_box2 with an interval
+// in the point's place
+__device__ __forceinline__ float box_box2(float lx, float ly, float lz, float hx, float hy, float hz, float qlx, float qly, float qlz,
+                                          float qhx, float qhy, float qhz)
+{
+    const float gx = fmaxf(fmaxf(lx - qhx, qlx - hx), 0.0f);
+    const float gy = fmaxf(fmaxf(ly - qhy, qly - hy), 0.0f);
+    const float gz = fmaxf(fmaxf(lz - qhz, qlz - hz), 0.0f);
+    return (gx * gx + gy * gy) + gz * gz;
+}
+
+// One query triangle per lane over the four-wide nodes: segment_query_wide_kernel with box2q in the place of the grown box's
+// distance — the query's box is taken once per query — and triangle_triangle2 at a leaf slot, after `skip`.  box2q is monotone in
+// the node box, so a subtree skipped because box2q > best holds no candidate at or below best, and the record does not depend on
+// the order of the walk.  The closest form keeps {best, tri, edge, s, delta} in registers, forms delta only for a pair it takes
+// (the operands of the winning m once more), and writes two 16-byte stores when the lane's walk ends.  ANY: a flag, the walk cut
+// off at its first candidate (best stays R); no delta.
+template <bool ANY, bool STATS>
+__global__ __launch_bounds__(64) void triangle_distance_wide_kernel(const lbvh_tri_distance_query* __restrict__ queries, uint32_t total,
+                                                                    const lbvh_wide_node* __restrict__ wide,
+                                                                    const lbvh_fast_node* __restrict__ lines,
+                                                                    std::conditional_t<ANY, uint32_t, lbvh_tri_closest>* __restrict__ out,
+                                                                    uint32_t* __restrict__ deep,     // [gridDim.x][kWideStackDeep][64]
+                                                                    uint32_t lds_depth,              // <= kWideStackLds
+                                                                    uint32_t deep_cap,               // <= kWideStackDeep
+                                                                    uint32_t* __restrict__ fault, lbvh_ray_stats* stats)
+{
+    __shared__ uint32_t s_stack[kWideStackLds][LBVH_WAVE];
+    uint32_t* my_deep = deep + (size_t)blockIdx.x * (kWideStackDeep * LBVH_WAVE) + threadIdx.x;
+    const uint32_t lane = threadIdx.x;
+    const uint32_t run = max((total + gridDim.x - 1) / gridDim.x, 32u);
+    uint32_t next = blockIdx.x * run;
+    if (next >= total) return;
+    const uint32_t end = min(next + run, total);
+    uint32_t n_queries = 0, n_steps = 0, n_tris = 0;
+
+    bool active = false, took = false;
+    uint32_t i = 0, skip = kWideEmpty;
+    float ax = 0.0f, ay = 0.0f, az = 0.0f, bx = 0.0f, by = 0.0f, bz = 0.0f, cx = 0.0f, cy = 0.0f, cz = 0.0f;
+    float lx = 0.0f, ly = 0.0f, lz = 0.0f, hx = 0.0f, hy = 0.0f, hz = 0.0f;      // the query's box
+    float best = LBVH_MAX_FLOAT, best_s = 0.0f, best_dx = 0.0f, best_dy = 0.0f, best_dz = 0.0f;
+    uint32_t best_tri = 0, best_edge = 0, sp = 0, node = 0;
+    auto push = [&](uint32_t ref) {
+        if (sp < lds_depth) { s_stack[sp][lane] = ref; sp++; }
+        else if (sp < lds_depth + deep_cap) { my_deep[(sp - lds_depth) * LBVH_WAVE] = ref; sp++; }
+        // a dropped entry would be a silently wrong record: report it, as the ray walkers do (lbvh_debug_ray_stack_limit provokes it)
+        else __hip_atomic_store(fault, LBVH_FAULT_RAY_STACK, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    };
+    for (;;) {
+        const uint64_t idle = __ballot(!active);
+        if (idle != 0 && next < end) {
+            if (!active) {
+                const uint32_t k = next + mbcnt64(idle);
+                if (k < end) {
+                    i = k;
+                    float4 qa, qb, qc;
+                    active = load_tri_distance_query<ANY>(queries, k, qa, qb, qc, best, out);
+                    ax = qa.x; ay = qa.y; az = qa.z; skip = __float_as_uint(qa.w);
+                    bx = qb.x; by = qb.y; bz = qb.z;
+                    cx = qc.x; cy = qc.y; cz = qc.z;
+                    lx = fminf(fminf(ax, bx), cx); ly = fminf(fminf(ay, by), cy); lz = fminf(fminf(az, bz), cz);
+                    hx = fmaxf(fmaxf(ax, bx), cx); hy = fmaxf(fmaxf(ay, by), cy); hz = fmaxf(fmaxf(az, bz), cz);
+                    best_tri = 0; best_edge = 0; best_s = 0.0f; best_dx = 0.0f; best_dy = 0.0f; best_dz = 0.0f; took = false;
+                    sp = 0; node = 0;
+                    if (STATS && active) n_queries++;
+                }
+            }
+            next += (uint32_t)__popcll(idle);
+        }
+        if (!__any(active) && next >= end) break;
+        if (active) {
+            if (STATS) n_steps++;
+            const float4* w = reinterpret_cast<const float4*>(&wide[node]);
+            const float4 lox = w[0], loy = w[1], loz = w[2], hix = w[3], hiy = w[4], hiz = w[5];
+            const uint4 ref = reinterpret_cast<const uint4*>(w)[6];
+#define BOX2Q(c) box_box2(lox.c, loy.c, loz.c, hix.c, hiy.c, hiz.c, lx, ly, lz, hx, hy, hz)
+            const float b0 = BOX2Q(x), b1 = BOX2Q(y), b2 = BOX2Q(z), b3 = BOX2Q(w);
+#undef BOX2Q
+            const bool h0 = !(b0 > best) && ref.x != kWideEmpty, h1 = !(b1 > best) && ref.y != kWideEmpty;
+            const bool h2 = !(b2 > best) && ref.z != kWideEmpty, h3 = !(b3 > best) && ref.w != kWideEmpty;
+            // leaf slots first: a lane's leaves one after the other, every lane's k-th at the same time
+            uint32_t leaves = (h0 && (ref.x >> 31) ? 1u : 0u) | (h1 && (ref.y >> 31) ? 2u : 0u) | (h2 && (ref.z >> 31) ? 4u : 0u) |
+                              (h3 && (ref.w >> 31) ? 8u : 0u);
+            bool found = false;                          // ANY: a candidate was accepted
+            while (leaves != 0u) {
+                const uint32_t k = (uint32_t)__builtin_ctz(leaves);
+                leaves &= leaves - 1u;
+                float4 v0, v1, v2;
+                unpack_fast_triangle(reinterpret_cast<const float4*>(&lines[pick4(ref, k) & 0x7FFFFFFFu]), v0, v1, v2);
+                const uint32_t tri = __float_as_uint(v0.w);
+                if (tri == skip) continue;
+                if (STATS) n_tris++;
+                uint32_t edge = 0u;
+                float s = 0.0f, u = 0.0f, v = 0.0f;
+                const float dist2 = triangle_triangle2(ax, ay, az, bx, by, bz, cx, cy, cz, v0, v1, v2, edge, s, u, v);
+                const float own = k == 0u ? b0 : (k == 1u ? b1 : (k == 2u ? b2 : b3));
+                // best starts at R and best_tri at 0: dist2 == R is never taken.  Ties go to the lower triangle index.
+                if (!(dist2 < own) && (dist2 < best || (dist2 == best && tri < best_tri))) {
+                    if constexpr (ANY) { found = true; break; }
+                    else {
+                        best = dist2; best_tri = tri; best_edge = edge; best_s = s; took = true;
+                        // delta: the residual of point_triangle2 at x = P + D*s of the winning test, turned round for a scene edge
+                        // (m >= 3) so that it points from the scene triangle to the query; 0 where pierced.  The three lines below must
+                        // stay operation for operation what segment_query_wide_kernel forms its delta with — x = o + h*s, ap = x - a,
+                        // rv = ap - (e1*u + e2*v), step 3 of the header, on the (u, v) segment_triangle2 returned —: relation (c)
+                        // promises the same words
+                        ray_t seg;
+                        float4 p, f1, f2;
+                        triangle_edge_test(edge & 7u, ax, ay, az, bx, by, bz, cx, cy, cz, v0, v1, v2, seg, p, f1, f2);
+                        const float apx = (seg.ox + seg.dx * s) - p.x, apy = (seg.oy + seg.dy * s) - p.y, apz = (seg.oz + seg.dz * s) - p.z;
+                        const float rx = apx - (f1.x * u + f2.x * v), ry = apy - (f1.y * u + f2.y * v), rz = apz - (f1.z * u + f2.z * v);
+                        const bool pierced = (edge & 8u) != 0u, turn = (edge & 7u) >= 3u;
+                        best_dx = pierced ? 0.0f : (turn ? -rx : rx);
+                        best_dy = pierced ? 0.0f : (turn ? -ry : ry);
+                        best_dz = pierced ? 0.0f : (turn ? -rz : rz);
+                    }
+                }
+            }
+            if (ANY && found) {
+                if constexpr (ANY) out[i] = 1u;
+                active = false;
+                continue;
+            }
+            // nodes to enter, ordered by box distance as in point_query_wide_kernel: the distance's bit pattern with the slot number
+            // in its two lowest bits; compared with `best` once more, which may have shrunk in the leaf loop
+            constexpr uint32_t none = 0xFFFFFFFFu;
+            uint32_t k0 = h0 && !(ref.x >> 31) && !(b0 > best) ? ((__float_as_uint(b0) & ~3u) | 0u) : none;
+            uint32_t k1 = h1 && !(ref.y >> 31) && !(b1 > best) ? ((__float_as_uint(b1) & ~3u) | 1u) : none;
+            uint32_t k2 = h2 && !(ref.z >> 31) && !(b2 > best) ? ((__float_as_uint(b2) & ~3u) | 2u) : none;
+            uint32_t k3 = h3 && !(ref.w >> 31) && !(b3 > best) ? ((__float_as_uint(b3) & ~3u) | 3u) : none;
+            {   // five compare-exchanges
+                uint32_t a, b;
+                a = min(k0, k1); b = max(k0, k1); k0 = a; k1 = b;
+                a = min(k2, k3); b = max(k2, k3); k2 = a; k3 = b;
+                a = min(k0, k2); b = max(k0, k2); k0 = a; k2 = b;
+                a = min(k1, k3); b = max(k1, k3); k1 = a; k3 = b;
+                a = min(k1, k2); b = max(k1, k2); k1 = a; k2 = b;
+            }
+            if (k0 != none) {
+                if (k3 != none) push(pick4(ref, k3 & 3u));       // farthest first: the nearest waiting sibling is popped first
+                if (k2 != none) push(pick4(ref, k2 & 3u));
+                if (k1 != none) push(pick4(ref, k1 & 3u));
+                node = pick4(ref, k0 & 3u);
+            } else if (sp != 0) {
+                sp--;
+                node = sp < lds_depth ? s_stack[sp][lane] : my_deep[(sp - lds_depth) * LBVH_WAVE];
+            } else {
+                if constexpr (ANY) out[i] = 0u;
+                else {
+                    float4* rec = reinterpret_cast<float4*>(out) + 2 * (size_t)i;
+                    rec[0] = make_float4(took ? best : LBVH_MAX_FLOAT, __uint_as_float(best_tri), __uint_as_float(best_edge), best_s);
+                    rec[1] = make_float4(best_dx, best_dy, best_dz, __uint_as_float(0u));
+                }
+                active = false;
+            }
+        }
+    }
+    if (STATS) add_ray_stats(stats, n_queries, n_steps, n_tris);
+}
+
 // ---- box contacts: how deep an oriented box is in each triangle it touches, and which way out (lbvh_obb_contacts, ------------
 // lbvh_obb_deepest, include/lbvh.h).  The frame and the slot test of shape_overlap_wide_kernel<kShapeObb>; the count walk of
 // lbvh_obb_contacts IS that kernel's kTriCount form.  The two forms are capsule_contact_wide_kernel's.
@@ -4160,6 +4394,7 @@ static lbvh_status launch_per_query(lbvh_context* ctx, const QUERY* d_queries, s
                       ctx->fast_nodes, d_out, w.deep, w.lds, w.deep_cap, ctx->fault_dev, ctx->ray_stats)
     if constexpr (std::is_same_v<QUERY, lbvh_point_query>) PER_QUERY_WALK(point_query_wide_kernel);
     else if constexpr (std::is_same_v<QUERY, lbvh_segment_query>) PER_QUERY_WALK(segment_query_wide_kernel);
+    else if constexpr (std::is_same_v<QUERY, lbvh_tri_distance_query>) PER_QUERY_WALK(triangle_distance_wide_kernel);
     else if constexpr (std::is_same_v<QUERY, lbvh_sphere_ray>) PER_QUERY_WALK(sphere_cast_wide_kernel);
     else if constexpr (std::is_same_v<QUERY, lbvh_capsule_ray>) PER_QUERY_WALK(capsule_cast_wide_kernel);
     else if constexpr (std::is_same_v<QUERY, lbvh_capsule>)          // lbvh_capsule_deepest: the contact walk's one-record form
@@ -4189,10 +4424,11 @@ static lbvh_status point_queries(lbvh_context* ctx, const lbvh_point_query* d_qu
     return launch_per_query<ANY>(ctx, d_queries, count, h_scene, d_out, who);
 }
 
-// lbvh_segment_closest_point / lbvh_segment_within_distance: the point queries' checks on 32-byte queries and records
-template <bool ANY>
-static lbvh_status segment_queries(lbvh_context* ctx, const lbvh_segment_query* d_queries, size_t count, const lbvh_scene* h_scene,
-                                   std::conditional_t<ANY, uint32_t, lbvh_segment_closest>* d_out, const char* who)
+// lbvh_segment_closest_point / lbvh_segment_within_distance and lbvh_triangle_closest_point / lbvh_triangle_within_distance: the
+// point queries' checks on 32- or 48-byte queries and 32-byte records
+template <bool ANY, class QUERY, class OUT>
+static lbvh_status distance_queries(lbvh_context* ctx, const QUERY* d_queries, size_t count, const lbvh_scene* h_scene, OUT* d_out,
+                                    const char* who)
 {
     if (!ctx) return LBVH_ERR_INVALID_ARG;
     if (count == 0) return LBVH_OK;
@@ -4781,13 +5017,25 @@ lbvh_status lbvh_within_distance(lbvh_context* ctx, const lbvh_point_query* d_qu
 lbvh_status lbvh_segment_closest_point(lbvh_context* ctx, const lbvh_segment_query* d_queries, size_t count, const lbvh_scene* h_scene,
                                        lbvh_segment_closest* d_out)
 {
-    return segment_queries<false>(ctx, d_queries, count, h_scene, d_out, "lbvh_segment_closest_point");
+    return distance_queries<false>(ctx, d_queries, count, h_scene, d_out, "lbvh_segment_closest_point");
 }
 
 lbvh_status lbvh_segment_within_distance(lbvh_context* ctx, const lbvh_segment_query* d_queries, size_t count, const lbvh_scene* h_scene,
                                          uint32_t* d_flags)
 {
-    return segment_queries<true>(ctx, d_queries, count, h_scene, d_flags, "lbvh_segment_within_distance");
+    return distance_queries<true>(ctx, d_queries, count, h_scene, d_flags, "lbvh_segment_within_distance");
+}
+
+lbvh_status lbvh_triangle_closest_point(lbvh_context* ctx, const lbvh_tri_distance_query* d_queries, size_t count, const lbvh_scene* h_scene,
+                                        lbvh_tri_closest* d_out)
+{
+    return distance_queries<false>(ctx, d_queries, count, h_scene, d_out, "lbvh_triangle_closest_point");
+}
+
+lbvh_status lbvh_triangle_within_distance(lbvh_context* ctx, const lbvh_tri_distance_query* d_queries, size_t count,
+                                          const lbvh_scene* h_scene, uint32_t* d_flags)
+{
+    return distance_queries<true>(ctx, d_queries, count, h_scene, d_flags, "lbvh_triangle_within_distance");
 }
 
 // the four-wide walk only, one launch; the per-lane lists are dynamic LDS sized from k

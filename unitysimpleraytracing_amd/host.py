@@ -117,6 +117,56 @@ def tri_queries_from_mesh(triangles, skip_self=False):
     return out
 
 
+def tri_distance_queries(a, b, c, max_dist2=np.inf, skip=None):
+    """layouts.TRI_DISTANCE_QUERY records for triangle_closest_points / triangle_within_distance: the triangles (a, b, c) (shapes
+    (..., 3), broadcast against each other) with the given SQUARED search radii (+inf: unbounded) and `skip` (ORIGINAL triangle
+    indices never reported; None: layouts.NULL), rounded to fp32 once."""
+    a, b, c = np.broadcast_arrays(*(np.asarray(x, dtype=np.float32) for x in (a, b, c)))
+    out = np.zeros(a.shape[:-1], dtype=L.TRI_DISTANCE_QUERY)
+    out["a"], out["b"], out["c"], out["max_dist2"] = a, b, c, np.asarray(max_dist2, dtype=np.float32)
+    out["skip"] = L.NULL if skip is None else np.asarray(skip, dtype=np.uint32)
+    return out if out.ndim else out.reshape(1)
+
+
+def tri_distance_queries_from_mesh(triangles, max_dist2=np.inf, self_skip=False):
+    """The same from another mesh — or the same one: `triangles` is an array of layouts.TRIANGLE, or a tuple (a, b, c) of (n, 3)
+    vertex arrays.  self_skip=True sets skip = each query's own index (a mesh against itself: a triangle never reports itself;
+    neighbours that share a vertex or an edge are at the distance 0 and are the caller's to tell apart), else layouts.NULL."""
+    if isinstance(triangles, np.ndarray) and triangles.dtype == L.TRIANGLE:
+        a, b, c = (triangles[k][:, :3] for k in "abc")
+    else:
+        a, b, c = (np.asarray(x, dtype=np.float32).reshape(-1, 3) for x in triangles)
+    return tri_distance_queries(a, b, c, max_dist2, np.arange(len(a), dtype=np.uint32) if self_skip else None)
+
+
+def tri_closest_witness(queries, scene_triangles, records):
+    """The two nearest points that layouts.TRI_CLOSEST `records` name, for the layouts.TRI_DISTANCE_QUERY `queries` they answer and
+    the scene's triangles (`scene_triangles`: an array of layouts.TRIANGLE in ORIGINAL order, or a tuple (a, b, c) of (n, 3) vertex
+    arrays).  -> (point_on_query, point_on_scene), float64 (count, 3); NaN rows for none-records.  `edge` says which edge holds
+    the point P + D*s — an edge of the query (0 .. 2: from a, b, c) or of scene triangle `tri` (3 .. 5: v0-v1, v0-v2, v1-v2) — and
+    `delta` leads from the scene's point to the query's: nothing is found again by comparing floats."""
+    if isinstance(scene_triangles, np.ndarray) and scene_triangles.dtype == L.TRIANGLE:
+        sa, sb, sc = (scene_triangles[k][:, :3] for k in "abc")
+    else:
+        sa, sb, sc = (np.asarray(x, dtype=np.float32).reshape(-1, 3) for x in scene_triangles)
+    queries, records = np.atleast_1d(queries), np.atleast_1d(records)
+    found = records["dist2"] != L.MAX_FLOAT
+    tri = np.where(found, records["tri"], 0).astype(np.int64)
+    v = [x[tri].astype(np.float64) for x in (sa, sb, sc)]
+    q = [queries[k].astype(np.float64) for k in "abc"]
+    m = (records["edge"] & 7).astype(np.int64)
+    starts = np.stack([q[0], q[1], q[2], v[0], v[0], v[1]])
+    ends = np.stack([q[1], q[2], q[0], v[1], v[2], v[2]])
+    rows = np.arange(len(records))
+    on_edge = starts[m, rows] + (ends[m, rows] - starts[m, rows]) * records["s"].astype(np.float64)[:, None]
+    delta = records["delta"].astype(np.float64)
+    query_edge = (m < 3)[:, None]
+    on_query = np.where(query_edge, on_edge, on_edge + delta)
+    on_scene = np.where(query_edge, on_edge - delta, on_edge)
+    on_query[~found], on_scene[~found] = np.nan, np.nan
+    return on_query, on_scene
+
+
 def segment_edges(records):
     """The `edges` word of layouts.TRI_SEGMENT records, unpacked: -> (passed, from_p0, from_p1): passed is a bool array (..., 6),
     passed[..., j] = edge test j passed (j = 0, 1, 2: the query's edges from a, b, c; j = 3, 4, 5: the scene triangle's edges
@@ -834,6 +884,45 @@ class RaytracingMeshDrawer:
         with np.errstate(invalid="ignore"):
             gap = np.where(found, np.sqrt(records["dist2"]) - shapes["radius"], np.float32(np.inf)).astype(np.float32)
         return gap, records
+
+    def triangle_closest_points(self, queries, out):
+        """Nearest scene triangle of each triangle of the DataBuffer `queries` (layouts.TRI_DISTANCE_QUERY: a, skip, b, max_dist2, c;
+        see tri_distance_queries) into the DataBuffer `out` (layouts.TRI_CLOSEST: dist2, tri, the edge test that gave it, s on that
+        edge, delta from the scene triangle's nearest point to the query's; see tri_closest_witness), over the derived scene.  No
+        triangle nearer than sqrt(max_dist2): dist2 = layouts.MAX_FLOAT and zeros.  Asynchronous; read with out.get_data()."""
+        self._per_query(N.lib.lbvh_triangle_closest_point, queries, "TRI_DISTANCE_QUERY", out, L.TRI_CLOSEST, "queries")
+
+    def triangle_within_distance(self, queries, flags):
+        """1 into the uint32 DataBuffer `flags` for each triangle of `queries` with a scene triangle nearer than sqrt(max_dist2), else 0."""
+        self._per_query(N.lib.lbvh_triangle_within_distance, queries, "TRI_DISTANCE_QUERY", flags, np.uint32, "queries", "flags")
+
+    def mesh_distance(self, other_triangles, max_dist=np.inf):
+        """Convenience: the least distance between the mesh `other_triangles` (an array of layouts.TRIANGLE, or a tuple (a, b, c) of
+        (n, 3) vertex arrays) and this one, by one triangle_closest_points with max_dist2 = max_dist^2 on every triangle of it.
+        Returns (distance, query_index, scene_tri, p_query, p_scene): the least record's sqrt(dist2), which triangle of
+        `other_triangles` and which ORIGINAL triangle of this mesh are that near, and the nearest points on them
+        (tri_closest_witness); (inf, -1, -1, None, None) where nothing is nearer than max_dist.  On equal dist2 the lower query
+        index.  Allocates, waits on the host; not part of the word-for-word contract of include/lbvh.h."""
+        q = tri_distance_queries_from_mesh(other_triangles, np.float32(max_dist) * np.float32(max_dist))
+        n = len(q)
+        queries = DataBuffer(self.ctx, max(n, 1), L.TRI_DISTANCE_QUERY)
+        out = DataBuffer(self.ctx, max(n, 1), L.TRI_CLOSEST)
+        try:
+            queries.local[:n] = q
+            queries.local[n:]["max_dist2"] = 0                        # (the one spare query of an empty set is inactive)
+            queries.sync()
+            self.triangle_closest_points(queries, out)
+            records = out.get_data()[:n].copy()
+        finally:
+            queries.dispose()
+            out.dispose()
+        found = np.nonzero(records["dist2"] != L.MAX_FLOAT)[0]
+        if len(found) == 0:
+            return float("inf"), -1, -1, None, None
+        k = int(found[np.argmin(records["dist2"][found])])
+        tris = self.container.triangle_data.local[:self.container.triangles_length]
+        p_query, p_scene = tri_closest_witness(q[k:k + 1], tris, records[k:k + 1])
+        return float(np.sqrt(np.float64(records["dist2"][k]))), k, int(records["tri"][k]), p_query[0], p_scene[0]
 
     def obb_contacts(self, shapes, offsets, contacts=None):
         """The same for the oriented boxes of the DataBuffer `shapes` (layouts.OBB): obb_overlaps with a layouts.BOX_CONTACT record

@@ -94,6 +94,11 @@
 //                                                max_dist2 = 9 for the even ones, +inf for the odd ones.  SegmentClosestPoints and
 //                                                SegmentWithinDistance; prints how many have a record, how many flags are set, the sum
 //                                                of the records' words weighted by word and segment, and the first records as words
+//     lbvh_driver triclosest <n_queries> [seed]  the same mesh and n_queries query triangles (SplitMix64, seed default 21) drawn as
+//                                                `tris` draws its own; max_dist2 = 4 for the even ones, +inf for the odd ones.
+//                                                TriangleClosestPoints and TriangleWithinDistance; prints how many have a record, how
+//                                                many flags are set, how many records are pierced, the sum of the records' words
+//                                                weighted by word and query, and the first records as words
 //     lbvh_driver boxcontacts <n_shapes> [seed]  the same mesh and n_shapes sheared boxes (SplitMix64, seed default 13): per box and axis
 //                                                k the centre uniform in the mesh's box, then component k of ax, ay, az as `shapes`
 //                                                draws them.  ObbContacts (count only, one 8-byte read, fill) and ObbDeepest; prints
@@ -951,6 +956,63 @@ static int segclosest_main(int argc, char** argv)
     return 0;
 }
 
+static int triclosest_main(int argc, char** argv)
+{
+    const size_t count = argc > 2 ? (size_t)strtoull(argv[2], nullptr, 10) : 65536;
+    uint64_t seed = argc > 3 ? strtoull(argv[3], nullptr, 10) : 21;
+    const std::vector<lbvh_triangle> mesh = random_mesh(4096);
+    float lo[3], hi[3];
+    mesh_box(mesh, lo, hi);
+    lbvh::Context ctx(0);
+    lbvh::RaytracingMeshDrawer drawer(ctx, mesh);
+    drawer.Awake();
+    lbvh::DataBuffer<lbvh_tri_distance_query> queries(ctx, count);
+    for (size_t i = 0; i < count; i++) {               // the draws of triangles_in
+        lbvh_tri_distance_query& q = queries.LocalBuffer()[i];
+        std::memset(&q, 0, sizeof q);
+        q.skip = LBVH_NULL;
+        q.max_dist2 = (i & 1) ? INFINITY : 4.0f;
+        for (int k = 0; k < 3; k++) {
+            const float centre = uniform(seed, lo[k], hi[k]);
+            q.a[k] = centre;
+            q.b[k] = centre + uniform(seed, -3.0f, 3.0f);
+            q.c[k] = centre + uniform(seed, -3.0f, 3.0f);
+        }
+    }
+    queries.Sync();
+    lbvh::DataBuffer<lbvh_tri_closest> closest(ctx, count);
+    lbvh::DataBuffer<uint32_t> within(ctx, count);
+    drawer.TriangleClosestPoints(queries, closest);
+    drawer.TriangleWithinDistance(queries, within);
+    closest.GetData();
+    within.GetData();
+    size_t found = 0, n_within = 0, pierced = 0;
+    unsigned long long words = 0;
+    for (size_t i = 0; i < count; i++) {
+        uint32_t w[8];
+        std::memcpy(w, &closest.LocalBuffer()[i], sizeof w);
+        unsigned long long sum = 0;
+        for (int k = 0; k < 8; k++) sum += (unsigned long long)(k + 1) * w[k];
+        words += (unsigned long long)(i + 1) * sum;
+        found += closest.LocalBuffer()[i].dist2 != LBVH_MAX_FLOAT;
+        pierced += (closest.LocalBuffer()[i].edge & 8u) != 0;
+        n_within += within.LocalBuffer()[i];
+    }
+    std::printf("{\"triangles\": %zu, \"queries\": %zu, \"found\": %zu, \"within\": %zu, \"pierced\": %zu, \"word_sum\": %llu, \"closest\": [",
+                mesh.size(), count, found, n_within, pierced, words);
+    size_t shown = 0;
+    for (size_t i = 0; i < count && shown < 3; i++) {
+        if (closest.LocalBuffer()[i].dist2 == LBVH_MAX_FLOAT) continue;
+        uint32_t w[8];
+        std::memcpy(w, &closest.LocalBuffer()[i], sizeof w);
+        std::printf("%s[%zu", shown++ ? ", " : "", i);
+        for (int k = 0; k < 8; k++) std::printf(", %u", w[k]);
+        std::printf("]");
+    }
+    std::printf("]}\n");
+    return 0;
+}
+
 static int boxcontacts_main(int argc, char** argv)
 {
     const size_t count = argc > 2 ? (size_t)strtoull(argv[2], nullptr, 10) : 65536;
@@ -1400,7 +1462,7 @@ int main(int argc, char** argv)
 {
     static const struct { const char* name; int (*run)(int, char**); } commands[] = {
         {"crossings", crossings_main}, {"points", points_main}, {"knn", knn_main},   {"khits", khits_main}, {"gather", gather_main}, {"sortedhits", sortedhits_main},
-        {"sweep", sweep_main},         {"capsule", capsule_main}, {"boxcast", boxcast_main}, {"castall", castall_main},         {"overlaps", overlaps_main}, {"tris", tris_main}, {"trisegs", trisegs_main}, {"shapes", shapes_main}, {"contacts", contacts_main}, {"boxcontacts", boxcontacts_main}, {"segclosest", segclosest_main}, {"regions", regions_main}, {"rays", rays_main}, {"sort", sort_main},   {"multi", multi_main}};
+        {"sweep", sweep_main},         {"capsule", capsule_main}, {"boxcast", boxcast_main}, {"castall", castall_main},         {"overlaps", overlaps_main}, {"tris", tris_main}, {"trisegs", trisegs_main}, {"shapes", shapes_main}, {"contacts", contacts_main}, {"boxcontacts", boxcontacts_main}, {"segclosest", segclosest_main}, {"triclosest", triclosest_main}, {"regions", regions_main}, {"rays", rays_main}, {"sort", sort_main},   {"multi", multi_main}};
     try {
         for (const auto& c : commands)
             if (argc > 1 && std::strcmp(argv[1], c.name) == 0) return c.run(argc, argv);

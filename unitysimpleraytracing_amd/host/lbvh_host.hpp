@@ -551,6 +551,23 @@ public:
         check(ctx_.get(), lbvh_segment_within_distance(ctx_.get(), (const lbvh_segment_query*)queries.DeviceBuffer(), queries.Size(), &s,
                                                        (uint32_t*)flags.DeviceBuffer()));
     }
+    // triangles of the caller's own (lbvh_tri_distance_query: a, skip, b, max_dist2, c) over the derived scene: the nearest scene
+    // triangle of each — {dist2, tri, edge, s, delta}: the distance between two meshes is the least record's sqrt(dist2) — or whether
+    // any lies within the radius, 1 / 0 per query (lbvh_triangle_closest_point / lbvh_triangle_within_distance; asynchronous)
+    void TriangleClosestPoints(const DataBuffer<lbvh_tri_distance_query>& queries, DataBuffer<lbvh_tri_closest>& out)
+    {
+        if (out.Size() < queries.Size()) throw Error(LBVH_ERR_INVALID_ARG, "TriangleClosestPoints: fewer records than queries");
+        const lbvh_scene s = container_->Scene();
+        check(ctx_.get(), lbvh_triangle_closest_point(ctx_.get(), (const lbvh_tri_distance_query*)queries.DeviceBuffer(), queries.Size(), &s,
+                                                      (lbvh_tri_closest*)out.DeviceBuffer()));
+    }
+    void TriangleWithinDistance(const DataBuffer<lbvh_tri_distance_query>& queries, DataBuffer<uint32_t>& flags)
+    {
+        if (flags.Size() < queries.Size()) throw Error(LBVH_ERR_INVALID_ARG, "TriangleWithinDistance: fewer flags than queries");
+        const lbvh_scene s = container_->Scene();
+        check(ctx_.get(), lbvh_triangle_within_distance(ctx_.get(), (const lbvh_tri_distance_query*)queries.DeviceBuffer(), queries.Size(), &s,
+                                                        (uint32_t*)flags.DeviceBuffer()));
+    }
     // The same for oriented boxes: ObbOverlaps with a lbvh_box_contact record (depth, tri, the axis of the thirteen that gave it,
     // back, the unit push-out normal) in place of an index; or the deepest record per box (lbvh_obb_contacts / lbvh_obb_deepest)
     void ObbContacts(const DataBuffer<lbvh_obb>& shapes, DataBuffer<uint64_t>& offsets, DataBuffer<lbvh_box_contact>* contacts = nullptr)

@@ -77,6 +77,14 @@ assert CONTACT.itemsize == 32
 SEGMENT_QUERY = np.dtype([("origin", "<f4", 3), ("max_dist2", "<f4"), ("axis", "<f4", 3), ("_pad", "<u4")])
 SEGMENT_CLOSEST = np.dtype([("dist2", "<f4"), ("tri", "<u4"), ("u", "<f4"), ("v", "<f4"), ("delta", "<f4", 3), ("s", "<f4")])
 assert SEGMENT_QUERY.itemsize == 32 and SEGMENT_CLOSEST.itemsize == 32
+# lbvh_triangle_closest_point / lbvh_triangle_within_distance: TRI_QUERY with a squared search radius (active iff max_dist2 > 0 and all
+# nine coordinates are finite), and the answer: dist2 of the query triangle from triangle `tri`, given by edge test `edge` & 7 (0 .. 2:
+# the query's edges from a, b, c against the scene triangle; 3 .. 5: the scene triangle's edges v0-v1, v0-v2, v1-v2 against the query;
+# | 8: that edge pierces), s the nearest point's parameter on that edge, delta from the scene triangle's nearest point to the query's;
+# the none-record is {MAX_FLOAT, 0, 0, 0, (0, 0, 0), 0}
+TRI_DISTANCE_QUERY = np.dtype([("a", "<f4", 3), ("skip", "<u4"), ("b", "<f4", 3), ("max_dist2", "<f4"), ("c", "<f4", 3), ("_pad", "<u4")])
+TRI_CLOSEST = np.dtype([("dist2", "<f4"), ("tri", "<u4"), ("edge", "<u4"), ("s", "<f4"), ("delta", "<f4", 3), ("_zero", "<u4")])
+assert TRI_DISTANCE_QUERY.itemsize == 48 and TRI_CLOSEST.itemsize == 32
 # lbvh_obb_contacts / lbvh_obb_deepest: one contact of an oriented box with a triangle — depth = the least push along normal that
 # separates them, axis the j of the box cast's thirteen axes that gave it (BOX_AXIS_START: none counted), back the push along
 # -normal on the same axis; the none-record of lbvh_obb_deepest has tri = NULL below and zeros elsewhere
