@@ -82,6 +82,13 @@ public static class LbvhNative
     // bits 0 .. 5 which of the six edge tests passed, bits 8 .. 10 the test that gave p0, bits 12 .. 14 the one that gave p1
     // (TriangleSegments.cs)
     [StructLayout(LayoutKind.Sequential)]
+    public struct PlaneSegment { public float p0X, p0Y, p0Z; public uint tri; public float p1X, p1Y, p1Z; public uint edges; }
+    // lbvh_plane (include/lbvh.h): n . x + d = 0, 16 bytes; lbvh_plane_segment above: where a plane cuts scene triangle tri, 32 bytes:
+    // p0 on the edge that leaves the positive side, p1 on the edge that returns to it, and edges: bits 0 .. 2 the two crossing edges,
+    // bits 8 .. 9 the edge of p0, bits 12 .. 13 the edge of p1, bits 16 .. 18 the sides of v0, v1, v2 (PlaneSections.cs)
+    [StructLayout(LayoutKind.Sequential)]
+    public struct Plane { public float nX, nY, nZ; public float d; }
+    [StructLayout(LayoutKind.Sequential)]
     public struct TriSegment { public float p0X, p0Y, p0Z; public uint tri; public float p1X, p1Y, p1Z; public uint edges; }
 
     // lbvh_point_query / lbvh_closest_point (include/lbvh.h): a point with its squared search radius (active iff maxDist2 > 0) and
@@ -235,6 +242,8 @@ public static class LbvhNative
     // few large regions (at most 65 536), each spread over the device: the same lists as lbvh_region_overlaps
     [DllImport(Lib)] public static extern int lbvh_region_overlaps_large(IntPtr ctx, IntPtr dRegions, UIntPtr count, uint mode, ref Scene scene, IntPtr dOffsets,
         IntPtr dTris, ulong capacity);
+    [DllImport(Lib)] public static extern int lbvh_plane_sections(IntPtr ctx, IntPtr dPlanes, UIntPtr count, ref Scene scene, IntPtr dOffsets,
+        IntPtr dSegments, ulong capacity);
     [DllImport(Lib)] public static extern int lbvh_k_closest_points(IntPtr ctx, IntPtr dQueries, UIntPtr count, uint k, ref Scene scene, IntPtr dOut,
         IntPtr dFound);
     [DllImport(Lib)] public static extern int lbvh_trace_k_closest(IntPtr ctx, IntPtr dRays, UIntPtr count, uint k, ref Scene scene, IntPtr dHits,

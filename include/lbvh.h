@@ -1764,6 +1764,89 @@ lbvh_status lbvh_region_overlaps_any(lbvh_context* ctx, const lbvh_region* d_reg
 lbvh_status lbvh_region_overlaps_large(lbvh_context* ctx, const lbvh_region* d_regions, size_t count, uint32_t mode, const lbvh_scene* h_scene,
                                        uint64_t* d_offsets, uint32_t* d_tris, uint64_t capacity);
 
+/* A plane n . x + d = 0: 16 bytes, arrays 16-byte aligned.  The normal need not be unit length; the side n . x + d >= 0 is the
+ * positive side. */
+typedef struct lbvh_plane { float n[3]; float d; } lbvh_plane;
+
+/* Where a plane cuts one scene triangle: 32 bytes, arrays 16-byte aligned; written as two 16-byte stores. */
+typedef struct lbvh_plane_segment {
+    float p0[3]; uint32_t tri;     /* the crossing on the edge that leaves the positive side; ORIGINAL index of the scene triangle */
+    float p1[3]; uint32_t edges;   /* the crossing on the edge that returns to it; which edges, and the three sides (below) */
+} lbvh_plane_segment;
+
+/* Plane sections: WHERE does a plane cut the mesh — a cross-section or contour line, a slice for 3D printing, one image of a
+ * CT-style stack, a water line, the outline of a clipping cap, a section view in an editor —, as a CSR list of one record per cut
+ * triangle over the derived traversal scene in its four-wide form, every plane spread over the device in the frame of
+ * lbvh_region_overlaps_large.
+ *   Arithmetic: strict fp32, every operation rounded on its own, no contraction, gradual underflow (what numpy does).
+ *       pv(x) = ((nx * x0 + ny * x1) + nz * x2) + d        the expression lbvh_region_overlaps uses for a plane's value
+ *   Box test: for a box [lo, hi], P and N are exactly the P and N of lbvh_region_overlaps above for the plane {n, d} — the plane's
+ *   value at the box corner farthest and nearest along n, each axis choosing by n_a >= 0 (true for -0, false for NaN).  A box
+ *   passes iff P >= 0 && N <= 0.  Any NaN makes the test false, so a NaN plane has no candidates.  (An infinite word gives what
+ *   the arithmetic gives; where a record then holds a NaN, which NaN is not specified.)
+ *   Candidate: triangle i has the line (a, e1, e2) of the derived scene (e1 = b - a, e2 = c - a, fp32 differences taken once at
+ *   build time) and the padded own box A = scene.triangle_aabb[i].  It is a candidate iff
+ *     (1) A passes the box test, and
+ *     (2) with V0 = a, V1 = a + e1, V2 = a + e2 (per component), s_k = pv(V_k) and side_k = (s_k >= 0) (true for -0, false for
+ *         NaN), the three sides are not all equal.
+ *   A triangle lying in the plane (all s_k == 0) has three equal sides and is not reported: coplanar faces are out of scope, as in
+ *   the triangle queries.
+ *   Record of a candidate: of the edges E0 = V0 -> V1, E1 = V1 -> V2, E2 = V2 -> V0 exactly two join different sides (true of any
+ *   three booleans that are not all equal).  For such an edge let (Vp, sp) be its end with side true and (Vm, sm) the other end:
+ *       t = sp / (sp - sm),    X = Vp + (Vm - Vp) * t     per component: one subtraction, one multiplication, one addition.
+ *   The crossing is computed from the positive end whichever way the edge runs, so it is a function of the two endpoint values
+ *   only.  p0 is the crossing on the edge that runs from the true side to the false side in the order above, p1 the crossing on
+ *   the other edge (which runs from false to true).  tri is the ORIGINAL triangle index.  edges: bits 0 .. 2 the two crossing
+ *   edges (bit k: E_k); bits 8 .. 9 the edge that gave p0; bits 12 .. 13 the edge that gave p1; bits 16 .. 18 side_0 .. side_2;
+ *   every other bit zero.
+ *   What follows from this definition:
+ *     STITCHING.  On a consistently wound mesh the neighbour across an edge runs it the other way, so the p1-edge of one record
+ *     is the p0-edge of the neighbour across it: all records of a contour run the same way round (p0 -> p1 turns about n in one
+ *     sense on an outward-wound closed mesh), and a caller stitches closed, oriented contours by (triangle, edge) through the
+ *     mesh's own adjacency — no floats are compared.
+ *     Two triangles compute bit-identical crossings on a shared edge only if their lines give bit-identical vertices: a + e1 can
+ *     differ from the stored vertex in the last place, so matching ends by float value is NOT promised.
+ *     A vertex exactly on the plane (s_k == 0) counts as the positive side.  It gives a zero-length record (p0 == p1 up to the
+ *     rounding of a + e) in triangles that otherwise lie on the negative side, and none in triangles that otherwise lie on the
+ *     positive side.
+ *   Why the list does not depend on the walk — the argument of lbvh_region_overlaps: every box of the derived tree is the exact
+ *   min / max union of what lies below it, fp32 multiplication by a fixed factor and fp32 addition are monotone, so P only grows
+ *   towards the root and N only shrinks: every ancestor slot of a candidate's leaf passes the box test.  Rule (2) and the record
+ *   are functions of (plane, triangle) only.  Each triangle is one leaf, so each candidate appears exactly once.
+ *   How: lbvh_region_overlaps_large's pipeline.  One workgroup per plane opens the four-wide tree breadth first with the box
+ *   test until one more round could exceed task_cap entries or only leaves are left (a leaf slot stays iff its box passes; the
+ *   expansion reads no triangle); every task is walked by one lane, which reads the triangle's 64-byte line at every leaf slot
+ *   that passes — and for a leaf task — and applies rule (2); the per-task counts are scanned into 64-bit task offsets, d_offsets
+ *   picks every plane's first, and the fill walk, taking the same decisions from the same values, writes each task's records at
+ *   the task's own offset.  No atomic is on the output path and no kernel waits for another workgroup.  task_cap is
+ *   lbvh_region_overlaps_large's: the largest power of two not above min(65536, 2^22 / count).
+ * Output — lbvh_triangle_intersection_segments' CSR contract, word for word:
+ *   d_offsets: count + 1 words of 64 bits.  d_offsets[k] = the number of candidates of planes 0 .. k-1, d_offsets[count] = the
+ *   total.  Always written in full, whatever `capacity` is.
+ *   d_segments, `capacity` records of 32 bytes: segment k = d_segments[d_offsets[k] .. d_offsets[k+1]) = one record per candidate
+ *   of plane k, each triangle exactly once.  THE ORDER INSIDE A SEGMENT IS NOT PART OF THE CONTRACT (sort by `tri` on the host if
+ *   an order is needed), but two calls with the same inputs on the same scene write the same bytes.
+ *   Overflow: no record at index >= capacity is ever written; every segment with d_offsets[k+1] <= capacity is complete; records
+ *   below `capacity` that belong to a segment which does not fit are unspecified.  The call never waits on the host and returns
+ *   LBVH_OK in both cases: the caller reads d_offsets[count] (one 8-byte download) to learn what was needed.
+ *   Count-only form: capacity == 0 writes the offsets in one walk (d_segments may be NULL); otherwise the tasks are walked twice.
+ *   d_segments == NULL with capacity > 0 is LBVH_ERR_INVALID_ARG.
+ * Needs the derived traversal scene (lbvh_build_fast_scene; a stale one is LBVH_ERR_INVALID_ARG), is asynchronous on the context's
+ * stream with no host wait, and uses the context's ray scratch and lbvh_region_overlaps_large's task scratch: it drops the path
+ * tracer's live-path list (see lbvh_path_bounce).  A failed scratch allocation is LBVH_ERR_OUT_OF_MEMORY and leaves the context
+ * usable.  count == 0 is a no-op: nothing is enqueued and no buffer is touched, d_offsets[0] included.  Rejected
+ * (LBVH_ERR_INVALID_ARG, the message names this entry point): NULL ctx / d_planes / h_scene / d_offsets, d_planes or d_segments
+ * not 16-byte aligned, d_offsets not 8-byte aligned, count > LBVH_PLANE_SECTIONS_MAX_COUNT.  lbvh_debug_region_task_cap,
+ * lbvh_debug_ray_waves, lbvh_debug_ray_stack_split and lbvh_debug_ray_stack_limit apply to the task walks;
+ * lbvh_ray_stats_target: rays counts the tasks that are not empty, node_fetches the node lines of the task walks plus the nodes
+ * the expansion opened, triangle_tests the triangle lines read; the full form adds the walks' share twice.
+ * Measurements: tools/plane_sections_bench.py (written, not yet recorded).
+ * Out of scope: a per-lane form for more than 65 536 planes; an _any form; a device-side sort of 32-byte segments; merging records
+ * into polylines on the device (host.stitch_sections does it on the host); coplanar faces. */
+#define LBVH_PLANE_SECTIONS_MAX_COUNT 65536
+lbvh_status lbvh_plane_sections(lbvh_context* ctx, const lbvh_plane* d_planes, size_t count, const lbvh_scene* h_scene,
+                                uint64_t* d_offsets, lbvh_plane_segment* d_segments, uint64_t capacity);
+
 /* Camera rays into path states (origin/dir as Raytracing.compute:108-126, throughput 1, radiance 0, alive). */
 lbvh_status lbvh_path_begin(lbvh_context* ctx, const lbvh_camera* h_camera, lbvh_path_state* d_states);
 
@@ -1788,7 +1871,7 @@ lbvh_status lbvh_path_scatter(lbvh_context* ctx, const lbvh_scene* h_scene, cons
  * lbvh_path_bounce on the same d_states / d_hits listed as live (a list kept by the context).  Every library call that writes
  * into those buffers drops the list (lbvh_path_begin, lbvh_trace_rays, a primary trace into any part of d_hits,
  * lbvh_buffer_upload / _fill_u32 / _free), and so does lbvh_trace_forget — and so do lbvh_trace_closest,
- * lbvh_trace_occluded, lbvh_closest_point_query, lbvh_within_distance, lbvh_count_hits, lbvh_point_crossings, lbvh_box_overlaps, lbvh_gather_within_distance, lbvh_k_closest_points, lbvh_trace_k_closest, lbvh_gather_hits, lbvh_sphere_cast, lbvh_sphere_cast_any, lbvh_capsule_cast, lbvh_capsule_cast_any, lbvh_box_cast, lbvh_box_cast_any, lbvh_triangle_intersections, lbvh_triangle_intersects_any, lbvh_triangle_intersection_segments, lbvh_capsule_overlaps, lbvh_capsule_overlaps_any, lbvh_obb_overlaps, lbvh_obb_overlaps_any, lbvh_capsule_contacts, lbvh_capsule_deepest, lbvh_obb_contacts, lbvh_obb_deepest, lbvh_segment_closest_point, lbvh_segment_within_distance, lbvh_triangle_closest_point, lbvh_triangle_within_distance, lbvh_sphere_cast_all, lbvh_capsule_cast_all, lbvh_box_cast_all, lbvh_region_overlaps, lbvh_region_overlaps_any and lbvh_region_overlaps_large, whatever buffers they are given, since they use the same ray scratch; then every state is scanned again.  The one exception among the query calls:
+ * lbvh_trace_occluded, lbvh_closest_point_query, lbvh_within_distance, lbvh_count_hits, lbvh_point_crossings, lbvh_box_overlaps, lbvh_gather_within_distance, lbvh_k_closest_points, lbvh_trace_k_closest, lbvh_gather_hits, lbvh_sphere_cast, lbvh_sphere_cast_any, lbvh_capsule_cast, lbvh_capsule_cast_any, lbvh_box_cast, lbvh_box_cast_any, lbvh_triangle_intersections, lbvh_triangle_intersects_any, lbvh_triangle_intersection_segments, lbvh_capsule_overlaps, lbvh_capsule_overlaps_any, lbvh_obb_overlaps, lbvh_obb_overlaps_any, lbvh_capsule_contacts, lbvh_capsule_deepest, lbvh_obb_contacts, lbvh_obb_deepest, lbvh_segment_closest_point, lbvh_segment_within_distance, lbvh_triangle_closest_point, lbvh_triangle_within_distance, lbvh_sphere_cast_all, lbvh_capsule_cast_all, lbvh_box_cast_all, lbvh_region_overlaps, lbvh_region_overlaps_any, lbvh_region_overlaps_large and lbvh_plane_sections, whatever buffers they are given, since they use the same ray scratch; then every state is scanned again.  The one exception among the query calls:
  * lbvh_sort_hit_segments and lbvh_sort_index_segments take no context scratch and keep the live-path list (they drop it only when the
  * buffer they sort is d_hits itself).  What the library
  * cannot see is a write of the CALLER's own (a kernel or hipMemcpy that revives or ends paths, Russian roulette): between two

@@ -129,6 +129,7 @@ SIGNATURES = {
     "lbvh_region_overlaps": (_I32, [_P, _P, _SZ, _U32, C.POINTER(Scene), _P, _P, C.c_uint64]),
     "lbvh_region_overlaps_any": (_I32, [_P, _P, _SZ, _U32, C.POINTER(Scene), _P]),
     "lbvh_region_overlaps_large": (_I32, [_P, _P, _SZ, _U32, C.POINTER(Scene), _P, _P, C.c_uint64]),
+    "lbvh_plane_sections": (_I32, [_P, _P, _SZ, C.POINTER(Scene), _P, _P, C.c_uint64]),
     "lbvh_count_hits": (_I32, [_P, _P, _SZ, C.POINTER(Scene), _P]),
     "lbvh_point_crossings": (_I32, [_P, _P, _SZ, C.POINTER(C.c_float), _U32, C.POINTER(Scene), _P]),
     "lbvh_path_begin": (_I32, [_P, C.POINTER(Camera), _P]),
@@ -161,6 +162,7 @@ SORT_SHARDED_MAX_CONTEXTS = 16           # include/lbvh.h LBVH_SORT_SHARDED_MAX_
 SORT_SHARDED_REPLICATE = 1               # LBVH_SORT_SHARDED_REPLICATE
 K_CLOSEST_MAX = 32                       # LBVH_K_CLOSEST_MAX
 REGION_LARGE_MAX_COUNT = 65536           # LBVH_REGION_LARGE_MAX_COUNT
+PLANE_SECTIONS_MAX_COUNT = 65536         # LBVH_PLANE_SECTIONS_MAX_COUNT
 
 # include/lbvh_debug.h: not part of the drop-in boundary
 DEBUG_SWITCH_SORT_QUEUES, DEBUG_SWITCH_COLD_ORDER, DEBUG_SWITCH_BUILD_FORM, DEBUG_SWITCH_FRAME_WAIT_MS, DEBUG_SWITCH_SORT_FORM, DEBUG_SWITCH_FAIL_RESERVE = range(6)

@@ -177,6 +177,83 @@ def segment_edges(records):
     return passed, ((e >> 8) & 7).astype(np.uint32), ((e >> 12) & 7).astype(np.uint32)
 
 
+def planes(normals, points):
+    """layouts.PLANE records for plane_sections / cross_sections: the planes with the given normals (they need not be unit length)
+    through the given points, d = -(n . point) formed in float64 and rounded once.  Either argument may be a single vector: a
+    stack of parallel planes is planes(n, points), a fan through one point planes(normals, p)."""
+    n = np.atleast_2d(np.asarray(normals, dtype=np.float64))
+    p = np.atleast_2d(np.asarray(points, dtype=np.float64))
+    n, p = np.broadcast_arrays(n, p)
+    out = np.zeros(len(n), dtype=L.PLANE)
+    out["n"] = n
+    out["d"] = -(out["n"].astype(np.float64) * p).sum(axis=1)
+    return out
+
+
+def section_edges(edges):
+    """The `edges` word of layouts.PLANE_SEGMENT records (or the records themselves), unpacked: -> (crossing, from_p0, from_p1,
+    sides): crossing is a bool array (..., 3), crossing[..., k] = edge k of the triangle crosses the plane (k = 0, 1, 2: v0-v1,
+    v1-v2, v2-v0); from_p0 / from_p1 the edge that gave p0 / p1; sides a bool array (..., 3), the side of v0, v1, v2 (True:
+    n . x + d >= 0)."""
+    e = np.asarray(edges["edges"] if getattr(edges, "dtype", None) == L.PLANE_SEGMENT else edges, dtype=np.uint32)
+    three = np.arange(3, dtype=np.uint32)
+    return ((e[..., None] >> three) & 1).astype(bool), ((e >> 8) & 3).astype(np.uint32), ((e >> 12) & 3).astype(np.uint32), \
+        ((e[..., None] >> (three + np.uint32(16))) & 1).astype(bool)
+
+
+def stitch_sections(segments, triangles):
+    """Chains the layouts.PLANE_SEGMENT records of ONE plane into polylines: -> (loops, chains), each a list of (points, tris):
+    points a float32 array (m, 3), tris the m triangles walked, in order.  A loop is closed (the last record's p1 lies on the edge
+    of the first record's p0, the point is not repeated: m points, m records); an open chain starts at a p0 no record leads to and
+    has m + 1 points for m records (a mesh with a border, or a record set that is not complete).
+    Records are joined by EDGE KEYS made from the ORIGINAL vertex bytes of `triangles` (layouts.TRIANGLE, the scene's own records,
+    indexed by `tri`): the key of edge k of a triangle is the sorted pair of the 12-byte positions of its two vertices, so two
+    triangles agree on a shared edge exactly when the mesh stores the same vertex bytes in both.  No computed float is compared.
+    On a consistently wound mesh the p1-edge of a record is the p0-edge of its neighbour, so every chain runs one way round."""
+    segments = np.asarray(segments)
+    _, from_p0, from_p1, _ = section_edges(segments)
+    tri = segments["tri"].astype(np.int64)
+    verts = [np.ascontiguousarray(triangles[k][tri][:, :3], dtype=np.float32) for k in "abc"]
+    raw = [[v[i].tobytes() for i in range(len(tri))] for v in verts]
+
+    def key(i, k):
+        u, v = raw[k][i], raw[(k + 1) % 3][i]
+        return (u, v) if u <= v else (v, u)
+
+    starts = {}
+    for i in range(len(tri)):
+        starts.setdefault(key(i, int(from_p0[i])), []).append(i)
+    used = np.zeros(len(tri), dtype=bool)
+
+    def follow(first):
+        order, i = [], first
+        while True:
+            used[i] = True
+            order.append(i)
+            nxt = [j for j in starts.get(key(i, int(from_p1[i])), ()) if not used[j]]
+            if not nxt:
+                return order, key(i, int(from_p1[i])) == key(first, int(from_p0[first]))
+            i = nxt[0]
+
+    ends = {}
+    for i in range(len(tri)):
+        ends[key(i, int(from_p1[i]))] = ends.get(key(i, int(from_p1[i])), 0) + 1
+    loops, chains = [], []
+    # open chains first, from the records no other record leads to; what is left are loops
+    for i in range(len(tri)):
+        if not used[i] and key(i, int(from_p0[i])) not in ends:
+            order, _ = follow(i)
+            chains.append((np.concatenate([segments["p0"][order], segments["p1"][order[-1:]]]), segments["tri"][order].copy()))
+    for i in range(len(tri)):
+        if not used[i]:
+            order, closed = follow(i)
+            if closed:
+                loops.append((segments["p0"][order].copy(), segments["tri"][order].copy()))
+            else:
+                chains.append((np.concatenate([segments["p0"][order], segments["p1"][order[-1:]]]), segments["tri"][order].copy()))
+    return loops, chains
+
+
 class _DeviceWords:
     """`count` 32-bit floats at a device pointer, for torch.as_tensor (zero copy)"""
 
@@ -974,6 +1051,49 @@ class RaytracingMeshDrawer:
         if regions.size > N.REGION_LARGE_MAX_COUNT:
             raise ValueError(f"region_overlaps_large takes at most {N.REGION_LARGE_MAX_COUNT} regions")
         self._overlaps(lambda h, q, n, s, o, t, cap: N.lib.lbvh_region_overlaps_large(h, q, n, mode, s, o, t, cap), regions, L.REGION, offsets, tris)
+
+    def plane_sections(self, planes, offsets, segments=None):
+        """WHERE each plane of the DataBuffer `planes` (layouts.PLANE: n, d with n . x + d = 0; see host.planes) cuts the mesh: one
+        layouts.PLANE_SEGMENT record per cut triangle (p0 and p1 on two of its edges, tri, and `edges`: which edges and the three
+        sides; see host.section_edges), every plane spread over the device (lbvh_plane_sections; at most
+        _native.PLANE_SECTIONS_MAX_COUNT planes).  `offsets` (uint64 DataBuffer, at least planes.size + 1 entries) is always
+        complete; `segments` (layouts.PLANE_SEGMENT DataBuffer, its size is the capacity) receives the records, segment k =
+        segments[offsets[k] : offsets[k + 1]], in no particular order; segments=None counts only.  Asynchronous."""
+        if planes.dtype != L.PLANE or offsets.dtype != np.uint64 or offsets.size < planes.size + 1 or \
+                (segments is not None and segments.dtype != L.PLANE_SEGMENT):
+            raise ValueError("planes must be a DataBuffer of layouts.PLANE, offsets one of uint64 with one entry more, segments one of "
+                             "layouts.PLANE_SEGMENT or None")
+        if planes.size > N.PLANE_SECTIONS_MAX_COUNT:
+            raise ValueError(f"plane_sections takes at most {N.PLANE_SECTIONS_MAX_COUNT} planes")
+        s = self.container.scene()
+        N.check(self.ctx.handle, N.lib.lbvh_plane_sections(self.ctx.handle, planes.device, planes.size, C.byref(s), offsets.device,
+                                                           segments.device if segments is not None else None,
+                                                           segments.size if segments is not None else 0))
+
+    def cross_sections(self, planes, stitch=False, min_capacity=1):
+        """Convenience: count -> one 8-byte download -> allocate -> fill -> download, for layouts.PLANE records on the host (see
+        host.planes) or a DataBuffer of them.  Returns (offsets, records): uint64[count + 1] and layouts.PLANE_SEGMENT[total],
+        every segment ordered by `tri` on the host.  stitch=True returns instead a list with one (loops, chains) of
+        host.stitch_sections per plane, stitched through the scene's own triangle records."""
+        own = not isinstance(planes, DataBuffer)
+        if own:
+            host_planes = np.ascontiguousarray(planes, dtype=L.PLANE).reshape(-1)
+            if len(host_planes) == 0:
+                return [] if stitch else (np.zeros(1, dtype=np.uint64), np.zeros(0, dtype=L.PLANE_SEGMENT))
+            planes = DataBuffer(self.ctx, len(host_planes), L.PLANE)
+            planes.local[:] = host_planes
+            planes.sync()
+        try:
+            off, rec = self._csr_lists(self.plane_sections, planes, min_capacity, False, dtype=L.PLANE_SEGMENT)
+            segment = np.repeat(np.arange(planes.size), np.diff(off).astype(np.int64))
+            rec = rec[np.lexsort((rec["tri"], segment))]
+        finally:
+            if own:
+                planes.dispose()
+        if not stitch:
+            return off, rec
+        tris = self.container.triangle_data.local[:self.container.triangles_length]
+        return [stitch_sections(rec[int(off[k]):int(off[k + 1])], tris) for k in range(len(off) - 1)]
 
     def region_overlaps_any(self, regions, mode, flags):
         """1 into the uint32 DataBuffer `flags` for each region of `regions` that has a candidate in `mode`, else 0."""

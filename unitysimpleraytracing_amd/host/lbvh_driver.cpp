@@ -113,6 +113,13 @@
 //                                                device-sorted list (mod 2^64), and the first TOUCHING segments.  With `large` after
 //                                                the seed the lists come from RegionOverlapsLarge (n_regions <= 65 536): the same
 //                                                numbers, and "large": true in the output
+//     lbvh_driver sections <n_planes> [seed]     the 4 096 triangles of cfg1 and n_planes planes (SplitMix64, seed default 7): per plane
+//                                                and axis k the normal's component uniform in [-1, 1], then a point's coordinate
+//                                                uniform in the mesh's box; d = -((nx * px + ny * py) + nz * pz) in fp32.
+//                                                PlaneSections (count only, one 8-byte read, fill), every segment sorted by tri on the
+//                                                host; prints the total, how many segments are non-empty, the sum of (k + 1) *
+//                                                offsets[k] and the sum of (position + 1) * (the record's eight words) over the sorted
+//                                                list (both mod 2^64)
 #include <algorithm>
 #include <chrono>
 #include <cmath>
@@ -745,6 +752,60 @@ static int trisegs_main(int argc, char** argv)
     }
     std::printf("{\"triangles\": %zu, \"queries\": %zu, \"total\": %llu, \"non_empty\": %zu, \"two_ends\": %zu, \"offset_sum\": %llu, "
                 "\"record_sum\": %llu}\n", mesh.size(), count, total, non_empty, two_ends, offset_sum, record_sum);
+    return 0;
+}
+
+// `sections`: PlaneSections (count only, one 8-byte read, fill), every segment sorted by tri on the host; the sums of `trisegs`
+static int sections_main(int argc, char** argv)
+{
+    const size_t count = argc > 2 ? (size_t)strtoull(argv[2], nullptr, 10) : 64;
+    uint64_t seed = argc > 3 ? strtoull(argv[3], nullptr, 10) : 7;
+    const std::vector<lbvh_triangle> mesh = random_mesh(4096);
+    float lo[3], hi[3];
+    mesh_box(mesh, lo, hi);
+    lbvh::Context ctx(0);
+    lbvh::RaytracingMeshDrawer drawer(ctx, mesh);
+    drawer.Awake();
+    lbvh::DataBuffer<lbvh_plane> planes(ctx, count);
+    for (size_t i = 0; i < count; i++) {
+        lbvh_plane& q = planes.LocalBuffer()[i];
+        float p[3];
+        for (int k = 0; k < 3; k++) {
+            q.n[k] = uniform(seed, -1.0f, 1.0f);
+            p[k] = uniform(seed, lo[k], hi[k]);
+        }
+        const float xy = q.n[0] * p[0] + q.n[1] * p[1];
+        const float xyz = xy + q.n[2] * p[2];
+        q.d = -xyz;
+    }
+    planes.Sync();
+    lbvh::DataBuffer<uint64_t> offsets(ctx, count + 1);
+    drawer.PlaneSections(planes, offsets);
+    offsets.GetData();
+    const unsigned long long total = offsets.LocalBuffer()[count];
+    lbvh::DataBuffer<lbvh_plane_segment> segments(ctx, total ? (size_t)total : 1);
+    drawer.PlaneSections(planes, offsets, &segments);
+    offsets.GetData();
+    segments.GetData();
+    std::vector<lbvh_plane_segment>& rec = segments.LocalBuffer();
+    size_t non_empty = 0;
+    unsigned long long offset_sum = 0, record_sum = 0;
+    for (size_t k = 0; k <= count; k++) offset_sum += (unsigned long long)(k + 1) * offsets.LocalBuffer()[k];
+    for (size_t k = 0; k < count; k++) {
+        const uint64_t first = offsets.LocalBuffer()[k], last = offsets.LocalBuffer()[k + 1];
+        non_empty += last > first;
+        std::sort(rec.begin() + (ptrdiff_t)first, rec.begin() + (ptrdiff_t)last,
+                  [](const lbvh_plane_segment& x, const lbvh_plane_segment& y) { return x.tri < y.tri; });
+    }
+    for (size_t i = 0; i < (size_t)total; i++) {
+        uint32_t w[8];
+        std::memcpy(w, &rec[i], sizeof w);
+        unsigned long long words = 0;
+        for (uint32_t x : w) words += x;
+        record_sum += (unsigned long long)(i + 1) * words;
+    }
+    std::printf("{\"triangles\": %zu, \"planes\": %zu, \"total\": %llu, \"non_empty\": %zu, \"offset_sum\": %llu, \"record_sum\": %llu}\n",
+                mesh.size(), count, total, non_empty, offset_sum, record_sum);
     return 0;
 }
 
@@ -1462,7 +1523,7 @@ int main(int argc, char** argv)
 {
     static const struct { const char* name; int (*run)(int, char**); } commands[] = {
         {"crossings", crossings_main}, {"points", points_main}, {"knn", knn_main},   {"khits", khits_main}, {"gather", gather_main}, {"sortedhits", sortedhits_main},
-        {"sweep", sweep_main},         {"capsule", capsule_main}, {"boxcast", boxcast_main}, {"castall", castall_main},         {"overlaps", overlaps_main}, {"tris", tris_main}, {"trisegs", trisegs_main}, {"shapes", shapes_main}, {"contacts", contacts_main}, {"boxcontacts", boxcontacts_main}, {"segclosest", segclosest_main}, {"triclosest", triclosest_main}, {"regions", regions_main}, {"rays", rays_main}, {"sort", sort_main},   {"multi", multi_main}};
+        {"sweep", sweep_main},         {"capsule", capsule_main}, {"boxcast", boxcast_main}, {"castall", castall_main},         {"overlaps", overlaps_main}, {"tris", tris_main}, {"trisegs", trisegs_main}, {"sections", sections_main}, {"shapes", shapes_main}, {"contacts", contacts_main}, {"boxcontacts", boxcontacts_main}, {"segclosest", segclosest_main}, {"triclosest", triclosest_main}, {"regions", regions_main}, {"rays", rays_main}, {"sort", sort_main},   {"multi", multi_main}};
     try {
         for (const auto& c : commands)
             if (argc > 1 && std::strcmp(argv[1], c.name) == 0) return c.run(argc, argv);

@@ -623,6 +623,20 @@ public:
                                                      (uint64_t*)offsets.DeviceBuffer(), tris ? (uint32_t*)tris->DeviceBuffer() : nullptr,
                                                      tris ? (uint64_t)tris->Size() : 0));
     }
+    // WHERE each plane (lbvh_plane: n . x + d = 0) cuts the mesh: one lbvh_plane_segment per cut triangle — p0 on the edge that
+    // leaves the positive side, p1 on the edge that returns to it, tri, and edges: bits 0 .. 2 the two crossing edges, bits 8 .. 9 /
+    // 12 .. 13 the edges of p0 / p1, bits 16 .. 18 the sides of the three vertices —, every plane spread over the device; at most
+    // LBVH_PLANE_SECTIONS_MAX_COUNT planes.  A contour is stitched by (triangle, edge): the p1-edge of a record is the p0-edge of
+    // the neighbour across it (lbvh_plane_sections; asynchronous).
+    void PlaneSections(const DataBuffer<lbvh_plane>& planes, DataBuffer<uint64_t>& offsets, DataBuffer<lbvh_plane_segment>* segments = nullptr)
+    {
+        if (offsets.Size() < planes.Size() + 1) throw Error(LBVH_ERR_INVALID_ARG, "PlaneSections: offsets needs one entry more than planes");
+        const lbvh_scene s = container_->Scene();
+        check(ctx_.get(), lbvh_plane_sections(ctx_.get(), (const lbvh_plane*)planes.DeviceBuffer(), planes.Size(), &s,
+                                              (uint64_t*)offsets.DeviceBuffer(),
+                                              segments ? (lbvh_plane_segment*)segments->DeviceBuffer() : nullptr,
+                                              segments ? (uint64_t)segments->Size() : 0));
+    }
     void RegionOverlapsAny(const DataBuffer<lbvh_region>& regions, uint32_t mode, DataBuffer<uint32_t>& flags)
     {
         if (flags.Size() < regions.Size()) throw Error(LBVH_ERR_INVALID_ARG, "RegionOverlapsAny: fewer flags than regions");

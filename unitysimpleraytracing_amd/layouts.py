@@ -58,6 +58,12 @@ assert TRI_QUERY.itemsize == 48
 # which of the six edge tests passed, bits 8 .. 10 the test that gave p0, bits 12 .. 14 the one that gave p1 (host.segment_edges)
 TRI_SEGMENT = np.dtype([("p0", "<f4", 3), ("tri", "<u4"), ("p1", "<f4", 3), ("edges", "<u4")])
 assert TRI_SEGMENT.itemsize == 32
+# lbvh_plane_sections: a plane n . x + d = 0, and where it cuts scene triangle `tri` — p0 the crossing on the edge that leaves the
+# positive side, p1 the one on the edge that returns to it, and `edges`: bits 0 .. 2 the two crossing edges (v0-v1, v1-v2, v2-v0),
+# bits 8 .. 9 the edge that gave p0, bits 12 .. 13 the one that gave p1, bits 16 .. 18 the sides of v0, v1, v2 (host.section_edges)
+PLANE = np.dtype([("n", "<f4", 3), ("d", "<f4")])
+PLANE_SEGMENT = np.dtype([("p0", "<f4", 3), ("tri", "<u4"), ("p1", "<f4", 3), ("edges", "<u4")])
+assert PLANE.itemsize == 16 and PLANE_SEGMENT.itemsize == 32
 # lbvh_capsule_overlaps / lbvh_obb_overlaps and their _any forms: a capsule (the segment origin .. origin + axis and the radius) and
 # an oriented box { centre + s0*ax + s1*ay + s2*az : |s_i| <= 1 } where they stand — CAPSULE_RAY and BOX_RAY without the motion;
 # the pads are not read
