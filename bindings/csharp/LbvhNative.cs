@@ -230,6 +230,8 @@ public static class LbvhNative
     [DllImport(Lib)] public static extern int lbvh_segment_within_distance(IntPtr ctx, IntPtr dQueries, UIntPtr count, ref Scene scene, IntPtr dFlags);
     [DllImport(Lib)] public static extern int lbvh_triangle_closest_point(IntPtr ctx, IntPtr dQueries, UIntPtr count, ref Scene scene, IntPtr dOut);
     [DllImport(Lib)] public static extern int lbvh_triangle_within_distance(IntPtr ctx, IntPtr dQueries, UIntPtr count, ref Scene scene, IntPtr dFlags);
+    [DllImport(Lib)] public static extern int lbvh_triangle_gather_within_distance(IntPtr ctx, IntPtr dQueries, UIntPtr count, ref Scene scene, IntPtr dOffsets,
+        IntPtr dRecords, ulong capacity);
     [DllImport(Lib)] public static extern int lbvh_obb_contacts(IntPtr ctx, IntPtr dShapes, UIntPtr count, ref Scene scene, IntPtr dOffsets,
         IntPtr dContacts, ulong capacity);
     [DllImport(Lib)] public static extern int lbvh_obb_deepest(IntPtr ctx, IntPtr dShapes, UIntPtr count, ref Scene scene, IntPtr dOut);

@@ -1581,13 +1581,67 @@ typedef struct lbvh_tri_closest {
  * index is `skip` is not counted, as at lbvh_triangle_intersections).
  * Cost: up to six segment tests (54 point tests) per triangle line read: several times lbvh_segment_closest_point's narrow phase on
  * boxes grown by the whole query.  Pass active queries only where time matters, and a search radius where one is known.
- * Out of scope: the k nearest triangles of a triangle; a gather of every triangle within the distance; a two-tree (mesh-BVH against
- * mesh-BVH) descent; exact coplanar-overlap handling beyond what the arithmetic gives; oriented-box distance; a unit
- * normal in the record (delta / sqrtf(dist2) where dist2 > 0; the caller's square root). */
+ * Every triangle within the distance, not only the nearest: lbvh_triangle_gather_within_distance below.
+ * Out of scope: the k nearest triangles of a triangle; a two-tree (mesh-BVH against mesh-BVH) descent; exact coplanar-overlap
+ * handling beyond what the arithmetic gives; oriented-box distance; a unit normal in the record (delta / sqrtf(dist2) where
+ * dist2 > 0; the caller's square root). */
 lbvh_status lbvh_triangle_closest_point(lbvh_context* ctx, const lbvh_tri_distance_query* d_queries, size_t count, const lbvh_scene* h_scene,
                                         lbvh_tri_closest* d_out);
 lbvh_status lbvh_triangle_within_distance(lbvh_context* ctx, const lbvh_tri_distance_query* d_queries, size_t count, const lbvh_scene* h_scene,
                                           uint32_t* d_flags);
+
+/* Triangle proximity: EVERY scene triangle within a distance of a triangle, each with its distance, witness feature and direction
+ * (what a cloth or contact solver asks: proximity pairs for cloth and self-collision, a mesh against itself with `skip`; speculative
+ * contacts for mesh colliders inside a margin — one record per PAIR, where lbvh_triangle_closest_point gives one per query), as a
+ * CSR list of lbvh_tri_closest records over the derived traversal scene in its four-wide form, one query per lane.  The last cell
+ * of the distance family: lbvh_gather_within_distance for a point, lbvh_capsule_contacts for a segment, this call for a triangle.
+ * Everything is defined by reference to lbvh_triangle_closest_point above:
+ *   Arithmetic: the active query, R, the query box, the six edge tests, the pair result (dist2, edge, s, delta) and box2q are that
+ *   call's, unchanged; so is the early exit at the first dist2_m == +0.
+ *   Candidate: triangle i is a candidate for a query iff its ORIGINAL index != skip, dist2_i < R and
+ *   !(dist2_i < box2q(own AABB_i)): the same predicate as the closest call's.  The radius is open: dist2 == R is not listed.
+ *   Record: the record of a candidate is what lbvh_triangle_closest_point would write were that triangle the only one:
+ *   {dist2, tri, edge, s, delta, 0}.
+ *   Slot test: a slot of the tree is entered iff box2q(slot) < R (false for a NaN).  There is no nearest-first order and no
+ *   shrinking bound: every passing slot is visited.
+ * Why the list does not depend on the walk (the argument at lbvh_gather_within_distance with box2q for box2): box2q is monotone in
+ * the box and every box of the derived tree is the exact min / max union of what is below it, so
+ * box2q(ancestor) <= box2q(leaf) <= dist2 < R for every candidate, against a fixed bound: every slot on the way to a candidate is
+ * entered, whatever the order.  Each triangle is one leaf, so each candidate appears exactly once.
+ * Output — the CSR contract of lbvh_gather_within_distance / lbvh_capsule_contacts with a 32-byte record:
+ *   d_offsets: count + 1 words of 64 bits, segment k = d_records[d_offsets[k] .. d_offsets[k+1]), d_offsets[count] = the total.
+ *   Always written in full.
+ *   d_records, `capacity` records of 32 bytes, each written as two 16-byte stores: one record per candidate of query k.  THE ORDER
+ *   INSIDE A SEGMENT IS THE WALK'S AND IS NOT PART OF THE CONTRACT (sort on the host by (dist2, tri) where an order is needed).
+ *   Overflow: no record at index >= capacity is ever written; every segment with d_offsets[k+1] <= capacity is complete; records
+ *   below `capacity` that belong to a segment which does not fit are unspecified.  The call never waits on the host and returns
+ *   LBVH_OK in both cases: the caller reads d_offsets[count] to learn what was needed.
+ *   Count-only form: capacity == 0 writes the offsets and walks once (d_records may be NULL); otherwise the scene is walked twice
+ *   (a count walk, the device-side scan, a fill walk that makes the same decisions from the same values and forms delta).
+ *   d_records == NULL with capacity > 0 is LBVH_ERR_INVALID_ARG.  Two calls on the same input write the same bytes.
+ *   An inactive query gets an empty segment.
+ * Relations (tests/test_triangle_proximity.py holds each):
+ *   (a) segment k is non-empty exactly when lbvh_triangle_within_distance gives 1 for query k.
+ *   (b) the least record of a non-empty segment by (dist2 as an fp32 value, tri) equals lbvh_triangle_closest_point's record in
+ *       all eight words.
+ *   (c) every triangle lbvh_triangle_intersections lists for {a, b, c, skip} is in the segment with dist2 == +0 and edge & 8 set.
+ *       The converse is NOT promised (a pair at distance +0 without a pierce, a touching vertex, is listed here and not there).
+ *   (d) the capacity == 0 form writes the same offsets as the full form.
+ * Needs the derived traversal scene (lbvh_build_fast_scene; a stale one is LBVH_ERR_INVALID_ARG with this entry point's name), is
+ * asynchronous on the context's stream with no host wait, and uses the context's ray scratch: it drops the path tracer's live-path
+ * list (see lbvh_path_bounce).  count == 0 is a no-op: nothing is enqueued and no buffer is touched, d_offsets[0] included.
+ * Rejected: NULL ctx / d_queries / h_scene / d_offsets, d_queries or d_records not 16-byte aligned, d_offsets not 8-byte aligned,
+ * count > 2^32 - 1.  Four-wide walk only; lbvh_debug_ray_waves, lbvh_debug_ray_stack_split, lbvh_debug_ray_stack_limit and
+ * lbvh_ray_stats_target apply as to lbvh_capsule_contacts (`rays` = active queries per walk; triangle_tests counts the triangle
+ * lines read after `skip`; the full form reports the count walk's plus the fill walk's: twice the count-only form's).
+ * Cost: an unbounded query lists the whole mesh.  There is no shrinking bound, so every pair whose boxes are inside R pays up to
+ * six segment tests (54 point tests) in BOTH walks; pass the margin the solver needs, not more.
+ * Out of scope: a device-side sort of 32-byte records (the host sorts; lbvh_sort_hit_segments is for 16-byte records); the k
+ * nearest triangles of a triangle; a two-tree (mesh-BVH against mesh-BVH) descent; removing the (i, j) / (j, i) duplicates or the
+ * adjacent triangles of a self-query on the device (the host does, from the returned list). */
+lbvh_status lbvh_triangle_gather_within_distance(lbvh_context* ctx, const lbvh_tri_distance_query* d_queries, size_t count,
+                                                 const lbvh_scene* h_scene, uint64_t* d_offsets, lbvh_tri_closest* d_records,
+                                                 uint64_t capacity);
 
 /* One contact of an oriented box with a triangle: 32 bytes, arrays 16-byte aligned; written as two 16-byte stores. */
 typedef struct lbvh_box_contact {
@@ -1871,7 +1925,7 @@ lbvh_status lbvh_path_scatter(lbvh_context* ctx, const lbvh_scene* h_scene, cons
  * lbvh_path_bounce on the same d_states / d_hits listed as live (a list kept by the context).  Every library call that writes
  * into those buffers drops the list (lbvh_path_begin, lbvh_trace_rays, a primary trace into any part of d_hits,
  * lbvh_buffer_upload / _fill_u32 / _free), and so does lbvh_trace_forget — and so do lbvh_trace_closest,
- * lbvh_trace_occluded, lbvh_closest_point_query, lbvh_within_distance, lbvh_count_hits, lbvh_point_crossings, lbvh_box_overlaps, lbvh_gather_within_distance, lbvh_k_closest_points, lbvh_trace_k_closest, lbvh_gather_hits, lbvh_sphere_cast, lbvh_sphere_cast_any, lbvh_capsule_cast, lbvh_capsule_cast_any, lbvh_box_cast, lbvh_box_cast_any, lbvh_triangle_intersections, lbvh_triangle_intersects_any, lbvh_triangle_intersection_segments, lbvh_capsule_overlaps, lbvh_capsule_overlaps_any, lbvh_obb_overlaps, lbvh_obb_overlaps_any, lbvh_capsule_contacts, lbvh_capsule_deepest, lbvh_obb_contacts, lbvh_obb_deepest, lbvh_segment_closest_point, lbvh_segment_within_distance, lbvh_triangle_closest_point, lbvh_triangle_within_distance, lbvh_sphere_cast_all, lbvh_capsule_cast_all, lbvh_box_cast_all, lbvh_region_overlaps, lbvh_region_overlaps_any, lbvh_region_overlaps_large and lbvh_plane_sections, whatever buffers they are given, since they use the same ray scratch; then every state is scanned again.  The one exception among the query calls:
+ * lbvh_trace_occluded, lbvh_closest_point_query, lbvh_within_distance, lbvh_count_hits, lbvh_point_crossings, lbvh_box_overlaps, lbvh_gather_within_distance, lbvh_k_closest_points, lbvh_trace_k_closest, lbvh_gather_hits, lbvh_sphere_cast, lbvh_sphere_cast_any, lbvh_capsule_cast, lbvh_capsule_cast_any, lbvh_box_cast, lbvh_box_cast_any, lbvh_triangle_intersections, lbvh_triangle_intersects_any, lbvh_triangle_intersection_segments, lbvh_capsule_overlaps, lbvh_capsule_overlaps_any, lbvh_obb_overlaps, lbvh_obb_overlaps_any, lbvh_capsule_contacts, lbvh_capsule_deepest, lbvh_obb_contacts, lbvh_obb_deepest, lbvh_segment_closest_point, lbvh_segment_within_distance, lbvh_triangle_closest_point, lbvh_triangle_within_distance, lbvh_triangle_gather_within_distance, lbvh_sphere_cast_all, lbvh_capsule_cast_all, lbvh_box_cast_all, lbvh_region_overlaps, lbvh_region_overlaps_any, lbvh_region_overlaps_large and lbvh_plane_sections, whatever buffers they are given, since they use the same ray scratch; then every state is scanned again.  The one exception among the query calls:
  * lbvh_sort_hit_segments and lbvh_sort_index_segments take no context scratch and keep the live-path list (they drop it only when the
  * buffer they sort is d_hits itself).  What the library
  * cannot see is a write of the CALLER's own (a kernel or hipMemcpy that revives or ends paths, Russian roulette): between two

@@ -71,7 +71,8 @@ lbvh_status lbvh_debug_ray_waves(lbvh_context* ctx, uint32_t max_waves);
  * and lbvh_sphere_cast / lbvh_sphere_cast_any, lbvh_capsule_cast / lbvh_capsule_cast_any and lbvh_box_cast / lbvh_box_cast_any
  * (`rays` = active casts; a triangle line counts once, whatever number of its derived triangles or axes is tested), and
  * lbvh_capsule_overlaps / lbvh_obb_overlaps and their _any forms in the same way (`rays` = active shapes; the full form adds twice
- * what the count-only form adds) — lbvh_capsule_contacts, lbvh_capsule_deepest, lbvh_obb_contacts and lbvh_obb_deepest likewise, and lbvh_segment_closest_point / lbvh_segment_within_distance and lbvh_triangle_closest_point / lbvh_triangle_within_distance (`rays` = active queries) —, and both walks of lbvh_gather_hits (`rays` = active rays: the
+ * what the count-only form adds) — lbvh_capsule_contacts, lbvh_capsule_deepest, lbvh_obb_contacts and lbvh_obb_deepest likewise, and lbvh_segment_closest_point / lbvh_segment_within_distance and lbvh_triangle_closest_point / lbvh_triangle_within_distance (`rays` = active queries) —, and both walks of
+ * lbvh_triangle_gather_within_distance (`rays` = active queries: the full form adds twice what the count-only form adds), and both walks of lbvh_gather_hits (`rays` = active rays: the
  * full form adds twice what the count-only form adds). */
 typedef struct lbvh_ray_stats {
     uint64_t rays;

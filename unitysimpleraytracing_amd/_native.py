@@ -121,6 +121,7 @@ SIGNATURES = {
     "lbvh_segment_closest_point": (_I32, [_P, _P, _SZ, C.POINTER(Scene), _P]),
     "lbvh_segment_within_distance": (_I32, [_P, _P, _SZ, C.POINTER(Scene), _P]),
     "lbvh_triangle_closest_point": (_I32, [_P, _P, _SZ, C.POINTER(Scene), _P]),
+    "lbvh_triangle_gather_within_distance": (_I32, [_P, _P, _SZ, C.POINTER(Scene), _P, _P, C.c_uint64]),
     "lbvh_triangle_within_distance": (_I32, [_P, _P, _SZ, C.POINTER(Scene), _P]),
     "lbvh_obb_overlaps": (_I32, [_P, _P, _SZ, C.POINTER(Scene), _P, _P, C.c_uint64]),
     "lbvh_obb_overlaps_any": (_I32, [_P, _P, _SZ, C.POINTER(Scene), _P]),

@@ -3440,6 +3440,170 @@ __global__ __launch_bounds__(64) void triangle_distance_wide_kernel(const lbvh_t
     if (STATS) add_ray_stats(stats, n_queries, n_steps, n_tris);
 }
 
+// ---- triangle proximity: every triangle within a distance of a triangle (lbvh_triangle_gather_within_distance, include/lbvh.h). --
+// The frame of shape_overlap_wide_kernel / capsule_contact_wide_kernel — nothing shrinks, so there is no nearest-first order: every
+// passing inner slot is pushed — with triangle_distance_wide_kernel's query, box2q against the fixed bound R for the four slots and
+// triangle_triangle2 at a leaf slot, after `skip`.
+
+// delta of a listed pair: a COPY of the lines triangle_distance_wide_kernel forms its record's delta with — sharing one function
+// between the two kernels changed that kernel's instructions, which this file's existing kernels must keep —: the residual of
+// point_triangle2 at x = P + D*s of the winning test, turned round for a scene edge (m >= 3) so that it points from the scene triangle
+// to the query; 0 where pierced.  The three lines must stay operation for operation those: relation (b) of
+// lbvh_triangle_gather_within_distance promises the closest call's words.
+__device__ __forceinline__ void triangle_pair_delta(uint32_t edge, float s, float u, float v, float ax, float ay, float az, float bx, float by,
+                                                    float bz, float cx, float cy, float cz, const float4 v0, const float4 v1, const float4 v2,
+                                                    float& dx, float& dy, float& dz)
+{
+    ray_t seg;
+    float4 p, f1, f2;
+    triangle_edge_test(edge & 7u, ax, ay, az, bx, by, bz, cx, cy, cz, v0, v1, v2, seg, p, f1, f2);
+    const float apx = (seg.ox + seg.dx * s) - p.x, apy = (seg.oy + seg.dy * s) - p.y, apz = (seg.oz + seg.dz * s) - p.z;
+    const float rx = apx - (f1.x * u + f2.x * v), ry = apy - (f1.y * u + f2.y * v), rz = apz - (f1.z * u + f2.z * v);
+    const bool pierced = (edge & 8u) != 0u, turn = (edge & 7u) >= 3u;
+    dx = pierced ? 0.0f : (turn ? -rx : rx);
+    dy = pierced ? 0.0f : (turn ? -ry : ry);
+    dz = pierced ? 0.0f : (turn ? -rz : rz);
+}
+
+// the header's active rule of a triangle distance query {a, skip | b, max_dist2 | c, _pad}, false for a NaN radius or coordinate: a
+// copy of load_tri_distance_query's condition (that function also writes the closest call's none-record, and taking the condition
+// out of it changed triangle_distance_wide_kernel's instructions)
+__device__ __forceinline__ bool tri_distance_query_active(const float4 qa, const float4 qb, const float4 qc)
+{
+    const float inf = __builtin_inff();
+    return qb.w > 0.0f && fabsf(qa.x) < inf && fabsf(qa.y) < inf && fabsf(qa.z) < inf && fabsf(qb.x) < inf && fabsf(qb.y) < inf &&
+           fabsf(qb.z) < inf && fabsf(qc.x) < inf && fabsf(qc.y) < inf && fabsf(qc.z) < inf;
+}
+
+// The one decision of both walks: the pair's record values, and whether the triangle is a candidate (the closest call's predicate
+// against the fixed R; `own` is box2q of the leaf slot's box).  Count and fill call it on the same values.
+__device__ __forceinline__ bool triangle_proximity_of(float ax, float ay, float az, float bx, float by, float bz, float cx, float cy, float cz,
+                                                      const float4 v0, const float4 v1, const float4 v2, float own, float R, float& dist2,
+                                                      uint32_t& edge, float& s, float& u, float& v)
+{
+    dist2 = triangle_triangle2(ax, ay, az, bx, by, bz, cx, cy, cz, v0, v1, v2, edge, s, u, v);
+    return dist2 < R && !(dist2 < own);                  // both false for a NaN
+}
+
+// FILL false: the candidates of query k are counted into counts[k] (0 for an inactive query).  FILL true: the lane starts at
+// offsets[k] and writes {dist2, tri, edge, s | delta, 0} as two 16-byte stores per candidate, never at or beyond the capacity.
+template <bool FILL, bool STATS>
+__global__ __launch_bounds__(64) void triangle_proximity_wide_kernel(const lbvh_tri_distance_query* __restrict__ queries, uint32_t total,
+                                                                     const lbvh_wide_node* __restrict__ wide,
+                                                                     const lbvh_fast_node* __restrict__ lines,
+                                                                     uint32_t* __restrict__ counts,            // !FILL: candidates of query k
+                                                                     const uint64_t* __restrict__ offsets,     // FILL: where segment k starts
+                                                                     lbvh_tri_closest* __restrict__ out,       // FILL: the records
+                                                                     uint64_t capacity,                        // FILL: records in `out`
+                                                                     uint32_t* __restrict__ deep,     // [gridDim.x][kWideStackDeep][64]
+                                                                     uint32_t lds_depth,              // <= kWideStackLds
+                                                                     uint32_t deep_cap,               // <= kWideStackDeep
+                                                                     uint32_t* __restrict__ fault, lbvh_ray_stats* stats)
+{
+    __shared__ uint32_t s_stack[kWideStackLds][LBVH_WAVE];
+    uint32_t* my_deep = deep + (size_t)blockIdx.x * (kWideStackDeep * LBVH_WAVE) + threadIdx.x;
+    float4* records = reinterpret_cast<float4*>(out);
+    const uint32_t lane = threadIdx.x;
+    const uint32_t run = max((total + gridDim.x - 1) / gridDim.x, 32u);
+    uint32_t next = blockIdx.x * run;
+    if (next >= total) return;
+    const uint32_t end = min(next + run, total);
+    uint32_t n_queries = 0, n_steps = 0, n_tris = 0;
+
+    bool active = false;
+    uint32_t i = 0, skip = kWideEmpty;
+    float ax = 0.0f, ay = 0.0f, az = 0.0f, bx = 0.0f, by = 0.0f, bz = 0.0f, cx = 0.0f, cy = 0.0f, cz = 0.0f;
+    float lx = 0.0f, ly = 0.0f, lz = 0.0f, hx = 0.0f, hy = 0.0f, hz = 0.0f;      // the query's box
+    float R = 0.0f;
+    uint32_t n_found = 0, sp = 0, node = 0;
+    uint64_t pos = 0;                                    // FILL: where this lane's next record goes
+    auto push = [&](uint32_t ref) {
+        if (sp < lds_depth) { s_stack[sp][lane] = ref; sp++; }
+        else if (sp < lds_depth + deep_cap) { my_deep[(sp - lds_depth) * LBVH_WAVE] = ref; sp++; }
+        // a dropped entry would be a silently short list: report it, as the other walkers do (lbvh_debug_ray_stack_limit provokes it)
+        else __hip_atomic_store(fault, LBVH_FAULT_RAY_STACK, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    };
+    for (;;) {
+        const uint64_t idle = __ballot(!active);
+        if (idle != 0 && next < end) {
+            if (!active) {
+                const uint32_t k = next + mbcnt64(idle);
+                if (k < end) {
+                    i = k;
+                    const float4 qa = reinterpret_cast<const float4*>(queries)[3 * (size_t)k];
+                    const float4 qb = reinterpret_cast<const float4*>(queries)[3 * (size_t)k + 1];
+                    const float4 qc = reinterpret_cast<const float4*>(queries)[3 * (size_t)k + 2];
+                    active = tri_distance_query_active(qa, qb, qc);
+                    R = fminf(qb.w, LBVH_MAX_FLOAT);
+                    ax = qa.x; ay = qa.y; az = qa.z; skip = __float_as_uint(qa.w);
+                    bx = qb.x; by = qb.y; bz = qb.z;
+                    cx = qc.x; cy = qc.y; cz = qc.z;
+                    lx = fminf(fminf(ax, bx), cx); ly = fminf(fminf(ay, by), cy); lz = fminf(fminf(az, bz), cz);
+                    hx = fmaxf(fmaxf(ax, bx), cx); hy = fmaxf(fmaxf(ay, by), cy); hz = fmaxf(fmaxf(az, bz), cz);
+                    sp = 0; node = 0;
+                    if constexpr (FILL) { if (active) pos = offsets[k]; }
+                    else { n_found = 0; if (!active) counts[k] = 0u; }
+                    if (STATS && active) n_queries++;
+                }
+            }
+            next += (uint32_t)__popcll(idle);
+        }
+        if (!__any(active) && next >= end) break;
+        if (active) {
+            if (STATS) n_steps++;
+            const float4* w = reinterpret_cast<const float4*>(&wide[node]);
+            const float4 lox = w[0], loy = w[1], loz = w[2], hix = w[3], hiy = w[4], hiz = w[5];
+            const uint4 ref = reinterpret_cast<const uint4*>(w)[6];
+#define BOX2Q(c) box_box2(lox.c, loy.c, loz.c, hix.c, hiy.c, hiz.c, lx, ly, lz, hx, hy, hz)
+            const float b0 = BOX2Q(x), b1 = BOX2Q(y), b2 = BOX2Q(z), b3 = BOX2Q(w);
+#undef BOX2Q
+            // entered iff box2q < R: false for a NaN
+            const bool h0 = b0 < R && ref.x != kWideEmpty, h1 = b1 < R && ref.y != kWideEmpty;
+            const bool h2 = b2 < R && ref.z != kWideEmpty, h3 = b3 < R && ref.w != kWideEmpty;
+            const uint32_t hit = (h0 ? 1u : 0u) | (h1 ? 2u : 0u) | (h2 ? 4u : 0u) | (h3 ? 8u : 0u);
+            const uint32_t leaf = (ref.x >> 31) | ((ref.y >> 31) << 1) | ((ref.z >> 31) << 2) | ((ref.w >> 31) << 3);
+            uint32_t leaves = hit & leaf, inner = hit & ~leaf;
+            while (leaves != 0u) {
+                const uint32_t k = (uint32_t)__builtin_ctz(leaves);
+                leaves &= leaves - 1u;
+                float4 v0, v1, v2;
+                unpack_fast_triangle(reinterpret_cast<const float4*>(&lines[pick4(ref, k) & 0x7FFFFFFFu]), v0, v1, v2);
+                const uint32_t tri = __float_as_uint(v0.w);
+                if (tri == skip) continue;
+                if (STATS) n_tris++;
+                const float own = k == 0u ? b0 : (k == 1u ? b1 : (k == 2u ? b2 : b3));
+                uint32_t edge = 0u;
+                float dist2 = 0.0f, s = 0.0f, u = 0.0f, v = 0.0f;
+                if (!triangle_proximity_of(ax, ay, az, bx, by, bz, cx, cy, cz, v0, v1, v2, own, R, dist2, edge, s, u, v)) continue;
+                if constexpr (FILL) {
+                    if (pos < capacity) {                        // never a record at or beyond the capacity
+                        float dx, dy, dz;
+                        triangle_pair_delta(edge, s, u, v, ax, ay, az, bx, by, bz, cx, cy, cz, v0, v1, v2, dx, dy, dz);
+                        records[2 * pos] = make_float4(dist2, __uint_as_float(tri), __uint_as_float(edge), s);
+                        records[2 * pos + 1] = make_float4(dx, dy, dz, __uint_as_float(0u));
+                    }
+                    pos++;
+                } else n_found++;
+            }
+            if (inner != 0u) {
+                node = pick4(ref, (uint32_t)__builtin_ctz(inner));
+                inner &= inner - 1u;
+                while (inner != 0u) {
+                    push(pick4(ref, (uint32_t)__builtin_ctz(inner)));
+                    inner &= inner - 1u;
+                }
+            } else if (sp != 0) {
+                sp--;
+                node = sp < lds_depth ? s_stack[sp][lane] : my_deep[(sp - lds_depth) * LBVH_WAVE];
+            } else {
+                if constexpr (!FILL) counts[i] = n_found;
+                active = false;
+            }
+        }
+    }
+    if (STATS) add_ray_stats(stats, n_queries, n_steps, n_tris);
+}
+
 // ---- box contacts: how deep an oriented box is in each triangle it touches, and which way out (lbvh_obb_contacts, ------------
 // lbvh_obb_deepest, include/lbvh.h).  The frame and the slot test of shape_overlap_wide_kernel<kShapeObb>; the count walk of
 // lbvh_obb_contacts IS that kernel's kTriCount form.  The two forms are capsule_contact_wide_kernel's.
@@ -4951,6 +5115,35 @@ static lbvh_status capsule_contacts(lbvh_context* ctx, const lbvh_capsule* d_sha
         });
 }
 
+// lbvh_triangle_gather_within_distance: capsule_contacts with the triangle distance query — both walks are
+// triangle_proximity_wide_kernel's.  Four-wide walk only.  (a rejection names the entry point)
+static lbvh_status triangle_proximity(lbvh_context* ctx, const lbvh_tri_distance_query* d_queries, size_t count, const lbvh_scene* h_scene,
+                                      uint64_t* d_offsets, lbvh_tri_closest* d_records, uint64_t capacity, const char* who)
+{
+    if (!ctx) return LBVH_ERR_INVALID_ARG;
+    if (count == 0) return LBVH_OK;
+    NAMED_REQUIRE(d_queries != nullptr && h_scene != nullptr && d_offsets != nullptr);
+    NAMED_REQUIRE(d_records != nullptr || capacity == 0);
+    NAMED_REQUIRE(((uintptr_t)d_queries & 15) == 0 && ((uintptr_t)d_offsets & 7) == 0 && ((uintptr_t)d_records & 15) == 0);
+    NAMED_REQUIRE(count <= 0xFFFFFFFFull);
+    walk_launch w;
+    const lbvh_status rc = begin_walk(ctx, h_scene, count, who, true, &w);
+    if (rc != LBVH_OK) return rc;
+    const uint32_t total = (uint32_t)count;
+    return csr_query(
+        ctx, count, d_offsets, capacity,
+        [&](uint32_t* counts) {
+            LBVH_LAUNCH_STATS(ctx, ctx->ray_stats, (triangle_proximity_wide_kernel<false, STATS>), dim3(w.waves), dim3(LBVH_WAVE), d_queries, total,
+                              w.wn, ctx->fast_nodes, counts, (const uint64_t*)nullptr, (lbvh_tri_closest*)nullptr, (uint64_t)0, w.deep, w.lds,
+                              w.deep_cap, ctx->fault_dev, ctx->ray_stats);
+        },
+        [&] {
+            LBVH_LAUNCH_STATS(ctx, ctx->ray_stats, (triangle_proximity_wide_kernel<true, STATS>), dim3(w.waves), dim3(LBVH_WAVE), d_queries, total,
+                              w.wn, ctx->fast_nodes, (uint32_t*)nullptr, (const uint64_t*)d_offsets, d_records, capacity, w.deep, w.lds, w.deep_cap,
+                              ctx->fault_dev, ctx->ray_stats);
+        });
+}
+
 static lbvh_status capsule_deepest(lbvh_context* ctx, const lbvh_capsule* d_shapes, size_t count, const lbvh_scene* h_scene, lbvh_contact* d_out,
                                    const char* who)
 {
@@ -5348,6 +5541,13 @@ lbvh_status lbvh_triangle_within_distance(lbvh_context* ctx, const lbvh_tri_dist
                                           const lbvh_scene* h_scene, uint32_t* d_flags)
 {
     return distance_queries<true>(ctx, d_queries, count, h_scene, d_flags, "lbvh_triangle_within_distance");
+}
+
+lbvh_status lbvh_triangle_gather_within_distance(lbvh_context* ctx, const lbvh_tri_distance_query* d_queries, size_t count,
+                                                 const lbvh_scene* h_scene, uint64_t* d_offsets, lbvh_tri_closest* d_records,
+                                                 uint64_t capacity)
+{
+    return triangle_proximity(ctx, d_queries, count, h_scene, d_offsets, d_records, capacity, "lbvh_triangle_gather_within_distance");
 }
 
 // the four-wide walk only, one launch; the per-lane lists are dynamic LDS sized from k

@@ -167,6 +167,27 @@ def tri_closest_witness(queries, scene_triangles, records):
     return on_query, on_scene
 
 
+def unique_self_pairs(offsets, records, triangles):
+    """The pairs of a self-proximity pass (proximity_pairs(mesh, margin, self_skip=True) on the mesh itself: query k IS triangle
+    k), each once and without the neighbours: a pair (i, j) = (query, records["tri"]) is kept only for i < j — (j, i) is the same
+    pair found from the other side —, and not when the two triangles share a vertex (equal coordinates, word for word: they touch
+    by construction and are at the distance 0).  `triangles`: an array of layouts.TRIANGLE in ORIGINAL order, or a tuple (a, b, c)
+    of (n, 3) vertex arrays.  -> (pairs, kept): an (m, 2) int64 array of (i, j) and the m layouts.TRI_CLOSEST records, in the
+    list's order.  Pure numpy."""
+    if isinstance(triangles, np.ndarray) and triangles.dtype == L.TRIANGLE:
+        a, b, c = (triangles[k][:, :3] for k in "abc")
+    else:
+        a, b, c = (np.asarray(x, dtype=np.float32).reshape(-1, 3) for x in triangles)
+    offsets = np.asarray(offsets, dtype=np.uint64)
+    records = np.atleast_1d(records)
+    i = np.repeat(np.arange(len(offsets) - 1, dtype=np.int64), np.diff(offsets).astype(np.int64))
+    j = records["tri"].astype(np.int64)
+    verts = np.ascontiguousarray(np.stack([a, b, c], axis=1), dtype=np.float32).view(np.uint32)        # [triangle, vertex, word]
+    shared = (verts[i][:, :, None, :] == verts[j][:, None, :, :]).all(axis=3).any(axis=(1, 2))
+    keep = (i < j) & ~shared
+    return np.stack([i[keep], j[keep]], axis=1), records[keep]
+
+
 def segment_edges(records):
     """The `edges` word of layouts.TRI_SEGMENT records, unpacked: -> (passed, from_p0, from_p1): passed is a bool array (..., 6),
     passed[..., j] = edge test j passed (j = 0, 1, 2: the query's edges from a, b, c; j = 3, 4, 5: the scene triangle's edges
@@ -1000,6 +1021,47 @@ class RaytracingMeshDrawer:
         tris = self.container.triangle_data.local[:self.container.triangles_length]
         p_query, p_scene = tri_closest_witness(q[k:k + 1], tris, records[k:k + 1])
         return float(np.sqrt(np.float64(records["dist2"][k]))), k, int(records["tri"][k]), p_query[0], p_scene[0]
+
+    def triangle_gather_within_distance(self, queries, offsets, records=None):
+        """EVERY scene triangle within sqrt(max_dist2) of each triangle of the DataBuffer `queries` (layouts.TRI_DISTANCE_QUERY), one
+        layouts.TRI_CLOSEST record per pair — what triangle_closest_points would write were that triangle the only one —, as a CSR
+        list on the caller's buffers: `offsets` (uint64 DataBuffer, at least queries.size + 1 entries) always complete; `records`
+        (layouts.TRI_CLOSEST DataBuffer, its size is the capacity), segment k = records[offsets[k] : offsets[k + 1]], in no
+        particular order; records=None counts only.  Asynchronous."""
+        if queries.dtype != L.TRI_DISTANCE_QUERY or offsets.dtype != np.uint64 or offsets.size < queries.size + 1 or \
+                (records is not None and records.dtype != L.TRI_CLOSEST):
+            raise ValueError("queries must be a DataBuffer of layouts.TRI_DISTANCE_QUERY, offsets one of uint64 with one entry more, records "
+                             "one of layouts.TRI_CLOSEST or None")
+        s = self.container.scene()
+        N.check(self.ctx.handle, N.lib.lbvh_triangle_gather_within_distance(self.ctx.handle, queries.device, queries.size, C.byref(s),
+                                                                            offsets.device, records.device if records is not None else None,
+                                                                            records.size if records is not None else 0))
+
+    def proximity_pairs(self, other, max_dist, self_skip=False, sort=False, min_capacity=1):
+        """Convenience, as contacts(): count -> one 8-byte download -> allocate -> fill.  `other`: an array of
+        layouts.TRI_DISTANCE_QUERY (taken as it is: max_dist and self_skip are not applied), or a mesh as mesh_distance takes it (an
+        array of layouts.TRIANGLE or a tuple (a, b, c) of (n, 3) vertex arrays), every triangle of it with max_dist2 = max_dist^2 and,
+        self_skip=True, skip = its own index (this mesh against itself; see unique_self_pairs).  Returns (offsets, records): host
+        arrays, uint64[n + 1] and layouts.TRI_CLOSEST[total], every segment in the walk's order; sort=True orders every segment by
+        (dist2, tri) HERE, ON THE HOST.  Allocates, waits on the host."""
+        if isinstance(other, np.ndarray) and other.dtype == L.TRI_DISTANCE_QUERY:
+            q = other.reshape(-1)
+        else:
+            q = tri_distance_queries_from_mesh(other, np.float32(max_dist) * np.float32(max_dist), self_skip)
+        n = len(q)
+        if n == 0:
+            return np.zeros(1, dtype=np.uint64), np.zeros(0, dtype=L.TRI_CLOSEST)
+        queries = DataBuffer(self.ctx, n, L.TRI_DISTANCE_QUERY)
+        try:
+            queries.local[:] = q
+            queries.sync()
+            off, rec = self._csr_lists(self.triangle_gather_within_distance, queries, min_capacity, False, dtype=L.TRI_CLOSEST)
+        finally:
+            queries.dispose()
+        if sort:
+            segment = np.repeat(np.arange(n), np.diff(off).astype(np.int64))
+            rec = rec[np.lexsort((rec["tri"], rec["dist2"], segment))]
+        return off, rec
 
     def obb_contacts(self, shapes, offsets, contacts=None):
         """The same for the oriented boxes of the DataBuffer `shapes` (layouts.OBB): obb_overlaps with a layouts.BOX_CONTACT record

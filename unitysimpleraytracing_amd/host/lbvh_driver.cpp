@@ -99,6 +99,11 @@
 //                                                TriangleClosestPoints and TriangleWithinDistance; prints how many have a record, how
 //                                                many flags are set, how many records are pierced, the sum of the records' words
 //                                                weighted by word and query, and the first records as words
+//     lbvh_driver triprox <n_queries> [seed]     the same mesh and the query triangles of `triclosest` (the same draws, seed default
+//                                                21), every max_dist2 = 4: nothing is unbounded.  TriangleGatherWithinDistance (count
+//                                                only, one 8-byte read, fill); prints the total, how many segments are non-empty, the
+//                                                longest segment, how many records are pierced, and the sum of the records' words
+//                                                weighted by word and by the record's position after sorting each segment by tri
 //     lbvh_driver boxcontacts <n_shapes> [seed]  the same mesh and n_shapes sheared boxes (SplitMix64, seed default 13): per box and axis
 //                                                k the centre uniform in the mesh's box, then component k of ax, ay, az as `shapes`
 //                                                draws them.  ObbContacts (count only, one 8-byte read, fill) and ObbDeepest; prints
@@ -1074,6 +1079,60 @@ static int triclosest_main(int argc, char** argv)
     return 0;
 }
 
+static int triprox_main(int argc, char** argv)
+{
+    const size_t count = argc > 2 ? (size_t)strtoull(argv[2], nullptr, 10) : 65536;
+    uint64_t seed = argc > 3 ? strtoull(argv[3], nullptr, 10) : 21;
+    const std::vector<lbvh_triangle> mesh = random_mesh(4096);
+    float lo[3], hi[3];
+    mesh_box(mesh, lo, hi);
+    lbvh::Context ctx(0);
+    lbvh::RaytracingMeshDrawer drawer(ctx, mesh);
+    drawer.Awake();
+    lbvh::DataBuffer<lbvh_tri_distance_query> queries(ctx, count);
+    for (size_t i = 0; i < count; i++) {               // the draws of triclosest
+        lbvh_tri_distance_query& q = queries.LocalBuffer()[i];
+        std::memset(&q, 0, sizeof q);
+        q.skip = LBVH_NULL;
+        q.max_dist2 = 4.0f;
+        for (int k = 0; k < 3; k++) {
+            const float centre = uniform(seed, lo[k], hi[k]);
+            q.a[k] = centre;
+            q.b[k] = centre + uniform(seed, -3.0f, 3.0f);
+            q.c[k] = centre + uniform(seed, -3.0f, 3.0f);
+        }
+    }
+    queries.Sync();
+    lbvh::DataBuffer<uint64_t> offsets(ctx, count + 1);
+    drawer.TriangleGatherWithinDistance(queries, offsets);              // count only
+    offsets.GetData();
+    const size_t total = (size_t)offsets.LocalBuffer()[count];
+    lbvh::DataBuffer<lbvh_tri_closest> records(ctx, total ? total : 1);
+    drawer.TriangleGatherWithinDistance(queries, offsets, &records);
+    offsets.GetData();
+    records.GetData();
+    size_t nonempty = 0, longest = 0, pierced = 0;
+    unsigned long long words = 0;
+    lbvh_tri_closest* rec = records.LocalBuffer().data();
+    for (size_t i = 0; i < count; i++) {
+        const size_t from = (size_t)offsets.LocalBuffer()[i], to = (size_t)offsets.LocalBuffer()[i + 1];
+        nonempty += to > from;
+        longest = std::max(longest, to - from);
+        std::sort(rec + from, rec + to, [](const lbvh_tri_closest& x, const lbvh_tri_closest& y) { return x.tri < y.tri; });
+        for (size_t p = from; p < to; p++) {
+            uint32_t w[8];
+            std::memcpy(w, &rec[p], sizeof w);
+            unsigned long long sum = 0;
+            for (int k = 0; k < 8; k++) sum += (unsigned long long)(k + 1) * w[k];
+            words += (unsigned long long)(p + 1) * sum;
+            pierced += (rec[p].edge & 8u) != 0;
+        }
+    }
+    std::printf("{\"triangles\": %zu, \"queries\": %zu, \"total\": %zu, \"nonempty\": %zu, \"longest\": %zu, \"pierced\": %zu, \"word_sum\": %llu}\n",
+                mesh.size(), count, total, nonempty, longest, pierced, words);
+    return 0;
+}
+
 static int boxcontacts_main(int argc, char** argv)
 {
     const size_t count = argc > 2 ? (size_t)strtoull(argv[2], nullptr, 10) : 65536;
@@ -1523,7 +1582,7 @@ int main(int argc, char** argv)
 {
     static const struct { const char* name; int (*run)(int, char**); } commands[] = {
         {"crossings", crossings_main}, {"points", points_main}, {"knn", knn_main},   {"khits", khits_main}, {"gather", gather_main}, {"sortedhits", sortedhits_main},
-        {"sweep", sweep_main},         {"capsule", capsule_main}, {"boxcast", boxcast_main}, {"castall", castall_main},         {"overlaps", overlaps_main}, {"tris", tris_main}, {"trisegs", trisegs_main}, {"sections", sections_main}, {"shapes", shapes_main}, {"contacts", contacts_main}, {"boxcontacts", boxcontacts_main}, {"segclosest", segclosest_main}, {"triclosest", triclosest_main}, {"regions", regions_main}, {"rays", rays_main}, {"sort", sort_main},   {"multi", multi_main}};
+        {"sweep", sweep_main},         {"capsule", capsule_main}, {"boxcast", boxcast_main}, {"castall", castall_main},         {"overlaps", overlaps_main}, {"tris", tris_main}, {"trisegs", trisegs_main}, {"sections", sections_main}, {"shapes", shapes_main}, {"contacts", contacts_main}, {"boxcontacts", boxcontacts_main}, {"segclosest", segclosest_main}, {"triclosest", triclosest_main}, {"triprox", triprox_main}, {"regions", regions_main}, {"rays", rays_main}, {"sort", sort_main},   {"multi", multi_main}};
     try {
         for (const auto& c : commands)
             if (argc > 1 && std::strcmp(argv[1], c.name) == 0) return c.run(argc, argv);

@@ -568,6 +568,20 @@ public:
         check(ctx_.get(), lbvh_triangle_within_distance(ctx_.get(), (const lbvh_tri_distance_query*)queries.DeviceBuffer(), queries.Size(), &s,
                                                         (uint32_t*)flags.DeviceBuffer()));
     }
+    // EVERY scene triangle within the radius of each query triangle, one lbvh_tri_closest record per pair (what TriangleClosestPoints
+    // would write were that triangle the only one) as a CSR list in no particular order inside a segment; records = nullptr counts
+    // only, offsets[queries] says what is needed (lbvh_triangle_gather_within_distance; asynchronous)
+    void TriangleGatherWithinDistance(const DataBuffer<lbvh_tri_distance_query>& queries, DataBuffer<uint64_t>& offsets,
+                                      DataBuffer<lbvh_tri_closest>* records = nullptr)
+    {
+        if (offsets.Size() < queries.Size() + 1)
+            throw Error(LBVH_ERR_INVALID_ARG, "TriangleGatherWithinDistance: offsets needs one entry more than queries");
+        const lbvh_scene s = container_->Scene();
+        check(ctx_.get(), lbvh_triangle_gather_within_distance(ctx_.get(), (const lbvh_tri_distance_query*)queries.DeviceBuffer(), queries.Size(), &s,
+                                                               (uint64_t*)offsets.DeviceBuffer(),
+                                                               records ? (lbvh_tri_closest*)records->DeviceBuffer() : nullptr,
+                                                               records ? (uint64_t)records->Size() : 0));
+    }
     // The same for oriented boxes: ObbOverlaps with a lbvh_box_contact record (depth, tri, the axis of the thirteen that gave it,
     // back, the unit push-out normal) in place of an index; or the deepest record per box (lbvh_obb_contacts / lbvh_obb_deepest)
     void ObbContacts(const DataBuffer<lbvh_obb>& shapes, DataBuffer<uint64_t>& offsets, DataBuffer<lbvh_box_contact>* contacts = nullptr)
