@@ -91,6 +91,15 @@ public static class LbvhNative
     [StructLayout(LayoutKind.Sequential)]
     public struct TriSegment { public float p0X, p0Y, p0Z; public uint tri; public float p1X, p1Y, p1Z; public uint edges; }
 
+    // lbvh_tri_ray / lbvh_tri_cast_hit (include/lbvh.h): a triangle moving along dir without turning, 64 bytes (skip = the ORIGINAL index of
+    // a scene triangle never reported, 0xFFFFFFFF = none; the pads are not read), and its record, 16 bytes: feature = the pair that gave
+    // the time (0 - 2 a moving vertex on the scene face, 3 - 5 a scene vertex on the moving face, 6 + 3m + n moving edge m on scene edge
+    // n at position w of it, 16 | j = intersecting at the start) (TriangleCasts.cs)
+    [StructLayout(LayoutKind.Sequential)]
+    public struct TriRay { public float aX, aY, aZ; public uint skip; public float bX, bY, bZ, tMax; public float cX, cY, cZ; public uint pad0; public float dirX, dirY, dirZ; public uint pad1; }
+    [StructLayout(LayoutKind.Sequential)]
+    public struct TriCastHit { public float t; public uint tri; public uint feature; public float w; }
+
     // lbvh_point_query / lbvh_closest_point (include/lbvh.h): a point with its squared search radius (active iff maxDist2 > 0) and
     // the nearest triangle's record, 16 bytes each (PointQueries.cs)
     [StructLayout(LayoutKind.Sequential)]
@@ -209,6 +218,8 @@ public static class LbvhNative
     [DllImport(Lib)] public static extern int lbvh_capsule_cast_any(IntPtr ctx, IntPtr dCasts, UIntPtr count, ref Scene scene, IntPtr dFlags);
     [DllImport(Lib)] public static extern int lbvh_box_cast(IntPtr ctx, IntPtr dCasts, UIntPtr count, ref Scene scene, IntPtr dHits);
     [DllImport(Lib)] public static extern int lbvh_box_cast_any(IntPtr ctx, IntPtr dCasts, UIntPtr count, ref Scene scene, IntPtr dFlags);
+    [DllImport(Lib)] public static extern int lbvh_triangle_cast(IntPtr ctx, IntPtr dCasts, UIntPtr count, ref Scene scene, IntPtr dHits);
+    [DllImport(Lib)] public static extern int lbvh_triangle_cast_any(IntPtr ctx, IntPtr dCasts, UIntPtr count, ref Scene scene, IntPtr dFlags);
     [DllImport(Lib)] public static extern int lbvh_sphere_cast_all(IntPtr ctx, IntPtr dCasts, UIntPtr count, ref Scene scene, IntPtr dOffsets, IntPtr dHits,
         ulong capacity);
     [DllImport(Lib)] public static extern int lbvh_capsule_cast_all(IntPtr ctx, IntPtr dCasts, UIntPtr count, ref Scene scene, IntPtr dOffsets, IntPtr dHits,

@@ -1198,6 +1198,88 @@ lbvh_status lbvh_triangle_intersections(lbvh_context* ctx, const lbvh_tri_query*
 lbvh_status lbvh_triangle_intersects_any(lbvh_context* ctx, const lbvh_tri_query* d_queries, size_t count, const lbvh_scene* h_scene,
                                          uint32_t* d_flags);
 
+/* A moving triangle: 64 bytes, arrays 16-byte aligned. */
+typedef struct lbvh_tri_ray {
+    float a[3];   uint32_t skip;     /* ORIGINAL index of a scene triangle that is never reported; LBVH_NULL = none */
+    float b[3];   float    t_max;
+    float c[3];   uint32_t _pad0;    /* not read */
+    float dir[3]; uint32_t _pad1;    /* not read */
+} lbvh_tri_ray;
+
+/* lbvh_triangle_cast's record, 16 bytes (the shape of lbvh_hit): the time, the ORIGINAL triangle index, the feature pair that
+ * gave the time and, for an edge against an edge, the position on the scene triangle's edge. */
+typedef struct lbvh_tri_cast_hit { float t; uint32_t tri; uint32_t feature; float w; } lbvh_tri_cast_hit;
+
+#define LBVH_TRI_CAST_START 16u   /* lbvh_tri_cast_hit.feature & 16: the triangles intersect at the start (t = +0) */
+
+/* First contact of `count` moving triangles with the mesh (a "triangle cast": how far a second mesh, a piece of debris or cloth
+ * may move along a direction before it touches the scene; the sweep test of a mesh collider), over the derived traversal scene in
+ * its four-wide form by the walk of lbvh_sphere_cast.  The query triangle moves without turning: its vertices are a + dir*t,
+ * b + dir*t, c + dir*t for 0 <= t < T, T = min(t_max, LBVH_MAX_FLOAT); dir need not be unit length and t is in units of dir.
+ *   Active cast: the nine coordinates of a, b and c are finite, every component of dir is finite, dot(dir, dir) > 0 and t_max > 0
+ *   (all false for a NaN).  An inactive cast is never walked; it gets the miss record {LBVH_MAX_FLOAT, 0, 0, +0}
+ *   (lbvh_triangle_cast) or 0 (lbvh_triangle_cast_any).
+ *   Two tests, in strict fp32, every operation rounded on its own, dot and cross as at lbvh_triangle_intersections:
+ *     pierce(P, D; V, E1, E2) is the edge test of lbvh_triangle_intersections, unchanged, with its u, v and t.
+ *     pierce_quad(P, D; V, E1, E2) is the same arithmetic with the rejections u < 0 || u > 1 and v < 0 || v > 1 in place of
+ *     u < 0 || u > 1 and v < 0 || u + v > 1: the ray against the parallelogram V + E1*u + E2*v, not the triangle.  The rejection
+ *     det < 1e-8 && det > -1e-8 stays.  A rejected test has t = LBVH_MAX_FLOAT in both.
+ *   Time with one scene triangle, v0, e1, e2 as its line of the derived scene holds them, every vector below formed per component
+ *   in fp32 (a negation is exact):
+ *     Start overlap.  If rules (2) and (3) of lbvh_triangle_intersections hold for the query {a, b, c} — the triangle's own box
+ *     overlaps the query's exact box, and one of the six edge tests passes with 0 <= t <= 1 — the time is +0, feature = 16 | j
+ *     with j = 0 .. 5 the first passing test in that call's order, and w = +0.
+ *     Otherwise the time is the least t with 0 <= t && t < LBVH_MAX_FLOAT among fifteen features, taken in this order, a later
+ *     one replacing an earlier one only when strictly less, compared as fp32 values; a NaN never counts; w = +0 except where
+ *     stated.  With E_ab = b - a, E_bc = c - b, E_ca = a - c:
+ *       feature 0, 1, 2        a moving vertex onto the scene face: pierce(X, dir; v0, e1, e2) for X = a, b, c
+ *       feature 3, 4, 5        a scene vertex onto the moving face: pierce(Y, -dir; a, b - a, c - a) for Y = v0, v0 + e1, v0 + e2
+ *       feature 6 + 3*m + n    moving edge m against scene edge n: pierce_quad(P, dir; Q, F, -E) with (P, E) = (a, E_ab), (b, E_bc),
+ *                              (c, E_ca) for m = 0, 1, 2 and (Q, F) = (v0, e1), (v0, e2), (v0 + e1, e2 - e1) for n = 0, 1, 2 (the
+ *                              edge list of lbvh_sphere_cast).  P + E*s + dir*t = Q + F*u is the ray from P meeting the
+ *                              parallelogram Q + F*u - E*s: the test's u is the position on the scene edge and is the record's w,
+ *                              its v the position s on the moving edge.
+ *     No feature with such a t: the triangle has no time.
+ *   What the definition gives and what it leaves out: two triangles that translate relative to each other and start apart first
+ *   touch with a vertex of one on the face of the other or with an edge of one on an edge of the other, and every passing feature
+ *   is a real common point of the two triangles at its t; so in exact arithmetic the least of the fifteen is the time of first
+ *   contact.  Parallel edges and a coplanar approach (an edge sliding into an edge of the same line, a face onto a face) have
+ *   det ~ 0 and fall to the det rejection, as coplanar overlap does at lbvh_triangle_intersections: they are reported only through
+ *   the other features that touch at the same time, if any does.  The time may be -0 only where the arithmetic gives a feature
+ *   t = -0; a start overlap is +0 exactly.
+ *   Candidate: triangle i is a candidate iff its ORIGINAL index is not `skip`, it has a time t_i, t_i < T, the ray (a, dir) passes
+ *   the slab test of the triangle's own box grown by the query's extent relative to a — scene.triangle_aabb[i] with, per axis k
+ *   and h1 = b - a, h2 = c - a,
+ *       min' = min_k - fmaxf(fmaxf(h1_k, h2_k), 0)      max' = max_k - fminf(fminf(h1_k, h2_k), 0),
+ *   one fp32 operation per bound, the slab test of every walker of this library — with entry distance e_i, and !(t_i < e_i).  (a
+ *   is in the grown box exactly when some point of the query's box is in the own box, per axis.)
+ *   lbvh_triangle_cast: d_hits[k] = {t, tri, feature, w} of cast k's candidate with the least t (compared as fp32 values); on
+ *   equal t the lower original triangle index, whatever order the walk meets them in.  The contact point and normal follow from
+ *   the feature: 0 - 2 the moved vertex X + dir*t and the scene face's normal cross(e1, e2); 3 - 5 the scene vertex Y and the
+ *   moving face's normal cross(b - a, c - a); 6 - 14 the point Q + F*w and cross(E, F); each normal turned against dir.  No
+ *   candidate: the miss record, never T.
+ *   lbvh_triangle_cast_any: d_flags[k] = 1 if cast k has any candidate, else 0.  The walk is the same (same near-first order) cut
+ *   off at its first accepted candidate: never more node fetches or triangle tests per cast.
+ * Why the record does not depend on the order of the walk (the argument of lbvh_capsule_cast): lo - max(h1, h2, 0) and
+ * hi - min(h1, h2, 0) are each one operation monotone in lo and hi, and every box of the derived tree is the exact min / max union
+ * of what is below it, so the grown box of an ancestor contains the grown box of everything below it exactly in fp32; slab entries
+ * grow from a box to any box inside it, so e(ancestor) <= e(leaf) <= t for every candidate.  A slot is skipped only if the ray
+ * misses its grown box or its entry is > best, strictly: a subtree skipped that way holds no candidate at or below best.  Nothing
+ * is pruned on a box's exit distance.  `skip`, the start rule and the fifteen features are functions of (cast, triangle) only.
+ * Both need the derived traversal scene (lbvh_build_fast_scene; a stale one is LBVH_ERR_INVALID_ARG), are asynchronous on the
+ * context's stream with no host wait, and use the context's ray scratch: they drop the path tracer's live-path list (see
+ * lbvh_path_bounce).  count == 0 is a no-op.  Rejected: NULL pointers, d_casts or d_hits not 16-byte aligned, d_flags not 4-byte
+ * aligned, count > 2^32 - 1.  Four-wide walk only (lbvh_debug_ray_walker does not apply); lbvh_debug_ray_stack_split,
+ * lbvh_debug_ray_stack_limit, lbvh_ray_stats_target and lbvh_debug_ray_waves apply as to the sphere cast (triangle_tests counts the
+ * triangle lines that reached the narrow phase: `skip` is not counted).  The cost grows with the query (every tree box is larger
+ * by its extent) and each tested triangle costs fifteen Moeller-Trumbore tests, twenty-one where the boxes overlap.  A whole mesh
+ * is one cast per triangle with the same dir, the least record taken by the caller.  Every contact along the way
+ * (lbvh_triangle_cast_all) is out of scope; the record has the shape of lbvh_hit so that lbvh_sort_hit_segments would apply. */
+lbvh_status lbvh_triangle_cast(lbvh_context* ctx, const lbvh_tri_ray* d_casts, size_t count, const lbvh_scene* h_scene,
+                               lbvh_tri_cast_hit* d_hits);
+lbvh_status lbvh_triangle_cast_any(lbvh_context* ctx, const lbvh_tri_ray* d_casts, size_t count, const lbvh_scene* h_scene,
+                                   uint32_t* d_flags);
+
 /* Where a query triangle cuts one scene triangle: 32 bytes, arrays 16-byte aligned; written as two 16-byte stores. */
 typedef struct lbvh_tri_segment {
     float p0[3]; uint32_t tri;     /* one end of the segment; ORIGINAL index of the scene triangle */
@@ -1925,7 +2007,7 @@ lbvh_status lbvh_path_scatter(lbvh_context* ctx, const lbvh_scene* h_scene, cons
  * lbvh_path_bounce on the same d_states / d_hits listed as live (a list kept by the context).  Every library call that writes
  * into those buffers drops the list (lbvh_path_begin, lbvh_trace_rays, a primary trace into any part of d_hits,
  * lbvh_buffer_upload / _fill_u32 / _free), and so does lbvh_trace_forget — and so do lbvh_trace_closest,
- * lbvh_trace_occluded, lbvh_closest_point_query, lbvh_within_distance, lbvh_count_hits, lbvh_point_crossings, lbvh_box_overlaps, lbvh_gather_within_distance, lbvh_k_closest_points, lbvh_trace_k_closest, lbvh_gather_hits, lbvh_sphere_cast, lbvh_sphere_cast_any, lbvh_capsule_cast, lbvh_capsule_cast_any, lbvh_box_cast, lbvh_box_cast_any, lbvh_triangle_intersections, lbvh_triangle_intersects_any, lbvh_triangle_intersection_segments, lbvh_capsule_overlaps, lbvh_capsule_overlaps_any, lbvh_obb_overlaps, lbvh_obb_overlaps_any, lbvh_capsule_contacts, lbvh_capsule_deepest, lbvh_obb_contacts, lbvh_obb_deepest, lbvh_segment_closest_point, lbvh_segment_within_distance, lbvh_triangle_closest_point, lbvh_triangle_within_distance, lbvh_triangle_gather_within_distance, lbvh_sphere_cast_all, lbvh_capsule_cast_all, lbvh_box_cast_all, lbvh_region_overlaps, lbvh_region_overlaps_any, lbvh_region_overlaps_large and lbvh_plane_sections, whatever buffers they are given, since they use the same ray scratch; then every state is scanned again.  The one exception among the query calls:
+ * lbvh_trace_occluded, lbvh_closest_point_query, lbvh_within_distance, lbvh_count_hits, lbvh_point_crossings, lbvh_box_overlaps, lbvh_gather_within_distance, lbvh_k_closest_points, lbvh_trace_k_closest, lbvh_gather_hits, lbvh_sphere_cast, lbvh_sphere_cast_any, lbvh_capsule_cast, lbvh_capsule_cast_any, lbvh_box_cast, lbvh_box_cast_any, lbvh_triangle_cast, lbvh_triangle_cast_any, lbvh_triangle_intersections, lbvh_triangle_intersects_any, lbvh_triangle_intersection_segments, lbvh_capsule_overlaps, lbvh_capsule_overlaps_any, lbvh_obb_overlaps, lbvh_obb_overlaps_any, lbvh_capsule_contacts, lbvh_capsule_deepest, lbvh_obb_contacts, lbvh_obb_deepest, lbvh_segment_closest_point, lbvh_segment_within_distance, lbvh_triangle_closest_point, lbvh_triangle_within_distance, lbvh_triangle_gather_within_distance, lbvh_sphere_cast_all, lbvh_capsule_cast_all, lbvh_box_cast_all, lbvh_region_overlaps, lbvh_region_overlaps_any, lbvh_region_overlaps_large and lbvh_plane_sections, whatever buffers they are given, since they use the same ray scratch; then every state is scanned again.  The one exception among the query calls:
  * lbvh_sort_hit_segments and lbvh_sort_index_segments take no context scratch and keep the live-path list (they drop it only when the
  * buffer they sort is d_hits itself).  What the library
  * cannot see is a write of the CALLER's own (a kernel or hipMemcpy that revives or ends paths, Russian roulette): between two

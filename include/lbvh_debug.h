@@ -68,8 +68,9 @@ lbvh_status lbvh_debug_ray_waves(lbvh_context* ctx, uint32_t max_waves);
  * per (point, direction) pair), and lbvh_k_closest_points (`rays` = active queries; the triangle lines read again for the
  * survivors' u, v at the end of a query are not counted: with k = 1 the three counters equal lbvh_closest_point_query's),
  * and lbvh_trace_k_closest in the same way (`rays` = active rays; with k = 1 the counters equal the four-wide lbvh_trace_closest's),
- * and lbvh_sphere_cast / lbvh_sphere_cast_any, lbvh_capsule_cast / lbvh_capsule_cast_any and lbvh_box_cast / lbvh_box_cast_any
- * (`rays` = active casts; a triangle line counts once, whatever number of its derived triangles or axes is tested), and
+ * and lbvh_sphere_cast / lbvh_sphere_cast_any, lbvh_capsule_cast / lbvh_capsule_cast_any, lbvh_box_cast / lbvh_box_cast_any
+ * and lbvh_triangle_cast / lbvh_triangle_cast_any
+ * (`rays` = active casts; a triangle line counts once, whatever number of its derived triangles, axes or features is tested), and
  * lbvh_capsule_overlaps / lbvh_obb_overlaps and their _any forms in the same way (`rays` = active shapes; the full form adds twice
  * what the count-only form adds) — lbvh_capsule_contacts, lbvh_capsule_deepest, lbvh_obb_contacts and lbvh_obb_deepest likewise, and lbvh_segment_closest_point / lbvh_segment_within_distance and lbvh_triangle_closest_point / lbvh_triangle_within_distance (`rays` = active queries) —, and both walks of
  * lbvh_triangle_gather_within_distance (`rays` = active queries: the full form adds twice what the count-only form adds), and both walks of lbvh_gather_hits (`rays` = active rays: the

@@ -108,6 +108,8 @@ SIGNATURES = {
     "lbvh_capsule_cast_any": (_I32, [_P, _P, _SZ, C.POINTER(Scene), _P]),
     "lbvh_box_cast": (_I32, [_P, _P, _SZ, C.POINTER(Scene), _P]),
     "lbvh_box_cast_any": (_I32, [_P, _P, _SZ, C.POINTER(Scene), _P]),
+    "lbvh_triangle_cast": (_I32, [_P, _P, _SZ, C.POINTER(Scene), _P]),
+    "lbvh_triangle_cast_any": (_I32, [_P, _P, _SZ, C.POINTER(Scene), _P]),
     "lbvh_sphere_cast_all": (_I32, [_P, _P, _SZ, C.POINTER(Scene), _P, _P, C.c_uint64]),
     "lbvh_capsule_cast_all": (_I32, [_P, _P, _SZ, C.POINTER(Scene), _P, _P, C.c_uint64]),
     "lbvh_box_cast_all": (_I32, [_P, _P, _SZ, C.POINTER(Scene), _P, _P, C.c_uint64]),

@@ -2492,6 +2492,229 @@ __global__ __launch_bounds__(64) void triangle_query_wide_kernel(const float4* _
     if (STATS) add_ray_stats(stats, n_queries, n_steps, n_tris);
 }
 
+// ---- triangle casts: where a moving triangle first hits the mesh (lbvh_triangle_cast, include/lbvh.h) ----------------------
+// The header's time of the query triangle (a, b, c) moving along d with one scene triangle line (t0, t1, t2), LBVH_MAX_FLOAT if it
+// has none.  ONE copy of the Moeller-Trumbore body in a loop that is not unrolled, over 21 tests: the six start tests of
+// triangles_pierce (they count only where `start` says the own box overlaps the query's), then the fifteen features.  The ray
+// (P, D) and the target (V, E1, E2) of test j are picked by selects on j from five tables of 3-bit fields; nothing is indexed, so
+// nothing goes to scratch.
+//   P:  0 a   1 b   2 c   3 v0   4 v0 + e1   5 v0 + e2
+//   D:  0 b - a   1 c - b   2 a - c   3 e1   4 e2   5 e2 - e1   6 d   7 -d
+//   V:  0 v0   1 a   2 v0 + e1
+//   E1: 0 e1   1 b - a   2 e2   3 e2 - e1
+//   E2: 0 e2   1 c - a   2 -(b - a)   3 -(c - b)   4 -(a - c)
+// `first` is 0, or 6 where no lane of the wave at this leaf has a start overlap to test (the same for every lane).  Tests 12 .. 20
+// (features 6 .. 14) are the parallelogram mode of ray_triangle_edges; its u is the position on the scene edge.
+__device__ __forceinline__ float triangle_cast_time(float ax, float ay, float az, float bx, float by, float bz, float cx, float cy, float cz,
+                                                    float dx, float dy, float dz, const float4 t0, const float4 t1, const float4 t2,
+                                                    bool start, uint32_t first, uint32_t& feature, float& w)
+{
+    const float abx = bx - ax, aby = by - ay, abz = bz - az;
+    const float bcx = cx - bx, bcy = cy - by, bcz = cz - bz;
+    const float cax = ax - cx, cay = ay - cy, caz = az - cz;
+    const float acx = cx - ax, acy = cy - ay, acz = cz - az;
+    const float v1x = t0.x + t1.x, v1y = t0.y + t1.y, v1z = t0.z + t1.z;
+    const float v2x = t0.x + t2.x, v2y = t0.y + t2.y, v2z = t0.z + t2.z;
+    const float e3x = t2.x - t1.x, e3y = t2.y - t1.y, e3z = t2.z - t1.z;
+    float best = LBVH_MAX_FLOAT;
+    feature = 0u;
+    w = 0.0f;
+#pragma nounroll
+    for (uint32_t j = first; j < 21u; j++) {
+        const uint32_t pi = (uint32_t)(0x2489200b1a223688ull >> (3u * j)) & 7u;
+        const uint32_t di = (uint32_t)(0x6db6db6ffedac688ull >> (3u * j)) & 7u;
+        const uint32_t vi = (uint32_t)(0x2010080248009200ull >> (3u * j)) & 7u;
+        const uint32_t fi = (uint32_t)(0x341a0d0248009200ull >> (3u * j)) & 7u;
+        const uint32_t gi = (uint32_t)(0x491b692248009200ull >> (3u * j)) & 7u;
+#define TRI_CAST_PICK6(i, s0, s1, s2, s3, s4, s5) ((i) == 0u ? (s0) : ((i) == 1u ? (s1) : ((i) == 2u ? (s2) : ((i) == 3u ? (s3) : ((i) == 4u ? (s4) : (s5))))))
+        ray_t r;
+        r.ox = TRI_CAST_PICK6(pi, ax, bx, cx, t0.x, v1x, v2x);
+        r.oy = TRI_CAST_PICK6(pi, ay, by, cy, t0.y, v1y, v2y);
+        r.oz = TRI_CAST_PICK6(pi, az, bz, cz, t0.z, v1z, v2z);
+        r.dx = di == 6u ? dx : (di == 7u ? -dx : TRI_CAST_PICK6(di, abx, bcx, cax, t1.x, t2.x, e3x));
+        r.dy = di == 6u ? dy : (di == 7u ? -dy : TRI_CAST_PICK6(di, aby, bcy, cay, t1.y, t2.y, e3y));
+        r.dz = di == 6u ? dz : (di == 7u ? -dz : TRI_CAST_PICK6(di, abz, bcz, caz, t1.z, t2.z, e3z));
+        r.ix = 0.0f; r.iy = 0.0f; r.iz = 0.0f;           // (not read by the triangle test)
+        const float4 v = make_float4(vi == 0u ? t0.x : (vi == 1u ? ax : v1x), vi == 0u ? t0.y : (vi == 1u ? ay : v1y),
+                                     vi == 0u ? t0.z : (vi == 1u ? az : v1z), 0.0f);
+        const float fx = fi == 0u ? t1.x : (fi == 1u ? abx : (fi == 2u ? t2.x : e3x));
+        const float fy = fi == 0u ? t1.y : (fi == 1u ? aby : (fi == 2u ? t2.y : e3y));
+        const float fz = fi == 0u ? t1.z : (fi == 1u ? abz : (fi == 2u ? t2.z : e3z));
+        const float gx = TRI_CAST_PICK6(gi, t2.x, acx, -abx, -bcx, -cax, 0.0f);
+        const float gy = TRI_CAST_PICK6(gi, t2.y, acy, -aby, -bcy, -cay, 0.0f);
+        const float gz = TRI_CAST_PICK6(gi, t2.z, acz, -abz, -bcz, -caz, 0.0f);
+#undef TRI_CAST_PICK6
+        const bool quad = j >= 12u;
+        float u = 0.0f, vv = 0.0f;
+        const float t = ray_triangle_edges<true>(r, v, fx, fy, fz, gx, gy, gz, u, vv, quad);
+        if (j < 6u) {
+            if (start && 0.0f <= t && t <= 1.0f) { feature = 16u | j; return 0.0f; }      // in overlap at the start: +0, w = +0
+        } else if (t >= 0.0f && t < best) {              // false for a NaN; a rejected test has LBVH_MAX_FLOAT and replaces nothing
+            best = t; feature = j - 6u; w = quad ? u : 0.0f;
+        }
+    }
+    return best;
+}
+
+// cast k into the lane (best_t = T): false (miss record / 0 written, lane stays idle) for an inactive cast
+template <bool ANY>
+__device__ __forceinline__ bool load_triangle_cast(const lbvh_tri_ray* __restrict__ casts, uint32_t k, float4& qa, float4& qb, float4& qc,
+                                                   ray_t& ray, float& best_t, std::conditional_t<ANY, uint32_t, lbvh_tri_cast_hit>* __restrict__ out)
+{
+    const float inf = __builtin_inff();
+    const float4* q = reinterpret_cast<const float4*>(&casts[k]);
+    qa = q[0]; qb = q[1]; qc = q[2];
+    const float4 d = q[3];
+    ray.ox = qa.x; ray.oy = qa.y; ray.oz = qa.z;
+    ray.dx = d.x; ray.dy = d.y; ray.dz = d.z;
+    ray.ix = 1.0f / d.x; ray.iy = 1.0f / d.y; ray.iz = 1.0f / d.z;
+    best_t = fminf(qb.w, LBVH_MAX_FLOAT);                // T: candidates have t < T
+    if (qb.w > 0.0f && fabsf(qa.x) < inf && fabsf(qa.y) < inf && fabsf(qa.z) < inf && fabsf(qb.x) < inf && fabsf(qb.y) < inf &&
+        fabsf(qb.z) < inf && fabsf(qc.x) < inf && fabsf(qc.y) < inf && fabsf(qc.z) < inf && fabsf(d.x) < inf && fabsf(d.y) < inf &&
+        fabsf(d.z) < inf && dot3(d.x, d.y, d.z, d.x, d.y, d.z) > 0.0f) return true;
+    if constexpr (ANY) out[k] = 0u;
+    else reinterpret_cast<float4*>(out)[k] = make_float4(LBVH_MAX_FLOAT, __uint_as_float(0u), __uint_as_float(0u), 0.0f);
+    return false;
+}
+
+// One cast per lane in the frame of box_cast_wide_kernel, the ray that of vertex a.  The four slot boxes are grown by the query's
+// extent relative to a: lo - max(b - a, c - a, 0) and hi - min(b - a, c - a, 0) per axis, one operation per bound and monotone in
+// lo / hi, so a grown box contains the grown boxes of everything below it and the record does not depend on the order of the walk,
+// as there.  A slot is skipped when the ray misses its grown box or enters it beyond best_t, strictly, never on an exit distance.
+// A leaf slot's box before it is grown is the triangle's own: it decides with the query's exact box whether the start tests count.
+// The record is {t, tri, feature, w}; ANY: a flag, the walk cut off at its first candidate (best_t stays T).
+template <bool ANY, bool STATS>
+__global__ __launch_bounds__(64) void triangle_cast_wide_kernel(const lbvh_tri_ray* __restrict__ casts, uint32_t total,
+                                                                const lbvh_wide_node* __restrict__ wide,
+                                                                const lbvh_fast_node* __restrict__ lines,
+                                                                std::conditional_t<ANY, uint32_t, lbvh_tri_cast_hit>* __restrict__ out,
+                                                                uint32_t* __restrict__ deep,     // [gridDim.x][kWideStackDeep][64]
+                                                                uint32_t lds_depth,              // <= kWideStackLds
+                                                                uint32_t deep_cap,               // <= kWideStackDeep
+                                                                uint32_t* __restrict__ fault, lbvh_ray_stats* stats)
+{
+    __shared__ uint32_t s_stack[kWideStackLds][LBVH_WAVE];
+    uint32_t* my_deep = deep + (size_t)blockIdx.x * (kWideStackDeep * LBVH_WAVE) + threadIdx.x;
+    const uint32_t lane = threadIdx.x;
+    const uint32_t run = max((total + gridDim.x - 1) / gridDim.x, 32u);
+    uint32_t next = blockIdx.x * run;
+    if (next >= total) return;
+    const uint32_t end = min(next + run, total);
+    uint32_t n_casts = 0, n_steps = 0, n_tris = 0;
+
+    bool active = false, took = false;
+    uint32_t i = 0;
+    ray_t ray = {};
+    float4 qa = {}, qb = {}, qc = {};                    // the three vertices; qa.w = skip
+    float ux = 0.0f, uy = 0.0f, uz = 0.0f, ox = 0.0f, oy = 0.0f, oz = 0.0f;      // what a box's lower / upper bounds lose
+    float best_t = LBVH_MAX_FLOAT, best_w = 0.0f;
+    uint32_t best_tri = 0, best_feature = 0, sp = 0, node = 0;
+    auto push = [&](uint32_t ref) {
+        if (sp < lds_depth) { s_stack[sp][lane] = ref; sp++; }
+        else if (sp < lds_depth + deep_cap) { my_deep[(sp - lds_depth) * LBVH_WAVE] = ref; sp++; }
+        // a dropped entry would be a silently wrong record: report it, as the ray walkers do (lbvh_debug_ray_stack_limit provokes it)
+        else __hip_atomic_store(fault, LBVH_FAULT_RAY_STACK, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    };
+    for (;;) {
+        const uint64_t idle = __ballot(!active);
+        if (idle != 0 && next < end) {
+            if (!active) {
+                const uint32_t k = next + mbcnt64(idle);
+                if (k < end) {
+                    i = k;
+                    active = load_triangle_cast<ANY>(casts, k, qa, qb, qc, ray, best_t, out);
+                    const float h1x = qb.x - qa.x, h1y = qb.y - qa.y, h1z = qb.z - qa.z;
+                    const float h2x = qc.x - qa.x, h2y = qc.y - qa.y, h2z = qc.z - qa.z;
+                    ux = fmaxf(fmaxf(h1x, h2x), 0.0f); uy = fmaxf(fmaxf(h1y, h2y), 0.0f); uz = fmaxf(fmaxf(h1z, h2z), 0.0f);
+                    ox = fminf(fminf(h1x, h2x), 0.0f); oy = fminf(fminf(h1y, h2y), 0.0f); oz = fminf(fminf(h1z, h2z), 0.0f);
+                    best_tri = 0; best_feature = 0; best_w = 0.0f; took = false;
+                    sp = 0; node = 0;
+                    if (STATS && active) n_casts++;
+                }
+            }
+            next += (uint32_t)__popcll(idle);
+        }
+        if (!__any(active) && next >= end) break;
+        if (active) {
+            if (STATS) n_steps++;
+            const float4* w = reinterpret_cast<const float4*>(&wide[node]);
+            const float4 lox = w[0], loy = w[1], loz = w[2], hix = w[3], hiy = w[4], hiz = w[5];
+            const uint4 ref = reinterpret_cast<const uint4*>(w)[6];
+            float t0, t1, t2, t3;
+            const bool h0 = wide_box(lox.x - ux, loy.x - uy, loz.x - uz, hix.x - ox, hiy.x - oy, hiz.x - oz, ray, t0) && !(t0 > best_t) && ref.x != kWideEmpty;
+            const bool h1 = wide_box(lox.y - ux, loy.y - uy, loz.y - uz, hix.y - ox, hiy.y - oy, hiz.y - oz, ray, t1) && !(t1 > best_t) && ref.y != kWideEmpty;
+            const bool h2 = wide_box(lox.z - ux, loy.z - uy, loz.z - uz, hix.z - ox, hiy.z - oy, hiz.z - oz, ray, t2) && !(t2 > best_t) && ref.z != kWideEmpty;
+            const bool h3 = wide_box(lox.w - ux, loy.w - uy, loz.w - uz, hix.w - ox, hiy.w - oy, hiz.w - oz, ray, t3) && !(t3 > best_t) && ref.w != kWideEmpty;
+            // leaf slots first: a lane's leaves one after the other, every lane's k-th at the same time
+            uint32_t leaves = (h0 && (ref.x >> 31) ? 1u : 0u) | (h1 && (ref.y >> 31) ? 2u : 0u) | (h2 && (ref.z >> 31) ? 4u : 0u) |
+                              (h3 && (ref.w >> 31) ? 8u : 0u);
+            bool found = false;                          // ANY: a candidate was accepted
+            while (leaves != 0u) {
+                const uint32_t k = (uint32_t)__builtin_ctz(leaves);
+                leaves &= leaves - 1u;
+                float4 v0, v1, v2;
+                unpack_fast_triangle(reinterpret_cast<const float4*>(&lines[pick4(ref, k) & 0x7FFFFFFFu]), v0, v1, v2);
+                const uint32_t tri = __float_as_uint(v0.w);
+                if (tri == __float_as_uint(qa.w)) continue;          // `skip`
+                if (STATS) n_tris++;
+                // rule (2) of lbvh_triangle_intersections: the triangle's own box (the slot's, not grown) against the query's exact box
+                const bool start = boxes_overlap(fminf(fminf(qa.x, qb.x), qc.x), fminf(fminf(qa.y, qb.y), qc.y), fminf(fminf(qa.z, qb.z), qc.z),
+                                                 fmaxf(fmaxf(qa.x, qb.x), qc.x), fmaxf(fmaxf(qa.y, qb.y), qc.y), fmaxf(fmaxf(qa.z, qb.z), qc.z),
+                                                 k == 0u ? lox.x : (k == 1u ? lox.y : (k == 2u ? lox.z : lox.w)),
+                                                 k == 0u ? loy.x : (k == 1u ? loy.y : (k == 2u ? loy.z : loy.w)),
+                                                 k == 0u ? loz.x : (k == 1u ? loz.y : (k == 2u ? loz.z : loz.w)),
+                                                 k == 0u ? hix.x : (k == 1u ? hix.y : (k == 2u ? hix.z : hix.w)),
+                                                 k == 0u ? hiy.x : (k == 1u ? hiy.y : (k == 2u ? hiy.z : hiy.w)),
+                                                 k == 0u ? hiz.x : (k == 1u ? hiz.y : (k == 2u ? hiz.z : hiz.w)));
+                uint32_t feature;
+                float fw;
+                const float t = triangle_cast_time(qa.x, qa.y, qa.z, qb.x, qb.y, qb.z, qc.x, qc.y, qc.z, ray.dx, ray.dy, ray.dz, v0, v1, v2,
+                                                   start, __any(start) ? 0u : 6u, feature, fw);
+                const float entry = k == 0u ? t0 : (k == 1u ? t1 : (k == 2u ? t2 : t3));
+                // best_t starts at T and best_tri at 0: t == T is never taken.  Ties go to the lower triangle index.
+                if (hit_counts(t, entry) && (t < best_t || (t == best_t && tri < best_tri))) {
+                    if constexpr (ANY) { found = true; break; }
+                    else { best_t = t; best_tri = tri; best_feature = feature; best_w = fw; took = true; }
+                }
+            }
+            if (ANY && found) {
+                if constexpr (ANY) out[i] = 1u;
+                active = false;
+                continue;
+            }
+            // nodes to enter, ordered by entry distance (the order key of sphere_cast_wide_kernel)
+            constexpr uint32_t none = 0xFFFFFFFFu;
+            uint32_t k0 = h0 && !(ref.x >> 31) && !(t0 > best_t) ? ((__float_as_uint(fmaxf(t0, 0.0f)) & ~3u) | 0u) : none;
+            uint32_t k1 = h1 && !(ref.y >> 31) && !(t1 > best_t) ? ((__float_as_uint(fmaxf(t1, 0.0f)) & ~3u) | 1u) : none;
+            uint32_t k2 = h2 && !(ref.z >> 31) && !(t2 > best_t) ? ((__float_as_uint(fmaxf(t2, 0.0f)) & ~3u) | 2u) : none;
+            uint32_t k3 = h3 && !(ref.w >> 31) && !(t3 > best_t) ? ((__float_as_uint(fmaxf(t3, 0.0f)) & ~3u) | 3u) : none;
+            {   // five compare-exchanges
+                uint32_t a, c;
+                a = min(k0, k1); c = max(k0, k1); k0 = a; k1 = c;
+                a = min(k2, k3); c = max(k2, k3); k2 = a; k3 = c;
+                a = min(k0, k2); c = max(k0, k2); k0 = a; k2 = c;
+                a = min(k1, k3); c = max(k1, k3); k1 = a; k3 = c;
+                a = min(k1, k2); c = max(k1, k2); k1 = a; k2 = c;
+            }
+            if (k0 != none) {
+                if (k3 != none) push(pick4(ref, k3 & 3u));       // farthest first: the nearest waiting sibling is popped first
+                if (k2 != none) push(pick4(ref, k2 & 3u));
+                if (k1 != none) push(pick4(ref, k1 & 3u));
+                node = pick4(ref, k0 & 3u);
+            } else if (sp != 0) {
+                sp--;
+                node = sp < lds_depth ? s_stack[sp][lane] : my_deep[(sp - lds_depth) * LBVH_WAVE];
+            } else {
+                if constexpr (ANY) out[i] = 0u;
+                else reinterpret_cast<float4*>(out)[i] = make_float4(took ? best_t : LBVH_MAX_FLOAT, __uint_as_float(best_tri),
+                                                                     __uint_as_float(best_feature), best_w);
+                active = false;
+            }
+        }
+    }
+    if (STATS) add_ray_stats(stats, n_casts, n_steps, n_tris);
+}
+
 // ---- triangle intersection segments: WHERE a triangle cuts each scene triangle it intersects ------------------------------
 // (lbvh_triangle_intersection_segments, include/lbvh.h).  The frame, the slot test and `skip` of triangle_query_wide_kernel; the
 // count walk of the call IS that kernel's kTriCount form.  This is the fill walk: it writes a 32-byte lbvh_tri_segment where
@@ -4833,6 +5056,7 @@ static lbvh_status launch_per_query(lbvh_context* ctx, const QUERY* d_queries, s
         LBVH_LAUNCH_STATS(ctx, ctx->ray_stats, (box_contact_wide_kernel<kContactDeepest, STATS>), dim3(w.waves), dim3(LBVH_WAVE), d_queries,
                           (uint32_t)count, w.wn, ctx->fast_nodes, (const uint64_t*)nullptr, d_out, (uint64_t)0, w.deep, w.lds, w.deep_cap,
                           ctx->fault_dev, ctx->ray_stats);
+    else if constexpr (std::is_same_v<QUERY, lbvh_tri_ray>) PER_QUERY_WALK(triangle_cast_wide_kernel);
     else PER_QUERY_WALK(box_cast_wide_kernel);
 #undef PER_QUERY_WALK
     LBVH_HIP_TRY(ctx, hipGetLastError());
@@ -4874,16 +5098,17 @@ static lbvh_status distance_queries(lbvh_context* ctx, const QUERY* d_queries, s
     } while (0)
 
 // lbvh_sphere_cast / lbvh_sphere_cast_any (CAST = lbvh_sphere_ray), lbvh_capsule_cast / lbvh_capsule_cast_any (lbvh_capsule_ray),
-// lbvh_box_cast / lbvh_box_cast_any (lbvh_box_ray, HIT = lbvh_box_hit).  The box casts' rejections name the entry point; the
-// sphere and capsule casts keep the text they have had.
+// lbvh_box_cast / lbvh_box_cast_any (lbvh_box_ray, HIT = lbvh_box_hit), lbvh_triangle_cast / lbvh_triangle_cast_any (lbvh_tri_ray,
+// lbvh_tri_cast_hit).  The box and triangle casts' rejections name the entry point; the sphere and capsule casts keep the text
+// they have had.
 template <bool ANY, class CAST, class HIT = lbvh_hit>
 static lbvh_status shape_casts(lbvh_context* ctx, const CAST* d_casts, size_t count, const lbvh_scene* h_scene,
                                std::conditional_t<ANY, uint32_t, HIT>* d_out, const char* who)
 {
-#define CAST_REQUIRE(cond)                                                                          \
-    do {                                                                                            \
-        if constexpr (std::is_same_v<CAST, lbvh_box_ray>) NAMED_REQUIRE(cond);                      \
-        else LBVH_REQUIRE(ctx, cond);                                                               \
+#define CAST_REQUIRE(cond)                                                                                        \
+    do {                                                                                                          \
+        if constexpr (std::is_same_v<CAST, lbvh_box_ray> || std::is_same_v<CAST, lbvh_tri_ray>) NAMED_REQUIRE(cond); \
+        else LBVH_REQUIRE(ctx, cond);                                                                             \
     } while (0)
     if (!ctx) return LBVH_ERR_INVALID_ARG;
     if (count == 0) return LBVH_OK;
@@ -5479,6 +5704,16 @@ lbvh_status lbvh_box_cast(lbvh_context* ctx, const lbvh_box_ray* d_casts, size_t
 lbvh_status lbvh_box_cast_any(lbvh_context* ctx, const lbvh_box_ray* d_casts, size_t count, const lbvh_scene* h_scene, uint32_t* d_flags)
 {
     return shape_casts<true, lbvh_box_ray, lbvh_box_hit>(ctx, d_casts, count, h_scene, d_flags, "lbvh_box_cast_any");
+}
+
+lbvh_status lbvh_triangle_cast(lbvh_context* ctx, const lbvh_tri_ray* d_casts, size_t count, const lbvh_scene* h_scene, lbvh_tri_cast_hit* d_hits)
+{
+    return shape_casts<false, lbvh_tri_ray, lbvh_tri_cast_hit>(ctx, d_casts, count, h_scene, d_hits, "lbvh_triangle_cast");
+}
+
+lbvh_status lbvh_triangle_cast_any(lbvh_context* ctx, const lbvh_tri_ray* d_casts, size_t count, const lbvh_scene* h_scene, uint32_t* d_flags)
+{
+    return shape_casts<true, lbvh_tri_ray, lbvh_tri_cast_hit>(ctx, d_casts, count, h_scene, d_flags, "lbvh_triangle_cast_any");
 }
 
 // the four-wide walk only (lbvh_debug_ray_walker does not apply), the directions by value in the arguments

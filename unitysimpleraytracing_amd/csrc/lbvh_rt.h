@@ -74,8 +74,13 @@ __device__ __forceinline__ float dot3(float ax, float ay, float az, float bx, fl
 
 // RayTriangleIntersection, Raytracing.compute:37-73, from the first vertex and the two edge vectors
 // e1 = v1 - v0, e2 = v2 - v0 (:41-42).  Returns distance (LBVH_MAX_FLOAT = miss).
+// quad (lbvh_triangle_cast's pierce_quad, include/lbvh.h): the same arithmetic against the parallelogram v0 + e1*u + e2*v, whose
+// last rejection is v > 1 where the triangle's is u + v > 1.  QUAD = true compiles the choice in (the mode is then the argument
+// `quad`); every caller but that cast leaves both out and gets the triangle's test, the same instructions as ever.
+template <bool QUAD = false>
 __device__ __forceinline__ float ray_triangle_edges(const ray_t& r, const float4 v0, const float e1x, const float e1y, const float e1z,
-                                                    const float e2x, const float e2y, const float e2z, float& u_out, float& v_out)
+                                                    const float e2x, const float e2y, const float e2z, float& u_out, float& v_out,
+                                                    const bool quad = false)
 {
     // pvec = cross(dir, e2)
     const float px = r.dy * e2z - r.dz * e2y;
@@ -92,7 +97,11 @@ __device__ __forceinline__ float ray_triangle_edges(const ray_t& r, const float4
     const float qy = tz * e1x - tx * e1z;
     const float qz = tx * e1y - ty * e1x;
     const float v = dot3(r.dx, r.dy, r.dz, qx, qy, qz) * inv_det;
-    if (v < 0.0f || u + v > 1.0f) return LBVH_MAX_FLOAT;
+    if constexpr (QUAD) {
+        if (v < 0.0f || (quad ? v : u + v) > 1.0f) return LBVH_MAX_FLOAT;
+    } else {
+        if (v < 0.0f || u + v > 1.0f) return LBVH_MAX_FLOAT;
+    }
     u_out = u;
     v_out = v;
     return dot3(e2x, e2y, e2z, qx, qy, qz) * inv_det;

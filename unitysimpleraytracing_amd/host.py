@@ -117,6 +117,65 @@ def tri_queries_from_mesh(triangles, skip_self=False):
     return out
 
 
+def tri_casts(a, b, c, direction, t_max=np.inf, skip=None):
+    """layouts.TRI_RAY records for triangle_cast / triangle_cast_any: the triangles (a, b, c) (shapes (..., 3), broadcast against
+    each other and against `direction`) moving along `direction` for 0 <= t < t_max (+inf: open), with `skip` (ORIGINAL triangle
+    indices never reported; None: layouts.NULL), rounded to fp32 once."""
+    a, b, c, d = np.broadcast_arrays(*(np.asarray(x, dtype=np.float32) for x in (a, b, c, direction)))
+    out = np.zeros(a.shape[:-1], dtype=L.TRI_RAY)
+    out["a"], out["b"], out["c"], out["dir"], out["t_max"] = a, b, c, d, t_max
+    out["skip"] = L.NULL if skip is None else skip
+    return out if out.ndim else out.reshape(1)
+
+
+def tri_casts_from_mesh(triangles, direction, t_max=np.inf, skip_self=False):
+    """layouts.TRI_RAY records that move another mesh — or the same one — along `direction` (one (3,) vector, or one per triangle):
+    `triangles` is an array of layouts.TRIANGLE, or a tuple (a, b, c) of (n, 3) vertex arrays.  skip_self=True sets skip = each
+    cast's own index (a part of the scene moved against the scene: a triangle never reports itself), else layouts.NULL."""
+    if isinstance(triangles, np.ndarray) and triangles.dtype == L.TRIANGLE:
+        a, b, c = (triangles[k][:, :3] for k in "abc")
+    else:
+        a, b, c = (np.asarray(x, dtype=np.float32).reshape(-1, 3) for x in triangles)
+    return tri_casts(a, b, c, direction, t_max, np.arange(len(a), dtype=np.uint32) if skip_self else None)
+
+
+def triangle_cast_contact(casts, hits, scene_triangles):
+    """The contact point and the unit normal of each lbvh_triangle_cast record, in float64 from the fp32 values: `casts`
+    layouts.TRI_RAY, `hits` layouts.TRI_CAST_HIT, `scene_triangles` the scene as layouts.TRIANGLE or a tuple (a, b, c) of (n, 3)
+    arrays.  -> (points, normals), each (n, 3); NaN rows for a miss record and for a start in overlap (feature & TRI_CAST_START:
+    no single point, no normal).
+        feature 0 - 2: the moved vertex X + dir * t and the scene face's normal cross(e1, e2)
+        feature 3 - 5: the scene vertex and the moving face's normal cross(b - a, c - a)
+        feature 6 - 14: the point Q + F * w on the scene edge and cross(E, F) of the two edges
+    each normal turned against dir, so that it points from the scene to the moving triangle."""
+    if isinstance(scene_triangles, np.ndarray) and scene_triangles.dtype == L.TRIANGLE:
+        sa, sb, sc = (scene_triangles[k][:, :3] for k in "abc")
+    else:
+        sa, sb, sc = scene_triangles
+    casts, hits = np.atleast_1d(casts), np.atleast_1d(hits)
+    f8 = lambda x: np.asarray(x, dtype=np.float64)
+    tri = hits["tri"].astype(np.int64)
+    v0, e1, e2 = f8(sa)[tri], f8(sb)[tri] - f8(sa)[tri], f8(sc)[tri] - f8(sa)[tri]
+    a, b, c, d = (f8(casts[k]) for k in ("a", "b", "c", "dir"))
+    t, w, feature = f8(hits["t"])[:, None], f8(hits["w"])[:, None], hits["feature"].astype(np.int64)
+    moving = np.stack([a, b, c], axis=1)                              # [cast, vertex]
+    scene = np.stack([v0, v0 + e1, v0 + e2], axis=1)
+    rows = np.arange(len(hits))
+    m, n = np.clip((feature - 6) // 3, 0, 2), np.clip((feature - 6) % 3, 0, 2)
+    edge = (np.roll(moving, -1, axis=1) - moving)[rows, m]            # E_ab, E_bc, E_ca
+    q = scene[rows, np.array([0, 0, 1])[n]]
+    f = np.stack([e1, e2, e2 - e1], axis=1)[rows, n]
+    point = np.where((feature < 3)[:, None], moving[rows, np.clip(feature, 0, 2)] + d * t,
+                     np.where((feature < 6)[:, None], scene[rows, np.clip(feature - 3, 0, 2)], q + f * w))
+    normal = np.where((feature < 3)[:, None], np.cross(e1, e2), np.where((feature < 6)[:, None], np.cross(b - a, c - a), np.cross(edge, f)))
+    with np.errstate(all="ignore"):
+        normal = normal / np.linalg.norm(normal, axis=1, keepdims=True)
+        normal = np.where(np.sum(normal * d, axis=1, keepdims=True) > 0, -normal, normal)
+    none = (hits["t"] >= L.MAX_FLOAT) | (feature >= L.TRI_CAST_START)
+    point[none], normal[none] = np.nan, np.nan
+    return point, normal
+
+
 def tri_distance_queries(a, b, c, max_dist2=np.inf, skip=None):
     """layouts.TRI_DISTANCE_QUERY records for triangle_closest_points / triangle_within_distance: the triangles (a, b, c) (shapes
     (..., 3), broadcast against each other) with the given SQUARED search radii (+inf: unbounded) and `skip` (ORIGINAL triangle
@@ -778,6 +837,36 @@ class RaytracingMeshDrawer:
     def box_cast_any(self, casts, flags):
         """1 into the uint32 DataBuffer `flags` for each box of `casts` that touches anything on its way, else 0."""
         self._per_query(N.lib.lbvh_box_cast_any, casts, "BOX_RAY", flags, np.uint32, "casts")
+
+    def triangle_cast(self, casts, hits):
+        """First contact of each moving triangle of the DataBuffer `casts` (layouts.TRI_RAY: a, skip, b, t_max, c, dir, as tri_casts
+        makes them) with the mesh into the DataBuffer `hits` (layouts.TRI_CAST_HIT: t, tri, the feature pair that gave the time and
+        w, the position on the scene edge for an edge against an edge — triangle_cast_contact turns a record into the contact
+        point and normal), over the derived scene.  The triangle is at a + dir * t, b + dir * t, c + dir * t; no contact in
+        [0, t_max): the miss record.  Asynchronous; read with hits.get_data()."""
+        self._per_query(N.lib.lbvh_triangle_cast, casts, "TRI_RAY", hits, L.TRI_CAST_HIT, "casts")
+
+    def triangle_cast_any(self, casts, flags):
+        """1 into the uint32 DataBuffer `flags` for each triangle of `casts` that touches anything on its way, else 0."""
+        self._per_query(N.lib.lbvh_triangle_cast_any, casts, "TRI_RAY", flags, np.uint32, "casts")
+
+    def mesh_sweep(self, other_triangles, direction, t_max=np.inf):
+        """Convenience: how far the whole mesh `other_triangles` (layouts.TRIANGLE, or a tuple (a, b, c) of (n, 3) arrays) may
+        move along `direction` before it touches this mesh: one triangle_cast per triangle and the least record over them, by
+        (t, the moving triangle's index).  Returns (record, index): the layouts.TRI_CAST_HIT record and the index of the moving
+        triangle that gave it; (the miss record, -1) if nothing touches for 0 <= t < t_max.  Blocking."""
+        casts = tri_casts_from_mesh(other_triangles, direction, t_max)
+        buf, hits = DataBuffer(self.ctx, len(casts), L.TRI_RAY), DataBuffer(self.ctx, len(casts), L.TRI_CAST_HIT)
+        try:
+            buf.local[:] = casts
+            buf.sync()
+            self.triangle_cast(buf, hits)
+            got = hits.get_data().copy()
+        finally:
+            buf.dispose()
+            hits.dispose()
+        k = int(np.argmin(got["t"]))                                   # the first least t; a miss record has LBVH_MAX_FLOAT
+        return (got[k], k) if got["t"][k] < L.MAX_FLOAT else (got[k], -1)
 
     def closest_points(self, queries, out):
         """Nearest triangle of each point of the DataBuffer `queries` (layouts.POINT_QUERY: p, max_dist2) into the DataBuffer `out`

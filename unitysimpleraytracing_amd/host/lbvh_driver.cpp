@@ -71,6 +71,11 @@
 //                                                SortIndexSegments, TriangleIntersectsAny; prints the total, how many segments are
 //                                                non-empty, how many flags are set, the sum of (position + 1) * triangle index over
 //                                                the device-sorted list (mod 2^64) and the first segments
+//     lbvh_driver tricast <n> [seed] [t_max]     the 4 096 triangles of cfg1 and n moving triangles (default 6 000; SplitMix64, seed
+//                                                default 5; t_max default 2): per axis the vertex a as `sweep` draws an origin, b's and
+//                                                c's offsets uniform in [-3, 3], then dir = a target in the mesh's box minus a.
+//                                                TriangleCast and TriangleCastAny; prints how many casts touch, how many start in
+//                                                overlap, the number of records per feature, the word sum and the first records
 //     lbvh_driver trisegs <n_queries> [seed]     the mesh and the queries of `tris`; TriangleIntersectionSegments (count only, one
 //                                                8-byte read, fill), every segment sorted by tri on the host; prints the total, how
 //                                                many segments are non-empty, how many records have two different ends, the sum of
@@ -709,6 +714,62 @@ static int tris_main(int argc, char** argv)
         std::printf("%s[%zu", shown++ ? ", " : "", i);
         for (uint64_t j = first; j < last; j++) std::printf(", %u", tris.LocalBuffer()[j]);
         std::printf("]");
+    }
+    std::printf("]}\n");
+    return 0;
+}
+
+// moving triangles against the mesh of `tris`: per cast and axis k the vertex a around the mesh's box (as `sweep` draws an origin),
+// b's and c's offsets uniform in [-3, 3], then dir = a target uniform in the box minus a.  TriangleCast and TriangleCastAny.
+static int tricast_main(int argc, char** argv)
+{
+    const size_t count = argc > 2 ? (size_t)strtoull(argv[2], nullptr, 10) : 6000;
+    uint64_t seed = argc > 3 ? strtoull(argv[3], nullptr, 10) : 5;
+    const float t_max = argc > 4 ? (float)atof(argv[4]) : 2.0f;
+    const std::vector<lbvh_triangle> mesh = random_mesh(4096);
+    float lo[3], hi[3];
+    mesh_box(mesh, lo, hi);
+    lbvh::Context ctx(0);
+    lbvh::RaytracingMeshDrawer drawer(ctx, mesh);
+    drawer.Awake();
+    lbvh::DataBuffer<lbvh_tri_ray> casts(ctx, count);
+    for (auto& c : casts.LocalBuffer()) {
+        std::memset(&c, 0, sizeof c);
+        c.skip = LBVH_NULL;
+        c.t_max = t_max;
+        for (int k = 0; k < 3; k++) {
+            const float grow = 0.25f * (hi[k] - lo[k]);
+            c.a[k] = uniform(seed, lo[k] - grow, hi[k] + grow);
+            c.b[k] = c.a[k] + uniform(seed, -3.0f, 3.0f);
+            c.c[k] = c.a[k] + uniform(seed, -3.0f, 3.0f);
+            c.dir[k] = uniform(seed, lo[k], hi[k]) - c.a[k];
+        }
+    }
+    casts.Sync();
+    lbvh::DataBuffer<lbvh_tri_cast_hit> hits(ctx, count);
+    lbvh::DataBuffer<uint32_t> flags(ctx, count);
+    drawer.TriangleCast(casts, hits);
+    drawer.TriangleCastAny(casts, flags);
+    hits.GetData();
+    flags.GetData();
+    size_t touching = 0, flagged = 0, at_start = 0, by_feature[22] = {};
+    uint64_t words = 0;
+    for (size_t i = 0; i < count; i++) {
+        const lbvh_tri_cast_hit& h = hits.LocalBuffer()[i];
+        words += word_sum(h);
+        touching += h.t < LBVH_MAX_FLOAT;
+        at_start += h.t < LBVH_MAX_FLOAT && (h.feature & LBVH_TRI_CAST_START) != 0;
+        if (h.t < LBVH_MAX_FLOAT && h.feature < 22) by_feature[h.feature]++;
+        flagged += flags.LocalBuffer()[i];
+    }
+    std::printf("{\"triangles\": %zu, \"casts\": %zu, \"t_max\": %.9g, \"touching\": %zu, \"flagged\": %zu, \"at_start\": %zu, "
+                "\"word_sum\": %llu, \"by_feature\": [",
+                mesh.size(), count, t_max, touching, flagged, at_start, (unsigned long long)words);
+    for (int j = 0; j < 22; j++) std::printf("%s%zu", j ? ", " : "", by_feature[j]);
+    std::printf("], \"records\": [");
+    for (size_t i = 0; i < std::min<size_t>(count, 3); i++) {
+        const lbvh_tri_cast_hit& h = hits.LocalBuffer()[i];
+        std::printf("%s[%.9g, %u, %u, %.9g]", i ? ", " : "", h.t, h.tri, h.feature, h.w);
     }
     std::printf("]}\n");
     return 0;
@@ -1582,7 +1643,7 @@ int main(int argc, char** argv)
 {
     static const struct { const char* name; int (*run)(int, char**); } commands[] = {
         {"crossings", crossings_main}, {"points", points_main}, {"knn", knn_main},   {"khits", khits_main}, {"gather", gather_main}, {"sortedhits", sortedhits_main},
-        {"sweep", sweep_main},         {"capsule", capsule_main}, {"boxcast", boxcast_main}, {"castall", castall_main},         {"overlaps", overlaps_main}, {"tris", tris_main}, {"trisegs", trisegs_main}, {"sections", sections_main}, {"shapes", shapes_main}, {"contacts", contacts_main}, {"boxcontacts", boxcontacts_main}, {"segclosest", segclosest_main}, {"triclosest", triclosest_main}, {"triprox", triprox_main}, {"regions", regions_main}, {"rays", rays_main}, {"sort", sort_main},   {"multi", multi_main}};
+        {"sweep", sweep_main},         {"capsule", capsule_main}, {"boxcast", boxcast_main}, {"tricast", tricast_main}, {"castall", castall_main},         {"overlaps", overlaps_main}, {"tris", tris_main}, {"trisegs", trisegs_main}, {"sections", sections_main}, {"shapes", shapes_main}, {"contacts", contacts_main}, {"boxcontacts", boxcontacts_main}, {"segclosest", segclosest_main}, {"triclosest", triclosest_main}, {"triprox", triprox_main}, {"regions", regions_main}, {"rays", rays_main}, {"sort", sort_main},   {"multi", multi_main}};
     try {
         for (const auto& c : commands)
             if (argc > 1 && std::strcmp(argv[1], c.name) == 0) return c.run(argc, argv);

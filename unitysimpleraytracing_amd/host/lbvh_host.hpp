@@ -435,6 +435,23 @@ public:
         const lbvh_scene s = container_->Scene();
         check(ctx_.get(), lbvh_box_cast_any(ctx_.get(), (const lbvh_box_ray*)casts.DeviceBuffer(), casts.Size(), &s, (uint32_t*)flags.DeviceBuffer()));
     }
+    // moving triangles of the caller's own (lbvh_tri_ray: a, skip, b, t_max, c, dir; the triangle is at a + dir * t, b + dir * t,
+    // c + dir * t) over the derived scene: the first contact of each — {t, tri, feature, w}, feature the pair that gave the time
+    // (0 - 2 a moving vertex on the scene face, 3 - 5 a scene vertex on the moving face, 6 + 3m + n moving edge m on scene edge n
+    // at Q + F * w, LBVH_TRI_CAST_START | j: intersecting at the start) — or whether it touches anything on its way, 1 / 0 per
+    // cast (lbvh_triangle_cast / lbvh_triangle_cast_any; asynchronous)
+    void TriangleCast(const DataBuffer<lbvh_tri_ray>& casts, DataBuffer<lbvh_tri_cast_hit>& hits)
+    {
+        if (hits.Size() < casts.Size()) throw Error(LBVH_ERR_INVALID_ARG, "TriangleCast: fewer hit records than casts");
+        const lbvh_scene s = container_->Scene();
+        check(ctx_.get(), lbvh_triangle_cast(ctx_.get(), (const lbvh_tri_ray*)casts.DeviceBuffer(), casts.Size(), &s, (lbvh_tri_cast_hit*)hits.DeviceBuffer()));
+    }
+    void TriangleCastAny(const DataBuffer<lbvh_tri_ray>& casts, DataBuffer<uint32_t>& flags)
+    {
+        if (flags.Size() < casts.Size()) throw Error(LBVH_ERR_INVALID_ARG, "TriangleCastAny: fewer flags than casts");
+        const lbvh_scene s = container_->Scene();
+        check(ctx_.get(), lbvh_triangle_cast_any(ctx_.get(), (const lbvh_tri_ray*)casts.DeviceBuffer(), casts.Size(), &s, (uint32_t*)flags.DeviceBuffer()));
+    }
     // the k nearest triangles of each point (1 <= k <= LBVH_K_CLOSEST_MAX): out[q * k + j] = the j-th nearest of query q, ties by
     // the lower triangle index, padded with none-records; found (optional): the number of real records per row
     // (lbvh_k_closest_points; asynchronous)

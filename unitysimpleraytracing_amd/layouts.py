@@ -54,6 +54,14 @@ assert POINT_QUERY.itemsize == 16 and CLOSEST_POINT.itemsize == 16
 # never a candidate (NULL below, LBVH_NULL: none)
 TRI_QUERY = np.dtype([("a", "<f4", 3), ("skip", "<u4"), ("b", "<f4", 3), ("_pad0", "<u4"), ("c", "<f4", 3), ("_pad1", "<u4")])
 assert TRI_QUERY.itemsize == 48
+# lbvh_triangle_cast / lbvh_triangle_cast_any: a triangle moving along dir without turning (the pads are not read) and its record;
+# feature = which pair gave the time (0 - 2 a moving vertex on the scene face, 3 - 5 a scene vertex on the moving face, 6 + 3m + n
+# moving edge m on scene edge n, w the position on that scene edge), TRI_CAST_START | j = the triangles intersect at the start
+TRI_RAY = np.dtype([("a", "<f4", 3), ("skip", "<u4"), ("b", "<f4", 3), ("t_max", "<f4"), ("c", "<f4", 3), ("_pad0", "<u4"),
+                    ("dir", "<f4", 3), ("_pad1", "<u4")])
+TRI_CAST_HIT = np.dtype([("t", "<f4"), ("tri", "<u4"), ("feature", "<u4"), ("w", "<f4")])
+assert TRI_RAY.itemsize == 64 and TRI_CAST_HIT.itemsize == 16
+TRI_CAST_START = 16
 # lbvh_triangle_intersection_segments: where a query triangle cuts scene triangle `tri` — the two ends p0, p1 and `edges`: bits 0 .. 5
 # which of the six edge tests passed, bits 8 .. 10 the test that gave p0, bits 12 .. 14 the one that gave p1 (host.segment_edges)
 TRI_SEGMENT = np.dtype([("p0", "<f4", 3), ("tri", "<u4"), ("p1", "<f4", 3), ("edges", "<u4")])
