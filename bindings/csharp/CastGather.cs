@@ -3,7 +3,8 @@
 // CSR list: offsets (ulong, count + 1 of them) and 16-byte records, segment q = hits[offsets[q] .. offsets[q + 1]) — LbvhNative.Hit
 // {t, tri, u, v} for spheres and capsules, LbvhNative.BoxHit {t, tri, axis, 0} for boxes: what SphereCasts / CapsuleCasts / BoxCasts
 // would write were that triangle the first.  Twin of host.py / lbvh_host.hpp RaytracingMeshDrawer.sphere_cast_all / SphereCastAll
-// and their capsule and box forms.  The counterparts of Unity's Physics.SphereCastAll, CapsuleCastAll and BoxCastAll, with the
+// and their capsule and box forms.  TriangleCastAll is the same for moving triangles (lbvh_triangle_cast_all; LbvhNative.TriCastHit
+// {t, tri, feature, w}, what TriangleCasts would write), twin of triangle_cast_all / TriangleCastAll.  The counterparts of Unity's Physics.SphereCastAll, CapsuleCastAll and BoxCastAll, with the
 // same promise about order: NONE.  Each record carries its t: SegmentSort.SortHits orders every segment by (t, tri) on the device
 // (box records included: t and tri are the same two words).  The scene is the container's; it must have been built with the derived
 // traversal scene (the drawer's Awake does that).
@@ -45,6 +46,17 @@ public sealed class CastGather
         Check(casts, 80, offsets, hits, count);
         LbvhNative.Scene scene = _container.NativeScene();
         LbvhNative.Check(casts.Context, LbvhNative.lbvh_box_cast_all(casts.Context, casts.Pointer, (UIntPtr)(ulong)count, ref scene, offsets.Pointer,
+            hits == null ? IntPtr.Zero : hits.Pointer, hits == null ? 0UL : (ulong)hits.count));
+    }
+
+    /// The same for moving triangles (LbvhNative.TriRay, stride 64, as TriangleCasts takes them; lbvh_triangle_cast_all); `hits`
+    /// holds LbvhNative.TriCastHit records (stride 16): {t, tri, feature, w} of every triangle touched, `skip` never among them.
+    /// SegmentSort.SortHits takes these records too: feature and w travel with their record.
+    public void TriangleCastAll(NativeBuffer casts, NativeBuffer offsets, NativeBuffer hits, int count)
+    {
+        Check(casts, 64, offsets, hits, count);
+        LbvhNative.Scene scene = _container.NativeScene();
+        LbvhNative.Check(casts.Context, LbvhNative.lbvh_triangle_cast_all(casts.Context, casts.Pointer, (UIntPtr)(ulong)count, ref scene, offsets.Pointer,
             hits == null ? IntPtr.Zero : hits.Pointer, hits == null ? 0UL : (ulong)hits.count));
     }
 

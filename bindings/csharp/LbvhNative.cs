@@ -226,6 +226,8 @@ public static class LbvhNative
         ulong capacity);
     [DllImport(Lib)] public static extern int lbvh_box_cast_all(IntPtr ctx, IntPtr dCasts, UIntPtr count, ref Scene scene, IntPtr dOffsets, IntPtr dHits,
         ulong capacity);
+    [DllImport(Lib)] public static extern int lbvh_triangle_cast_all(IntPtr ctx, IntPtr dCasts, UIntPtr count, ref Scene scene, IntPtr dOffsets, IntPtr dHits,
+        ulong capacity);
     [DllImport(Lib)] public static extern int lbvh_triangle_intersections(IntPtr ctx, IntPtr dQueries, UIntPtr count, ref Scene scene, IntPtr dOffsets,
         IntPtr dTris, ulong capacity);
     [DllImport(Lib)] public static extern int lbvh_triangle_intersects_any(IntPtr ctx, IntPtr dQueries, UIntPtr count, ref Scene scene, IntPtr dFlags);

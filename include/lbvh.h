@@ -1280,6 +1280,62 @@ lbvh_status lbvh_triangle_cast(lbvh_context* ctx, const lbvh_tri_ray* d_casts, s
 lbvh_status lbvh_triangle_cast_any(lbvh_context* ctx, const lbvh_tri_ray* d_casts, size_t count, const lbvh_scene* h_scene,
                                    uint32_t* d_flags);
 
+/* Every triangle a moving triangle touches, as a CSR list — the "all" form of lbvh_triangle_cast / lbvh_triangle_cast_any, what
+ * lbvh_sphere_cast_all is to lbvh_sphere_cast (a sweep-test-all of a mesh collider: filter triggers or the body's own triangles by
+ * index, debris that cuts through several sheets, every pair of a cloth step that comes into contact during the step).  The call
+ * that the block above names as out of scope now exists; this is it.  Over the same scene by the four-wide walk of the cast, in
+ * the count -> device-side scan -> fill shape of lbvh_gather_hits.  Nothing below is new arithmetic: every term is the one
+ * defined at lbvh_triangle_cast.
+ *   Active cast, T = min(t_max, LBVH_MAX_FLOAT), `skip`, the time with one scene triangle (the start overlap by rules (2) and (3)
+ *   of lbvh_triangle_intersections, else the least of the fifteen features), the triangle's own grown box, its entry distance e_i
+ *   and the candidate rule are exactly lbvh_triangle_cast's: triangle i is a candidate iff its ORIGINAL index is not `skip`, it
+ *   has a time t_i, t_i < T, the ray (a, dir) passes the slab test of the triangle's own grown box, and !(t_i < e_i).  A NaN never
+ *   counts; an inactive cast has an empty segment and is never walked.
+ * Output: lbvh_gather_hits' contract, verbatim as at lbvh_sphere_cast_all.
+ *   d_offsets: count + 1 words of 64 bits.  d_offsets[q] = the number of candidates of casts 0 .. q-1, d_offsets[count] = the
+ *   total M.  Always written in full, whatever `capacity` is.
+ *   d_hits, `capacity` records of 16 bytes: segment q = d_hits[d_offsets[q] .. d_offsets[q+1]) = one record per candidate of cast
+ *   q, each exactly once: the {t, tri, feature, w} that lbvh_triangle_cast would write were that candidate the nearest.
+ *   THE ORDER INSIDE A SEGMENT IS THE WALK'S AND IS NOT PART OF THE CONTRACT.  Sort a segment by (t, tri) if an order is needed —
+ *   two candidates of a cast never share a triangle index, so that order is canonical.  lbvh_sort_hit_segments applies unchanged
+ *   and puts every segment into that order on the device, in place: t and tri are words 0 and 1 as in lbvh_hit, and feature and w
+ *   travel with their record as u and v do — pass the records to it as lbvh_hit*.
+ *   Overflow: no record at index >= capacity is ever written; every segment with d_offsets[q+1] <= capacity is complete; records
+ *   below `capacity` that belong to a segment which does not fit are unspecified.  The call never waits on the host and returns
+ *   LBVH_OK in both cases: the caller reads d_offsets[count] (one 8-byte download) to learn whether everything fitted.
+ *   Count-only form: capacity == 0 writes the offsets and walks once (d_hits may be NULL); otherwise the scene is walked twice
+ *   (count, device-side scan, fill).  d_hits == NULL with capacity > 0 is LBVH_ERR_INVALID_ARG.
+ * Hence, for every cast q with m = d_offsets[q+1] - d_offsets[q] records:
+ *   m >= 1 exactly when lbvh_triangle_cast_any gives 1;
+ *   the least record of segment q by (t as an fp32 value, tri) is lbvh_triangle_cast's record word for word, and when m == 0
+ *   that call writes the miss record {LBVH_MAX_FLOAT, 0, 0, +0};
+ *   a triangle that lbvh_triangle_intersections lists for {a, b, c, skip} is in the segment with t == +0 and
+ *   feature & LBVH_TRI_CAST_START wherever the grown-box rule admits it.  That last relation can fail in the definition itself:
+ *   the intersection call has no grown box and no !(t_i < e_i) — a start overlap has t = +0, and where fp32 puts the entry of the
+ *   triangle's own grown box above 0, or makes the ray miss that box, the pair is no candidate of either cast form
+ *   (tests/test_triangle_cast.py documents this for the first-contact call; DESIGN.md records the count on the test sets).
+ * Why the list does not depend on the walk: the grown-box containment argument of lbvh_triangle_cast with the fixed bound T in
+ * place of best.  lo - max(h1, h2, 0) and hi - min(h1, h2, 0) are monotone, so the grown box of an ancestor contains the grown box
+ * of everything below it exactly in fp32, slab entries grow from a box to any box inside it, and every ancestor of a candidate's
+ * leaf passes its slab test with entry <= e <= t < T; the walk skips only boxes that the ray misses or whose entry is > T.  The
+ * bound is T from the first step to the last: nothing shrinks and nothing is pruned on a box's exit distance.  Each triangle is
+ * exactly one leaf, so each candidate is met exactly once.  The count walk and the fill walk are the same kernel making the same
+ * decisions, so a segment never outgrows its slot.
+ * Needs the derived traversal scene (lbvh_build_fast_scene; a stale one is LBVH_ERR_INVALID_ARG), is asynchronous on the
+ * context's stream with no host wait, and uses the context's ray scratch: it drops the path tracer's live-path list (see
+ * lbvh_path_bounce); a failed growth of that scratch is LBVH_ERR_OUT_OF_MEMORY with nothing written.  count == 0 is a no-op:
+ * nothing is enqueued and no buffer is touched, d_offsets[0] included.  Rejected, the message naming lbvh_triangle_cast_all: NULL
+ * ctx / d_casts / h_scene / d_offsets, d_casts or d_hits not 16-byte aligned, d_offsets not 8-byte aligned, count > 2^32 - 1.
+ * Four-wide walk only (lbvh_debug_ray_walker does not apply); lbvh_debug_ray_waves, lbvh_debug_ray_stack_split,
+ * lbvh_debug_ray_stack_limit and lbvh_ray_stats_target apply as to lbvh_sphere_cast_all (the stats of both walks are added: the
+ * full form reports twice the count-only form's; triangle_tests counts the triangle lines that reached the narrow phase: `skip`
+ * is not counted).
+ * One cast per lane.  The cost grows with the swept volume — every grown box the motion crosses before T is opened — and every
+ * tested triangle costs fifteen Moeller-Trumbore tests, twenty-one where the boxes overlap, in each of the two walks: give a move
+ * its real length as t_max, not +inf. */
+lbvh_status lbvh_triangle_cast_all(lbvh_context* ctx, const lbvh_tri_ray* d_casts, size_t count, const lbvh_scene* h_scene,
+                                   uint64_t* d_offsets, lbvh_tri_cast_hit* d_hits, uint64_t capacity);
+
 /* Where a query triangle cuts one scene triangle: 32 bytes, arrays 16-byte aligned; written as two 16-byte stores. */
 typedef struct lbvh_tri_segment {
     float p0[3]; uint32_t tri;     /* one end of the segment; ORIGINAL index of the scene triangle */
@@ -2007,7 +2063,7 @@ lbvh_status lbvh_path_scatter(lbvh_context* ctx, const lbvh_scene* h_scene, cons
  * lbvh_path_bounce on the same d_states / d_hits listed as live (a list kept by the context).  Every library call that writes
  * into those buffers drops the list (lbvh_path_begin, lbvh_trace_rays, a primary trace into any part of d_hits,
  * lbvh_buffer_upload / _fill_u32 / _free), and so does lbvh_trace_forget — and so do lbvh_trace_closest,
- * lbvh_trace_occluded, lbvh_closest_point_query, lbvh_within_distance, lbvh_count_hits, lbvh_point_crossings, lbvh_box_overlaps, lbvh_gather_within_distance, lbvh_k_closest_points, lbvh_trace_k_closest, lbvh_gather_hits, lbvh_sphere_cast, lbvh_sphere_cast_any, lbvh_capsule_cast, lbvh_capsule_cast_any, lbvh_box_cast, lbvh_box_cast_any, lbvh_triangle_cast, lbvh_triangle_cast_any, lbvh_triangle_intersections, lbvh_triangle_intersects_any, lbvh_triangle_intersection_segments, lbvh_capsule_overlaps, lbvh_capsule_overlaps_any, lbvh_obb_overlaps, lbvh_obb_overlaps_any, lbvh_capsule_contacts, lbvh_capsule_deepest, lbvh_obb_contacts, lbvh_obb_deepest, lbvh_segment_closest_point, lbvh_segment_within_distance, lbvh_triangle_closest_point, lbvh_triangle_within_distance, lbvh_triangle_gather_within_distance, lbvh_sphere_cast_all, lbvh_capsule_cast_all, lbvh_box_cast_all, lbvh_region_overlaps, lbvh_region_overlaps_any, lbvh_region_overlaps_large and lbvh_plane_sections, whatever buffers they are given, since they use the same ray scratch; then every state is scanned again.  The one exception among the query calls:
+ * lbvh_trace_occluded, lbvh_closest_point_query, lbvh_within_distance, lbvh_count_hits, lbvh_point_crossings, lbvh_box_overlaps, lbvh_gather_within_distance, lbvh_k_closest_points, lbvh_trace_k_closest, lbvh_gather_hits, lbvh_sphere_cast, lbvh_sphere_cast_any, lbvh_capsule_cast, lbvh_capsule_cast_any, lbvh_box_cast, lbvh_box_cast_any, lbvh_triangle_cast, lbvh_triangle_cast_any, lbvh_triangle_intersections, lbvh_triangle_intersects_any, lbvh_triangle_intersection_segments, lbvh_capsule_overlaps, lbvh_capsule_overlaps_any, lbvh_obb_overlaps, lbvh_obb_overlaps_any, lbvh_capsule_contacts, lbvh_capsule_deepest, lbvh_obb_contacts, lbvh_obb_deepest, lbvh_segment_closest_point, lbvh_segment_within_distance, lbvh_triangle_closest_point, lbvh_triangle_within_distance, lbvh_triangle_gather_within_distance, lbvh_sphere_cast_all, lbvh_capsule_cast_all, lbvh_box_cast_all, lbvh_triangle_cast_all, lbvh_region_overlaps, lbvh_region_overlaps_any, lbvh_region_overlaps_large and lbvh_plane_sections, whatever buffers they are given, since they use the same ray scratch; then every state is scanned again.  The one exception among the query calls:
  * lbvh_sort_hit_segments and lbvh_sort_index_segments take no context scratch and keep the live-path list (they drop it only when the
  * buffer they sort is d_hits itself).  What the library
  * cannot see is a write of the CALLER's own (a kernel or hipMemcpy that revives or ends paths, Russian roulette): between two

@@ -113,6 +113,7 @@ SIGNATURES = {
     "lbvh_sphere_cast_all": (_I32, [_P, _P, _SZ, C.POINTER(Scene), _P, _P, C.c_uint64]),
     "lbvh_capsule_cast_all": (_I32, [_P, _P, _SZ, C.POINTER(Scene), _P, _P, C.c_uint64]),
     "lbvh_box_cast_all": (_I32, [_P, _P, _SZ, C.POINTER(Scene), _P, _P, C.c_uint64]),
+    "lbvh_triangle_cast_all": (_I32, [_P, _P, _SZ, C.POINTER(Scene), _P, _P, C.c_uint64]),
     "lbvh_triangle_intersections": (_I32, [_P, _P, _SZ, C.POINTER(Scene), _P, _P, C.c_uint64]),
     "lbvh_triangle_intersects_any": (_I32, [_P, _P, _SZ, C.POINTER(Scene), _P]),
     "lbvh_triangle_intersection_segments": (_I32, [_P, _P, _SZ, C.POINTER(Scene), _P, _P, C.c_uint64]),

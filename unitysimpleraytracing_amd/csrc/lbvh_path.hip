@@ -2556,8 +2556,9 @@ __device__ __forceinline__ float triangle_cast_time(float ax, float ay, float az
     return best;
 }
 
-// cast k into the lane (best_t = T): false (miss record / 0 written, lane stays idle) for an inactive cast
-template <bool ANY>
+// cast k into the lane (best_t = T): false (miss record / 0 written, lane stays idle) for an inactive cast; !RECORD (the cast-all
+// walks): nothing is written
+template <bool ANY, bool RECORD = true>
 __device__ __forceinline__ bool load_triangle_cast(const lbvh_tri_ray* __restrict__ casts, uint32_t k, float4& qa, float4& qb, float4& qc,
                                                    ray_t& ray, float& best_t, std::conditional_t<ANY, uint32_t, lbvh_tri_cast_hit>* __restrict__ out)
 {
@@ -2572,7 +2573,8 @@ __device__ __forceinline__ bool load_triangle_cast(const lbvh_tri_ray* __restric
     if (qb.w > 0.0f && fabsf(qa.x) < inf && fabsf(qa.y) < inf && fabsf(qa.z) < inf && fabsf(qb.x) < inf && fabsf(qb.y) < inf &&
         fabsf(qb.z) < inf && fabsf(qc.x) < inf && fabsf(qc.y) < inf && fabsf(qc.z) < inf && fabsf(d.x) < inf && fabsf(d.y) < inf &&
         fabsf(d.z) < inf && dot3(d.x, d.y, d.z, d.x, d.y, d.z) > 0.0f) return true;
-    if constexpr (ANY) out[k] = 0u;
+    if constexpr (!RECORD) return false;
+    else if constexpr (ANY) out[k] = 0u;
     else reinterpret_cast<float4*>(out)[k] = make_float4(LBVH_MAX_FLOAT, __uint_as_float(0u), __uint_as_float(0u), 0.0f);
     return false;
 }
@@ -2708,6 +2710,133 @@ __global__ __launch_bounds__(64) void triangle_cast_wide_kernel(const lbvh_tri_r
                 if constexpr (ANY) out[i] = 0u;
                 else reinterpret_cast<float4*>(out)[i] = make_float4(took ? best_t : LBVH_MAX_FLOAT, __uint_as_float(best_tri),
                                                                      __uint_as_float(best_feature), best_w);
+                active = false;
+            }
+        }
+    }
+    if (STATS) add_ray_stats(stats, n_casts, n_steps, n_tris);
+}
+
+// ---- every triangle a moving triangle touches, as a CSR list (lbvh_triangle_cast_all, include/lbvh.h) -----------------------
+// The frame of cast_gather_wide_kernel (count walk, scan, fill walk: the same kernel, the same decisions; persistent waves, lane
+// refill with the write position reloaded, LDS + device-memory stack, leaf slots first, the first passing inner slot entered and
+// the others pushed) around the arithmetic of triangle_cast_wide_kernel: load_triangle_cast's activity test and T, the grown box
+// lo - u / hi - o against the FIXED bound T, `skip` before the stats count, the start flag from the slot's own box, and
+// triangle_cast_time.  A candidate is what the cast kernel accepts while its best is still (T, 0): hit_counts(t, entry) && t < T.
+// triangle_cast_time gives the whole record {t, tri, feature, w} in both walks; the count walk leaves feature and w unread.
+// A kernel of its own, not a fourth shape of cast_gather_wide_kernel: the cast record's type is spelled in that kernel's symbols,
+// and the walk as a device function under two entries changed the instructions of six of its twelve instantiations (DESIGN).
+template <bool FILL, bool STATS>
+__global__ __launch_bounds__(64) void triangle_cast_gather_wide_kernel(const lbvh_tri_ray* __restrict__ casts, uint32_t total,
+                                                                       const lbvh_wide_node* __restrict__ wide,
+                                                                       const lbvh_fast_node* __restrict__ lines,
+                                                                       uint32_t* __restrict__ counts,            // !FILL: candidates of cast k
+                                                                       const uint64_t* __restrict__ offsets,     // FILL: where segment k starts
+                                                                       float4* __restrict__ hits, uint64_t capacity,     // lbvh_tri_cast_hit records
+                                                                       uint32_t* __restrict__ deep,     // [gridDim.x][kWideStackDeep][64]
+                                                                       uint32_t lds_depth,              // <= kWideStackLds
+                                                                       uint32_t deep_cap,               // <= kWideStackDeep
+                                                                       uint32_t* __restrict__ fault, lbvh_ray_stats* stats)
+{
+    __shared__ uint32_t s_stack[kWideStackLds][LBVH_WAVE];
+    uint32_t* my_deep = deep + (size_t)blockIdx.x * (kWideStackDeep * LBVH_WAVE) + threadIdx.x;
+    const uint32_t lane = threadIdx.x;
+    const uint32_t run = max((total + gridDim.x - 1) / gridDim.x, 32u);
+    uint32_t next = blockIdx.x * run;
+    if (next >= total) return;
+    const uint32_t end = min(next + run, total);
+    uint32_t n_casts = 0, n_steps = 0, n_tris = 0;
+
+    bool active = false;
+    uint32_t i = 0;
+    ray_t ray = {};
+    float4 qa = {}, qb = {}, qc = {};                    // the three vertices; qa.w = skip
+    float ux = 0.0f, uy = 0.0f, uz = 0.0f, ox = 0.0f, oy = 0.0f, oz = 0.0f;      // what a box's lower / upper bounds lose
+    float T = LBVH_MAX_FLOAT;
+    uint32_t n_found = 0, sp = 0, node = 0;
+    uint64_t pos = 0;                                    // FILL: where this lane's next record goes
+    auto push = [&](uint32_t ref) {
+        if (sp < lds_depth) { s_stack[sp][lane] = ref; sp++; }
+        else if (sp < lds_depth + deep_cap) { my_deep[(sp - lds_depth) * LBVH_WAVE] = ref; sp++; }
+        // a dropped entry would be a silently short segment: report it, as the other walkers do (lbvh_debug_ray_stack_limit provokes it)
+        else __hip_atomic_store(fault, LBVH_FAULT_RAY_STACK, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    };
+    for (;;) {
+        const uint64_t idle = __ballot(!active);
+        if (idle != 0 && next < end) {
+            if (!active) {
+                const uint32_t k = next + mbcnt64(idle);
+                if (k < end) {
+                    i = k;
+                    active = load_triangle_cast<false, false>(casts, k, qa, qb, qc, ray, T, nullptr);
+                    const float h1x = qb.x - qa.x, h1y = qb.y - qa.y, h1z = qb.z - qa.z;
+                    const float h2x = qc.x - qa.x, h2y = qc.y - qa.y, h2z = qc.z - qa.z;
+                    ux = fmaxf(fmaxf(h1x, h2x), 0.0f); uy = fmaxf(fmaxf(h1y, h2y), 0.0f); uz = fmaxf(fmaxf(h1z, h2z), 0.0f);
+                    ox = fminf(fminf(h1x, h2x), 0.0f); oy = fminf(fminf(h1y, h2y), 0.0f); oz = fminf(fminf(h1z, h2z), 0.0f);
+                    sp = 0; node = 0;
+                    if constexpr (FILL) { if (active) pos = offsets[k]; }      // (reloaded at every refill: a lane serves many casts)
+                    else { n_found = 0; if (!active) counts[k] = 0u; }
+                    if (STATS && active) n_casts++;
+                }
+            }
+            next += (uint32_t)__popcll(idle);
+        }
+        if (!__any(active) && next >= end) break;
+        if (active) {
+            if (STATS) n_steps++;
+            const float4* w = reinterpret_cast<const float4*>(&wide[node]);
+            const float4 lox = w[0], loy = w[1], loz = w[2], hix = w[3], hiy = w[4], hiz = w[5];
+            const uint4 ref = reinterpret_cast<const uint4*>(w)[6];
+            float t0, t1, t2, t3;
+            const bool h0 = wide_box(lox.x - ux, loy.x - uy, loz.x - uz, hix.x - ox, hiy.x - oy, hiz.x - oz, ray, t0) && !(t0 > T) && ref.x != kWideEmpty;
+            const bool h1 = wide_box(lox.y - ux, loy.y - uy, loz.y - uz, hix.y - ox, hiy.y - oy, hiz.y - oz, ray, t1) && !(t1 > T) && ref.y != kWideEmpty;
+            const bool h2 = wide_box(lox.z - ux, loy.z - uy, loz.z - uz, hix.z - ox, hiy.z - oy, hiz.z - oz, ray, t2) && !(t2 > T) && ref.z != kWideEmpty;
+            const bool h3 = wide_box(lox.w - ux, loy.w - uy, loz.w - uz, hix.w - ox, hiy.w - oy, hiz.w - oz, ray, t3) && !(t3 > T) && ref.w != kWideEmpty;
+            const uint32_t hit = (h0 ? 1u : 0u) | (h1 ? 2u : 0u) | (h2 ? 4u : 0u) | (h3 ? 8u : 0u);
+            const uint32_t leaf = (ref.x >> 31) | ((ref.y >> 31) << 1) | ((ref.z >> 31) << 2) | ((ref.w >> 31) << 3);
+            uint32_t leaves = hit & leaf, inner = hit & ~leaf;
+            while (leaves != 0u) {
+                const uint32_t k = (uint32_t)__builtin_ctz(leaves);
+                leaves &= leaves - 1u;
+                float4 v0, v1, v2;
+                unpack_fast_triangle(reinterpret_cast<const float4*>(&lines[pick4(ref, k) & 0x7FFFFFFFu]), v0, v1, v2);
+                if (__float_as_uint(v0.w) == __float_as_uint(qa.w)) continue;      // `skip`
+                if (STATS) n_tris++;
+                // rule (2) of lbvh_triangle_intersections: the triangle's own box (the slot's, not grown) against the query's exact box
+                const bool start = boxes_overlap(fminf(fminf(qa.x, qb.x), qc.x), fminf(fminf(qa.y, qb.y), qc.y), fminf(fminf(qa.z, qb.z), qc.z),
+                                                 fmaxf(fmaxf(qa.x, qb.x), qc.x), fmaxf(fmaxf(qa.y, qb.y), qc.y), fmaxf(fmaxf(qa.z, qb.z), qc.z),
+                                                 k == 0u ? lox.x : (k == 1u ? lox.y : (k == 2u ? lox.z : lox.w)),
+                                                 k == 0u ? loy.x : (k == 1u ? loy.y : (k == 2u ? loy.z : loy.w)),
+                                                 k == 0u ? loz.x : (k == 1u ? loz.y : (k == 2u ? loz.z : loz.w)),
+                                                 k == 0u ? hix.x : (k == 1u ? hix.y : (k == 2u ? hix.z : hix.w)),
+                                                 k == 0u ? hiy.x : (k == 1u ? hiy.y : (k == 2u ? hiy.z : hiy.w)),
+                                                 k == 0u ? hiz.x : (k == 1u ? hiz.y : (k == 2u ? hiz.z : hiz.w)));
+                uint32_t feature;
+                float fw;
+                const float t = triangle_cast_time(qa.x, qa.y, qa.z, qb.x, qb.y, qb.z, qc.x, qc.y, qc.z, ray.dx, ray.dy, ray.dz, v0, v1, v2,
+                                                   start, __any(start) ? 0u : 6u, feature, fw);
+                const float entry = k == 0u ? t0 : (k == 1u ? t1 : (k == 2u ? t2 : t3));
+                if (hit_counts(t, entry) && t < T) {
+                    if constexpr (FILL) {
+                        if (pos < capacity) hits[pos] = make_float4(t, v0.w, __uint_as_float(feature), fw);      // never at or beyond the capacity
+                        pos++;
+                    } else {
+                        n_found++;
+                    }
+                }
+            }
+            if (inner != 0u) {
+                node = pick4(ref, (uint32_t)__builtin_ctz(inner));
+                inner &= inner - 1u;
+                while (inner != 0u) {
+                    push(pick4(ref, (uint32_t)__builtin_ctz(inner)));
+                    inner &= inner - 1u;
+                }
+            } else if (sp != 0) {
+                sp--;
+                node = sp < lds_depth ? s_stack[sp][lane] : my_deep[(sp - lds_depth) * LBVH_WAVE];
+            } else {
+                if constexpr (!FILL) counts[i] = n_found;
                 active = false;
             }
         }
@@ -5311,6 +5440,35 @@ static lbvh_status cast_gathers(lbvh_context* ctx, const cast_ray<SHAPE>* d_cast
         });
 }
 
+// lbvh_triangle_cast_all: cast_gathers with the triangle's own kernel (triangle_cast_gather_wide_kernel says why it has one)
+static lbvh_status triangle_cast_gathers(lbvh_context* ctx, const lbvh_tri_ray* d_casts, size_t count, const lbvh_scene* h_scene, uint64_t* d_offsets,
+                                         lbvh_tri_cast_hit* d_hits, uint64_t capacity, const char* who)
+{
+    static_assert(sizeof(lbvh_tri_cast_hit) == sizeof(float4), "a cast-all record is one float4");
+    if (!ctx) return LBVH_ERR_INVALID_ARG;
+    if (count == 0) return LBVH_OK;
+    NAMED_REQUIRE(d_casts != nullptr && h_scene != nullptr && d_offsets != nullptr);
+    NAMED_REQUIRE(d_hits != nullptr || capacity == 0);
+    NAMED_REQUIRE(((uintptr_t)d_casts & 15) == 0 && ((uintptr_t)d_offsets & 7) == 0 && ((uintptr_t)d_hits & 15) == 0);
+    NAMED_REQUIRE(count <= 0xFFFFFFFFull);
+    walk_launch w;
+    const lbvh_status rc = begin_walk(ctx, h_scene, count, who, true, &w);
+    if (rc != LBVH_OK) return rc;
+    const uint32_t total = (uint32_t)count;
+    return csr_query(
+        ctx, count, d_offsets, capacity,
+        [&](uint32_t* counts) {
+            LBVH_LAUNCH_STATS(ctx, ctx->ray_stats, (triangle_cast_gather_wide_kernel<false, STATS>), dim3(w.waves), dim3(LBVH_WAVE), d_casts, total, w.wn,
+                              ctx->fast_nodes, counts, (const uint64_t*)nullptr, (float4*)nullptr, (uint64_t)0, w.deep, w.lds, w.deep_cap, ctx->fault_dev,
+                              ctx->ray_stats);
+        },
+        [&] {
+            LBVH_LAUNCH_STATS(ctx, ctx->ray_stats, (triangle_cast_gather_wide_kernel<true, STATS>), dim3(w.waves), dim3(LBVH_WAVE), d_casts, total, w.wn,
+                              ctx->fast_nodes, (uint32_t*)nullptr, (const uint64_t*)d_offsets, (float4*)d_hits, capacity, w.deep, w.lds, w.deep_cap,
+                              ctx->fault_dev, ctx->ray_stats);
+        });
+}
+
 // lbvh_capsule_contacts: shape_overlaps<kShapeCapsule, false> with a record in place of an index — the count walk is that
 // function's, the fill walk forms the contacts.  lbvh_capsule_deepest: one record per shape through launch_per_query.
 static lbvh_status capsule_contacts(lbvh_context* ctx, const lbvh_capsule* d_shapes, size_t count, const lbvh_scene* h_scene, uint64_t* d_offsets,
@@ -5859,6 +6017,12 @@ lbvh_status lbvh_box_cast_all(lbvh_context* ctx, const lbvh_box_ray* d_casts, si
                               uint64_t* d_offsets, lbvh_box_hit* d_hits, uint64_t capacity)
 {
     return cast_gathers<kCastBox>(ctx, d_casts, count, h_scene, d_offsets, d_hits, capacity, "lbvh_box_cast_all");
+}
+
+lbvh_status lbvh_triangle_cast_all(lbvh_context* ctx, const lbvh_tri_ray* d_casts, size_t count, const lbvh_scene* h_scene,
+                                   uint64_t* d_offsets, lbvh_tri_cast_hit* d_hits, uint64_t capacity)
+{
+    return triangle_cast_gathers(ctx, d_casts, count, h_scene, d_offsets, d_hits, capacity, "lbvh_triangle_cast_all");
 }
 
 lbvh_status lbvh_animate(lbvh_context* ctx, const lbvh_triangle* d_rest, uint32_t n, const uint32_t* d_body,

@@ -607,8 +607,9 @@ def sort_hit_segments(ctx, offsets, hits, count=None):
     """Every segment of a gathered list into (t, tri) order, in place, on the device (lbvh_sort_hit_segments): `offsets` the uint64
     DataBuffer a gather wrote (count + 1 entries; count defaults to offsets.size - 1), `hits` the layouts.HIT DataBuffer given to
     that gather — its size is the capacity; a segment that did not fit is left as it is.  Needs no scene.  Asynchronous.
-    The layouts.BOX_HIT records of box_cast_all are taken too: t and tri are in the same words, axis travels with its record."""
-    _sort_segments(N.lib.lbvh_sort_hit_segments, ctx, offsets, hits, L.BOX_HIT if hits.dtype == L.BOX_HIT else L.HIT, count)
+    The layouts.BOX_HIT records of box_cast_all and the layouts.TRI_CAST_HIT records of triangle_cast_all are taken too: t and tri
+    are in the same words, axis — or feature and w — travel with their record."""
+    _sort_segments(N.lib.lbvh_sort_hit_segments, ctx, offsets, hits, hits.dtype if hits.dtype in (L.BOX_HIT, L.TRI_CAST_HIT) else L.HIT, count)
 
 
 def sort_index_segments(ctx, offsets, tris, count=None):
@@ -1320,6 +1321,33 @@ class RaytracingMeshDrawer:
         (t, tri, axis) of every triangle touched.  sort_hit_segments takes these records as they are."""
         self._cast_all(N.lib.lbvh_box_cast_all, casts, "BOX_RAY", offsets, hits, "BOX_HIT")
 
+    def triangle_cast_all(self, casts, offsets, hits=None):
+        """The same for the moving triangles of `casts` (layouts.TRI_RAY, as tri_casts makes them), `hits` a layouts.TRI_CAST_HIT
+        DataBuffer: triangle_cast's record (t, tri, feature, w) of every triangle touched, `skip` never among them.
+        sort_hit_segments takes these records as they are."""
+        self._cast_all(N.lib.lbvh_triangle_cast_all, casts, "TRI_RAY", offsets, hits, "TRI_CAST_HIT")
+
+    def mesh_sweep_all(self, other_triangles, direction, t_max, sort=True):
+        """Convenience, the "all" twin of mesh_sweep: every pair of a triangle of the mesh `other_triangles` (layouts.TRIANGLE, or a
+        tuple (a, b, c) of (n, 3) arrays) and a triangle of this mesh that touch while the other mesh moves along `direction` for
+        0 <= t < t_max — one triangle_cast_all over one cast per moving triangle, count -> allocate -> fill.  Returns
+        (moving, tri, t, feature, w): five arrays with one entry per pair, `moving` the index into other_triangles and the rest the
+        layouts.TRI_CAST_HIT words.  sort=True orders the rows by (t, moving, tri), so row 0 is mesh_sweep's answer; sort=False
+        leaves them grouped by moving triangle, each group in the order of the walk.  Blocking."""
+        casts = tri_casts_from_mesh(other_triangles, direction, t_max)
+        buf = DataBuffer(self.ctx, len(casts), L.TRI_RAY)
+        try:
+            buf.local[:] = casts
+            buf.sync()
+            off, rec = self.cast_all(buf)
+        finally:
+            buf.dispose()
+        moving = np.repeat(np.arange(len(casts), dtype=np.int64), np.diff(off).astype(np.int64))
+        if sort:
+            order = np.lexsort((rec["tri"], moving, rec["t"]))
+            moving, rec = moving[order], rec[order]
+        return moving, rec["tri"].copy(), rec["t"].copy(), rec["feature"].copy(), rec["w"].copy()
+
     def _cast_all(self, fn, casts, layout, offsets, hits, record):
         if casts.dtype != getattr(L, layout) or offsets.dtype != np.uint64 or offsets.size < casts.size + 1 or \
                 (hits is not None and hits.dtype != getattr(L, record)):
@@ -1331,12 +1359,13 @@ class RaytracingMeshDrawer:
 
     def cast_all(self, casts, sort=False, device_sort=False, min_capacity=1):
         """Convenience, as all_hits(): count -> one 8-byte download -> allocate -> fill, for a DataBuffer of layouts.SPHERE_RAY,
-        layouts.CAPSULE_RAY or layouts.BOX_RAY.  Returns (offsets, records): host arrays, uint64[casts.size + 1] and layouts.HIT[total]
-        (layouts.BOX_HIT[total] for boxes).  sort=True orders every segment by (t, tri) on the host; device_sort=True issues
-        sort_hit_segments before the download instead."""
-        calls = {L.SPHERE_RAY: (self.sphere_cast_all, L.HIT), L.CAPSULE_RAY: (self.capsule_cast_all, L.HIT), L.BOX_RAY: (self.box_cast_all, L.BOX_HIT)}
+        layouts.CAPSULE_RAY, layouts.BOX_RAY or layouts.TRI_RAY.  Returns (offsets, records): host arrays, uint64[casts.size + 1] and
+        layouts.HIT[total] (layouts.BOX_HIT[total] for boxes, layouts.TRI_CAST_HIT[total] for triangles).  sort=True orders every
+        segment by (t, tri) on the host; device_sort=True issues sort_hit_segments before the download instead."""
+        calls = {L.SPHERE_RAY: (self.sphere_cast_all, L.HIT), L.CAPSULE_RAY: (self.capsule_cast_all, L.HIT), L.BOX_RAY: (self.box_cast_all, L.BOX_HIT),
+                 L.TRI_RAY: (self.triangle_cast_all, L.TRI_CAST_HIT)}
         if casts.dtype not in calls:
-            raise ValueError("casts must be a DataBuffer of layouts.SPHERE_RAY, layouts.CAPSULE_RAY or layouts.BOX_RAY")
+            raise ValueError("casts must be a DataBuffer of layouts.SPHERE_RAY, layouts.CAPSULE_RAY, layouts.BOX_RAY or layouts.TRI_RAY")
         call, record = calls[casts.dtype]
         off, rec = self._csr_lists(call, casts, min_capacity, device_sort, record, sort_hit_segments)
         if sort:

@@ -51,9 +51,10 @@
 //                                                [-half_extent / 2, half_extent / 2] (sheared, always solid).  BoxCast and
 //                                                BoxCastAny; prints how many casts touch, how many overlap at the start, the
 //                                                number of records per axis, the word sum and the first records
-//     lbvh_driver castall <sphere|capsule|box> <n_casts> [seed] [t_max]  the 4 096 triangles of cfg1 and n_casts sweeps (seed default 3,
+//     lbvh_driver castall <sphere|capsule|box|triangle> <n_casts> [seed] [t_max]  the 4 096 triangles of cfg1 and n_casts sweeps (seed default 3,
 //                                                t_max default 2): spheres of radius 1.5 drawn as `sweep` draws them, the capsules of
-//                                                `capsule` (radius 1.5, height 4) or the boxes of `boxcast` (half_extent 1.5).  The
+//                                                `capsule` (radius 1.5, height 4), the boxes of `boxcast` (half_extent 1.5) or the
+//                                                moving triangles of `tricast` (castall triangle <n> [seed] [t_max]).  The
 //                                                shape's CastAll (count only, one 8-byte read, fill), SortHitSegments, then the
 //                                                first-contact and the any-contact call on the same casts; prints the total, how many
 //                                                segments are non-empty, how many flags are set, for how many casts the first record of
@@ -720,20 +721,11 @@ static int tris_main(int argc, char** argv)
 }
 
 // moving triangles against the mesh of `tris`: per cast and axis k the vertex a around the mesh's box (as `sweep` draws an origin),
-// b's and c's offsets uniform in [-3, 3], then dir = a target uniform in the box minus a.  TriangleCast and TriangleCastAny.
-static int tricast_main(int argc, char** argv)
+// b's and c's offsets uniform in [-3, 3], then dir = a target uniform in the box minus a (the casts of `tricast` and of
+// `castall triangle`)
+static void triangle_casts(const float lo[3], const float hi[3], uint64_t seed, float t_max, std::vector<lbvh_tri_ray>& casts)
 {
-    const size_t count = argc > 2 ? (size_t)strtoull(argv[2], nullptr, 10) : 6000;
-    uint64_t seed = argc > 3 ? strtoull(argv[3], nullptr, 10) : 5;
-    const float t_max = argc > 4 ? (float)atof(argv[4]) : 2.0f;
-    const std::vector<lbvh_triangle> mesh = random_mesh(4096);
-    float lo[3], hi[3];
-    mesh_box(mesh, lo, hi);
-    lbvh::Context ctx(0);
-    lbvh::RaytracingMeshDrawer drawer(ctx, mesh);
-    drawer.Awake();
-    lbvh::DataBuffer<lbvh_tri_ray> casts(ctx, count);
-    for (auto& c : casts.LocalBuffer()) {
+    for (auto& c : casts) {
         std::memset(&c, 0, sizeof c);
         c.skip = LBVH_NULL;
         c.t_max = t_max;
@@ -745,6 +737,22 @@ static int tricast_main(int argc, char** argv)
             c.dir[k] = uniform(seed, lo[k], hi[k]) - c.a[k];
         }
     }
+}
+
+// TriangleCast and TriangleCastAny.
+static int tricast_main(int argc, char** argv)
+{
+    const size_t count = argc > 2 ? (size_t)strtoull(argv[2], nullptr, 10) : 6000;
+    const uint64_t seed = argc > 3 ? strtoull(argv[3], nullptr, 10) : 5;
+    const float t_max = argc > 4 ? (float)atof(argv[4]) : 2.0f;
+    const std::vector<lbvh_triangle> mesh = random_mesh(4096);
+    float lo[3], hi[3];
+    mesh_box(mesh, lo, hi);
+    lbvh::Context ctx(0);
+    lbvh::RaytracingMeshDrawer drawer(ctx, mesh);
+    drawer.Awake();
+    lbvh::DataBuffer<lbvh_tri_ray> casts(ctx, count);
+    triangle_casts(lo, hi, seed, t_max, casts.LocalBuffer());
     casts.Sync();
     lbvh::DataBuffer<lbvh_tri_cast_hit> hits(ctx, count);
     lbvh::DataBuffer<uint32_t> flags(ctx, count);
@@ -1506,7 +1514,17 @@ static int castall_main(int argc, char** argv)
             ctx, drawer, shape, mesh.size(), casts, t_max, [&](lbvh::DataBuffer<uint64_t>& o, lbvh::DataBuffer<lbvh_box_hit>* h) { drawer.BoxCastAll(casts, o, h); },
             [&](lbvh::DataBuffer<lbvh_box_hit>& h) { drawer.BoxCast(casts, h); }, [&](lbvh::DataBuffer<uint32_t>& f) { drawer.BoxCastAny(casts, f); });
     }
-    std::fprintf(stderr, "castall: the shape is sphere, capsule or box\n");
+    if (std::strcmp(shape, "triangle") == 0) {              // `castall triangle <n> [seed] [t_max]`: the casts of `tricast`
+        lbvh::DataBuffer<lbvh_tri_ray> casts(ctx, count);
+        triangle_casts(lo, hi, seed, t_max, casts.LocalBuffer());
+        casts.Sync();
+        return castall_report<lbvh_tri_ray, lbvh_tri_cast_hit>(
+            ctx, drawer, shape, mesh.size(), casts, t_max,
+            [&](lbvh::DataBuffer<uint64_t>& o, lbvh::DataBuffer<lbvh_tri_cast_hit>* h) { drawer.TriangleCastAll(casts, o, h); },
+            [&](lbvh::DataBuffer<lbvh_tri_cast_hit>& h) { drawer.TriangleCast(casts, h); },
+            [&](lbvh::DataBuffer<uint32_t>& f) { drawer.TriangleCastAny(casts, f); });
+    }
+    std::fprintf(stderr, "castall: the shape is sphere, capsule, box or triangle\n");
     return 2;
 }
 

@@ -730,6 +730,15 @@ public:
         check(ctx_.get(), lbvh_box_cast_all(ctx_.get(), (const lbvh_box_ray*)casts.DeviceBuffer(), casts.Size(), &s, (uint64_t*)offsets.DeviceBuffer(),
                                             hits ? (lbvh_box_hit*)hits->DeviceBuffer() : nullptr, hits ? (uint64_t)hits->Size() : 0));
     }
+    // the same for moving triangles (lbvh_triangle_cast_all): TriangleCast's record {t, tri, feature, w} of every triangle touched,
+    // `skip` never among them
+    void TriangleCastAll(const DataBuffer<lbvh_tri_ray>& casts, DataBuffer<uint64_t>& offsets, DataBuffer<lbvh_tri_cast_hit>* hits = nullptr)
+    {
+        if (offsets.Size() < casts.Size() + 1) throw Error(LBVH_ERR_INVALID_ARG, "TriangleCastAll: offsets needs one entry more than casts");
+        const lbvh_scene s = container_->Scene();
+        check(ctx_.get(), lbvh_triangle_cast_all(ctx_.get(), (const lbvh_tri_ray*)casts.DeviceBuffer(), casts.Size(), &s, (uint64_t*)offsets.DeviceBuffer(),
+                                                 hits ? (lbvh_tri_cast_hit*)hits->DeviceBuffer() : nullptr, hits ? (uint64_t)hits->Size() : 0));
+    }
     // Every segment of a gathered list into (t, tri) order / ascending index order, in place, on the device (lbvh_sort_hit_segments,
     // lbvh_sort_index_segments; asynchronous, no scratch, the path tracer's live-path list is kept).  The data buffer's size is the
     // capacity: pass the buffer that was given to GatherHits / the overlap query.  A segment that did not fit is left as it is.
@@ -741,6 +750,13 @@ public:
     }
     // the same for the lbvh_box_hit records of BoxCastAll: t and tri are the same two words, axis travels with its record
     void SortHitSegments(const DataBuffer<uint64_t>& offsets, DataBuffer<lbvh_box_hit>& hits, size_t count)
+    {
+        if (offsets.Size() < count + 1) throw Error(LBVH_ERR_INVALID_ARG, "SortHitSegments: offsets needs count + 1 entries");
+        check(ctx_.get(), lbvh_sort_hit_segments(ctx_.get(), (const uint64_t*)offsets.DeviceBuffer(), count, (lbvh_hit*)hits.DeviceBuffer(),
+                                                 (uint64_t)hits.Size()));
+    }
+    // and for the lbvh_tri_cast_hit records of TriangleCastAll: feature and w travel with their record
+    void SortHitSegments(const DataBuffer<uint64_t>& offsets, DataBuffer<lbvh_tri_cast_hit>& hits, size_t count)
     {
         if (offsets.Size() < count + 1) throw Error(LBVH_ERR_INVALID_ARG, "SortHitSegments: offsets needs count + 1 entries");
         check(ctx_.get(), lbvh_sort_hit_segments(ctx_.get(), (const uint64_t*)offsets.DeviceBuffer(), count, (lbvh_hit*)hits.DeviceBuffer(),
