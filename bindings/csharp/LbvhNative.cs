@@ -271,6 +271,9 @@ public static class LbvhNative
         ulong capacity);
     [DllImport(Lib)] public static extern int lbvh_sort_hit_segments(IntPtr ctx, IntPtr dOffsets, UIntPtr count, IntPtr dHits, ulong capacity);
     [DllImport(Lib)] public static extern int lbvh_sort_index_segments(IntPtr ctx, IntPtr dOffsets, UIntPtr count, IntPtr dTris, ulong capacity);
+    public const uint SortRecordsAscending = 0, SortRecordsDescending = 1, SortRecordsByTri = 2;   // LBVH_SORT_RECORDS_*
+    [DllImport(Lib)] public static extern int lbvh_sort_record_segments(IntPtr ctx, IntPtr dOffsets, UIntPtr count, IntPtr dRecords, ulong capacity,
+        uint order);
     [DllImport(Lib)] public static extern int lbvh_count_hits(IntPtr ctx, IntPtr dRays, UIntPtr count, ref Scene scene, IntPtr dCounts);
     [DllImport(Lib)] public static extern int lbvh_point_crossings(IntPtr ctx, IntPtr dPoints, UIntPtr count, float[] hDirs, uint nDirs, ref Scene scene,
         IntPtr dParity);

@@ -4,6 +4,8 @@
 // candidate lists are to be de-duplicated or intersected.  Twin of host.py sort_hit_segments / sort_index_segments and of
 // lbvh_host.hpp SortHitSegments / SortIndexSegments.  Hit records are ordered by (t, tri), indices ascending; a segment that did not
 // fit the capacity of the data buffer is left as it is.  The call needs no scene and keeps the path tracer's live-path list.
+// SortRecords is the same pass for the lists of 32-byte records (lbvh_sort_record_segments; host.py sort_record_segments,
+// lbvh_host.hpp SortRecordSegments): contacts deepest first, proximity records nearest first, segment and section records by triangle.
 // SOURCE ONLY (no C# toolchain in the build image).
 using System;
 
@@ -26,10 +28,23 @@ public static class SegmentSort
             (ulong)tris.count));
     }
 
+    /// The same for the 32-byte records (stride 32) of ShapeContacts, TriangleProximity, TriangleSegments and PlaneSections
+    /// (lbvh_sort_record_segments).  `order`: LbvhNative.SortRecordsAscending — (word 0 as a float, word 1): nearest first for
+    /// proximity records —, SortRecordsDescending — deepest first for contacts, the first record of a segment is the Deepest
+    /// call's —, SortRecordsByTri — word 3, the triangle of a segment or section record.
+    public static void SortRecords(NativeBuffer offsets, NativeBuffer records, int count, uint order)
+    {
+        Check(offsets, records, 32, count);
+        if (order > LbvhNative.SortRecordsByTri)
+            throw new ArgumentException("SegmentSort: order is one of LbvhNative.SortRecords*");
+        LbvhNative.Check(offsets.Context, LbvhNative.lbvh_sort_record_segments(offsets.Context, offsets.Pointer, (UIntPtr)(ulong)count,
+            records.Pointer, (ulong)records.count, order));
+    }
+
     static void Check(NativeBuffer offsets, NativeBuffer data, int stride, int count)
     {
         if (offsets == null || data == null || offsets.stride != 8 || data.stride != stride)
-            throw new ArgumentException("SegmentSort: offsets are ulong (stride 8), the data LbvhNative.Hit (16) or uint (4)");
+            throw new ArgumentException("SegmentSort: offsets are ulong (stride 8), the data LbvhNative.Hit (16), uint (4) or a 32-byte record");
         if (count < 0 || count + 1 > offsets.count)
             throw new ArgumentException("SegmentSort: offsets needs count + 1 entries");
         if (offsets.Context != data.Context)

@@ -866,6 +866,46 @@ lbvh_status lbvh_gather_hits(lbvh_context* ctx, const lbvh_ray* d_rays, size_t c
 lbvh_status lbvh_sort_hit_segments(lbvh_context* ctx, const uint64_t* d_offsets, size_t count, lbvh_hit* d_hits, uint64_t capacity);
 lbvh_status lbvh_sort_index_segments(lbvh_context* ctx, const uint64_t* d_offsets, size_t count, uint32_t* d_tris, uint64_t capacity);
 
+/* The same pass for the CSR lists of 32-byte records: lbvh_contact (lbvh_capsule_contacts), lbvh_box_contact (lbvh_obb_contacts),
+ * lbvh_tri_closest (lbvh_triangle_gather_within_distance), lbvh_tri_segment (lbvh_triangle_intersection_segments) and
+ * lbvh_plane_segment (lbvh_plane_sections), all declared below.  d_records holds `capacity` records of 32 bytes, read as eight
+ * 32-bit words (word 0 first); the array is 16-byte aligned, like every 32-byte record array of the library.
+ * The contract is that of the two calls above, word for word, with "record" for "hit": which segments count as fitting
+ * (d_offsets[q] <= d_offsets[q+1] <= capacity) and come out as a permutation of what they were; that a segment which does not fit
+ * or whose pair of offsets decreases is left untouched, that no record at index >= capacity is ever read or written and that
+ * d_offsets is never written; that THE SORT IS NOT STABLE; asynchronous with no host wait, NO context scratch, no scene, the path
+ * tracer's live-path list kept (unless the buffer is that frame's d_hits); count == 0 is a no-op and capacity == 0 is a no-op that
+ * returns LBVH_OK.  Rejected with LBVH_ERR_INVALID_ARG: NULL ctx / d_offsets / d_records, d_offsets not 8-byte aligned, d_records
+ * not 16-byte aligned, count > 2^32 - 1, and order > 2 (checked first: also with count == 0).
+ *   Key under `order`, K the K of lbvh_sort_hit_segments, operation by operation:
+ *     LBVH_SORT_RECORDS_ASCENDING   the 64-bit pair (K(word 0), word 1), K(word 0) the more significant half.  Word 0 is dist2 or
+ *                                   depth as an fp32 value: -0 sorts with +0, every NaN is one class after +inf.  Word 1 is `tri` in
+ *                                   lbvh_contact, lbvh_box_contact and lbvh_tri_closest, and decides ties.
+ *     LBVH_SORT_RECORDS_DESCENDING  (D(word 0), word 1) ascending, with D = 0xFFFFFFFF for a NaN and ~K(word 0) otherwise.  K of a
+ *                                   value that is not a NaN is never 0xFFFFFFFF and never 0, so D reverses K below the NaNs: the
+ *                                   greatest value first, on equal values (-0 and +0 are equal) the lower word 1 first, NaNs still
+ *                                   last.
+ *     LBVH_SORT_RECORDS_BY_TRI      word 3, ascending: the `tri` of lbvh_tri_segment and lbvh_plane_segment.
+ *   Words that are not in the key travel with their record and are not compared.
+ * Hence — a candidate appears once per segment, so all three orders are canonical on what the five queries write:
+ *   after lbvh_triangle_gather_within_distance + ASCENDING (same d_offsets and capacity), the first record of a non-empty fitting
+ *   segment is lbvh_triangle_closest_point's record for that query in all eight words (least dist2, then the lower index: the same
+ *   rule; a candidate's dist2 is below the bound, never a NaN);
+ *   after lbvh_capsule_contacts or lbvh_obb_contacts + DESCENDING, the first record is lbvh_capsule_deepest's / lbvh_obb_deepest's
+ *   in all eight words — AS LONG AS NO DEPTH OF THE SEGMENT IS A NaN: the deepest rule replaces its record when the new depth is
+ *   greater, or is not less and the index is lower, so a NaN depth compares as equal to everything there and which record wins
+ *   depends on the walk, while here a NaN always sorts last;
+ *   after lbvh_triangle_intersection_segments or lbvh_plane_sections + BY_TRI, the `tri` words of a fitting segment are strictly
+ *   ascending and the segment equals the numpy restatement sorted by `tri` (tests/record_sort_reference.py).
+ * Segments of up to 256 records are sorted 64 queries at a time by one wave; a longer one by ONE workgroup, in chunks of 1 024
+ * records in LDS and, beyond one chunk, in O(n log^2 n) exchanges partly on device memory.  The network orders 16-byte entries
+ * (key, source slot, rank), not the records: every record is moved once per pass over its chunk. */
+#define LBVH_SORT_RECORDS_ASCENDING   0u   /* key (K(word 0), word 1)          */
+#define LBVH_SORT_RECORDS_DESCENDING  1u   /* key (D(word 0), word 1)          */
+#define LBVH_SORT_RECORDS_BY_TRI      2u   /* key word 3                       */
+lbvh_status lbvh_sort_record_segments(lbvh_context* ctx, const uint64_t* d_offsets, size_t count,
+                                      void* d_records, uint64_t capacity, uint32_t order);
+
 /* A moving sphere: 32 bytes, arrays 16-byte aligned: lbvh_ray with the radius where t_min is. */
 typedef struct lbvh_sphere_ray {
     float origin[3]; float radius;
@@ -1390,7 +1430,9 @@ typedef struct lbvh_tri_segment {
  * Cost: the fill walk visits what lbvh_triangle_intersections' visits, but evaluates all six tests for every box-overlapping
  * triangle where that call stops at the first that passes, and a record is 32 bytes.
  * Out of scope: a device-side sort of 32-byte record segments; exact coplanar overlap; merging records into polylines; a contact
- * normal or depth for triangle pairs; an _any form (it is lbvh_triangle_intersects_any) or a form for one huge query. */
+ * normal or depth for triangle pairs; an _any form (it is lbvh_triangle_intersects_any) or a form for one huge query.  (Out of
+ * scope of THIS call: the device-side sort of 32-byte record segments by `tri` is lbvh_sort_record_segments with
+ * LBVH_SORT_RECORDS_BY_TRI, above.) */
 lbvh_status lbvh_triangle_intersection_segments(lbvh_context* ctx, const lbvh_tri_query* d_queries, size_t count,
                                                 const lbvh_scene* h_scene, uint64_t* d_offsets,
                                                 lbvh_tri_segment* d_segments, uint64_t capacity);
@@ -1546,7 +1588,9 @@ typedef struct lbvh_contact {
  * pierce is evaluated for every triangle that passes rule 1, a candidate takes a ninth point test, and a record is 32 bytes.
  * Out of scope: box and sheared-box contacts (the least-overlap axis of the thirteen); a manifold of more than one point per
  * triangle; a device-side sort of contact segments (lbvh_sort_hit_segments is for 16-byte records); a form that spreads one huge
- * capsule over the device.  (The box and the sheared box have calls of their own: lbvh_obb_contacts / lbvh_obb_deepest below.) */
+ * capsule over the device.  (The box and the sheared box have calls of their own: lbvh_obb_contacts / lbvh_obb_deepest below.  The
+ * device-side sort of contact segments has one too: lbvh_sort_record_segments, above; with LBVH_SORT_RECORDS_DESCENDING the first
+ * record of a segment is lbvh_capsule_deepest's.) */
 lbvh_status lbvh_capsule_contacts(lbvh_context* ctx, const lbvh_capsule* d_shapes, size_t count, const lbvh_scene* h_scene,
                                   uint64_t* d_offsets, lbvh_contact* d_contacts, uint64_t capacity);
 lbvh_status lbvh_capsule_deepest(lbvh_context* ctx, const lbvh_capsule* d_shapes, size_t count, const lbvh_scene* h_scene,
@@ -1776,7 +1820,9 @@ lbvh_status lbvh_triangle_within_distance(lbvh_context* ctx, const lbvh_tri_dist
  * six segment tests (54 point tests) in BOTH walks; pass the margin the solver needs, not more.
  * Out of scope: a device-side sort of 32-byte records (the host sorts; lbvh_sort_hit_segments is for 16-byte records); the k
  * nearest triangles of a triangle; a two-tree (mesh-BVH against mesh-BVH) descent; removing the (i, j) / (j, i) duplicates or the
- * adjacent triangles of a self-query on the device (the host does, from the returned list). */
+ * adjacent triangles of a self-query on the device (the host does, from the returned list).  (Out of scope of THIS call: the
+ * device-side sort of 32-byte records is lbvh_sort_record_segments, above; with LBVH_SORT_RECORDS_ASCENDING the first record of a
+ * segment is lbvh_triangle_closest_point's.) */
 lbvh_status lbvh_triangle_gather_within_distance(lbvh_context* ctx, const lbvh_tri_distance_query* d_queries, size_t count,
                                                  const lbvh_scene* h_scene, uint64_t* d_offsets, lbvh_tri_closest* d_records,
                                                  uint64_t capacity);
@@ -1850,7 +1896,9 @@ typedef struct lbvh_box_contact {
  * 32 bytes.
  * Out of scope: a contact point or a manifold for the box (a box touches a triangle in a point, a segment or a polygon); flat
  * boxes (det == 0 is inactive, as everywhere); a device-side sort of 32-byte segments (lbvh_sort_hit_segments is for 16-byte
- * records); a form that spreads one huge box over the device. */
+ * records); a form that spreads one huge box over the device.  (Out of scope of THESE two calls: the device-side sort of 32-byte
+ * segments is lbvh_sort_record_segments, above; with LBVH_SORT_RECORDS_DESCENDING the first record of a segment is
+ * lbvh_obb_deepest's.) */
 lbvh_status lbvh_obb_contacts(lbvh_context* ctx, const lbvh_obb* d_shapes, size_t count, const lbvh_scene* h_scene,
                               uint64_t* d_offsets, lbvh_box_contact* d_contacts, uint64_t capacity);
 lbvh_status lbvh_obb_deepest(lbvh_context* ctx, const lbvh_obb* d_shapes, size_t count, const lbvh_scene* h_scene,
@@ -2034,7 +2082,8 @@ typedef struct lbvh_plane_segment {
  * the expansion opened, triangle_tests the triangle lines read; the full form adds the walks' share twice.
  * Measurements: tools/plane_sections_bench.py (written, not yet recorded).
  * Out of scope: a per-lane form for more than 65 536 planes; an _any form; a device-side sort of 32-byte segments; merging records
- * into polylines on the device (host.stitch_sections does it on the host); coplanar faces. */
+ * into polylines on the device (host.stitch_sections does it on the host); coplanar faces.  (Out of scope of THIS call: the
+ * device-side sort of these 32-byte segments by `tri` is lbvh_sort_record_segments with LBVH_SORT_RECORDS_BY_TRI, above.) */
 #define LBVH_PLANE_SECTIONS_MAX_COUNT 65536
 lbvh_status lbvh_plane_sections(lbvh_context* ctx, const lbvh_plane* d_planes, size_t count, const lbvh_scene* h_scene,
                                 uint64_t* d_offsets, lbvh_plane_segment* d_segments, uint64_t capacity);
@@ -2064,7 +2113,7 @@ lbvh_status lbvh_path_scatter(lbvh_context* ctx, const lbvh_scene* h_scene, cons
  * into those buffers drops the list (lbvh_path_begin, lbvh_trace_rays, a primary trace into any part of d_hits,
  * lbvh_buffer_upload / _fill_u32 / _free), and so does lbvh_trace_forget — and so do lbvh_trace_closest,
  * lbvh_trace_occluded, lbvh_closest_point_query, lbvh_within_distance, lbvh_count_hits, lbvh_point_crossings, lbvh_box_overlaps, lbvh_gather_within_distance, lbvh_k_closest_points, lbvh_trace_k_closest, lbvh_gather_hits, lbvh_sphere_cast, lbvh_sphere_cast_any, lbvh_capsule_cast, lbvh_capsule_cast_any, lbvh_box_cast, lbvh_box_cast_any, lbvh_triangle_cast, lbvh_triangle_cast_any, lbvh_triangle_intersections, lbvh_triangle_intersects_any, lbvh_triangle_intersection_segments, lbvh_capsule_overlaps, lbvh_capsule_overlaps_any, lbvh_obb_overlaps, lbvh_obb_overlaps_any, lbvh_capsule_contacts, lbvh_capsule_deepest, lbvh_obb_contacts, lbvh_obb_deepest, lbvh_segment_closest_point, lbvh_segment_within_distance, lbvh_triangle_closest_point, lbvh_triangle_within_distance, lbvh_triangle_gather_within_distance, lbvh_sphere_cast_all, lbvh_capsule_cast_all, lbvh_box_cast_all, lbvh_triangle_cast_all, lbvh_region_overlaps, lbvh_region_overlaps_any, lbvh_region_overlaps_large and lbvh_plane_sections, whatever buffers they are given, since they use the same ray scratch; then every state is scanned again.  The one exception among the query calls:
- * lbvh_sort_hit_segments and lbvh_sort_index_segments take no context scratch and keep the live-path list (they drop it only when the
+ * lbvh_sort_hit_segments, lbvh_sort_index_segments and lbvh_sort_record_segments take no context scratch and keep the live-path list (they drop it only when the
  * buffer they sort is d_hits itself).  What the library
  * cannot see is a write of the CALLER's own (a kernel or hipMemcpy that revives or ends paths, Russian roulette): between two
  * consecutive bounces of a frame d_states and d_hits must not be written from outside the library — or lbvh_trace_forget must be

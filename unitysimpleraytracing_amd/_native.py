@@ -102,6 +102,7 @@ SIGNATURES = {
     "lbvh_gather_hits": (_I32, [_P, _P, _SZ, C.POINTER(Scene), _P, _P, C.c_uint64]),
     "lbvh_sort_hit_segments": (_I32, [_P, _P, _SZ, _P, C.c_uint64]),
     "lbvh_sort_index_segments": (_I32, [_P, _P, _SZ, _P, C.c_uint64]),
+    "lbvh_sort_record_segments": (_I32, [_P, _P, _SZ, _P, C.c_uint64, _U32]),
     "lbvh_sphere_cast": (_I32, [_P, _P, _SZ, C.POINTER(Scene), _P]),
     "lbvh_sphere_cast_any": (_I32, [_P, _P, _SZ, C.POINTER(Scene), _P]),
     "lbvh_capsule_cast": (_I32, [_P, _P, _SZ, C.POINTER(Scene), _P]),
@@ -167,6 +168,7 @@ SORT_SHARDED_REPLICATE = 1               # LBVH_SORT_SHARDED_REPLICATE
 K_CLOSEST_MAX = 32                       # LBVH_K_CLOSEST_MAX
 REGION_LARGE_MAX_COUNT = 65536           # LBVH_REGION_LARGE_MAX_COUNT
 PLANE_SECTIONS_MAX_COUNT = 65536         # LBVH_PLANE_SECTIONS_MAX_COUNT
+SORT_RECORDS_ASCENDING, SORT_RECORDS_DESCENDING, SORT_RECORDS_BY_TRI = range(3)      # LBVH_SORT_RECORDS_*
 
 # include/lbvh_debug.h: not part of the drop-in boundary
 DEBUG_SWITCH_SORT_QUEUES, DEBUG_SWITCH_COLD_ORDER, DEBUG_SWITCH_BUILD_FORM, DEBUG_SWITCH_FRAME_WAIT_MS, DEBUG_SWITCH_SORT_FORM, DEBUG_SWITCH_FAIL_RESERVE = range(6)

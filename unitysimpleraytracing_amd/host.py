@@ -618,6 +618,31 @@ def sort_index_segments(ctx, offsets, tris, count=None):
     _sort_segments(N.lib.lbvh_sort_index_segments, ctx, offsets, tris, np.dtype(np.uint32), count)
 
 
+def _record_orders():
+    return {L.TRI_CLOSEST: N.SORT_RECORDS_ASCENDING, L.CONTACT: N.SORT_RECORDS_DESCENDING, L.BOX_CONTACT: N.SORT_RECORDS_DESCENDING,
+            L.TRI_SEGMENT: N.SORT_RECORDS_BY_TRI, L.PLANE_SEGMENT: N.SORT_RECORDS_BY_TRI}
+
+
+def sort_record_segments(ctx, offsets, records, order=None, count=None):
+    """The same for a DataBuffer of 32-byte records (lbvh_sort_record_segments): layouts.TRI_CLOSEST, CONTACT, BOX_CONTACT,
+    TRI_SEGMENT or PLANE_SEGMENT; its size is the capacity.  `order`: _native.SORT_RECORDS_ASCENDING — (word 0 as an fp32 value,
+    word 1) —, SORT_RECORDS_DESCENDING — the greatest word 0 first, the lower word 1 on ties, NaNs last — or SORT_RECORDS_BY_TRI —
+    word 3.  None chooses by the dtype: TRI_CLOSEST ascending (nearest first), CONTACT and BOX_CONTACT descending (deepest first),
+    TRI_SEGMENT and PLANE_SEGMENT by tri.  Needs no scene.  Asynchronous."""
+    orders = _record_orders()
+    if records.dtype not in orders:
+        raise ValueError("records must be a DataBuffer of layouts.TRI_CLOSEST, CONTACT, BOX_CONTACT, TRI_SEGMENT or PLANE_SEGMENT")
+    order = orders[records.dtype] if order is None else int(order)
+    if order not in (N.SORT_RECORDS_ASCENDING, N.SORT_RECORDS_DESCENDING, N.SORT_RECORDS_BY_TRI):
+        raise ValueError("order must be one of _native.SORT_RECORDS_ASCENDING, SORT_RECORDS_DESCENDING, SORT_RECORDS_BY_TRI")
+    _sort_segments(lambda h, o, n, d, cap: N.lib.lbvh_sort_record_segments(h, o, n, d, cap, order), ctx, offsets, records, records.dtype, count)
+
+
+def _sort_records_by_dtype(ctx, offsets, records, count):
+    """_csr_lists' segment_sort hook: sort_record_segments in the order the dtype names"""
+    sort_record_segments(ctx, offsets, records, None, count)
+
+
 def _sort_segments(fn, ctx, offsets, data, dtype, count):
     count = offsets.size - 1 if count is None else int(count)
     if offsets.dtype != np.uint64 or data.dtype != dtype or count < 0 or offsets.size < count + 1:
@@ -974,13 +999,14 @@ class RaytracingMeshDrawer:
                                                                            segments.device if segments is not None else None,
                                                                            segments.size if segments is not None else 0))
 
-    def intersection_segments(self, queries, sort=False, min_capacity=1):
+    def intersection_segments(self, queries, sort=False, min_capacity=1, device_sort=False):
         """Convenience, as intersections(): count -> one 8-byte download -> allocate -> fill, for a DataBuffer of layouts.TRI_QUERY.
         Returns (offsets, records): host arrays, uint64[queries.size + 1] and layouts.TRI_SEGMENT[total], every segment in the
         walk's order.  sort=True orders every segment by `tri` HERE, ON THE HOST (each triangle appears once per segment, so the
-        order is total)."""
-        off, rec = self._csr_lists(self.triangle_intersection_segments, queries, min_capacity, False, dtype=L.TRI_SEGMENT)
-        if sort:
+        order is total).  device_sort=True issues sort_record_segments before the download instead: the same arrays."""
+        off, rec = self._csr_lists(self.triangle_intersection_segments, queries, min_capacity, device_sort, dtype=L.TRI_SEGMENT,
+                                   segment_sort=_sort_records_by_dtype)
+        if sort and not device_sort:
             segment = np.repeat(np.arange(queries.size), np.diff(off).astype(np.int64))
             rec = rec[np.lexsort((rec["tri"], segment))]
         return off, rec
@@ -1127,13 +1153,14 @@ class RaytracingMeshDrawer:
                                                                             offsets.device, records.device if records is not None else None,
                                                                             records.size if records is not None else 0))
 
-    def proximity_pairs(self, other, max_dist, self_skip=False, sort=False, min_capacity=1):
+    def proximity_pairs(self, other, max_dist, self_skip=False, sort=False, min_capacity=1, device_sort=False):
         """Convenience, as contacts(): count -> one 8-byte download -> allocate -> fill.  `other`: an array of
         layouts.TRI_DISTANCE_QUERY (taken as it is: max_dist and self_skip are not applied), or a mesh as mesh_distance takes it (an
         array of layouts.TRIANGLE or a tuple (a, b, c) of (n, 3) vertex arrays), every triangle of it with max_dist2 = max_dist^2 and,
         self_skip=True, skip = its own index (this mesh against itself; see unique_self_pairs).  Returns (offsets, records): host
         arrays, uint64[n + 1] and layouts.TRI_CLOSEST[total], every segment in the walk's order; sort=True orders every segment by
-        (dist2, tri) HERE, ON THE HOST.  Allocates, waits on the host."""
+        (dist2, tri) HERE, ON THE HOST; device_sort=True issues sort_record_segments before the download instead: the same
+        arrays.  Allocates, waits on the host."""
         if isinstance(other, np.ndarray) and other.dtype == L.TRI_DISTANCE_QUERY:
             q = other.reshape(-1)
         else:
@@ -1145,10 +1172,11 @@ class RaytracingMeshDrawer:
         try:
             queries.local[:] = q
             queries.sync()
-            off, rec = self._csr_lists(self.triangle_gather_within_distance, queries, min_capacity, False, dtype=L.TRI_CLOSEST)
+            off, rec = self._csr_lists(self.triangle_gather_within_distance, queries, min_capacity, device_sort, dtype=L.TRI_CLOSEST,
+                                       segment_sort=_sort_records_by_dtype)
         finally:
             queries.dispose()
-        if sort:
+        if sort and not device_sort:
             segment = np.repeat(np.arange(n), np.diff(off).astype(np.int64))
             rec = rec[np.lexsort((rec["tri"], rec["dist2"], segment))]
         return off, rec
@@ -1174,15 +1202,17 @@ class RaytracingMeshDrawer:
         Asynchronous; read with out.get_data()."""
         self._per_query(N.lib.lbvh_obb_deepest, shapes, "OBB", out, L.BOX_CONTACT, "shapes")
 
-    def contacts(self, shapes, min_capacity=1):
+    def contacts(self, shapes, min_capacity=1, device_sort=False):
         """Convenience, as touching(): count -> one 8-byte download -> allocate -> fill, for a DataBuffer of layouts.CAPSULE or of
         layouts.OBB.  Returns (offsets, contacts): host arrays, uint64[shapes.size + 1] and layouts.CONTACT[total] (capsules) or
-        layouts.BOX_CONTACT[total] (boxes), every segment in the walk's order."""
+        layouts.BOX_CONTACT[total] (boxes), every segment in the walk's order.  device_sort=True issues sort_record_segments
+        before the download: every segment deepest first, the lower triangle index first on equal depth — its first record is
+        capsule_deepest's / obb_deepest's."""
         if shapes.dtype not in (L.CAPSULE, L.OBB):
             raise ValueError("shapes must be a DataBuffer of layouts.CAPSULE or layouts.OBB")
         if shapes.dtype == L.OBB:
-            return self._csr_lists(self.obb_contacts, shapes, min_capacity, False, dtype=L.BOX_CONTACT)
-        return self._csr_lists(self.capsule_contacts, shapes, min_capacity, False, dtype=L.CONTACT)
+            return self._csr_lists(self.obb_contacts, shapes, min_capacity, device_sort, dtype=L.BOX_CONTACT, segment_sort=_sort_records_by_dtype)
+        return self._csr_lists(self.capsule_contacts, shapes, min_capacity, device_sort, dtype=L.CONTACT, segment_sort=_sort_records_by_dtype)
 
     def region_overlaps(self, regions, mode, offsets, tris=None):
         """Every triangle in each convex region of the DataBuffer `regions` (layouts.REGION: six planes {nx, ny, nz, d}, each keeping
@@ -1222,10 +1252,11 @@ class RaytracingMeshDrawer:
                                                            segments.device if segments is not None else None,
                                                            segments.size if segments is not None else 0))
 
-    def cross_sections(self, planes, stitch=False, min_capacity=1):
+    def cross_sections(self, planes, stitch=False, min_capacity=1, device_sort=False):
         """Convenience: count -> one 8-byte download -> allocate -> fill -> download, for layouts.PLANE records on the host (see
         host.planes) or a DataBuffer of them.  Returns (offsets, records): uint64[count + 1] and layouts.PLANE_SEGMENT[total],
-        every segment ordered by `tri` on the host.  stitch=True returns instead a list with one (loops, chains) of
+        every segment ordered by `tri` on the host — or, device_sort=True, on the device before the download
+        (sort_record_segments): the same arrays.  stitch=True returns instead a list with one (loops, chains) of
         host.stitch_sections per plane, stitched through the scene's own triangle records."""
         own = not isinstance(planes, DataBuffer)
         if own:
@@ -1236,9 +1267,11 @@ class RaytracingMeshDrawer:
             planes.local[:] = host_planes
             planes.sync()
         try:
-            off, rec = self._csr_lists(self.plane_sections, planes, min_capacity, False, dtype=L.PLANE_SEGMENT)
-            segment = np.repeat(np.arange(planes.size), np.diff(off).astype(np.int64))
-            rec = rec[np.lexsort((rec["tri"], segment))]
+            off, rec = self._csr_lists(self.plane_sections, planes, min_capacity, device_sort, dtype=L.PLANE_SEGMENT,
+                                       segment_sort=_sort_records_by_dtype)
+            if not device_sort:
+                segment = np.repeat(np.arange(planes.size), np.diff(off).astype(np.int64))
+                rec = rec[np.lexsort((rec["tri"], segment))]
         finally:
             if own:
                 planes.dispose()

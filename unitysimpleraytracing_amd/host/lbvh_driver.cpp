@@ -35,6 +35,11 @@
 //     lbvh_driver sortedhits <n_rays> [t_max]    `gather` with the segments ordered on the device instead: GatherHits, then
 //                                                SortHitSegments, then the download; no host sort; prints the same fields, the
 //                                                position-weighted sum now over the device-sorted order
+//     lbvh_driver sortedrecords <contacts|boxcontacts|triprox|trisegs|sections> <n> [seed]   a synthetic CSR list of n segments of
+//                                                32-byte records (SplitMix64: lengths 0 .. 23, every 97th 300 .. 2 299; word 0 a
+//                                                multiple of 0.25, words 1 and 3 distinct inside a segment), SortRecordSegments in
+//                                                the order of that list (deepest first / nearest first / by triangle); prints the
+//                                                total, the sum of all words and the sum of (position + 1) * (word 1 ^ word 7)
 //     lbvh_driver sweep [n | file.obj] [count] [radius]  the mesh of `points` and `count` spheres of the given radius (default 1 %
 //                                                of the largest extent) from points around the mesh's box towards points inside
 //                                                it (t = 1 at the target, t_max 2); SphereCast and SphereCastAny; prints how
@@ -567,6 +572,59 @@ static int gather_run(int argc, char** argv, bool device_sort)
 
 static int gather_main(int argc, char** argv) { return gather_run(argc, argv, false); }
 static int sortedhits_main(int argc, char** argv) { return gather_run(argc, argv, true); }
+
+// `sortedrecords`: a synthetic CSR list of 32-byte records, ordered by lbvh_sort_record_segments in the order of the named list
+static int sortedrecords_main(int argc, char** argv)
+{
+    static const struct { const char* kind; uint32_t order; } kinds[] = {
+        {"contacts", LBVH_SORT_RECORDS_DESCENDING}, {"boxcontacts", LBVH_SORT_RECORDS_DESCENDING}, {"triprox", LBVH_SORT_RECORDS_ASCENDING},
+        {"trisegs", LBVH_SORT_RECORDS_BY_TRI},      {"sections", LBVH_SORT_RECORDS_BY_TRI}};
+    uint32_t order = 3;
+    for (const auto& k : kinds)
+        if (argc > 2 && std::strcmp(argv[2], k.kind) == 0) order = k.order;
+    if (order > LBVH_SORT_RECORDS_BY_TRI) throw std::runtime_error("sortedrecords <contacts|boxcontacts|triprox|trisegs|sections> <n> [seed]");
+    const size_t count = argc > 3 ? (size_t)strtoull(argv[3], nullptr, 10) : 4096;
+    uint64_t seed = argc > 4 ? strtoull(argv[4], nullptr, 10) : 5;
+    // segment q: every 97th has 300 .. 2 299 records, the others 0 .. 23
+    std::vector<uint64_t> off(count + 1, 0);
+    for (size_t q = 0; q < count; q++)
+        off[q + 1] = off[q] + (q % 97 == 5 ? 300u + (uint32_t)uniform(seed, 0.0f, 2000.0f) : (uint32_t)uniform(seed, 0.0f, 24.0f));
+    const uint64_t total = off[count];
+    lbvh::Context ctx(0);
+    lbvh::DataBuffer<uint64_t> offsets(ctx, count + 1);
+    offsets.LocalBuffer() = off;
+    offsets.Sync();
+    lbvh::DataBuffer<lbvh_contact> records(ctx, std::max<size_t>((size_t)total, 1));
+    // record j of segment q, i its position in the list: word 0 a multiple of 0.25 in [-2, 2) (many ties), words 1 and 3 distinct
+    // inside the segment (j times an odd number), the other words a fingerprint of i
+    for (size_t q = 0; q < count; q++)
+        for (uint64_t i = off[q]; i < off[q + 1]; i++) {
+            const uint32_t j = (uint32_t)(i - off[q]);
+            const float v = floorf(uniform(seed, 0.0f, 16.0f)) * 0.25f - 2.0f;
+            uint32_t w[8];
+            for (uint32_t k = 0; k < 8; k++) w[k] = ((uint32_t)i * 8u + k) * 2654435761u;
+            std::memcpy(&w[0], &v, 4);
+            w[1] = j * 2654435761u + (uint32_t)q;
+            w[3] = j * 2246822519u + 7u * (uint32_t)q;
+            std::memcpy(&records.LocalBuffer()[i], w, 32);
+        }
+    records.Sync();
+    lbvh::RaytracingMeshDrawer drawer(ctx, random_mesh(64));       // the sort needs no scene: the wrapper is the drawer's
+    drawer.SortRecordSegments(offsets, records, count, order);
+    records.GetData();
+    uint64_t words = 0, weighted_sum = 0;
+    size_t nonempty = 0;
+    for (size_t q = 0; q < count; q++) nonempty += off[q + 1] > off[q];
+    for (uint64_t i = 0; i < total; i++) {
+        uint32_t w[8];
+        std::memcpy(w, &records.LocalBuffer()[i], 32);
+        for (uint32_t k = 0; k < 8; k++) words += w[k];
+        weighted_sum += (i + 1) * (uint64_t)(w[1] ^ w[7]);
+    }
+    std::printf("{\"kind\": \"%s\", \"order\": %u, \"segments\": %zu, \"total\": %llu, \"nonempty\": %zu, \"word_sum\": %llu, \"weighted_sum\": %llu}\n",
+                argv[2], order, count, (unsigned long long)total, nonempty, (unsigned long long)words, (unsigned long long)weighted_sum);
+    return 0;
+}
 
 static int sweep_main(int argc, char** argv)
 {
@@ -1660,7 +1718,7 @@ static int frame_main(int argc, char** argv)
 int main(int argc, char** argv)
 {
     static const struct { const char* name; int (*run)(int, char**); } commands[] = {
-        {"crossings", crossings_main}, {"points", points_main}, {"knn", knn_main},   {"khits", khits_main}, {"gather", gather_main}, {"sortedhits", sortedhits_main},
+        {"crossings", crossings_main}, {"points", points_main}, {"knn", knn_main},   {"khits", khits_main}, {"gather", gather_main}, {"sortedhits", sortedhits_main}, {"sortedrecords", sortedrecords_main},
         {"sweep", sweep_main},         {"capsule", capsule_main}, {"boxcast", boxcast_main}, {"tricast", tricast_main}, {"castall", castall_main},         {"overlaps", overlaps_main}, {"tris", tris_main}, {"trisegs", trisegs_main}, {"sections", sections_main}, {"shapes", shapes_main}, {"contacts", contacts_main}, {"boxcontacts", boxcontacts_main}, {"segclosest", segclosest_main}, {"triclosest", triclosest_main}, {"triprox", triprox_main}, {"regions", regions_main}, {"rays", rays_main}, {"sort", sort_main},   {"multi", multi_main}};
     try {
         for (const auto& c : commands)

@@ -768,6 +768,17 @@ public:
         check(ctx_.get(), lbvh_sort_index_segments(ctx_.get(), (const uint64_t*)offsets.DeviceBuffer(), count, (uint32_t*)tris.DeviceBuffer(),
                                                    (uint64_t)tris.Size()));
     }
+    // The same pass for the 32-byte records of CapsuleContacts / ObbContacts (order LBVH_SORT_RECORDS_DESCENDING: deepest first, the
+    // first record is the _deepest call's), TriangleGatherWithinDistance (LBVH_SORT_RECORDS_ASCENDING: nearest first) and
+    // TriangleIntersectionSegments / PlaneSections (LBVH_SORT_RECORDS_BY_TRI), lbvh_sort_record_segments: T is any 32-byte record.
+    template <typename T>
+    void SortRecordSegments(const DataBuffer<uint64_t>& offsets, DataBuffer<T>& records, size_t count, uint32_t order)
+    {
+        static_assert(sizeof(T) == 32, "SortRecordSegments: a 32-byte record");
+        if (offsets.Size() < count + 1) throw Error(LBVH_ERR_INVALID_ARG, "SortRecordSegments: offsets needs count + 1 entries");
+        check(ctx_.get(), lbvh_sort_record_segments(ctx_.get(), (const uint64_t*)offsets.DeviceBuffer(), count, (void*)records.DeviceBuffer(),
+                                                    (uint64_t)records.Size(), order));
+    }
     void PointCrossings(const DataBuffer<lbvh_point_query>& points, const std::vector<float>& dirs, DataBuffer<uint32_t>& parity)
     {
         if (parity.Size() < points.Size()) throw Error(LBVH_ERR_INVALID_ARG, "PointCrossings: fewer parity words than points");
