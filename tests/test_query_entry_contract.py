@@ -1,4 +1,4 @@
-"""What the entry points that walk the derived scene one ray or query per lane have in common (lbvh_path.hip: begin_walk, the
+"""What the entry points that walk the derived scene one ray or query per lane have in common (lbvh_walk.h, lbvh_walk.hip: begin_walk, the
 prologue they share; LBVH_LAUNCH_STATS, the one place that picks the counting or the plain instantiation of a walker;
 launch_per_query, the one launch of the point queries and the sphere and capsule casts; csr_query and csr_offsets, the count walk
 -> scan -> fill walk of every CSR answer — while each family keeps its own argument checks, whose text a row quotes): one
@@ -38,7 +38,7 @@ def _table(tris):
     """name -> (queries, extra arguments between count and the scene, outputs as (dtype, entries, required alignment in bytes),
     lbvh_last_error after a misaligned pointer).  The call is fn(ctx, queries, count, *extra, scene, *outputs), a CSR row's capacity
     last; the extra arguments are lbvh_point_crossings' directions, k, and the region rows' mode.  The message is the text of the
-    alignment check of the entry point's family in lbvh_path.hip, as LBVH_REQUIRE reports it ("invalid argument: " and the
+    alignment check of the entry point's family in lbvh_path.hip or lbvh_query_*.hip, as LBVH_REQUIRE reports it ("invalid argument: " and the
     condition) or, for the region rows, under the entry point's own name."""
     lay = L()
     rng = np.random.default_rng(23)

@@ -1,6 +1,6 @@
 """The lane refill of the per-lane walkers, and the overlap scan at scale.
 
-Every per-lane walk of lbvh_path.hip launches min(8192, ceil(count / 64)) one-wave workgroups; a wave owns a run of
+Every per-lane walk of lbvh_path.hip and lbvh_query_*.hip launches min(8192, ceil(count / 64)) one-wave workgroups; a wave owns a run of
 ceil(count / waves) consecutive queries and refills a lane from the run when the lane's query is finished.  For every call of
 at most 524 288 queries the run is at most 64 and the first hand-out takes all of it: no lane is ever refilled.  Here the refill
 runs: lbvh_debug_ray_waves caps the grid so that 1 500 queries make runs of 215 .. 1 501 (part 2), and calls of more than a

@@ -8,9 +8,9 @@ NAME=$1; shift
 CS=$R/unitysimpleraytracing_amd/csrc
 OUT=$R/build_exp
 mkdir -p $OUT/obj_$NAME
-for f in lbvh_api lbvh_sort lbvh_sort_sharded lbvh_build lbvh_trace lbvh_shade lbvh_path lbvh_segsort; do
+for f in $(sed -n 's/^SRCS *:= *//p' $CS/Makefile); do        # the one list of sources: csrc/Makefile
   /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off -fno-fast-math -Wall -Wno-unused-function "$@" \
-      -c $CS/$f.hip -o $OUT/obj_$NAME/$f.o &
+      -c $CS/$f -o $OUT/obj_$NAME/${f%.hip}.o &
 done
 wait
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o $OUT/liblbvh_$NAME.so $OUT/obj_$NAME/*.o

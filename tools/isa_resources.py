@@ -11,12 +11,19 @@ The gate for a change that must leave the device code alone: bo
 flags of each tree's csrc/Makefile, and every kernel's instruction stream is compared as text — comments and directive lines dropped,
 local labels (.LBB...) folded to one token, so that moved or renumbered source does not show.  One line per kernel, `same` or
 `DIFFERENT`, `missing` for a kernel only <tree a> has and `extra` for one only <tree b> has; the exit status is 1 unless every line
-says `same`."""
+says `same`.
+
+    python tools/isa_resources.py --compare <tree a> <tree b>
+
+The same over every .hip of each tree's own SRCS (csrc/Makefile), the kernels of a tree pooled by mangled name: a kernel that moved
+to another file is `same` where it is found (`old.hip -> new.hip`).  A kernel that two files of one tree hold is `duplicate` and
+fails the run like a difference: every kernel is instantiated in one translation unit."""
 import os
 import re
 import subprocess
 import sys
 import tempfile
+from concurrent.futures import ThreadPoolExecutor
 
 FIELDS = (("TotalSGPRs", "sgpr"), ("VGPRs", "vgpr"), ("ScratchSize [bytes/lane]", "scratch"), ("Occupancy [waves/SIMD]", "occ"),
           ("LDS Size [bytes/block]", "lds"))
@@ -79,16 +86,51 @@ def instruction_streams(tree, src):
     return streams
 
 
-def compare(tree_a, tree_b, src):
-    a, b = instruction_streams(tree_a, src), instruction_streams(tree_b, src)
-    pretty = demangle(sorted(set(a) | set(b)))
-    bad = 0
-    for name in sorted(pretty, key=pretty.get):
-        verdict = "missing" if name not in b else "extra" if name not in a else "same" if a[name] == b[name] else "DIFFERENT"
+def makefile_srcs(csrc):
+    m = re.search(r"^SRCS\s*:=\s*(.+)$", open(os.path.join(csrc, "Makefile")).read(), re.M)
+    return m.group(1).split()
+
+
+def pooled_streams(tree):
+    """Every .hip of the tree's own SRCS: ({mangled kernel name: (file, instructions)}, [(name, file, other file)] for a kernel two files hold)"""
+    srcs = makefile_srcs(os.path.join(os.path.abspath(tree), "unitysimpleraytracing_amd", "csrc"))
+    with ThreadPoolExecutor(max_workers=min(8, os.cpu_count() or 1)) as pool:
+        per_file = list(pool.map(lambda src: instruction_streams(tree, src), srcs))
+    kernels, twice = {}, []
+    for src, streams in zip(srcs, per_file):
+        for name, text in streams.items():
+            if name in kernels:
+                twice.append((name, kernels[name][0], src))
+            else:
+                kernels[name] = (src, text)
+    return kernels, twice
+
+
+def compare(tree_a, tree_b, src=None):
+    if src:
+        a = {name: (src, text) for name, text in instruction_streams(tree_a, src).items()}
+        b = {name: (src, text) for name, text in instruction_streams(tree_b, src).items()}
+        twice = []
+    else:
+        (a, twice_a), (b, twice_b) = pooled_streams(tree_a), pooled_streams(tree_b)
+        twice = [(tree_a,) + t for t in twice_a] + [(tree_b,) + t for t in twice_b]
+    pretty = demangle(sorted(set(a) | set(b) | {t[1] for t in twice}))
+    bad, per_file = len(twice), {}
+    for tree, name, first, second in twice:
+        print(f"{first} + {second}: duplicate {pretty[name]}  in {tree}")
+    for name in sorted(set(a) | set(b), key=lambda n: ((a.get(n) or b[n])[0], pretty[n])):
+        verdict = "missing" if name not in b else "extra" if name not in a else "same" if a[name][1] == b[name][1] else "DIFFERENT"
         bad += verdict != "same"
-        insts = sum(1 for ln in (a.get(name) or b[name]).splitlines() if ln != ".LBB:")
-        print(f"{src}: {verdict:9s} {pretty[name]}  insts={insts}")
-    print(f"{src}: {len(pretty)} kernels, {len(pretty) - bad} same, {bad} not")
+        was, now = (a.get(name) or b[name])[0], (b.get(name) or a[name])[0]
+        count = per_file.setdefault(was, [0, 0])
+        count[0] += 1
+        count[1] += verdict == "same"
+        insts = sum(1 for ln in (a.get(name) or b[name])[1].splitlines() if ln != ".LBB:")
+        print(f"{was if was == now else was + ' -> ' + now}: {verdict:9s} {pretty[name]}  insts={insts}")
+    for was, (n, same) in sorted(per_file.items()):
+        print(f"{was}: {n} kernels, {same} same, {n - same} not")
+    if not src:
+        print(f"all sources: {len(set(a) | set(b))} kernels, {bad} not same or duplicate")
     return bad
 
 

@@ -820,7 +820,7 @@ static void evaluate(const char* name, const tree_t* t, double build_s)
 
 // ---- k-wide collapses of a binary tree for the per-ray walk (round 6, VERDICT r5 item 7: decide cfg5's 8-wide node HERE) -------------------
 // A wide node = a binary node with its children opened by surface — the internal child with the largest box area is replaced by its
-// two children — until it has k children or only leaves are left.  k = 4 is the product's four-wide form (lbvh_path.hip: up to four
+// two children — until it has k children or only leaves are left.  k = 4 is the product's four-wide form (lbvh_walk.hip: up to four
 // child boxes per 128-byte line).  k = 8 fits one 128-byte line only with boxes on a node-local 8-bit grid (origin + extent of the
 // node: 24 B, 8 x 6 B of quantised corners, 8 x 4 B of references = 104 B): `quant` rounds every child box OUTWARD onto that grid,
 // as such a node would have to.  Counted per diffuse bounce ray: node lines fetched (one per wide node visited) and triangle lines.

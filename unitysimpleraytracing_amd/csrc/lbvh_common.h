@@ -143,7 +143,7 @@ struct lbvh_context {
     struct { const void *states, *hits; size_t count; uint32_t bounce, turn; bool valid; } ray_list = {nullptr, nullptr, 0, 0, 0, false};
     uint32_t ray_stack_lds = 16;              // lbvh_debug_ray_stack_split
     uint32_t ray_stack_deep = 0xFFFFFFFFu;    // lbvh_debug_ray_stack_limit: entries of the device-memory part the walkers may use
-    uint32_t ray_max_waves = 0;               // lbvh_debug_ray_waves: cap of a per-lane walk's grid (0: kRayWaves)
+    uint32_t ray_max_waves = 0;               // lbvh_debug_ray_waves: cap of a per-lane walk's grid (0: kRayWaves, lbvh_walk.h)
     size_t ray_scratch_bytes = 0;
     // the derived scene as four-wide nodes for the per-ray walk: made by the first lbvh_trace_rays / bounce after a rebuild
     void* wide_nodes = nullptr;

@@ -8,6 +8,7 @@
 #include <type_traits>
 #include "lbvh_common.h"
 #include "lbvh_rt.h"
+#include "lbvh_walk.h"
 
 namespace {
 
@@ -52,19 +53,7 @@ __global__ __launch_bounds__(256) void path_begin_kernel(lbvh_camera cam, lbvh_p
 // ---- arbitrary rays: one ray per lane over the derived traversal scene -----------------------------------
 // Secondary rays are incoherent, so the packet walk of lbvh_trace.hip does not apply: every lane walks on its
 // own (64-byte fused nodes, near child first, boxes beyond the best hit skipped) with a stack of its own, laid out
-// [entry][lane].  One wave per workgroup, no barriers.
-// The first kRayStackLds entries of a lane's stack are in LDS (4 KB per wave: all 32 wave slots of a CU fit; with 34
-// entries in LDS only 18 did and the four bounces took 1.70 ms instead of 1.46), deeper ones — rare: the fused tree
-// is walked near child first — in a per-wave slab of global memory, up to 64 entries in all like the reference's
-// stack (Raytracing.compute:113).
-constexpr int kRayStackLds = 16;
-constexpr int kRayStackDeep = 48;
-// the four-wide walk further down: three siblings can wait per level.  (Neither stack can overflow on a tree of this library:
-// the derived tree is a radix tree over unique 32-bit keys, at most 32 levels deep — 32 waiting entries for the binary walk,
-// 3 x 32 for the four-wide one, whose levels are binary levels or pairs of them.)
-constexpr int kWideStackLds = 16;
-constexpr int kWideStackDeep = 112;
-
+// [entry][lane].  One wave per workgroup, no barriers.  The stack split, the grid, the lane refill and the four-wide node: lbvh_walk.h.
 // Live rays only: alive_rays_kernel writes the miss record of every dead ray and compacts the indices of the live
 // ones (after the first bounce more than half of a frame's paths have left the scene).  (Sorting the live rays by direction octant + Morton code of the origin on top of this was
 // measured: the sort costs 0.15 ms per bounce and the walk does not get faster.  Measured again in round 5 on the four-wide
@@ -92,27 +81,6 @@ __global__ __launch_bounds__(256) void alive_rays_kernel(const lbvh_path_state* 
     __syncthreads();
     if (alive) list[s_base + wave_ofs + mbcnt64(m)] = (uint32_t)i;
 }
-
-// One ray per lane; a wave owns a run of consecutive entries of the live-ray list and REFILLS a lane from it as
-// soon as that lane's ray is finished, so a wave's run time is the sum of its rays' steps / 64 and not the step
-// count of its longest ray (incoherent rays: mean ~100 steps, maxima of several hundred).  The grid is a fixed
-// number of waves (every wave slot of the chip once) and the live rays are dealt out evenly: at least 64 per wave.
-// Measured per frame of 4 bounces: no refill 3.75 ms; fixed runs of 128 / 256 / 512 rays 1.83 / 2.62 / 4.44 ms
-// (long runs leave most of the chip empty).
-constexpr uint32_t kRayWaves = 8192;
-// ray scratch: [live-ray count (256 B) | indices of the live rays | deep stack slabs of the launch's waves]
-static inline uint32_t ray_waves_of(size_t count) { return (uint32_t)std::min<size_t>(kRayWaves, (count + LBVH_WAVE - 1) / LBVH_WAVE); }
-// the slab is indexed by blockIdx.x: one launch needs ray_waves_of(count) of them (a 64-ray call: 12 KB, not 96 MB)
-static inline size_t deep_bytes(size_t count) { return (size_t)ray_waves_of(count) * std::max(kWideStackDeep, kRayStackDeep) * LBVH_WAVE * 4; }
-static inline size_t list_bytes(size_t count) { return (count * 4 + 255) & ~(size_t)255; }
-// ray scratch: [two live-ray counters (256 B: words 0 and 16) | live-ray list 0 | live-ray list 1 | deep stack slabs].  Two lists
-// take turns (round 5): lbvh_path_bounce b builds the list of the paths that go on FROM the list bounce b - 1 left behind, not
-// from a scan over all pixels — after the first bounce most of a frame's paths are dead (870 k, 350 k, 150 k, 60 k live of 2 M).
-static inline size_t ray_scratch_bytes_for(size_t count);
-static inline uint32_t* ray_counter(lbvh_context* ctx, uint32_t turn) { return (uint32_t*)ctx->ray_scratch + 16u * turn; }
-static inline uint32_t* ray_list(lbvh_context* ctx, size_t count, uint32_t turn) { return (uint32_t*)((char*)ctx->ray_scratch + 256 + turn * list_bytes(count)); }
-static inline uint32_t* deep_stacks(lbvh_context* ctx, size_t count) { return (uint32_t*)((char*)ctx->ray_scratch + 256 + 2 * list_bytes(count)); }
-static inline size_t ray_scratch_bytes_for(size_t count) { return 256 + 2 * list_bytes(count) + deep_bytes(count); }
 
 // The three walkers below serve two ray sources and three queries (template arguments PLAIN, Q):
 //   PLAIN = false: path states, the live ones listed in `list` (*n_alive of them), one t_min for all (lbvh_trace_rays, the bounces)
@@ -272,107 +240,6 @@ __global__ __launch_bounds__(64) void trace_rays_kernel(const walk_src<PLAIN>* _
                 active = false;
             }
         }
-    }
-}
-
-// ---- the per-ray walk over four-wide nodes -------------------------------------------------------------------
-// The per-ray kernel's time follows the number of steps its lanes take (profiles/r3: requests, bytes and L1 traffic per
-// step could be halved without moving it), so the derived scene gets a second, shallower form for rays that do not
-// come in packets: every binary node with its larger children opened once or twice = up to four child boxes in one
-// 128-byte line.  Same leaves, same boxes, same triangle lines: which triangles a ray can meet does not change, and
-// with ties going to the lower triangle index neither does the record it ends with.
-struct alignas(128) lbvh_wide_node {
-    float lo[3][4];          // [axis][slot]
-    float hi[3][4];
-    uint32_t ref[4];         // node index | LEAF + triangle line | kWideEmpty
-    uint32_t pad[4];
-};
-static_assert(sizeof(lbvh_wide_node) == 128, "wide node must be one 128-byte line");
-constexpr uint32_t kWideEmpty = 0xFFFFFFFFu;
-
-struct wide_slot { float mn[3], mx[3]; uint32_t ref; };
-
-__device__ __forceinline__ float half_area(const wide_slot& b)
-{
-    const float dx = b.mx[0] - b.mn[0], dy = b.mx[1] - b.mn[1], dz = b.mx[2] - b.mn[2];
-    return dx * dy + dy * dz + dz * dx;
-}
-
-__device__ __forceinline__ void children_of(const lbvh_fast_node* __restrict__ nodes, uint32_t i, wide_slot& l, wide_slot& r)
-{
-    const float4* q = reinterpret_cast<const float4*>(&nodes[i]);
-    const float4 q0 = q[0], q1 = q[1], q2 = q[2], q3 = q[3];
-    l.mn[0] = q0.x; l.mn[1] = q0.y; l.mn[2] = q0.z; l.mx[0] = q1.x; l.mx[1] = q1.y; l.mx[2] = q1.z; l.ref = __float_as_uint(q0.w);
-    r.mn[0] = q2.x; r.mn[1] = q2.y; r.mn[2] = q2.z; r.mx[0] = q3.x; r.mx[1] = q3.y; r.mx[2] = q3.z; r.ref = __float_as_uint(q1.w);
-}
-
-// one thread per binary node: its two children, then twice the internal child with the largest surface opened
-__global__ __launch_bounds__(256) void collapse_wide_kernel(const lbvh_fast_node* __restrict__ nodes, uint32_t n_internal,
-                                                            lbvh_wide_node* __restrict__ wide)
-{
-    const uint32_t i = blockIdx.x * 256 + threadIdx.x;
-    if (i >= n_internal) return;
-    wide_slot s[4];
-    children_of(nodes, i, s[0], s[1]);
-    s[2].ref = kWideEmpty; s[3].ref = kWideEmpty;
-#pragma unroll
-    for (int k = 2; k < 4; k++)
-#pragma unroll
-        for (int a = 0; a < 3; a++) { s[k].mn[a] = 0.0f; s[k].mx[a] = 0.0f; }
-#pragma unroll
-    for (int round = 0; round < 2; round++) {
-        int open = -1;
-        float open_area = -1.0f;
-#pragma unroll
-        for (int k = 0; k < 2 + round; k++) {
-            const float a = half_area(s[k]);
-            if (!(s[k].ref & 0x80000000u) && (open < 0 || a > open_area)) { open = k; open_area = a; }
-        }
-        if (open < 0) break;
-        uint32_t parent = 0;
-#pragma unroll
-        for (int k = 0; k < 2 + round; k++)
-            if (k == open) parent = s[k].ref;
-        wide_slot l, r;
-        children_of(nodes, parent, l, r);
-#pragma unroll
-        for (int k = 0; k < 2 + round; k++)
-            if (k == open) s[k] = l;
-        s[2 + round] = r;
-    }
-    lbvh_wide_node out;
-#pragma unroll
-    for (int k = 0; k < 4; k++) {
-#pragma unroll
-        for (int a = 0; a < 3; a++) { out.lo[a][k] = s[k].mn[a]; out.hi[a][k] = s[k].mx[a]; }
-        out.ref[k] = s[k].ref;
-        out.pad[k] = 0u;
-    }
-    float4* dst = reinterpret_cast<float4*>(&wide[i]);
-    const float4* src = reinterpret_cast<const float4*>(&out);
-#pragma unroll
-    for (int k = 0; k < 8; k++) dst[k] = src[k];
-}
-
-__device__ __forceinline__ uint32_t pick4(const uint4 v, uint32_t k) { return k == 0u ? v.x : (k == 1u ? v.y : (k == 2u ? v.z : v.w)); }
-
-// RayBoxIntersection (Raytracing.compute:75-87) on one slot of a wide node: the same six products, minima and maxima
-__device__ __forceinline__ bool wide_box(float lx, float ly, float lz, float hx, float hy, float hz, const ray_t& r, float& tmin_out)
-{
-    return ray_box(make_float4(lx, ly, lz, 0.0f), make_float4(hx, hy, hz, 0.0f), r, tmin_out);
-}
-
-// what a launch of the per-ray walk did (lbvh_ray_stats_target: the algorithmic bytes of cfg5's roofline): wave reduction,
-// one atomic per counter per wave at the end of the kernel
-__device__ __forceinline__ void add_ray_stats(lbvh_ray_stats* stats, uint32_t rays, uint32_t steps, uint32_t tris)
-{
-    uint32_t v[3] = {rays, steps, tris};
-#pragma unroll
-    for (int k = 0; k < 3; k++) v[k] = wave_total_from_inclusive(wave_inclusive_sum(v[k]));
-    if (lane_id() == 0) {
-        atomicAdd((unsigned long long*)&stats->rays, (unsigned long long)v[0]);
-        atomicAdd((unsigned long long*)&stats->node_fetches, (unsigned long long)v[1]);
-        atomicAdd((unsigned long long*)&stats->triangle_tests, (unsigned long long)v[2]);
     }
 }
 
@@ -1671,168 +1538,6 @@ __global__ __launch_bounds__(64) void k_closest_wide_kernel(const lbvh_point_que
     if (STATS) add_ray_stats(stats, n_queries, n_steps, n_tris);
 }
 
-// lbvh_trace_k_closest: the walk of trace_rays_wide_kernel<true, kClosest> with "closest so far" replaced by "k-th closest so far",
-// and the per-lane list of k_closest_wide_kernel: three arrays [slot][lane] of t bits, triangle index and the index of the
-// triangle's line, `cap` slots per lane, dynamic LDS sized at the launch from k (768 * k bytes per wave).  (best_t, best_tri) is the
-// pruning bound: (T, 0) while fewer than k candidates are held — the state the closest walk starts in, so t == T is never taken —,
-// then the list's last entry; a leaf is taken by the closest walk's own comparison against it and inserted by shifting the entries
-// that sort after it.  Boxes are skipped on their ENTRY distance only, strictly beyond the bound.  With k = 1 every decision is
-// the closest walk's.  u and v are not carried: when a ray's walk ends, ray_fast_triangle is evaluated once more on the stored
-// line of each survivor — the same operations on the same values, hence the same words — and the row is written, padded with
-// miss records.
-template <bool STATS>
-__global__ __launch_bounds__(64) void k_hits_wide_kernel(const lbvh_ray* __restrict__ rays, uint32_t total, uint32_t cap,
-                                                         const lbvh_wide_node* __restrict__ wide,
-                                                         const lbvh_fast_node* __restrict__ lines,
-                                                         lbvh_hit* __restrict__ out,               // [total][cap]
-                                                         uint32_t* __restrict__ found_out,         // [total] or nullptr
-                                                         uint32_t* __restrict__ deep,     // [gridDim.x][kWideStackDeep][64]
-                                                         uint32_t lds_depth,              // <= kWideStackLds
-                                                         uint32_t deep_cap,               // <= kWideStackDeep
-                                                         uint32_t* __restrict__ fault, lbvh_ray_stats* stats)
-{
-    __shared__ uint32_t s_stack[kWideStackLds][LBVH_WAVE];
-    extern __shared__ uint32_t s_list[];                 // [3][cap][64]: t bits | triangle index | line index
-    const uint32_t lane = threadIdx.x;
-    uint32_t* const l_t = s_list + lane;
-    uint32_t* const l_tri = l_t + cap * LBVH_WAVE;
-    uint32_t* const l_line = l_tri + cap * LBVH_WAVE;
-    uint32_t* my_deep = deep + (size_t)blockIdx.x * (kWideStackDeep * LBVH_WAVE) + threadIdx.x;
-    const uint32_t run = max((total + gridDim.x - 1) / gridDim.x, 32u);
-    uint32_t next = blockIdx.x * run;
-    if (next >= total) return;
-    const uint32_t end = min(next + run, total);
-    uint32_t n_rays = 0, n_steps = 0, n_tris = 0;
-    const float4 miss_record = make_float4(LBVH_MAX_FLOAT, __uint_as_float(0u), 0.0f, 0.0f);
-
-    bool active = false;
-    uint32_t i = 0;
-    ray_t ray = {};
-    float lo = 0.0f, best_t = LBVH_MAX_FLOAT;
-    uint32_t best_tri = 0, held = 0, sp = 0, node = 0;
-    auto push = [&](uint32_t ref) {
-        if (sp < lds_depth) { s_stack[sp][lane] = ref; sp++; }
-        else if (sp < lds_depth + deep_cap) { my_deep[(sp - lds_depth) * LBVH_WAVE] = ref; sp++; }
-        // a dropped entry would be a silently wrong row: report it, as the other walkers do (lbvh_debug_ray_stack_limit provokes it)
-        else __hip_atomic_store(fault, LBVH_FAULT_RAY_STACK, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-    };
-    for (;;) {
-        const uint64_t idle = __ballot(!active);
-        if (idle != 0 && next < end) {
-            if (!active) {
-                const uint32_t k = next + mbcnt64(idle);
-                if (k < end) {
-                    i = k;
-                    const float4* r = reinterpret_cast<const float4*>(&rays[k]);
-                    const float4 o = r[0], d = r[1];
-                    ray.ox = o.x; ray.oy = o.y; ray.oz = o.z;
-                    ray.dx = d.x; ray.dy = d.y; ray.dz = d.z;
-                    ray.ix = 1.0f / d.x; ray.iy = 1.0f / d.y; ray.iz = 1.0f / d.z;
-                    lo = o.w;
-                    best_t = fminf(d.w, LBVH_MAX_FLOAT);         // T: candidates lie in (t_min, T)
-                    best_tri = 0; held = 0; sp = 0; node = 0;
-                    active = o.w < d.w;                          // load_plain_ray's rule: false for NaN bounds too
-                    if (!active) {                               // no candidates, no walk: the whole row is miss records
-                        float4* row = reinterpret_cast<float4*>(out) + (size_t)k * cap;
-                        for (uint32_t j = 0; j < cap; j++) row[j] = miss_record;
-                        if (found_out) found_out[k] = 0u;
-                    }
-                    if (STATS && active) n_rays++;
-                }
-            }
-            next += (uint32_t)__popcll(idle);
-        }
-        if (!__any(active) && next >= end) break;
-        if (active) {
-            if (STATS) n_steps++;
-            const float4* w = reinterpret_cast<const float4*>(&wide[node]);
-            const float4 lox = w[0], loy = w[1], loz = w[2], hix = w[3], hiy = w[4], hiz = w[5];
-            const uint4 ref = reinterpret_cast<const uint4*>(w)[6];
-            float t0, t1, t2, t3;
-            const bool h0 = wide_box(lox.x, loy.x, loz.x, hix.x, hiy.x, hiz.x, ray, t0) && !(t0 > best_t) && ref.x != kWideEmpty;
-            const bool h1 = wide_box(lox.y, loy.y, loz.y, hix.y, hiy.y, hiz.y, ray, t1) && !(t1 > best_t) && ref.y != kWideEmpty;
-            const bool h2 = wide_box(lox.z, loy.z, loz.z, hix.z, hiy.z, hiz.z, ray, t2) && !(t2 > best_t) && ref.z != kWideEmpty;
-            const bool h3 = wide_box(lox.w, loy.w, loz.w, hix.w, hiy.w, hiz.w, ray, t3) && !(t3 > best_t) && ref.w != kWideEmpty;
-            // leaf slots first: a lane's leaves one after the other, every lane's k-th at the same time
-            uint32_t leaves = (h0 && (ref.x >> 31) ? 1u : 0u) | (h1 && (ref.y >> 31) ? 2u : 0u) | (h2 && (ref.z >> 31) ? 4u : 0u) |
-                              (h3 && (ref.w >> 31) ? 8u : 0u);
-            while (leaves != 0u) {
-                const uint32_t k = (uint32_t)__builtin_ctz(leaves);
-                leaves &= leaves - 1u;
-                if (STATS) n_tris++;
-                const uint32_t line = pick4(ref, k) & 0x7FFFFFFFu;
-                float4 v0, v1, v2;
-                unpack_fast_triangle(reinterpret_cast<const float4*>(&lines[line]), v0, v1, v2);
-                float u = 0.0f, v = 0.0f;
-                const float dist = ray_fast_triangle(ray, v0, v1, v2, u, v);
-                const uint32_t tri = __float_as_uint(v0.w);
-                const float entry = k == 0u ? t0 : (k == 1u ? t1 : (k == 2u ? t2 : t3));
-                // (best_t, best_tri) is (T, 0) until k are held: dist == T is never taken.  Then it is the k-th held: the candidate
-                // must sort before it, ties by the lower triangle index
-                if (dist > lo && hit_counts(dist, entry) && (dist < best_t || (dist == best_t && tri < best_tri))) {
-                    uint32_t j = min(held, cap - 1u);    // the slot that becomes free: the end of the list, or its dropped last entry
-                    while (j != 0u) {
-                        const float tj = __uint_as_float(l_t[(j - 1u) * LBVH_WAVE]);
-                        const uint32_t ij = l_tri[(j - 1u) * LBVH_WAVE];
-                        if (!(dist < tj || (dist == tj && tri < ij))) break;
-                        l_t[j * LBVH_WAVE] = __float_as_uint(tj);
-                        l_tri[j * LBVH_WAVE] = ij;
-                        l_line[j * LBVH_WAVE] = l_line[(j - 1u) * LBVH_WAVE];
-                        j--;
-                    }
-                    l_t[j * LBVH_WAVE] = __float_as_uint(dist);
-                    l_tri[j * LBVH_WAVE] = tri;
-                    l_line[j * LBVH_WAVE] = line;
-                    held = min(held + 1u, cap);
-                    if (held == cap) {
-                        best_t = __uint_as_float(l_t[(cap - 1u) * LBVH_WAVE]);
-                        best_tri = l_tri[(cap - 1u) * LBVH_WAVE];
-                    }
-                }
-            }
-            // nodes to enter, ordered by entry distance: the order key is the distance's bit pattern (non-negative floats
-            // order like integers) with the slot number in its two lowest bits.  (best_t may have shrunk in the leaf loop since
-            // h0 .. h3 were formed: the entry distances are compared with it once more)
-            constexpr uint32_t none = 0xFFFFFFFFu;
-            uint32_t k0 = h0 && !(ref.x >> 31) && !(t0 > best_t) ? ((__float_as_uint(fmaxf(t0, 0.0f)) & ~3u) | 0u) : none;
-            uint32_t k1 = h1 && !(ref.y >> 31) && !(t1 > best_t) ? ((__float_as_uint(fmaxf(t1, 0.0f)) & ~3u) | 1u) : none;
-            uint32_t k2 = h2 && !(ref.z >> 31) && !(t2 > best_t) ? ((__float_as_uint(fmaxf(t2, 0.0f)) & ~3u) | 2u) : none;
-            uint32_t k3 = h3 && !(ref.w >> 31) && !(t3 > best_t) ? ((__float_as_uint(fmaxf(t3, 0.0f)) & ~3u) | 3u) : none;
-            {   // five compare-exchanges
-                uint32_t a, b;
-                a = min(k0, k1); b = max(k0, k1); k0 = a; k1 = b;
-                a = min(k2, k3); b = max(k2, k3); k2 = a; k3 = b;
-                a = min(k0, k2); b = max(k0, k2); k0 = a; k2 = b;
-                a = min(k1, k3); b = max(k1, k3); k1 = a; k3 = b;
-                a = min(k1, k2); b = max(k1, k2); k1 = a; k2 = b;
-            }
-            if (k0 != none) {
-                if (k3 != none) push(pick4(ref, k3 & 3u));       // farthest first: the nearest waiting sibling is popped first
-                if (k2 != none) push(pick4(ref, k2 & 3u));
-                if (k1 != none) push(pick4(ref, k1 & 3u));
-                node = pick4(ref, k0 & 3u);
-            } else if (sp != 0) {
-                sp--;
-                node = sp < lds_depth ? s_stack[sp][lane] : my_deep[(sp - lds_depth) * LBVH_WAVE];
-            } else {
-                // the row: the survivors in order, t, u and v from their lines again, then miss records
-                float4* row = reinterpret_cast<float4*>(out) + (size_t)i * cap;
-                for (uint32_t j = 0; j < held; j++) {
-                    float4 v0, v1, v2;
-                    unpack_fast_triangle(reinterpret_cast<const float4*>(&lines[l_line[j * LBVH_WAVE]]), v0, v1, v2);
-                    float u = 0.0f, v = 0.0f;
-                    const float dist = ray_fast_triangle(ray, v0, v1, v2, u, v);
-                    row[j] = make_float4(dist, v0.w, u, v);
-                }
-                for (uint32_t j = held; j < cap; j++) row[j] = miss_record;
-                if (found_out) found_out[i] = held;
-                active = false;
-            }
-        }
-    }
-    if (STATS) add_ray_stats(stats, n_rays, n_steps, n_tris);
-}
-
 // ---- overlap queries: every triangle in a box / within a distance, as a CSR list (include/lbvh.h) -----------------------
 // The first queries whose output length is not known at the call: a COUNT walk writes one 32-bit count per query into the ray
 // scratch, three small kernels scan the counts into the caller's 64-bit offsets, and a FILL walk — the same kernel, the same
@@ -1982,212 +1687,6 @@ __global__ __launch_bounds__(64) void overlap_wide_kernel(const float4* __restri
         }
     }
     if (STATS) add_ray_stats(stats, n_queries, n_steps, n_tris);
-}
-
-// The scan of the counts into the 64-bit offsets: tiles of 1024 counts (256 threads x one 16-byte load), (1) a sum per tile,
-// (2) one workgroup scans the tile sums in place, (3) every tile scans its own counts on top of its prefix and writes
-// offsets[first .. first + 1024) — offsets[total] = the grand total included, so the tiles cover total + 1 outputs.
-constexpr uint32_t kScanTile = 1024;
-
-__device__ __forceinline__ uint64_t wave_inclusive_sum_u64(uint64_t v)
-{
-    const uint32_t lane = lane_id();
-#pragma unroll
-    for (int d = 1; d < LBVH_WAVE; d <<= 1) {
-        const uint64_t o = __shfl_up(v, d, LBVH_WAVE);
-        if (lane >= (uint32_t)d) v += o;
-    }
-    return v;
-}
-
-// the four counts of a thread of a tile; counts at or beyond `total` read as 0
-__device__ __forceinline__ uint4 load_tile_counts(const uint32_t* __restrict__ counts, uint64_t first, uint32_t total)
-{
-    uint4 c = make_uint4(0u, 0u, 0u, 0u);
-    if (first + 3 < total) c = reinterpret_cast<const uint4*>(counts)[first >> 2];
-    else {
-        if (first < total) c.x = counts[first];
-        if (first + 1 < total) c.y = counts[first + 1];
-        if (first + 2 < total) c.z = counts[first + 2];
-    }
-    return c;
-}
-
-__global__ __launch_bounds__(256) void overlap_tile_sums_kernel(const uint32_t* __restrict__ counts, uint32_t total, uint64_t* __restrict__ sums)
-{
-    __shared__ uint64_t s_wave[4];
-    const uint4 c = load_tile_counts(counts, (uint64_t)blockIdx.x * kScanTile + threadIdx.x * 4u, total);
-    const uint64_t incl = wave_inclusive_sum_u64(((uint64_t)c.x + c.y) + ((uint64_t)c.z + c.w));
-    if (lane_id() == LBVH_WAVE - 1) s_wave[threadIdx.x / LBVH_WAVE] = incl;
-    __syncthreads();
-    if (threadIdx.x == 0) sums[blockIdx.x] = (s_wave[0] + s_wave[1]) + (s_wave[2] + s_wave[3]);
-}
-
-__global__ __launch_bounds__(1024) void overlap_scan_sums_kernel(uint64_t* __restrict__ sums, uint32_t n_tiles)
-{
-    __shared__ uint64_t s_wave[16];
-    const uint32_t wave = threadIdx.x / LBVH_WAVE;
-    uint64_t carry = 0;
-    for (uint32_t base = 0; base < n_tiles; base += 1024u) {
-        const uint32_t t = base + threadIdx.x;
-        const uint64_t v = t < n_tiles ? sums[t] : 0;
-        const uint64_t incl = wave_inclusive_sum_u64(v);
-        if (lane_id() == LBVH_WAVE - 1) s_wave[wave] = incl;
-        __syncthreads();
-        uint64_t before = 0, all = 0;
-#pragma unroll
-        for (uint32_t k = 0; k < 16u; k++) {
-            const uint64_t s = s_wave[k];
-            if (k < wave) before += s;
-            all += s;
-        }
-        if (t < n_tiles) sums[t] = carry + before + (incl - v);
-        carry += all;
-        __syncthreads();
-    }
-}
-
-__global__ __launch_bounds__(256) void overlap_offsets_kernel(const uint32_t* __restrict__ counts, uint32_t total,
-                                                              const uint64_t* __restrict__ tile_prefix,   // nullptr: one tile
-                                                              uint64_t* __restrict__ offsets)             // total + 1 words
-{
-    __shared__ uint64_t s_wave[4];
-    const uint64_t first = (uint64_t)blockIdx.x * kScanTile + threadIdx.x * 4u;
-    const uint4 c = load_tile_counts(counts, first, total);
-    const uint64_t mine = ((uint64_t)c.x + c.y) + ((uint64_t)c.z + c.w);
-    const uint64_t incl = wave_inclusive_sum_u64(mine);
-    const uint32_t wave = threadIdx.x / LBVH_WAVE;
-    if (lane_id() == LBVH_WAVE - 1) s_wave[wave] = incl;
-    __syncthreads();
-    uint64_t o0 = (tile_prefix ? tile_prefix[blockIdx.x] : 0) + (incl - mine);
-#pragma unroll
-    for (uint32_t k = 0; k < 3u; k++)
-        if (k < wave) o0 += s_wave[k];
-    const uint64_t o1 = o0 + c.x, o2 = o1 + c.y, o3 = o2 + c.z;
-    if (first + 3 <= total && ((uintptr_t)offsets & 15) == 0) {
-        ulonglong2* dst = reinterpret_cast<ulonglong2*>(offsets + first);
-        dst[0] = make_ulonglong2(o0, o1);
-        dst[1] = make_ulonglong2(o2, o3);
-    } else {
-        if (first <= total) offsets[first] = o0;
-        if (first + 1 <= total) offsets[first + 1] = o1;
-        if (first + 2 <= total) offsets[first + 2] = o2;
-        if (first + 3 <= total) offsets[first + 3] = o3;
-    }
-}
-
-// ---- every hit along a ray as a CSR list (lbvh_gather_hits, include/lbvh.h) --------------------------------------------
-// The frame of overlap_wide_kernel (count walk, the scan above, fill walk: the same kernel, the same decisions, so a segment can
-// never outgrow its slot) around the ray arithmetic of trace_rays_wide_kernel<true, kCount>: load_plain_ray's activity test and T,
-// the slab tests against the FIXED bound T, ray_fast_triangle, hit_counts(dist, entry) and lo < dist < T.  Nothing shrinks and no
-// order is promised, so the ordering network of the ray walkers is not needed: the first passing inner slot is entered, the
-// others wait on the stack.  A candidate's record is the float4 put_hit would write were it the nearest: {dist, tri, u, v}.
-// A kernel of its own and not a fourth walk_query: a new parameter would move the arguments of every other instantiation.
-template <bool FILL, bool STATS>
-__global__ __launch_bounds__(64) void gather_hits_wide_kernel(const lbvh_ray* __restrict__ rays, uint32_t total,
-                                                              const lbvh_wide_node* __restrict__ wide,
-                                                              const lbvh_fast_node* __restrict__ lines,
-                                                              uint32_t* __restrict__ counts,            // !FILL: candidates of ray k
-                                                              const uint64_t* __restrict__ offsets,     // FILL: where segment k starts
-                                                              lbvh_hit* __restrict__ hits, uint64_t capacity,
-                                                              uint32_t* __restrict__ deep,     // [gridDim.x][kWideStackDeep][64]
-                                                              uint32_t lds_depth,              // <= kWideStackLds
-                                                              uint32_t deep_cap,               // <= kWideStackDeep
-                                                              uint32_t* __restrict__ fault, lbvh_ray_stats* stats)
-{
-    __shared__ uint32_t s_stack[kWideStackLds][LBVH_WAVE];
-    uint32_t* my_deep = deep + (size_t)blockIdx.x * (kWideStackDeep * LBVH_WAVE) + threadIdx.x;
-    const uint32_t lane = threadIdx.x;
-    const uint32_t run = max((total + gridDim.x - 1) / gridDim.x, 32u);
-    uint32_t next = blockIdx.x * run;
-    if (next >= total) return;
-    const uint32_t end = min(next + run, total);
-    uint32_t n_rays = 0, n_steps = 0, n_tris = 0;
-
-    bool active = false;
-    uint32_t i = 0;
-    ray_t ray = {};
-    float lo = 0.0f, T = LBVH_MAX_FLOAT;
-    uint32_t n_found = 0, sp = 0, node = 0;
-    uint64_t pos = 0;                                    // FILL: where this lane's next record goes
-    auto push = [&](uint32_t ref) {
-        if (sp < lds_depth) { s_stack[sp][lane] = ref; sp++; }
-        else if (sp < lds_depth + deep_cap) { my_deep[(sp - lds_depth) * LBVH_WAVE] = ref; sp++; }
-        // a dropped entry would be a silently short segment: report it, as the other walkers do (lbvh_debug_ray_stack_limit provokes it)
-        else __hip_atomic_store(fault, LBVH_FAULT_RAY_STACK, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-    };
-    for (;;) {
-        const uint64_t idle = __ballot(!active);
-        if (idle != 0 && next < end) {
-            if (!active) {
-                const uint32_t k = next + mbcnt64(idle);
-                if (k < end) {
-                    i = k;
-                    const float4* r = reinterpret_cast<const float4*>(&rays[k]);
-                    const float4 o = r[0], d = r[1];
-                    ray.ox = o.x; ray.oy = o.y; ray.oz = o.z;
-                    ray.dx = d.x; ray.dy = d.y; ray.dz = d.z;
-                    ray.ix = 1.0f / d.x; ray.iy = 1.0f / d.y; ray.iz = 1.0f / d.z;
-                    lo = o.w;
-                    T = fminf(d.w, LBVH_MAX_FLOAT);              // candidates lie in (t_min, T)
-                    active = o.w < d.w;                          // load_plain_ray's rule: false for NaN bounds too
-                    sp = 0; node = 0;
-                    if constexpr (FILL) { if (active) pos = offsets[k]; }      // (reloaded at every refill: a lane serves many rays)
-                    else { n_found = 0; if (!active) counts[k] = 0u; }
-                    if (STATS && active) n_rays++;
-                }
-            }
-            next += (uint32_t)__popcll(idle);
-        }
-        if (!__any(active) && next >= end) break;
-        if (active) {
-            if (STATS) n_steps++;
-            const float4* w = reinterpret_cast<const float4*>(&wide[node]);
-            const float4 lox = w[0], loy = w[1], loz = w[2], hix = w[3], hiy = w[4], hiz = w[5];
-            const uint4 ref = reinterpret_cast<const uint4*>(w)[6];
-            float t0, t1, t2, t3;
-            const bool h0 = wide_box(lox.x, loy.x, loz.x, hix.x, hiy.x, hiz.x, ray, t0) && !(t0 > T) && ref.x != kWideEmpty;
-            const bool h1 = wide_box(lox.y, loy.y, loz.y, hix.y, hiy.y, hiz.y, ray, t1) && !(t1 > T) && ref.y != kWideEmpty;
-            const bool h2 = wide_box(lox.z, loy.z, loz.z, hix.z, hiy.z, hiz.z, ray, t2) && !(t2 > T) && ref.z != kWideEmpty;
-            const bool h3 = wide_box(lox.w, loy.w, loz.w, hix.w, hiy.w, hiz.w, ray, t3) && !(t3 > T) && ref.w != kWideEmpty;
-            const uint32_t hit = (h0 ? 1u : 0u) | (h1 ? 2u : 0u) | (h2 ? 4u : 0u) | (h3 ? 8u : 0u);
-            const uint32_t leaf = (ref.x >> 31) | ((ref.y >> 31) << 1) | ((ref.z >> 31) << 2) | ((ref.w >> 31) << 3);
-            uint32_t leaves = hit & leaf, inner = hit & ~leaf;
-            while (leaves != 0u) {
-                const uint32_t k = (uint32_t)__builtin_ctz(leaves);
-                leaves &= leaves - 1u;
-                if (STATS) n_tris++;
-                float4 v0, v1, v2;
-                unpack_fast_triangle(reinterpret_cast<const float4*>(&lines[pick4(ref, k) & 0x7FFFFFFFu]), v0, v1, v2);
-                float u = 0.0f, v = 0.0f;
-                const float dist = ray_fast_triangle(ray, v0, v1, v2, u, v);
-                const float entry = k == 0u ? t0 : (k == 1u ? t1 : (k == 2u ? t2 : t3));
-                if (dist > lo && hit_counts(dist, entry) && dist < T) {
-                    if constexpr (FILL) {
-                        if (pos < capacity) reinterpret_cast<float4*>(hits)[pos] = make_float4(dist, v0.w, u, v);   // never at or beyond the capacity
-                        pos++;
-                    } else {
-                        n_found++;
-                    }
-                }
-            }
-            if (inner != 0u) {
-                node = pick4(ref, (uint32_t)__builtin_ctz(inner));
-                inner &= inner - 1u;
-                while (inner != 0u) {
-                    push(pick4(ref, (uint32_t)__builtin_ctz(inner)));
-                    inner &= inner - 1u;
-                }
-            } else if (sp != 0) {
-                sp--;
-                node = sp < lds_depth ? s_stack[sp][lane] : my_deep[(sp - lds_depth) * LBVH_WAVE];
-            } else {
-                if constexpr (!FILL) counts[i] = n_found;
-                active = false;
-            }
-        }
-    }
-    if (STATS) add_ray_stats(stats, n_rays, n_steps, n_tris);
 }
 
 // ---- every contact of a sweep as a CSR list (lbvh_sphere_cast_all / lbvh_capsule_cast_all / lbvh_box_cast_all, include/lbvh.h) --
@@ -4785,121 +4284,6 @@ __global__ __launch_bounds__(64) void plane_task_wide_kernel(const float4* __res
     if (STATS) add_ray_stats(stats, n_queries, n_steps, n_tris);
 }
 
-// ---- crossing parities of points along fixed directions (lbvh_point_crossings, include/lbvh.h) -------------------------
-// The directions travel by value in the kernel's arguments; a lane reads the one it walks next from there.
-struct crossing_dirs { float d[LBVH_CROSSING_MAX_DIRS][3]; };
-
-// One POINT per lane over the four-wide nodes, in the frame of trace_rays_wide_kernel<PLAIN> (persistent waves, lanes refilled
-// from the wave's run of consecutive points, LDS + device-memory stack).  The lane walks the rays {p, t_min = 0, dirs[j],
-// T = LBVH_MAX_FLOAT} for j = 0 .. n_dirs - 1 one after the other: the count walk of the ray walkers (best_t stays T, every
-// candidate adds one, the walk ends with an empty stack), each finished count's lowest bit kept in a register and the point's
-// word stored once, after its last direction.  No ray is written to memory.  The children to enter are taken in slot order: a
-// count does not depend on the order, and at most three siblings wait per level as in the other walks.
-// amdgpu_waves_per_eu(8): without it the lane-indexed direction and the point / direction / parity registers took 66 VGPRs
-// (7 waves per SIMD) and the walk was slower than lbvh_count_hits on the same rays written out
-template <bool STATS>
-__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(8, 8))) void point_crossings_wide_kernel(const lbvh_point_query* __restrict__ points, uint32_t total,
-                                                                  const crossing_dirs dirs, uint32_t n_dirs,
-                                                                  const lbvh_wide_node* __restrict__ wide,
-                                                                  const lbvh_fast_node* __restrict__ lines, uint32_t* __restrict__ parity,
-                                                                  uint32_t* __restrict__ deep,     // [gridDim.x][kWideStackDeep][64]
-                                                                  uint32_t lds_depth,              // <= kWideStackLds
-                                                                  uint32_t deep_cap,               // <= kWideStackDeep
-                                                                  uint32_t* __restrict__ fault, lbvh_ray_stats* stats)
-{
-    __shared__ uint32_t s_stack[kWideStackLds][LBVH_WAVE];
-    uint32_t* my_deep = deep + (size_t)blockIdx.x * (kWideStackDeep * LBVH_WAVE) + threadIdx.x;
-    const uint32_t lane = threadIdx.x;
-    const uint32_t run = max((total + gridDim.x - 1) / gridDim.x, 32u);
-    uint32_t next = blockIdx.x * run;
-    if (next >= total) return;
-    const uint32_t end = min(next + run, total);
-    uint32_t n_rays = 0, n_steps = 0, n_tris = 0;
-
-    bool active = false;
-    uint32_t i = 0, j = 0, bits = 0, n_hit = 0;          // point, direction, parities so far, candidates of direction j so far
-    ray_t ray = {};
-    uint32_t sp = 0, node = 0;
-    auto push = [&](uint32_t ref) {
-        if (sp < lds_depth) { s_stack[sp][lane] = ref; sp++; }
-        else if (sp < lds_depth + deep_cap) { my_deep[(sp - lds_depth) * LBVH_WAVE] = ref; sp++; }
-        // a dropped entry would be a silently wrong count: report it, as the ray walkers do (lbvh_debug_ray_stack_limit provokes it)
-        else __hip_atomic_store(fault, LBVH_FAULT_RAY_STACK, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-    };
-    auto aim = [&](uint32_t jj) {                        // direction jj from the lane's point: a fresh walk
-        ray.dx = dirs.d[jj][0]; ray.dy = dirs.d[jj][1]; ray.dz = dirs.d[jj][2];
-        ray.ix = 1.0f / ray.dx; ray.iy = 1.0f / ray.dy; ray.iz = 1.0f / ray.dz;
-        sp = 0; node = 0; n_hit = 0;
-        if (STATS) n_rays++;
-    };
-    for (;;) {
-        const uint64_t idle = __ballot(!active);
-        if (idle != 0 && next < end) {
-            if (!active) {
-                const uint32_t k = next + mbcnt64(idle);
-                if (k < end) {
-                    i = k;
-                    const float4 p = reinterpret_cast<const float4*>(points)[k];     // max_dist2 (.w) is not read
-                    ray.ox = p.x; ray.oy = p.y; ray.oz = p.z;
-                    j = 0; bits = 0;
-                    aim(0u);
-                    active = true;
-                }
-            }
-            next += (uint32_t)__popcll(idle);
-        }
-        if (!__any(active) && next >= end) break;
-        if (active) {
-            if (STATS) n_steps++;
-            const float4* w = reinterpret_cast<const float4*>(&wide[node]);
-            const float4 lox = w[0], loy = w[1], loz = w[2], hix = w[3], hiy = w[4], hiz = w[5];
-            const uint4 ref = reinterpret_cast<const uint4*>(w)[6];
-            float t0, t1, t2, t3;
-            // T = min(+inf, LBVH_MAX_FLOAT): a box entered beyond it holds no candidate
-            const bool h0 = wide_box(lox.x, loy.x, loz.x, hix.x, hiy.x, hiz.x, ray, t0) && !(t0 > LBVH_MAX_FLOAT) && ref.x != kWideEmpty;
-            const bool h1 = wide_box(lox.y, loy.y, loz.y, hix.y, hiy.y, hiz.y, ray, t1) && !(t1 > LBVH_MAX_FLOAT) && ref.y != kWideEmpty;
-            const bool h2 = wide_box(lox.z, loy.z, loz.z, hix.z, hiy.z, hiz.z, ray, t2) && !(t2 > LBVH_MAX_FLOAT) && ref.z != kWideEmpty;
-            const bool h3 = wide_box(lox.w, loy.w, loz.w, hix.w, hiy.w, hiz.w, ray, t3) && !(t3 > LBVH_MAX_FLOAT) && ref.w != kWideEmpty;
-            uint32_t leaves = (h0 && (ref.x >> 31) ? 1u : 0u) | (h1 && (ref.y >> 31) ? 2u : 0u) | (h2 && (ref.z >> 31) ? 4u : 0u) |
-                              (h3 && (ref.w >> 31) ? 8u : 0u);
-            while (leaves != 0u) {
-                const uint32_t k = (uint32_t)__builtin_ctz(leaves);
-                leaves &= leaves - 1u;
-                if (STATS) n_tris++;
-                float4 v0, v1, v2;
-                unpack_fast_triangle(reinterpret_cast<const float4*>(&lines[pick4(ref, k) & 0x7FFFFFFFu]), v0, v1, v2);
-                float u = 0.0f, v = 0.0f;
-                const float dist = ray_fast_triangle(ray, v0, v1, v2, u, v);
-                const float entry = k == 0u ? t0 : (k == 1u ? t1 : (k == 2u ? t2 : t3));
-                if (dist > 0.0f && hit_counts(dist, entry) && dist < LBVH_MAX_FLOAT) n_hit++;
-            }
-            // nodes to enter, in slot order: the first is walked next, the others wait
-            constexpr uint32_t none = 0xFFFFFFFFu;
-            uint32_t go = none;
-            if (h0 && !(ref.x >> 31)) go = ref.x;
-            if (h1 && !(ref.y >> 31)) { if (go != none) push(go); go = ref.y; }
-            if (h2 && !(ref.z >> 31)) { if (go != none) push(go); go = ref.z; }
-            if (h3 && !(ref.w >> 31)) { if (go != none) push(go); go = ref.w; }
-            if (go != none) {
-                node = go;
-            } else if (sp != 0) {
-                sp--;
-                node = sp < lds_depth ? s_stack[sp][lane] : my_deep[(sp - lds_depth) * LBVH_WAVE];
-            } else {
-                bits |= (n_hit & 1u) << j;
-                j++;
-                if (j < n_dirs) {
-                    aim(j);
-                } else {
-                    parity[i] = bits;
-                    active = false;
-                }
-            }
-        }
-    }
-    if (STATS) add_ray_stats(stats, n_rays, n_steps, n_tris);
-}
-
 // ---- bounce ----------------------------------------------------------------------------------------------
 __device__ __forceinline__ uint32_t pcg_hash(uint32_t v)
 {
@@ -5066,60 +4450,6 @@ __global__ __launch_bounds__(256) void path_resolve_kernel(const lbvh_path_state
 
 static_assert(sizeof(lbvh_path_state) == 64, "path state must be 64 bytes");
 
-// what the launch of a per-lane walk takes from the context: filled by begin_walk, the last three by use_wide_nodes
-struct walk_launch {
-    uint32_t waves = 0;                     // the grid: one wave per workgroup, one deep stack slab per wave
-    uint32_t* deep = nullptr;               // the deep stack slabs
-    uint32_t lds = 0, deep_cap = 0;         // a lane's stack entries in LDS / in its wave's slab, as the four-wide walkers take them
-    const lbvh_wide_node* wn = nullptr;
-};
-
-// the four-wide form of the derived tree, made on first use after a rebuild and shared by the ray and the point walkers, and the
-// stack split clamped to what those walkers have room for
-static lbvh_status use_wide_nodes(lbvh_context* ctx, walk_launch* w)
-{
-    if (!ctx->wide_valid) {
-        const uint32_t n_internal = ctx->fast_src.n - 1;
-        const int rc = lbvh_reserve(ctx, &ctx->wide_nodes, &ctx->wide_nodes_bytes, (size_t)n_internal * sizeof(lbvh_wide_node));
-        if (rc != LBVH_OK) return (lbvh_status)rc;
-        LBVH_LAUNCH(ctx, collapse_wide_kernel, dim3((n_internal + 255) / 256), dim3(256), ctx->fast_nodes, n_internal,
-                    (lbvh_wide_node*)ctx->wide_nodes);
-        ctx->wide_valid = true;
-    }
-    w->lds = std::min<uint32_t>(ctx->ray_stack_lds, kWideStackLds);
-    w->deep_cap = std::min<uint32_t>(ctx->ray_stack_deep, kWideStackDeep);
-    w->wn = (const lbvh_wide_node*)ctx->wide_nodes;
-    return LBVH_OK;
-}
-
-// The prologue of every entry point that walks the derived scene one ray or query per lane, after the entry point's own argument
-// checks: h_scene must be what the derived scene was built from (`who`: the entry point's name in the message), the ray scratch
-// holds `count` lanes' worth, and `w` is what the launches take.
-// The scratch is laid out as for lbvh_trace_rays whatever the caller, [two live-ray counters (256 B) | live-ray list 0 | live-ray
-// list 1 | deep stack slabs of the launch's waves] (ray_scratch_bytes_for): the queries over plain rays, points and spheres use
-// the slabs only (the overlap queries also the lists' space), so the live-path list a bounce may have left there is dropped —
-// except for keep_list (lbvh_path_bounce, which goes on from that list) while the scratch stays where it was.
-// wide: the four-wide walk is the only one the caller has.  launch_ray_walk's callers pass false: it asks for the wide nodes itself,
-// after their own launches, where its walker switch takes that walk.
-static lbvh_status begin_walk(lbvh_context* ctx, const lbvh_scene* h_scene, size_t count, const char* who, bool wide, walk_launch* w,
-                              bool keep_list = false)
-{
-    {
-        const int frc = lbvh_require_fast(ctx, *h_scene, who);
-        if (frc != LBVH_OK) return frc;
-    }
-    LBVH_HIP_TRY(ctx, hipSetDevice(ctx->device));
-    void* before = ctx->ray_scratch;
-    const int rc = lbvh_reserve(ctx, &ctx->ray_scratch, &ctx->ray_scratch_bytes, ray_scratch_bytes_for(count));
-    if (rc != LBVH_OK) return rc;
-    if (!keep_list || ctx->ray_scratch != before) ctx->ray_list.valid = false;
-    // (lbvh_debug_ray_waves can only lower the grid: the slabs stay sized by ray_waves_of(count), one per launched wave and more)
-    w->waves = ray_waves_of(count);
-    if (ctx->ray_max_waves != 0u) w->waves = std::min(w->waves, ctx->ray_max_waves);
-    w->deep = deep_stacks(ctx, count);
-    return wide ? use_wide_nodes(ctx, w) : LBVH_OK;
-}
-
 // the walk over the live rays of `list` (or over plain rays, PLAIN: `total` is their count): four-wide nodes (made on first use
 // after a rebuild) — few_rays: with the kernel that keeps two fetches of a step in flight (the later bounces of a frame) —, or the
 // binary nodes the packet walk uses (lbvh_debug_ray_walker(ctx, 0): the cross-check of the tests; 2: the few-rays kernel for every launch)
@@ -5161,37 +4491,6 @@ static lbvh_status trace_plain_rays(lbvh_context* ctx, const lbvh_ray* d_rays, s
     return launch_ray_walk<true, Q>(ctx, d_rays, (uint32_t)count, nullptr, 0.0f, d_out, w);
 }
 
-// One record or flag per query, after the entry family's own argument checks: begin_walk, the one launch of the four-wide walk
-// (lbvh_debug_ray_walker does not apply), hipGetLastError.  The four walkers take the same arguments; the record type picks one.
-template <bool ANY, class QUERY, class OUT>
-static lbvh_status launch_per_query(lbvh_context* ctx, const QUERY* d_queries, size_t count, const lbvh_scene* h_scene, OUT* d_out, const char* who)
-{
-    walk_launch w;
-    const lbvh_status rc = begin_walk(ctx, h_scene, count, who, true, &w);
-    if (rc != LBVH_OK) return rc;
-#define PER_QUERY_WALK(kernel)                                                                                                     \
-    LBVH_LAUNCH_STATS(ctx, ctx->ray_stats, (kernel<ANY, STATS>), dim3(w.waves), dim3(LBVH_WAVE), d_queries, (uint32_t)count, w.wn, \
-                      ctx->fast_nodes, d_out, w.deep, w.lds, w.deep_cap, ctx->fault_dev, ctx->ray_stats)
-    if constexpr (std::is_same_v<QUERY, lbvh_point_query>) PER_QUERY_WALK(point_query_wide_kernel);
-    else if constexpr (std::is_same_v<QUERY, lbvh_segment_query>) PER_QUERY_WALK(segment_query_wide_kernel);
-    else if constexpr (std::is_same_v<QUERY, lbvh_tri_distance_query>) PER_QUERY_WALK(triangle_distance_wide_kernel);
-    else if constexpr (std::is_same_v<QUERY, lbvh_sphere_ray>) PER_QUERY_WALK(sphere_cast_wide_kernel);
-    else if constexpr (std::is_same_v<QUERY, lbvh_capsule_ray>) PER_QUERY_WALK(capsule_cast_wide_kernel);
-    else if constexpr (std::is_same_v<QUERY, lbvh_capsule>)          // lbvh_capsule_deepest: the contact walk's one-record form
-        LBVH_LAUNCH_STATS(ctx, ctx->ray_stats, (capsule_contact_wide_kernel<kContactDeepest, STATS>), dim3(w.waves), dim3(LBVH_WAVE), d_queries,
-                          (uint32_t)count, w.wn, ctx->fast_nodes, (const uint64_t*)nullptr, d_out, (uint64_t)0, w.deep, w.lds, w.deep_cap,
-                          ctx->fault_dev, ctx->ray_stats);
-    else if constexpr (std::is_same_v<QUERY, lbvh_obb>)              // lbvh_obb_deepest: the same of the box contact walk
-        LBVH_LAUNCH_STATS(ctx, ctx->ray_stats, (box_contact_wide_kernel<kContactDeepest, STATS>), dim3(w.waves), dim3(LBVH_WAVE), d_queries,
-                          (uint32_t)count, w.wn, ctx->fast_nodes, (const uint64_t*)nullptr, d_out, (uint64_t)0, w.deep, w.lds, w.deep_cap,
-                          ctx->fault_dev, ctx->ray_stats);
-    else if constexpr (std::is_same_v<QUERY, lbvh_tri_ray>) PER_QUERY_WALK(triangle_cast_wide_kernel);
-    else PER_QUERY_WALK(box_cast_wide_kernel);
-#undef PER_QUERY_WALK
-    LBVH_HIP_TRY(ctx, hipGetLastError());
-    return LBVH_OK;
-}
-
 // lbvh_closest_point_query / lbvh_within_distance
 template <bool ANY>
 static lbvh_status point_queries(lbvh_context* ctx, const lbvh_point_query* d_queries, size_t count, const lbvh_scene* h_scene,
@@ -5202,7 +4501,12 @@ static lbvh_status point_queries(lbvh_context* ctx, const lbvh_point_query* d_qu
     LBVH_REQUIRE(ctx, d_queries != nullptr && h_scene != nullptr && d_out != nullptr);
     LBVH_REQUIRE(ctx, ((uintptr_t)d_queries & 15) == 0 && ((uintptr_t)d_out & (ANY ? 3 : 15)) == 0);
     LBVH_REQUIRE(ctx, count <= 0xFFFFFFFFull);
-    return launch_per_query<ANY>(ctx, d_queries, count, h_scene, d_out, who);
+    walk_launch w;
+    const lbvh_status rc = begin_walk(ctx, h_scene, count, who, true, &w);
+    if (rc != LBVH_OK) return rc;
+    PER_QUERY_WALK(point_query_wide_kernel, d_queries, d_out);
+    LBVH_HIP_TRY(ctx, hipGetLastError());
+    return LBVH_OK;
 }
 
 // lbvh_segment_closest_point / lbvh_segment_within_distance and lbvh_triangle_closest_point / lbvh_triangle_within_distance: the
@@ -5216,15 +4520,14 @@ static lbvh_status distance_queries(lbvh_context* ctx, const QUERY* d_queries, s
     LBVH_REQUIRE(ctx, d_queries != nullptr && h_scene != nullptr && d_out != nullptr);
     LBVH_REQUIRE(ctx, ((uintptr_t)d_queries & 15) == 0 && ((uintptr_t)d_out & (ANY ? 3 : 15)) == 0);
     LBVH_REQUIRE(ctx, count <= 0xFFFFFFFFull);
-    return launch_per_query<ANY>(ctx, d_queries, count, h_scene, d_out, who);
+    walk_launch w;
+    const lbvh_status rc = begin_walk(ctx, h_scene, count, who, true, &w);
+    if (rc != LBVH_OK) return rc;
+    if constexpr (std::is_same_v<QUERY, lbvh_segment_query>) PER_QUERY_WALK(segment_query_wide_kernel, d_queries, d_out);
+    else PER_QUERY_WALK(triangle_distance_wide_kernel, d_queries, d_out);
+    LBVH_HIP_TRY(ctx, hipGetLastError());
+    return LBVH_OK;
 }
-
-// LBVH_REQUIRE with the entry point's name (`who`, a variable of the caller) in front of the message, as the stale-scene message
-// of begin_walk has it: the box casts and the region family
-#define NAMED_REQUIRE(cond)                                                                                         \
-    do {                                                                                                            \
-        if (!(cond)) return (lbvh_status)lbvh_set_error(ctx, LBVH_ERR_INVALID_ARG, who, "invalid argument: " #cond); \
-    } while (0)
 
 // lbvh_sphere_cast / lbvh_sphere_cast_any (CAST = lbvh_sphere_ray), lbvh_capsule_cast / lbvh_capsule_cast_any (lbvh_capsule_ray),
 // lbvh_box_cast / lbvh_box_cast_any (lbvh_box_ray, HIT = lbvh_box_hit), lbvh_triangle_cast / lbvh_triangle_cast_any (lbvh_tri_ray,
@@ -5245,36 +4548,13 @@ static lbvh_status shape_casts(lbvh_context* ctx, const CAST* d_casts, size_t co
     CAST_REQUIRE(((uintptr_t)d_casts & 15) == 0 && ((uintptr_t)d_out & (ANY ? 3 : 15)) == 0);
     CAST_REQUIRE(count <= 0xFFFFFFFFull);
 #undef CAST_REQUIRE
-    return launch_per_query<ANY>(ctx, d_casts, count, h_scene, d_out, who);
-}
-
-// The scan behind every CSR answer: the `slots` 32-bit counts a count walk left in slice 0 of the ray scratch (csr_counts) ->
-// their slots + 1 exclusive 64-bit offsets in d_offsets_out, the grand total last.  The counts (4 bytes per slot) and the tile
-// sums of the scan live where lbvh_trace_rays keeps its two live-ray lists: the ray scratch is sized for 8 bytes per slot there
-// (begin_walk with the same `slots`), and the list is dropped anyway.  The tiles cover slots + 1 offsets, 8 bytes per tile sum:
-// (slots / 1024 + 1) * 8 <= list_bytes(slots) = 4 * slots rounded up to 256, for every slots >= 1.  One tile needs no sums.
-static inline uint32_t* csr_counts(lbvh_context* ctx, size_t slots) { return ray_list(ctx, slots, 0); }
-static void csr_offsets(lbvh_context* ctx, size_t slots, uint64_t* d_offsets_out)
-{
-    const uint32_t total = (uint32_t)slots, n_tiles = total / kScanTile + 1u;
-    const uint32_t* counts = csr_counts(ctx, slots);
-    uint64_t* tile_sums = n_tiles > 1u ? (uint64_t*)ray_list(ctx, slots, 1) : nullptr;
-    if (tile_sums) {
-        LBVH_LAUNCH(ctx, overlap_tile_sums_kernel, dim3(n_tiles), dim3(256), counts, total, tile_sums);
-        LBVH_LAUNCH(ctx, overlap_scan_sums_kernel, dim3(1), dim3(1024), tile_sums, n_tiles);
-    }
-    LBVH_LAUNCH(ctx, overlap_offsets_kernel, dim3(n_tiles), dim3(256), counts, total, (const uint64_t*)tile_sums, d_offsets_out);
-}
-
-// A CSR answer on the caller's buffers, after begin_walk: count_walk(counts) launches the family's walk in its counting form,
-// the scan turns the counts into d_offsets, fill_walk() launches the filling form unless the call only counts.  All on the
-// context's stream, no host wait.
-template <class COUNT_WALK, class FILL_WALK>
-static lbvh_status csr_query(lbvh_context* ctx, size_t count, uint64_t* d_offsets, uint64_t capacity, COUNT_WALK count_walk, FILL_WALK fill_walk)
-{
-    count_walk(csr_counts(ctx, count));
-    csr_offsets(ctx, count, d_offsets);
-    if (capacity != 0) fill_walk();
+    walk_launch w;
+    const lbvh_status rc = begin_walk(ctx, h_scene, count, who, true, &w);
+    if (rc != LBVH_OK) return rc;
+    if constexpr (std::is_same_v<CAST, lbvh_sphere_ray>) PER_QUERY_WALK(sphere_cast_wide_kernel, d_casts, d_out);
+    else if constexpr (std::is_same_v<CAST, lbvh_capsule_ray>) PER_QUERY_WALK(capsule_cast_wide_kernel, d_casts, d_out);
+    else if constexpr (std::is_same_v<CAST, lbvh_box_ray>) PER_QUERY_WALK(box_cast_wide_kernel, d_casts, d_out);
+    else PER_QUERY_WALK(triangle_cast_wide_kernel, d_casts, d_out);
     LBVH_HIP_TRY(ctx, hipGetLastError());
     return LBVH_OK;
 }
@@ -5470,7 +4750,7 @@ static lbvh_status triangle_cast_gathers(lbvh_context* ctx, const lbvh_tri_ray* 
 }
 
 // lbvh_capsule_contacts: shape_overlaps<kShapeCapsule, false> with a record in place of an index — the count walk is that
-// function's, the fill walk forms the contacts.  lbvh_capsule_deepest: one record per shape through launch_per_query.
+// function's, the fill walk forms the contacts.  lbvh_capsule_deepest: the contact walk's one-record form, one launch.
 static lbvh_status capsule_contacts(lbvh_context* ctx, const lbvh_capsule* d_shapes, size_t count, const lbvh_scene* h_scene, uint64_t* d_offsets,
                                     lbvh_contact* d_contacts, uint64_t capacity, const char* who)
 {
@@ -5535,11 +4815,18 @@ static lbvh_status capsule_deepest(lbvh_context* ctx, const lbvh_capsule* d_shap
     NAMED_REQUIRE(d_shapes != nullptr && h_scene != nullptr && d_out != nullptr);
     NAMED_REQUIRE(((uintptr_t)d_shapes & 15) == 0 && ((uintptr_t)d_out & 15) == 0);
     NAMED_REQUIRE(count <= 0xFFFFFFFFull);
-    return launch_per_query<false>(ctx, d_shapes, count, h_scene, d_out, who);
+    walk_launch w;
+    const lbvh_status rc = begin_walk(ctx, h_scene, count, who, true, &w);
+    if (rc != LBVH_OK) return rc;
+    LBVH_LAUNCH_STATS(ctx, ctx->ray_stats, (capsule_contact_wide_kernel<kContactDeepest, STATS>), dim3(w.waves), dim3(LBVH_WAVE), d_shapes,
+                      (uint32_t)count, w.wn, ctx->fast_nodes, (const uint64_t*)nullptr, d_out, (uint64_t)0, w.deep, w.lds, w.deep_cap,
+                      ctx->fault_dev, ctx->ray_stats);
+    LBVH_HIP_TRY(ctx, hipGetLastError());
+    return LBVH_OK;
 }
 
 // lbvh_obb_contacts / lbvh_obb_deepest: capsule_contacts / capsule_deepest for the box — the count walk is
-// shape_overlaps<kShapeObb, false>'s, the fill walk forms the contacts; one record per shape through launch_per_query.
+// shape_overlaps<kShapeObb, false>'s, the fill walk forms the contacts; one record per shape from the contact walk's one-record form.
 static lbvh_status obb_contacts(lbvh_context* ctx, const lbvh_obb* d_shapes, size_t count, const lbvh_scene* h_scene, uint64_t* d_offsets,
                                 lbvh_box_contact* d_contacts, uint64_t capacity, const char* who)
 {
@@ -5575,7 +4862,14 @@ static lbvh_status obb_deepest(lbvh_context* ctx, const lbvh_obb* d_shapes, size
     NAMED_REQUIRE(d_shapes != nullptr && h_scene != nullptr && d_out != nullptr);
     NAMED_REQUIRE(((uintptr_t)d_shapes & 15) == 0 && ((uintptr_t)d_out & 15) == 0);
     NAMED_REQUIRE(count <= 0xFFFFFFFFull);
-    return launch_per_query<false>(ctx, d_shapes, count, h_scene, d_out, who);
+    walk_launch w;
+    const lbvh_status rc = begin_walk(ctx, h_scene, count, who, true, &w);
+    if (rc != LBVH_OK) return rc;
+    LBVH_LAUNCH_STATS(ctx, ctx->ray_stats, (box_contact_wide_kernel<kContactDeepest, STATS>), dim3(w.waves), dim3(LBVH_WAVE), d_shapes,
+                      (uint32_t)count, w.wn, ctx->fast_nodes, (const uint64_t*)nullptr, d_out, (uint64_t)0, w.deep, w.lds, w.deep_cap,
+                      ctx->fault_dev, ctx->ray_stats);
+    LBVH_HIP_TRY(ctx, hipGetLastError());
+    return LBVH_OK;
 }
 
 // lbvh_region_overlaps: a CSR answer; lbvh_region_overlaps_any: one launch, the flags are the walk's own output.  Four-wide walk only.
@@ -5710,7 +5004,6 @@ static lbvh_status plane_sections(lbvh_context* ctx, const lbvh_plane* d_planes,
     LBVH_HIP_TRY(ctx, hipGetLastError());
     return LBVH_OK;
 }
-#undef NAMED_REQUIRE
 
 extern "C" {
 
@@ -5814,26 +5107,6 @@ lbvh_status lbvh_obb_overlaps_any(lbvh_context* ctx, const lbvh_obb* d_shapes, s
     return shape_overlaps<kShapeObb, true>(ctx, d_shapes, count, h_scene, nullptr, nullptr, 0, d_flags, "lbvh_obb_overlaps_any");
 }
 
-// the four-wide walk only (lbvh_debug_ray_walker does not apply), one launch; the per-lane lists are dynamic LDS sized from k
-lbvh_status lbvh_trace_k_closest(lbvh_context* ctx, const lbvh_ray* d_rays, size_t count, uint32_t k, const lbvh_scene* h_scene,
-                                 lbvh_hit* d_hits, uint32_t* d_found)
-{
-    if (!ctx) return LBVH_ERR_INVALID_ARG;
-    if (count == 0) return LBVH_OK;
-    LBVH_REQUIRE(ctx, d_rays != nullptr && h_scene != nullptr && d_hits != nullptr);
-    LBVH_REQUIRE(ctx, k >= 1u && k <= (uint32_t)LBVH_K_CLOSEST_MAX);
-    LBVH_REQUIRE(ctx, ((uintptr_t)d_rays & 15) == 0 && ((uintptr_t)d_hits & 15) == 0 && ((uintptr_t)d_found & 3) == 0);
-    LBVH_REQUIRE(ctx, count <= 0xFFFFFFFFull);
-    walk_launch w;
-    const lbvh_status rc = begin_walk(ctx, h_scene, count, "lbvh_trace_k_closest", true, &w);
-    if (rc != LBVH_OK) return rc;
-    const size_t list_lds = (size_t)3 * k * LBVH_WAVE * sizeof(uint32_t);       // 768 bytes per slot: 24 KiB at k = 32
-    LBVH_LAUNCH_STATS_SHMEM(ctx, ctx->ray_stats, k_hits_wide_kernel<STATS>, dim3(w.waves), dim3(LBVH_WAVE), list_lds, d_rays, (uint32_t)count, k,
-                            w.wn, ctx->fast_nodes, d_hits, d_found, w.deep, w.lds, w.deep_cap, ctx->fault_dev, ctx->ray_stats);
-    LBVH_HIP_TRY(ctx, hipGetLastError());
-    return LBVH_OK;
-}
-
 lbvh_status lbvh_sphere_cast(lbvh_context* ctx, const lbvh_sphere_ray* d_casts, size_t count, const lbvh_scene* h_scene, lbvh_hit* d_hits)
 {
     return shape_casts<false>(ctx, d_casts, count, h_scene, d_hits, "lbvh_sphere_cast");
@@ -5872,32 +5145,6 @@ lbvh_status lbvh_triangle_cast(lbvh_context* ctx, const lbvh_tri_ray* d_casts, s
 lbvh_status lbvh_triangle_cast_any(lbvh_context* ctx, const lbvh_tri_ray* d_casts, size_t count, const lbvh_scene* h_scene, uint32_t* d_flags)
 {
     return shape_casts<true, lbvh_tri_ray, lbvh_tri_cast_hit>(ctx, d_casts, count, h_scene, d_flags, "lbvh_triangle_cast_any");
-}
-
-// the four-wide walk only (lbvh_debug_ray_walker does not apply), the directions by value in the arguments
-lbvh_status lbvh_point_crossings(lbvh_context* ctx, const lbvh_point_query* d_points, size_t count, const float* h_dirs, uint32_t n_dirs,
-                                 const lbvh_scene* h_scene, uint32_t* d_parity)
-{
-    if (!ctx) return LBVH_ERR_INVALID_ARG;
-    if (count == 0) return LBVH_OK;
-    LBVH_REQUIRE(ctx, d_points != nullptr && h_dirs != nullptr && h_scene != nullptr && d_parity != nullptr);
-    LBVH_REQUIRE(ctx, ((uintptr_t)d_points & 15) == 0 && ((uintptr_t)d_parity & 3) == 0);
-    LBVH_REQUIRE(ctx, count <= 0xFFFFFFFFull);
-    LBVH_REQUIRE(ctx, n_dirs >= 1u && n_dirs <= (uint32_t)LBVH_CROSSING_MAX_DIRS);
-    crossing_dirs dirs = {};
-    for (uint32_t j = 0; j < n_dirs; j++) {
-        const float x = h_dirs[3 * j], y = h_dirs[3 * j + 1], z = h_dirs[3 * j + 2];
-        LBVH_REQUIRE(ctx, std::isfinite(x) && std::isfinite(y) && std::isfinite(z));
-        LBVH_REQUIRE(ctx, x != 0.0f || y != 0.0f || z != 0.0f);
-        dirs.d[j][0] = x; dirs.d[j][1] = y; dirs.d[j][2] = z;
-    }
-    walk_launch w;
-    const lbvh_status rc = begin_walk(ctx, h_scene, count, "lbvh_point_crossings", true, &w);
-    if (rc != LBVH_OK) return rc;
-    LBVH_LAUNCH_STATS(ctx, ctx->ray_stats, point_crossings_wide_kernel<STATS>, dim3(w.waves), dim3(LBVH_WAVE), d_points, (uint32_t)count, dirs,
-                      n_dirs, w.wn, ctx->fast_nodes, d_parity, w.deep, w.lds, w.deep_cap, ctx->fault_dev, ctx->ray_stats);
-    LBVH_HIP_TRY(ctx, hipGetLastError());
-    return LBVH_OK;
 }
 
 lbvh_status lbvh_closest_point_query(lbvh_context* ctx, const lbvh_point_query* d_queries, size_t count, const lbvh_scene* h_scene,
@@ -5973,32 +5220,6 @@ lbvh_status lbvh_gather_within_distance(lbvh_context* ctx, const lbvh_point_quer
                                         uint64_t* d_offsets, uint32_t* d_tris, uint64_t capacity)
 {
     return overlap_queries<false>(ctx, d_queries, count, h_scene, d_offsets, d_tris, capacity, "lbvh_gather_within_distance");
-}
-
-// a CSR answer of hit records.  Four-wide walk only.
-lbvh_status lbvh_gather_hits(lbvh_context* ctx, const lbvh_ray* d_rays, size_t count, const lbvh_scene* h_scene, uint64_t* d_offsets,
-                             lbvh_hit* d_hits, uint64_t capacity)
-{
-    if (!ctx) return LBVH_ERR_INVALID_ARG;
-    if (count == 0) return LBVH_OK;
-    LBVH_REQUIRE(ctx, d_rays != nullptr && h_scene != nullptr && d_offsets != nullptr);
-    LBVH_REQUIRE(ctx, d_hits != nullptr || capacity == 0);
-    LBVH_REQUIRE(ctx, ((uintptr_t)d_rays & 15) == 0 && ((uintptr_t)d_offsets & 7) == 0 && ((uintptr_t)d_hits & 15) == 0);
-    LBVH_REQUIRE(ctx, count <= 0xFFFFFFFFull);
-    walk_launch w;
-    const lbvh_status rc = begin_walk(ctx, h_scene, count, "lbvh_gather_hits", true, &w);
-    if (rc != LBVH_OK) return rc;
-    const uint32_t total = (uint32_t)count;
-    return csr_query(
-        ctx, count, d_offsets, capacity,
-        [&](uint32_t* counts) {
-            LBVH_LAUNCH_STATS(ctx, ctx->ray_stats, (gather_hits_wide_kernel<false, STATS>), dim3(w.waves), dim3(LBVH_WAVE), d_rays, total, w.wn, ctx->fast_nodes,
-                              counts, (const uint64_t*)nullptr, (lbvh_hit*)nullptr, (uint64_t)0, w.deep, w.lds, w.deep_cap, ctx->fault_dev, ctx->ray_stats);
-        },
-        [&] {
-            LBVH_LAUNCH_STATS(ctx, ctx->ray_stats, (gather_hits_wide_kernel<true, STATS>), dim3(w.waves), dim3(LBVH_WAVE), d_rays, total, w.wn, ctx->fast_nodes,
-                              (uint32_t*)nullptr, (const uint64_t*)d_offsets, d_hits, capacity, w.deep, w.lds, w.deep_cap, ctx->fault_dev, ctx->ray_stats);
-        });
 }
 
 lbvh_status lbvh_sphere_cast_all(lbvh_context* ctx, const lbvh_sphere_ray* d_casts, size_t count, const lbvh_scene* h_scene,
@@ -6086,45 +5307,6 @@ lbvh_status lbvh_trace_occluded(lbvh_context* ctx, const lbvh_ray* d_rays, size_
 lbvh_status lbvh_count_hits(lbvh_context* ctx, const lbvh_ray* d_rays, size_t count, const lbvh_scene* h_scene, uint32_t* d_counts)
 {
     return trace_plain_rays<kCount>(ctx, d_rays, count, h_scene, d_counts, "lbvh_count_hits");
-}
-
-lbvh_status lbvh_debug_ray_walker(lbvh_context* ctx, uint32_t walker)
-{
-    if (!ctx) return LBVH_ERR_INVALID_ARG;
-    LBVH_REQUIRE(ctx, walker <= 2u);
-    ctx->ray_walker = walker;
-    return LBVH_OK;
-}
-
-lbvh_status lbvh_debug_ray_stack_split(lbvh_context* ctx, uint32_t lds_entries)
-{
-    if (!ctx) return LBVH_ERR_INVALID_ARG;
-    LBVH_REQUIRE(ctx, lds_entries >= 1 && lds_entries <= (uint32_t)kRayStackLds);
-    ctx->ray_stack_lds = lds_entries;
-    return LBVH_OK;
-}
-
-lbvh_status lbvh_debug_ray_waves(lbvh_context* ctx, uint32_t max_waves)
-{
-    if (!ctx) return LBVH_ERR_INVALID_ARG;
-    LBVH_REQUIRE(ctx, max_waves <= kRayWaves);
-    ctx->ray_max_waves = max_waves;
-    return LBVH_OK;
-}
-
-lbvh_status lbvh_ray_stats_target(lbvh_context* ctx, lbvh_ray_stats* d_stats)
-{
-    if (!ctx) return LBVH_ERR_INVALID_ARG;
-    LBVH_REQUIRE(ctx, ((uintptr_t)d_stats & 7) == 0);
-    ctx->ray_stats = d_stats;
-    return LBVH_OK;
-}
-
-lbvh_status lbvh_debug_ray_stack_limit(lbvh_context* ctx, uint32_t deep_entries)
-{
-    if (!ctx) return LBVH_ERR_INVALID_ARG;
-    ctx->ray_stack_deep = deep_entries == 0u ? 0xFFFFFFFFu : deep_entries;       // the kernels clamp it to their slab's size
-    return LBVH_OK;
 }
 
 lbvh_status lbvh_path_scatter(lbvh_context* ctx, const lbvh_scene* h_scene, const lbvh_hit* d_hits, size_t count,

@@ -1,5 +1,5 @@
 // lbvh_rt.h — ray generation and the reference's intersection arithmetic, shared by the traversal
-// kernels (lbvh_trace.hip, lbvh_path.hip).  Strict fp32 in the reference's operation order
+// kernels (lbvh_trace.hip, lbvh_path.hip, lbvh_query_*.hip).  Strict fp32 in the reference's operation order
 // (Assets/_Shaders/Raytracing/Raytracing.compute:37-87, 108-126); the library is built with
 // -ffp-contract=off so these round exactly like oracle/lbvh_oracle.c.
 #pragma once

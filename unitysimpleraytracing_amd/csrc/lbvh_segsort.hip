@@ -40,7 +40,7 @@ constexpr uint32_t kBlockRecords = 4096;       // B: records of a block-tier chu
 constexpr uint32_t kBlockThreads = 1024;
 constexpr uint32_t kBlockWaves = kBlockThreads / LBVH_WAVE;
 constexpr uint32_t kRecordChunk = 1024;        // records of a block-tier chunk of 32-byte records: 32 KiB of records + 16 KiB of entries
-constexpr uint32_t kSortWaves = 8192;          // the per-lane walkers' grid (lbvh_path.hip kRayWaves): 32 waves on each of 256 CUs
+constexpr uint32_t kSortWaves = 8192;          // the per-lane walkers' grid (lbvh_walk.h kRayWaves): 32 waves on each of 256 CUs
 constexpr uint32_t kSortBlocks = 512;          // block tier: two workgroups of 1 024 threads per CU
 static_assert((kWaveRecords & (kWaveRecords - 1)) == 0 && kWaveRecords <= (1u << 14) && kWaveRecords % LBVH_WAVE == 0, "tier border");
 static_assert((kBlockRecords & (kBlockRecords - 1)) == 0 && kBlockRecords <= (1u << 14) && kBlockRecords >= kWaveRecords, "tier border");
