@@ -149,7 +149,7 @@ struct lbvh_context {
     void* wide_nodes = nullptr;
     size_t wide_nodes_bytes = 0;
     bool wide_valid = false;
-    // lbvh_region_overlaps_large (lbvh_path.hip): the task array, its twin and the 64-bit task offsets of the last call
+    // lbvh_region_overlaps_large and lbvh_plane_sections (lbvh_query_region.hip): the task array, its twin and the 64-bit task offsets of the last call
     void* region_tasks = nullptr;
     size_t region_tasks_bytes = 0;
     uint32_t region_task_cap = 0;             // lbvh_debug_region_task_cap: tasks per region (0: the host's choice)
