@@ -15,7 +15,8 @@ default stack split and once more with the LDS part of the stack cut to one entr
     lbvh_closest_point_query / lbvh_within_distance                point_reference
     lbvh_k_closest_points, k = 1, 3, 32                            k_closest_reference
     lbvh_gather_within_distance / lbvh_box_overlaps                overlap_reference
-The swept shapes, contacts, triangle, segment and region queries are not covered here."""
+The region family (regions, large regions, plane sections) is held to its brute force on the same scenes in
+tests/test_hostile_regions.py; the swept shapes, the contacts and the triangle and segment families are not covered yet."""
 import numpy as np
 import pytest
 
